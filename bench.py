@@ -12,17 +12,24 @@ HBM before the timed region; every stream has its own private copy of its inputs
 frame store.  The IDR picture and W P pictures are the untimed warm-up, then exactly K P
 pictures per stream are timed.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--dump-outputs DIR] [--full]
   N>1: one rank per GPU, streams sharded across ranks, no data-path collective (weak scaling).  Either the caller starts the
        ranks (python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...: RANK / WORLD_SIZE in the
        environment) or bench.py does: `python bench.py --gpus N` without WORLD_SIZE starts that same command as a child
        process - the parent never touches the GPU - and relays rank 0's JSON line.  A WORLD_SIZE that differs from --gpus
        is an error (exit 2), never a silent one-rank run.
 
-Prints ONE JSON line (rank 0).  Besides the contract's fields: `roofline` (the dominant stage), `kernels` (every stage with
-its own fraction of the HBM roofline), `cpu_baseline` (the real reference decoder on one host core, N=1 only), a
-`golden_check` (the timed output of a golden-seeded stream hashed against the committed reference hash) and `extras`
-(never `value`: config 2, config 3 I+P, the parse- and PCIe-inclusive pipeline, the single-stream drop-in API; N=1 only).
+Every stream keeps at most RESIDENT_PICTURES // S pictures of input resident in HBM (48 at the default 2048 streams).  A run
+longer than that cycles its P pictures over an even window of them: a picture's reference slot is still the one the step
+before wrote, so any --steps fits, but the frames then differ from the reference decoder's (no golden check).
+
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the
+outputs of the last step when --dump-outputs is given (DIR/frame_{y,u,v}.npy, float32, the planes of a fixed seeded sample of
+streams), and the contract's fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+--full adds everything else: `roofline` (the dominant stage), `kernels` (every stage with its own fraction of the HBM
+roofline), `cpu_baseline` (the real reference decoder on one host core, N=1 only), a `golden_check` (the timed output of a
+golden-seeded stream hashed against the committed reference hash), live counters, `extras` (never `value`: config 2, config 3
+I+P, the parse- and PCIe-inclusive pipeline, the single-stream drop-in API; N=1 only) and, N>1, the config-5 fan-out leg.
 """
 import argparse
 import ctypes as C
@@ -40,6 +47,18 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E peak, /opt/skills/guides/MI355X_MI
 MB_W, MB_H = 120, 68
 N_MB = MB_W * MB_H
 DISTINCT = 4                   # distinct synthetic streams per rank; the S streams cycle through private copies of them
+RESIDENT_PICTURES = 2048 * 48  # pictures of parsed input resident per GPU (1.4 MB each: 138 GB), whatever --steps asks for
+
+
+def resident_window(S, T):
+    """(pictures resident per stream, picture index of step t).  Up to RESIDENT_PICTURES // S pictures per stream step t
+    decodes picture t, as every run did before there was a cap; past them the steps cycle over the first even number of P
+    pictures, so that picture and step agree on which of the two frame slots they write."""
+    R = T if S * T <= RESIDENT_PICTURES else max(3, RESIDENT_PICTURES // S)
+    cycle = (R - 1) & ~1
+    return R, (lambda t: t if t < R else 1 + (t - 1) % cycle)
+
+
 def stage_kernels(edge_info_fused):
     """Which kernels a stage's time covers.  Round 4: in batches of P pictures the loop filter's edge-info pass (the boundary
     strengths: 84 B of records and vectors per macroblock in) runs as extra workgroups of the k_intra_sparse launch, where it
@@ -644,6 +663,25 @@ def measured_copy_bandwidth(torch):
     return round(gbps, 1)
 
 
+def dump_streams(S):
+    """The streams whose frames --dump-outputs writes: one of the streams of each of the DISTINCT inputs (stream s decodes
+    input s % DISTINCT), drawn with a fixed seed - the same for every run with the same --streams.  4 x 3.1 M samples as float32
+    = 50 MB."""
+    import numpy as np
+    rng = np.random.default_rng(264)
+    return [int(g + DISTINCT * rng.integers(0, (S - 1 - g) // DISTINCT + 1)) for g in range(min(S, DISTINCT))]
+
+
+def dump_outputs(hip, out_dir, S, slot):
+    """What the last timed step decoded, as a caller of the path receives it (p264hip_read_frame: the coded 1920x1088 luma
+    and 960x544 chroma planes), for the streams of dump_streams(S): DIR/frame_{y,u,v}.npy, float32, shape (streams, rows, columns)."""
+    import numpy as np
+    planes = [hip.read_frame(s, slot) for s in dump_streams(S)]
+    os.makedirs(out_dir, exist_ok=True)
+    for i, name in enumerate(("frame_y", "frame_u", "frame_v")):
+        np.save(os.path.join(out_dir, name + ".npy"), np.stack([p[i] for p in planes]).astype(np.float32))
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves.  This process has not touched the GPU (no
     HIP call, not even torch imported) and never will: the ranks are fresh children of `python -m torch.distributed.run`
@@ -686,6 +724,11 @@ def main():
     # 2048 streams = 8 pictures per CU and launch (round 4: 1024 -> 2048 streams +5 % frames/s, 3072 / 4096 no more; the wavefront
     # kernels balance their bands better with more pictures per workgroup).  26 pictures x 2048 streams of parsed input = 80 GB.
     ap.add_argument("--streams", type=int, default=2048, help="independent 1080p streams per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write the frames the last step decoded (Y, U, V planes of a fixed seeded "
+                    "sample of %d streams, one per distinct input, rank 0) to DIR/frame_y.npy, frame_u.npy, frame_v.npy as float32" % DISTINCT)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything that is not the headline: stage times and rooflines, the golden "
+                    "check against the reference decoder's hashes, the CPU baseline, live counters, extras and (N > 1) the fan-out leg.  The --no-* "
+                    "options below leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the non-metric figures (config 2, config 3 I+P, pipeline, drop-in API)")
     ap.add_argument("--no-live-counters", action="store_true", help="do not run the rocprofv3 --pmc child passes (HBM traffic, vector instructions) behind the timed region")
@@ -695,6 +738,8 @@ def main():
     ap.add_argument("--only-upload-inclusive", action="store_true", help="print extras.upload_inclusive (both formats) and nothing else")
     ap.add_argument("--only-batch-256", action="store_true", help="print extras.batch_256 (the metric's workload at 256 pictures per launch) and nothing else")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.streams < 1:
+        ap.error("--steps and --streams must be at least 1, --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:    # no launcher around us: be the launcher (before anything touches the GPU)
         return launch_ranks(args.gpus, sys.argv[1:])
@@ -728,34 +773,35 @@ def main():
             print(json.dumps({"extras": {"batch_256": small_batch_leg(lib, K=args.steps, Wm=args.warmup)}}), flush=True)
         return
     S, K, Wm = args.streams, args.steps, args.warmup
-    T = 1 + Wm + K                                        # pictures per stream: IDR + warm-up + timed
+    T = 1 + Wm + K                                        # steps per stream: IDR + warm-up + timed
+    R, pic_of = resident_window(S, T)                     # pictures per stream resident in HBM, picture index of a step
     # ---- set-up (untimed): write + parse DISTINCT streams, make every stream's inputs resident ----
     # Stream 0 of every rank is the golden all-P stream (tests/golden/synth_cfg3_1080p_allp.sha256: per-picture hashes of
-    # the REAL reference decoder) as long as it is long enough: its timed output is checked against those hashes below.
-    golden_case = "cfg3_1080p_allp" if T <= 30 else "cfg3_1080p_allp_300"      # (the same stream, 30 / 300 pictures of it)
+    # the REAL reference decoder) as long as it is long enough: with --full its timed output is checked against those hashes below.
+    golden_case = "cfg3_1080p_allp" if R <= 30 else "cfg3_1080p_allp_300"      # (the same stream, 30 / 300 pictures of it)
     golden_hashes = synth_cases.golden(golden_case)[1]
-    use_golden = T <= len(golden_hashes)
+    use_golden = R <= len(golden_hashes)
     synth_extra = os.environ.get("P264AMD_BENCH_SYNTH_EXTRA", "")     # experiments only (e.g. "--mvmax 0"): no golden stream then
     if synth_extra or os.environ.get("P264AMD_BENCH_NO_GOLDEN"):     # timing experiments with deliberately wrong kernels (scratch/)
         use_golden = False
     paths, parsed = [], []
     for g in range(DISTINCT):
-        path = synth_cases.generate(golden_case) if (g == 0 and use_golden) else synth_cases.generate(synth_args(T, 1000 + 16 * rank + g) + (" " + synth_extra if synth_extra else ""))
+        path = synth_cases.generate(golden_case) if (g == 0 and use_golden) else synth_cases.generate(synth_args(R, 1000 + 16 * rank + g) + (" " + synth_extra if synth_extra else ""))
         paths.append(path)
-        pics = Parser(quiet=True, lib=lib).parse_stream(open(path, "rb").read(), limit=T)
-        assert len(pics) == T and all(p.desc.slice_type == 0 for p in pics[1:])
+        pics = Parser(quiet=True, lib=lib).parse_stream(open(path, "rb").read(), limit=R)
+        assert len(pics) == R and all(p.desc.slice_type == 0 for p in pics[1:])
         parsed.append(pics)
-    hip = HipReconstructor(MB_W, MB_H, n_streams=S, slots=2, max_pictures=S * T, device=local_rank, lib=lib)
+    hip = HipReconstructor(MB_W, MB_H, n_streams=S, slots=2, max_pictures=S * R, device=local_rank, lib=lib)
     for s in range(min(S, DISTINCT)):
-        hip.upload(s * T, parsed[s])
+        hip.upload(s * R, parsed[s])
     for s in range(DISTINCT, S):
-        for t in range(T):
-            hip.clone_picture(s * T + t, (s % DISTINCT) * T + t)
+        for t in range(R):
+            hip.clone_picture(s * R + t, (s % DISTINCT) * R + t)
     hip.sync()
     streams = list(range(S))
 
     def step(t):
-        hip.reconstruct([s * T + t for s in streams], streams)
+        hip.reconstruct([s * R + pic_of(t) for s in streams], streams)
 
     for t in range(1 + Wm):                               # IDR + W P pictures
         step(t)
@@ -779,12 +825,12 @@ def main():
     EDGE_INFO_FUSED = launch["edge_info_fused"] > 0
     STAGE_KERNELS = stage_kernels(EDGE_INFO_FUSED)
 
-    # ---- the timed output against the real reference decoder: the last picture of stream 0 and of its last clone must
-    #      hash to what the reference produced for that picture of the golden stream (committed fixture) ----
+    # ---- --full: the timed output against the real reference decoder: the last picture of stream 0 and of its last clone
+    #      must hash to what the reference produced for that picture of the golden stream (committed fixture) ----
     from tests.conftest import frame_sha256
-    last = parsed[0][-1].desc.dst_slot
+    last = parsed[0][pic_of(T - 1)].desc.dst_slot
     golden_check = {"stream": golden_case, "picture": T - 1, "checked": False}
-    if use_golden:
+    if args.full and use_golden and R == T:
         clone = S - 1 - (S - 1) % DISTINCT                  # the last stream that decodes stream 0's pictures
         for s in sorted({0, clone}):
             got = frame_sha256(*hip.read_frame(s, last))
@@ -792,17 +838,33 @@ def main():
                 raise SystemExit("bench.py: stream %d picture %d differs from the reference decoder (%s != %s)" % (s, T - 1, got[:16], golden_hashes[T - 1][:16]))
         golden_check.update(checked=True, streams_checked=sorted({0, clone}), sha256=golden_hashes[T - 1][:16] + "...",
                             source="tests/golden/synth_%s.sha256 (oracle/_ref, the real reference decoder)" % golden_case)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(hip, args.dump_outputs, S, last)
 
-    # what every rank did (N > 1: the streams each rank owns are its own - S per rank, weak scaling - and every rank checks its
-    # own golden stream against the reference's hash)
+    # what every rank did (N > 1: the streams each rank owns are its own - S per rank, weak scaling - and with --full every rank
+    # checks its own golden stream against the reference's hash)
     ranks = shard.gather_objects({"rank": rank, "device": local_rank, "streams": S, "frames": S * K, "golden_checked": golden_check["checked"],
                                   "first_global_stream": rank * S})
-    copy_gbps = measured_copy_bandwidth(torch) if rank == 0 else None
+    copy_gbps = measured_copy_bandwidth(torch) if rank == 0 and args.full else None
     if rank == 0:
         frames = sum(r["frames"] for r in ranks)
         assert frames == S * K * world and len(ranks) == world
         fps = frames / elapsed
-        alg = algorithmic_bytes([parsed[s % DISTINCT][t] for s in streams for t in (T - 1,)], EDGE_INFO_FUSED)   # one representative step
+        out = {
+            "metric": "1080p decoded frames/sec", "value": round(fps, 2), "unit": "frames/s",
+            "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": round(elapsed / K * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int16", "data": "synthetic",
+            "config": {"workload": "BASELINE config 3: 1920x1080 (coded 1920x1088) Baseline CAVLC all-P stream (1 IDR + P), "
+                                   "reconstruction hot path (MC + residual, intra, deblock), parsed inputs resident in HBM",
+                       "streams_per_gpu": S, "pictures_per_step": S * world, "mb_per_picture": N_MB, "parallelism": "stream-parallel x%d" % world,
+                       "pictures_resident_per_stream": R},
+            "macroblocks_per_s": round(fps * N_MB, 0),
+            "ranks": ranks,
+            "launch": launch,
+            "build": {"timing_build": bool(lib.p264hip_build_info() & 1)},
+        }
+    if rank == 0 and args.full:
+        alg = algorithmic_bytes([parsed[s % DISTINCT][pic_of(T - 1)] for s in streams], EDGE_INFO_FUSED)   # one representative step
         kernels = {}
         for name in ("inter", "intra", "deblock"):
             ms, cnt = timing[name]
@@ -856,29 +918,19 @@ def main():
                 if traffic:
                     r["traffic_over_algorithmic_with_residual"] = round(traffic / kernels[stage]["algorithmic_bytes_with_residual"], 3)
             return r
-        out = {
-            "metric": "1080p decoded frames/sec", "value": round(fps, 2), "unit": "frames/s",
-            "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": round(elapsed / K * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int16", "data": "synthetic",
-            "config": {"workload": "BASELINE config 3: 1920x1080 (coded 1920x1088) Baseline CAVLC all-P stream (1 IDR + P), "
-                                   "reconstruction hot path (MC + residual, intra, deblock), parsed inputs resident in HBM",
-                       "streams_per_gpu": S, "pictures_per_step": S * world, "mb_per_picture": N_MB, "parallelism": "stream-parallel x%d" % world},
-            "macroblocks_per_s": round(fps * N_MB, 0),
-            # `roofline` = the stage that takes longest (the contract's "dominant kernel"); `roofline_mc` = the motion-compensation
-            # stage, which the north star names, whichever is longer
-            "roofline": roofline_of(dom),
-            "roofline_mc": roofline_of("inter") if "inter" in kernels else None,
-            "kernels": kernels,
-            "reconstruct_call_ms": round(timing["reconstruct"][0] / max(timing["reconstruct"][1], 1), 4),
-            "golden_check": golden_check,
-            "ranks": ranks,
-            "launch": launch,
-            "build": {"timing_build": bool(lib.p264hip_build_info() & 1)},
-        }
+        # `roofline` = the stage that takes longest (the contract's "dominant kernel"); `roofline_mc` = the motion-compensation
+        # stage, which the north star names, whichever is longer
+        out.update(roofline=roofline_of(dom), roofline_mc=roofline_of("inter") if "inter" in kernels else None, kernels=kernels,
+                   reconstruct_call_ms=round(timing["reconstruct"][0] / max(timing["reconstruct"][1], 1), 4), golden_check=golden_check)
         if not args.no_cpu_baseline and world == 1:          # rank 0 at N=1 only: a reported baseline, not part of the scaling runs
-            out["cpu_baseline"] = cpu_baseline(paths[0], T)
-    hip.close()
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_live_counters:
+            out["cpu_baseline"] = cpu_baseline(paths[0], R)
+    if args.full:
+        hip.close()
+    else:
+        # a plain run has nothing left to do on the device: its context is left to the process exit, which hands the memory back
+        # at once, where p264hip_destroy frees the S x R input copies one hipFree at a time (9 s at 2048 streams x 24 pictures)
+        hip.h = None
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.no_live_counters:
         # counters of this build on this box, in child processes after the timed region (never inside it)
         try:
             live = live_counters(S, EDGE_INFO_FUSED)
@@ -904,10 +956,10 @@ def main():
                                  "source": "live: SQ_INSTS_VALU pass of the same child run, 4 cycles per wave instruction"}
     fan = None
     fan_env = os.environ.get("P264AMD_BENCH_FANOUT", "")
-    if world > 1 and not args.no_fanout and fan_env != "0" and (world == 2 or fan_env == "1"):
+    if world > 1 and args.full and not args.no_fanout and fan_env != "0" and (world == 2 or fan_env == "1"):
         fan = fanout_leg(rank, local_rank, world, lib)       # after the timed region, in child processes, never `value`
     if rank == 0:
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             out["extras"] = extras(lib, None if args.no_cpu_baseline else paths[0])
         if fan is not None:
             out.setdefault("extras", {})["fanout_config5"] = fan

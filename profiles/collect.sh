@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the round's evidence on the GPU box (run through gpurun from the repo root):
 #   gpurun --timeout 1100 -- 'bash profiles/collect.sh r01_final'
-# 1. bench.py (default arguments) -> <tag>_bench.json
+# 1. bench.py --full (default arguments) -> <tag>_bench.json
 # 2. rocprofv3 --kernel-trace --stats of the same command -> <tag>_kernel_stats.csv
 # 3. separate --pmc passes (never combined with traces): HBM traffic and instruction mix -> <tag>_pmc_*.csv
 # Everything lands in gpurun_out/<tag>/; profiles/summarize.py turns it into the committed summaries.
@@ -14,7 +14,7 @@ S=${STREAMS:+--streams $STREAMS}
 BENCH="bench.py --steps 3 --warmup 1 --no-extras $S"
 BENCH_FULL="bench.py $S"
 echo "[collect] bench" | tee $out/progress.log
-python3 bench.py $S ${STREAMS:+--no-extras} > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -5 $out/bench.err; exit 1; }
+python3 bench.py --full $S ${STREAMS:+--no-extras} > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -5 $out/bench.err; exit 1; }
 echo "[collect] kernel trace" | tee -a $out/progress.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $BENCH_FULL --no-cpu-baseline --no-extras > $out/trace.log 2>&1 || { echo "trace failed"; tail -5 $out/trace.log; exit 1; }
 i=0

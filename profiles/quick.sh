@@ -7,7 +7,7 @@ tag=${1:-quick}
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-BENCH="bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-extras"
+BENCH="bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-extras"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $BENCH > $out/trace.log 2>&1 || { echo "trace failed"; tail -5 $out/trace.log; exit 1; }
 python3 - $out <<'PY' | tee $out/stats.txt
 import csv, glob, sys

@@ -79,11 +79,24 @@ def oracle_golden(name):
 BIG = ("cfg2_720p_intra", "cfg3_1080p_ip", "cfg3_1080p_ip_l32", "cfg3_1080p_allp", "cfg3_1080p_allp_300", "qpd_1080p", "uhd_2160p_allp")
 
 
+_tool_sha = {}
+
+
 def ensure_tool():
-    if not os.path.exists(TOOL):
-        from p264decoder_amd import build
-        build.build_tools()
+    """The stream writer, rebuilt when its sources are newer than the binary (build_tools is incremental)."""
+    from p264decoder_amd import build
+    build.build_tools()
     return TOOL
+
+
+def tool_digest():
+    """SHA-1 of the stream writer binary: part of every cache key, so that a stream written by another build of the tool (an
+    older checkout, another tree) is never reused."""
+    st = os.stat(TOOL)
+    key = (st.st_mtime_ns, st.st_size)
+    if _tool_sha.get("key") != key:
+        _tool_sha.update(key=key, sha=hashlib.sha1(open(TOOL, "rb").read()).hexdigest())
+    return _tool_sha["sha"]
 
 
 def generate(name, extra_args=None):
@@ -93,7 +106,7 @@ def generate(name, extra_args=None):
     args = CASES[name][0] if name in CASES else name
     if extra_args:
         args = args + " " + extra_args
-    tag = hashlib.sha1(args.encode()).hexdigest()[:16]
+    tag = hashlib.sha1((tool_digest() + " " + args).encode()).hexdigest()[:16]
     path = os.path.join(CACHE, "%s.264" % tag)
     if not os.path.exists(path):
         tmp = path + ".tmp%d" % os.getpid()

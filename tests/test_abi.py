@@ -1,6 +1,7 @@
 """The C-ABI library loads without a GPU and exports every symbol include/*.h declares;
 struct layouts seen by ctypes equal what a C compiler sees.  No compute calls here."""
 import ctypes as C
+import json
 import os
 import re
 import subprocess
@@ -73,10 +74,8 @@ int main(void) {
     assert out["launch"] == [C.sizeof(N.LaunchInfo), N.LaunchInfo.deblock_wgs.offset]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/p264.h"), reason="reference tree not present (GPU box)")
-def test_dropin_structs_match_the_reference_header():
-    """Binary contract of the drop-in: same sizes/offsets as the reference's own p264.h."""
-    body = r'''
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+DROPIN_LAYOUT = r'''
 int main(void) {
   printf("%zu %zu %zu %zu %zu ", sizeof(p264_param_t), offsetof(p264_param_t, vui), offsetof(p264_param_t, cqm_4iy), offsetof(p264_param_t, analyse), offsetof(p264_param_t, rc));
   printf("%zu %zu %zu ", offsetof(p264_param_t, pf_log), offsetof(p264_param_t, b_aud), offsetof(p264_param_t, b_repeat_headers));
@@ -84,15 +83,23 @@ int main(void) {
   printf("%zu %zu %zu\n", sizeof(p264_nal_t), offsetof(p264_nal_t, i_payload), offsetof(p264_nal_t, p_payload));
   return 0; }
 '''
-    outs = []
+
+
+def dropin_layout(inc, hdr):
+    """Sizes and offsets of the drop-in structs as a C compiler sees them through header `hdr` of directory `inc`."""
     with tempfile.TemporaryDirectory() as td:
-        for inc, hdr in ((INC, "p264_dropin.h"), ("/root/reference", "p264.h")):
-            c = os.path.join(td, "t.c")
-            open(c, "w").write("#include <stdio.h>\n#include <stddef.h>\n#include <stdint.h>\n#include \"%s\"\n%s" % (hdr, body))
-            exe = os.path.join(td, "t")
-            subprocess.run(["gcc", "-w", "-I" + inc, c, "-o", exe], check=True)
-            outs.append(subprocess.run([exe], stdout=subprocess.PIPE, text=True, check=True).stdout)
-    assert outs[0] == outs[1]
+        c = os.path.join(td, "t.c")
+        open(c, "w").write("#include <stdio.h>\n#include <stddef.h>\n#include <stdint.h>\n#include \"%s\"\n%s" % (hdr, DROPIN_LAYOUT))
+        exe = os.path.join(td, "t")
+        subprocess.run(["gcc", "-w", "-I" + inc, c, "-o", exe], check=True)
+        return subprocess.run([exe], stdout=subprocess.PIPE, text=True, check=True).stdout
+
+
+def test_dropin_structs_match_the_reference_header():
+    """Binary contract of the drop-in: same sizes/offsets as the reference's own p264.h (what a compiler sees through it,
+    recorded by tests/golden/make_ref_abi.py in tests/golden/ref_dropin_layout.txt)."""
+    want = open(os.path.join(GOLDEN, "ref_dropin_layout.txt")).read()
+    assert dropin_layout(INC, "p264_dropin.h") == want
 
 
 def test_open_fails_loudly_without_a_gpu(lib):
@@ -133,7 +140,7 @@ def _param_values(p):
             if hasattr(v, "_fields_"):
                 walk(key + ".", v)
             elif isinstance(v, C.Array):
-                out[key] = list(v)
+                out[key] = [list(x) if isinstance(x, C.Array) else x for x in v]
             elif typ is C.c_char_p:
                 out[key] = v
             elif typ is C.c_void_p or (isinstance(typ, type) and issubclass(typ, C._Pointer)):
@@ -144,17 +151,20 @@ def _param_values(p):
     return out
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libp264ref_kat.so")), reason="oracle/_ref not built")
+def param_values_json(p):
+    """_param_values in the form tests/golden/ref_param_default.json keeps them (strings by content as latin-1 text)."""
+    return json.loads(json.dumps({k: {"bytes": v.decode("latin-1")} if isinstance(v, bytes) else v for k, v in _param_values(p).items()}))
+
+
 def test_param_default_values_match_the_reference(lib):
-    """p264_param_default fills every field with the reference's value (core/core.c:41-137): compared against the REAL
-    function, linked into oracle/_ref/libp264ref_kat.so from the reference's own objects."""
-    ref = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libp264ref_kat.so"))
-    a, b = D.Param(), D.Param()
-    C.memset(C.byref(a), 0xAA, C.sizeof(a)); C.memset(C.byref(b), 0x55, C.sizeof(b))
+    """p264_param_default fills every field with the reference's value (core/core.c:41-137): compared against what the REAL
+    function filled in, recorded by tests/golden/make_ref_abi.py from oracle/_ref/libp264ref_kat.so (the reference's own
+    objects) in tests/golden/ref_param_default.json."""
+    a = D.Param()
+    C.memset(C.byref(a), 0xAA, C.sizeof(a))
     D._bind(lib)
     lib.p264_param_default(C.byref(a))
-    ref.p264_param_default(C.byref(b))
-    va, vb = _param_values(a), _param_values(b)
+    va, vb = param_values_json(a), json.load(open(os.path.join(GOLDEN, "ref_param_default.json")))
     assert va.keys() == vb.keys() and len(va) > 60
     diff = {k: (va[k], vb[k]) for k in va if va[k] != vb[k]}
     assert not diff, diff
@@ -178,25 +188,45 @@ def test_picture_alloc_and_clean(lib):
 REF = "/root/reference"
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "p264decoder.c")), reason="build container only: the reference's source does not travel")
+CLI_NEEDS = {"p264_param_default", "p264_decoder_open", "p264_decoder_decode", "p264_decoder_close", "p264_nal_decode", "p264_mdate"}
+
+
+def compile_reference_cli(ref, tmp):
+    """The reference's own caller (p264decoder.c), compiled from where it lies and linked against libp264amd.so; the empty
+    config.h its line 44 includes is written to `tmp` (upstream's configure writes it, SURVEY App. C uses an empty one)."""
+    open(os.path.join(tmp, "config.h"), "w").write("")
+    exe = os.path.join(tmp, "p264decoder_ref_cli")
+    cc = subprocess.run(["gcc", "-O1", "-std=gnu99", "-w", "-D__P264__", "-DHAVE_STDINT_H", "-I" + tmp, "-I" + ref, os.path.join(ref, "p264decoder.c"),
+                         "-L" + os.path.dirname(N.LIB_PATH), "-lp264amd", "-Wl,-rpath," + os.path.dirname(N.LIB_PATH), "-Wl,--no-undefined", "-lm", "-o", exe],
+                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    return exe, cc
+
+
+def undefined_p264_symbols(exe):
+    undefined = {l.split()[-1] for l in subprocess.run(["nm", "-u", exe], stdout=subprocess.PIPE, text=True).stdout.splitlines() if " p264_" in l or l.strip().startswith("U p264_")}
+    return {u.split("@")[0] for u in undefined}
+
+
 def test_the_reference_cli_links_unchanged_against_the_library(lib, tmp_path):
     """the reference's own caller (p264decoder.c:69-381: main, Decode, write_frame) compiled from
     where it lies, UNCHANGED, with the reference's headers, and linked against libp264amd.so instead of the reference's core/ and
     decoder/ objects - every symbol it needs (p264_param_default, p264_decoder_open / _decode / _close, p264_nal_decode,
-    p264_mdate) must resolve to the library.  The one thing supplied is the `config.h` its line 44 includes: upstream's configure
-    writes it, this tree has no configure, SURVEY App. C uses an empty one - so does this test (in tmp, nothing enters the repo).
-    Run here without a GPU the binary must get as far as the reference would with a decoder that cannot open: Help() on no
-    arguments, and "p264_decoder_open failed" on `-d` (p264decoder.c:203-207) - through OUR p264_decoder_open."""
-    (tmp_path / "config.h").write_text("")
-    exe = str(tmp_path / "p264decoder_ref_cli")
-    cc = subprocess.run(["gcc", "-O1", "-std=gnu99", "-w", "-D__P264__", "-DHAVE_STDINT_H", "-I" + str(tmp_path), "-I" + REF, os.path.join(REF, "p264decoder.c"),
-                         "-L" + os.path.dirname(N.LIB_PATH), "-lp264amd", "-Wl,-rpath," + os.path.dirname(N.LIB_PATH), "-Wl,--no-undefined", "-lm", "-o", exe],
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    p264_mdate) must resolve to the library.  The symbols it leaves undefined are recorded in tests/golden/ref_cli_symbols.txt
+    (tests/golden/make_ref_abi.py) and checked against the library everywhere.  Where the reference's source is at hand the
+    caller itself is compiled as well - with the empty `config.h` its line 44 includes (upstream's configure writes it, this tree
+    has no configure, SURVEY App. C uses an empty one; in tmp, nothing enters the repo) - and must leave exactly those symbols
+    undefined.  Run there without a GPU the binary must get as far as the reference would with a decoder that cannot open:
+    Help() on no arguments, and "p264_decoder_open failed" on `-d` (p264decoder.c:203-207) - through OUR p264_decoder_open."""
+    recorded = set(open(os.path.join(GOLDEN, "ref_cli_symbols.txt")).read().split())
+    assert CLI_NEEDS <= recorded
+    assert all(hasattr(lib, u) for u in recorded), sorted(u for u in recorded if not hasattr(lib, u))
+    if not os.path.exists(os.path.join(REF, "p264decoder.c")):
+        return                                                        # the reference's source does not travel: the recorded list is the check
+    exe, cc = compile_reference_cli(REF, str(tmp_path))
     assert cc.returncode == 0, cc.stdout[-3000:]
     # every p264_* symbol the caller leaves undefined is one the library defines
-    undefined = {l.split()[-1] for l in subprocess.run(["nm", "-u", exe], stdout=subprocess.PIPE, text=True).stdout.splitlines() if " p264_" in l or l.strip().startswith("U p264_")}
-    undefined = {u.split("@")[0] for u in undefined}
-    assert {"p264_param_default", "p264_decoder_open", "p264_decoder_decode", "p264_decoder_close", "p264_nal_decode", "p264_mdate"} <= undefined
+    undefined = undefined_p264_symbols(exe)
+    assert CLI_NEEDS <= undefined and undefined == recorded
     assert all(hasattr(lib, u) for u in undefined), undefined
     ldd = subprocess.run(["ldd", exe], stdout=subprocess.PIPE, text=True).stdout
     assert "libp264amd.so" in ldd and "not found" not in ldd

@@ -56,3 +56,27 @@ def test_the_committed_counter_summary_belongs_to_these_kernels():
     import os
     tj = json.load(open(os.path.join(bench.ROOT, "profiles", "traffic_latest.json")))
     assert tj.get("kernels_sha256") == bench.kernel_fingerprint(), "csrc/hip changed since profiles/%s was collected: run profiles/collect.sh + summarize.py" % tj.get("source")
+
+
+def test_a_long_run_cycles_over_the_resident_pictures():
+    """--steps is never cut short: a run that fits decodes picture t at step t, a longer one keeps RESIDENT_PICTURES // S pictures
+    per stream and cycles over an even window of its P pictures, so every step writes the frame slot its picture writes (the
+    parser alternates two slots) and reads the one the step before wrote."""
+    R, pic = bench.resident_window(2048, 24)
+    assert R == 24 and [pic(t) for t in range(24)] == list(range(24))
+    S = 2048
+    T = bench.RESIDENT_PICTURES // S + 500
+    R, pic = bench.resident_window(S, T)
+    assert S * R <= bench.RESIDENT_PICTURES and R >= 3
+    seq = [pic(t) for t in range(T)]
+    assert seq[:R] == list(range(R)) and min(seq[1:]) == 1 and max(seq) == R - 1
+    assert all(i % 2 == t % 2 for t, i in enumerate(seq))
+    R, pic = bench.resident_window(bench.RESIDENT_PICTURES, 50)          # one picture of room per stream: still IDR + two P
+    assert R == 3 and [pic(t) for t in range(6)] == [0, 1, 2, 1, 2, 1]
+
+
+def test_the_dumped_streams_are_a_fixed_sample_of_every_input():
+    d = bench.dump_streams(2048)
+    assert d == bench.dump_streams(2048) and [s % bench.DISTINCT for s in d] == list(range(bench.DISTINCT)) and max(d) < 2048
+    assert bench.dump_streams(4) == [0, 1, 2, 3] and bench.dump_streams(3) == [0, 1, 2]
+    assert all(max(bench.dump_streams(S)) < S for S in range(1, 40))

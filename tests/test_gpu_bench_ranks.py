@@ -21,7 +21,7 @@ def test_bench_gpus_2_starts_its_own_ranks(lib):
         env.pop(k, None)
     S, K, W = 6, 2, 1
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--streams", str(S), "--steps", str(K), "--warmup", str(W),
-                          "--no-cpu-baseline", "--no-extras"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env, cwd=ROOT)
+                          "--full", "--no-cpu-baseline", "--no-extras"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout                             # ONE JSON line, rank 0's
