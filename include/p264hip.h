@@ -113,6 +113,17 @@ typedef struct p264hip_picture {
     int32_t             weighted_bipred;
     int32_t             ref_slot_l1[P264HIP_MAX_REFS];
     int16_t             bipred_weight[P264HIP_MAX_REFS * P264HIP_MAX_REFS];   /* [ref_idx][ref_idx_l1], -64 .. 128 */
+    /* ---- explicit weighted prediction (H.264 8.4.2.3: P pictures with weighted_pred_flag, B pictures with weighted_bipred_idc 1;
+     * no counterpart in the reference, whose pred_weight_table parser is a stub).  explicit_wp != 0: every inter prediction of
+     * the picture is weighted - one list: Clip1(((p * w + 2^(d-1)) >> d) + o) (d = 0: Clip1(p * w + o)); two lists:
+     * Clip1(((p0 * w0 + p1 * w1 + 2^d) >> (d + 1)) + ((o0 + o1 + 1) >> 1)) - with d = wp_log2_denom[plane != 0] (0 .. 7),
+     * (w, o) = wp[list][ref_idx][plane] (offsets -128 .. 127; weights -128 .. 128, where 128 is only the inferred 2^7 of a reference
+     * without coded weights; a stream keeps the pairs its blocks use within -128 <= w0 + w1 <= (d == 7 ? 127 : 128), any sum gives
+     * a defined result here).  weighted_bipred must be 0 then.  Explicit pictures carry the table in their input slot (off_wp
+     * below): p264hip_upload copies the descriptor's, the packed and compact roads carry the block's. */
+    int32_t             explicit_wp;
+    int32_t             wp_log2_denom[2];                                      /* luma, chroma */
+    int16_t             wp[2][P264HIP_MAX_REFS][3][2];                         /* [list][ref_idx][Y, Cb, Cr][weight, offset] */
 } p264hip_picture_t;
 
 typedef struct p264hip_ctx p264hip_ctx;
@@ -159,8 +170,11 @@ typedef struct p264hip_input_layout {
     size_t off_mb, off_mv, off_ref, off_i4, off_coef;      /* p264hip_mb_t[n], int16[n][16][2], int8[n][4], uint8[n][16], int16[n_coef_blocks][16] */
     size_t off_mv_l1, off_ref_l1, off_weights;             /* B pictures only (0 otherwise): list-1 vectors, indices, bipred_weight[] */
     size_t bytes;                                          /* of the whole block */
+    size_t off_wp;                                         /* explicit_wp pictures only (0 otherwise): wp[][][][], behind everything else */
 } p264hip_input_layout_t;
 int  p264hip_input_layout(const p264hip_picture_t *desc, p264hip_input_layout_t *out);
+/* 0, or P264HIP_EINVAL where an explicit_wp picture's denominators, weights or offsets are out of range (every upload path checks it) */
+int  p264hip_wp_check(const p264hip_picture_t *desc);
 /* host side, no device involved: the picture's arrays copied into `dst` (cap >= layout.bytes) in that layout; the
  * macroblock records are checked as p264hip_upload checks them (coefficient ranges inside coefs[]).  Returns the bytes used
  * or a negative P264HIP_E* code. */
@@ -198,7 +212,8 @@ typedef struct p264hip_compact_hdr {                /* 128 bytes; sections follo
     uint32_t off_rec, off_i4flag, off_i4, off_lvflag, off_levels, off_weights;      /* off_weights: 0 unless n_lists == 2 */
     uint32_t n_i4, level_bytes;                     /* macroblocks with an Intra4x4 mode entry, bytes of levels */
     struct { uint32_t off_ref, off_shape, off_vec, n_vec; } list[2];               /* n_vec: vectors (dwords) in the list's vec section */
-    uint32_t reserved[11];
+    uint32_t off_wp;                                /* explicit_wp pictures: wp[][][][] (384 bytes), 0 otherwise */
+    uint32_t reserved[10];
 } p264hip_compact_hdr_t;
 /* bytes a compact block of this picture needs at most */
 size_t  p264hip_compact_bound(const p264hip_picture_t *pic);

@@ -43,6 +43,7 @@ class Picture(C.Structure):
         ("i4modes", C.POINTER(C.c_uint8)), ("coefs", C.POINTER(C.c_int16)),
         ("mv_l1", C.POINTER(C.c_int16)), ("ref_idx_l1", C.POINTER(C.c_int8)), ("n_ref_l1", C.c_int32), ("weighted_bipred", C.c_int32),
         ("ref_slot_l1", C.c_int32 * MAX_REFS), ("bipred_weight", C.c_int16 * (MAX_REFS * MAX_REFS)),
+        ("explicit_wp", C.c_int32), ("wp_log2_denom", C.c_int32 * 2), ("wp", C.c_int16 * (2 * MAX_REFS * 3 * 2)),   # wp: [list][ref_idx][Y, Cb, Cr][weight, offset], flat
     ]
 
 
@@ -60,7 +61,7 @@ BUILD_TIMING = 1
 
 class InputLayout(C.Structure):
     """p264hip_input_layout_t"""
-    _fields_ = [(n, C.c_size_t) for n in ("off_mb", "off_mv", "off_ref", "off_i4", "off_coef", "off_mv_l1", "off_ref_l1", "off_weights", "bytes")]
+    _fields_ = [(n, C.c_size_t) for n in ("off_mb", "off_mv", "off_ref", "off_i4", "off_coef", "off_mv_l1", "off_ref_l1", "off_weights", "bytes", "off_wp")]
 
 
 class CompactList(C.Structure):
@@ -71,7 +72,7 @@ class CompactHdr(C.Structure):
     """p264hip_compact_hdr_t (128 bytes)"""
     _fields_ = [("magic", C.c_uint32), ("n_mb", C.c_uint32), ("n_coef_blocks", C.c_uint32), ("bytes", C.c_uint32), ("n_lists", C.c_uint32),
                 ("off_rec", C.c_uint32), ("off_i4flag", C.c_uint32), ("off_i4", C.c_uint32), ("off_lvflag", C.c_uint32), ("off_levels", C.c_uint32),
-                ("off_weights", C.c_uint32), ("n_i4", C.c_uint32), ("level_bytes", C.c_uint32), ("list", CompactList * 2), ("reserved", C.c_uint32 * 11)]
+                ("off_weights", C.c_uint32), ("n_i4", C.c_uint32), ("level_bytes", C.c_uint32), ("list", CompactList * 2), ("off_wp", C.c_uint32), ("reserved", C.c_uint32 * 10)]
 
 
 class PipeStats(C.Structure):

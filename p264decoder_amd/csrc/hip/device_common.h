@@ -29,6 +29,9 @@ struct PicDev {
     const int16_t      *bipred_w;  // [16][16] weight of the list-0 prediction (used when weighted != 0)
     int32_t n_ref_l1, weighted;
     uint32_t ref_off_l1[P264HIP_MAX_REFS];
+    // explicit weighted prediction (p264hip_picture_t::explicit_wp; P and B pictures):
+    const int16_t      *wp;        // [list][16][Y, Cb, Cr][weight, offset]
+    int32_t explicit_wp, wp_denom_y, wp_denom_c;
 };
 
 // Geometry shared by every picture of a context.

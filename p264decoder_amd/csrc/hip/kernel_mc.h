@@ -202,7 +202,7 @@ __device__ __forceinline__ McIn mc_load(const PicDev *pd, int mbi)
     }
     return in;
 }
-template <bool BPIC>
+template <bool BPIC, bool WP>
 __device__ __forceinline__ McMb mc_classify(const PicDev *pd, const Geom &g, const McIn &in, int mbi, uint32_t inv_mbw, int band_log2, int pass)
 {
     McMb k;
@@ -216,6 +216,19 @@ __device__ __forceinline__ McMb mc_classify(const PicDev *pd, const Geom &g, con
     if (mbi - mby * g.mb_w >= g.mb_w) mby++;
     const int mbx = mbi - mby * g.mb_w, band = mby >> band_log2;
     const unsigned mask = rec.y, cc = mask & (0x00ff0000u | P264_COEF_CHROMA_DC);   // any chroma level present
+    if (WP && pd->explicit_wp) {
+        // explicit weighted prediction (wave-uniform: a picture per workgroup; compiled into the k_mc_sort*_wp instances only): every inter macroblock goes to the generic two-list
+        // class, all four quadrants, first pass - its lanes look up their lists, indices and weights themselves (mc_luma_body /
+        // mc_chroma_body: wp_combine4)
+        if (pass || !(k.info & MCMB_INTER)) { k.info = 0; return k; }
+        const int kc = band * MCC_KEYS + MCC_BI + (cc ? MCC_RESID : 0);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int ky = band * MCY_KEYS + (PC_GEN | (((mask >> (4 * q)) & 15) ? MCY_RESID : 0));
+            k.key[q] = (uint32_t)ky | (uint32_t)kc << 16;
+        }
+        return k;
+    }
     const int n_ref = pd->n_ref;
     int ri[4];
     bool zq[4] = { false, false, false, false };           // Z per quadrant
@@ -383,7 +396,7 @@ __device__ __forceinline__ void mc_scatter(const McSortCtx &c, const McMb &k, in
 // One picture: P pictures one pass (the classification of up to MC_SORT_KEEP macroblocks per thread stays in registers between
 // counting and scattering: the macroblock arrays are read once); B pictures both passes in one sweep (the arrays are read
 // twice - keeping two classifications of eight macroblocks does not fit the register file).
-template <bool BPIC>
+template <bool BPIC, bool WP>
 __device__ __forceinline__ void mc_sort_picture(const PicDev *__restrict__ pics, uint32_t *__restrict__ mc_all, const Geom &g, const McLayout &ml, uint32_t inv_mbw,
                                                 uint32_t *cnt, uint32_t *pos, uint8_t *__restrict__ is_intra_all)
 {
@@ -413,7 +426,7 @@ __device__ __forceinline__ void mc_sort_picture(const PicDev *__restrict__ pics,
             const int mbi = tid + j * MC_SORT_THREADS;
             kept[j].info = 0;
             if (mbi < g.n_mb) {
-                kept[j] = mc_classify<BPIC>(pd, g, mc_load<BPIC>(pd, mbi), mbi, inv_mbw, (int)ml.band_log2, 0); mc_count(ctx[0], kept[j]);
+                kept[j] = mc_classify<BPIC, WP>(pd, g, mc_load<BPIC>(pd, mbi), mbi, inv_mbw, (int)ml.band_log2, 0); mc_count(ctx[0], kept[j]);
                 is_intra[mbi] = (uint8_t)!(kept[j].info & MCMB_INTER);
             }
         }
@@ -422,7 +435,7 @@ __device__ __forceinline__ void mc_sort_picture(const PicDev *__restrict__ pics,
             const McIn in = mc_load<BPIC>(pd, mbi);
             is_intra[mbi] = (uint8_t)(P264_MB_IS_INTRA(in.rec.x & 255) != 0);
 #pragma unroll
-            for (int ps = 0; ps < NP; ps++) if (ps < n_pass) mc_count(ctx[ps], mc_classify<BPIC>(pd, g, in, mbi, inv_mbw, (int)ml.band_log2, ps));
+            for (int ps = 0; ps < NP; ps++) if (ps < n_pass) mc_count(ctx[ps], mc_classify<BPIC, WP>(pd, g, in, mbi, inv_mbw, (int)ml.band_log2, ps));
         }
     }
     __syncthreads();
@@ -457,7 +470,7 @@ __device__ __forceinline__ void mc_sort_picture(const PicDev *__restrict__ pics,
         for (int mbi = tid; mbi < g.n_mb; mbi += MC_SORT_THREADS) {
             const McIn in = mc_load<BPIC>(pd, mbi);
 #pragma unroll
-            for (int ps = 0; ps < NP; ps++) if (ps < n_pass) mc_scatter(ctx[ps], mc_classify<BPIC>(pd, g, in, mbi, inv_mbw, (int)ml.band_log2, ps), mbi, g, inv_mbw);
+            for (int ps = 0; ps < NP; ps++) if (ps < n_pass) mc_scatter(ctx[ps], mc_classify<BPIC, WP>(pd, g, in, mbi, inv_mbw, (int)ml.band_log2, ps), mbi, g, inv_mbw);
         }
     }
     __syncthreads();
@@ -486,7 +499,14 @@ __global__ __launch_bounds__(MC_SORT_THREADS)
 void k_mc_sort(const PicDev *__restrict__ pics, uint32_t *__restrict__ mc_all, Geom g, McLayout ml, uint32_t inv_mbw, uint8_t *__restrict__ is_intra)
 {
     __shared__ uint32_t cnt[MC_KEY_SLOTS], pos[MC_KEY_SLOTS];
-    mc_sort_picture<false>(pics, mc_all, g, ml, inv_mbw, cnt, pos, is_intra);
+    mc_sort_picture<false, false>(pics, mc_all, g, ml, inv_mbw, cnt, pos, is_intra);
+}
+// the same for batches with a picture of explicit weighted prediction (launched with k_mc_wp; k_mc_sort itself has no test for it)
+__global__ __launch_bounds__(MC_SORT_THREADS)
+void k_mc_sort_wp(const PicDev *__restrict__ pics, uint32_t *__restrict__ mc_all, Geom g, McLayout ml, uint32_t inv_mbw, uint8_t *__restrict__ is_intra)
+{
+    __shared__ uint32_t cnt[MC_KEY_SLOTS], pos[MC_KEY_SLOTS];
+    mc_sort_picture<false, true>(pics, mc_all, g, ml, inv_mbw, cnt, pos, is_intra);
 }
 // batches with B pictures
 #ifndef MC_SORT_B_WAVES_PER_EU
@@ -497,7 +517,13 @@ __global__ __launch_bounds__(MC_SORT_THREADS, MC_SORT_B_WAVES_PER_EU)
 void k_mc_sort_b(const PicDev *__restrict__ pics, uint32_t *__restrict__ mc_all, Geom g, McLayout ml, uint32_t inv_mbw, uint8_t *__restrict__ is_intra)
 {
     __shared__ uint32_t cnt[2 * MC_KEY_SLOTS], pos[2 * MC_KEY_SLOTS];
-    mc_sort_picture<true>(pics, mc_all, g, ml, inv_mbw, cnt, pos, is_intra);
+    mc_sort_picture<true, false>(pics, mc_all, g, ml, inv_mbw, cnt, pos, is_intra);
+}
+__global__ __launch_bounds__(MC_SORT_THREADS, MC_SORT_B_WAVES_PER_EU)
+void k_mc_sort_b_wp(const PicDev *__restrict__ pics, uint32_t *__restrict__ mc_all, Geom g, McLayout ml, uint32_t inv_mbw, uint8_t *__restrict__ is_intra)
+{
+    __shared__ uint32_t cnt[2 * MC_KEY_SLOTS], pos[2 * MC_KEY_SLOTS];
+    mc_sort_picture<true, true>(pics, mc_all, g, ml, inv_mbw, cnt, pos, is_intra);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -755,6 +781,23 @@ __device__ __forceinline__ uint32_t bipred_weight4(uint32_t a, uint32_t b, int w
     for (int i = 0; i < 4; i++) v[i] = (int)((a >> (8 * i)) & 255u) * w1 + (int)((b >> (8 * i)) & 255u) * w2 + 32;
     return round_pack4<6>(v);
 }
+// explicit weighted sample prediction (H.264 8.4.2.3.2), four samples at a time; wo = weight | offset << 16 (int16 each, one
+// entry of PicDev::wp), d = logWD.  One list: Clip1(((p * w + 2^(d-1)) >> d) + o), d = 0: Clip1(p * w + o); both lists:
+// Clip1(((p0 * w0 + p1 * w1 + 2^d) >> (d + 1)) + ((o0 + o1 + 1) >> 1)).  32-bit products (p0 * w0 + p1 * w1 needs 17 bits).
+__device__ __forceinline__ uint32_t wp_combine4(uint32_t a, uint32_t b, uint32_t wa, uint32_t wb, int d, bool use_a, bool use_b)
+{
+    const int w0 = (int)(int16_t)(wa & 0xffffu), o0 = (int)wa >> 16, w1 = (int)(int16_t)(wb & 0xffffu), o1 = (int)wb >> 16;
+    const bool bi = use_a && use_b;
+    // one list: the used one as "a" with its weight, the other one's weight 0; the shift and rounding of its form
+    const int wA = bi || use_a ? w0 : w1, wB = bi ? w1 : 0;
+    const uint32_t pa = bi || use_a ? a : b;
+    const int sh = bi ? d + 1 : d, rnd = bi ? 1 << d : (d ? 1 << (d - 1) : 0);
+    const int off = bi ? (o0 + o1 + 1) >> 1 : use_a ? o0 : o1;
+    int v[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) v[i] = clip255((((int)((pa >> (8 * i)) & 255u) * wA + (int)((b >> (8 * i)) & 255u) * wB + rnd) >> sh) + off);
+    return pack4(v[0], v[1], v[2], v[3]);
+}
 // ---- the seven phase classes: out[y] = the four samples of row y of the lane's 4x4 block -----------------------------
 // (ix, iy) = integer position of the block's first sample in the reference, (fx, fy) = quarter-pel phase.
 template <class W> __device__ __forceinline__ void mc_copy(uint32_t (&out)[4], const W &w, int ix, int iy)
@@ -966,7 +1009,7 @@ __device__ __forceinline__ uint3 mc_entry_record(const PicDev *__restrict__ pd, 
 // mc_luma_body<MB, PB> (a role of k_mc / k_mc_second): one wavefront = one chunk of one key: 4 macroblock items of 16 lanes, or 16 quadrant items of 4 lanes;
 // the lane is one 4x4 block
 // ------------------------------------------------------------------------------------------
-template <bool MB, bool PB>
+template <bool MB, bool PB, bool WP>
 __device__ __forceinline__ void mc_luma_body(uint8_t *images, const uint32_t *ref_tab, const PicDev *__restrict__ pd, const uint32_t *__restrict__ mc, const Geom &g,
                                              const McLayout &ml, int sub, int role_wgs)
 {
@@ -1099,7 +1142,24 @@ __device__ __forceinline__ void mc_luma_body(uint8_t *images, const uint32_t *re
             }
         };
         if (key & MCY_CLAMP) predict(roff, mvp, valid, out);
-        else {
+        else if (WP && pd->explicit_wp) {
+            // explicit weighted prediction (every inter block of such a picture is here, mc_classify): the lane's lists and
+            // indices, a prediction from each list it uses, the weights of (list, index) for luma
+            const int mbi = mby * g.mb_w + mbx;
+            const bool bpic = pd->slice_type == P264_SLICE_B;         // (wave-uniform)
+            const int r0 = (int)glob(pd->ref_idx)[mbi * 4 + q];
+            int r1 = -1, mv1 = 0;
+            if (bpic) { r1 = (int)glob(pd->ref_idx_l1)[mbi * 4 + q]; mv1 = (int)gload1(pd->mv_l1 + mbi * 16 + by * 4 + bx); }
+            const bool u1 = valid && r1 >= 0, u0 = valid && (r0 >= 0 || r1 < 0);
+            const int r0c = min(max(r0, 0), pd->n_ref - 1), r1c = bpic ? min(max(r1, 0), pd->n_ref_l1 - 1) : 0;
+            const uint32_t ro0 = glob(pd->ref_off)[r0c], ro1 = glob(pd->ref_off_l1)[r1c];
+            const uint32_t wa = gload1(pd->wp + r0c * 6), wb = gload1(pd->wp + (P264HIP_MAX_REFS + r1c) * 6);
+            uint32_t p0[4], p1[4];
+            predict(ro0, mvp, u0, p0);
+            predict(ro1, mv1, u1, p1);
+#pragma unroll
+            for (int y = 0; y < 4; y++) out[y] = wp_combine4(p0[y], p1[y], wa, wb, pd->wp_denom_y, u0, u1);
+        } else {
             // B picture, two lists (core/macroblock.c:525-583): which lists the lane's quadrant uses, a prediction from each,
             // then pixel_avg / pixel_avg_weight (core/mc.c:76-132)
             const int mbi = mby * g.mb_w + mbx;
@@ -1247,7 +1307,7 @@ __device__ __forceinline__ u32x4 chroma_piece_clamp(u32x4 t, const Geom &g, int 
 }
 __device__ __forceinline__ void lds_put16(uint8_t *p, u32x4 v) { *(uint2 *)p = make_uint2(v.x, v.y); *(uint2 *)(p + 8) = make_uint2(v.z, v.w); }
 
-template <bool MB, bool PB>
+template <bool MB, bool PB, bool WP>
 __device__ __forceinline__ void mc_chroma_body(uint8_t *images, const uint32_t *ref_tab, const PicDev *__restrict__ pd, const uint32_t *__restrict__ mc, const Geom &g,
                                                const McLayout &ml, int sub, int role_wgs)
 {
@@ -1396,7 +1456,20 @@ __device__ __forceinline__ void mc_chroma_body(uint8_t *images, const uint32_t *
             }
         };
         if (!(key & MCC_BI)) predict(roff, (valid && (e.x & MCE_LIST1)) ? pd->mv_l1 : pd->mv, valid, out);      // (padding lanes: list 0, mv_l1 is null outside B pictures)
-        else {
+        else if (WP && pd->explicit_wp) {
+            // explicit weighted prediction: as in mc_luma_body, with the weights of the lane's plane (Cb = plane 0, Cr = plane 1)
+            const bool bpic = pd->slice_type == P264_SLICE_B;         // (wave-uniform)
+            const int r0 = (int)glob(pd->ref_idx)[mbi * 4 + q], r1 = bpic ? (int)glob(pd->ref_idx_l1)[mbi * 4 + q] : -1;
+            const bool u1 = valid && r1 >= 0, u0 = valid && (r0 >= 0 || r1 < 0);
+            const int r0c = min(max(r0, 0), pd->n_ref - 1), r1c = bpic ? min(max(r1, 0), pd->n_ref_l1 - 1) : 0;
+            const uint32_t ro0 = glob(pd->ref_off)[r0c], ro1 = glob(pd->ref_off_l1)[r1c];
+            const uint32_t wa = gload1(pd->wp + r0c * 6 + 2 + 2 * p), wb = gload1(pd->wp + (P264HIP_MAX_REFS + r1c) * 6 + 2 + 2 * p);
+            uint32_t p0[4], p1[4] = { 0, 0, 0, 0 };
+            predict(ro0, pd->mv, u0, p0);
+            if (bpic) predict(ro1, pd->mv_l1, u1, p1);
+#pragma unroll
+            for (int y = 0; y < 4; y++) out[y] = wp_combine4(p0[y], p1[y], wa, wb, pd->wp_denom_c, u0, u1);
+        } else {
             // B picture, two lists: as in mc_luma_body
             const int r0 = (int)glob(pd->ref_idx)[mbi * 4 + q], r1 = (int)glob(pd->ref_idx_l1)[mbi * 4 + q];
             const bool u0 = valid && r0 >= 0, u1 = valid && r1 >= 0;
@@ -1478,7 +1551,7 @@ __device__ __forceinline__ void mc_chroma_body(uint8_t *images, const uint32_t *
 #define MC_COST_CM 5u
 #define MC_COST_CQ 9u
 #endif
-template <bool PB>
+template <bool PB, bool WP>
 __device__ __forceinline__ void mc_roles(uint8_t *images, uint32_t *ref_tab, const PicDev *__restrict__ pics, const uint32_t *__restrict__ mc_all, const Geom &g, const McLayout &ml,
                                          int wgs_per_pic, int n_wgs, uint32_t inv_wgs)
 {
@@ -1509,10 +1582,10 @@ __device__ __forceinline__ void mc_roles(uint8_t *images, uint32_t *ref_tab, con
     if (EXPM_ONLY == 1 && s >= w0 + w1) return;                                 // (timing switches)
     if (EXPM_ONLY == 2 && s < w0 + w1) return;
     if (EXPM_ONLY == 3 && !(s < w0 || (s >= w0 + w1 && s < w0 + w1 + w2))) return;   // macroblock items only
-    if (s < w0) mc_luma_body<true, PB>(images, ref_tab, pd, mc, g, ml, s, w0);
-    else if (s < w0 + w1) mc_luma_body<false, PB>(images, ref_tab, pd, mc, g, ml, s - w0, w1);
-    else if (s < w0 + w1 + w2) mc_chroma_body<true, PB>(images, ref_tab, pd, mc, g, ml, s - w0 - w1, w2);
-    else mc_chroma_body<false, PB>(images, ref_tab, pd, mc, g, ml, s - w0 - w1 - w2, w3);
+    if (s < w0) mc_luma_body<true, PB, WP>(images, ref_tab, pd, mc, g, ml, s, w0);
+    else if (s < w0 + w1) mc_luma_body<false, PB, WP>(images, ref_tab, pd, mc, g, ml, s - w0, w1);
+    else if (s < w0 + w1 + w2) mc_chroma_body<true, PB, WP>(images, ref_tab, pd, mc, g, ml, s - w0 - w1, w2);
+    else mc_chroma_body<false, PB, WP>(images, ref_tab, pd, mc, g, ml, s - w0 - w1 - w2, w3);
 }
 #ifndef MC_IMAGE_BYTES
 #define MC_IMAGE_BYTES (YItem<false>::LEAD + 4 * YItem<false>::WAVE_BYTES)         // the largest of the four roles' images
@@ -1527,7 +1600,18 @@ void k_mc(const PicDev *__restrict__ pics, const uint32_t *__restrict__ mc_all, 
 {
     __shared__ __attribute__((aligned(16))) uint8_t images[MC_IMAGE_BYTES];
     __shared__ uint32_t ref_tab[2 * P264HIP_MAX_REFS];
-    mc_roles<false>(images, ref_tab, pics, mc_all, g, ml, wgs_per_pic, n_wgs, inv_wgs);
+    mc_roles<false, false>(images, ref_tab, pics, mc_all, g, ml, wgs_per_pic, n_wgs, inv_wgs);
+}
+// batches with a picture of explicit weighted prediction: k_mc with the weighted generic class compiled in (mc_classify sends every
+// inter macroblock of such a picture there; the batch's other pictures run exactly as in k_mc) - a launch of its own so that k_mc
+// keeps its registers and unweighted batches run nothing new.  (Three wavefronts per SIMD: with k_mc's four the weighted generic
+// class spills three registers.)
+__global__ __launch_bounds__(256, 3)
+void k_mc_wp(const PicDev *__restrict__ pics, const uint32_t *__restrict__ mc_all, Geom g, McLayout ml, int wgs_per_pic, int n_wgs, uint32_t inv_wgs)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t images[MC_IMAGE_BYTES];
+    __shared__ uint32_t ref_tab[2 * P264HIP_MAX_REFS];
+    mc_roles<false, true>(images, ref_tab, pics, mc_all, g, ml, wgs_per_pic, n_wgs, inv_wgs);
 }
 // B pictures: the second pass (list-1 predictions of the blocks that use both lists), behind k_mc
 __global__ __launch_bounds__(256, 4)
@@ -1535,5 +1619,5 @@ void k_mc_second(const PicDev *__restrict__ pics, const uint32_t *__restrict__ m
 {
     __shared__ __attribute__((aligned(16))) uint8_t images[MC_IMAGE_BYTES];
     __shared__ uint32_t ref_tab[2 * P264HIP_MAX_REFS];
-    mc_roles<true>(images, ref_tab, pics, mc_all, g, ml, wgs_per_pic, n_wgs, inv_wgs);
+    mc_roles<true, false>(images, ref_tab, pics, mc_all, g, ml, wgs_per_pic, n_wgs, inv_wgs);
 }

@@ -51,7 +51,7 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 struct PicSlot {                       // one device-resident parsed picture
     uint8_t *dev = nullptr;
     size_t   cap = 0;                  // bytes allocated
-    size_t   off_mv = 0, off_ref = 0, off_i4 = 0, off_coef = 0, off_mv_l1 = 0, off_ref_l1 = 0, off_weights = 0;   // p264hip_input_layout_t (the last three: B pictures)
+    size_t   off_mv = 0, off_ref = 0, off_i4 = 0, off_coef = 0, off_mv_l1 = 0, off_ref_l1 = 0, off_weights = 0, off_wp = 0;   // p264hip_input_layout_t (off_mv_l1 .. off_weights: B pictures; off_wp: explicit_wp)
     size_t   bytes = 0;                // bytes in use
     p264hip_picture_t meta;            // scalar fields only; pointers unused
     bool     valid = false, reserved = false;   // reserved: p264hip_input_reserve handed the block out, commit is pending
@@ -259,6 +259,9 @@ static int check_pic(p264hip_ctx *c, const p264hip_picture_t *p, bool arrays)
             for (int i = 0; i < P264HIP_MAX_REFS * P264HIP_MAX_REFS; i++)
                 if (p->bipred_weight[i] < -64 || p->bipred_weight[i] > 128) return fail(P264HIP_EINVAL, "bipred_weight[%d]=%d out of range (-64 .. 128)", i, p->bipred_weight[i]);
     }
+    if (p264hip_wp_check(p))
+        return fail(P264HIP_EINVAL, "explicit weight table out of range (denominators %d / %d: 0 .. 7, weights -128 .. 128, offsets -128 .. 127, no implicit weights beside it, not in an I picture)",
+                    p->wp_log2_denom[0], p->wp_log2_denom[1]);
     if (!arrays) return 0;
     if (!p->mb || !p->mv || !p->ref_idx || !p->i4modes || (p->n_coef_blocks && !p->coefs)) return fail(P264HIP_EINVAL, "null picture array");
     // every macroblock's packed blocks must lie inside coefs[] (the kernels index it without further checks)
@@ -283,7 +286,7 @@ static int slot_prepare(p264hip_ctx *c, PicSlot &s, const p264hip_input_layout_t
         s.cap = cap;
     }
     s.off_mv = L.off_mv; s.off_ref = L.off_ref; s.off_i4 = L.off_i4; s.off_coef = L.off_coef;
-    s.off_mv_l1 = L.off_mv_l1; s.off_ref_l1 = L.off_ref_l1; s.off_weights = L.off_weights; s.bytes = L.bytes;
+    s.off_mv_l1 = L.off_mv_l1; s.off_ref_l1 = L.off_ref_l1; s.off_weights = L.off_weights; s.off_wp = L.off_wp; s.bytes = L.bytes;
     return 0;
 }
 static void slot_meta(PicSlot &s, const p264hip_picture_t *p)
@@ -320,7 +323,7 @@ static int expand_pending(p264hip_ctx *c)
     for (int i = 0; i < n; i++) {
         PicSlot &s = c->pics[(size_t)c->pending[(size_t)i]];
         c->h_jobs[i] = ExpandJob{ s.stage, s.dev, (uint32_t)s.off_mv, (uint32_t)s.off_ref, (uint32_t)s.off_i4, (uint32_t)s.off_coef,
-                                  (uint32_t)s.off_mv_l1, (uint32_t)s.off_ref_l1, (uint32_t)s.off_weights, 0u };
+                                  (uint32_t)s.off_mv_l1, (uint32_t)s.off_ref_l1, (uint32_t)s.off_weights, (uint32_t)s.off_wp };
         s.pending = false;
     }
     c->pending.clear();
@@ -370,7 +373,8 @@ static int upload_one(p264hip_ctx *c, int id, const p264hip_picture_t *p)
         if (p->n_coef_blocks)
             HIPCHK(hipMemcpyAsync(s.dev + L.off_coef, p->coefs, (size_t)p->n_coef_blocks * 32, hipMemcpyHostToDevice, c->stream));
     }
-    c->upload_copies += as_slot ? 1 : 5;
+    if (p->explicit_wp) HIPCHK(hipMemcpyAsync(s.dev + L.off_wp, p->wp, sizeof p->wp, hipMemcpyHostToDevice, c->stream));
+    c->upload_copies += (as_slot ? 1 : 5) + (p->explicit_wp ? 1 : 0);
     slot_meta(s, p);
     s.valid = true; s.unchecked = false; s.last_use = ++c->epoch;
     return 0;
@@ -385,6 +389,11 @@ extern "C" int p264hip_upload_packed(p264hip_ctx *c, int slot, const p264hip_pic
     if (rc) return rc;
     p264hip_input_layout_t L;
     if (p264hip_input_layout(desc, &L) || bytes != L.bytes) return fail(P264HIP_EINVAL, "p264hip_upload_packed: %zu bytes, the layout has %zu", bytes, L.bytes);
+    if (desc->explicit_wp) {                                 // the table the kernels will read is the block's: its ranges too
+        p264hip_picture_t t = *desc;
+        memcpy(t.wp, (const uint8_t *)packed + L.off_wp, sizeof t.wp);
+        if (p264hip_wp_check(&t)) return fail(P264HIP_EINVAL, "p264hip_upload_packed: the block's explicit weight table is out of range");
+    }
     unpend(c, slot);
     PicSlot &s = c->pics[(size_t)slot];
     if ((rc = slot_prepare(c, s, L))) return rc;
@@ -609,7 +618,7 @@ extern "C" int p264hip_clone_picture(p264hip_ctx *c, int dst, int src)
     // verdict along (behind the check on the same stream), any other clone clears what an earlier tenant of dst left there
     if (s.unchecked) HIPCHK(hipMemcpyAsync(c->d_slot_bad + dst, c->d_slot_bad + src, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
     else HIPCHK(hipMemsetAsync(c->d_slot_bad + dst, 0, sizeof(int), c->stream));
-    d.off_mv = s.off_mv; d.off_ref = s.off_ref; d.off_i4 = s.off_i4; d.off_coef = s.off_coef; d.off_mv_l1 = s.off_mv_l1; d.off_ref_l1 = s.off_ref_l1; d.off_weights = s.off_weights; d.bytes = s.bytes;
+    d.off_mv = s.off_mv; d.off_ref = s.off_ref; d.off_i4 = s.off_i4; d.off_coef = s.off_coef; d.off_mv_l1 = s.off_mv_l1; d.off_ref_l1 = s.off_ref_l1; d.off_weights = s.off_weights; d.off_wp = s.off_wp; d.bytes = s.bytes;
     d.meta = s.meta; d.valid = true; d.unchecked = s.unchecked; d.last_use = s.last_use = ++c->epoch;
     return P264HIP_OK;
 }
@@ -671,7 +680,7 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     const int r = c->ring; c->ring = (c->ring + 1) % BATCH_RING;
     HIPCHK(hipEventSynchronize(c->batch_free[r]));            // the copy that last used this staging buffer is done
     PicDev *hb = c->h_batch[r];
-    bool any_p = false, any_b = false, any_i = false;       // any picture with inter macroblocks / any B picture / any I picture
+    bool any_p = false, any_b = false, any_i = false, any_wp = false;   // any picture with inter macroblocks / any B picture / any I picture / any explicit weights
     for (int i = 0; i < n; i++) {                          // two pictures of one call must not share a stream: they would race on its frames
         const int st = streams[i];
         if (st < 0 || st >= c->n_streams) return fail(P264HIP_EINVAL, "stream %d out of range", st);
@@ -708,6 +717,11 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
                 d.ref_off_l1[k] = (uint32_t)(c->frame_bytes * (size_t)(k < s.meta.n_ref_l1 ? s.meta.ref_slot_l1[k] : s.meta.ref_slot_l1[0]));
             any_b = true;
         }
+        if (s.meta.explicit_wp) {
+            d.wp = (const int16_t *)(s.dev + s.off_wp);
+            d.explicit_wp = 1; d.wp_denom_y = s.meta.wp_log2_denom[0]; d.wp_denom_c = s.meta.wp_log2_denom[1];
+            any_wp = true;
+        }
         any_p |= s.meta.slice_type != P264_SLICE_I;
         any_i |= s.meta.slice_type == P264_SLICE_I;
     }
@@ -730,8 +744,9 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
         // interpolation has to do, then the luma and chroma kernels over the sorted lists (kernel_mc.h), side by side
         ScopedStamp t(c, 0);
         const McLayout ml = c->ml;
-        if (any_b) hipLaunchKernelGGL(k_mc_sort_b, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, c->d_batch[r], c->d_mc, g, ml, inv_mbw, c->d_is_intra);
-        else hipLaunchKernelGGL(k_mc_sort, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, c->d_batch[r], c->d_mc, g, ml, inv_mbw, c->d_is_intra);
+        // (explicit weighted prediction in the batch: the instances that route such pictures to the weighted class, kernel_mc.h)
+        if (any_b) hipLaunchKernelGGL(any_wp ? k_mc_sort_b_wp : k_mc_sort_b, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, c->d_batch[r], c->d_mc, g, ml, inv_mbw, c->d_is_intra);
+        else hipLaunchKernelGGL(any_wp ? k_mc_sort_wp : k_mc_sort, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, c->d_batch[r], c->d_mc, g, ml, inv_mbw, c->d_is_intra);
         // one launch for luma / chroma, macroblock / quadrant items (k_mc): every picture gets the same number of workgroups,
         // which split into the four roles on the device.  Enough workgroups per picture to fill the chip a few times over,
         // no more than there can be chunks (four wavefronts per workgroup, one chunk per wavefront pass).
@@ -745,7 +760,8 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
         if (c->tune_mc_wgs >= 4 && c->tune_mc_wgs <= max_wgs) wgs = c->tune_mc_wgs;
         if (wgs < 4) wgs = 4;
         li.mc_wgs_per_picture = wgs;
-        hipLaunchKernelGGL(k_mc, dim3(((size_t)wgs * n + 7) / 8 * 8), dim3(256), 0, c->stream, (const PicDev *)c->d_batch[r], (const uint32_t *)c->d_mc, g, ml,
+        // (a batch with explicit weighted prediction somewhere: the instance with the weighted generic class, kernel_mc.h: k_mc_wp)
+        hipLaunchKernelGGL(any_wp ? k_mc_wp : k_mc, dim3(((size_t)wgs * n + 7) / 8 * 8), dim3(256), 0, c->stream, (const PicDev *)c->d_batch[r], (const uint32_t *)c->d_mc, g, ml,
                            wgs, wgs * n, (uint32_t)(((1ull << 32) - 1) / (unsigned)wgs));
         // B pictures: the blocks that predict from both lists get their second prediction (and their residual) in a second pass
         if (any_b)
@@ -764,7 +780,7 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
         else {
             // (P / B pictures only.  Batches without B pictures: the loop filter's edge info is computed by extra workgroups of this
             // launch, kernel_intra.h)
-            bs_fused = !any_b && c->tune_bs_fused != 0;
+            bs_fused = !any_b && !any_wp && c->tune_bs_fused != 0;
             const int bs_wgs = bs_fused ? (c->tune_bs_fused > 0 ? c->tune_bs_fused : INTRA_BS_WGS) : 0;
             li.edge_info_fused = bs_wgs;
             hipLaunchKernelGGL(k_intra_sparse, dim3((unsigned)n * (2 + bs_wgs)), dim3(intra_waves * 64), (size_t)intra_waves * sizeof(IntraLds), c->stream, c->d_batch[r], g, c->d_status,
@@ -774,7 +790,8 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     {
         ScopedStamp t(c, 2);
         // edge info (boundary strengths, averaged QPs per edge class): everything about an edge that does not depend on samples
-        if (any_b) hipLaunchKernelGGL(k_deblock_bs<true>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, c->d_batch[r], g, c->d_edge, inv_mbw);
+        // (explicit weighted prediction: the two-list instance, which compares reference pictures rather than indices - kernel_deblock.h)
+        if (any_b || any_wp) hipLaunchKernelGGL(k_deblock_bs<true>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, c->d_batch[r], g, c->d_edge, inv_mbw);
         else if (!bs_fused) hipLaunchKernelGGL(k_deblock_bs<false>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, c->d_batch[r], g, c->d_edge, inv_mbw);
         // pictures per workgroup = as many as it takes to cover the batch with one workgroup per CU (a second, half-empty round
         // of workgroups costs more than sharing a workgroup: 1280 pictures as 320 workgroups of 4 took 5.35 ms, as 256 of 5 ...)

@@ -14,7 +14,7 @@ size_t p264hip_compact_bound(const p264hip_picture_t *p)
     if (!p || p->mb_w < 1 || p->mb_h < 1) return 0;
     const size_t n = (size_t)p->mb_w * (size_t)p->mb_h, lists = p->slice_type == P264_SLICE_B ? 2 : 1;
     return sizeof(p264hip_compact_hdr_t) + n * 16 + 16 + lists * (n * 4 + 16 + n / 4 + 32 + n * 64 + 16) + n / 8 + 32 + n * 16 + 16
-           + (size_t)p->n_coef_blocks / 8 + 32 + (size_t)p->n_coef_blocks * 32 + 64 + 512 + 64;
+           + (size_t)p->n_coef_blocks / 8 + 32 + (size_t)p->n_coef_blocks * 32 + 64 + 512 + 64 + (p->explicit_wp ? sizeof p->wp + 16 : 0);
 }
 
 /* 0 sixteen zero vectors, 1 one vector, 2 one per 8x8 quadrant, 3 sixteen */
@@ -35,6 +35,7 @@ int64_t p264hip_pack_compact(const p264hip_picture_t *p, void *dst_, size_t cap)
     if (!p->mb || !p->mv || !p->ref_idx || !p->i4modes || (p->n_coef_blocks && !p->coefs)) return P264HIP_EINVAL;
     const int isB = p->slice_type == P264_SLICE_B;
     if (isB && (!p->mv_l1 || !p->ref_idx_l1)) return P264HIP_EINVAL;
+    if (p264hip_wp_check(p)) return P264HIP_EINVAL;
     const size_t n = (size_t)p->mb_w * (size_t)p->mb_h;
     if (n > P264HIP_COMPACT_MAX_MB) return P264HIP_EINVAL;
     if (cap < p264hip_compact_bound(p)) return P264HIP_ENOMEM;
@@ -108,6 +109,7 @@ int64_t p264hip_pack_compact(const p264hip_picture_t *p, void *dst_, size_t cap)
     memset(lv + used, 0, 32);                                 /* (the expansion reads 32 bytes at a block's place whatever its width) */
     at = up16(at + used) + 32;
     if (isB) { h.off_weights = at; memcpy(dst + at, p->bipred_weight, 512); at += 512; }
+    if (p->explicit_wp) { h.off_wp = at; memcpy(dst + at, p->wp, sizeof p->wp); at += (uint32_t)sizeof p->wp; }     /* (384: stays 16-byte aligned) */
     h.bytes = at;
     memcpy(dst, &h, sizeof h);
     return (int64_t)h.bytes;
@@ -148,15 +150,17 @@ int p264hip_compact_header_ok(const p264hip_picture_t *d, const void *compact, s
     at = (uint64_t)h.off_lvflag + (h.n_coef_blocks + 7) / 8;
     if (h.off_levels < at) return 0;
     at = (uint64_t)h.off_levels + h.level_bytes + 32;
-    if ((h.off_i4flag | h.off_i4 | h.off_lvflag | h.off_levels | h.off_weights) & 15u) return 0;
+    if ((h.off_i4flag | h.off_i4 | h.off_lvflag | h.off_levels | h.off_weights | h.off_wp) & 15u) return 0;
     if (h.n_lists == 2) { if (h.off_weights < at) return 0; at = (uint64_t)h.off_weights + 512; }
     else if (h.off_weights) return 0;
+    if (d->explicit_wp) { if (h.off_wp < at) return 0; at = (uint64_t)h.off_wp + sizeof d->wp; }
+    else if (h.off_wp) return 0;
     return at <= h.bytes;
 }
 
 /* Everything a block from an untrusted producer should pass before the device walks it: the header (above), the counts the
  * expansion derives from the shape and flag bits are the header's, the records' coefficient ranges as p264hip_upload checks
- * them, a B picture's weights inside -64 .. 128. */
+ * them, a B picture's weights inside -64 .. 128, an explicit table inside its ranges (p264hip_wp_check). */
 int p264hip_compact_check(const p264hip_picture_t *d, const void *compact, size_t bytes)
 {
     if (!p264hip_compact_header_ok(d, compact, bytes)) return P264HIP_EINVAL;
@@ -182,6 +186,11 @@ int p264hip_compact_check(const p264hip_picture_t *d, const void *compact, size_
         int16_t w[256];
         memcpy(w, b + h.off_weights, 512);
         if (d->weighted_bipred) for (int i = 0; i < 256; i++) if (w[i] < -64 || w[i] > 128) return P264HIP_EINVAL;
+    }
+    if (d->explicit_wp) {                                     /* the table as it travels, with the descriptor's denominators */
+        p264hip_picture_t t = *d;
+        memcpy(t.wp, b + h.off_wp, sizeof t.wp);
+        if (p264hip_wp_check(&t)) return P264HIP_EINVAL;
     }
     return P264HIP_OK;
 }
@@ -221,5 +230,6 @@ int p264hip_expand_compact(const p264hip_picture_t *d, const void *compact, size
         else { memcpy(co + (size_t)k * 16, lv, 32); lv += 32; }
     }
     if (h.n_lists == 2) memcpy(out + L.off_weights, b + h.off_weights, 512);
+    if (h.off_wp) memcpy(out + L.off_wp, b + h.off_wp, sizeof d->wp);
     return P264HIP_OK;
 }

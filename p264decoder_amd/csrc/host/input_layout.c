@@ -24,6 +24,10 @@ int p264hip_input_layout(const p264hip_picture_t *d, p264hip_input_layout_t *o)
         o->off_weights = o->off_ref_l1 + up256(n * 4);
         end = o->off_weights + 512;
     }
+    if (d->explicit_wp) {                                                       /* (unweighted pictures: the layout of before, byte for byte) */
+        o->off_wp = end;
+        end += up256(sizeof d->wp);
+    }
     o->bytes = end;
     return P264HIP_OK;
 }
@@ -54,7 +58,26 @@ int64_t p264hip_pack_input(const p264hip_picture_t *p, void *dst_, size_t cap)
         memcpy(dst + L.off_ref_l1, p->ref_idx_l1, n * 4);
         memcpy(dst + L.off_weights, p->bipred_weight, sizeof p->bipred_weight);
     }
+    if (p->explicit_wp) {
+        if (p264hip_wp_check(p)) return P264HIP_EINVAL;
+        memcpy(dst + L.off_wp, p->wp, sizeof p->wp);
+    }
     return (int64_t)L.bytes;
+}
+
+/* the ranges of H.264 7.4.3.2 (include/p264hip.h): denominators 0 .. 7, offsets -128 .. 127, weights -128 .. 128 (128: the
+ * inferred 2^7 of a reference without coded weights).  What pairs of a B picture add up to is the parser's check (it is a rule
+ * for the stream; every sum gives a defined result here). */
+int p264hip_wp_check(const p264hip_picture_t *p)
+{
+    if (!p->explicit_wp) return 0;
+    if (p->weighted_bipred || p->slice_type == P264_SLICE_I) return P264HIP_EINVAL;
+    for (int c = 0; c < 2; c++) if (p->wp_log2_denom[c] < 0 || p->wp_log2_denom[c] > 7) return P264HIP_EINVAL;
+    for (int l = 0; l < 2; l++)
+        for (int i = 0; i < P264HIP_MAX_REFS; i++)
+            for (int c = 0; c < 3; c++)
+                if (p->wp[l][i][c][0] < -128 || p->wp[l][i][c][0] > 128 || p->wp[l][i][c][1] < -128 || p->wp[l][i][c][1] > 127) return P264HIP_EINVAL;
+    return 0;
 }
 
 int p264hip_unpack_input(const p264hip_picture_t *desc, const void *packed, size_t bytes, p264hip_picture_t *pic)
@@ -74,5 +97,6 @@ int p264hip_unpack_input(const p264hip_picture_t *desc, const void *packed, size
         pic->mv_l1 = (const int16_t *)(b + L.off_mv_l1);
         pic->ref_idx_l1 = (const int8_t *)(b + L.off_ref_l1);
     }
+    if (desc->explicit_wp) memcpy(pic->wp, b + L.off_wp, sizeof pic->wp);     /* the table the block carries (what the kernels read) */
     return P264HIP_OK;
 }

@@ -10,7 +10,7 @@
  * operations, and - SURVEY 8f rank 4, where the reference stops at decoder/lists.c:136 and
  * decoder/macroblock.c:168-171 - CAVLC B slices: two lists ordered by picture order count,
  * every B macroblock and sub-macroblock type, spatial and temporal direct prediction, implicit
- * bi-prediction weights); everything else is rejected with -1 and a line on stderr, the
+ * bi-prediction weights, explicit weighted prediction); everything else is rejected with -1 and a line on stderr, the
  * reference's error convention (decoder/decoder.c:558-577,780-795).
  */
 #include <stdio.h>
@@ -53,6 +53,8 @@ typedef struct {
     int poc_lsb, delta_poc_bottom, direct_spatial, cabac_init_idc;
     int no_output_of_prior, long_term_flag, adaptive_marking;
     int n_mmco; struct { int op, a, b; } mmco[34];   /* memory_management_control_operation 1..6 and its operands */
+    int wp, wp_denom[2];                             /* pred_weight_table( ) (7.3.3.2): present, luma / chroma log2 denominators */
+    int16_t wp_tab[2][P264HIP_MAX_REFS][3][2];       /* [list][ref_idx][Y, Cb, Cr][weight, offset], defaults filled in */
 } slice_t;
 
 typedef struct { int used, frame_num, pic_num, is_long, long_idx;   /* long_idx = LongTermFrameIdx (= LongTermPicNum for frames) */
@@ -93,6 +95,7 @@ struct p264parse {
     int list1[P264HIP_MAX_REFS], n_list1;     /* B pictures */
     int16_t bipred_weight[P264HIP_MAX_REFS * P264HIP_MAX_REFS];   /* implicit weights of the picture (8.4.2.3.1) */
     int weighted_bipred;
+    int pic_wp_set;                           /* the picture's explicit weight table: taken from its first P / B slice (p->sh0 keeps it) */
     /* picture order count (8.2.1) */
     int cur_poc, prev_poc_msb, prev_poc_lsb, prev_frame_num, frame_num_offset;
     uint32_t next_uid, cur_uid;
@@ -289,6 +292,36 @@ static int init_context(p264parse *p, int sps_id, int pps_id)
 }
 
 /* ---------------------------------------------------------------- slice header ---------- */
+/* pred_weight_table( ) (H.264 7.3.3.2, 4:2:0) with the semantics of 7.4.3.2: a reference without coded weights gets weight
+ * 2^denom and offset 0; denominators 0 .. 7, coded weights and offsets -128 .. 127.  The limit on the pairs of a B picture is
+ * checked on the pairs its blocks use (bipred_sums_bad). */
+static int parse_pred_weight_table(p264parse *p, bitrd_t *b, slice_t *sh)
+{
+    (void)p;
+    const unsigned dl = br_ue(b), dc = br_ue(b);
+    if (dl > 7 || dc > 7) { ERR(p, "log2 weight denominators %u / %u out of range (0 .. 7)", dl, dc); return -1; }
+    sh->wp_denom[0] = (int)dl; sh->wp_denom[1] = (int)dc;
+    const int isB = sh->type == P264_SLICE_B;
+    for (int l = 0; l < (isB ? 2 : 1); l++) {
+        const int n = l ? sh->num_ref_idx_l1 : sh->num_ref_idx;
+        for (int i = 0; i < n; i++) {
+            int16_t (*e)[2] = sh->wp_tab[l][i];
+            for (int c = 0; c < 3; c++) { e[c][0] = (int16_t)(1 << sh->wp_denom[c > 0]); e[c][1] = 0; }
+            for (int k = 0; k < 2; k++) {                 /* luma_weight_lX_flag, then chroma_weight_lX_flag */
+                if (!br_u1(b)) continue;
+                for (int c = k ? 1 : 0; c < (k ? 3 : 1); c++) {
+                    const int w = br_se(b), o = br_se(b);
+                    if (w < -128 || w > 127 || o < -128 || o > 127 || br_overrun(b)) {
+                        ERR(p, "list %d index %d: weight %d / offset %d out of range (-128 .. 127)", l, i, w, o); return -1;
+                    }
+                    e[c][0] = (int16_t)w; e[c][1] = (int16_t)o;
+                }
+            }
+        }
+    }
+    return br_overrun(b) ? -1 : 0;
+}
+
 /* decoder/decoder.c:70-301,368-488.  Fields the reconstruction does not need are skipped. */
 static int parse_slice_header(p264parse *p, bitrd_t *b, int nal_type, int nal_ref_idc, slice_t *sh)
 {
@@ -338,8 +371,9 @@ static int parse_slice_header(p264parse *p, bitrd_t *b, int nal_type, int nal_re
                 (*n)++;
             }
         }
-        if (pps->weighted_pred && sh->type == P264_SLICE_P) { ERR(p, "weighted prediction unsupported (decoder/decoder.c:259-262)"); return -1; }
-        if (pps->weighted_bipred == 1 && sh->type == P264_SLICE_B) { ERR(p, "explicit weighted bi-prediction unsupported (decoder/decoder.c:259-262)"); return -1; }
+        /* explicit weighted prediction (the reference's pred_weight_table parser is a stub, decoder/decoder.c:259-262) */
+        sh->wp = (pps->weighted_pred && sh->type == P264_SLICE_P) || (pps->weighted_bipred == 1 && sh->type == P264_SLICE_B);
+        if (sh->wp && parse_pred_weight_table(p, b, sh) < 0) return -1;
     }
     if (nal_ref_idc != 0) {
         if (nal_type == NAL_SLICE_IDR) { sh->no_output_of_prior = (int)br_u1(b); sh->long_term_flag = (int)br_u1(b); }
@@ -371,6 +405,25 @@ static int parse_slice_header(p264parse *p, bitrd_t *b, int nal_type, int nal_re
         if (sh->disable_deblock != 1) { sh->alpha_off = br_se(b); sh->beta_off = br_se(b); }
     }
     if (br_overrun(b)) { ERR(p, "slice header overruns the NAL"); return -1; }
+    return 0;
+}
+
+/* A B picture with explicit weights: every pair of references a bi-predicted 8x8 quadrant uses keeps
+ * -128 <= w0 + w1 <= (logWD == 7 ? 127 : 128) for each component (H.264 8.4.2.3).  Pairs no block uses are not limited. */
+static int bipred_sums_bad(p264parse *p)
+{
+    const picbuf_t *q = &p->buf[p->cur];
+    for (int i = 0; i < p->n_mb * 4; i++) {
+        const int r0 = q->ref[i], r1 = q->ref1[i];
+        if (r0 < 0 || r1 < 0 || r0 >= P264HIP_MAX_REFS || r1 >= P264HIP_MAX_REFS) continue;
+        for (int c = 0; c < 3; c++) {
+            const int d = p->sh0.wp_denom[c > 0], sum = p->sh0.wp_tab[0][r0][c][0] + p->sh0.wp_tab[1][r1][c][0];
+            if (sum < -128 || sum > (d == 7 ? 127 : 128)) {
+                ERR(p, "macroblock %d: weights of list-0 index %d and list-1 index %d add up to %d (component %d, denominator %d; H.264 8.4.2.3)", i / 4, r0, r1, sum, c, d);
+                return 1;
+            }
+        }
+    }
     return 0;
 }
 
@@ -1241,6 +1294,11 @@ static void publish_picture(p264parse *p)
         d->weighted_bipred = p->weighted_bipred;
         memcpy(d->bipred_weight, p->bipred_weight, sizeof d->bipred_weight);
     }
+    if (p->pic_wp_set && p->sh0.wp) {
+        d->explicit_wp = 1;
+        d->wp_log2_denom[0] = p->sh0.wp_denom[0]; d->wp_log2_denom[1] = p->sh0.wp_denom[1];
+        memcpy(d->wp, p->sh0.wp_tab, sizeof d->wp);
+    }
 }
 
 /* decoder/decoder.c:502-593,598-664 */
@@ -1278,7 +1336,7 @@ static int decode_slice(p264parse *p, int nal_type, int nal_ref_idc, const uint8
         p->pic_deblock = 0; p->pic_alpha = p->pic_beta = 0;
         p->buf[p->cur].coef_n = 0;
         memset(p->slice_of, 0xff, (size_t)p->n_mb * sizeof(uint16_t));
-        p->n_list0 = 0; p->n_list1 = 0;
+        p->n_list0 = 0; p->n_list1 = 0; p->pic_wp_set = 0;
         p->cur_poc = picture_order_count(p, &sh, p->pic_is_idr, nal_ref_idc);
         p->cur_uid = ++p->next_uid;
         if (p->buf[p->cur].ref1) memset(p->buf[p->cur].ref1, -1, (size_t)p->n_mb * 4);   /* nothing predicts from list 1 until a B macroblock says so */
@@ -1308,6 +1366,15 @@ static int decode_slice(p264parse *p, int nal_type, int nal_ref_idc, const uint8
         } else {
             if (p->sh0.type == P264_SLICE_B) { ERR(p, "P and B slices in one picture unsupported"); return -1; }
             p->sh0.type = P264_SLICE_P;           /* a picture with any P slice is reconstructed as P */
+        }
+        /* explicit weights: ONE table per picture on the device (like the lists); the first P / B slice's, every other one must match */
+        if (!p->pic_wp_set) {
+            p->pic_wp_set = 1;
+            p->sh0.wp = sh.wp; p->sh0.wp_denom[0] = sh.wp_denom[0]; p->sh0.wp_denom[1] = sh.wp_denom[1];
+            memcpy(p->sh0.wp_tab, sh.wp_tab, sizeof sh.wp_tab);
+        } else if (sh.wp != p->sh0.wp || (sh.wp && (sh.wp_denom[0] != p->sh0.wp_denom[0] || sh.wp_denom[1] != p->sh0.wp_denom[1]
+                                                     || memcmp(sh.wp_tab, p->sh0.wp_tab, sizeof sh.wp_tab)))) {
+            ERR(p, "slices of one picture with different weight tables unsupported"); return -1;
         }
     }
     p->qp_pred = sh.qp;
@@ -1362,6 +1429,7 @@ static int decode_slice(p264parse *p, int nal_type, int nal_ref_idc, const uint8
     }
     if (p->next_mb < p->n_mb) return 0;                       /* wait for the next slice of this picture */
 
+    if (p->sh0.type == P264_SLICE_B && p->pic_wp_set && p->sh0.wp && bipred_sums_bad(p)) { p->pic_open = 0; return -1; }
     publish_picture(p);
     *pic = &p->desc[p->cur];
     finish_picture_marking(p);

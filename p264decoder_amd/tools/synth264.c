@@ -38,6 +38,17 @@
  *                            the entropy coder, so `args` and `args --cabac` describe the same pictures
  *            [--pps-alt]     two identical PPS (ids 0 and 1), pictures alternate between them: every picture re-activates a
  *                            parameter set (context re-initialisation in the decoder, decoder/decoder.c:304-343)
+ *            [--wp]          Main profile with weighted_pred_flag 1: every P picture carries one random pred_weight_table (H.264
+ *                            7.3.3.2) in all of its slices - denominators 0 .. 7, per-reference flags, weights and offsets out to
+ *                            the clip on both ends; [--wp-bi] weighted_bipred_idc 1, the same for B pictures (pairs within the legal
+ *                            sum of 8.4.2.3); [--wp-dup] (with --refs >= 2) list-0 reordering that puts the most recent frame at
+ *                            indices 0 and 1, with different weights; [--wp-identity] every table weight 2^denom, offset 0, and
+ *                            no extra random draws: the same macroblocks as the stream without the weights; [--dump-wp f] per
+ *                            picture int16 explicit, luma denom, chroma denom, then the table [list][16][Y, Cb, Cr][weight, offset]
+ *                            with the defaults of references without weights filled in; [--wp-slice-differ] slices after the
+ *                            first carry a different table, [--wp-bad-sum] B pictures' luma weights 100 on every entry (pairs
+ *                            past the limit of 8.4.2.3: streams the decoder must refuse).  None of it draws a random number
+ *                            unless asked for: the other options write the bytes they wrote before.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -109,6 +120,58 @@ static int8_t  *i4m;                        /* [mb][16], 2 for non-I4x4 */
 static int cur;                             /* current MB index */
 
 static int opt_pps_alt = 0, cur_pps = 0;
+static int opt_wp = 0, opt_wp_bi = 0, opt_wp_dup = 0, opt_wp_identity = 0, opt_wp_differ = 0, opt_wp_bad_sum = 0;
+static FILE *dump_wp = NULL;
+/* the current picture's pred_weight_table: [list][index][Y, Cb, Cr][weight, offset]; flags per entry and component kind */
+static int wp_on, wp_denom[2], wp_tab[2][16][3][2], wp_flag[2][16][2];
+
+/* one table per picture.  P pictures: weights -128 .. 127, offsets -128 .. 127; B pictures: weights -64 .. 63 (any pair adds up to
+ * -128 .. 126: inside the limit of 8.4.2.3 for every denominator), a reference without coded weights only where 2^denom fits that */
+static void wp_draw(int is_b, int n0, int n1)
+{
+    memset(wp_tab, 0, sizeof wp_tab); memset(wp_flag, 0, sizeof wp_flag);
+    if (opt_wp_identity) { wp_denom[0] = 5; wp_denom[1] = 3; }
+    else { wp_denom[0] = rnd(8); wp_denom[1] = rnd(8); }
+    for (int l = 0; l < (is_b ? 2 : 1); l++)
+        for (int i = 0; i < (l ? n1 : n0); i++)
+            for (int k = 0; k < 2; k++) {
+                const int d = wp_denom[k], def = 1 << d;
+                const int flag = opt_wp_identity ? 1 : (is_b && def > 63) ? 1 : pct(75);
+                wp_flag[l][i][k] = flag;
+                for (int c = k ? 1 : 0; c < (k ? 3 : 1); c++) {
+                    int w = def, o = 0;
+                    if (flag && !opt_wp_identity) {
+                        const int lo = is_b ? -64 : -128, hi = is_b ? 63 : 127;
+                        w = pct(20) ? lo + rnd(hi - lo + 1) : def + rnd(2 * def + 1) - def;      /* (some anywhere, most near 2^d) */
+                        if (w < lo) w = lo;
+                        if (w > hi) w = hi;
+                        o = pct(20) ? (rnd(2) ? 127 : -128) : rnd(61) - 30;
+                    }
+                    wp_tab[l][i][c][0] = w; wp_tab[l][i][c][1] = o;
+                }
+            }
+    if (opt_wp_bad_sum && is_b) {                    /* a pair beyond the limit of 8.4.2.3 on every list entry (a stream to refuse) */
+        for (int l = 0; l < 2; l++) for (int i = 0; i < (l ? n1 : n0); i++) { wp_flag[l][i][0] = 1; wp_tab[l][i][0][0] = 100; }
+    }
+    if (opt_wp_dup && !is_b && n0 > 1 && !opt_wp_identity) {       /* the frame at indices 0 and 1: different weights */
+        wp_flag[0][1][0] = 1;
+        if (wp_tab[0][1][0][0] == wp_tab[0][0][0][0] && wp_tab[0][1][0][1] == wp_tab[0][0][0][1]) wp_tab[0][1][0][1] = wp_tab[0][0][0][1] > 0 ? wp_tab[0][0][0][1] - 1 : wp_tab[0][0][0][1] + 1;
+    }
+}
+static void wp_put(bw_t *b, int is_b, int n0, int n1, int differ)
+{
+    bw_ue(b, (uint32_t)wp_denom[0]); bw_ue(b, (uint32_t)wp_denom[1]);
+    for (int l = 0; l < (is_b ? 2 : 1); l++)
+        for (int i = 0; i < (l ? n1 : n0); i++)
+            for (int k = 0; k < 2; k++) {
+                const int flag = wp_flag[l][i][k] || (differ && l == 0 && i == 0 && k == 0);
+                bw_put(b, 1, (uint32_t)flag);
+                if (flag) for (int c = k ? 1 : 0; c < (k ? 3 : 1); c++) {
+                    const int o = wp_tab[l][i][c][1] + ((differ && l == 0 && i == 0 && c == 0) ? (wp_tab[l][i][c][1] < 127 ? 1 : -1) : 0);
+                    bw_se(b, wp_tab[l][i][c][0]); bw_se(b, o);
+                }
+            }
+}
 static int opt_mmco = 0, opt_mmco5 = 0, had_mmco5 = 0;   /* --mmco5: also memory_management_control_operation 5; had_mmco5: the picture just written carried one */
 /* the writer's own model of the decoded picture buffer (H.264 8.2.4, 8.2.5) */
 typedef struct { int used, pic, frame_num, is_long, long_idx;
@@ -509,6 +572,8 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
         b_build_lists();
         n_active = blist_n[0] > 4 ? 4 : blist_n[0]; n_active1 = blist_n[1] > 4 ? 4 : blist_n[1];
     }
+    wp_on = (is_p && opt_wp) || (is_b && opt_wp_bi);
+    if (wp_on) wp_draw(is_b, n_active, is_b ? n_active1 : 0);
     /* ---- reference picture marking of this picture (decided once, written into every slice header) ---- */
     int n_cmd = 0, cmd[8][3], idr_long = 0, cur_long = 0, cur_long_idx = 0;
     if (opt_mmco) {
@@ -587,8 +652,12 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
             if (opt_reorder && n_active > 1 && slice_reordered) {
                 /* list 0 starts as (frame_num - 1, frame_num - 2); "subtract 2 from the prediction" puts frame_num - 2 first */
                 bw_put(&b, 1, 1); bw_ue(&b, 0); bw_ue(&b, 1); bw_ue(&b, 3);
+            } else if (opt_wp_dup && n_active > 1) {
+                /* frame_num - 1 at index 0, then once more at index 1: a difference of MaxPicNum brings the prediction back to it (8.2.4.3.1) */
+                bw_put(&b, 1, 1); bw_ue(&b, 0); bw_ue(&b, 0); bw_ue(&b, 0); bw_ue(&b, (uint32_t)(max_fn - 1)); bw_ue(&b, 3);
             } else bw_put(&b, 1, 0);                        /* no reordering */
         }
+        if (wp_on) wp_put(&b, is_b, n_active, is_b ? n_active1 : 0, opt_wp_differ && sl > 0);
         if (is_b) { }                               /* a non-reference picture: no dec_ref_pic_marking */
         else if (idr) { bw_put(&b, 1, 0); bw_put(&b, 1, (uint32_t)idr_long); }    /* no_output_of_prior_pics, long_term_reference */
         else if (n_cmd) {
@@ -640,6 +709,15 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
         free(b.buf);
     }
     slice_first = 0;
+    if (dump_wp) {
+        int16_t rec[3 + 2 * 16 * 3 * 2];
+        memset(rec, 0, sizeof rec);
+        if (wp_on) {
+            rec[0] = 1; rec[1] = (int16_t)wp_denom[0]; rec[2] = (int16_t)wp_denom[1];
+            for (int l = 0; l < 2; l++) for (int i = 0; i < 16; i++) for (int c = 0; c < 3; c++) for (int k = 0; k < 2; k++) rec[3 + ((l * 16 + i) * 3 + c) * 2 + k] = (int16_t)wp_tab[l][i][c][k];
+        }
+        fwrite(rec, sizeof rec, 1, dump_wp);
+    }
     if (opt_bframes && !is_b && cur_entry >= 0) b_save_col(&wdpb[cur_entry], !is_p);
     if (dump_mv) {
         fwrite(mvs, 2, (size_t)NMB * 32, dump_mv); fwrite(refs, 1, (size_t)NMB * 16, dump_mv);
@@ -697,6 +775,13 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--d8inf")) opt_d8inf = 1;
         else if (!strcmp(a, "--mmco")) opt_mmco = 1;
         else if (!strcmp(a, "--mmco5")) opt_mmco = opt_mmco5 = 1;
+        else if (!strcmp(a, "--wp")) opt_wp = 1;
+        else if (!strcmp(a, "--wp-bi")) opt_wp_bi = 1;
+        else if (!strcmp(a, "--wp-dup")) opt_wp_dup = 1;
+        else if (!strcmp(a, "--wp-identity")) opt_wp_identity = 1;
+        else if (!strcmp(a, "--wp-slice-differ")) opt_wp_differ = 1;
+        else if (!strcmp(a, "--wp-bad-sum")) opt_wp_bad_sum = 1;
+        else if (!strcmp(a, "--dump-wp")) { dump_wp = fopen(argv[i + 1], "wb"); i++; }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
     if (W < 1 || H < 1 || W > 512 || H > 512 || frames < 1 || opt_qp < 0 || opt_qp > 51 || opt_refs < 1 || opt_refs > ((opt_mmco || opt_bframes) ? 4 : 2) || (opt_bframes && (opt_refs < 2 || opt_bframes > 4)) || opt_alpha < -6 || opt_alpha > 6 || opt_beta < -6 || opt_beta > 6) { fprintf(stderr, "bad geometry\n"); return 2; }
@@ -709,7 +794,7 @@ int main(int argc, char **argv)
     const int log2_fn = 8;
     {   /* SPS: Baseline, POC type 2, one reference frame */
         bw_t b = { 0 };
-        if (opt_bframes || opt_cabac) { bw_put(&b, 8, 77); bw_put(&b, 8, 0x40); bw_put(&b, 8, 40); }      /* Main profile */
+        if (opt_bframes || opt_cabac || opt_wp || opt_wp_bi) { bw_put(&b, 8, 77); bw_put(&b, 8, 0x40); bw_put(&b, 8, 40); }      /* Main profile */
         else { bw_put(&b, 8, 66); bw_put(&b, 8, 0xc0); bw_put(&b, 8, 40); }
         bw_ue(&b, 0); bw_ue(&b, log2_fn - 4);
         if (opt_bframes) { bw_ue(&b, 0); bw_ue(&b, 8 - 4); }   /* pic_order_cnt_type 0, log2_max_pic_order_cnt_lsb 8 */
@@ -726,7 +811,7 @@ int main(int argc, char **argv)
     for (int pps = 0; pps <= opt_pps_alt; pps++) {   /* PPS: CAVLC, deblocking control present */
         bw_t b = { 0 };
         bw_ue(&b, (uint32_t)pps); bw_ue(&b, 0); bw_put(&b, 1, (uint32_t)opt_cabac); bw_put(&b, 1, 0); bw_ue(&b, 0);   /* ids, entropy_coding_mode, pic_order_present, slice groups */
-        bw_ue(&b, 0); bw_ue(&b, 0); bw_put(&b, 1, 0); bw_put(&b, 2, (uint32_t)(opt_implicit ? 2 : 0));   /* weighted_pred 0, weighted_bipred_idc */
+        bw_ue(&b, 0); bw_ue(&b, 0); bw_put(&b, 1, (uint32_t)opt_wp); bw_put(&b, 2, (uint32_t)(opt_wp_bi ? 1 : opt_implicit ? 2 : 0));   /* weighted_pred, weighted_bipred_idc */
         bw_se(&b, opt_qp - 26); bw_se(&b, 0); bw_se(&b, opt_cqo);
         bw_put(&b, 1, 1); bw_put(&b, 1, 0); bw_put(&b, 1, 0);
         bw_trailing(&b);
@@ -748,6 +833,7 @@ int main(int argc, char **argv)
         }
         fclose(f);
         if (dump_mv) fclose(dump_mv);
+        if (dump_wp) fclose(dump_wp);
         return 0;
     }
     for (int n = 0; n < frames; n++) {
@@ -762,5 +848,6 @@ int main(int argc, char **argv)
     }
     fclose(f);
     if (dump_mv) fclose(dump_mv);
+    if (dump_wp) fclose(dump_wp);
     return 0;
 }
