@@ -227,7 +227,9 @@ int     p264hip_upload_compact(p264hip_ctx *ctx, int slot, const p264hip_picture
 /* device producers: reserve makes room in `slot` for a picture described by desc (scalar fields; its pointers are ignored)
  * and returns where its packed arrays are to be written (it waits for the context's stream only if work that still uses the
  * slot's previous picture is in flight: one wait covers a whole round of reserves); the slot becomes usable with commit, which
- * the caller issues once its writes have completed (the context's stream does not wait for anybody else's).  commit queues
+ * the caller issues once its writes have completed (the context's stream does not wait for anybody else's).  Commit is
+ * P264HIP_EINVAL unless the slot is still reserved: any other road into the slot in between (an upload, a clone into it)
+ * takes the reservation back, and a reserved slot that was not committed is empty to p264hip_reconstruct.  commit queues
  * the record check p264hip_upload runs on the host (every macroblock's packed blocks inside coefs[]) as a kernel over the
  * block; p264hip_reconstruct reads the verdicts of a batch's committed pictures with one wait and fails with P264HIP_EINVAL
  * where a block is inconsistent - the producer is not trusted. */

@@ -48,18 +48,23 @@ extern "C" int p264hip_build_info(void)
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// What an input slot holds.  Every road into a slot leaves it in exactly one state (from -> to):
+//   p264hip_upload / _upload_async / _upload_packed: any -> READY     p264hip_upload_compact: any -> STAGED (appended to c->pending)
+//   expand_pending: STAGED -> READY, or EMPTY when the expansion could not be queued
+//   p264hip_input_reserve: any -> RESERVED                            p264hip_input_commit: RESERVED -> UNCHECKED
+//   p264hip_clone_picture (dst): any -> the source's READY / UNCHECKED   p264hip_reconstruct: UNCHECKED -> READY, or EMPTY for a bad block
+// A road that fails once it has started to rewrite a slot leaves it EMPTY.  Reconstruct and clone read the slots that hold a
+// picture, state >= STAGED (expand_pending turns every STAGED one READY first).
+enum SlotState : uint8_t { EMPTY, RESERVED, STAGED, UNCHECKED, READY };
+
 struct PicSlot {                       // one device-resident parsed picture
     uint8_t *dev = nullptr;
     size_t   cap = 0;                  // bytes allocated
-    size_t   off_mv = 0, off_ref = 0, off_i4 = 0, off_coef = 0, off_mv_l1 = 0, off_ref_l1 = 0, off_weights = 0, off_wp = 0;   // p264hip_input_layout_t (off_mv_l1 .. off_weights: B pictures; off_wp: explicit_wp)
-    size_t   bytes = 0;                // bytes in use
+    p264hip_input_layout_t L = {};     // where the arrays lie in dev, and the bytes in use
     p264hip_picture_t meta;            // scalar fields only; pointers unused
-    bool     valid = false, reserved = false;   // reserved: p264hip_input_reserve handed the block out, commit is pending
-    uint8_t *stage = nullptr; size_t stage_cap = 0;   // p264hip_upload_compact: the compact block as it arrived; pending: its expansion into dev has not been launched yet
-    bool     pending = false;
-    int      stage_cs = 0;                            // the side stream that carried the pending block (a second block for the same slot follows on the same one)
-    bool     unchecked = false;                  // committed by a device producer: the record check (k_check_records) has been queued, its verdict not yet read
-    uint64_t last_use = 0;                       // epoch of the last work queued on the context's stream that reads or writes the block
+    SlotState state = EMPTY;
+    uint8_t *stage = nullptr; size_t stage_cap = 0;   // p264hip_upload_compact: the compact block as it arrived (STAGED: its expansion into dev has not been launched yet)
+    uint64_t last_use{};                         // epoch of the last work queued on the context's stream that reads or writes the block
 };
 
 #define BATCH_RING 4
@@ -109,14 +114,15 @@ struct p264hip_ctx {
     int batch_cap = 0, ring = 0;
     int *d_status = nullptr;
     int *d_slot_bad = nullptr;             // [max_pictures]: k_check_records' verdict per input slot
-    std::vector<int> pending;              // input slots whose compact block waits for k_expand_compact (launched in front of the next reconstruct / clone / sync)
+    std::vector<int> pending;              // the STAGED input slots, in upload order: k_expand_compact's jobs (launched in front of the next reconstruct / clone / sync)
     ExpandJob *h_jobs = nullptr, *d_jobs = nullptr; int jobs_cap = 0; hipEvent_t jobs_free = nullptr;
-    // compact blocks travel on COPY_STREAMS side streams, round robin: a copy of ~0.5 MB costs ~18 us of fixed latency beside ~9 us of
-    // transfer (measured, round 6: 512 copies per step on the context's one stream ran at 19.6 GB/s) - side by side the latencies overlap.
+    // compact blocks travel on COPY_STREAMS side streams, slot % COPY_STREAMS (two copies into one staging area on two streams would
+    // land in any order): a copy of ~0.5 MB costs ~18 us of fixed latency beside ~9 us of transfer (measured, round 6: 512 copies per
+    // step on the context's one stream ran at 19.6 GB/s) - side by side the latencies overlap.
     // The expansion kernel (context's stream) waits for the side streams' copies; a side stream waits for the last expansion before it
     // overwrites a staging area.
     hipStream_t cstream[COPY_STREAMS] = {}; hipEvent_t cdone[COPY_STREAMS] = {}; bool cdirty[COPY_STREAMS] = {}, cwaited[COPY_STREAMS] = {};
-    hipEvent_t expand_done = nullptr; int next_cs = 0;
+    hipEvent_t expand_done = nullptr;
     uint64_t upload_copies = 0;            // host -> HBM copies queued by p264hip_upload / _upload_async (one per picture whose arrays lie like a slot)
     uint64_t epoch = 0, done_epoch = 0;    // work queued on the stream / known to have completed (a slot is free for a new producer once its last_use is done)
     EdgeInfo *d_edge = nullptr;            // [batch_cap][n_mb], scratch between k_deblock_bs and k_deblock
@@ -212,12 +218,13 @@ extern "C" void p264hip_destroy(p264hip_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    // (the side streams too, before any staging area goes: a compact block that was never expanded may still be on its way)
+    for (int i = 0; i < COPY_STREAMS; i++) { if (c->cstream[i]) { (void)hipStreamSynchronize(c->cstream[i]); (void)hipStreamDestroy(c->cstream[i]); } if (c->cdone[i]) (void)hipEventDestroy(c->cdone[i]); }
     for (auto &p : c->pics) { if (p.dev) (void)hipFree(p.dev); if (p.stage) (void)hipFree(p.stage); }
     if (c->h_jobs) (void)hipHostFree(c->h_jobs);
     if (c->d_jobs) (void)hipFree(c->d_jobs);
     if (c->jobs_free) (void)hipEventDestroy(c->jobs_free);
     if (c->expand_done) (void)hipEventDestroy(c->expand_done);
-    for (int i = 0; i < COPY_STREAMS; i++) { if (c->cstream[i]) { (void)hipStreamSynchronize(c->cstream[i]); (void)hipStreamDestroy(c->cstream[i]); } if (c->cdone[i]) (void)hipEventDestroy(c->cdone[i]); }
     for (int i = 0; i < BATCH_RING; i++) {
         if (c->h_batch[i]) (void)hipHostFree(c->h_batch[i]);
         if (c->d_batch[i]) (void)hipFree(c->d_batch[i]);
@@ -275,58 +282,83 @@ static int check_pic(p264hip_ctx *c, const p264hip_picture_t *p, bool arrays)
     return 0;
 }
 
-// room for a picture of this layout in slot `id`; the slot's offsets follow the layout (include/p264hip.h)
-static int slot_prepare(p264hip_ctx *c, PicSlot &s, const p264hip_input_layout_t &L)
+// The one way a context buffer grows (input slots, staging areas, clone destinations, job table, batch ring): the old buffer
+// is freed after `wait` (what may still use it; WAIT_NONE: the caller has waited), then need + slack bytes of device memory -
+// pinned: of host memory the device reads - replace it.  cap: the bytes held (nullptr: the caller has decided to grow).
+enum Wait { WAIT_NONE, WAIT_STREAM, WAIT_DEVICE };
+static int grow(p264hip_ctx *c, void **buf, size_t *cap, size_t need, size_t slack, bool pinned, Wait wait, const char *what)
 {
-    if (L.bytes > s.cap) {
-        if (s.dev) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(s.dev)); s.dev = nullptr; s.cap = 0; }
-        size_t cap = L.bytes + L.bytes / 4;
-        hipError_t e = hipMalloc((void **)&s.dev, cap);
-        if (e != hipSuccess) return fail(P264HIP_ENOMEM, "hipMalloc(%zu) for picture input: %s", cap, hipGetErrorString(e));
-        s.cap = cap;
+    if (cap && need <= *cap) return 0;
+    if (cap) *cap = 0;
+    if (*buf) {
+        HIPCHK(wait == WAIT_STREAM ? hipStreamSynchronize(c->stream) : wait == WAIT_DEVICE ? hipDeviceSynchronize() : hipSuccess);
+        HIPCHK(pinned ? hipHostFree(*buf) : hipFree(*buf));
+        *buf = nullptr;
     }
-    s.off_mv = L.off_mv; s.off_ref = L.off_ref; s.off_i4 = L.off_i4; s.off_coef = L.off_coef;
-    s.off_mv_l1 = L.off_mv_l1; s.off_ref_l1 = L.off_ref_l1; s.off_weights = L.off_weights; s.off_wp = L.off_wp; s.bytes = L.bytes;
+    const hipError_t e = pinned ? hipHostMalloc(buf, need + slack, hipHostMallocDefault) : hipMalloc(buf, need + slack);
+    if (e != hipSuccess) { *buf = nullptr; return fail(P264HIP_ENOMEM, "%s(%zu) for %s: %s", pinned ? "hipHostMalloc" : "hipMalloc", need + slack, what, hipGetErrorString(e)); }
+    if (cap) *cap = need + slack;
     return 0;
 }
-static void slot_meta(PicSlot &s, const p264hip_picture_t *p)
+
+// Work that reads or writes slot s has been queued (or is about to be) under the context's current epoch: a later
+// p264hip_input_reserve of the slot waits for the stream unless that epoch is known to be done.
+static void stamp(p264hip_ctx *c, PicSlot &s) { s.last_use = c->epoch; }
+
+// ---- the roads into a slot (include/p264hip.h) ----
+// First step of every road with a new picture: argument, device, descriptor (arrays: its host arrays too), layout; the slot is untouched
+static int slot_enter(p264hip_ctx *c, int id, const p264hip_picture_t *p, bool arrays, p264hip_input_layout_t *L, const char *who)
 {
-    s.meta = *p;
+    if (!c || !p || id < 0 || id >= c->max_pictures) return fail(P264HIP_EINVAL, "%s: bad argument (slot %d)", who, id);
+    HIPCHK(hipSetDevice(c->device));
+    const int rc = check_pic(c, p, arrays);
+    if (rc) return rc;
+    return p264hip_input_layout(p, L) ? fail(P264HIP_EINVAL, "%s: picture layout", who) : 0;
+}
+// The slot starts to be rewritten: no picture until the road ends (a STAGED block drops out of c->pending); room for L + slack
+static int slot_prepare(p264hip_ctx *c, int id, const p264hip_input_layout_t &L, size_t slack)
+{
+    PicSlot &s = c->pics[(size_t)id];
+    if (s.state == STAGED)
+        for (size_t i = 0; i < c->pending.size(); i++) if (c->pending[i] == id) { c->pending.erase(c->pending.begin() + (long)i); break; }
+    s.state = EMPTY;
+    s.L = L;
+    return grow(c, (void **)&s.dev, &s.cap, L.bytes, slack, false, WAIT_STREAM, "picture input");
+}
+// Last step of every road: the picture's scalar fields, the slot's new state and the epoch of the work just queued on it.
+static void slot_exit(p264hip_ctx *c, int id, const p264hip_picture_t &p, SlotState state)
+{
+    PicSlot &s = c->pics[(size_t)id];
+    s.meta = p;
     s.meta.mb = nullptr; s.meta.mv = nullptr; s.meta.ref_idx = nullptr; s.meta.i4modes = nullptr; s.meta.coefs = nullptr; s.meta.mv_l1 = nullptr; s.meta.ref_idx_l1 = nullptr;
+    if (state == STAGED) c->pending.push_back(id);
+    s.state = state;
+    ++c->epoch;
+    stamp(c, s);
 }
 
 // ---- compact link format (include/p264hip.h, kernel_expand.h) ----
-// a slot that gets new content by another road no longer waits for its compact block's expansion
-static void unpend(p264hip_ctx *c, int id)
-{
-    PicSlot &s = c->pics[(size_t)id];
-    if (!s.pending) return;
-    s.pending = false;
-    for (size_t i = 0; i < c->pending.size(); i++) if (c->pending[i] == id) { c->pending.erase(c->pending.begin() + (long)i); break; }
-}
 // ONE launch expands every compact block uploaded since the last one
-static int expand_pending(p264hip_ctx *c)
+static int expand_launch(p264hip_ctx *c)
 {
     const int n = (int)c->pending.size();
-    if (!n) return 0;
+    if (c->jobs_free) HIPCHK(hipEventSynchronize(c->jobs_free));        // the copy that last read h_jobs is done
+    else HIPCHK(hipEventCreateWithFlags(&c->jobs_free, hipEventDisableTiming));
     if (n > c->jobs_cap) {
-        if (c->jobs_free) HIPCHK(hipEventSynchronize(c->jobs_free));
-        if (c->h_jobs) (void)hipHostFree(c->h_jobs);
-        if (c->d_jobs) (void)hipFree(c->d_jobs);
-        c->h_jobs = nullptr; c->d_jobs = nullptr;
         const int cap = n + n / 2 + 16;
-        HIPCHK(hipHostMalloc((void **)&c->h_jobs, (size_t)cap * sizeof(ExpandJob), hipHostMallocDefault));
-        HIPCHK(hipMalloc((void **)&c->d_jobs, (size_t)cap * sizeof(ExpandJob)));
-        if (!c->jobs_free) HIPCHK(hipEventCreateWithFlags(&c->jobs_free, hipEventDisableTiming));
+        c->jobs_cap = 0;
+        int rc = grow(c, (void **)&c->h_jobs, nullptr, (size_t)cap * sizeof(ExpandJob), 0, true, WAIT_NONE, "the expansion jobs");
+        if (rc || (rc = grow(c, (void **)&c->d_jobs, nullptr, (size_t)cap * sizeof(ExpandJob), 0, false, WAIT_NONE, "the expansion jobs"))) return rc;
         c->jobs_cap = cap;
-    } else HIPCHK(hipEventSynchronize(c->jobs_free));        // the copy that last read h_jobs is done
+    }
+    // the kernel writes the slots' arrays: a later p264hip_input_reserve of one of them must wait for it
+    ++c->epoch;
     for (int i = 0; i < n; i++) {
         PicSlot &s = c->pics[(size_t)c->pending[(size_t)i]];
-        c->h_jobs[i] = ExpandJob{ s.stage, s.dev, (uint32_t)s.off_mv, (uint32_t)s.off_ref, (uint32_t)s.off_i4, (uint32_t)s.off_coef,
-                                  (uint32_t)s.off_mv_l1, (uint32_t)s.off_ref_l1, (uint32_t)s.off_weights, (uint32_t)s.off_wp };
-        s.pending = false;
+        c->h_jobs[i] = ExpandJob{ s.stage, s.dev, (uint32_t)s.L.off_mv, (uint32_t)s.L.off_ref, (uint32_t)s.L.off_i4, (uint32_t)s.L.off_coef,
+                                  (uint32_t)s.L.off_mv_l1, (uint32_t)s.L.off_ref_l1, (uint32_t)s.L.off_weights, (uint32_t)s.L.off_wp };
+        stamp(c, s);
     }
-    c->pending.clear();
     for (int i = 0; i < COPY_STREAMS; i++) {                 // the blocks' copies (side streams) in front of the kernel that reads them
         if (!c->cdirty[i]) continue;
         HIPCHK(hipEventRecord(c->cdone[i], c->cstream[i]));
@@ -342,17 +374,24 @@ static int expand_pending(p264hip_ctx *c)
     for (int i = 0; i < COPY_STREAMS; i++) c->cwaited[i] = false;
     return 0;
 }
-
-static int upload_one(p264hip_ctx *c, int id, const p264hip_picture_t *p)
+// STAGED -> READY once the expansion is queued; if it is not, the slots are EMPTY (a retried reconstruct reports them empty
+// instead of decoding arrays that were never written)
+static int expand_pending(p264hip_ctx *c)
 {
-    int rc = check_pic(c, p, true);
-    if (rc) return rc;
-    unpend(c, id);
+    if (c->pending.empty()) return 0;
+    const int rc = expand_launch(c);
+    for (int id : c->pending) c->pics[(size_t)id].state = rc ? EMPTY : READY;
+    c->pending.clear();
+    return rc;
+}
+
+extern "C" int p264hip_upload_async(p264hip_ctx *c, int id, const p264hip_picture_t *p)
+{
+    p264hip_input_layout_t L;
+    int rc = slot_enter(c, id, p, true, &L, "p264hip_upload_async");
+    if (rc || (rc = slot_prepare(c, id, L, L.bytes / 4))) return rc;
     PicSlot &s = c->pics[(size_t)id];
     const size_t n = (size_t)c->g.n_mb;
-    p264hip_input_layout_t L;
-    if (p264hip_input_layout(p, &L)) return fail(P264HIP_EINVAL, "picture layout");
-    if ((rc = slot_prepare(c, s, L))) return rc;
     if (p->slice_type == P264_SLICE_B) {
         HIPCHK(hipMemcpyAsync(s.dev + L.off_mv_l1, p->mv_l1, n * 64, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(s.dev + L.off_ref_l1, p->ref_idx_l1, n * 4, hipMemcpyHostToDevice, c->stream));
@@ -375,56 +414,40 @@ static int upload_one(p264hip_ctx *c, int id, const p264hip_picture_t *p)
     }
     if (p->explicit_wp) HIPCHK(hipMemcpyAsync(s.dev + L.off_wp, p->wp, sizeof p->wp, hipMemcpyHostToDevice, c->stream));
     c->upload_copies += (as_slot ? 1 : 5) + (p->explicit_wp ? 1 : 0);
-    slot_meta(s, p);
-    s.valid = true; s.unchecked = false; s.last_use = ++c->epoch;
-    return 0;
+    slot_exit(c, id, *p, READY);
+    return P264HIP_OK;
 }
 
 // ---- other ways into a slot (include/p264hip.h): a packed host block in one copy; a device producer (reserve / commit) ----
 extern "C" int p264hip_upload_packed(p264hip_ctx *c, int slot, const p264hip_picture_t *desc, const void *packed, size_t bytes)
 {
-    if (!c || !desc || !packed || slot < 0 || slot >= c->max_pictures) return fail(P264HIP_EINVAL, "p264hip_upload_packed: bad argument (slot %d)", slot);
-    HIPCHK(hipSetDevice(c->device));
-    int rc = check_pic(c, desc, false);
-    if (rc) return rc;
+    if (!packed) return fail(P264HIP_EINVAL, "p264hip_upload_packed: null block");
     p264hip_input_layout_t L;
-    if (p264hip_input_layout(desc, &L) || bytes != L.bytes) return fail(P264HIP_EINVAL, "p264hip_upload_packed: %zu bytes, the layout has %zu", bytes, L.bytes);
+    int rc = slot_enter(c, slot, desc, false, &L, "p264hip_upload_packed");
+    if (rc) return rc;
+    if (bytes != L.bytes) return fail(P264HIP_EINVAL, "p264hip_upload_packed: %zu bytes, the layout has %zu", bytes, L.bytes);
     if (desc->explicit_wp) {                                 // the table the kernels will read is the block's: its ranges too
         p264hip_picture_t t = *desc;
         memcpy(t.wp, (const uint8_t *)packed + L.off_wp, sizeof t.wp);
         if (p264hip_wp_check(&t)) return fail(P264HIP_EINVAL, "p264hip_upload_packed: the block's explicit weight table is out of range");
     }
-    unpend(c, slot);
-    PicSlot &s = c->pics[(size_t)slot];
-    if ((rc = slot_prepare(c, s, L))) return rc;
-    HIPCHK(hipMemcpyAsync(s.dev, packed, L.bytes, hipMemcpyHostToDevice, c->stream));
-    slot_meta(s, desc);
-    s.valid = true; s.unchecked = false; s.last_use = ++c->epoch;
+    if ((rc = slot_prepare(c, slot, L, L.bytes / 4))) return rc;
+    HIPCHK(hipMemcpyAsync(c->pics[(size_t)slot].dev, packed, L.bytes, hipMemcpyHostToDevice, c->stream));
+    slot_exit(c, slot, *desc, READY);
     return P264HIP_OK;
 }
 
 extern "C" int p264hip_upload_compact(p264hip_ctx *c, int slot, const p264hip_picture_t *desc, const void *compact, size_t bytes)
 {
-    if (!c || !desc || !compact || slot < 0 || slot >= c->max_pictures) return fail(P264HIP_EINVAL, "p264hip_upload_compact: bad argument (slot %d)", slot);
-    HIPCHK(hipSetDevice(c->device));
-    int rc = check_pic(c, desc, false);
+    if (!compact) return fail(P264HIP_EINVAL, "p264hip_upload_compact: null block");
+    p264hip_input_layout_t L;
+    int rc = slot_enter(c, slot, desc, false, &L, "p264hip_upload_compact");
     if (rc) return rc;
     if (!p264hip_compact_header_ok(desc, compact, bytes)) return fail(P264HIP_EINVAL, "p264hip_upload_compact: the block is not a consistent compact picture of %dx%d macroblocks with %u coefficient blocks", desc->mb_w, desc->mb_h, desc->n_coef_blocks);
-    p264hip_input_layout_t L;
-    if (p264hip_input_layout(desc, &L)) return fail(P264HIP_EINVAL, "picture layout");
+    if ((rc = slot_prepare(c, slot, L, L.bytes / 4))) return rc;
     PicSlot &s = c->pics[(size_t)slot];
-    if ((rc = slot_prepare(c, s, L))) return rc;
-    if (bytes > s.stage_cap) {
-        if (s.stage) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(s.stage)); s.stage = nullptr; s.stage_cap = 0; }
-        const size_t cap = bytes + bytes / 4;
-        hipError_t e = hipMalloc((void **)&s.stage, cap);
-        if (e != hipSuccess) return fail(P264HIP_ENOMEM, "hipMalloc(%zu) for a compact picture: %s", cap, hipGetErrorString(e));
-        s.stage_cap = cap;
-    }
-    // (a slot whose block is still waiting for its expansion gets the newer block on the SAME side stream: two copies into one
-    // staging area on two streams would land in any order)
-    int cs = s.stage_cs;
-    if (!s.pending) { cs = c->next_cs; c->next_cs = (c->next_cs + 1) % COPY_STREAMS; s.stage_cs = cs; }
+    if ((rc = grow(c, (void **)&s.stage, &s.stage_cap, bytes, bytes / 4, false, WAIT_DEVICE, "a compact picture"))) return rc;
+    const int cs = slot % COPY_STREAMS;
     if (!c->cstream[cs]) {
         HIPCHK(hipStreamCreateWithFlags(&c->cstream[cs], hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&c->cdone[cs], hipEventDisableTiming));
@@ -438,37 +461,30 @@ extern "C" int p264hip_upload_compact(p264hip_ctx *c, int slot, const p264hip_pi
     HIPCHK(hipMemcpyAsync(s.stage, compact, bytes, hipMemcpyHostToDevice, c->cstream[cs]));
     c->cdirty[cs] = true;
     c->upload_copies += 1;
-    slot_meta(s, desc);
-    if (!s.pending) { s.pending = true; c->pending.push_back(slot); }
-    s.valid = true; s.unchecked = false; s.reserved = false; s.last_use = ++c->epoch;
+    slot_exit(c, slot, *desc, STAGED);
     return P264HIP_OK;
 }
 
 extern "C" int p264hip_input_reserve(p264hip_ctx *c, int slot, const p264hip_picture_t *desc, void **dev, size_t *bytes)
 {
-    if (!c || !desc || !dev || !bytes || slot < 0 || slot >= c->max_pictures) return fail(P264HIP_EINVAL, "p264hip_input_reserve: bad argument (slot %d)", slot);
-    HIPCHK(hipSetDevice(c->device));
-    int rc = check_pic(c, desc, false);
-    if (rc) return rc;
+    if (!dev || !bytes) return fail(P264HIP_EINVAL, "p264hip_input_reserve: null argument");
     p264hip_input_layout_t L;
-    if (p264hip_input_layout(desc, &L)) return fail(P264HIP_EINVAL, "picture layout");
-    unpend(c, slot);
+    int rc = slot_enter(c, slot, desc, false, &L, "p264hip_input_reserve");
+    if (rc) return rc;
     PicSlot &s = c->pics[(size_t)slot];
-    s.valid = false;
-    // Whatever still reads the slot's previous picture on the context's stream must be through before somebody else writes
-    // it.  One wait covers everything queued so far: the first reserve of a round waits (if the last batch is still running),
-    // the others find their slots' work already known to be done - not one hipStreamSynchronize per picture.
+    // Whatever still reads or writes the slot's previous picture on the context's stream must be through before somebody else
+    // writes it.  One wait covers everything queued so far: the first reserve of a round waits (if the last batch is still
+    // running), the others find their slots' work already known to be done - not one hipStreamSynchronize per picture.
     if (s.last_use > c->done_epoch) { const uint64_t upto = c->epoch; HIPCHK(hipStreamSynchronize(c->stream)); c->done_epoch = upto; }
-    if ((rc = slot_prepare(c, s, L))) return rc;
-    slot_meta(s, desc);
-    s.reserved = true;
+    if ((rc = slot_prepare(c, slot, L, L.bytes / 4))) return rc;
+    slot_exit(c, slot, *desc, RESERVED);
     *dev = s.dev; *bytes = L.bytes;
     return P264HIP_OK;
 }
 
 extern "C" int p264hip_input_commit(p264hip_ctx *c, int slot)
 {
-    if (!c || slot < 0 || slot >= c->max_pictures || !c->pics[(size_t)slot].reserved) return fail(P264HIP_EINVAL, "p264hip_input_commit: slot %d is not reserved", slot);
+    if (!c || slot < 0 || slot >= c->max_pictures || c->pics[(size_t)slot].state != RESERVED) return fail(P264HIP_EINVAL, "p264hip_input_commit: slot %d is not reserved", slot);
     PicSlot &s = c->pics[(size_t)slot];
     HIPCHK(hipSetDevice(c->device));
     // The producer wrote the arrays (it says they are complete on the device: include/p264hip.h); their records get the check
@@ -478,7 +494,7 @@ extern "C" int p264hip_input_commit(p264hip_ctx *c, int slot)
     const int n_mb = c->g.n_mb;
     hipLaunchKernelGGL(k_check_records, dim3((n_mb + 255) / 256), dim3(256), 0, c->stream, (const p264hip_mb_t *)s.dev, n_mb, s.meta.n_coef_blocks, c->d_slot_bad + slot);
     HIPCHK(hipGetLastError());
-    s.reserved = false; s.valid = true; s.unchecked = true; s.last_use = ++c->epoch;
+    slot_exit(c, slot, s.meta, UNCHECKED);
     return P264HIP_OK;
 }
 
@@ -518,17 +534,10 @@ extern "C" int p264hip_upload(p264hip_ctx *c, int first, const p264hip_picture_t
 {
     if (!c || !pics || n < 0 || first < 0 || first + n > c->max_pictures) return fail(P264HIP_EINVAL, "p264hip_upload: bad range [%d,+%d)", first, n);
     HIPCHK(hipSetDevice(c->device));
-    for (int i = 0; i < n; i++) { int rc = upload_one(c, first + i, &pics[i]); if (rc) return rc; }
+    for (int i = 0; i < n; i++) { int rc = p264hip_upload_async(c, first + i, &pics[i]); if (rc) return rc; }
     // sources are pageable host memory owned by the caller: make sure they are consumed before returning
     HIPCHK(hipStreamSynchronize(c->stream));
     return P264HIP_OK;
-}
-
-extern "C" int p264hip_upload_async(p264hip_ctx *c, int slot, const p264hip_picture_t *pic)
-{
-    if (!c || !pic || slot < 0 || slot >= c->max_pictures) return fail(P264HIP_EINVAL, "p264hip_upload_async: bad slot %d", slot);
-    HIPCHK(hipSetDevice(c->device));
-    return upload_one(c, slot, pic);
 }
 
 // Host buffers the device reads by DMA (the parsers write their pictures into them: p264parse_set_allocator).  Ordinary pages,
@@ -600,26 +609,19 @@ extern "C" int p264hip_marker_wait(p264hip_ctx *c, int marker)
 
 extern "C" int p264hip_clone_picture(p264hip_ctx *c, int dst, int src)
 {
-    if (!c || dst < 0 || src < 0 || dst >= c->max_pictures || src >= c->max_pictures || dst == src || !c->pics[(size_t)src].valid)
+    if (!c || dst < 0 || src < 0 || dst >= c->max_pictures || src >= c->max_pictures || dst == src || c->pics[(size_t)src].state < STAGED)
         return fail(P264HIP_EINVAL, "p264hip_clone_picture: bad slots %d <- %d", dst, src);
     HIPCHK(hipSetDevice(c->device));
-    unpend(c, dst);
-    { const int rc = expand_pending(c); if (rc) return rc; }   // (src may still be a compact block)
     PicSlot &d = c->pics[(size_t)dst], &s = c->pics[(size_t)src];
-    size_t need = s.bytes;
-    if (need > d.cap) {
-        if (d.dev) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(d.dev)); d.dev = nullptr; d.cap = 0; }
-        hipError_t e = hipMalloc((void **)&d.dev, need);
-        if (e != hipSuccess) return fail(P264HIP_ENOMEM, "hipMalloc(%zu) for picture clone: %s", need, hipGetErrorString(e));
-        d.cap = need;
-    }
-    HIPCHK(hipMemcpyAsync(d.dev, s.dev, need, hipMemcpyDeviceToDevice, c->stream));
+    int rc = slot_prepare(c, dst, s.L, 0);
+    if (rc || (rc = expand_pending(c))) return rc;            // (src may still be a compact block)
+    HIPCHK(hipMemcpyAsync(d.dev, s.dev, s.L.bytes, hipMemcpyDeviceToDevice, c->stream));
     // the verdict of the record check is kept per slot (k_check_records -> d_slot_bad[slot]): an unchecked block takes its
     // verdict along (behind the check on the same stream), any other clone clears what an earlier tenant of dst left there
-    if (s.unchecked) HIPCHK(hipMemcpyAsync(c->d_slot_bad + dst, c->d_slot_bad + src, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+    if (s.state == UNCHECKED) HIPCHK(hipMemcpyAsync(c->d_slot_bad + dst, c->d_slot_bad + src, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
     else HIPCHK(hipMemsetAsync(c->d_slot_bad + dst, 0, sizeof(int), c->stream));
-    d.off_mv = s.off_mv; d.off_ref = s.off_ref; d.off_i4 = s.off_i4; d.off_coef = s.off_coef; d.off_mv_l1 = s.off_mv_l1; d.off_ref_l1 = s.off_ref_l1; d.off_weights = s.off_weights; d.off_wp = s.off_wp; d.bytes = s.bytes;
-    d.meta = s.meta; d.valid = true; d.unchecked = s.unchecked; d.last_use = s.last_use = ++c->epoch;
+    slot_exit(c, dst, s.meta, s.state);
+    stamp(c, s);
     return P264HIP_OK;
 }
 
@@ -641,28 +643,22 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     HIPCHK(hipSetDevice(c->device));
     { const int rc = expand_pending(c); if (rc) return rc; }   // compact uploads since the last launch: one expansion kernel for all of them
     if (n > c->batch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));              // (one wait for every buffer of the ring)
+        c->batch_cap = 0;
         for (int i = 0; i < BATCH_RING; i++) {
-            if (c->h_batch[i]) (void)hipHostFree(c->h_batch[i]);
-            if (c->d_batch[i]) (void)hipFree(c->d_batch[i]);
-            c->h_batch[i] = nullptr; c->d_batch[i] = nullptr;
-            HIPCHK(hipHostMalloc((void **)&c->h_batch[i], (size_t)n * sizeof(PicDev), hipHostMallocDefault));
-            HIPCHK(hipMalloc((void **)&c->d_batch[i], (size_t)n * sizeof(PicDev)));
+            int rc = grow(c, (void **)&c->h_batch[i], nullptr, (size_t)n * sizeof(PicDev), 0, true, WAIT_NONE, "the batch");
+            if (rc || (rc = grow(c, (void **)&c->d_batch[i], nullptr, (size_t)n * sizeof(PicDev), 0, false, WAIT_NONE, "the batch"))) return rc;
             if (!c->batch_free[i]) HIPCHK(hipEventCreateWithFlags(&c->batch_free[i], hipEventDisableTiming));
             HIPCHK(hipEventRecord(c->batch_free[i], c->stream));
         }
-        if (c->d_edge) (void)hipFree(c->d_edge);
-        if (c->d_mc) (void)hipFree(c->d_mc);
-        if (c->d_is_intra) (void)hipFree(c->d_is_intra);
-        c->d_edge = nullptr; c->d_mc = nullptr; c->d_is_intra = nullptr;
-        HIPCHK(hipMalloc((void **)&c->d_is_intra, (size_t)n * c->g.n_mb));
-        HIPCHK(hipMalloc((void **)&c->d_edge, (size_t)n * c->g.n_mb * sizeof(EdgeInfo)));
-        HIPCHK(hipMalloc((void **)&c->d_mc, (size_t)n * c->ml.words * sizeof(uint32_t)));
+        int rc = grow(c, (void **)&c->d_is_intra, nullptr, (size_t)n * c->g.n_mb, 0, false, WAIT_NONE, "the batch");
+        if (rc || (rc = grow(c, (void **)&c->d_edge, nullptr, (size_t)n * c->g.n_mb * sizeof(EdgeInfo), 0, false, WAIT_NONE, "the batch")) ||
+            (rc = grow(c, (void **)&c->d_mc, nullptr, (size_t)n * c->ml.words * sizeof(uint32_t), 0, false, WAIT_NONE, "the batch"))) return rc;
         c->batch_cap = n;
     }
     {   // pictures that came through p264hip_input_commit: the verdicts of their record checks, one wait for the whole batch
         bool any_unchecked = false;
-        for (int i = 0; i < n; i++) { const int id = pic_ids[i]; if (id >= 0 && id < c->max_pictures && c->pics[(size_t)id].unchecked) any_unchecked = true; }
+        for (int i = 0; i < n; i++) { const int id = pic_ids[i]; if (id >= 0 && id < c->max_pictures && c->pics[(size_t)id].state == UNCHECKED) any_unchecked = true; }
         if (any_unchecked) {
             std::vector<int> bad((size_t)c->max_pictures);
             const uint64_t upto = c->epoch;
@@ -671,9 +667,9 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
             c->done_epoch = upto;
             for (int i = 0; i < n; i++) {
                 const int id = pic_ids[i];
-                if (id < 0 || id >= c->max_pictures || !c->pics[(size_t)id].unchecked) continue;
-                if (bad[(size_t)id]) { c->pics[(size_t)id].valid = false; c->pics[(size_t)id].unchecked = false; return fail(P264HIP_EINVAL, "picture slot %d: a macroblock's coefficient blocks lie outside coefs[] (the block a device producer committed is inconsistent)", id); }
-                c->pics[(size_t)id].unchecked = false;
+                if (id < 0 || id >= c->max_pictures || c->pics[(size_t)id].state != UNCHECKED) continue;
+                if (bad[(size_t)id]) { c->pics[(size_t)id].state = EMPTY; return fail(P264HIP_EINVAL, "picture slot %d: a macroblock's coefficient blocks lie outside coefs[] (the block a device producer committed is inconsistent)", id); }
+                c->pics[(size_t)id].state = READY;
             }
         }
     }
@@ -688,17 +684,17 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     }
     for (int i = 0; i < n; i++) {
         int id = pic_ids[i], st = streams[i];
-        if (id < 0 || id >= c->max_pictures || !c->pics[(size_t)id].valid) return fail(P264HIP_EINVAL, "picture slot %d is empty", id);
+        if (id < 0 || id >= c->max_pictures || c->pics[(size_t)id].state < STAGED) return fail(P264HIP_EINVAL, "picture slot %d is empty", id);
         if (c->stream_seen[(size_t)st]) return fail(P264HIP_EINVAL, "stream %d is named twice in one batch (entries %d and %d)", st, c->stream_seen[(size_t)st] - 1, i);
         c->stream_seen[(size_t)st] = i + 1;
         const PicSlot &s = c->pics[(size_t)id];
         PicDev &d = hb[i];
         memset(&d, 0, sizeof d);
         d.mb = (const p264hip_mb_t *)s.dev;
-        d.mv = (const int *)(s.dev + s.off_mv);
-        d.ref_idx = (const int8_t *)(s.dev + s.off_ref);
-        d.i4modes = s.dev + s.off_i4;
-        d.coefs = (const int16_t *)(s.dev + s.off_coef);
+        d.mv = (const int *)(s.dev + s.L.off_mv);
+        d.ref_idx = (const int8_t *)(s.dev + s.L.off_ref);
+        d.i4modes = s.dev + s.L.off_i4;
+        d.coefs = (const int16_t *)(s.dev + s.L.off_coef);
         d.dst = frame_ptr(c, st, s.meta.dst_slot);
         d.store = frame_ptr(c, st, 0);
         d.store_bytes = (uint32_t)(c->frame_bytes * (size_t)c->slots);
@@ -709,16 +705,16 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
         d.chroma_qp_offset = s.meta.chroma_qp_offset; d.deblock = s.meta.deblock;
         d.alpha_off = s.meta.alpha_c0_offset; d.beta_off = s.meta.beta_offset;
         if (s.meta.slice_type == P264_SLICE_B) {
-            d.mv_l1 = (const int *)(s.dev + s.off_mv_l1);
-            d.ref_idx_l1 = (const int8_t *)(s.dev + s.off_ref_l1);
-            d.bipred_w = (const int16_t *)(s.dev + s.off_weights);
+            d.mv_l1 = (const int *)(s.dev + s.L.off_mv_l1);
+            d.ref_idx_l1 = (const int8_t *)(s.dev + s.L.off_ref_l1);
+            d.bipred_w = (const int16_t *)(s.dev + s.L.off_weights);
             d.n_ref_l1 = s.meta.n_ref_l1; d.weighted = s.meta.weighted_bipred;
             for (int k = 0; k < P264HIP_MAX_REFS; k++)
                 d.ref_off_l1[k] = (uint32_t)(c->frame_bytes * (size_t)(k < s.meta.n_ref_l1 ? s.meta.ref_slot_l1[k] : s.meta.ref_slot_l1[0]));
             any_b = true;
         }
         if (s.meta.explicit_wp) {
-            d.wp = (const int16_t *)(s.dev + s.off_wp);
+            d.wp = (const int16_t *)(s.dev + s.L.off_wp);
             d.explicit_wp = 1; d.wp_denom_y = s.meta.wp_log2_denom[0]; d.wp_denom_c = s.meta.wp_log2_denom[1];
             any_wp = true;
         }
@@ -729,7 +725,7 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     // launch, so that whichever way this function returns - a launch error half-way included - a later p264hip_input_reserve
     // of one of them waits for the stream instead of letting a peer overwrite a block under running kernels
     ++c->epoch;
-    for (int i = 0; i < n; i++) c->pics[(size_t)pic_ids[i]].last_use = c->epoch;
+    for (int i = 0; i < n; i++) stamp(c, c->pics[(size_t)pic_ids[i]]);
     ScopedStamp whole(c, 3);
     HIPCHK(hipMemcpyAsync(c->d_batch[r], hb, (size_t)n * sizeof(PicDev), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->batch_free[r], c->stream));

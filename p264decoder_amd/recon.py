@@ -117,6 +117,9 @@ class HipReconstructor:
         if rc != 0:
             raise P264Error("p264hip_create: %s" % self.lib.p264hip_last_error().decode())
         self.h = h
+        # blocks given to upload_compact / upload_packed: their copies are asynchronous, so they stay referenced until sync()
+        # or close() (a list, not one per slot: a second upload into a slot must not drop the first block while it travels)
+        self._in_flight = []
 
     def _chk(self, rc, what):
         if rc != 0:
@@ -126,6 +129,7 @@ class HipReconstructor:
         if getattr(self, "h", None):
             self.lib.p264hip_destroy(self.h)
             self.h = None
+            self._in_flight = []
 
     def __del__(self):
         try:
@@ -175,9 +179,11 @@ class HipReconstructor:
         return out
 
     def upload_compact(self, slot, picture, compact):
+        self._in_flight.append(compact)
         self._chk(self.lib.p264hip_upload_compact(self.h, slot, C.byref(picture.desc), compact.ctypes.data, compact.size), "p264hip_upload_compact")
 
     def upload_packed(self, slot, picture, packed):
+        self._in_flight.append(packed)
         self._chk(self.lib.p264hip_upload_packed(self.h, slot, C.byref(picture.desc), packed.ctypes.data, packed.size), "p264hip_upload_packed")
 
     def input_reserve(self, slot, picture):
@@ -208,6 +214,7 @@ class HipReconstructor:
 
     def sync(self):
         self._chk(self.lib.p264hip_sync(self.h), "p264hip_sync")
+        self._in_flight = []
 
     def read_frame(self, stream, slot):
         w, h = self.mb_w * 16, self.mb_h * 16

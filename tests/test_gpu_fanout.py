@@ -275,6 +275,83 @@ def test_a_clone_takes_the_verdict_of_the_record_check_along(lib):
     hip.close()
 
 
+def test_a_reserve_waits_for_the_expansion_of_its_slot(lib):
+    """k_expand_compact writes a slot's arrays: p264hip_input_reserve of that slot must wait for it even when a sync has happened
+    between the slot's compact upload and the expansion.  Picture A goes compact into N slots, X last; a reserve of Y syncs;
+    a batch without X launches the one expansion of them all (X's job last, behind N copies); right after it X is reserved for
+    picture B, which a producer writes at once.  If the reserve did not wait, the expansion would overwrite B with A.  (A's block
+    lies in pinned memory, as the bench's and the pipeline's do: its copies are asynchronous, and the expansion waits for them.)"""
+    import ctypes as C
+    import numpy as np
+    from p264decoder_amd import HipReconstructor, Parser
+    from tests.conftest import frame_sha256
+    parser = Parser(quiet=True, lib=lib)
+    pics = parser.parse_stream(synth_cases.stream_bytes("cfg3_1080p_allp"), limit=2)
+    hashes = synth_cases.golden("cfg3_1080p_allp")[1]
+    B, A = pics                                                   # an I picture and a P picture
+    assert B.desc.slice_type == 2 and A.desc.slice_type == 0
+    N = 512
+    X, Y, others = N - 1, 0, list(range(1, N - 1))
+    hip = HipReconstructor(120, 68, n_streams=N, slots=parser.slots, max_pictures=N, lib=lib)
+    cb, pa, pb = HipReconstructor.pack_compact(B, lib), HipReconstructor.pack(A, lib), HipReconstructor.pack(B, lib)
+    blk = HipReconstructor.pack_compact(A, lib)
+    ptr = lib.p264hip_host_alloc(blk.size)
+    assert ptr
+    ca = np.frombuffer((C.c_uint8 * blk.size).from_address(ptr), np.uint8)
+    ca[:] = blk
+    # set-up: every buffer the timed sequence uses is at its size (no growth, and so no wait, on the way)
+    hip.upload_compact(X, B, cb)
+    for s in [Y] + others:
+        hip.upload_compact(s, A, ca)
+    hip.reconstruct(others, others)
+    hip.reconstruct([Y, X], [Y, X])
+    hip.sync()
+    for s in [Y] + others + [X]:
+        hip.upload_compact(s, A, ca)
+    dev, n = hip.input_reserve(Y, A)                              # waits for the stream: every upload so far is known done
+    assert lib.p264hip_copy_to_device(dev, pa.ctypes.data, n) == 0
+    hip.input_commit(Y)
+    hip.reconstruct(others, others)                               # expands Y .. X as one launch, X's job last; no wait
+    dev, n = hip.input_reserve(X, B)
+    assert n == pb.size
+    assert lib.p264hip_copy_to_device(dev, pb.ctypes.data, n) == 0
+    hip.input_commit(X)
+    hip.reconstruct([X], [X])
+    hip.sync()
+    got = frame_sha256(*hip.read_frame(X, B.desc.dst_slot))
+    hip.close()
+    lib.p264hip_host_free(ptr)
+    assert got == hashes[0]
+
+
+def test_only_a_reserved_slot_can_be_committed(lib):
+    """The slot states of p264hip.hip: a commit is accepted from RESERVED only.  An upload or a clone into a reserved slot takes the
+    reservation back (its commit is P264HIP_EINVAL and the slot keeps what the upload or the clone put there); a slot reserved
+    and never committed is empty to p264hip_reconstruct."""
+    import numpy as np
+    from p264decoder_amd import HipReconstructor, Parser
+    parser = Parser(quiet=True, lib=lib)
+    p = parser.parse_stream(synth_cases.stream_bytes("cif_ip"))[0]
+    hip = HipReconstructor(p.mb_w, p.mb_h, n_streams=3, slots=parser.slots, max_pictures=3, lib=lib)
+    blk = HipReconstructor.pack(p, lib)
+    hip.upload(0, [p])
+    hip.input_reserve(1, p)
+    with pytest.raises(Exception, match="empty"):
+        hip.reconstruct([1], [1])
+    hip.upload_packed(1, p, blk)
+    assert lib.p264hip_input_commit(hip.h, 1) == -1               # P264HIP_EINVAL
+    hip.input_reserve(2, p)
+    hip.clone_picture(2, 0)
+    assert lib.p264hip_input_commit(hip.h, 2) == -1
+    hip.reconstruct([0, 1, 2], [0, 1, 2])
+    hip.sync()
+    f0 = hip.read_frame(0, p.desc.dst_slot)
+    for s in (1, 2):
+        for a, b in zip(f0, hip.read_frame(s, p.desc.dst_slot)):
+            assert np.array_equal(a, b)
+    hip.close()
+
+
 def test_compact_uploads_match_the_plain_upload(lib):
     """p264hip_upload_compact (the compact link format, include/p264hip.h) against p264hip_upload, picture by picture and as a
     batch: the blocks of several pictures wait for ONE expansion kernel (k_expand_compact) in front of the reconstruct call;
@@ -288,16 +365,17 @@ def test_compact_uploads_match_the_plain_upload(lib):
     pics = parser.parse_stream(synth_cases.stream_bytes("cif_ip"))[:10]
     S = 3
     hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=S + 1, slots=parser.slots, max_pictures=S + 2, lib=lib)
+    blk0 = HipReconstructor.pack_compact(pics[0], lib)            # (every block stays alive until the sync behind its expansion)
     for i, p in enumerate(pics):
         blk = HipReconstructor.pack_compact(p, lib)
         hip.upload(0, [p])
         for s in range(1, S):
             hip.upload_compact(s, p, blk)
         if i == 3:                                              # superseded before it was expanded: the plain upload must win
-            hip.upload_compact(1, pics[0], HipReconstructor.pack_compact(pics[0], lib))
+            hip.upload_compact(1, pics[0], blk0)
             hip.upload(1, [p])
         if i == 5:                                              # two compact blocks for one slot, no expansion in between: the later one counts
-            hip.upload_compact(2, pics[0], HipReconstructor.pack_compact(pics[0], lib))
+            hip.upload_compact(2, pics[0], blk0)
             hip.upload_compact(2, p, blk)
         hip.clone_picture(S, 2)                                 # (expands what is pending first)
         hip.reconstruct([0, 1, 2, S], [0, 1, 2, S])
@@ -318,7 +396,8 @@ def test_compact_uploads_match_the_plain_upload(lib):
         p = seam_fuzz.make_picture(rng, mb_w, mb_h, p_picture=(k != 3), b_picture=(k >= 8), n_ref=2, n_ref_l1=2, slots=3, dst_slot=k % 3,
                                    level_style=["small", "large", "wrap", "mixed"][k % 4], sub8x8=True)
         hip.upload(0, [p])
-        hip.upload_compact(1, p, HipReconstructor.pack_compact(p, lib))
+        blk = HipReconstructor.pack_compact(p, lib)
+        hip.upload_compact(1, p, blk)
         hip.reconstruct([0, 1], [0, 1])
         hip.sync()
         for a, b in zip(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(1, p.desc.dst_slot)):
@@ -332,7 +411,8 @@ def test_compact_uploads_match_the_plain_upload(lib):
     hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=2, slots=parser.slots, max_pictures=2, lib=lib)
     for i, p in enumerate(pics):
         hip.upload(0, [p])
-        hip.upload_compact(1, p, HipReconstructor.pack_compact(p, lib))
+        blk = HipReconstructor.pack_compact(p, lib)
+        hip.upload_compact(1, p, blk)
         hip.reconstruct([0, 1], [0, 1])
         hip.sync()
         for a, b in zip(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(1, p.desc.dst_slot)):
