@@ -487,7 +487,7 @@ static void recon_inter(const rc_t *r, const p264hip_mb_t *m, int mbx, int mby, 
         uint8_t *dy = r->y + Y*r->w + X, *du = r->u + (Y/2)*r->cw + X/2, *dv = r->v + (Y/2)*r->cw + X/2;
         if (!isB || r0 >= 0) {
             int ri = r0;
-            if (ri < 0 || ri >= pic->n_ref) ri = isB ? clip3(ri, 0, pic->n_ref - 1) : 0;
+            if (ri < 0 || ri >= pic->n_ref) ri = 0;                            /* past the list: entry 0 (include/p264hip.h, ref_idx) */
             int slot = pic->ref_slot[ri];
             int mvx = pic->mv[(mbi*16 + b)*2], mvy = pic->mv[(mbi*16 + b)*2 + 1];
             oracle_mc_luma(r->planes[slot*3], r->w, r->h, X, Y, mvx, mvy, 4, 4, dy, r->w);
@@ -495,7 +495,7 @@ static void recon_inter(const rc_t *r, const p264hip_mb_t *m, int mbx, int mby, 
             oracle_mc_chroma(r->planes[slot*3+2], r->cw, r->ch, X/2, Y/2, mvx, mvy, 2, 2, dv, r->cw);
         }
         if (isB && r1 >= 0) {
-            int ri = clip3(r1, 0, pic->n_ref_l1 - 1), slot = pic->ref_slot_l1[ri];
+            int ri = r1 < pic->n_ref_l1 ? r1 : 0, slot = pic->ref_slot_l1[ri];
             int mvx = pic->mv_l1[(mbi*16 + b)*2], mvy = pic->mv_l1[(mbi*16 + b)*2 + 1];
             if (r0 < 0) {                                                    /* list 1 only: straight into the picture */
                 oracle_mc_luma(r->planes[slot*3], r->w, r->h, X, Y, mvx, mvy, 4, 4, dy, r->w);
@@ -503,7 +503,7 @@ static void recon_inter(const rc_t *r, const p264hip_mb_t *m, int mbx, int mby, 
                 oracle_mc_chroma(r->planes[slot*3+2], r->cw, r->ch, X/2, Y/2, mvx, mvy, 2, 2, dv, r->cw);
             } else {
                 uint8_t ty[16], tu[4], tv[4];
-                int w1 = pic->bipred_weight[clip3(r0, 0, pic->n_ref - 1) * P264HIP_MAX_REFS + ri];
+                int w1 = pic->bipred_weight[(r0 < pic->n_ref ? r0 : 0) * P264HIP_MAX_REFS + ri];
                 oracle_mc_luma(r->planes[slot*3], r->w, r->h, X, Y, mvx, mvy, 4, 4, ty, 4);
                 oracle_mc_chroma(r->planes[slot*3+1], r->cw, r->ch, X/2, Y/2, mvx, mvy, 2, 2, tu, 2);
                 oracle_mc_chroma(r->planes[slot*3+2], r->cw, r->ch, X/2, Y/2, mvx, mvy, 2, 2, tv, 2);
@@ -688,6 +688,8 @@ int oracle_deblock_picture(const p264hip_picture_t *pic, uint8_t **planes)
                         if (((m->coef_mask >> blk_at[y][x]) & 1) || ((n->coef_mask >> blk_at[yn][xn]) & 1)) bS[i] = 2;
                         else {
                             int rp = pic->ref_idx[mbi*4 + (y >> 1)*2 + (x >> 1)], rq = pic->ref_idx[nbi*4 + (yn >> 1)*2 + (xn >> 1)];
+                            if (rp < 0 || rp >= pic->n_ref) rp = 0;          /* negative or past the list: entry 0 (include/p264hip.h, ref_idx) */
+                            if (rq < 0 || rq >= pic->n_ref) rq = 0;
                             const int16_t *vp = pic->mv + (mbi*16 + y*4 + x)*2, *vq = pic->mv + (nbi*16 + yn*4 + xn)*2;
                             bS[i] = (rp != rq || iabs(vp[0] - vq[0]) >= 4 || iabs(vp[1] - vq[1]) >= 4) ? 1 : 0;   /* :565-577, one list */
                             if (pic->slice_type == P264_SLICE_B) bS[i] = b_motion_strength(pic, mbi, x, y, nbi, xn, yn);

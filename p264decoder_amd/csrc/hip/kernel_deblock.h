@@ -217,7 +217,10 @@ __device__ __forceinline__ uint4 edge_info_of(const PicDev *pd, const Geom &g, i
     const unsigned mmask = rec.y, lmask = recLy, tmask = recT.y;
     const bool m_intra = P264_MB_IS_INTRA(m_type), l_intra = P264_MB_IS_INTRA(recLx & 255), t_intra = P264_MB_IS_INTRA(recT.x & 255);
     const bool fL = m_edges & P264_EDGE_LEFT, fT = m_edges & P264_EDGE_TOP;
-    auto ref_of = [](uint32_t r4, int x, int y) { return (int)((r4 >> (8 * ((y >> 1) * 2 + (x >> 1)))) & 255); };
+    // (the index of the quadrant as the motion compensation reads it: negative or past the list = entry 0 - include/p264hip.h, ref_idx;
+    // intra quadrants take strength 3 / 4 whatever it says)
+    const int n_ref = pd->n_ref;
+    auto ref_of = [n_ref](uint32_t r4, int x, int y) { const int r = (int)(int8_t)(r4 >> (8 * ((y >> 1) * 2 + (x >> 1)))); return (r < 0 || r >= n_ref) ? 0 : r; };
 
     // ---- boundary strengths, core/frame.c:535-581 ----
     uint32_t word[2] = { 0, 0 };

@@ -129,6 +129,9 @@ static inline McLayout mc_layout(int mb_w, int mb_h, int band_log2)
     return L;
 }
 
+// the list entry a reference index names: negative (list unused) or at / past the list's length = entry 0, on every road
+// (prediction, implicit and explicit weights; the loop filter's pic_of_init reads the same, include/p264hip.h: ref_idx)
+__device__ __forceinline__ int ref_entry(int r, int n) { return (r < 0 || r >= n) ? 0 : r; }
 __device__ __forceinline__ int mv_x(int packed) { return (int)(int16_t)(packed & 0xffff); }
 __device__ __forceinline__ int mv_y(int packed) { return packed >> 16; }
 
@@ -239,7 +242,7 @@ __device__ __forceinline__ McMb mc_classify(const PicDev *pd, const Geom &g, con
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             ri[q] = (int)(int8_t)(refs >> (8 * q));
-            if (ri[q] < 0 || ri[q] >= n_ref) ri[q] = 0;    // negative or past the list: entry 0, as the reference's flat lists
+            ri[q] = ref_entry(ri[q], n_ref);                // negative or past the list: entry 0, as the reference's flat lists
             k.info |= (uint32_t)ri[q] << (8 + 4 * q);
         }
     } else {
@@ -257,7 +260,7 @@ __device__ __forceinline__ McMb mc_classify(const PicDev *pd, const Geom &g, con
             bool l1; int r;
             if (!pass) { l1 = !u0; zq[q] = bi; r = l1 ? r1 : r0; any = true; }
             else       { l1 = bi; zq[q] = !bi; r = bi ? r1 : 0; any |= bi; }
-            if (r < 0 || r >= (l1 ? pd->n_ref_l1 : n_ref)) r = 0;
+            r = ref_entry(r, l1 ? pd->n_ref_l1 : n_ref);
             // (list and index: what a whole macroblock has to agree on; second pass: the list-0 index too - the weight is per pair)
             ri[q] = r | (l1 ? 16 : 0) | ((pass && bi) ? (r0 & 15) << 5 : 0);
             k.info |= (uint32_t)r << (8 + 4 * q);
@@ -374,7 +377,7 @@ __device__ __forceinline__ void mc_scatter(const McSortCtx &c, const McMb &k, in
     for (int q = 0; q < 4; q++) {
         int w = 32;
         if (c.pd->weighted) {
-            const int r0 = min(max((int)(int8_t)(refs >> (8 * q)), 0), c.pd->n_ref - 1), r1 = (int)((k.info >> (8 + 4 * q)) & 15u);
+            const int r0 = ref_entry((int)(int8_t)(refs >> (8 * q)), c.pd->n_ref), r1 = (int)((k.info >> (8 + 4 * q)) & 15u);
             w = (int)glob(c.pd->bipred_w)[r0 * P264HIP_MAX_REFS + r1];
         }
         ew[q] = (rec.z & ((1u << MCE_W_SHIFT) - 1u)) | (uint32_t)w << MCE_W_SHIFT;
@@ -1151,7 +1154,7 @@ __device__ __forceinline__ void mc_luma_body(uint8_t *images, const uint32_t *re
             int r1 = -1, mv1 = 0;
             if (bpic) { r1 = (int)glob(pd->ref_idx_l1)[mbi * 4 + q]; mv1 = (int)gload1(pd->mv_l1 + mbi * 16 + by * 4 + bx); }
             const bool u1 = valid && r1 >= 0, u0 = valid && (r0 >= 0 || r1 < 0);
-            const int r0c = min(max(r0, 0), pd->n_ref - 1), r1c = bpic ? min(max(r1, 0), pd->n_ref_l1 - 1) : 0;
+            const int r0c = ref_entry(r0, pd->n_ref), r1c = bpic ? ref_entry(r1, pd->n_ref_l1) : 0;
             const uint32_t ro0 = glob(pd->ref_off)[r0c], ro1 = glob(pd->ref_off_l1)[r1c];
             const uint32_t wa = gload1(pd->wp + r0c * 6), wb = gload1(pd->wp + (P264HIP_MAX_REFS + r1c) * 6);
             uint32_t p0[4], p1[4];
@@ -1165,7 +1168,7 @@ __device__ __forceinline__ void mc_luma_body(uint8_t *images, const uint32_t *re
             const int mbi = mby * g.mb_w + mbx;
             const int r0 = (int)glob(pd->ref_idx)[mbi * 4 + q], r1 = (int)glob(pd->ref_idx_l1)[mbi * 4 + q];
             const bool u0 = valid && r0 >= 0, u1 = valid && r1 >= 0;
-            const int r0c = min(max(r0, 0), pd->n_ref - 1), r1c = min(max(r1, 0), pd->n_ref_l1 - 1);
+            const int r0c = ref_entry(r0, pd->n_ref), r1c = ref_entry(r1, pd->n_ref_l1);
             const int mv1 = (int)gload1(pd->mv_l1 + mbi * 16 + by * 4 + bx);
             const uint32_t ro0 = glob(pd->ref_off)[r0c], ro1 = glob(pd->ref_off_l1)[r1c];
             int wgt = 32;
@@ -1461,7 +1464,7 @@ __device__ __forceinline__ void mc_chroma_body(uint8_t *images, const uint32_t *
             const bool bpic = pd->slice_type == P264_SLICE_B;         // (wave-uniform)
             const int r0 = (int)glob(pd->ref_idx)[mbi * 4 + q], r1 = bpic ? (int)glob(pd->ref_idx_l1)[mbi * 4 + q] : -1;
             const bool u1 = valid && r1 >= 0, u0 = valid && (r0 >= 0 || r1 < 0);
-            const int r0c = min(max(r0, 0), pd->n_ref - 1), r1c = bpic ? min(max(r1, 0), pd->n_ref_l1 - 1) : 0;
+            const int r0c = ref_entry(r0, pd->n_ref), r1c = bpic ? ref_entry(r1, pd->n_ref_l1) : 0;
             const uint32_t ro0 = glob(pd->ref_off)[r0c], ro1 = glob(pd->ref_off_l1)[r1c];
             const uint32_t wa = gload1(pd->wp + r0c * 6 + 2 + 2 * p), wb = gload1(pd->wp + (P264HIP_MAX_REFS + r1c) * 6 + 2 + 2 * p);
             uint32_t p0[4], p1[4] = { 0, 0, 0, 0 };
@@ -1473,7 +1476,7 @@ __device__ __forceinline__ void mc_chroma_body(uint8_t *images, const uint32_t *
             // B picture, two lists: as in mc_luma_body
             const int r0 = (int)glob(pd->ref_idx)[mbi * 4 + q], r1 = (int)glob(pd->ref_idx_l1)[mbi * 4 + q];
             const bool u0 = valid && r0 >= 0, u1 = valid && r1 >= 0;
-            const int r0c = min(max(r0, 0), pd->n_ref - 1), r1c = min(max(r1, 0), pd->n_ref_l1 - 1);
+            const int r0c = ref_entry(r0, pd->n_ref), r1c = ref_entry(r1, pd->n_ref_l1);
             const uint32_t ro0 = glob(pd->ref_off)[r0c], ro1 = glob(pd->ref_off_l1)[r1c];
             int wgt = 32;
             if (pd->weighted) wgt = (int)glob(pd->bipred_w)[r0c * P264HIP_MAX_REFS + r1c];

@@ -79,13 +79,19 @@ def _levels(rng, n, style):
 
 
 def make_picture(rng, mb_w, mb_h, *, p_picture=True, n_ref=1, slots=2, dst_slot=0, level_style="small", qp_mode="random",
-                 mv_range=80, sub8x8=True, intra_share=0.15, slices=1, deblock_offsets=True, b_picture=False, n_ref_l1=1, weighted=None, mirror_l1=0.0):
+                 mv_range=80, sub8x8=True, intra_share=0.15, slices=1, deblock_offsets=True, b_picture=False, n_ref_l1=1, weighted=None, mirror_l1=0.0,
+                 explicit_wp=None, wp_denoms=None, dup_refs=False, past_list=0.0, slice_idcs=None):
     """Draw one picture.  qp_mode: 'random' (0..51 per macroblock), 'two' (two values), or an int (constant).
     b_picture: a B picture - every inter macroblock is P264_MB_B, each 8x8 quadrant predicts from list 0, list 1 or both
     (a negative index = list unused, its vectors 0); weighted: None = drawn, else weighted_bipred on / off; mirror_l1: share of
     the B macroblocks whose list-1 vectors repeat their list-0 vectors (with the same frames in both lists: blocks that read the
     same picture through different lists with equal vectors - the case where H.264 8.7.2.1's boundary strength by PICTURE and a
-    list-by-list comparison of indices differ)."""
+    list-by-list comparison of indices differ).
+    explicit_wp: None, or "legal" / "wide" - a table of explicit weights (draw_wp_table; wp_denoms = (luma, chroma) denominators,
+    None = drawn).  dup_refs: list 0 (and list 1) start with one frame at indices 0 and 1 - with explicit weights, two different
+    weights of one frame.  past_list: share of the inter quadrants (skipped macroblocks aside) whose indices are drawn from
+    n_ref .. 15 instead, in each list the quadrant uses - an index past its list means entry 0 (include/p264hip.h, ref_idx).
+    slice_idcs: the slices' deblocking idcs in turn (None: drawn)."""
     pic = SeamPicture(mb_w, mb_h)
     d = pic.desc
     n = mb_w * mb_h
@@ -103,17 +109,17 @@ def make_picture(rng, mb_w, mb_h, *, p_picture=True, n_ref=1, slots=2, dst_slot=
     d.n_ref = n_ref if p_picture else 0
     others = [s for s in range(slots) if s != dst_slot]
     for i in range(d.n_ref):
-        d.ref_slot[i] = others[i % len(others)]
+        d.ref_slot[i] = others[(i - 1 if dup_refs and i else i) % len(others)]
     if d.slice_type == N.SLICE_B:
         d.n_ref_l1 = n_ref_l1
         for i in range(n_ref_l1):
-            d.ref_slot_l1[i] = others[(len(others) - 1 - i) % len(others)]      # list 1 walks the store the other way round
-        d.weighted_bipred = int(rng.random() < 0.5) if weighted is None else int(bool(weighted))
+            d.ref_slot_l1[i] = others[(len(others) - 1 - (i - 1 if dup_refs and i else i)) % len(others)]      # list 1 walks the store the other way round
+        d.weighted_bipred = 0 if explicit_wp else int(rng.random() < 0.5) if weighted is None else int(bool(weighted))
         for i in range(N.MAX_REFS * N.MAX_REFS):                           # implicit weights: 64 - dist_scale_factor, -64 .. 128; often 32
             d.bipred_weight[i] = 32 if rng.random() < 0.3 else int(rng.integers(-64, 129))
     # slice structure: first macroblock of every slice and its deblocking idc (0 all edges, 1 none, 2 not across slices)
     starts = sorted(set([0] + [int(x) for x in rng.integers(1, max(n, 2), size=slices - 1)])) if slices > 1 and n > 1 else [0]
-    idcs = [int(rng.choice([0, 0, 2, 1])) for _ in starts]
+    idcs = [int(rng.choice([0, 0, 2, 1])) for _ in starts] if slice_idcs is None else [slice_idcs[k % len(slice_idcs)] for k in range(len(starts))]
     slice_of = np.zeros(n, np.int32)
     for k, s in enumerate(starts):
         slice_of[s:] = k
@@ -241,6 +247,13 @@ def make_picture(rng, mb_w, mb_h, *, p_picture=True, n_ref=1, slots=2, dst_slot=
                     else:
                         ref1[m, q] = int(rng.integers(0, n_ref_l1))
                 mv1[m] = c1.reshape(16, 2)
+            if past_list and not skip:
+                for q in range(4):
+                    if rng.random() < past_list:
+                        if ref[m, q] >= 0:
+                            ref[m, q] = int(rng.integers(d.n_ref, N.MAX_REFS))
+                        if ref1[m, q] >= 0:
+                            ref1[m, q] = int(rng.integers(d.n_ref_l1, N.MAX_REFS))
             cbp_l = 0 if skip else (int(rng.integers(0, 16)) if rng.random() < 0.6 else 0)
             for b in range(16):
                 if (cbp_l >> (b >> 2)) & 1 and rng.random() < 0.6:
@@ -270,7 +283,80 @@ def make_picture(rng, mb_w, mb_h, *, p_picture=True, n_ref=1, slots=2, dst_slot=
     d.n_coef_blocks = len(blocks)
     if blocks:
         pic.coefs = np.concatenate(blocks).astype(np.int16)
+    if explicit_wp and d.slice_type != N.SLICE_I:
+        draw_wp_table(rng, pic, explicit_wp, wp_denoms)
     return pic.seal()
+
+
+def bi_pairs(pic):
+    """the (list-0 entry, list-1 entry) pairs the bi-predicted quadrants of a B picture's inter macroblocks use (indices past a
+    list mapped to entry 0, as every road reads them)"""
+    d = pic.desc
+    if d.slice_type != N.SLICE_B:
+        return set()
+    inter = np.repeat(pic.rec["mb_type"] > N.MB_IPCM, 4)
+    r0, r1 = pic.ref_idx.astype(int), pic.ref_idx_l1.astype(int)
+    bi = inter & (r0 >= 0) & (r1 >= 0)
+    e0 = np.where(r0 < d.n_ref, r0, 0)
+    e1 = np.where(r1 < d.n_ref_l1, r1, 0)
+    return set(zip(e0[bi].tolist(), e1[bi].tolist()))
+
+
+def wp_limit_ok(w0, w1, denom):
+    """8.4.2.3: the constraint a stream keeps on the weights of the pairs its bi-predicted blocks use"""
+    return -128 <= w0 + w1 <= (127 if denom == 7 else 128)
+
+
+def draw_wp_table(rng, pic, mode="legal", denoms=None):
+    """An explicit weight table over the whole range p264hip_wp_check accepts: denominators 0 .. 7 per luma / chroma (denoms =
+    (luma, chroma) forces them), weights -128 .. 127 with both ends frequent and the inferred (2^denom, 0) - weight 128 at
+    denominator 7 - offsets -128 .. 127 with both ends frequent, each (list, entry, plane) drawn on its own; Cb and Cr of an entry
+    never equal.  mode "legal": the pairs bi-predicted blocks use keep -128 <= w0 + w1 <= (d == 7 ? 127 : 128) (list-1 weights
+    pulled into range, list 0 left as drawn); "wide": no such limit - the header gives every sum a defined result."""
+    d = pic.desc
+    den = [int(rng.integers(0, 8)), int(rng.integers(0, 8))] if denoms is None else [int(x) for x in denoms]
+    t = np.zeros((2, N.MAX_REFS, 3, 2), np.int64)
+    for l in range(2):
+        for i in range(N.MAX_REFS):
+            for c in range(3):
+                dd = den[min(c, 1)]
+                k = int(rng.integers(0, 8))
+                if k == 0:
+                    t[l, i, c] = (1 << dd, 0)                                 # inferred: no weights coded for this reference
+                    continue
+                w = [-128, 127, 1 << dd, -(1 << dd)][k - 1] if k <= 4 else int(rng.integers(-128, 128))
+                o = [-128, 127, 0][k % 3] if rng.random() < 0.5 else int(rng.integers(-128, 128))
+                t[l, i, c] = (w, o)
+            while tuple(t[l, i, 1]) == tuple(t[l, i, 2]):
+                t[l, i, 2, 1] = int(rng.integers(-128, 128))
+    if mode == "legal":
+        pairs = bi_pairs(pic)
+        for c in range(3):
+            dd = den[min(c, 1)]
+            for _ in range(8):
+                bad = [(a, b) for a, b in sorted(pairs) if not wp_limit_ok(int(t[0, a, c, 0]), int(t[1, b, c, 0]), dd)]
+                if not bad:
+                    break
+                for a, b in bad:
+                    w0 = int(t[0, a, c, 0])
+                    t[1, b, c, 0] = min(max(int(t[1, b, c, 0]), -128 - w0), (127 if dd == 7 else 128) - w0)
+            if any(not wp_limit_ok(int(t[0, a, c, 0]), int(t[1, b, c, 0]), dd) for a, b in pairs):
+                # (a list-1 weight shared by pairs of far-apart list-0 weights: every weight of the pairs into -64 .. 63)
+                for a, b in pairs:
+                    t[0, a, c, 0], t[1, b, c, 0] = min(max(int(t[0, a, c, 0]), -64), 63), min(max(int(t[1, b, c, 0]), -64), 63)
+            assert all(wp_limit_ok(int(t[0, a, c, 0]), int(t[1, b, c, 0]), dd) for a, b in pairs)
+        for l in range(2):
+            for i in range(N.MAX_REFS):
+                while tuple(t[l, i, 1]) == tuple(t[l, i, 2]):
+                    t[l, i, 2, 1] = int(rng.integers(-128, 128))
+    else:
+        assert mode == "wide", mode
+    t[:, :, :, 0] = np.clip(t[:, :, :, 0], -128, 128)
+    d.explicit_wp = 1
+    d.weighted_bipred = 0
+    d.wp_log2_denom[0], d.wp_log2_denom[1] = den
+    np.ctypeslib.as_array(d.wp)[:] = t.reshape(-1).astype(np.int16)
+    return den, t
 
 
 def random_frame(rng, mb_w, mb_h, kind="noise"):

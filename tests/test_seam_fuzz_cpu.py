@@ -1,6 +1,8 @@
 """CPU half of the seam fuzz: the random-picture builder (tests/seam_fuzz.py) produces well-formed p264hip_picture_t input -
 the oracle consumes it, the result is deterministic for a seed, and the packed coefficient stream is laid out as
 include/p264hip.h says.  (The comparison with the HIP kernels is tests/test_gpu_seam_fuzz.py.)"""
+import ctypes as C
+
 import numpy as np
 
 from p264decoder_amd import _native as N
@@ -66,3 +68,31 @@ def test_fuzz_configurations_reach_the_paths_they_are_meant_for(oracle):
         if kw.get("mirror_l1"):
             oracle.oracle_bs_by_picture.restype = C.c_longlong
             assert oracle.oracle_bs_by_picture() > 20, (name, oracle.oracle_bs_by_picture())
+
+
+def test_an_index_past_its_list_decodes_as_index_0(oracle):
+    """include/p264hip.h, ref_idx: an index at or past its list's length means entry 0 - prediction, implicit weights and the loop
+    filter (P pictures compare indices there) - so the oracle gives the same frame when every such index is rewritten to 0"""
+    from tests import wp_checker
+    for b_picture in (False, True):
+        rng = np.random.default_rng(44 + b_picture)
+        frames = [seam_fuzz.random_frame(rng, 8, 6, "smooth") for _ in range(4)]
+        past = 0
+        for i in range(4):
+            pic = seam_fuzz.make_picture(rng, 8, 6, n_ref=3, n_ref_l1=2, slots=4, dst_slot=i % 4, b_picture=b_picture, mv_range=12, past_list=0.3)
+            d = pic.desc
+            flat = wp_checker._Copy(pic)
+            past += int((flat.ref_idx >= d.n_ref).sum() + (flat.ref_idx_l1 >= d.n_ref_l1).sum())
+            flat.ref_idx[flat.ref_idx >= d.n_ref] = 0
+            flat.ref_idx_l1[flat.ref_idx_l1 >= d.n_ref_l1] = 0
+            got = []
+            for desc in (pic.desc, flat.desc):
+                store = oracle_bind.FrameStore(8, 6, 4)
+                for s in range(4):
+                    for dst, src in zip(store[s], frames[s]):
+                        dst[:] = src
+                oracle.oracle_reconstruct(C.byref(desc), store.ptrs)
+                got.append([p.copy() for p in store[d.dst_slot]])
+            for c in range(3):
+                assert np.array_equal(got[0][c], got[1][c]), "B %d picture %d plane %d" % (b_picture, i, c)
+        assert past > 40

@@ -1,6 +1,7 @@
 """Explicit weighted prediction on the host (H.264 7.3.3.2 / 7.4.3.2): the parser's pred_weight_table against what the stream
 writer meant (--dump-wp), the refusals, and the weight table's way through the slot layout and the compact link format."""
 import ctypes as C
+import itertools
 import os
 import subprocess
 
@@ -261,3 +262,110 @@ def test_checker_with_identity_weights_is_the_oracle(lib, oracle, tmp_path, args
         want = oracle_bind.reconstruct(oracle, ref, p)
         for c in range(3):
             assert np.array_equal(got[c], want[c]), "picture %d plane %d" % (k, c)
+
+
+def clip1(x):
+    return 0 if x < 0 else 255 if x > 255 else x
+
+
+def weighted_sample(p0, p1, w0, o0, w1, o1, log_wd, pred_l0, pred_l1):
+    """H.264 8.4.2.3.2 on Python integers, as the text states it (>> on a negative value rounds towards minus infinity, as in the
+    standard's arithmetic): one list - Clip1(((predPartLX * wX + 2^(logWD - 1)) >> logWD) + oX) for logWD >= 1, else
+    Clip1(predPartLX * wX + oX); both lists - Clip1(((predPartL0 * w0 + predPartL1 * w1 + 2^logWD) >> (logWD + 1)) + ((o0 + o1 + 1) >> 1))"""
+    if pred_l0 and pred_l1:
+        return clip1(((p0 * w0 + p1 * w1 + 2 ** log_wd) >> (log_wd + 1)) + ((o0 + o1 + 1) >> 1))
+    p, w, o = (p0, w0, o0) if pred_l0 else (p1, w1, o1)
+    if log_wd >= 1:
+        return clip1(((p * w + 2 ** (log_wd - 1)) >> log_wd) + o)
+    return clip1(p * w + o)
+
+
+def test_both_weighting_helpers_follow_the_standard():
+    """wp_checker._weigh and test_gpu_weighted_pred.weigh (the two numpy versions the GPU tests trust) against weighted_sample:
+    every logWD, the ends of the weight and offset ranges, the inferred 2^logWD and 128, weight sums past the 8.4.2.3 limit, and
+    samples at 0, 1, 127, 128, 254, 255 in both lists"""
+    from tests import test_gpu_weighted_pred, wp_checker
+    samples = [0, 1, 127, 128, 254, 255]
+    p0 = np.array([a for a in samples for _ in samples], np.int64).reshape(6, 6)
+    p1 = np.array([b for _ in samples for b in samples], np.int64).reshape(6, 6)
+    offsets = [-128, -1, 0, 1, 127]
+    past = 0
+    for d in range(8):
+        weights = sorted({-128, -127, -1, 0, 1, 1 << d, 127, 128})
+        for w0, o0 in itertools.product(weights, offsets):
+            # (one list: the other list's entry is another (weight, offset) - a helper that takes the wrong list's pair fails)
+            w1, o1 = (-w0 - 1 if w0 < 128 else -128), -o0 - 1
+            for l0, l1 in ((True, False), (False, True)):
+                want = np.array([[weighted_sample(int(a), int(b), w0, o0, w1, o1, d, l0, l1) for a, b in zip(ra, rb)] for ra, rb in zip(p0, p1)])
+                got = wp_checker._weigh(p0 if l0 else None, p1 if l1 else None, l0, l1, (w0, o0), (w1, o1), d)
+                assert np.array_equal(got, want), (d, w0, o0, l0)
+                assert np.array_equal(test_gpu_weighted_pred.weigh(p0, p1, l0, l1, (w0, o0), (w1, o1), d), want), (d, w0, o0, l0)
+            for w1, o1 in itertools.product(weights, offsets[::2]):
+                past += not -128 <= w0 + w1 <= (127 if d == 7 else 128)
+                want = np.array([[weighted_sample(int(a), int(b), w0, o0, w1, o1, d, True, True) for a, b in zip(ra, rb)] for ra, rb in zip(p0, p1)])
+                assert np.array_equal(wp_checker._weigh(p0, p1, True, True, (w0, o0), (w1, o1), d), want), (d, w0, o0, w1, o1)
+                assert np.array_equal(test_gpu_weighted_pred.weigh(p0, p1, True, True, (w0, o0), (w1, o1), d), want), (d, w0, o0, w1, o1)
+    assert past > 100
+
+
+@pytest.mark.parametrize("mode", ["legal", "wide"])
+def test_seam_fuzz_weight_tables(lib, mode):
+    """tests/seam_fuzz.draw_wp_table: tables p264hip_wp_check accepts, forced denominators kept, Cb and Cr of an entry never one
+    table, the 8.4.2.3 limit kept ("legal") or broken ("wide") on the pairs bi-predicted blocks use, both ends of the ranges drawn"""
+    from tests import seam_fuzz
+    rng = np.random.default_rng(5 if mode == "legal" else 6)
+    ends, broken = set(), 0
+    for i in range(12):
+        den = (i % 8, 7 - i % 8)
+        pic = seam_fuzz.make_picture(rng, 6, 4, n_ref=3, n_ref_l1=3, slots=4, b_picture=i % 3 != 0, explicit_wp=mode, wp_denoms=den,
+                                     dup_refs=i % 2 == 1, past_list=0.2)
+        d = pic.desc
+        assert lib.p264hip_wp_check(C.byref(d)) == 0 and d.explicit_wp == 1 and d.weighted_bipred == 0
+        assert (d.wp_log2_denom[0], d.wp_log2_denom[1]) == den
+        t = np.ctypeslib.as_array(d.wp).reshape(2, 16, 3, 2).astype(int)
+        assert all(tuple(t[l, k, 1]) != tuple(t[l, k, 2]) for l in range(2) for k in range(16))
+        ends |= {int(w) for w in t[..., 0].reshape(-1) if abs(w) >= 127} | {("o", int(o)) for o in t[..., 1].reshape(-1) if o in (-128, 127)}
+        for a, b in seam_fuzz.bi_pairs(pic):
+            for c in range(3):
+                broken += not seam_fuzz.wp_limit_ok(int(t[0, a, c, 0]), int(t[1, b, c, 0]), den[min(c, 1)])
+        if i % 2 == 1:
+            assert d.ref_slot[0] == d.ref_slot[1] and not np.array_equal(t[0, 0], t[0, 1])
+    assert ends >= {-128, 127, 128, ("o", -128), ("o", 127)}, ends
+    assert (broken == 0) if mode == "legal" else (broken > 10), broken
+
+
+@pytest.mark.parametrize("b_picture", [False, True])
+def test_checker_with_identity_weights_is_the_oracle_on_seam_pictures(lib, oracle, b_picture):
+    """as test_checker_with_identity_weights_is_the_oracle, on seam-fuzz pictures no stream carries: intra macroblocks, three
+    slices with deblocking idc 2, 0 and 1, sub-4x4 partitions, int16-wrapping levels and indices past their list - steps 2 and 3
+    of the checker (the oracle's residual after a prediction from S, its loop filter with the picture's own motion) proven on them.
+    The oracle gets the indices as drawn: past the list it predicts and filters from entry 0 like the checker."""
+    from tests import oracle_bind, seam_fuzz, wp_checker
+    rng = np.random.default_rng(31 + b_picture)
+    mb_w, mb_h, slots = 7, 5, 5
+    chk = wp_checker.WeightedChecker(oracle, mb_w, mb_h, slots)
+    ref = oracle_bind.FrameStore(mb_w, mb_h, slots)
+    for s in range(slots):
+        f = seam_fuzz.random_frame(rng, mb_w, mb_h, "smooth")
+        for a, b, src in zip(chk.store[s], ref[s], f):
+            a[:] = src
+            b[:] = src
+    past = 0
+    for i in range(6):
+        pic = seam_fuzz.make_picture(rng, mb_w, mb_h, p_picture=i != 2, dst_slot=i % slots, n_ref=3, n_ref_l1=2, slots=slots, b_picture=b_picture,
+                                     level_style="mixed", qp_mode="random", intra_share=0.3, slices=3, slice_idcs=[2, 0, 1], mv_range=20,
+                                     explicit_wp="wide", past_list=0.25)
+        d = pic.desc
+        if d.slice_type != N.SLICE_I:
+            t = np.ctypeslib.as_array(d.wp).reshape(2, 16, 3, 2)
+            for c in range(3):
+                t[:, :, c] = (1 << d.wp_log2_denom[min(c, 1)], 0)
+        past += int((pic.ref_idx >= d.n_ref).sum())
+        plain = wp_checker._Copy(pic)
+        plain.desc.explicit_wp = 0
+        got = chk.reconstruct(pic)
+        oracle.oracle_reconstruct(C.byref(plain.desc), ref.ptrs)
+        want = ref[d.dst_slot]
+        for c in range(3):
+            assert np.array_equal(got[c], want[c]), "picture %d plane %d" % (i, c)
+    assert past > 20

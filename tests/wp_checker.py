@@ -23,13 +23,20 @@ def _bind(oracle):
         getattr(oracle, f).restype = None
 
 
-def _weigh(p0, p1, use0, use1, e0, e1, d):
-    """8.4.2.3.2; p0 / p1 int64 arrays (None where the list is unused), e = (weight, offset)"""
+def _weigh(p0, p1, use0, use1, e0, e1, d, stats=None):
+    """8.4.2.3.2; p0 / p1 int64 arrays (None where the list is unused), e = (weight, offset).  stats: a dict whose counters
+    'clip_low' / 'clip_high' (samples the final Clip1 moved) and 'bi_past_limit' (bi-predicted blocks whose weight sum is outside
+    -128 .. (d == 7 ? 127 : 128)) are raised"""
     if use0 and use1:
         v = ((p0 * e0[0] + p1 * e1[0] + (1 << d)) >> (d + 1)) + ((e0[1] + e1[1] + 1) >> 1)
     else:
         p, (w, o) = (p0, e0) if use0 else (p1, e1)
         v = (((p * w + (1 << (d - 1))) >> d) + o) if d >= 1 else p * w + o
+    if stats is not None:
+        stats["clip_low"] = stats.get("clip_low", 0) + int((v < 0).sum())
+        stats["clip_high"] = stats.get("clip_high", 0) + int((v > 255).sum())
+        if use0 and use1 and not -128 <= int(e0[0]) + int(e1[0]) <= (127 if d == 7 else 128):
+            stats["bi_past_limit"] = stats.get("bi_past_limit", 0) + 1
     return np.clip(v, 0, 255).astype(np.uint8)
 
 
@@ -70,8 +77,8 @@ class WeightedChecker:
         fn(plane.ctypes.data, w, h, x, y, mvx, mvy, n, n, out.ctypes.data, n)
         return out.astype(np.int64)
 
-    def predict(self, pic):
-        """step 1: the weighted predictions of every inter block into S"""
+    def predict(self, pic, stats=None):
+        """step 1: the weighted predictions of every inter block into S (stats: see _weigh)"""
         d = pic.desc
         is_b = d.slice_type == N.SLICE_B
         recs = pic.mb_records()
@@ -88,8 +95,8 @@ class WeightedChecker:
                 r1 = int(pic.ref_idx_l1[m * 4 + q]) if is_b else -1
                 use1 = r1 >= 0
                 use0 = r0 >= 0 or not use1
-                i0 = min(max(r0, 0), d.n_ref - 1)
-                i1 = min(max(r1, 0), d.n_ref_l1 - 1) if use1 else 0
+                i0 = r0 if 0 <= r0 < d.n_ref else 0                 # (negative or past the list: entry 0, include/p264hip.h)
+                i1 = r1 if use1 and r1 < d.n_ref_l1 else 0
                 X, Y = mbx * 16 + bx * 4, mby * 16 + by * 4
                 v0 = pic.mv[(m * 16 + b) * 2:(m * 16 + b) * 2 + 2]
                 v1 = pic.mv_l1[(m * 16 + b) * 2:(m * 16 + b) * 2 + 2] if is_b else (0, 0)
@@ -97,14 +104,14 @@ class WeightedChecker:
                     n, x, y = (4, X, Y) if c == 0 else (2, X // 2, Y // 2)
                     p0 = self._mc(d.ref_slot[i0], c, x, y, int(v0[0]), int(v0[1]), n) if use0 else None
                     p1 = self._mc(d.ref_slot_l1[i1], c, x, y, int(v1[0]), int(v1[1]), n) if use1 else None
-                    S[c][y:y + n, x:x + n] = _weigh(p0, p1, use0, use1, tab[0, i0, c], tab[1, i1, c], d.wp_log2_denom[min(c, 1)])
+                    S[c][y:y + n, x:x + n] = _weigh(p0, p1, use0, use1, tab[0, i0, c], tab[1, i1, c], d.wp_log2_denom[min(c, 1)], stats)
 
-    def reconstruct(self, pic):
+    def reconstruct(self, pic, stats=None):
         """the picture as a decoder with explicit weights makes it; returns its planes (views into the store)"""
         d = pic.desc
         if not d.explicit_wp:
             return oracle_bind.reconstruct(self.oracle, self.store, pic)
-        self.predict(pic)
+        self.predict(pic, stats)
         # step 2: list 0, index 0 = S, vector 0, for every inter macroblock
         flat = _Copy(pic)
         inter = np.repeat(pic.mb_records()["mb_type"] > N.MB_IPCM, 4)
@@ -121,7 +128,7 @@ class WeightedChecker:
             if not mapped.is_b:
                 slots = [d.ref_slot[j] for j in range(d.n_ref)]
                 for i, r in enumerate(mapped.ref_idx):
-                    if 0 <= r < d.n_ref:
-                        mapped.ref_idx[i] = slots.index(slots[r])
+                    if r >= 0:
+                        mapped.ref_idx[i] = slots.index(slots[r if r < d.n_ref else 0])
             self.oracle.oracle_deblock_picture(C.byref(mapped.desc), self.store.ptrs)
         return self.store[d.dst_slot]
