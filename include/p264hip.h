@@ -33,7 +33,8 @@ extern "C" {
 enum {
     P264_MB_I4x4   = 0,
     P264_MB_I16x16 = 1,
-    P264_MB_IPCM   = 2,   /* reserved: rejected by the reference (decoder/macroblock.c:510-514) */
+    P264_MB_IPCM   = 2,   /* I_PCM: 384 samples instead of levels, see P264_IPCM_COEF_MASK (the reference rejects the type,
+                             decoder/macroblock.c:510-514: H.264 7.3.5, 8.3.5) */
     P264_MB_P_L0   = 3,   /* 16x16, 16x8, 8x16 */
     P264_MB_P_8x8  = 4,
     P264_MB_P_SKIP = 5,
@@ -57,6 +58,18 @@ enum {
 #define P264_COEF_LUMA_DC   (1u << 24)   /* Intra16x16 DC block present (16 levels, zig-zag order) */
 #define P264_COEF_CHROMA_DC (1u << 25)   /* one packed block: Cb DC[0..3], Cr DC[4..7] (raster 2x2) */
 
+/* An I_PCM macroblock (mb_type P264_MB_IPCM, in a picture of any slice type) carries its samples where other macroblocks
+ * carry levels: TWELVE consecutive 32-byte blocks of coefs[] from coef_index, read as 384 bytes in bitstream order - 256 luma
+ * (raster, 16 per row), 64 Cb, 64 Cr (raster, 8 per row).  Its record: coef_mask = P264_IPCM_COEF_MASK exactly (popcount 12: the
+ * range rule "coef_index + popcount(coef_mask & 0x3ffffff) <= n_coef_blocks" covers the samples as it covers levels, and so do
+ * the compact format's per-block sums), qp = 0 (H.264 8.7.2.2: the loop filter treats its edges with qPp = 0; the filter reads
+ * the record's qp), cbp = 0, intra_modes = 0, flags = 0; ref_idx -1, vectors 0, the sixteen i4modes 2, like every macroblock
+ * that is not Intra4x4.  avail and edges mean what they mean everywhere.  Every road into an input slot (p264hip_upload,
+ * p264hip_pack_input, p264hip_pack_compact, p264hip_compact_check, the device check behind p264hip_input_commit) rejects an
+ * I_PCM record with any other mask: the kernels read twelve blocks whatever the mask says. */
+#define P264_IPCM_COEF_MASK 0x00000fffu
+#define P264_IPCM_BLOCKS    12
+
 /* One per macroblock, 16 bytes.  Everything is as parsed (before dequantisation). */
 typedef struct p264hip_mb {
     uint8_t  mb_type;      /* P264_MB_* */
@@ -65,7 +78,7 @@ typedef struct p264hip_mb {
     uint8_t  intra_modes;  /* bits 0-1 intra16x16_pred_mode, bits 4-5 intra_chroma_pred_mode (as coded) */
     uint32_t coef_mask;    /* bit b<24: 4x4 block b has total_coeff>0 (0-15 luma in decode order
                               core/macroblock.h:194-201, 16-19 Cb, 20-23 Cr); | P264_COEF_* */
-    uint32_t coef_index;   /* index, in 16-level blocks, of this MB's first packed block */
+    uint32_t coef_index;   /* index, in 16-level blocks, of this MB's first packed block (I_PCM: of its first sample block) */
     uint8_t  avail;        /* P264_AVAIL_*: neighbouring MBs usable for intra prediction
                               (core/macroblock.c:926-1033; picture border / slice membership) */
     uint8_t  edges;        /* P264_EDGE_*: which MB edges the loop filter touches (core/frame.c:524) */

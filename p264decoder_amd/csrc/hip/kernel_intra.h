@@ -142,6 +142,14 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
     const unsigned mask = rec.y;
     const int16_t *cf = pd->coefs + (size_t)rec.z * 16;
     const bool is16 = mb_type == P264_MB_I16x16;
+    // ---- I_PCM (H.264 8.3.5): the macroblock's twelve blocks of coefs[] ARE its samples (p264hip.h), lane l copies row l into
+    //      the strip layout - no neighbours, no tile, no residual.  A test per group, in front of everything: the groups of a
+    //      wavefront that hold other types run on as before (the sparse lists and the band walk hand this function mixed
+    //      types anyway), and a wavefront without an I_PCM macroblock skips the two instructions with one branch. ----
+    if (mb_type == P264_MB_IPCM) {
+        gstore4(F + mb_luma_off(g, mbx, mby) + l * 16, gload4((const uint8_t *)cf + l * 16));
+        return;
+    }
 
     // ---- (a) neighbour samples, 128 where the neighbour does not exist: lane l the left sample of row l; lanes 0..3 the
     //      four dwords of the row above, lane 4 the top-right dword, lane 5 the corner ----
@@ -318,6 +326,11 @@ __device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, I
     const int16_t *cf = pd->coefs + (size_t)rec.z * 16;
     const int p = l >> 3, r = l & 7;
     uint8_t *tile = L.tile + p * (9 * CT_STRIDE);
+    // ---- I_PCM: lane (p, r) copies the eight samples of its row from behind the 256 luma bytes (as in intra_luma4) ----
+    if ((int)(rec.x & 255u) == P264_MB_IPCM) {
+        gstore2(F + mb_chroma_off(g, mbx, mby) + r * 16 + p * 8, gload2((const uint8_t *)cf + 256 + p * 64 + r * 8));
+        return;
+    }
 
     // ---- neighbours: lane (p, r) the left sample of its row; r = 0, 1 the two dwords of the row above, r = 2 the corner ----
     int vL = 128;
@@ -413,7 +426,8 @@ __device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, I
 #define INTRA_BAND 4                // macroblock rows per wavefront = groups of sixteen lanes
 // P / B pictures: intra macroblocks without an intra neighbour to the left or above depend on nothing this kernel writes.
 // They are collected first (two lists, by macroblock type, so that the four macroblocks of an iteration run the same code)
-// and reconstructed four at a time in any order; only the rest goes through the ordered band walk below.
+// and reconstructed four at a time in any order; only the rest goes through the ordered band walk below.  (I_PCM macroblocks
+// ride on the Intra4x4 list: they are told apart per group inside intra_luma4 / intra_chroma4, where they are a copy.)
 #ifndef INTRA_ROUNDS
 #define INTRA_ROUNDS     2          // rounds of ready macroblocks before the ordered band walk takes what is left (measured on the
                                     // bench stream: 1 / 2 / 3 and more rounds 0.46 / 0.33 / 0.37 ms per launch)

@@ -99,6 +99,7 @@ __global__ void k_check_records(const p264hip_mb_t *mb, int n_mb, uint32_t n_coe
     if (i >= n_mb) return;
     const uint4 r = gload4(mb + i);
     if (r.y && (uint64_t)r.z + (uint64_t)__popc(r.y & 0x3ffffffu) > (uint64_t)n_coef_blocks) atomicOr(bad, 1);
+    if ((r.x & 255u) == P264_MB_IPCM && r.y != P264_IPCM_COEF_MASK) atomicOr(bad, 1);       // (the intra kernels read twelve blocks of samples)
 }
 
 struct p264hip_ctx {
@@ -278,6 +279,8 @@ static int check_pic(p264hip_ctx *c, const p264hip_picture_t *p, bool arrays)
         if (m.coef_mask && (uint64_t)m.coef_index + (uint64_t)__builtin_popcount(m.coef_mask & 0x3ffffffu) > p->n_coef_blocks)
             return fail(P264HIP_EINVAL, "macroblock %d: coefficient blocks [%u, +%d) outside coefs[%u]", i, m.coef_index,
                         __builtin_popcount(m.coef_mask & 0x3ffffffu), p->n_coef_blocks);
+        if (m.mb_type == P264_MB_IPCM && m.coef_mask != P264_IPCM_COEF_MASK)
+            return fail(P264HIP_EINVAL, "macroblock %d: I_PCM with coef_mask 0x%x (its twelve sample blocks are 0x%x)", i, m.coef_mask, P264_IPCM_COEF_MASK);
     }
     return 0;
 }

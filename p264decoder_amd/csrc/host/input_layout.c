@@ -46,6 +46,7 @@ int64_t p264hip_pack_input(const p264hip_picture_t *p, void *dst_, size_t cap)
     for (size_t i = 0; i < n; i++) {
         const p264hip_mb_t *m = &p->mb[i];
         if (m->coef_mask && (uint64_t)m->coef_index + (uint64_t)__builtin_popcount(m->coef_mask & 0x3ffffffu) > p->n_coef_blocks) return P264HIP_EINVAL;
+        if (m->mb_type == P264_MB_IPCM && m->coef_mask != P264_IPCM_COEF_MASK) return P264HIP_EINVAL;   /* (the kernels read twelve blocks of samples) */
     }
     uint8_t *dst = (uint8_t *)dst_;
     memcpy(dst + L.off_mb, p->mb, n * sizeof(p264hip_mb_t));

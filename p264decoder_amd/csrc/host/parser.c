@@ -932,6 +932,57 @@ static void decode_pskip(p264parse *p)
     if (p->cabac_on) p->cinfo[p->mbi] |= CI_SKIP;
 }
 
+/* I_PCM (H.264 7.3.5, 8.3.5): pcm_alignment_zero_bits, then 384 sample bytes that go into the macroblock's place in coefs[] in one
+ * piece - twelve 32-byte blocks, luma, Cb, Cr as the stream has them (include/p264hip.h).  The reference stops here
+ * (decoder/macroblock.c:510-514).  For later macroblocks it counts as coded everywhere: total_coeff 16 in all 24 blocks (9.2.1),
+ * every coded_block_flag 1 and coded_block_pattern 0x2f (9.3.3.1.1.9 / .4: cb_cbp asks nb_cbp), no mb_qp_delta (the next one's
+ * context sees a delta of 0) and the QP chain untouched.  Its record carries qp 0: what the loop filter takes for it (8.7.2.2).
+ * CAVLC: the samples lie at the next byte boundary of the bit reader.  CABAC: the terminate bin in front of them came back 1 and
+ * the encoder has flushed as at the end of a slice (9.3.4.5: ten bits, the last of them a 1).  Where a bit-serial decoder stands
+ * then is pos * 8 - n (what p264cabac_bits_left counts with), and that is the bit BEHIND the flush's last one: measured at the
+ * end of every CABAC slice of the golden and test streams, where the same flush ends in the rbsp_stop_one_bit - pos * 8 - n was
+ * rbsp_stop_bit() + 1 in all of them.  So the alignment zeros start at pos * 8 - n, the samples at the next
+ * byte boundary, and the engine starts again behind them (9.3.1.2) with every context state kept. */
+static int parse_ipcm(p264parse *p, bitrd_t *b, p264hip_mb_t *m)
+{
+    picbuf_t *q = &p->buf[p->cur];
+    const uint8_t *src;
+    if (p->cabac_on) {
+        p264cabac_t *c = &p->cb;
+        const int64_t bit = (int64_t)c->pos * 8 - c->n;          /* the first bit behind the flush */
+        if (bit < 0 || bit > (int64_t)c->size * 8) { ERR(p, "macroblock overruns the slice data"); return -1; }
+        const size_t at = (size_t)((bit + 7) >> 3);
+        for (int64_t k = bit; k < (int64_t)at * 8; k++)
+            if ((c->data[k >> 3] >> (7 - (k & 7))) & 1) { ERR(p, "pcm_alignment_zero_bit is not zero"); return -1; }
+        /* (behind the samples the engine needs something to start on: at least end_of_slice_flag follows) */
+        if (at + 384 >= c->size) { ERR(p, "macroblock overruns the slice data"); return -1; }
+        src = c->data + at;
+        p264cabac_start(c, src + 384, c->size - at - 384);
+        p->cinfo[p->mbi] |= CI_DC_Y | CI_DC_CB | CI_DC_CR;
+    } else {
+        const int pad = (int)((0 - br_consumed(b)) & 7);
+        if (pad && br_u(b, pad)) { ERR(p, "pcm_alignment_zero_bit is not zero"); return -1; }
+        const size_t at = br_consumed(b) >> 3;
+        if (br_overrun(b) || at + 384 > b->size) { ERR(p, "macroblock overruns the slice data"); return -1; }
+        src = b->buf + at;
+        b->pos = at + 384; b->win = 0; b->avail = 0;            /* the bit reader goes on behind the samples */
+        br_refill(b);
+    }
+    if (coef_reserve(q, P264_IPCM_BLOCKS) < 0) return -1;
+    memcpy(q->coef + q->coef_n * 16, src, 384);
+    m->mb_type = P264_MB_IPCM;                                   /* qp, cbp, intra_modes, flags: 0 (begin_mb) */
+    m->coef_mask = P264_IPCM_COEF_MASK;
+    m->coef_index = (uint32_t)q->coef_n;
+    q->coef_n += P264_IPCM_BLOCKS;
+    memset(q->ref + p->mbi * 4, -1, 4);
+    memset(q->mv + p->mbi * 32, 0, 64);
+    if (q->mv1) { memset(q->ref1 + p->mbi * 4, -1, 4); memset(q->mv1 + p->mbi * 32, 0, 64); }
+    memset(q->i4 + p->mbi * 16, 2, 16);
+    memset(p->nnz + (size_t)p->mbi * 24, 16, 24);
+    p->last_dqp = 0;
+    return 0;
+}
+
 /* t: mb_type as read (P slices), intra_t >= 0: the macroblock is intra with that I-slice type (I slices; P / B slices after
  * their offset of 5 / 23) */
 static int parse_mb_t(p264parse *p, bitrd_t *b, unsigned t, int intra_t)
@@ -946,7 +997,7 @@ static int parse_mb_t(p264parse *p, bitrd_t *b, unsigned t, int intra_t)
     if (intra_t >= 0) {
         /* ---- intra (decoder/macroblock.c:117-139, 265-301) ---- */
         if (intra_t > 25) { ERR(p, "invalid mb type %d", intra_t); return -1; }
-        if (intra_t == 25) { ERR(p, "unsupport i_pcm mb"); return -1; }
+        if (intra_t == 25) return parse_ipcm(p, b, m);
         memset(ref, -1, 4);
         memset(q->mv + p->mbi * 32, 0, 64);
         if (q->mv1) { memset(q->ref1 + p->mbi * 4, -1, 4); memset(q->mv1 + p->mbi * 32, 0, 64); }

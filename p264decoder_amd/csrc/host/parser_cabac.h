@@ -180,20 +180,22 @@ static int cb_chroma_pred_mode(p264parse *p)
     if (!p264cabac_decision(c, 64 + 3)) return 1;
     return p264cabac_decision(c, 64 + 3) ? 3 : 2;
 }
+/* coded_block_pattern of a neighbour as the contexts see it: an I_PCM macroblock counts as all coded (its record says 0) */
+static inline int nb_cbp(const p264hip_mb_t *m) { return m->mb_type == P264_MB_IPCM ? 0x2f : m->cbp; }
 static int cb_cbp(p264parse *p)
 {
     const picbuf_t *q = &p->buf[p->cur];
     p264cabac_t *c = &p->cb;
     /* neighbours' patterns; an unavailable neighbour counts as "coded" for luma (condition 0) and "not coded" for chroma */
     const int L = cb_left(p) != 0, T = cb_top(p) != 0;
-    const int cl = L ? q->mb[p->mbi - 1].cbp : 0x0f, ct = T ? q->mb[p->mbi - p->mb_w].cbp : 0x0f;
+    const int cl = L ? nb_cbp(&q->mb[p->mbi - 1]) : 0x0f, ct = T ? nb_cbp(&q->mb[p->mbi - p->mb_w]) : 0x0f;
     int cbp = 0;
     for (int b8 = 0; b8 < 4; b8++) {
         const int a = (b8 & 1) ? (cbp >> (b8 - 1)) & 1 : (cl >> (b8 + 1)) & 1;         /* left 8x8: inside this macroblock, or the left one's right column */
         const int b = (b8 & 2) ? (cbp >> (b8 - 2)) & 1 : (ct >> (b8 + 2)) & 1;         /* upper 8x8 */
         cbp |= p264cabac_decision(c, 73 + !a + 2 * !b) << b8;
     }
-    const int ccl = L ? q->mb[p->mbi - 1].cbp >> 4 : 0, cct = T ? q->mb[p->mbi - p->mb_w].cbp >> 4 : 0;
+    const int ccl = L ? nb_cbp(&q->mb[p->mbi - 1]) >> 4 : 0, cct = T ? nb_cbp(&q->mb[p->mbi - p->mb_w]) >> 4 : 0;
     if (p264cabac_decision(c, 77 + (ccl != 0) + 2 * (cct != 0)))
         cbp |= (1 + p264cabac_decision(c, 77 + 4 + (ccl == 2) + 2 * (cct == 2))) << 4;
     return cbp;

@@ -58,6 +58,14 @@ class ParsedPicture:
                        ("coef_mask", "<u4"), ("coef_index", "<u4"), ("avail", "u1"), ("edges", "u1"), ("flags", "<u2")])
         return self.mb.view(dt)
 
+    def ipcm_macroblocks(self):
+        """The picture's I_PCM macroblocks: a list of (macroblock index, its 384 sample bytes: 256 luma, 64 Cb, 64 Cr) -
+        the twelve blocks of coefs[] at the record's coef_index (include/p264hip.h)."""
+        raw = self.coefs.view(np.uint8)
+        r = self.mb_records()
+        return [(int(i), raw[int(r["coef_index"][i]) * 32:int(r["coef_index"][i]) * 32 + 384].copy())
+                for i in np.flatnonzero(r["mb_type"] == N.MB_IPCM)]
+
 
 class Parser:
     """p264parse_* : NAL units in, complete parsed pictures out (CPU, serial by nature)."""

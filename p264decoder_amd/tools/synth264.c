@@ -107,7 +107,7 @@ static void write_nal(FILE *f, int ref_idc, int type, const bw_t *b)
 }
 
 /* ---------------------------------------------------------------- stream state ---------- */
-enum { T_I4 = 0, T_I16 = 1, T_P = 3, T_P8 = 4, T_SKIP = 5 };
+enum { T_I4 = 0, T_I16 = 1, T_PCM = 2, T_P = 3, T_P8 = 4, T_SKIP = 5 };
 static int W, H, NMB;                       /* in macroblocks */
 static int opt_qp = 26, opt_coded = 12, opt_maxlevel = 32, opt_mvmax = 64, opt_cqo = 0, opt_deblock = 1, opt_refs = 1;
 static int n_active = 1;                    /* num_ref_idx_l0_active of the current slice */
@@ -198,7 +198,7 @@ static nb_t nb_motion_l(int x4, int y4, int l)
     int i = (y4 >> 2) * W + (x4 >> 2), sub = (y4 & 3) * 4 + (x4 & 3);
     if (i == cur) { if (!(((l ? mv_done1 : mv_done) >> sub) & 1)) return r; }
     else if (i > cur || i < slice_first) return r;
-    if (i != cur && mb_type[i] <= T_I16) { r.ref = -1; return r; }
+    if (i != cur && mb_type[i] <= T_PCM) { r.ref = -1; return r; }
     const int8_t *rf = l ? refs1 : refs; const int16_t *mv = l ? mvs1 : mvs;
     r.ref = rf[i * 16 + sub]; r.x = mv[(i * 16 + sub) * 2]; r.y = mv[(i * 16 + sub) * 2 + 1];
     return r;
@@ -464,6 +464,36 @@ static void put_intra(bw_t *b, int mbx, int mby, int type_offset)
     else { memset(nnz + (size_t)cur * 24, 0, 24); w_last_dqp = 0; }
 }
 
+/* I_PCM (--ipcm PCT): mb_type 25 in I-slice numbering, alignment, 384 sample bytes.  With CABAC the type's terminate bin is 1 and
+ * flushes the encoder as at the end of a slice (ce_intra_type), and the encoder starts again behind the samples (9.3.4.1) with
+ * its context states kept.  For the macroblocks that follow it counts as coded everywhere: 16 coefficients per block, every
+ * coded_block_flag 1, coded_block_pattern 0x2f, chroma mode 0, no mb_qp_delta. */
+static int opt_ipcm = 0, opt_ipcm_style = 0;    /* style: 0 noise, 1 flat (runs of 0x00 / 0xff / 0x03: emulation prevention inside the samples), 2 edge */
+static FILE *dump_pcm;                          /* --dump-pcm: per picture a count, then per I_PCM macroblock its index and its 384 bytes */
+static uint32_t *pcm_idx; static uint8_t *pcm_bytes; static int pcm_n;
+static void put_ipcm(bw_t *b, int type_offset)
+{
+    uint8_t *px = pcm_bytes + (size_t)pcm_n * 384;
+    pcm_idx[pcm_n++] = (uint32_t)cur;
+    if (opt_ipcm_style == 1) {
+        static const uint8_t runs[3] = { 0x00, 0xff, 0x03 };
+        for (int i = 0; i < 384; ) { const uint8_t v = runs[rnd(3)]; for (int n = 3 + rnd(38); n > 0 && i < 384; n--) px[i++] = v; }
+    } else if (opt_ipcm_style == 2) {
+        static const uint8_t lv[4] = { 0, 255, 128, 127 };
+        for (int i = 0; i < 384; ) { const uint8_t v = lv[rnd(4)]; for (int n = 1 + rnd(6); n > 0 && i < 384; n--) px[i++] = v; }
+    } else for (int i = 0; i < 384; i++) px[i] = (uint8_t)rnd(256);
+    mb_type[cur] = T_PCM;
+    memset(i4m + cur * 16, 2, 16);
+    memset(mvs + cur * 32, 0, 64);
+    memset(refs + cur * 16, -1, 16);
+    memset(nnz + (size_t)cur * 24, 16, 24);
+    w_cbp[cur] = 0x2f; w_cmode[cur] = 0; w_dc[cur] = 7; w_last_dqp = 0;
+    sx_mb_type(b, type_offset + 25);
+    while (b->nacc) bw_put(b, 1, 0);                        /* pcm_alignment_zero_bit */
+    for (int i = 0; i < 384; i++) bw_byte(b, px[i]);
+    if (opt_cabac) { ce.low = 0; ce.range = 510; ce.outstanding = 0; ce.first = 1; }
+}
+
 /* try to write a non-skipped inter MB; returns 0 if no legal vectors were found */
 static void put_inter(bw_t *b, int mbx, int mby)
 {
@@ -686,14 +716,17 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
             w_begin_mb();
             if (opt_bframes) { memset(refs1 + cur * 16, -1, 16); memset(mvs1 + cur * 32, 0, 64); }
             int skipped = 0, k = 0;
-            if (is_b) { k = rnd(100); if (k < 18) { b_skip(mbx, mby); skipped = 1; } }
+            const int pcm = opt_ipcm && pct(opt_ipcm);      /* (no number drawn without --ipcm: every other stream stays as it was) */
+            if (pcm) { }
+            else if (is_b) { k = rnd(100); if (k < 18) { b_skip(mbx, mby); skipped = 1; } }
             else if (is_p) { k = rnd(100); if (k < 20 && try_skip(mbx, mby)) skipped = 1; }
             if (is_b || is_p) {
                 if (opt_cabac) sx_mb_skip(&b, skipped);
                 else if (skipped) skip_run++;
                 else { bw_ue(&b, (uint32_t)skip_run); skip_run = 0; }
             }
-            if (!skipped) {
+            if (pcm) put_ipcm(&b, is_b ? 23 : is_p ? 5 : 0);
+            else if (!skipped) {
                 if (is_b) { if (k >= 95) put_intra(&b, mbx, mby, 23); else put_b_mb(&b, mbx, mby); }
                 else if (is_p) { if (k >= 96) put_intra(&b, mbx, mby, 5); else put_inter(&b, mbx, mby); }
                 else put_intra(&b, mbx, mby, 0);
@@ -709,6 +742,12 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
         free(b.buf);
     }
     slice_first = 0;
+    if (dump_pcm) {
+        const uint32_t n = (uint32_t)pcm_n;
+        fwrite(&n, 4, 1, dump_pcm);
+        for (int i = 0; i < pcm_n; i++) { fwrite(&pcm_idx[i], 4, 1, dump_pcm); fwrite(pcm_bytes + (size_t)i * 384, 1, 384, dump_pcm); }
+    }
+    pcm_n = 0;
     if (dump_wp) {
         int16_t rec[3 + 2 * 16 * 3 * 2];
         memset(rec, 0, sizeof rec);
@@ -781,6 +820,9 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--wp-identity")) opt_wp_identity = 1;
         else if (!strcmp(a, "--wp-slice-differ")) opt_wp_differ = 1;
         else if (!strcmp(a, "--wp-bad-sum")) opt_wp_bad_sum = 1;
+        else if (!strcmp(a, "--ipcm")) { opt_ipcm = v < 0 ? 0 : v > 100 ? 100 : v; i++; }
+        else if (!strcmp(a, "--ipcm-style")) { const char *st = i + 1 < argc ? argv[i + 1] : ""; opt_ipcm_style = !strcmp(st, "flat") ? 1 : !strcmp(st, "edge") ? 2 : 0; i++; }
+        else if (!strcmp(a, "--dump-pcm")) { dump_pcm = fopen(argv[i + 1], "wb"); i++; }
         else if (!strcmp(a, "--dump-wp")) { dump_wp = fopen(argv[i + 1], "wb"); i++; }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
@@ -788,6 +830,7 @@ int main(int argc, char **argv)
     NMB = W * H;
     g_rng = seed * 0x9e3779b97f4a7c15ull + 264;
     w_alloc();
+    if (opt_ipcm) { pcm_idx = calloc((size_t)NMB, 4); pcm_bytes = malloc((size_t)NMB * 384); }
     mb_type = calloc((size_t)NMB, 1); mvs = calloc((size_t)NMB * 32, 2); nnz = calloc((size_t)NMB, 24); i4m = calloc((size_t)NMB, 16); refs = calloc((size_t)NMB, 16);
     FILE *f = fopen(argv[1], "wb");
     if (!f) { perror(argv[1]); return 2; }
@@ -834,6 +877,7 @@ int main(int argc, char **argv)
         fclose(f);
         if (dump_mv) fclose(dump_mv);
         if (dump_wp) fclose(dump_wp);
+        if (dump_pcm) fclose(dump_pcm);
         return 0;
     }
     for (int n = 0; n < frames; n++) {
@@ -849,5 +893,6 @@ int main(int argc, char **argv)
     fclose(f);
     if (dump_mv) fclose(dump_mv);
     if (dump_wp) fclose(dump_wp);
+    if (dump_pcm) fclose(dump_pcm);
     return 0;
 }

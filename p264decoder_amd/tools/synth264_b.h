@@ -226,7 +226,7 @@ static void b_save_col(wdpb_t *e, int is_intra_picture)
 {
     if (!e->cmv) { e->cmv = calloc((size_t)NMB * 32, 2); e->cref = malloc((size_t)NMB * 16); e->cpic = malloc((size_t)NMB * 16 * sizeof(int)); }
     for (int i = 0; i < NMB * 16; i++) {
-        const int intra = is_intra_picture || mb_type[i >> 4] <= T_I16;
+        const int intra = is_intra_picture || mb_type[i >> 4] <= T_PCM;
         const int r = intra ? -1 : refs[i];
         e->cref[i] = (int8_t)r;
         e->cpic[i] = r < 0 ? -1 : wlist[r < wlist_n ? r : wlist_n - 1];

@@ -88,7 +88,7 @@ static void w_begin_mb(void)
 }
 static int w_A(void) { return avail(cur % W - 1, cur / W); }                 /* the macroblock to the left / above is usable */
 static int w_B(void) { return avail(cur % W, cur / W - 1); }
-static int w_is_intra(int mb) { return mb_type[mb] <= T_I16; }
+static int w_is_intra(int mb) { return mb_type[mb] <= T_PCM; }
 
 /* ---- macroblock types ------------------------------------------------------------------------------------------------------ */
 static void sx_mb_skip(bw_t *b, int skipped)
@@ -98,7 +98,7 @@ static void sx_mb_skip(bw_t *b, int skipped)
     if (skipped) { w_skip[cur] = 1; w_last_dqp = 0; if (slice_kind == 2) { w_direct16[cur] = 1; w_d8[cur] = 15; } }
 }
 static void ce_intra_type(bw_t *b, int ti, int base)
-{   /* ti: I-slice numbering 0 .. 24 */
+{   /* ti: I-slice numbering 0 .. 25 */
     const int in_i = slice_kind == 0;
     int s;
     if (in_i) {
@@ -111,6 +111,7 @@ static void ce_intra_type(bw_t *b, int ti, int base)
         if (!ti) return;
         s = base;
     }
+    if (ti == 25) { ce_terminate(b, 1); return; }            /* I_PCM: the encoder flushes (9.3.4.5); put_ipcm starts it again behind the samples */
     ce_terminate(b, 0);                                      /* not I_PCM */
     const int v = ti - 1, luma = v / 12, chroma = (v % 12) / 4, pm = v & 3;
     ce_bin(b, s + 1, luma);
