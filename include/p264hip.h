@@ -79,8 +79,10 @@ typedef struct p264hip_mb {
     uint32_t coef_mask;    /* bit b<24: 4x4 block b has total_coeff>0 (0-15 luma in decode order
                               core/macroblock.h:194-201, 16-19 Cb, 20-23 Cr); | P264_COEF_* */
     uint32_t coef_index;   /* index, in 16-level blocks, of this MB's first packed block (I_PCM: of its first sample block) */
-    uint8_t  avail;        /* P264_AVAIL_*: neighbouring MBs usable for intra prediction
-                              (core/macroblock.c:926-1033; picture border / slice membership) */
+    uint8_t  avail;        /* P264_AVAIL_*: neighbouring MBs usable for intra prediction (core/macroblock.c:926-1033): inside the
+                              picture, in this macroblock's slice and - for an intra macroblock of a picture with
+                              constrained_intra_pred_flag - intra themselves; the four flags are independent, any of the
+                              sixteen combinations may occur */
     uint8_t  edges;        /* P264_EDGE_*: which MB edges the loop filter touches (core/frame.c:524) */
     uint16_t flags;        /* reserved, 0 */
 } p264hip_mb_t;

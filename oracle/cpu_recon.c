@@ -545,7 +545,7 @@ static void recon_intra(const rc_t *r, const p264hip_mb_t *m, int mbx, int mby, 
     if (m->mb_type == P264_MB_I16x16) {
         /* decoder/macroblock.c:771-798 */
         int mode = m->intra_modes & 3;
-        if (mode == 2) mode = TL ? 2 : L ? 4 : T ? 5 : 6;                   /* valid_intra16x16_mode :635-667 */
+        if (mode == 2) mode = (L && T) ? 2 : L ? 4 : T ? 5 : 6;             /* H.264 8.3.3.3; :635-667 keys on TL, SURVEY A-Q7 */
         gather(r->y, r->w, mbx*16, mby*16, 16, 16, L, T, 0, TL, l, t, &tl);
         pred16(mode, l, t, tl, o);
         for (int y = 0; y < 16; y++) memcpy(Y + y*r->w, o + y*16, 16);
@@ -581,7 +581,7 @@ static void recon_intra(const rc_t *r, const p264hip_mb_t *m, int mbx, int mby, 
     }
     /* chroma: decoder/macroblock.c:853-859 */
     int cmode = (m->intra_modes >> 4) & 3;
-    if (cmode == 0) cmode = TL ? 0 : L ? 4 : T ? 5 : 6;                     /* valid_intra8x8c_mode :721-753 */
+    if (cmode == 0) cmode = (L && T) ? 0 : L ? 4 : T ? 5 : 6;               /* H.264 8.3.4; :721-753 keys on TL, SURVEY A-Q7 */
     for (int ch = 0; ch < 2; ch++) {
         uint8_t *plane = ch ? r->v : r->u;
         gather(plane, r->cw, mbx*8, mby*8, 8, 8, L, T, 0, TL, l, t, &tl);

@@ -234,7 +234,7 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
         if (is16) {
             // ---- Intra16x16 (core/predict.c:55-193): lane l = row l ----
             int mode = modes & 3;
-            if (mode == 2) mode = aTL ? 2 : aL ? 4 : aT ? 5 : 6;                // :635-667
+            if (mode == 2) mode = (aL && aT) ? 2 : aL ? 4 : aT ? 5 : 6;         // H.264 8.3.3.3 (:635-667 keys on the corner, SURVEY A-Q7)
             const uint32_t *trow = (const uint32_t *)(L.tile + 4);
             const uint32_t t0 = trow[0], t1 = trow[1], t2 = trow[2], t3 = trow[3];
             uint32_t pv[4];
@@ -378,7 +378,7 @@ __device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, I
 
     // ---- prediction: 8 samples of row r ----
     int mode = (modes >> 4) & 3;
-    if (mode == 0) mode = aTL ? 0 : aL ? 4 : aT ? 5 : 6;                         // :721-753
+    if (mode == 0) mode = (aL && aT) ? 0 : aL ? 4 : aT ? 5 : 6;                  // H.264 8.3.4 (:721-753 keys on the corner, SURVEY A-Q7)
     const uint32_t ta = *(const uint32_t *)(tile + 4), tb = *(const uint32_t *)(tile + 8);
     const int s0 = byte_sum(ta), s1 = byte_sum(tb);
     const int sq = sum_lanes(vL, 4);                                             // left sum of this lane's half (rows 0..3 or 4..7)

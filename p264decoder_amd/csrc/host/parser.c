@@ -746,17 +746,20 @@ static void set_motion_l(p264parse *p, int bx, int by, int bw, int bh, int mvx, 
 }
 static void set_motion(p264parse *p, int bx, int by, int bw, int bh, int mvx, int mvy) { set_motion_l(p, bx, by, bw, bh, mvx, mvy, 0); }
 
-/* Intra4x4PredMode predictor (H.264 8.3.1.1; core/macroblock.c:40-51) */
+/* Intra4x4PredMode predictor (H.264 8.3.1.1; core/macroblock.c:40-51).  Both entropy coders come through here.
+ * dcPredModePredictedFlag: a neighbouring macroblock that is not available - or, with constrained_intra_pred_flag, is inter -
+ * makes the prediction 2 whatever the other neighbour says (the reference reads the flag and drops it, decoder/set.c:241) */
 static int predict_i4mode(const p264parse *p, int blk)
 {
     const picbuf_t *q = &p->buf[p->cur];
+    const int cip = p->pps[p->sh.pps_id].constrained_intra;
     int x = blk_x[blk], y = blk_y[blk], ma, mb;
     if (x > 0) ma = q->i4[p->mbi * 16 + blk_of_xy[y][x-1]];
-    else if (p->cur_avail & P264_AVAIL_LEFT)
+    else if ((p->cur_avail & P264_AVAIL_LEFT) && !(cip && !P264_MB_IS_INTRA(q->mb[p->mbi - 1].mb_type)))
         ma = q->mb[p->mbi - 1].mb_type == P264_MB_I4x4 ? q->i4[(p->mbi - 1) * 16 + blk_of_xy[y][3]] : 2;
     else ma = -1;
     if (y > 0) mb = q->i4[p->mbi * 16 + blk_of_xy[y-1][x]];
-    else if (p->cur_avail & P264_AVAIL_TOP)
+    else if ((p->cur_avail & P264_AVAIL_TOP) && !(cip && !P264_MB_IS_INTRA(q->mb[p->mbi - p->mb_w].mb_type)))
         mb = q->mb[p->mbi - p->mb_w].mb_type == P264_MB_I4x4 ? q->i4[(p->mbi - p->mb_w) * 16 + blk_of_xy[3][x]] : 2;
     else mb = -1;
     int m = ma < mb ? ma : mb;
@@ -895,6 +898,22 @@ static void begin_mb(p264parse *p, p264hip_mb_t *m)
     m->edges = (uint8_t)e;
 }
 
+/* the record's `avail` of an INTRA macroblock (I_PCM included): what intra prediction may read.  With constrained_intra_pred_flag
+ * a neighbour in the slice counts only if it is intra itself (H.264 8.3.1.2, 8.3.3, 8.3.4).  p->cur_avail - vector prediction, nC,
+ * the CABAC context increments - stays what the slice gives (data partitioning, the one exception of 9.2.1, is not decoded). */
+static int intra_avail(const p264parse *p)
+{
+    int a = p->cur_avail;
+    if (!p->pps[p->sh.pps_id].constrained_intra) return a;
+    const p264hip_mb_t *mb = p->buf[p->cur].mb;
+    const int i = p->mbi, w = p->mb_w;
+    if ((a & P264_AVAIL_LEFT) && !P264_MB_IS_INTRA(mb[i - 1].mb_type)) a &= ~P264_AVAIL_LEFT;
+    if ((a & P264_AVAIL_TOP) && !P264_MB_IS_INTRA(mb[i - w].mb_type)) a &= ~P264_AVAIL_TOP;
+    if ((a & P264_AVAIL_TOPRIGHT) && !P264_MB_IS_INTRA(mb[i - w + 1].mb_type)) a &= ~P264_AVAIL_TOPRIGHT;
+    if ((a & P264_AVAIL_TOPLEFT) && !P264_MB_IS_INTRA(mb[i - w - 1].mb_type)) a &= ~P264_AVAIL_TOPLEFT;
+    return a;
+}
+
 /* QP bookkeeping of core/macroblock.c:1247-1252 (or the conformant chain in strict mode) */
 static void finish_mb_qp(p264parse *p, p264hip_mb_t *m, int has_residual_syntax, int qp)
 {
@@ -997,6 +1016,7 @@ static int parse_mb_t(p264parse *p, bitrd_t *b, unsigned t, int intra_t)
     if (intra_t >= 0) {
         /* ---- intra (decoder/macroblock.c:117-139, 265-301) ---- */
         if (intra_t > 25) { ERR(p, "invalid mb type %d", intra_t); return -1; }
+        m->avail = (uint8_t)intra_avail(p);
         if (intra_t == 25) return parse_ipcm(p, b, m);
         memset(ref, -1, 4);
         memset(q->mv + p->mbi * 32, 0, 64);

@@ -49,6 +49,11 @@
  *                            first carry a different table, [--wp-bad-sum] B pictures' luma weights 100 on every entry (pairs
  *                            past the limit of 8.4.2.3: streams the decoder must refuse).  None of it draws a random number
  *                            unless asked for: the other options write the bytes they wrote before.
+ *            [--constrained-intra] constrained_intra_pred_flag 1: intra macroblocks of P / B pictures predict from intra neighbours
+ *                            only (modes drawn from that availability, the Intra4x4 mode prediction of 8.3.1.1); [--dump-avail f]
+ *                            per picture one byte per macroblock: the availability the writer assumed, then its Intra4x4 modes;
+ *                            [--intra-pct N] N % (up to 80) of the macroblocks of P / B pictures intra instead of 4 / 5 %.  Without
+ *                            these options the streams are what they were, byte for byte.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -399,14 +404,26 @@ static void put_residual(bw_t *b, int mbx, int mby, const resid_t *r, int is_i16
     }
 }
 
+/* --constrained-intra: constrained_intra_pred_flag 1 in the PPS.  For intra prediction a neighbouring macroblock then counts only
+ * if it is intra itself (I_PCM included; H.264 8.3.1.2, 8.3.3, 8.3.4): the modes of intra macroblocks are drawn from that masked
+ * availability, and the Intra4x4 mode prediction says 2 as soon as one of the two neighbours is inter (8.3.1.1,
+ * dcPredModePredictedFlag).  Vector prediction, nC and the CABAC context increments keep the slice's availability. */
+static int opt_cintra = 0;
+static int opt_intra_pct = 0;               /* --intra-pct N: N % of the non-skipped macroblocks of P / B pictures are intra (0: the 4 / 5 % of always) */
+static FILE *dump_avail;                    /* --dump-avail: per picture one byte per macroblock, the availability the writer assumed for
+                                               intra prediction (1 left, 2 top, 4 top-right, 8 top-left; inter macroblocks: the slice's),
+                                               then sixteen bytes per macroblock, its Intra4x4 modes (meaningful for Intra4x4 macroblocks) */
+static uint8_t *w_avail;
+static int iavail(int mbx, int mby) { return avail(mbx, mby) && (!opt_cintra || mb_type[mby * W + mbx] <= T_PCM); }
+
 static int pred_i4mode(int mbx, int mby, int blk)
 {
     int x = blk_x[blk], y = blk_y[blk], ma, mb;
     if (x > 0) ma = i4m[cur * 16 + blk_of_xy[y][x-1]];
-    else if (avail(mbx - 1, mby)) ma = mb_type[cur - 1] == T_I4 ? i4m[(cur - 1) * 16 + blk_of_xy[y][3]] : 2;
+    else if (iavail(mbx - 1, mby)) ma = mb_type[cur - 1] == T_I4 ? i4m[(cur - 1) * 16 + blk_of_xy[y][3]] : 2;
     else ma = -1;
     if (y > 0) mb = i4m[cur * 16 + blk_of_xy[y-1][x]];
-    else if (avail(mbx, mby - 1)) mb = mb_type[cur - W] == T_I4 ? i4m[(cur - W) * 16 + blk_of_xy[3][x]] : 2;
+    else if (iavail(mbx, mby - 1)) mb = mb_type[cur - W] == T_I4 ? i4m[(cur - W) * 16 + blk_of_xy[3][x]] : 2;
     else mb = -1;
     int m = ma < mb ? ma : mb;
     return m < 0 ? 2 : m;
@@ -415,7 +432,7 @@ static int pred_i4mode(int mbx, int mby, int blk)
 /* intra MB (I slice: offset 0; P slice: mb_type + 5) */
 static void put_intra(bw_t *b, int mbx, int mby, int type_offset)
 {
-    int L = avail(mbx - 1, mby), T = avail(mbx, mby - 1), TL = avail(mbx - 1, mby - 1);
+    int L = iavail(mbx - 1, mby), T = iavail(mbx, mby - 1), TL = iavail(mbx - 1, mby - 1);
     int is16 = pct(50);
     resid_t r; int i16_ac = 0;
     int cbp = rand_residual(&r, is16, &i16_ac);
@@ -727,9 +744,14 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
             }
             if (pcm) put_ipcm(&b, is_b ? 23 : is_p ? 5 : 0);
             else if (!skipped) {
-                if (is_b) { if (k >= 95) put_intra(&b, mbx, mby, 23); else put_b_mb(&b, mbx, mby); }
-                else if (is_p) { if (k >= 96) put_intra(&b, mbx, mby, 5); else put_inter(&b, mbx, mby); }
+                if (is_b) { if (k >= (opt_intra_pct ? 100 - opt_intra_pct : 95)) put_intra(&b, mbx, mby, 23); else put_b_mb(&b, mbx, mby); }
+                else if (is_p) { if (k >= (opt_intra_pct ? 100 - opt_intra_pct : 96)) put_intra(&b, mbx, mby, 5); else put_inter(&b, mbx, mby); }
                 else put_intra(&b, mbx, mby, 0);
+            }
+            if (w_avail) {
+                const int intra = mb_type[cur] <= T_PCM;
+                w_avail[cur] = (uint8_t)((intra ? iavail(mbx - 1, mby) : avail(mbx - 1, mby)) | (intra ? iavail(mbx, mby - 1) : avail(mbx, mby - 1)) << 1 |
+                                         (intra ? iavail(mbx + 1, mby - 1) : avail(mbx + 1, mby - 1)) << 2 | (intra ? iavail(mbx - 1, mby - 1) : avail(mbx - 1, mby - 1)) << 3);
             }
             if (opt_cabac) ce_terminate(&b, cur == end - 1);      /* end_of_slice_flag */
         }
@@ -748,6 +770,7 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
         for (int i = 0; i < pcm_n; i++) { fwrite(&pcm_idx[i], 4, 1, dump_pcm); fwrite(pcm_bytes + (size_t)i * 384, 1, 384, dump_pcm); }
     }
     pcm_n = 0;
+    if (dump_avail) { fwrite(w_avail, 1, (size_t)NMB, dump_avail); fwrite(i4m, 1, (size_t)NMB * 16, dump_avail); }
     if (dump_wp) {
         int16_t rec[3 + 2 * 16 * 3 * 2];
         memset(rec, 0, sizeof rec);
@@ -824,6 +847,9 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--ipcm-style")) { const char *st = i + 1 < argc ? argv[i + 1] : ""; opt_ipcm_style = !strcmp(st, "flat") ? 1 : !strcmp(st, "edge") ? 2 : 0; i++; }
         else if (!strcmp(a, "--dump-pcm")) { dump_pcm = fopen(argv[i + 1], "wb"); i++; }
         else if (!strcmp(a, "--dump-wp")) { dump_wp = fopen(argv[i + 1], "wb"); i++; }
+        else if (!strcmp(a, "--constrained-intra")) opt_cintra = 1;
+        else if (!strcmp(a, "--intra-pct")) { opt_intra_pct = v < 0 ? 0 : v > 80 ? 80 : v; i++; }
+        else if (!strcmp(a, "--dump-avail")) { dump_avail = fopen(argv[i + 1], "wb"); i++; }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
     if (W < 1 || H < 1 || W > 512 || H > 512 || frames < 1 || opt_qp < 0 || opt_qp > 51 || opt_refs < 1 || opt_refs > ((opt_mmco || opt_bframes) ? 4 : 2) || (opt_bframes && (opt_refs < 2 || opt_bframes > 4)) || opt_alpha < -6 || opt_alpha > 6 || opt_beta < -6 || opt_beta > 6) { fprintf(stderr, "bad geometry\n"); return 2; }
@@ -831,6 +857,7 @@ int main(int argc, char **argv)
     g_rng = seed * 0x9e3779b97f4a7c15ull + 264;
     w_alloc();
     if (opt_ipcm) { pcm_idx = calloc((size_t)NMB, 4); pcm_bytes = malloc((size_t)NMB * 384); }
+    if (dump_avail) w_avail = calloc((size_t)NMB, 1);
     mb_type = calloc((size_t)NMB, 1); mvs = calloc((size_t)NMB * 32, 2); nnz = calloc((size_t)NMB, 24); i4m = calloc((size_t)NMB, 16); refs = calloc((size_t)NMB, 16);
     FILE *f = fopen(argv[1], "wb");
     if (!f) { perror(argv[1]); return 2; }
@@ -856,7 +883,7 @@ int main(int argc, char **argv)
         bw_ue(&b, (uint32_t)pps); bw_ue(&b, 0); bw_put(&b, 1, (uint32_t)opt_cabac); bw_put(&b, 1, 0); bw_ue(&b, 0);   /* ids, entropy_coding_mode, pic_order_present, slice groups */
         bw_ue(&b, 0); bw_ue(&b, 0); bw_put(&b, 1, (uint32_t)opt_wp); bw_put(&b, 2, (uint32_t)(opt_wp_bi ? 1 : opt_implicit ? 2 : 0));   /* weighted_pred, weighted_bipred_idc */
         bw_se(&b, opt_qp - 26); bw_se(&b, 0); bw_se(&b, opt_cqo);
-        bw_put(&b, 1, 1); bw_put(&b, 1, 0); bw_put(&b, 1, 0);
+        bw_put(&b, 1, 1); bw_put(&b, 1, (uint32_t)opt_cintra); bw_put(&b, 1, 0);   /* deblocking_filter_control_present, constrained_intra_pred, redundant_pic_cnt_present */
         bw_trailing(&b);
         write_nal(f, 3, 8, &b); free(b.buf);
     }
@@ -878,6 +905,7 @@ int main(int argc, char **argv)
         if (dump_mv) fclose(dump_mv);
         if (dump_wp) fclose(dump_wp);
         if (dump_pcm) fclose(dump_pcm);
+        if (dump_avail) fclose(dump_avail);
         return 0;
     }
     for (int n = 0; n < frames; n++) {
@@ -894,5 +922,6 @@ int main(int argc, char **argv)
     if (dump_mv) fclose(dump_mv);
     if (dump_wp) fclose(dump_wp);
     if (dump_pcm) fclose(dump_pcm);
+    if (dump_avail) fclose(dump_avail);
     return 0;
 }

@@ -20,6 +20,15 @@ def load():
     for f in ("oracle_reconstruct", "oracle_reconstruct_nodeblock", "oracle_deblock_picture"):
         getattr(lib, f).argtypes = [C.POINTER(N.Picture), C.POINTER(C.c_void_p)]
         getattr(lib, f).restype = C.c_int
+    # the kernel-level entry points of the residual arithmetic (tests/intra_checker.py)
+    for f in ("oracle_dequant4x4", "oracle_dequant4x4_dc", "oracle_dequant2x2_dc"):
+        getattr(lib, f).argtypes = [C.c_void_p, C.c_int]
+        getattr(lib, f).restype = None
+    for f in ("oracle_idct4x4dc", "oracle_idct2x2dc"):
+        getattr(lib, f).argtypes = [C.c_void_p]
+        getattr(lib, f).restype = None
+    lib.oracle_add4x4_idct.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.oracle_add4x4_idct.restype = None
     return lib
 
 

@@ -3,7 +3,8 @@
 The stream writer can only produce what a conformant CAVLC stream can carry and what the reference decodes; the seam is
 wider: any macroblock type mix, every partition shape down to 4x4 with its own vector, a QP per macroblock, levels up to
 the int16 limits (storage wrap, SURVEY A-Q8), several reference frames, every neighbour-availability / edge pattern a
-slice structure can produce, deblocking offsets.  `make_picture` draws such a picture; the GPU test feeds the same
+slice structure can produce - or, with avail_mode="free", all sixteen combinations of the four flags, as constrained intra
+prediction produces them - deblocking offsets.  `make_picture` draws such a picture; the GPU test feeds the same
 arrays to p264hip_submit and to the CPU oracle and compares bytes (tests/test_gpu_seam_fuzz.py).
 """
 import ctypes as C
@@ -80,7 +81,7 @@ def _levels(rng, n, style):
 
 def make_picture(rng, mb_w, mb_h, *, p_picture=True, n_ref=1, slots=2, dst_slot=0, level_style="small", qp_mode="random",
                  mv_range=80, sub8x8=True, intra_share=0.15, slices=1, deblock_offsets=True, b_picture=False, n_ref_l1=1, weighted=None, mirror_l1=0.0,
-                 explicit_wp=None, wp_denoms=None, dup_refs=False, past_list=0.0, slice_idcs=None):
+                 explicit_wp=None, wp_denoms=None, dup_refs=False, past_list=0.0, slice_idcs=None, avail_mode="slices", slice_starts=None, force=None):
     """Draw one picture.  qp_mode: 'random' (0..51 per macroblock), 'two' (two values), or an int (constant).
     b_picture: a B picture - every inter macroblock is P264_MB_B, each 8x8 quadrant predicts from list 0, list 1 or both
     (a negative index = list unused, its vectors 0); weighted: None = drawn, else weighted_bipred on / off; mirror_l1: share of
@@ -91,7 +92,16 @@ def make_picture(rng, mb_w, mb_h, *, p_picture=True, n_ref=1, slots=2, dst_slot=
     None = drawn).  dup_refs: list 0 (and list 1) start with one frame at indices 0 and 1 - with explicit weights, two different
     weights of one frame.  past_list: share of the inter quadrants (skipped macroblocks aside) whose indices are drawn from
     n_ref .. 15 instead, in each list the quadrant uses - an index past its list means entry 0 (include/p264hip.h, ref_idx).
-    slice_idcs: the slices' deblocking idcs in turn (None: drawn)."""
+    slice_idcs: the slices' deblocking idcs in turn (None: drawn).
+    avail_mode: "slices" - `avail` is what the slice structure and the picture's borders give (nothing else is drawn: a seed gives the
+    picture it always gave); "free" - the four flags of every macroblock are drawn independently wherever the neighbour lies inside
+    the picture (flags across the border stay off), as constrained intra prediction produces them (H.264 8.3.1.2: a neighbour in
+    an inter macroblock is not available): all sixteen combinations, intra modes drawn from what the DRAWN flags make legal;
+    `edges` and everything the inter path reads stay slice-shaped.
+    slice_starts: the first macroblock of every slice (None: drawn).  force: {macroblock: "i16" | "i4"} - that macroblock is intra,
+    Intra16x16 with DC prediction or Intra4x4, with chroma DC (make_directed)."""
+    assert avail_mode in ("slices", "free"), avail_mode
+    force = force or {}
     pic = SeamPicture(mb_w, mb_h)
     d = pic.desc
     n = mb_w * mb_h
@@ -118,7 +128,10 @@ def make_picture(rng, mb_w, mb_h, *, p_picture=True, n_ref=1, slots=2, dst_slot=
         for i in range(N.MAX_REFS * N.MAX_REFS):                           # implicit weights: 64 - dist_scale_factor, -64 .. 128; often 32
             d.bipred_weight[i] = 32 if rng.random() < 0.3 else int(rng.integers(-64, 129))
     # slice structure: first macroblock of every slice and its deblocking idc (0 all edges, 1 none, 2 not across slices)
-    starts = sorted(set([0] + [int(x) for x in rng.integers(1, max(n, 2), size=slices - 1)])) if slices > 1 and n > 1 else [0]
+    if slice_starts is not None:
+        starts = sorted(set([0] + [int(x) for x in slice_starts]))
+    else:
+        starts = sorted(set([0] + [int(x) for x in rng.integers(1, max(n, 2), size=slices - 1)])) if slices > 1 and n > 1 else [0]
     idcs = [int(rng.choice([0, 0, 2, 1])) for _ in starts] if slice_idcs is None else [slice_idcs[k % len(slice_idcs)] for k in range(len(starts))]
     slice_of = np.zeros(n, np.int32)
     for k, s in enumerate(starts):
@@ -144,9 +157,13 @@ def make_picture(rng, mb_w, mb_h, *, p_picture=True, n_ref=1, slots=2, dst_slot=
             if mby > 0 and (idc == 0 or T):
                 e |= N.EDGE_TOP
         r["edges"] = e
+        if avail_mode == "free":
+            inside = [mbx > 0, mby > 0, mby > 0 and mbx + 1 < mb_w, mbx > 0 and mby > 0]
+            L, T, TR, TL = [bool(i and rng.random() < 0.5) for i in inside]
+            r["avail"] = (N.AVAIL_LEFT if L else 0) | (N.AVAIL_TOP if T else 0) | (N.AVAIL_TOPRIGHT if TR else 0) | (N.AVAIL_TOPLEFT if TL else 0)
         r["qp"] = int(rng.integers(0, 52)) if qp_mode == "random" else int(two[rng.integers(0, 2)]) if qp_mode == "two" else int(qp_mode)
         style = level_style if level_style != "mixed" else str(rng.choice(["small", "small", "large", "wrap"]))
-        intra = (not p_picture) or rng.random() < intra_share
+        intra = (not p_picture) or rng.random() < intra_share or m in force
         mask = 0
         mb_blocks = []
         if intra:
@@ -154,10 +171,12 @@ def make_picture(rng, mb_w, mb_h, *, p_picture=True, n_ref=1, slots=2, dst_slot=
             is16 = rng.random() < 0.5
             legal_c = [0] + ([1] if L else []) + ([2] if T else []) + ([3] if L and T and TL else [])
             cmode = int(rng.choice(legal_c))
+            if m in force:
+                is16, cmode = force[m] == "i16", 0
             if is16:
                 r["mb_type"] = N.MB_I16x16
                 legal = ([0] if T else []) + ([1] if L else []) + [2] + ([3] if L and T and TL else [])
-                r["intra_modes"] = int(rng.choice(legal)) | (cmode << 4)
+                r["intra_modes"] = (2 if m in force else int(rng.choice(legal))) | (cmode << 4)
                 cbp_l = 15 if rng.random() < 0.4 else 0
                 if rng.random() < 0.7:
                     mask |= N.COEF_LUMA_DC
@@ -286,6 +305,40 @@ def make_picture(rng, mb_w, mb_h, *, p_picture=True, n_ref=1, slots=2, dst_slot=
     if explicit_wp and d.slice_type != N.SLICE_I:
         draw_wp_table(rng, pic, explicit_wp, wp_denoms)
     return pic.seal()
+
+
+def make_directed(rng, mb_w, mb_h, kind, **kw):
+    """The macroblock below the first macroblock of a slice that starts inside a row: a two-slice picture whose second slice starts
+    at a column drawn from [1, mb_w - 2] (any row but the last); the macroblock below the start - LEFT, TOP and TOPRIGHT in its slice,
+    TOPLEFT outside it - is forced intra (kind "i16": Intra16x16 DC, "i4": Intra4x4; chroma DC either way, make_picture's `force`),
+    and its left and top neighbours become I_PCM macroblocks of dark (left) and bright (top) samples, so that the DC of both
+    neighbours and the DC of the left column alone are far apart.  Returns (picture, the forced macroblock)."""
+    from tests import pcm_fuzz
+    assert mb_w >= 3 and mb_h >= 2
+    start = int(rng.integers(0, mb_h - 1)) * mb_w + int(rng.integers(1, mb_w - 1))
+    target = start + mb_w
+    pic = make_picture(rng, mb_w, mb_h, slice_starts=[start], force={target: kind}, **kw)
+    assert pic.rec["avail"][target] == N.AVAIL_LEFT | N.AVAIL_TOP | N.AVAIL_TOPRIGHT
+    chosen = np.zeros(mb_w * mb_h, bool)
+    chosen[[target - 1, start]] = True
+    src = [np.full((mb_h * 16, mb_w * 16), 30, np.uint8), np.full((mb_h * 8, mb_w * 8), 40, np.uint8), np.full((mb_h * 8, mb_w * 8), 50, np.uint8)]
+    bx, by = start % mb_w, start // mb_w
+    for plane, s, v in zip(src, (16, 8, 8), (220, 200, 190)):
+        plane[by * s:by * s + s, bx * s:bx * s + s] = v
+    pcm_fuzz.to_ipcm(rng, pic, 0, samples="frame", src=src, chosen=chosen, noise=3)
+    return pic, target
+
+
+def picture_digest(pic):
+    """a digest of everything a drawn picture consists of (the descriptor's scalars and the arrays)"""
+    import hashlib
+    d = pic.desc
+    h = hashlib.sha256()
+    h.update(np.array([d.mb_w, d.mb_h, d.slice_type, d.chroma_qp_offset, d.deblock, d.alpha_c0_offset, d.beta_offset, d.dst_slot, d.n_ref,
+                       d.n_coef_blocks, d.n_ref_l1, d.weighted_bipred, d.explicit_wp] + list(d.ref_slot) + list(d.ref_slot_l1), np.int64).tobytes())
+    for a in (pic.rec, pic.mv, pic.ref_idx, pic.i4modes, pic.coefs[:16 * max(d.n_coef_blocks, 1)], pic.mv_l1, pic.ref_idx_l1):
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()[:16]
 
 
 def bi_pairs(pic):
