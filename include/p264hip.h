@@ -115,8 +115,10 @@ typedef struct p264hip_picture {
     const int16_t      *mv;         /* [mb][16][2] quarter-pel, 4x4 blocks in raster order inside the MB */
     const int8_t       *ref_idx;    /* [mb][4] per 8x8 (raster), -1 for intra.  An index at or past its list's length (n_ref .. 15;
                                      * ref_idx_l1 the same with n_ref_l1) means entry 0 on every road: the prediction, the implicit
-                                     * and explicit weights and the loop filter's reference picture (for unweighted P pictures,
-                                     * which compare indices there, index 0; negative indices of inter quadrants too) */
+                                     * and explicit weights and the loop filter's reference picture.  The loop filter compares
+                                     * reference PICTURES (H.264 8.7.2.1), i.e. the frame-store slots ref_slot[] / ref_slot_l1[] of
+                                     * the entries, in P and B pictures alike: two indices that name one slot are one picture.  An
+                                     * inter quadrant without any list (negative index, P) counts as list 0, entry 0 */
     const uint8_t      *i4modes;    /* [mb][16] Intra4x4PredMode per block in decode order (0..8) */
     const int16_t      *coefs;      /* [n_coef_blocks][16] */
     /* ---- B pictures only (slice_type == P264_SLICE_B; ignored otherwise).  A quadrant whose list-X index is negative

@@ -633,12 +633,14 @@ static void edge(const p264hip_picture_t *pic, uint8_t *pix, int stride, int dir
     }
 }
 
-/* B pictures, H.264 8.7.2.1: the two blocks either side of an edge segment get strength 1 when they predict from different
+/* P and B pictures, H.264 8.7.2.1: the two blocks either side of an edge segment get strength 1 when they predict from different
  * reference PICTURES or a different number of vectors, or when vectors that belong to the same picture differ by >= 4
  * quarter-pels in a component.  The reference's loop (core/frame.c:565-577, encoder side: its decoder never gets here,
  * decoder/macroblock.c:168-171) compares list by list on the indices, which is only the same thing while no picture sits in
- * both lists.  Pictures are told apart by their frame-store slot; an unused list is slot -1 with a zero vector (the parser
- * keeps that), a quadrant without any list predicts from list 0, entry 0 (as the motion compensation reads it). */
+ * both lists and none twice in one list - and a P picture's list may hold one frame at several indices (reordering commands
+ * that name it twice, a list padded with its last frame).  Pictures are told apart by their frame-store slot; an unused list
+ * (list 1 of every P picture) is slot -1 with a zero vector (the parser keeps that), a quadrant without any list predicts from
+ * list 0, entry 0 (as the motion compensation reads it). */
 static int b_slot(const p264hip_picture_t *pic, int list, int idx)
 {
     if (idx < 0) return -1;
@@ -649,17 +651,20 @@ static int mv_far(const int16_t *a, const int16_t *b) { return iabs(a[0] - b[0])
 static int b_motion_strength(const p264hip_picture_t *pic, int mbi, int x, int y, int nbi, int xn, int yn)
 {
     const int qp_ = mbi*4 + (y >> 1)*2 + (x >> 1), qn_ = nbi*4 + (yn >> 1)*2 + (xn >> 1);
-    int p0 = b_slot(pic, 0, pic->ref_idx[qp_]), p1 = b_slot(pic, 1, pic->ref_idx_l1[qp_]);
-    int q0 = b_slot(pic, 0, pic->ref_idx[qn_]), q1 = b_slot(pic, 1, pic->ref_idx_l1[qn_]);
+    static const int16_t none[2] = { 0, 0 };
+    const int two = pic->slice_type == P264_SLICE_B;
+    const int i1p = two ? pic->ref_idx_l1[qp_] : -1, i1q = two ? pic->ref_idx_l1[qn_] : -1;
+    int p0 = b_slot(pic, 0, pic->ref_idx[qp_]), p1 = b_slot(pic, 1, i1p);
+    int q0 = b_slot(pic, 0, pic->ref_idx[qn_]), q1 = b_slot(pic, 1, i1q);
     if (p0 < 0 && p1 < 0) p0 = pic->ref_slot[0];
     if (q0 < 0 && q1 < 0) q0 = pic->ref_slot[0];
     const int16_t *vp0 = pic->mv + (mbi*16 + y*4 + x)*2, *vq0 = pic->mv + (nbi*16 + yn*4 + xn)*2;
-    const int16_t *vp1 = pic->mv_l1 + (mbi*16 + y*4 + x)*2, *vq1 = pic->mv_l1 + (nbi*16 + yn*4 + xn)*2;
+    const int16_t *vp1 = two ? pic->mv_l1 + (mbi*16 + y*4 + x)*2 : none, *vq1 = two ? pic->mv_l1 + (nbi*16 + yn*4 + xn)*2 : none;
     const int straight = p0 == q0 && p1 == q1 && !mv_far(vp0, vq0) && !mv_far(vp1, vq1);
     const int crossed  = p0 == q1 && p1 == q0 && !mv_far(vp0, vq1) && !mv_far(vp1, vq0);
     const int bs = !(straight || crossed);
     {   /* coverage: what the list-by-list comparison of indices would have said */
-        int by_index = pic->ref_idx[qp_] != pic->ref_idx[qn_] || mv_far(vp0, vq0) || pic->ref_idx_l1[qp_] != pic->ref_idx_l1[qn_] || mv_far(vp1, vq1);
+        int by_index = pic->ref_idx[qp_] != pic->ref_idx[qn_] || mv_far(vp0, vq0) || i1p != i1q || mv_far(vp1, vq1);
         if (by_index != bs) g_bs_by_picture++;
     }
     return bs;
@@ -686,14 +691,7 @@ int oracle_deblock_picture(const p264hip_picture_t *pic, uint8_t **planes)
                         int x = dir == 0 ? e : i, y = dir == 0 ? i : e;
                         int xn = dir == 0 ? (x - 1) & 3 : x, yn = dir == 0 ? y : (y - 1) & 3;
                         if (((m->coef_mask >> blk_at[y][x]) & 1) || ((n->coef_mask >> blk_at[yn][xn]) & 1)) bS[i] = 2;
-                        else {
-                            int rp = pic->ref_idx[mbi*4 + (y >> 1)*2 + (x >> 1)], rq = pic->ref_idx[nbi*4 + (yn >> 1)*2 + (xn >> 1)];
-                            if (rp < 0 || rp >= pic->n_ref) rp = 0;          /* negative or past the list: entry 0 (include/p264hip.h, ref_idx) */
-                            if (rq < 0 || rq >= pic->n_ref) rq = 0;
-                            const int16_t *vp = pic->mv + (mbi*16 + y*4 + x)*2, *vq = pic->mv + (nbi*16 + yn*4 + xn)*2;
-                            bS[i] = (rp != rq || iabs(vp[0] - vq[0]) >= 4 || iabs(vp[1] - vq[1]) >= 4) ? 1 : 0;   /* :565-577, one list */
-                            if (pic->slice_type == P264_SLICE_B) bS[i] = b_motion_strength(pic, mbi, x, y, nbi, xn, yn);
-                        }
+                        else bS[i] = b_motion_strength(pic, mbi, x, y, nbi, xn, yn);      /* by picture, P and B alike */
                     }
                     int qp = m->qp, qpn = n->qp;
                     if (qp != qpn && (bS[0] | bS[1] | bS[2] | bS[3])) g_stats[6]++;   /* an edge filtered with the mean of two QPs */

@@ -62,6 +62,11 @@ def _headers():
 def build(force=False, verbose=False):
     os.makedirs(OBJ_DIR, exist_ok=True)
     hdrs = _headers()
+    srcs = [os.path.join(HOST_DIR, s) for s in HOST_SRCS] + [os.path.join(HIP_DIR, s) for s in HIP_SRCS]
+    if not force and not _newer(LIB, srcs + hdrs):
+        # the library is newer than every source and header: nothing to do, also where the object files did not travel with it
+        build_tools(force=False)
+        return LIB
     objs = []
     for s in HOST_SRCS:
         src = os.path.join(HOST_DIR, s)

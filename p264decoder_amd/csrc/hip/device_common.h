@@ -32,7 +32,11 @@ struct PicDev {
     // explicit weighted prediction (p264hip_picture_t::explicit_wp; P and B pictures):
     const int16_t      *wp;        // [list][16][Y, Cb, Cr][weight, offset]
     int32_t explicit_wp, wp_denom_y, wp_denom_c;
+    // unweighted P pictures whose list 0 holds one frame at several indices: the loop filter's motion test goes by picture
+    // (kernel_deblock.h, edge_info_of).  Sits in what was the struct's tail padding: its size and every other offset are as before.
+    int32_t dup_refs;
 };
+static_assert(sizeof(PicDev) == 272, "PicDev: the stride every kernel multiplies by");
 
 // Geometry shared by every picture of a context.
 struct Geom {

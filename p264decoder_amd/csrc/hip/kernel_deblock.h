@@ -142,10 +142,11 @@ __device__ __forceinline__ uint4 edge_info_of(const PicDev *pd, const Geom &g, i
                                               const uint4 m0, const uint4 m1, const uint4 m2, const uint4 m3, const uint32_t refs, const PicOf *pic_tab,
                                               const EdgeTop *top = nullptr)
 {
-    // (P pictures with explicit weights take the two-list test too, with list 1 empty: their list may hold one frame at several
-    // indices with different weights, and "different reference pictures" (H.264 8.7.2.1) is about pictures - unweighted P
-    // pictures keep the index comparison)
-    const bool b_pic = TWO_LISTS && (pd->slice_type == P264_SLICE_B || pd->explicit_wp);
+    // (P pictures whose list holds one frame at several indices - dup_refs, found by the host; any P picture with explicit weights,
+    // where such entries carry different weights - take the two-list test too, with list 1 empty: "different reference pictures"
+    // (H.264 8.7.2.1) is about pictures.  Every other P picture's indices name different pictures: there the index comparison
+    // below IS the comparison by picture, and the batch may take the one-list instances)
+    const bool b_pic = TWO_LISTS && (pd->slice_type == P264_SLICE_B || pd->explicit_wp || pd->dup_refs);
     // neighbours (self where there is none: unused).  (ti written so that no select needs the picture width in a vector register)
     const int above = mbi - g.mb_w;
     const int li = mbx > 0 ? mbi - 1 : mbi, ti = above >= 0 ? above : mbi;
@@ -181,7 +182,7 @@ __device__ __forceinline__ uint4 edge_info_of(const PicDev *pd, const Geom &g, i
     // pictures per 8x8 quadrant: own (4), right column of the left macroblock (quadrants 1, 3), bottom row of the one above (2, 3)
     uint32_t own0[4] = { 0 }, own1[4] = { 0 }, lft0[2] = { 0 }, lft1[2] = { 0 }, top0[2] = { 0 }, top1[2] = { 0 };
     if (b_pic) {
-      if (pd->slice_type != P264_SLICE_B) { refs1 = refs1L = refs1T = ~0u; }      // (explicit P: no list-1 index anywhere, vectors 0)
+      if (pd->slice_type != P264_SLICE_B) { refs1 = refs1L = refs1T = ~0u; }      // (P: no list-1 index anywhere, vectors 0)
       else {
         const int *m1 = pd->mv_l1;
         const uint4 a0 = gload4(ubase(m1, (uint32_t)mbi * 64u)), a1 = gload4(ubase(m1, (uint32_t)mbi * 64u + 16u)), a2 = gload4(ubase(m1, (uint32_t)mbi * 64u + 32u)), a3 = gload4(ubase(m1, (uint32_t)mbi * 64u + 48u));
@@ -277,7 +278,7 @@ void k_deblock_bs(const PicDev *__restrict__ pics, Geom g, EdgeInfo *__restrict_
     if (!pd->deblock) return;
     __shared__ PicOf pic_tab;
     if (TWO_LISTS) {
-        if (pd->slice_type == P264_SLICE_B || pd->explicit_wp) pic_of_init(pic_tab, pd);
+        if (pd->slice_type == P264_SLICE_B || pd->explicit_wp || pd->dup_refs) pic_of_init(pic_tab, pd);
         __syncthreads();
     }
     const int mbi = blockIdx.x * 256 + threadIdx.x;

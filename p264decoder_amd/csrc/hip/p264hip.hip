@@ -680,6 +680,7 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     HIPCHK(hipEventSynchronize(c->batch_free[r]));            // the copy that last used this staging buffer is done
     PicDev *hb = c->h_batch[r];
     bool any_p = false, any_b = false, any_i = false, any_wp = false;   // any picture with inter macroblocks / any B picture / any I picture / any explicit weights
+    bool any_dup = false;                                   // any unweighted P picture whose list 0 holds one frame at several indices
     for (int i = 0; i < n; i++) {                          // two pictures of one call must not share a stream: they would race on its frames
         const int st = streams[i];
         if (st < 0 || st >= c->n_streams) return fail(P264HIP_EINVAL, "stream %d out of range", st);
@@ -720,6 +721,13 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
             d.wp = (const int16_t *)(s.dev + s.L.off_wp);
             d.explicit_wp = 1; d.wp_denom_y = s.meta.wp_log2_denom[0]; d.wp_denom_c = s.meta.wp_log2_denom[1];
             any_wp = true;
+        }
+        if (s.meta.slice_type == P264_SLICE_P && !s.meta.explicit_wp) {
+            // one frame at two indices (reordering commands that name it twice, a list padded with its last frame): the loop filter
+            // tells reference PICTURES apart (H.264 8.7.2.1), so such a picture takes the by-picture edge info, as weighted ones do
+            for (int k = 1; k < s.meta.n_ref && k < P264HIP_MAX_REFS; k++)
+                for (int j = 0; j < k; j++) if (s.meta.ref_slot[k] == s.meta.ref_slot[j]) d.dup_refs = 1;
+            any_dup |= d.dup_refs != 0;
         }
         any_p |= s.meta.slice_type != P264_SLICE_I;
         any_i |= s.meta.slice_type == P264_SLICE_I;
@@ -779,7 +787,7 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
         else {
             // (P / B pictures only.  Batches without B pictures: the loop filter's edge info is computed by extra workgroups of this
             // launch, kernel_intra.h)
-            bs_fused = !any_b && !any_wp && c->tune_bs_fused != 0;
+            bs_fused = !any_b && !any_wp && !any_dup && c->tune_bs_fused != 0;
             const int bs_wgs = bs_fused ? (c->tune_bs_fused > 0 ? c->tune_bs_fused : INTRA_BS_WGS) : 0;
             li.edge_info_fused = bs_wgs;
             hipLaunchKernelGGL(k_intra_sparse, dim3((unsigned)n * (2 + bs_wgs)), dim3(intra_waves * 64), (size_t)intra_waves * sizeof(IntraLds), c->stream, c->d_batch[r], g, c->d_status,
@@ -789,8 +797,9 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     {
         ScopedStamp t(c, 2);
         // edge info (boundary strengths, averaged QPs per edge class): everything about an edge that does not depend on samples
-        // (explicit weighted prediction: the two-list instance, which compares reference pictures rather than indices - kernel_deblock.h)
-        if (any_b || any_wp) hipLaunchKernelGGL(k_deblock_bs<true>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, c->d_batch[r], g, c->d_edge, inv_mbw);
+        // (explicit weighted prediction, a P list with one frame twice: the two-list instance, which compares reference pictures rather
+        // than indices - kernel_deblock.h)
+        if (any_b || any_wp || any_dup) hipLaunchKernelGGL(k_deblock_bs<true>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, c->d_batch[r], g, c->d_edge, inv_mbw);
         else if (!bs_fused) hipLaunchKernelGGL(k_deblock_bs<false>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, c->d_batch[r], g, c->d_edge, inv_mbw);
         // pictures per workgroup = as many as it takes to cover the batch with one workgroup per CU (a second, half-empty round
         // of workgroups costs more than sharing a workgroup: 1280 pictures as 320 workgroups of 4 took 5.35 ms, as 256 of 5 ...)

@@ -198,7 +198,8 @@ class Pool:
 
 
 def expected_edge_info_fused(pics, knob=None):
-    """edge_info_fused of a batch: 0 with any I, B or explicit-weight picture (own k_deblock_bs launch), else the knob or 1"""
-    if any(p.desc.slice_type != N.SLICE_P or p.desc.explicit_wp for p in pics):
+    """edge_info_fused of a batch: 0 with any I, B or explicit-weight picture, or a P picture whose list holds one frame at several
+    indices (own k_deblock_bs launch), else the knob or 1"""
+    if any(p.desc.slice_type != N.SLICE_P or p.desc.explicit_wp or len(set(p.desc.ref_slot[:p.desc.n_ref])) < p.desc.n_ref for p in pics):
         return 0
     return 1 if knob is None else int(knob)

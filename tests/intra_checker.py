@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from p264decoder_amd import _native as N
-from tests import pcm_checker, wp_checker
+from tests import pcm_checker
 
 # 4x4 luma blocks in decoding order -> position in units of blocks (6.4.3, figure 6-10)
 BLK_X = [0, 1, 0, 1, 2, 3, 2, 3, 0, 1, 0, 1, 2, 3, 2, 3]
@@ -369,15 +369,7 @@ class IntraChecker:
         d = pic.desc
         self.nodeblock(pic)
         if d.deblock:
-            if d.explicit_wp and d.slice_type != N.SLICE_B:    # (as wp_checker: a P picture's indices -> the first index of the same frame)
-                mapped = wp_checker._Copy(pic)
-                slots = [d.ref_slot[j] for j in range(d.n_ref)]
-                for i, r in enumerate(mapped.ref_idx):
-                    if r >= 0:
-                        mapped.ref_idx[i] = slots.index(slots[r if r < d.n_ref else 0])
-                self.oracle.oracle_deblock_picture(C.byref(mapped.desc), self.store.ptrs)
-            else:
-                self.oracle.oracle_deblock_picture(C.byref(pic.desc), self.store.ptrs)
+            self.oracle.oracle_deblock_picture(C.byref(pic.desc), self.store.ptrs)
         return self.store[d.dst_slot]
 
 

@@ -131,15 +131,7 @@ class PcmChecker:
         before = [a.copy() for a in self.nodeblock(pic)]
         self.last_nodeblock = before
         if d.deblock:
-            if d.explicit_wp and d.slice_type != N.SLICE_B:    # (as wp_checker: a P picture's indices -> the first index of the same frame)
-                mapped = wp_checker._Copy(pic)
-                slots = [d.ref_slot[j] for j in range(d.n_ref)]
-                for i, r in enumerate(mapped.ref_idx):
-                    if r >= 0:
-                        mapped.ref_idx[i] = slots.index(slots[r if r < d.n_ref else 0])
-                self.oracle.oracle_deblock_picture(C.byref(mapped.desc), self.store.ptrs)
-            else:
-                self.oracle.oracle_deblock_picture(C.byref(pic.desc), self.store.ptrs)
+            self.oracle.oracle_deblock_picture(C.byref(pic.desc), self.store.ptrs)
         out = self.store[d.dst_slot]
         if stats is not None:
             ym = np.kron(pcm.reshape(d.mb_h, d.mb_w), np.ones((16, 16), bool))

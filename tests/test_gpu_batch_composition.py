@@ -1,5 +1,6 @@
 """A picture's bytes do not depend on its batch.  p264hip_reconstruct picks its kernels by looking at the whole batch once: any B
-picture switches every picture to k_mc_sort_b + k_mc_second + k_deblock_bs<true>, any explicit weights to the _wp instances, any
+picture switches every picture to k_mc_sort_b + k_mc_second + k_deblock_bs<true>, any explicit weights to the _wp instances (any
+explicit weights or any P list that holds a frame twice to k_deblock_bs<true>), any
 I picture to the dense k_intra without the fused edge-info pass, and the batch size sets intra_waves, the loop filter's pictures
 per workgroup / band height / odd_single and the motion-compensation workgroups per picture.  So an unweighted P picture decodes
 through different code depending on what shares its call.  A pool of one picture per kind (each on its own stream and frame store)
@@ -26,7 +27,8 @@ KINDS = {
     "B_implicit": dict(n_ref=2, n_ref_l1=2, b_picture=True, weighted=True),
     "B_weighted": dict(n_ref=2, n_ref_l1=2, b_picture=True, explicit_wp="legal"),
 }
-PLAIN_P = {"P", "P_multi_dup"}   # the kinds whose batches alone keep the fused edge-info pass
+PLAIN_P = {"P"}                  # the kinds whose batches alone keep the fused edge-info pass (P_multi_dup: one frame at two indices -
+                                 # the loop filter compares pictures, H.264 8.7.2.1, which the two-list edge-info kernel does)
 
 
 def draw(rng, mb_w, mb_h, kind):

@@ -72,7 +72,7 @@ def test_fuzz_configurations_reach_the_paths_they_are_meant_for(oracle):
 
 def test_an_index_past_its_list_decodes_as_index_0(oracle):
     """include/p264hip.h, ref_idx: an index at or past its list's length means entry 0 - prediction, implicit weights and the loop
-    filter (P pictures compare indices there) - so the oracle gives the same frame when every such index is rewritten to 0"""
+    filter (which compares the frames the entries name) - so the oracle gives the same frame when every such index is rewritten to 0"""
     from tests import wp_checker
     for b_picture in (False, True):
         rng = np.random.default_rng(44 + b_picture)

@@ -6,8 +6,8 @@ Per picture:
 2. a copy of the picture in which every inter macroblock predicts from list 0, index 0, vector 0 (B pictures: list 1 unused),
    list 0's entry 0 being S - residual and intra macroblocks unchanged - through oracle_reconstruct_nodeblock: the weighted
    prediction plus the residual, in that order;
-3. oracle_deblock_picture with the picture's own vectors; a P picture's list-0 indices mapped to the first index that names
-   the same frame (the oracle compares P indices, 8.7.2.1 compares pictures; its B test already compares frames).
+3. oracle_deblock_picture on the picture's own records, vectors and indices (it tells reference pictures apart by their frame,
+   H.264 8.7.2.1, in P and B pictures alike - tests/deblock_checker.py holds it to that).
 With identity tables (weight 2^denom, offset 0) this is oracle_reconstruct bit for bit (tests/test_weighted_pred_cpu.py)."""
 import ctypes as C
 
@@ -122,13 +122,7 @@ class WeightedChecker:
         flat.desc.ref_slot[0] = self.s_slot
         flat.desc.weighted_bipred = 0
         self.oracle.oracle_reconstruct_nodeblock(C.byref(flat.desc), self.store.ptrs)
-        # step 3: the loop filter with the picture's own motion (P: indices -> first index of the same frame)
+        # step 3: the loop filter with the picture's own motion
         if d.deblock:
-            mapped = _Copy(pic)
-            if not mapped.is_b:
-                slots = [d.ref_slot[j] for j in range(d.n_ref)]
-                for i, r in enumerate(mapped.ref_idx):
-                    if r >= 0:
-                        mapped.ref_idx[i] = slots.index(slots[r if r < d.n_ref else 0])
-            self.oracle.oracle_deblock_picture(C.byref(mapped.desc), self.store.ptrs)
+            self.oracle.oracle_deblock_picture(C.byref(pic.desc), self.store.ptrs)
         return self.store[d.dst_slot]
