@@ -63,7 +63,7 @@ enum {
  * (raster, 16 per row), 64 Cb, 64 Cr (raster, 8 per row).  Its record: coef_mask = P264_IPCM_COEF_MASK exactly (popcount 12: the
  * range rule "coef_index + popcount(coef_mask & 0x3ffffff) <= n_coef_blocks" covers the samples as it covers levels, and so do
  * the compact format's per-block sums), qp = 0 (H.264 8.7.2.2: the loop filter treats its edges with qPp = 0; the filter reads
- * the record's qp), cbp = 0, intra_modes = 0, flags = 0; ref_idx -1, vectors 0, the sixteen i4modes 2, like every macroblock
+ * the record's qp), cbp = 0, intra_modes = 0; flags: its slice's filter-offset deltas, like any other macroblock; ref_idx -1, vectors 0, the sixteen i4modes 2, like every macroblock
  * that is not Intra4x4.  avail and edges mean what they mean everywhere.  Every road into an input slot (p264hip_upload,
  * p264hip_pack_input, p264hip_pack_compact, p264hip_compact_check, the device check behind p264hip_input_commit) rejects an
  * I_PCM record with any other mask: the kernels read twelve blocks whatever the mask says. */
@@ -84,7 +84,16 @@ typedef struct p264hip_mb {
                               constrained_intra_pred_flag - intra themselves; the four flags are independent, any of the
                               sixteen combinations may occur */
     uint8_t  edges;        /* P264_EDGE_*: which MB edges the loop filter touches (core/frame.c:524) */
-    uint16_t flags;        /* reserved, 0 */
+    uint16_t flags;        /* the macroblock's loop-filter offsets, as signed DELTAS on the picture's: bits 0-7 (int8) are added to
+                              p264hip_picture_t.alpha_c0_offset, bits 8-15 (int8) to beta_offset - in the units of those fields, as
+                              given (the unshifted convention of the descriptor stays).  The offsets that govern an edge are those
+                              of the macroblock whose left, top or inner edge is filtered (H.264 8.7.2.2: filterOffsetA / B of the
+                              slice that holds q0); both macroblocks' QPs still count.  0 = the picture's offsets: what every
+                              record said while the field was reserved.  Any int8 pair is legal - indexA / indexB are clipped to
+                              0 .. 51 - so no upload path checks or refuses anything here; every road into an input slot
+                              (p264hip_upload, the packed and compact forms, reserve / commit, p264hip_clone_picture) carries
+                              the record's sixteen bytes unchanged.  The host parser writes (slice's offsets - picture's), 0 in
+                              slices that do not filter */
 } p264hip_mb_t;
 
 #define P264_AVAIL_LEFT     1
@@ -104,11 +113,13 @@ typedef struct p264hip_picture {
     int32_t  slice_type;            /* P264_SLICE_P / P264_SLICE_I */
     int32_t  chroma_qp_offset;      /* pps chroma_qp_index_offset */
     int32_t  deblock;               /* run the loop filter (decoder/decoder.c:639) */
-    int32_t  alpha_c0_offset;       /* used unshifted, as the reference does (core/frame.c:476-478) */
-    int32_t  beta_offset;
+    int32_t  alpha_c0_offset;       /* used unshifted, as the reference does (core/frame.c:476-478); per macroblock plus the deltas */
+    int32_t  beta_offset;           /* of its record's flags.  (The host parser: the offsets of the picture's first slice that filters) */
     int32_t  dst_slot;              /* frame-store slot reconstructed into */
     int32_t  n_ref;                 /* list-0 length */
-    int32_t  ref_slot[P264HIP_MAX_REFS];
+    int32_t  ref_slot[P264HIP_MAX_REFS];   /* ONE list 0 (and one list 1, one weight table) per picture.  The host parser makes that true for
+                                            * pictures whose slices reorder or size their lists differently: the first P / B slice's lists
+                                            * verbatim, later slices' entries merged into them or appended, their indices remapped */
     uint32_t n_coef_blocks;         /* entries in coefs[] */
     uint32_t frame_num;             /* informational */
     const p264hip_mb_t *mb;         /* [mb_w*mb_h] raster order */

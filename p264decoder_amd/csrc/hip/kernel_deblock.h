@@ -75,7 +75,9 @@ enum { EC_LEFT = 0, EC_TOP = 1, EC_INNER = 2 };     // edge classes
 //   bs[dir]  two bits per (edge, segment), bit 2 * (4 * edge + segment): the boundary strength, except that on a macroblock
 //            edge (edge 0) code 3 stands for strength 4 - strength 3 only exists on inner edges, strength 4 only on
 //            macroblock edges (core/frame.c:535-538)
-//   qp       own luma QP (= the averaged QP of the inner edges)
+//   qp       bits 0-7 own luma QP (= the averaged QP of the inner edges); bits 16-31 the record's flags as they stand: the
+//            macroblock's signed deltas on the picture's alpha (bits 16-23) and beta (bits 24-31) offsets (include/p264hip.h).
+//            A change of offsets is thereby a change of this word, which is what makes the consumer expand again
 //   avg      the averaged QPs of the other five edge classes, six bits each: luma left, luma top, chroma left, chroma
 //            top, chroma inner (core/frame.c:593-601)
 // alpha / beta / tc0 come out of tables in the consumer (edge_expand below).
@@ -214,7 +216,11 @@ __device__ __forceinline__ uint4 edge_info_of(const PicDev *pd, const Geom &g, i
         pics_of(refsT, refs1T, 2, top0[0], top1[0]); pics_of(refsT, refs1T, 3, top0[1], top1[1]);
     }
 
-    const int m_type = rec.x & 255, m_qp = (rec.x >> 8) & 255, m_edges = (rec.w >> 8) & 255;
+    // (the EdgeInfo qp word right away - the QP and, in its free upper half, the record's flags as they stand: ONE register lives through
+    // the strengths instead of two record words; the edge-info role of the 64-register k_intra_sparse build has none to spare)
+    uint32_t qp_word = ((rec.x >> 8) & 255u) | (rec.w & 0xffff0000u);
+    asm volatile("" : "+v"(qp_word));
+    const int m_type = rec.x & 255, m_qp = (int)(qp_word & 255u), m_edges = (rec.w >> 8) & 255;
     const unsigned mmask = rec.y, lmask = recLy, tmask = recT.y;
     const bool m_intra = P264_MB_IS_INTRA(m_type), l_intra = P264_MB_IS_INTRA(recLx & 255), t_intra = P264_MB_IS_INTRA(recT.x & 255);
     const bool fL = m_edges & P264_EDGE_LEFT, fT = m_edges & P264_EDGE_TOP;
@@ -264,7 +270,7 @@ __device__ __forceinline__ uint4 edge_info_of(const PicDev *pd, const Geom &g, i
     const uint32_t avg = (uint32_t)((m_qp + qpL + 1) >> 1) | (uint32_t)((m_qp + qpT + 1) >> 1) << 6
                        | (uint32_t)((cq_own + chroma_qp(clip3i(qpL + cqo, 0, 51)) + 1) >> 1) << 12
                        | (uint32_t)((cq_own + chroma_qp(clip3i(qpT + cqo, 0, 51)) + 1) >> 1) << 18 | (uint32_t)cq_own << 24;
-    return make_uint4(word[0], word[1], (uint32_t)m_qp, avg);
+    return make_uint4(word[0], word[1], qp_word, avg);
 }
 
 // One lane per macroblock.  (Round 4 also had the work-list sort of the MC stage write the edge info while it holds the same
@@ -304,14 +310,16 @@ __device__ __forceinline__ void edge_tables_init(EdgeTables &T)
     }
 }
 // Class k = class + 3 * chroma of a macroblock: alpha, beta, tc0 (deblock_edge, core/frame.c:472-488; offsets unshifted:
-// A-Q3).  k may vary per lane.  On the macroblock-edge classes code 3 means strength 4, which has no tc0: byte 3 = 0.
+// A-Q3).  k may vary per lane.  qp is the EdgeInfo word: the QP in its low six bits, the macroblock's deltas on the picture's
+// offsets in bytes 2 and 3 - all six classes, the left and top macroblock edges included, take the offsets of the macroblock
+// that holds q0 (H.264 8.7.2.2), any int8 pair is fine because the indices are clipped.  On the macroblock-edge classes code 3 means strength 4, which has no tc0: byte 3 = 0.
 struct EdgeClass { uint4 ab; uint32_t tc; };         // {alpha, beta, -alpha, -beta} as pairs; tc0 bytes
 __device__ __forceinline__ EdgeClass edge_expand(const EdgeTables &T, uint32_t qp, uint32_t avg, int k, int alpha_off, int beta_off)
 {
     const int sh = k < 2 ? 6 * k : 6 * (k - 1);                        // k: 0 1 [2] 3 4 5 -> field 0 1 [qp] 2 3 4 of avg
     const int q = k == 2 ? (int)(qp & 63u) : (int)((avg >> sh) & 63u);
-    const uint32_t at = T.alpha_tc[clip3i(q + alpha_off, 0, 51)];
-    const uint32_t be = T.beta[clip3i(q + beta_off, 0, 51)];
+    const uint32_t at = T.alpha_tc[clip3i(q + alpha_off + (int)(int8_t)(qp >> 16), 0, 51)];
+    const uint32_t be = T.beta[clip3i(q + beta_off + ((int)qp >> 24), 0, 51)];
     uint32_t v = at + (k >= 3 ? 0x01010100u : 0u);                     // chroma: tc0 + 1 (no carries: tc0 <= 25)
     if (k != 2 && k != 5) v &= 0x00ffffffu;
     const uint32_t a2 = (v & 0xffu) * 0x00010001u, b2 = be * 0x00010001u;
@@ -662,7 +670,8 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
             {
                 const uint4 v = act ? *(const uint4 *)L.edge : make_uint4(0, 0, 0, 0);
                 E.e[0] = v.x; E.e[1] = v.y; E.lds = L.edge;
-                // the class parameters of the octet's LDS copy follow the macroblock's QPs: expanded again only when those change
+                // the class parameters of the octet's LDS copy follow the macroblock's QPs and offset deltas (v.z holds both): expanded
+                // again only when those change
                 const bool changed = act && (v.z != last_qp || v.w != last_avg);
                 if (__ballot(changed)) {
                     if (act) {

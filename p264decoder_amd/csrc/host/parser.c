@@ -91,8 +91,18 @@ struct p264parse {
     slice_t sh;                               /* current slice */
     slice_t sh0;                              /* first slice of the picture */
     int pic_deblock, pic_alpha, pic_beta;     /* loop filter of the picture: on if any slice enables it, offsets of the first such slice */
+    uint16_t slice_flags;                     /* the records' `flags` of the current slice: its offsets minus the picture's (include/p264hip.h) */
+    /* The lists of the CURRENT SLICE: what its macroblocks are parsed against (vector prediction, CABAC contexts, skip / direct
+     * inference and temporal direct's list-0 mapping are slice-local).  Between pictures - publish_picture, finish_picture_marking -
+     * they hold the picture's canonical lists. */
     int list0[P264HIP_MAX_REFS], n_list0;
     int list1[P264HIP_MAX_REFS], n_list1;     /* B pictures */
+    /* The picture's CANONICAL lists, the ones the device gets: the first P / B slice's verbatim; a later slice's entries are
+     * mapped onto them (ref_map: slice index -> canonical index), new ones appended, and the indices the slice wrote are
+     * rewritten when it ends (end_slice) */
+    int pic_list[2][P264HIP_MAX_REFS], n_pic_list[2];
+    int8_t ref_map[2][P264HIP_MAX_REFS]; int ref_map_used[2];
+    int16_t wp_first[2][P264HIP_MAX_REFS][3][2];   /* the first P / B slice's weight table: what every other slice's must equal (p->sh0.wp_tab grows) */
     int16_t bipred_weight[P264HIP_MAX_REFS * P264HIP_MAX_REFS];   /* implicit weights of the picture (8.4.2.3.1) */
     int weighted_bipred;
     int pic_wp_set;                           /* the picture's explicit weight table: taken from its first P / B slice (p->sh0 keeps it) */
@@ -402,7 +412,13 @@ static int parse_slice_header(p264parse *p, bitrd_t *b, int nal_type, int nal_re
     sh->qp = pps->pic_init_qp + br_se(b);
     if (pps->deblock_ctrl) {
         sh->disable_deblock = (int)br_ue(b);
-        if (sh->disable_deblock != 1) { sh->alpha_off = br_se(b); sh->beta_off = br_se(b); }
+        if (sh->disable_deblock > 2) { ERR(p, "disable_deblocking_filter_idc %d out of range", sh->disable_deblock); return -1; }
+        if (sh->disable_deblock != 1) {
+            sh->alpha_off = br_se(b); sh->beta_off = br_se(b);
+            if (sh->alpha_off < -6 || sh->alpha_off > 6 || sh->beta_off < -6 || sh->beta_off > 6) {          /* 7.4.3 */
+                ERR(p, "slice_alpha_c0_offset_div2 %d / slice_beta_offset_div2 %d out of range (-6 .. 6)", sh->alpha_off, sh->beta_off); return -1;
+            }
+        }
     }
     if (br_overrun(b)) { ERR(p, "slice header overruns the NAL"); return -1; }
     return 0;
@@ -614,24 +630,6 @@ static void finish_picture_marking(p264parse *p)
         p->prev_poc_lsb = had_mmco5 ? 0 : p->sh0.poc_lsb;
     }
     if (sps->poc_type == 2) { p->frame_num_offset = had_mmco5 ? 0 : frame_num_offset_of(p, sps, &p->sh0, p->pic_is_idr); p->prev_frame_num = had_mmco5 ? 0 : p->sh0.frame_num; }
-    /* the motion of a reference picture is what the direct prediction of later B pictures reads (8.4.1.2) */
-    if (p->pic_ref_idc && p->has_col) {
-        const picbuf_t *q = &p->buf[p->cur];
-        int16_t *cm = p->col_mv[p->cur_slot]; int8_t *cr = p->col_ref[p->cur_slot]; int32_t *cu = p->col_uid[p->cur_slot];
-        const int isB = p->sh0.type == P264_SLICE_B;
-        for (int i = 0; i < p->n_mb * 4; i++) {
-            const int r0 = q->ref[i], r1 = isB ? q->ref1[i] : -1;
-            const int mbi = i >> 2, q8 = i & 3, b0 = (q8 >> 1) * 8 + (q8 & 1) * 2;
-            const int16_t *src = r0 >= 0 || r1 < 0 ? q->mv : q->mv1;                          /* the list-0 motion if there is one, else list 1 */
-            const int r = r0 >= 0 ? r0 : r1;
-            cr[i] = (int8_t)r;
-            cu[i] = r < 0 ? -1 : (int32_t)p->dpb[r0 >= 0 ? p->list0[r0 < p->n_list0 ? r0 : 0] : p->list1[r1 < p->n_list1 ? r1 : 0]].uid;
-            for (int k = 0; k < 4; k++) {
-                const int blk = b0 + (k >> 1) * 4 + (k & 1);
-                cm[(mbi * 16 + blk) * 2] = r < 0 ? 0 : src[(mbi * 16 + blk) * 2]; cm[(mbi * 16 + blk) * 2 + 1] = r < 0 ? 0 : src[(mbi * 16 + blk) * 2 + 1];
-            }
-        }
-    }
     /* next picture goes into a slot that holds no reference */
     int next = -1;
     for (int i = 0; i < p->slots; i++) if (!p->dpb[i].used) { next = i; break; }
@@ -896,6 +894,7 @@ static void begin_mb(p264parse *p, p264hip_mb_t *m)
         if (p->mby > 0 && (p->sh.disable_deblock == 0 || (a & P264_AVAIL_TOP)))  e |= P264_EDGE_TOP;
     }
     m->edges = (uint8_t)e;
+    m->flags = p->slice_flags;                /* (0 in a slice that does not filter) */
 }
 
 /* the record's `avail` of an INTRA macroblock (I_PCM included): what intra prediction may read.  With constrained_intra_pred_flag
@@ -989,7 +988,7 @@ static int parse_ipcm(p264parse *p, bitrd_t *b, p264hip_mb_t *m)
     }
     if (coef_reserve(q, P264_IPCM_BLOCKS) < 0) return -1;
     memcpy(q->coef + q->coef_n * 16, src, 384);
-    m->mb_type = P264_MB_IPCM;                                   /* qp, cbp, intra_modes, flags: 0 (begin_mb) */
+    m->mb_type = P264_MB_IPCM;                                   /* qp, cbp, intra_modes: 0; flags: the slice's deltas, like any macroblock (begin_mb) */
     m->coef_mask = P264_IPCM_COEF_MASK;
     m->coef_index = (uint32_t)q->coef_n;
     q->coef_n += P264_IPCM_BLOCKS;
@@ -1058,7 +1057,7 @@ static int parse_mb_t(p264parse *p, bitrd_t *b, unsigned t, int intra_t)
         } else {
             m->mb_type = P264_MB_P_8x8;
             int sub[4];
-            for (int k = 0; k < 4; k++) { sub[k] = rd_sub_mb_type(p, b); if (sub[k] > 3) { ERR(p, "invalid i_sub_partition"); return -1; } }
+            for (int k = 0; k < 4; k++) { sub[k] = rd_sub_mb_type(p, b); if (sub[k] < 0 || sub[k] > 3) { ERR(p, "invalid i_sub_partition"); return -1; } }   /* (< 0: a ue(v) past 2^31 in a damaged stream) */
             memset(ref, 0, 4);
             for (int k = 0; k < 4; k++) {
                 int r = 0;
@@ -1268,7 +1267,7 @@ static int parse_mb_b_t(p264parse *p, bitrd_t *b, unsigned t)
         int sub[4], any_direct = 0;
         for (int k = 0; k < 4; k++) {
             sub[k] = rd_sub_mb_type(p, b);
-            if (sub[k] > 12) { ERR(p, "invalid B sub_mb_type %d", sub[k]); return -1; }
+            if (sub[k] < 0 || sub[k] > 12) { ERR(p, "invalid B sub_mb_type %d", sub[k]); return -1; }   /* (< 0: as above; found by tests/tools/asan_slices.sh) */
             any_direct |= sub[k] == 0;
             if (p->cabac_on && sub[k] == 0) p->cinfo[p->mbi] |= CI_D8(k);
         }
@@ -1341,6 +1340,74 @@ static long rbsp_stop_bit(const uint8_t *buf, int size)
 }
 
 /* ---------------------------------------------------------------- slice ------------------ */
+/* List X of the slice that starts (p->list0 / p->list1, with the slice's weights in p->sh.wp_tab) onto the picture's canonical list:
+ * the first P / B slice's list IS the canonical list, verbatim, with its length and its duplicates.  Every entry i of a later slice
+ * maps to canonical entry i where that one names the same frame (slices that agree keep their indices: such a picture is what it
+ * was with one list per picture), else to the first canonical entry with the same frame - and, under explicit weights, the same
+ * (weight, offset) for Y, Cb and Cr; without a match the entry is appended, with its weights.  More than P264HIP_MAX_REFS entries
+ * are refused (without explicit weights that cannot happen: at most 16 frames, and an entry is only appended for a new frame). */
+static int map_slice_list(p264parse *p, int X)
+{
+    const int *loc = X ? p->list1 : p->list0, n_loc = X ? p->n_list1 : p->n_list0;
+    int *can = p->pic_list[X], *n_can = &p->n_pic_list[X];
+    const int wp = p->sh0.wp;
+    p->ref_map_used[X] = 0;
+    if (*n_can == 0) {
+        memcpy(can, loc, sizeof(int) * (size_t)n_loc); *n_can = n_loc;
+        for (int i = 0; i < P264HIP_MAX_REFS; i++) p->ref_map[X][i] = (int8_t)i;
+        return 0;
+    }
+    for (int i = 0; i < n_loc; i++) {
+        int j = -1;
+#define SAME_ENTRY(k) (can[k] == loc[i] && (!wp || !memcmp(p->sh0.wp_tab[X][k], p->sh.wp_tab[X][i], sizeof p->sh.wp_tab[X][i])))
+        if (i < *n_can && SAME_ENTRY(i)) j = i;
+        for (int k = 0; k < *n_can && j < 0; k++) if (SAME_ENTRY(k)) j = k;
+#undef SAME_ENTRY
+        if (j < 0) {
+            if (*n_can >= P264HIP_MAX_REFS) { ERR(p, "the slices of the picture need more than %d entries in reference list %d", P264HIP_MAX_REFS, X); return -1; }
+            j = (*n_can)++;
+            can[j] = loc[i];
+            if (wp) memcpy(p->sh0.wp_tab[X][j], p->sh.wp_tab[X][i], sizeof p->sh.wp_tab[X][i]);
+        }
+        p->ref_map[X][i] = (int8_t)j;
+        if (j != i) p->ref_map_used[X] = 1;
+    }
+    for (int i = n_loc; i < P264HIP_MAX_REFS; i++) p->ref_map[X][i] = p->ref_map[X][0];     /* (past the list = entry 0) */
+    return 0;
+}
+
+/* The slice [first, end) is parsed.  What outlives it must not name its own list indices:
+ * - the motion of a reference picture, kept for the direct prediction of later B pictures (8.4.1.2): per 8x8 the PICTURE the
+ *   index meant (uid) - through the slice's own lists, here, while they are at hand - and the index as the slice coded it, which is
+ *   what colZeroFlag asks about (8.4.1.2.2: refIdxCol is 0);
+ * - ref_idx[] / ref_idx_l1[] of its macroblocks: rewritten to the picture's canonical indices (negative ones stay). */
+static void end_slice(p264parse *p, int first, int end)
+{
+    picbuf_t *q = &p->buf[p->cur];
+    const int isB = p->sh.type == P264_SLICE_B;
+    if (p->pic_ref_idc && p->has_col) {
+        int16_t *cm = p->col_mv[p->cur_slot]; int8_t *cr = p->col_ref[p->cur_slot]; int32_t *cu = p->col_uid[p->cur_slot];
+        for (int i = first * 4; i < end * 4; i++) {
+            const int r0 = q->ref[i], r1 = isB ? q->ref1[i] : -1;
+            const int mbi = i >> 2, q8 = i & 3, b0 = (q8 >> 1) * 8 + (q8 & 1) * 2;
+            const int16_t *src = r0 >= 0 || r1 < 0 ? q->mv : q->mv1;                          /* the list-0 motion if there is one, else list 1 */
+            const int r = r0 >= 0 ? r0 : r1;
+            cr[i] = (int8_t)r;
+            cu[i] = r < 0 ? -1 : (int32_t)p->dpb[r0 >= 0 ? p->list0[r0 < p->n_list0 ? r0 : 0] : p->list1[r1 < p->n_list1 ? r1 : 0]].uid;
+            for (int k = 0; k < 4; k++) {
+                const int blk = b0 + (k >> 1) * 4 + (k & 1);
+                cm[(mbi * 16 + blk) * 2] = r < 0 ? 0 : src[(mbi * 16 + blk) * 2]; cm[(mbi * 16 + blk) * 2 + 1] = r < 0 ? 0 : src[(mbi * 16 + blk) * 2 + 1];
+            }
+        }
+    }
+    if (p->sh.type == P264_SLICE_I) return;
+    for (int X = 0; X < (isB ? 2 : 1); X++) {
+        if (!p->ref_map_used[X]) continue;
+        int8_t *ref = X ? q->ref1 : q->ref;
+        for (int i = first * 4; i < end * 4; i++) if (ref[i] >= 0) ref[i] = p->ref_map[X][ref[i] & (P264HIP_MAX_REFS - 1)];
+    }
+}
+
 static void publish_picture(p264parse *p)
 {
     picbuf_t *q = &p->buf[p->cur];
@@ -1408,6 +1475,7 @@ static int decode_slice(p264parse *p, int nal_type, int nal_ref_idc, const uint8
         p->buf[p->cur].coef_n = 0;
         memset(p->slice_of, 0xff, (size_t)p->n_mb * sizeof(uint16_t));
         p->n_list0 = 0; p->n_list1 = 0; p->pic_wp_set = 0;
+        p->n_pic_list[0] = p->n_pic_list[1] = 0;
         p->cur_poc = picture_order_count(p, &sh, p->pic_is_idr, nal_ref_idc);
         p->cur_uid = ++p->next_uid;
         if (p->buf[p->cur].ref1) memset(p->buf[p->cur].ref1, -1, (size_t)p->n_mb * 4);   /* nothing predicts from list 1 until a B macroblock says so */
@@ -1417,23 +1485,20 @@ static int decode_slice(p264parse *p, int nal_type, int nal_ref_idc, const uint8
     }
     if (sh.disable_deblock != 1) {                /* the filter parameters are per picture on the device */
         if (!p->pic_deblock) { p->pic_deblock = 1; p->pic_alpha = sh.alpha_off; p->pic_beta = sh.beta_off; }
-        else if (sh.alpha_off != p->pic_alpha || sh.beta_off != p->pic_beta) { ERR(p, "per-slice deblocking offsets unsupported"); return -1; }
     }
+    /* the device adds every macroblock's deltas to the picture's offsets: this slice's minus those of the first slice that filters */
+    p->slice_flags = sh.disable_deblock == 1 ? 0 : (uint16_t)(((sh.alpha_off - p->pic_alpha) & 255) | ((sh.beta_off - p->pic_beta) & 255) << 8);
     p->sh = sh;
     if (sh.type == P264_SLICE_P || sh.type == P264_SLICE_B) {
-        int prev[P264HIP_MAX_REFS], n_prev = p->n_list0, prev1[P264HIP_MAX_REFS], n_prev1 = p->n_list1;
-        memcpy(prev, p->list0, sizeof prev); memcpy(prev1, p->list1, sizeof prev1);
+        /* the slice's own lists; reference indices are resolved through ONE list 0 (and one list 1) per picture on the device: the
+         * canonical lists, onto which the slice's are mapped below */
         if ((p->n_list0 = build_list(p, &sh, 0, p->list0)) < 0) { p->n_list0 = 0; return -1; }
-        /* reference indices are resolved through ONE list 0 (and one list 1) per picture on the device */
-        if (n_prev && (n_prev != p->n_list0 || memcmp(prev, p->list0, sizeof(int) * (size_t)n_prev))) { ERR(p, "slices of one picture with different reference lists unsupported"); return -1; }
         if (sh.type == P264_SLICE_B) {
             if (!p->has_col) { ERR(p, "B slice without list-1 storage (Baseline parameter set)"); return -1; }
             if ((p->n_list1 = build_list(p, &sh, 1, p->list1)) < 0) { p->n_list1 = 0; return -1; }
-            if (n_prev1 && (n_prev1 != p->n_list1 || memcmp(prev1, p->list1, sizeof(int) * (size_t)n_prev1))) { ERR(p, "slices of one picture with different reference lists unsupported"); return -1; }
             if (p->sh0.type != P264_SLICE_B && p->slice_no > 0 && p->sh0.type == P264_SLICE_P) { ERR(p, "P and B slices in one picture unsupported"); return -1; }
             p->sh0.type = P264_SLICE_B;           /* a picture with any B slice is reconstructed as B */
-            p->weighted_bipred = pps->weighted_bipred == 2;
-            implicit_weights(p);
+            p->weighted_bipred = pps->weighted_bipred == 2;          /* (the weights themselves: on the canonical lists, when the picture is complete) */
         } else {
             if (p->sh0.type == P264_SLICE_B) { ERR(p, "P and B slices in one picture unsupported"); return -1; }
             p->sh0.type = P264_SLICE_P;           /* a picture with any P slice is reconstructed as P */
@@ -1442,11 +1507,12 @@ static int decode_slice(p264parse *p, int nal_type, int nal_ref_idc, const uint8
         if (!p->pic_wp_set) {
             p->pic_wp_set = 1;
             p->sh0.wp = sh.wp; p->sh0.wp_denom[0] = sh.wp_denom[0]; p->sh0.wp_denom[1] = sh.wp_denom[1];
-            memcpy(p->sh0.wp_tab, sh.wp_tab, sizeof sh.wp_tab);
+            memcpy(p->sh0.wp_tab, sh.wp_tab, sizeof sh.wp_tab); memcpy(p->wp_first, sh.wp_tab, sizeof sh.wp_tab);
         } else if (sh.wp != p->sh0.wp || (sh.wp && (sh.wp_denom[0] != p->sh0.wp_denom[0] || sh.wp_denom[1] != p->sh0.wp_denom[1]
-                                                     || memcmp(sh.wp_tab, p->sh0.wp_tab, sizeof sh.wp_tab)))) {
+                                                     || memcmp(sh.wp_tab, p->wp_first, sizeof sh.wp_tab)))) {
             ERR(p, "slices of one picture with different weight tables unsupported"); return -1;
         }
+        if (map_slice_list(p, 0) < 0 || (sh.type == P264_SLICE_B && map_slice_list(p, 1) < 0)) { p->pic_open = 0; return -1; }
     }
     p->qp_pred = sh.qp;
     /* The reference's QP bookkeeping (delta added to the slice QP, last QP carried over residual-free macroblocks and across
@@ -1498,8 +1564,13 @@ static int decode_slice(p264parse *p, int nal_type, int nal_ref_idc, const uint8
         p->next_mb++;
     }
     }
+    end_slice(p, sh.first_mb, p->next_mb);
     if (p->next_mb < p->n_mb) return 0;                       /* wait for the next slice of this picture */
 
+    /* the picture as the device gets it, and as reference marking reads it: the canonical lists */
+    p->n_list0 = p->n_pic_list[0]; memcpy(p->list0, p->pic_list[0], sizeof p->list0);
+    p->n_list1 = p->n_pic_list[1]; memcpy(p->list1, p->pic_list[1], sizeof p->list1);
+    if (p->sh0.type == P264_SLICE_B) implicit_weights(p);     /* a function of the picture pair: per canonical pair */
     if (p->sh0.type == P264_SLICE_B && p->pic_wp_set && p->sh0.wp && bipred_sums_bad(p)) { p->pic_open = 0; return -1; }
     publish_picture(p);
     *pic = &p->desc[p->cur];

@@ -54,6 +54,21 @@
  *                            per picture one byte per macroblock: the availability the writer assumed, then its Intra4x4 modes;
  *                            [--intra-pct N] N % (up to 80) of the macroblocks of P / B pictures intra instead of 4 / 5 %.  Without
  *                            these options the streams are what they were, byte for byte.
+ *            [--slice-deblock] every slice its own disable_deblocking_filter_idc (0, 1 or 2) and slice_alpha_c0_offset_div2 /
+ *                            slice_beta_offset_div2 (-6 .. 6), some slices repeating the slice before them
+ *            [--slice-lists] (with --refs >= 2 and --slices >= 2; not with --mmco) every P / B slice its own reference lists: some
+ *                            are left alone, the others reorder list 0 and list 1 independently (ref_pic_list_reordering, short-term
+ *                            commands), and - without explicit weights, whose table is one per picture - some carry their own
+ *                            num_ref_idx_active_override lengths; the macroblocks are written against the slice's lists
+ *            [--slice-lists-many] with --slice-lists, --wp and four reference frames: every P slice lists the four frames twice
+ *                            (eight entries, eight different weights), each slice rotated by one: three slices need 24 different
+ *                            (frame, weights) entries - a stream for a decoder that keeps one list per picture to refuse
+ *            [--dump-slices f] per picture: per macroblock four bytes - its slice, that slice's idc, alpha and beta offsets (signed) -
+ *                            then int16 [list 0, list 1][macroblock][8x8 quadrant]: the PICTURE (decode-order number) the writer
+ *                            means the quadrant to predict from through that list, -1 = none; skipped and direct macroblocks as
+ *                            the writer's mirror of the decoder infers them; then int16 the number of slices and per slice and
+ *                            list its length and its entries as picture numbers.
+ *                            None of these draws a random number unless asked for.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -189,7 +204,12 @@ static int opt_idc = 0;                     /* --deblock-idc 2: no filtering acr
 /* --bframes N: N non-reference B pictures between consecutive reference pictures (Main profile, picture order count type 0) */
 static int opt_bframes = 0, opt_temporal = 0, opt_implicit = 0, opt_d8inf = 0;
 static int cur_poc, n_active1 = 1, blist[2][8], blist_n[2], cur_entry = -1;      /* B picture: its order count and its two lists as indices into wdpb */
-static int opt_slices = 1, slice_first;     /* --slices: equal runs of macroblocks; slice_first = first MB of the current slice */
+static int opt_slice_deblock = 0, opt_slice_lists = 0, opt_slice_lists_many = 0;
+static FILE *dump_slices;
+static int8_t *w_slice;                     /* [mb][4]: slice, idc, alpha, beta */
+static int16_t *w_qpic[2];                  /* [mb][16]: the picture every 4x4 block predicts from, per list (-1 none) */
+static int16_t w_slists[64][2][17]; static int w_nslices;   /* per slice and list: the length, then the list as picture numbers */
+static int opt_slices = 1, slice_first;    /* --slices: equal runs of macroblocks; slice_first = first MB of the current slice */
 /* a neighbour is usable for prediction when it was coded earlier IN THE SAME SLICE (H.264 6.4.x) */
 static int avail(int mbx, int mby) { return mbx >= 0 && mby >= 0 && mbx < W && mby < H && mby * W + mbx < cur && mby * W + mbx >= slice_first; }
 
@@ -605,6 +625,36 @@ static int model_list0(int frame_num, int max_fn, int *list)
     return n;
 }
 
+/* ref_pic_list_reordering commands (7.3.3.1, 8.2.4.3.1; short-term pictures) that put the pictures with the frame_nums fn[0 .. k)
+ * at the head of a list, in that order */
+static void put_reordering(bw_t *b, const int *fn, int k, int cur_fn, int max_fn)
+{
+    int pred = cur_fn;
+    bw_put(b, 1, 1);
+    for (int i = 0; i < k; i++) {
+        const int d = fn[i] - pred;                    /* both in 0 .. MaxFrameNum - 1 */
+        if (d < 0) { bw_ue(b, 0); bw_ue(b, (uint32_t)(-d - 1)); }
+        else if (d > 0) { bw_ue(b, 1); bw_ue(b, (uint32_t)(d - 1)); }
+        else { bw_ue(b, 0); bw_ue(b, (uint32_t)(max_fn - 1)); }      /* the same picture again: a difference of MaxPicNum */
+        pred = fn[i];
+    }
+    bw_ue(b, 3);
+}
+/* what the commands make of a list (8.2.4.3.1): the picked entries, then the initial list (its first len entries, the last one
+ * repeated where it is shorter) without them, cut to len */
+static void reordered_list(const int *init, int n_init, int len, const int *picked, int k, int *out)
+{
+    int n = 0;
+    for (int i = 0; i < k && n < len; i++) out[n++] = picked[i];
+    for (int i = 0; i < len && n < len; i++) {
+        const int e = init[i < n_init ? i : n_init - 1];
+        int taken = 0;
+        for (int j = 0; j < k; j++) if (picked[j] == e) taken = 1;
+        if (!taken) out[n++] = e;
+    }
+    while (n < len) { out[n] = out[n - 1]; n++; }
+}
+
 static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int idr_id, int log2_fn, int refs_available, int pic_no)
 {
     const int max_fn = 1 << log2_fn;
@@ -619,6 +669,23 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
         b_build_lists();
         n_active = blist_n[0] > 4 ? 4 : blist_n[0]; n_active1 = blist_n[1] > 4 ? 4 : blist_n[1];
     }
+    /* --slice-lists / --dump-slices: the lists before any reordering, as entries 0 .. n - 1 with their picture, frame_num (P) or
+     * frame-store entry (B); taken here, before this picture's marking changes the model */
+    int init_pic[8] = { 0 }, init_fn[8] = { 0 }, n_init = 0, binit[2][8], binit_n[2] = { 0, 0 }, sl_prev[3] = { 0, 0, 0 };
+    if (is_p && (opt_slice_lists || dump_slices)) {
+        if (opt_mmco || opt_bframes) {
+            n_init = n_full;
+            for (int i = 0; i < n_full; i++) { init_pic[i] = full[i]; for (int e = 0; e < 8; e++) if (wdpb[e].used && wdpb[e].pic == full[i]) init_fn[i] = wdpb[e].frame_num; }
+        } else {
+            n_init = refs_available < opt_refs ? refs_available : opt_refs;
+            for (int i = 0; i < n_init; i++) { init_pic[i] = pic_no - 1 - i; init_fn[i] = (frame_num - 1 - i) & (max_fn - 1); }
+        }
+    }
+    memset(binit, 0, sizeof binit);
+    if (is_b) { memcpy(binit, blist, sizeof binit); binit_n[0] = blist_n[0]; binit_n[1] = blist_n[1]; }
+    const int many = opt_slice_lists_many && is_p && opt_wp && n_init == 4;
+    if (many) n_active = 8;
+    const int pic_n_active = n_active, pic_n_active1 = n_active1;
     wp_on = (is_p && opt_wp) || (is_b && opt_wp_bi);
     if (wp_on) wp_draw(is_b, n_active, is_b ? n_active1 : 0);
     /* ---- reference picture marking of this picture (decided once, written into every slice header) ---- */
@@ -681,6 +748,50 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
         const int first = (int)((long)NMB * sl / opt_slices), end = (int)((long)NMB * (sl + 1) / opt_slices);
         if (first == end) continue;
         slice_first = first;
+        /* ---- this slice's loop filter and lists ---- */
+        int s_idc = opt_deblock ? opt_idc : 1, s_alpha = opt_alpha, s_beta = opt_beta;
+        if (opt_slice_deblock && opt_deblock) {
+            if (sl > 0 && pct(25)) { s_idc = sl_prev[0]; s_alpha = sl_prev[1]; s_beta = sl_prev[2]; }     /* equal to the slice before */
+            else { static const int idcs[4] = { 0, 0, 2, 1 }; s_idc = idcs[rnd(4)]; s_alpha = rnd(13) - 6; s_beta = rnd(13) - 6; }
+            sl_prev[0] = s_idc; sl_prev[1] = s_alpha; sl_prev[2] = s_beta;
+        }
+        int spic[2][16], n_picked[2] = { 0, 0 }, picked_fn[2][16];
+        memset(spic, 0xff, sizeof spic);
+        n_active = pic_n_active; n_active1 = pic_n_active1;
+        if (is_b) { memcpy(blist, binit, sizeof blist); blist_n[0] = binit_n[0]; blist_n[1] = binit_n[1]; }
+        if (opt_slice_lists && (is_p || is_b)) {
+            for (int X = 0; X < (is_b ? 2 : 1); X++) {
+                const int ni = is_b ? binit_n[X] : n_init;
+                int len = X ? pic_n_active1 : pic_n_active, idx[16], init_idx[8], list[16], k = 0;
+                for (int i = 0; i < 8; i++) init_idx[i] = i;
+                if (many) {                                   /* the four frames twice, rotated by the slice's number: all eight entries named */
+                    k = 8;
+                    for (int i = 0; i < 8; i++) idx[i] = (i + sl) & 3;
+                    for (int i = 0; i < 8; i++) list[i] = idx[i];
+                } else {
+                    if (!wp_on && ni > 1 && pct(50)) len = 1 + rnd(ni < 4 ? ni : 4);
+                    if (ni > 1 && pct(sl ? 65 : 35)) {
+                        k = 1 + rnd(len);
+                        for (int i = 0; i < k; i++) { int again; do { idx[i] = rnd(ni); again = 0; for (int j = 0; j < i; j++) again |= idx[j] == idx[i]; } while (again); }
+                    }
+                    reordered_list(init_idx, ni, len, idx, k, list);
+                }
+                n_picked[X] = k;
+                for (int i = 0; i < k; i++) picked_fn[X][i] = is_b ? wdpb[binit[X][idx[i]]].frame_num : init_fn[idx[i]];
+                for (int i = 0; i < len; i++) {
+                    if (is_b) { blist[X][i] = binit[X][list[i]]; spic[X][i] = wdpb[blist[X][i]].pic; }
+                    else spic[X][i] = init_pic[list[i]];
+                }
+                if (is_b) blist_n[X] = len;
+                if (X) n_active1 = len; else n_active = len;
+            }
+        } else if (is_p && n_init) {
+            for (int i = 0; i < n_active; i++) spic[0][i] = init_pic[i < n_init ? i : n_init - 1];
+            if (slice_reordered) { const int t = spic[0][0]; spic[0][0] = spic[0][1]; spic[0][1] = t; }
+            else if (opt_wp_dup && n_active > 1) { for (int i = n_active - 1; i > 1; i--) spic[0][i] = spic[0][i - 1]; spic[0][1] = spic[0][0]; }
+        } else if (is_b) {
+            for (int X = 0; X < 2; X++) for (int i = 0; i < (X ? n_active1 : n_active); i++) spic[X][i] = wdpb[blist[X][i < blist_n[X] ? i : blist_n[X] - 1]].pic;
+        }
         bw_t b = { 0 };
         bw_ue(&b, (uint32_t)first);                 /* first_mb_in_slice */
         bw_ue(&b, is_b ? 6 : is_p ? 5 : 7);         /* slice_type: all slices of the picture alike */
@@ -691,12 +802,15 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
         if (is_b) {
             bw_put(&b, 1, (uint32_t)!opt_temporal);                   /* direct_spatial_mv_pred_flag */
             bw_put(&b, 1, 1); bw_ue(&b, (uint32_t)(n_active - 1)); bw_ue(&b, (uint32_t)(n_active1 - 1));   /* num_ref_idx_active_override */
-            bw_put(&b, 1, 0); bw_put(&b, 1, 0);                       /* no reordering of list 0, list 1 */
+            for (int X = 0; X < 2; X++) {                             /* reordering of list 0, list 1 (--slice-lists), or none */
+                if (n_picked[X]) put_reordering(&b, picked_fn[X], n_picked[X], frame_num, max_fn); else bw_put(&b, 1, 0);
+            }
         }
         if (is_p) {
             if (opt_refs > 1) { bw_put(&b, 1, 1); bw_ue(&b, (uint32_t)(n_active - 1)); }   /* num_ref_idx_active_override */
             else bw_put(&b, 1, 0);
-            if (opt_reorder && n_active > 1 && slice_reordered) {
+            if (opt_slice_lists) { if (n_picked[0]) put_reordering(&b, picked_fn[0], n_picked[0], frame_num, max_fn); else bw_put(&b, 1, 0); }
+            else if (opt_reorder && n_active > 1 && slice_reordered) {
                 /* list 0 starts as (frame_num - 1, frame_num - 2); "subtract 2 from the prediction" puts frame_num - 2 first */
                 bw_put(&b, 1, 1); bw_ue(&b, 0); bw_ue(&b, 1); bw_ue(&b, 3);
             } else if (opt_wp_dup && n_active > 1) {
@@ -718,8 +832,8 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
         } else bw_put(&b, 1, 0);                            /* sliding-window marking */
         if (opt_cabac && (is_p || is_b)) bw_ue(&b, (uint32_t)(pic_no % 3));   /* cabac_init_idc */
         bw_se(&b, 0);                               /* slice_qp_delta */
-        bw_ue(&b, (uint32_t)(opt_deblock ? opt_idc : 1)); /* disable_deblocking_filter_idc: 0 also across slice boundaries, 2 not */
-        if (opt_deblock) { bw_se(&b, opt_alpha); bw_se(&b, opt_beta); }
+        bw_ue(&b, (uint32_t)s_idc);                 /* disable_deblocking_filter_idc: 0 also across slice boundaries, 2 not, 1 no filter */
+        if (s_idc != 1) { bw_se(&b, s_alpha); bw_se(&b, s_beta); }
         int skip_run = 0;
         slice_kind = is_b ? 2 : is_p ? 1 : 0;
         w_last_dqp = 0;
@@ -762,8 +876,32 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
         }
         write_nal(f, is_b ? 0 : 3, idr ? 5 : 1, &b);
         free(b.buf);
+        if (w_slice && w_nslices < 64) {
+            for (int X = 0; X < 2; X++) {
+                const int len = !(is_p || is_b) || (X && !is_b) ? 0 : X ? n_active1 : n_active;
+                w_slists[w_nslices][X][0] = (int16_t)len;
+                for (int i = 0; i < len; i++) w_slists[w_nslices][X][1 + i] = (int16_t)spic[X][i];
+            }
+            w_nslices++;
+        }
+        if (w_slice) for (int m = first; m < end; m++) {              /* what this slice's macroblocks mean, while its lists are at hand */
+            w_slice[m * 4] = (int8_t)sl; w_slice[m * 4 + 1] = (int8_t)s_idc; w_slice[m * 4 + 2] = (int8_t)(s_idc == 1 ? 0 : s_alpha); w_slice[m * 4 + 3] = (int8_t)(s_idc == 1 ? 0 : s_beta);
+            for (int k = 0; k < 16; k++) {
+                const int inter = (is_p || is_b) && mb_type[m] > T_PCM, r0 = inter ? refs[m * 16 + k] : -1, r1 = inter && is_b ? refs1[m * 16 + k] : -1;
+                w_qpic[0][m * 16 + k] = (int16_t)(r0 < 0 ? -1 : spic[0][r0 & 15]);
+                w_qpic[1][m * 16 + k] = (int16_t)(r1 < 0 ? -1 : spic[1][r1 & 15]);
+            }
+        }
     }
     slice_first = 0;
+    if (dump_slices) {
+        fwrite(w_slice, 1, (size_t)NMB * 4, dump_slices);
+        for (int X = 0; X < 2; X++) for (int m = 0; m < NMB; m++) for (int q = 0; q < 4; q++) fwrite(&w_qpic[X][m * 16 + (q >> 1) * 8 + (q & 1) * 2], 2, 1, dump_slices);
+        const int16_t ns = (int16_t)w_nslices;
+        fwrite(&ns, 2, 1, dump_slices);
+        for (int k = 0; k < w_nslices; k++) for (int X = 0; X < 2; X++) fwrite(w_slists[k][X], 2, (size_t)(1 + w_slists[k][X][0]), dump_slices);
+    }
+    w_nslices = 0;
     if (dump_pcm) {
         const uint32_t n = (uint32_t)pcm_n;
         fwrite(&n, 4, 1, dump_pcm);
@@ -850,10 +988,16 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--constrained-intra")) opt_cintra = 1;
         else if (!strcmp(a, "--intra-pct")) { opt_intra_pct = v < 0 ? 0 : v > 80 ? 80 : v; i++; }
         else if (!strcmp(a, "--dump-avail")) { dump_avail = fopen(argv[i + 1], "wb"); i++; }
+        else if (!strcmp(a, "--slice-deblock")) opt_slice_deblock = 1;
+        else if (!strcmp(a, "--slice-lists")) opt_slice_lists = 1;
+        else if (!strcmp(a, "--slice-lists-many")) opt_slice_lists = opt_slice_lists_many = 1;
+        else if (!strcmp(a, "--dump-slices")) { dump_slices = fopen(argv[i + 1], "wb"); i++; }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
     if (W < 1 || H < 1 || W > 512 || H > 512 || frames < 1 || opt_qp < 0 || opt_qp > 51 || opt_refs < 1 || opt_refs > ((opt_mmco || opt_bframes) ? 4 : 2) || (opt_bframes && (opt_refs < 2 || opt_bframes > 4)) || opt_alpha < -6 || opt_alpha > 6 || opt_beta < -6 || opt_beta > 6) { fprintf(stderr, "bad geometry\n"); return 2; }
+    if (opt_slice_lists && (opt_mmco || opt_refs < 2 || opt_reorder || opt_wp_dup)) { fprintf(stderr, "--slice-lists needs --refs >= 2 and excludes --mmco, --reorder, --wp-dup\n"); return 2; }
     NMB = W * H;
+    if (opt_slice_lists || dump_slices) { w_slice = calloc((size_t)NMB, 4); w_qpic[0] = malloc((size_t)NMB * 32); w_qpic[1] = malloc((size_t)NMB * 32); }
     g_rng = seed * 0x9e3779b97f4a7c15ull + 264;
     w_alloc();
     if (opt_ipcm) { pcm_idx = calloc((size_t)NMB, 4); pcm_bytes = malloc((size_t)NMB * 384); }
@@ -906,6 +1050,7 @@ int main(int argc, char **argv)
         if (dump_wp) fclose(dump_wp);
         if (dump_pcm) fclose(dump_pcm);
         if (dump_avail) fclose(dump_avail);
+        if (dump_slices) fclose(dump_slices);
         return 0;
     }
     for (int n = 0; n < frames; n++) {
@@ -923,5 +1068,6 @@ int main(int argc, char **argv)
     if (dump_wp) fclose(dump_wp);
     if (dump_pcm) fclose(dump_pcm);
     if (dump_avail) fclose(dump_avail);
+    if (dump_slices) fclose(dump_slices);
     return 0;
 }

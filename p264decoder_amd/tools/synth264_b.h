@@ -229,7 +229,8 @@ static void b_save_col(wdpb_t *e, int is_intra_picture)
         const int intra = is_intra_picture || mb_type[i >> 4] <= T_PCM;
         const int r = intra ? -1 : refs[i];
         e->cref[i] = (int8_t)r;
-        e->cpic[i] = r < 0 ? -1 : wlist[r < wlist_n ? r : wlist_n - 1];
+        /* (--slice-lists: the index means what its own slice's list says - recorded per block when the slice ended) */
+        e->cpic[i] = r < 0 ? -1 : w_qpic[0] ? w_qpic[0][i] : wlist[r < wlist_n ? r : wlist_n - 1];
         e->cmv[i * 2] = r < 0 ? 0 : mvs[i * 2]; e->cmv[i * 2 + 1] = r < 0 ? 0 : mvs[i * 2 + 1];
     }
 }

@@ -1,0 +1,105 @@
+"""Per-macroblock filter offsets (`flags`, include/p264hip.h) on the MI355X: the families of tests/slice_filter_fuzz.py - pictures
+of seam_fuzz.make_picture (P, B, I, sliced, lists that hold a frame twice, explicit weights, I_PCM), deltas per slice run or per
+macroblock over the whole int8 range or over -12 .. 12, next to pictures without deltas in the same launch - against the oracle's
+unfiltered reconstruction followed by tests/slice_filter_checker.py.  Bytes of all three planes, every picture, no tolerance.
+
+Every family goes through the compact upload and one p264hip_reconstruct call (one stream per picture), and picture by picture
+through p264hip_submit; the launch info says which edge-info instance ran (the role fused into k_intra_sparse, k_deblock_bs<false>,
+k_deblock_bs<true>).  Three families - one per instance - repeat at the launch shapes of tests/test_gpu_batch_shapes.py.  What the
+comparisons cover is asserted on the CPU (tests/test_slice_filter_cpu.py::test_coverage_of_the_drawn_families).
+
+All of it fails on kernels that ignore `flags`: the pictures with deltas come out filtered with the picture's offsets."""
+import pytest
+
+from p264decoder_amd import HipReconstructor
+from tests import slice_filter_fuzz as sff
+from tests.test_gpu_batch_shapes import SHAPES
+from tests.test_gpu_seam_fuzz import compare
+
+pytestmark = pytest.mark.gpu
+
+
+def check_instance(name, li):
+    instance = sff.FAMILIES[name][2]
+    assert (li["edge_info_fused"] > 0) == (instance == "fused"), (name, li)
+
+
+def run_family(lib, oracle, name, road):
+    mb_w, mb_h, instance, _ = sff.FAMILIES[name]
+    cases, counts = sff.family(oracle, name)
+    n = len(cases)
+    hip = HipReconstructor(mb_w, mb_h, n_streams=n, slots=sff.SLOTS, max_pictures=n, lib=lib)
+    try:
+        for s, c in enumerate(cases):
+            for slot, f in enumerate(c.refs):
+                hip.write_frame(s, slot, *f)
+        if road == "compact":
+            for s, c in enumerate(cases):
+                hip.upload_compact(s, c.pic, HipReconstructor.pack_compact(c.pic, lib))
+            hip.reconstruct(list(range(n)), list(range(n)))
+            li = hip.last_launch()
+            assert li["pictures"] == n
+            check_instance(name, li)
+            for s, c in enumerate(cases):
+                compare(hip.read_frame(s, sff.DST), c.want, "%s stream %d of %d, compact upload, deltas %s" % (name, s, n, c.mode), c.pic)
+        else:
+            for s, c in enumerate(cases):
+                hip.submit(s, c.pic)
+                compare(hip.read_frame(s, sff.DST), c.want, "%s stream %d, p264hip_submit, deltas %s" % (name, s, c.mode), c.pic)
+        hip.sync()
+    finally:
+        hip.close()
+
+
+@pytest.mark.parametrize("road", ["compact", "submit"])
+@pytest.mark.parametrize("name", list(sff.FAMILIES))
+def test_slice_filter_fuzz(lib, oracle, name, road):
+    run_family(lib, oracle, name, road)
+
+
+@pytest.mark.parametrize("rb,per_wg,intra_waves", SHAPES)
+@pytest.mark.parametrize("name", ["p_plain", "p_with_i", "b_mix"])
+def test_slice_filter_fuzz_at_every_launch_shape(lib, oracle, name, rb, per_wg, intra_waves, monkeypatch):
+    monkeypatch.setenv("P264AMD_DEBLOCK_RB_LOG2", rb)
+    monkeypatch.setenv("P264AMD_DEBLOCK_PICS_PER_WG", per_wg)
+    monkeypatch.setenv("P264AMD_INTRA_WAVES", intra_waves)
+    run_family(lib, oracle, name, "compact")
+
+
+@pytest.mark.parametrize("name", ["b_mix", "pcm_p"])
+def test_every_road_into_a_slot_carries_the_deltas(lib, oracle, name):
+    """plain upload, the packed block, the compact block, reserve / commit (the device's record check in front of the launch) and
+    p264hip_clone_picture - the picture of stream s goes in by road s % 5, all in one launch"""
+    mb_w, mb_h, instance, _ = sff.FAMILIES[name]
+    cases, _ = sff.family(oracle, name)
+    n = len(cases)
+    hip = HipReconstructor(mb_w, mb_h, n_streams=n, slots=sff.SLOTS, max_pictures=2 * n, lib=lib)
+    try:
+        roads = []
+        for s, c in enumerate(cases):
+            for slot, f in enumerate(c.refs):
+                hip.write_frame(s, slot, *f)
+            road = ("upload", "packed", "compact", "commit", "clone")[s % 5]
+            roads.append(road)
+            if road == "upload":
+                hip.upload(s, [c.pic])
+            elif road == "packed":
+                hip.upload_packed(s, c.pic, HipReconstructor.pack(c.pic, lib))
+            elif road == "compact":
+                hip.upload_compact(s, c.pic, HipReconstructor.pack_compact(c.pic, lib))
+            elif road == "commit":
+                blk = HipReconstructor.pack(c.pic, lib)
+                dev, size = hip.input_reserve(s, c.pic)
+                assert size == blk.size and lib.p264hip_copy_to_device(dev, blk.ctypes.data, size) == 0
+                hip.input_commit(s)
+            else:
+                hip.upload(n + s, [c.pic])
+                hip.clone_picture(s, n + s)
+        assert len(set(roads)) == min(n, 5)
+        hip.reconstruct(list(range(n)), list(range(n)))
+        check_instance(name, hip.last_launch())
+        for s, c in enumerate(cases):
+            compare(hip.read_frame(s, sff.DST), c.want, "%s stream %d by %s, deltas %s" % (name, s, roads[s], c.mode), c.pic)
+        hip.sync()
+    finally:
+        hip.close()
