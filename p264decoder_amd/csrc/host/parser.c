@@ -41,15 +41,15 @@ typedef struct {
 
 typedef struct {
     int valid, sps_id, cabac, pic_order_present, num_slice_groups;
-    int num_ref_idx_l0, num_ref_idx_l1, weighted_pred, weighted_bipred;
+    int num_ref_idx[2], weighted_pred, weighted_bipred;    /* num_ref_idx: the default active length per list */
     int pic_init_qp, chroma_qp_offset, deblock_ctrl, constrained_intra, redundant_pic_cnt;
 } pps_t;
 
 typedef struct {
     int first_mb, type, pps_id, frame_num, idr_pic_id;
-    int num_ref_idx, qp, disable_deblock, alpha_off, beta_off;
-    int n_reorder; struct { int idc, arg; } reorder[34];
-    int num_ref_idx_l1, n_reorder1; struct { int idc, arg; } reorder1[34];   /* B slices: list 1 */
+    int qp, disable_deblock, alpha_off, beta_off;
+    int num_ref_idx[2], n_reorder[2];                /* per list ([1]: B slices) */
+    struct { int idc, arg; } reorder[2][34];
     int poc_lsb, delta_poc_bottom, direct_spatial, cabac_init_idc;
     int no_output_of_prior, long_term_flag, adaptive_marking;
     int n_mmco; struct { int op, a, b; } mmco[34];   /* memory_management_control_operation 1..6 and its operands */
@@ -61,16 +61,36 @@ typedef struct { int used, frame_num, pic_num, is_long, long_idx;   /* long_idx 
                  int poc; uint32_t uid; } dpb_frame_t;              /* picture order count; uid: which decoded picture the slot holds */
 
 typedef struct {
-    p264hip_mb_t *mb; int16_t *mv; int8_t *ref; uint8_t *i4; int16_t *coef;
-    int16_t *mv1; int8_t *ref1;               /* list 1 (B pictures; allocated with the others for non-Baseline streams) */
+    p264hip_mb_t *mb; int16_t *mv[2]; int8_t *ref[2]; uint8_t *i4; int16_t *coef;   /* mv, ref: per list ([1]: B pictures; allocated for non-Baseline streams) */
     size_t coef_cap, coef_n;
-    /* mb, mv, ref, i4 and coef are sections of ONE allocation laid out like an input slot of the HIP layer (p264hip_input_layout:
+    /* mb, mv[0], ref[0], i4 and coef are sections of ONE allocation laid out like an input slot of the HIP layer (p264hip_input_layout:
      * records | vectors | reference indices | intra 4x4 modes | coded levels, each on a 256-byte boundary), so that a picture goes
      * host -> HBM as one copy (p264hip_upload / _upload_async notice it); coef_own: the coded levels outgrew their section and
      * moved to an allocation of their own (the picture then travels in pieces, as every picture did until round 5) */
     uint8_t *block; int coef_own;
     void *(*alloc)(size_t); void (*release)(void *);   /* where the arrays live (p264parse_set_allocator) */
 } picbuf_t;
+
+/* The picture being built: everything that is a property of the PICTURE, from its first slice to the hand-over. */
+typedef struct {
+    int open, is_idr, ref_idc;
+    int next_mb, slice_no;
+    int poc; uint32_t uid;                    /* picture order count (8.2.1); which decoded picture this is */
+    slice_t first;                            /* header of the first slice: written when the picture opens, read-only from then on (marking and
+                                               * the order count read frame_num, poc_lsb, delta_poc_bottom, long_term_flag, the marking commands) */
+    /* what the device gets */
+    int type;                                 /* P264_SLICE_*: B with any B slice, P with any P slice, else I */
+    int deblock, alpha, beta;                 /* loop filter: on if any slice enables it, offsets of the first such slice */
+    /* the CANONICAL lists: the first P / B slice's verbatim; a later slice's entries are mapped onto them (ref_map: slice index ->
+     * canonical index), new ones appended, and the indices the slice wrote are rewritten when it ends (end_slice) */
+    int list[2][P264HIP_MAX_REFS], n_list[2];
+    /* explicit weights: taken from the first P / B slice (wp_set).  wp_tab is the canonical table, which grows with the canonical
+     * lists; wp_coded stays the first slice's table as coded: what every other slice's must equal */
+    int wp_set, wp, wp_denom[2];
+    int16_t wp_tab[2][P264HIP_MAX_REFS][3][2], wp_coded[2][P264HIP_MAX_REFS][3][2];
+    int weighted_bipred;
+    int16_t bipred_weight[P264HIP_MAX_REFS * P264HIP_MAX_REFS];   /* implicit weights (8.4.2.3.1) */
+} curpic_t;
 
 struct p264parse {
     int opts;
@@ -86,29 +106,17 @@ struct p264parse {
     uint8_t  *nnz;                            /* [n_mb][24] total_coeff per 4x4 block */
     uint16_t *slice_of;                       /* [n_mb] slice number inside the picture, 0xffff = not decoded */
 
-    int pic_open, next_mb, slice_no;
-    int pic_is_idr, pic_ref_idc;
+    curpic_t pic;
+    /* slice scope */
     slice_t sh;                               /* current slice */
-    slice_t sh0;                              /* first slice of the picture */
-    int pic_deblock, pic_alpha, pic_beta;     /* loop filter of the picture: on if any slice enables it, offsets of the first such slice */
     uint16_t slice_flags;                     /* the records' `flags` of the current slice: its offsets minus the picture's (include/p264hip.h) */
-    /* The lists of the CURRENT SLICE: what its macroblocks are parsed against (vector prediction, CABAC contexts, skip / direct
-     * inference and temporal direct's list-0 mapping are slice-local).  Between pictures - publish_picture, finish_picture_marking -
-     * they hold the picture's canonical lists. */
-    int list0[P264HIP_MAX_REFS], n_list0;
-    int list1[P264HIP_MAX_REFS], n_list1;     /* B pictures */
-    /* The picture's CANONICAL lists, the ones the device gets: the first P / B slice's verbatim; a later slice's entries are
-     * mapped onto them (ref_map: slice index -> canonical index), new ones appended, and the indices the slice wrote are
-     * rewritten when it ends (end_slice) */
-    int pic_list[2][P264HIP_MAX_REFS], n_pic_list[2];
+    /* the slice's OWN lists: what its macroblocks are parsed against (vector prediction, CABAC contexts, skip / direct inference and
+     * temporal direct's list-0 mapping are slice-local) and what end_slice resolves its indices through */
+    int list[2][P264HIP_MAX_REFS], n_list[2];
     int8_t ref_map[2][P264HIP_MAX_REFS]; int ref_map_used[2];
-    int16_t wp_first[2][P264HIP_MAX_REFS][3][2];   /* the first P / B slice's weight table: what every other slice's must equal (p->sh0.wp_tab grows) */
-    int16_t bipred_weight[P264HIP_MAX_REFS * P264HIP_MAX_REFS];   /* implicit weights of the picture (8.4.2.3.1) */
-    int weighted_bipred;
-    int pic_wp_set;                           /* the picture's explicit weight table: taken from its first P / B slice (p->sh0 keeps it) */
-    /* picture order count (8.2.1) */
-    int cur_poc, prev_poc_msb, prev_poc_lsb, prev_frame_num, frame_num_offset;
-    uint32_t next_uid, cur_uid;
+    /* picture order count (8.2.1): what the next picture measures its own against */
+    int prev_poc_msb, prev_poc_lsb, prev_frame_num, frame_num_offset;
+    uint32_t next_uid;
     /* motion of every reference picture, kept for the direct prediction of later B pictures (the co-located picture is
      * RefPicList1[0]): per frame-store slot, per 4x4 block the vector, per 8x8 the reference index it used and the uid of the
      * picture that index meant (-1 = intra) */
@@ -123,7 +131,7 @@ struct p264parse {
 
     /* current MB */
     int mbx, mby, mbi;
-    unsigned mv_done, mv_done1;               /* bit (y*4+x): that 4x4 of the current MB has its list-0 / list-1 motion */
+    unsigned mv_done[2];                      /* per list, bit (y*4+x): that 4x4 of the current MB has its motion */
     int      cur_avail;                       /* P264_AVAIL_* of the current MB (set by begin_mb) */
     int skip_run;
     /* CABAC (parser_cabac.h): the engine, and what context selection needs from earlier macroblocks */
@@ -205,9 +213,9 @@ static int parse_pps(p264parse *p, bitrd_t *b)
     q->pic_order_present = (int)br_u1(b);
     q->num_slice_groups = (int)br_ue(b) + 1;
     if (q->num_slice_groups > 1) { ERR(p, "FMO unsupported"); return -1; }
-    q->num_ref_idx_l0 = (int)br_ue(b) + 1;
-    q->num_ref_idx_l1 = (int)br_ue(b) + 1;
-    if (q->num_ref_idx_l0 < 1 || q->num_ref_idx_l0 > 32 || q->num_ref_idx_l1 < 1 || q->num_ref_idx_l1 > 32) { ERR(p, "pps: num_ref_idx out of range"); return -1; }
+    q->num_ref_idx[0] = (int)br_ue(b) + 1;
+    q->num_ref_idx[1] = (int)br_ue(b) + 1;
+    if (q->num_ref_idx[0] < 1 || q->num_ref_idx[0] > 32 || q->num_ref_idx[1] < 1 || q->num_ref_idx[1] > 32) { ERR(p, "pps: num_ref_idx out of range"); return -1; }
     q->weighted_pred = (int)br_u1(b);
     q->weighted_bipred = (int)br_u(b, 2);
     q->pic_init_qp = br_se(b) + 26;
@@ -219,7 +227,7 @@ static int parse_pps(p264parse *p, bitrd_t *b)
     if (br_eof(b)) { ERR(p, "incomplete PPS"); return -1; }
     q->valid = 1;
     INFO(p, "p264amd: pps:%u sps:%d %s ref0:%d QP:%d QC=%d DFC:%d CIP:%d\n", id, q->sps_id,
-         q->cabac ? "CABAC" : "CAVLC", q->num_ref_idx_l0, q->pic_init_qp, q->chroma_qp_offset,
+         q->cabac ? "CABAC" : "CAVLC", q->num_ref_idx[0], q->pic_init_qp, q->chroma_qp_offset,
          q->deblock_ctrl, q->constrained_intra);
     return (int)id;
 }
@@ -227,7 +235,7 @@ static int parse_pps(p264parse *p, bitrd_t *b)
 /* ---------------------------------------------------------------- context --------------- */
 static void release_bufs(picbuf_t *q)
 {
-    if (q->release) { q->release(q->block); if (q->coef_own) q->release(q->coef); if (q->mv1) q->release(q->mv1); if (q->ref1) q->release(q->ref1); }
+    if (q->release) { q->release(q->block); if (q->coef_own) q->release(q->coef); if (q->mv[1]) q->release(q->mv[1]); if (q->ref[1]) q->release(q->ref[1]); }
     memset(q, 0, sizeof *q);
 }
 /* A caller may still be reading the last completed picture's arrays when the next slice re-initialises the context (the
@@ -267,16 +275,16 @@ static int init_context(p264parse *p, int sps_id, int pps_id)
         q->block = (uint8_t *)q->alloc(lay.bytes);
         if (!q->block) return -1;
         q->mb  = (p264hip_mb_t *)(q->block + lay.off_mb);
-        q->mv  = (int16_t *)(q->block + lay.off_mv);
-        q->ref = (int8_t *)(q->block + lay.off_ref);
+        q->mv[0]  = (int16_t *)(q->block + lay.off_mv);
+        q->ref[0] = (int8_t *)(q->block + lay.off_ref);
         q->i4  = (uint8_t *)(q->block + lay.off_i4);
         q->coef = (int16_t *)(q->block + lay.off_coef); q->coef_own = 0;
-        memset(q->mb, 0, n * sizeof(p264hip_mb_t)); memset(q->mv, 0, n * 32 * sizeof(int16_t));
-        memset(q->ref, 0, n * 4); memset(q->i4, 0, n * 16);
+        memset(q->mb, 0, n * sizeof(p264hip_mb_t)); memset(q->mv[0], 0, n * 32 * sizeof(int16_t));
+        memset(q->ref[0], 0, n * 4); memset(q->i4, 0, n * 16);
         if (s->profile_idc != 66) {                 /* anything but Baseline may carry B slices: list-1 arrays */
-            q->mv1 = (int16_t *)q->alloc(n * 32 * sizeof(int16_t)); q->ref1 = (int8_t *)q->alloc(n * 4);
-            if (!q->mv1 || !q->ref1) return -1;
-            memset(q->mv1, 0, n * 32 * sizeof(int16_t)); memset(q->ref1, -1, n * 4);
+            q->mv[1] = (int16_t *)q->alloc(n * 32 * sizeof(int16_t)); q->ref[1] = (int8_t *)q->alloc(n * 4);
+            if (!q->mv[1] || !q->ref[1]) return -1;
+            memset(q->mv[1], 0, n * 32 * sizeof(int16_t)); memset(q->ref[1], -1, n * 4);
         }
     }
     if (s->profile_idc != 66) {
@@ -296,7 +304,7 @@ static int init_context(p264parse *p, int sps_id, int pps_id)
     p->cur_slot = 0;
     p->active_sps = sps_id; p->active_pps = pps_id;
     p->generation++;
-    p->pic_open = 0;
+    p->pic.open = 0;
     INFO(p, "p264amd: %dx%d\n", 16 * p->mb_w, 16 * p->mb_h);
     return 0;
 }
@@ -313,8 +321,7 @@ static int parse_pred_weight_table(p264parse *p, bitrd_t *b, slice_t *sh)
     sh->wp_denom[0] = (int)dl; sh->wp_denom[1] = (int)dc;
     const int isB = sh->type == P264_SLICE_B;
     for (int l = 0; l < (isB ? 2 : 1); l++) {
-        const int n = l ? sh->num_ref_idx_l1 : sh->num_ref_idx;
-        for (int i = 0; i < n; i++) {
+        for (int i = 0; i < sh->num_ref_idx[l]; i++) {
             int16_t (*e)[2] = sh->wp_tab[l][i];
             for (int c = 0; c < 3; c++) { e[c][0] = (int16_t)(1 << sh->wp_denom[c > 0]); e[c][1] = 0; }
             for (int k = 0; k < 2; k++) {                 /* luma_weight_lX_flag, then chroma_weight_lX_flag */
@@ -362,22 +369,21 @@ static int parse_slice_header(p264parse *p, bitrd_t *b, int nal_type, int nal_re
         if (pps->pic_order_present) br_se(b);
     }
     if (pps->redundant_pic_cnt && br_ue(b) != 0) return 1;       /* redundant picture: ignore the slice */
-    sh->num_ref_idx = 0;
     if (sh->type == P264_SLICE_B) sh->direct_spatial = (int)br_u1(b);
     if (sh->type == P264_SLICE_P || sh->type == P264_SLICE_B) {
-        sh->num_ref_idx = pps->num_ref_idx_l0; sh->num_ref_idx_l1 = pps->num_ref_idx_l1;
-        if (br_u1(b)) { sh->num_ref_idx = (int)br_ue(b) + 1; if (sh->type == P264_SLICE_B) sh->num_ref_idx_l1 = (int)br_ue(b) + 1; }
-        if (sh->num_ref_idx < 1 || sh->num_ref_idx > P264HIP_MAX_REFS) { ERR(p, "num_ref_idx_l0_active %d too large", sh->num_ref_idx); return -1; }
-        if (sh->type == P264_SLICE_B && (sh->num_ref_idx_l1 < 1 || sh->num_ref_idx_l1 > P264HIP_MAX_REFS)) { ERR(p, "num_ref_idx_l1_active %d too large", sh->num_ref_idx_l1); return -1; }
-        for (int l = 0; l < (sh->type == P264_SLICE_B ? 2 : 1); l++) {
+        const int n_lists = sh->type == P264_SLICE_B ? 2 : 1;
+        sh->num_ref_idx[0] = pps->num_ref_idx[0]; sh->num_ref_idx[1] = pps->num_ref_idx[1];
+        if (br_u1(b)) for (int l = 0; l < n_lists; l++) sh->num_ref_idx[l] = (int)br_ue(b) + 1;
+        for (int l = 0; l < n_lists; l++)
+            if (sh->num_ref_idx[l] < 1 || sh->num_ref_idx[l] > P264HIP_MAX_REFS) { ERR(p, "num_ref_idx_l%d_active %d too large", l, sh->num_ref_idx[l]); return -1; }
+        for (int l = 0; l < n_lists; l++) {
             if (!br_u1(b)) continue;                              /* ref_pic_list_reordering_flag_l0 / _l1 */
             for (;;) {
                 unsigned idc = br_ue(b);
-                int *n = l ? &sh->n_reorder1 : &sh->n_reorder;
+                int *n = &sh->n_reorder[l];
                 if (idc == 3) break;
                 if (idc > 3 || *n >= 33 || br_overrun(b)) { ERR(p, "wrong reordering of pic nums idc"); return -1; }
-                if (l) { sh->reorder1[*n].idc = (int)idc; sh->reorder1[*n].arg = (int)br_ue(b); }
-                else   { sh->reorder[*n].idc = (int)idc; sh->reorder[*n].arg = (int)br_ue(b); }
+                sh->reorder[l][*n].idc = (int)idc; sh->reorder[l][*n].arg = (int)br_ue(b);
                 (*n)++;
             }
         }
@@ -430,10 +436,10 @@ static int bipred_sums_bad(p264parse *p)
 {
     const picbuf_t *q = &p->buf[p->cur];
     for (int i = 0; i < p->n_mb * 4; i++) {
-        const int r0 = q->ref[i], r1 = q->ref1[i];
+        const int r0 = q->ref[0][i], r1 = q->ref[1][i];
         if (r0 < 0 || r1 < 0 || r0 >= P264HIP_MAX_REFS || r1 >= P264HIP_MAX_REFS) continue;
         for (int c = 0; c < 3; c++) {
-            const int d = p->sh0.wp_denom[c > 0], sum = p->sh0.wp_tab[0][r0][c][0] + p->sh0.wp_tab[1][r1][c][0];
+            const int d = p->pic.wp_denom[c > 0], sum = p->pic.wp_tab[0][r0][c][0] + p->pic.wp_tab[1][r1][c][0];
             if (sum < -128 || sum > (d == 7 ? 127 : 128)) {
                 ERR(p, "macroblock %d: weights of list-0 index %d and list-1 index %d add up to %d (component %d, denominator %d; H.264 8.4.2.3)", i / 4, r0, r1, sum, c, d);
                 return 1;
@@ -471,6 +477,9 @@ static int picture_order_count(const p264parse *p, const slice_t *sh, int idr, i
     return 0;
 }
 
+/* PicNum of a short-term frame as the picture with frame_num `cur` sees it (8.2.4.1: FrameNumWrap) */
+static inline int pic_num_of(int frame_num, int cur, int max_fn) { return frame_num > cur ? frame_num - max_fn : frame_num; }
+
 /* Reference list X of the slice (H.264 8.2.4.2, 8.2.4.3).  Initial order - P slices: short-term pictures by descending
  * PicNum (decoder/lists.c:72-143); B slices (the reference stops at decoder/lists.c:136): list 0 the short-term pictures
  * before the current one in output order, nearest first, then those after it, nearest first - list 1 the other way round;
@@ -486,15 +495,15 @@ static int build_list(p264parse *p, const slice_t *sh, int X, int *out)
         n = 0;
         for (int i = 0; i < p->slots; i++) {
             if (!p->dpb[i].used || p->dpb[i].is_long || i == p->cur_slot) continue;
-            p->dpb[i].pic_num = p->dpb[i].frame_num > sh->frame_num ? p->dpb[i].frame_num - max_fn : p->dpb[i].frame_num;
+            p->dpb[i].pic_num = pic_num_of(p->dpb[i].frame_num, sh->frame_num, max_fn);
             int j = n++;
             if (!isB) while (j > 0 && p->dpb[idx[L][j-1]].pic_num < p->dpb[i].pic_num) { idx[L][j] = idx[L][j-1]; j--; }
             else {
                 /* order key: list 0 wants POC below the current one first, descending, then the rest ascending; list 1 the mirror image */
-                const int before_i = p->dpb[i].poc < p->cur_poc;
+                const int before_i = p->dpb[i].poc < p->pic.poc;
                 for (; j > 0; j--) {
                     const dpb_frame_t *o = &p->dpb[idx[L][j-1]];
-                    const int before_o = o->poc < p->cur_poc;
+                    const int before_o = o->poc < p->pic.poc;
                     int i_first;
                     if (before_i != before_o) i_first = L == 0 ? before_i : !before_i;
                     else i_first = before_i ? p->dpb[i].poc > o->poc : p->dpb[i].poc < o->poc;     /* nearest first on either side */
@@ -517,13 +526,12 @@ static int build_list(p264parse *p, const slice_t *sh, int X, int *out)
     if (n == 0) { ERR(p, "%s slice without a reference picture", isB ? "B" : "P"); return -1; }
     if (isB && n > 1 && !memcmp(idx[0], idx[1], sizeof(int) * (size_t)n)) { const int t = idx[1][0]; idx[1][0] = idx[1][1]; idx[1][1] = t; }
     const int *ini = idx[isB ? X : 0];
-    const int len = X ? sh->num_ref_idx_l1 : sh->num_ref_idx;
-    const int n_cmd = X ? sh->n_reorder1 : sh->n_reorder;
+    const int len = sh->num_ref_idx[X], n_cmd = sh->n_reorder[X];
     int list[P264HIP_MAX_REFS + 1];
     for (int i = 0; i < len; i++) list[i] = ini[i < n ? i : n - 1];
     int pred = sh->frame_num, at = 0;
     for (int k = 0; k < n_cmd && at < len; k++) {
-        const int idc = X ? sh->reorder1[k].idc : sh->reorder[k].idc, arg = X ? sh->reorder1[k].arg : sh->reorder[k].arg;
+        const int idc = sh->reorder[X][k].idc, arg = sh->reorder[X][k].arg;
         int slot = -1;
         if (idc == 2) {                                   /* long_term_pic_num */
             for (int i = n_short; i < n; i++) if (p->dpb[ini[i]].long_idx == arg) slot = ini[i];
@@ -532,7 +540,7 @@ static int build_list(p264parse *p, const slice_t *sh, int X, int *out)
             pred = idc == 0 ? pred - d : pred + d;
             if (pred < 0) pred += max_fn;
             if (pred >= max_fn) pred -= max_fn;
-            int want = pred > sh->frame_num ? pred - max_fn : pred;
+            int want = pic_num_of(pred, sh->frame_num, max_fn);
             for (int i = 0; i < p->slots; i++) if (p->dpb[i].used && !p->dpb[i].is_long && i != p->cur_slot && p->dpb[i].pic_num == want) slot = i;
         }
         if (slot < 0) { ERR(p, "reordering names a picture that is not in the frame store"); return -1; }
@@ -553,16 +561,16 @@ static void implicit_weights(p264parse *p)
     for (int r0 = 0; r0 < P264HIP_MAX_REFS; r0++)
         for (int r1 = 0; r1 < P264HIP_MAX_REFS; r1++) {
             int w0 = 32;
-            if (p->weighted_bipred && r0 < p->n_list0 && r1 < p->n_list1) {
-                const dpb_frame_t *f0 = &p->dpb[p->list0[r0]], *f1 = &p->dpb[p->list1[r1]];
-                const int td = clip3i(f1->poc - f0->poc, -128, 127), tb = clip3i(p->cur_poc - f0->poc, -128, 127);
+            if (p->pic.weighted_bipred && r0 < p->pic.n_list[0] && r1 < p->pic.n_list[1]) {
+                const dpb_frame_t *f0 = &p->dpb[p->pic.list[0][r0]], *f1 = &p->dpb[p->pic.list[1][r1]];
+                const int td = clip3i(f1->poc - f0->poc, -128, 127), tb = clip3i(p->pic.poc - f0->poc, -128, 127);
                 if (td != 0 && !f0->is_long && !f1->is_long) {
                     const int tx = (16384 + (td < 0 ? -td : td) / 2) / td;
                     const int dsf = clip3i((tb * tx + 32) >> 6, -1024, 1023) >> 2;
                     if (dsf >= -64 && dsf <= 128) w0 = 64 - dsf;
                 }
             }
-            p->bipred_weight[r0 * P264HIP_MAX_REFS + r1] = (int16_t)w0;
+            p->pic.bipred_weight[r0 * P264HIP_MAX_REFS + r1] = (int16_t)w0;
         }
 }
 
@@ -571,23 +579,23 @@ static void implicit_weights(p264parse *p)
 static void finish_picture_marking(p264parse *p)
 {
     const sps_t *sps = &p->sps[p->active_sps];
+    const slice_t *first = &p->pic.first;
     int max_fn = 1 << sps->log2_max_frame_num;
     dpb_frame_t *cur = &p->dpb[p->cur_slot];
     int cur_long = 0, cur_long_idx = 0, had_mmco5 = 0;
-    if (p->pic_is_idr) {
+    if (p->pic.is_idr) {
         for (int i = 0; i < p->slots; i++) if (i != p->cur_slot) p->dpb[i].used = 0;
-        if (p->sh0.long_term_flag) { cur_long = 1; cur_long_idx = 0; }
-    } else if (p->pic_ref_idc && p->sh0.adaptive_marking) {
+        if (first->long_term_flag) { cur_long = 1; cur_long_idx = 0; }
+    } else if (p->pic.ref_idc && first->adaptive_marking) {
         /* 8.2.5.4: the commands in order; PicNum relative to the current picture's frame_num */
-        for (int k = 0; k < p->sh0.n_mmco; k++) {
-            const int op = p->sh0.mmco[k].op, a = p->sh0.mmco[k].a, b = p->sh0.mmco[k].b;
+        for (int k = 0; k < first->n_mmco; k++) {
+            const int op = first->mmco[k].op, a = first->mmco[k].a, b = first->mmco[k].b;
             if (op == 1 || op == 3) {
-                const int want = p->sh0.frame_num - (a + 1);
+                const int want = first->frame_num - (a + 1);
                 for (int i = 0; i < p->slots; i++) {
                     dpb_frame_t *f = &p->dpb[i];
                     if (!f->used || f->is_long || i == p->cur_slot) continue;
-                    const int num = f->frame_num > p->sh0.frame_num ? f->frame_num - max_fn : f->frame_num;
-                    if (num != want) continue;
+                    if (pic_num_of(f->frame_num, first->frame_num, max_fn) != want) continue;
                     if (op == 1) f->used = 0;
                     else {                                  /* 3: the index is taken away from whoever holds it, then assigned */
                         for (int j = 0; j < p->slots; j++) if (j != i && p->dpb[j].used && p->dpb[j].is_long && p->dpb[j].long_idx == b) p->dpb[j].used = 0;
@@ -606,14 +614,14 @@ static void finish_picture_marking(p264parse *p)
                 cur_long = 1; cur_long_idx = b;
             }
         }
-    } else if (p->pic_ref_idc) {
+    } else if (p->pic.ref_idc) {
         /* 8.2.5.3 sliding window: when short-term + long-term pictures fill num_ref_frames, the oldest short-term one goes */
         int cnt = 0, oldest = -1, oldest_num = 0;
         for (int i = 0; i < p->slots; i++) {
             if (!p->dpb[i].used || i == p->cur_slot) continue;
             cnt++;
             if (p->dpb[i].is_long) continue;
-            int num = p->dpb[i].frame_num > p->sh0.frame_num ? p->dpb[i].frame_num - max_fn : p->dpb[i].frame_num;
+            const int num = pic_num_of(p->dpb[i].frame_num, first->frame_num, max_fn);
             if (oldest < 0 || num < oldest_num) { oldest = i; oldest_num = num; }
         }
         int cap = sps->num_ref_frames > 0 ? sps->num_ref_frames : 1;
@@ -621,15 +629,15 @@ static void finish_picture_marking(p264parse *p)
     }
     /* after memory_management_control_operation 5 the picture is inferred to have had frame_num 0 (H.264 7.4.3, 8.2.1): the
      * pictures that follow compute their PicNums against that */
-    if (p->pic_ref_idc) { cur->used = 1; cur->frame_num = had_mmco5 ? 0 : p->sh0.frame_num; cur->is_long = cur_long; cur->long_idx = cur_long_idx; }
+    if (p->pic.ref_idc) { cur->used = 1; cur->frame_num = had_mmco5 ? 0 : first->frame_num; cur->is_long = cur_long; cur->long_idx = cur_long_idx; }
     /* picture order count: what the pictures behind this one measure theirs against (8.2.1; after operation 5 the picture
      * counts as POC 0 - frames, bottom not below top) */
-    cur->poc = had_mmco5 ? 0 : p->cur_poc; cur->uid = p->cur_uid;
-    if (sps->poc_type == 0 && p->pic_ref_idc) {
-        p->prev_poc_msb = had_mmco5 ? 0 : poc_msb_of(p, sps, &p->sh0, p->pic_is_idr);
-        p->prev_poc_lsb = had_mmco5 ? 0 : p->sh0.poc_lsb;
+    cur->poc = had_mmco5 ? 0 : p->pic.poc; cur->uid = p->pic.uid;
+    if (sps->poc_type == 0 && p->pic.ref_idc) {
+        p->prev_poc_msb = had_mmco5 ? 0 : poc_msb_of(p, sps, first, p->pic.is_idr);
+        p->prev_poc_lsb = had_mmco5 ? 0 : first->poc_lsb;
     }
-    if (sps->poc_type == 2) { p->frame_num_offset = had_mmco5 ? 0 : frame_num_offset_of(p, sps, &p->sh0, p->pic_is_idr); p->prev_frame_num = had_mmco5 ? 0 : p->sh0.frame_num; }
+    if (sps->poc_type == 2) { p->frame_num_offset = had_mmco5 ? 0 : frame_num_offset_of(p, sps, first, p->pic.is_idr); p->prev_frame_num = had_mmco5 ? 0 : first->frame_num; }
     /* next picture goes into a slot that holds no reference */
     int next = -1;
     for (int i = 0; i < p->slots; i++) if (!p->dpb[i].used) { next = i; break; }
@@ -637,7 +645,7 @@ static void finish_picture_marking(p264parse *p)
         int oldest = -1, oldest_num = 0;
         for (int i = 0; i < p->slots; i++) {
             if (p->dpb[i].is_long) continue;
-            int num = p->dpb[i].frame_num > p->sh0.frame_num ? p->dpb[i].frame_num - max_fn : p->dpb[i].frame_num;
+            const int num = pic_num_of(p->dpb[i].frame_num, first->frame_num, max_fn);
             if (oldest < 0 || num < oldest_num) { oldest = i; oldest_num = num; }
         }
         next = oldest >= 0 ? oldest : p->cur_slot;
@@ -647,17 +655,10 @@ static void finish_picture_marking(p264parse *p)
 }
 
 /* ---------------------------------------------------------------- neighbours ------------ */
-static inline int mb_avail(const p264parse *p, int mbx, int mby)
-{
-    if (mbx < 0 || mby < 0 || mbx >= p->mb_w || mby >= p->mb_h) return 0;
-    int i = mby * p->mb_w + mbx;
-    return i < p->mbi && p->slice_of[i] == (uint16_t)p->slice_no;
-}
-
 typedef struct { int ref, mvx, mvy; } nbmv_t;      /* ref: -2 unavailable, -1 intra */
 
 /* motion data of the 4x4 block at picture position (x4,y4), as a predictor for the current MB */
-static nbmv_t nb_motion_l(const p264parse *p, int x4, int y4, int list)
+static nbmv_t nb_motion(const p264parse *p, int x4, int y4, int list)
 {
     nbmv_t r = { -2, 0, 0 };
     /* where the block lies relative to the current macroblock decides everything: inside it - decoded so far or not; in the
@@ -665,7 +666,7 @@ static nbmv_t nb_motion_l(const p264parse *p, int x4, int y4, int list)
     const int dx = x4 - p->mbx * 4, dy = y4 - p->mby * 4, sub = (y4 & 3) * 4 + (x4 & 3);
     int i;
     if (dy >= 0) {
-        if (dx >= 0) { if (dx >= 4 || dy >= 4 || !(((list ? p->mv_done1 : p->mv_done) >> sub) & 1)) return r; i = p->mbi; }
+        if (dx >= 0) { if (dx >= 4 || dy >= 4 || !((p->mv_done[list] >> sub) & 1)) return r; i = p->mbi; }
         else { if (dy >= 4 || !(p->cur_avail & P264_AVAIL_LEFT)) return r; i = p->mbi - 1; }
     } else {
         if (dx < 0)      { if (!(p->cur_avail & P264_AVAIL_TOPLEFT)) return r;  i = p->mbi - p->mb_w - 1; }
@@ -673,7 +674,7 @@ static nbmv_t nb_motion_l(const p264parse *p, int x4, int y4, int list)
         else             { if (dx >= 8 || !(p->cur_avail & P264_AVAIL_TOPRIGHT)) return r; i = p->mbi - p->mb_w + 1; }
     }
     const picbuf_t *q = &p->buf[p->cur];
-    const int8_t *ref = list ? q->ref1 : q->ref; const int16_t *mv = list ? q->mv1 : q->mv;
+    const int8_t *ref = q->ref[list]; const int16_t *mv = q->mv[list];
     r.ref = ref[i * 4 + ((y4 & 2) | ((x4 >> 1) & 1))];     /* -1: intra, or (B pictures) this list is not used there */
     r.mvx = mv[(i * 16 + sub) * 2]; r.mvy = mv[(i * 16 + sub) * 2 + 1];
     return r;
@@ -685,13 +686,13 @@ static nbmv_t nb_motion_l(const p264parse *p, int x4, int y4, int list)
 static inline nbmv_t nb_of_mb(const p264parse *p, int i, int sub, int list)
 {
     const picbuf_t *q = &p->buf[p->cur];
-    const int8_t *ref = list ? q->ref1 : q->ref; const int16_t *mv = list ? q->mv1 : q->mv;
+    const int8_t *ref = q->ref[list]; const int16_t *mv = q->mv[list];
     nbmv_t r;
     r.ref = ref[i * 4 + (((sub >> 2) & 2) | ((sub >> 1) & 1))];
     r.mvx = mv[(i * 16 + sub) * 2]; r.mvy = mv[(i * 16 + sub) * 2 + 1];
     return r;
 }
-static void predict_mv_l(const p264parse *p, int bx, int by, int bw, int ref, int dir, int *px, int *py, int list)
+static void predict_mv(const p264parse *p, int bx, int by, int bw, int ref, int dir, int *px, int *py, int list)
 {
     int x0 = p->mbx * 4 + bx, y0 = p->mby * 4 + by;
     nbmv_t a, b, c;
@@ -706,8 +707,8 @@ static void predict_mv_l(const p264parse *p, int bx, int by, int bw, int ref, in
         c = (av & P264_AVAIL_TOPRIGHT) ? nb_of_mb(p, p->mbi - p->mb_w + 1, 12, list)
           : (av & P264_AVAIL_TOPLEFT) ? nb_of_mb(p, p->mbi - p->mb_w - 1, 15, list) : none;
     } else {
-        a = nb_motion_l(p, x0 - 1, y0, list); b = nb_motion_l(p, x0, y0 - 1, list); c = nb_motion_l(p, x0 + bw, y0 - 1, list);
-        if (c.ref == -2) c = nb_motion_l(p, x0 - 1, y0 - 1, list);
+        a = nb_motion(p, x0 - 1, y0, list); b = nb_motion(p, x0, y0 - 1, list); c = nb_motion(p, x0 + bw, y0 - 1, list);
+        if (c.ref == -2) c = nb_motion(p, x0 - 1, y0 - 1, list);
     }
     if (dir == 1 && b.ref == ref) { *px = b.mvx; *py = b.mvy; return; }
     if (dir == 2 && a.ref == ref) { *px = a.mvx; *py = a.mvy; return; }
@@ -721,28 +722,26 @@ static void predict_mv_l(const p264parse *p, int bx, int by, int bw, int ref, in
     if (hits == 0 && b.ref == -2 && c.ref == -2 && a.ref != -2) { *px = a.mvx; *py = a.mvy; return; }
     *px = median3(a.mvx, b.mvx, c.mvx); *py = median3(a.mvy, b.mvy, c.mvy);
 }
-static void predict_mv(const p264parse *p, int bx, int by, int bw, int ref, int dir, int *px, int *py) { predict_mv_l(p, bx, by, bw, ref, dir, px, py, 0); }
 
-static void set_motion_l(p264parse *p, int bx, int by, int bw, int bh, int mvx, int mvy, int list)
+static void set_motion(p264parse *p, int bx, int by, int bw, int bh, int mvx, int mvy, int list)
 {
     picbuf_t *q = &p->buf[p->cur];
-    int16_t *mv = list ? q->mv1 : q->mv;
+    int16_t *mv = q->mv[list];
     if (bw == 4 && bh == 4) {                                   /* the whole macroblock: sixteen equal vectors, eight 8-byte stores */
         const uint32_t one = (uint32_t)(uint16_t)mvx | (uint32_t)(uint16_t)mvy << 16;
         const uint64_t two = (uint64_t)one | (uint64_t)one << 32;
         int16_t *d = mv + (size_t)p->mbi * 32;
         for (int k = 0; k < 8; k++) memcpy(d + 4 * k, &two, 8);
-        if (list) p->mv_done1 = 0xffffu; else p->mv_done = 0xffffu;
+        p->mv_done[list] = 0xffffu;
         return;
     }
     for (int y = by; y < by + bh; y++)
         for (int x = bx; x < bx + bw; x++) {
             mv[(p->mbi * 16 + y * 4 + x) * 2] = (int16_t)mvx;
             mv[(p->mbi * 16 + y * 4 + x) * 2 + 1] = (int16_t)mvy;
-            if (list) p->mv_done1 |= 1u << (y * 4 + x); else p->mv_done |= 1u << (y * 4 + x);
+            p->mv_done[list] |= 1u << (y * 4 + x);
         }
 }
-static void set_motion(p264parse *p, int bx, int by, int bw, int bh, int mvx, int mvy) { set_motion_l(p, bx, by, bw, bh, mvx, mvy, 0); }
 
 /* Intra4x4PredMode predictor (H.264 8.3.1.1; core/macroblock.c:40-51).  Both entropy coders come through here.
  * dcPredModePredictedFlag: a neighbouring macroblock that is not available - or, with constrained_intra_pred_flag, is inter -
@@ -864,13 +863,13 @@ static int store_coefs(p264parse *p, p264hip_mb_t *m, const mbcoef_t *cf)
     return 0;
 }
 
-/* the four neighbours (mb_avail, spelled out: they all lie in front of this macroblock, so only the picture's borders and the
- * slice they belong to are left to ask) */
+/* the four neighbours: they all lie in front of this macroblock, so only the picture's borders and the slice they belong to are
+ * left to ask */
 static inline int mb_neighbours(p264parse *p)
 {
     int a = 0;
     const int w = p->mb_w, i = p->mbi, x = p->mbx;
-    const uint16_t sn = (uint16_t)p->slice_no, *so = p->slice_of;
+    const uint16_t sn = (uint16_t)p->pic.slice_no, *so = p->slice_of;
     if (x > 0 && so[i - 1] == sn) a |= P264_AVAIL_LEFT;
     if (p->mby > 0) {
         if (so[i - w] == sn) a |= P264_AVAIL_TOP;
@@ -883,7 +882,7 @@ static inline int mb_neighbours(p264parse *p)
 static void begin_mb(p264parse *p, p264hip_mb_t *m)
 {
     memset(m, 0, sizeof *m);
-    p->mv_done = 0; p->mv_done1 = 0;
+    p->mv_done[0] = p->mv_done[1] = 0;
     if (p->cabac_on) { p->cinfo[p->mbi] = 0; memset(p->mvd_abs[0] + p->mbi * 32, 0, 32); memset(p->mvd_abs[1] + p->mbi * 32, 0, 32); }
     const int a = mb_neighbours(p);
     m->avail = (uint8_t)a;
@@ -926,28 +925,12 @@ static void finish_mb_qp(p264parse *p, p264hip_mb_t *m, int has_residual_syntax,
     m->qp = (uint8_t)clip3i(qp, 0, 51);
 }
 
-/* decoder/macroblock.c:895-934 */
-static void decode_pskip(p264parse *p)
+/* this macroblock has no motion (intra, or a B macroblock before its partitions are read): index -1 and zero vectors, in list 1
+ * where the stream can have B pictures at all */
+static void clear_motion(p264parse *p)
 {
     picbuf_t *q = &p->buf[p->cur];
-    p264hip_mb_t *m = &q->mb[p->mbi];
-    begin_mb(p, m);
-    m->mb_type = P264_MB_P_SKIP;
-    memset(p->nnz + (size_t)p->mbi * 24, 0, 24);
-    memset(q->ref + p->mbi * 4, 0, 4);
-    memset(q->i4 + p->mbi * 16, 2, 16);
-    int mvx = 0, mvy = 0;
-    /* (8.4.1.1: the zero vector without a left or an upper neighbour or next to one at rest on reference 0; else the 16x16 prediction) */
-    if ((p->cur_avail & (P264_AVAIL_LEFT | P264_AVAIL_TOP)) == (P264_AVAIL_LEFT | P264_AVAIL_TOP)) {
-        const nbmv_t a = nb_of_mb(p, p->mbi - 1, 3, 0), b = nb_of_mb(p, p->mbi - p->mb_w, 12, 0);
-        if (!((a.ref == 0 && a.mvx == 0 && a.mvy == 0) || (b.ref == 0 && b.mvx == 0 && b.mvy == 0)))
-            predict_mv(p, 0, 0, 4, 0, 0, &mvx, &mvy);
-    }
-    set_motion(p, 0, 0, 4, 4, mvx, mvy);
-    m->coef_index = (uint32_t)q->coef_n;
-    finish_mb_qp(p, m, 0, p->sh.qp);
-    p->last_dqp = 0;
-    if (p->cabac_on) p->cinfo[p->mbi] |= CI_SKIP;
+    for (int l = 0; l < 2 && q->mv[l]; l++) { memset(q->ref[l] + p->mbi * 4, -1, 4); memset(q->mv[l] + p->mbi * 32, 0, 64); }
 }
 
 /* I_PCM (H.264 7.3.5, 8.3.5): pcm_alignment_zero_bits, then 384 sample bytes that go into the macroblock's place in coefs[] in one
@@ -992,114 +975,15 @@ static int parse_ipcm(p264parse *p, bitrd_t *b, p264hip_mb_t *m)
     m->coef_mask = P264_IPCM_COEF_MASK;
     m->coef_index = (uint32_t)q->coef_n;
     q->coef_n += P264_IPCM_BLOCKS;
-    memset(q->ref + p->mbi * 4, -1, 4);
-    memset(q->mv + p->mbi * 32, 0, 64);
-    if (q->mv1) { memset(q->ref1 + p->mbi * 4, -1, 4); memset(q->mv1 + p->mbi * 32, 0, 64); }
+    clear_motion(p);
     memset(q->i4 + p->mbi * 16, 2, 16);
     memset(p->nnz + (size_t)p->mbi * 24, 16, 24);
     p->last_dqp = 0;
     return 0;
 }
 
-/* t: mb_type as read (P slices), intra_t >= 0: the macroblock is intra with that I-slice type (I slices; P / B slices after
- * their offset of 5 / 23) */
-static int parse_mb_t(p264parse *p, bitrd_t *b, unsigned t, int intra_t)
-{
-    picbuf_t *q = &p->buf[p->cur];
-    p264hip_mb_t *m = &q->mb[p->mbi];
-    mbcoef_t cf; cf.mask = 0;
-    begin_mb(p, m);
-    int8_t *ref = q->ref + p->mbi * 4;
-    uint8_t *i4 = q->i4 + p->mbi * 16;
-
-    if (intra_t >= 0) {
-        /* ---- intra (decoder/macroblock.c:117-139, 265-301) ---- */
-        if (intra_t > 25) { ERR(p, "invalid mb type %d", intra_t); return -1; }
-        m->avail = (uint8_t)intra_avail(p);
-        if (intra_t == 25) return parse_ipcm(p, b, m);
-        memset(ref, -1, 4);
-        memset(q->mv + p->mbi * 32, 0, 64);
-        if (q->mv1) { memset(q->ref1 + p->mbi * 4, -1, 4); memset(q->mv1 + p->mbi * 32, 0, 64); }
-        if (intra_t == 0) {
-            m->mb_type = P264_MB_I4x4;
-            for (int i = 0; i < 16; i++) i4[i] = (uint8_t)rd_intra4x4_mode(p, b, predict_i4mode(p, i));
-        } else {
-            m->mb_type = P264_MB_I16x16;
-            m->intra_modes = (uint8_t)((intra_t - 1) & 3);
-            m->cbp = (uint8_t)((((intra_t - 1) >> 2) % 3) << 4 | (intra_t > 12 ? 15 : 0));
-            memset(i4, 2, 16);
-        }
-        unsigned cm = rd_chroma_pred_mode(p, b);
-        if (cm > 3) { ERR(p, "invalid intra chroma pred mode %u", cm); return -1; }
-        m->intra_modes |= (uint8_t)(cm << 4);
-    } else {
-        /* ---- inter (decoder/macroblock.c:140-167, 304-408) ---- */
-        memset(i4, 2, 16);
-        int nref = p->sh.num_ref_idx;
-        if (t <= 2) {
-            m->mb_type = P264_MB_P_L0;
-            static const int8_t geo[3][2][4] = {   /* x, y, w, h in 4x4 units */
-                { {0,0,4,4}, {0,0,0,0} }, { {0,0,4,2}, {0,2,4,2} }, { {0,0,2,4}, {2,0,2,4} } };
-            int nparts = t == 0 ? 1 : 2, r[2] = { 0, 0 };
-            for (int k = 0; k < nparts; k++) {
-                r[k] = rd_ref_idx(p, b, 0, geo[t][k][0], geo[t][k][1], nref);
-                if (r[k] < 0 || r[k] >= nref) { ERR(p, "ref_idx out of range"); return -1; }
-                for (int y = geo[t][k][1] >> 1; y < (geo[t][k][1] + geo[t][k][3]) >> 1; y++)      /* (at once: the next partition's context looks at it) */
-                    for (int x = geo[t][k][0] >> 1; x < (geo[t][k][0] + geo[t][k][2]) >> 1; x++) ref[y * 2 + x] = (int8_t)r[k];
-            }
-            for (int k = 0; k < nparts; k++) {
-                int dx, dy, px, py;
-                if (rd_mvd(p, b, 0, geo[t][k][0], geo[t][k][1], geo[t][k][2], geo[t][k][3], &dx, &dy) < 0) { ERR(p, "mvd out of range"); return -1; }
-                int dir = t == 0 ? 0 : t == 1 ? 1 + k : 3 + k;
-                predict_mv(p, geo[t][k][0], geo[t][k][1], geo[t][k][2], r[k], dir, &px, &py);
-                set_motion(p, geo[t][k][0], geo[t][k][1], geo[t][k][2], geo[t][k][3], px + dx, py + dy);
-            }
-        } else {
-            m->mb_type = P264_MB_P_8x8;
-            int sub[4];
-            for (int k = 0; k < 4; k++) { sub[k] = rd_sub_mb_type(p, b); if (sub[k] < 0 || sub[k] > 3) { ERR(p, "invalid i_sub_partition"); return -1; } }   /* (< 0: a ue(v) past 2^31 in a damaged stream) */
-            memset(ref, 0, 4);
-            for (int k = 0; k < 4; k++) {
-                int r = 0;
-                if (nref > 1 && t == 3) { r = rd_ref_idx(p, b, 0, (k & 1) * 2, (k >> 1) * 2, nref); if (r < 0 || r >= nref) { ERR(p, "ref_idx out of range"); return -1; } }
-                ref[k] = (int8_t)r;
-            }
-            for (int k = 0; k < 4; k++) {
-                int ox = (k & 1) * 2, oy = (k >> 1) * 2;
-                int sw = (sub[k] == 0 || sub[k] == 1) ? 2 : 1, shh = (sub[k] == 0 || sub[k] == 2) ? 2 : 1;
-                for (int sy = 0; sy < 2; sy += shh)
-                    for (int sx = 0; sx < 2; sx += sw) {
-                        int dx, dy, px, py;
-                        if (rd_mvd(p, b, 0, ox + sx, oy + sy, sw, shh, &dx, &dy) < 0) { ERR(p, "mvd out of range"); return -1; }
-                        predict_mv(p, ox + sx, oy + sy, sw, ref[k], 0, &px, &py);
-                        set_motion(p, ox + sx, oy + sy, sw, shh, px + dx, py + dy);
-                    }
-            }
-        }
-    }
-
-    /* ---- coded_block_pattern, mb_qp_delta, residual (decoder/macroblock.c:540-587) ---- */
-    if (m->mb_type != P264_MB_I16x16) {
-        const int c = rd_cbp(p, b, m->mb_type == P264_MB_I4x4);
-        if (c < 0) { ERR(p, "invalid cbp"); return -1; }
-        m->cbp = (uint8_t)c;
-    }
-    int qp = p->sh.qp, has_res = (m->cbp != 0 || m->mb_type == P264_MB_I16x16);
-    if (has_res) {
-        int dqp = rd_mb_qp_delta(p, b);
-        if (dqp < -52 || dqp > 52) { ERR(p, "mb_qp_delta out of range"); return -1; }
-        if (p->strict_qp) qp = (p->qp_pred + dqp + 52) % 52;
-        else qp = p->sh.qp + dqp;                 /* delta is NOT accumulated: decoder/macroblock.c:568 */
-        if (rd_residual(p, b, m, &cf) < 0) { ERR(p, "read residual data failed"); return -1; }
-    } else { memset(p->nnz + (size_t)p->mbi * 24, 0, 24); p->last_dqp = 0; }
-    if (store_coefs(p, m, &cf) < 0) return -1;
-    finish_mb_qp(p, m, has_res, qp);
-    if (br_overrun(b)) { ERR(p, "macroblock overruns the slice data"); return -1; }
-    return 0;
-}
-
-/* ---------------------------------------------------------------- B macroblocks ---------- */
-/* The reference has none of this (decoder/macroblock.c:168-171 rejects B macroblock types; its encoder-side helpers
+/* ---------------------------------------------------------------- direct prediction ------ */
+/* B macroblocks: the reference has none of this (decoder/macroblock.c:168-171 rejects B macroblock types; its encoder-side helpers
  * core/macroblock.c:254-429 are not reachable from the decoder): H.264 7.3.5, 7.4.5 (tables 7-14, 7-18), 8.4.1.2. */
 
 /* Direct prediction of the current macroblock (B_Skip, B_Direct_16x16, and the direct 8x8 quadrants of B_8x8): reference
@@ -1115,16 +999,16 @@ static void direct_spatial(const p264parse *p, direct_t *d)
     const int x0 = p->mbx * 4, y0 = p->mby * 4;
     int ref[2], mv[2][2] = { { 0, 0 }, { 0, 0 } };
     for (int l = 0; l < 2; l++) {
-        nbmv_t a = nb_motion_l(p, x0 - 1, y0, l), b = nb_motion_l(p, x0, y0 - 1, l), c = nb_motion_l(p, x0 + 4, y0 - 1, l);
-        if (c.ref == -2) c = nb_motion_l(p, x0 - 1, y0 - 1, l);
+        nbmv_t a = nb_motion(p, x0 - 1, y0, l), b = nb_motion(p, x0, y0 - 1, l), c = nb_motion(p, x0 + 4, y0 - 1, l);
+        if (c.ref == -2) c = nb_motion(p, x0 - 1, y0 - 1, l);
         ref[l] = min_positive(a.ref < 0 ? -1 : a.ref, min_positive(b.ref < 0 ? -1 : b.ref, c.ref < 0 ? -1 : c.ref));
     }
     const int zero_pred = ref[0] < 0 && ref[1] < 0;
     if (zero_pred) ref[0] = ref[1] = 0;
-    else for (int l = 0; l < 2; l++) if (ref[l] >= 0) predict_mv_l(p, 0, 0, 4, ref[l], 0, &mv[l][0], &mv[l][1], l);
+    else for (int l = 0; l < 2; l++) if (ref[l] >= 0) predict_mv(p, 0, 0, 4, ref[l], 0, &mv[l][0], &mv[l][1], l);
     /* colZeroFlag: RefPicList1[0] is a short-term picture and the co-located block used reference index 0 with a vector
      * inside +-1 (direct_8x8_inference: the corner block of the quadrant speaks for it) */
-    const int col_slot = p->list1[0];
+    const int col_slot = p->list[1][0];
     const int col_short = !p->dpb[col_slot].is_long;
     const int8_t *cr = p->col_ref[col_slot] + p->mbi * 4; const int16_t *cm = p->col_mv[col_slot] + p->mbi * 32;
     const int inf = p->sps[p->active_sps].direct_8x8_inference;
@@ -1143,7 +1027,7 @@ static void direct_spatial(const p264parse *p, direct_t *d)
 static void direct_temporal(const p264parse *p, direct_t *d)
 {   /* 8.4.1.2.3: list 0 points at the picture the co-located block referred to, list 1 at RefPicList1[0]; the co-located
      * vector split in proportion to the picture distances */
-    const int col_slot = p->list1[0];
+    const int col_slot = p->list[1][0];
     const int8_t *cr = p->col_ref[col_slot] + p->mbi * 4; const int32_t *cu = p->col_uid[col_slot] + p->mbi * 4;
     const int16_t *cm = p->col_mv[col_slot] + p->mbi * 32;
     const int inf = p->sps[p->active_sps].direct_8x8_inference;
@@ -1151,10 +1035,10 @@ static void direct_temporal(const p264parse *p, direct_t *d)
         int r0 = 0, scale = 0, use_col = 0;                       /* intra co-located block: both indices 0, zero vectors */
         if (cr[q] >= 0) {
             r0 = -1;
-            for (int i = 0; i < p->n_list0 && r0 < 0; i++) if ((int32_t)p->dpb[p->list0[i]].uid == cu[q]) r0 = i;   /* lowest index that names that picture */
+            for (int i = 0; i < p->n_list[0] && r0 < 0; i++) if ((int32_t)p->dpb[p->list[0][i]].uid == cu[q]) r0 = i;   /* lowest index that names that picture */
             if (r0 < 0) r0 = 0;                                   /* (a stream that dropped it from list 0: not conformant; stay defined) */
-            const dpb_frame_t *f0 = &p->dpb[p->list0[r0]], *f1 = &p->dpb[col_slot];
-            const int tb = clip3i(p->cur_poc - f0->poc, -128, 127), td = clip3i(f1->poc - f0->poc, -128, 127);
+            const dpb_frame_t *f0 = &p->dpb[p->list[0][r0]], *f1 = &p->dpb[col_slot];
+            const int tb = clip3i(p->pic.poc - f0->poc, -128, 127), td = clip3i(f1->poc - f0->poc, -128, 127);
             use_col = 1;
             if (f0->is_long || td == 0) scale = -1;               /* mvL0 = mvCol, mvL1 = 0 */
             else { const int tx = (16384 + (td < 0 ? -td : td) / 2) / td; scale = clip3i((tb * tx + 32) >> 6, -1024, 1023); }
@@ -1180,34 +1064,191 @@ static void direct_predict(const p264parse *p, direct_t *d)
 static void store_direct_quadrant(p264parse *p, const direct_t *d, int q, int list)
 {
     picbuf_t *b = &p->buf[p->cur];
-    (list ? b->ref1 : b->ref)[p->mbi * 4 + q] = d->ref[list][q];
+    b->ref[list][p->mbi * 4 + q] = d->ref[list][q];
     for (int k = 0; k < 4; k++) {
         const int bx = (q & 1) * 2 + (k & 1), by = (q >> 1) * 2 + (k >> 1), blk = by * 4 + bx;
         const int used = d->ref[list][q] >= 0;
-        set_motion_l(p, bx, by, 1, 1, used ? d->mv[list][blk][0] : 0, used ? d->mv[list][blk][1] : 0, list);
+        set_motion(p, bx, by, 1, 1, used ? d->mv[list][blk][0] : 0, used ? d->mv[list][blk][1] : 0, list);
     }
 }
 
-static void decode_bskip(p264parse *p)
+/* the whole macroblock direct-predicted (B_Skip, B_Direct_16x16) */
+static void store_direct_mb(p264parse *p)
+{
+    direct_t d;
+    direct_predict(p, &d);
+    for (int l = 0; l < 2; l++) for (int k = 0; k < 4; k++) store_direct_quadrant(p, &d, k, l);
+    if (p->cabac_on) p->cinfo[p->mbi] |= CI_DIRECT16 | CI_D8(0) | CI_D8(1) | CI_D8(2) | CI_D8(3);
+}
+
+/* P_Skip (decoder/macroblock.c:895-934) and B_Skip: no syntax, inferred motion, no residual */
+static void decode_skip(p264parse *p)
 {
     picbuf_t *q = &p->buf[p->cur];
     p264hip_mb_t *m = &q->mb[p->mbi];
     begin_mb(p, m);
-    m->mb_type = P264_MB_B;
     memset(p->nnz + (size_t)p->mbi * 24, 0, 24);
     memset(q->i4 + p->mbi * 16, 2, 16);
-    direct_t d;
-    direct_predict(p, &d);
-    for (int l = 0; l < 2; l++) for (int k = 0; k < 4; k++) store_direct_quadrant(p, &d, k, l);
+    if (p->sh.type == P264_SLICE_B) {
+        m->mb_type = P264_MB_B;
+        store_direct_mb(p);
+    } else {
+        m->mb_type = P264_MB_P_SKIP;
+        memset(q->ref[0] + p->mbi * 4, 0, 4);
+        int mvx = 0, mvy = 0;
+        /* (8.4.1.1: the zero vector without a left or an upper neighbour or next to one at rest on reference 0; else the 16x16 prediction) */
+        if ((p->cur_avail & (P264_AVAIL_LEFT | P264_AVAIL_TOP)) == (P264_AVAIL_LEFT | P264_AVAIL_TOP)) {
+            const nbmv_t a = nb_of_mb(p, p->mbi - 1, 3, 0), b = nb_of_mb(p, p->mbi - p->mb_w, 12, 0);
+            if (!((a.ref == 0 && a.mvx == 0 && a.mvy == 0) || (b.ref == 0 && b.mvx == 0 && b.mvy == 0)))
+                predict_mv(p, 0, 0, 4, 0, 0, &mvx, &mvy, 0);
+        }
+        set_motion(p, 0, 0, 4, 4, mvx, mvy, 0);
+    }
     m->coef_index = (uint32_t)q->coef_n;
     finish_mb_qp(p, m, 0, p->sh.qp);
     p->last_dqp = 0;
-    if (p->cabac_on) p->cinfo[p->mbi] |= CI_SKIP | CI_DIRECT16 | CI_D8(0) | CI_D8(1) | CI_D8(2) | CI_D8(3);
+    if (p->cabac_on) p->cinfo[p->mbi] |= CI_SKIP;
 }
 
-/* which lists a partition predicts from: bit 0 list 0, bit 1 list 1 */
+/* ---------------------------------------------------------------- inter prediction ------- */
+/* The partitions of an inter macroblock, P (decoder/macroblock.c:140-167, 304-408) or B: one, two or four; a partition of an 8x8
+ * macroblock splits into sub-partitions of (sw, sh), any other is its own only sub-partition. */
+
+/* which lists a partition predicts from: bit 0 list 0, bit 1 list 1; 0: a direct quadrant of B_8x8 */
 enum { PRED_L0 = 1, PRED_L1 = 2, PRED_BI = 3 };
-static const uint8_t b_pair[9][2] = {           /* mb_type 4..21, table 7-14: (type - 4) >> 1 -> prediction of the two partitions */
+typedef struct { uint8_t x, y, w, h, sw, sh, dir, pred; } part_t;     /* 4x4 units inside the macroblock; dir: see predict_mv */
+
+/* 16x16, 16x8 or 8x16 (shape 0, 1, 2) with the prediction of each partition; returns their number */
+static inline int mb_partitions(part_t *pt, int shape, const uint8_t *pred)
+{
+    static const uint8_t geo[3][2][5] = {   /* x, y, w, h, dir */
+        { {0,0,4,4,0}, {0,0,0,0,0} }, { {0,0,4,2,1}, {0,2,4,2,2} }, { {0,0,2,4,3}, {2,0,2,4,4} } };
+    const int n = shape == 0 ? 1 : 2;
+    for (int k = 0; k < n; k++) {
+        const uint8_t *g = geo[shape][k];
+        pt[k] = (part_t){ g[0], g[1], g[2], g[3], g[2], g[3], g[4], pred[k] };
+    }
+    return n;
+}
+/* quadrant k of an 8x8 macroblock with sub-partitions of (sw, sh) */
+static inline void sub_partition(part_t *pt, int k, int sw, int sh, int pred)
+{
+    pt[k] = (part_t){ (uint8_t)((k & 1) * 2), (uint8_t)((k >> 1) * 2), 2, 2, (uint8_t)sw, (uint8_t)sh, 0, (uint8_t)pred };
+}
+
+/* ref_idx and mvd of the partitions pt[0 .. np) for n_lists lists (P: 1, every partition PRED_L0; B: 2), in the order of the syntax:
+ * all ref_idx_l0, all ref_idx_l1, all mvd_l0, all mvd_l1.  read_ref 0: the indices are not coded, all 0 (P_8x8ref0).  d: the
+ * direct prediction of the macroblock where a partition is direct.  n_lists is a constant at both call sites: the compiler makes
+ * two routines of this one, and the P one is the hottest host code there is. */
+static inline __attribute__((always_inline)) int parse_inter_pred(p264parse *p, bitrd_t *b, const int n_lists, int np, const part_t *pt, int read_ref, const direct_t *d)
+{
+    picbuf_t *q = &p->buf[p->cur];
+    int r[2][4];
+    for (int l = 0; l < n_lists; l++) {
+        const int nref = p->sh.num_ref_idx[l];
+        int8_t *ref = q->ref[l] + p->mbi * 4;
+        for (int k = 0; k < np; k++) {
+            if (!(pt[k].pred & (1 << l))) continue;
+            r[l][k] = read_ref ? rd_ref_idx(p, b, l, pt[k].x, pt[k].y, nref) : 0;
+            if (r[l][k] < 0 || r[l][k] >= nref) { ERR(p, "ref_idx out of range"); return -1; }
+            for (int y = pt[k].y >> 1; y < (pt[k].y + pt[k].h) >> 1; y++)                    /* (at once: the next partition's context looks at it) */
+                for (int x = pt[k].x >> 1; x < (pt[k].x + pt[k].w) >> 1; x++) ref[y * 2 + x] = (int8_t)r[l][k];
+        }
+    }
+    for (int l = 0; l < n_lists; l++)
+        for (int k = 0; k < np; k++) {
+            const part_t *t = &pt[k];
+            if (t->pred == 0) { store_direct_quadrant(p, d, k, l); continue; }                /* its turn: the derived motion becomes visible */
+            /* a partition that does not use the list still becomes "decoded" for it (index -1, zero vector) when its turn comes */
+            if (!(t->pred & (1 << l))) { set_motion(p, t->x, t->y, t->w, t->h, 0, 0, l); continue; }
+            for (int sy = 0; sy < t->h; sy += t->sh)
+                for (int sx = 0; sx < t->w; sx += t->sw) {
+                    int dx, dy, px, py;
+                    if (rd_mvd(p, b, l, t->x + sx, t->y + sy, t->sw, t->sh, &dx, &dy) < 0) { ERR(p, "mvd out of range"); return -1; }
+                    predict_mv(p, t->x + sx, t->y + sy, t->sw, r[l][k], t->dir, &px, &py, l);
+                    set_motion(p, t->x + sx, t->y + sy, t->sw, t->sh, px + dx, py + dy, l);
+                }
+        }
+    return 0;
+}
+
+/* ---------------------------------------------------------------- macroblocks ------------ */
+/* What follows the prediction syntax in every macroblock but I_PCM: coded_block_pattern (Intra16x16 carries it in its type),
+ * mb_qp_delta, residual (decoder/macroblock.c:540-587), then the levels and the QP into the record */
+static int parse_mb_tail(p264parse *p, bitrd_t *b, p264hip_mb_t *m)
+{
+    mbcoef_t cf; cf.mask = 0;
+    if (m->mb_type != P264_MB_I16x16) {
+        const int c = rd_cbp(p, b, m->mb_type == P264_MB_I4x4);
+        if (c < 0) { ERR(p, "invalid cbp"); return -1; }
+        m->cbp = (uint8_t)c;
+    }
+    int qp = p->sh.qp, has_res = (m->cbp != 0 || m->mb_type == P264_MB_I16x16);
+    if (has_res) {
+        int dqp = rd_mb_qp_delta(p, b);
+        if (dqp < -52 || dqp > 52) { ERR(p, "mb_qp_delta out of range"); return -1; }
+        if (p->strict_qp) qp = (p->qp_pred + dqp + 52) % 52;
+        else qp = p->sh.qp + dqp;                 /* delta is NOT accumulated: decoder/macroblock.c:568 */
+        if (rd_residual(p, b, m, &cf) < 0) { ERR(p, "read residual data failed"); return -1; }
+    } else { memset(p->nnz + (size_t)p->mbi * 24, 0, 24); p->last_dqp = 0; }
+    if (store_coefs(p, m, &cf) < 0) return -1;
+    finish_mb_qp(p, m, has_res, qp);
+    if (br_overrun(b)) { ERR(p, "macroblock overruns the slice data"); return -1; }
+    return 0;
+}
+
+/* t: mb_type as read (P slices), intra_t >= 0: the macroblock is intra with that I-slice type (I slices; P / B slices after
+ * their offset of 5 / 23) */
+static int parse_mb_t(p264parse *p, bitrd_t *b, unsigned t, int intra_t)
+{
+    picbuf_t *q = &p->buf[p->cur];
+    p264hip_mb_t *m = &q->mb[p->mbi];
+    begin_mb(p, m);
+    uint8_t *i4 = q->i4 + p->mbi * 16;
+
+    if (intra_t >= 0) {
+        /* ---- intra (decoder/macroblock.c:117-139, 265-301) ---- */
+        if (intra_t > 25) { ERR(p, "invalid mb type %d", intra_t); return -1; }
+        m->avail = (uint8_t)intra_avail(p);
+        if (intra_t == 25) return parse_ipcm(p, b, m);
+        clear_motion(p);
+        if (intra_t == 0) {
+            m->mb_type = P264_MB_I4x4;
+            for (int i = 0; i < 16; i++) i4[i] = (uint8_t)rd_intra4x4_mode(p, b, predict_i4mode(p, i));
+        } else {
+            m->mb_type = P264_MB_I16x16;
+            m->intra_modes = (uint8_t)((intra_t - 1) & 3);
+            m->cbp = (uint8_t)((((intra_t - 1) >> 2) % 3) << 4 | (intra_t > 12 ? 15 : 0));
+            memset(i4, 2, 16);
+        }
+        unsigned cm = rd_chroma_pred_mode(p, b);
+        if (cm > 3) { ERR(p, "invalid intra chroma pred mode %u", cm); return -1; }
+        m->intra_modes |= (uint8_t)(cm << 4);
+    } else {
+        /* ---- inter: P_L0_16x16, P_L0_L0_16x8, P_L0_L0_8x16, P_8x8, P_8x8ref0 ---- */
+        static const uint8_t all_l0[2] = { PRED_L0, PRED_L0 };
+        static const uint8_t sub_w[4] = { 2, 2, 1, 1 }, sub_h[4] = { 2, 1, 2, 1 };    /* sub_mb_type 8x8, 8x4, 4x8, 4x4 in 4x4 units */
+        memset(i4, 2, 16);
+        part_t pt[4];
+        int np = 4;
+        if (t <= 2) {
+            m->mb_type = P264_MB_P_L0;
+            np = mb_partitions(pt, (int)t, all_l0);
+        } else {
+            m->mb_type = P264_MB_P_8x8;
+            for (int k = 0; k < 4; k++) {
+                const int sub = rd_sub_mb_type(p, b);
+                if (sub < 0 || sub > 3) { ERR(p, "invalid i_sub_partition"); return -1; }   /* (< 0: a ue(v) past 2^31 in a damaged stream) */
+                sub_partition(pt, k, sub_w[sub], sub_h[sub], PRED_L0);
+            }
+        }
+        if (parse_inter_pred(p, b, 1, np, pt, t != 4, NULL) < 0) return -1;
+    }
+    return parse_mb_tail(p, b, m);
+}
+
+/* table 7-14, mb_type 4..21: (type - 4) >> 1 -> prediction of the two partitions (even types 16x8, odd types 8x16) */
+static const uint8_t b_pair[9][2] = {
     { PRED_L0, PRED_L0 }, { PRED_L1, PRED_L1 }, { PRED_L0, PRED_L1 }, { PRED_L1, PRED_L0 }, { PRED_L0, PRED_BI },
     { PRED_L1, PRED_BI }, { PRED_BI, PRED_L0 }, { PRED_BI, PRED_L1 }, { PRED_BI, PRED_BI } };
 static const uint8_t b_sub_pred[13] = { 0, PRED_L0, PRED_L1, PRED_BI, PRED_L0, PRED_L0, PRED_L1, PRED_L1, PRED_BI, PRED_BI, PRED_L0, PRED_L1, PRED_BI };   /* table 7-18; 0 = direct */
@@ -1220,100 +1261,33 @@ static int parse_mb_b_t(p264parse *p, bitrd_t *b, unsigned t)
     if (t >= 23) {                                            /* intra macroblock in a B slice: the I-slice syntax with the type offset */
         return parse_mb_t(p, b, t, (int)t - 23);
     }
-    mbcoef_t cf; cf.mask = 0;
     begin_mb(p, m);
     m->mb_type = P264_MB_B;
-    int8_t *ref[2] = { q->ref + p->mbi * 4, q->ref1 + p->mbi * 4 };
     memset(q->i4 + p->mbi * 16, 2, 16);
-    memset(ref[0], -1, 4); memset(ref[1], -1, 4);
-    memset(q->mv + p->mbi * 32, 0, 64); memset(q->mv1 + p->mbi * 32, 0, 64);
-    const int nref[2] = { p->sh.num_ref_idx, p->sh.num_ref_idx_l1 };
-    int direct_all = 0;
-    if (t == 0) {                                             /* B_Direct_16x16: like B_Skip, with a residual */
+    clear_motion(p);
+    if (t == 0) store_direct_mb(p);                           /* B_Direct_16x16: like B_Skip, with a residual */
+    else {
+        part_t pt[4];
         direct_t d;
-        direct_predict(p, &d);
-        for (int l = 0; l < 2; l++) for (int k = 0; k < 4; k++) store_direct_quadrant(p, &d, k, l);
-        direct_all = 1;
-        if (p->cabac_on) p->cinfo[p->mbi] |= CI_DIRECT16 | CI_D8(0) | CI_D8(1) | CI_D8(2) | CI_D8(3);
-    } else if (t <= 21) {
-        /* one or two partitions: geometry and which lists each uses */
-        int nparts, geo[2][4], pred[2];
-        if (t <= 3) { nparts = 1; geo[0][0] = 0; geo[0][1] = 0; geo[0][2] = 4; geo[0][3] = 4; pred[0] = t == 1 ? PRED_L0 : t == 2 ? PRED_L1 : PRED_BI; pred[1] = 0; }
-        else {
-            nparts = 2;
-            const int tall = (int)t & 1;                      /* odd types: 8x16 */
-            for (int k = 0; k < 2; k++) { geo[k][0] = tall ? 2 * k : 0; geo[k][1] = tall ? 0 : 2 * k; geo[k][2] = tall ? 2 : 4; geo[k][3] = tall ? 4 : 2; pred[k] = b_pair[(t - 4) >> 1][k]; }
-        }
-        int r[2][2] = { { -1, -1 }, { -1, -1 } };
-        for (int l = 0; l < 2; l++)                           /* all ref_idx_l0, then all ref_idx_l1 */
-            for (int k = 0; k < nparts; k++) {
-                if (!(pred[k] & (1 << l))) continue;
-                r[l][k] = rd_ref_idx(p, b, l, geo[k][0], geo[k][1], nref[l]);
-                if (r[l][k] < 0 || r[l][k] >= nref[l]) { ERR(p, "ref_idx out of range"); return -1; }
-                for (int y = geo[k][1] >> 1; y < (geo[k][1] + geo[k][3]) >> 1; y++)          /* (at once: the next partition's context looks at it) */
-                    for (int x = geo[k][0] >> 1; x < (geo[k][0] + geo[k][2]) >> 1; x++) ref[l][y * 2 + x] = (int8_t)r[l][k];
-            }
-        for (int l = 0; l < 2; l++)                           /* all mvd_l0, then all mvd_l1; a partition that does not use the list still
-                                                               * becomes "decoded" for it (index -1, zero vector) when its turn comes */
-            for (int k = 0; k < nparts; k++) {
-                if (!(pred[k] & (1 << l))) { set_motion_l(p, geo[k][0], geo[k][1], geo[k][2], geo[k][3], 0, 0, l); continue; }
-                int dx, dy, px, py;
-                if (rd_mvd(p, b, l, geo[k][0], geo[k][1], geo[k][2], geo[k][3], &dx, &dy) < 0) { ERR(p, "mvd out of range"); return -1; }
-                const int dir = nparts == 1 ? 0 : geo[0][2] == 4 ? 1 + k : 3 + k;
-                predict_mv_l(p, geo[k][0], geo[k][1], geo[k][2], r[l][k], dir, &px, &py, l);
-                set_motion_l(p, geo[k][0], geo[k][1], geo[k][2], geo[k][3], px + dx, py + dy, l);
-            }
-    } else {                                                  /* 22: B_8x8 */
-        int sub[4], any_direct = 0;
-        for (int k = 0; k < 4; k++) {
-            sub[k] = rd_sub_mb_type(p, b);
-            if (sub[k] < 0 || sub[k] > 12) { ERR(p, "invalid B sub_mb_type %d", sub[k]); return -1; }   /* (< 0: as above; found by tests/tools/asan_slices.sh) */
-            any_direct |= sub[k] == 0;
-            if (p->cabac_on && sub[k] == 0) p->cinfo[p->mbi] |= CI_D8(k);
-        }
-        direct_t d;
-        if (any_direct) direct_predict(p, &d);                /* from the macroblock's neighbours, before any of its own motion exists */
-        int r[2][4];
-        for (int l = 0; l < 2; l++)
+        int np = 4;
+        if (t <= 3) {                                         /* B_L0_16x16, B_L1_16x16, B_Bi_16x16 */
+            const uint8_t pred = t == 1 ? PRED_L0 : t == 2 ? PRED_L1 : PRED_BI;
+            np = mb_partitions(pt, 0, &pred);
+        } else if (t <= 21) np = mb_partitions(pt, (t & 1) ? 2 : 1, b_pair[(t - 4) >> 1]);
+        else {                                                /* 22: B_8x8 */
+            int any_direct = 0;
             for (int k = 0; k < 4; k++) {
-                r[l][k] = -1;
-                if (!(b_sub_pred[sub[k]] & (1 << l))) continue;
-                r[l][k] = rd_ref_idx(p, b, l, (k & 1) * 2, (k >> 1) * 2, nref[l]);
-                if (r[l][k] < 0 || r[l][k] >= nref[l]) { ERR(p, "ref_idx out of range"); return -1; }
-                ref[l][k] = (int8_t)r[l][k];
+                const int sub = rd_sub_mb_type(p, b);
+                if (sub < 0 || sub > 12) { ERR(p, "invalid B sub_mb_type %d", sub); return -1; }   /* (< 0: as above; found by tests/tools/asan_slices.sh) */
+                sub_partition(pt, k, b_sub_w[sub], b_sub_h[sub], b_sub_pred[sub]);
+                any_direct |= sub == 0;
+                if (p->cabac_on && sub == 0) p->cinfo[p->mbi] |= CI_D8(k);
             }
-        for (int l = 0; l < 2; l++)
-            for (int k = 0; k < 4; k++) {
-                const int ox = (k & 1) * 2, oy = (k >> 1) * 2;
-                if (sub[k] == 0) { store_direct_quadrant(p, &d, k, l); continue; }             /* its turn: the derived motion becomes visible */
-                if (!(b_sub_pred[sub[k]] & (1 << l))) { set_motion_l(p, ox, oy, 2, 2, 0, 0, l); continue; }
-                const int sw = b_sub_w[sub[k]], shh = b_sub_h[sub[k]];
-                for (int sy = 0; sy < 2; sy += shh)
-                    for (int sx = 0; sx < 2; sx += sw) {
-                        int dx, dy, px, py;
-                        if (rd_mvd(p, b, l, ox + sx, oy + sy, sw, shh, &dx, &dy) < 0) { ERR(p, "mvd out of range"); return -1; }
-                        predict_mv_l(p, ox + sx, oy + sy, sw, r[l][k], 0, &px, &py, l);
-                        set_motion_l(p, ox + sx, oy + sy, sw, shh, px + dx, py + dy, l);
-                    }
-            }
+            if (any_direct) direct_predict(p, &d);            /* from the macroblock's neighbours, before any of its own motion exists */
+        }
+        if (parse_inter_pred(p, b, 2, np, pt, 1, &d) < 0) return -1;
     }
-    (void)direct_all;
-    /* ---- coded_block_pattern, mb_qp_delta, residual: as in P macroblocks ---- */
-    const int c = rd_cbp(p, b, 0);
-    if (c < 0) { ERR(p, "invalid cbp"); return -1; }
-    m->cbp = (uint8_t)c;
-    int qp = p->sh.qp, has_res = m->cbp != 0;
-    if (has_res) {
-        int dqp = rd_mb_qp_delta(p, b);
-        if (dqp < -52 || dqp > 52) { ERR(p, "mb_qp_delta out of range"); return -1; }
-        if (p->strict_qp) qp = (p->qp_pred + dqp + 52) % 52;
-        else qp = p->sh.qp + dqp;
-        if (rd_residual(p, b, m, &cf) < 0) { ERR(p, "read residual data failed"); return -1; }
-    } else { memset(p->nnz + (size_t)p->mbi * 24, 0, 24); p->last_dqp = 0; }
-    if (store_coefs(p, m, &cf) < 0) return -1;
-    finish_mb_qp(p, m, has_res, qp);
-    if (br_overrun(b)) { ERR(p, "macroblock overruns the slice data"); return -1; }
-    return 0;
+    return parse_mb_tail(p, b, m);
 }
 
 /* one non-skipped macroblock of the current slice, whatever its slice type and entropy coder */
@@ -1340,7 +1314,7 @@ static long rbsp_stop_bit(const uint8_t *buf, int size)
 }
 
 /* ---------------------------------------------------------------- slice ------------------ */
-/* List X of the slice that starts (p->list0 / p->list1, with the slice's weights in p->sh.wp_tab) onto the picture's canonical list:
+/* List X of the slice that starts (p->list[X], with the slice's weights in p->sh.wp_tab) onto the picture's canonical list:
  * the first P / B slice's list IS the canonical list, verbatim, with its length and its duplicates.  Every entry i of a later slice
  * maps to canonical entry i where that one names the same frame (slices that agree keep their indices: such a picture is what it
  * was with one list per picture), else to the first canonical entry with the same frame - and, under explicit weights, the same
@@ -1348,9 +1322,9 @@ static long rbsp_stop_bit(const uint8_t *buf, int size)
  * are refused (without explicit weights that cannot happen: at most 16 frames, and an entry is only appended for a new frame). */
 static int map_slice_list(p264parse *p, int X)
 {
-    const int *loc = X ? p->list1 : p->list0, n_loc = X ? p->n_list1 : p->n_list0;
-    int *can = p->pic_list[X], *n_can = &p->n_pic_list[X];
-    const int wp = p->sh0.wp;
+    const int *loc = p->list[X], n_loc = p->n_list[X];
+    int *can = p->pic.list[X], *n_can = &p->pic.n_list[X];
+    const int wp = p->pic.wp;
     p->ref_map_used[X] = 0;
     if (*n_can == 0) {
         memcpy(can, loc, sizeof(int) * (size_t)n_loc); *n_can = n_loc;
@@ -1359,7 +1333,7 @@ static int map_slice_list(p264parse *p, int X)
     }
     for (int i = 0; i < n_loc; i++) {
         int j = -1;
-#define SAME_ENTRY(k) (can[k] == loc[i] && (!wp || !memcmp(p->sh0.wp_tab[X][k], p->sh.wp_tab[X][i], sizeof p->sh.wp_tab[X][i])))
+#define SAME_ENTRY(k) (can[k] == loc[i] && (!wp || !memcmp(p->pic.wp_tab[X][k], p->sh.wp_tab[X][i], sizeof p->sh.wp_tab[X][i])))
         if (i < *n_can && SAME_ENTRY(i)) j = i;
         for (int k = 0; k < *n_can && j < 0; k++) if (SAME_ENTRY(k)) j = k;
 #undef SAME_ENTRY
@@ -1367,7 +1341,7 @@ static int map_slice_list(p264parse *p, int X)
             if (*n_can >= P264HIP_MAX_REFS) { ERR(p, "the slices of the picture need more than %d entries in reference list %d", P264HIP_MAX_REFS, X); return -1; }
             j = (*n_can)++;
             can[j] = loc[i];
-            if (wp) memcpy(p->sh0.wp_tab[X][j], p->sh.wp_tab[X][i], sizeof p->sh.wp_tab[X][i]);
+            if (wp) memcpy(p->pic.wp_tab[X][j], p->sh.wp_tab[X][i], sizeof p->sh.wp_tab[X][i]);
         }
         p->ref_map[X][i] = (int8_t)j;
         if (j != i) p->ref_map_used[X] = 1;
@@ -1385,15 +1359,16 @@ static void end_slice(p264parse *p, int first, int end)
 {
     picbuf_t *q = &p->buf[p->cur];
     const int isB = p->sh.type == P264_SLICE_B;
-    if (p->pic_ref_idc && p->has_col) {
+    if (p->pic.ref_idc && p->has_col) {
         int16_t *cm = p->col_mv[p->cur_slot]; int8_t *cr = p->col_ref[p->cur_slot]; int32_t *cu = p->col_uid[p->cur_slot];
         for (int i = first * 4; i < end * 4; i++) {
-            const int r0 = q->ref[i], r1 = isB ? q->ref1[i] : -1;
+            const int r0 = q->ref[0][i], r1 = isB ? q->ref[1][i] : -1;
             const int mbi = i >> 2, q8 = i & 3, b0 = (q8 >> 1) * 8 + (q8 & 1) * 2;
-            const int16_t *src = r0 >= 0 || r1 < 0 ? q->mv : q->mv1;                          /* the list-0 motion if there is one, else list 1 */
+            const int l = r0 >= 0 || r1 < 0 ? 0 : 1;                                          /* the list-0 motion if there is one, else list 1 */
+            const int16_t *src = q->mv[l];
             const int r = r0 >= 0 ? r0 : r1;
             cr[i] = (int8_t)r;
-            cu[i] = r < 0 ? -1 : (int32_t)p->dpb[r0 >= 0 ? p->list0[r0 < p->n_list0 ? r0 : 0] : p->list1[r1 < p->n_list1 ? r1 : 0]].uid;
+            cu[i] = r < 0 ? -1 : (int32_t)p->dpb[p->list[l][r < p->n_list[l] ? r : 0]].uid;
             for (int k = 0; k < 4; k++) {
                 const int blk = b0 + (k >> 1) * 4 + (k & 1);
                 cm[(mbi * 16 + blk) * 2] = r < 0 ? 0 : src[(mbi * 16 + blk) * 2]; cm[(mbi * 16 + blk) * 2 + 1] = r < 0 ? 0 : src[(mbi * 16 + blk) * 2 + 1];
@@ -1403,181 +1378,225 @@ static void end_slice(p264parse *p, int first, int end)
     if (p->sh.type == P264_SLICE_I) return;
     for (int X = 0; X < (isB ? 2 : 1); X++) {
         if (!p->ref_map_used[X]) continue;
-        int8_t *ref = X ? q->ref1 : q->ref;
+        int8_t *ref = q->ref[X];
         for (int i = first * 4; i < end * 4; i++) if (ref[i] >= 0) ref[i] = p->ref_map[X][ref[i] & (P264HIP_MAX_REFS - 1)];
     }
 }
 
+/* the picture as the device gets it: the canonical lists and weights */
 static void publish_picture(p264parse *p)
 {
     picbuf_t *q = &p->buf[p->cur];
     p264hip_picture_t *d = &p->desc[p->cur];
     const pps_t *pps = &p->pps[p->active_pps];
+    const curpic_t *c = &p->pic;
     memset(d, 0, sizeof *d);
     d->mb_w = p->mb_w; d->mb_h = p->mb_h;
-    d->slice_type = p->sh0.type;
+    d->slice_type = c->type;
     d->chroma_qp_offset = pps->chroma_qp_offset;
-    d->deblock = (!pps->deblock_ctrl || p->pic_deblock) ? 1 : 0;     /* per-macroblock `edges` gate the slices that switch it off */
-    d->alpha_c0_offset = p->pic_alpha; d->beta_offset = p->pic_beta;
+    d->deblock = (!pps->deblock_ctrl || c->deblock) ? 1 : 0;         /* per-macroblock `edges` gate the slices that switch it off */
+    d->alpha_c0_offset = c->alpha; d->beta_offset = c->beta;
     d->dst_slot = p->cur_slot;
-    d->n_ref = p->n_list0;
-    for (int i = 0; i < p->n_list0; i++) d->ref_slot[i] = p->list0[i];
+    d->n_ref = c->n_list[0];
+    for (int i = 0; i < c->n_list[0]; i++) d->ref_slot[i] = c->list[0][i];
     d->n_coef_blocks = (uint32_t)q->coef_n;
-    d->frame_num = (uint32_t)p->sh0.frame_num;
-    d->mb = q->mb; d->mv = q->mv; d->ref_idx = q->ref; d->i4modes = q->i4; d->coefs = q->coef;
-    if (p->sh0.type == P264_SLICE_B) {
-        d->mv_l1 = q->mv1; d->ref_idx_l1 = q->ref1;
-        d->n_ref_l1 = p->n_list1;
-        for (int i = 0; i < p->n_list1; i++) d->ref_slot_l1[i] = p->list1[i];
-        d->weighted_bipred = p->weighted_bipred;
-        memcpy(d->bipred_weight, p->bipred_weight, sizeof d->bipred_weight);
+    d->frame_num = (uint32_t)c->first.frame_num;
+    d->mb = q->mb; d->mv = q->mv[0]; d->ref_idx = q->ref[0]; d->i4modes = q->i4; d->coefs = q->coef;
+    if (c->type == P264_SLICE_B) {
+        d->mv_l1 = q->mv[1]; d->ref_idx_l1 = q->ref[1];
+        d->n_ref_l1 = c->n_list[1];
+        for (int i = 0; i < c->n_list[1]; i++) d->ref_slot_l1[i] = c->list[1][i];
+        d->weighted_bipred = c->weighted_bipred;
+        memcpy(d->bipred_weight, c->bipred_weight, sizeof d->bipred_weight);
     }
-    if (p->pic_wp_set && p->sh0.wp) {
+    if (c->wp_set && c->wp) {
         d->explicit_wp = 1;
-        d->wp_log2_denom[0] = p->sh0.wp_denom[0]; d->wp_log2_denom[1] = p->sh0.wp_denom[1];
-        memcpy(d->wp, p->sh0.wp_tab, sizeof d->wp);
+        d->wp_log2_denom[0] = c->wp_denom[0]; d->wp_log2_denom[1] = c->wp_denom[1];
+        memcpy(d->wp, c->wp_tab, sizeof d->wp);
     }
 }
 
-/* decoder/decoder.c:502-593,598-664 */
+/* The steps of decode_slice return 0 or one of these.  A refused slice leaves the picture open: the next slice may still continue
+ * it (DESIGN.md section 7 lists these exits; some of them leave state of the refused slice behind). */
+enum { REFUSE_SLICE = -1, ABANDON_PICTURE = -2 };
+
+/* Step 1: the slice header (> 0: a slice to ignore), and the parameter sets it names made the active ones.  A new context
+ * (buffers, frame store) only when the picture geometry or the frame-store size changes; switching between parameter sets of the
+ * same geometry just activates them (H.264 7.4.1.2.1: the frame store lives on.  The reference loops forever in its context
+ * switch here, decoder/decoder.c:380-396, so there is nothing to match). */
+static int slice_header_and_context(p264parse *p, bitrd_t *b, int nal_type, int nal_ref_idc, slice_t *sh)
+{
+    const int rc = parse_slice_header(p, b, nal_type, nal_ref_idc, sh);
+    if (rc < 0) { ERR(p, "slice header decode failed"); return REFUSE_SLICE; }
+    if (rc > 0) return rc;
+    const pps_t *pps = &p->pps[sh->pps_id];
+    const sps_t *sps = &p->sps[pps->sps_id];
+    int slots = sps->num_ref_frames + 1;
+    if (slots < 2) slots = 2;
+    if (p->active_sps < 0 || !p->buf[0].mb || sps->mb_w != p->mb_w || sps->mb_h != p->mb_h || slots != p->slots) {
+        if (init_context(p, pps->sps_id, sh->pps_id) < 0) { ERR(p, "out of memory"); return REFUSE_SLICE; }
+    } else { p->active_sps = pps->sps_id; p->active_pps = sh->pps_id; }
+    return 0;
+}
+
+/* Step 2: the slice opens a new picture (decoder/decoder.c:502-593) or continues the open one */
+static int open_picture(p264parse *p, const slice_t *sh, int nal_type, int nal_ref_idc)
+{
+    curpic_t *c = &p->pic;
+    if (sh->first_mb != 0 && c->open) {
+        if (sh->first_mb != c->next_mb) { ERR(p, "slice starts at MB %d, expected %d", sh->first_mb, c->next_mb); return REFUSE_SLICE; }
+        c->slice_no++;
+        return 0;
+    }
+    if (sh->first_mb != 0) { ERR(p, "slice starts at MB %d but no picture is open", sh->first_mb); return REFUSE_SLICE; }
+    c->open = 1; c->next_mb = 0; c->slice_no = 0;
+    c->is_idr = nal_type == NAL_SLICE_IDR; c->ref_idc = nal_ref_idc;
+    if (c->is_idr) {                              /* p264_slice_idr, decoder/decoder.c:43-64 */
+        for (int i = 0; i < p->slots; i++) p->dpb[i].used = 0;
+        p->cur_slot = 0;
+    }
+    c->first = *sh;
+    c->type = sh->type;
+    c->deblock = 0; c->alpha = c->beta = 0;
+    c->n_list[0] = c->n_list[1] = 0; c->wp_set = 0;
+    p->n_list[0] = p->n_list[1] = 0;
+    p->buf[p->cur].coef_n = 0;
+    memset(p->slice_of, 0xff, (size_t)p->n_mb * sizeof(uint16_t));
+    c->poc = picture_order_count(p, sh, c->is_idr, nal_ref_idc);
+    c->uid = ++p->next_uid;
+    if (p->buf[p->cur].ref[1]) memset(p->buf[p->cur].ref[1], -1, (size_t)p->n_mb * 4);   /* nothing predicts from list 1 until a B macroblock says so */
+    return 0;
+}
+
+/* Step 3: what the macroblocks of the slice are parsed with - the filter deltas, its lists mapped onto the picture's, the QP chain */
+static int open_slice(p264parse *p, const slice_t *sh)
+{
+    curpic_t *c = &p->pic;
+    const pps_t *pps = &p->pps[sh->pps_id];
+    if (sh->disable_deblock != 1 && !c->deblock) {        /* the filter parameters are per picture on the device */
+        c->deblock = 1; c->alpha = sh->alpha_off; c->beta = sh->beta_off;
+    }
+    /* the device adds every macroblock's deltas to the picture's offsets: this slice's minus those of the first slice that filters */
+    p->slice_flags = sh->disable_deblock == 1 ? 0 : (uint16_t)(((sh->alpha_off - c->alpha) & 255) | ((sh->beta_off - c->beta) & 255) << 8);
+    p->sh = *sh;
+    if (sh->type == P264_SLICE_P || sh->type == P264_SLICE_B) {
+        /* the slice's own lists; reference indices are resolved through ONE list 0 (and one list 1) per picture on the device: the
+         * canonical lists, onto which the slice's are mapped below */
+        const int n_lists = sh->type == P264_SLICE_B ? 2 : 1;
+        for (int X = 0; X < n_lists; X++) {
+            if (X == 1 && !p->has_col) { ERR(p, "B slice without list-1 storage (Baseline parameter set)"); return REFUSE_SLICE; }
+            if ((p->n_list[X] = build_list(p, sh, X, p->list[X])) < 0) { p->n_list[X] = 0; return REFUSE_SLICE; }
+        }
+        /* a picture with any B slice is reconstructed as B, one with any P slice as P */
+        if (c->type != P264_SLICE_I && c->type != sh->type) { ERR(p, "P and B slices in one picture unsupported"); return REFUSE_SLICE; }
+        c->type = sh->type;
+        if (sh->type == P264_SLICE_B) c->weighted_bipred = pps->weighted_bipred == 2;    /* (the weights themselves: on the canonical lists, when the picture is complete) */
+        /* explicit weights: ONE table per picture on the device (like the lists); the first P / B slice's, every other one must match */
+        if (!c->wp_set) {
+            c->wp_set = 1;
+            c->wp = sh->wp; c->wp_denom[0] = sh->wp_denom[0]; c->wp_denom[1] = sh->wp_denom[1];
+            memcpy(c->wp_tab, sh->wp_tab, sizeof c->wp_tab); memcpy(c->wp_coded, sh->wp_tab, sizeof c->wp_coded);
+        } else if (sh->wp != c->wp || (sh->wp && (sh->wp_denom[0] != c->wp_denom[0] || sh->wp_denom[1] != c->wp_denom[1]
+                                                   || memcmp(sh->wp_tab, c->wp_coded, sizeof sh->wp_tab)))) {
+            ERR(p, "slices of one picture with different weight tables unsupported"); return REFUSE_SLICE;
+        }
+        for (int X = 0; X < n_lists; X++) if (map_slice_list(p, X) < 0) return ABANDON_PICTURE;
+    }
+    p->qp_pred = sh->qp;
+    /* The reference's QP bookkeeping (delta added to the slice QP, last QP carried over residual-free macroblocks and across
+     * pictures: SURVEY A-Q2) is kept for what the reference decodes - Baseline CAVLC I / P slices.  It decodes neither CABAC nor
+     * B slices nor any other profile (SURVEY 0): there is no behaviour to match there, those streams get the standard's chain. */
+    p->strict_qp = (p->opts & P264PARSE_OPT_STRICT) || pps->cabac || p->sps[pps->sps_id].profile_idc != 66 || sh->type == P264_SLICE_B;
+    p->cabac_on = pps->cabac;
+    p->last_dqp = 0;
+    return 0;
+}
+
+/* Step 4, CAVLC: slice_data( ) (7.3.4) with mb_skip_run (decoder/decoder.c:598-664) */
+static int slice_data_cavlc(p264parse *p, bitrd_t *b, const uint8_t *payload, int size)
+{
+    const int type = p->sh.type;
+    const long stop = rbsp_stop_bit(payload, size);
+    p->skip_run = -1;
+    while (p->pic.next_mb < p->n_mb) {
+        p->mbi = p->pic.next_mb; p->mbx = p->mbi % p->mb_w; p->mby = p->mbi / p->mb_w;
+        if (p->skip_run <= 0 && (long)br_consumed(b) >= stop) break;    /* !more_rbsp_data(): the slice ends here */
+        if (type != P264_SLICE_I && p->skip_run < 0) {
+            p->skip_run = (int)br_ue(b);
+            if (p->skip_run > p->n_mb - p->pic.next_mb) { ERR(p, "mb_skip_run %d runs past the picture", p->skip_run); return ABANDON_PICTURE; }
+        }
+        if (p->skip_run > 0) {
+            decode_skip(p);
+            p->skip_run--;
+        } else {
+            if ((long)br_consumed(b) >= stop) break;
+            if (parse_mb(p, b) < 0) { ERR(p, "macroblock read failed [%d,%d]", p->mbx, p->mby); return ABANDON_PICTURE; }
+            p->skip_run = -1;
+        }
+        p->slice_of[p->mbi] = (uint16_t)p->pic.slice_no;
+        p->pic.next_mb++;
+    }
+    return 0;
+}
+
+/* Step 4, CABAC: slice_data( ) (7.3.4): alignment bits, the engine started on the next byte, contexts from the slice QP; per
+ * macroblock mb_skip_flag (P / B), the macroblock, end_of_slice_flag */
+static int slice_data_cabac(p264parse *p, bitrd_t *b, const uint8_t *payload, int size)
+{
+    const int type = p->sh.type;
+    if (!p->cinfo) { ERR(p, "CABAC slice without its context storage (Baseline parameter set)"); return REFUSE_SLICE; }
+    const size_t at = (size_t)((br_consumed(b) + 7) >> 3);
+    if (at >= (size_t)size) { ERR(p, "CABAC slice without data"); return REFUSE_SLICE; }
+    p264cabac_init_contexts(&p->cb, type == P264_SLICE_I, p->sh.cabac_init_idc, p->sh.qp);
+    p264cabac_start(&p->cb, payload + at, (size_t)size - at);
+    for (;;) {
+        if (p->pic.next_mb >= p->n_mb) { ERR(p, "slice data runs past the picture"); return ABANDON_PICTURE; }
+        p->mbi = p->pic.next_mb; p->mbx = p->mbi % p->mb_w; p->mby = p->mbi / p->mb_w;
+        /* (the neighbour flags of the macroblock are needed before its first bin: begin_mb computes them again, identically) */
+        mb_neighbours(p);
+        if (type != P264_SLICE_I && cb_mb_skip_flag(p)) decode_skip(p);
+        else if (parse_mb(p, b) < 0) { ERR(p, "macroblock read failed [%d,%d]", p->mbx, p->mby); return ABANDON_PICTURE; }
+        if (p264cabac_bits_left(&p->cb) < -64) { ERR(p, "CABAC data overrun"); return ABANDON_PICTURE; }
+        p->slice_of[p->mbi] = (uint16_t)p->pic.slice_no;
+        p->pic.next_mb++;
+        if (p264cabac_terminate(&p->cb)) break;                  /* end_of_slice_flag */
+    }
+    return 0;
+}
+
+/* Step 6: every macroblock of the picture is there */
+static int close_picture(p264parse *p, const p264hip_picture_t **pic)
+{
+    curpic_t *c = &p->pic;
+    if (c->type == P264_SLICE_B) implicit_weights(p);         /* a function of the picture pair: per canonical pair */
+    if (c->type == P264_SLICE_B && c->wp_set && c->wp && bipred_sums_bad(p)) return ABANDON_PICTURE;
+    publish_picture(p);
+    *pic = &p->desc[p->cur];
+    finish_picture_marking(p);
+    p->cur ^= 1;
+    c->open = 0;
+    return 0;
+}
+
+/* One slice NAL: 1 = it completed a picture, 0 = it did not, -1 = refused.  Which refusals also abandon the open picture is
+ * decided here and nowhere else. */
 static int decode_slice(p264parse *p, int nal_type, int nal_ref_idc, const uint8_t *payload, int size,
                         const p264hip_picture_t **pic)
 {
     bitrd_t b; br_init(&b, payload, (size_t)size);
     slice_t sh;
-    int rc = parse_slice_header(p, &b, nal_type, nal_ref_idc, &sh);
-    if (rc < 0) { ERR(p, "slice header decode failed"); return -1; }
-    if (rc > 0) return 0;
-    const pps_t *pps = &p->pps[sh.pps_id];
-    /* A new context (buffers, frame store) only when the picture geometry or the frame-store size changes; switching
-     * between parameter sets of the same geometry just activates them (H.264 7.4.1.2.1: the frame store lives on.  The
-     * reference loops forever in its context switch here, decoder/decoder.c:380-396, so there is nothing to match). */
-    {
-        const sps_t *sps = &p->sps[pps->sps_id];
-        int slots = sps->num_ref_frames + 1;
-        if (slots < 2) slots = 2;
-        if (p->active_sps < 0 || !p->buf[0].mb || sps->mb_w != p->mb_w || sps->mb_h != p->mb_h || slots != p->slots) {
-            if (init_context(p, pps->sps_id, sh.pps_id) < 0) { ERR(p, "out of memory"); return -1; }
-        } else { p->active_sps = pps->sps_id; p->active_pps = sh.pps_id; }
+    int rc = slice_header_and_context(p, &b, nal_type, nal_ref_idc, &sh);
+    if (rc > 0) return 0;                                     /* redundant picture: ignore the slice */
+    if (rc == 0) rc = open_picture(p, &sh, nal_type, nal_ref_idc);
+    if (rc == 0) rc = open_slice(p, &sh);
+    if (rc == 0) rc = p->cabac_on ? slice_data_cabac(p, &b, payload, size) : slice_data_cavlc(p, &b, payload, size);
+    if (rc == 0) {
+        end_slice(p, sh.first_mb, p->pic.next_mb);
+        if (p->pic.next_mb < p->n_mb) return 0;               /* wait for the next slice of this picture */
+        rc = close_picture(p, pic);
     }
-
-    if (sh.first_mb == 0 || !p->pic_open) {
-        /* first slice of a new picture */
-        if (sh.first_mb != 0) { ERR(p, "slice starts at MB %d but no picture is open", sh.first_mb); return -1; }
-        p->pic_open = 1; p->next_mb = 0; p->slice_no = 0;
-        p->pic_is_idr = nal_type == NAL_SLICE_IDR; p->pic_ref_idc = nal_ref_idc;
-        if (p->pic_is_idr) {                      /* p264_slice_idr, decoder/decoder.c:43-64 */
-            for (int i = 0; i < p->slots; i++) p->dpb[i].used = 0;
-            p->cur_slot = 0;
-        }
-        p->sh0 = sh;
-        p->pic_deblock = 0; p->pic_alpha = p->pic_beta = 0;
-        p->buf[p->cur].coef_n = 0;
-        memset(p->slice_of, 0xff, (size_t)p->n_mb * sizeof(uint16_t));
-        p->n_list0 = 0; p->n_list1 = 0; p->pic_wp_set = 0;
-        p->n_pic_list[0] = p->n_pic_list[1] = 0;
-        p->cur_poc = picture_order_count(p, &sh, p->pic_is_idr, nal_ref_idc);
-        p->cur_uid = ++p->next_uid;
-        if (p->buf[p->cur].ref1) memset(p->buf[p->cur].ref1, -1, (size_t)p->n_mb * 4);   /* nothing predicts from list 1 until a B macroblock says so */
-    } else {
-        if (sh.first_mb != p->next_mb) { ERR(p, "slice starts at MB %d, expected %d", sh.first_mb, p->next_mb); return -1; }
-        p->slice_no++;
-    }
-    if (sh.disable_deblock != 1) {                /* the filter parameters are per picture on the device */
-        if (!p->pic_deblock) { p->pic_deblock = 1; p->pic_alpha = sh.alpha_off; p->pic_beta = sh.beta_off; }
-    }
-    /* the device adds every macroblock's deltas to the picture's offsets: this slice's minus those of the first slice that filters */
-    p->slice_flags = sh.disable_deblock == 1 ? 0 : (uint16_t)(((sh.alpha_off - p->pic_alpha) & 255) | ((sh.beta_off - p->pic_beta) & 255) << 8);
-    p->sh = sh;
-    if (sh.type == P264_SLICE_P || sh.type == P264_SLICE_B) {
-        /* the slice's own lists; reference indices are resolved through ONE list 0 (and one list 1) per picture on the device: the
-         * canonical lists, onto which the slice's are mapped below */
-        if ((p->n_list0 = build_list(p, &sh, 0, p->list0)) < 0) { p->n_list0 = 0; return -1; }
-        if (sh.type == P264_SLICE_B) {
-            if (!p->has_col) { ERR(p, "B slice without list-1 storage (Baseline parameter set)"); return -1; }
-            if ((p->n_list1 = build_list(p, &sh, 1, p->list1)) < 0) { p->n_list1 = 0; return -1; }
-            if (p->sh0.type != P264_SLICE_B && p->slice_no > 0 && p->sh0.type == P264_SLICE_P) { ERR(p, "P and B slices in one picture unsupported"); return -1; }
-            p->sh0.type = P264_SLICE_B;           /* a picture with any B slice is reconstructed as B */
-            p->weighted_bipred = pps->weighted_bipred == 2;          /* (the weights themselves: on the canonical lists, when the picture is complete) */
-        } else {
-            if (p->sh0.type == P264_SLICE_B) { ERR(p, "P and B slices in one picture unsupported"); return -1; }
-            p->sh0.type = P264_SLICE_P;           /* a picture with any P slice is reconstructed as P */
-        }
-        /* explicit weights: ONE table per picture on the device (like the lists); the first P / B slice's, every other one must match */
-        if (!p->pic_wp_set) {
-            p->pic_wp_set = 1;
-            p->sh0.wp = sh.wp; p->sh0.wp_denom[0] = sh.wp_denom[0]; p->sh0.wp_denom[1] = sh.wp_denom[1];
-            memcpy(p->sh0.wp_tab, sh.wp_tab, sizeof sh.wp_tab); memcpy(p->wp_first, sh.wp_tab, sizeof sh.wp_tab);
-        } else if (sh.wp != p->sh0.wp || (sh.wp && (sh.wp_denom[0] != p->sh0.wp_denom[0] || sh.wp_denom[1] != p->sh0.wp_denom[1]
-                                                     || memcmp(sh.wp_tab, p->wp_first, sizeof sh.wp_tab)))) {
-            ERR(p, "slices of one picture with different weight tables unsupported"); return -1;
-        }
-        if (map_slice_list(p, 0) < 0 || (sh.type == P264_SLICE_B && map_slice_list(p, 1) < 0)) { p->pic_open = 0; return -1; }
-    }
-    p->qp_pred = sh.qp;
-    /* The reference's QP bookkeeping (delta added to the slice QP, last QP carried over residual-free macroblocks and across
-     * pictures: SURVEY A-Q2) is kept for what the reference decodes - Baseline CAVLC I / P slices.  It decodes neither CABAC nor
-     * B slices nor any other profile (SURVEY 0): there is no behaviour to match there, those streams get the standard's chain. */
-    p->strict_qp = (p->opts & P264PARSE_OPT_STRICT) || pps->cabac || p->sps[pps->sps_id].profile_idc != 66 || sh.type == P264_SLICE_B;
-
-    p->cabac_on = pps->cabac;
-    p->last_dqp = 0;
-    if (p->cabac_on) {
-        /* slice_data( ) with CABAC (7.3.4): alignment bits, the engine started on the next byte, contexts from the slice QP;
-         * per macroblock mb_skip_flag (P / B), the macroblock, end_of_slice_flag */
-        if (!p->cinfo) { ERR(p, "CABAC slice without its context storage (Baseline parameter set)"); return -1; }
-        const size_t at = (size_t)((br_consumed(&b) + 7) >> 3);
-        if (at >= (size_t)size) { ERR(p, "CABAC slice without data"); return -1; }
-        p264cabac_init_contexts(&p->cb, sh.type == P264_SLICE_I, sh.cabac_init_idc, sh.qp);
-        p264cabac_start(&p->cb, payload + at, (size_t)size - at);
-        for (;;) {
-            if (p->next_mb >= p->n_mb) { ERR(p, "slice data runs past the picture"); p->pic_open = 0; return -1; }
-            p->mbi = p->next_mb; p->mbx = p->mbi % p->mb_w; p->mby = p->mbi / p->mb_w;
-            /* (the neighbour flags of the macroblock are needed before its first bin: begin_mb computes them again, identically) */
-            mb_neighbours(p);
-            if (sh.type != P264_SLICE_I && cb_mb_skip_flag(p)) { if (sh.type == P264_SLICE_B) decode_bskip(p); else decode_pskip(p); }
-            else if (parse_mb(p, &b) < 0) { ERR(p, "macroblock read failed [%d,%d]", p->mbx, p->mby); p->pic_open = 0; return -1; }
-            if (p264cabac_bits_left(&p->cb) < -64) { ERR(p, "CABAC data overrun"); p->pic_open = 0; return -1; }
-            p->slice_of[p->mbi] = (uint16_t)p->slice_no;
-            p->next_mb++;
-            if (p264cabac_terminate(&p->cb)) break;              /* end_of_slice_flag */
-        }
-    } else {
-    long stop = rbsp_stop_bit(payload, size);
-    p->skip_run = -1;
-    while (p->next_mb < p->n_mb) {
-        p->mbi = p->next_mb; p->mbx = p->mbi % p->mb_w; p->mby = p->mbi / p->mb_w;
-        if (p->skip_run <= 0 && (long)br_consumed(&b) >= stop) break;   /* !more_rbsp_data(): the slice ends here */
-        if (sh.type != P264_SLICE_I && p->skip_run < 0) {
-            p->skip_run = (int)br_ue(&b);
-            if (p->skip_run > p->n_mb - p->next_mb) { ERR(p, "mb_skip_run %d runs past the picture", p->skip_run); p->pic_open = 0; return -1; }
-        }
-        if (p->skip_run > 0) {
-            if (sh.type == P264_SLICE_B) decode_bskip(p); else decode_pskip(p);
-            p->skip_run--;
-        } else {
-            if ((long)br_consumed(&b) >= stop) break;
-            if (parse_mb(p, &b) < 0) { ERR(p, "macroblock read failed [%d,%d]", p->mbx, p->mby); p->pic_open = 0; return -1; }
-            p->skip_run = -1;
-        }
-        p->slice_of[p->mbi] = (uint16_t)p->slice_no;
-        p->next_mb++;
-    }
-    }
-    end_slice(p, sh.first_mb, p->next_mb);
-    if (p->next_mb < p->n_mb) return 0;                       /* wait for the next slice of this picture */
-
-    /* the picture as the device gets it, and as reference marking reads it: the canonical lists */
-    p->n_list0 = p->n_pic_list[0]; memcpy(p->list0, p->pic_list[0], sizeof p->list0);
-    p->n_list1 = p->n_pic_list[1]; memcpy(p->list1, p->pic_list[1], sizeof p->list1);
-    if (p->sh0.type == P264_SLICE_B) implicit_weights(p);     /* a function of the picture pair: per canonical pair */
-    if (p->sh0.type == P264_SLICE_B && p->pic_wp_set && p->sh0.wp && bipred_sums_bad(p)) { p->pic_open = 0; return -1; }
-    publish_picture(p);
-    *pic = &p->desc[p->cur];
-    finish_picture_marking(p);
-    p->cur ^= 1;
-    p->pic_open = 0;
-    return 1;
+    if (rc == ABANDON_PICTURE) p->pic.open = 0;
+    return rc < 0 ? -1 : 1;
 }
 
 /* ---------------------------------------------------------------- public ---------------- */
@@ -1669,8 +1688,7 @@ static p264parse *kat_state(void)
     if (!p) return NULL;
     p->mb_w = 3; p->mb_h = 2; p->n_mb = 6; p->slots = P264HIP_MAX_REFS + 1;
     picbuf_t *q = &p->buf[0];
-    q->mv = (int16_t *)calloc(6 * 32, sizeof(int16_t)); q->mv1 = (int16_t *)calloc(6 * 32, sizeof(int16_t));
-    q->ref = (int8_t *)malloc(6 * 4); q->ref1 = (int8_t *)malloc(6 * 4);
+    for (int l = 0; l < 2; l++) { q->mv[l] = (int16_t *)calloc(6 * 32, sizeof(int16_t)); q->ref[l] = (int8_t *)malloc(6 * 4); }
     for (int i = 0; i <= P264HIP_MAX_REFS; i++) {
         p->col_mv[i] = (int16_t *)calloc(6 * 32, sizeof(int16_t)); p->col_ref[i] = (int8_t *)malloc(6 * 4); p->col_uid[i] = (int32_t *)malloc(6 * 4 * sizeof(int32_t));
     }
@@ -1680,23 +1698,23 @@ static p264parse *kat_state(void)
 }
 static void kat_free(p264parse *p)
 {
-    free(p->buf[0].mv); free(p->buf[0].mv1); free(p->buf[0].ref); free(p->buf[0].ref1);
+    for (int l = 0; l < 2; l++) { free(p->buf[0].mv[l]); free(p->buf[0].ref[l]); }
     for (int i = 0; i <= P264HIP_MAX_REFS; i++) { free(p->col_mv[i]); free(p->col_ref[i]); free(p->col_uid[i]); }
     free(p);
 }
-/* lists of a B picture from picture order counts: slot i holds list-0 entry i, slot n0 + k list-1 entry k unless that picture
- * (same order count) already sits in list 0 */
-static void kat_lists(p264parse *p, int n0, const int *poc0, int n1, const int *poc1, int cur_poc)
+/* lists of a B picture from picture order counts, into list / n_list (the picture's or the slice's: whichever the function under
+ * test reads): slot i holds list-0 entry i, slot n0 + k list-1 entry k unless that picture (same order count) already sits in list 0 */
+static void kat_lists(p264parse *p, int (*list)[P264HIP_MAX_REFS], int *n_list, int n0, const int *poc0, int n1, const int *poc1, int cur_poc)
 {
     int n = 0;
-    for (int i = 0; i < n0; i++) { p->dpb[n].used = 1; p->dpb[n].poc = poc0[i]; p->dpb[n].uid = (uint32_t)(poc0[i] + 4096); p->list0[i] = n++; }
+    for (int i = 0; i < n0; i++) { p->dpb[n].used = 1; p->dpb[n].poc = poc0[i]; p->dpb[n].uid = (uint32_t)(poc0[i] + 4096); list[0][i] = n++; }
     for (int k = 0; k < n1; k++) {
         int s = -1;
-        for (int i = 0; i < n0; i++) if (poc0[i] == poc1[k]) { s = p->list0[i]; break; }
+        for (int i = 0; i < n0; i++) if (poc0[i] == poc1[k]) { s = list[0][i]; break; }
         if (s < 0) { p->dpb[n].used = 1; p->dpb[n].poc = poc1[k]; p->dpb[n].uid = (uint32_t)(poc1[k] + 4096); s = n++; }
-        p->list1[k] = s;
+        list[1][k] = s;
     }
-    p->n_list0 = n0; p->n_list1 = n1; p->cur_poc = cur_poc;
+    n_list[0] = n0; n_list[1] = n1; p->pic.poc = cur_poc;
 }
 
 int p264parse_kat_bipred(int n0, const int *poc0, int n1, const int *poc1, int cur_poc, int16_t *weights)
@@ -1704,10 +1722,10 @@ int p264parse_kat_bipred(int n0, const int *poc0, int n1, const int *poc1, int c
     if (n0 < 0 || n1 < 0 || n0 > 8 || n1 > 8) return -1;
     p264parse *p = kat_state();
     if (!p) return -1;
-    kat_lists(p, n0, poc0, n1, poc1, cur_poc);
-    p->weighted_bipred = 1;
+    kat_lists(p, p->pic.list, p->pic.n_list, n0, poc0, n1, poc1, cur_poc);
+    p->pic.weighted_bipred = 1;
     implicit_weights(p);
-    memcpy(weights, p->bipred_weight, sizeof p->bipred_weight);
+    memcpy(weights, p->pic.bipred_weight, sizeof p->pic.bipred_weight);
     kat_free(p);
     return 0;
 }
@@ -1719,10 +1737,10 @@ int p264parse_kat_direct(int spatial, const int8_t *nb_ref, const int16_t *nb_mv
     if (n0 < 1 || n0 > 8 || n_col_list < 0 || n_col_list > 8) return -1;
     p264parse *p = kat_state();
     if (!p) return -1;
-    kat_lists(p, n0, poc0, 1, &poc1_0, cur_poc);
+    kat_lists(p, p->list, p->n_list, n0, poc0, 1, &poc1_0, cur_poc);
     p->sh.direct_spatial = spatial;
     picbuf_t *q = &p->buf[0];
-    memset(q->ref, -1, 24); memset(q->ref1, -1, 24);
+    memset(q->ref[0], -1, 24); memset(q->ref[1], -1, 24);
     /* neighbours A, B, C, D: the 4x4 block left of / above / above right of / above left of the macroblock's first block */
     static const int nb_mb[4] = { 3, 1, 2, 0 }, nb_quad[4] = { 1, 2, 2, 3 }, nb_sub[4] = { 3, 12, 12, 15 };
     static const int nb_flag[4] = { P264_AVAIL_LEFT, P264_AVAIL_TOP, P264_AVAIL_TOPRIGHT, P264_AVAIL_TOPLEFT };
@@ -1730,13 +1748,13 @@ int p264parse_kat_direct(int spatial, const int8_t *nb_ref, const int16_t *nb_mv
     for (int n = 0; n < 4; n++) {
         if (nb_ref[n] != -2) p->cur_avail |= nb_flag[n];        /* (availability is a property of the macroblock: both lists agree) */
         for (int l = 0; l < 2; l++) {
-            (l ? q->ref1 : q->ref)[nb_mb[n] * 4 + nb_quad[n]] = nb_ref[l * 4 + n] < 0 ? -1 : nb_ref[l * 4 + n];
-            int16_t *mv = (l ? q->mv1 : q->mv) + (nb_mb[n] * 16 + nb_sub[n]) * 2;
+            q->ref[l][nb_mb[n] * 4 + nb_quad[n]] = nb_ref[l * 4 + n] < 0 ? -1 : nb_ref[l * 4 + n];
+            int16_t *mv = q->mv[l] + (nb_mb[n] * 16 + nb_sub[n]) * 2;
             mv[0] = nb_mv[(l * 4 + n) * 2]; mv[1] = nb_mv[(l * 4 + n) * 2 + 1];
         }
     }
     /* the co-located macroblock as finish_picture_marking would have left it: the list-0 motion where there is one, else list 1 */
-    const int cs = p->list1[0];
+    const int cs = p->list[1][0];
     for (int q8 = 0; q8 < 4; q8++) {
         const int r0 = col_intra ? -1 : col_ref[q8], r1 = col_intra ? -1 : col_ref[4 + q8], r = r0 >= 0 ? r0 : r1;
         p->col_ref[cs][p->mbi * 4 + q8] = (int8_t)r;

@@ -106,14 +106,14 @@ static int cb_block(const p264parse *p, int x4, int y4, int *mbi, int *blk)
     const int mx = x4 >> 2, my = y4 >> 2;
     if (mx >= p->mb_w || my >= p->mb_h) return 0;
     const int i = my * p->mb_w + mx;
-    if (i != p->mbi && !(i < p->mbi && p->slice_of[i] == (uint16_t)p->slice_no)) return 0;
+    if (i != p->mbi && !(i < p->mbi && p->slice_of[i] == (uint16_t)p->pic.slice_no)) return 0;
     *mbi = i; *blk = (y4 & 3) * 4 + (x4 & 3);
     return 1;
 }
 static int cb_ref_idx(p264parse *p, int list, int bx, int by)
 {
     const picbuf_t *q = &p->buf[p->cur];
-    const int8_t *ref = list ? q->ref1 : q->ref;
+    const int8_t *ref = q->ref[list];
     const int x0 = p->mbx * 4 + bx, y0 = p->mby * 4 + by;
     int ctx = 0, mbi, blk;
     for (int n = 0; n < 2; n++) {
