@@ -206,6 +206,9 @@ typedef struct p264hip_input_layout {
 int  p264hip_input_layout(const p264hip_picture_t *desc, p264hip_input_layout_t *out);
 /* 0, or P264HIP_EINVAL where an explicit_wp picture's denominators, weights or offsets are out of range (every upload path checks it) */
 int  p264hip_wp_check(const p264hip_picture_t *desc);
+/* the index of the first of n_mb records whose coefficient blocks do not lie inside coefs[n_coef_blocks], or which is an I_PCM
+ * record without its twelve-block mask; -1 where there is none (every upload path checks it, device producers' blocks on the device) */
+int64_t p264hip_records_check(const p264hip_mb_t *mb, size_t n_mb, uint32_t n_coef_blocks);
 /* host side, no device involved: the picture's arrays copied into `dst` (cap >= layout.bytes) in that layout; the
  * macroblock records are checked as p264hip_upload checks them (coefficient ranges inside coefs[]).  Returns the bytes used
  * or a negative P264HIP_E* code. */
@@ -317,10 +320,9 @@ typedef struct p264hip_launch_info {
 } p264hip_launch_info_t;
 int  p264hip_last_launch(p264hip_ctx *ctx, p264hip_launch_info_t *out);
 
-/* Properties of the library build.  Bit 0 (P264HIP_BUILD_TIMING): compiled with -DP264AMD_TIMING_BUILD, which unlocks the
- * EXPM_* / EXPD_* switches of the kernel headers - pieces of the kernels compiled out to time the rest.  Such a build
- * produces wrong pictures; p264hip_create refuses to run in it unless P264AMD_TIMING_BUILD_OK=1 is set in the environment
- * (scratch/variants_run.sh does), bench.py records the flag and the test suite asserts it is clear. */
+/* Properties of the library build.  Bit 0 (P264HIP_BUILD_TIMING) is reserved and always clear: it marked builds with pieces of
+ * the kernels compiled out to time the rest, which no longer exist.  bench.py records the bit and the test suite asserts it is
+ * clear. */
 #define P264HIP_BUILD_TIMING 1
 int  p264hip_build_info(void);
 

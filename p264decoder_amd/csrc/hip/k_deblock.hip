@@ -6,11 +6,3 @@
 #include "p264hip.h"
 #include "device_common.h"
 #include "kernel_deblock.h"
-
-#ifdef EXPD_STAMPS
-// diagnostic build (scratch/r4_stamps.sh): the clock stamps of one wavefront, for p264hip_sync to write out
-extern "C" int p264hip_db_stamps_read(unsigned long long *h, size_t bytes)
-{
-    return hipMemcpyFromSymbol(h, HIP_SYMBOL(g_db_stamps), bytes) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -24,46 +24,7 @@
 #pragma once
 #include "device_common.h"
 #include "wavefront_sync.h"
-#ifndef DEBLOCK_WAIT_SLEEP
 #define DEBLOCK_WAIT_SLEEP 16
-#endif
-
-// Timing experiments (scratch/variant.sh, r4_dbexp.sh): results are wrong unless all defaults hold, so the switches only exist
-// in a build that says what it is (-DP264AMD_TIMING_BUILD, see kernel_mc.h and p264hip_build_info()).
-#if !defined(P264AMD_TIMING_BUILD) && (defined(EXPD_LUMA_EDGES) || defined(EXPD_CHROMA_EDGES) || defined(EXPD_STRONG) || defined(EXPD_HPASS) || defined(EXPD_BANDSYNC) || defined(EXPD_VMCNT) || defined(EXPD_STAMPS) || defined(EXPD_NO_SAMPLE_LOADS) || defined(EXPD_EDGE_INFO_EDGES))
-#error "EXPD_* switches produce wrong pictures: they need -DP264AMD_TIMING_BUILD"
-#endif
-#ifndef EXPD_LUMA_EDGES
-#define EXPD_LUMA_EDGES 4
-#endif
-#ifndef EXPD_CHROMA_EDGES
-#define EXPD_CHROMA_EDGES 4
-#endif
-#ifndef EXPD_STRONG
-#define EXPD_STRONG 1
-#endif
-#ifndef EXPD_HPASS
-#define EXPD_HPASS 1
-#endif
-#ifndef EXPD_BANDSYNC
-#define EXPD_BANDSYNC 1
-#endif
-#ifndef EXPD_VMCNT
-#define EXPD_VMCNT 1
-#endif
-#ifndef EXPD_EDGE_INFO_EDGES
-#define EXPD_EDGE_INFO_EDGES 4     // 1: the edge-info pass looks at the macroblock edges only (round 5: what a cheap road for macroblocks with one vector could save at most)
-#endif
-#ifndef EXPD_NO_SAMPLE_LOADS
-#define EXPD_NO_SAMPLE_LOADS 0     // 1: the macroblock's own samples are not loaded (round 5: what a fused prediction + filter pass could save at most)
-#endif
-#if defined(EXPD_STAMPS) && !defined(P264HIP_K_DEBLOCK_DECL_ONLY)
-// in-kernel clock stamps of one wavefront (diagnostic build only: scratch/r4_stamps.sh)
-__device__ unsigned long long g_db_stamps[256 * 8];
-#define DB_STAMP(k) do { if (stamp_me && t < 256) g_db_stamps[t * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define DB_STAMP(k) do { } while (0)
-#endif
 #define DY_DW 5                    // luma tile row: 5 dwords = cols -4..15
 #define DC_DW 3                    // chroma tile row: 3 dwords = cols -4..7
 #define DY_STRIDE (DY_DW * 4)
@@ -238,7 +199,7 @@ __device__ __forceinline__ uint4 edge_info_of(const PicDev *pd, const Geom &g, i
 #pragma unroll
     for (int dir = 0; dir < 2; dir++)
 #pragma unroll
-        for (int e = 0; e < EXPD_EDGE_INFO_EDGES; e++)
+        for (int e = 0; e < 4; e++)
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 if ((pass == 0) != (dir == 1 && e == 0)) continue;
@@ -483,9 +444,7 @@ template <int K> __device__ __forceinline__ pk16 pair_byte(uint32_t a, uint32_t 
 // work on macroblock x - 1 of its row in the SAME iteration: a lag of one column per row, not two (rounds 1 - 5 ran with two:
 // 2 x 67 + 120 = 254 dependent iterations down a 1080p picture instead of 67 + 120 = 187 - what a picture costs where it has a
 // CU to itself: 0.98 -> 0.7x ms at 256 pictures per launch and for the single picture of the drop-in API).
-#ifndef DB_LAG
 #define DB_LAG 1
-#endif
 #define RING_SLOTS   4
 #define RING_DW      24            // per slot: 4 luma rows x 4 dwords, then 2 planes x 2 rows x 2 dwords
 #define TILE_DW      100           // 16 luma rows x 4 dwords, 2 planes x 8 rows x 2 dwords, +4 so that octets land on different banks
@@ -567,7 +526,7 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
         const bool have_row = pic_ok && gr < nrows;
         const bool below_in_band = gr < last;                  // the row below belongs to the next octet
         const bool top_exists = row > 0;
-        const bool from_above = EXPD_BANDSYNC && have_row && gr == 0 && band > 0;   // the rows above come from the band above, through memory
+        const bool from_above = have_row && gr == 0 && band > 0;   // the rows above come from the band above, through memory
         const int rowc = min(row, g.mb_h - 1);
         // Strip layout: macroblock x of this row owns the 256 luma bytes at x*ystrip + row*256 and the 128 chroma bytes at
         // coff + x*cstrip + row*128 (rows of 8 bytes U, 8 bytes V).  This lane's two luma rows are the 32 bytes at +32j, its
@@ -619,23 +578,14 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
                     else { uint2 v2 = gload2(tp); fT.x = v2.x; fT.y = v2.y; }
                 }
                 const uint8_t *yp = ownY0 + (ptrdiff_t)t * (ptrdiff_t)sY, *cp2 = ownC0 + (ptrdiff_t)t * (ptrdiff_t)sC;
-                if (EXPD_NO_SAMPLE_LOADS) {
-                    const uint32_t a = (uint32_t)(uintptr_t)yp, b2 = (uint32_t)(uintptr_t)cp2;
-                    fYa = make_uint4(a, a + 1, a + 2, a + 3); fYb = fYa; fC = make_uint4(b2, b2 + 1, b2 + 2, b2 + 3);
-                    asm volatile("" : "+v"(fYa.x), "+v"(fYb.y), "+v"(fC.z));
-                } else {
                 fYa = gload4(yp); fYb = gload4(yp + 16);
-                { const uint2 ca2 = gload2(cp2), cb2 = gload2(cp2 + 16); fC = make_uint4(ca2.x, ca2.y, cb2.x, cb2.y); }
-                }
+                const uint2 ca2 = gload2(cp2), cb2 = gload2(cp2 + 16);
+                fC = make_uint4(ca2.x, ca2.y, cb2.x, cb2.y);
             }
         };
 
-#ifdef EXPD_STAMPS
-        const bool stamp_me = blockIdx.x == 100 && wave == EXPD_STAMPS && unit == wave && lane == 0;
-#endif
         prefetch(0);
         for (int t = 0; t < n_iter; t++) {
-            DB_STAMP(0);
             const int x = t - DB_LAG * gr;
             const bool act = have_row && x >= 0 && x < g.mb_w;         // filter macroblock x
             const bool flush = have_row && x >= 1 && x <= g.mb_w;       // store macroblock x-1
@@ -655,8 +605,7 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
             // Publish with RELEASE semantics at workgroup scope: the band below reads these macroblocks' pixels through global
             // memory on the same CU.  (The explicit wait drains the WHOLE wave's stores - the publisher lane speaks for all
             // eight octets of its wave, and a release fence only orders the publishing lane's own view.)
-            if (EXPD_VMCNT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            DB_STAMP(1);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (publisher) __hip_atomic_store(my_progress, min(max(x - 1, 0), g.mb_w), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             wave_lds_fence();
             // the rows above macroblock x-1 were finished by its horizontal pass in the previous iteration
@@ -686,7 +635,7 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
             if (any_edges) {
                 // ---------- vertical edges, in registers ----------
 #pragma unroll
-                for (int ed = 0; ed < EXPD_LUMA_EDGES; ed++) {
+                for (int ed = 0; ed < 4; ed++) {
                     const int b = E.code(0, ed, seg2), k = edge_class(0, ed);
                     if (__ballot(b != 0) == 0) continue;
                     pk16 p2 = pair_byte<1>(ya[ed], yb[ed]), p1 = pair_byte<2>(ya[ed], yb[ed]), p0 = pair_byte<3>(ya[ed], yb[ed]);
@@ -701,7 +650,7 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
                     pk_luma_normal(p2, p1, p0, q0, q1, q2, e, f & en, ap, aq, as_pk(ep.tc2(b)));
                     // bS 4 exists on macroblock edges only (k_deblock_bs), and the strong filter changes nothing where the
                     // sample flag is off
-                    if (EXPD_STRONG && ed == 0 && __ballot((as_u(f) & mask_bs4(b)) != 0)) {
+                    if (ed == 0 && __ballot((as_u(f) & mask_bs4(b)) != 0)) {
                         const pk16 str = as_pk(mask_bs4(b));
                         pk16 sp2 = op2, sp1 = op1, sp0 = op0, sq0 = oq0, sq1 = oq1, sq2 = oq2;
                         pk_luma_strong(pair_byte<0>(ya[ed], yb[ed]), sp2, sp1, sp0, sq0, sq1, sq2, pair_byte<3>(ya[ed+1], yb[ed+1]), f & str, ap, aq, A);
@@ -715,7 +664,7 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
                     ya[ed+1] = perm(tq, ya[ed+1], 0x03020504u); yb[ed+1] = perm(tq, yb[ed+1], 0x03020706u);
                 }
 #pragma unroll
-                for (int ed = 0; ed < EXPD_CHROMA_EDGES; ed += 2) {
+                for (int ed = 0; ed < 4; ed += 2) {
                     const int b = E.code(0, ed, cseg2), k = edge_class(0, ed) + 3, c = ed >> 1;
                     if (__ballot(b != 0) == 0) continue;
                     pk16 p1 = pair_byte<2>(ca[c], cb[c]), p0 = pair_byte<3>(ca[c], cb[c]);
@@ -730,7 +679,6 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
                     ca[c+1] = perm(Q0, ca[c+1], 0x03020104u); cb[c+1] = perm(Q0, cb[c+1], 0x03020105u);
                 }
             }
-            DB_STAMP(2);
             // ---- macroblock x-1 is final now: columns 0..11 still sit in the tile, its last four columns are ya[0]/yb[0].
             // Store it as whole rows; rows 12..15 go to the octet below instead, which stores them as its "rows above".
             if (flush) {
@@ -751,11 +699,9 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
                 *(uint2 *)tCa = make_uint2(ca[1], ca[2]);               *(uint2 *)tCb = make_uint2(cb[1], cb[2]);
             }
             wave_lds_fence();
-            DB_STAMP(3);
             if (t + 1 < n_iter) prefetch(t + 1);                      // the next iteration's loads travel during the horizontal pass
             // ---------- horizontal edges: column pairs out of the tile, filtered, back into the tile ----------
-            DB_STAMP(4);
-            const bool h_edges = EXPD_HPASS && __ballot(E.e[1] != 0) != 0;
+            const bool h_edges = __ballot(E.e[1] != 0) != 0;
             if (h_edges) {
                 if (act) {
                     // luma: columns 2j, 2j+1
@@ -766,7 +712,7 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
 #pragma unroll
                     for (int r = 0; r < 16; r++) { uint32_t v = *(const uint16_t *)(col + r * 16); c[4 + r] = as_pk(perm(v, v, 0x0c010c00u)); }
 #pragma unroll
-                    for (int ed = 0; ed < EXPD_LUMA_EDGES; ed++) {
+                    for (int ed = 0; ed < 4; ed++) {
                         const int b = E.code(1, ed, seg2), k = edge_class(1, ed);
                         if (__ballot(b != 0) == 0) continue;
                         pk16 &p3 = c[4*ed], &p2 = c[4*ed+1], &p1 = c[4*ed+2], &p0 = c[4*ed+3], &q0 = c[4*ed+4], &q1 = c[4*ed+5], &q2 = c[4*ed+6], &q3 = c[4*ed+7];
@@ -778,7 +724,7 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
                         const pk16 en = as_pk(mask_bs123(b, ed));
                         pk16 sp2 = p2, sp1 = p1, sp0 = p0, sq0 = q0, sq1 = q1, sq2 = q2;
                         pk_luma_normal(p2, p1, p0, q0, q1, q2, e, f & en, ap, aq, as_pk(ep.tc2(b)));
-                        if (EXPD_STRONG && ed == 0 && __ballot((as_u(f) & mask_bs4(b)) != 0)) {
+                        if (ed == 0 && __ballot((as_u(f) & mask_bs4(b)) != 0)) {
                             const pk16 str = as_pk(mask_bs4(b));
                             pk_luma_strong(p3, sp2, sp1, sp0, sq0, sq1, sq2, q3, f & str, ap, aq, A);
                             p2 = pk_sel(str, sp2, p2); p1 = pk_sel(str, sp1, p1); p0 = pk_sel(str, sp0, p0);
@@ -804,7 +750,7 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
 #pragma unroll
                     for (int r = 0; r < 8; r++) { uint32_t v = *(const uint16_t *)(ccol + r * 8); d[2 + r] = as_pk(perm(v, v, 0x0c010c00u)); }
 #pragma unroll
-                    for (int ed = 0; ed < EXPD_CHROMA_EDGES; ed += 2) {
+                    for (int ed = 0; ed < 4; ed += 2) {
                         const int b = E.code(1, ed, cseg2), k = edge_class(1, ed) + 3;
                         if (__ballot(b != 0) == 0) continue;
                         const EdgeParams ep(E, k);
@@ -821,7 +767,6 @@ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restr
                 }
                 wave_lds_fence();
             }
-            DB_STAMP(5);
             // the last four columns of this macroblock are the next one's columns -4..-1
             if (act) { ya0 = tYa[3]; yb0 = tYb[3]; ca0 = tCa[1]; cb0 = tCb[1]; }
             wave_lds_fence();

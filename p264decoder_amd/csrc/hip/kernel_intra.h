@@ -415,23 +415,17 @@ __device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, I
     gstore2(F + mb_chroma_off(g, mbx, mby) + r * 16 + p * 8, make_uint2(pa, pb));
 }
 
-#ifndef INTRA_ROW_WAVES
 #define INTRA_ROW_WAVES 16          // most wavefronts per picture workgroup
-#endif
-#ifndef INTRA_WAVES_PER_EU
 #define INTRA_WAVES_PER_EU 8        // (64 registers.  Round 3's kernel spilled at that and was built for 5 wavefronts per SIMD - 96 registers; since
                                     //  the band walk's state is scalar it needs 75 and fits 64 without scratch: config 2 at 5 / 6 / 7 / 8 wavefronts
                                     //  per SIMD 235 / 234 / 242 / 254 k frames/s, scratch/r4_intraocc.sh)
-#endif
 #define INTRA_BAND 4                // macroblock rows per wavefront = groups of sixteen lanes
 // P / B pictures: intra macroblocks without an intra neighbour to the left or above depend on nothing this kernel writes.
 // They are collected first (two lists, by macroblock type, so that the four macroblocks of an iteration run the same code)
 // and reconstructed four at a time in any order; only the rest goes through the ordered band walk below.  (I_PCM macroblocks
 // ride on the Intra4x4 list: they are told apart per group inside intra_luma4 / intra_chroma4, where they are a copy.)
-#ifndef INTRA_ROUNDS
 #define INTRA_ROUNDS     2          // rounds of ready macroblocks before the ordered band walk takes what is left (measured on the
                                     // bench stream: 1 / 2 / 3 and more rounds 0.46 / 0.33 / 0.37 ms per launch)
-#endif
 #define INTRA_FREE_CAP   256        // entries per list (uint16 macroblock index); macroblocks beyond it stay in the band walk
 #define INTRA_MASKS      160        // pictures of up to this many row windows (rows x windows of 64 macroblocks): 1080p has 136
 struct IntraSync { int progress[MAX_MB_ROWS / INTRA_BAND + 1]; };            // per band: columns of its last row that are final
@@ -689,9 +683,7 @@ void k_intra(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t
     __shared__ IntraShared sh;
     intra_picture(sh, pics, g, status, is_intra, (int)blockIdx.x, blockIdx.y != 0);
 }
-#ifndef INTRA_SPARSE_WAVES_PER_EU
 #define INTRA_SPARSE_WAVES_PER_EU 8
-#endif
 // The sparse build also carries the loop filter's EDGE INFO pass (kernel_deblock.h, K4a) as a third role: that pass is bound
 // by memory (84 bytes of records and vectors per macroblock in, 16 out) and depends on nothing but the parsed input, this
 // kernel is bound by vector-instruction issue and leaves the memory pipes idle - side by side in ONE launch they overlap

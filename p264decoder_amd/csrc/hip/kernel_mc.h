@@ -41,39 +41,6 @@
 #pragma once
 #include "device_common.h"
 #include <type_traits>
-// Timing experiments (scratch/r4_mcexp.sh, r4_mcparts.sh): pieces of the kernels compiled out to time the rest.  Results are
-// wrong unless all defaults hold, so the switches only exist in a build that says what it is: -DP264AMD_TIMING_BUILD, in
-// which p264hip_create refuses to run without P264AMD_TIMING_BUILD_OK=1 and p264hip_build_info() reports the flag.
-#if !defined(P264AMD_TIMING_BUILD) && (defined(EXPM_LUMA_COPY) || defined(EXPM_NO_STORE) || defined(EXPM_NO_WINDOW) || defined(EXPM_ONLY) || defined(EXPM_RESID) || defined(EXPM_FORCE_KEY) || defined(EXPM_HALF_LEVELS))
-#error "EXPM_* switches produce wrong pictures: they need -DP264AMD_TIMING_BUILD"
-#endif
-#ifndef EXPM_LUMA_COPY
-#define EXPM_LUMA_COPY 0
-#endif
-#ifndef EXPM_NO_STORE
-#define EXPM_NO_STORE 0            // 1: the sample stores are left out (their operands are still computed)
-#endif
-#ifndef EXPM_NO_WINDOW
-#define EXPM_NO_WINDOW 0           // 1: the reference-window loads are left out (the staging stores and everything behind them stay)
-#endif
-#ifndef EXPM_ONLY
-#define EXPM_ONLY 0                // 1: only the luma roles work, 2: only the chroma roles
-#endif
-#ifndef EXPM_RESID
-#define EXPM_RESID 1
-#endif
-#ifndef EXPM_HALF_LEVELS
-#define EXPM_HALF_LEVELS 0         // 1: a coded block's levels are read as ONE 16-byte piece at half the stride (round 6: what 8-bit levels could save at most)
-#endif
-// a coded block's sixteen levels (two 16-byte pieces)
-#define MC_LOAD_LEVELS(cfp, la_, lb_) do { if (EXPM_HALF_LEVELS) { la_ = gload4((const int16_t *)((const uint8_t *)(cfp) - ((const uint8_t *)(cfp) - (const uint8_t *)pd->coefs) / 2)); lb_ = la_; } \
-                                            else { la_ = gload4(cfp); lb_ = gload4((cfp) + 8); } } while (0)
-// EXPM_FORCE_KEY=k: every chunk is taken for key k (scratch/mc_count.sh: static instruction counts per role and class)
-#ifdef EXPM_FORCE_KEY
-#define MC_CHUNK_KEY(v) ((void)(v), (int)(EXPM_FORCE_KEY))
-#else
-#define MC_CHUNK_KEY(v) (v)
-#endif
 
 // ------------------------------------------------------------------------------------------
 // work lists
@@ -512,10 +479,8 @@ void k_mc_sort_wp(const PicDev *__restrict__ pics, uint32_t *__restrict__ mc_all
     mc_sort_picture<false, true>(pics, mc_all, g, ml, inv_mbw, cnt, pos, is_intra);
 }
 // batches with B pictures
-#ifndef MC_SORT_B_WAVES_PER_EU
 #define MC_SORT_B_WAVES_PER_EU 4       // 78 registers, no scratch, one workgroup per CU (round 4 shipped 8: 64 registers of which 9 spilled, two workgroups
                                        // per CU - the MC stage of a B launch 5.44 -> 5.37 ms, scratch/r4_sortb_occ.sh; given back for a binary without scratch)
-#endif
 __global__ __launch_bounds__(MC_SORT_THREADS, MC_SORT_B_WAVES_PER_EU)
 void k_mc_sort_b(const PicDev *__restrict__ pics, uint32_t *__restrict__ mc_all, Geom g, McLayout ml, uint32_t inv_mbw, uint8_t *__restrict__ is_intra)
 {
@@ -553,26 +518,17 @@ __device__ __forceinline__ void bstore(rsrc_t r, uint32_t off, uint32_t v) { __b
 __device__ __forceinline__ u32x4 bload4(rsrc_t r, uint32_t off) { return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0)); }
 // reconstructed samples are written once and not read again by this stage: non-temporal stores keep them from pushing
 // reference lines out of L2 (measured: -3 % on the stage)
-#ifndef MC_ST_AUX
 #define MC_ST_AUX 2
-#endif
 __device__ __forceinline__ u32x2 bload2(rsrc_t r, uint32_t off) { return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0)); }
 // (the 8-byte stores of quadrant items fill half a 16-byte row each: left to L2 to merge - non-temporal they cost 0.27 GB of
 // extra HBM writes per launch)
-#ifndef MC_ST2_AUX
 #define MC_ST2_AUX 0
-#endif
 __device__ __forceinline__ void bstore2(rsrc_t r, uint32_t off, uint32_t a, uint32_t b)
 {
-    if (EXPM_NO_STORE) { asm volatile("" :: "v"(a), "v"(b), "v"(off)); return; }
     const u32x2 v = { a, b }; __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)off, 0, MC_ST2_AUX);
 }
-// a reference-window load (timing switch EXPM_NO_WINDOW: no load, the offset stands in for the data)
-__device__ __forceinline__ u32x4 wload4(rsrc_t r, uint32_t off)
-{
-    if (EXPM_NO_WINDOW) { u32x4 v = { off, off, off, off }; asm volatile("" : "+v"(v)); return v; }
-    return bload4(r, off);
-}
+// a reference-window load
+__device__ __forceinline__ u32x4 wload4(rsrc_t r, uint32_t off) { return bload4(r, off); }
 // the value of lane ^ 1 / lane ^ 2 (inside a group of four lanes: DPP quad_perm, no LDS traffic)
 __device__ __forceinline__ uint32_t lane_xor1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true); }
 __device__ __forceinline__ uint32_t lane_xor2(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true); }
@@ -594,7 +550,6 @@ __device__ __forceinline__ void quad_transpose(uint32_t (&t)[4], const uint32_t 
 }
 __device__ __forceinline__ void bstore4(rsrc_t r, uint32_t off, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
 {
-    if (EXPM_NO_STORE) { asm volatile("" :: "v"(a), "v"(b), "v"(c), "v"(d), "v"(off)); return; }
     const u32x4 v = { a, b, c, d }; __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, MC_ST_AUX);
 }
 
@@ -1031,7 +986,7 @@ __device__ __forceinline__ void mc_luma_body(uint8_t *images, const uint32_t *re
     uint32_t key_w = cls_w[chunk >> 2];
     uint4 e = mc_entry_load<PB>(list, chunk * I::PER_WAVE + it);
     uint3 rec = make_uint3(0, 0, 0);
-    if (!PB) rec = mc_entry_record(pd, g, e.x, (MC_CHUNK_KEY((int)((key_w >> (8 * (chunk & 3))) & 255u)) & MCY_RESID) != 0);
+    if (!PB) rec = mc_entry_record(pd, g, e.x, ((int)((key_w >> (8 * (chunk & 3))) & 255u) & MCY_RESID) != 0);
   for (;;) {
     const int next = chunk + stride;
     const bool more = next < n_chunks;
@@ -1040,7 +995,7 @@ __device__ __forceinline__ void mc_luma_body(uint8_t *images, const uint32_t *re
     const int nx = min(next, n_chunks - 1);
     const uint32_t key_w_next = cls_w[nx >> 2];
     const uint4 e_next = mc_entry_load<PB>(list, nx * I::PER_WAVE + it);
-    const int key = MC_CHUNK_KEY((int)((key_w >> (8 * (chunk & 3))) & 255u));                   // scalar: the chunk's key bits
+    const int key = (int)((key_w >> (8 * (chunk & 3))) & 255u);                   // scalar: the chunk's key bits
     const int pc = key & 7;
     wave_lds_fence();                                      // the previous chunk's image has been read
     const bool valid = (e.x & MC_ITEM_MASK) != MC_ITEM_MASK;
@@ -1109,12 +1064,12 @@ __device__ __forceinline__ void mc_luma_body(uint8_t *images, const uint32_t *re
             if (!PB) resid_fields();
             if (coded) {
                 const int16_t *cf = pd->coefs + ((size_t)cidx + coef_slot(mask, blk)) * 16;
-                MC_LOAD_LEVELS(cf, la, lb);
+                la = gload4(cf); lb = gload4(cf + 8);
             }
         }
         wave_lds_fence();
         const LWin<I::PITCH> w = { img, xs & ~3, wy };
-        mc_luma_class(EXPM_LUMA_COPY ? PC_COPY : pc, out, w, ix, iy, fx, fy);
+        mc_luma_class(pc, out, w, ix, iy, fx, fy);
     } else {
         // The vectors differ inside the quadrant (sub-8x8 partitions), every lane has its own window and phase: windows
         // straight from memory, one pass per phase class present among the lanes.
@@ -1122,7 +1077,7 @@ __device__ __forceinline__ void mc_luma_body(uint8_t *images, const uint32_t *re
             if (!PB) resid_fields();
             if (coded) {
                 const int16_t *cf = pd->coefs + ((size_t)cidx + coef_slot(mask, blk)) * 16;
-                MC_LOAD_LEVELS(cf, la, lb);
+                la = gload4(cf); lb = gload4(cf + 8);
             }
         }
         // one prediction per lane from reference frame `ro` with vector `mv` (lanes with use = false are left alone)
@@ -1185,7 +1140,7 @@ __device__ __forceinline__ void mc_luma_body(uint8_t *images, const uint32_t *re
     }
     // the next chunk's record (its entries have long arrived: they were requested in front of this chunk's windows), in flight
     // while this chunk adds its residual and stores
-    if (!PB) rec = mc_entry_record(pd, g, e_next.x, (MC_CHUNK_KEY((int)((key_w_next >> (8 * (nx & 3))) & 255u)) & MCY_RESID) != 0);
+    if (!PB) rec = mc_entry_record(pd, g, e_next.x, ((int)((key_w_next >> (8 * (nx & 3))) & 255u) & MCY_RESID) != 0);
     if (PB) {
         // (core/macroblock.c:525-583, core/mc.c:76-132) the first pass's rows back into block order, then the mean or the weighted sum
         uint32_t p0[4];
@@ -1201,7 +1156,7 @@ __device__ __forceinline__ void mc_luma_body(uint8_t *images, const uint32_t *re
         for (int y = 0; y < 4; y++) out[y] = pd->weighted ? bipred_weight4(p0[y], out[y], wgt) : bipred_avg4(p0[y], out[y]);
     }
     // ---- residual (decoder/macroblock.c:839-847) ----
-    if (EXPM_RESID && (key & MCY_RESID) && __ballot(coded)) {
+    if ((key & MCY_RESID) && __ballot(coded)) {
         const uint32_t lv[8] = { la.x, la.y, la.z, la.w, lb.x, lb.y, lb.z, lb.w };
         uint32_t col[4][2];
         unscan_cols<false>(lv, col);
@@ -1327,14 +1282,14 @@ __device__ __forceinline__ void mc_chroma_body(uint8_t *images, const uint32_t *
     uint32_t key_w = cls_w[chunk >> 2];
     uint4 e = mc_entry_load<PB>(list, chunk * I::PER_WAVE + it);
     uint3 rec = make_uint3(0, 0, 0);
-    if (!PB) rec = mc_entry_record(pd, g, e.x, (MC_CHUNK_KEY((int)((key_w >> (8 * (chunk & 3))) & 255u)) & MCC_RESID) != 0);
+    if (!PB) rec = mc_entry_record(pd, g, e.x, ((int)((key_w >> (8 * (chunk & 3))) & 255u) & MCC_RESID) != 0);
   for (;;) {
     const int next = chunk + stride;
     const bool more = next < n_chunks;
     const int nx = min(next, n_chunks - 1);                // (unconditional, as in mc_luma_body)
     const uint32_t key_w_next = cls_w[nx >> 2];
     const uint4 e_next = mc_entry_load<PB>(list, nx * I::PER_WAVE + it);
-    const int key = MC_CHUNK_KEY((int)((key_w >> (8 * (chunk & 3))) & 255u));
+    const int key = (int)((key_w >> (8 * (chunk & 3))) & 255u);
     wave_lds_fence();                                      // the previous chunk's image has been read
     const bool valid = (e.x & MC_ITEM_MASK) != MC_ITEM_MASK;
     const int mbx = valid ? (int)((e.x >> 2) & 2047u) : 0, mby = valid ? (int)((e.x >> 13) & 1023u) : 0;
@@ -1413,7 +1368,7 @@ __device__ __forceinline__ void mc_chroma_body(uint8_t *images, const uint32_t *
         if (key & MCC_RESID) {
             if (!PB) resid_fields();
             const int16_t *cf = pd->coefs + (size_t)cidx * 16;
-            if (has_res && ((mask >> cb) & 1)) { const int16_t *c = cf + coef_slot(mask, cb) * 16; MC_LOAD_LEVELS(c, la, lb); }
+            if (has_res && ((mask >> cb) & 1)) { const int16_t *c = cf + coef_slot(mask, cb) * 16; la = gload4(c); lb = gload4(c + 8); }
             if (has_res && (mask & P264_COEF_CHROMA_DC)) dcl = gload2(cf + ((mask >> 24) & 1) * 16 + p * 4);
         }
         wave_lds_fence();
@@ -1432,7 +1387,7 @@ __device__ __forceinline__ void mc_chroma_body(uint8_t *images, const uint32_t *
         if (key & MCC_RESID) {
             if (!PB) resid_fields();
             const int16_t *cf = pd->coefs + (size_t)cidx * 16;
-            if (has_res && ((mask >> cb) & 1)) { const int16_t *c = cf + coef_slot(mask, cb) * 16; MC_LOAD_LEVELS(c, la, lb); }
+            if (has_res && ((mask >> cb) & 1)) { const int16_t *c = cf + coef_slot(mask, cb) * 16; la = gload4(c); lb = gload4(c + 8); }
             if (has_res && (mask & P264_COEF_CHROMA_DC)) dcl = gload2(cf + ((mask >> 24) & 1) * 16 + p * 4);
         }
         const int b0 = (q >> 1) * 8 + (q & 1) * 2;
@@ -1491,7 +1446,7 @@ __device__ __forceinline__ void mc_chroma_body(uint8_t *images, const uint32_t *
         }
     }
     // (the next chunk's record, as in mc_luma_body)
-    if (!PB) rec = mc_entry_record(pd, g, e_next.x, (MC_CHUNK_KEY((int)((key_w_next >> (8 * (nx & 3))) & 255u)) & MCC_RESID) != 0);
+    if (!PB) rec = mc_entry_record(pd, g, e_next.x, ((int)((key_w_next >> (8 * (nx & 3))) & 255u) & MCC_RESID) != 0);
     if (PB) {
         // the first pass's rows (dwords U left, U right, V left, V right) back into block order; then the mean or the weighted
         // sum, or - quadrants that were finished in the first pass - the samples as they are
@@ -1507,7 +1462,7 @@ __device__ __forceinline__ void mc_chroma_body(uint8_t *images, const uint32_t *
         }
     }
     // ---- residual (decoder/macroblock.c:851-890): chroma DC through the 2x2 transform, AC, inverse transform ----
-    if (EXPM_RESID && (key & MCC_RESID) && __ballot(has_res)) {
+    if ((key & MCC_RESID) && __ballot(has_res)) {
         const int qpc = chroma_qp(clip3i(qp + pd->chroma_qp_offset, 0, 51));
         const uint32_t lv[8] = { la.x, la.y, la.z, la.w, lb.x, lb.y, lb.z, lb.w };
         uint32_t col[4][2];
@@ -1548,12 +1503,10 @@ __device__ __forceinline__ void mc_chroma_body(uint8_t *images, const uint32_t *
 // windows ask for it (as four launches every kernel pulled the whole reference through HBM again: measured 7.0 GB of reads
 // against 3.1 GB of reference samples), and the bandwidth-bound chroma work shares its CU with the issue-bound luma work.
 // ------------------------------------------------------------------------------------------
-#ifndef MC_COST_YM
 #define MC_COST_YM 7u               // relative cost of one chunk (wavefront pass) per role, from the round-2 profiles (swept again in round 5: scratch/r5_mccost.sh)
 #define MC_COST_YQ 10u
 #define MC_COST_CM 5u
 #define MC_COST_CQ 9u
-#endif
 template <bool PB, bool WP>
 __device__ __forceinline__ void mc_roles(uint8_t *images, uint32_t *ref_tab, const PicDev *__restrict__ pics, const uint32_t *__restrict__ mc_all, const Geom &g, const McLayout &ml,
                                          int wgs_per_pic, int n_wgs, uint32_t inv_wgs)
@@ -1582,22 +1535,14 @@ __device__ __forceinline__ void mc_roles(uint8_t *images, uint32_t *ref_tab, con
     const float inv = (float)spare / (float)tt;
     const int w1 = (n1 != 0) + (int)((float)t1 * inv), w2 = (n2 != 0) + (int)((float)t2 * inv), w3 = (n3 != 0) + (int)((float)t3 * inv);
     const int w0 = wgs_per_pic - w1 - w2 - w3;             // (luma macroblock items take the rounding remainder)
-    if (EXPM_ONLY == 1 && s >= w0 + w1) return;                                 // (timing switches)
-    if (EXPM_ONLY == 2 && s < w0 + w1) return;
-    if (EXPM_ONLY == 3 && !(s < w0 || (s >= w0 + w1 && s < w0 + w1 + w2))) return;   // macroblock items only
     if (s < w0) mc_luma_body<true, PB, WP>(images, ref_tab, pd, mc, g, ml, s, w0);
     else if (s < w0 + w1) mc_luma_body<false, PB, WP>(images, ref_tab, pd, mc, g, ml, s - w0, w1);
     else if (s < w0 + w1 + w2) mc_chroma_body<true, PB, WP>(images, ref_tab, pd, mc, g, ml, s - w0 - w1, w2);
     else mc_chroma_body<false, PB, WP>(images, ref_tab, pd, mc, g, ml, s - w0 - w1 - w2, w3);
 }
-#ifndef MC_IMAGE_BYTES
 #define MC_IMAGE_BYTES (YItem<false>::LEAD + 4 * YItem<false>::WAVE_BYTES)         // the largest of the four roles' images
-#endif
-static_assert(EXPM_ONLY == 3 || (MC_IMAGE_BYTES >= YItem<true>::LEAD + 4 * YItem<true>::WAVE_BYTES && MC_IMAGE_BYTES >= 4 * CItem<true>::WAVE_BYTES && MC_IMAGE_BYTES >= 4 * CItem<false>::WAVE_BYTES), "image space");
-static_assert(MC_IMAGE_BYTES >= YItem<true>::LEAD + 4 * YItem<true>::WAVE_BYTES && MC_IMAGE_BYTES >= 4 * CItem<true>::WAVE_BYTES, "image space of the macroblock roles");
-#ifndef MC_WAVES_PER_EU
+static_assert(MC_IMAGE_BYTES >= YItem<true>::LEAD + 4 * YItem<true>::WAVE_BYTES && MC_IMAGE_BYTES >= 4 * CItem<true>::WAVE_BYTES && MC_IMAGE_BYTES >= 4 * CItem<false>::WAVE_BYTES, "image space");
 #define MC_WAVES_PER_EU 4
-#endif
 __global__ __launch_bounds__(256, MC_WAVES_PER_EU)
 void k_mc(const PicDev *__restrict__ pics, const uint32_t *__restrict__ mc_all, Geom g, McLayout ml, int wgs_per_pic, int n_wgs, uint32_t inv_wgs)
 {

@@ -39,11 +39,7 @@ extern "C" int p264hip_device_count(void)
 
 extern "C" int p264hip_build_info(void)
 {
-#ifdef P264AMD_TIMING_BUILD
-    return P264HIP_BUILD_TIMING;
-#else
-    return 0;
-#endif
+    return 0;                              // (bit 0, P264HIP_BUILD_TIMING, is reserved: include/p264hip.h)
 }
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -90,9 +86,9 @@ __global__ void k_tile_convert(uint8_t *frame, uint8_t *planar, Geom g, int to_p
     if (to_planar) *q = *t; else *t = *q;
 }
 
-// The check p264hip_upload runs on the host, for pictures that arrive in device memory (p264hip_input_reserve / _commit): every
-// macroblock's packed blocks must lie inside coefs[] - the kernels index the coefficient stream without further checks
-// (include/p264hip.h).  One flag per input slot.
+// The device twin of p264hip_records_check (csrc/host/input_layout.c), for pictures that arrive in device memory
+// (p264hip_input_reserve / _commit): every macroblock's packed blocks must lie inside coefs[] - the kernels index the coefficient
+// stream without further checks (include/p264hip.h).  One flag per input slot.
 __global__ void k_check_records(const p264hip_mb_t *mb, int n_mb, uint32_t n_coef_blocks, int *bad)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -156,14 +152,6 @@ extern "C" int p264hip_create(p264hip_ctx **out, int device, int mb_w, int mb_h,
     if (!out || mb_w < 1 || mb_w > 2047 || mb_h < 1 || mb_h > MAX_MB_ROWS ||    /* (11 bits of macroblock column in a work-list entry) */
         n_streams < 1 || slots < 1 || slots > P264HIP_MAX_REFS + 1 || max_pictures < 1)
         return fail(P264HIP_EINVAL, "p264hip_create: bad argument (mb %dx%d, streams %d, slots %d, pictures %d)", mb_w, mb_h, n_streams, slots, max_pictures);
-#ifdef P264AMD_TIMING_BUILD
-    {   // a build with pieces of the kernels compiled out: its pictures are wrong, it only runs for whoever asks for exactly that
-        const char *ok = getenv("P264AMD_TIMING_BUILD_OK");
-        if (!ok || strcmp(ok, "1") != 0)
-            return fail(P264HIP_EINVAL, "this library is a timing build (-DP264AMD_TIMING_BUILD: kernels with pieces compiled out, wrong pictures); "
-                                        "set P264AMD_TIMING_BUILD_OK=1 to run it anyway");
-    }
-#endif
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
         return fail(P264HIP_ENODEV, "no HIP device available: the MI355X reconstruction path cannot run (there is no CPU fallback)");
@@ -272,17 +260,13 @@ static int check_pic(p264hip_ctx *c, const p264hip_picture_t *p, bool arrays)
                     p->wp_log2_denom[0], p->wp_log2_denom[1]);
     if (!arrays) return 0;
     if (!p->mb || !p->mv || !p->ref_idx || !p->i4modes || (p->n_coef_blocks && !p->coefs)) return fail(P264HIP_EINVAL, "null picture array");
-    // every macroblock's packed blocks must lie inside coefs[] (the kernels index it without further checks)
-    const int n_mb = c->g.n_mb;
-    for (int i = 0; i < n_mb; i++) {
-        const p264hip_mb_t &m = p->mb[i];
-        if (m.coef_mask && (uint64_t)m.coef_index + (uint64_t)__builtin_popcount(m.coef_mask & 0x3ffffffu) > p->n_coef_blocks)
-            return fail(P264HIP_EINVAL, "macroblock %d: coefficient blocks [%u, +%d) outside coefs[%u]", i, m.coef_index,
-                        __builtin_popcount(m.coef_mask & 0x3ffffffu), p->n_coef_blocks);
-        if (m.mb_type == P264_MB_IPCM && m.coef_mask != P264_IPCM_COEF_MASK)
-            return fail(P264HIP_EINVAL, "macroblock %d: I_PCM with coef_mask 0x%x (its twelve sample blocks are 0x%x)", i, m.coef_mask, P264_IPCM_COEF_MASK);
-    }
-    return 0;
+    const int bad = (int)p264hip_records_check(p->mb, (size_t)c->g.n_mb, p->n_coef_blocks);
+    if (bad < 0) return 0;
+    const p264hip_mb_t &m = p->mb[bad];                       // which half of the rule the record breaks (the range first)
+    const int blocks = __builtin_popcount(m.coef_mask & 0x3ffffffu);
+    if (m.coef_mask && (uint64_t)m.coef_index + (uint64_t)blocks > p->n_coef_blocks)
+        return fail(P264HIP_EINVAL, "macroblock %d: coefficient blocks [%u, +%d) outside coefs[%u]", bad, m.coef_index, blocks, p->n_coef_blocks);
+    return fail(P264HIP_EINVAL, "macroblock %d: I_PCM with coef_mask 0x%x (its twelve sample blocks are 0x%x)", bad, m.coef_mask, P264_IPCM_COEF_MASK);
 }
 
 // The one way a context buffer grows (input slots, staging areas, clone destinations, job table, batch ring): the old buffer
@@ -501,21 +485,36 @@ extern "C" int p264hip_input_commit(p264hip_ctx *c, int slot)
     return P264HIP_OK;
 }
 
+// ---- frames at the host boundary: the strip layout of the device <-> planar I420 ----
+static size_t planar_bytes(const Geom &g) { return (size_t)g.w * g.h + 2 * (size_t)g.cw * g.ch; }
+// frame (stream, slot) -> the planar device buffer (to_planar) or back, queued on the context's stream
+static int tile_convert(p264hip_ctx *c, int stream, int slot, uint8_t *planar, bool to_planar)
+{
+    const int n_dw = c->g.n_mb * 96;
+    hipLaunchKernelGGL(k_tile_convert, dim3((n_dw + 255) / 256), dim3(256), 0, c->stream, frame_ptr(c, stream, slot), planar, c->g, to_planar ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the context's one planar staging frame (p264hip_read_frame / _read_frame_async / _write_frame), allocated at its first use
+static int planar_staging(p264hip_ctx *c)
+{
+    if (!c->d_planar) HIPCHK(hipMalloc((void **)&c->d_planar, planar_bytes(c->g)));
+    return 0;
+}
+
 extern "C" int p264hip_frame_planar_device(p264hip_ctx *c, int stream, int slot, int index, void **dev, size_t *bytes)
 {
     if (!c || !dev || !bytes || stream < 0 || stream >= c->n_streams || slot < 0 || slot >= c->slots || index < 0 || index >= 4096)
         return fail(P264HIP_EINVAL, "p264hip_frame_planar_device: bad argument (stream %d slot %d buffer %d)", stream, slot, index);
     HIPCHK(hipSetDevice(c->device));
-    const Geom &g = c->g;
-    const size_t sz = (size_t)g.w * g.h + 2 * (size_t)g.cw * g.ch;
+    const size_t sz = planar_bytes(c->g);
     if ((size_t)index >= c->planar_pool.size()) c->planar_pool.resize((size_t)index + 1, nullptr);
     if (!c->planar_pool[(size_t)index]) {
         hipError_t e = hipMalloc((void **)&c->planar_pool[(size_t)index], sz);
         if (e != hipSuccess) { c->planar_pool[(size_t)index] = nullptr; return fail(P264HIP_ENOMEM, "hipMalloc(%zu) for a planar frame: %s", sz, hipGetErrorString(e)); }
     }
-    const int n_dw = g.n_mb * 96;
-    hipLaunchKernelGGL(k_tile_convert, dim3((n_dw + 255) / 256), dim3(256), 0, c->stream, frame_ptr(c, stream, slot), c->planar_pool[(size_t)index], g, 1);
-    HIPCHK(hipGetLastError());
+    const int rc = tile_convert(c, stream, slot, c->planar_pool[(size_t)index], true);
+    if (rc) return rc;
     *dev = c->planar_pool[(size_t)index]; *bytes = sz;
     return P264HIP_OK;
 }
@@ -640,202 +639,266 @@ struct ScopedStamp {                   // HIP events on the context's own stream
     ~ScopedStamp() { if (c->timing) { (void)hipEventRecord(b, c->stream); c->stamps.push_back({ a, b, k }); } }
 };
 
-extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int *streams, int n)
+// ---- p264hip_reconstruct, step by step (in call order) ----
+// room for a batch of n pictures: the ring of descriptor buffers and the per-picture scratch of the kernels
+static int batch_reserve(p264hip_ctx *c, int n)
 {
-    if (!c || !pic_ids || !streams || n < 1) return fail(P264HIP_EINVAL, "p264hip_reconstruct: bad argument");
-    HIPCHK(hipSetDevice(c->device));
-    { const int rc = expand_pending(c); if (rc) return rc; }   // compact uploads since the last launch: one expansion kernel for all of them
-    if (n > c->batch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));              // (one wait for every buffer of the ring)
-        c->batch_cap = 0;
-        for (int i = 0; i < BATCH_RING; i++) {
-            int rc = grow(c, (void **)&c->h_batch[i], nullptr, (size_t)n * sizeof(PicDev), 0, true, WAIT_NONE, "the batch");
-            if (rc || (rc = grow(c, (void **)&c->d_batch[i], nullptr, (size_t)n * sizeof(PicDev), 0, false, WAIT_NONE, "the batch"))) return rc;
-            if (!c->batch_free[i]) HIPCHK(hipEventCreateWithFlags(&c->batch_free[i], hipEventDisableTiming));
-            HIPCHK(hipEventRecord(c->batch_free[i], c->stream));
-        }
-        int rc = grow(c, (void **)&c->d_is_intra, nullptr, (size_t)n * c->g.n_mb, 0, false, WAIT_NONE, "the batch");
-        if (rc || (rc = grow(c, (void **)&c->d_edge, nullptr, (size_t)n * c->g.n_mb * sizeof(EdgeInfo), 0, false, WAIT_NONE, "the batch")) ||
-            (rc = grow(c, (void **)&c->d_mc, nullptr, (size_t)n * c->ml.words * sizeof(uint32_t), 0, false, WAIT_NONE, "the batch"))) return rc;
-        c->batch_cap = n;
+    if (n <= c->batch_cap) return 0;
+    HIPCHK(hipStreamSynchronize(c->stream));              // (one wait for every buffer of the ring)
+    c->batch_cap = 0;
+    for (int i = 0; i < BATCH_RING; i++) {
+        int rc = grow(c, (void **)&c->h_batch[i], nullptr, (size_t)n * sizeof(PicDev), 0, true, WAIT_NONE, "the batch");
+        if (rc || (rc = grow(c, (void **)&c->d_batch[i], nullptr, (size_t)n * sizeof(PicDev), 0, false, WAIT_NONE, "the batch"))) return rc;
+        if (!c->batch_free[i]) HIPCHK(hipEventCreateWithFlags(&c->batch_free[i], hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->batch_free[i], c->stream));
     }
-    {   // pictures that came through p264hip_input_commit: the verdicts of their record checks, one wait for the whole batch
-        bool any_unchecked = false;
-        for (int i = 0; i < n; i++) { const int id = pic_ids[i]; if (id >= 0 && id < c->max_pictures && c->pics[(size_t)id].state == UNCHECKED) any_unchecked = true; }
-        if (any_unchecked) {
-            std::vector<int> bad((size_t)c->max_pictures);
-            const uint64_t upto = c->epoch;
-            HIPCHK(hipMemcpyAsync(bad.data(), c->d_slot_bad, sizeof(int) * bad.size(), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->done_epoch = upto;
-            for (int i = 0; i < n; i++) {
-                const int id = pic_ids[i];
-                if (id < 0 || id >= c->max_pictures || c->pics[(size_t)id].state != UNCHECKED) continue;
-                if (bad[(size_t)id]) { c->pics[(size_t)id].state = EMPTY; return fail(P264HIP_EINVAL, "picture slot %d: a macroblock's coefficient blocks lie outside coefs[] (the block a device producer committed is inconsistent)", id); }
-                c->pics[(size_t)id].state = READY;
-            }
-        }
+    int rc = grow(c, (void **)&c->d_is_intra, nullptr, (size_t)n * c->g.n_mb, 0, false, WAIT_NONE, "the batch");
+    if (rc || (rc = grow(c, (void **)&c->d_edge, nullptr, (size_t)n * c->g.n_mb * sizeof(EdgeInfo), 0, false, WAIT_NONE, "the batch")) ||
+        (rc = grow(c, (void **)&c->d_mc, nullptr, (size_t)n * c->ml.words * sizeof(uint32_t), 0, false, WAIT_NONE, "the batch"))) return rc;
+    c->batch_cap = n;
+    return 0;
+}
+
+// pictures that came through p264hip_input_commit: the verdicts of their record checks, one wait for the whole batch
+static int settle_unchecked(p264hip_ctx *c, const int *pic_ids, int n)
+{
+    bool any_unchecked = false;
+    for (int i = 0; i < n; i++) { const int id = pic_ids[i]; if (id >= 0 && id < c->max_pictures && c->pics[(size_t)id].state == UNCHECKED) any_unchecked = true; }
+    if (!any_unchecked) return 0;
+    std::vector<int> bad((size_t)c->max_pictures);
+    const uint64_t upto = c->epoch;
+    HIPCHK(hipMemcpyAsync(bad.data(), c->d_slot_bad, sizeof(int) * bad.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->done_epoch = upto;
+    for (int i = 0; i < n; i++) {
+        const int id = pic_ids[i];
+        if (id < 0 || id >= c->max_pictures || c->pics[(size_t)id].state != UNCHECKED) continue;
+        if (bad[(size_t)id]) { c->pics[(size_t)id].state = EMPTY; return fail(P264HIP_EINVAL, "picture slot %d: a macroblock's coefficient blocks lie outside coefs[] (the block a device producer committed is inconsistent)", id); }
+        c->pics[(size_t)id].state = READY;
     }
-    const int r = c->ring; c->ring = (c->ring + 1) % BATCH_RING;
-    HIPCHK(hipEventSynchronize(c->batch_free[r]));            // the copy that last used this staging buffer is done
-    PicDev *hb = c->h_batch[r];
-    bool any_p = false, any_b = false, any_i = false, any_wp = false;   // any picture with inter macroblocks / any B picture / any I picture / any explicit weights
-    bool any_dup = false;                                   // any unweighted P picture whose list 0 holds one frame at several indices
+    return 0;
+}
+
+// what the kernels see of the picture in input slot s when it decodes into frame store `st`
+static PicDev picdev_of(p264hip_ctx *c, const PicSlot &s, int st)
+{
+    PicDev d;
+    memset(&d, 0, sizeof d);
+    d.mb = (const p264hip_mb_t *)s.dev;
+    d.mv = (const int *)(s.dev + s.L.off_mv);
+    d.ref_idx = (const int8_t *)(s.dev + s.L.off_ref);
+    d.i4modes = s.dev + s.L.off_i4;
+    d.coefs = (const int16_t *)(s.dev + s.L.off_coef);
+    d.dst = frame_ptr(c, st, s.meta.dst_slot);
+    d.store = frame_ptr(c, st, 0);
+    d.store_bytes = (uint32_t)(c->frame_bytes * (size_t)c->slots);
+    d.dst_off = (uint32_t)(c->frame_bytes * (size_t)s.meta.dst_slot);
+    for (int k = 0; k < P264HIP_MAX_REFS; k++)
+        d.ref_off[k] = (uint32_t)(c->frame_bytes * (size_t)(k < s.meta.n_ref ? s.meta.ref_slot[k] : (s.meta.n_ref ? s.meta.ref_slot[0] : s.meta.dst_slot)));
+    d.n_ref = s.meta.n_ref; d.slice_type = s.meta.slice_type;
+    d.chroma_qp_offset = s.meta.chroma_qp_offset; d.deblock = s.meta.deblock;
+    d.alpha_off = s.meta.alpha_c0_offset; d.beta_off = s.meta.beta_offset;
+    if (s.meta.slice_type == P264_SLICE_B) {
+        d.mv_l1 = (const int *)(s.dev + s.L.off_mv_l1);
+        d.ref_idx_l1 = (const int8_t *)(s.dev + s.L.off_ref_l1);
+        d.bipred_w = (const int16_t *)(s.dev + s.L.off_weights);
+        d.n_ref_l1 = s.meta.n_ref_l1; d.weighted = s.meta.weighted_bipred;
+        for (int k = 0; k < P264HIP_MAX_REFS; k++)
+            d.ref_off_l1[k] = (uint32_t)(c->frame_bytes * (size_t)(k < s.meta.n_ref_l1 ? s.meta.ref_slot_l1[k] : s.meta.ref_slot_l1[0]));
+    }
+    if (s.meta.explicit_wp) {
+        d.wp = (const int16_t *)(s.dev + s.L.off_wp);
+        d.explicit_wp = 1; d.wp_denom_y = s.meta.wp_log2_denom[0]; d.wp_denom_c = s.meta.wp_log2_denom[1];
+    }
+    if (s.meta.slice_type == P264_SLICE_P && !s.meta.explicit_wp) {
+        // one frame at two indices (reordering commands that name it twice, a list padded with its last frame): the loop filter
+        // tells reference PICTURES apart (H.264 8.7.2.1), so such a picture takes the by-picture edge info, as weighted ones do
+        for (int k = 1; k < s.meta.n_ref && k < P264HIP_MAX_REFS; k++)
+            for (int j = 0; j < k; j++) if (s.meta.ref_slot[k] == s.meta.ref_slot[j]) d.dup_refs = 1;
+    }
+    return d;
+}
+
+// What the batch holds - the kernel instances and launch shapes follow from it: any picture with inter macroblocks / any B picture /
+// any I picture / any explicit weights / any unweighted P picture whose list 0 holds one frame at several indices
+struct BatchKinds { bool p = false, b = false, i = false, wp = false, dup = false; };
+
+// the batch's streams and slots checked (nothing is queued yet), one PicDev per picture in hb
+static int batch_fill(p264hip_ctx *c, const int *pic_ids, const int *streams, int n, PicDev *hb, BatchKinds *kinds)
+{
     for (int i = 0; i < n; i++) {                          // two pictures of one call must not share a stream: they would race on its frames
         const int st = streams[i];
         if (st < 0 || st >= c->n_streams) return fail(P264HIP_EINVAL, "stream %d out of range", st);
         c->stream_seen[(size_t)st] = 0;
     }
+    BatchKinds k;
     for (int i = 0; i < n; i++) {
         int id = pic_ids[i], st = streams[i];
         if (id < 0 || id >= c->max_pictures || c->pics[(size_t)id].state < STAGED) return fail(P264HIP_EINVAL, "picture slot %d is empty", id);
         if (c->stream_seen[(size_t)st]) return fail(P264HIP_EINVAL, "stream %d is named twice in one batch (entries %d and %d)", st, c->stream_seen[(size_t)st] - 1, i);
         c->stream_seen[(size_t)st] = i + 1;
         const PicSlot &s = c->pics[(size_t)id];
-        PicDev &d = hb[i];
-        memset(&d, 0, sizeof d);
-        d.mb = (const p264hip_mb_t *)s.dev;
-        d.mv = (const int *)(s.dev + s.L.off_mv);
-        d.ref_idx = (const int8_t *)(s.dev + s.L.off_ref);
-        d.i4modes = s.dev + s.L.off_i4;
-        d.coefs = (const int16_t *)(s.dev + s.L.off_coef);
-        d.dst = frame_ptr(c, st, s.meta.dst_slot);
-        d.store = frame_ptr(c, st, 0);
-        d.store_bytes = (uint32_t)(c->frame_bytes * (size_t)c->slots);
-        d.dst_off = (uint32_t)(c->frame_bytes * (size_t)s.meta.dst_slot);
-        for (int k = 0; k < P264HIP_MAX_REFS; k++)
-            d.ref_off[k] = (uint32_t)(c->frame_bytes * (size_t)(k < s.meta.n_ref ? s.meta.ref_slot[k] : (s.meta.n_ref ? s.meta.ref_slot[0] : s.meta.dst_slot)));
-        d.n_ref = s.meta.n_ref; d.slice_type = s.meta.slice_type;
-        d.chroma_qp_offset = s.meta.chroma_qp_offset; d.deblock = s.meta.deblock;
-        d.alpha_off = s.meta.alpha_c0_offset; d.beta_off = s.meta.beta_offset;
-        if (s.meta.slice_type == P264_SLICE_B) {
-            d.mv_l1 = (const int *)(s.dev + s.L.off_mv_l1);
-            d.ref_idx_l1 = (const int8_t *)(s.dev + s.L.off_ref_l1);
-            d.bipred_w = (const int16_t *)(s.dev + s.L.off_weights);
-            d.n_ref_l1 = s.meta.n_ref_l1; d.weighted = s.meta.weighted_bipred;
-            for (int k = 0; k < P264HIP_MAX_REFS; k++)
-                d.ref_off_l1[k] = (uint32_t)(c->frame_bytes * (size_t)(k < s.meta.n_ref_l1 ? s.meta.ref_slot_l1[k] : s.meta.ref_slot_l1[0]));
-            any_b = true;
-        }
-        if (s.meta.explicit_wp) {
-            d.wp = (const int16_t *)(s.dev + s.L.off_wp);
-            d.explicit_wp = 1; d.wp_denom_y = s.meta.wp_log2_denom[0]; d.wp_denom_c = s.meta.wp_log2_denom[1];
-            any_wp = true;
-        }
-        if (s.meta.slice_type == P264_SLICE_P && !s.meta.explicit_wp) {
-            // one frame at two indices (reordering commands that name it twice, a list padded with its last frame): the loop filter
-            // tells reference PICTURES apart (H.264 8.7.2.1), so such a picture takes the by-picture edge info, as weighted ones do
-            for (int k = 1; k < s.meta.n_ref && k < P264HIP_MAX_REFS; k++)
-                for (int j = 0; j < k; j++) if (s.meta.ref_slot[k] == s.meta.ref_slot[j]) d.dup_refs = 1;
-            any_dup |= d.dup_refs != 0;
-        }
-        any_p |= s.meta.slice_type != P264_SLICE_I;
-        any_i |= s.meta.slice_type == P264_SLICE_I;
+        hb[i] = picdev_of(c, s, st);
+        k.p |= s.meta.slice_type != P264_SLICE_I;
+        k.b |= s.meta.slice_type == P264_SLICE_B;
+        k.i |= s.meta.slice_type == P264_SLICE_I;
+        k.wp |= s.meta.explicit_wp != 0;
+        k.dup |= hb[i].dup_refs != 0;
     }
+    *kinds = k;
+    return 0;
+}
+
+// The launch shapes: functions of the geometry, the compute units, the batch size, the batch's kinds and the tune_* knobs - no
+// HIP call in them.  Each fills its part of p264hip_launch_info_t.
+// k_mc: every picture gets the same number of workgroups, which split into the four roles on the device.  Enough workgroups per
+// picture to fill the chip a few times over, no more than there can be chunks (four wavefronts per workgroup, one chunk per
+// wavefront pass).
+static int mc_wgs_per_picture(const p264hip_ctx *c, int n)
+{
+    int wgs = (c->n_cu * 48 + n - 1) / n;   // (a dozen rounds of workgroups on small batches.  Round 5, 256 pictures per launch: 48 / 64 / 96 / 128 / 192 / 256
+                                       //  per picture -> 0.685 / 0.687 / 0.691 / 0.704 / 0.724 / 0.751 ms for the stage - a wavefront's first chunk has no prefetch)
+    if (wgs < 48) wgs = 48;            // (2048 pictures: 24 / 32 / 48 / 64 / 96 per picture -> 5.34 / 5.31 / 5.24 / 5.31 / 5.34 ms; with 24 the stage's reads grew by half:
+                                       //  a picture's roles drift apart and stop sharing reference lines in L2)
+    int max_wgs = 0;
+    for (int l = 0; l < ML_LISTS; l++) max_wgs += (int)(c->ml.max_chunks[l] + 3) / 4;
+    if (wgs > max_wgs) wgs = max_wgs;
+    if (c->tune_mc_wgs >= 4 && c->tune_mc_wgs <= max_wgs) wgs = c->tune_mc_wgs;
+    return wgs < 4 ? 4 : wgs;
+}
+
+// k_intra / k_intra_sparse, one workgroup per picture and role: 16 wavefronts while every picture can have a CU to itself, else 8 or
+// 4 so that two or four pictures share a CU (measured +19 % at 512 and +9 % at 1024 pictures; 2048: 2 / 4 / 8 / 16 -> 1.02 / 0.87 /
+// 0.90 / 1.10 ms)
+static int intra_waves(const p264hip_ctx *c, int n)
+{
+    if (c->tune_intra_waves >= 1 && c->tune_intra_waves <= INTRA_ROW_WAVES) return c->tune_intra_waves;
+    return n > 2 * c->n_cu ? INTRA_ROW_WAVES / 4 : n > c->n_cu ? INTRA_ROW_WAVES / 2 : INTRA_ROW_WAVES;
+}
+
+// edge-info workgroups per picture inside the k_intra_sparse launch (P pictures only, by index: no B picture, no explicit weights,
+// no frame twice in a list), 0: the pass takes its own launch (k_deblock_bs)
+static int edge_info_fused(const p264hip_ctx *c, const BatchKinds &k)
+{
+    if (k.i || k.b || k.wp || k.dup || c->tune_bs_fused == 0) return 0;
+    return c->tune_bs_fused > 0 ? c->tune_bs_fused : INTRA_BS_WGS;
+}
+
+static void deblock_shape(const p264hip_ctx *c, int n, p264hip_launch_info_t *li)
+{
+    const Geom &g = c->g;
+    // pictures per workgroup = as many as it takes to cover the batch with one workgroup per CU (a second, half-empty round
+    // of workgroups costs more than sharing a workgroup: 1280 pictures as 320 workgroups of 4 took 5.35 ms, as 256 of 5 ...)
+    int per_wg = (n + c->n_cu - 1) / c->n_cu;
+    if (per_wg < 1) per_wg = 1;
+    if (per_wg > MAX_PICS_PER_WG) per_wg = MAX_PICS_PER_WG;
+    // bands of 8 rows of one picture per wavefront while every picture has a CU to itself, else 4 rows of two pictures; a
+    // workgroup with more pictures than a wavefront holds (8 >> rb_log2) works on them in groups (units = band x group).
+    // (Round 4: 2 rows x 4 pictures ran as fast, 2.70 ms, but every second row's bottom lines cross a band - 0.4 GB more
+    // through memory per launch.)
+    // Which shape: the stage's time follows the wavefront-iterations it issues (round 5: 1.07 ms per 16 units of 127 iterations at
+    // 2 ... 15 pictures per workgroup, half-empty units included - it is bound by vector-instruction issue).  Bands of 4 rows hold
+    // two pictures per wavefront: an odd picture count leaves one unit in every band half empty; bands of 8 rows hold one picture,
+    // but run 8 iterations longer and the last band of a 68-row picture is half empty.  Take the cheaper one.
+    auto units_cost = [&](int lg) {
+        const int rows = 1 << lg, pw = 8 >> lg;
+        const long bands = (g.mb_h + rows - 1) / rows, groups = (per_wg + pw - 1) / pw;
+        return bands * groups * (long)(g.mb_w + 1 + DB_LAG * (rows - 1));
+    };
+    int rb_log2 = units_cost(3) < units_cost(2) ? 3 : 2;
+    // an odd number (>= 3) of pictures: the pairs in bands of 4 rows, the last picture alone in bands of 8 (k_deblock, odd_single)
+    const long cost_mixed = (per_wg >= 3 && (per_wg & 1)) ? ((g.mb_h + 3) / 4) * (long)(per_wg / 2) * (g.mb_w + 1 + 3 * DB_LAG) + ((g.mb_h + 7) / 8) * (long)(g.mb_w + 1 + 7 * DB_LAG) : -1;
+    int odd_single = cost_mixed >= 0 && cost_mixed < units_cost(rb_log2);
+    if (odd_single) rb_log2 = 2;
+    if (c->tune_rb_log2 >= 1 && c->tune_rb_log2 <= 3) { rb_log2 = c->tune_rb_log2; odd_single = 0; }
+    if (c->tune_pics_per_wg >= 1 && c->tune_pics_per_wg <= MAX_PICS_PER_WG) { per_wg = c->tune_pics_per_wg; odd_single = 0; }
+    if (c->tune_odd_single >= 0) odd_single = c->tune_odd_single && rb_log2 == 2 && per_wg >= 3 && (per_wg & 1);
+    const int n_bands = (g.mb_h + (1 << rb_log2) - 1) >> rb_log2;
+    const int n_units = !odd_single ? n_bands * ((per_wg + (8 >> rb_log2) - 1) / (8 >> rb_log2)) : n_bands * (per_wg / 2) + (g.mb_h + 7) / 8;
+    int waves = n_units < ROW_WAVES ? n_units : ROW_WAVES;
+    if (c->tune_db_waves >= 1 && c->tune_db_waves < waves) waves = c->tune_db_waves;
+    li->deblock_pics_per_wg = per_wg; li->deblock_rb_log2 = rb_log2; li->deblock_waves = waves; li->deblock_wgs = (n + per_wg - 1) / per_wg;
+    li->deblock_odd_single = odd_single;
+}
+
+// The launches, in stream order.  batch: the n PicDevs on the device; a failed launch is reported by p264hip_reconstruct's
+// hipGetLastError behind the last of them.
+static uint32_t inv_mb_w(const p264hip_ctx *c) { return (uint32_t)(((1ull << 32) - 1) / (unsigned)c->g.mb_w); }
+
+// motion compensation + residual of all inter macroblocks: device-side counting sort of the work items by what the
+// interpolation has to do, then the luma and chroma kernels over the sorted lists (kernel_mc.h), side by side
+static void launch_inter(p264hip_ctx *c, const PicDev *batch, int n, const BatchKinds &k)
+{
+    ScopedStamp t(c, 0);
+    const Geom g = c->g;
+    const McLayout ml = c->ml;
+    // (explicit weighted prediction in the batch: the instances that route such pictures to the weighted class, kernel_mc.h)
+    if (k.b) hipLaunchKernelGGL(k.wp ? k_mc_sort_b_wp : k_mc_sort_b, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, batch, c->d_mc, g, ml, inv_mb_w(c), c->d_is_intra);
+    else hipLaunchKernelGGL(k.wp ? k_mc_sort_wp : k_mc_sort, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, batch, c->d_mc, g, ml, inv_mb_w(c), c->d_is_intra);
+    // one launch for luma / chroma, macroblock / quadrant items (k_mc)
+    const int wgs = c->last.mc_wgs_per_picture = mc_wgs_per_picture(c, n);
+    // (a batch with explicit weighted prediction somewhere: the instance with the weighted generic class, kernel_mc.h: k_mc_wp)
+    hipLaunchKernelGGL(k.wp ? k_mc_wp : k_mc, dim3(((size_t)wgs * n + 7) / 8 * 8), dim3(256), 0, c->stream, batch, (const uint32_t *)c->d_mc, g, ml,
+                       wgs, wgs * n, (uint32_t)(((1ull << 32) - 1) / (unsigned)wgs));
+    // B pictures: the blocks that predict from both lists get their second prediction (and their residual) in a second pass
+    if (k.b)
+        hipLaunchKernelGGL(k_mc_second, dim3(((size_t)wgs * n + 7) / 8 * 8), dim3(256), 0, c->stream, batch, (const uint32_t *)c->d_mc, g, ml,
+                           wgs, wgs * n, (uint32_t)(((1ull << 32) - 1) / (unsigned)wgs));
+}
+
+static void launch_intra(p264hip_ctx *c, const PicDev *batch, int n, const BatchKinds &k)
+{
+    ScopedStamp t(c, 1);
+    const int waves = c->last.intra_waves = intra_waves(c, n);
+    // luma and chroma of a picture are independent chains: as two workgroups they run side by side
+    if (k.i) hipLaunchKernelGGL(k_intra, dim3(n, 2), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status, (const uint8_t *)c->d_is_intra);
+    else {
+        // (P / B pictures only.  Batches without B pictures: the loop filter's edge info is computed by extra workgroups of this
+        // launch, kernel_intra.h)
+        const int bs_wgs = c->last.edge_info_fused = edge_info_fused(c, k);
+        hipLaunchKernelGGL(k_intra_sparse, dim3((unsigned)n * (2 + bs_wgs)), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status,
+                           (const uint8_t *)c->d_is_intra, c->d_edge, inv_mb_w(c), bs_wgs);
+    }
+}
+
+static void launch_deblock(p264hip_ctx *c, const PicDev *batch, int n, const BatchKinds &k)
+{
+    ScopedStamp t(c, 2);
+    const Geom g = c->g;
+    // edge info (boundary strengths, averaged QPs per edge class): everything about an edge that does not depend on samples
+    // (explicit weighted prediction, a P list with one frame twice: the two-list instance, which compares reference pictures rather
+    // than indices - kernel_deblock.h)
+    if (k.b || k.wp || k.dup) hipLaunchKernelGGL(k_deblock_bs<true>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, batch, g, c->d_edge, inv_mb_w(c));
+    else if (!c->last.edge_info_fused) hipLaunchKernelGGL(k_deblock_bs<false>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, batch, g, c->d_edge, inv_mb_w(c));
+    p264hip_launch_info_t &li = c->last;
+    deblock_shape(c, n, &li);
+    hipLaunchKernelGGL(k_deblock, dim3(li.deblock_wgs), dim3(li.deblock_waves * 64), 0, c->stream, batch, g,
+                       (const EdgeInfo *)c->d_edge, c->d_status, n, li.deblock_rb_log2, li.deblock_pics_per_wg, li.deblock_odd_single);
+}
+
+extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int *streams, int n)
+{
+    if (!c || !pic_ids || !streams || n < 1) return fail(P264HIP_EINVAL, "p264hip_reconstruct: bad argument");
+    HIPCHK(hipSetDevice(c->device));
+    int rc = expand_pending(c);                             // compact uploads since the last launch: one expansion kernel for all of them
+    if (rc || (rc = batch_reserve(c, n)) || (rc = settle_unchecked(c, pic_ids, n))) return rc;
+    const int r = c->ring; c->ring = (c->ring + 1) % BATCH_RING;
+    HIPCHK(hipEventSynchronize(c->batch_free[r]));            // the copy that last used this staging buffer is done
+    BatchKinds k;
+    if ((rc = batch_fill(c, pic_ids, streams, n, c->h_batch[r], &k))) return rc;
     // from here on work that reads the batch's input slots is (about to be) queued: the slots carry the new epoch BEFORE the first
     // launch, so that whichever way this function returns - a launch error half-way included - a later p264hip_input_reserve
     // of one of them waits for the stream instead of letting a peer overwrite a block under running kernels
     ++c->epoch;
     for (int i = 0; i < n; i++) stamp(c, c->pics[(size_t)pic_ids[i]]);
     ScopedStamp whole(c, 3);
-    HIPCHK(hipMemcpyAsync(c->d_batch[r], hb, (size_t)n * sizeof(PicDev), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_batch[r], c->h_batch[r], (size_t)n * sizeof(PicDev), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->batch_free[r], c->stream));
-    const Geom g = c->g;
-    const uint32_t inv_mbw = (uint32_t)(((1ull << 32) - 1) / (unsigned)g.mb_w);
-    bool bs_fused = false;
-    p264hip_launch_info_t &li = c->last;
-    memset(&li, 0, sizeof li);
-    li.pictures = n; li.compute_units = c->n_cu;
-    if (any_p) {
-        // motion compensation + residual of all inter macroblocks: device-side counting sort of the work items by what the
-        // interpolation has to do, then the luma and chroma kernels over the sorted lists (kernel_mc.h), side by side
-        ScopedStamp t(c, 0);
-        const McLayout ml = c->ml;
-        // (explicit weighted prediction in the batch: the instances that route such pictures to the weighted class, kernel_mc.h)
-        if (any_b) hipLaunchKernelGGL(any_wp ? k_mc_sort_b_wp : k_mc_sort_b, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, c->d_batch[r], c->d_mc, g, ml, inv_mbw, c->d_is_intra);
-        else hipLaunchKernelGGL(any_wp ? k_mc_sort_wp : k_mc_sort, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, c->d_batch[r], c->d_mc, g, ml, inv_mbw, c->d_is_intra);
-        // one launch for luma / chroma, macroblock / quadrant items (k_mc): every picture gets the same number of workgroups,
-        // which split into the four roles on the device.  Enough workgroups per picture to fill the chip a few times over,
-        // no more than there can be chunks (four wavefronts per workgroup, one chunk per wavefront pass).
-        int wgs = (c->n_cu * 48 + n - 1) / n;   // (a dozen rounds of workgroups on small batches.  Round 5, 256 pictures per launch: 48 / 64 / 96 / 128 / 192 / 256
-                                           //  per picture -> 0.685 / 0.687 / 0.691 / 0.704 / 0.724 / 0.751 ms for the stage - a wavefront's first chunk has no prefetch)
-        if (wgs < 48) wgs = 48;            // (2048 pictures: 24 / 32 / 48 / 64 / 96 per picture -> 5.34 / 5.31 / 5.24 / 5.31 / 5.34 ms; with 24 the stage's reads grew by half:
-                                           //  a picture's roles drift apart and stop sharing reference lines in L2)
-        int max_wgs = 0;
-        for (int l = 0; l < ML_LISTS; l++) max_wgs += (int)(ml.max_chunks[l] + 3) / 4;
-        if (wgs > max_wgs) wgs = max_wgs;
-        if (c->tune_mc_wgs >= 4 && c->tune_mc_wgs <= max_wgs) wgs = c->tune_mc_wgs;
-        if (wgs < 4) wgs = 4;
-        li.mc_wgs_per_picture = wgs;
-        // (a batch with explicit weighted prediction somewhere: the instance with the weighted generic class, kernel_mc.h: k_mc_wp)
-        hipLaunchKernelGGL(any_wp ? k_mc_wp : k_mc, dim3(((size_t)wgs * n + 7) / 8 * 8), dim3(256), 0, c->stream, (const PicDev *)c->d_batch[r], (const uint32_t *)c->d_mc, g, ml,
-                           wgs, wgs * n, (uint32_t)(((1ull << 32) - 1) / (unsigned)wgs));
-        // B pictures: the blocks that predict from both lists get their second prediction (and their residual) in a second pass
-        if (any_b)
-            hipLaunchKernelGGL(k_mc_second, dim3(((size_t)wgs * n + 7) / 8 * 8), dim3(256), 0, c->stream, (const PicDev *)c->d_batch[r], (const uint32_t *)c->d_mc, g, ml,
-                               wgs, wgs * n, (uint32_t)(((1ull << 32) - 1) / (unsigned)wgs));
-    }
-    {
-        ScopedStamp t(c, 1);
-        // one workgroup per picture and role: 16 wavefronts while every picture can have a CU to itself, else 8 or 4 so that two or
-        // four pictures share a CU (measured +19 % at 512 and +9 % at 1024 pictures; 2048: 2 / 4 / 8 / 16 -> 1.02 / 0.87 / 0.90 / 1.10 ms)
-        int intra_waves = n > 2 * c->n_cu ? INTRA_ROW_WAVES / 4 : n > c->n_cu ? INTRA_ROW_WAVES / 2 : INTRA_ROW_WAVES;
-        if (c->tune_intra_waves >= 1 && c->tune_intra_waves <= INTRA_ROW_WAVES) intra_waves = c->tune_intra_waves;
-        li.intra_waves = intra_waves;
-        // luma and chroma of a picture are independent chains: as two workgroups they run side by side
-        if (any_i) hipLaunchKernelGGL(k_intra, dim3(n, 2), dim3(intra_waves * 64), (size_t)intra_waves * sizeof(IntraLds), c->stream, c->d_batch[r], g, c->d_status, (const uint8_t *)c->d_is_intra);
-        else {
-            // (P / B pictures only.  Batches without B pictures: the loop filter's edge info is computed by extra workgroups of this
-            // launch, kernel_intra.h)
-            bs_fused = !any_b && !any_wp && !any_dup && c->tune_bs_fused != 0;
-            const int bs_wgs = bs_fused ? (c->tune_bs_fused > 0 ? c->tune_bs_fused : INTRA_BS_WGS) : 0;
-            li.edge_info_fused = bs_wgs;
-            hipLaunchKernelGGL(k_intra_sparse, dim3((unsigned)n * (2 + bs_wgs)), dim3(intra_waves * 64), (size_t)intra_waves * sizeof(IntraLds), c->stream, c->d_batch[r], g, c->d_status,
-                               (const uint8_t *)c->d_is_intra, c->d_edge, inv_mbw, bs_wgs);
-        }
-    }
-    {
-        ScopedStamp t(c, 2);
-        // edge info (boundary strengths, averaged QPs per edge class): everything about an edge that does not depend on samples
-        // (explicit weighted prediction, a P list with one frame twice: the two-list instance, which compares reference pictures rather
-        // than indices - kernel_deblock.h)
-        if (any_b || any_wp || any_dup) hipLaunchKernelGGL(k_deblock_bs<true>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, c->d_batch[r], g, c->d_edge, inv_mbw);
-        else if (!bs_fused) hipLaunchKernelGGL(k_deblock_bs<false>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, c->d_batch[r], g, c->d_edge, inv_mbw);
-        // pictures per workgroup = as many as it takes to cover the batch with one workgroup per CU (a second, half-empty round
-        // of workgroups costs more than sharing a workgroup: 1280 pictures as 320 workgroups of 4 took 5.35 ms, as 256 of 5 ...)
-        int per_wg = (n + c->n_cu - 1) / c->n_cu;
-        if (per_wg < 1) per_wg = 1;
-        if (per_wg > MAX_PICS_PER_WG) per_wg = MAX_PICS_PER_WG;
-        // bands of 8 rows of one picture per wavefront while every picture has a CU to itself, else 4 rows of two pictures; a
-        // workgroup with more pictures than a wavefront holds (8 >> rb_log2) works on them in groups (units = band x group).
-        // (Round 4: 2 rows x 4 pictures ran as fast, 2.70 ms, but every second row's bottom lines cross a band - 0.4 GB more
-        // through memory per launch.)
-        // Which shape: the stage's time follows the wavefront-iterations it issues (round 5: 1.07 ms per 16 units of 127 iterations at
-        // 2 ... 15 pictures per workgroup, half-empty units included - it is bound by vector-instruction issue).  Bands of 4 rows hold
-        // two pictures per wavefront: an odd picture count leaves one unit in every band half empty; bands of 8 rows hold one picture,
-        // but run 8 iterations longer and the last band of a 68-row picture is half empty.  Take the cheaper one.
-        auto units_cost = [&](int lg) {
-            const int rows = 1 << lg, pw = 8 >> lg;
-            const long bands = (g.mb_h + rows - 1) / rows, groups = (per_wg + pw - 1) / pw;
-            return bands * groups * (long)(g.mb_w + 1 + DB_LAG * (rows - 1));
-        };
-        int rb_log2 = units_cost(3) < units_cost(2) ? 3 : 2;
-        // an odd number (>= 3) of pictures: the pairs in bands of 4 rows, the last picture alone in bands of 8 (k_deblock, odd_single)
-        const long cost_mixed = (per_wg >= 3 && (per_wg & 1)) ? ((g.mb_h + 3) / 4) * (long)(per_wg / 2) * (g.mb_w + 1 + 3 * DB_LAG) + ((g.mb_h + 7) / 8) * (long)(g.mb_w + 1 + 7 * DB_LAG) : -1;
-        int odd_single = cost_mixed >= 0 && cost_mixed < units_cost(rb_log2);
-        if (odd_single) rb_log2 = 2;
-        if (c->tune_rb_log2 >= 1 && c->tune_rb_log2 <= 3) { rb_log2 = c->tune_rb_log2; odd_single = 0; }
-        if (c->tune_pics_per_wg >= 1 && c->tune_pics_per_wg <= MAX_PICS_PER_WG) { per_wg = c->tune_pics_per_wg; odd_single = 0; }
-        if (c->tune_odd_single >= 0) odd_single = c->tune_odd_single && rb_log2 == 2 && per_wg >= 3 && (per_wg & 1);
-        const int n_bands = (g.mb_h + (1 << rb_log2) - 1) >> rb_log2;
-        const int n_units = !odd_single ? n_bands * ((per_wg + (8 >> rb_log2) - 1) / (8 >> rb_log2)) : n_bands * (per_wg / 2) + (g.mb_h + 7) / 8;
-        int waves = n_units < ROW_WAVES ? n_units : ROW_WAVES;
-        if (c->tune_db_waves >= 1 && c->tune_db_waves < waves) waves = c->tune_db_waves;
-        li.deblock_pics_per_wg = per_wg; li.deblock_rb_log2 = rb_log2; li.deblock_waves = waves; li.deblock_wgs = (n + per_wg - 1) / per_wg;
-        li.deblock_odd_single = odd_single;
-        hipLaunchKernelGGL(k_deblock, dim3((n + per_wg - 1) / per_wg), dim3(waves * 64), 0, c->stream, c->d_batch[r], g,
-                           (const EdgeInfo *)c->d_edge, c->d_status, n, rb_log2, per_wg, odd_single);
-    }
+    memset(&c->last, 0, sizeof c->last);
+    c->last.pictures = n; c->last.compute_units = c->n_cu;
+    if (k.p) launch_inter(c, c->d_batch[r], n, k);
+    launch_intra(c, c->d_batch[r], n, k);
+    launch_deblock(c, c->d_batch[r], n, k);
     HIPCHK(hipGetLastError());
     return P264HIP_OK;
 }
@@ -878,21 +941,8 @@ static int drain_stamps(p264hip_ctx *c)
     return 0;
 }
 
-#ifdef EXPD_STAMPS
-extern "C" int p264hip_db_stamps_read(unsigned long long *h, size_t bytes);     // k_deblock.hip
-#endif
 extern "C" int p264hip_sync(p264hip_ctx *c)
 {
-#ifdef EXPD_STAMPS
-    if (const char *path = getenv("P264AMD_STAMPS_OUT")) {     // diagnostic build: the clock stamps of one k_deblock wavefront
-        static unsigned long long h[256 * 8];
-        (void)hipDeviceSynchronize();
-        if (p264hip_db_stamps_read(h, sizeof h) == 0) {
-            FILE *f = fopen(path, "w");
-            if (f) { for (int i = 0; i < 256; i++) { for (int k = 0; k < 8; k++) fprintf(f, "%llu ", h[i * 8 + k]); fprintf(f, "\n"); } fclose(f); }
-        }
-    }
-#endif
     if (!c) return fail(P264HIP_EINVAL, "null context");
     HIPCHK(hipSetDevice(c->device));
     { const int rc = expand_pending(c); if (rc) return rc; }
@@ -913,27 +963,23 @@ static int frame_io(p264hip_ctx *c, int stream, int slot, uint8_t *y, int ys, ui
         return fail(P264HIP_EINVAL, "frame access: bad argument (stream %d slot %d strides %d/%d)", stream, slot, ys, cs);
     HIPCHK(hipSetDevice(c->device));
     int rc = p264hip_sync(c);
-    if (rc) return rc;
     // frames live in the strip layout on the device; the host sees planes, through a planar staging buffer
-    uint8_t *f = frame_ptr(c, stream, slot);
+    if (rc || (rc = planar_staging(c))) return rc;
     const Geom &g = c->g;
     const size_t ysz = (size_t)g.w * g.h, csz = (size_t)g.cw * g.ch;
-    if (!c->d_planar) HIPCHK(hipMalloc((void **)&c->d_planar, ysz + 2 * csz));
     uint8_t *s = c->d_planar;
     hipMemcpyKind k = read ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice;
     struct { uint8_t *host; int hs; uint8_t *dev; int w, h; } pl[3] = {
         { y, ys, s, g.w, g.h }, { u, cs, s + ysz, g.cw, g.ch }, { v, cs, s + ysz + csz, g.cw, g.ch } };
-    const int n_dw = g.n_mb * 96;
     if (read) {
-        hipLaunchKernelGGL(k_tile_convert, dim3((n_dw + 255) / 256), dim3(256), 0, c->stream, f, s, g, 1);
+        if ((rc = tile_convert(c, stream, slot, s, true))) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
         for (auto &p : pl) HIPCHK(hipMemcpy2D(p.host, (size_t)p.hs, p.dev, (size_t)p.w, (size_t)p.w, (size_t)p.h, k));
     } else {
         for (auto &p : pl) HIPCHK(hipMemcpy2D(p.dev, (size_t)p.w, p.host, (size_t)p.hs, (size_t)p.w, (size_t)p.h, k));
-        hipLaunchKernelGGL(k_tile_convert, dim3((n_dw + 255) / 256), dim3(256), 0, c->stream, f, s, g, 0);
+        if ((rc = tile_convert(c, stream, slot, s, false))) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    HIPCHK(hipGetLastError());
     return P264HIP_OK;
 }
 
@@ -942,16 +988,14 @@ extern "C" int p264hip_read_frame_async(p264hip_ctx *c, int stream, int slot, ui
     if (!c || stream < 0 || stream >= c->n_streams || slot < 0 || slot >= c->slots || !y || !u || !v || ys < c->g.w || cs < c->g.cw)
         return fail(P264HIP_EINVAL, "frame access: bad argument (stream %d slot %d strides %d/%d)", stream, slot, ys, cs);
     HIPCHK(hipSetDevice(c->device));
+    int rc = planar_staging(c);
+    if (rc || (rc = tile_convert(c, stream, slot, c->d_planar, true))) return rc;
     const Geom &g = c->g;
     const size_t ysz = (size_t)g.w * g.h, csz = (size_t)g.cw * g.ch;
-    if (!c->d_planar) HIPCHK(hipMalloc((void **)&c->d_planar, ysz + 2 * csz));
     uint8_t *s = c->d_planar;
-    const int n_dw = g.n_mb * 96;
-    hipLaunchKernelGGL(k_tile_convert, dim3((n_dw + 255) / 256), dim3(256), 0, c->stream, frame_ptr(c, stream, slot), s, g, 1);
     HIPCHK(hipMemcpy2DAsync(y, (size_t)ys, s, (size_t)g.w, (size_t)g.w, (size_t)g.h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpy2DAsync(u, (size_t)cs, s + ysz, (size_t)g.cw, (size_t)g.cw, (size_t)g.ch, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpy2DAsync(v, (size_t)cs, s + ysz + csz, (size_t)g.cw, (size_t)g.cw, (size_t)g.ch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipGetLastError());
     return P264HIP_OK;
 }
 

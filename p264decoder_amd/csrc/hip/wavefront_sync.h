@@ -14,9 +14,7 @@
 #define ROW_WAVES      16            // wavefronts per picture workgroup (1024 threads)
 #define MAX_MB_ROWS    512
 #define SPIN_LIMIT     (1 << 22)
-#ifndef WAIT_SLEEP
 #define WAIT_SLEEP     32            // x64 cycles between polls: a polling wave must not eat the CU's scalar issue slots
-#endif
 
 struct RowSync {
     int progress[MAX_MB_ROWS];

@@ -39,11 +39,7 @@ int64_t p264hip_pack_compact(const p264hip_picture_t *p, void *dst_, size_t cap)
     const size_t n = (size_t)p->mb_w * (size_t)p->mb_h;
     if (n > P264HIP_COMPACT_MAX_MB) return P264HIP_EINVAL;
     if (cap < p264hip_compact_bound(p)) return P264HIP_ENOMEM;
-    for (size_t i = 0; i < n; i++) {                          /* as p264hip_pack_input: every macroblock's blocks inside coefs[] */
-        const p264hip_mb_t *m = &p->mb[i];
-        if (m->coef_mask && (uint64_t)m->coef_index + (uint64_t)__builtin_popcount(m->coef_mask & 0x3ffffffu) > p->n_coef_blocks) return P264HIP_EINVAL;
-        if (m->mb_type == P264_MB_IPCM && m->coef_mask != P264_IPCM_COEF_MASK) return P264HIP_EINVAL;   /* (the kernels read twelve blocks of samples) */
-    }
+    if (p264hip_records_check(p->mb, n, p->n_coef_blocks) >= 0) return P264HIP_EINVAL;      /* as p264hip_pack_input */
     uint8_t *dst = (uint8_t *)dst_;
     p264hip_compact_hdr_t h;
     memset(&h, 0, sizeof h);
@@ -169,12 +165,7 @@ int p264hip_compact_check(const p264hip_picture_t *d, const void *compact, size_
     p264hip_compact_hdr_t h;
     memcpy(&h, b, sizeof h);
     const size_t n = (size_t)d->mb_w * (size_t)d->mb_h;
-    const p264hip_mb_t *rec = (const p264hip_mb_t *)(b + h.off_rec);
-    for (size_t i = 0; i < n; i++)
-    {
-        if (rec[i].coef_mask && (uint64_t)rec[i].coef_index + (uint64_t)__builtin_popcount(rec[i].coef_mask & 0x3ffffffu) > h.n_coef_blocks) return P264HIP_EINVAL;
-        if (rec[i].mb_type == P264_MB_IPCM && rec[i].coef_mask != P264_IPCM_COEF_MASK) return P264HIP_EINVAL;
-    }
+    if (p264hip_records_check((const p264hip_mb_t *)(b + h.off_rec), n, h.n_coef_blocks) >= 0) return P264HIP_EINVAL;
     for (uint32_t l = 0; l < h.n_lists; l++) {
         const uint8_t *shape = b + h.list[l].off_shape;
         uint64_t nv = 0;

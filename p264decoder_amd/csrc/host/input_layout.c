@@ -42,12 +42,7 @@ int64_t p264hip_pack_input(const p264hip_picture_t *p, void *dst_, size_t cap)
     const int isB = p->slice_type == P264_SLICE_B;
     if (isB && (!p->mv_l1 || !p->ref_idx_l1)) return P264HIP_EINVAL;
     const size_t n = (size_t)p->mb_w * (size_t)p->mb_h;
-    /* every macroblock's packed blocks must lie inside coefs[] (the kernels index it without further checks) */
-    for (size_t i = 0; i < n; i++) {
-        const p264hip_mb_t *m = &p->mb[i];
-        if (m->coef_mask && (uint64_t)m->coef_index + (uint64_t)__builtin_popcount(m->coef_mask & 0x3ffffffu) > p->n_coef_blocks) return P264HIP_EINVAL;
-        if (m->mb_type == P264_MB_IPCM && m->coef_mask != P264_IPCM_COEF_MASK) return P264HIP_EINVAL;   /* (the kernels read twelve blocks of samples) */
-    }
+    if (p264hip_records_check(p->mb, n, p->n_coef_blocks) >= 0) return P264HIP_EINVAL;
     uint8_t *dst = (uint8_t *)dst_;
     memcpy(dst + L.off_mb, p->mb, n * sizeof(p264hip_mb_t));
     memcpy(dst + L.off_mv, p->mv, n * 64);
@@ -64,6 +59,20 @@ int64_t p264hip_pack_input(const p264hip_picture_t *p, void *dst_, size_t cap)
         memcpy(dst + L.off_wp, p->wp, sizeof p->wp);
     }
     return (int64_t)L.bytes;
+}
+
+/* The rule every road into a slot holds the macroblock records to: a macroblock's packed blocks lie inside coefs[] (the
+ * kernels index the coefficient stream without further checks), and an I_PCM record carries its twelve-block mask (the intra
+ * kernels read twelve blocks of samples).  The index of the first record that breaks it, or -1.  On the device, for blocks
+ * that never pass through the host: k_check_records (p264hip.hip). */
+int64_t p264hip_records_check(const p264hip_mb_t *mb, size_t n_mb, uint32_t n_coef_blocks)
+{
+    for (size_t i = 0; i < n_mb; i++) {
+        const p264hip_mb_t *m = &mb[i];
+        if (m->coef_mask && (uint64_t)m->coef_index + (uint64_t)__builtin_popcount(m->coef_mask & 0x3ffffffu) > n_coef_blocks) return (int64_t)i;
+        if (m->mb_type == P264_MB_IPCM && m->coef_mask != P264_IPCM_COEF_MASK) return (int64_t)i;
+    }
+    return -1;
 }
 
 /* the ranges of H.264 7.4.3.2 (include/p264hip.h): denominators 0 .. 7, offsets -128 .. 127, weights -128 .. 128 (128: the

@@ -40,8 +40,8 @@ def test_library_exports_every_declared_symbol(lib):
 
 
 def test_library_is_not_a_timing_build(lib):
-    """-DP264AMD_TIMING_BUILD unlocks the EXPM_* / EXPD_* switches (kernels with pieces compiled out, wrong pictures): the
-    library under test, and the one that travels to the GPU box, must not be one."""
+    """Bit 0 of p264hip_build_info() marked a library with pieces of its kernels compiled out (wrong pictures).  No such build
+    exists any more; the bit is reserved and stays clear in the library under test and the one that travels to the GPU box."""
     assert lib.p264hip_build_info() & N.BUILD_TIMING == 0
 
 
