@@ -15,7 +15,10 @@ Per picture:
    do the arithmetic, on coefficient blocks found as include/p264hip.h lays them out ([luma DC][chroma DC][blocks 0..23 present]
    from coef_index, levels in zig-zag order, AC-only blocks in [0..14]);
 3. oracle_deblock_picture on the picture's own records, as pcm_checker does.
-On a single-slice picture this is oracle_reconstruct, byte for byte (tests/test_intra_checker_cpu.py)."""
+On a single-slice picture this is oracle_reconstruct, byte for byte (tests/test_intra_checker_cpu.py).
+The two things borrowed from the oracle - the inter macroblocks' samples of step 1 and the residual arithmetic of step 2 - are
+pluggable (IntraChecker's `inter` and `residual`): tests/spec_recon.py plugs in tests/inter_checker.py and
+tests/residual_checker.py, filters with tests/slice_filter_checker.py and needs no oracle at all."""
 import ctypes as C
 
 import numpy as np
@@ -214,11 +217,23 @@ class IntraChecker:
     self.dc_log: one entry per macroblock with LEFT and TOP and without TOPLEFT that predicts Intra16x16 DC or chroma DC -
     (macroblock, 'i16' / 'cb' / 'cr', mb_type, the DC of the standard, the DC of the left column alone)."""
 
-    def __init__(self, oracle, mb_w, mb_h, slots):
+    def __init__(self, oracle, mb_w, mb_h, slots, residual=None, inter=None, store=None):
+        """residual: an object with the three hooks _luma4x4_residual / _luma16x16_residual / _chroma_residual (None: this
+        object's, which call the oracle's entry points); inter: a callable (pic) that leaves the finished inter macroblocks of
+        a P / B picture in store[dst_slot] (None: oracle_reconstruct_nodeblock on a flattened copy); store: the frame store,
+        store[slot] = [y, u, v] (None: the weighted checker's).  With all three given no oracle handle is needed (oracle=None:
+        tests/spec_recon.py); reconstruct()'s loop filter is the oracle's - such a caller filters nodeblock()'s result itself."""
         self.oracle = oracle
-        self.pcm = pcm_checker.PcmChecker(oracle, mb_w, mb_h, slots)
-        self.wp = self.pcm.wp
-        self.store, self.s_slot = self.pcm.store, self.pcm.s_slot
+        if oracle is not None:
+            self.pcm = pcm_checker.PcmChecker(oracle, mb_w, mb_h, slots)
+            self.wp = self.pcm.wp
+            self.store, self.s_slot = self.pcm.store, self.pcm.s_slot
+        else:
+            assert residual is not None and inter is not None and store is not None, "without an oracle every source must be given"
+        if store is not None:
+            self.store = store
+        self.residual = self if residual is None else residual
+        self.inter = self._oracle_inter if inter is None else inter
         self.dc_log = []
 
     # ---- the residual: arithmetic by the oracle's entry points, layout by include/p264hip.h ----
@@ -307,7 +322,7 @@ class IntraChecker:
             Y[y0:y0 + 16, x0:x0 + 16] = pred16x16(mode, left, top, corner)
             if quirk and mode == 2:
                 self.dc_log.append((m, "i16", t, dc_value(left, top, 5), dc_value(left, None, 5)))
-            self._luma16x16_residual(pic, r, Y, x0, y0)
+            self.residual._luma16x16_residual(pic, r, Y, x0, y0)
         else:
             assert t == N.MB_I4x4, t
             for i in range(16):
@@ -318,7 +333,7 @@ class IntraChecker:
                 corner = int(Y[y - 1, x - 1]) if bc else None
                 Y[y:y + 4, x:x + 4] = pred4x4(int(pic.i4modes[m * 16 + i]), left, top8, corner)
                 if int(r["coef_mask"]) >> i & 1:
-                    self._luma4x4_residual(pic, r, Y, x, y, i)
+                    self.residual._luma4x4_residual(pic, r, Y, x, y, i)
         cx, cy = x0 // 2, y0 // 2
         cmode = (int(r["intra_modes"]) >> 4) & 3
         for ch in (1, 2):
@@ -330,35 +345,42 @@ class IntraChecker:
             P[cy:cy + 8, cx:cx + 8] = o
             if quirk and cmode == 0:
                 self.dc_log.append((m, "cb" if ch == 1 else "cr", t, int(o[0, 0]), dc_value(left[:4], None, 3)))
-        self._chroma_residual(pic, r, F, cx, cy)
+        self.residual._chroma_residual(pic, r, F, cx, cy)
 
-    def nodeblock(self, pic):
-        """steps 1 and 2: the picture before the loop filter, in its frame of the store"""
+    def _oracle_inter(self, pic):
+        """the samples of the inter macroblocks: a copy of the picture in which every intra macroblock is an inter macroblock with
+        vector 0 and no residual, through oracle_reconstruct_nodeblock"""
         d = pic.desc
         rec = pic.mb_records()
         n = d.mb_w * d.mb_h
         intra = rec["mb_type"] <= N.MB_IPCM
+        flat = pcm_checker._Copy(pic)
+        if d.explicit_wp:
+            self.wp.predict(pic)                           # the weighted predictions of the inter macroblocks into S ...
+            flat.ref_idx[:] = 0                            # ... from where every macroblock of the copy takes them
+            flat.mv[:] = 0
+            flat.desc.ref_slot[0] = self.s_slot
+            flat.desc.weighted_bipred = 0
+            flat.desc.explicit_wp = 0
+        else:
+            flat.ref_idx[np.repeat(intra, 4)] = 0
+            flat.mv[np.repeat(intra, 32)] = 0
+        l1 = np.ones(n, bool) if d.explicit_wp else intra
+        flat.ref_idx_l1[np.repeat(l1, 4)] = -1
+        flat.mv_l1[np.repeat(l1, 32)] = 0
+        flat.rec["mb_type"][intra] = N.MB_B if d.slice_type == N.SLICE_B else N.MB_P_L0
+        flat.rec["coef_mask"][intra] = 0
+        flat.rec["cbp"][intra] = 0
+        self.oracle.oracle_reconstruct_nodeblock(C.byref(flat.desc), self.store.ptrs)
+
+    def nodeblock(self, pic):
+        """steps 1 and 2: the picture before the loop filter, in its frame of the store"""
+        d = pic.desc
+        intra = pic.mb_records()["mb_type"] <= N.MB_IPCM
         if d.slice_type == N.SLICE_I:
             assert intra.all(), "an I picture with inter macroblocks"
         else:
-            flat = pcm_checker._Copy(pic)
-            if d.explicit_wp:
-                self.wp.predict(pic)                           # the weighted predictions of the inter macroblocks into S ...
-                flat.ref_idx[:] = 0                            # ... from where every macroblock of the copy takes them
-                flat.mv[:] = 0
-                flat.desc.ref_slot[0] = self.s_slot
-                flat.desc.weighted_bipred = 0
-                flat.desc.explicit_wp = 0
-            else:
-                flat.ref_idx[np.repeat(intra, 4)] = 0
-                flat.mv[np.repeat(intra, 32)] = 0
-            l1 = np.ones(n, bool) if d.explicit_wp else intra
-            flat.ref_idx_l1[np.repeat(l1, 4)] = -1
-            flat.mv_l1[np.repeat(l1, 32)] = 0
-            flat.rec["mb_type"][intra] = N.MB_B if d.slice_type == N.SLICE_B else N.MB_P_L0
-            flat.rec["coef_mask"][intra] = 0
-            flat.rec["cbp"][intra] = 0
-            self.oracle.oracle_reconstruct_nodeblock(C.byref(flat.desc), self.store.ptrs)
+            self.inter(pic)
         F = self.store[d.dst_slot]
         for m in np.flatnonzero(intra):
             self._intra_mb(pic, int(m), F)
