@@ -70,6 +70,21 @@ enum {
 #define P264_IPCM_COEF_MASK 0x00000fffu
 #define P264_IPCM_BLOCKS    12
 
+/* transform_size_8x8_flag (High profile, H.264 7.3.5 / 8.5.13): bit 2 of intra_modes - free on every record, inter records
+ * leave the rest of the byte 0 - says that the macroblock's luma residual is coded as 8x8 blocks.  Legal on INTER records only
+ * (mb_type >= P264_MB_P_L0), in pictures whose descriptor says transform_8x8 != 0.  On a flagged record
+ *   bits 0-15 of coef_mask come in nibbles: nibble k (bits 4k .. 4k+3) is 0xF where luma 8x8 block k (the quadrants in raster
+ *   order) has a non-zero level, else 0x0;
+ *   a coded 8x8 block occupies FOUR consecutive 16-level entries of the packed stream: its 64 levels in the 8x8 frame zig-zag
+ *   order (entry j holds scan positions 16j .. 16j+15).
+ * The range rule (coef_index + popcount(mask) <= n_coef_blocks), the compact format's int8 / int16 choice per entry and the loop
+ * filter's "the block that holds the sample has coefficients" (8.7.2.1: the 8x8 block, for such a macroblock) read the mask as
+ * they read any other.  Chroma (bits 16-25, its entries behind the luma ones) is as on every record; the levels are scaled with
+ * flat scaling lists.  The loop filter leaves the macroblock's inner luma edges 1 and 3 alone (8.7: no transform edges).  Every
+ * road into an input slot (the list at P264_IPCM_COEF_MASK) rejects a flagged record that is not inter, one whose luma nibbles are
+ * neither 0x0 nor 0xF, and one in a picture whose descriptor says 0. */
+#define P264_MB_T8X8 0x04
+
 /* One per macroblock, 16 bytes.  Everything is as parsed (before dequantisation). */
 typedef struct p264hip_mb {
     uint8_t  mb_type;      /* P264_MB_* */
@@ -155,6 +170,9 @@ typedef struct p264hip_picture {
     int32_t             explicit_wp;
     int32_t             wp_log2_denom[2];                                      /* luma, chroma */
     int16_t             wp[2][P264HIP_MAX_REFS][3][2];                         /* [list][ref_idx][Y, Cb, Cr][weight, offset] */
+    /* ---- the 8x8 transform (P264_MB_T8X8 above).  != 0: inter records of the picture may carry the flag, and a batch that holds
+     * the picture launches the kernel that adds their luma residual (k_t8x8, between motion compensation and intra prediction) */
+    int32_t             transform_8x8;
 } p264hip_picture_t;
 
 typedef struct p264hip_ctx p264hip_ctx;
@@ -206,9 +224,13 @@ typedef struct p264hip_input_layout {
 int  p264hip_input_layout(const p264hip_picture_t *desc, p264hip_input_layout_t *out);
 /* 0, or P264HIP_EINVAL where an explicit_wp picture's denominators, weights or offsets are out of range (every upload path checks it) */
 int  p264hip_wp_check(const p264hip_picture_t *desc);
-/* the index of the first of n_mb records whose coefficient blocks do not lie inside coefs[n_coef_blocks], or which is an I_PCM
- * record without its twelve-block mask; -1 where there is none (every upload path checks it, device producers' blocks on the device) */
+/* the index of the first of n_mb records whose coefficient blocks do not lie inside coefs[n_coef_blocks], which is an I_PCM
+ * record without its twelve-block mask, or which carries P264_MB_T8X8 without being inter or with a luma nibble that is neither
+ * 0x0 nor 0xF; -1 where there is none (every upload path checks it, device producers' blocks on the device) */
 int64_t p264hip_records_check(const p264hip_mb_t *mb, size_t n_mb, uint32_t n_coef_blocks);
+/* the same for the records of a picture with this descriptor: also the first record that carries P264_MB_T8X8 where
+ * desc->transform_8x8 is 0 (what the roads that check on the host run) */
+int64_t p264hip_records_check_pic(const p264hip_picture_t *desc, const p264hip_mb_t *mb);
 /* host side, no device involved: the picture's arrays copied into `dst` (cap >= layout.bytes) in that layout; the
  * macroblock records are checked as p264hip_upload checks them (coefficient ranges inside coefs[]).  Returns the bytes used
  * or a negative P264HIP_E* code. */
@@ -316,7 +338,8 @@ typedef struct p264hip_launch_info {
     int32_t edge_info_fused;       /* edge-info workgroups per picture inside the k_intra_sparse launch (0: own launch k_deblock_bs) */
     int32_t deblock_pics_per_wg, deblock_rb_log2, deblock_waves, deblock_wgs;
     int32_t deblock_odd_single;    /* 1: odd pictures per workgroup - pairs in bands of 4 rows, the last picture alone in bands of 8 */
-    int32_t reserved[6];
+    int32_t t8x8_wgs;              /* k_t8x8: workgroups of the launch (0: no picture of the batch has transform_8x8, no launch) */
+    int32_t reserved[5];
 } p264hip_launch_info_t;
 int  p264hip_last_launch(p264hip_ctx *ctx, p264hip_launch_info_t *out);
 

@@ -20,6 +20,7 @@ COEF_LUMA_DC = 1 << 24
 COEF_CHROMA_DC = 1 << 25
 AVAIL_LEFT, AVAIL_TOP, AVAIL_TOPRIGHT, AVAIL_TOPLEFT = 1, 2, 4, 8
 EDGE_LEFT, EDGE_TOP, EDGE_INNER = 1, 2, 4
+MB_T8X8 = 0x04          # bit of MbInfo.intra_modes: the inter macroblock's luma residual is coded as 8x8 blocks
 
 
 class MbInfo(C.Structure):
@@ -44,6 +45,7 @@ class Picture(C.Structure):
         ("mv_l1", C.POINTER(C.c_int16)), ("ref_idx_l1", C.POINTER(C.c_int8)), ("n_ref_l1", C.c_int32), ("weighted_bipred", C.c_int32),
         ("ref_slot_l1", C.c_int32 * MAX_REFS), ("bipred_weight", C.c_int16 * (MAX_REFS * MAX_REFS)),
         ("explicit_wp", C.c_int32), ("wp_log2_denom", C.c_int32 * 2), ("wp", C.c_int16 * (2 * MAX_REFS * 3 * 2)),   # wp: [list][ref_idx][Y, Cb, Cr][weight, offset], flat
+        ("transform_8x8", C.c_int32),
     ]
 
 
@@ -53,7 +55,7 @@ assert C.sizeof(MbInfo) == 16
 class LaunchInfo(C.Structure):
     """p264hip_launch_info_t"""
     _fields_ = [(n, C.c_int32) for n in ("pictures", "compute_units", "mc_wgs_per_picture", "intra_waves", "edge_info_fused",
-                                         "deblock_pics_per_wg", "deblock_rb_log2", "deblock_waves", "deblock_wgs", "deblock_odd_single")] + [("reserved", C.c_int32 * 6)]
+                                         "deblock_pics_per_wg", "deblock_rb_log2", "deblock_waves", "deblock_wgs", "deblock_odd_single", "t8x8_wgs")] + [("reserved", C.c_int32 * 5)]
 
 
 BUILD_TIMING = 1
@@ -158,6 +160,10 @@ def load(path=None):
         lib.p264hip_pack_input.argtypes = [C.POINTER(Picture), C.c_void_p, C.c_size_t]
         lib.p264hip_unpack_input.argtypes = [C.POINTER(Picture), C.c_void_p, C.c_size_t, C.POINTER(Picture)]
         lib.p264hip_upload_packed.argtypes = [C.c_void_p, C.c_int, C.POINTER(Picture), C.c_void_p, C.c_size_t]
+        lib.p264hip_records_check.restype = C.c_int64
+        lib.p264hip_records_check.argtypes = [C.POINTER(MbInfo), C.c_size_t, C.c_uint32]
+        lib.p264hip_records_check_pic.restype = C.c_int64
+        lib.p264hip_records_check_pic.argtypes = [C.POINTER(Picture), C.POINTER(MbInfo)]
         lib.p264hip_input_reserve.argtypes = [C.c_void_p, C.c_int, C.POINTER(Picture), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         lib.p264hip_input_commit.argtypes = [C.c_void_p, C.c_int]
         lib.p264hip_frame_planar_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]

@@ -100,7 +100,7 @@ __device__ __forceinline__ void pic_of_init(PicOf &T, const PicDev *pd)
 // its vectors, its reference indices.  A caller that walks a column downwards has them in registers from the row before
 // (the edge-info role of k_intra_sparse, round 6); everybody else lets edge_info_of load them (top = nullptr).
 struct EdgeTop { uint32_t rec_x, rec_y, refs; uint4 mv; };
-template <bool TWO_LISTS>
+template <bool TWO_LISTS, bool T8X8 = true>
 __device__ __forceinline__ uint4 edge_info_of(const PicDev *pd, const Geom &g, int mbi, int mbx, int mby, const uint4 rec,
                                               const uint4 m0, const uint4 m1, const uint4 m2, const uint4 m3, const uint32_t refs, const PicOf *pic_tab,
                                               const EdgeTop *top = nullptr)
@@ -223,6 +223,16 @@ __device__ __forceinline__ uint4 edge_info_of(const PicDev *pd, const Geom &g, i
                 if (!enabled) bS = 0;
                 word[dir] |= (uint32_t)bS << (2 * (4 * e + i));
             }
+
+    // a macroblock with the 8x8 transform: its inner luma edges 1 and 3 are no transform edges (H.264 8.7), strength 0 in both
+    // directions (chroma reads the strengths of edges 0 and 2)
+    // (T8X8 = false, the edge-info role of the 64-register k_intra_sparse build: the mask cost it four spilled registers whichever
+    // way the flag was carried - bits 8-15 of qp_word included -, so batches with such pictures take k_deblock_bs: p264hip.hip)
+    if (T8X8) {
+        // (the words as they stand first: the mask is two instructions here, not a select folded into each of the thirty-two segments above)
+        asm volatile("" : "+v"(word[0]), "+v"(word[1]));
+        if ((rec.x >> 24) & P264_MB_T8X8) { word[0] &= 0x00ff00ffu; word[1] &= 0x00ff00ffu; }
+    }
 
     // ---- averaged QPs per edge class (deblock_edge, core/frame.c:472-488,593-601) ----
     const int cqo = pd->chroma_qp_offset;

@@ -748,7 +748,7 @@ void k_intra_sparse(const PicDev *__restrict__ pics, Geom g, int *status, const 
                 const uint4 c0 = carry[0];
                 const EdgeTop top = { c0.x, c0.y, c0.z, carry[1] };
                 carry[0] = make_uint4(rec.x, rec.y, refs, 0u); carry[1] = m3;
-                const uint4 ei = edge_info_of<false>(pd, g, mbi, col, y, rec, m0, m1, m2, m3, refs, nullptr, &top);
+                const uint4 ei = edge_info_of<false, false>(pd, g, mbi, col, y, rec, m0, m1, m2, m3, refs, nullptr, &top);
                 // (the store's offset from the thread number once more: kept alive across edge_info_of it was the build's one spill)
                 int tid2 = (int)threadIdx.x;
                 asm volatile("" : "+v"(tid2));
@@ -768,7 +768,7 @@ void k_intra_sparse(const PicDev *__restrict__ pics, Geom g, int *status, const 
             const int *mvs = pd->mv;
             const uint4 m0 = gload4(ubase(mvs, (uint32_t)mbi * 64u)), m1 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 16u)), m2 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 32u)), m3 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 48u));
             const uint32_t refs = gload1(ubase(pd->ref_idx, (uint32_t)mbi * 4u));
-            const uint4 ei = edge_info_of<false>(pd, g, mbi, mbx, mby, rec, m0, m1, m2, m3, refs, nullptr);
+            const uint4 ei = edge_info_of<false, false>(pd, g, mbi, mbx, mby, rec, m0, m1, m2, m3, refs, nullptr);
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{ ei.x, ei.y, ei.z, ei.w }, info_rs, (int)((uint32_t)mbi_it * 16u), 0, 0);
         }
         return;

@@ -185,7 +185,9 @@ __device__ __forceinline__ McMb mc_classify(const PicDev *pd, const Geom &g, con
     int mby = (int)__umulhi((unsigned)mbi, inv_mbw);
     if (mbi - mby * g.mb_w >= g.mb_w) mby++;
     const int mbx = mbi - mby * g.mb_w, band = mby >> band_log2;
-    const unsigned mask = rec.y, cc = mask & (0x00ff0000u | P264_COEF_CHROMA_DC);   // any chroma level present
+    const unsigned cc = rec.y & (0x00ff0000u | P264_COEF_CHROMA_DC);   // any chroma level present
+    // (a macroblock with P264_MB_T8X8: its luma items are filed as "no residual" - k_t8x8 adds it behind this stage, kernel_t8x8.h)
+    const unsigned mask = ((rec.x >> 24) & P264_MB_T8X8) ? (rec.y & ~0xffffu) : rec.y;
     if (WP && pd->explicit_wp) {
         // explicit weighted prediction (wave-uniform: a picture per workgroup; compiled into the k_mc_sort*_wp instances only): every inter macroblock goes to the generic two-list
         // class, all four quadrants, first pass - its lanes look up their lists, indices and weights themselves (mc_luma_body /
@@ -338,6 +340,8 @@ __device__ __forceinline__ void mc_scatter(const McSortCtx &c, const McMb &k, in
     // core/macroblock.c:525-583; 32 = plain average) ride in the entry
     const uint4 rec = gload4(c.pd->mb + mbi);              // (second look at the record: out of the cache)
     const uint32_t ez = (rec.y & 0x03ffffffu) | ((rec.x >> 8) & 63u) << 26;
+    // (luma entries of a P264_MB_T8X8 macroblock: no coded block; the chroma entries keep the bits - they count them to find their levels)
+    const uint32_t ezy = ((rec.x >> 24) & P264_MB_T8X8) ? (ez & ~0xffffu) : ez;
     uint32_t ew[4];
     const uint32_t refs = gload1(c.pd->ref_idx + mbi * 4);
 #pragma unroll
@@ -350,15 +354,17 @@ __device__ __forceinline__ void mc_scatter(const McSortCtx &c, const McMb &k, in
         ew[q] = (rec.z & ((1u << MCE_W_SHIFT) - 1u)) | (uint32_t)w << MCE_W_SHIFT;
     }
     if (k.info & MCMB_WHOLE) {
-        const uint4 e = make_uint4(mcmb_entry(k, mbx, mby, 0, 1), k.vec[0], ((k.info >> 28) & 1u) ? (ez & 0xfc000000u) : ez, ew[0]);
-        gstore4(c.out + c.l_ym + 4u * atomicAdd(&c.pos[c.b_ym + (k.key[0] & 0xffffu)], 1u), e);
+        const bool z = (k.info >> 28) & 1u;
+        const uint4 e = make_uint4(mcmb_entry(k, mbx, mby, 0, 1), k.vec[0], z ? (ez & 0xfc000000u) : ez, ew[0]);
+        gstore4(c.out + c.l_ym + 4u * atomicAdd(&c.pos[c.b_ym + (k.key[0] & 0xffffu)], 1u), make_uint4(e.x, e.y, z ? e.z : ezy, e.w));
         gstore4(c.out + c.l_cm + 4u * atomicAdd(&c.pos[c.b_cm + (k.key[0] >> 16)], 1u), e);
     } else {
         const uint32_t cq = atomicAdd(&c.pos[c.b_cq + (k.key[0] >> 16)], 4u);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            const uint4 e = make_uint4(mcmb_entry(k, mbx, mby, q, 1), k.vec[q], ((k.info >> (28 + q)) & 1u) ? (ez & 0xfc000000u) : ez, ew[q]);
-            if (mcmb_luma_quad(k, q, 1)) gstore4(c.out + c.l_yq + 4u * atomicAdd(&c.pos[c.b_yq + (k.key[q] & 0xffffu)], 1u), e);
+            const bool z = (k.info >> (28 + q)) & 1u;
+            const uint4 e = make_uint4(mcmb_entry(k, mbx, mby, q, 1), k.vec[q], z ? (ez & 0xfc000000u) : ez, ew[q]);
+            if (mcmb_luma_quad(k, q, 1)) gstore4(c.out + c.l_yq + 4u * atomicAdd(&c.pos[c.b_yq + (k.key[q] & 0xffffu)], 1u), make_uint4(e.x, e.y, z ? e.z : ezy, e.w));
             gstore4(c.out + c.l_cq + 4u * (cq + (uint32_t)q), e);
         }
     }

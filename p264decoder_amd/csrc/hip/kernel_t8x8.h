@@ -1,0 +1,119 @@
+// kernel_t8x8.h - the luma residual of inter macroblocks coded with the 8x8 transform (transform_size_8x8_flag, High profile).
+//
+// No counterpart in the reference (Baseline / Main tools only).  H.264 8.5.6 (inverse 8x8 scan), 8.5.9 / 8.5.13 (scaling with flat
+// scaling lists, the 8x8 inverse transform) and the picture construction of 8.5.14 for the macroblocks whose record carries
+// P264_MB_T8X8 (include/p264hip.h).  k_mc_sort files the luma of such a macroblock as "no residual", so k_mc / k_mc_second leave
+// its plain prediction in the frame store; this kernel, launched behind them and in front of the intra stage, adds the residual of
+// every coded 8x8 block in place.  Chroma of the macroblock went the usual way.
+//
+// Shape: one wavefront per TWO macroblocks, 8 lanes per 8x8 block, lane r of a block = its row r (levels 8r .. 8r+7 in scan
+// order, then row r of the horizontal pass, column r of the vertical pass, row r of the samples).  The three changes of
+// ownership go through LDS; nothing leaves the wavefront, so fences do (device_common.h: wave_lds_fence).  All arithmetic is
+// 32-bit: a conforming stream keeps every value inside 16 bits, anything else still gives a defined result here.
+#pragma once
+#include "device_common.h"
+
+#define T8_THREADS    256
+#define T8_MBS_PER_WG (T8_THREADS / 32)
+#define T8_BLK_STRIDE 72             // dwords between the 8x8 tiles of a wavefront in LDS: 64 + 8, so that the eight blocks' column reads meet no bank twice
+
+// 8x8 zig-zag frame scan (H.264 8.5.6): scan index -> x + 8 * y
+__device__ __constant__ __attribute__((aligned(8))) const uint8_t c_scan8x8[64] = {
+     0,  1,  8, 16,  9,  2,  3, 10, 17, 24, 32, 25, 18, 11,  4,  5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13,  6,  7, 14, 21, 28,
+    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63 };
+// normAdjust8x8 (H.264 8.5.9, equation 8-316 ff.): v by qP % 6 for the six position classes, one byte per class
+#define T8_V6(a, b, c, d, e, f) ((uint64_t)(a) | (uint64_t)(b) << 8 | (uint64_t)(c) << 16 | (uint64_t)(d) << 24 | (uint64_t)(e) << 32 | (uint64_t)(f) << 40)
+__device__ __constant__ const uint64_t c_t8_v[6] = {
+    T8_V6(20, 18, 32, 19, 25, 24), T8_V6(22, 19, 35, 21, 28, 26), T8_V6(26, 23, 42, 24, 33, 31),
+    T8_V6(28, 25, 45, 26, 35, 33), T8_V6(32, 28, 51, 30, 40, 38), T8_V6(36, 32, 58, 34, 46, 43) };
+// position class by (y & 3) * 4 + (x & 3): 0 3 4 3 / 3 1 5 1 / 4 5 2 5 / 3 1 5 1, one nibble each
+#define T8_CLASSES 0x1513525415133430ull
+
+// one level at raster position p of the block, scaled (flat scaling lists: weight 16)
+__device__ __forceinline__ int t8_scale(int c, int p, uint64_t vrow, int per)
+{
+    const int cls = (int)((T8_CLASSES >> (4 * (((p >> 3) & 3) * 4 + (p & 3)))) & 15u);
+    const int t = c * 16 * (int)((vrow >> (8 * cls)) & 255u);
+    return per >= 6 ? (int)((unsigned)t << (per - 6)) : (t + (1 << (5 - per))) >> (6 - per);
+}
+
+// the one-dimensional stage of 8.5.13, in place
+__device__ __forceinline__ void t8_idct1d(int (&d)[8])
+{
+    const int a0 = d[0] + d[4], a4 = d[0] - d[4], a2 = (d[2] >> 1) - d[6], a6 = d[2] + (d[6] >> 1);
+    const int a1 = -d[3] + d[5] - d[7] - (d[7] >> 1), a3 = d[1] + d[7] - d[3] - (d[3] >> 1);
+    const int a5 = -d[1] + d[7] + d[5] + (d[5] >> 1), a7 = d[3] + d[5] + d[1] + (d[1] >> 1);
+    const int b0 = a0 + a6, b2 = a4 + a2, b4 = a4 - a2, b6 = a0 - a6;
+    const int b1 = a1 + (a7 >> 2), b3 = a3 + (a5 >> 2), b5 = (a3 >> 2) - a5, b7 = a7 - (a1 >> 2);
+    d[0] = b0 + b7; d[1] = b2 + b5; d[2] = b4 + b3; d[3] = b6 + b1;
+    d[4] = b6 - b1; d[5] = b4 - b3; d[6] = b2 - b5; d[7] = b0 - b7;
+}
+
+// grid: (macroblocks of a picture / T8_MBS_PER_WG, pictures of the batch)
+__global__ __launch_bounds__(T8_THREADS)
+void k_t8x8(const PicDev *__restrict__ pics, Geom g)
+{
+    __shared__ int tiles[(T8_THREADS / 64) * 8 * T8_BLK_STRIDE];
+    const PicDev *pd = pics + blockIdx.y;
+    if (pd->slice_type == P264_SLICE_I) return;            // (no inter record, and only those may carry the flag)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int mbi = ((int)blockIdx.x * (T8_THREADS / 64) + wave) * 2 + (lane >> 5);
+    const int k = (lane >> 3) & 3, r = lane & 7;           // 8x8 block of the macroblock (quadrants in raster order), row / column of the block
+    uint4 rec = make_uint4(0, 0, 0, 0);
+    if (mbi < g.n_mb) rec = gload4(pd->mb + mbi);
+    const unsigned mask = rec.y;
+    const bool coded = ((rec.x >> 24) & P264_MB_T8X8) && !P264_MB_IS_INTRA(rec.x & 255u) && ((mask >> (4 * k)) & 1u);
+    if (!__ballot(coded)) return;                          // unflagged macroblocks leave at once
+    int *tile = tiles + (wave * 8 + (lane >> 3)) * T8_BLK_STRIDE;
+    // ---- levels 8r .. 8r+7 of the block's scan, scaled, to their places in the tile
+    if (coded) {
+        const int qp = (int)((rec.x >> 8) & 63u), per = (qp * 43) >> 8;
+        const uint64_t vrow = c_t8_v[qp - per * 6];
+        const int16_t *lv = pd->coefs + ((size_t)rec.z + coef_slot(mask, 4 * k)) * 16 + r * 8;     // four entries per coded block: 64 levels
+        const uint4 l = gload4(lv);
+        const uint2 sc = *(const uint2 *)(c_scan8x8 + r * 8);
+        const uint32_t lw[4] = { l.x, l.y, l.z, l.w };
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int c = (i & 1) ? (int)lw[i >> 1] >> 16 : (int)(int16_t)(lw[i >> 1] & 0xffffu);
+            const int p = (int)(((i < 4 ? sc.x : sc.y) >> (8 * (i & 3))) & 63u);
+            tile[p] = t8_scale(c, p, vrow, per);
+        }
+    }
+    wave_lds_fence();
+    int d[8];
+    // ---- rows first (the >> 1 and >> 2 of the stage make the order observable): row r, back in place
+    if (coded) {
+        const int4 lo = *(const int4 *)(tile + r * 8), hi = *(const int4 *)(tile + r * 8 + 4);
+        d[0] = lo.x; d[1] = lo.y; d[2] = lo.z; d[3] = lo.w; d[4] = hi.x; d[5] = hi.y; d[6] = hi.z; d[7] = hi.w;
+        t8_idct1d(d);
+        *(int4 *)(tile + r * 8) = make_int4(d[0], d[1], d[2], d[3]);
+        *(int4 *)(tile + r * 8 + 4) = make_int4(d[4], d[5], d[6], d[7]);
+    }
+    wave_lds_fence();
+    // ---- column r, rounded, back in place (a lane reads and writes its own column only)
+    if (coded) {
+#pragma unroll
+        for (int y = 0; y < 8; y++) d[y] = tile[y * 8 + r];
+        t8_idct1d(d);
+#pragma unroll
+        for (int y = 0; y < 8; y++) tile[y * 8 + r] = (d[y] + 32) >> 6;
+    }
+    wave_lds_fence();
+    // ---- row r of the block: 8 samples of the prediction the inter launches left, plus the residual, clipped
+    if (coded) {
+        int mby = mbi / g.mb_w;
+        const int mbx = mbi - mby * g.mb_w;
+        uint8_t *px = pd->dst + mb_luma_off(g, mbx, mby) + (uint32_t)(((k >> 1) * 8 + r) * 16 + (k & 1) * 8);
+        const uint2 s = gload2(px);
+        const int4 lo = *(const int4 *)(tile + r * 8), hi = *(const int4 *)(tile + r * 8 + 4);
+        const int res[8] = { lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w };
+        uint32_t o[2] = { 0, 0 };
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int v = clip255((int)(((i < 4 ? s.x : s.y) >> (8 * (i & 3))) & 255u) + res[i]);
+            o[i >> 2] |= (uint32_t)v << (8 * (i & 3));
+        }
+        gstore2(px, make_uint2(o[0], o[1]));
+    }
+}

@@ -18,6 +18,7 @@
 #include "kernel_deblock.h"
 #include "kernel_mc.h"
 #include "kernel_intra.h"
+#include "kernel_t8x8.h"
 #include "kernel_expand.h"
 
 static thread_local char g_err[512] = "";
@@ -89,13 +90,15 @@ __global__ void k_tile_convert(uint8_t *frame, uint8_t *planar, Geom g, int to_p
 // The device twin of p264hip_records_check (csrc/host/input_layout.c), for pictures that arrive in device memory
 // (p264hip_input_reserve / _commit): every macroblock's packed blocks must lie inside coefs[] - the kernels index the coefficient
 // stream without further checks (include/p264hip.h).  One flag per input slot.
-__global__ void k_check_records(const p264hip_mb_t *mb, int n_mb, uint32_t n_coef_blocks, int *bad)
+__global__ void k_check_records(const p264hip_mb_t *mb, int n_mb, uint32_t n_coef_blocks, int t8x8, int *bad)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_mb) return;
     const uint4 r = gload4(mb + i);
     if (r.y && (uint64_t)r.z + (uint64_t)__popc(r.y & 0x3ffffffu) > (uint64_t)n_coef_blocks) atomicOr(bad, 1);
     if ((r.x & 255u) == P264_MB_IPCM && r.y != P264_IPCM_COEF_MASK) atomicOr(bad, 1);       // (the intra kernels read twelve blocks of samples)
+    // P264_MB_T8X8: in pictures that say so, inter, whole luma nibbles (k_t8x8 reads four entries per set nibble)
+    if ((r.x >> 24) & P264_MB_T8X8) { if (!t8x8 || P264_MB_IS_INTRA(r.x & 255u) || (r.y & 0xffffu) != (r.y & 0x1111u) * 15u) atomicOr(bad, 1); }
 }
 
 struct p264hip_ctx {
@@ -260,12 +263,15 @@ static int check_pic(p264hip_ctx *c, const p264hip_picture_t *p, bool arrays)
                     p->wp_log2_denom[0], p->wp_log2_denom[1]);
     if (!arrays) return 0;
     if (!p->mb || !p->mv || !p->ref_idx || !p->i4modes || (p->n_coef_blocks && !p->coefs)) return fail(P264HIP_EINVAL, "null picture array");
-    const int bad = (int)p264hip_records_check(p->mb, (size_t)c->g.n_mb, p->n_coef_blocks);
+    const int bad = (int)p264hip_records_check_pic(p, p->mb);
     if (bad < 0) return 0;
-    const p264hip_mb_t &m = p->mb[bad];                       // which half of the rule the record breaks (the range first)
+    const p264hip_mb_t &m = p->mb[bad];                       // which part of the rule the record breaks (the range first)
     const int blocks = __builtin_popcount(m.coef_mask & 0x3ffffffu);
     if (m.coef_mask && (uint64_t)m.coef_index + (uint64_t)blocks > p->n_coef_blocks)
         return fail(P264HIP_EINVAL, "macroblock %d: coefficient blocks [%u, +%d) outside coefs[%u]", bad, m.coef_index, blocks, p->n_coef_blocks);
+    if (m.intra_modes & P264_MB_T8X8)
+        return fail(P264HIP_EINVAL, "macroblock %d: P264_MB_T8X8 on a record of type %d with coef_mask 0x%x in a picture with transform_8x8 = %d (inter records with whole luma nibbles, in pictures that say so)",
+                    bad, m.mb_type, m.coef_mask, p->transform_8x8);
     return fail(P264HIP_EINVAL, "macroblock %d: I_PCM with coef_mask 0x%x (its twelve sample blocks are 0x%x)", bad, m.coef_mask, P264_IPCM_COEF_MASK);
 }
 
@@ -479,7 +485,7 @@ extern "C" int p264hip_input_commit(p264hip_ctx *c, int slot)
     // an out-of-bounds read.  The verdict is read once per batch, by p264hip_reconstruct.
     HIPCHK(hipMemsetAsync(c->d_slot_bad + slot, 0, sizeof(int), c->stream));
     const int n_mb = c->g.n_mb;
-    hipLaunchKernelGGL(k_check_records, dim3((n_mb + 255) / 256), dim3(256), 0, c->stream, (const p264hip_mb_t *)s.dev, n_mb, s.meta.n_coef_blocks, c->d_slot_bad + slot);
+    hipLaunchKernelGGL(k_check_records, dim3((n_mb + 255) / 256), dim3(256), 0, c->stream, (const p264hip_mb_t *)s.dev, n_mb, s.meta.n_coef_blocks, s.meta.transform_8x8, c->d_slot_bad + slot);
     HIPCHK(hipGetLastError());
     slot_exit(c, slot, s.meta, UNCHECKED);
     return P264HIP_OK;
@@ -673,7 +679,7 @@ static int settle_unchecked(p264hip_ctx *c, const int *pic_ids, int n)
     for (int i = 0; i < n; i++) {
         const int id = pic_ids[i];
         if (id < 0 || id >= c->max_pictures || c->pics[(size_t)id].state != UNCHECKED) continue;
-        if (bad[(size_t)id]) { c->pics[(size_t)id].state = EMPTY; return fail(P264HIP_EINVAL, "picture slot %d: a macroblock's coefficient blocks lie outside coefs[] (the block a device producer committed is inconsistent)", id); }
+        if (bad[(size_t)id]) { c->pics[(size_t)id].state = EMPTY; return fail(P264HIP_EINVAL, "picture slot %d: a macroblock's coefficient blocks lie outside coefs[], or a record is an I_PCM or 8x8-transform record of the wrong form (the block a device producer committed is inconsistent)", id); }
         c->pics[(size_t)id].state = READY;
     }
     return 0;
@@ -720,8 +726,9 @@ static PicDev picdev_of(p264hip_ctx *c, const PicSlot &s, int st)
 }
 
 // What the batch holds - the kernel instances and launch shapes follow from it: any picture with inter macroblocks / any B picture /
-// any I picture / any explicit weights / any unweighted P picture whose list 0 holds one frame at several indices
-struct BatchKinds { bool p = false, b = false, i = false, wp = false, dup = false; };
+// any I picture / any explicit weights / any unweighted P picture whose list 0 holds one frame at several indices / any picture
+// whose inter macroblocks may use the 8x8 transform
+struct BatchKinds { bool p = false, b = false, i = false, wp = false, dup = false, t8 = false; };
 
 // the batch's streams and slots checked (nothing is queued yet), one PicDev per picture in hb
 static int batch_fill(p264hip_ctx *c, const int *pic_ids, const int *streams, int n, PicDev *hb, BatchKinds *kinds)
@@ -744,6 +751,7 @@ static int batch_fill(p264hip_ctx *c, const int *pic_ids, const int *streams, in
         k.i |= s.meta.slice_type == P264_SLICE_I;
         k.wp |= s.meta.explicit_wp != 0;
         k.dup |= hb[i].dup_refs != 0;
+        k.t8 |= s.meta.transform_8x8 != 0 && s.meta.slice_type != P264_SLICE_I;
     }
     *kinds = k;
     return 0;
@@ -777,10 +785,11 @@ static int intra_waves(const p264hip_ctx *c, int n)
 }
 
 // edge-info workgroups per picture inside the k_intra_sparse launch (P pictures only, by index: no B picture, no explicit weights,
-// no frame twice in a list), 0: the pass takes its own launch (k_deblock_bs)
+// no frame twice in a list, no 8x8 transform - the fused role is compiled without its edge mask), 0: the pass takes its own launch
+// (k_deblock_bs)
 static int edge_info_fused(const p264hip_ctx *c, const BatchKinds &k)
 {
-    if (k.i || k.b || k.wp || k.dup || c->tune_bs_fused == 0) return 0;
+    if (k.i || k.b || k.wp || k.dup || k.t8 || c->tune_bs_fused == 0) return 0;
     return c->tune_bs_fused > 0 ? c->tune_bs_fused : INTRA_BS_WGS;
 }
 
@@ -846,6 +855,17 @@ static void launch_inter(p264hip_ctx *c, const PicDev *batch, int n, const Batch
                            wgs, wgs * n, (uint32_t)(((1ull << 32) - 1) / (unsigned)wgs));
 }
 
+// luma residual of the macroblocks with P264_MB_T8X8 (kernel_t8x8.h), on top of the prediction the inter launches left in the
+// frame store; in front of the intra launch, whose macroblocks predict from their inter neighbours' finished samples.  Counts
+// as inter time (timing index 0).
+static void launch_t8x8(p264hip_ctx *c, const PicDev *batch, int n)
+{
+    ScopedStamp t(c, 0);
+    const int per_pic = (c->g.n_mb + T8_MBS_PER_WG - 1) / T8_MBS_PER_WG;
+    c->last.t8x8_wgs = per_pic * n;
+    hipLaunchKernelGGL(k_t8x8, dim3((unsigned)per_pic, (unsigned)n), dim3(T8_THREADS), 0, c->stream, batch, c->g);
+}
+
 static void launch_intra(p264hip_ctx *c, const PicDev *batch, int n, const BatchKinds &k)
 {
     ScopedStamp t(c, 1);
@@ -897,6 +917,7 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     memset(&c->last, 0, sizeof c->last);
     c->last.pictures = n; c->last.compute_units = c->n_cu;
     if (k.p) launch_inter(c, c->d_batch[r], n, k);
+    if (k.t8) launch_t8x8(c, c->d_batch[r], n);
     launch_intra(c, c->d_batch[r], n, k);
     launch_deblock(c, c->d_batch[r], n, k);
     HIPCHK(hipGetLastError());

@@ -39,7 +39,7 @@ int64_t p264hip_pack_compact(const p264hip_picture_t *p, void *dst_, size_t cap)
     const size_t n = (size_t)p->mb_w * (size_t)p->mb_h;
     if (n > P264HIP_COMPACT_MAX_MB) return P264HIP_EINVAL;
     if (cap < p264hip_compact_bound(p)) return P264HIP_ENOMEM;
-    if (p264hip_records_check(p->mb, n, p->n_coef_blocks) >= 0) return P264HIP_EINVAL;      /* as p264hip_pack_input */
+    if (p264hip_records_check_pic(p, p->mb) >= 0) return P264HIP_EINVAL;                  /* as p264hip_pack_input */
     uint8_t *dst = (uint8_t *)dst_;
     p264hip_compact_hdr_t h;
     memset(&h, 0, sizeof h);
@@ -165,7 +165,7 @@ int p264hip_compact_check(const p264hip_picture_t *d, const void *compact, size_
     p264hip_compact_hdr_t h;
     memcpy(&h, b, sizeof h);
     const size_t n = (size_t)d->mb_w * (size_t)d->mb_h;
-    if (p264hip_records_check((const p264hip_mb_t *)(b + h.off_rec), n, h.n_coef_blocks) >= 0) return P264HIP_EINVAL;
+    if (p264hip_records_check_pic(d, (const p264hip_mb_t *)(b + h.off_rec)) >= 0) return P264HIP_EINVAL;      /* (the header's counts are the descriptor's) */
     for (uint32_t l = 0; l < h.n_lists; l++) {
         const uint8_t *shape = b + h.list[l].off_shape;
         uint64_t nv = 0;

@@ -42,7 +42,7 @@ int64_t p264hip_pack_input(const p264hip_picture_t *p, void *dst_, size_t cap)
     const int isB = p->slice_type == P264_SLICE_B;
     if (isB && (!p->mv_l1 || !p->ref_idx_l1)) return P264HIP_EINVAL;
     const size_t n = (size_t)p->mb_w * (size_t)p->mb_h;
-    if (p264hip_records_check(p->mb, n, p->n_coef_blocks) >= 0) return P264HIP_EINVAL;
+    if (p264hip_records_check_pic(p, p->mb) >= 0) return P264HIP_EINVAL;
     uint8_t *dst = (uint8_t *)dst_;
     memcpy(dst + L.off_mb, p->mb, n * sizeof(p264hip_mb_t));
     memcpy(dst + L.off_mv, p->mv, n * 64);
@@ -62,16 +62,30 @@ int64_t p264hip_pack_input(const p264hip_picture_t *p, void *dst_, size_t cap)
 }
 
 /* The rule every road into a slot holds the macroblock records to: a macroblock's packed blocks lie inside coefs[] (the
- * kernels index the coefficient stream without further checks), and an I_PCM record carries its twelve-block mask (the intra
- * kernels read twelve blocks of samples).  The index of the first record that breaks it, or -1.  On the device, for blocks
- * that never pass through the host: k_check_records (p264hip.hip). */
+ * kernels index the coefficient stream without further checks), an I_PCM record carries its twelve-block mask (the intra
+ * kernels read twelve blocks of samples), and a record with P264_MB_T8X8 is inter with whole luma nibbles (k_t8x8 reads four
+ * entries per set nibble; the intra kernels know no 8x8 block).  The index of the first record that breaks it, or -1.  On the
+ * device, for blocks that never pass through the host: k_check_records (p264hip.hip). */
 int64_t p264hip_records_check(const p264hip_mb_t *mb, size_t n_mb, uint32_t n_coef_blocks)
 {
     for (size_t i = 0; i < n_mb; i++) {
         const p264hip_mb_t *m = &mb[i];
         if (m->coef_mask && (uint64_t)m->coef_index + (uint64_t)__builtin_popcount(m->coef_mask & 0x3ffffffu) > n_coef_blocks) return (int64_t)i;
         if (m->mb_type == P264_MB_IPCM && m->coef_mask != P264_IPCM_COEF_MASK) return (int64_t)i;
+        if (m->intra_modes & P264_MB_T8X8) {
+            const uint32_t lo = m->coef_mask & 0x1111u;                          /* whole nibbles: every bit equals its nibble's lowest */
+            if (P264_MB_IS_INTRA(m->mb_type) || (m->coef_mask & 0xffffu) != lo * 15u) return (int64_t)i;
+        }
     }
+    return -1;
+}
+
+int64_t p264hip_records_check_pic(const p264hip_picture_t *d, const p264hip_mb_t *mb)
+{
+    const size_t n = (size_t)d->mb_w * (size_t)d->mb_h;
+    const int64_t bad = p264hip_records_check(mb, n, d->n_coef_blocks);
+    if (bad >= 0 || d->transform_8x8) return bad;
+    for (size_t i = 0; i < n; i++) if (mb[i].intra_modes & P264_MB_T8X8) return (int64_t)i;
     return -1;
 }
 

@@ -37,12 +37,15 @@ typedef struct {
     int delta_pic_order_always_zero, num_ref_frames_in_poc_cycle;
     int num_ref_frames, gaps_allowed, mb_w, mb_h, frame_mbs_only, direct_8x8_inference;
     int crop[4];
+    int high;                                        /* one of the profiles whose SPS and PPS carry the High extensions (sps_is_high) */
 } sps_t;
 
 typedef struct {
     int valid, sps_id, cabac, pic_order_present, num_slice_groups;
     int num_ref_idx[2], weighted_pred, weighted_bipred;    /* num_ref_idx: the default active length per list */
     int pic_init_qp, chroma_qp_offset, deblock_ctrl, constrained_intra, redundant_pic_cnt;
+    /* what follows while more_rbsp_data( ) (7.3.2.2), as read; honoured only by slices whose SPS is a High one (open_slice) */
+    int ext, t8x8_mode, scaling_matrix, second_chroma_qp_offset;
 } pps_t;
 
 typedef struct {
@@ -90,6 +93,7 @@ typedef struct {
     int16_t wp_tab[2][P264HIP_MAX_REFS][3][2], wp_coded[2][P264HIP_MAX_REFS][3][2];
     int weighted_bipred;
     int16_t bipred_weight[P264HIP_MAX_REFS * P264HIP_MAX_REFS];   /* implicit weights (8.4.2.3.1) */
+    int t8x8;                                 /* a slice of the picture had transform_8x8_mode_flag: its inter records may carry P264_MB_T8X8 */
 } curpic_t;
 
 struct p264parse {
@@ -110,6 +114,7 @@ struct p264parse {
     /* slice scope */
     slice_t sh;                               /* current slice */
     uint16_t slice_flags;                     /* the records' `flags` of the current slice: its offsets minus the picture's (include/p264hip.h) */
+    int t8x8_mode;                            /* transform_8x8_mode_flag of the slice's PPS, under a High SPS (0 otherwise) */
     /* the slice's OWN lists: what its macroblocks are parsed against (vector prediction, CABAC contexts, skip / direct inference and
      * temporal direct's list-0 mapping are slice-local) and what end_slice resolves its indices through */
     int list[2][P264HIP_MAX_REFS], n_list[2];
@@ -152,6 +157,14 @@ static inline int median3(int a, int b, int c)
 }
 
 /* ---------------------------------------------------------------- parameter sets -------- */
+static long rbsp_stop_bit(const uint8_t *buf, int size);
+/* the profiles whose SPS carries chroma_format_idc .. seq_scaling_matrix_present_flag behind its id (7.3.2.1.1) and whose PPS may
+ * carry transform_8x8_mode_flag */
+static int sps_is_high(int profile)
+{
+    return profile == 100 || profile == 110 || profile == 122 || profile == 244 || profile == 44 || profile == 83 || profile == 86 ||
+           profile == 118 || profile == 128;
+}
 /* decoder/set.c:37-167 */
 static int parse_sps(p264parse *p, bitrd_t *b)
 {
@@ -164,6 +177,20 @@ static int parse_sps(p264parse *p, bitrd_t *b)
     sps_t old = *s;
     memset(s, 0, sizeof *s);
     s->profile_idc = profile; s->level_idc = level;
+    s->high = sps_is_high(profile);
+    if (s->high) {
+        /* what the kernels decode of the High tools: 4:2:0, 8 bits, no transform bypass, flat scaling lists */
+        const unsigned cf = br_ue(b);
+        const int separate = cf == 3 ? (int)br_u1(b) : 0;
+        const unsigned bd_y = br_ue(b), bd_c = br_ue(b);
+        const int bypass = (int)br_u1(b), matrices = (int)br_u1(b);
+        if (br_eof(b) || cf != 1 || separate || bd_y || bd_c || bypass || matrices) {
+            ERR(p, "SPS %u (profile %d): chroma_format_idc %u, bit depths %u / %u, transform bypass %d, scaling matrices %d unsupported (4:2:0, 8 bits, flat lists)",
+                id, profile, cf, bd_y + 8, bd_c + 8, bypass, matrices);
+            *s = old;                                   /* keep the set we had */
+            return -1;
+        }
+    }
     s->log2_max_frame_num = (int)br_ue(b) + 4;
     s->poc_type = (int)br_ue(b);
     if (s->poc_type == 0) s->log2_max_poc_lsb = (int)br_ue(b) + 4;
@@ -225,6 +252,14 @@ static int parse_pps(p264parse *p, bitrd_t *b)
     q->constrained_intra = (int)br_u1(b);
     q->redundant_pic_cnt = (int)br_u1(b);
     if (br_eof(b)) { ERR(p, "incomplete PPS"); return -1; }
+    /* while more_rbsp_data( ): the High extension.  Only remembered here - which SPS the PPS goes with is known when a slice
+     * activates the pair, and under any other profile nothing of it is looked at (a PPS of such a stream never fails on it) */
+    if ((long)br_consumed(b) < rbsp_stop_bit(b->buf, (int)b->size)) {
+        q->t8x8_mode = (int)br_u1(b);
+        q->scaling_matrix = (int)br_u1(b);
+        q->second_chroma_qp_offset = q->scaling_matrix ? q->chroma_qp_offset : br_se(b);      /* (behind matrices nothing can be read without parsing them) */
+        q->ext = !br_eof(b);
+    }
     q->valid = 1;
     INFO(p, "p264amd: pps:%u sps:%d %s ref0:%d QP:%d QC=%d DFC:%d CIP:%d\n", id, q->sps_id,
          q->cabac ? "CABAC" : "CAVLC", q->num_ref_idx[0], q->pic_init_qp, q->chroma_qp_offset,
@@ -817,10 +852,23 @@ static int parse_residual(p264parse *p, bitrd_t *b, p264hip_mb_t *m, mbcoef_t *c
         if (tc) cf->mask |= P264_COEF_LUMA_DC;
     }
     int maxc = m->mb_type == P264_MB_I16x16 ? 15 : 16;
+    const int t8 = m->intra_modes & P264_MB_T8X8;
     for (int i = 0; i < 16; i++) {
         const int at = nc_pos[i];
         nnz[i] = 0; nc[at] = 0;
         if (!(cbp_l & (1 << (i >> 2)))) continue;
+        if (t8) {
+            /* 7.3.5.3.2: an 8x8 block travels as four 4x4 blocks, each with its own nC and total_coeff (kept for the neighbours' nC);
+             * level k of block j is scan position 4 k + j of the 8x8 block, whose 64 levels fill the quadrant's four entries */
+            int16_t lv[16], *l8 = cf->blk[i & ~3];
+            memset(lv, 0, sizeof lv);
+            if ((i & 3) == 0) memset(l8, 0, 128);
+            if ((tc = cavlc_read_block(b, nc_of(nc, at), 16, lv)) < 0) return -1;
+            for (int k = 0; k < 16; k++) l8[4 * k + (i & 3)] = lv[k];
+            nnz[i] = (uint8_t)tc; nc[at] = (uint8_t)tc;
+            if (tc) cf->mask |= 0xfu << (i & ~3);
+            continue;
+        }
         if ((tc = cavlc_read_block(b, nc_of(nc, at), maxc, cf->blk[i])) < 0) return -1;
         nnz[i] = (uint8_t)tc; nc[at] = (uint8_t)tc;
         if (tc) cf->mask |= 1u << i;
@@ -1175,13 +1223,16 @@ static inline __attribute__((always_inline)) int parse_inter_pred(p264parse *p, 
 /* ---------------------------------------------------------------- macroblocks ------------ */
 /* What follows the prediction syntax in every macroblock but I_PCM: coded_block_pattern (Intra16x16 carries it in its type),
  * mb_qp_delta, residual (decoder/macroblock.c:540-587), then the levels and the QP into the record */
-static int parse_mb_tail(p264parse *p, bitrd_t *b, p264hip_mb_t *m)
+/* t8_ok: the macroblock's prediction lets transform_size_8x8_flag follow the pattern (7.3.5): inter, no sub-macroblock partition
+ * below 8x8, direct-predicted quadrants (or B_Direct_16x16) only under direct_8x8_inference_flag */
+static int parse_mb_tail(p264parse *p, bitrd_t *b, p264hip_mb_t *m, int t8_ok)
 {
     mbcoef_t cf; cf.mask = 0;
     if (m->mb_type != P264_MB_I16x16) {
         const int c = rd_cbp(p, b, m->mb_type == P264_MB_I4x4);
         if (c < 0) { ERR(p, "invalid cbp"); return -1; }
         m->cbp = (uint8_t)c;
+        if ((c & 15) && p->t8x8_mode && t8_ok && rd_t8x8_flag(p, b)) m->intra_modes |= P264_MB_T8X8;
     }
     int qp = p->sh.qp, has_res = (m->cbp != 0 || m->mb_type == P264_MB_I16x16);
     if (has_res) {
@@ -1205,6 +1256,7 @@ static int parse_mb_t(p264parse *p, bitrd_t *b, unsigned t, int intra_t)
     p264hip_mb_t *m = &q->mb[p->mbi];
     begin_mb(p, m);
     uint8_t *i4 = q->i4 + p->mbi * 16;
+    int t8_ok = intra_t < 0;
 
     if (intra_t >= 0) {
         /* ---- intra (decoder/macroblock.c:117-139, 265-301) ---- */
@@ -1214,6 +1266,8 @@ static int parse_mb_t(p264parse *p, bitrd_t *b, unsigned t, int intra_t)
         clear_motion(p);
         if (intra_t == 0) {
             m->mb_type = P264_MB_I4x4;
+            /* I_NxN: transform_size_8x8_flag comes in front of the prediction modes; 1 = Intra 8x8 prediction, which no kernel does */
+            if (p->t8x8_mode && rd_t8x8_flag(p, b)) { ERR(p, "Intra 8x8 prediction unsupported"); return -1; }
             for (int i = 0; i < 16; i++) i4[i] = (uint8_t)rd_intra4x4_mode(p, b, predict_i4mode(p, i));
         } else {
             m->mb_type = P264_MB_I16x16;
@@ -1240,11 +1294,12 @@ static int parse_mb_t(p264parse *p, bitrd_t *b, unsigned t, int intra_t)
                 const int sub = rd_sub_mb_type(p, b);
                 if (sub < 0 || sub > 3) { ERR(p, "invalid i_sub_partition"); return -1; }   /* (< 0: a ue(v) past 2^31 in a damaged stream) */
                 sub_partition(pt, k, sub_w[sub], sub_h[sub], PRED_L0);
+                t8_ok &= sub == 0;
             }
         }
         if (parse_inter_pred(p, b, 1, np, pt, t != 4, NULL) < 0) return -1;
     }
-    return parse_mb_tail(p, b, m);
+    return parse_mb_tail(p, b, m, t8_ok);
 }
 
 /* table 7-14, mb_type 4..21: (type - 4) >> 1 -> prediction of the two partitions (even types 16x8, odd types 8x16) */
@@ -1265,7 +1320,9 @@ static int parse_mb_b_t(p264parse *p, bitrd_t *b, unsigned t)
     m->mb_type = P264_MB_B;
     memset(q->i4 + p->mbi * 16, 2, 16);
     clear_motion(p);
-    if (t == 0) store_direct_mb(p);                           /* B_Direct_16x16: like B_Skip, with a residual */
+    int t8_ok = 1;
+    const int inf8 = p->sps[p->active_sps].direct_8x8_inference;
+    if (t == 0) { store_direct_mb(p); t8_ok = inf8; }         /* B_Direct_16x16: like B_Skip, with a residual */
     else {
         part_t pt[4];
         direct_t d;
@@ -1281,13 +1338,14 @@ static int parse_mb_b_t(p264parse *p, bitrd_t *b, unsigned t)
                 if (sub < 0 || sub > 12) { ERR(p, "invalid B sub_mb_type %d", sub); return -1; }   /* (< 0: as above; found by tests/tools/asan_slices.sh) */
                 sub_partition(pt, k, b_sub_w[sub], b_sub_h[sub], b_sub_pred[sub]);
                 any_direct |= sub == 0;
+                t8_ok &= sub == 0 ? inf8 : sub <= 3;
                 if (p->cabac_on && sub == 0) p->cinfo[p->mbi] |= CI_D8(k);
             }
             if (any_direct) direct_predict(p, &d);            /* from the macroblock's neighbours, before any of its own motion exists */
         }
         if (parse_inter_pred(p, b, 2, np, pt, 1, &d) < 0) return -1;
     }
-    return parse_mb_tail(p, b, m);
+    return parse_mb_tail(p, b, m, t8_ok);
 }
 
 /* one non-skipped macroblock of the current slice, whatever its slice type and entropy coder */
@@ -1409,6 +1467,7 @@ static void publish_picture(p264parse *p)
         d->weighted_bipred = c->weighted_bipred;
         memcpy(d->bipred_weight, c->bipred_weight, sizeof d->bipred_weight);
     }
+    d->transform_8x8 = c->t8x8;
     if (c->wp_set && c->wp) {
         d->explicit_wp = 1;
         d->wp_log2_denom[0] = c->wp_denom[0]; d->wp_log2_denom[1] = c->wp_denom[1];
@@ -1458,7 +1517,7 @@ static int open_picture(p264parse *p, const slice_t *sh, int nal_type, int nal_r
     c->first = *sh;
     c->type = sh->type;
     c->deblock = 0; c->alpha = c->beta = 0;
-    c->n_list[0] = c->n_list[1] = 0; c->wp_set = 0;
+    c->n_list[0] = c->n_list[1] = 0; c->wp_set = 0; c->t8x8 = 0;
     p->n_list[0] = p->n_list[1] = 0;
     p->buf[p->cur].coef_n = 0;
     memset(p->slice_of, 0xff, (size_t)p->n_mb * sizeof(uint16_t));
@@ -1477,6 +1536,17 @@ static int open_slice(p264parse *p, const slice_t *sh)
         c->deblock = 1; c->alpha = sh->alpha_off; c->beta = sh->beta_off;
     }
     /* the device adds every macroblock's deltas to the picture's offsets: this slice's minus those of the first slice that filters */
+    /* the PPS extension counts under a High SPS (decided here, where the pair is known, not where the PPS was parsed) */
+    p->t8x8_mode = 0;
+    if (p->sps[pps->sps_id].high && pps->ext) {
+        if (pps->scaling_matrix) { ERR(p, "pic_scaling_matrix_present_flag unsupported (flat scaling lists only)"); return REFUSE_SLICE; }
+        if (pps->second_chroma_qp_offset != pps->chroma_qp_offset) {
+            ERR(p, "second_chroma_qp_index_offset %d differs from chroma_qp_index_offset %d: unsupported", pps->second_chroma_qp_offset, pps->chroma_qp_offset);
+            return REFUSE_SLICE;
+        }
+        p->t8x8_mode = pps->t8x8_mode;
+        c->t8x8 |= pps->t8x8_mode;
+    }
     p->slice_flags = sh->disable_deblock == 1 ? 0 : (uint16_t)(((sh->alpha_off - c->alpha) & 255) | ((sh->beta_off - c->beta) & 255) << 8);
     p->sh = *sh;
     if (sh->type == P264_SLICE_P || sh->type == P264_SLICE_B) {

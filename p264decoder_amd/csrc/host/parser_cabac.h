@@ -245,6 +245,51 @@ static int cb_residual_block(p264parse *p, int cat, int nza, int nzb, int16_t *o
     }
     return cnt;
 }
+/* A luma 8x8 block (ctxBlockCat 5; 9.3.3.1.3, frame macroblocks): no coded_block_flag - it is inferred 1 -, the significance map
+ * over 63 positions with the context increments of table 9-43, the levels from context 426 with the increments of the other
+ * categories that are not chroma DC.  64 levels in scan order; returns their number (>= 1) */
+static const uint8_t t8_sig_inc[63] = { 0, 1, 2, 3, 4, 5, 5, 4, 4, 3, 3, 4, 4, 4, 5, 5, 4, 4, 4, 4, 3, 3, 6, 7, 7, 7, 8, 9, 10, 9, 8, 7,
+    7, 6, 11, 12, 13, 11, 6, 7, 8, 9, 14, 10, 9, 8, 6, 11, 12, 13, 11, 6, 9, 14, 10, 9, 11, 12, 13, 11, 14, 10, 12 };
+static const uint8_t t8_last_inc[63] = { 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2,
+    3, 3, 3, 3, 3, 3, 3, 3, 4, 4, 4, 4, 4, 4, 4, 4, 5, 5, 5, 5, 6, 6, 6, 6, 7, 7, 7, 7, 8, 8, 8 };
+static int cb_residual_block8(p264parse *p, int16_t *out)
+{
+    p264cabac_t *c = &p->cb;
+    int pos[64], cnt = 0, i;
+    for (i = 0; i < 63; i++) {
+        if (!p264cabac_decision(c, 402 + t8_sig_inc[i])) continue;
+        pos[cnt++] = i;
+        if (p264cabac_decision(c, 417 + t8_last_inc[i])) break;
+    }
+    if (i == 63) pos[cnt++] = 63;
+    int eq1 = 0, gt1 = 0;
+    for (int k = cnt - 1; k >= 0; k--) {
+        int a = 1;
+        if (p264cabac_decision(c, 426 + (gt1 ? 0 : (eq1 < 3 ? 1 + eq1 : 4)))) {
+            const int ctx = 426 + 5 + (gt1 < 4 ? gt1 : 4);
+            a = 2;
+            while (a < 15 && p264cabac_decision(c, ctx)) a++;
+            if (a >= 15) {
+                int j = 0;
+                while (p264cabac_bypass(c)) { a += 1 << j; if (++j > 16) return -1; }
+                while (j--) a += p264cabac_bypass(c) << j;
+            }
+            gt1++;
+        } else eq1++;
+        if (a > 32767) return -1;
+        out[pos[k]] = (int16_t)(p264cabac_bypass(c) ? -a : a);
+    }
+    return cnt;
+}
+/* transform_size_8x8_flag (9.3.3.1.1.10): the flags of the macroblocks to the left and above (a skipped one's is 0) */
+static int cb_t8x8_flag(p264parse *p)
+{
+    const picbuf_t *q = &p->buf[p->cur];
+    int ctx = 399;
+    if (cb_left(p) && (q->mb[p->mbi - 1].intra_modes & P264_MB_T8X8) && !P264_MB_IS_INTRA(q->mb[p->mbi - 1].mb_type)) ctx++;
+    if (cb_top(p) && (q->mb[p->mbi - p->mb_w].intra_modes & P264_MB_T8X8) && !P264_MB_IS_INTRA(q->mb[p->mbi - p->mb_w].mb_type)) ctx++;
+    return p264cabac_decision(&p->cb, ctx);
+}
 /* coded_block_flag of the block left of / above block blk (0..15 luma, 16..23 chroma AC) */
 static void cb_nz_neighbours(const p264parse *p, int blk, int intra, int *nza, int *nzb)
 {
@@ -279,7 +324,18 @@ static int parse_residual_cabac(p264parse *p, p264hip_mb_t *m, mbcoef_t *cf)
         if ((tc = cb_residual_block(p, 0, a, b, cf->dc_luma)) < 0) return -1;
         if (tc) { cf->mask |= P264_COEF_LUMA_DC; p->cinfo[p->mbi] |= CI_DC_Y; }
     }
+    for (int k8 = 0; (m->intra_modes & P264_MB_T8X8) && !intra && k8 < 4; k8++) {
+        /* 8x8 blocks: the quadrant's four entries hold the 64 levels; every 4x4 block of a coded quadrant counts as coded for the
+         * coded_block_flag contexts of the blocks that follow (its flag is inferred 1) */
+        memset(nnz + 4 * k8, 0, 4);
+        if (!(cbp_l & (1 << k8))) continue;
+        memset(cf->blk[4 * k8], 0, 128);
+        if ((tc = cb_residual_block8(p, cf->blk[4 * k8])) < 0) return -1;
+        memset(nnz + 4 * k8, 1, 4);
+        cf->mask |= 0xfu << (4 * k8);
+    }
     for (int i = 0; i < 16; i++) {
+        if ((m->intra_modes & P264_MB_T8X8) && !intra) break;
         nnz[i] = 0;
         if (!(cbp_l & (1 << (i >> 2)))) continue;
         memset(cf->blk[i], 0, sizeof cf->blk[i]);
@@ -340,6 +396,7 @@ static int rd_cbp(p264parse *p, bitrd_t *b, int intra4x4)
     if (c >= 48) return -1;
     return intra4x4 ? cbp_intra_of_code[c] : cbp_inter_of_code[c];
 }
+static int rd_t8x8_flag(p264parse *p, bitrd_t *b) { return p->cabac_on ? cb_t8x8_flag(p) : (int)br_u1(b); }
 static int rd_mb_qp_delta(p264parse *p, bitrd_t *b)
 {
     const int v = p->cabac_on ? cb_mb_qp_delta(p) : br_se(b);

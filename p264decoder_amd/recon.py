@@ -252,10 +252,17 @@ class HipReconstructor:
 
 
     def last_launch(self):
-        """What the last reconstruct call launched (p264hip_launch_info_t as a dict)."""
+        """The launch shapes of the last reconstruct call (p264hip_launch_info_t as a dict; what depends on the batch's CONTENT
+        rather than its size has its own accessor: last_t8x8_wgs)."""
         li = N.LaunchInfo()
         self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
-        return {n: int(getattr(li, n)) for n, _ in N.LaunchInfo._fields_ if n != "reserved"}
+        return {n: int(getattr(li, n)) for n, _ in N.LaunchInfo._fields_ if n not in ("reserved", "t8x8_wgs")}
+
+    def last_t8x8_wgs(self):
+        """Workgroups of k_t8x8 in the last reconstruct call: 0 unless a picture of the batch had transform_8x8."""
+        li = N.LaunchInfo()
+        self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
+        return int(li.t8x8_wgs)
 
 
 def device_count(lib=None):

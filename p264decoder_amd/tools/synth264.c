@@ -69,6 +69,15 @@
  *                            the writer's mirror of the decoder infers them; then int16 the number of slices and per slice and
  *                            list its length and its entries as picture numbers.
  *                            None of these draws a random number unless asked for.
+ *            [--t8x8 PCT]    High profile (profile_idc 100: chroma_format_idc 1, 8 bits, no scaling matrices) with
+ *                            transform_8x8_mode_flag 1 in the PPS extension: PCT percent of the inter macroblocks that may carry
+ *                            transform_size_8x8_flag 1 (7.3.5: coded luma, no partition below 8x8, direct prediction only with
+ *                            --d8inf) do, their luma written as 8x8 blocks - CAVLC: four interleaved 4x4 blocks each, CABAC: one
+ *                            block of category 5; [--dump-t8x8 f] per picture uint32 macroblocks, then per macroblock one byte
+ *                            flag, one byte with a bit per quadrant that carries levels, and per such quadrant its 64 levels in
+ *                            8x8 scan order (int16); [--t8x8-intra PCT] PCT percent of the I_NxN macroblocks carry the flag too
+ *                            (Intra 8x8 prediction, written on as Intra4x4: a stream for a decoder to refuse).  Without --t8x8
+ *                            the streams are what they were, byte for byte.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -140,6 +149,7 @@ static int8_t  *i4m;                        /* [mb][16], 2 for non-I4x4 */
 static int cur;                             /* current MB index */
 
 static int opt_pps_alt = 0, cur_pps = 0;
+static int opt_t8x8 = -1, opt_t8x8_intra = 0;   /* --t8x8 PCT (-1: not given), --t8x8-intra PCT: see put_inter_tail */
 static int opt_wp = 0, opt_wp_bi = 0, opt_wp_dup = 0, opt_wp_identity = 0, opt_wp_differ = 0, opt_wp_bad_sum = 0;
 static FILE *dump_wp = NULL;
 /* the current picture's pred_weight_table: [list][index][Y, Cb, Cr][weight, offset]; flags per entry and component kind */
@@ -398,11 +408,25 @@ static int rand_residual(resid_t *r, int is_i16, int *i16_ac)
     return cbp | (cc << 4);
 }
 
-static void put_residual(bw_t *b, int mbx, int mby, const resid_t *r, int is_i16, int cbp)
+/* l8 (--t8x8, transform_size_8x8_flag 1): the macroblock's luma as 8x8 blocks, [quadrant][64 levels in scan order].  CAVLC: four
+ * interleaved 4x4 blocks each, level k of block j = scan position 4 k + j (7.3.5.3.2), each with its own nC and total_coeff;
+ * CABAC: one block of category 5, and every 4x4 block of the quadrant counts as coded for the blocks that follow */
+static void put_residual(bw_t *b, int mbx, int mby, const resid_t *r, int is_i16, int cbp, const int16_t (*l8)[64])
 {
     uint8_t *nz = nnz + (size_t)cur * 24;
     if (is_i16) { if (opt_cabac) ce_block(b, 0, 0, r->dc_luma, 16); else put_block(b, r->dc_luma, 16, predict_nc(mbx, mby, 0)); }
-    for (int i = 0; i < 16; i++) {
+    for (int q = 0; l8 && q < 4; q++) {
+        memset(nz + 4 * q, 0, 4);
+        if (!(cbp & (1 << q))) continue;
+        if (opt_cabac) { ce_block8(b, l8[q]); memset(nz + 4 * q, 1, 4); continue; }
+        for (int j = 0; j < 4; j++) {
+            int16_t lv[16]; int tc = 0;
+            for (int k = 0; k < 16; k++) { lv[k] = l8[q][4 * k + j]; tc += lv[k] != 0; }
+            put_block(b, lv, 16, predict_nc(mbx, mby, 4 * q + j));
+            nz[4 * q + j] = (uint8_t)tc;
+        }
+    }
+    for (int i = 0; i < 16 && !l8; i++) {
         nz[i] = 0;
         if (!(cbp & (1 << (i >> 2)))) continue;
         if (opt_cabac) ce_block(b, is_i16 ? 1 : 2, i, r->blk[i], is_i16 ? 15 : 16);
@@ -472,6 +496,9 @@ static void put_intra(bw_t *b, int mbx, int mby, int type_offset)
     } else {
         mb_type[cur] = T_I4;
         sx_mb_type(b, type_offset);
+        /* (--t8x8-intra: a flagged I_NxN macroblock is written on as Intra4x4 - a decoder that takes Intra 8x8 reads something else from
+         * here on, one that refuses it stops at the flag) */
+        if (opt_t8x8 >= 0) sx_t8x8_flag(b, pct(opt_t8x8_intra));
         for (int i = 0; i < 16; i++) {
             int bx = blk_x[i], by = blk_y[i];
             int l = bx > 0 || L, t = by > 0 || T;
@@ -497,7 +524,7 @@ static void put_intra(bw_t *b, int mbx, int mby, int type_offset)
         sx_chroma_mode(b, legal[rnd(nl)]);
     }
     if (!is16) sx_cbp(b, cbp, 1);
-    if (cbp || is16) { sx_dqp(b, rand_qp_delta()); put_residual(b, mbx, mby, &r, is16, cbp); }
+    if (cbp || is16) { sx_dqp(b, rand_qp_delta()); put_residual(b, mbx, mby, &r, is16, cbp, NULL); }
     else { memset(nnz + (size_t)cur * 24, 0, 24); w_last_dqp = 0; }
 }
 
@@ -531,6 +558,42 @@ static void put_ipcm(bw_t *b, int type_offset)
     if (opt_cabac) { ce.low = 0; ce.range = 510; ce.outstanding = 0; ce.first = 1; }
 }
 
+/* --t8x8 PCT: High profile with transform_8x8_mode_flag 1; PCT percent of the inter macroblocks that may carry
+ * transform_size_8x8_flag 1 (7.3.5: luma coded, no partition below 8x8, direct prediction only under direct_8x8_inference) do */
+static FILE *dump_t8;                       /* --dump-t8x8: per picture the macroblock count, then per macroblock the flag, the quadrants with levels
+                                               (a bit each) and per such quadrant its 64 levels in scan order (int16) */
+static void rand_block8(int16_t *lv)
+{
+    memset(lv, 0, 128);
+    int tc = 1;
+    while (tc < 64 && pct(70)) tc++;
+    if (pct(3)) tc = 64;
+    for (int k = 0; k < tc; k++) {
+        int p;
+        do p = pct(60) ? rnd(24) : rnd(64); while (lv[p]);
+        lv[p] = (int16_t)(pct(35) ? (rnd(2) ? 1 : -1) : rand_level());
+    }
+}
+/* what follows the prediction syntax of an inter macroblock: coded_block_pattern, transform_size_8x8_flag, mb_qp_delta, residual */
+static void put_inter_tail(bw_t *b, int mbx, int mby, int t8_eligible)
+{
+    resid_t r; int dummy;
+    int cbp = rand_residual(&r, 0, &dummy);
+    sx_cbp(b, cbp, 0);
+    int16_t (*l8)[64] = NULL;
+    if (opt_t8x8 >= 0 && (cbp & 15) && t8_eligible) {
+        const int use = pct(opt_t8x8);
+        sx_t8x8_flag(b, use);
+        if (use) {
+            l8 = (int16_t (*)[64])(w_t8lv + (size_t)cur * 256);
+            for (int q = 0; q < 4; q++) if (cbp & (1 << q)) rand_block8(l8[q]);
+            w_t8cbp[cur] = (uint8_t)(cbp & 15);
+        }
+    }
+    if (cbp) { sx_dqp(b, rand_qp_delta()); put_residual(b, mbx, mby, &r, 0, cbp, l8); }
+    else { memset(nnz + (size_t)cur * 24, 0, 24); w_last_dqp = 0; }
+}
+
 /* try to write a non-skipped inter MB; returns 0 if no legal vectors were found */
 static void put_inter(bw_t *b, int mbx, int mby)
 {
@@ -541,7 +604,7 @@ static void put_inter(bw_t *b, int mbx, int mby)
     memset(i4m + cur * 16, 2, 16);
     sx_mb_type(b, t);
     /* te(v) with two active references: one bit, inverted */
-    int pref[4] = { 0, 0, 0, 0 };
+    int pref[4] = { 0, 0, 0, 0 }, t8_ok = 1;
     if (t < 3) {
         int np = t == 0 ? 1 : 2;
         for (int k = 0; k < np; k++) {
@@ -558,7 +621,7 @@ static void put_inter(bw_t *b, int mbx, int mby)
         }
     } else {
         int sub[4];
-        for (int k = 0; k < 4; k++) { sub[k] = opt_sub8x8 ? rnd(4) : 0; sx_sub_mb_type(b, k, sub[k]); }   /* sub_mb_type: 8x8 only inside the reference's safe subset (A-Q4) */
+        for (int k = 0; k < 4; k++) { sub[k] = opt_sub8x8 ? rnd(4) : 0; sx_sub_mb_type(b, k, sub[k]); t8_ok &= sub[k] == 0; }   /* sub_mb_type: 8x8 only inside the reference's safe subset (A-Q4) */
         for (int k = 0; k < 4; k++) {
             if (n_active > 1) pref[k] = pct(55) ? 0 : rnd(n_active);
             sx_ref_idx(b, 0, (k & 1) * 2, (k >> 1) * 2, 2, 2, n_active, pref[k]);
@@ -577,11 +640,7 @@ static void put_inter(bw_t *b, int mbx, int mby)
                 }
         }
     }
-    resid_t r; int dummy;
-    int cbp = rand_residual(&r, 0, &dummy);
-    sx_cbp(b, cbp, 0);
-    if (cbp) { sx_dqp(b, rand_qp_delta()); put_residual(b, mbx, mby, &r, 0, cbp); }
-    else { memset(nnz + (size_t)cur * 24, 0, 24); w_last_dqp = 0; }
+    put_inter_tail(b, mbx, mby, t8_ok);
 }
 
 /* P_SKIP motion (8.4.1.1); returns 0 when the inferred vector would leave the safe zone */
@@ -908,6 +967,14 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
         for (int i = 0; i < pcm_n; i++) { fwrite(&pcm_idx[i], 4, 1, dump_pcm); fwrite(pcm_bytes + (size_t)i * 384, 1, 384, dump_pcm); }
     }
     pcm_n = 0;
+    if (dump_t8) {
+        const uint32_t n = (uint32_t)NMB;
+        fwrite(&n, 4, 1, dump_t8);
+        for (int m = 0; m < NMB; m++) {
+            fwrite(&w_t8[m], 1, 1, dump_t8); fwrite(&w_t8cbp[m], 1, 1, dump_t8);
+            for (int q = 0; q < 4; q++) if (w_t8[m] && (w_t8cbp[m] >> q) & 1) fwrite(w_t8lv + (size_t)m * 256 + q * 64, 2, 64, dump_t8);
+        }
+    }
     if (dump_avail) { fwrite(w_avail, 1, (size_t)NMB, dump_avail); fwrite(i4m, 1, (size_t)NMB * 16, dump_avail); }
     if (dump_wp) {
         int16_t rec[3 + 2 * 16 * 3 * 2];
@@ -992,6 +1059,9 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--slice-lists")) opt_slice_lists = 1;
         else if (!strcmp(a, "--slice-lists-many")) opt_slice_lists = opt_slice_lists_many = 1;
         else if (!strcmp(a, "--dump-slices")) { dump_slices = fopen(argv[i + 1], "wb"); i++; }
+        else if (!strcmp(a, "--t8x8")) { opt_t8x8 = v < 0 ? 0 : v > 100 ? 100 : v; i++; }
+        else if (!strcmp(a, "--t8x8-intra")) { opt_t8x8_intra = v < 0 ? 0 : v > 100 ? 100 : v; i++; }
+        else if (!strcmp(a, "--dump-t8x8")) { dump_t8 = fopen(argv[i + 1], "wb"); i++; }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
     if (W < 1 || H < 1 || W > 512 || H > 512 || frames < 1 || opt_qp < 0 || opt_qp > 51 || opt_refs < 1 || opt_refs > ((opt_mmco || opt_bframes) ? 4 : 2) || (opt_bframes && (opt_refs < 2 || opt_bframes > 4)) || opt_alpha < -6 || opt_alpha > 6 || opt_beta < -6 || opt_beta > 6) { fprintf(stderr, "bad geometry\n"); return 2; }
@@ -1008,9 +1078,13 @@ int main(int argc, char **argv)
     const int log2_fn = 8;
     {   /* SPS: Baseline, POC type 2, one reference frame */
         bw_t b = { 0 };
-        if (opt_bframes || opt_cabac || opt_wp || opt_wp_bi) { bw_put(&b, 8, 77); bw_put(&b, 8, 0x40); bw_put(&b, 8, 40); }      /* Main profile */
+        if (opt_t8x8 >= 0) { bw_put(&b, 8, 100); bw_put(&b, 8, 0); bw_put(&b, 8, 40); }                                           /* High profile */
+        else if (opt_bframes || opt_cabac || opt_wp || opt_wp_bi) { bw_put(&b, 8, 77); bw_put(&b, 8, 0x40); bw_put(&b, 8, 40); }      /* Main profile */
         else { bw_put(&b, 8, 66); bw_put(&b, 8, 0xc0); bw_put(&b, 8, 40); }
-        bw_ue(&b, 0); bw_ue(&b, log2_fn - 4);
+        bw_ue(&b, 0);
+        /* High: chroma_format_idc 1, both bit depths 8, no transform bypass, no scaling matrices */
+        if (opt_t8x8 >= 0) { bw_ue(&b, 1); bw_ue(&b, 0); bw_ue(&b, 0); bw_put(&b, 1, 0); bw_put(&b, 1, 0); }
+        bw_ue(&b, log2_fn - 4);
         if (opt_bframes) { bw_ue(&b, 0); bw_ue(&b, 8 - 4); }   /* pic_order_cnt_type 0, log2_max_pic_order_cnt_lsb 8 */
         else bw_ue(&b, 2);
         bw_ue(&b, (uint32_t)opt_refs); bw_put(&b, 1, 0);    /* num_ref_frames */
@@ -1028,6 +1102,7 @@ int main(int argc, char **argv)
         bw_ue(&b, 0); bw_ue(&b, 0); bw_put(&b, 1, (uint32_t)opt_wp); bw_put(&b, 2, (uint32_t)(opt_wp_bi ? 1 : opt_implicit ? 2 : 0));   /* weighted_pred, weighted_bipred_idc */
         bw_se(&b, opt_qp - 26); bw_se(&b, 0); bw_se(&b, opt_cqo);
         bw_put(&b, 1, 1); bw_put(&b, 1, (uint32_t)opt_cintra); bw_put(&b, 1, 0);   /* deblocking_filter_control_present, constrained_intra_pred, redundant_pic_cnt_present */
+        if (opt_t8x8 >= 0) { bw_put(&b, 1, 1); bw_put(&b, 1, 0); bw_se(&b, opt_cqo); }   /* transform_8x8_mode_flag, pic_scaling_matrix_present_flag, second_chroma_qp_index_offset */
         bw_trailing(&b);
         write_nal(f, 3, 8, &b); free(b.buf);
     }
@@ -1051,6 +1126,7 @@ int main(int argc, char **argv)
         if (dump_pcm) fclose(dump_pcm);
         if (dump_avail) fclose(dump_avail);
         if (dump_slices) fclose(dump_slices);
+        if (dump_t8) fclose(dump_t8);
         return 0;
     }
     for (int n = 0; n < frames; n++) {
@@ -1069,5 +1145,6 @@ int main(int argc, char **argv)
     if (dump_pcm) fclose(dump_pcm);
     if (dump_avail) fclose(dump_avail);
     if (dump_slices) fclose(dump_slices);
+    if (dump_t8) fclose(dump_t8);
     return 0;
 }

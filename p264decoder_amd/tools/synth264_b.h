@@ -143,8 +143,10 @@ static void put_b_mb(bw_t *b, int mbx, int mby)
     mb_type[cur] = T_P;
     memset(i4m + cur * 16, 2, 16);
     const int pick = rnd(100);
+    int t8_ok = 1;                                                      /* transform_size_8x8_flag may follow (7.3.5) */
     if (pick < 12) {                                                    /* B_Direct_16x16 */
         bdirect_t d;
+        t8_ok = opt_d8inf;
         sx_mb_type(b, 0);
         b_direct(mbx, mby, &d);
         b_apply_direct(&d, 0, 0, 4, 4, 0);
@@ -188,7 +190,7 @@ static void put_b_mb(bw_t *b, int mbx, int mby)
         static const int s_w[13] = { 2, 2, 2, 2, 2, 1, 2, 1, 2, 1, 1, 1, 1 }, s_h[13] = { 2, 2, 2, 2, 1, 2, 1, 2, 1, 2, 1, 1, 1 };
         int sub[4], any_direct = 0;
         sx_mb_type(b, 22);
-        for (int k = 0; k < 4; k++) { sub[k] = pct(25) ? 0 : 1 + rnd(opt_sub8x8 ? 12 : 3); sx_sub_mb_type(b, k, sub[k]); any_direct |= !sub[k]; }
+        for (int k = 0; k < 4; k++) { sub[k] = pct(25) ? 0 : 1 + rnd(opt_sub8x8 ? 12 : 3); sx_sub_mb_type(b, k, sub[k]); any_direct |= !sub[k]; t8_ok &= sub[k] ? sub[k] <= 3 : opt_d8inf; }
         bdirect_t d;
         if (any_direct) b_direct(mbx, mby, &d);
         int r[2][4];
@@ -214,11 +216,7 @@ static void put_b_mb(bw_t *b, int mbx, int mby)
                     }
             }
     }
-    resid_t rs; int dummy;
-    int cbp = rand_residual(&rs, 0, &dummy);
-    sx_cbp(b, cbp, 0);
-    if (cbp) { sx_dqp(b, rand_qp_delta()); put_residual(b, mbx, mby, &rs, 0, cbp); }
-    else { memset(nnz + (size_t)cur * 24, 0, 24); w_last_dqp = 0; }
+    put_inter_tail(b, mbx, mby, t8_ok);
 }
 
 /* the motion of a finished reference picture, kept with its frame-store entry (for the direct prediction of B pictures) */

@@ -72,8 +72,11 @@ static void ce_terminate(bw_t *b, int bin)
 /* ---- the writer's record of what context selection looks at ------------------------------------------------------------ */
 static uint8_t *w_skip, *w_direct16, *w_d8, *w_cbp, *w_cmode, *w_dc, *w_mvd[2];   /* per macroblock; w_mvd: [mb][16][2] */
 static int w_last_dqp;
+/* --t8x8: per macroblock transform_size_8x8_flag, the 8x8 blocks that carry levels (a bit per quadrant) and those levels in scan order */
+static uint8_t *w_t8, *w_t8cbp; static int16_t *w_t8lv;
 static void w_alloc(void)
 {
+    w_t8 = calloc((size_t)NMB, 1); w_t8cbp = calloc((size_t)NMB, 1); w_t8lv = calloc((size_t)NMB * 256, 2);
     w_skip = calloc((size_t)NMB, 1); w_direct16 = calloc((size_t)NMB, 1); w_d8 = calloc((size_t)NMB, 1); w_cbp = calloc((size_t)NMB, 1);
     w_cmode = calloc((size_t)NMB, 1); w_dc = calloc((size_t)NMB, 1); w_mvd[0] = calloc((size_t)NMB, 32); w_mvd[1] = calloc((size_t)NMB, 32);
 }
@@ -83,7 +86,7 @@ static void w_begin_mb(void)
      * the current macroblock before their vectors are written) */
     memset(refs + cur * 16, -1, 16);
     if (refs1) memset(refs1 + cur * 16, -1, 16);
-    w_skip[cur] = 0; w_direct16[cur] = 0; w_d8[cur] = 0; w_cbp[cur] = 0; w_cmode[cur] = 0; w_dc[cur] = 0;
+    w_skip[cur] = 0; w_direct16[cur] = 0; w_d8[cur] = 0; w_cbp[cur] = 0; w_cmode[cur] = 0; w_dc[cur] = 0; w_t8[cur] = 0; w_t8cbp[cur] = 0;
     memset(w_mvd[0] + cur * 32, 0, 32); memset(w_mvd[1] + cur * 32, 0, 32);
 }
 static int w_A(void) { return avail(cur % W - 1, cur / W); }                 /* the macroblock to the left / above is usable */
@@ -268,6 +271,13 @@ static void sx_cbp(bw_t *b, int cbp, int intra4x4)
     ce_bin(b, 77 + (la != 0) + 2 * (lb != 0), cc != 0);
     if (cc) ce_bin(b, 81 + (la == 2) + 2 * (lb == 2), cc == 2);
 }
+/* transform_size_8x8_flag (7.3.5; 9.3.3.1.1.10: the neighbours' flags) */
+static void sx_t8x8_flag(bw_t *b, int v)
+{
+    if (!opt_cabac) bw_put(b, 1, (uint32_t)v);
+    else ce_bin(b, 399 + (w_A() && w_t8[cur - 1]) + (w_B() && w_t8[cur - W]), v);
+    w_t8[cur] = (uint8_t)v;
+}
 static void sx_dqp(bw_t *b, int v)
 {
     if (!opt_cabac) { bw_se(b, v); return; }
@@ -322,6 +332,41 @@ static void ce_block(bw_t *b, int cat, int blk, const int16_t *lv, int n)
         ce_bin(b, abs0[cat] + (big ? 0 : ones < 3 ? 1 + ones : 4), a > 1);
         if (a > 1) {
             const int cap = cat == 3 ? 3 : 4, ctx = abs0[cat] + 5 + (big < cap ? big : cap);
+            for (int k = 2; k < (a < 15 ? a : 15); k++) ce_bin(b, ctx, 1);
+            if (a < 15) ce_bin(b, ctx, 0);
+            else {
+                int rest = a - 15, k = 0;
+                while (rest >= (1 << k)) { ce_bypass(b, 1); rest -= 1 << k; k++; }
+                ce_bypass(b, 0);
+                while (k--) ce_bypass(b, (rest >> k) & 1);
+            }
+            big++;
+        } else ones++;
+        ce_bypass(b, lv[i] < 0);
+    }
+}
+
+/* a luma 8x8 block (ctxBlockCat 5): 64 levels in scan order, at least one of them non-zero - the category has no coded_block_flag
+ * (inferred 1).  Frame macroblocks: table 9-43's ctxIdxInc of significant_coeff_flag / last_significant_coeff_flag by scan position */
+static const uint8_t t8_sig_inc[63] = { 0, 1, 2, 3, 4, 5, 5, 4, 4, 3, 3, 4, 4, 4, 5, 5, 4, 4, 4, 4, 3, 3, 6, 7, 7, 7, 8, 9, 10, 9, 8, 7,
+    7, 6, 11, 12, 13, 11, 6, 7, 8, 9, 14, 10, 9, 8, 6, 11, 12, 13, 11, 6, 9, 14, 10, 9, 11, 12, 13, 11, 14, 10, 12 };
+static const uint8_t t8_last_inc[63] = { 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2,
+    3, 3, 3, 3, 3, 3, 3, 3, 4, 4, 4, 4, 4, 4, 4, 4, 5, 5, 5, 5, 6, 6, 6, 6, 7, 7, 7, 7, 8, 8, 8 };
+static void ce_block8(bw_t *b, const int16_t *lv)
+{
+    int last = 63;
+    while (last > 0 && !lv[last]) last--;
+    for (int i = 0; i < 63 && i <= last; i++) {
+        ce_bin(b, 402 + t8_sig_inc[i], lv[i] != 0);
+        if (lv[i]) ce_bin(b, 417 + t8_last_inc[i], i == last);
+    }
+    int ones = 0, big = 0;
+    for (int i = last; i >= 0; i--) {
+        if (!lv[i]) continue;
+        const int a = lv[i] < 0 ? -lv[i] : lv[i];
+        ce_bin(b, 426 + (big ? 0 : ones < 3 ? 1 + ones : 4), a > 1);
+        if (a > 1) {
+            const int ctx = 426 + 5 + (big < 4 ? big : 4);
             for (int k = 2; k < (a < 15 ? a : 15); k++) ce_bin(b, ctx, 1);
             if (a < 15) ce_bin(b, ctx, 0);
             else {
