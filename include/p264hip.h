@@ -295,6 +295,52 @@ int  p264hip_input_commit(p264hip_ctx *ctx, int slot);
  * the context (buffers are created on demand and live as long as the context); enqueued on the context's stream - *dev is
  * readable by other streams / RCCL after p264hip_sync or a marker. */
 int  p264hip_frame_planar_device(p264hip_ctx *ctx, int stream, int slot, int index, void **dev, size_t *bytes);
+/* ---- frames handed on ON THE DEVICE: a batch of pictures, cropped to a window, as I420 / NV12 / RGB, in ONE launch into memory
+ * the caller owns (a torch tensor's data_ptr(), an encoder's input surface).  Nothing of this has a counterpart in the reference,
+ * whose frames leave as MB-aligned planes on the host (decoder/decoder.c:652-657).
+ *
+ * Layout of one picture in dst, in bytes; P = pitch, W x H = the window (tight P: the value pitch = 0 stands for):
+ *   I420   tight P = W    Y row y at y*P; U at P*H, rows P/2 apart, H/2 rows; V at P*H + (P/2)*(H/2).  P even.     P*H*3/2 bytes
+ *   NV12   tight P = W    Y as above; ONE plane of interleaved U, V pairs at P*H, rows P apart, H/2 rows           P*H*3/2 bytes
+ *   RGB24  tight P = 3W   row y at y*P; pixel x is the bytes R, G, B at 3x                                         P*H bytes
+ *   RGBP   tight P = W    three planes of P*H bytes each, in the order R, G, B                                     3*P*H bytes
+ * Picture i of a call lies at dst + i*frame_stride (0 = tight: the picture's bytes).  Every byte of dst outside the rows' W
+ * (RGB24: 3W) bytes is left untouched: between a row's end and P, between a picture's end and frame_stride.
+ *
+ * RGB arithmetic (bit-exact; tests/export_checker.py is the same in numpy).  Chroma is the nearest sample, (x >> 1, y >> 1).
+ *   channel = clip255((cy*(Y - yo) + cu*(Cb - 128) + cv*(Cr - 128) + 4096) >> 13)     (arithmetic shift)
+ * yo = 16 for limited range, 0 for full range; each coefficient is floor(c*8192 + 1/2) of the matrix's exact rational c:
+ * Kr, Kb = 0.299, 0.114 (BT.601) or 0.2126, 0.0722 (BT.709), Kg = 1 - Kr - Kb; luma scale 255/219 and chroma scale s = 255/224
+ * for limited range, both 1 for full range;  R: cv = 2(1-Kr)s;  G: cu = -2Kb(1-Kb)s/Kg, cv = -2Kr(1-Kr)s/Kg;  B: cu = 2(1-Kb)s:
+ *                    cy    R.cv   G.cu   G.cv   B.cu
+ *   601 limited     9539  13075  -3209  -6660  16525
+ *   601 full        8192  11485  -2819  -5850  14516
+ *   709 limited     9539  14686  -1747  -4366  17305
+ *   709 full        8192  12901  -1535  -3835  15201
+ * Over all 2^24 (Y, Cb, Cr) the result is within 1 of clip(floor(real + 1/2)), and every sum stays below 2^23 in magnitude. */
+enum { P264HIP_FMT_I420 = 0, P264HIP_FMT_NV12 = 1, P264HIP_FMT_RGB24 = 2, P264HIP_FMT_RGBP = 3 };
+enum { P264HIP_MATRIX_BT601 = 0, P264HIP_MATRIX_BT709 = 1 };
+typedef struct p264hip_export {
+    int32_t format, matrix, full_range;          /* matrix / full_range: RGB formats only, otherwise must be 0 */
+    int32_t crop_left, crop_top, width, height;  /* window of the luma plane, in samples; all four even, width, height > 0 */
+    int32_t pitch;                               /* bytes per row of plane 0; 0 = tight */
+    int64_t frame_stride;                        /* bytes from one picture to the next in dst; 0 = tight */
+} p264hip_export_t;
+/* bytes of one picture (host only, no device); < 0 = P264HIP_EINVAL: a null argument, an unknown format or matrix, matrix /
+ * full_range on a YUV format, a window with an odd or non-positive member, a pitch below the tight one, an odd pitch for I420 */
+int64_t p264hip_export_frame_bytes(const p264hip_export_t *e);
+/* 0, or P264HIP_EINVAL for what p264hip_export_frame_bytes refuses, a window that leaves the frame of mb_w x mb_h macroblocks and a
+ * frame_stride (other than 0) below the picture's bytes (host only) */
+int     p264hip_export_check(const p264hip_export_t *e, int mb_w, int mb_h);
+/* picture i = frame slots[i] of stream streams[i], written at dst_dev + i*frame_stride.  Asynchronous on the context's stream: it
+ * runs behind every reconstruct queued before it, and dst_dev is complete after p264hip_sync or a marker.  streams[] and slots[]
+ * are consumed before the call returns; entries may repeat; n >= 1, bounded only by dst_bytes (more than 65535 pictures go out
+ * as several launches).  P264HIP_EINVAL, before anything is queued, for a null argument, n < 1, a stream or slot out of range,
+ * whatever p264hip_export_check refuses, and dst_bytes < (n-1)*frame_stride + the picture's bytes.  The kernel writes the bytes
+ * listed above and no others. */
+int     p264hip_export_frames(p264hip_ctx *ctx, const int *streams, const int *slots, int n,
+                              const p264hip_export_t *e, void *dst_dev, size_t dst_bytes);
+
 /* plain synchronous copies between host and device memory (the fan-out's TCP transport uses them where it stands in for a
  * device-to-device transport in tests) */
 int  p264hip_copy_to_device(void *dev, const void *host, size_t bytes);

@@ -47,6 +47,11 @@ int p264parse_nal(p264parse *p, int nal_type, int nal_ref_idc,
 int p264parse_mb_width(const p264parse *p);
 int p264parse_mb_height(const p264parse *p);
 int p264parse_slots(const p264parse *p);          /* num_ref_frames + 1 */
+/* The display window of the active SPS in luma samples: its frame cropping offsets times 2 in both directions (4:2:0, frame
+ * macroblocks only); without cropping the MB-aligned frame.  The parser itself never crops: its pictures, and every frame store
+ * behind them, stay MB-aligned - the window is what a caller puts into a p264hip_export_t.  -1 before the first slice, or where
+ * the offsets leave no sample. */
+int p264parse_crop(const p264parse *p, int *left, int *top, int *width, int *height);
 /* bumped every time a new SPS/PPS pair is activated (context re-init, decoder.c:304-343) */
 int p264parse_generation(const p264parse *p);
 

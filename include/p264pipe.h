@@ -6,7 +6,8 @@
  * into pinned memory (registered huge pages, p264hip_host_alloc), so the uploads are plain DMA; while the GPU works on round r
  * the threads already parse round r+1 - they do not stop at the end of a round: a stream's next picture may be parsed as
  * soon as its previous one is and the device has finished with the round before that (whose buffers the parser reuses).  Output pictures stay in HBM (the frame stores of p264hip); p264pipe_read_frame fetches the last one of a
- * stream.  There is no counterpart in the reference (its decoder is single-stream, single-threaded,
+ * stream to the host, p264pipe_export_last hands the last one of every stream on in device memory, and a sink
+ * (p264pipe_set_sink) receives every round's pictures there while the run goes on.  There is no counterpart in the reference (its decoder is single-stream, single-threaded,
  * p264decoder.c:164-381); the per-stream behaviour is that of p264_decoder_decode.
  *
  * device < 0 runs the parsers only (no GPU is touched): the host-side ceiling of the pipeline.
@@ -14,6 +15,8 @@
 #ifndef P264PIPE_H
 #define P264PIPE_H
 #include <stdint.h>
+#include <stddef.h>
+#include "p264hip.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -42,6 +45,25 @@ int  p264pipe_run(p264pipe *p, int max_pictures, p264pipe_stats_t *stats);
 int  p264pipe_frame_size(p264pipe *p, int *width, int *height);
 int  p264pipe_read_frame(p264pipe *p, int stream, uint8_t *y, int y_stride, uint8_t *u, uint8_t *v, int c_stride);
 int64_t p264pipe_stream_pictures(p264pipe *p, int stream);
+
+/* ---- pictures handed on in device memory (p264hip_export_t, include/p264hip.h: formats, layouts, the RGB arithmetic) ----
+ * The display window of stream 0's SPS (p264parse_crop), for the caller to put into a p264hip_export_t.  -1 before a slice of
+ * stream 0 has been parsed. */
+int  p264pipe_crop(p264pipe *p, int *left, int *top, int *width, int *height);
+/* The last decoded picture of EVERY stream, stream i at dst_dev + i * frame_stride, in one launch; complete when the call
+ * returns.  -1 if a stream has no picture yet, or where p264hip_export_frames refuses. */
+int  p264pipe_export_last(p264pipe *p, const p264hip_export_t *e, void *dst_dev, size_t bytes);
+/* A sink receives every picture of a run, round by round.  Inside p264pipe_run the pictures of round r are exported into
+ * bufs[r % n_bufs] (device memory of the caller, buf_bytes each) right behind the round's p264hip_reconstruct, picture k of the
+ * round at k * frame_stride; fn is called on the thread that runs p264pipe_run, after the wait for the round's marker - the
+ * buffer is complete - with the round's number, its n pictures' streams (ascending; a stream that has ended is absent) and the
+ * buffer.  The buffer is written again n_bufs rounds later: whatever still reads it then (work the callback queued on another
+ * stream) is the caller's to wait for.  Pictures arrive in DECODE order; display-order output (reordering B pictures by their
+ * picture order counts) is not part of this.  A buf_bytes too small for n_streams pictures is refused here, a window that does
+ * not fit the streams' frame at the first round (p264pipe_run fails): never by writing short.  fn = NULL takes the sink away.
+ * The description and the pointers are copied; the buffers are borrowed until the sink is replaced or the pipeline closed. */
+typedef void (*p264pipe_sink_fn)(void *user, int round, int n, const int *streams, void *dev);
+int  p264pipe_set_sink(p264pipe *p, const p264hip_export_t *e, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user);
 void p264pipe_close(p264pipe *p);
 
 #ifdef __cplusplus

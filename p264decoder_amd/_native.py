@@ -83,6 +83,52 @@ class PipeStats(C.Structure):
                 ("submit_seconds", C.c_double), ("rounds", C.c_int), ("streams", C.c_int), ("threads", C.c_int), ("reserved", C.c_int),
                 ("bytes_uploaded", C.c_int64), ("wait_parse_seconds", C.c_double), ("wait_device_seconds", C.c_double)]
 
+class Export(C.Structure):
+    """p264hip_export_t"""
+    _fields_ = [("format", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32),
+                ("crop_left", C.c_int32), ("crop_top", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("pitch", C.c_int32), ("frame_stride", C.c_int64)]
+
+
+FMT_I420, FMT_NV12, FMT_RGB24, FMT_RGBP = range(4)
+MATRIX_BT601, MATRIX_BT709 = 0, 1
+FORMATS = {"i420": FMT_I420, "nv12": FMT_NV12, "rgb24": FMT_RGB24, "rgbp": FMT_RGBP}
+MATRICES = {"bt601": MATRIX_BT601, "bt709": MATRIX_BT709}
+# p264pipe_sink_fn: (user, round, n, streams, dev)
+SINK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p)
+
+
+def export_desc(fmt="i420", crop=None, frame=None, matrix="bt601", full_range=False, pitch=0, frame_stride=0):
+    """A p264hip_export_t: fmt / matrix by name (or number), crop = (left, top, width, height) or None for the whole `frame` =
+    (width, height).  Names that do not exist raise; everything else is the library's to check."""
+    e = Export()
+    e.format = FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+    e.matrix = MATRICES[matrix] if isinstance(matrix, str) else int(matrix)
+    e.full_range = int(full_range)
+    e.crop_left, e.crop_top, e.width, e.height = crop if crop is not None else (0, 0, frame[0], frame[1])
+    e.pitch, e.frame_stride = int(pitch), int(frame_stride)
+    return e
+
+
+def import_torch():
+    """torch, for the calls that hand frames to it (HipReconstructor.export_frames, Pipeline.export_last / set_sink).  A process must
+    hold ONE HIP runtime: a torch wheel brings its own libamdhip64.so, which libp264amd.so shares when torch was imported before
+    the library was loaded - the other way round the process ends up with two runtimes and the second sees no device."""
+    import torch
+    paths = set()
+    try:
+        with open("/proc/self/maps") as f:
+            for line in f:
+                name = line.rstrip("\n").rsplit(None, 1)[-1]
+                if os.path.basename(name).startswith("libamdhip64.so"):
+                    paths.add(os.path.realpath(name))
+    except OSError:
+        pass
+    if len(paths) > 1:
+        raise RuntimeError("two HIP runtimes in this process (%s): import torch before p264decoder_amd loads libp264amd.so" % ", ".join(sorted(paths)))
+    return torch
+
+
 _lib = None
 
 
@@ -102,6 +148,10 @@ def load(path=None):
     for f in ("p264parse_mb_width", "p264parse_mb_height", "p264parse_slots", "p264parse_generation"):
         getattr(lib, f).restype = C.c_int
         getattr(lib, f).argtypes = [C.c_void_p]
+    ip = C.POINTER(C.c_int)
+    if hasattr(lib, "p264parse_crop"):
+        lib.p264parse_crop.restype = C.c_int
+        lib.p264parse_crop.argtypes = [C.c_void_p, ip, ip, ip, ip]
     lib.p264_annexb_next.restype = C.c_int
     lib.p264_annexb_next.argtypes = [C.c_void_p, C.c_int64, i64p, i64p, i64p]
     # ---- p264hip.h
@@ -172,6 +222,13 @@ def load(path=None):
         lib.p264hip_marker.argtypes = [C.c_void_p]
         lib.p264hip_marker_wait.restype = C.c_int
         lib.p264hip_marker_wait.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(lib, "p264hip_export_frames"):
+        lib.p264hip_export_frame_bytes.restype = C.c_int64
+        lib.p264hip_export_frame_bytes.argtypes = [C.POINTER(Export)]
+        lib.p264hip_export_check.restype = C.c_int
+        lib.p264hip_export_check.argtypes = [C.POINTER(Export), C.c_int, C.c_int]
+        lib.p264hip_export_frames.restype = C.c_int
+        lib.p264hip_export_frames.argtypes = [C.c_void_p, ip, ip, C.c_int, C.POINTER(Export), C.c_void_p, C.c_size_t]
     # ---- p264pipe.h
     if hasattr(lib, "p264pipe_open"):
         lib.p264pipe_open.restype = C.c_void_p
@@ -187,6 +244,13 @@ def load(path=None):
         lib.p264pipe_stream_pictures.restype = C.c_int64
         lib.p264pipe_stream_pictures.argtypes = [C.c_void_p, C.c_int]
         lib.p264pipe_close.argtypes = [C.c_void_p]
+    if hasattr(lib, "p264pipe_set_sink"):
+        lib.p264pipe_crop.restype = C.c_int
+        lib.p264pipe_crop.argtypes = [C.c_void_p, ip, ip, ip, ip]
+        lib.p264pipe_export_last.restype = C.c_int
+        lib.p264pipe_export_last.argtypes = [C.c_void_p, C.POINTER(Export), C.c_void_p, C.c_size_t]
+        lib.p264pipe_set_sink.restype = C.c_int
+        lib.p264pipe_set_sink.argtypes = [C.c_void_p, C.POINTER(Export), C.POINTER(C.c_void_p), C.c_int, C.c_size_t, SINK_FN, C.c_void_p]
     if path is None:
         _lib = lib
     return lib

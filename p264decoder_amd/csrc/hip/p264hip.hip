@@ -20,6 +20,7 @@
 #include "kernel_intra.h"
 #include "kernel_t8x8.h"
 #include "kernel_expand.h"
+#include "kernel_export.h"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -132,6 +133,8 @@ struct p264hip_ctx {
     std::vector<int> stream_seen;          // p264hip_reconstruct: batch index + 1 that last named a stream in the current call
     uint8_t *d_planar = nullptr;           // planar staging for p264hip_read_frame / p264hip_write_frame
     std::vector<uint8_t *> planar_pool;    // p264hip_frame_planar_device: planar I420 frames that stay on the device
+    // p264hip_export_frames: the frame index (stream * slots + slot) of every picture of a call, a ring like the batch's
+    uint32_t *h_exp[BATCH_RING] = {}, *d_exp[BATCH_RING] = {}; hipEvent_t exp_free[BATCH_RING] = {}; int exp_cap = 0, exp_ring = 0;
     // tuning knobs, read from the environment ONCE (p264hip_create); 0 = built-in choice
     int tune_mc_wgs = 0, tune_intra_waves = 0, tune_rb_log2 = 0, tune_pics_per_wg = 0, tune_db_waves = 0, tune_bs_fused = -1, tune_odd_single = -1;
     p264hip_launch_info_t last = {};       // what the last p264hip_reconstruct launched
@@ -221,6 +224,11 @@ extern "C" void p264hip_destroy(p264hip_ctx *c)
         if (c->h_batch[i]) (void)hipHostFree(c->h_batch[i]);
         if (c->d_batch[i]) (void)hipFree(c->d_batch[i]);
         if (c->batch_free[i]) (void)hipEventDestroy(c->batch_free[i]);
+    }
+    for (int i = 0; i < BATCH_RING; i++) {
+        if (c->h_exp[i]) (void)hipHostFree(c->h_exp[i]);
+        if (c->d_exp[i]) (void)hipFree(c->d_exp[i]);
+        if (c->exp_free[i]) (void)hipEventDestroy(c->exp_free[i]);
     }
     for (auto &s : c->stamps) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
@@ -522,6 +530,83 @@ extern "C" int p264hip_frame_planar_device(p264hip_ctx *c, int stream, int slot,
     const int rc = tile_convert(c, stream, slot, c->planar_pool[(size_t)index], true);
     if (rc) return rc;
     *dev = c->planar_pool[(size_t)index]; *bytes = sz;
+    return P264HIP_OK;
+}
+
+// ---- frames handed on on the device (include/p264hip.h: p264hip_export_t; kernel_export.h) ----
+extern "C" const char *p264hip_export_why_(const p264hip_export_t *e, int mb_w, int mb_h);     // csrc/host/export_layout.c
+
+// room for the table of a call with n pictures in every buffer of the ring
+static int export_reserve(p264hip_ctx *c, int n)
+{
+    if (n <= c->exp_cap) return 0;
+    HIPCHK(hipStreamSynchronize(c->stream));              // (one wait for every buffer of the ring)
+    const int cap = n + n / 2 + 16;
+    c->exp_cap = 0;
+    for (int i = 0; i < BATCH_RING; i++) {
+        int rc = grow(c, (void **)&c->h_exp[i], nullptr, (size_t)cap * sizeof(uint32_t), 0, true, WAIT_NONE, "the export table");
+        if (rc || (rc = grow(c, (void **)&c->d_exp[i], nullptr, (size_t)cap * sizeof(uint32_t), 0, false, WAIT_NONE, "the export table"))) return rc;
+        if (!c->exp_free[i]) HIPCHK(hipEventCreateWithFlags(&c->exp_free[i], hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->exp_free[i], c->stream));
+    }
+    c->exp_cap = cap;
+    return 0;
+}
+
+// the tiles of a picture (kernel_export.h); the description has passed p264hip_export_check
+static ExportParams export_params(const p264hip_export_t &e, int64_t pitch, int64_t stride)
+{
+    ExportParams p = {};
+    p.x0 = e.crop_left; p.y0 = e.crop_top; p.w = e.width; p.h = e.height;
+    const int s1 = (p.x0 + p.w - 1) >> 4;
+    p.s0 = p.x0 >> 4; p.n_cols = s1 - p.s0 + 1;
+    p.g0 = p.y0 >> 3; p.n_groups = ((p.y0 + p.h - 1) >> 3) - p.g0 + 1;
+    p.cg0 = (p.y0 >> 1) >> 3; p.n_cgroups = ((((p.y0 + p.h) >> 1) - 1) >> 3) - p.cg0 + 1;
+    p.ltx = (p.n_cols + 7) / 8; p.n_ltiles = p.ltx * ((p.n_groups + EXPORT_GROUPS - 1) / EXPORT_GROUPS);
+    if (e.format == P264HIP_FMT_NV12) { p.c0 = p.s0; p.n_ccols = p.n_cols; }
+    if (e.format == P264HIP_FMT_I420) { p.c0 = p.s0 >> 1; p.n_ccols = (s1 >> 1) - p.c0 + 1; }
+    p.ctx = p.n_ccols ? (p.n_ccols + 7) / 8 : 1;
+    p.n_tiles = p.n_ltiles + (p.n_ccols ? p.ctx * ((p.n_cgroups + EXPORT_GROUPS - 1) / EXPORT_GROUPS) : 0);
+    p.pitch = pitch; p.frame_stride = stride;
+    const int32_t *k = export_coefs[e.matrix][e.full_range];
+    p.cy = k[0]; p.yo = e.full_range ? 0 : 16; p.r_cv = k[1]; p.g_cu = k[2]; p.g_cv = k[3]; p.b_cu = k[4];
+    return p;
+}
+
+extern "C" int p264hip_export_frames(p264hip_ctx *c, const int *streams, const int *slots, int n, const p264hip_export_t *e, void *dst, size_t dst_bytes)
+{
+    if (!c || !streams || !slots || !e || !dst || n < 1) return fail(P264HIP_EINVAL, "p264hip_export_frames: bad argument (n %d)", n);
+    if (const char *why = p264hip_export_why_(e, c->g.mb_w, c->g.mb_h))
+        return fail(P264HIP_EINVAL, "p264hip_export_frames: %s (format %d matrix %d full_range %d, window %d,%d %dx%d in a %dx%d frame, pitch %d, frame_stride %lld)", why,
+                    e->format, e->matrix, e->full_range, e->crop_left, e->crop_top, e->width, e->height, c->g.w, c->g.h, e->pitch, (long long)e->frame_stride);
+    for (int i = 0; i < n; i++)
+        if (streams[i] < 0 || streams[i] >= c->n_streams || slots[i] < 0 || slots[i] >= c->slots)
+            return fail(P264HIP_EINVAL, "p264hip_export_frames: picture %d names stream %d slot %d (have %d x %d)", i, streams[i], slots[i], c->n_streams, c->slots);
+    const int64_t bytes = p264hip_export_frame_bytes(e), stride = e->frame_stride ? e->frame_stride : bytes;
+    const int64_t pitch = e->pitch ? e->pitch : (e->format == P264HIP_FMT_RGB24 ? 3 * (int64_t)e->width : (int64_t)e->width);
+    if (n > 1 && stride > (INT64_MAX - bytes) / (n - 1)) return fail(P264HIP_EINVAL, "p264hip_export_frames: %d pictures %lld bytes apart", n, (long long)stride);
+    const uint64_t need = (uint64_t)(n - 1) * (uint64_t)stride + (uint64_t)bytes;
+    if ((uint64_t)dst_bytes < need) return fail(P264HIP_EINVAL, "p264hip_export_frames: %d pictures need %llu bytes, dst has %zu", n, (unsigned long long)need, dst_bytes);
+    HIPCHK(hipSetDevice(c->device));
+    int rc = export_reserve(c, n);
+    if (rc) return rc;
+    const int r = c->exp_ring; c->exp_ring = (c->exp_ring + 1) % BATCH_RING;
+    HIPCHK(hipEventSynchronize(c->exp_free[r]));              // the copy that last used this staging buffer is done
+    for (int i = 0; i < n; i++) c->h_exp[r][i] = (uint32_t)(streams[i] * c->slots + slots[i]);
+    HIPCHK(hipMemcpyAsync(c->d_exp[r], c->h_exp[r], (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->exp_free[r], c->stream));
+    const ExportParams p = export_params(*e, pitch, stride);
+    const unsigned gx = (unsigned)((p.n_tiles + EXPORT_THREADS / WAVE - 1) / (EXPORT_THREADS / WAVE));
+    for (int base = 0; base < n; base += 65535) {            // (a grid's second dimension ends at 65535)
+        const dim3 grid(gx, (unsigned)(n - base < 65535 ? n - base : 65535));
+        switch (e->format) {
+        case P264HIP_FMT_I420:  hipLaunchKernelGGL(k_export_i420, grid, dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p); break;
+        case P264HIP_FMT_NV12:  hipLaunchKernelGGL(k_export_nv12, grid, dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p); break;
+        case P264HIP_FMT_RGB24: hipLaunchKernelGGL(k_export_rgb24, grid, dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p); break;
+        default:                hipLaunchKernelGGL(k_export_rgbp, grid, dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p); break;
+        }
+    }
+    HIPCHK(hipGetLastError());
     return P264HIP_OK;
 }
 

@@ -208,7 +208,7 @@ static int parse_sps(p264parse *p, bitrd_t *b)
     s->frame_mbs_only = (int)br_u1(b);
     if (!s->frame_mbs_only) br_u1(b);
     s->direct_8x8_inference = (int)br_u1(b);
-    if (br_u1(b)) for (int i = 0; i < 4; i++) s->crop[i] = (int)br_ue(b);   /* parsed, never applied (A-Q1) */
+    if (br_u1(b)) for (int i = 0; i < 4; i++) s->crop[i] = (int)br_ue(b);   /* left, right, top, bottom: never applied to what the parser delivers (A-Q1), reported by p264parse_crop */
     br_u1(b);                                       /* vui_parameters_present: not parsed, like set.c:136-144 */
     if (br_eof(b)) { ERR(p, "incomplete SPS"); return -1; }
     /* untrusted input: H.264 7.4.2.1 ranges (the slice header reads fields of these widths; sizes drive every allocation) */
@@ -1721,6 +1721,22 @@ int p264parse_mb_width(const p264parse *p)   { return p ? p->mb_w : 0; }
 int p264parse_mb_height(const p264parse *p)  { return p ? p->mb_h : 0; }
 int p264parse_slots(const p264parse *p)      { return p ? p->slots : 0; }
 int p264parse_generation(const p264parse *p) { return p ? p->generation : 0; }
+
+/* the display window of the active SPS (H.264 7.4.2.1.1, 4:2:0 frame macroblocks: CropUnitX = CropUnitY = 2) */
+int p264parse_crop(const p264parse *p, int *left, int *top, int *width, int *height)
+{
+    if (!p || p->active_sps < 0 || !p->mb_w) return -1;
+    const sps_t *s = &p->sps[p->active_sps];
+    int64_t c[4];
+    for (int i = 0; i < 4; i++) c[i] = 2 * (int64_t)(uint32_t)s->crop[i];
+    const int64_t w = (int64_t)s->mb_w * 16 - c[0] - c[1], h = (int64_t)s->mb_h * 16 - c[2] - c[3];
+    if (w < 1 || h < 1) return -1;                  /* the offsets leave no sample */
+    if (left) *left = (int)c[0];
+    if (top) *top = (int)c[2];
+    if (width) *width = (int)w;
+    if (height) *height = (int)h;
+    return 0;
+}
 
 /* first index >= from with buf[i..i+2] == 00 00 01, or an index with i + 3 > size; the scan hops between zero bytes */
 static int64_t annexb_find(const uint8_t *buf, int64_t size, int64_t from)

@@ -49,6 +49,8 @@ struct p264pipe {
     int failed_in_round[2];              /* a task of the round failed (under mu) */
     const p264hip_picture_t **round_pic[2];  /* [round parity][stream]: the picture a round's task produced, or NULL */
     double parse_seconds;
+    /* the sink (p264pipe_set_sink): every round's pictures exported into the caller's device buffers */
+    p264hip_export_t sink_e; void **sink_bufs; int sink_n_bufs; size_t sink_bytes; p264pipe_sink_fn sink_fn; void *sink_user;
 };
 
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
@@ -211,8 +213,9 @@ int p264pipe_run(p264pipe *p, int max_pictures, p264pipe_stats_t *stats)
     for (int i = 0; i < p->n_streams; i++) if (!p->st[i].in) { fprintf(stderr, "p264pipe_run: stream %d has no input\n", i); return -1; }
     p->max_pictures = max_pictures; p->parse_seconds = 0;
     int *ids = (int *)malloc(sizeof(int) * (size_t)p->n_streams), *sts = (int *)malloc(sizeof(int) * (size_t)p->n_streams);
+    int *dsts = (int *)malloc(sizeof(int) * (size_t)p->n_streams);
     const p264hip_picture_t **pics = (const p264hip_picture_t **)malloc(sizeof(void *) * (size_t)p->n_streams);
-    if (!ids || !sts || !pics) { free(ids); free(sts); free(pics); return -1; }
+    if (!ids || !sts || !dsts || !pics) { free(ids); free(sts); free(dsts); free(pics); return -1; }
     int rounds = 0, rc = 0;
     int64_t pictures = 0, uploaded = 0;
     double submit = 0, wait_parse = 0, wait_gpu = 0;          /* (the main thread's waits: P264AMD_PIPE_DEBUG=1 prints them) */
@@ -224,7 +227,7 @@ int p264pipe_run(p264pipe *p, int max_pictures, p264pipe_stats_t *stats)
         for (int i = 0; i < p->n_streams; i++) {
             pstream_t *s = &p->st[i];
             const p264hip_picture_t *pic = p->round_pic[r & 1][i];
-            if (pic) { pics[n] = pic; sts[n] = i; ids[n] = i * 2 + (r & 1); s->last_slot = pic->dst_slot; n++; }
+            if (pic) { pics[n] = pic; sts[n] = i; ids[n] = i * 2 + (r & 1); dsts[n] = s->last_slot = pic->dst_slot; n++; }
         }
         if (n == 0 || rc) break;
         rounds++; pictures += n;
@@ -242,6 +245,8 @@ int p264pipe_run(p264pipe *p, int max_pictures, p264pipe_stats_t *stats)
                 else uploaded += (int64_t)p->mb_w * p->mb_h * (16 + 64 + 4 + 16) + (int64_t)pics[k]->n_coef_blocks * 32;
             }
             if (!rc && p264hip_reconstruct(p->ctx, ids, sts, n)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
+            void *sink = p->sink_fn ? p->sink_bufs[r % p->sink_n_bufs] : NULL;       /* the round's pictures, behind its kernels */
+            if (!rc && sink && p264hip_export_frames(p->ctx, sts, dsts, n, &p->sink_e, sink, p->sink_bytes)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
             int marker = -1;
             if (!rc) { marker = p264hip_marker(p->ctx); if (marker < 0) rc = -1; }
             submit += now_s() - s0;
@@ -250,6 +255,7 @@ int p264pipe_run(p264pipe *p, int max_pictures, p264pipe_stats_t *stats)
             const double w0 = now_s();
             if (p264hip_marker_wait(p->ctx, marker)) { rc = -1; break; }
             wait_gpu += now_s() - w0;
+            if (sink) p->sink_fn(p->sink_user, r, n, sts, sink);
         }
         rounds_done(p, r);
     }
@@ -266,7 +272,7 @@ int p264pipe_run(p264pipe *p, int max_pictures, p264pipe_stats_t *stats)
         stats->rounds = rounds; stats->streams = p->n_streams; stats->threads = p->n_threads; stats->bytes_uploaded = uploaded;
         for (int i = 0; i < p->n_streams; i++) stats->bytes += p->st[i].pos;
     }
-    free(ids); free(sts); free(pics);
+    free(ids); free(sts); free(dsts); free(pics);
     return rc;
 }
 
@@ -284,6 +290,51 @@ int p264pipe_read_frame(p264pipe *p, int stream, uint8_t *y, int y_stride, uint8
     return p264hip_read_frame(p->ctx, stream, p->st[stream].last_slot, y, y_stride, u, v, c_stride) ? -1 : 0;
 }
 
+int p264pipe_crop(p264pipe *p, int *left, int *top, int *width, int *height)
+{
+    return p ? p264parse_crop(p->st[0].parser, left, top, width, height) : -1;
+}
+
+int p264pipe_export_last(p264pipe *p, const p264hip_export_t *e, void *dst_dev, size_t bytes)
+{
+    if (!p || !p->ctx || !e || !dst_dev) return -1;
+    int *sts = (int *)malloc(sizeof(int) * 2 * (size_t)p->n_streams);
+    if (!sts) return -1;
+    int rc = 0;
+    for (int i = 0; i < p->n_streams; i++) {
+        if (p->st[i].last_slot < 0) rc = -1;
+        sts[i] = i; sts[p->n_streams + i] = p->st[i].last_slot;
+    }
+    if (!rc && (p264hip_export_frames(p->ctx, sts, sts + p->n_streams, p->n_streams, e, dst_dev, bytes) || p264hip_sync(p->ctx))) {
+        fprintf(stderr, "p264pipe_export_last: %s\n", p264hip_last_error()); rc = -1;
+    }
+    free(sts);
+    return rc;
+}
+
+int p264pipe_set_sink(p264pipe *p, const p264hip_export_t *e, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user)
+{
+    if (!p) return -1;
+    if (!fn) { free(p->sink_bufs); p->sink_bufs = NULL; p->sink_fn = NULL; p->sink_n_bufs = 0; return 0; }
+    if (p->device < 0 || !e || !bufs || n_bufs < 1) return -1;
+    for (int i = 0; i < n_bufs; i++) if (!bufs[i]) return -1;
+    /* every round may bring a picture of every stream (the frame itself is known at the first round: p264hip_export_frames checks the window) */
+    const int64_t bytes = p264hip_export_frame_bytes(e);
+    if (bytes < 0 || (p->mb_w && p264hip_export_check(e, p->mb_w, p->mb_h)) || e->frame_stride < 0 || (e->frame_stride && e->frame_stride < bytes)) {
+        fprintf(stderr, "p264pipe_set_sink: bad export description\n"); return -1;
+    }
+    const int64_t stride = e->frame_stride ? e->frame_stride : bytes;
+    if (stride > (INT64_MAX - bytes) / p->n_streams || (uint64_t)buf_bytes < (uint64_t)(p->n_streams - 1) * (uint64_t)stride + (uint64_t)bytes) {
+        fprintf(stderr, "p264pipe_set_sink: %d pictures %lld bytes apart do not fit %zu bytes\n", p->n_streams, (long long)stride, buf_bytes); return -1;
+    }
+    void **copy = (void **)malloc(sizeof(void *) * (size_t)n_bufs);
+    if (!copy) return -1;
+    memcpy(copy, bufs, sizeof(void *) * (size_t)n_bufs);
+    free(p->sink_bufs);
+    p->sink_e = *e; p->sink_bufs = copy; p->sink_n_bufs = n_bufs; p->sink_bytes = buf_bytes; p->sink_fn = fn; p->sink_user = user;
+    return 0;
+}
+
 int64_t p264pipe_stream_pictures(p264pipe *p, int stream)
 {
     return (p && stream >= 0 && stream < p->n_streams) ? p->st[stream].pictures : -1;
@@ -299,5 +350,6 @@ void p264pipe_close(p264pipe *p)
     if (p->ctx) p264hip_destroy(p->ctx);
     pthread_mutex_destroy(&p->mu); pthread_cond_destroy(&p->go); pthread_cond_destroy(&p->idle); pthread_cond_destroy(&p->turn);
     free(p->parsed); free((void *)p->round_pic[0]); free((void *)p->round_pic[1]);
+    free(p->sink_bufs);
     free(p->st); free(p->threads); free(p);
 }

@@ -15,13 +15,18 @@ class Pipeline:
         self.h = self.lib.p264pipe_open(device, len(streams), threads)
         if not self.h:
             raise RuntimeError("p264pipe_open failed (no HIP device? the reconstruction has no CPU fallback; device=-1 parses only)")
+        self._sink, self._sink_error = None, None
         for i, b in enumerate(self._bufs):
             if self.lib.p264pipe_set_input(self.h, i, b, len(b)):
                 raise RuntimeError("p264pipe_set_input(%d) failed" % i)
 
     def run(self, max_pictures=0):
         st = N.PipeStats()
-        if self.lib.p264pipe_run(self.h, max_pictures, C.byref(st)):
+        self._sink_error = None
+        rc = self.lib.p264pipe_run(self.h, max_pictures, C.byref(st))
+        if self._sink_error is not None:
+            raise self._sink_error
+        if rc:
             raise RuntimeError("p264pipe_run failed")
         return {f: getattr(st, f) for f, _ in st._fields_}
 
@@ -36,6 +41,78 @@ class Pipeline:
         if self.lib.p264pipe_read_frame(self.h, stream, y.ctypes.data, w.value, u.ctypes.data, v.ctypes.data, w.value // 2):
             raise RuntimeError("p264pipe_read_frame(%d) failed" % stream)
         return y, u, v
+
+    def crop(self):
+        """(left, top, width, height): the display window of stream 0's SPS (p264pipe_crop); None before its first slice is parsed."""
+        v = [C.c_int() for _ in range(4)]
+        if self.lib.p264pipe_crop(self.h, *[C.byref(x) for x in v]):
+            return None
+        return tuple(x.value for x in v)
+
+    def _window(self, crop):
+        """crop, or the display window: the pipeline's once it has parsed a slice, else read from stream 0's headers here"""
+        if crop is None:
+            crop = self.crop()
+        if crop is None:
+            from .recon import Parser
+            ps = Parser(lib=self.lib)
+            try:
+                ps.parse_stream(bytes(self._bufs[0]), limit=1)
+                crop = ps.crop
+            finally:
+                ps.close()
+        if crop is None:
+            raise RuntimeError("stream 0 has no picture: no display window")
+        return crop
+
+    def export_last(self, fmt="i420", crop=None, matrix="bt601", full_range=False, pitch=0, out=None):
+        """The last picture of every stream in device memory, stream i first to last (p264pipe_export_last); `out` and the result as
+        HipReconstructor.export_frames has them."""
+        n = len(self._bufs)
+        crop = self._window(crop)
+        e = N.export_desc(fmt, crop, None, matrix, full_range, pitch)
+        per = self.lib.p264hip_export_frame_bytes(C.byref(e))
+        if per < 0:
+            raise RuntimeError("export_last: p264hip_export_frame_bytes refuses the description")
+        if out is None:
+            torch = N.import_torch()
+            W, H = e.width, e.height
+            shape = (n, H * 3 // 2, W) if e.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if e.format == N.FMT_RGB24 else (n, 3, H, W)
+            out = torch.empty(shape if not pitch else (n, per), dtype=torch.uint8, device="cuda")
+        ptr, cap = out if isinstance(out, tuple) else (out.data_ptr(), out.numel())
+        if self.lib.p264pipe_export_last(self.h, C.byref(e), ptr, cap):
+            raise RuntimeError("p264pipe_export_last failed: %s" % self.lib.p264hip_last_error().decode())
+        return out
+
+    def set_sink(self, fmt, callback, depth=2, crop=None, matrix="bt601", full_range=False, pitch=0, buffers=None):
+        """callback(round, streams, dev, bytes) for every round of run(): `streams` lists the round's streams, picture k of the round
+        lies at dev + k * bytes in device memory, in format `fmt`, cropped to `crop` (None: the display window of stream 0).  `depth`
+        buffers take turns: one is written again `depth` rounds later.  Pictures arrive in decode order.  buffers: (pointer, bytes)
+        pairs of the caller's device memory; None allocates torch tensors.  The wrapper keeps callback and buffers alive."""
+        n = len(self._bufs)
+        e = N.export_desc(fmt, self._window(crop), None, matrix, full_range, pitch)
+        per = self.lib.p264hip_export_frame_bytes(C.byref(e))
+        if per < 0:
+            raise RuntimeError("set_sink: p264hip_export_frame_bytes refuses the description")
+        keep = None
+        if buffers is None:
+            torch = N.import_torch()
+            keep = [torch.empty(n * per, dtype=torch.uint8, device="cuda") for _ in range(depth)]
+            buffers = [(t.data_ptr(), t.numel()) for t in keep]
+        ptrs = (C.c_void_p * len(buffers))(*[b[0] for b in buffers])
+        cap = min(b[1] for b in buffers)
+
+        def trampoline(user, rnd, k, streams, dev):
+            try:                                          # (an exception cannot cross the C frames: run() raises it)
+                if self._sink_error is None:
+                    callback(rnd, [streams[i] for i in range(k)], dev, per)
+            except BaseException as exc:
+                self._sink_error = exc
+        fn = N.SINK_FN(trampoline)
+        if self.lib.p264pipe_set_sink(self.h, C.byref(e), ptrs, len(buffers), cap, fn, None):
+            raise RuntimeError("p264pipe_set_sink refused (a buffer too small for %d pictures of %d bytes?)" % (n, per))
+        self._sink = (fn, keep, ptrs, callback)
+        return per
 
     def close(self):
         if self.h:

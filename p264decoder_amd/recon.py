@@ -100,6 +100,14 @@ class Parser:
     def slots(self):
         return self.lib.p264parse_slots(self.h)
 
+    @property
+    def crop(self):
+        """(left, top, width, height) of the active SPS's display window in luma samples (p264parse_crop); None before the first slice."""
+        v = [C.c_int() for _ in range(4)]
+        if self.lib.p264parse_crop(self.h, *[C.byref(x) for x in v]):
+            return None
+        return tuple(x.value for x in v)
+
     def parse_stream(self, data, limit=None):
         """All pictures of an Annex-B byte string."""
         out = []
@@ -207,6 +215,40 @@ class HipReconstructor:
         dev, n = C.c_void_p(), C.c_size_t()
         self._chk(self.lib.p264hip_frame_planar_device(self.h, stream, slot, index, C.byref(dev), C.byref(n)), "p264hip_frame_planar_device")
         return dev.value, n.value
+
+    def export_frames(self, streams, slots, fmt="i420", crop=None, matrix="bt601", full_range=False, pitch=0, out=None, sync=True,
+                      frame_stride=0):
+        """Frames slots[i] of streams[i] into device memory, cropped to crop = (left, top, width, height) (None: the whole frame), as
+        "i420" / "nv12" / "rgb24" / "rgbp" (p264hip_export_frames: one launch, queued behind every reconstruct before it).
+        out: a torch uint8 tensor on the device (filled in place, from its first byte), a (device pointer, bytes) pair, or None -
+        a new torch tensor (n, H*3//2, W) for I420 / NV12, (n, H, W, 3) for RGB24, (n, 3, H, W) for RGBP at the tight pitch, (n, bytes)
+        otherwise.  Returns the tensor (the pair as given).  sync=False leaves the wait to sync() or a marker."""
+        n = len(streams)
+        e = N.export_desc(fmt, crop, (self.mb_w * 16, self.mb_h * 16), matrix, full_range, pitch, frame_stride)
+        if len(slots) != n:
+            raise P264Error("export_frames: %d streams, %d slots" % (n, len(slots)))
+        if out is None:
+            torch = N.import_torch()                      # only here: the module imports without torch or a GPU
+            per = self.lib.p264hip_export_frame_bytes(C.byref(e))
+            if per < 0:
+                raise P264Error("export_frames: p264hip_export_frame_bytes refuses the description")
+            W, H = e.width, e.height
+            shape = (n, H * 3 // 2, W) if e.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if e.format == N.FMT_RGB24 else (n, 3, H, W)
+            out = torch.empty(shape if not pitch and not frame_stride else (n, e.frame_stride or per), dtype=torch.uint8, device="cuda")
+        if isinstance(out, tuple):
+            ptr, cap = out
+        else:
+            if not (out.is_cuda and out.is_contiguous() and out.element_size() == 1):
+                raise P264Error("export_frames: out must be a contiguous uint8 tensor on the device")
+            torch = N.import_torch()
+            torch.cuda.current_stream(out.device).synchronize()     # (whatever torch still has queued on the tensor: the context has its own stream)
+            ptr, cap = out.data_ptr(), out.numel()
+        a = (C.c_int * max(n, 1))(*streams)
+        b = (C.c_int * max(n, 1))(*slots)
+        self._chk(self.lib.p264hip_export_frames(self.h, a, b, n, C.byref(e), ptr, cap), "p264hip_export_frames")
+        if sync:
+            self.sync()
+        return out
 
     def clone_picture(self, dst, src):
         self._chk(self.lib.p264hip_clone_picture(self.h, dst, src), "p264hip_clone_picture")

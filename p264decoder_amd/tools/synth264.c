@@ -1007,7 +1007,7 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
 int main(int argc, char **argv)
 {
     if (argc < 2) { fprintf(stderr, "usage: synth264 out.264 [--mbw N --mbh N --frames N --gop N --seed N --intra-only ...]\n"); return 2; }
-    int frames = 30, gop = 30, intra_only = 0, crop_bottom = 0;
+    int frames = 30, gop = 30, intra_only = 0, crop_bottom = 0, crop[4] = { 0, 0, 0, 0 }, have_crop = 0;
     uint64_t seed = 1;
     W = 22; H = 18;
     for (int i = 2; i < argc; i++) {
@@ -1024,6 +1024,10 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--mvmax")) { opt_mvmax = v; i++; }
         else if (!strcmp(a, "--cqo")) { opt_cqo = v; i++; }
         else if (!strcmp(a, "--crop-bottom")) { crop_bottom = v; i++; }
+        else if (!strcmp(a, "--crop")) {                /* left right top bottom, in cropping units (two luma samples) */
+            for (int k = 0; k < 4; k++) crop[k] = i + 1 + k < argc ? atoi(argv[i + 1 + k]) : 0;
+            have_crop = 1; i += 4;
+        }
         else if (!strcmp(a, "--intra-only")) intra_only = 1;
         else if (!strcmp(a, "--nodeblock")) opt_deblock = 0;
         else if (!strcmp(a, "--refs")) { opt_refs = v; i++; }
@@ -1090,7 +1094,8 @@ int main(int argc, char **argv)
         bw_ue(&b, (uint32_t)opt_refs); bw_put(&b, 1, 0);    /* num_ref_frames */
         bw_ue(&b, (uint32_t)(W - 1)); bw_ue(&b, (uint32_t)(H - 1));
         bw_put(&b, 1, 1); bw_put(&b, 1, (uint32_t)(opt_bframes ? opt_d8inf : 1));    /* frame_mbs_only, direct_8x8_inference */
-        if (crop_bottom) { bw_put(&b, 1, 1); bw_ue(&b, 0); bw_ue(&b, 0); bw_ue(&b, 0); bw_ue(&b, (uint32_t)crop_bottom); }
+        if (have_crop) { bw_put(&b, 1, 1); for (int k = 0; k < 4; k++) bw_ue(&b, (uint32_t)crop[k]); }
+        else if (crop_bottom) { bw_put(&b, 1, 1); bw_ue(&b, 0); bw_ue(&b, 0); bw_ue(&b, 0); bw_ue(&b, (uint32_t)crop_bottom); }
         else bw_put(&b, 1, 0);
         bw_put(&b, 1, 0);
         bw_trailing(&b);
