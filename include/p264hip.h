@@ -85,6 +85,22 @@ enum {
  * neither 0x0 nor 0xF, and one in a picture whose descriptor says 0. */
 #define P264_MB_T8X8 0x04
 
+/* Intra 8x8 prediction (High profile, H.264 8.3.2: an I_NxN macroblock with transform_size_8x8_flag 1): bit 3 of intra_modes.
+ * Legal only on records of mb_type P264_MB_I4x4 - the type stays I4x4, so availability, constrained intra prediction, the work
+ * lists and P264_MB_IS_INTRA see what they see on any Intra4x4 record - in pictures whose descriptor carries P264_T8X8_INTRA in
+ * transform_8x8, and never together with P264_MB_T8X8.  On a flagged record
+ *   the luma bits of coef_mask and the luma entries are laid out as on a P264_MB_T8X8 record (whole nibbles; four consecutive
+ *   entries per coded 8x8 block, its 64 levels in the 8x8 frame zig-zag order);
+ *   i4modes[4k .. 4k+3] all hold Intra8x8PredMode of 8x8 block k (decode-order indices 4k .. 4k+3 are quadrant k), so that the
+ *   mode predictor of a neighbouring Intra4x4 block (8.3.1.1) and the compact format read them as they read any other;
+ *   chroma, cbp, qp, avail, edges and flags are as on any Intra4x4 record.
+ * The loop filter leaves luma edges 1 and 3 alone, as for P264_MB_T8X8.  Every road into an input slot (the list at
+ * P264_IPCM_COEF_MASK) rejects a flagged record that is not I4x4, one whose luma nibbles are neither 0x0 nor 0xF, one that also
+ * carries P264_MB_T8X8 and one in a picture whose descriptor lacks P264_T8X8_INTRA. */
+#define P264_MB_I8X8 0x08
+/* bits of p264hip_picture_t.transform_8x8 */
+#define P264_T8X8_INTRA 2
+
 /* One per macroblock, 16 bytes.  Everything is as parsed (before dequantisation). */
 typedef struct p264hip_mb {
     uint8_t  mb_type;      /* P264_MB_* */
@@ -170,8 +186,10 @@ typedef struct p264hip_picture {
     int32_t             explicit_wp;
     int32_t             wp_log2_denom[2];                                      /* luma, chroma */
     int16_t             wp[2][P264HIP_MAX_REFS][3][2];                         /* [list][ref_idx][Y, Cb, Cr][weight, offset] */
-    /* ---- the 8x8 transform (P264_MB_T8X8 above).  != 0: inter records of the picture may carry the flag, and a batch that holds
-     * the picture launches the kernel that adds their luma residual (k_t8x8, between motion compensation and intra prediction) */
+    /* ---- the 8x8 transform, a bit set.  Bit 1 (P264_T8X8_INTRA): Intra4x4 records of the picture may carry P264_MB_I8X8, and a
+     * batch that holds the picture launches the Intra 8x8 instances of the intra kernels (k_intra_i8 / k_intra_sparse_i8).  Any
+     * other bit: inter records of the picture may carry P264_MB_T8X8, and a batch that holds the picture launches the kernel that
+     * adds their luma residual (k_t8x8, between motion compensation and intra prediction).  0 and 1 mean what they always meant. */
     int32_t             transform_8x8;
 } p264hip_picture_t;
 
@@ -226,10 +244,12 @@ int  p264hip_input_layout(const p264hip_picture_t *desc, p264hip_input_layout_t 
 int  p264hip_wp_check(const p264hip_picture_t *desc);
 /* the index of the first of n_mb records whose coefficient blocks do not lie inside coefs[n_coef_blocks], which is an I_PCM
  * record without its twelve-block mask, or which carries P264_MB_T8X8 without being inter or with a luma nibble that is neither
- * 0x0 nor 0xF; -1 where there is none (every upload path checks it, device producers' blocks on the device) */
+ * 0x0 nor 0xF, or which carries P264_MB_I8X8 without being I4x4, with such a nibble or together with P264_MB_T8X8; -1 where there is
+ * none (every upload path checks it, device producers' blocks on the device) */
 int64_t p264hip_records_check(const p264hip_mb_t *mb, size_t n_mb, uint32_t n_coef_blocks);
 /* the same for the records of a picture with this descriptor: also the first record that carries P264_MB_T8X8 where
- * desc->transform_8x8 is 0 (what the roads that check on the host run) */
+ * desc->transform_8x8 has no bit other than P264_T8X8_INTRA, or P264_MB_I8X8 where it lacks that bit (what the roads that check on
+ * the host run) */
 int64_t p264hip_records_check_pic(const p264hip_picture_t *desc, const p264hip_mb_t *mb);
 /* host side, no device involved: the picture's arrays copied into `dst` (cap >= layout.bytes) in that layout; the
  * macroblock records are checked as p264hip_upload checks them (coefficient ranges inside coefs[]).  Returns the bytes used
@@ -385,7 +405,8 @@ typedef struct p264hip_launch_info {
     int32_t deblock_pics_per_wg, deblock_rb_log2, deblock_waves, deblock_wgs;
     int32_t deblock_odd_single;    /* 1: odd pictures per workgroup - pairs in bands of 4 rows, the last picture alone in bands of 8 */
     int32_t t8x8_wgs;              /* k_t8x8: workgroups of the launch (0: no picture of the batch has transform_8x8, no launch) */
-    int32_t reserved[5];
+    int32_t reserved[4];
+    int32_t intra_i8;              /* 1: the intra launch ran the Intra 8x8 instances (a picture of the batch has P264_T8X8_INTRA) */
 } p264hip_launch_info_t;
 int  p264hip_last_launch(p264hip_ctx *ctx, p264hip_launch_info_t *out);
 

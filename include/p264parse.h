@@ -24,6 +24,10 @@ typedef struct p264parse p264parse;
 
 enum {
     P264PARSE_OPT_QUIET  = 1,   /* do not print SPS/PPS/size lines to stderr (the reference prints them) */
+    P264PARSE_OPT_INTRA8X8 = 4, /* hand out Intra 8x8 macroblocks (I_NxN with transform_size_8x8_flag 1, High profile) as I4x4 records with
+                                   P264_MB_I8X8, in pictures whose descriptor carries P264_T8X8_INTRA (include/p264hip.h).  Off by default:
+                                   only the owner of the backend that takes the pictures can say whether it knows the record; without
+                                   the option such a macroblock ends the slice with "Intra 8x8 prediction unsupported" */
     P264PARSE_OPT_STRICT = 2    /* H.264-conformant QP accumulation also for Baseline CAVLC streams, where the default is the
                                    reference's rule (decoder/macroblock.c:568, core/macroblock.c:1247-1252; SURVEY A-Q2).
                                    CABAC, B slices and every profile but Baseline - none of which the reference decodes -

@@ -20,6 +20,8 @@ COEF_LUMA_DC = 1 << 24
 COEF_CHROMA_DC = 1 << 25
 AVAIL_LEFT, AVAIL_TOP, AVAIL_TOPRIGHT, AVAIL_TOPLEFT = 1, 2, 4, 8
 EDGE_LEFT, EDGE_TOP, EDGE_INNER = 1, 2, 4
+MB_I8X8 = 0x08          # bit of MbInfo.intra_modes: an I4x4 record predicted as Intra 8x8 (luma coded as 8x8 blocks)
+T8X8_INTRA = 2          # bit of Picture.transform_8x8: Intra4x4 records may carry MB_I8X8
 MB_T8X8 = 0x04          # bit of MbInfo.intra_modes: the inter macroblock's luma residual is coded as 8x8 blocks
 
 
@@ -55,7 +57,7 @@ assert C.sizeof(MbInfo) == 16
 class LaunchInfo(C.Structure):
     """p264hip_launch_info_t"""
     _fields_ = [(n, C.c_int32) for n in ("pictures", "compute_units", "mc_wgs_per_picture", "intra_waves", "edge_info_fused",
-                                         "deblock_pics_per_wg", "deblock_rb_log2", "deblock_waves", "deblock_wgs", "deblock_odd_single", "t8x8_wgs")] + [("reserved", C.c_int32 * 5)]
+                                         "deblock_pics_per_wg", "deblock_rb_log2", "deblock_waves", "deblock_wgs", "deblock_odd_single", "t8x8_wgs")] + [("reserved", C.c_int32 * 4), ("intra_i8", C.c_int32)]
 
 
 BUILD_TIMING = 1

@@ -224,14 +224,14 @@ __device__ __forceinline__ uint4 edge_info_of(const PicDev *pd, const Geom &g, i
                 word[dir] |= (uint32_t)bS << (2 * (4 * e + i));
             }
 
-    // a macroblock with the 8x8 transform: its inner luma edges 1 and 3 are no transform edges (H.264 8.7), strength 0 in both
+    // a macroblock with the 8x8 transform (inter: P264_MB_T8X8, Intra 8x8: P264_MB_I8X8): its inner luma edges 1 and 3 are no transform edges (H.264 8.7), strength 0 in both
     // directions (chroma reads the strengths of edges 0 and 2)
     // (T8X8 = false, the edge-info role of the 64-register k_intra_sparse build: the mask cost it four spilled registers whichever
     // way the flag was carried - bits 8-15 of qp_word included -, so batches with such pictures take k_deblock_bs: p264hip.hip)
     if (T8X8) {
         // (the words as they stand first: the mask is two instructions here, not a select folded into each of the thirty-two segments above)
         asm volatile("" : "+v"(word[0]), "+v"(word[1]));
-        if ((rec.x >> 24) & P264_MB_T8X8) { word[0] &= 0x00ff00ffu; word[1] &= 0x00ff00ffu; }
+        if ((rec.x >> 24) & (P264_MB_T8X8 | P264_MB_I8X8)) { word[0] &= 0x00ff00ffu; word[1] &= 0x00ff00ffu; }
     }
 
     // ---- averaged QPs per edge class (deblock_edge, core/frame.c:472-488,593-601) ----

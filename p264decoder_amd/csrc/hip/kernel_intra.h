@@ -26,6 +26,7 @@
 #include "device_common.h"
 #include "wavefront_sync.h"
 #include "kernel_deblock.h"             // (edge_info_of: the edge-info role of k_intra_sparse)
+#include "kernel_t8x8.h"                // (c_scan8x8, t8_scale, t8_idct1d: the residual of Intra 8x8 macroblocks)
 
 #define IT_STRIDE 24               // luma tile: row -1..15, byte 3 = left column, 4..19 = MB, 20..23 = top-right
 #define CT_STRIDE 12               // chroma tile (one per plane): byte 3 = left column, 4..11 = MB
@@ -123,12 +124,58 @@ __device__ __forceinline__ uint32_t add_res4(uint32_t px, uint32_t r01, uint32_t
     return perm(as_u32(hi), as_u32(lo), 0x06040200u);
 }
 
+// Intra 8x8 prediction (H.264 8.3.2.2; the I8 instances only) over the FILTERED edge of the 8x8 block, kept per group in LDS:
+// E[0..26] = l7 l7 l6 .. l0 lt t0 .. t15 t15 (p'[-1, 7] .. p'[-1, 0], p'[-1, -1], p'[0, -1] .. p'[15, -1]; the ends replicated).  As for
+// 4x4 blocks every mode is copy / two-tap / three-tap at an index c that follows from (mode, x, y), and all three are ONE formula
+// over three places; the places come out of a 9 x 64 table in LDS, filled from this function when the kernel starts.
+__device__ __forceinline__ void pred8x8_where(int mode, int x, int y, int &c, int &kind)
+{
+    switch (mode) {
+    case 0: c = 10 + x; kind = P4_COPY; break;                                                  // vertical, 8.3.2.2.2
+    case 1: c = 8 - y; kind = P4_COPY; break;                                                   // horizontal
+    case 2: c = 1; kind = P4_DC; break;
+    case 3: c = 11 + x + y; kind = P4_F3; break;                                                // diagonal down-left (x = y = 7: E[26] = E[25])
+    case 4: c = 9 + x - y; kind = P4_F3; break;                                                 // diagonal down-right
+    case 5: { int z = 2 * x - y;                                                                // vertical-right
+              c = z >= 0 ? 9 + x - (y >> 1) : z == -1 ? 9 : 10 - y + 2 * x; kind = (z >= 0 && !(z & 1)) ? P4_F2 : P4_F3; break; }
+    case 6: { int z = 2 * y - x, k = y - (x >> 1);                                              // horizontal-down
+              c = z >= 0 ? ((z & 1) ? 9 - k : 8 - k) : z == -1 ? 9 : 8 + x - 2 * y; kind = (z >= 0 && !(z & 1)) ? P4_F2 : P4_F3; break; }
+    case 7: { int k = x + (y >> 1); c = (y & 1) ? 11 + k : 10 + k; kind = (y & 1) ? P4_F3 : P4_F2; break; }   // vertical-left
+    default: { int z = x + 2 * y;                                                               // 8: horizontal-up (z = 13: E[0] = E[1])
+              c = z >= 13 ? 1 : 7 - y - (x >> 1); kind = z > 13 ? P4_COPY : (z == 13 || (z & 1)) ? P4_F3 : P4_F2; break; }
+    }
+}
+#define INTRA_LUT8_ENTRIES (9 * 64)        // uint32: index of A | index of B << 8 | index of D << 16 | DC << 24
+__device__ __forceinline__ uint32_t lut8_entry(int mode, int x, int y)
+{
+    int c, kind;
+    pred8x8_where(mode, x, y, c, kind);
+    const int pb = c, pd = c + 1, pa = kind == P4_F3 ? c - 1 : kind == P4_F2 ? pd : pb;
+    return (uint32_t)pa | (uint32_t)pb << 8 | (uint32_t)(kind == P4_COPY ? pb : pd) << 16 | (uint32_t)(kind == P4_DC) << 24;
+}
+#define I8_EDGE_AT 2                       // E[j] lies at byte j + 2 of the group's dc area: t0 .. t7 are two aligned dwords
+
 // ------------------------------------------------------------------------------------------
 // luma of one intra macroblock per group of sixteen lanes (l = lane inside the group).  Every global load the macroblock
 // needs is issued at the top, before anything waits: one memory round trip per iteration, everything after that runs out
 // of registers and LDS.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, IntraGrp &L, const uint32_t *lut, int mbx, int mby, const uint4 rec, int l)
+//
+// I8 (k_intra_i8 / k_intra_sparse_i8, the instances a batch takes when one of its pictures may hold Intra 8x8 macroblocks): a group
+// whose record carries P264_MB_I8X8 takes the Intra 8x8 road, told apart per group as I_PCM and Intra16x16 are.  Its lane plan:
+//   levels    lane l = row octet l & 7 (scan positions 8r .. 8r+7) of 8x8 blocks (l >> 3) and 2 + (l >> 3): two loads at the top;
+//   residual  two passes of eight lanes per block pair (blocks 0, 1 then 2, 3), lane = row, then column, of its block exactly as in
+//             k_t8x8 (scan, t8_scale, t8_idct1d on rows, then on columns, (v + 32) >> 6, all 32-bit); the 2 x 64 ints of a pass live
+//             in the group's res[] area, the results wait in registers and are parked there as int16 (saturated: the sum with a
+//             sample is clipped to 0 .. 255 anyway) once both passes are through - block k at res[64 k], raster;
+//   edge      per block the 25 reference samples straight out of the tile (128 where the neighbour is missing, the row above's
+//             second top-right dword out of pad[]), filtered (8.3.2.2.1: every end and corner case is "a neighbour that is not
+//             there counts as the sample itself"), into E[] in the dc[] area - lane l the samples l + 1 and l + 17;
+//   samples   lane l = row l >> 1, samples 4 (l & 1) .. + 3: three table places each, DC apart; residual added, one dword into the
+//             tile, from where the next block takes its neighbours.
+// With I8 = false none of this exists: the instances k_intra / k_intra_sparse are the code they were.
+template <bool I8>
+__device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, IntraGrp &L, const uint32_t *lut, const uint32_t *lut8, int mbx, int mby, const uint4 rec, int l)
 {
     // Everything below that depends on the lane number alone (roles, tile offsets, edge slots) would otherwise be hoisted
     // out of the caller's loops and kept - or spilled - across them: recomputing it per macroblock is a few dozen
@@ -142,6 +189,7 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
     const unsigned mask = rec.y;
     const int16_t *cf = pd->coefs + (size_t)rec.z * 16;
     const bool is16 = mb_type == P264_MB_I16x16;
+    const bool i8 = I8 && mb_type == P264_MB_I4x4 && (modes & P264_MB_I8X8);
     // ---- I_PCM (H.264 8.3.5): the macroblock's twelve blocks of coefs[] ARE its samples (p264hip.h), lane l copies row l into
     //      the strip layout - no neighbours, no tile, no residual.  A test per group, in front of everything: the groups of a
     //      wavefront that hold other types run on as before (the sparse lists and the band walk hand this function mixed
@@ -159,9 +207,18 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
     if (l < 4)       { if (aT)  vT = gload1(F + luma_off(g, X0 + 4 * l, Y0 - 1)); }
     else if (l == 4) { if (aTR) vT = gload1(F + luma_off(g, X0 + 16, Y0 - 1)); }
     else if (l == 5) { if (aTL) vT = Fg[luma_off(g, X0 - 1, Y0 - 1)]; }
+    else if (I8 && l == 6) { if (i8 && aTR) vT = gload1(F + luma_off(g, X0 + 20, Y0 - 1)); }   // (Intra 8x8 block 1 reads x = 16 .. 23 of the row above)
     // ---- (b) levels: lane l = block l (decode order), all 16 slots of it ----
-    const bool coded = (mask >> l) & 1;
+    bool coded = (mask >> l) & 1;
     uint4 la = make_uint4(0, 0, 0, 0), lb = la;
+    bool c8a = false, c8b = false;                         // (Intra 8x8: the lane's two 8x8 blocks are coded)
+    if (I8 && i8) {
+        coded = false;
+        const int k0 = l >> 3;
+        c8a = (mask >> (4 * k0)) & 1; c8b = (mask >> (4 * k0 + 8)) & 1;
+        if (c8a) la = gload4(cf + coef_slot(mask, 4 * k0) * 16 + (l & 7) * 8);
+        if (c8b) lb = gload4(cf + coef_slot(mask, 4 * k0 + 8) * 16 + (l & 7) * 8);
+    } else
     if (coded) { const int16_t *c = cf + coef_slot(mask, l) * 16; la = gload4(c); lb = gload4(c + 8); }
     const bool dcflag = is16 && (mask & P264_COEF_LUMA_DC);
     int ldc = 0;                                           // Intra16x16 DC level l (scan order)
@@ -174,12 +231,17 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
     L.tile[(l + 1) * IT_STRIDE + 3] = (uint8_t)vL;
     if (l < 5) *(uint32_t *)(L.tile + 4 + 4 * l) = vT;
     else if (l == 5) L.tile[3] = (uint8_t)vT;
+    else if (I8 && l == 6) *(uint32_t *)L.pad = vT;
     wave_lds_fence();
-    if (!aTR && l == 4) *(uint32_t *)(L.tile + 20) = (uint32_t)L.tile[19] * 0x01010101u;   // top-right of the MB missing: replicate t15 (:706-709)
+    if (!aTR && l == 4) {                                  // top-right of the MB missing: replicate t15 (:706-709)
+        const uint32_t t15 = (uint32_t)L.tile[19] * 0x01010101u;
+        *(uint32_t *)(L.tile + 20) = t15;
+        if (I8) *(uint32_t *)L.pad = t15;
+    }
     wave_lds_fence();
 
     // ---- residuals of all sixteen blocks into LDS (lane = block) ----
-    const bool grp_res = (mask & 0xffffu) != 0 || dcflag;  // (the same for the sixteen lanes)
+    const bool grp_res = !i8 && ((mask & 0xffffu) != 0 || dcflag);  // (the same for the sixteen lanes)
     if (__ballot(grp_res)) {
         int dcv = 0;
         if (__ballot(dcflag)) {
@@ -229,6 +291,59 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
         out[1] = mine ? make_uint4(r[2][0], r[2][1], r[3][0], r[3][1]) : make_uint4(0, 0, 0, 0);
         wave_lds_fence();
     }
+    if (I8) {
+        // ---- Intra 8x8: the residual of the coded 8x8 blocks (kernel_t8x8.h's arithmetic, see the lane plan above) ----
+        const bool res8 = i8 && (mask & 0xffffu) != 0;
+        if (__ballot(res8)) {
+            const int r = l & 7, q8 = (int)((rec.x >> 8) & 63u), per = (q8 * 43) >> 8;
+            const uint64_t vrow = c_t8_v[q8 - per * 6];
+            int *t8 = (int *)L.res + (l >> 3) * 64;
+            uint32_t keep[2][4] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };           // column r of the lane's two blocks, eight int16 each
+#pragma unroll
+            for (int ps = 0; ps < 2; ps++) {
+                const bool c8 = res8 && (ps ? c8b : c8a);
+                int d[8];
+                if (c8) {
+                    const uint2 sc = *(const uint2 *)(c_scan8x8 + r * 8);
+                    const uint32_t lw[4] = { ps ? lb.x : la.x, ps ? lb.y : la.y, ps ? lb.z : la.z, ps ? lb.w : la.w };
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+                        const int c = (i & 1) ? (int)lw[i >> 1] >> 16 : (int)(int16_t)(lw[i >> 1] & 0xffffu);
+                        const int p = (int)(((i < 4 ? sc.x : sc.y) >> (8 * (i & 3))) & 63u);
+                        t8[p] = t8_scale(c, p, vrow, per);
+                    }
+                }
+                wave_lds_fence();
+                if (c8) {                                   // rows first
+                    const int2 a = *(const int2 *)(t8 + r * 8), b = *(const int2 *)(t8 + r * 8 + 2), c = *(const int2 *)(t8 + r * 8 + 4), e = *(const int2 *)(t8 + r * 8 + 6);
+                    d[0] = a.x; d[1] = a.y; d[2] = b.x; d[3] = b.y; d[4] = c.x; d[5] = c.y; d[6] = e.x; d[7] = e.y;
+                    t8_idct1d(d);
+                    *(int2 *)(t8 + r * 8) = make_int2(d[0], d[1]); *(int2 *)(t8 + r * 8 + 2) = make_int2(d[2], d[3]);
+                    *(int2 *)(t8 + r * 8 + 4) = make_int2(d[4], d[5]); *(int2 *)(t8 + r * 8 + 6) = make_int2(d[6], d[7]);
+                }
+                wave_lds_fence();
+                if (c8) {                                   // column r
+#pragma unroll
+                    for (int y = 0; y < 8; y++) d[y] = t8[y * 8 + r];
+                    t8_idct1d(d);
+#pragma unroll
+                    for (int y = 0; y < 8; y++) {
+                        const int v = min(max((d[y] + 32) >> 6, -32768), 32767);
+                        keep[ps][y >> 1] |= ((uint32_t)v & 0xffffu) << (16 * (y & 1));
+                    }
+                }
+                wave_lds_fence();                          // (the next pass, and the parking below, write where this one read)
+            }
+#pragma unroll
+            for (int ps = 0; ps < 2; ps++)
+                if (res8 && (ps ? c8b : c8a)) {
+                    int16_t *out = L.res + (ps * 2 + (l >> 3)) * 64 + r;
+#pragma unroll
+                    for (int y = 0; y < 8; y++) out[y * 8] = (int16_t)(keep[ps][y >> 1] >> (16 * (y & 1)));
+                }
+            wave_lds_fence();
+        }
+    }
 
     if (__ballot(is16)) {
         if (is16) {
@@ -268,8 +383,65 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
             gstore4(F + mb_luma_off(g, mbx, mby) + l * 16, make_uint4(pv[0], pv[1], pv[2], pv[3]));
         }
     }
-    if (__ballot(!is16)) {
-        if (!is16) {
+    if (I8 && __ballot(i8)) {
+        if (i8) {
+            // ---- Intra 8x8 (H.264 8.3.2): four dependent blocks, quadrants in raster order ----
+            const int grp_base = (int)(threadIdx.x & 48);
+            uint8_t *E = (uint8_t *)L.dc + I8_EDGE_AT;
+            const uint8_t *tr2 = L.pad;                    // x = 20 .. 23 of the row above the macroblock
+            const int y = l >> 1, x0 = (l & 1) * 4;
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const int bx = b & 1, by = b >> 1;
+                // left / top / corner of the block (top-right: block 0 the row above, block 1 the macroblock's, block 2 block 1, block 3 none)
+                const bool avL = bx || aL, avT = by || aT, avC = b == 0 ? aTL : b == 1 ? aT : b == 2 ? aL : true;
+                const int mode = min(__shfl(modebyte, grp_base + 4 * b), 8);
+                uint8_t *o = L.tile + (by * 8 + 1) * IT_STRIDE + 4 + bx * 8;            // block origin inside the tile
+                // sample j (1 .. 25) of the unfiltered edge; where the top is there and the top-right is not, the tile holds p[7, -1] there
+                auto raw = [&](int j) -> int {
+                    j = min(max(j, 1), 25);
+                    int x = j - 10;                                                 // (-1: the corner)
+                    if (b == 3) x = min(x, 7);
+                    int v = o[j <= 8 ? (8 - j) * IT_STRIDE - 1 : x - IT_STRIDE];
+                    if (b == 1 && j >= 22) v = tr2[j - 22];
+                    return v;
+                };
+                auto there = [&](int j) -> bool { return j < 1 || j > 25 ? false : j <= 8 ? avL : j == 9 ? avC : avT; };
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int j = l + 1 + 16 * h;
+                    if (j <= 25) {
+                        const int B = raw(j), A = there(j - 1) ? raw(j - 1) : B, D = there(j + 1) ? raw(j + 1) : B;
+                        const int v = there(j) ? (A + 2 * B + D + 2) >> 2 : 128;
+                        E[j] = (uint8_t)v;
+                        if (j == 1) E[0] = (uint8_t)v;
+                        if (j == 25) E[26] = (uint8_t)v;
+                    }
+                }
+                wave_lds_fence();
+                uint32_t px = 0;
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const uint32_t wk = lut8[mode * 64 + y * 8 + x0 + i];
+                    const int a = E[wk & 255u], c = E[(wk >> 8) & 255u], d = E[(wk >> 16) & 255u];
+                    px |= (uint32_t)((a + 2 * c + d + 2) >> 2) << (8 * i);
+                }
+                if (mode == 2) {                                                    // DC and its fall-backs, 8.3.2.2.4
+                    const int st = byte_sum(*(const uint32_t *)(E + 10)) + byte_sum(*(const uint32_t *)(E + 14));
+                    const int sl = E[1] + byte_sum(*(const uint32_t *)(E + 2)) + E[6] + E[7] + E[8];
+                    const int dcv = (avL && avT) ? (sl + st + 8) >> 4 : avL ? (sl + 4) >> 3 : avT ? (st + 4) >> 3 : 128;
+                    px = (uint32_t)dcv * 0x01010101u;
+                }
+                if ((mask >> (4 * b)) & 1) { const uint2 rr = *(const uint2 *)(L.res + b * 64 + y * 8 + x0); px = add_res4(px, rr.x, rr.y); }
+                *(uint32_t *)(o + y * IT_STRIDE + x0) = px;
+                wave_lds_fence();
+            }
+            const uint32_t *row = (const uint32_t *)(L.tile + (l + 1) * IT_STRIDE + 4);
+            gstore4(F + mb_luma_off(g, mbx, mby) + l * 16, make_uint4(row[0], row[1], row[2], row[3]));
+        }
+    }
+    if (__ballot(!is16 && !i8)) {
+        if (!is16 && !i8) {
             // ---- Intra4x4: sixteen dependent blocks (decoder/macroblock.c:799-831), lane l = sample (x, y) of the current block.
             // The samples a prediction reads are the edge S = l3 l3 l2 l1 l0 lt t0..t7 t7 around the block (pred4x4_where); they
             // are read straight out of the tile: cells of neighbours that do not exist already hold their substitute (128, put
@@ -436,7 +608,8 @@ struct IntraShared {
     unsigned long long m_intra[INTRA_MASKS], m_walk[INTRA_MASKS];   // per row window: intra macroblocks / those left to the band walk
     int free_n[2];
 };
-__device__ __forceinline__ void intra_picture(IntraShared &sh, const PicDev *__restrict__ pics, const Geom &g, int *status, const uint8_t *__restrict__ is_intra_all,
+template <bool I8>
+__device__ __forceinline__ void intra_picture(IntraShared &sh, uint32_t *lut8, const PicDev *__restrict__ pics, const Geom &g, int *status, const uint8_t *__restrict__ is_intra_all,
                                               const int pic_index, const bool chroma_role)
 {
     IntraSync &sync = sh.sync;
@@ -454,6 +627,7 @@ __device__ __forceinline__ void intra_picture(IntraShared &sh, const PicDev *__r
     const int n_waves = blockDim.x >> 6;                       // 16 per picture, or fewer when pictures share a CU (host's choice)
     const int n_bands = (g.mb_h + INTRA_BAND - 1) / INTRA_BAND;
     for (int i = threadIdx.x; i < INTRA_LUT_ENTRIES; i += blockDim.x) lut[i] = lut_entry(i >> 4, i & 3, (i >> 2) & 3);
+    if (I8) for (int i = threadIdx.x; i < INTRA_LUT8_ENTRIES; i += blockDim.x) lut8[i] = lut8_entry(i >> 6, i & 7, (i >> 3) & 7);
     for (int i = threadIdx.x; i <= n_bands; i += blockDim.x) sync.progress[i] = 0;
     const int wins = (g.mb_w + 63) / 64, n_win = g.mb_h * wins;
     const bool use_free = pd->slice_type != P264_SLICE_I && n_win <= INTRA_MASKS && g.n_mb < 65536;     // (scalar)
@@ -539,7 +713,7 @@ __device__ __forceinline__ void intra_picture(IntraShared &sh, const PicDev *__r
                     const int mbx = mbi - mby * g.mb_w;
                     if (active) {
                         if (chroma_role) intra_chroma4(pd, g, L, mbx, mby, rec, l);
-                        else             intra_luma4(pd, g, L, lut, mbx, mby, rec, l);
+                        else             intra_luma4<I8>(pd, g, L, lut, lut8, mbx, mby, rec, l);
                     }
                     k = kn; mbi = mbi_n; rec = rec_n;
                 }
@@ -668,7 +842,7 @@ __device__ __forceinline__ void intra_picture(IntraShared &sh, const PicDev *__r
                                          pick(srec[0].z, srec[1].z, srec[2].z, srec[3].z), pick(srec[0].w, srec[1].w, srec[2].w, srec[3].w));
             if (active) {
                 if (chroma_role) intra_chroma4(pd, g, L, mbx, R0 + grp, rec, l);
-                else             intra_luma4(pd, g, L, lut, mbx, R0 + grp, rec, l);
+                else             intra_luma4<I8>(pd, g, L, lut, lut8, mbx, R0 + grp, rec, l);
             }
 #pragma unroll
             for (int r = 0; r < INTRA_BAND; r++) if (go[r]) todo[r] &= todo[r] - 1;
@@ -681,7 +855,27 @@ __global__ __launch_bounds__(INTRA_ROW_WAVES * 64, INTRA_WAVES_PER_EU)
 void k_intra(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra)
 {
     __shared__ IntraShared sh;
-    intra_picture(sh, pics, g, status, is_intra, (int)blockIdx.x, blockIdx.y != 0);
+    intra_picture<false>(sh, nullptr, pics, g, status, is_intra, (int)blockIdx.x, blockIdx.y != 0);
+}
+// The Intra 8x8 instances (intra_luma4<true>): what a batch launches in place of the two kernels around here when one of its pictures
+// carries P264_T8X8_INTRA.  128 registers (the sixteen wavefronts of a workgroup are four per SIMD whatever the bound says) and a
+// second table in LDS; k_intra_sparse_i8 has no edge-info role (such batches take k_deblock_bs, which knows the flag).
+#define INTRA_I8_WAVES_PER_EU 4
+__global__ __launch_bounds__(INTRA_ROW_WAVES * 64, INTRA_I8_WAVES_PER_EU)
+void k_intra_i8(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra)
+{
+    __shared__ IntraShared sh;
+    __shared__ uint32_t lut8[INTRA_LUT8_ENTRIES];
+    intra_picture<true>(sh, lut8, pics, g, status, is_intra, (int)blockIdx.x, blockIdx.y != 0);
+}
+__global__ __launch_bounds__(INTRA_ROW_WAVES * 64, INTRA_I8_WAVES_PER_EU)
+void k_intra_sparse_i8(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra, EdgeInfo *__restrict__ info, uint32_t inv_mbw, int bs_wgs)
+{
+    (void)info; (void)inv_mbw; (void)bs_wgs;               // (the signature of k_intra_sparse; two workgroups per picture)
+    __shared__ IntraShared sh;
+    __shared__ uint32_t lut8[INTRA_LUT8_ENTRIES];
+    const int pic = rfl((int)(blockIdx.x >> 1));
+    intra_picture<true>(sh, lut8, pics, g, status, is_intra, pic, (blockIdx.x & 1) != 0);
 }
 #define INTRA_SPARSE_WAVES_PER_EU 8
 // The sparse build also carries the loop filter's EDGE INFO pass (kernel_deblock.h, K4a) as a third role: that pass is bound
@@ -774,5 +968,5 @@ void k_intra_sparse(const PicDev *__restrict__ pics, Geom g, int *status, const 
         return;
     }
     __shared__ IntraShared sh;
-    intra_picture(sh, pics, g, status, is_intra, pic, role != 0);
+    intra_picture<false>(sh, nullptr, pics, g, status, is_intra, pic, role != 0);
 }

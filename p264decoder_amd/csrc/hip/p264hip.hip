@@ -99,7 +99,9 @@ __global__ void k_check_records(const p264hip_mb_t *mb, int n_mb, uint32_t n_coe
     if (r.y && (uint64_t)r.z + (uint64_t)__popc(r.y & 0x3ffffffu) > (uint64_t)n_coef_blocks) atomicOr(bad, 1);
     if ((r.x & 255u) == P264_MB_IPCM && r.y != P264_IPCM_COEF_MASK) atomicOr(bad, 1);       // (the intra kernels read twelve blocks of samples)
     // P264_MB_T8X8: in pictures that say so, inter, whole luma nibbles (k_t8x8 reads four entries per set nibble)
-    if ((r.x >> 24) & P264_MB_T8X8) { if (!t8x8 || P264_MB_IS_INTRA(r.x & 255u) || (r.y & 0xffffu) != (r.y & 0x1111u) * 15u) atomicOr(bad, 1); }
+    if ((r.x >> 24) & P264_MB_T8X8) { if (!(t8x8 & ~P264_T8X8_INTRA) || P264_MB_IS_INTRA(r.x & 255u) || (r.y & 0xffffu) != (r.y & 0x1111u) * 15u) atomicOr(bad, 1); }
+    // P264_MB_I8X8: in pictures that say so, I4x4, whole luma nibbles, not beside P264_MB_T8X8 (the Intra 8x8 instances of the intra kernels read four entries per set nibble)
+    if ((r.x >> 24) & P264_MB_I8X8) { if (!(t8x8 & P264_T8X8_INTRA) || (r.x & 255u) != P264_MB_I4x4 || ((r.x >> 24) & P264_MB_T8X8) || (r.y & 0xffffu) != (r.y & 0x1111u) * 15u) atomicOr(bad, 1); }
 }
 
 struct p264hip_ctx {
@@ -277,6 +279,9 @@ static int check_pic(p264hip_ctx *c, const p264hip_picture_t *p, bool arrays)
     const int blocks = __builtin_popcount(m.coef_mask & 0x3ffffffu);
     if (m.coef_mask && (uint64_t)m.coef_index + (uint64_t)blocks > p->n_coef_blocks)
         return fail(P264HIP_EINVAL, "macroblock %d: coefficient blocks [%u, +%d) outside coefs[%u]", bad, m.coef_index, blocks, p->n_coef_blocks);
+    if (m.intra_modes & P264_MB_I8X8)
+        return fail(P264HIP_EINVAL, "macroblock %d: P264_MB_I8X8 on a record of type %d with intra_modes 0x%x and coef_mask 0x%x in a picture with transform_8x8 = %d (I4x4 records with whole luma nibbles and without P264_MB_T8X8, in pictures that carry P264_T8X8_INTRA)",
+                    bad, m.mb_type, m.intra_modes, m.coef_mask, p->transform_8x8);
     if (m.intra_modes & P264_MB_T8X8)
         return fail(P264HIP_EINVAL, "macroblock %d: P264_MB_T8X8 on a record of type %d with coef_mask 0x%x in a picture with transform_8x8 = %d (inter records with whole luma nibbles, in pictures that say so)",
                     bad, m.mb_type, m.coef_mask, p->transform_8x8);
@@ -812,8 +817,8 @@ static PicDev picdev_of(p264hip_ctx *c, const PicSlot &s, int st)
 
 // What the batch holds - the kernel instances and launch shapes follow from it: any picture with inter macroblocks / any B picture /
 // any I picture / any explicit weights / any unweighted P picture whose list 0 holds one frame at several indices / any picture
-// whose inter macroblocks may use the 8x8 transform
-struct BatchKinds { bool p = false, b = false, i = false, wp = false, dup = false, t8 = false; };
+// whose inter macroblocks may use the 8x8 transform / any picture whose Intra4x4 records may carry P264_MB_I8X8
+struct BatchKinds { bool p = false, b = false, i = false, wp = false, dup = false, t8 = false, i8 = false; };
 
 // the batch's streams and slots checked (nothing is queued yet), one PicDev per picture in hb
 static int batch_fill(p264hip_ctx *c, const int *pic_ids, const int *streams, int n, PicDev *hb, BatchKinds *kinds)
@@ -836,7 +841,8 @@ static int batch_fill(p264hip_ctx *c, const int *pic_ids, const int *streams, in
         k.i |= s.meta.slice_type == P264_SLICE_I;
         k.wp |= s.meta.explicit_wp != 0;
         k.dup |= hb[i].dup_refs != 0;
-        k.t8 |= s.meta.transform_8x8 != 0 && s.meta.slice_type != P264_SLICE_I;
+        k.t8 |= (s.meta.transform_8x8 & ~P264_T8X8_INTRA) != 0 && s.meta.slice_type != P264_SLICE_I;
+        k.i8 |= (s.meta.transform_8x8 & P264_T8X8_INTRA) != 0;
     }
     *kinds = k;
     return 0;
@@ -874,7 +880,7 @@ static int intra_waves(const p264hip_ctx *c, int n)
 // (k_deblock_bs)
 static int edge_info_fused(const p264hip_ctx *c, const BatchKinds &k)
 {
-    if (k.i || k.b || k.wp || k.dup || k.t8 || c->tune_bs_fused == 0) return 0;
+    if (k.i || k.b || k.wp || k.dup || k.t8 || k.i8 || c->tune_bs_fused == 0) return 0;
     return c->tune_bs_fused > 0 ? c->tune_bs_fused : INTRA_BS_WGS;
 }
 
@@ -955,6 +961,15 @@ static void launch_intra(p264hip_ctx *c, const PicDev *batch, int n, const Batch
 {
     ScopedStamp t(c, 1);
     const int waves = c->last.intra_waves = intra_waves(c, n);
+    // (a picture of the batch may hold Intra 8x8 macroblocks: the instances that know them - kernel_intra.h; the edge info then has
+    // its own launch, edge_info_fused)
+    if (k.i8) {
+        c->last.intra_i8 = 1;
+        if (k.i) hipLaunchKernelGGL(k_intra_i8, dim3(n, 2), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status, (const uint8_t *)c->d_is_intra);
+        else hipLaunchKernelGGL(k_intra_sparse_i8, dim3((unsigned)n * 2), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status,
+                                (const uint8_t *)c->d_is_intra, c->d_edge, inv_mb_w(c), 0);
+        return;
+    }
     // luma and chroma of a picture are independent chains: as two workgroups they run side by side
     if (k.i) hipLaunchKernelGGL(k_intra, dim3(n, 2), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status, (const uint8_t *)c->d_is_intra);
     else {

@@ -296,6 +296,7 @@ struct p264fan {
     int rank, world, device;
     p264fan_transport_t t;
     p264fan_backend_t bk; void *bk_ctx;
+    int own_bk;                               /* the backend is this library's HIP path: it knows P264_MB_I8X8, the parsers may hand it out */
 };
 
 p264fan *p264fan_open(int rank, int world, const p264fan_transport_t *t, const p264fan_backend_t *backend, int device)
@@ -307,6 +308,7 @@ p264fan *p264fan_open(int rank, int world, const p264fan_transport_t *t, const p
     f->rank = rank; f->world = world; f->device = device;
     if (t) f->t = *t;
     f->bk = backend ? *backend : g_hip_backend;
+    f->own_bk = backend == NULL;
     return f;
 }
 void p264fan_close(p264fan *f)
@@ -533,7 +535,9 @@ int p264fan_root_run(p264fan *f, int n_streams, const uint8_t *const *annexb, co
         if (!R->msg || !R->cap || !R->len || !R->index || !R->head) rc = fail("out of memory");
     }
     for (int s = 0; s < n_streams && !rc; s++) {
-        P.st[s].parser = p264parse_open(P264PARSE_OPT_QUIET);
+        /* (Intra 8x8 macroblocks only for the library's own backend on every rank - a plug-in backend's owner has not said that it
+         * knows the record, include/p264parse.h) */
+        P.st[s].parser = p264parse_open(P264PARSE_OPT_QUIET | (f->own_bk ? P264PARSE_OPT_INTRA8X8 : 0));
         P.st[s].in = annexb[s]; P.st[s].size = sizes[s];
         if (!P.st[s].parser) rc = fail("p264parse_open failed");
     }

@@ -64,7 +64,8 @@ int64_t p264hip_pack_input(const p264hip_picture_t *p, void *dst_, size_t cap)
 /* The rule every road into a slot holds the macroblock records to: a macroblock's packed blocks lie inside coefs[] (the
  * kernels index the coefficient stream without further checks), an I_PCM record carries its twelve-block mask (the intra
  * kernels read twelve blocks of samples), and a record with P264_MB_T8X8 is inter with whole luma nibbles (k_t8x8 reads four
- * entries per set nibble; the intra kernels know no 8x8 block).  The index of the first record that breaks it, or -1.  On the
+ * entries per set nibble), and a record with P264_MB_I8X8 is I4x4 with whole luma nibbles and without P264_MB_T8X8 (the Intra 8x8
+ * instances of the intra kernels read four entries per set nibble; every other kernel knows no intra 8x8 block).  The index of the first record that breaks it, or -1.  On the
  * device, for blocks that never pass through the host: k_check_records (p264hip.hip). */
 int64_t p264hip_records_check(const p264hip_mb_t *mb, size_t n_mb, uint32_t n_coef_blocks)
 {
@@ -76,6 +77,10 @@ int64_t p264hip_records_check(const p264hip_mb_t *mb, size_t n_mb, uint32_t n_co
             const uint32_t lo = m->coef_mask & 0x1111u;                          /* whole nibbles: every bit equals its nibble's lowest */
             if (P264_MB_IS_INTRA(m->mb_type) || (m->coef_mask & 0xffffu) != lo * 15u) return (int64_t)i;
         }
+        if (m->intra_modes & P264_MB_I8X8) {
+            const uint32_t lo = m->coef_mask & 0x1111u;
+            if (m->mb_type != P264_MB_I4x4 || (m->intra_modes & P264_MB_T8X8) || (m->coef_mask & 0xffffu) != lo * 15u) return (int64_t)i;
+        }
     }
     return -1;
 }
@@ -84,8 +89,11 @@ int64_t p264hip_records_check_pic(const p264hip_picture_t *d, const p264hip_mb_t
 {
     const size_t n = (size_t)d->mb_w * (size_t)d->mb_h;
     const int64_t bad = p264hip_records_check(mb, n, d->n_coef_blocks);
-    if (bad >= 0 || d->transform_8x8) return bad;
-    for (size_t i = 0; i < n; i++) if (mb[i].intra_modes & P264_MB_T8X8) return (int64_t)i;
+    if (bad >= 0) return bad;
+    /* the flags the descriptor does not announce */
+    const int off = ((d->transform_8x8 & ~P264_T8X8_INTRA) ? 0 : P264_MB_T8X8) | ((d->transform_8x8 & P264_T8X8_INTRA) ? 0 : P264_MB_I8X8);
+    if (!off) return -1;
+    for (size_t i = 0; i < n; i++) if (mb[i].intra_modes & off) return (int64_t)i;
     return -1;
 }
 

@@ -94,6 +94,7 @@ typedef struct {
     int weighted_bipred;
     int16_t bipred_weight[P264HIP_MAX_REFS * P264HIP_MAX_REFS];   /* implicit weights (8.4.2.3.1) */
     int t8x8;                                 /* a slice of the picture had transform_8x8_mode_flag: its inter records may carry P264_MB_T8X8 */
+    int i8x8;                                 /* the picture holds at least one Intra 8x8 record (P264_MB_I8X8) */
 } curpic_t;
 
 struct p264parse {
@@ -797,6 +798,29 @@ static int predict_i4mode(const p264parse *p, int blk)
     int m = ma < mb ? ma : mb;
     return m < 0 ? 2 : m;
 }
+/* (An Intra 8x8 neighbour - an I4x4 record with P264_MB_I8X8 - gives Intra8x8PredMode[luma4x4BlkIdxN >> 2] (8.3.1.1): its record keeps
+ * the mode of 8x8 block k at i4[4k .. 4k+3], and decode-order indices 4k .. 4k+3 are quadrant k, so the look-ups above read exactly
+ * that.)
+ * Intra8x8PredMode predictor (H.264 8.3.2.1) of 8x8 block k: the minimum over the neighbours A (left) and B (above); 2 where one is
+ * not available or, under constrained_intra_pred_flag, inter; a neighbour that is neither I4x4 nor Intra 8x8 counts as 2; an Intra 8x8
+ * neighbour gives its block's mode, an Intra4x4 one Intra4x4PredMode[8x8 block N * 4 + n] with n = 1 for A and n = 2 for B - one
+ * look-up for both kinds, the storage being what it is */
+static int predict_i8mode(const p264parse *p, int k)
+{
+    const picbuf_t *q = &p->buf[p->cur];
+    const int cip = p->pps[p->sh.pps_id].constrained_intra;
+    int ma, mb;
+    if (k & 1) ma = q->i4[p->mbi * 16 + 4 * (k - 1)];
+    else if ((p->cur_avail & P264_AVAIL_LEFT) && !(cip && !P264_MB_IS_INTRA(q->mb[p->mbi - 1].mb_type)))
+        ma = q->mb[p->mbi - 1].mb_type == P264_MB_I4x4 ? q->i4[(p->mbi - 1) * 16 + 4 * (k + 1) + 1] : 2;
+    else ma = -1;
+    if (k & 2) mb = q->i4[p->mbi * 16 + 4 * (k - 2)];
+    else if ((p->cur_avail & P264_AVAIL_TOP) && !(cip && !P264_MB_IS_INTRA(q->mb[p->mbi - p->mb_w].mb_type)))
+        mb = q->mb[p->mbi - p->mb_w].mb_type == P264_MB_I4x4 ? q->i4[(p->mbi - p->mb_w) * 16 + 4 * (k + 2) + 2] : 2;
+    else mb = -1;
+    int m = ma < mb ? ma : mb;
+    return m < 0 ? 2 : m;
+}
 
 /* ---------------------------------------------------------------- macroblock layer ------ */
 typedef struct {
@@ -852,7 +876,7 @@ static int parse_residual(p264parse *p, bitrd_t *b, p264hip_mb_t *m, mbcoef_t *c
         if (tc) cf->mask |= P264_COEF_LUMA_DC;
     }
     int maxc = m->mb_type == P264_MB_I16x16 ? 15 : 16;
-    const int t8 = m->intra_modes & P264_MB_T8X8;
+    const int t8 = m->intra_modes & (P264_MB_T8X8 | P264_MB_I8X8);
     for (int i = 0; i < 16; i++) {
         const int at = nc_pos[i];
         nnz[i] = 0; nc[at] = 0;
@@ -1266,8 +1290,15 @@ static int parse_mb_t(p264parse *p, bitrd_t *b, unsigned t, int intra_t)
         clear_motion(p);
         if (intra_t == 0) {
             m->mb_type = P264_MB_I4x4;
-            /* I_NxN: transform_size_8x8_flag comes in front of the prediction modes; 1 = Intra 8x8 prediction, which no kernel does */
-            if (p->t8x8_mode && rd_t8x8_flag(p, b)) { ERR(p, "Intra 8x8 prediction unsupported"); return -1; }
+            /* I_NxN: transform_size_8x8_flag comes in front of the prediction modes; 1 = Intra 8x8 prediction, which only a backend that
+             * knows P264_MB_I8X8 does (P264PARSE_OPT_INTRA8X8) */
+            if (p->t8x8_mode && rd_t8x8_flag(p, b)) {
+                if (!(p->opts & P264PARSE_OPT_INTRA8X8)) { ERR(p, "Intra 8x8 prediction unsupported"); return -1; }
+                /* four prev_intra8x8_pred_mode_flag / rem_intra8x8_pred_mode pairs: the 4x4 elements' code and contexts (7.3.5.1) */
+                m->intra_modes = P264_MB_I8X8;
+                p->pic.i8x8 = 1;
+                for (int k = 0; k < 4; k++) memset(i4 + 4 * k, rd_intra4x4_mode(p, b, predict_i8mode(p, k)), 4);
+            } else
             for (int i = 0; i < 16; i++) i4[i] = (uint8_t)rd_intra4x4_mode(p, b, predict_i4mode(p, i));
         } else {
             m->mb_type = P264_MB_I16x16;
@@ -1467,7 +1498,7 @@ static void publish_picture(p264parse *p)
         d->weighted_bipred = c->weighted_bipred;
         memcpy(d->bipred_weight, c->bipred_weight, sizeof d->bipred_weight);
     }
-    d->transform_8x8 = c->t8x8;
+    d->transform_8x8 = c->t8x8 | (c->i8x8 ? P264_T8X8_INTRA : 0);
     if (c->wp_set && c->wp) {
         d->explicit_wp = 1;
         d->wp_log2_denom[0] = c->wp_denom[0]; d->wp_log2_denom[1] = c->wp_denom[1];
@@ -1517,7 +1548,7 @@ static int open_picture(p264parse *p, const slice_t *sh, int nal_type, int nal_r
     c->first = *sh;
     c->type = sh->type;
     c->deblock = 0; c->alpha = c->beta = 0;
-    c->n_list[0] = c->n_list[1] = 0; c->wp_set = 0; c->t8x8 = 0;
+    c->n_list[0] = c->n_list[1] = 0; c->wp_set = 0; c->t8x8 = 0; c->i8x8 = 0;
     p->n_list[0] = p->n_list[1] = 0;
     p->buf[p->cur].coef_n = 0;
     memset(p->slice_of, 0xff, (size_t)p->n_mb * sizeof(uint16_t));

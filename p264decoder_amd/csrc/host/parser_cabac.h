@@ -281,13 +281,18 @@ static int cb_residual_block8(p264parse *p, int16_t *out)
     }
     return cnt;
 }
+/* transform_size_8x8_flag of a parsed record: P264_MB_T8X8 on an inter record, P264_MB_I8X8 on an I4x4 one */
+static inline int mb_t8x8_flag(const p264hip_mb_t *m)
+{
+    return P264_MB_IS_INTRA(m->mb_type) ? m->mb_type == P264_MB_I4x4 && (m->intra_modes & P264_MB_I8X8) : (m->intra_modes & P264_MB_T8X8) != 0;
+}
 /* transform_size_8x8_flag (9.3.3.1.1.10): the flags of the macroblocks to the left and above (a skipped one's is 0) */
 static int cb_t8x8_flag(p264parse *p)
 {
     const picbuf_t *q = &p->buf[p->cur];
     int ctx = 399;
-    if (cb_left(p) && (q->mb[p->mbi - 1].intra_modes & P264_MB_T8X8) && !P264_MB_IS_INTRA(q->mb[p->mbi - 1].mb_type)) ctx++;
-    if (cb_top(p) && (q->mb[p->mbi - p->mb_w].intra_modes & P264_MB_T8X8) && !P264_MB_IS_INTRA(q->mb[p->mbi - p->mb_w].mb_type)) ctx++;
+    if (cb_left(p) && mb_t8x8_flag(&q->mb[p->mbi - 1])) ctx++;
+    if (cb_top(p) && mb_t8x8_flag(&q->mb[p->mbi - p->mb_w])) ctx++;
     return p264cabac_decision(&p->cb, ctx);
 }
 /* coded_block_flag of the block left of / above block blk (0..15 luma, 16..23 chroma AC) */
@@ -324,7 +329,8 @@ static int parse_residual_cabac(p264parse *p, p264hip_mb_t *m, mbcoef_t *cf)
         if ((tc = cb_residual_block(p, 0, a, b, cf->dc_luma)) < 0) return -1;
         if (tc) { cf->mask |= P264_COEF_LUMA_DC; p->cinfo[p->mbi] |= CI_DC_Y; }
     }
-    for (int k8 = 0; (m->intra_modes & P264_MB_T8X8) && !intra && k8 < 4; k8++) {
+    const int t8 = mb_t8x8_flag(m);
+    for (int k8 = 0; t8 && k8 < 4; k8++) {
         /* 8x8 blocks: the quadrant's four entries hold the 64 levels; every 4x4 block of a coded quadrant counts as coded for the
          * coded_block_flag contexts of the blocks that follow (its flag is inferred 1) */
         memset(nnz + 4 * k8, 0, 4);
@@ -335,7 +341,7 @@ static int parse_residual_cabac(p264parse *p, p264hip_mb_t *m, mbcoef_t *cf)
         cf->mask |= 0xfu << (4 * k8);
     }
     for (int i = 0; i < 16; i++) {
-        if ((m->intra_modes & P264_MB_T8X8) && !intra) break;
+        if (t8) break;
         nnz[i] = 0;
         if (!(cbp_l & (1 << (i >> 2)))) continue;
         memset(cf->blk[i], 0, sizeof cf->blk[i]);

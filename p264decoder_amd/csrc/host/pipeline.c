@@ -185,7 +185,8 @@ p264pipe *p264pipe_open(int device, int n_streams, int n_threads)
     pthread_mutex_init(&p->mu, NULL); pthread_cond_init(&p->go, NULL); pthread_cond_init(&p->idle, NULL); pthread_cond_init(&p->turn, NULL);
     if (!p->st || !p->threads || !p->parsed || !p->round_pic[0] || !p->round_pic[1]) { p264pipe_close(p); return NULL; }
     for (int i = 0; i < n_streams; i++) {
-        p->st[i].parser = p264parse_open(P264PARSE_OPT_QUIET);
+        /* (the pictures go to this library's HIP layer, which knows Intra 8x8 records; device -1 parses for nobody: the default) */
+        p->st[i].parser = p264parse_open(P264PARSE_OPT_QUIET | (device >= 0 ? P264PARSE_OPT_INTRA8X8 : 0));
         if (!p->st[i].parser) { p264pipe_close(p); return NULL; }
         /* picture buffers in pinned host memory when they are uploaded (P264AMD_PIPE_PINNED=0 / 1 forces either kind: experiments) */
         const char *pin = getenv("P264AMD_PIPE_PINNED");

@@ -70,9 +70,11 @@ class ParsedPicture:
 class Parser:
     """p264parse_* : NAL units in, complete parsed pictures out (CPU, serial by nature)."""
 
-    def __init__(self, quiet=True, strict=False, lib=None):
+    def __init__(self, quiet=True, strict=False, lib=None, intra8x8=False):
+        """intra8x8: hand out Intra 8x8 macroblocks as I4x4 records with MB_I8X8 (P264PARSE_OPT_INTRA8X8) - for pictures that go to
+        a backend that knows the record, as HipReconstructor does; off, such a macroblock ends its slice with an error"""
         self.lib = lib or N.load()
-        self.h = self.lib.p264parse_open((1 if quiet else 0) | (2 if strict else 0))
+        self.h = self.lib.p264parse_open((1 if quiet else 0) | (2 if strict else 0) | (4 if intra8x8 else 0))
         if not self.h:
             raise P264Error("p264parse_open failed")
 
@@ -295,16 +297,23 @@ class HipReconstructor:
 
     def last_launch(self):
         """The launch shapes of the last reconstruct call (p264hip_launch_info_t as a dict; what depends on the batch's CONTENT
-        rather than its size has its own accessor: last_t8x8_wgs)."""
+        rather than its size has its own accessor: last_t8x8_wgs, last_intra_i8)."""
         li = N.LaunchInfo()
         self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
-        return {n: int(getattr(li, n)) for n, _ in N.LaunchInfo._fields_ if n not in ("reserved", "t8x8_wgs")}
+        return {n: int(getattr(li, n)) for n, _ in N.LaunchInfo._fields_ if n not in ("reserved", "t8x8_wgs", "intra_i8")}
 
     def last_t8x8_wgs(self):
         """Workgroups of k_t8x8 in the last reconstruct call: 0 unless a picture of the batch had transform_8x8."""
         li = N.LaunchInfo()
         self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
         return int(li.t8x8_wgs)
+
+    def last_intra_i8(self):
+        """1 where the last reconstruct call ran the Intra 8x8 instances of the intra kernels (a picture of the batch had
+        T8X8_INTRA in transform_8x8), else 0."""
+        li = N.LaunchInfo()
+        self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
+        return int(li.intra_i8)
 
 
 def device_count(lib=None):

@@ -78,6 +78,11 @@
  *                            8x8 scan order (int16); [--t8x8-intra PCT] PCT percent of the I_NxN macroblocks carry the flag too
  *                            (Intra 8x8 prediction, written on as Intra4x4: a stream for a decoder to refuse).  Without --t8x8
  *                            the streams are what they were, byte for byte.
+ *            [--i8x8 PCT]    (needs --t8x8) PCT percent of the I_NxN macroblocks are real Intra 8x8 macroblocks: the flag, four
+ *                            Intra8x8PredModes legal for the block's neighbours and coded against the predictor of 8.3.2.1, luma as
+ *                            8x8 blocks in both coders (they appear in --dump-t8x8 like flagged inter macroblocks); [--dump-i8x8 f]
+ *                            per picture uint32 macroblocks, then per macroblock the flag and the four modes.  --t8x8-intra has
+ *                            no effect beside it.  Without --i8x8 the streams are what they were, byte for byte.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -149,6 +154,7 @@ static int8_t  *i4m;                        /* [mb][16], 2 for non-I4x4 */
 static int cur;                             /* current MB index */
 
 static int opt_pps_alt = 0, cur_pps = 0;
+static int opt_i8x8 = -1;                     /* --i8x8 PCT (-1: not given): see put_intra */
 static int opt_t8x8 = -1, opt_t8x8_intra = 0;   /* --t8x8 PCT (-1: not given), --t8x8-intra PCT: see put_inter_tail */
 static int opt_wp = 0, opt_wp_bi = 0, opt_wp_dup = 0, opt_wp_identity = 0, opt_wp_differ = 0, opt_wp_bad_sum = 0;
 static FILE *dump_wp = NULL;
@@ -473,6 +479,27 @@ static int pred_i4mode(int mbx, int mby, int blk)
     return m < 0 ? 2 : m;
 }
 
+/* --i8x8 PCT (needs --t8x8): PCT percent of the I_NxN macroblocks are Intra 8x8 macroblocks (7.3.5: transform_size_8x8_flag 1, four
+ * prev_intra8x8_pred_mode_flag / rem_intra8x8_pred_mode pairs, luma as 8x8 blocks).  The modes are drawn legal for the availability
+ * of the 8x8 block (6.4.11.2; block 3 has no top-right, which no mode needs: it is replicated) and coded against the predictor of
+ * 8.3.2.1.  i4m[] keeps the mode of 8x8 block k at 4k .. 4k+3: the Intra4x4 predictor of a neighbour (8.3.1.1) and pred_i8mode read
+ * Intra4x4 and Intra 8x8 neighbours with one look-up.  [--dump-i8x8 f] per picture uint32 macroblocks, then per macroblock the
+ * flag and the four modes (five bytes).  Without the option nothing here draws a number. */
+static FILE *dump_i8;
+static void rand_block8(int16_t *lv);
+static int pred_i8mode(int mbx, int mby, int k)
+{
+    int ma, mb;
+    if (k & 1) ma = i4m[cur * 16 + 4 * (k - 1)];
+    else if (iavail(mbx - 1, mby)) ma = mb_type[cur - 1] == T_I4 ? i4m[(cur - 1) * 16 + 4 * (k + 1) + 1] : 2;
+    else ma = -1;
+    if (k & 2) mb = i4m[cur * 16 + 4 * (k - 2)];
+    else if (iavail(mbx, mby - 1)) mb = mb_type[cur - W] == T_I4 ? i4m[(cur - W) * 16 + 4 * (k + 2) + 2] : 2;
+    else mb = -1;
+    int m = ma < mb ? ma : mb;
+    return m < 0 ? 2 : m;
+}
+
 /* intra MB (I slice: offset 0; P slice: mb_type + 5) */
 static void put_intra(bw_t *b, int mbx, int mby, int type_offset)
 {
@@ -498,7 +525,38 @@ static void put_intra(bw_t *b, int mbx, int mby, int type_offset)
         sx_mb_type(b, type_offset);
         /* (--t8x8-intra: a flagged I_NxN macroblock is written on as Intra4x4 - a decoder that takes Intra 8x8 reads something else from
          * here on, one that refuses it stops at the flag) */
+        int i8 = 0;
+        if (opt_t8x8 >= 0 && opt_i8x8 >= 0) { i8 = pct(opt_i8x8); sx_t8x8_flag(b, i8); }
+        else
         if (opt_t8x8 >= 0) sx_t8x8_flag(b, pct(opt_t8x8_intra));
+        for (int k = 0; i8 && k < 4; k++) {
+            const int l = (k & 1) || L, t = (k & 2) || T, tl = k == 3 ? 1 : k == 2 ? L : k == 1 ? T : TL;
+            int legal[9], nl = 0;
+            if (t) legal[nl++] = 0;
+            if (l) legal[nl++] = 1;
+            legal[nl++] = 2;
+            if (t) { legal[nl++] = 3; legal[nl++] = 7; }
+            if (l && t && tl) { legal[nl++] = 4; legal[nl++] = 5; legal[nl++] = 6; }
+            if (l) legal[nl++] = 8;
+            const int mode = legal[rnd(nl)], pred = pred_i8mode(mbx, mby, k);
+            memset(i4m + cur * 16 + 4 * k, mode, 4);
+            sx_i4mode(b, mode, pred);
+        }
+        if (i8) {
+            int16_t (*l8)[64] = (int16_t (*)[64])(w_t8lv + (size_t)cur * 256);
+            for (int q = 0; q < 4; q++) if (cbp & (1 << q)) rand_block8(l8[q]);
+            w_t8cbp[cur] = (uint8_t)(cbp & 15);
+            int legal[4], nl = 0;
+            legal[nl++] = 0;
+            if (L) legal[nl++] = 1;
+            if (T) legal[nl++] = 2;
+            if (L && T && TL) legal[nl++] = 3;
+            sx_chroma_mode(b, legal[rnd(nl)]);
+            sx_cbp(b, cbp, 1);
+            if (cbp) { sx_dqp(b, rand_qp_delta()); put_residual(b, mbx, mby, &r, 0, cbp, l8); }
+            else { memset(nnz + (size_t)cur * 24, 0, 24); w_last_dqp = 0; }
+            return;
+        }
         for (int i = 0; i < 16; i++) {
             int bx = blk_x[i], by = blk_y[i];
             int l = bx > 0 || L, t = by > 0 || T;
@@ -975,6 +1033,15 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
             for (int q = 0; q < 4; q++) if (w_t8[m] && (w_t8cbp[m] >> q) & 1) fwrite(w_t8lv + (size_t)m * 256 + q * 64, 2, 64, dump_t8);
         }
     }
+    if (dump_i8) {
+        const uint32_t n = (uint32_t)NMB;
+        fwrite(&n, 4, 1, dump_i8);
+        for (int m = 0; m < NMB; m++) {
+            const uint8_t f = (uint8_t)(opt_i8x8 >= 0 && w_t8[m] && mb_type[m] == T_I4);
+            const uint8_t rec[5] = { f, (uint8_t)i4m[m * 16], (uint8_t)i4m[m * 16 + 4], (uint8_t)i4m[m * 16 + 8], (uint8_t)i4m[m * 16 + 12] };
+            fwrite(rec, 1, 5, dump_i8);
+        }
+    }
     if (dump_avail) { fwrite(w_avail, 1, (size_t)NMB, dump_avail); fwrite(i4m, 1, (size_t)NMB * 16, dump_avail); }
     if (dump_wp) {
         int16_t rec[3 + 2 * 16 * 3 * 2];
@@ -1065,6 +1132,8 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--dump-slices")) { dump_slices = fopen(argv[i + 1], "wb"); i++; }
         else if (!strcmp(a, "--t8x8")) { opt_t8x8 = v < 0 ? 0 : v > 100 ? 100 : v; i++; }
         else if (!strcmp(a, "--t8x8-intra")) { opt_t8x8_intra = v < 0 ? 0 : v > 100 ? 100 : v; i++; }
+        else if (!strcmp(a, "--i8x8")) { opt_i8x8 = v < 0 ? 0 : v > 100 ? 100 : v; i++; }
+        else if (!strcmp(a, "--dump-i8x8")) { dump_i8 = fopen(argv[i + 1], "wb"); i++; }
         else if (!strcmp(a, "--dump-t8x8")) { dump_t8 = fopen(argv[i + 1], "wb"); i++; }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
@@ -1132,6 +1201,7 @@ int main(int argc, char **argv)
         if (dump_avail) fclose(dump_avail);
         if (dump_slices) fclose(dump_slices);
         if (dump_t8) fclose(dump_t8);
+        if (dump_i8) fclose(dump_i8);
         return 0;
     }
     for (int n = 0; n < frames; n++) {
@@ -1151,5 +1221,6 @@ int main(int argc, char **argv)
     if (dump_avail) fclose(dump_avail);
     if (dump_slices) fclose(dump_slices);
     if (dump_t8) fclose(dump_t8);
+    if (dump_i8) fclose(dump_i8);
     return 0;
 }
