@@ -183,6 +183,18 @@ static void drop_device(p264_t *h)
     for (int i = 0; i < OUT_BUFS; i++) { p264hip_host_free(h->out_mem[i]); h->out_mem[i] = NULL; }
 }
 
+/* the output planes inside one buffer, with the reference's geometry: stride W+64, 32 (16) pad lines above and below */
+typedef struct { int w, h, ys, cs; size_t y, u, v, bytes; } out_geometry_t;      /* y, u, v: the planes' origins inside the buffer */
+static out_geometry_t out_geometry(const p264_t *h)
+{
+    out_geometry_t g;
+    g.w = h->mb_w * 16; g.h = h->mb_h * 16; g.ys = g.w + 64; g.cs = g.ys / 2;
+    const size_t ysz = (size_t)g.ys * (g.h + 64), csz = (size_t)g.cs * (g.h / 2 + 32);
+    g.y = (size_t)g.ys * 32 + 32; g.u = ysz + (size_t)g.cs * 16 + 16; g.v = ysz + csz + (size_t)g.cs * 16 + 16;
+    g.bytes = ysz + 2 * csz;
+    return g;
+}
+
 /* decoder/decoder.c:304-343: new geometry -> new frame store (device) and output planes (host) */
 static int ensure_device(p264_t *h)
 {
@@ -195,16 +207,14 @@ static int ensure_device(p264_t *h)
         h->hip = NULL;
         return -1;
     }
-    /* host planes with the reference's geometry: stride W+64, 32 (16) pad lines above and below */
-    int w = h->mb_w * 16, hh = h->mb_h * 16, ys = w + 64, cs = ys / 2;
-    size_t ysz = (size_t)ys * (hh + 64), csz = (size_t)cs * (hh / 2 + 32);
+    const out_geometry_t g = out_geometry(h);
     for (int i = 0; i < OUT_BUFS; i++) {
-        h->out_mem[i] = (uint8_t *)p264hip_host_alloc(ysz + 2 * csz);      /* pinned: the plane copies are real DMA */
+        h->out_mem[i] = (uint8_t *)p264hip_host_alloc(g.bytes);      /* pinned: the plane copies are real DMA */
         if (!h->out_mem[i]) return -1;
-        memset(h->out_mem[i], 0, ysz + 2 * csz);
+        memset(h->out_mem[i], 0, g.bytes);
     }
     h->generation = gen;
-    h->param.i_width = w; h->param.i_height = hh;
+    h->param.i_width = g.w; h->param.i_height = g.h;
     return 0;
 }
 
@@ -220,20 +230,19 @@ int p264_decoder_decode(p264_t *h, p264_picture_t **pp_pic, p264_nal_t *nal)
      * conversion and the plane copies are enqueued back to back and p264hip_sync waits for all of them (the API hands the
      * planes of THIS picture back from THIS call, decoder/decoder.c:652-657: nothing can be deferred past the return) */
     if (p264hip_submit_async(h->hip, 0, pic) != P264HIP_OK) { fprintf(stderr, "p264amd: %s\n", p264hip_last_error()); return -1; }
-    int w = h->mb_w * 16, hh = h->mb_h * 16, ys = w + 64, cs = ys / 2;
-    size_t ysz = (size_t)ys * (hh + 64), csz = (size_t)cs * (hh / 2 + 32);
+    const out_geometry_t g = out_geometry(h);
     uint8_t *base = h->out_mem[h->out_next];
     h->out_next = (h->out_next + 1) % OUT_BUFS;
-    uint8_t *y = base + (size_t)ys * 32 + 32, *u = base + ysz + (size_t)cs * 16 + 16, *v = base + ysz + csz + (size_t)cs * 16 + 16;
-    if (p264hip_read_frame_async(h->hip, 0, pic->dst_slot, y, ys, u, v, cs) != P264HIP_OK || p264hip_sync(h->hip) != P264HIP_OK) {
+    uint8_t *y = base + g.y, *u = base + g.u, *v = base + g.v;
+    if (p264hip_read_frame_async(h->hip, 0, pic->dst_slot, y, g.ys, u, v, g.cs) != P264HIP_OK || p264hip_sync(h->hip) != P264HIP_OK) {
         fprintf(stderr, "p264amd: %s\n", p264hip_last_error());
         return -1;
     }
     p264_picture_t *o = &h->pic;
     memset(o, 0, sizeof *o);
-    o->i_width = w; o->i_height = hh;
+    o->i_width = g.w; o->i_height = g.h;
     o->img.i_csp = P264_CSP_I420; o->img.i_plane = 3;
-    o->img.i_stride[0] = ys; o->img.i_stride[1] = cs; o->img.i_stride[2] = cs;
+    o->img.i_stride[0] = g.ys; o->img.i_stride[1] = g.cs; o->img.i_stride[2] = g.cs;
     o->img.plane[0] = y; o->img.plane[1] = u; o->img.plane[2] = v;
     *pp_pic = o;
     return 0;

@@ -17,6 +17,7 @@
 #include "p264parse.h"
 #include "p264_dropin.h"
 #include "host_cpu.h"
+#include "annexb_reader.h"
 
 static __thread char g_err[512] = "";
 static int fail(const char *fmt, ...)
@@ -30,6 +31,21 @@ int p264fan_set_error(const char *fmt, ...)
 {
     va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
     return -1;
+}
+/* keep the error text across calls that may overwrite it */
+typedef struct { char text[sizeof g_err]; } err_keep_t;
+static void err_keep(err_keep_t *k) { memcpy(k->text, g_err, sizeof g_err); }
+static void err_restore(const err_keep_t *k) { memcpy(g_err, k->text, sizeof g_err); }
+/* fit *buf to `need` bytes (contents are not kept): grown with a quarter to spare, never shrunk.  -1 = out of memory, the
+ * buffer is gone then */
+static int fit_buffer(uint8_t **buf, size_t *cap, size_t need)
+{
+    if (need <= *cap) return 0;
+    free(*buf); *cap = 0;
+    *buf = (uint8_t *)malloc(need + need / 4);
+    if (!*buf) return -1;
+    *cap = need + need / 4;
+    return 0;
 }
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 
@@ -45,11 +61,21 @@ static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t
  *   worker -> root   fan_status_t                    0, or what failed on the worker (it keeps serving: the root ends the job
  *                                                    with FAN_FINISHED at the next round boundary)
  *   worker -> root   n frames of MB-aligned I420     only when the status is 0
- * The root sends FAN_FINISHED only where a worker expects a control block.  Everything on the root that can fail
- * without the transport failing (parse, allocation, packing) happens BEFORE the round's control block goes out, and a
- * failure of the root's own reconstruction is reported only after the round's gather: the root never leaves a worker
- * in the middle of a round.  If the transport itself fails there is nothing left to say - both transports' calls
- * return an error then (TCP: peer closed). */
+ * Each line is a step of the two loops further down, named after it: the root's root_scatter sends the first three (the
+ * FAN_FINISHED block: root_finish) and its root_gather receives the last two; the worker receives them in worker_recv_ctrl,
+ * worker_recv_heads and worker_recv_pictures and sends both answers in worker_answer.  What the steps keep, by number in their
+ * comments:
+ *   1. Everything on the root that can fail without the transport failing (parse, allocation, packing, opening the backend)
+ *      happens BEFORE the round's control block goes out.
+ *   2. A failure of the root's own reconstruction is reported only after the round's gather.  With 1: the root never leaves
+ *      a worker in the middle of a round.
+ *   3. A worker always receives the round's pictures, whatever state it is in; what fails there becomes the round's status, and
+ *      the first failure every later round's.  FAN_FINISHED only arrives where a worker expects a control block.
+ *   4. A rank that cannot stay in step (`fatal`) aborts the transport and keeps its error text.  A plain transport failure does
+ *      not: there is nothing left to say - both transports' calls return an error then (TCP: peer closed).
+ *   5. Order and sizes of the messages are fixed: the table above, the structs below.
+ *   6. The error texts are part of the interface (callers and tests match on them).
+ *   7. Every field of p264fan_stats_t is accumulated by one step, named in that step's comment. */
 #define FAN_MAX_PER_ROUND 64            /* pictures one worker takes per round */
 #define FAN_FINISHED (-1)
 typedef struct {                        /* root -> worker, once per round, fixed size */
@@ -136,6 +162,12 @@ static int hipbk_sync(void *ctx)
     }
     return p264hip_sync(b->hip) == P264HIP_OK ? 0 : fail("%s", p264hip_last_error());
 }
+/* one more picture of the round: its stream (= input slot), frame-store slot and where its frame goes (NULL: planes on the device) */
+static void hipbk_note(hipbk_t *b, int s, int dst_slot, uint8_t *i420)
+{
+    b->stream[b->n_pend] = s; b->slot[b->n_pend] = dst_slot; b->out[b->n_pend] = i420;
+    b->n_pend++;
+}
 static int hipbk_reconstruct(void *ctx, int s, const p264hip_picture_t *pic, uint8_t *i420)
 {
     hipbk_t *b = (hipbk_t *)ctx;
@@ -143,8 +175,7 @@ static int hipbk_reconstruct(void *ctx, int s, const p264hip_picture_t *pic, uin
     for (int i = 0; i < b->n_pend; i++)
         if (b->stream[i] == s) { if (hipbk_sync(b)) return -1; break; }     /* (a second picture of a stream: the first one has to be through) */
     if (p264hip_upload_async(b->hip, s, pic) != P264HIP_OK) return fail("%s", p264hip_last_error());
-    b->stream[b->n_pend] = s; b->slot[b->n_pend] = pic->dst_slot; b->out[b->n_pend] = i420;
-    b->n_pend++;
+    hipbk_note(b, s, pic->dst_slot, i420);
     return 0;
 }
 /* the device road: the picture's arrays are written into the stream's input slot by the transport */
@@ -162,8 +193,7 @@ static int hipbk_reconstruct_reserved(void *ctx, int s, const p264hip_picture_t 
     hipbk_t *b = (hipbk_t *)ctx;
     if (s < 0 || s >= b->n_local || b->n_pend >= b->n_local) return fail("local stream %d out of range", s);
     if (p264hip_input_commit(b->hip, s) != P264HIP_OK) return fail("%s", p264hip_last_error());
-    b->stream[b->n_pend] = s; b->slot[b->n_pend] = desc->dst_slot; b->out[b->n_pend] = NULL;
-    b->n_pend++;
+    hipbk_note(b, s, desc->dst_slot, NULL);
     return 0;
 }
 static int hipbk_planes(void *ctx, int k, void **dev, size_t *bytes)
@@ -210,8 +240,7 @@ static int tcp_nop(void *c) { (void)c; return 0; }
  * ranks share one GPU (tests of the device road; RCCL needs one GPU per rank) */
 static uint8_t *tcp_bounce(tcp_t *t, size_t n)
 {
-    if (n > t->bounce_cap) { free(t->bounce); t->bounce = (uint8_t *)malloc(n + n / 4); t->bounce_cap = t->bounce ? n + n / 4 : 0; }
-    if (!t->bounce) fail("out of memory");
+    if (fit_buffer(&t->bounce, &t->bounce_cap, n) || !t->bounce) fail("out of memory");
     return t->bounce;
 }
 static int tcp_send_dev(void *c, int peer, const void *dev, size_t n)
@@ -318,111 +347,171 @@ void p264fan_close(p264fan *f)
     if (f->t.close) f->t.close(f->t.ctx);
     free(f);
 }
-static int gb(p264fan *f) { return f->t.group_begin ? f->t.group_begin(f->t.ctx) : 0; }
-static int ge(p264fan *f) { return f->t.group_end ? f->t.group_end(f->t.ctx) : 0; }
 static int bk_sync(p264fan *f) { return (f->bk.sync && f->bk_ctx) ? f->bk.sync(f->bk_ctx) : 0; }
+
+/* One step of a round's exchange: n transfers of one kind, posted inside one group_begin / group_end.  Any failure in it is
+ * the transport's, and ends the rank's loop: there is nobody left to talk to. */
+typedef enum { FAN_SEND, FAN_RECV, FAN_SEND_DEV, FAN_RECV_DEV } fan_dir_t;
+typedef struct { int peer; void *buf; size_t bytes; } fan_xfer_t;
+static int post_group(p264fan *f, fan_dir_t dir, const fan_xfer_t *x, int n)
+{
+    if (f->t.group_begin && f->t.group_begin(f->t.ctx)) return -1;
+    int rc = 0;
+    for (int i = 0; i < n && !rc; i++)
+        switch (dir) {
+        case FAN_SEND:     rc = f->t.send(f->t.ctx, x[i].peer, x[i].buf, x[i].bytes); break;
+        case FAN_RECV:     rc = f->t.recv(f->t.ctx, x[i].peer, x[i].buf, x[i].bytes); break;
+        case FAN_SEND_DEV: rc = f->t.send_dev(f->t.ctx, x[i].peer, x[i].buf, x[i].bytes); break;
+        case FAN_RECV_DEV: rc = f->t.recv_dev(f->t.ctx, x[i].peer, x[i].buf, x[i].bytes); break;
+        }
+    if (f->t.group_end && f->t.group_end(f->t.ctx)) rc = -1;
+    return rc ? -1 : 0;
+}
+
+/* ---------------------------------------------------------------- worker ---------------- */
+/* A round on a worker, in the words of the protocol comment above: receive the control block, worker_recv_heads,
+ * worker_open_backend_once, worker_recv_pictures, worker_reconstruct, worker_answer.  Only a transport failure (or a rank out of
+ * step: `fatal`) ends the loop; whatever else fails becomes the round's status (w->st). */
+typedef struct {
+    p264fan *f;
+    int dev_road;                       /* the device road: pictures straight into their input slots, planes straight out of the conversion buffers */
+    fan_head_t *heads;                  /* [FAN_MAX_PER_ROUND] the round's descriptors */
+    uint8_t *msg[FAN_MAX_PER_ROUND]; size_t cap[FAN_MAX_PER_ROUND];       /* the round's packed pictures (host road) */
+    uint8_t *out; size_t frame; int out_pinned;                           /* the round's frames (host road), `frame` bytes each */
+    int on_device;                      /* this round goes the device road */
+    void *slot_dev[FAN_MAX_PER_ROUND], *plane_dev[FAN_MAX_PER_ROUND];
+    fan_xfer_t x[FAN_MAX_PER_ROUND];
+    fan_status_t st;                    /* the round's answer */
+    char first_err[248];                /* the first round that failed: every later round answers with it */
+    int fatal;                          /* this rank cannot stay in step */
+} worker_t;
+
+static int worker_init(worker_t *w, p264fan *f)
+{
+    memset(w, 0, sizeof *w);
+    w->f = f;
+    w->dev_road = f->t.recv_dev && f->t.send_dev && f->bk.reserve && f->bk.reconstruct_reserved && f->bk.planes;
+    w->heads = (fan_head_t *)malloc(sizeof(fan_head_t) * FAN_MAX_PER_ROUND);
+    if (!w->heads) { w->fatal = 1; return fail("out of memory"); }
+    return 0;
+}
+/* Invariant 4: leaving out of step (`fatal`) aborts the transport - the root must not wait for this rank's status or frames
+ * (RCCL has no "peer closed") - and keeps the error text; a plain transport failure does not abort.  Invariant 3: a worker
+ * that left in step, on FINISHED, still returns its first error. */
+static int worker_free(worker_t *w, int rc)
+{
+    if (w->fatal && w->f->t.abort) { err_keep_t keep; err_keep(&keep); w->f->t.abort(w->f->t.ctx); err_restore(&keep); }
+    for (int k = 0; k < FAN_MAX_PER_ROUND; k++) free(w->msg[k]);
+    free(w->heads);
+    if (w->out) frames_free(w->out, w->out_pinned);
+    if (!rc && w->first_err[0]) rc = fail("%s", w->first_err);    /* the job failed on this worker, even though it left in step */
+    return rc;
+}
+/* The round's control block - or FAN_FINISHED, which only ever arrives here (invariant 3).  A block out of range means this
+ * rank is out of step: nothing sane left to do (invariant 4). */
+static int worker_recv_ctrl(worker_t *w, fan_ctrl_t *c)
+{
+    const fan_xfer_t x = { 0, c, sizeof *c };
+    if (post_group(w->f, FAN_RECV, &x, 1)) return -1;
+    if (c->n == FAN_FINISHED) return 0;
+    if (c->n < 0 || c->n > FAN_MAX_PER_ROUND) { w->fatal = 1; return fail("worker %d: bad control block", w->f->rank); }
+    memset(&w->st, 0, sizeof w->st); w->st.n = c->n;
+    return 0;
+}
+/* The round's descriptors, one message (invariant 5: none when the round brings this worker no picture).  A bad head, or a
+ * round that failed earlier - this worker's frame stores are stale then - is the round's status (invariant 3). */
+static int worker_recv_heads(worker_t *w, const fan_ctrl_t *c)
+{
+    const fan_xfer_t x = { 0, w->heads, sizeof(fan_head_t) * (size_t)c->n };
+    if (c->n && post_group(w->f, FAN_RECV, &x, 1)) return -1;
+    for (int k = 0; k < c->n && !w->st.rc; k++) if (check_head(&w->heads[k], c->bytes[k])) w->st.rc = -1;
+    if (w->first_err[0]) { w->st.rc = -1; fail("%s", w->first_err); }
+    return 0;
+}
+/* The backend and the frame area, at the first round that is sound; a failure is the round's status (invariant 3). */
+static void worker_open_backend_once(worker_t *w, const fan_ctrl_t *c)
+{
+    p264fan *f = w->f;
+    if (w->st.rc || f->bk_ctx) return;
+    if (f->bk.open(&f->bk_ctx, f->device, c->mb_w, c->mb_h, c->n_local_streams, c->slots)) { w->st.rc = -1; f->bk_ctx = NULL; return; }
+    w->frame = (size_t)c->mb_w * c->mb_h * 384;
+    if (w->dev_road) return;
+    w->out = frames_alloc(w->frame * FAN_MAX_PER_ROUND, &w->out_pinned);
+    if (!w->out) { w->st.rc = -1; fail("worker %d: out of memory", f->rank); }
+}
+/* Invariant 3: the round's pictures are ALWAYS received, whatever state this worker is in - the error text of the state kept
+ * across the receives.  Device road: every picture's slot is reserved first; if that fails for one of them the whole round
+ * goes to host buffers and is answered with the error.  No memory to receive into: out of step (invariant 4). */
+static int worker_recv_pictures(worker_t *w, const fan_ctrl_t *c)
+{
+    p264fan *f = w->f;
+    w->on_device = w->dev_road && !w->st.rc;
+    for (int k = 0; k < c->n && w->on_device; k++) {
+        size_t bytes = 0;
+        if (f->bk.reserve(f->bk_ctx, w->heads[k].local_stream, &w->heads[k].desc, &w->slot_dev[k], &bytes) || bytes != c->bytes[k]) {
+            if (bytes && bytes != c->bytes[k]) fail("worker %d: slot of %zu bytes for a picture of %u", f->rank, bytes, c->bytes[k]);
+            w->st.rc = -1; w->on_device = 0;
+        }
+    }
+    for (int k = 0; k < c->n && !w->on_device; k++)
+        if (fit_buffer(&w->msg[k], &w->cap[k], c->bytes[k])) { w->fatal = 1; return fail("worker %d: out of memory", f->rank); }
+    for (int k = 0; k < c->n; k++) w->x[k] = (fan_xfer_t){ 0, w->on_device ? w->slot_dev[k] : (void *)w->msg[k], c->bytes[k] };
+    err_keep_t keep; err_keep(&keep);
+    if (post_group(f, w->on_device ? FAN_RECV_DEV : FAN_RECV, w->x, c->n)) return -1;
+    if (w->st.rc) err_restore(&keep);
+    return 0;
+}
+/* Reconstruct the round; a failure becomes the round's status, and the first one every later round's (invariant 3). */
+static void worker_reconstruct(worker_t *w, const fan_ctrl_t *c)
+{
+    p264fan *f = w->f;
+    fan_status_t *st = &w->st;
+    for (int k = 0; k < c->n && !st->rc; k++) {
+        if (w->on_device) { if (f->bk.reconstruct_reserved(f->bk_ctx, w->heads[k].local_stream, &w->heads[k].desc)) st->rc = -1; continue; }
+        p264hip_picture_t pic; int ls = 0;
+        if (unpack_picture(&w->heads[k], w->msg[k], c->bytes[k], &pic, &ls) || f->bk.reconstruct(f->bk_ctx, ls, &pic, w->out + w->frame * (size_t)k)) st->rc = -1;
+    }
+    if (!st->rc && bk_sync(f)) st->rc = -1;
+    for (int k = 0; k < c->n && !st->rc && w->on_device; k++) {
+        size_t bytes = 0;
+        if (f->bk.planes(f->bk_ctx, k, &w->plane_dev[k], &bytes) || bytes != w->frame) {
+            if (bytes && bytes != w->frame) fail("worker %d: planes of %zu bytes, a frame has %zu", f->rank, bytes, w->frame);
+            st->rc = -1;
+        }
+    }
+    if (!st->rc) return;
+    snprintf(st->msg, sizeof st->msg, "%.236s", g_err[0] ? g_err : "reconstruction failed");
+    if (!w->first_err[0]) snprintf(w->first_err, sizeof w->first_err, "%.236s", st->msg);
+}
+/* The status block, then - only when the status is 0 - the round's frames (invariant 5). */
+static int worker_answer(worker_t *w, const fan_ctrl_t *c)
+{
+    w->st.device_road = w->on_device && !w->st.rc && c->n > 0;
+    const fan_xfer_t x = { 0, &w->st, sizeof w->st };
+    if (post_group(w->f, FAN_SEND, &x, 1)) return -1;
+    if (w->st.rc) return 0;
+    for (int k = 0; k < c->n; k++) w->x[k] = (fan_xfer_t){ 0, w->on_device ? w->plane_dev[k] : (void *)(w->out + w->frame * (size_t)k), w->frame };
+    return post_group(w->f, w->on_device ? FAN_SEND_DEV : FAN_SEND, w->x, c->n);
+}
 
 int p264fan_worker_run(p264fan *f)
 {
     if (!f || f->rank == 0) return fail("p264fan_worker_run: not a worker");
-    uint8_t *msg[FAN_MAX_PER_ROUND] = { 0 }; size_t cap[FAN_MAX_PER_ROUND] = { 0 };
-    fan_head_t *heads = (fan_head_t *)malloc(sizeof(fan_head_t) * FAN_MAX_PER_ROUND);
-    uint8_t *out = NULL; size_t frame = 0; int out_pinned = 0;
-    int rc = heads ? 0 : fail("out of memory"), fatal = heads ? 0 : 1;  /* rc: transport failures only, they end the loop; fatal: this rank cannot stay in step */
-    char first_err[248] = "";
-    /* the device road: pictures straight into their input slots, planes straight out of the conversion buffers */
-    const int dev_road = f->t.recv_dev && f->t.send_dev && f->bk.reserve && f->bk.reconstruct_reserved && f->bk.planes;
+    worker_t w;
+    int rc = worker_init(&w, f);        /* rc: transport failures (and `fatal`) only - they end the loop */
     while (!rc) {
         fan_ctrl_t c;
-        if (gb(f) || f->t.recv(f->t.ctx, 0, &c, sizeof c) || ge(f)) { rc = -1; break; }
-        if (c.n == FAN_FINISHED) break;
-        if (c.n < 0 || c.n > FAN_MAX_PER_ROUND) { rc = fail("worker %d: bad control block", f->rank); fatal = 1; break; }   /* (out of step: nothing sane left to do) */
-        fan_status_t st; memset(&st, 0, sizeof st); st.n = c.n;
-        /* ---- the round's descriptors */
-        if (c.n && (gb(f) || f->t.recv(f->t.ctx, 0, heads, sizeof(fan_head_t) * (size_t)c.n) || ge(f))) { rc = -1; break; }
-        for (int k = 0; k < c.n && !st.rc; k++) if (check_head(&heads[k], c.bytes[k])) st.rc = -1;
-        /* ---- the backend, once */
-        if (!st.rc && !f->bk_ctx && !first_err[0]) {
-            if (f->bk.open(&f->bk_ctx, f->device, c.mb_w, c.mb_h, c.n_local_streams, c.slots)) { st.rc = -1; f->bk_ctx = NULL; }
-            else {
-                frame = (size_t)c.mb_w * c.mb_h * 384;
-                if (!dev_road) { out = frames_alloc(frame * FAN_MAX_PER_ROUND, &out_pinned); if (!out) { st.rc = -1; fail("worker %d: out of memory", f->rank); } }
-            }
-        }
-        if (first_err[0]) { st.rc = -1; fail("%s", first_err); }      /* an earlier round failed: this worker's frame stores are stale */
-        /* ---- the round's pictures: always received, whatever state this worker is in.  Device road: every picture's slot is
-         *      reserved first; if that fails for one of them the whole round goes to host buffers and is answered with the error */
-        void *slot_dev[FAN_MAX_PER_ROUND]; int on_device = dev_road && !st.rc;
-        for (int k = 0; k < c.n && on_device; k++) {
-            size_t bytes = 0;
-            if (f->bk.reserve(f->bk_ctx, heads[k].local_stream, &heads[k].desc, &slot_dev[k], &bytes) || bytes != c.bytes[k]) { if (bytes && bytes != c.bytes[k]) fail("worker %d: slot of %zu bytes for a picture of %u", f->rank, bytes, c.bytes[k]); st.rc = -1; on_device = 0; }
-        }
-        if (!on_device)
-            for (int k = 0; k < c.n; k++)
-                if (c.bytes[k] > cap[k]) {
-                    free(msg[k]); cap[k] = 0;
-                    msg[k] = (uint8_t *)malloc((size_t)c.bytes[k] + c.bytes[k] / 4);
-                    if (!msg[k]) { rc = fail("worker %d: out of memory", f->rank); fatal = 1; break; }       /* (cannot even receive: the transport is aborted below) */
-                    cap[k] = (size_t)c.bytes[k] + c.bytes[k] / 4;
-                }
-        if (rc) break;
-        char keep_err[sizeof g_err]; memcpy(keep_err, g_err, sizeof keep_err);
-        if (gb(f)) { rc = -1; break; }
-        for (int k = 0; k < c.n && !rc; k++)
-            if (on_device ? f->t.recv_dev(f->t.ctx, 0, slot_dev[k], c.bytes[k]) : f->t.recv(f->t.ctx, 0, msg[k], c.bytes[k])) rc = -1;
-        if (ge(f) || rc) { rc = -1; break; }
-        if (st.rc) memcpy(g_err, keep_err, sizeof keep_err);
-        /* ---- reconstruct; a failure becomes the round's status and the worker keeps serving */
-        for (int k = 0; k < c.n && !st.rc; k++) {
-            if (on_device) { if (f->bk.reconstruct_reserved(f->bk_ctx, heads[k].local_stream, &heads[k].desc)) st.rc = -1; continue; }
-            p264hip_picture_t pic; int ls = 0;
-            if (unpack_picture(&heads[k], msg[k], c.bytes[k], &pic, &ls) || f->bk.reconstruct(f->bk_ctx, ls, &pic, out + frame * (size_t)k)) st.rc = -1;
-        }
-        if (!st.rc && bk_sync(f)) st.rc = -1;
-        void *plane_dev[FAN_MAX_PER_ROUND];
-        for (int k = 0; k < c.n && !st.rc && on_device; k++) {
-            size_t bytes = 0;
-            if (f->bk.planes(f->bk_ctx, k, &plane_dev[k], &bytes) || bytes != frame) { if (bytes && bytes != frame) fail("worker %d: planes of %zu bytes, a frame has %zu", f->rank, bytes, frame); st.rc = -1; }
-        }
-        if (st.rc) { snprintf(st.msg, sizeof st.msg, "%.236s", g_err[0] ? g_err : "reconstruction failed"); if (!first_err[0]) snprintf(first_err, sizeof first_err, "%.236s", st.msg); }
-        /* ---- status, then the frames */
-        st.device_road = on_device && !st.rc && c.n > 0;
-        if (gb(f) || f->t.send(f->t.ctx, 0, &st, sizeof st) || ge(f)) { rc = -1; break; }
-        if (st.rc) continue;
-        if (gb(f)) { rc = -1; break; }
-        for (int k = 0; k < c.n && !rc; k++)
-            if (on_device ? f->t.send_dev(f->t.ctx, 0, plane_dev[k], frame) : f->t.send(f->t.ctx, 0, out + frame * (size_t)k, frame)) rc = -1;
-        if (ge(f) || rc) { rc = -1; break; }
+        if ((rc = worker_recv_ctrl(&w, &c)) || c.n == FAN_FINISHED) break;
+        if ((rc = worker_recv_heads(&w, &c))) break;
+        worker_open_backend_once(&w, &c);
+        if ((rc = worker_recv_pictures(&w, &c))) break;
+        worker_reconstruct(&w, &c);
+        rc = worker_answer(&w, &c);
     }
-    /* leaving out of step: the root must not wait for this rank's status or frames (RCCL has no "peer closed") */
-    if (fatal && f->t.abort) { char keep[sizeof g_err]; memcpy(keep, g_err, sizeof keep); f->t.abort(f->t.ctx); memcpy(g_err, keep, sizeof keep); }
-    for (int k = 0; k < FAN_MAX_PER_ROUND; k++) free(msg[k]);
-    free(heads);
-    if (out) frames_free(out, out_pinned);
-    if (!rc && first_err[0]) rc = fail("%s", first_err);    /* the job failed on this worker, even though it left in step */
-    return rc;
+    return worker_free(&w, rc);
 }
 
-typedef struct { p264parse *parser; const uint8_t *in; int64_t size, pos; uint8_t *rbsp; int64_t rbsp_cap; int done; int64_t pictures; } fstream_t;
-/* next picture of a stream, or NULL at its end */
-static const p264hip_picture_t *next_picture(fstream_t *s, int max_pictures, int *failed)
-{
-    if (s->done || (max_pictures > 0 && s->pictures >= max_pictures)) { s->done = 1; return NULL; }
-    int64_t off, len;
-    while (p264_annexb_next(s->in, s->size, &s->pos, &off, &len)) {
-        if (len < 1) continue;
-        if (len + 8 > s->rbsp_cap) { free(s->rbsp); s->rbsp_cap = len * 2 + 64; s->rbsp = (uint8_t *)malloc((size_t)s->rbsp_cap); if (!s->rbsp) { *failed = 1; return NULL; } }
-        p264_nal_t nal; nal.p_payload = s->rbsp;
-        p264_nal_decode(&nal, (void *)(s->in + off), (int)len);
-        const p264hip_picture_t *pic = NULL;
-        int rc = p264parse_nal(s->parser, nal.i_type, nal.i_ref_idc, nal.p_payload, nal.i_payload, &pic);
-        if (rc < 0) { *failed = 1; return NULL; }
-        if (rc == 1) { s->pictures++; return pic; }
-    }
-    s->done = 1;
-    return NULL;
-}
-
+/* ---------------------------------------------------------------- the root's parse side - */
 /* One round's worth of work, produced by the parse side and consumed by the exchange side: every stream's next picture,
  * PACKED (the parser's arrays only live until the stream's next call; a packed copy lets the next round be parsed while
  * this one travels and is reconstructed - for the root's own streams too). */
@@ -434,7 +523,7 @@ typedef struct {
     char err[200];
 } fan_round_t;
 typedef struct {
-    fstream_t *st; int n_streams, world, max_pictures, threads;
+    annexb_reader_t *st; int n_streams, world, max_pictures, threads;
     fan_round_t rounds[2];
     int ready[2];                       /* 0 free, 1 filled */
     int stop;
@@ -449,15 +538,10 @@ static void *parse_worker(void *arg)
     fan_producer_t *P = j->P; fan_round_t *R = j->R;
     for (int s = j->first; s < P->n_streams; s += j->step) {
         R->len[s] = 0;
-        const p264hip_picture_t *pic = next_picture(&P->st[s], P->max_pictures, &j->failed);
-        if (!pic) continue;
+        const p264hip_picture_t *pic = annexb_reader_next(&P->st[s], P->max_pictures);
+        if (!pic) { if (annexb_reader_failed(&P->st[s])) j->failed = 1; continue; }
         const size_t need = packed_size(pic);
-        if (need > R->cap[s]) {
-            free(R->msg[s]); R->cap[s] = 0;
-            R->msg[s] = (uint8_t *)malloc(need + need / 4);
-            if (!R->msg[s]) { j->failed = 1; continue; }
-            R->cap[s] = need + need / 4;
-        }
+        if (fit_buffer(&R->msg[s], &R->cap[s], need)) { j->failed = 1; continue; }
         if (!need || pack_picture(&R->head[s], R->msg[s], R->cap[s], s / P->world, pic)) { j->failed = 1; continue; }
         R->len[s] = need;
         R->index[s] = P->st[s].pictures - 1;
@@ -513,22 +597,38 @@ static void *producer_main(void *arg)
     return NULL;
 }
 
-int p264fan_root_run(p264fan *f, int n_streams, const uint8_t *const *annexb, const int64_t *sizes, int max_pictures,
-                     p264fan_frame_cb on_frame, void *user, p264fan_stats_t *stats)
+/* ---------------------------------------------------------------- root ------------------ */
+/* A round on the root, in the words of the protocol comment above: wait for the parsed round, root_first_round,
+ * root_check_round, root_scatter, root_own_streams, root_gather, root_deliver; root_finish at the round boundary where the
+ * job ends, whatever ended it. */
+typedef struct {
+    p264fan *f; int n_streams, W, per_rank;         /* per_rank: local streams of every rank (the biggest share) */
+    fan_producer_t P; pthread_t producer; int have_producer;
+    fan_ctrl_t *ctrl; fan_status_t *status;         /* [W] the round's control and status blocks */
+    fan_head_t *heads; int *head_at;                /* the round's descriptors grouped by worker: heads[head_at[r] .. head_at[r + 1]) in the order of r's control block */
+    fan_xfer_t *x;                                  /* [max(n_streams, W)] one step's transfers */
+    uint8_t *frames; size_t frame; int frames_pinned;       /* [n_streams] the round's frames, `frame` bytes each */
+    int mb_w, mb_h, slots;                          /* the job's geometry: the first round's */
+    int rc_local; char err_local[256];              /* the root's own reconstruction of the round */
+    p264fan_frame_cb on_frame; void *user;
+    p264fan_stats_t S; double t0;
+} root_job_t;
+
+static int root_job_init(root_job_t *J, p264fan *f, int n_streams, const uint8_t *const *annexb, const int64_t *sizes, int max_pictures, p264fan_frame_cb on_frame, void *user)
 {
-    if (!f || f->rank != 0 || n_streams < 1 || !annexb || !sizes) return fail("p264fan_root_run: bad argument");
+    memset(J, 0, sizeof *J);
     const int W = f->world;
-    if ((n_streams + W - 1) / W > FAN_MAX_PER_ROUND) return fail("p264fan_root_run: more than %d streams per rank", FAN_MAX_PER_ROUND);
-    fan_producer_t P; memset(&P, 0, sizeof P);
-    P.st = (fstream_t *)calloc((size_t)n_streams, sizeof *P.st);
-    fan_ctrl_t *ctrl = (fan_ctrl_t *)calloc((size_t)W, sizeof *ctrl);
-    fan_status_t *status = (fan_status_t *)calloc((size_t)W, sizeof *status);
-    fan_head_t *heads = (fan_head_t *)malloc(sizeof(fan_head_t) * (size_t)n_streams);     /* a round's descriptors, grouped by worker */
-    int *head_at = (int *)calloc((size_t)W + 1, sizeof(int));
-    uint8_t *frames = NULL; size_t frame = 0; int frames_pinned = 0;
-    int rc = (P.st && ctrl && status && heads && head_at) ? 0 : fail("out of memory");
+    fan_producer_t *P = &J->P;
+    J->f = f; J->n_streams = n_streams; J->W = W; J->per_rank = (n_streams + W - 1) / W; J->on_frame = on_frame; J->user = user;
+    P->st = (annexb_reader_t *)calloc((size_t)n_streams, sizeof *P->st);
+    J->ctrl = (fan_ctrl_t *)calloc((size_t)W, sizeof *J->ctrl);
+    J->status = (fan_status_t *)calloc((size_t)W, sizeof *J->status);
+    J->heads = (fan_head_t *)malloc(sizeof(fan_head_t) * (size_t)n_streams);
+    J->head_at = (int *)calloc((size_t)W + 1, sizeof(int));
+    J->x = (fan_xfer_t *)calloc((size_t)(n_streams > W ? n_streams : W), sizeof *J->x);
+    int rc = (P->st && J->ctrl && J->status && J->heads && J->head_at && J->x) ? 0 : fail("out of memory");
     for (int k = 0; k < 2 && !rc; k++) {
-        fan_round_t *R = &P.rounds[k];
+        fan_round_t *R = &P->rounds[k];
         R->msg = (uint8_t **)calloc((size_t)n_streams, sizeof *R->msg); R->cap = (size_t *)calloc((size_t)n_streams, sizeof *R->cap);
         R->len = (size_t *)calloc((size_t)n_streams, sizeof *R->len); R->index = (int64_t *)calloc((size_t)n_streams, sizeof *R->index);
         R->head = (fan_head_t *)calloc((size_t)n_streams, sizeof *R->head);
@@ -537,120 +637,192 @@ int p264fan_root_run(p264fan *f, int n_streams, const uint8_t *const *annexb, co
     for (int s = 0; s < n_streams && !rc; s++) {
         /* (Intra 8x8 macroblocks only for the library's own backend on every rank - a plug-in backend's owner has not said that it
          * knows the record, include/p264parse.h) */
-        P.st[s].parser = p264parse_open(P264PARSE_OPT_QUIET | (f->own_bk ? P264PARSE_OPT_INTRA8X8 : 0));
-        P.st[s].in = annexb[s]; P.st[s].size = sizes[s];
-        if (!P.st[s].parser) rc = fail("p264parse_open failed");
+        P->st[s].parser = p264parse_open(P264PARSE_OPT_QUIET | (f->own_bk ? P264PARSE_OPT_INTRA8X8 : 0));
+        annexb_reader_set_input(&P->st[s], annexb[s], sizes[s]);
+        if (!P->st[s].parser) rc = fail("p264parse_open failed");
     }
-    p264fan_stats_t S; memset(&S, 0, sizeof S); S.world = W;
-    P.n_streams = n_streams; P.world = W; P.max_pictures = max_pictures;
-    P.threads = n_streams;                                   /* one parser thread per stream unless P264AMD_FAN_THREADS says otherwise */
-    { const char *e = getenv("P264AMD_FAN_THREADS"); if (e && atoi(e) >= 1) P.threads = atoi(e); }
-    S.parse_threads = P.threads < n_streams ? P.threads : n_streams;
-    if (S.parse_threads > 64) S.parse_threads = 64;
-    pthread_t producer; int have_producer = 0;
+    J->S.world = W;
+    P->n_streams = n_streams; P->world = W; P->max_pictures = max_pictures;
+    P->threads = n_streams;                                  /* one parser thread per stream unless P264AMD_FAN_THREADS says otherwise */
+    { const char *e = getenv("P264AMD_FAN_THREADS"); if (e && atoi(e) >= 1) P->threads = atoi(e); }
+    J->S.parse_threads = P->threads < n_streams ? P->threads : n_streams;
+    if (J->S.parse_threads > 64) J->S.parse_threads = 64;
     if (!rc) {
-        pthread_mutex_init(&P.mu, NULL); pthread_cond_init(&P.cv, NULL);
-        if (pthread_create(&producer, NULL, producer_main, &P)) rc = fail("cannot start the parse thread");
-        else have_producer = 1;
+        pthread_mutex_init(&P->mu, NULL); pthread_cond_init(&P->cv, NULL);
+        if (pthread_create(&J->producer, NULL, producer_main, P)) rc = fail("cannot start the parse thread");
+        else J->have_producer = 1;
     }
-    const double t0 = now_s();
-    int mb_w = 0, mb_h = 0, slots = 0;
-    for (int k = 0; !rc; k ^= 1) {
-        /* ---- the next round, parsed and packed while the previous one travelled */
-        const double w0 = now_s();
-        pthread_mutex_lock(&P.mu);
-        while (!P.ready[k]) pthread_cond_wait(&P.cv, &P.mu);
-        pthread_mutex_unlock(&P.mu);
-        S.parse_wait_seconds += now_s() - w0;
-        fan_round_t *R = &P.rounds[k];
-        if (R->failed) { rc = fail("%s", R->err); break; }
-        if (!R->n) break;
-        if (!mb_w) {
-            mb_w = R->mb_w; mb_h = R->mb_h; slots = R->slots;
-            frame = (size_t)mb_w * mb_h * 384;
-            frames = frames_alloc(frame * (size_t)n_streams, &frames_pinned);
-            if (!frames) { rc = fail("out of memory"); break; }
-            if (f->bk.open(&f->bk_ctx, f->device, mb_w, mb_h, (n_streams + W - 1) / W, slots)) { f->bk_ctx = NULL; rc = -1; break; }
-        }
-        if (R->mb_w != mb_w || R->mb_h != mb_h) { rc = fail("the picture size changed inside the job (%dx%d -> %dx%d macroblocks)", mb_w, mb_h, R->mb_w, R->mb_h); break; }
-        if (R->slots > slots) { rc = fail("a stream now needs %d frame slots, the ranks' frame stores were opened with %d (num_ref_frames grew inside the job)", R->slots, slots); break; }
-        /* ---- scatter: control blocks, then the packed pictures of the remote streams.  From here to the end of the gather
-         *      nothing but the transport may end the round. */
-        const double e0 = now_s();
-        int rc_local = 0; char err_local[256] = "";
-        for (int r = 1; r < W; r++) { memset(&ctrl[r], 0, sizeof ctrl[r]); ctrl[r].mb_w = mb_w; ctrl[r].mb_h = mb_h; ctrl[r].slots = slots; ctrl[r].n_local_streams = (n_streams + W - 1) / W; }
-        for (int s = 0; s < n_streams; s++) {
-            const int r = s % W;
-            if (!R->len[s] || r == 0) continue;
-            ctrl[r].bytes[ctrl[r].n++] = (uint32_t)R->len[s];
-            S.bytes_scattered += (int64_t)R->len[s]; S.pictures_remote++;
-        }
-        /* (the descriptors of worker r's pictures, in the order of its control block: heads[head_at[r] .. head_at[r + 1])) */
-        head_at[0] = head_at[1] = 0;
-        for (int r = 1; r < W; r++) {
-            int at = head_at[r];
-            for (int s = r; s < n_streams; s += W) if (R->len[s]) heads[at++] = R->head[s];
-            head_at[r + 1] = at;
-        }
-        if (gb(f)) { rc = -1; break; }
-        for (int r = 1; r < W && !rc; r++) if (f->t.send(f->t.ctx, r, &ctrl[r], sizeof ctrl[r])) rc = -1;
-        if (ge(f) || rc || gb(f)) { rc = -1; break; }
-        for (int r = 1; r < W && !rc; r++) if (ctrl[r].n && f->t.send(f->t.ctx, r, heads + head_at[r], sizeof(fan_head_t) * (size_t)ctrl[r].n)) rc = -1;
-        if (ge(f) || rc || gb(f)) { rc = -1; break; }
-        for (int s = 0; s < n_streams && !rc; s++) if (R->len[s] && s % W) if (f->t.send(f->t.ctx, s % W, R->msg[s], R->len[s])) rc = -1;
-        if (ge(f) || rc) { rc = -1; break; }
-        S.exchange_seconds += now_s() - e0;
-        /* ---- the root's own streams while the workers are busy */
-        const double r0 = now_s();
-        for (int s = 0; s < n_streams && !rc_local; s += W) {
-            if (!R->len[s]) continue;
-            p264hip_picture_t pic; int ls = 0;
-            if (unpack_picture(&R->head[s], R->msg[s], R->len[s], &pic, &ls) || f->bk.reconstruct(f->bk_ctx, ls, &pic, frames + frame * (size_t)s)) rc_local = -1;
-        }
-        if (!rc_local && bk_sync(f)) rc_local = -1;
-        if (rc_local) snprintf(err_local, sizeof err_local, "root: %.240s", g_err);
-        S.reconstruct_seconds += now_s() - r0;
-        /* ---- gather: every worker's status, then the frames of those that have them */
-        const double g0 = now_s();
-        if (gb(f)) { rc = -1; break; }
-        for (int r = 1; r < W && !rc; r++) if (f->t.recv(f->t.ctx, r, &status[r], sizeof status[r])) rc = -1;
-        if (ge(f) || rc || gb(f)) { rc = -1; break; }
-        for (int s = 0; s < n_streams && !rc; s++)
-            if (R->len[s] && s % W && status[s % W].rc == 0) { if (f->t.recv(f->t.ctx, s % W, frames + frame * (size_t)s, frame)) rc = -1; S.bytes_gathered += (int64_t)frame; }
-        if (ge(f) || rc) { rc = -1; break; }
-        S.exchange_seconds += now_s() - g0;
-        for (int r = 1; r < W; r++) if (!status[r].rc && status[r].device_road) S.device_road_rounds++;
-        for (int r = 1; r < W && !rc; r++)
-            if (status[r].rc) { status[r].msg[sizeof status[r].msg - 1] = 0; rc = fail("worker %d: %s", r, status[r].msg); }
-        if (!rc && rc_local) rc = fail("%s", err_local);
-        if (rc) break;
-        for (int s = 0; s < n_streams; s++) if (R->len[s]) { S.pictures++; if (on_frame) on_frame(user, s, R->index[s], mb_w * 16, mb_h * 16, frames + frame * (size_t)s); }
-        S.rounds++;
-        pthread_mutex_lock(&P.mu); P.ready[k] = 0; pthread_cond_broadcast(&P.cv); pthread_mutex_unlock(&P.mu);
-    }
-    /* ---- round boundary (or a dead transport): tell the workers to leave */
-    char keep[sizeof g_err]; memcpy(keep, g_err, sizeof keep);
-    if (ctrl && f->t.send) {
-        gb(f);
-        for (int r = 1; r < W; r++) { memset(&ctrl[r], 0, sizeof ctrl[r]); ctrl[r].n = FAN_FINISHED; f->t.send(f->t.ctx, r, &ctrl[r], sizeof ctrl[r]); }
-        ge(f);
-    }
-    if (rc) memcpy(g_err, keep, sizeof keep);
-    if (have_producer) {
-        pthread_mutex_lock(&P.mu); P.stop = 1; P.ready[0] = P.ready[1] = 0; pthread_cond_broadcast(&P.cv); pthread_mutex_unlock(&P.mu);
-        pthread_join(producer, NULL);
-        pthread_mutex_destroy(&P.mu); pthread_cond_destroy(&P.cv);
-    }
-    S.seconds = now_s() - t0;
-    S.parse_seconds = P.parse_seconds;
-    if (stats) *stats = S;
-    if (P.st) for (int s = 0; s < n_streams; s++) { if (P.st[s].parser) p264parse_close(P.st[s].parser); free(P.st[s].rbsp); }
+    J->t0 = now_s();
+    return rc;
+}
+static void root_job_free(root_job_t *J)
+{
+    fan_producer_t *P = &J->P;
+    if (P->st) for (int s = 0; s < J->n_streams; s++) annexb_reader_close(&P->st[s]);
     for (int k = 0; k < 2; k++) {
-        fan_round_t *R = &P.rounds[k];
-        if (R->msg) for (int s = 0; s < n_streams; s++) free(R->msg[s]);
+        fan_round_t *R = &P->rounds[k];
+        if (R->msg) for (int s = 0; s < J->n_streams; s++) free(R->msg[s]);
         free(R->msg); free(R->cap); free(R->len); free(R->index); free(R->head);
     }
-    if (frames) frames_free(frames, frames_pinned);
-    free(P.st); free(ctrl); free(status); free(heads); free(head_at);
+    if (J->frames) frames_free(J->frames, J->frames_pinned);
+    free(P->st); free(J->ctrl); free(J->status); free(J->heads); free(J->head_at); free(J->x);
+}
+/* the next round, parsed and packed while the previous one travelled (invariant 7: parse_wait_seconds) / hand its buffers back
+ * to the parse side */
+static fan_round_t *root_wait_round(root_job_t *J, int k)
+{
+    const double w0 = now_s();
+    pthread_mutex_lock(&J->P.mu);
+    while (!J->P.ready[k]) pthread_cond_wait(&J->P.cv, &J->P.mu);
+    pthread_mutex_unlock(&J->P.mu);
+    J->S.parse_wait_seconds += now_s() - w0;
+    return &J->P.rounds[k];
+}
+static void root_release_round(root_job_t *J, int k)
+{
+    pthread_mutex_lock(&J->P.mu); J->P.ready[k] = 0; pthread_cond_broadcast(&J->P.cv); pthread_mutex_unlock(&J->P.mu);
+}
+/* The job's geometry, the frames and the root's backend, from the first round.  Invariant 1: it can fail, so it runs before
+ * the round's control block goes out. */
+static int root_first_round(root_job_t *J, const fan_round_t *R)
+{
+    p264fan *f = J->f;
+    if (J->mb_w) return 0;
+    J->mb_w = R->mb_w; J->mb_h = R->mb_h; J->slots = R->slots;
+    J->frame = (size_t)J->mb_w * J->mb_h * 384;
+    J->frames = frames_alloc(J->frame * (size_t)J->n_streams, &J->frames_pinned);
+    if (!J->frames) return fail("out of memory");
+    if (f->bk.open(&f->bk_ctx, f->device, J->mb_w, J->mb_h, J->per_rank, J->slots)) { f->bk_ctx = NULL; return -1; }
+    return 0;
+}
+/* A later round must fit what every rank opened with: same picture size, no more frame slots.  Invariant 1 again. */
+static int root_check_round(root_job_t *J, const fan_round_t *R)
+{
+    if (R->mb_w != J->mb_w || R->mb_h != J->mb_h) return fail("the picture size changed inside the job (%dx%d -> %dx%d macroblocks)", J->mb_w, J->mb_h, R->mb_w, R->mb_h);
+    if (R->slots > J->slots) return fail("a stream now needs %d frame slots, the ranks' frame stores were opened with %d (num_ref_frames grew inside the job)", R->slots, J->slots);
+    return 0;
+}
+/* Scatter: every worker's control block, then its pictures' heads as one message (none for a worker without a picture in
+ * this round), then the packed pictures (invariant 5).
+ * Invariant 1: from here to the end of the gather nothing but the transport ends the round.  Invariant 7: bytes_scattered,
+ * pictures_remote and this half of exchange_seconds. */
+static int root_scatter(root_job_t *J, const fan_round_t *R)
+{
+    const int W = J->W, n_streams = J->n_streams;
+    fan_ctrl_t *ctrl = J->ctrl;
+    const double e0 = now_s();
+    for (int r = 1; r < W; r++) { memset(&ctrl[r], 0, sizeof ctrl[r]); ctrl[r].mb_w = J->mb_w; ctrl[r].mb_h = J->mb_h; ctrl[r].slots = J->slots; ctrl[r].n_local_streams = J->per_rank; }
+    for (int s = 0; s < n_streams; s++) {
+        const int r = s % W;
+        if (!R->len[s] || r == 0) continue;
+        ctrl[r].bytes[ctrl[r].n++] = (uint32_t)R->len[s];
+        J->S.bytes_scattered += (int64_t)R->len[s]; J->S.pictures_remote++;
+    }
+    J->head_at[0] = J->head_at[1] = 0;
+    for (int r = 1; r < W; r++) {
+        int at = J->head_at[r];
+        for (int s = r; s < n_streams; s += W) if (R->len[s]) J->heads[at++] = R->head[s];
+        J->head_at[r + 1] = at;
+    }
+    for (int r = 1; r < W; r++) J->x[r - 1] = (fan_xfer_t){ r, &ctrl[r], sizeof ctrl[r] };
+    if (post_group(J->f, FAN_SEND, J->x, W - 1)) return -1;
+    int n = 0;
+    for (int r = 1; r < W; r++) if (ctrl[r].n) J->x[n++] = (fan_xfer_t){ r, J->heads + J->head_at[r], sizeof(fan_head_t) * (size_t)ctrl[r].n };
+    if (post_group(J->f, FAN_SEND, J->x, n)) return -1;
+    n = 0;
+    for (int s = 0; s < n_streams; s++) if (R->len[s] && s % W) J->x[n++] = (fan_xfer_t){ s % W, R->msg[s], R->len[s] };
+    if (post_group(J->f, FAN_SEND, J->x, n)) return -1;
+    J->S.exchange_seconds += now_s() - e0;
+    return 0;
+}
+/* The root's own streams while the workers are busy.  Invariant 2: a failure is only noted here (rc_local, err_local);
+ * root_deliver reports it after the round's gather.  Invariant 7: reconstruct_seconds. */
+static void root_own_streams(root_job_t *J, const fan_round_t *R)
+{
+    p264fan *f = J->f;
+    const double r0 = now_s();
+    J->rc_local = 0; J->err_local[0] = 0;
+    for (int s = 0; s < J->n_streams && !J->rc_local; s += J->W) {
+        if (!R->len[s]) continue;
+        p264hip_picture_t pic; int ls = 0;
+        if (unpack_picture(&R->head[s], R->msg[s], R->len[s], &pic, &ls) || f->bk.reconstruct(f->bk_ctx, ls, &pic, J->frames + J->frame * (size_t)s)) J->rc_local = -1;
+    }
+    if (!J->rc_local && bk_sync(f)) J->rc_local = -1;
+    if (J->rc_local) snprintf(J->err_local, sizeof J->err_local, "root: %.240s", g_err);
+    J->S.reconstruct_seconds += now_s() - r0;
+}
+/* Gather: every worker's status, then the frames of those whose status is 0 (invariant 5).  Invariant 7: bytes_gathered, the
+ * other half of exchange_seconds, device_road_rounds. */
+static int root_gather(root_job_t *J, const fan_round_t *R)
+{
+    const int W = J->W;
+    const double g0 = now_s();
+    for (int r = 1; r < W; r++) J->x[r - 1] = (fan_xfer_t){ r, &J->status[r], sizeof J->status[r] };
+    if (post_group(J->f, FAN_RECV, J->x, W - 1)) return -1;
+    int n = 0;
+    for (int s = 0; s < J->n_streams; s++)
+        if (R->len[s] && s % W && J->status[s % W].rc == 0) { J->x[n++] = (fan_xfer_t){ s % W, J->frames + J->frame * (size_t)s, J->frame }; J->S.bytes_gathered += (int64_t)J->frame; }
+    if (post_group(J->f, FAN_RECV, J->x, n)) return -1;
+    J->S.exchange_seconds += now_s() - g0;
+    for (int r = 1; r < W; r++) if (!J->status[r].rc && J->status[r].device_road) J->S.device_road_rounds++;
+    return 0;
+}
+/* The round's outcome: the first worker's error, then the root's own (invariant 2: only now, after the gather), else every
+ * picture to on_frame.  Invariant 7: pictures, rounds. */
+static int root_deliver(root_job_t *J, const fan_round_t *R)
+{
+    for (int r = 1; r < J->W; r++)
+        if (J->status[r].rc) { J->status[r].msg[sizeof J->status[r].msg - 1] = 0; return fail("worker %d: %s", r, J->status[r].msg); }
+    if (J->rc_local) return fail("%s", J->err_local);
+    for (int s = 0; s < J->n_streams; s++)
+        if (R->len[s]) { J->S.pictures++; if (J->on_frame) J->on_frame(J->user, s, R->index[s], J->mb_w * 16, J->mb_h * 16, J->frames + J->frame * (size_t)s); }
+    J->S.rounds++;
+    return 0;
+}
+/* The round boundary where the job ends (or a dead transport): FAN_FINISHED to every worker - each gets its block whatever
+ * happens to the others', so not post_group - with the job's error text kept (invariant 6); then the parse side is stopped and
+ * everything freed.
+ * Invariant 3: this is the only place FINISHED is sent from, and every way out of a round leads here with the workers waiting
+ * for a control block, or with the transport dead.
+ * Invariant 7: seconds, parse_seconds. */
+static int root_finish(root_job_t *J, int rc, p264fan_stats_t *stats)
+{
+    p264fan *f = J->f;
+    fan_producer_t *P = &J->P;
+    err_keep_t keep; err_keep(&keep);
+    if (J->ctrl && f->t.send) {
+        if (f->t.group_begin) f->t.group_begin(f->t.ctx);
+        for (int r = 1; r < J->W; r++) { memset(&J->ctrl[r], 0, sizeof J->ctrl[r]); J->ctrl[r].n = FAN_FINISHED; f->t.send(f->t.ctx, r, &J->ctrl[r], sizeof J->ctrl[r]); }
+        if (f->t.group_end) f->t.group_end(f->t.ctx);
+    }
+    if (rc) err_restore(&keep);
+    if (J->have_producer) {
+        pthread_mutex_lock(&P->mu); P->stop = 1; P->ready[0] = P->ready[1] = 0; pthread_cond_broadcast(&P->cv); pthread_mutex_unlock(&P->mu);
+        pthread_join(J->producer, NULL);
+        pthread_mutex_destroy(&P->mu); pthread_cond_destroy(&P->cv);
+    }
+    J->S.seconds = now_s() - J->t0;
+    J->S.parse_seconds = P->parse_seconds;
+    if (stats) *stats = J->S;
+    root_job_free(J);
     return rc;
+}
+
+int p264fan_root_run(p264fan *f, int n_streams, const uint8_t *const *annexb, const int64_t *sizes, int max_pictures,
+                     p264fan_frame_cb on_frame, void *user, p264fan_stats_t *stats)
+{
+    if (!f || f->rank != 0 || n_streams < 1 || !annexb || !sizes) return fail("p264fan_root_run: bad argument");
+    if ((n_streams + f->world - 1) / f->world > FAN_MAX_PER_ROUND) return fail("p264fan_root_run: more than %d streams per rank", FAN_MAX_PER_ROUND);
+    root_job_t J;
+    int rc = root_job_init(&J, f, n_streams, annexb, sizes, max_pictures, on_frame, user);
+    for (int k = 0; !rc; k ^= 1) {
+        const fan_round_t *R = root_wait_round(&J, k);
+        if (R->failed) { rc = fail("%s", R->err); break; }
+        if (!R->n) break;
+        if ((rc = root_first_round(&J, R)) || (rc = root_check_round(&J, R)) || (rc = root_scatter(&J, R))) break;
+        root_own_streams(&J, R);
+        if ((rc = root_gather(&J, R)) || (rc = root_deliver(&J, R))) break;
+        root_release_round(&J, k);
+    }
+    return root_finish(&J, rc, stats);
 }

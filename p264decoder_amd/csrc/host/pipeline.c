@@ -21,14 +21,12 @@
 #include "p264hip.h"
 #include "p264_dropin.h"
 #include "host_cpu.h"
+#include "annexb_reader.h"
 
 typedef struct {
-    p264parse *parser;
-    const uint8_t *in; int64_t size, pos;
-    uint8_t *rbsp; int64_t rbsp_cap;
+    annexb_reader_t rd;
     const p264hip_picture_t *pic;        /* picture completed in the current round, or NULL */
-    int done, failed, last_slot;
-    int64_t pictures;
+    int last_slot;
 } pstream_t;
 
 struct p264pipe {
@@ -45,6 +43,7 @@ struct p264pipe {
     int done_rounds;                     /* rounds the device has finished with (under mu; waited for through `go`) */
     int stop;                            /* (atomic) no more tasks */
     int *parsed;                         /* [stream] rounds parsed so far (atomic) */
+    int *ids, *sts, *dsts; const p264hip_picture_t **pics;   /* [stream] the round being submitted: input slots, streams, frame-store slots, pictures */
     int parsed_in_round[2];              /* tasks finished per round parity (under mu; its last one signals `idle`) */
     int failed_in_round[2];              /* a task of the round failed (under mu) */
     const p264hip_picture_t **round_pic[2];  /* [round parity][stream]: the picture a round's task produced, or NULL */
@@ -54,28 +53,6 @@ struct p264pipe {
 };
 
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
-
-/* feed NAL units of one stream until a picture completes or the stream ends */
-static void parse_one(p264pipe *p, pstream_t *s)
-{
-    s->pic = NULL;
-    if (s->done || (p->max_pictures > 0 && s->pictures >= p->max_pictures)) { s->done = 1; return; }
-    int64_t off, len;
-    while (p264_annexb_next(s->in, s->size, &s->pos, &off, &len)) {
-        if (len < 1) continue;
-        if (len + 8 > s->rbsp_cap) {
-            free(s->rbsp); s->rbsp_cap = len * 2 + 64; s->rbsp = (uint8_t *)malloc((size_t)s->rbsp_cap);
-            if (!s->rbsp) { __atomic_store_n(&s->failed, 1, __ATOMIC_RELAXED); s->done = 1; return; }
-        }
-        p264_nal_t nal; nal.p_payload = s->rbsp;
-        p264_nal_decode(&nal, (void *)(s->in + off), (int)len);
-        const p264hip_picture_t *pic = NULL;
-        int rc = p264parse_nal(s->parser, nal.i_type, nal.i_ref_idc, nal.p_payload, nal.i_payload, &pic);
-        if (rc < 0) { __atomic_store_n(&s->failed, 1, __ATOMIC_RELAXED); s->done = 1; return; }
-        if (rc == 1) { s->pic = pic; s->pictures++; return; }
-    }
-    s->done = 1;
-}
 
 static void *worker(void *arg)
 {
@@ -110,11 +87,11 @@ static void *worker(void *arg)
             }
             if (__atomic_load_n(&p->stop, __ATOMIC_ACQUIRE)) break;
             double t0 = now_s();
-            parse_one(p, &p->st[s]);
+            p->st[s].pic = annexb_reader_next(&p->st[s].rd, p->max_pictures);
             spent += now_s() - t0;
             p->round_pic[R & 1][s] = p->st[s].pic;
             __atomic_store_n(&p->parsed[s], R + 1, __ATOMIC_RELEASE);
-            const int failed = __atomic_load_n(&p->st[s].failed, __ATOMIC_RELAXED);
+            const int failed = annexb_reader_failed(&p->st[s].rd);
             pthread_mutex_lock(&p->mu);
             if (failed) p->failed_in_round[R & 1] = 1;
             if (p->turn_waiters) pthread_cond_broadcast(&p->turn);     /* (parsed[s] was stored before mu was taken: a waiter has seen it or is waiting) */
@@ -182,15 +159,19 @@ p264pipe *p264pipe_open(int device, int n_streams, int n_threads)
     p->parsed = (int *)calloc((size_t)n_streams, sizeof(int));
     p->round_pic[0] = (const p264hip_picture_t **)calloc((size_t)n_streams, sizeof(void *));
     p->round_pic[1] = (const p264hip_picture_t **)calloc((size_t)n_streams, sizeof(void *));
+    p->ids = (int *)malloc(sizeof(int) * (size_t)n_streams); p->sts = (int *)malloc(sizeof(int) * (size_t)n_streams);
+    p->dsts = (int *)malloc(sizeof(int) * (size_t)n_streams);
+    p->pics = (const p264hip_picture_t **)malloc(sizeof(void *) * (size_t)n_streams);
     pthread_mutex_init(&p->mu, NULL); pthread_cond_init(&p->go, NULL); pthread_cond_init(&p->idle, NULL); pthread_cond_init(&p->turn, NULL);
-    if (!p->st || !p->threads || !p->parsed || !p->round_pic[0] || !p->round_pic[1]) { p264pipe_close(p); return NULL; }
+    if (!p->st || !p->threads || !p->parsed || !p->round_pic[0] || !p->round_pic[1] || !p->ids || !p->sts || !p->dsts || !p->pics) { p264pipe_close(p); return NULL; }
+    /* picture buffers in pinned host memory when they are uploaded (P264AMD_PIPE_PINNED=0 / 1 forces either kind: experiments) */
+    const char *pin = getenv("P264AMD_PIPE_PINNED");
+    const int pinned = pin ? atoi(pin) != 0 : device >= 0;
     for (int i = 0; i < n_streams; i++) {
         /* (the pictures go to this library's HIP layer, which knows Intra 8x8 records; device -1 parses for nobody: the default) */
-        p->st[i].parser = p264parse_open(P264PARSE_OPT_QUIET | (device >= 0 ? P264PARSE_OPT_INTRA8X8 : 0));
-        if (!p->st[i].parser) { p264pipe_close(p); return NULL; }
-        /* picture buffers in pinned host memory when they are uploaded (P264AMD_PIPE_PINNED=0 / 1 forces either kind: experiments) */
-        const char *pin = getenv("P264AMD_PIPE_PINNED");
-        if (pin ? atoi(pin) != 0 : device >= 0) p264parse_set_allocator(p->st[i].parser, p264hip_host_alloc, p264hip_host_free);
+        p->st[i].rd.parser = p264parse_open(P264PARSE_OPT_QUIET | (device >= 0 ? P264PARSE_OPT_INTRA8X8 : 0));
+        if (!p->st[i].rd.parser) { p264pipe_close(p); return NULL; }
+        if (pinned) p264parse_set_allocator(p->st[i].rd.parser, p264hip_host_alloc, p264hip_host_free);
         p->st[i].last_slot = -1;
     }
     for (int i = 0; i < p->n_threads; i++) {
@@ -203,77 +184,82 @@ p264pipe *p264pipe_open(int device, int n_streams, int n_threads)
 int p264pipe_set_input(p264pipe *p, int stream, const uint8_t *annexb, int64_t size)
 {
     if (!p || stream < 0 || stream >= p->n_streams || !annexb || size < 0) return -1;
-    pstream_t *s = &p->st[stream];
-    s->in = annexb; s->size = size; s->pos = 0; s->done = 0; s->failed = 0; s->pictures = 0; s->pic = NULL;
+    annexb_reader_set_input(&p->st[stream].rd, annexb, size);
+    p->st[stream].pic = NULL;
+    return 0;
+}
+
+/* round r's pictures, in stream order, into p->pics / sts / ids / dsts; returns how many */
+static int collect_round(p264pipe *p, int r)
+{
+    int n = 0;
+    for (int i = 0; i < p->n_streams; i++) {
+        const p264hip_picture_t *pic = p->round_pic[r & 1][i];
+        if (pic) { p->pics[n] = pic; p->sts[n] = i; p->ids[n] = i * 2 + (r & 1); p->dsts[n] = p->st[i].last_slot = pic->dst_slot; n++; }
+    }
+    return n;
+}
+/* the device context, once: geometry is known after the first picture */
+static int ensure_context(p264pipe *p)
+{
+    if (p->device < 0 || p->ctx) return 0;
+    p->mb_w = p->pics[0]->mb_w; p->mb_h = p->pics[0]->mb_h; p->slots = p264parse_slots(p->st[p->sts[0]].rd.parser);
+    if (p264hip_create(&p->ctx, p->device, p->mb_w, p->mb_h, p->n_streams, p->slots, p->n_streams * 2)) {
+        fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); return -1;
+    }
+    return 0;
+}
+/* round r's n pictures to the device: uploads, one batched reconstruct, the sink's export behind the round's kernels, and the
+ * wait for the marker behind all of it */
+static int submit_round(p264pipe *p, int r, int n, p264pipe_stats_t *S)
+{
+    const double s0 = now_s();
+    int rc = 0;
+    for (int k = 0; k < n && !rc; k++) {
+        if (p->pics[k]->mb_w != p->mb_w || p->pics[k]->mb_h != p->mb_h) { fprintf(stderr, "p264pipe_run: stream %d has a different picture size\n", p->sts[k]); rc = -1; }
+        else if (p264hip_upload_async(p->ctx, p->ids[k], p->pics[k])) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
+        else S->bytes_uploaded += (int64_t)p->mb_w * p->mb_h * (16 + 64 + 4 + 16) + (int64_t)p->pics[k]->n_coef_blocks * 32;
+    }
+    if (!rc && p264hip_reconstruct(p->ctx, p->ids, p->sts, n)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
+    void *sink = p->sink_fn ? p->sink_bufs[r % p->sink_n_bufs] : NULL;       /* the round's pictures, behind its kernels */
+    if (!rc && sink && p264hip_export_frames(p->ctx, p->sts, p->dsts, n, &p->sink_e, sink, p->sink_bytes)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
+    int marker = -1;
+    if (!rc) { marker = p264hip_marker(p->ctx); if (marker < 0) rc = -1; }
+    S->submit_seconds += now_s() - s0;
+    if (rc) return rc;
+    /* the parsers reuse round r's buffers in round r + 2: its uploads must have been consumed (the threads are in round r + 1) */
+    const double w0 = now_s();
+    if (p264hip_marker_wait(p->ctx, marker)) return -1;
+    S->wait_device_seconds += now_s() - w0;
+    if (sink) p->sink_fn(p->sink_user, r, n, p->sts, sink);
     return 0;
 }
 
 int p264pipe_run(p264pipe *p, int max_pictures, p264pipe_stats_t *stats)
 {
     if (!p) return -1;
-    for (int i = 0; i < p->n_streams; i++) if (!p->st[i].in) { fprintf(stderr, "p264pipe_run: stream %d has no input\n", i); return -1; }
+    for (int i = 0; i < p->n_streams; i++) if (!p->st[i].rd.in) { fprintf(stderr, "p264pipe_run: stream %d has no input\n", i); return -1; }
     p->max_pictures = max_pictures; p->parse_seconds = 0;
-    int *ids = (int *)malloc(sizeof(int) * (size_t)p->n_streams), *sts = (int *)malloc(sizeof(int) * (size_t)p->n_streams);
-    int *dsts = (int *)malloc(sizeof(int) * (size_t)p->n_streams);
-    const p264hip_picture_t **pics = (const p264hip_picture_t **)malloc(sizeof(void *) * (size_t)p->n_streams);
-    if (!ids || !sts || !dsts || !pics) { free(ids); free(sts); free(dsts); free(pics); return -1; }
-    int rounds = 0, rc = 0;
-    int64_t pictures = 0, uploaded = 0;
-    double submit = 0, wait_parse = 0, wait_gpu = 0;          /* (the main thread's waits: P264AMD_PIPE_DEBUG=1 prints them) */
+    p264pipe_stats_t S; memset(&S, 0, sizeof S);                /* (the main thread's waits: P264AMD_PIPE_DEBUG=1 prints them) */
+    int rc = 0;
     const double t0 = now_s();
     start_run(p);
     for (int r = 0;; r++) {
-        { const double w0 = now_s(); if (finish_round(p, r)) rc = -1; wait_parse += now_s() - w0; }
-        int n = 0;
-        for (int i = 0; i < p->n_streams; i++) {
-            pstream_t *s = &p->st[i];
-            const p264hip_picture_t *pic = p->round_pic[r & 1][i];
-            if (pic) { pics[n] = pic; sts[n] = i; ids[n] = i * 2 + (r & 1); dsts[n] = s->last_slot = pic->dst_slot; n++; }
-        }
+        { const double w0 = now_s(); if (finish_round(p, r)) rc = -1; S.wait_parse_seconds += now_s() - w0; }
+        const int n = collect_round(p, r);
         if (n == 0 || rc) break;
-        rounds++; pictures += n;
-        if (p->device >= 0 && !p->ctx) {                     /* geometry is known after the first picture */
-            p->mb_w = pics[0]->mb_w; p->mb_h = pics[0]->mb_h; p->slots = p264parse_slots(p->st[sts[0]].parser);
-            if (p264hip_create(&p->ctx, p->device, p->mb_w, p->mb_h, p->n_streams, p->slots, p->n_streams * 2)) {
-                fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; break;
-            }
-        }
-        if (p->ctx) {
-            const double s0 = now_s();
-            for (int k = 0; k < n && !rc; k++) {
-                if (pics[k]->mb_w != p->mb_w || pics[k]->mb_h != p->mb_h) { fprintf(stderr, "p264pipe_run: stream %d has a different picture size\n", sts[k]); rc = -1; }
-                else if (p264hip_upload_async(p->ctx, ids[k], pics[k])) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
-                else uploaded += (int64_t)p->mb_w * p->mb_h * (16 + 64 + 4 + 16) + (int64_t)pics[k]->n_coef_blocks * 32;
-            }
-            if (!rc && p264hip_reconstruct(p->ctx, ids, sts, n)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
-            void *sink = p->sink_fn ? p->sink_bufs[r % p->sink_n_bufs] : NULL;       /* the round's pictures, behind its kernels */
-            if (!rc && sink && p264hip_export_frames(p->ctx, sts, dsts, n, &p->sink_e, sink, p->sink_bytes)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
-            int marker = -1;
-            if (!rc) { marker = p264hip_marker(p->ctx); if (marker < 0) rc = -1; }
-            submit += now_s() - s0;
-            if (rc) break;
-            /* the parsers reuse round r's buffers in round r + 2: its uploads must have been consumed (the threads are in round r + 1) */
-            const double w0 = now_s();
-            if (p264hip_marker_wait(p->ctx, marker)) { rc = -1; break; }
-            wait_gpu += now_s() - w0;
-            if (sink) p->sink_fn(p->sink_user, r, n, sts, sink);
-        }
+        S.rounds++; S.pictures += n;
+        if ((rc = ensure_context(p)) || (p->ctx && (rc = submit_round(p, r, n, &S)))) break;
         rounds_done(p, r);
     }
     end_run(p);
     if (p->ctx && p264hip_sync(p->ctx)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
-    const double t1 = now_s();
+    S.seconds = now_s() - t0; S.parse_seconds = p->parse_seconds; S.streams = p->n_streams; S.threads = p->n_threads;
     if (getenv("P264AMD_PIPE_DEBUG"))
         fprintf(stderr, "p264pipe_run: %d rounds, %.3f s: main thread waited %.3f s for the parsers, %.3f s for the device, submitted for %.3f s; parser threads %.3f s in all (%d threads)\n",
-                rounds, t1 - t0, wait_parse, wait_gpu, submit, p->parse_seconds, p->n_threads);
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->pictures = pictures; stats->seconds = t1 - t0; stats->parse_seconds = p->parse_seconds; stats->submit_seconds = submit;
-        stats->wait_parse_seconds = wait_parse; stats->wait_device_seconds = wait_gpu;
-        stats->rounds = rounds; stats->streams = p->n_streams; stats->threads = p->n_threads; stats->bytes_uploaded = uploaded;
-        for (int i = 0; i < p->n_streams; i++) stats->bytes += p->st[i].pos;
-    }
-    free(ids); free(sts); free(dsts); free(pics);
+                S.rounds, S.seconds, S.wait_parse_seconds, S.wait_device_seconds, S.submit_seconds, p->parse_seconds, p->n_threads);
+    for (int i = 0; i < p->n_streams; i++) S.bytes += p->st[i].rd.pos;
+    if (stats) *stats = S;
     return rc;
 }
 
@@ -293,7 +279,7 @@ int p264pipe_read_frame(p264pipe *p, int stream, uint8_t *y, int y_stride, uint8
 
 int p264pipe_crop(p264pipe *p, int *left, int *top, int *width, int *height)
 {
-    return p ? p264parse_crop(p->st[0].parser, left, top, width, height) : -1;
+    return p ? p264parse_crop(p->st[0].rd.parser, left, top, width, height) : -1;
 }
 
 int p264pipe_export_last(p264pipe *p, const p264hip_export_t *e, void *dst_dev, size_t bytes)
@@ -338,7 +324,7 @@ int p264pipe_set_sink(p264pipe *p, const p264hip_export_t *e, void *const *bufs,
 
 int64_t p264pipe_stream_pictures(p264pipe *p, int stream)
 {
-    return (p && stream >= 0 && stream < p->n_streams) ? p->st[stream].pictures : -1;
+    return (p && stream >= 0 && stream < p->n_streams) ? p->st[stream].rd.pictures : -1;
 }
 
 void p264pipe_close(p264pipe *p)
@@ -347,10 +333,10 @@ void p264pipe_close(p264pipe *p)
     pthread_mutex_lock(&p->mu); p->quit = 1; pthread_cond_broadcast(&p->go); pthread_mutex_unlock(&p->mu);
     for (int i = 0; i < p->started; i++) pthread_join(p->threads[i], NULL);
     if (p->ctx) { (void)p264hip_sync(p->ctx); }
-    if (p->st) for (int i = 0; i < p->n_streams; i++) { if (p->st[i].parser) p264parse_close(p->st[i].parser); free(p->st[i].rbsp); }
+    if (p->st) for (int i = 0; i < p->n_streams; i++) annexb_reader_close(&p->st[i].rd);
     if (p->ctx) p264hip_destroy(p->ctx);
     pthread_mutex_destroy(&p->mu); pthread_cond_destroy(&p->go); pthread_cond_destroy(&p->idle); pthread_cond_destroy(&p->turn);
     free(p->parsed); free((void *)p->round_pic[0]); free((void *)p->round_pic[1]);
-    free(p->sink_bufs);
+    free(p->sink_bufs); free(p->ids); free(p->sts); free(p->dsts); free((void *)p->pics);
     free(p->st); free(p->threads); free(p);
 }

@@ -9,10 +9,11 @@ from p264decoder_amd import _native as N
 from p264decoder_amd.fanout import BK_CLOSE, BK_OPEN, BK_RECON, Backend, FanOut
 
 
-def oracle_backend(fail_at=None, delay=0.0):
+def oracle_backend(fail_at=None, delay=0.0, fail_open=False):
     """p264fan_backend_t whose reconstruct() is oracle_reconstruct on host planes (one frame store per local stream).
     fail_at = n: the n-th reconstruct call of this rank fails on purpose (the failure-path tests); delay: seconds of sleep
-    per call (stands in for reconstruction time in the overlap test)."""
+    per call (stands in for reconstruction time in the overlap test); fail_open: open() returns -1 (a rank whose backend
+    cannot open)."""
     import time
     from tests import oracle_bind
     ora = oracle_bind.load()
@@ -20,6 +21,8 @@ def oracle_backend(fail_at=None, delay=0.0):
     calls = [0]
 
     def bk_open(ctx, device, mb_w, mb_h, n_local, slots):
+        if fail_open:
+            return -1
         state.update(mb_w=mb_w, mb_h=mb_h, stores=[oracle_bind.FrameStore(mb_w, mb_h, slots) for _ in range(n_local)])
         ctx[0] = 1
         return 0
@@ -46,13 +49,13 @@ def oracle_backend(fail_at=None, delay=0.0):
     return b
 
 
-def run_rank(rank, world, port, streams, max_pictures, use_oracle, q, fail=None, delay=0.0, transport=None):
+def run_rank(rank, world, port, streams, max_pictures, use_oracle, q, fail=None, delay=0.0, transport=None, fail_open=None):
     """Entry point of one rank (spawned process).  The root returns {(stream, picture): sha256} through the queue.
     fail = (rank, n): that rank's n-th reconstruct call fails on purpose.  transport: None = TCP on `port`, or
-    ("rccl", unique id): one GPU per rank (device = rank)."""
+    ("rccl", unique id): one GPU per rank (device = rank).  fail_open = rank: that rank's backend cannot open."""
     try:
         lib = N.load()
-        bk = oracle_backend(fail_at=fail[1] if fail and fail[0] == rank else None, delay=delay) if use_oracle else None
+        bk = oracle_backend(fail_at=fail[1] if fail and fail[0] == rank else None, delay=delay, fail_open=fail_open == rank) if use_oracle else None
         fan = FanOut(rank, world, transport or ("tcp", "127.0.0.1", port), device=rank if transport else 0, backend=bk, lib=lib)
         if rank == 0:
             got = {}
@@ -86,7 +89,7 @@ def free_port(hint):
     return hint
 
 
-def run_job(world, streams, max_pictures, use_oracle, port, fail=None, delay=0.0, transport=None, expect_errors=False):
+def run_job(world, streams, max_pictures, use_oracle, port, fail=None, delay=0.0, transport=None, expect_errors=False, fail_open=None):
     """Runs one job with `world` processes.  Every rank must come back (a hang fails the test by time-out) and exit.
     expect_errors: return the raw per-rank results instead of asserting that nobody failed."""
     import multiprocessing as mp
@@ -94,7 +97,7 @@ def run_job(world, streams, max_pictures, use_oracle, port, fail=None, delay=0.0
         port = free_port(port)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=run_rank, args=(r, world, port, streams, max_pictures, use_oracle, q, fail, delay, transport)) for r in range(world)]
+    procs = [ctx.Process(target=run_rank, args=(r, world, port, streams, max_pictures, use_oracle, q, fail, delay, transport, fail_open)) for r in range(world)]
     for p in procs:
         p.start()
     results = [q.get(timeout=300) for _ in procs]

@@ -139,3 +139,70 @@ def test_worker_out_of_step_aborts_the_transport(lib):
     assert not th.is_alive() and "bad control block" in result.get("rc", ""), result
     conn.close()
     srv.close()
+
+
+# ---- what a job answers where it cannot run: error texts and who leaves how, pinned word for word --------------------------
+def _by_rank(res):
+    """{rank: "ok" | error text} and the root's (pictures, stats) of a run_job(..., expect_errors=True)."""
+    by_rank, ok = {}, None
+    for kind, a, b in res:
+        if kind == "error":
+            by_rank[int(a.split(":")[0])] = a
+        elif kind == "worker":
+            by_rank[a] = "ok"
+        else:
+            by_rank[0], ok = "ok", (a, b)
+    return by_rank, ok
+
+
+def test_fanout_streams_of_different_picture_sizes(lib):
+    cif, qpd = synth_cases.stream_bytes("cif_ip"), synth_cases.stream_bytes("qpdelta")
+    res = fan_helpers.run_job(3, [cif, qpd, cif], 4, True, 31500 + (os.getpid() % 300), expect_errors=True)
+    by_rank, _ = _by_rank(res)
+    assert len(res) == 3 and "stream 1 has a different picture size (11x9 macroblocks, the job runs at 22x18)" in by_rank[0], by_rank
+    assert by_rank[1] == "ok" and by_rank[2] == "ok", by_rank       # both workers left on FINISHED
+
+
+def test_fanout_picture_size_changes_inside_the_job(lib):
+    cif, qpd = synth_cases.stream_bytes("cif_ip"), synth_cases.stream_bytes("qpdelta")
+    res = fan_helpers.run_job(2, [cif + qpd, cif + qpd], 0, True, 31800 + (os.getpid() % 300), expect_errors=True)
+    by_rank, _ = _by_rank(res)
+    assert len(res) == 2 and "the picture size changed inside the job (22x18 -> 11x9 macroblocks)" in by_rank[0], by_rank
+    assert by_rank[1] == "ok", by_rank
+
+
+def test_fanout_stream_cut_inside_a_slice(lib):
+    cif = synth_cases.stream_bytes("cif_ip")
+    res = fan_helpers.run_job(2, [cif, cif[:2 * len(cif) // 3], cif], 0, True, 32100 + (os.getpid() % 300), expect_errors=True)
+    by_rank, _ = _by_rank(res)
+    assert len(res) == 2 and "a stream failed to parse (or the host ran out of memory)" in by_rank[0], by_rank
+    assert by_rank[1] == "ok", by_rank
+
+
+def test_fanout_empty_remote_stream(lib):
+    cif = synth_cases.stream_bytes("cif_ip")
+    cif_h = synth_cases.golden("cif_ip")[1]
+    res = fan_helpers.run_job(2, [cif, b"\0\0\0\1", cif], 3, True, 32400 + (os.getpid() % 300), expect_errors=True)
+    by_rank, ok = _by_rank(res)
+    assert by_rank == {0: "ok", 1: "ok"}, by_rank
+    got, st = ok
+    assert st["pictures"] == 6 and st["rounds"] == 3 and st["pictures_remote"] == 0 and st["bytes_scattered"] == 0, st
+    assert sorted(got) == [(s, i) for s in (0, 2) for i in range(3)]
+    assert all(got[(s, i)] == cif_h[i] for s in (0, 2) for i in range(3))
+
+
+def test_fanout_too_many_streams_per_rank(lib):
+    qpd = synth_cases.stream_bytes("qpdelta")
+    res = fan_helpers.run_job(1, [qpd] * 65, 1, True, 32700 + (os.getpid() % 300), expect_errors=True)
+    by_rank, _ = _by_rank(res)
+    assert len(res) == 1 and "p264fan_root_run: p264fan_root_run: more than 64 streams per rank" in by_rank[0], by_rank
+
+
+def test_fanout_worker_backend_cannot_open(lib):
+    """Rank 1's backend fails in open(): that is the round's status (the test backend leaves no text, so the worker says
+    "reconstruction failed"), the root names the worker, rank 1 itself returns the error and rank 2 leaves on FINISHED."""
+    cif = synth_cases.stream_bytes("cif_ip")
+    res = fan_helpers.run_job(3, [cif] * 3, 4, True, 33000 + (os.getpid() % 300), expect_errors=True, fail_open=1)
+    by_rank, _ = _by_rank(res)
+    assert len(res) == 3 and "worker 1: reconstruction failed" in by_rank[0], by_rank
+    assert by_rank[1] != "ok" and "reconstruction failed" in by_rank[1] and by_rank[2] == "ok", by_rank
