@@ -10,7 +10,7 @@ import random
 from p264decoder_amd import Parser, _native as N
 from p264decoder_amd.recon import P264Error
 from tests import slice_streams, synth_cases
-from tests import test_bslices, test_cabac_streams, test_constrained_intra_cpu, test_ipcm_cpu, test_multiref, test_weighted_pred_cpu
+from tests import stream_args as A
 
 GOLDEN = os.path.join(synth_cases.GOLDEN, "parse_corpus.json")
 DAMAGE_BELOW = 40000            # bytes: longer streams are parsed as they are only
@@ -20,15 +20,15 @@ COPIES = 8
 def arguments():
     """[(name, synth264 arguments)]"""
     out = [("synth:" + k, v[0]) for k, v in synth_cases.CASES.items() if k not in synth_cases.BIG]
-    out += [("ipcm:" + k, v) for k, v in test_ipcm_cpu.STREAMS.items()]
-    out += [("wp:" + k, v) for k, v in test_weighted_pred_cpu.STREAMS.items()]
-    out += [("cip:" + k, v + test_constrained_intra_cpu.CI) for k, v in test_constrained_intra_cpu.STREAMS.items()]
+    out += [("ipcm:" + k, v) for k, v in A.IPCM_STREAMS.items()]
+    out += [("wp:" + k, v) for k, v in A.WP_STREAMS.items()]
+    out += [("cip:" + k, v + A.CI) for k, v in A.CI_STREAMS.items()]
     out += [("slices:" + k, v) for k, v in slice_streams.STREAMS.items()]
     out += [("agreeing:" + k, v) for k, v in slice_streams.AGREEING.items()]
-    for i, v in enumerate(test_cabac_streams.STREAMS):
+    for i, v in enumerate(A.CABAC_STREAMS):
         out += [("cabac:%d:cavlc" % i, v), ("cabac:%d:cabac" % i, v + " --cabac")]
-    out += [("b:%d" % i, v) for i, v in enumerate(test_bslices.STREAMS)]
-    for tag, group in (("mmco", test_multiref.MMCO), ("sliced", test_multiref.SLICED), ("sub8x8", test_multiref.SUB8X8), ("reorder", [test_multiref.REORDER])):
+    out += [("b:%d" % i, v) for i, v in enumerate(A.B_STREAMS)]
+    for tag, group in (("mmco", A.MMCO), ("sliced", A.SLICED), ("sub8x8", A.SUB8X8), ("reorder", [A.REORDER])):
         out += [("multiref:%s:%d" % (tag, i), v) for i, v in enumerate(group)]
     return out
 

@@ -3,7 +3,6 @@ the filter offsets, reference-list reordering and num_ref_idx_active_override - 
 --slice-lists), with the writer's own record of what it means (--dump-slices): per macroblock its slice, idc and offsets, per 8x8
 quadrant and list the PICTURE it predicts from.  `check_against_dump` compares a parse with that record; `expected_pictures`
 decodes the parsed pictures on the CPU: the oracle's unfiltered reconstruction, then tests/slice_filter_checker.py."""
-import subprocess
 
 import numpy as np
 
@@ -32,10 +31,8 @@ STREAMS = {
 
 def make(tmp_path, args, extra=()):
     """(stream bytes, the --dump-slices record as bytes)"""
-    synth_cases.ensure_tool()
-    stream, dump = str(tmp_path / "s.264"), str(tmp_path / "s.slices")
-    subprocess.run([synth_cases.TOOL, stream] + args.split() + ["--dump-slices", dump] + list(extra), check=True)
-    return open(stream, "rb").read(), np.fromfile(dump, dtype=np.uint8)
+    data, dump = synth_cases.write_stream(tmp_path, " ".join([args, *extra]), dumps=("slices",))
+    return data, np.fromfile(dump, dtype=np.uint8)
 
 
 def records(dump, n_mb):

@@ -115,6 +115,17 @@ def generate(name, extra_args=None):
     return path
 
 
+def write_stream(tmp_path, args, tag="s", dumps=()):
+    """The stream of the arguments written to tmp_path/<tag>.264, past the cache; returns its bytes.  dumps names the writer's
+    records to ask for ("mv", "slices", ...): --dump-<kind> tmp_path/<tag>.<kind> each, and the return is (bytes, path, ...)."""
+    ensure_tool()
+    stream = str(tmp_path / ("%s.264" % tag))
+    paths = [str(tmp_path / ("%s.%s" % (tag, kind))) for kind in dumps]
+    subprocess.run([TOOL, stream] + args.split() + [a for kind, path in zip(dumps, paths) for a in ("--dump-" + kind, path)], check=True)
+    data = open(stream, "rb").read()
+    return (data, *paths) if dumps else data
+
+
 def stream_bytes(name):
     return open(generate(name), "rb").read()
 

@@ -5,28 +5,19 @@ picture-order-count order, list-wise vector prediction over every B macroblock a
 prediction (spatial and temporal, with and without direct_8x8_inference), implicit weights.  Then (GPU) the parsed
 pictures through the HIP kernels against the CPU oracle.  No reference decoder exists for these streams: parity with the
 reference is unpinned here; what is pinned to it are the two bi-prediction combines (kat_bipred.npz)."""
-import subprocess
 
 import numpy as np
 import pytest
 
 from p264decoder_amd import Parser, _native as N
 from tests import synth_cases
+from tests.stream_args import B_STREAMS as STREAMS
 
-STREAMS = [
-    "--mbw 9 --mbh 7 --frames 22 --seed 81 --refs 2 --bframes 2 --coded 10 --maxlevel 6",
-    "--mbw 8 --mbh 6 --frames 26 --seed 82 --refs 3 --bframes 3 --sub8x8 --implicit --coded 10 --maxlevel 6",
-    "--mbw 8 --mbh 6 --frames 22 --seed 83 --refs 2 --bframes 2 --temporal --sub8x8 --coded 8 --maxlevel 6",
-    "--mbw 7 --mbh 6 --frames 19 --seed 84 --refs 2 --bframes 1 --d8inf --sub8x8 --coded 8 --maxlevel 6",
-    "--mbw 7 --mbh 5 --frames 25 --seed 85 --refs 4 --bframes 3 --temporal --d8inf --implicit --slices 2 --coded 8 --maxlevel 6",
-]
 
 
 def make(tmp_path, args):
-    synth_cases.ensure_tool()
-    stream, dump = str(tmp_path / "b.264"), str(tmp_path / "b.mv")
-    subprocess.run([synth_cases.TOOL, stream] + args.split() + ["--dump-mv", dump], check=True)
-    return open(stream, "rb").read(), np.fromfile(dump, dtype=np.uint8)
+    data, dump = synth_cases.write_stream(tmp_path, args, "b", dumps=("mv",))
+    return data, np.fromfile(dump, dtype=np.uint8)
 
 
 @pytest.mark.parametrize("args", STREAMS)

@@ -6,39 +6,24 @@ the parsed pictures through the oracle and through tests/intra_checker.py.  Writ
 flag; what the intra predictors do with the availability it produces is checked by the intra checker, written from the
 standard's text.  Every parser test fails on the parent, which left `avail` slice-shaped."""
 import hashlib
-import subprocess
 
 import numpy as np
 import pytest
 
 from p264decoder_amd import Parser, _native as N
 from tests import synth_cases
-from tests.test_intra_checker_cpu import decode_both
+from tests.hip_harness import decode_both
+from tests.stream_args import CI, CI_STREAMS as STREAMS
+from tests.synth_cases import write_stream as write
 
-CI = " --constrained-intra --intra-pct 35"
-STREAMS = {
-    "ip": "--mbw 9 --mbh 7 --frames 8 --gop 4 --seed 401 --coded 25 --maxlevel 12",
-    "b": "--mbw 8 --mbh 6 --frames 13 --seed 402 --refs 2 --bframes 2 --sub8x8 --implicit --coded 12 --maxlevel 8",
-    "slices3": "--mbw 8 --mbh 6 --frames 8 --gop 4 --seed 403 --slices 3 --coded 20 --maxlevel 12",
-    "ipcm": "--mbw 9 --mbh 7 --frames 8 --gop 4 --seed 404 --coded 25 --maxlevel 12 --ipcm 15",
-    "sub8x8": "--mbw 8 --mbh 6 --frames 8 --gop 0 --seed 405 --refs 2 --sub8x8 --coded 20 --maxlevel 12",
-}
 FIELDS = ("mb", "mv", "ref_idx", "i4modes", "coefs")
-
-
-def write(tmp_path, args, tag="s", dumps=False):
-    synth_cases.ensure_tool()
-    stream = str(tmp_path / ("%s.264" % tag))
-    extra = ["--dump-avail", str(tmp_path / (tag + ".avail")), "--dump-mv", str(tmp_path / (tag + ".mv"))] if dumps else []
-    subprocess.run([synth_cases.TOOL, stream] + args.split() + extra, check=True)
-    return open(stream, "rb").read()
 
 
 @pytest.mark.parametrize("cabac", [False, True], ids=["cavlc", "cabac"])
 @pytest.mark.parametrize("name", list(STREAMS))
 def test_parser_against_the_writers_record(lib, tmp_path, name, cabac):
     args = STREAMS[name] + CI + (" --cabac" if cabac else "")
-    data = write(tmp_path, args, dumps=True)
+    data = write(tmp_path, args, dumps=("avail", "mv"))[0]
     pics = Parser(quiet=True, lib=lib).parse_stream(data)
     n = pics[0].n_mb
     dump = np.fromfile(str(tmp_path / "s.avail"), np.uint8).reshape(len(pics), n * 17)
@@ -66,7 +51,7 @@ def test_parser_against_the_writers_record(lib, tmp_path, name, cabac):
 def test_vector_prediction_keeps_the_slices_availability(lib, tmp_path):
     """the writer predicts vectors from every neighbour of the slice, intra ones counting as 'intra' (8.4.1.3), whatever the
     flag says: the parser's vectors are the writer's"""
-    data = write(tmp_path, STREAMS["sub8x8"] + CI, dumps=True)
+    data = write(tmp_path, STREAMS["sub8x8"] + CI, dumps=("avail", "mv"))[0]
     pics = Parser(quiet=True, lib=lib).parse_stream(data)
     n = pics[0].n_mb
     dump = np.fromfile(str(tmp_path / "s.mv"), np.uint8).reshape(len(pics), n * 64 + n * 16)

@@ -19,11 +19,11 @@ import pytest
 from p264decoder_amd import _native as N
 from tests import deblock_checker as dc
 from tests import deblock_stim, intra_checker, kat_seam, oracle_bind, seam_fuzz
-from tests import test_gpu_intra_avail as t_intra
-from tests import test_gpu_ipcm_seam_fuzz as t_ipcm
-from tests import test_gpu_seam_fuzz as t_seam
-from tests import test_gpu_wp_seam_fuzz as t_wp
+from tests import intra_avail_stim as t_intra
+from tests import ipcm_seam_stim as t_ipcm
+from tests import wp_seam_stim as t_wp
 from tests.conftest import GOLDEN
+from tests.stream_args import SEAM_CONFIGS
 
 # one frame at several indices of a list (what reordering commands that name a picture twice, or a list longer than the frame
 # store, produce): unweighted P - also with indices past the list - and B with a frame twice in a list and in both lists
@@ -93,7 +93,7 @@ def test_checker_equals_the_references_recorded_answers():
         assert differing(mine, want) == 0, "case %d: %d samples differ from the reference's filtered picture" % (i, differing(mine, want))
 
 
-@pytest.mark.parametrize("name,mb_w,mb_h,n_pics,kw", t_seam.CONFIGS, ids=[c[0] for c in t_seam.CONFIGS])
+@pytest.mark.parametrize("name,mb_w,mb_h,n_pics,kw", SEAM_CONFIGS, ids=[c[0] for c in SEAM_CONFIGS])
 def test_checker_equals_oracle_on_seam_fuzz(oracle, name, mb_w, mb_h, n_pics, kw):
     rng = np.random.default_rng(sum(map(ord, name)) * 7919)
     slots = kw["slots"]

@@ -6,14 +6,14 @@ from collections import Counter
 import pytest
 
 from p264decoder_amd import _native as N
-from tests import distinct_pool, test_gpu_distinct_shapes as shapes
+from tests import distinct_pool, stream_args as shapes
 
 POOLS = {"p": (distinct_pool.POOL_P, 8, 17), "b": (distinct_pool.POOL_B, 7, 17), "wp": (distinct_pool.POOL_WP, 7, 17),
          "bench": (distinct_pool.POOL_BENCH, 4, 9), "cfg4": (distinct_pool.POOL_CFG4, 7, 9)}
 N_CU = 256                               # an MI355X (the GPU tests assert the shapes they get)
 # (streams, pictures per k_deblock workgroup) of every batch the GPU tests run
-BATCHES = {name: [(shapes.S, int(pw)) for _, pw, _ in shapes.SHAPES] + [(shapes.S, int(pw)) for pw in shapes.ODD] +
-           [(shapes.S, int(pw)) for _, pw, _ in shapes.WAVES] + [(shapes.S, 1)]
+BATCHES = {name: [(shapes.DISTINCT_STREAMS, int(pw)) for _, pw, _ in shapes.LAUNCH_SHAPES] + [(shapes.DISTINCT_STREAMS, int(pw)) for pw in shapes.ODD] +
+           [(shapes.DISTINCT_STREAMS, int(pw)) for _, pw, _ in shapes.WAVES] + [(shapes.DISTINCT_STREAMS, 1)]
            for name in ("p", "b", "wp")}
 BATCHES["bench"] = [(8 * N_CU, 8)]
 BATCHES["cfg4"] = [(4 * N_CU, 4)]

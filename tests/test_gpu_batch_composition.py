@@ -11,37 +11,18 @@ import itertools
 import numpy as np
 import pytest
 
-from p264decoder_amd import HipReconstructor
 from tests import seam_fuzz, wp_checker
-from tests.test_gpu_seam_fuzz import compare
+from tests.hip_harness import compare, reconstructor
+from tests.stream_args import DST, KINDS, PLAIN_P, SLOTS, draw
 
 pytestmark = pytest.mark.gpu
-
-SLOTS, DST = 4, 3                # reference frames in slots 0 .. 2, every picture writes slot 3
-KINDS = {
-    "I": dict(p_picture=False),
-    "P": dict(n_ref=1),
-    "P_multi_dup": dict(n_ref=3, dup_refs=True),
-    "P_weighted": dict(n_ref=2, explicit_wp="legal"),
-    "B": dict(n_ref=2, n_ref_l1=2, b_picture=True, weighted=False),
-    "B_implicit": dict(n_ref=2, n_ref_l1=2, b_picture=True, weighted=True),
-    "B_weighted": dict(n_ref=2, n_ref_l1=2, b_picture=True, explicit_wp="legal"),
-}
-PLAIN_P = {"P"}                  # the kinds whose batches alone keep the fused edge-info pass (P_multi_dup: one frame at two indices -
-                                 # the loop filter compares pictures, H.264 8.7.2.1, which the two-list edge-info kernel does)
-
-
-def draw(rng, mb_w, mb_h, kind):
-    return seam_fuzz.make_picture(rng, mb_w, mb_h, slots=SLOTS, dst_slot=DST, level_style="mixed", qp_mode="random", intra_share=0.2,
-                                  slices=2, **KINDS[kind])
 
 
 class Pool:
     """one stream and frame store per picture, on the device and in a checker; want[i] = the checker's frame of picture i"""
 
-    def __init__(self, rng, oracle, lib, mb_w, mb_h, kinds):
-        self.kinds = kinds
-        self.hip = HipReconstructor(mb_w, mb_h, n_streams=len(kinds), slots=SLOTS, max_pictures=len(kinds), lib=lib)
+    def __init__(self, rng, oracle, hip, mb_w, mb_h, kinds):
+        self.kinds, self.hip = kinds, hip
         self.pics, self.want = [], []
         for s, kind in enumerate(kinds):
             chk = wp_checker.WeightedChecker(oracle, mb_w, mb_h, SLOTS)
@@ -71,15 +52,15 @@ class Pool:
 def test_every_kind_alone_in_pairs_and_together(lib, oracle):
     rng = np.random.default_rng(1016)
     kinds = list(KINDS)
-    pool = Pool(rng, oracle, lib, 5, 4, kinds)
     subsets = [(s,) for s in range(len(kinds))] + list(itertools.combinations(range(len(kinds)), 2)) + [tuple(range(len(kinds)))]
     waves = {}
-    for members in subsets:
-        li = pool.run(members)
-        plain_p = {kinds[s] for s in members} <= PLAIN_P
-        assert (li["edge_info_fused"] > 0) == plain_p, "batch %s: edge_info_fused %d" % ([kinds[s] for s in members], li["edge_info_fused"])
-        waves[len(members)] = li["intra_waves"]
-    pool.hip.close()
+    with reconstructor(lib, 5, 4, n_streams=len(kinds), slots=SLOTS, max_pictures=len(kinds)) as hip:
+        pool = Pool(rng, oracle, hip, 5, 4, kinds)
+        for members in subsets:
+            li = pool.run(members)
+            plain_p = {kinds[s] for s in members} <= PLAIN_P
+            assert (li["edge_info_fused"] > 0) == plain_p, "batch %s: edge_info_fused %d" % ([kinds[s] for s in members], li["edge_info_fused"])
+            waves[len(members)] = li["intra_waves"]
     assert len(set(waves.values())) == 1          # (small batches: one shape; the large one is below)
 
 
@@ -89,10 +70,10 @@ def test_a_large_batch_of_random_kinds(lib, oracle):
     rng = np.random.default_rng(600)
     n = 600
     kinds = [str(k) for k in rng.choice(list(KINDS), size=n)]
-    pool = Pool(rng, oracle, lib, 3, 2, kinds)
-    small = pool.run(tuple(range(len(KINDS))))
-    big = pool.run(tuple(range(n)))
-    pool.hip.close()
+    with reconstructor(lib, 3, 2, n_streams=n, slots=SLOTS, max_pictures=n) as hip:
+        pool = Pool(rng, oracle, hip, 3, 2, kinds)
+        small = pool.run(tuple(range(len(KINDS))))
+        big = pool.run(tuple(range(n)))
     assert n > 2 * big["compute_units"], "the batch does not reach the large-batch shapes on this device (%d CUs)" % big["compute_units"]
     assert big["intra_waves"] < small["intra_waves"], (small, big)
     assert big["deblock_pics_per_wg"] > 1 and big["edge_info_fused"] == 0

@@ -4,19 +4,14 @@ in groups of as many as a wavefront holds (work units = band x group); k_intra u
 P264AMD_* knobs (read once, when the context is created) and checked against the CPU oracle, picture by picture, on every stream."""
 import os
 
-import numpy as np
 import pytest
 
-from p264decoder_amd import HipReconstructor, Parser
+from p264decoder_amd import Parser
 from tests import oracle_bind, synth_cases
+from tests.hip_harness import compare, reconstructor
+from tests.stream_args import LAUNCH_SHAPES as SHAPES
 
 pytestmark = pytest.mark.gpu
-
-SHAPES = [  # (P264AMD_DEBLOCK_RB_LOG2, P264AMD_DEBLOCK_PICS_PER_WG, P264AMD_INTRA_WAVES)
-    ("3", "1", "16"), ("2", "2", "8"), ("2", "1", "4"), ("1", "4", "8"), ("1", "3", "1"), ("1", "1", "16"),
-    # more pictures per workgroup than a wavefront holds: groups (the last one partly empty with 7 streams)
-    ("2", "4", "8"), ("3", "4", "8"), ("2", "7", "4"), ("3", "16", "4"), ("1", "13", "2"),
-]
 
 
 @pytest.mark.parametrize("rb,per_wg,intra_waves", SHAPES)
@@ -30,16 +25,14 @@ def test_workgroup_shapes(lib, oracle, case, rb, per_wg, intra_waves, monkeypatc
     mb_w, mb_h = pics[0].mb_w, pics[0].mb_h
     S = 7                                                      # odd on purpose: the last workgroup is partly empty
     store = oracle_bind.FrameStore(mb_w, mb_h, parser.slots)
-    hip = HipReconstructor(mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics), lib=lib)
-    hip.upload(0, pics)
-    for i, p in enumerate(pics):
-        want = oracle_bind.reconstruct(oracle, store, p)
-        hip.reconstruct([i] * S, list(range(S)))
-        for s in range(S):
-            got = hip.read_frame(s, p.desc.dst_slot)
-            for plane, (a, b) in enumerate(zip(got, want)):
-                assert np.array_equal(a, b), "%s shape (%s,%s,%s): picture %d stream %d plane %d differs" % (case, rb, per_wg, intra_waves, i, s, plane)
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics)) as hip:
+        hip.upload(0, pics)
+        for i, p in enumerate(pics):
+            want = oracle_bind.reconstruct(oracle, store, p)
+            hip.reconstruct([i] * S, list(range(S)))
+            for s in range(S):
+                got = hip.read_frame(s, p.desc.dst_slot)
+                compare(got, want, "%s shape (%s,%s,%s): picture %d stream %d" % (case, rb, per_wg, intra_waves, i, s))
 
 
 @pytest.mark.parametrize("per_wg,S", [("3", 7), ("5", 11), ("7", 7), ("13", 14)])
@@ -56,18 +49,16 @@ def test_odd_picture_counts_as_pairs_and_a_single(lib, oracle, case, per_wg, S, 
     pics = parser.parse_stream(synth_cases.stream_bytes(case))[:6]
     mb_w, mb_h = pics[0].mb_w, pics[0].mb_h
     store = oracle_bind.FrameStore(mb_w, mb_h, parser.slots)
-    hip = HipReconstructor(mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics), lib=lib)
-    hip.upload(0, pics)
-    for i, p in enumerate(pics):
-        want = oracle_bind.reconstruct(oracle, store, p)
-        hip.reconstruct([i] * S, list(range(S)))
-        li = hip.last_launch()
-        assert li["deblock_odd_single"] == 1 and li["deblock_rb_log2"] == 2 and li["deblock_pics_per_wg"] == int(per_wg), li
-        for s in range(S):
-            got = hip.read_frame(s, p.desc.dst_slot)
-            for plane, (a, b) in enumerate(zip(got, want)):
-                assert np.array_equal(a, b), "%s, %s pictures per workgroup: picture %d stream %d plane %d differs" % (case, per_wg, i, s, plane)
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics)) as hip:
+        hip.upload(0, pics)
+        for i, p in enumerate(pics):
+            want = oracle_bind.reconstruct(oracle, store, p)
+            hip.reconstruct([i] * S, list(range(S)))
+            li = hip.last_launch()
+            assert li["deblock_odd_single"] == 1 and li["deblock_rb_log2"] == 2 and li["deblock_pics_per_wg"] == int(per_wg), li
+            for s in range(S):
+                got = hip.read_frame(s, p.desc.dst_slot)
+                compare(got, want, "%s, %s pictures per workgroup: picture %d stream %d" % (case, per_wg, i, s))
 
 
 def test_odd_picture_counts_at_1080p(lib, oracle, monkeypatch):
@@ -81,17 +72,15 @@ def test_odd_picture_counts_at_1080p(lib, oracle, monkeypatch):
         pics = parser.parse_stream(synth_cases.stream_bytes("cfg3_1080p_allp"))[:3]
         mb_w, mb_h = pics[0].mb_w, pics[0].mb_h
         store = oracle_bind.FrameStore(mb_w, mb_h, parser.slots)
-        hip = HipReconstructor(mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics), lib=lib)
-        hip.upload(0, pics)
-        for i, p in enumerate(pics):
-            want = oracle_bind.reconstruct(oracle, store, p)
-            hip.reconstruct([i] * S, list(range(S)))
-            assert hip.last_launch()["deblock_odd_single"] == 1
-            for s in range(S):
-                got = hip.read_frame(s, p.desc.dst_slot)
-                for plane, (a, b) in enumerate(zip(got, want)):
-                    assert np.array_equal(a, b), "%s pictures per workgroup: picture %d stream %d plane %d differs" % (per_wg, i, s, plane)
-        hip.close()
+        with reconstructor(lib, mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics)) as hip:
+            hip.upload(0, pics)
+            for i, p in enumerate(pics):
+                want = oracle_bind.reconstruct(oracle, store, p)
+                hip.reconstruct([i] * S, list(range(S)))
+                assert hip.last_launch()["deblock_odd_single"] == 1
+                for s in range(S):
+                    got = hip.read_frame(s, p.desc.dst_slot)
+                    compare(got, want, "%s pictures per workgroup: picture %d stream %d" % (per_wg, i, s))
 
 
 @pytest.mark.parametrize("fused", ["0", "1", "3", "16"])
@@ -105,16 +94,14 @@ def test_edge_info_inside_the_intra_launch_or_on_its_own(lib, oracle, case, fuse
     mb_w, mb_h = pics[0].mb_w, pics[0].mb_h
     S = 5
     store = oracle_bind.FrameStore(mb_w, mb_h, parser.slots)
-    hip = HipReconstructor(mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics), lib=lib)
-    hip.upload(0, pics)
-    for i, p in enumerate(pics):
-        want = oracle_bind.reconstruct(oracle, store, p)
-        hip.reconstruct([i] * S, list(range(S)))
-        for s in (0, S - 1):
-            got = hip.read_frame(s, p.desc.dst_slot)
-            for plane, (a, b) in enumerate(zip(got, want)):
-                assert np.array_equal(a, b), "%s, P264AMD_BS_FUSED=%s: picture %d stream %d plane %d differs" % (case, fused, i, s, plane)
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics)) as hip:
+        hip.upload(0, pics)
+        for i, p in enumerate(pics):
+            want = oracle_bind.reconstruct(oracle, store, p)
+            hip.reconstruct([i] * S, list(range(S)))
+            for s in (0, S - 1):
+                got = hip.read_frame(s, p.desc.dst_slot)
+                compare(got, want, "%s, P264AMD_BS_FUSED=%s: picture %d stream %d" % (case, fused, i, s))
 
 
 @pytest.mark.parametrize("band_log2,wgs", [("0", "4"), ("2", "7"), ("6", "200"), ("1", "16")])
@@ -129,16 +116,14 @@ def test_mc_launch_knobs(lib, oracle, band_log2, wgs, monkeypatch):
     mb_w, mb_h = pics[0].mb_w, pics[0].mb_h
     S = 5
     store = oracle_bind.FrameStore(mb_w, mb_h, parser.slots)
-    hip = HipReconstructor(mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics), lib=lib)
-    hip.upload(0, pics)
-    for i, p in enumerate(pics):
-        want = oracle_bind.reconstruct(oracle, store, p)
-        hip.reconstruct([i] * S, list(range(S)))
-        for s in (0, S - 1):
-            got = hip.read_frame(s, p.desc.dst_slot)
-            for plane, (a, b) in enumerate(zip(got, want)):
-                assert np.array_equal(a, b), "band %s wgs %s: picture %d stream %d plane %d differs" % (band_log2, wgs, i, s, plane)
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics)) as hip:
+        hip.upload(0, pics)
+        for i, p in enumerate(pics):
+            want = oracle_bind.reconstruct(oracle, store, p)
+            hip.reconstruct([i] * S, list(range(S)))
+            for s in (0, S - 1):
+                got = hip.read_frame(s, p.desc.dst_slot)
+                compare(got, want, "band %s wgs %s: picture %d stream %d" % (band_log2, wgs, i, s))
 
 
 def test_vectors_far_outside_the_picture(lib, oracle):
@@ -149,11 +134,9 @@ def test_vectors_far_outside_the_picture(lib, oracle):
     pics = parser.parse_stream(open(synth_cases.generate("--mbw 10 --mbh 8 --frames 6 --gop 6 --seed 29 --mvmax 400 --coded 5 --maxlevel 6"), "rb").read())
     mb_w, mb_h = pics[0].mb_w, pics[0].mb_h
     store = oracle_bind.FrameStore(mb_w, mb_h, parser.slots)
-    hip = HipReconstructor(mb_w, mb_h, n_streams=1, slots=parser.slots, max_pictures=1, lib=lib)
-    for i, p in enumerate(pics):
-        want = oracle_bind.reconstruct(oracle, store, p)
-        hip.submit(0, p)
-        got = hip.read_frame(0, p.desc.dst_slot)
-        for plane, (a, b) in enumerate(zip(got, want)):
-            assert np.array_equal(a, b), "picture %d plane %d differs" % (i, plane)
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=1, slots=parser.slots, max_pictures=1) as hip:
+        for i, p in enumerate(pics):
+            want = oracle_bind.reconstruct(oracle, store, p)
+            hip.submit(0, p)
+            got = hip.read_frame(0, p.desc.dst_slot)
+            compare(got, want, "picture %d" % i)

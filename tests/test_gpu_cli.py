@@ -7,12 +7,10 @@ import subprocess
 
 import pytest
 
-from p264decoder_amd import build as _build
 from tests.conftest import GOLDEN
+from tests.hip_harness import CLI
 
 pytestmark = pytest.mark.gpu
-
-CLI = os.path.join(os.path.dirname(_build.__file__), "tools", "p264decoder_amd")
 
 
 def test_cli_f26_matches_reference(tmp_path, f26_hashes):

@@ -16,10 +16,10 @@ import collections
 import numpy as np
 import pytest
 
-from p264decoder_amd import HipReconstructor, _native as N
+from p264decoder_amd import _native as N
 from tests import deblock_checker as dc
 from tests import deblock_stim, oracle_bind, seam_fuzz
-from tests.test_gpu_seam_fuzz import compare
+from tests.hip_harness import compare, load_frames, reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -78,19 +78,15 @@ def run_batch(lib, direction, batch, extra=None):
     mb_w, mb_h = GEOMS[direction]
     pics = [b[1] for b in batch] + ([extra] if extra is not None else [])
     n = len(pics)
-    hip = HipReconstructor(mb_w, mb_h, n_streams=n, slots=SLOTS, max_pictures=n, lib=lib)
-    try:
+    with reconstructor(lib, mb_w, mb_h, n_streams=n, slots=SLOTS, max_pictures=n) as hip:
         for s, (name, pic, frames, want) in enumerate(batch):
-            for slot, f in frames.items():
-                hip.write_frame(s, slot, *f)
+            load_frames(hip, s, frames)
         hip.upload(0, pics)
         hip.reconstruct(list(range(n)), list(range(n)))
         li = hip.last_launch()
         assert li["pictures"] == n
         for s, (name, pic, frames, want) in enumerate(batch):
             compare(hip.read_frame(s, 0), want, "%s (stream %d of %d)" % (name, s, n), pic)
-    finally:
-        hip.close()
     return li
 
 
@@ -181,14 +177,11 @@ def test_1080p_of_stimulus_rows_repeated(lib, oracle):
     census = collections.Counter()
     want = deblock_stim.expected(oracle, big, census)
     assert sum(n for c, n in census.items() if c[1] == 4) > 20000 and sum(n for c, n in census.items() if c[1] == 3) > 20000
-    hip = HipReconstructor(big.pic.mb_w, big.pic.mb_h, n_streams=1, slots=SLOTS, max_pictures=1, lib=lib)
-    try:
+    with reconstructor(lib, big.pic.mb_w, big.pic.mb_h, n_streams=1, slots=SLOTS, max_pictures=1) as hip:
         for slot in big.ref_slots:
             hip.write_frame(0, slot, *big.frame)
         hip.submit(0, big.pic)
         compare(hip.read_frame(0, 0), want, big.name, big.pic)
-    finally:
-        hip.close()
 
 
 def test_the_census_behind_this_file(cases):

@@ -6,17 +6,16 @@ batch entry j decodes source j % K (K = 10 and 9, more than the 8 and 4 pictures
 hashes, the others against the oracle."""
 import pytest
 
-from p264decoder_amd import HipReconstructor, _native as N
+from p264decoder_amd import _native as N
 from tests import distinct_pool
+from tests.hip_harness import reconstructor
 
 pytestmark = pytest.mark.gpu
 
 
 def compute_units(lib, pool):
-    probe = HipReconstructor(pool.mb_w, pool.mb_h, n_streams=1, slots=pool.slots, max_pictures=1, lib=lib)
-    n_cu = probe.last_launch()["compute_units"]
-    probe.close()
-    return n_cu
+    with reconstructor(lib, pool.mb_w, pool.mb_h, n_streams=1, slots=pool.slots, max_pictures=1) as probe:
+        return probe.last_launch()["compute_units"]
 
 
 def test_the_bench_s_own_batch_with_distinct_sources(lib, oracle):
@@ -28,16 +27,13 @@ def test_the_bench_s_own_batch_with_distinct_sources(lib, oracle):
     n_cu = compute_units(lib, pool)
     S = 8 * n_cu
     assert pool.K > 8
-    hip = HipReconstructor(pool.mb_w, pool.mb_h, n_streams=S, slots=pool.slots, max_pictures=pool.K, lib=lib)
 
     def on_step(t, li, pics):
         assert li["pictures"] == S and li["deblock_pics_per_wg"] == 8 and li["deblock_rb_log2"] == 2 and li["deblock_wgs"] == n_cu and li["intra_waves"] == 4, li
         if all(p.desc.slice_type == N.SLICE_P for p in pics):
             assert li["mc_wgs_per_picture"] == 48 and li["edge_info_fused"] == 1, li
-    try:
+    with reconstructor(lib, pool.mb_w, pool.mb_h, n_streams=S, slots=pool.slots, max_pictures=pool.K) as hip:
         pool.run(hip, S, 2048, on_step)
-    finally:
-        hip.close()
 
 
 def test_config4_batch_with_distinct_sources(lib, oracle):
@@ -49,7 +45,6 @@ def test_config4_batch_with_distinct_sources(lib, oracle):
     n_cu = compute_units(lib, pool)
     S = 4 * n_cu
     assert pool.K > 4 and not any(p.desc.explicit_wp for s in pool.sources for p in s.pics)
-    hip = HipReconstructor(pool.mb_w, pool.mb_h, n_streams=S, slots=pool.slots, max_pictures=pool.K, lib=lib)
     kinds = []
 
     def on_step(t, li, pics):
@@ -62,8 +57,6 @@ def test_config4_batch_with_distinct_sources(lib, oracle):
             # a B picture in the step: the B instances and k_deblock_bs<true>; P pictures only: the fused edge info
             assert li["edge_info_fused"] == (0 if N.SLICE_B in types else 1), (t, li)
         kinds.append(types)
-    try:
+    with reconstructor(lib, pool.mb_w, pool.mb_h, n_streams=S, slots=pool.slots, max_pictures=pool.K) as hip:
         pool.run(hip, S, 1024, on_step)
-    finally:
-        hip.close()
     assert {N.SLICE_P} in kinds and {N.SLICE_B} in kinds and kinds.count({N.SLICE_P, N.SLICE_B}) == 3, kinds

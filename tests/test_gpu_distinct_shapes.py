@@ -8,17 +8,13 @@ index is its stream.  Every stream of every step is checked; last_launch() shows
 instance ran."""
 import pytest
 
-from p264decoder_amd import HipReconstructor
 from tests import distinct_pool
-from tests.test_gpu_batch_shapes import SHAPES
+from tests.hip_harness import reconstructor
+from tests.stream_args import DISTINCT_STREAMS as S, LAUNCH_SHAPES as SHAPES, ODD, WAVES
 
 pytestmark = pytest.mark.gpu
 
-S = 37                                   # streams: more than two pools' worth, prime - the last workgroup of every shape is partly empty
 POOLS = {"p": (distinct_pool.POOL_P, 8), "b": (distinct_pool.POOL_B, 7), "wp": (distinct_pool.POOL_WP, 7)}
-ODD = ["3", "5", "7", "13"]                # odd pictures per k_deblock workgroup
-# (P264AMD_DEBLOCK_RB_LOG2, P264AMD_DEBLOCK_PICS_PER_WG, P264AMD_DEBLOCK_WAVES): more units than wavefronts
-WAVES = [("2", "4", "3"), ("3", "4", "5"), ("1", "8", "1"), ("2", "7", "2"), ("3", "3", "2")]
 FUSED = ["0", "1", "3", "16"]
 MC_KNOBS = [("0", "4"), ("2", "7"), ("6", "200"), ("1", "16")]
 
@@ -36,11 +32,8 @@ def pools(lib, oracle):
 
 
 def run(lib, pool, seed, on_step):
-    hip = HipReconstructor(pool.mb_w, pool.mb_h, n_streams=S, slots=pool.slots, max_pictures=pool.K, lib=lib)
-    try:
+    with reconstructor(lib, pool.mb_w, pool.mb_h, n_streams=S, slots=pool.slots, max_pictures=pool.K) as hip:
         pool.run(hip, S, seed, on_step)
-    finally:
-        hip.close()
 
 
 @pytest.mark.parametrize("rb,per_wg,intra_waves", SHAPES)

@@ -10,11 +10,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from p264decoder_amd import HipReconstructor, Parser, _native as N
+from p264decoder_amd import Parser, _native as N
 from p264decoder_amd.recon import P264Error
 from tests import export_checker as X
 from tests import synth_cases
 from tests.device_mem import DeviceBuffer
+from tests.hip_harness import reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -29,16 +30,15 @@ TAIL = 48          # bytes of the destination behind the last picture: they stay
 @pytest.fixture(scope="module")
 def store(lib):
     """a context whose six frames hold random planes, and those planes as read_frame returns them"""
-    hip = HipReconstructor(MB_W, MB_H, n_streams=STREAMS, slots=SLOTS, max_pictures=STREAMS, lib=lib)
-    g = np.random.default_rng(2640)
-    w, h = MB_W * 16, MB_H * 16
-    for s in range(STREAMS):
-        for k in range(SLOTS):
-            # (full range of every plane: the RGB clips are reached)
-            hip.write_frame(s, k, g.integers(0, 256, (h, w), np.uint8), g.integers(0, 256, (h // 2, w // 2), np.uint8), g.integers(0, 256, (h // 2, w // 2), np.uint8))
-    planes = {(s, k): hip.read_frame(s, k) for s in range(STREAMS) for k in range(SLOTS)}
-    yield hip, planes
-    hip.close()
+    with reconstructor(lib, MB_W, MB_H, n_streams=STREAMS, slots=SLOTS, max_pictures=STREAMS) as hip:
+        g = np.random.default_rng(2640)
+        w, h = MB_W * 16, MB_H * 16
+        for s in range(STREAMS):
+            for k in range(SLOTS):
+                # (full range of every plane: the RGB clips are reached)
+                hip.write_frame(s, k, g.integers(0, 256, (h, w), np.uint8), g.integers(0, 256, (h // 2, w // 2), np.uint8), g.integers(0, 256, (h // 2, w // 2), np.uint8))
+        planes = {(s, k): hip.read_frame(s, k) for s in range(STREAMS) for k in range(SLOTS)}
+        yield hip, planes
 
 
 def run(hip, planes, streams, slots, fmt, crop, matrix="bt601", full=False, pitch=0, stride=0, offset=0):
@@ -86,22 +86,21 @@ def test_i420_of_the_full_frame_is_the_planar_road(store):
 
 def test_more_pictures_than_a_grid_dimension(lib):
     """70 000 pictures of a 1 x 1 macroblock context (27 MB of I420): the launch is chunked at 65 535"""
-    hip = HipReconstructor(1, 1, n_streams=2, slots=2, max_pictures=1, lib=lib)
-    g = np.random.default_rng(7)
-    for s in range(2):
-        for k in range(2):
-            hip.write_frame(s, k, g.integers(0, 256, (16, 16), np.uint8), g.integers(0, 256, (8, 8), np.uint8), g.integers(0, 256, (8, 8), np.uint8))
-    planes = {(s, k): hip.read_frame(s, k) for s in range(2) for k in range(2)}
-    n = 70000
-    which = (np.arange(n) * 7 + np.arange(n) // 65535) % 4              # (stream, slot) = (which >> 1, which & 1); the pattern shifts at the seam
-    dst = DeviceBuffer(lib, n * 384 + TAIL)
-    hip.export_frames((which >> 1).tolist(), (which & 1).tolist(), "i420", out=(dst.ptr, n * 384))
-    got = dst.host()
-    dst.free()
-    four = np.stack([X.expected([planes[(w >> 1, w & 1)]], "i420", (0, 0, 16, 16)) for w in range(4)])
-    assert np.array_equal(got[:n * 384].reshape(n, 384), four[which])
-    assert np.all(got[n * 384:] == 0xA5)
-    hip.close()
+    with reconstructor(lib, 1, 1, n_streams=2, slots=2, max_pictures=1) as hip:
+        g = np.random.default_rng(7)
+        for s in range(2):
+            for k in range(2):
+                hip.write_frame(s, k, g.integers(0, 256, (16, 16), np.uint8), g.integers(0, 256, (8, 8), np.uint8), g.integers(0, 256, (8, 8), np.uint8))
+        planes = {(s, k): hip.read_frame(s, k) for s in range(2) for k in range(2)}
+        n = 70000
+        which = (np.arange(n) * 7 + np.arange(n) // 65535) % 4              # (stream, slot) = (which >> 1, which & 1); the pattern shifts at the seam
+        dst = DeviceBuffer(lib, n * 384 + TAIL)
+        hip.export_frames((which >> 1).tolist(), (which & 1).tolist(), "i420", out=(dst.ptr, n * 384))
+        got = dst.host()
+        dst.free()
+        four = np.stack([X.expected([planes[(w >> 1, w & 1)]], "i420", (0, 0, 16, 16)) for w in range(4)])
+        assert np.array_equal(got[:n * 384].reshape(n, 384), four[which])
+        assert np.all(got[n * 384:] == 0xA5)
 
 
 def test_an_export_runs_behind_the_reconstruct_before_it(lib):
@@ -109,16 +108,15 @@ def test_an_export_runs_behind_the_reconstruct_before_it(lib):
     parser = Parser(lib=lib)
     pics = parser.parse_stream(data)
     assert len(pics) == 3
-    hip = HipReconstructor(MB_W, MB_H, n_streams=1, slots=parser.slots, max_pictures=1, lib=lib)
-    dst = DeviceBuffer(lib, 80 * 48 * 3 // 2)
-    for p in pics:
-        hip.submit(0, p)                                                   # asynchronous: nothing waits for the kernels ...
-        hip.export_frames([0], [p.desc.dst_slot], "i420", out=(dst.ptr, dst.nbytes), sync=True)   # ... but the export is queued behind them
-        want = X.expected([hip.read_frame(0, p.desc.dst_slot)], "i420", (0, 0, 80, 48))
-        assert np.array_equal(dst.host(), want)
-    dst.free()
-    assert len({bytes(hip.read_frame(0, p.desc.dst_slot)[0]) for p in pics[:2]}) == 2      # (the pictures differ: a stale frame would show)
-    hip.close()
+    with reconstructor(lib, MB_W, MB_H, n_streams=1, slots=parser.slots, max_pictures=1) as hip:
+        dst = DeviceBuffer(lib, 80 * 48 * 3 // 2)
+        for p in pics:
+            hip.submit(0, p)                                                   # asynchronous: nothing waits for the kernels ...
+            hip.export_frames([0], [p.desc.dst_slot], "i420", out=(dst.ptr, dst.nbytes), sync=True)   # ... but the export is queued behind them
+            want = X.expected([hip.read_frame(0, p.desc.dst_slot)], "i420", (0, 0, 80, 48))
+            assert np.array_equal(dst.host(), want)
+        dst.free()
+        assert len({bytes(hip.read_frame(0, p.desc.dst_slot)[0]) for p in pics[:2]}) == 2      # (the pictures differ: a stale frame would show)
 
 
 def test_refusals_queue_nothing(store):

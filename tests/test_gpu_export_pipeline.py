@@ -5,10 +5,11 @@ tests/export_checker.py."""
 import numpy as np
 import pytest
 
-from p264decoder_amd import HipReconstructor, Parser, Pipeline
+from p264decoder_amd import Parser, Pipeline
 from tests import export_checker as X
 from tests import synth_cases
 from tests.device_mem import DeviceBuffer
+from tests.hip_harness import reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -30,12 +31,11 @@ def alone(lib, streams):
         parser = Parser(lib=lib)
         pics = parser.parse_stream(data)
         assert parser.crop == WINDOW
-        hip = HipReconstructor(8, 6, n_streams=1, slots=parser.slots, max_pictures=1, lib=lib)
-        frames = []
-        for p in pics:
-            hip.submit(0, p)
-            frames.append(hip.read_frame(0, p.desc.dst_slot))
-        hip.close()
+        with reconstructor(lib, 8, 6, n_streams=1, slots=parser.slots, max_pictures=1) as hip:
+            frames = []
+            for p in pics:
+                hip.submit(0, p)
+                frames.append(hip.read_frame(0, p.desc.dst_slot))
         out.append(frames)
     assert tuple(len(f) for f in out) == FRAMES
     return out

@@ -7,9 +7,10 @@ per-frame SHA-256 of the real reference decoder.  f26 exercises I4x4, I16x16, P_
 import numpy as np
 import pytest
 
-from p264decoder_amd import Decoder, HipReconstructor, Parser
+from p264decoder_amd import Decoder, Parser
 from tests import oracle_bind
 from tests.conftest import frame_sha256
+from tests.hip_harness import reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -19,18 +20,17 @@ def test_f26_hip_vs_oracle_and_reference(lib, oracle, f26, f26_hashes):
     pics = parser.parse_stream(f26)
     mb_w, mb_h = pics[0].mb_w, pics[0].mb_h
     store = oracle_bind.FrameStore(mb_w, mb_h, parser.slots)
-    hip = HipReconstructor(mb_w, mb_h, n_streams=1, slots=parser.slots, max_pictures=1, lib=lib)
-    for i, p in enumerate(pics):
-        ref = oracle_bind.reconstruct(oracle, store, p)
-        hip.submit(0, p)
-        got = hip.read_frame(0, p.desc.dst_slot)
-        for plane, (a, b) in enumerate(zip(got, ref)):
-            if not np.array_equal(a, b):
-                ys, xs = np.nonzero(a != b)
-                pytest.fail("frame %d plane %d: %d samples differ, first at (y=%d,x=%d) MB (%d,%d)" % (
-                    i, plane, len(ys), ys[0], xs[0], ys[0] // (16 if plane == 0 else 8), xs[0] // (16 if plane == 0 else 8)))
-        assert frame_sha256(*got) == f26_hashes[i], "frame %d differs from the reference decoder" % i
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=1, slots=parser.slots, max_pictures=1) as hip:
+        for i, p in enumerate(pics):
+            ref = oracle_bind.reconstruct(oracle, store, p)
+            hip.submit(0, p)
+            got = hip.read_frame(0, p.desc.dst_slot)
+            for plane, (a, b) in enumerate(zip(got, ref)):
+                if not np.array_equal(a, b):
+                    ys, xs = np.nonzero(a != b)
+                    pytest.fail("frame %d plane %d: %d samples differ, first at (y=%d,x=%d) MB (%d,%d)" % (
+                        i, plane, len(ys), ys[0], xs[0], ys[0] // (16 if plane == 0 else 8), xs[0] // (16 if plane == 0 else 8)))
+            assert frame_sha256(*got) == f26_hashes[i], "frame %d differs from the reference decoder" % i
 
 
 def test_f26_dropin_api(lib, f26, f26_hashes):
@@ -50,11 +50,10 @@ def test_f26_batched_streams(lib, oracle, f26, f26_hashes):
     parser = Parser(quiet=True, lib=lib)
     pics = parser.parse_stream(f26, limit=12)
     S = 5
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics), lib=lib)
-    hip.upload(0, pics)
-    for i in range(len(pics)):
-        hip.reconstruct([i] * S, list(range(S)))
-    for s in range(S):
-        got = hip.read_frame(s, pics[-1].desc.dst_slot)
-        assert frame_sha256(*got) == f26_hashes[len(pics) - 1]
-    hip.close()
+    with reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=S, slots=parser.slots, max_pictures=len(pics)) as hip:
+        hip.upload(0, pics)
+        for i in range(len(pics)):
+            hip.reconstruct([i] * S, list(range(S)))
+        for s in range(S):
+            got = hip.read_frame(s, pics[-1].desc.dst_slot)
+            assert frame_sha256(*got) == f26_hashes[len(pics) - 1]

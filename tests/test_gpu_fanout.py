@@ -8,6 +8,7 @@ import os
 import pytest
 
 from tests import fan_helpers, synth_cases
+from tests.hip_harness import compare, reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -50,7 +51,7 @@ def test_fanout_device_road_two_ranks_one_gpu(lib, f26, f26_hashes, monkeypatch)
     for i in range(24):
         assert got[(1, i)] == cif_h[i] and got[(2, i)] == cif_h[i]
     # B pictures (list-1 arrays and the weight table are part of the block) and 1080p
-    from tests.test_input_layout import B_CIF
+    from tests.stream_args import B_CIF
     from tests import oracle_bind
     from p264decoder_amd import Parser
     b = synth_cases.stream_bytes(B_CIF)
@@ -88,32 +89,30 @@ def test_packed_upload_and_reserved_slots_match_the_plain_upload(lib):
     import ctypes as C
     import numpy as np
     from p264decoder_amd import HipReconstructor, Parser
-    from tests.test_input_layout import B_CIF
+    from tests.stream_args import B_CIF
     parser = Parser(quiet=True, lib=lib)
     pics = parser.parse_stream(synth_cases.stream_bytes(B_CIF))
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=3, slots=parser.slots, max_pictures=3, lib=lib)
-    for p in pics:
-        blk = HipReconstructor.pack(p, lib)
-        hip.upload(0, [p])
-        hip.upload_packed(1, p, blk)
-        dev, n = hip.input_reserve(2, p)
-        assert n == blk.size
-        with pytest.raises(Exception):
-            hip.reconstruct([2], [2])                             # reserved, not committed: the slot is not usable yet
-        assert lib.p264hip_copy_to_device(dev, blk.ctypes.data, n) == 0
-        hip.input_commit(2)
-        hip.reconstruct([0, 1, 2], [0, 1, 2])
-        hip.sync()
-        f0 = hip.read_frame(0, p.desc.dst_slot)
-        for s in (1, 2):
-            for a, b in zip(f0, hip.read_frame(s, p.desc.dst_slot)):
-                assert np.array_equal(a, b)
-        pdev, pn = hip.frame_planar_device(2, p.desc.dst_slot, index=1)
-        hip.sync()
-        flat = np.empty(pn, np.uint8)
-        assert lib.p264hip_copy_from_device(flat.ctypes.data, pdev, pn) == 0
-        assert np.array_equal(flat, np.concatenate([a.reshape(-1) for a in f0]))
-    hip.close()
+    with reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=3, slots=parser.slots, max_pictures=3) as hip:
+        for p in pics:
+            blk = HipReconstructor.pack(p, lib)
+            hip.upload(0, [p])
+            hip.upload_packed(1, p, blk)
+            dev, n = hip.input_reserve(2, p)
+            assert n == blk.size
+            with pytest.raises(Exception):
+                hip.reconstruct([2], [2])                             # reserved, not committed: the slot is not usable yet
+            assert lib.p264hip_copy_to_device(dev, blk.ctypes.data, n) == 0
+            hip.input_commit(2)
+            hip.reconstruct([0, 1, 2], [0, 1, 2])
+            hip.sync()
+            f0 = hip.read_frame(0, p.desc.dst_slot)
+            for s in (1, 2):
+                compare(f0, hip.read_frame(s, p.desc.dst_slot), "the same picture on two streams")
+            pdev, pn = hip.frame_planar_device(2, p.desc.dst_slot, index=1)
+            hip.sync()
+            flat = np.empty(pn, np.uint8)
+            assert lib.p264hip_copy_from_device(flat.ctypes.data, pdev, pn) == 0
+            assert np.array_equal(flat, np.concatenate([a.reshape(-1) for a in f0]))
 
 
 def test_a_committed_block_with_bad_records_is_an_error_not_a_fault(lib):
@@ -126,30 +125,28 @@ def test_a_committed_block_with_bad_records_is_an_error_not_a_fault(lib):
     from p264decoder_amd import _native as N
     parser = Parser(quiet=True, lib=lib)
     pics = parser.parse_stream(synth_cases.stream_bytes("cif_ip"))[:2]
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=2, slots=parser.slots, max_pictures=2, lib=lib)
-    p = pics[0]
-    blk = HipReconstructor.pack(p, lib).copy()
-    # record 5: coefficient blocks far beyond the stream (coef_index is the third dword of the 16-byte record)
-    words = blk[:p.mb_w * p.mb_h * 16].view(np.uint32).reshape(-1, 4)
-    coded = int(np.flatnonzero(words[:, 1] != 0)[0])
-    words[coded, 2] = 0x7fffff00
-    dev, n = hip.input_reserve(1, p)
-    assert lib.p264hip_copy_to_device(dev, blk.ctypes.data, n) == 0
-    hip.input_commit(1)
-    with pytest.raises(Exception, match="outside coefs"):
-        hip.reconstruct([1], [1])
-    hip.sync()
-    # the same slot, the intact block: decodes like the plain upload
-    good = HipReconstructor.pack(p, lib)
-    dev, n = hip.input_reserve(1, p)
-    assert lib.p264hip_copy_to_device(dev, good.ctypes.data, n) == 0
-    hip.input_commit(1)
-    hip.upload(0, [p])
-    hip.reconstruct([0, 1], [0, 1])
-    hip.sync()
-    for a, b in zip(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(1, p.desc.dst_slot)):
-        assert np.array_equal(a, b)
-    hip.close()
+    with reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=2, slots=parser.slots, max_pictures=2) as hip:
+        p = pics[0]
+        blk = HipReconstructor.pack(p, lib).copy()
+        # record 5: coefficient blocks far beyond the stream (coef_index is the third dword of the 16-byte record)
+        words = blk[:p.mb_w * p.mb_h * 16].view(np.uint32).reshape(-1, 4)
+        coded = int(np.flatnonzero(words[:, 1] != 0)[0])
+        words[coded, 2] = 0x7fffff00
+        dev, n = hip.input_reserve(1, p)
+        assert lib.p264hip_copy_to_device(dev, blk.ctypes.data, n) == 0
+        hip.input_commit(1)
+        with pytest.raises(Exception, match="outside coefs"):
+            hip.reconstruct([1], [1])
+        hip.sync()
+        # the same slot, the intact block: decodes like the plain upload
+        good = HipReconstructor.pack(p, lib)
+        dev, n = hip.input_reserve(1, p)
+        assert lib.p264hip_copy_to_device(dev, good.ctypes.data, n) == 0
+        hip.input_commit(1)
+        hip.upload(0, [p])
+        hip.reconstruct([0, 1], [0, 1])
+        hip.sync()
+        compare(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(1, p.desc.dst_slot), "the same picture on two streams")
 
 
 def test_rccl_transport_self_exchange(lib):
@@ -181,21 +178,20 @@ def test_rccl_transport_self_exchange(lib):
     from p264decoder_amd import HipReconstructor
     assert t.send_dev and t.recv_dev
     send_dev, recv_dev = SEND(t.send_dev), SEND(t.recv_dev)
-    hip = HipReconstructor(120, 68, n_streams=1, slots=2, max_pictures=1, lib=lib)
-    (src, n), (dst, _) = hip.frame_planar_device(0, 0, index=0), hip.frame_planar_device(0, 1, index=1)
-    hip.sync()
-    assert n == 3133440
-    data = rng.integers(0, 256, size=n, dtype=np.uint8)
-    back = np.zeros(n, np.uint8)
-    assert lib.p264hip_copy_to_device(src, data.ctypes.data, n) == 0 and lib.p264hip_copy_to_device(dst, back.ctypes.data, n) == 0
-    ctrl, rctrl = rng.integers(0, 256, size=272, dtype=np.uint8), np.zeros(272, np.uint8)
-    assert begin(t.ctx) == 0
-    assert send(t.ctx, 0, ctrl.ctypes.data, ctrl.size) == 0 and send_dev(t.ctx, 0, src, n) == 0
-    assert recv(t.ctx, 0, rctrl.ctypes.data, rctrl.size) == 0 and recv_dev(t.ctx, 0, dst, n) == 0
-    assert end(t.ctx) == 0
-    assert lib.p264hip_copy_from_device(back.ctypes.data, dst, n) == 0
-    assert np.array_equal(ctrl, rctrl) and np.array_equal(data, back)
-    hip.close()
+    with reconstructor(lib, 120, 68, n_streams=1, slots=2, max_pictures=1) as hip:
+        (src, n), (dst, _) = hip.frame_planar_device(0, 0, index=0), hip.frame_planar_device(0, 1, index=1)
+        hip.sync()
+        assert n == 3133440
+        data = rng.integers(0, 256, size=n, dtype=np.uint8)
+        back = np.zeros(n, np.uint8)
+        assert lib.p264hip_copy_to_device(src, data.ctypes.data, n) == 0 and lib.p264hip_copy_to_device(dst, back.ctypes.data, n) == 0
+        ctrl, rctrl = rng.integers(0, 256, size=272, dtype=np.uint8), np.zeros(272, np.uint8)
+        assert begin(t.ctx) == 0
+        assert send(t.ctx, 0, ctrl.ctypes.data, ctrl.size) == 0 and send_dev(t.ctx, 0, src, n) == 0
+        assert recv(t.ctx, 0, rctrl.ctypes.data, rctrl.size) == 0 and recv_dev(t.ctx, 0, dst, n) == 0
+        assert end(t.ctx) == 0
+        assert lib.p264hip_copy_from_device(back.ctypes.data, dst, n) == 0
+        assert np.array_equal(ctrl, rctrl) and np.array_equal(data, back)
     close(t.ctx)
 
 
@@ -246,33 +242,31 @@ def test_a_clone_takes_the_verdict_of_the_record_check_along(lib):
     from p264decoder_amd import HipReconstructor, Parser
     parser = Parser(quiet=True, lib=lib)
     p = parser.parse_stream(synth_cases.stream_bytes("cif_ip"))[0]
-    hip = HipReconstructor(p.mb_w, p.mb_h, n_streams=3, slots=parser.slots, max_pictures=4, lib=lib)
-    good = HipReconstructor.pack(p, lib)
-    bad = good.copy()
-    words = bad[:p.mb_w * p.mb_h * 16].view(np.uint32).reshape(-1, 4)
-    words[int(np.flatnonzero(words[:, 1] != 0)[0]), 2] = 0x7fffff00
+    with reconstructor(lib, p.mb_w, p.mb_h, n_streams=3, slots=parser.slots, max_pictures=4) as hip:
+        good = HipReconstructor.pack(p, lib)
+        bad = good.copy()
+        words = bad[:p.mb_w * p.mb_h * 16].view(np.uint32).reshape(-1, 4)
+        words[int(np.flatnonzero(words[:, 1] != 0)[0]), 2] = 0x7fffff00
 
-    def commit(slot, blk):
-        dev, n = hip.input_reserve(slot, p)
-        assert lib.p264hip_copy_to_device(dev, blk.ctypes.data, n) == 0
-        hip.input_commit(slot)
-    commit(1, bad)
-    hip.clone_picture(2, 1)                                       # unchecked and bad: the clone is as bad
-    with pytest.raises(Exception, match="outside coefs"):
-        hip.reconstruct([2], [2])
-    hip.sync()
-    with pytest.raises(Exception, match="outside coefs"):         # (and so is the original, still)
-        hip.reconstruct([1], [1])
-    hip.sync()
-    # slot 2 has held a bad block; a good block committed into slot 3 and cloned into slot 2 must decode
-    commit(3, good)
-    hip.clone_picture(2, 3)
-    hip.upload(0, [p])
-    hip.reconstruct([0, 2], [0, 2])
-    hip.sync()
-    for a, b in zip(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(2, p.desc.dst_slot)):
-        assert np.array_equal(a, b)
-    hip.close()
+        def commit(slot, blk):
+            dev, n = hip.input_reserve(slot, p)
+            assert lib.p264hip_copy_to_device(dev, blk.ctypes.data, n) == 0
+            hip.input_commit(slot)
+        commit(1, bad)
+        hip.clone_picture(2, 1)                                       # unchecked and bad: the clone is as bad
+        with pytest.raises(Exception, match="outside coefs"):
+            hip.reconstruct([2], [2])
+        hip.sync()
+        with pytest.raises(Exception, match="outside coefs"):         # (and so is the original, still)
+            hip.reconstruct([1], [1])
+        hip.sync()
+        # slot 2 has held a bad block; a good block committed into slot 3 and cloned into slot 2 must decode
+        commit(3, good)
+        hip.clone_picture(2, 3)
+        hip.upload(0, [p])
+        hip.reconstruct([0, 2], [0, 2])
+        hip.sync()
+        compare(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(2, p.desc.dst_slot), "the same picture on two streams")
 
 
 def test_a_reserve_waits_for_the_expansion_of_its_slot(lib):
@@ -292,34 +286,33 @@ def test_a_reserve_waits_for_the_expansion_of_its_slot(lib):
     assert B.desc.slice_type == 2 and A.desc.slice_type == 0
     N = 512
     X, Y, others = N - 1, 0, list(range(1, N - 1))
-    hip = HipReconstructor(120, 68, n_streams=N, slots=parser.slots, max_pictures=N, lib=lib)
-    cb, pa, pb = HipReconstructor.pack_compact(B, lib), HipReconstructor.pack(A, lib), HipReconstructor.pack(B, lib)
-    blk = HipReconstructor.pack_compact(A, lib)
-    ptr = lib.p264hip_host_alloc(blk.size)
-    assert ptr
-    ca = np.frombuffer((C.c_uint8 * blk.size).from_address(ptr), np.uint8)
-    ca[:] = blk
-    # set-up: every buffer the timed sequence uses is at its size (no growth, and so no wait, on the way)
-    hip.upload_compact(X, B, cb)
-    for s in [Y] + others:
-        hip.upload_compact(s, A, ca)
-    hip.reconstruct(others, others)
-    hip.reconstruct([Y, X], [Y, X])
-    hip.sync()
-    for s in [Y] + others + [X]:
-        hip.upload_compact(s, A, ca)
-    dev, n = hip.input_reserve(Y, A)                              # waits for the stream: every upload so far is known done
-    assert lib.p264hip_copy_to_device(dev, pa.ctypes.data, n) == 0
-    hip.input_commit(Y)
-    hip.reconstruct(others, others)                               # expands Y .. X as one launch, X's job last; no wait
-    dev, n = hip.input_reserve(X, B)
-    assert n == pb.size
-    assert lib.p264hip_copy_to_device(dev, pb.ctypes.data, n) == 0
-    hip.input_commit(X)
-    hip.reconstruct([X], [X])
-    hip.sync()
-    got = frame_sha256(*hip.read_frame(X, B.desc.dst_slot))
-    hip.close()
+    with reconstructor(lib, 120, 68, n_streams=N, slots=parser.slots, max_pictures=N) as hip:
+        cb, pa, pb = HipReconstructor.pack_compact(B, lib), HipReconstructor.pack(A, lib), HipReconstructor.pack(B, lib)
+        blk = HipReconstructor.pack_compact(A, lib)
+        ptr = lib.p264hip_host_alloc(blk.size)
+        assert ptr
+        ca = np.frombuffer((C.c_uint8 * blk.size).from_address(ptr), np.uint8)
+        ca[:] = blk
+        # set-up: every buffer the timed sequence uses is at its size (no growth, and so no wait, on the way)
+        hip.upload_compact(X, B, cb)
+        for s in [Y] + others:
+            hip.upload_compact(s, A, ca)
+        hip.reconstruct(others, others)
+        hip.reconstruct([Y, X], [Y, X])
+        hip.sync()
+        for s in [Y] + others + [X]:
+            hip.upload_compact(s, A, ca)
+        dev, n = hip.input_reserve(Y, A)                              # waits for the stream: every upload so far is known done
+        assert lib.p264hip_copy_to_device(dev, pa.ctypes.data, n) == 0
+        hip.input_commit(Y)
+        hip.reconstruct(others, others)                               # expands Y .. X as one launch, X's job last; no wait
+        dev, n = hip.input_reserve(X, B)
+        assert n == pb.size
+        assert lib.p264hip_copy_to_device(dev, pb.ctypes.data, n) == 0
+        hip.input_commit(X)
+        hip.reconstruct([X], [X])
+        hip.sync()
+        got = frame_sha256(*hip.read_frame(X, B.desc.dst_slot))
     lib.p264hip_host_free(ptr)
     assert got == hashes[0]
 
@@ -332,24 +325,22 @@ def test_only_a_reserved_slot_can_be_committed(lib):
     from p264decoder_amd import HipReconstructor, Parser
     parser = Parser(quiet=True, lib=lib)
     p = parser.parse_stream(synth_cases.stream_bytes("cif_ip"))[0]
-    hip = HipReconstructor(p.mb_w, p.mb_h, n_streams=3, slots=parser.slots, max_pictures=3, lib=lib)
-    blk = HipReconstructor.pack(p, lib)
-    hip.upload(0, [p])
-    hip.input_reserve(1, p)
-    with pytest.raises(Exception, match="empty"):
-        hip.reconstruct([1], [1])
-    hip.upload_packed(1, p, blk)
-    assert lib.p264hip_input_commit(hip.h, 1) == -1               # P264HIP_EINVAL
-    hip.input_reserve(2, p)
-    hip.clone_picture(2, 0)
-    assert lib.p264hip_input_commit(hip.h, 2) == -1
-    hip.reconstruct([0, 1, 2], [0, 1, 2])
-    hip.sync()
-    f0 = hip.read_frame(0, p.desc.dst_slot)
-    for s in (1, 2):
-        for a, b in zip(f0, hip.read_frame(s, p.desc.dst_slot)):
-            assert np.array_equal(a, b)
-    hip.close()
+    with reconstructor(lib, p.mb_w, p.mb_h, n_streams=3, slots=parser.slots, max_pictures=3) as hip:
+        blk = HipReconstructor.pack(p, lib)
+        hip.upload(0, [p])
+        hip.input_reserve(1, p)
+        with pytest.raises(Exception, match="empty"):
+            hip.reconstruct([1], [1])
+        hip.upload_packed(1, p, blk)
+        assert lib.p264hip_input_commit(hip.h, 1) == -1               # P264HIP_EINVAL
+        hip.input_reserve(2, p)
+        hip.clone_picture(2, 0)
+        assert lib.p264hip_input_commit(hip.h, 2) == -1
+        hip.reconstruct([0, 1, 2], [0, 1, 2])
+        hip.sync()
+        f0 = hip.read_frame(0, p.desc.dst_slot)
+        for s in (1, 2):
+            compare(f0, hip.read_frame(s, p.desc.dst_slot), "the same picture on two streams")
 
 
 def test_compact_uploads_match_the_plain_upload(lib):
@@ -364,74 +355,67 @@ def test_compact_uploads_match_the_plain_upload(lib):
     parser = Parser(quiet=True, lib=lib)
     pics = parser.parse_stream(synth_cases.stream_bytes("cif_ip"))[:10]
     S = 3
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=S + 1, slots=parser.slots, max_pictures=S + 2, lib=lib)
-    blk0 = HipReconstructor.pack_compact(pics[0], lib)            # (every block stays alive until the sync behind its expansion)
-    for i, p in enumerate(pics):
-        blk = HipReconstructor.pack_compact(p, lib)
-        hip.upload(0, [p])
-        for s in range(1, S):
-            hip.upload_compact(s, p, blk)
-        if i == 3:                                              # superseded before it was expanded: the plain upload must win
-            hip.upload_compact(1, pics[0], blk0)
-            hip.upload(1, [p])
-        if i == 5:                                              # two compact blocks for one slot, no expansion in between: the later one counts
-            hip.upload_compact(2, pics[0], blk0)
-            hip.upload_compact(2, p, blk)
-        hip.clone_picture(S, 2)                                 # (expands what is pending first)
-        hip.reconstruct([0, 1, 2, S], [0, 1, 2, S])
-        hip.sync()
-        f0 = hip.read_frame(0, p.desc.dst_slot)
-        for s in (1, 2, S):
-            for a, b in zip(f0, hip.read_frame(s, p.desc.dst_slot)):
-                assert np.array_equal(a, b), "picture %d stream %d" % (i, s)
-    hip.close()
+    with reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=S + 1, slots=parser.slots, max_pictures=S + 2) as hip:
+        blk0 = HipReconstructor.pack_compact(pics[0], lib)            # (every block stays alive until the sync behind its expansion)
+        for i, p in enumerate(pics):
+            blk = HipReconstructor.pack_compact(p, lib)
+            hip.upload(0, [p])
+            for s in range(1, S):
+                hip.upload_compact(s, p, blk)
+            if i == 3:                                              # superseded before it was expanded: the plain upload must win
+                hip.upload_compact(1, pics[0], blk0)
+                hip.upload(1, [p])
+            if i == 5:                                              # two compact blocks for one slot, no expansion in between: the later one counts
+                hip.upload_compact(2, pics[0], blk0)
+                hip.upload_compact(2, p, blk)
+            hip.clone_picture(S, 2)                                 # (expands what is pending first)
+            hip.reconstruct([0, 1, 2, S], [0, 1, 2, S])
+            hip.sync()
+            f0 = hip.read_frame(0, p.desc.dst_slot)
+            for s in (1, 2, S):
+                compare(f0, hip.read_frame(s, p.desc.dst_slot), "picture %d stream %d" % (i, s))
     # seam-level pictures: every level style, sub-8x8 partitions, several references
     rng = np.random.default_rng(99)
     mb_w, mb_h = 9, 6
-    hip = HipReconstructor(mb_w, mb_h, n_streams=2, slots=3, max_pictures=2, lib=lib)
-    for s in range(2):
-        for slot in range(3):
-            hip.write_frame(s, slot, *seam_fuzz.random_frame(np.random.default_rng(5 + slot), mb_w, mb_h))
-    for k in range(12):
-        p = seam_fuzz.make_picture(rng, mb_w, mb_h, p_picture=(k != 3), b_picture=(k >= 8), n_ref=2, n_ref_l1=2, slots=3, dst_slot=k % 3,
-                                   level_style=["small", "large", "wrap", "mixed"][k % 4], sub8x8=True)
-        hip.upload(0, [p])
-        blk = HipReconstructor.pack_compact(p, lib)
-        hip.upload_compact(1, p, blk)
-        hip.reconstruct([0, 1], [0, 1])
-        hip.sync()
-        for a, b in zip(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(1, p.desc.dst_slot)):
-            assert np.array_equal(a, b), "seam picture %d" % k
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=2, slots=3, max_pictures=2) as hip:
+        for s in range(2):
+            for slot in range(3):
+                hip.write_frame(s, slot, *seam_fuzz.random_frame(np.random.default_rng(5 + slot), mb_w, mb_h))
+        for k in range(12):
+            p = seam_fuzz.make_picture(rng, mb_w, mb_h, p_picture=(k != 3), b_picture=(k >= 8), n_ref=2, n_ref_l1=2, slots=3, dst_slot=k % 3,
+                                       level_style=["small", "large", "wrap", "mixed"][k % 4], sub8x8=True)
+            hip.upload(0, [p])
+            blk = HipReconstructor.pack_compact(p, lib)
+            hip.upload_compact(1, p, blk)
+            hip.reconstruct([0, 1], [0, 1])
+            hip.sync()
+            compare(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(1, p.desc.dst_slot), "seam picture %d" % k)
     # a parsed Main-profile stream (CABAC, I + P + B, implicit weights, direct prediction): compact against plain, picture by picture
-    from tests.test_input_layout import B_CIF
+    from tests.stream_args import B_CIF
     parser = Parser(quiet=True, lib=lib)
     pics = parser.parse_stream(synth_cases.stream_bytes(B_CIF + " --cabac"))
     assert sum(p.desc.slice_type == 1 for p in pics) >= 3
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=2, slots=parser.slots, max_pictures=2, lib=lib)
-    for i, p in enumerate(pics):
-        hip.upload(0, [p])
-        blk = HipReconstructor.pack_compact(p, lib)
-        hip.upload_compact(1, p, blk)
-        hip.reconstruct([0, 1], [0, 1])
-        hip.sync()
-        for a, b in zip(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(1, p.desc.dst_slot)):
-            assert np.array_equal(a, b), "Main-profile picture %d (slice type %d)" % (i, p.desc.slice_type)
-    hip.close()
+    with reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=2, slots=parser.slots, max_pictures=2) as hip:
+        for i, p in enumerate(pics):
+            hip.upload(0, [p])
+            blk = HipReconstructor.pack_compact(p, lib)
+            hip.upload_compact(1, p, blk)
+            hip.reconstruct([0, 1], [0, 1])
+            hip.sync()
+            compare(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(1, p.desc.dst_slot), "Main-profile picture %d (slice type %d)" % (i, p.desc.slice_type))
     # 1080p: the golden all-P stream through compact uploads only, against the reference decoder's hashes
     from tests.conftest import frame_sha256
     parser = Parser(quiet=True, lib=lib)
     pics = parser.parse_stream(synth_cases.stream_bytes("cfg3_1080p_allp"), limit=4)
     hashes = synth_cases.golden("cfg3_1080p_allp")[1]
-    hip = HipReconstructor(120, 68, n_streams=1, slots=parser.slots, max_pictures=1, lib=lib)
-    sizes = []
-    for i, p in enumerate(pics):
-        blk = HipReconstructor.pack_compact(p, lib)
-        sizes.append((blk.size, HipReconstructor.pack(p, lib).size))
-        hip.upload_compact(0, p, blk)
-        hip.reconstruct([0], [0])
-        assert frame_sha256(*hip.read_frame(0, p.desc.dst_slot)) == hashes[i], "1080p picture %d through the compact format" % i
-    hip.close()
+    with reconstructor(lib, 120, 68, n_streams=1, slots=parser.slots, max_pictures=1) as hip:
+        sizes = []
+        for i, p in enumerate(pics):
+            blk = HipReconstructor.pack_compact(p, lib)
+            sizes.append((blk.size, HipReconstructor.pack(p, lib).size))
+            hip.upload_compact(0, p, blk)
+            hip.reconstruct([0], [0])
+            assert frame_sha256(*hip.read_frame(0, p.desc.dst_slot)) == hashes[i], "1080p picture %d through the compact format" % i
     assert all(c < 0.45 * f for c, f in sizes[1:]), sizes          # a P picture of the bench's kind: well under half its slot layout
 
 
@@ -446,31 +430,29 @@ def test_an_inconsistent_compact_block_is_a_wrong_picture_not_a_fault(lib):
     from p264decoder_amd import HipReconstructor, Parser, _native as N
     parser = Parser(quiet=True, lib=lib)
     pics = parser.parse_stream(synth_cases.stream_bytes("cif_ip"))[:3]
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=2, slots=parser.slots, max_pictures=2, lib=lib)
-    for p in pics:
-        good = HipReconstructor.pack_compact(p, lib)
-        hdr = N.CompactHdr.from_buffer_copy(good[:128].tobytes())
-        n = p.desc.mb_w * p.desc.mb_h
-        for what, lo, size, value in (("every macroblock sixteen vectors", hdr.list[0].off_shape, (n + 3) // 4, 0xff),
-                                      ("every macroblock an Intra4x4 entry", hdr.off_i4flag, (n + 7) // 8, 0xff),
-                                      ("every block sixteen-bit levels", hdr.off_lvflag, (p.desc.n_coef_blocks + 7) // 8, 0x00),
-                                      ("every block eight-bit levels", hdr.off_lvflag, (p.desc.n_coef_blocks + 7) // 8, 0xff)):
-            bad = good.copy()
-            bad[lo:lo + size] = value
-            if what == "every block eight-bit levels" and hdr.level_bytes == 16 * p.desc.n_coef_blocks:
-                continue                                       # (every block of this picture is narrow already: only padding bits would change)
-            assert lib.p264hip_compact_header_ok(C.byref(p.desc), bad.ctypes.data, bad.size) == 1, what
-            assert lib.p264hip_compact_check(C.byref(p.desc), bad.ctypes.data, bad.size) != 0, what
-            hip.upload_compact(1, p, bad)
-            hip.reconstruct([1], [1])                          # a wrong picture in stream 1's store; no fault, no error
+    with reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=2, slots=parser.slots, max_pictures=2) as hip:
+        for p in pics:
+            good = HipReconstructor.pack_compact(p, lib)
+            hdr = N.CompactHdr.from_buffer_copy(good[:128].tobytes())
+            n = p.desc.mb_w * p.desc.mb_h
+            for what, lo, size, value in (("every macroblock sixteen vectors", hdr.list[0].off_shape, (n + 3) // 4, 0xff),
+                                          ("every macroblock an Intra4x4 entry", hdr.off_i4flag, (n + 7) // 8, 0xff),
+                                          ("every block sixteen-bit levels", hdr.off_lvflag, (p.desc.n_coef_blocks + 7) // 8, 0x00),
+                                          ("every block eight-bit levels", hdr.off_lvflag, (p.desc.n_coef_blocks + 7) // 8, 0xff)):
+                bad = good.copy()
+                bad[lo:lo + size] = value
+                if what == "every block eight-bit levels" and hdr.level_bytes == 16 * p.desc.n_coef_blocks:
+                    continue                                       # (every block of this picture is narrow already: only padding bits would change)
+                assert lib.p264hip_compact_header_ok(C.byref(p.desc), bad.ctypes.data, bad.size) == 1, what
+                assert lib.p264hip_compact_check(C.byref(p.desc), bad.ctypes.data, bad.size) != 0, what
+                hip.upload_compact(1, p, bad)
+                hip.reconstruct([1], [1])                          # a wrong picture in stream 1's store; no fault, no error
+                hip.sync()
+            hip.upload(0, [p])
+            hip.upload_compact(1, p, good)
+            # stream 1's store holds garbage references by now: give both streams the same ones
+            for slot in range(parser.slots):
+                hip.write_frame(1, slot, *hip.read_frame(0, slot))
+            hip.reconstruct([0, 1], [0, 1])
             hip.sync()
-        hip.upload(0, [p])
-        hip.upload_compact(1, p, good)
-        # stream 1's store holds garbage references by now: give both streams the same ones
-        for slot in range(parser.slots):
-            hip.write_frame(1, slot, *hip.read_frame(0, slot))
-        hip.reconstruct([0, 1], [0, 1])
-        hip.sync()
-        for a, b in zip(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(1, p.desc.dst_slot)):
-            assert np.array_equal(a, b)
-    hip.close()
+            compare(hip.read_frame(0, p.desc.dst_slot), hip.read_frame(1, p.desc.dst_slot), "the same picture on two streams")

@@ -7,77 +7,40 @@ import numpy as np
 import pytest
 
 from p264decoder_amd import HipReconstructor, _native as N
-from p264decoder_amd.recon import P264Error
+from tests import hip_harness as H
 from tests import i8x8_checker as I8
 from tests import i8x8_stim as IS
 from tests import inter_stim
 from tests import spec_recon
 from tests import t8x8_checker as T8
-from tests import t8x8_stim as TS
-from tests.test_gpu_inter_spec import by_size, differences
+from tests import synth_cases, t8x8_stim as TS
 
 pytestmark = pytest.mark.gpu
 SLOTS = 3
 
 
-def expect(st, cls=I8.SpecRecon):
-    spec = cls(st.pic.mb_w, st.pic.mb_h, SLOTS)
-    for slot, f in st.frames.items():
-        spec.store.write(slot, f)
-    return [p.copy() for p in spec.reconstruct(st.pic)]
-
-
 @pytest.fixture(scope="module")
 def expected():
     """{set: [(stim, [y, u, v] by the standard)]}"""
-    return {which: [(st, expect(st)) for st in getattr(IS, which)()] for which in IS.SETS}
+    return {which: [(st, H.expect(st, I8.SpecRecon, SLOTS)) for st in getattr(IS, which)()] for which in IS.SETS}
 
 
 def has_i8(st):
     return bool(int(st.pic.desc.transform_8x8) & N.T8X8_INTRA)
 
 
+def launch_and_flag(hip, batch):
+    """per batch: (what the launch reported, whether a picture of the batch carries N.T8X8_INTRA)"""
+    return hip.last_intra_i8(), int(any(has_i8(st) for st, _ in batch))
+
+
 @pytest.mark.parametrize("which", IS.SETS)
 def test_submit_equals_the_standard(lib, expected, which):
-    bad, sent = [], []
-    for (mb_w, mb_h), cases in by_size(expected[which]).items():
-        hip = HipReconstructor(mb_w, mb_h, n_streams=1, slots=SLOTS, max_pictures=1, lib=lib)
-        for st, want in cases:
-            for slot, f in st.frames.items():
-                hip.write_frame(0, slot, *f)
-            hip.submit(0, st.pic)
-            assert hip.last_intra_i8() == 1
-            bad += differences(hip.read_frame(0, st.pic.desc.dst_slot), want, st.name, st.pic)
-            sent.append(st)
-        hip.close()
+    def probe(hip, st):
+        assert hip.last_intra_i8() == 1
+    bad, sent = H.submit_each(lib, expected[which], SLOTS, probe)
     assert not bad, "%d of %d pictures differ: %s" % (len(bad), len(sent), bad[:3])
     IS.assert_covered(which, sent)
-
-
-def run_batches(lib, cases, n=3, road="upload"):
-    """the cases (one picture size) in batches of n distinct pictures, one stream each.  Returns (differences, the stimuli sent,
-    per batch (what the launch reported, whether a picture of the batch carries N.T8X8_INTRA))"""
-    (mb_w, mb_h), = {(st.pic.mb_w, st.pic.mb_h) for st, _ in cases}
-    hip = HipReconstructor(mb_w, mb_h, n_streams=n, slots=SLOTS, max_pictures=n, lib=lib)
-    bad, sent, i8 = [], [], []
-    for at in range(0, len(cases), n):
-        batch = [cases[(at + k) % len(cases)] for k in range(n)]
-        assert len({id(st.pic) for st, _ in batch}) == n
-        for k, (st, _) in enumerate(batch):
-            for slot, f in st.frames.items():
-                hip.write_frame(k, slot, *f)
-        if road == "upload":
-            hip.upload(0, [st.pic for st, _ in batch])
-        else:
-            for k, (st, _) in enumerate(batch):
-                hip.upload_compact(k, st.pic, HipReconstructor.pack_compact(st.pic, lib))
-        hip.reconstruct(list(range(n)), list(range(n)))
-        i8.append((hip.last_intra_i8(), int(any(has_i8(st) for st, _ in batch))))
-        for k, (st, want) in enumerate(batch):
-            bad += differences(hip.read_frame(k, st.pic.desc.dst_slot), want, "%s (stream %d of a batch, %s)" % (st.name, k, road), st.pic)
-            sent.append(st)
-    hip.close()
-    return bad, sent, i8
 
 
 @pytest.fixture(scope="module")
@@ -94,21 +57,21 @@ def small_dense():
         RC.make_conformant(pic)
         drawn, redrawn = IS.convert(pic, rng, {m for m in range(w * h) if m % 5}, plan)
         st = IS.Stim("dense I %dx%d %d" % (w, h, i), pic, {}, drawn, redrawn)
-        out.append((st, expect(st)))
+        out.append((st, H.expect(st, I8.SpecRecon, SLOTS)))
     return out
 
 
 @pytest.mark.parametrize("road", ["upload", "compact"])
 def test_batches_of_three_equal_the_standard(lib, expected, small_dense, road):
     for cases in (expected["inter_set"], small_dense + expected["inter_set"][:3]):
-        bad, sent, i8 = run_batches(lib, cases, road=road)
+        bad, sent, i8 = H.run_batches(lib, cases, road=road, slots=SLOTS, probe=launch_and_flag)
         assert not bad, "%d of %d pictures differ: %s" % (len(bad), len(sent), bad[:3])
         assert all(got == 1 and want == 1 for got, want in i8), i8
     # the 9 x 9 picture in three streams (the band hand-over with neighbours in flight): three copies of its arrays are distinct pictures
     st, want = expected["dense_set"][0]
     rng = np.random.default_rng(8325)
     more = [IS.dense_picture(rng, IS.Plan(rng), name="dense I 9x9 b%d" % i, deblock=bool(i)) for i in range(2)]
-    bad, sent, i8 = run_batches(lib, [(st, want)] + [(s, expect(s)) for s in more], road=road)
+    bad, sent, i8 = H.run_batches(lib, [(st, want)] + [(s, H.expect(s, I8.SpecRecon, SLOTS)) for s in more], road=road, slots=SLOTS, probe=launch_and_flag)
     assert not bad, "%d of %d pictures differ: %s" % (len(bad), len(sent), bad[:3])
     assert i8 == [(1, 1)]
 
@@ -121,7 +84,7 @@ def plain_picture(rng, name, **kw):
     pic = seam_fuzz.make_picture(rng, IS.MB_W, IS.MB_H, slots=SLOTS, dst_slot=0, level_style="small", qp_mode="random", mv_range=40, **kw)
     RC.make_conformant(pic)
     st = IS.Stim(name, pic, inter_stim.frames_for(rng, IS.MB_W, IS.MB_H) if kw.get("p_picture", True) else {}, 0, 0)
-    return st, expect(st, spec_recon.SpecRecon)
+    return st, H.expect(st, spec_recon.SpecRecon, SLOTS)
 
 
 def test_mixed_batches_and_what_the_launch_reports(lib, expected, small_dense):
@@ -130,18 +93,18 @@ def test_mixed_batches_and_what_the_launch_reports(lib, expected, small_dense):
     rng = np.random.default_rng(8326)
     d = {st.name: (st, want) for st, want in expected["inter_set"]}
     t8 = TS.drawn_picture(rng, "P with T8X8 alone", IS.MB_W, IS.MB_H, share=0.7, intra_share=0.1, slices=1, slice_idcs=[0])
-    t8_only = (t8, expect(t8, T8.SpecRecon))
+    t8_only = (t8, H.expect(t8, T8.SpecRecon, SLOTS))
     plain = [plain_picture(rng, "plain B", b_picture=True), plain_picture(rng, "plain P"), plain_picture(rng, "plain P 2", slices=2),
              plain_picture(rng, "plain I", p_picture=False)]
     assert not any(st.pic.desc.transform_8x8 for st, _ in plain) and int(t8.pic.desc.transform_8x8) == 1
     mixed = [small_dense[0], d["P cluster"], t8_only, plain[0]]
     assert [(int(st.pic.desc.slice_type), int(st.pic.desc.transform_8x8)) for st, _ in mixed] == [(N.SLICE_I, 2), (N.SLICE_P, 3), (N.SLICE_P, 1), (N.SLICE_B, 0)]
-    bad, sent, i8 = run_batches(lib, mixed, n=4)
+    bad, sent, i8 = H.run_batches(lib, mixed, n=4, slots=SLOTS, probe=launch_and_flag)
     assert not bad, "%d of %d pictures differ: %s" % (len(bad), len(sent), bad[:3])
     assert i8 == [(1, 1)]
     # without a flagged picture: T8X8-only and plain pictures, plain P / B alone, a plain I picture beside them (the dense launch)
     for cases in ([t8_only, plain[0], plain[1]], plain[:3], [plain[3], plain[1], plain[2]]):
-        bad, sent, i8 = run_batches(lib, cases)
+        bad, sent, i8 = H.run_batches(lib, cases, slots=SLOTS, probe=launch_and_flag)
         assert not bad and i8 == [(0, 0)], (bad[:3], i8)
 
 
@@ -164,83 +127,34 @@ def bad_records(pic):
 
 def test_the_device_roads_refuse_what_the_seam_forbids(lib, expected):
     st, want = next(c for c in expected["inter_set"] if c[0].name == "P cluster")
-    pic, rec = st.pic, st.pic.mb_records()
-    hip = HipReconstructor(pic.mb_w, pic.mb_h, n_streams=1, slots=SLOTS, max_pictures=2, lib=lib)
-    for slot, f in st.frames.items():
-        hip.write_frame(0, slot, *f)
-    good = HipReconstructor.pack(pic, lib)
-    t8_keep = int(pic.desc.transform_8x8)
-    for m, field, value, t8 in bad_records(pic):
-        keep = rec[field][m]
-        rec[field][m], pic.desc.transform_8x8 = value, t8
-        try:
-            with pytest.raises(P264Error):                      # p264hip_upload checks on the host
-                hip.upload(1, [pic])
-            bad = good.copy()
-            bad[16 * m:16 * m + 16] = np.frombuffer(rec[m:m + 1].tobytes(), np.uint8)
-            dev, n = hip.input_reserve(0, pic)                  # reserve / commit: the check runs on the device
-            assert n == bad.size and lib.p264hip_copy_to_device(dev, bad.ctypes.data, n) == 0
-            hip.input_commit(0)
-            with pytest.raises(P264Error):
-                hip.reconstruct([0], [0])
-        finally:
-            rec[field][m], pic.desc.transform_8x8 = keep, t8_keep
-    dev, n = hip.input_reserve(0, pic)
-    assert lib.p264hip_copy_to_device(dev, good.ctypes.data, n) == 0
-    hip.input_commit(0)
-    hip.reconstruct([0], [0])
-    assert hip.last_intra_i8() == 1
-    assert not differences(hip.read_frame(0, pic.desc.dst_slot), want, "the good picture behind the refused ones", pic)
-    hip.close()
+    pic = st.pic
+    with H.reconstructor(lib, pic.mb_w, pic.mb_h, n_streams=1, slots=SLOTS, max_pictures=2) as hip:
+        H.load_frames(hip, 0, st.frames)
+        H.refused_on_device_roads(lib, hip, pic, HipReconstructor.pack(pic, lib), bad_records(pic))
+        H.put(hip, lib, 0, pic, "commit")
+        hip.reconstruct([0], [0])
+        assert hip.last_intra_i8() == 1
+        assert not H.differences(hip.read_frame(0, pic.desc.dst_slot), want, "the good picture behind the refused ones", pic)
 
 
 # ---- a whole stream ------------------------------------------------------------------------------------------------------------
 STREAM = "--mbw 8 --mbh 6 --frames 10 --refs 2 --bframes 2 --d8inf --cabac --t8x8 60 --i8x8 60 --intra-pct 25 --qp 14 --qp-delta 3 --coded 35 --maxlevel 3 --seed 86"
 
 
-def stream_and_standard(lib):
-    """(Annex-B bytes, the parser's pictures, the parser's slots, per picture [y, u, v] by the checker run picture after picture on
-    its own frame store, the checker)"""
-    from p264decoder_amd import Parser
-    from tests import synth_cases
-    data = open(synth_cases.generate(STREAM), "rb").read()
-    parser = Parser(quiet=True, lib=lib, intra8x8=True)
-    pics = parser.parse_stream(data)
-    spec = I8.SpecRecon(pics[0].mb_w, pics[0].mb_h, parser.slots)
-    want = [[a.copy() for a in spec.reconstruct(p)] for p in pics]
-    return data, pics, parser.slots, want, spec
-
-
 def test_a_high_profile_cabac_stream_with_intra_8x8_end_to_end(lib, tmp_path):
     """synth264 --cabac --t8x8 60 --i8x8 60 (I, P and B pictures) through the parser and p264hip_submit, through the drop-in decoder
     and through the command-line decoder: every picture equals the standard's"""
-    import os
-    import subprocess
-    from p264decoder_amd import Decoder, build as _build
-    data, pics, slots, want, spec = stream_and_standard(lib)
+    data = open(synth_cases.generate(STREAM), "rb").read()
+    pics, slots, want, spec = H.parse_and_expect(lib, data, I8.SpecRecon, intra8x8=True)
     assert len(pics) == 10 and {int(p.desc.slice_type) for p in pics} == {N.SLICE_I, N.SLICE_P, N.SLICE_B}
     flagged = [int(((p.mb_records()["intra_modes"] & N.MB_I8X8) != 0).sum()) for p in pics]
     assert spec.met >= 7 and sum(f > 0 for f in flagged) == spec.met and sum(flagged) >= 30, flagged
     assert any((p.mb_records()["intra_modes"] & N.MB_T8X8).any() for p in pics)
     assert len(spec.census8.blocks) >= 30 and spec.tells["v"] + spec.tells["h"] > 0
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=1, slots=slots, max_pictures=1, lib=lib)
-    for i, (p, w) in enumerate(zip(pics, want)):
-        hip.submit(0, p)
+    def probe(hip, i, p):
         assert hip.last_intra_i8() == int(flagged[i] > 0)
-        assert not differences(hip.read_frame(0, p.desc.dst_slot), w, "picture %d" % i, p)
-    hip.close()
-    dec = Decoder(lib=lib)
-    got = [[np.array(a) for a in pic] for pic in dec.decode_annexb(data)]
-    dec.close()
+    H.submit_stream(lib, pics, slots, want, "p264hip_submit", probe)
+    got = H.dropin_pictures(lib, data)
     assert len(got) == 10
-    for i, (g, w) in enumerate(zip(got, want)):
-        for plane, (a, b) in enumerate(zip(g, w)):
-            assert np.array_equal(a[:b.shape[0], :b.shape[1]], b), "drop-in decoder: picture %d plane %d" % (i, plane)
-    cli = os.path.join(os.path.dirname(_build.__file__), "tools", "p264decoder_amd")
-    src, out = tmp_path / "i8.264", tmp_path / "rec.yuv"
-    src.write_bytes(data)
-    r = subprocess.run([cli, "-d", str(src), str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    raw = out.read_bytes()
-    frame = b"".join(b"".join(pl.tobytes() for pl in w) for w in want)
-    assert raw == frame, "the command-line decoder's pictures differ from the standard's"
+    H.compare_pictures(got, want, "drop-in decoder", crop=True)
+    assert H.cli_bytes(tmp_path, data) == H.planes_bytes(want), "the command-line decoder's pictures differ from the standard's"

@@ -10,8 +10,9 @@ All cases of a family go through ONE p264hip_reconstruct call (a stream per case
 import numpy as np
 import pytest
 
-from p264decoder_amd import HipReconstructor, _native as N
+from p264decoder_amd import _native as N
 from tests import kat_seam as K
+from tests.hip_harness import reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -25,23 +26,22 @@ def run_batch(lib, jobs, launch):
     """jobs: [(picture, reference frame)] of one picture size.  Returns the reconstructed [y, u, v] per job."""
     pic0 = jobs[0][0]
     S = len(jobs) + (1 if launch == "dense" else 0)
-    hip = HipReconstructor(pic0.mb_w, pic0.mb_h, n_streams=S, slots=2, max_pictures=S, lib=lib)
-    keep = []
-    for s, (pic, ref) in enumerate(jobs):
-        hip.write_frame(s, 1, *ref)
-        hip.upload(s, [pic])
-    if launch == "dense":
-        ip = K.base_picture(pic0.mb_w, pic0.mb_h)
-        ip.desc.slice_type, ip.desc.n_ref = N.SLICE_I, 0
-        ip.rec["mb_type"], ip.rec["intra_modes"] = N.MB_I16x16, 2
-        ip.ref_idx[:] = -1
-        keep.append(K.set_blocks(ip, [[] for _ in range(ip.n_mb)]).seal())
-        hip.upload(S - 1, [keep[0]])
-    hip.reconstruct(list(range(S)), list(range(S)))
-    hip.sync()
-    assert (hip.last_launch()["edge_info_fused"] > 0) == (launch != "dense")     # (k_intra_sparse carries the edge-info role; k_intra does not)
-    out = [hip.read_frame(s, 0) for s in range(len(jobs))]
-    hip.close()
+    with reconstructor(lib, pic0.mb_w, pic0.mb_h, n_streams=S, slots=2, max_pictures=S) as hip:
+        keep = []
+        for s, (pic, ref) in enumerate(jobs):
+            hip.write_frame(s, 1, *ref)
+            hip.upload(s, [pic])
+        if launch == "dense":
+            ip = K.base_picture(pic0.mb_w, pic0.mb_h)
+            ip.desc.slice_type, ip.desc.n_ref = N.SLICE_I, 0
+            ip.rec["mb_type"], ip.rec["intra_modes"] = N.MB_I16x16, 2
+            ip.ref_idx[:] = -1
+            keep.append(K.set_blocks(ip, [[] for _ in range(ip.n_mb)]).seal())
+            hip.upload(S - 1, [keep[0]])
+        hip.reconstruct(list(range(S)), list(range(S)))
+        hip.sync()
+        assert (hip.last_launch()["edge_info_fused"] > 0) == (launch != "dense")     # (k_intra_sparse carries the edge-info role; k_intra does not)
+        out = [hip.read_frame(s, 0) for s in range(len(jobs))]
     return out
 
 

@@ -12,8 +12,9 @@ import os
 
 import pytest
 
-from p264decoder_amd import HipReconstructor, Parser, _native as N
+from p264decoder_amd import Parser, _native as N
 from tests import synth_cases
+from tests.hip_harness import reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -97,16 +98,13 @@ def run_case(lib, case, setenv):
         setenv(k, v)
     kinds, slots = pictures(lib, geometry)
     distinct = [kinds[k] for k in COMPOSITION[comp]][:n]
-    hip = HipReconstructor(distinct[0].mb_w, distinct[0].mb_h, n_streams=n, slots=slots, max_pictures=n, lib=lib)
-    try:
+    with reconstructor(lib, distinct[0].mb_w, distinct[0].mb_h, n_streams=n, slots=slots, max_pictures=n) as hip:
         hip.upload(0, distinct)
         for dst in range(len(distinct), n):
             hip.clone_picture(dst, len(distinct) - 1)
         hip.reconstruct(list(range(n)), list(range(n)))
         hip.sync()
         return hip.last_launch()
-    finally:
-        hip.close()
 
 
 @pytest.fixture(scope="module")

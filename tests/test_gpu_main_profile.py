@@ -8,9 +8,10 @@ import hashlib
 import numpy as np
 import pytest
 
-from p264decoder_amd import Decoder, HipReconstructor, Parser
+from p264decoder_amd import Decoder, Parser
 from tests import synth_cases
 from tests.conftest import frame_sha256
+from tests.hip_harness import compare, reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -24,11 +25,10 @@ def test_main_1080p_ipb_matches_the_oracle_hashes(lib, name):
     parser = Parser(quiet=True, lib=lib)
     pics = parser.parse_stream(data)
     assert len(pics) == len(hashes) and sum(p.desc.slice_type == 1 for p in pics) == 8
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=1, slots=parser.slots, max_pictures=1, lib=lib)
-    for i, p in enumerate(pics):
-        hip.submit(0, p)
-        assert frame_sha256(*hip.read_frame(0, p.desc.dst_slot)) == hashes[i], "picture %d (slice type %d) differs from the oracle" % (i, p.desc.slice_type)
-    hip.close()
+    with reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=1, slots=parser.slots, max_pictures=1) as hip:
+        for i, p in enumerate(pics):
+            hip.submit(0, p)
+            assert frame_sha256(*hip.read_frame(0, p.desc.dst_slot)) == hashes[i], "picture %d (slice type %d) differs from the oracle" % (i, p.desc.slice_type)
 
 
 def test_b_stream_through_the_dropin_api(lib):
@@ -36,12 +36,11 @@ def test_b_stream_through_the_dropin_api(lib):
     data = open(synth_cases.generate(args), "rb").read()
     parser = Parser(quiet=True, lib=lib)
     pics = parser.parse_stream(data)
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=1, slots=parser.slots, max_pictures=1, lib=lib)
-    want = []
-    for p in pics:
-        hip.submit(0, p)
-        want.append([a.copy() for a in hip.read_frame(0, p.desc.dst_slot)])
-    hip.close()
+    with reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=1, slots=parser.slots, max_pictures=1) as hip:
+        want = []
+        for p in pics:
+            hip.submit(0, p)
+            want.append([a.copy() for a in hip.read_frame(0, p.desc.dst_slot)])
     dec = Decoder(lib=lib)
     got = [[np.array(a) for a in pic] for pic in dec.decode_annexb(data)]
     dec.close()
@@ -64,18 +63,16 @@ def test_mixed_slice_types_in_one_batch(lib, oracle):
     mb_w, mb_h = pics[0].mb_w, pics[0].mb_h
     store = oracle_bind.FrameStore(mb_w, mb_h, parser.slots)
     want = [[a.copy() for a in oracle_bind.reconstruct(oracle, store, p)] for p in pics]
-    hip = HipReconstructor(mb_w, mb_h, n_streams=2, slots=parser.slots, max_pictures=len(pics), lib=lib)
-    hip.upload(0, pics)
-    mixed = 0
-    for i in range(len(pics) + 1):
-        ids, streams = [], []
-        if i < len(pics): ids.append(i); streams.append(0)
-        if i >= 1: ids.append(i - 1); streams.append(1)
-        mixed += len({types[k] for k in ids}) > 1
-        hip.reconstruct(ids, streams)
-        for k, s in zip(ids, streams):
-            got = hip.read_frame(s, pics[k].desc.dst_slot)
-            for plane, (a, b) in enumerate(zip(got, want[k])):
-                assert np.array_equal(a, b), "batch %d: picture %d (type %d) of stream %d, plane %d" % (i, k, types[k], s, plane)
-    assert mixed >= 6
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=2, slots=parser.slots, max_pictures=len(pics)) as hip:
+        hip.upload(0, pics)
+        mixed = 0
+        for i in range(len(pics) + 1):
+            ids, streams = [], []
+            if i < len(pics): ids.append(i); streams.append(0)
+            if i >= 1: ids.append(i - 1); streams.append(1)
+            mixed += len({types[k] for k in ids}) > 1
+            hip.reconstruct(ids, streams)
+            for k, s in zip(ids, streams):
+                got = hip.read_frame(s, pics[k].desc.dst_slot)
+                compare(got, want[k], "batch %d: picture %d (type %d) of stream %d" % (i, k, types[k], s))
+        assert mixed >= 6

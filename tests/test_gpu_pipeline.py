@@ -1,14 +1,15 @@
 """The multi-stream pipeline end to end on the MI355X: threaded parse into pinned buffers, asynchronous uploads, one
 batched reconstruction per round.  Streams of different content and length run side by side; the last picture of
 every stream must be the real reference decoder's (committed SHA-256)."""
+import contextlib
 import os
 
-import numpy as np
 import pytest
 
 from p264decoder_amd import Pipeline
 from tests import synth_cases
 from tests.conftest import frame_sha256
+from tests.hip_harness import compare, reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -85,33 +86,32 @@ print("ok")
 def test_parsed_pictures_go_up_in_one_copy(lib):
     """The parser lays a picture's arrays out like an input slot (tests/test_input_layout.py): p264hip_upload queues ONE host ->
     HBM copy per P / I picture; arrays that lie anywhere else (a caller's own: here numpy copies) still take five."""
-    from p264decoder_amd import HipReconstructor, Parser, _native as N
+    from p264decoder_amd import Parser, _native as N
     import ctypes as C
     h = lib.p264parse_open(1)
     data = synth_cases.stream_bytes("cif_ip")
     hip = None
-    want = 0
-    for typ, idc, rbsp in N.split_annexb(lib, data):
-        pic = C.POINTER(N.Picture)()
-        buf = (C.c_uint8 * max(len(rbsp), 1)).from_buffer_copy(rbsp if len(rbsp) else b"\0")
-        if lib.p264parse_nal(h, typ, idc, buf, len(rbsp), C.byref(pic)) != 1:
-            continue
-        d = pic.contents
-        if hip is None:
-            hip = HipReconstructor(d.mb_w, d.mb_h, n_streams=2, slots=lib.p264parse_slots(h), max_pictures=2, lib=lib)
-        assert lib.p264hip_upload(hip.h, 0, pic, 1) == 0
-        want += 1
-        assert lib.p264hip_upload_copies(hip.h) == want
-        hip.reconstruct([0], [0])
-    lib.p264parse_close(h)
-    # the same stream through owned copies of the arrays (recon.ParsedPicture): five copies each, the same pictures
-    pics = Parser(quiet=True, lib=lib).parse_stream(data)
-    for p in pics:
-        hip.upload(1, [p])
-        want += 5
-        assert lib.p264hip_upload_copies(hip.h) == want
-        hip.reconstruct([1], [1])
-    hip.sync()
-    for a, b in zip(hip.read_frame(0, pics[-1].desc.dst_slot), hip.read_frame(1, pics[-1].desc.dst_slot)):
-        assert np.array_equal(a, b)
-    hip.close()
+    with contextlib.ExitStack() as stack:                # (the context's size comes with the first picture)
+        want = 0
+        for typ, idc, rbsp in N.split_annexb(lib, data):
+            pic = C.POINTER(N.Picture)()
+            buf = (C.c_uint8 * max(len(rbsp), 1)).from_buffer_copy(rbsp if len(rbsp) else b"\0")
+            if lib.p264parse_nal(h, typ, idc, buf, len(rbsp), C.byref(pic)) != 1:
+                continue
+            d = pic.contents
+            if hip is None:
+                hip = stack.enter_context(reconstructor(lib, d.mb_w, d.mb_h, n_streams=2, slots=lib.p264parse_slots(h), max_pictures=2))
+            assert lib.p264hip_upload(hip.h, 0, pic, 1) == 0
+            want += 1
+            assert lib.p264hip_upload_copies(hip.h) == want
+            hip.reconstruct([0], [0])
+        lib.p264parse_close(h)
+        # the same stream through owned copies of the arrays (recon.ParsedPicture): five copies each, the same pictures
+        pics = Parser(quiet=True, lib=lib).parse_stream(data)
+        for p in pics:
+            hip.upload(1, [p])
+            want += 5
+            assert lib.p264hip_upload_copies(hip.h) == want
+            hip.reconstruct([1], [1])
+        hip.sync()
+        compare(hip.read_frame(0, pics[-1].desc.dst_slot), hip.read_frame(1, pics[-1].desc.dst_slot), "one copy against five")

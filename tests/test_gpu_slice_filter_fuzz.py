@@ -11,10 +11,9 @@ comparisons cover is asserted on the CPU (tests/test_slice_filter_cpu.py::test_c
 All of it fails on kernels that ignore `flags`: the pictures with deltas come out filtered with the picture's offsets."""
 import pytest
 
-from p264decoder_amd import HipReconstructor
 from tests import slice_filter_fuzz as sff
-from tests.test_gpu_batch_shapes import SHAPES
-from tests.test_gpu_seam_fuzz import compare
+from tests.stream_args import LAUNCH_SHAPES as SHAPES
+from tests.hip_harness import ROADS, compare, load_frames, put, reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -28,14 +27,12 @@ def run_family(lib, oracle, name, road):
     mb_w, mb_h, instance, _ = sff.FAMILIES[name]
     cases, counts = sff.family(oracle, name)
     n = len(cases)
-    hip = HipReconstructor(mb_w, mb_h, n_streams=n, slots=sff.SLOTS, max_pictures=n, lib=lib)
-    try:
+    with reconstructor(lib, mb_w, mb_h, n_streams=n, slots=sff.SLOTS, max_pictures=n) as hip:
         for s, c in enumerate(cases):
-            for slot, f in enumerate(c.refs):
-                hip.write_frame(s, slot, *f)
+            load_frames(hip, s, c.refs)
         if road == "compact":
             for s, c in enumerate(cases):
-                hip.upload_compact(s, c.pic, HipReconstructor.pack_compact(c.pic, lib))
+                put(hip, lib, s, c.pic, "compact")
             hip.reconstruct(list(range(n)), list(range(n)))
             li = hip.last_launch()
             assert li["pictures"] == n
@@ -47,8 +44,6 @@ def run_family(lib, oracle, name, road):
                 hip.submit(s, c.pic)
                 compare(hip.read_frame(s, sff.DST), c.want, "%s stream %d, p264hip_submit, deltas %s" % (name, s, c.mode), c.pic)
         hip.sync()
-    finally:
-        hip.close()
 
 
 @pytest.mark.parametrize("road", ["compact", "submit"])
@@ -73,33 +68,20 @@ def test_every_road_into_a_slot_carries_the_deltas(lib, oracle, name):
     mb_w, mb_h, instance, _ = sff.FAMILIES[name]
     cases, _ = sff.family(oracle, name)
     n = len(cases)
-    hip = HipReconstructor(mb_w, mb_h, n_streams=n, slots=sff.SLOTS, max_pictures=2 * n, lib=lib)
-    try:
+    with reconstructor(lib, mb_w, mb_h, n_streams=n, slots=sff.SLOTS, max_pictures=2 * n) as hip:
         roads = []
         for s, c in enumerate(cases):
-            for slot, f in enumerate(c.refs):
-                hip.write_frame(s, slot, *f)
-            road = ("upload", "packed", "compact", "commit", "clone")[s % 5]
+            load_frames(hip, s, c.refs)
+            road = (ROADS + ("clone",))[s % 5]
             roads.append(road)
-            if road == "upload":
-                hip.upload(s, [c.pic])
-            elif road == "packed":
-                hip.upload_packed(s, c.pic, HipReconstructor.pack(c.pic, lib))
-            elif road == "compact":
-                hip.upload_compact(s, c.pic, HipReconstructor.pack_compact(c.pic, lib))
-            elif road == "commit":
-                blk = HipReconstructor.pack(c.pic, lib)
-                dev, size = hip.input_reserve(s, c.pic)
-                assert size == blk.size and lib.p264hip_copy_to_device(dev, blk.ctypes.data, size) == 0
-                hip.input_commit(s)
-            else:
+            if road == "clone":
                 hip.upload(n + s, [c.pic])
                 hip.clone_picture(s, n + s)
+            else:
+                put(hip, lib, s, c.pic, road)
         assert len(set(roads)) == min(n, 5)
         hip.reconstruct(list(range(n)), list(range(n)))
         check_instance(name, hip.last_launch())
         for s, c in enumerate(cases):
             compare(hip.read_frame(s, sff.DST), c.want, "%s stream %d by %s, deltas %s" % (name, s, roads[s], c.mode), c.pic)
         hip.sync()
-    finally:
-        hip.close()

@@ -3,23 +3,15 @@ road that takes what the parser publishes: HipReconstructor picture by picture, 
 the Pipeline.  Expected pictures: the oracle's unfiltered reconstruction followed by tests/slice_filter_checker.py - the oracle's
 own filter knows one offset pair per picture - compared byte for byte."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from p264decoder_amd import Decoder, HipReconstructor, Pipeline, build as _build
+from p264decoder_amd import Pipeline
+from tests import hip_harness as H
 from tests import slice_streams as ss
 
 pytestmark = pytest.mark.gpu
-
-CLI = os.path.join(os.path.dirname(_build.__file__), "tools", "p264decoder_amd")
-
-
-def same(got, want, what):
-    for plane in range(3):
-        assert np.array_equal(got[plane], want[plane]), "%s plane %d" % (what, plane)
-
 
 @pytest.mark.parametrize("name", list(ss.STREAMS))
 def test_streams_through_the_reconstructor(lib, oracle, tmp_path, name):
@@ -27,17 +19,14 @@ def test_streams_through_the_reconstructor(lib, oracle, tmp_path, name):
     parser, pics = ss.parse(lib, data)
     ss.check_against_dump(pics, dump)
     want = ss.expected_pictures(oracle, pics, parser.slots)
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=1, slots=parser.slots, max_pictures=1, lib=lib)
-    try:
+    with H.reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=1, slots=parser.slots, max_pictures=1) as hip:
         for i, p in enumerate(pics):
             if i % 2:
                 hip.submit(0, p)
             else:
-                hip.upload_compact(0, p, HipReconstructor.pack_compact(p, lib))
+                H.put(hip, lib, 0, p, "compact")
                 hip.reconstruct([0], [0])
-            same(hip.read_frame(0, p.desc.dst_slot), want[i], "%s picture %d (slice type %d)" % (name, i, p.desc.slice_type))
-    finally:
-        hip.close()
+            H.compare(hip.read_frame(0, p.desc.dst_slot), want[i], "%s picture %d (slice type %d)" % (name, i, p.desc.slice_type), p)
 
 
 @pytest.mark.parametrize("name", ["p_cabac_3", "b_cavlc_temporal_4"])
@@ -45,22 +34,14 @@ def test_streams_through_the_dropin_decoder(lib, oracle, tmp_path, name):
     data, _ = ss.make(tmp_path, ss.STREAMS[name])
     parser, pics = ss.parse(lib, data)
     want = ss.expected_pictures(oracle, pics, parser.slots)
-    dec = Decoder(lib=lib)
-    got = list(dec.decode_annexb(data))
-    dec.close()
-    assert len(got) == len(want)
-    for i, (g, w) in enumerate(zip(got, want)):                    # (pictures come out in decode order)
-        same(g, w, "%s picture %d" % (name, i))
+    H.compare_pictures(H.dropin_pictures(lib, data), want, name)      # (pictures come out in decode order)
 
 
 def test_a_stream_through_the_cli(lib, oracle, tmp_path):
     data, _ = ss.make(tmp_path, ss.STREAMS["p_cavlc_4_sub8x8"])
     parser, pics = ss.parse(lib, data)
     want = ss.expected_pictures(oracle, pics, parser.slots)
-    out = tmp_path / "out.yuv"
-    r = subprocess.run([CLI, "-d", str(tmp_path / "s.264"), str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    assert out.read_bytes() == b"".join(np.ascontiguousarray(pl).tobytes() for f in want for pl in f)
+    assert H.cli_bytes(tmp_path, data) == H.planes_bytes(want)
 
 
 def test_streams_through_the_pipeline(lib, oracle, tmp_path):
@@ -83,7 +64,7 @@ def test_streams_through_the_pipeline(lib, oracle, tmp_path):
     st = pipe.run()
     assert st["pictures"] == 11 + 13 + 9 + 13 + 11
     for i, k in enumerate(order):
-        same(pipe.read_frame(i), last[k], "stream %d" % i)
+        H.compare(pipe.read_frame(i), last[k], "stream %d" % i)
     pipe.close()
 
 

@@ -5,9 +5,10 @@ buffers, byte for byte, and == the committed SHA-256 of the real reference decod
 import numpy as np
 import pytest
 
-from p264decoder_amd import Decoder, HipReconstructor, Parser
+from p264decoder_amd import Decoder, Parser
 from tests import oracle_bind, synth_cases
 from tests.conftest import frame_sha256
+from tests.hip_harness import reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -19,21 +20,20 @@ def run_case(lib, oracle, name, with_oracle=True):
     assert len(pics) == len(hashes)
     mb_w, mb_h = pics[0].mb_w, pics[0].mb_h
     store = oracle_bind.FrameStore(mb_w, mb_h, parser.slots) if with_oracle else None
-    hip = HipReconstructor(mb_w, mb_h, n_streams=1, slots=parser.slots, max_pictures=1, lib=lib)
-    for i, p in enumerate(pics):
-        hip.submit(0, p)
-        got = hip.read_frame(0, p.desc.dst_slot)
-        if with_oracle:
-            want = oracle_bind.reconstruct(oracle, store, p)
-            for plane, (a, b) in enumerate(zip(got, want)):
-                if not np.array_equal(a, b):
-                    ys, xs = np.nonzero(a != b)
-                    s = 16 if plane == 0 else 8
-                    pytest.fail("%s picture %d plane %d: %d samples differ from the oracle, first (y=%d,x=%d) MB (%d,%d) type %d" % (
-                        name, i, plane, len(ys), ys[0], xs[0], ys[0] // s, xs[0] // s,
-                        p.mb_records()["mb_type"][(ys[0] // s) * mb_w + xs[0] // s]))
-        assert frame_sha256(*got) == hashes[i], "%s picture %d differs from the reference decoder" % (name, i)
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=1, slots=parser.slots, max_pictures=1) as hip:
+        for i, p in enumerate(pics):
+            hip.submit(0, p)
+            got = hip.read_frame(0, p.desc.dst_slot)
+            if with_oracle:
+                want = oracle_bind.reconstruct(oracle, store, p)
+                for plane, (a, b) in enumerate(zip(got, want)):
+                    if not np.array_equal(a, b):
+                        ys, xs = np.nonzero(a != b)
+                        s = 16 if plane == 0 else 8
+                        pytest.fail("%s picture %d plane %d: %d samples differ from the oracle, first (y=%d,x=%d) MB (%d,%d) type %d" % (
+                            name, i, plane, len(ys), ys[0], xs[0], ys[0] // s, xs[0] // s,
+                            p.mb_records()["mb_type"][(ys[0] // s) * mb_w + xs[0] // s]))
+            assert frame_sha256(*got) == hashes[i], "%s picture %d differs from the reference decoder" % (name, i)
 
 
 @pytest.mark.parametrize("name", [n for n in synth_cases.CASES if n not in synth_cases.BIG])
@@ -81,16 +81,15 @@ def test_2160p_batch_of_streams(lib):
     parser = Parser(quiet=True, lib=lib)
     pics = parser.parse_stream(synth_cases.stream_bytes("uhd_2160p_allp"))
     S = 5
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=S, slots=parser.slots, max_pictures=S, lib=lib)
-    for i, p in enumerate(pics):
-        hip.upload(0, [p])
-        for s in range(1, S):
-            hip.clone_picture(s, 0)
-        hip.reconstruct(list(range(S)), list(range(S)))
-        hip.sync()
-        for s in range(S):
-            assert frame_sha256(*hip.read_frame(s, p.desc.dst_slot)) == hashes[i], "picture %d stream %d differs from the reference decoder" % (i, s)
-    hip.close()
+    with reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=S, slots=parser.slots, max_pictures=S) as hip:
+        for i, p in enumerate(pics):
+            hip.upload(0, [p])
+            for s in range(1, S):
+                hip.clone_picture(s, 0)
+            hip.reconstruct(list(range(S)), list(range(S)))
+            hip.sync()
+            for s in range(S):
+                assert frame_sha256(*hip.read_frame(s, p.desc.dst_slot)) == hashes[i], "picture %d stream %d differs from the reference decoder" % (i, s)
 
 
 def test_bench_shape_batch_against_reference_hashes(lib):
@@ -104,16 +103,15 @@ def test_bench_shape_batch_against_reference_hashes(lib):
     pics = parser.parse_stream(synth_cases.stream_bytes("cfg3_1080p_allp"), limit=4)      # IDR + 3 P pictures
     mb_w, mb_h = pics[0].mb_w, pics[0].mb_h
     S = 2 * 256 + 3
-    hip = HipReconstructor(mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=S, lib=lib)
-    for i, p in enumerate(pics):
-        hip.upload(0, [p])
-        for s in range(1, S):
-            hip.clone_picture(s, 0)
-        hip.reconstruct(list(range(S)), list(range(S)))
-        hip.sync()
-        for s in range(S):
-            assert frame_sha256(*hip.read_frame(s, p.desc.dst_slot)) == hashes[i], "picture %d stream %d differs from the reference decoder" % (i, s)
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=S) as hip:
+        for i, p in enumerate(pics):
+            hip.upload(0, [p])
+            for s in range(1, S):
+                hip.clone_picture(s, 0)
+            hip.reconstruct(list(range(S)), list(range(S)))
+            hip.sync()
+            for s in range(S):
+                assert frame_sha256(*hip.read_frame(s, p.desc.dst_slot)) == hashes[i], "picture %d stream %d differs from the reference decoder" % (i, s)
 
 
 def test_the_bench_s_own_batch_against_reference_hashes(lib):
@@ -126,24 +124,22 @@ def test_the_bench_s_own_batch_against_reference_hashes(lib):
     parser = Parser(quiet=True, lib=lib)
     pics = parser.parse_stream(synth_cases.stream_bytes("cfg3_1080p_allp"), limit=4)      # IDR + 3 P pictures
     mb_w, mb_h = pics[0].mb_w, pics[0].mb_h
-    probe = HipReconstructor(mb_w, mb_h, n_streams=1, slots=parser.slots, max_pictures=1, lib=lib)
-    n_cu = probe.last_launch()["compute_units"]
-    probe.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=1, slots=parser.slots, max_pictures=1) as probe:
+        n_cu = probe.last_launch()["compute_units"]
     S = 8 * n_cu
-    hip = HipReconstructor(mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=S, lib=lib)
-    for i, p in enumerate(pics):
-        hip.upload(0, [p])
-        for s in range(1, S):
-            hip.clone_picture(s, 0)
-        hip.reconstruct(list(range(S)), list(range(S)))
-        hip.sync()
-        li = hip.last_launch()
-        assert li["pictures"] == S and li["deblock_pics_per_wg"] == 8 and li["deblock_rb_log2"] == 2 and li["deblock_wgs"] == n_cu and li["intra_waves"] == 4, li
-        if p.desc.slice_type == 0:                     # P picture: the inter launch and the fused edge-info pass
-            assert li["mc_wgs_per_picture"] == 48 and li["edge_info_fused"] == 1, li
-        for s in range(S):
-            assert frame_sha256(*hip.read_frame(s, p.desc.dst_slot)) == hashes[i], "picture %d stream %d differs from the reference decoder" % (i, s)
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=S, slots=parser.slots, max_pictures=S) as hip:
+        for i, p in enumerate(pics):
+            hip.upload(0, [p])
+            for s in range(1, S):
+                hip.clone_picture(s, 0)
+            hip.reconstruct(list(range(S)), list(range(S)))
+            hip.sync()
+            li = hip.last_launch()
+            assert li["pictures"] == S and li["deblock_pics_per_wg"] == 8 and li["deblock_rb_log2"] == 2 and li["deblock_wgs"] == n_cu and li["intra_waves"] == 4, li
+            if p.desc.slice_type == 0:                     # P picture: the inter launch and the fused edge-info pass
+                assert li["mc_wgs_per_picture"] == 48 and li["edge_info_fused"] == 1, li
+            for s in range(S):
+                assert frame_sha256(*hip.read_frame(s, p.desc.dst_slot)) == hashes[i], "picture %d stream %d differs from the reference decoder" % (i, s)
 
 
 def test_config3_through_dropin_api(lib):

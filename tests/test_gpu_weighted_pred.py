@@ -8,13 +8,13 @@ boundary-strength test of weighted P pictures.
 - Streams: a table of weight 2^denom and offset 0 changes nothing, so a --wp-identity stream (every phase class, residual,
   sub-8x8, slices, CABAC B pictures) decodes to the frames of the unweighted stream from the same seed.
 """
-import subprocess
 
 import numpy as np
 import pytest
 
 from p264decoder_amd import HipReconstructor, Parser, _native as N
 from tests import seam_fuzz, synth_cases
+from tests.hip_harness import compare, cli_bytes, planes_bytes, reconstructor
 
 pytestmark = pytest.mark.gpu
 
@@ -130,26 +130,23 @@ def expected(pic, frames):
 def test_known_answer_pictures_mixed_batches(lib, batch):
     rng = np.random.default_rng(4100 + batch)
     mb_w, mb_h = (5, 3) if batch < 256 else (2, 2)
-    hip = HipReconstructor(mb_w, mb_h, n_streams=batch, slots=REFS + 1, max_pictures=batch, lib=lib)
-    shapes = [(mb_h * 16, mb_w * 16), (mb_h * 8, mb_w * 8), (mb_h * 8, mb_w * 8)]
-    pics, frames = [], []
-    for s in range(batch):
-        fr = [[rng.integers(0, 256, sh, dtype=np.uint8) for sh in shapes] for _ in range(REFS)]
-        for i, f in enumerate(fr):
-            hip.write_frame(s, i, *f)
-        is_b, weighted = bool(s & 2), (s % 3 != 1) if batch > 1 else True
-        pics.append(build(rng, mb_w, mb_h, is_b, weighted))
-        frames.append(fr)
-    hip.upload(0, pics)
-    hip.reconstruct(list(range(batch)), list(range(batch)))
-    hip.sync()
-    for s in range(batch):
-        got = hip.read_frame(s, REFS)
-        want = expected(pics[s], frames[s])
-        for c in range(3):
-            assert np.array_equal(got[c], want[c]), "stream %d (%s, weighted %d) plane %d" % (
-                s, "B" if pics[s].desc.slice_type == N.SLICE_B else "P", pics[s].desc.explicit_wp, c)
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=batch, slots=REFS + 1, max_pictures=batch) as hip:
+        shapes = [(mb_h * 16, mb_w * 16), (mb_h * 8, mb_w * 8), (mb_h * 8, mb_w * 8)]
+        pics, frames = [], []
+        for s in range(batch):
+            fr = [[rng.integers(0, 256, sh, dtype=np.uint8) for sh in shapes] for _ in range(REFS)]
+            for i, f in enumerate(fr):
+                hip.write_frame(s, i, *f)
+            is_b, weighted = bool(s & 2), (s % 3 != 1) if batch > 1 else True
+            pics.append(build(rng, mb_w, mb_h, is_b, weighted))
+            frames.append(fr)
+        hip.upload(0, pics)
+        hip.reconstruct(list(range(batch)), list(range(batch)))
+        hip.sync()
+        for s in range(batch):
+            got = hip.read_frame(s, REFS)
+            want = expected(pics[s], frames[s])
+            compare(got, want, "stream %d (%s, weighted %d)" % (s, "B" if pics[s].desc.slice_type == N.SLICE_B else "P", pics[s].desc.explicit_wp))
 
 
 def decode(lib, data):
@@ -157,19 +154,12 @@ def decode(lib, data):
     pics = parser.parse_stream(data)
     slots = parser.slots
     parser.close()
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=1, slots=slots, max_pictures=1, lib=lib)
-    out = []
-    for p in pics:
-        hip.submit(0, p)
-        out.append([a.copy() for a in hip.read_frame(0, p.desc.dst_slot)])
-    hip.close()
+    with reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=1, slots=slots, max_pictures=1) as hip:
+        out = []
+        for p in pics:
+            hip.submit(0, p)
+            out.append([a.copy() for a in hip.read_frame(0, p.desc.dst_slot)])
     return pics, out, slots
-
-
-def stream(tmp_path, args, name):
-    out = str(tmp_path / (name + ".264"))
-    subprocess.run([synth_cases.TOOL, out] + args.split(), check=True)
-    return open(out, "rb").read()
 
 
 @pytest.mark.parametrize("args", [
@@ -179,29 +169,26 @@ def stream(tmp_path, args, name):
 ])
 def test_identity_weights_decode_like_the_unweighted_stream(lib, tmp_path, args):
     base = args.replace(" --wp-bi", "").replace(" --wp", "")
-    pa, plain, _ = decode(lib, stream(tmp_path, base, "plain"))
-    pb, ident, _ = decode(lib, stream(tmp_path, args + " --wp-identity", "ident"))
+    pa, plain, _ = decode(lib, synth_cases.write_stream(tmp_path, base, "plain"))
+    pb, ident, _ = decode(lib, synth_cases.write_stream(tmp_path, args + " --wp-identity", "ident"))
     assert any(p.desc.explicit_wp for p in pb)
     assert len(plain) == len(ident)
     for k, (a, b) in enumerate(zip(plain, ident)):
-        for c in range(3):
-            assert np.array_equal(a[c], b[c]), "picture %d plane %d" % (k, c)
+        compare(a, b, "picture %d" % k)
 
 
 def test_weighted_streams_decode_the_same_on_every_road(lib, tmp_path):
     """one weighted stream (duplicated list entries, loop filter on): per picture, upload vs the compact link format"""
-    data = stream(tmp_path, "--mbw 8 --mbh 6 --frames 8 --gop 0 --seed 84 --refs 2 --wp --wp-dup --coded 25 --maxlevel 8", "dup")
+    data = synth_cases.write_stream(tmp_path, "--mbw 8 --mbh 6 --frames 8 --gop 0 --seed 84 --refs 2 --wp --wp-dup --coded 25 --maxlevel 8", "dup")
     pics, frames, slots = decode(lib, data)
     assert any(p.desc.explicit_wp and p.desc.n_ref > 1 and p.desc.ref_slot[0] == p.desc.ref_slot[1] for p in pics)
-    hip = HipReconstructor(pics[0].mb_w, pics[0].mb_h, n_streams=1, slots=slots, max_pictures=1, lib=lib)
-    for k, p in enumerate(pics):
-        compact = HipReconstructor.pack_compact(p, lib)
-        hip.upload_compact(0, p, compact)
-        hip.reconstruct([0], [0])
-        got = hip.read_frame(0, p.desc.dst_slot)
-        for c in range(3):
-            assert np.array_equal(got[c], frames[k][c]), "picture %d plane %d" % (k, c)
-    hip.close()
+    with reconstructor(lib, pics[0].mb_w, pics[0].mb_h, n_streams=1, slots=slots, max_pictures=1) as hip:
+        for k, p in enumerate(pics):
+            compact = HipReconstructor.pack_compact(p, lib)
+            hip.upload_compact(0, p, compact)
+            hip.reconstruct([0], [0])
+            got = hip.read_frame(0, p.desc.dst_slot)
+            compare(got, frames[k], "picture %d" % k)
 
 
 def test_duplicated_entries_loop_filter_against_oracle(lib, oracle, tmp_path):
@@ -209,7 +196,7 @@ def test_duplicated_entries_loop_filter_against_oracle(lib, oracle, tmp_path):
     filter must compare pictures (8.7.2.1), as the CPU oracle does on the picture's own indices - both agree, picture by picture,
     loop filter on."""
     from tests import oracle_bind
-    data = stream(tmp_path, "--mbw 8 --mbh 6 --frames 8 --gop 0 --seed 85 --refs 2 --wp --wp-dup --wp-identity --coded 25 --maxlevel 8", "dupid")
+    data = synth_cases.write_stream(tmp_path, "--mbw 8 --mbh 6 --frames 8 --gop 0 --seed 85 --refs 2 --wp --wp-dup --wp-identity --coded 25 --maxlevel 8", "dupid")
     pics, frames, slots = decode(lib, data)
     store = oracle_bind.FrameStore(pics[0].mb_w, pics[0].mb_h, slots)
     changed = 0
@@ -220,25 +207,17 @@ def test_duplicated_entries_loop_filter_against_oracle(lib, oracle, tmp_path):
                 first = [d.ref_slot[j] for j in range(d.n_ref)].index(d.ref_slot[r])
                 changed += first != r
         want = oracle_bind.reconstruct(oracle, store, p)
-        for c in range(3):
-            assert np.array_equal(frames[k][c], want[c]), "picture %d plane %d" % (k, c)
+        compare(frames[k], want, "picture %d" % k)
     assert changed > 0                                   # the stream does use the second index of a duplicated frame
 
 
 def test_cli_decodes_a_weighted_stream_like_the_python_path(lib, tmp_path):
     """the drop-in API (p264_decoder_decode) behind the command-line decoder: the same frames"""
-    from p264decoder_amd import build as _build
-    import os
-    cli = os.path.join(os.path.dirname(_build.__file__), "tools", "p264decoder_amd")
     args = "--mbw 8 --mbh 6 --frames 8 --gop 0 --seed 86 --refs 2 --sub8x8 --coded 25 --maxlevel 8 --wp --wp-dup"
-    data = stream(tmp_path, args, "cli")
+    data = synth_cases.write_stream(tmp_path, args, "cli")
     pics, frames, _ = decode(lib, data)
     assert all(p.desc.explicit_wp for p in pics[1:])
-    out = tmp_path / "rec.yuv"
-    r = subprocess.run([cli, "-d", str(tmp_path / "cli.264"), str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    want = b"".join(b"".join(np.ascontiguousarray(a).tobytes() for a in f) for f in frames)
-    assert out.read_bytes() == want
+    assert cli_bytes(tmp_path, data) == planes_bytes(frames)
 
 
 @pytest.mark.parametrize("args", [
@@ -255,11 +234,10 @@ def test_weighted_streams_against_the_checker(lib, oracle, tmp_path, args):
     """HIP against tests/wp_checker.py (oracle_mc_* + the 8.4.2.3.2 formula, then the oracle's residual and loop filter),
     picture by picture"""
     from tests import wp_checker
-    data = stream(tmp_path, args, "chk")
+    data = synth_cases.write_stream(tmp_path, args, "chk")
     pics, frames, slots = decode(lib, data)
     assert sum(p.desc.explicit_wp for p in pics) >= 3
     chk = wp_checker.WeightedChecker(oracle, pics[0].mb_w, pics[0].mb_h, slots)
     for k, p in enumerate(pics):
         want = chk.reconstruct(p)
-        for c in range(3):
-            assert np.array_equal(frames[k][c], want[c]), "picture %d (type %d, weighted %d) plane %d" % (k, p.desc.slice_type, p.desc.explicit_wp, c)
+        compare(frames[k], want, "picture %d (type %d, weighted %d)" % (k, p.desc.slice_type, p.desc.explicit_wp))

@@ -8,31 +8,12 @@ picture also goes through the packed and the compact upload, which must give the
 import numpy as np
 import pytest
 
-from p264decoder_amd import HipReconstructor, _native as N
+from p264decoder_amd import _native as N
 from tests import seam_fuzz, wp_checker
-from tests.test_gpu_seam_fuzz import compare
+from tests.hip_harness import ROADS, compare, reconstructor, through_roads
+from tests.wp_seam_stim import CONFIGS, config_inputs
 
 pytestmark = pytest.mark.gpu
-
-CONFIGS = [
-    # name, mb_w, mb_h, pictures, make_picture keywords.  Picture 2 is an I picture (the store moves on, no table).
-    ("p_sub4x4_3refs_dup", 8, 6, 6, dict(n_ref=3, slots=3, level_style="wrap", qp_mode="random", intra_share=0.3, slices=3,
-                                          slice_idcs=[0, 1, 2], explicit_wp="legal")),
-    ("b_sub8x8_legal", 9, 7, 6, dict(n_ref=2, n_ref_l1=2, slots=4, b_picture=True, level_style="small", qp_mode="random", explicit_wp="legal")),
-    ("b_wide_smooth", 10, 6, 6, dict(n_ref=2, n_ref_l1=2, slots=4, b_picture=True, level_style="small", qp_mode="two", mv_range=12, explicit_wp="wide")),
-    ("p_far", 6, 5, 5, dict(n_ref=2, slots=3, level_style="small", qp_mode=30, mv_range=500, explicit_wp="legal")),
-    ("b_far", 7, 6, 5, dict(n_ref=2, n_ref_l1=2, slots=4, b_picture=True, level_style="mixed", qp_mode="random", mv_range=500, slices=2, explicit_wp="legal")),
-    ("b_dup_lists", 8, 6, 5, dict(n_ref=3, n_ref_l1=3, slots=4, b_picture=True, level_style="small", qp_mode="random", dup_refs=True, explicit_wp="legal")),
-    ("p_single_column", 1, 9, 5, dict(n_ref=2, slots=3, level_style="mixed", qp_mode="random", slices=4, explicit_wp="legal")),
-    ("b_single_row", 11, 1, 5, dict(n_ref=2, n_ref_l1=2, slots=4, b_picture=True, level_style="mixed", qp_mode="random", slices=3, explicit_wp="wide")),
-    ("b_wide_picture", 67, 3, 5, dict(n_ref=2, n_ref_l1=2, slots=4, b_picture=True, level_style="small", qp_mode="random", explicit_wp="legal")),
-    # indices n_ref .. 15 in both lists: entry 0 for the prediction, both kinds of weights and the loop filter
-    ("past_list_p", 8, 6, 5, dict(n_ref=2, slots=4, level_style="small", qp_mode="random", mv_range=12, past_list=0.3)),
-    ("past_list_b", 8, 6, 5, dict(n_ref=3, n_ref_l1=2, slots=4, b_picture=True, level_style="small", qp_mode="random", mv_range=12, past_list=0.3)),
-    ("past_list_wp_p", 8, 6, 5, dict(n_ref=3, slots=4, level_style="small", qp_mode="random", mv_range=12, past_list=0.3, explicit_wp="legal")),
-    ("past_list_wp_b", 8, 6, 5, dict(n_ref=3, n_ref_l1=2, slots=4, b_picture=True, level_style="small", qp_mode="random", mv_range=12, past_list=0.3, explicit_wp="legal")),
-]
-FORCED_DENOMS = {0: (0, 7), 1: (7, 0)}       # picture -> (luma, chroma): both ends of the denominator in every config
 
 
 def entry(r, n):
@@ -81,48 +62,23 @@ def new_seen():
                 clip_low=0, clip_high=0, bi_past_limit=0)
 
 
-def three_roads(hip, pic, want, what, lib):
-    """the picture through p264hip_upload, p264hip_upload_packed and p264hip_upload_compact into input slot 0: the same bytes"""
-    dst = pic.desc.dst_slot
-    blank = [np.zeros_like(a) for a in want]
-    blocks = [HipReconstructor.pack(pic, lib), HipReconstructor.pack_compact(pic, lib)]    # (referenced until the sync below)
-    roads = [("upload", lambda: hip.upload(0, [pic]))]
-    if pic.desc.explicit_wp:
-        roads += [("packed", lambda: hip.upload_packed(0, pic, blocks[0])), ("compact", lambda: hip.upload_compact(0, pic, blocks[1]))]
-    for road, put in roads:
-        hip.write_frame(0, dst, *blank)           # (a road that wrote nothing cannot pass on the road before's output)
-        put()
-        hip.reconstruct([0], [0])
-        compare(hip.read_frame(0, dst), want, "%s (%s)" % (what, road), pic)
-    hip.sync()
-
-
-def config_inputs(name, mb_w, mb_h, n_pics, kw):
-    """a config's starting frames (one per store slot), then its pictures - drawn lazily, in this order, from the config's seed"""
-    rng = np.random.default_rng(sum(map(ord, name)) * 7727)
-    kind = "smooth" if ("smooth" in name or "past_list" in name) else "noise"
-    yield [seam_fuzz.random_frame(rng, mb_w, mb_h, kind) for _ in range(kw["slots"])]
-    for i in range(n_pics):
-        yield seam_fuzz.make_picture(rng, mb_w, mb_h, p_picture=(i != 2), dst_slot=i % kw["slots"], wp_denoms=FORCED_DENOMS.get(i), **kw)
-
-
 @pytest.mark.parametrize("name,mb_w,mb_h,n_pics,kw", CONFIGS, ids=[c[0] for c in CONFIGS])
 def test_wp_seam_fuzz(lib, oracle, name, mb_w, mb_h, n_pics, kw):
     slots = kw["slots"]
     chk = wp_checker.WeightedChecker(oracle, mb_w, mb_h, slots)
-    hip = HipReconstructor(mb_w, mb_h, n_streams=1, slots=slots, max_pictures=1, lib=lib)
-    inputs = config_inputs(name, mb_w, mb_h, n_pics, kw)
-    for s, f in enumerate(next(inputs)):
-        for dst, src in zip(chk.store[s], f):
-            dst[:] = src
-        hip.write_frame(0, s, *f)
-    seen = new_seen()
-    for i, pic in enumerate(inputs):
-        stats = {}
-        want = [a.copy() for a in chk.reconstruct(pic, stats)]
-        three_roads(hip, pic, want, "%s picture %d" % (name, i), lib)
-        note(seen, pic, stats)
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=1, slots=slots, max_pictures=1) as hip:
+        inputs = config_inputs(name, mb_w, mb_h, n_pics, kw)
+        for s, f in enumerate(next(inputs)):
+            for dst, src in zip(chk.store[s], f):
+                dst[:] = src
+            hip.write_frame(0, s, *f)
+        seen = new_seen()
+        for i, pic in enumerate(inputs):
+            stats = {}
+            want = [a.copy() for a in chk.reconstruct(pic, stats)]
+            # (a weighted picture also through the packed and the compact upload: the same bytes)
+            through_roads(hip, lib, pic, want, "%s picture %d" % (name, i), ROADS[:3] if pic.desc.explicit_wp else ROADS[:1])
+            note(seen, pic, stats)
     big = mb_w * mb_h >= 30
     if kw.get("past_list"):
         assert seen["past_list"] > 20, "hardly any index past its list"
@@ -146,21 +102,20 @@ def test_wp_seam_fuzz_1080p_batch(lib, oracle):
     picture decodes through the weighted instances because of its neighbours and must still be the oracle's"""
     rng = np.random.default_rng(20261016)
     mb_w, mb_h, S, slots = 120, 68, 3, 3
-    hip = HipReconstructor(mb_w, mb_h, n_streams=S, slots=slots, max_pictures=S, lib=lib)
-    chks = [wp_checker.WeightedChecker(oracle, mb_w, mb_h, slots) for _ in range(S)]
-    for s in range(S):
-        for slot in range(slots):
-            f = seam_fuzz.random_frame(rng, mb_w, mb_h, "smooth" if slot else "noise")
-            for dst, src in zip(chks[s].store[slot], f):
-                dst[:] = src
-            hip.write_frame(s, slot, *f)
-    kinds = [dict(explicit_wp="legal", intra_share=0.05, wp_denoms=(6, 1)),
-             dict(explicit_wp="legal", intra_share=0.05, b_picture=True, n_ref_l1=2, wp_denoms=(7, 5)),
-             dict(intra_share=0.05)]
-    pics = [seam_fuzz.make_picture(rng, mb_w, mb_h, dst_slot=2, n_ref=2, slots=slots, level_style="small", qp_mode="random", **k) for k in kinds]
-    hip.upload(0, pics)
-    hip.reconstruct(list(range(S)), list(range(S)))
-    assert hip.last_launch()["edge_info_fused"] == 0
-    for s in range(S):
-        compare(hip.read_frame(s, 2), chks[s].reconstruct(pics[s]), "1080p stream %d" % s, pics[s])
-    hip.close()
+    with reconstructor(lib, mb_w, mb_h, n_streams=S, slots=slots, max_pictures=S) as hip:
+        chks = [wp_checker.WeightedChecker(oracle, mb_w, mb_h, slots) for _ in range(S)]
+        for s in range(S):
+            for slot in range(slots):
+                f = seam_fuzz.random_frame(rng, mb_w, mb_h, "smooth" if slot else "noise")
+                for dst, src in zip(chks[s].store[slot], f):
+                    dst[:] = src
+                hip.write_frame(s, slot, *f)
+        kinds = [dict(explicit_wp="legal", intra_share=0.05, wp_denoms=(6, 1)),
+                 dict(explicit_wp="legal", intra_share=0.05, b_picture=True, n_ref_l1=2, wp_denoms=(7, 5)),
+                 dict(intra_share=0.05)]
+        pics = [seam_fuzz.make_picture(rng, mb_w, mb_h, dst_slot=2, n_ref=2, slots=slots, level_style="small", qp_mode="random", **k) for k in kinds]
+        hip.upload(0, pics)
+        hip.reconstruct(list(range(S)), list(range(S)))
+        assert hip.last_launch()["edge_info_fused"] == 0
+        for s in range(S):
+            compare(hip.read_frame(s, 2), chks[s].reconstruct(pics[s]), "1080p stream %d" % s, pics[s])

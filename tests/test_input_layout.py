@@ -7,13 +7,11 @@ import pytest
 
 from p264decoder_amd import HipReconstructor, Parser, _native as N
 from tests import synth_cases
+from tests.stream_args import B_CIF
 
 
 def _pictures(case, lib, limit=3):
     return Parser(quiet=True, lib=lib).parse_stream(synth_cases.stream_bytes(case), limit=limit)
-
-
-B_CIF = "--mbw 22 --mbh 18 --frames 7 --seed 5 --refs 2 --bframes 2 --implicit --d8inf --coded 8 --maxlevel 8"      # I P B B P B B
 
 
 @pytest.mark.parametrize("case", ["cif_ip", B_CIF])

@@ -5,8 +5,8 @@ import numpy as np
 import pytest
 
 from tests import pcm_checker, seam_fuzz
-from tests import test_gpu_intra_avail as G
-from tests.test_intra_checker_cpu import differences
+from tests import intra_avail_stim as G
+from tests.hip_harness import first_difference
 
 
 @pytest.mark.parametrize("with_i", [False, True], ids=["p_b_only", "with_i_picture"])
@@ -19,8 +19,8 @@ def test_oracle_equals_the_intra_checker(oracle, name, with_i):
         for slot in range(G.DST):
             for dst, src in zip(ref.store[slot], f):
                 dst[:] = src
-        n, at = differences(ref.reconstruct(pic), want)
-        assert n == 0, "%s stream %d: %d samples differ, first in plane %d at (y=%d, x=%d)" % ((name, s, n) + at)
+        d = first_difference(ref.reconstruct(pic), want, "%s stream %d" % (name, s), pic)
+        assert d is None, d
     if "directed" in name:
         G.check_directed(name, with_i, batch, log)
 

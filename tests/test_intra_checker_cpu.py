@@ -7,19 +7,15 @@ fail: the SLICED streams with 3395 / 5315 / 2285 differing samples (the first in
 the loop filter changes above such a macroblock; picture 0, plane 0, (y=46, x=32); picture 4, plane 1, (y=39, x=57)), the weighted
 three-slice B stream with 720 (picture 0, plane 2, (y=15, x=16)), the seam fuzz with 2, 3, 4 slices with 45 / 2819 / 353; the
 I_PCM three-slice stream, the two-slice B stream and the CABAC two-slice B stream hold no such macroblock with a DC mode."""
-import subprocess
-
 import numpy as np
 import pytest
 
-from p264decoder_amd import Parser, _native as N
+from p264decoder_amd import _native as N
 from tests import intra_checker as ic
 from tests import pcm_checker, pcm_fuzz, seam_fuzz, synth_cases
-from tests.test_bslices import STREAMS as B_STREAMS
-from tests.test_cabac_streams import STREAMS as CABAC_STREAMS
-from tests.test_ipcm_cpu import STREAMS as IPCM_STREAMS
-from tests.test_multiref import SLICED
-from tests.test_weighted_pred_cpu import STREAMS as WP_STREAMS
+from tests.hip_harness import decode_both, differences
+from tests.stream_args import B_STREAMS, CABAC_STREAMS, IPCM_STREAMS, SLICED, WP_STREAMS
+from tests.synth_cases import write_stream as synth
 
 L4, T4, TR4, C4 = [10, 20, 30, 40], [50, 60, 70, 80], [90, 100, 110, 120], 45
 T8 = T4 + TR4
@@ -113,43 +109,6 @@ def test_a_mode_that_needs_a_missing_neighbour_is_an_error(what, fn, mode, left,
 
 
 # ---- against the oracle on streams ------------------------------------------------------------------------------------------
-def synth(tmp_path, args):
-    synth_cases.ensure_tool()
-    stream = str(tmp_path / "s.264")
-    subprocess.run([synth_cases.TOOL, stream] + args.split(), check=True)
-    return open(stream, "rb").read()
-
-
-def differences(got, want):
-    """(samples that differ, (plane, y, x) of the first)"""
-    n, first = 0, None
-    for plane, (a, b) in enumerate(zip(got, want)):
-        ys, xs = np.nonzero(a != b)
-        n += len(ys)
-        if len(ys) and first is None:
-            first = (plane, int(ys[0]), int(xs[0]))
-    return n, first
-
-
-def decode_both(oracle, lib, data, limit=None):
-    """every picture through the checker and through the oracle (with pcm_checker's composition for I_PCM and explicit weights:
-    oracle_reconstruct itself without them), each with its own frame store; returns the parsed pictures, the number of samples
-    that differ and a description of the first"""
-    parser = Parser(quiet=True, lib=lib)
-    pics = parser.parse_stream(data, limit=limit) if limit else parser.parse_stream(data)
-    chk = ic.IntraChecker(oracle, pics[0].mb_w, pics[0].mb_h, parser.slots)
-    ref = pcm_checker.PcmChecker(oracle, pics[0].mb_w, pics[0].mb_h, parser.slots)
-    total, first = 0, None
-    for i, p in enumerate(pics):
-        n, at = differences(chk.reconstruct(p), ref.reconstruct(p))
-        total += n
-        if n and first is None:
-            s = 16 if at[0] == 0 else 8
-            m = (at[1] // s) * p.mb_w + at[2] // s
-            first = "picture %d plane %d (y=%d, x=%d), macroblock %d avail %d" % (i, at[0], at[1], at[2], m, p.mb_records()["avail"][m])
-    return pics, total, first, chk
-
-
 def n_intra(pics):
     return sum(int((p.mb_records()["mb_type"] <= N.MB_I16x16).sum()) for p in pics)
 
@@ -196,14 +155,14 @@ def test_multi_slice_streams_equal_the_oracle(oracle, lib, tmp_path, what, args)
     pics, n, first, chk = decode_both(oracle, lib, synth(tmp_path, args))
     if what.startswith("sliced") or what == "weighted_b_slices3":
         assert len(chk.dc_log) > 0, "no macroblock with LEFT and TOP and without TOPLEFT predicts DC"
-    assert n == 0, "%d samples differ, first: %s" % (n, first)
+    assert n == 0, first
 
 
 @pytest.mark.parametrize("slices", [2, 3, 4])
 def test_multi_slice_seam_fuzz_equals_the_oracle(oracle, slices):
     rng = np.random.default_rng(9000 + slices)
     mb_w, mb_h, slots = 8, 6, 3
-    total, first, quirk = 0, None, 0
+    bad, quirk = [], 0
     for k in range(12):
         chk = ic.IntraChecker(oracle, mb_w, mb_h, slots)
         ref = pcm_checker.PcmChecker(oracle, mb_w, mb_h, slots)
@@ -215,10 +174,7 @@ def test_multi_slice_seam_fuzz_equals_the_oracle(oracle, slices):
                                      slots=slots, dst_slot=2, level_style="mixed")
         if k % 3 == 2:
             pcm_fuzz.to_ipcm(rng, pic, 0.15)
-        n, at = differences(chk.reconstruct(pic), ref.reconstruct(pic))
-        total += n
-        if n and first is None:
-            first = "picture %d plane %d (y=%d, x=%d)" % ((k,) + at)
+        bad += differences(chk.reconstruct(pic), ref.reconstruct(pic), "picture %d" % k, pic)
         quirk += len(chk.dc_log)
     assert quirk > 0, "no macroblock with LEFT and TOP and without TOPLEFT predicts DC"
-    assert total == 0, "%d samples differ, first: %s" % (total, first)
+    assert not bad, "%d pictures differ, first: %s" % (len(bad), bad[0])

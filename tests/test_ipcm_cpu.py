@@ -3,7 +3,6 @@ checker's own check, the parser against the stream writer's record and against i
 streams contain, refusals, and the seam formats.  Every parser test fails without the feature (the parser refused the type)."""
 import ctypes as C
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,30 +10,11 @@ import pytest
 from p264decoder_amd import HipReconstructor, Parser, _native as N
 from p264decoder_amd.recon import P264Error
 from tests import oracle_bind, pcm_checker, pcm_fuzz, seam_fuzz, synth_cases
+from tests.stream_args import IPCM_STREAMS as STREAMS
 
 IPCM_MASK = 0x00000fff
 EINVAL = -1                                              # P264HIP_EINVAL
-# the streams of the differential parse (each also with --cabac) and, CIF-sized, of tests/test_gpu_ipcm.py
-STREAMS = {
-    "i_only": "--mbw 9 --mbh 7 --frames 4 --intra-only --seed 301 --coded 30 --ipcm 20",
-    "ip_baseline": "--mbw 9 --mbh 7 --frames 8 --gop 4 --seed 302 --coded 25 --maxlevel 12 --ipcm 15",
-    "b_spatial": "--mbw 8 --mbh 6 --frames 13 --seed 303 --refs 2 --bframes 2 --sub8x8 --implicit --coded 12 --maxlevel 8 --ipcm 12",
-    "b_temporal": "--mbw 7 --mbh 6 --frames 13 --seed 304 --refs 3 --bframes 2 --temporal --d8inf --coded 10 --maxlevel 8 --ipcm 12",
-    "refs2_sub8x8": "--mbw 8 --mbh 6 --frames 8 --gop 0 --seed 305 --refs 2 --sub8x8 --coded 20 --maxlevel 12 --ipcm 20",
-    "qp_delta": "--mbw 9 --mbh 7 --frames 8 --gop 4 --seed 306 --qp 28 --qp-delta 6 --coded 35 --maxlevel 8 --ipcm 25",
-    "slices3": "--mbw 8 --mbh 6 --frames 8 --gop 4 --seed 307 --slices 3 --coded 20 --maxlevel 12 --ipcm 40",
-    "all_ipcm": "--mbw 6 --mbh 5 --frames 6 --gop 3 --seed 308 --slices 3 --ipcm 100",
-    "style_flat": "--mbw 8 --mbh 6 --frames 6 --gop 3 --seed 309 --coded 20 --ipcm 30 --ipcm-style flat",
-    "style_edge": "--mbw 8 --mbh 6 --frames 6 --gop 3 --seed 310 --coded 20 --ipcm 30 --ipcm-style edge",
-}
 FIELDS = ("mb", "mv", "ref_idx", "i4modes", "coefs")
-
-
-def make(tmp_path, args, tag):
-    synth_cases.ensure_tool()
-    stream = str(tmp_path / ("%s.264" % tag))
-    subprocess.run([synth_cases.TOOL, stream] + args.split(), check=True)
-    return open(stream, "rb").read()
 
 
 def read_dump(path):
@@ -102,7 +82,7 @@ def test_road_model_of_the_sparse_path():
 @pytest.mark.parametrize("cabac", [False, True])
 def test_parser_finds_the_writers_samples(lib, tmp_path, name, cabac):
     dump = tmp_path / "pcm.bin"
-    data = make(tmp_path, STREAMS[name] + " --dump-pcm %s" % dump + (" --cabac" if cabac else ""), "s")
+    data = synth_cases.write_stream(tmp_path, STREAMS[name] + " --dump-pcm %s" % dump + (" --cabac" if cabac else ""), "s")
     pics = Parser(quiet=True, lib=lib).parse_stream(data)
     want = read_dump(str(dump))
     assert len(pics) == len(want) and sum(len(w) for w in want) > 20
@@ -121,8 +101,8 @@ def test_parser_finds_the_writers_samples(lib, tmp_path, name, cabac):
 @pytest.mark.parametrize("name", list(STREAMS))
 def test_cavlc_and_cabac_forms_of_ipcm_streams_parse_to_the_same_pictures(lib, tmp_path, name):
     args = STREAMS[name]
-    a = Parser(quiet=True, strict=True, lib=lib).parse_stream(make(tmp_path, args, "cavlc"))
-    c = Parser(quiet=True, lib=lib).parse_stream(make(tmp_path, args + " --cabac", "cabac"))
+    a = Parser(quiet=True, strict=True, lib=lib).parse_stream(synth_cases.write_stream(tmp_path, args, "cavlc"))
+    c = Parser(quiet=True, lib=lib).parse_stream(synth_cases.write_stream(tmp_path, args + " --cabac", "cabac"))
     assert len(a) == len(c) == int(args.split("--frames ")[1].split()[0])
     n_pcm = 0
     for i, (p, q) in enumerate(zip(a, c)):
@@ -140,7 +120,7 @@ def test_cavlc_and_cabac_forms_of_ipcm_streams_parse_to_the_same_pictures(lib, t
 def test_the_qp_chain_passes_through_an_ipcm_macroblock(lib, tmp_path):
     """no mb_qp_delta is coded for I_PCM: a macroblock without residual syntax right behind one carries the QP the chain had in
     front of it (conformant chain), and the I_PCM record itself says 0"""
-    pics = Parser(quiet=True, strict=True, lib=lib).parse_stream(make(tmp_path, STREAMS["qp_delta"], "q"))
+    pics = Parser(quiet=True, strict=True, lib=lib).parse_stream(synth_cases.write_stream(tmp_path, STREAMS["qp_delta"], "q"))
     seen = 0
     for p in pics:
         r = p.mb_records()
@@ -155,9 +135,9 @@ def test_the_qp_chain_passes_through_an_ipcm_macroblock(lib, tmp_path):
 def test_what_the_streams_contain(lib, tmp_path):
     kinds, corners, nc16, epb = set(), set(), 0, 0
     for name in ("ip_baseline", "slices3", "style_flat", "i_only", "refs2_sub8x8"):
-        data = make(tmp_path, STREAMS[name], "c")
+        data = synth_cases.write_stream(tmp_path, STREAMS[name], "c")
         if name == "style_flat":
-            plain = make(tmp_path, STREAMS[name].replace("--ipcm-style flat", ""), "p")
+            plain = synth_cases.write_stream(tmp_path, STREAMS[name].replace("--ipcm-style flat", ""), "p")
             epb = data.count(b"\x00\x00\x03") - plain.count(b"\x00\x00\x03")
         for p in Parser(quiet=True, lib=lib).parse_stream(data):
             kinds |= pcm_fuzz.neighbour_kinds(p)
@@ -178,7 +158,7 @@ def test_what_the_streams_contain(lib, tmp_path):
 
 def test_a_picture_of_nothing_but_ipcm_outgrows_the_levels_section(lib, tmp_path):
     """twelve blocks per macroblock against a section of eight: coef_reserve takes it"""
-    pics = Parser(quiet=True, lib=lib).parse_stream(make(tmp_path, "--mbw 20 --mbh 15 --frames 3 --gop 0 --seed 311 --ipcm 100", "big"))
+    pics = Parser(quiet=True, lib=lib).parse_stream(synth_cases.write_stream(tmp_path, "--mbw 20 --mbh 15 --frames 3 --gop 0 --seed 311 --ipcm 100", "big"))
     assert len(pics) == 3 and all(p.desc.n_coef_blocks == 12 * 300 for p in pics)
     dump = [(m, s) for m, s in pics[2].ipcm_macroblocks()]
     assert [m for m, _ in dump] == list(range(300))
@@ -195,7 +175,7 @@ def first_slice_at(data):
 
 @pytest.mark.parametrize("cabac", [False, True])
 def test_a_slice_that_ends_inside_the_samples_is_an_error(lib, tmp_path, capfd, cabac):
-    data = make(tmp_path, "--mbw 4 --mbh 3 --frames 1 --seed 312 --ipcm 100" + (" --cabac" if cabac else ""), "t")
+    data = synth_cases.write_stream(tmp_path, "--mbw 4 --mbh 3 --frames 1 --seed 312 --ipcm 100" + (" --cabac" if cabac else ""), "t")
     at = first_slice_at(data)
     for cut in (at + 40, at + 200, at + 380):              # (all inside the first macroblock's 384 bytes)
         capfd.readouterr()
@@ -209,7 +189,7 @@ def test_a_nonzero_alignment_bit_is_an_error(lib, tmp_path, capfd, cabac):
     """the bits between the macroblock type (CABAC: the encoder's flush) and the first sample byte: flipping one of the bits in
     front of the first macroblock's samples must be refused with the parser's message (which bit is an alignment bit depends on
     the slice header's length: every bit of the bytes in front of the samples is tried, one at a time)"""
-    data = make(tmp_path, "--mbw 4 --mbh 3 --frames 1 --seed 313 --qp 30 --ipcm 100 --dump-pcm %s" % (tmp_path / "d.bin") + (" --cabac" if cabac else ""), "t")
+    data = synth_cases.write_stream(tmp_path, "--mbw 4 --mbh 3 --frames 1 --seed 313 --qp 30 --ipcm 100 --dump-pcm %s" % (tmp_path / "d.bin") + (" --cabac" if cabac else ""), "t")
     first = read_dump(str(tmp_path / "d.bin"))[0][0][1]
     at = data.index(first[:16])                             # (noise samples: no emulation prevention in the first sixteen)
     hits = 0
@@ -227,7 +207,7 @@ def test_a_nonzero_alignment_bit_is_an_error(lib, tmp_path, capfd, cabac):
 
 @pytest.mark.parametrize("cabac", [False, True])
 def test_damaged_ipcm_streams_do_not_crash(lib, tmp_path, cabac):
-    data = make(tmp_path, STREAMS["b_spatial"] + (" --cabac" if cabac else ""), "c")
+    data = synth_cases.write_stream(tmp_path, STREAMS["b_spatial"] + (" --cabac" if cabac else ""), "c")
     random.seed(11 + cabac)
     ok = bad = 0
     for trial in range(100):

@@ -7,42 +7,20 @@ here (Appendix A-Q5: out-of-bounds scan8 index), so nothing can be pinned agains
   * GPU: the HIP path against the CPU oracle, picture by picture - both take reference slots per 8x8 quadrant, which
     exercises the per-item reference offsets of the motion-compensation kernels and the reference test of the boundary strengths."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from p264decoder_amd import Parser, _native as N
 from tests import synth_cases
+from tests.stream_args import MMCO, REORDER, SLICED, SUB8X8
 
 ARGS = "--mbw 11 --mbh 9 --frames 10 --gop 0 --seed 41 --refs 2 --coded 8 --maxlevel 6"
-# several slices per picture (the reference handles one, decoder/decoder.c:516-523): slice boundaries in the middle of
-# macroblock rows change every neighbour-availability pattern of the intra predictors and the vector / nC / mode predictors
-SLICED = ["--mbw 11 --mbh 9 --frames 8 --gop 4 --seed 43 --slices 4 --coded 10 --maxlevel 6",
-          "--mbw 7 --mbh 6 --frames 9 --gop 0 --seed 44 --slices 5 --refs 2 --coded 12 --maxlevel 6",
-          "--mbw 9 --mbh 7 --frames 8 --gop 4 --seed 45 --slices 3 --deblock-idc 2 --coded 14 --maxlevel 8"]   # no filtering across slices
-
-
-# sub-8x8 partitions (8x4, 4x8, 4x4; the reference mis-decodes them, A-Q4) and list-0 reordering (ignored by the reference,
-# decoder/lists.c:146-149): spec-driven, pinned by the writer's record and by HIP == oracle
-SUB8X8 = ["--mbw 11 --mbh 9 --frames 8 --gop 4 --seed 46 --sub8x8 --coded 10 --maxlevel 6",
-          "--mbw 9 --mbh 8 --frames 9 --gop 0 --seed 47 --sub8x8 --refs 2 --slices 2 --mvmax 40 --coded 12 --maxlevel 6"]
-REORDER = "--mbw 10 --mbh 8 --frames 12 --gop 0 --seed 48 --refs 2 --reorder --sub8x8 --coded 10 --maxlevel 6"
-
-
-MMCO = ["--mbw 8 --mbh 6 --frames 40 --gop 14 --seed 71 --refs 3 --mmco --coded 8 --maxlevel 6",
-        "--mbw 7 --mbh 5 --frames 36 --gop 0 --seed 72 --refs 4 --mmco --sub8x8 --coded 8 --maxlevel 6",
-        # operation 5 too: everything but the current picture goes, which then counts as frame_num 0 (7.4.3, 8.2.1) - the
-        # pictures behind it (at least num_ref_frames P pictures before the next one) build their lists against that
-        "--mbw 7 --mbh 5 --frames 60 --gop 0 --seed 73 --refs 3 --mmco5 --coded 8 --maxlevel 6"]
-
 
 
 def make(tmp_path, args=ARGS):
-    synth_cases.ensure_tool()
-    stream, dump = str(tmp_path / "mr.264"), str(tmp_path / "mr.mv")
-    subprocess.run([synth_cases.TOOL, stream] + args.split() + ["--dump-mv", dump], check=True)
-    return open(stream, "rb").read(), np.fromfile(dump, dtype=np.uint8)
+    data, dump = synth_cases.write_stream(tmp_path, args, "mr", dumps=("mv",))
+    return data, np.fromfile(dump, dtype=np.uint8)
 
 
 def test_parser_against_writer(lib, tmp_path):

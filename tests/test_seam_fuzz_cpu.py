@@ -47,7 +47,7 @@ def test_fuzz_configurations_reach_the_paths_they_are_meant_for(oracle):
     behind the comparison with the HIP kernels): the loop filter changes samples, edges between macroblocks of different QP
     get filtered, dequantised coefficients wrap their int16 store where the configuration asks for it."""
     import ctypes as C
-    from tests.test_gpu_seam_fuzz import CONFIGS
+    from tests.stream_args import SEAM_CONFIGS as CONFIGS
     for name, mb_w, mb_h, n_pics, kw in CONFIGS:
         rng = np.random.default_rng(sum(map(ord, name)) * 7919)
         slots = kw["slots"]

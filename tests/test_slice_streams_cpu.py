@@ -6,7 +6,6 @@ deblocking offsets unsupported" / "slices of one picture with different referenc
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -127,16 +126,13 @@ def test_more_than_sixteen_entries_are_refused(lib, tmp_path, capfd):
 
 def test_what_stays_refused(lib, tmp_path, capfd):
     """per-slice weight tables; P and B slices in one picture"""
-    synth_cases.ensure_tool()
-    out = str(tmp_path / "r.264")
-    subprocess.run([synth_cases.TOOL, out] + "--mbw 6 --mbh 4 --frames 3 --gop 0 --seed 77 --wp --slices 2 --wp-slice-differ".split(), check=True)
+    data = synth_cases.write_stream(tmp_path, "--mbw 6 --mbh 4 --frames 3 --gop 0 --seed 77 --wp --slices 2 --wp-slice-differ", "r")
     with pytest.raises(P264Error):
-        Parser(quiet=True, lib=lib).parse_stream(open(out, "rb").read())
+        Parser(quiet=True, lib=lib).parse_stream(data)
     assert "slices of one picture with different weight tables unsupported" in capfd.readouterr().err
     # a P picture's first slice, then a hand-written B slice header where its second slice should start (the refusal comes with the
     # header, before any macroblock): the stream has pic_order_cnt_type 0 with 8-bit counts and 8-bit frame_num, CAVLC, PPS 0
-    subprocess.run([synth_cases.TOOL, out] + "--mbw 6 --mbh 4 --frames 4 --seed 78 --refs 2 --bframes 1 --slices 2".split(), check=True)
-    nals = list(N.split_annexb(lib, open(out, "rb").read()))
+    nals = list(N.split_annexb(lib, synth_cases.write_stream(tmp_path, "--mbw 6 --mbh 4 --frames 4 --seed 78 --refs 2 --bframes 1 --slices 2", "r")))
     parser = Parser(quiet=True, lib=lib)
     slices = 0
     with pytest.raises(P264Error):
@@ -182,10 +178,7 @@ def test_a_sub_mb_type_past_the_int_range_is_refused(lib, tmp_path, capfd):
     """found by tests/tools/asan_slices.sh on a damaged stream: ue(v) codes of 32 zeros read as 0xffffffff, -1 as an int, and the
     sub_mb_type checks only looked at the upper end (the B path then indexed its tables at -1).  A hand-written P slice of a 1 x 1
     stream: header, mb_skip_run 0, mb_type P_8x8, then five zero bytes where the sub_mb_types should be."""
-    synth_cases.ensure_tool()
-    out = str(tmp_path / "t.264")
-    subprocess.run([synth_cases.TOOL, out] + "--mbw 1 --mbh 1 --frames 2 --gop 0 --seed 3".split(), check=True)
-    nals = list(N.split_annexb(lib, open(out, "rb").read()))
+    nals = list(N.split_annexb(lib, synth_cases.write_stream(tmp_path, "--mbw 1 --mbh 1 --frames 2 --gop 0 --seed 3", "t")))
     assert [t for t, _, _ in nals] == [7, 8, 5, 1]
     parser = Parser(quiet=True, lib=lib)
     for typ, idc, rbsp in nals[:3]:

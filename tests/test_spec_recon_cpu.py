@@ -12,9 +12,9 @@ import pytest
 from p264decoder_amd import _native as N
 from tests import inter_stim as S
 from tests import pcm_checker, pcm_fuzz, residual_checker, seam_fuzz, spec_recon
-from tests import test_gpu_ipcm_seam_fuzz as ipcm_cfg
-from tests import test_gpu_seam_fuzz as seam_cfg
-from tests import test_gpu_wp_seam_fuzz as wp_cfg
+from tests import ipcm_seam_stim as ipcm_cfg
+from tests import wp_seam_stim as wp_cfg
+from tests.stream_args import SEAM_CONFIGS
 
 SETS = S.SETS
 
@@ -71,7 +71,7 @@ def run_chain(oracle, mb_w, mb_h, slots, frames, pictures, what):
     return coded, changed, spec.census
 
 
-@pytest.mark.parametrize("name,mb_w,mb_h,n_pics,kw", seam_cfg.CONFIGS, ids=[c[0] for c in seam_cfg.CONFIGS])
+@pytest.mark.parametrize("name,mb_w,mb_h,n_pics,kw", SEAM_CONFIGS, ids=[c[0] for c in SEAM_CONFIGS])
 def test_seam_fuzz_pictures_made_conformant_equal_the_oracle(oracle, name, mb_w, mb_h, n_pics, kw):
     rng = np.random.default_rng(sum(map(ord, name)) * 7919)
     slots = kw["slots"]
@@ -92,7 +92,7 @@ def test_weighted_fuzz_pictures_made_conformant_equal_the_oracle(oracle, name, m
 
 @pytest.mark.parametrize("name", sorted(ipcm_cfg.CONFIGS))
 def test_ipcm_fuzz_pictures_made_conformant_equal_the_oracle(oracle, name):
-    """the pictures of test_gpu_ipcm_seam_fuzz.prepare (the batch without an I picture), drawn as it draws them"""
+    """the pictures of ipcm_seam_stim.prepare (the batch without an I picture), drawn as it draws them"""
     mb_w, mb_h, share, samples, kw = ipcm_cfg.CONFIGS[name]
     rng = np.random.default_rng(sum(map(ord, name)) * 131)
     smooth = samples == "frame"
@@ -155,7 +155,7 @@ DIGESTS = {"typical": "30400dbb7e0359da", "int16_wrap": "98293dd6eaa4e7e5", "mix
 
 def test_a_seed_gives_the_picture_it_always_gave():
     """seam_fuzz.make_picture's draws, pinned (digests taken on the commit before the checkers of this file existed)"""
-    for name, mb_w, mb_h, n_pics, kw in seam_cfg.CONFIGS[:6]:
+    for name, mb_w, mb_h, n_pics, kw in SEAM_CONFIGS[:6]:
         rng = np.random.default_rng(sum(map(ord, name)) * 7919)
         for s in range(kw["slots"]):
             seam_fuzz.random_frame(rng, mb_w, mb_h, "smooth" if "smooth" in name else "noise")

@@ -3,22 +3,20 @@ writer meant (--dump-wp), the refusals, and the weight table's way through the s
 import ctypes as C
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from p264decoder_amd import HipReconstructor, P264Error, Parser, _native as N
 from tests import synth_cases
+from tests.stream_args import WP_STREAMS as STREAMS
 
 WP_REC = 3 + 2 * 16 * 3 * 2          # int16 per picture in the writer's --dump-wp record
 
 
 def write_stream(tmp_path, args, name="s"):
-    out, dump = str(tmp_path / (name + ".264")), str(tmp_path / (name + ".wp"))
-    subprocess.run([synth_cases.TOOL, out] + args.split() + ["--dump-wp", dump], check=True)
-    recs = np.fromfile(dump, np.int16).reshape(-1, WP_REC)
-    return open(out, "rb").read(), recs
+    data, dump = synth_cases.write_stream(tmp_path, args, name, dumps=("wp",))
+    return data, np.fromfile(dump, np.int16).reshape(-1, WP_REC)
 
 
 def parsed_tables(lib, data):
@@ -45,15 +43,6 @@ def assert_tables_match(pics, recs):
         assert np.array_equal(got[0, :n0], want[0, :n0]), "picture %d list 0" % k
         assert np.array_equal(got[1, :n1], want[1, :n1]), "picture %d list 1" % k
         assert d.weighted_bipred == 0
-
-
-STREAMS = {
-    "p_cavlc": "--mbw 6 --mbh 4 --frames 8 --gop 0 --seed 71 --refs 2 --wp --sub8x8 --slices 2 --coded 20 --maxlevel 8",
-    "p_cabac": "--mbw 5 --mbh 3 --frames 6 --gop 0 --seed 72 --refs 2 --wp --cabac --coded 20 --maxlevel 8",
-    "b_cabac": "--mbw 5 --mbh 4 --frames 9 --seed 73 --refs 2 --bframes 2 --wp --wp-bi --cabac --coded 20 --maxlevel 8",
-    "b_cavlc_slices": "--mbw 6 --mbh 4 --frames 7 --seed 74 --refs 3 --bframes 2 --wp --wp-bi --slices 3 --coded 20 --maxlevel 8",
-    "dup": "--mbw 6 --mbh 4 --frames 6 --gop 0 --seed 75 --refs 2 --wp --wp-dup --coded 20 --maxlevel 8",
-}
 
 
 @pytest.mark.parametrize("name", sorted(STREAMS))
@@ -116,10 +105,8 @@ def test_writer_without_the_options_is_unchanged(tmp_path):
     import hashlib
     for name in ("cif_ip", "tiny_1x1", "qpdelta"):
         args = synth_cases.CASES[name][0]
-        out = str(tmp_path / "u.264")
-        subprocess.run([synth_cases.TOOL, out] + args.split(), check=True)
         golden = open(os.path.join(synth_cases.GOLDEN, "synth_%s.sha256" % name)).read().split()[0]
-        assert hashlib.sha256(open(out, "rb").read()).hexdigest() == golden
+        assert hashlib.sha256(synth_cases.write_stream(tmp_path, args, "u")).hexdigest() == golden
 
 
 # ---- the table through the ABI --------------------------------------------------------------------------------------------
