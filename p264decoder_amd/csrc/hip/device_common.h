@@ -72,6 +72,14 @@ __device__ __forceinline__ uint32_t chroma_off(const Geom &g, int plane, int x, 
 // first byte of a macroblock's luma / chroma part
 __device__ __forceinline__ uint32_t mb_luma_off(const Geom &g, int mbx, int mby) { return strip_mul(mbx, g.ystrip) + (uint32_t)mby * MB_LUMA_BYTES; }
 __device__ __forceinline__ uint32_t mb_chroma_off(const Geom &g, int mbx, int mby) { return g.coff + strip_mul(mbx, g.cstrip) + (uint32_t)mby * MB_CHROMA_BYTES; }
+// macroblock index -> column and row without a division: inv_mbw = 0xffffffff / mb_w (from the host) gives the row or one
+// less, the comparison fixes it up
+__device__ __forceinline__ void split_mb(int mbi, const Geom &g, uint32_t inv_mbw, int &mbx, int &mby)
+{
+    int row = (int)__umulhi((unsigned)mbi, inv_mbw);
+    if (mbi - row * g.mb_w >= g.mb_w) row++;
+    mbx = mbi - row * g.mb_w; mby = row;
+}
 
 // ---- global-memory accessors ------------------------------------------------------------
 // Pointers that reach a kernel through memory (the fields of PicDev) are "flat" to the compiler:
@@ -137,23 +145,17 @@ __device__ __constant__ const uint8_t c_tc0[52][3] = {
 // zig-zag scan position k -> raster position (same data as c_zigzag, one nibble per entry)
 __device__ __forceinline__ int zigzag_pos(int k) { return (int)(((k & 8) ? 0xFEB7ADC9u : 0x63258410u) >> (4 * (k & 7))) & 15; }
 
-// dequantisation parameters of one macroblock / plane: wave-uniform, so they live in SGPRs
-struct DqParams { int mf0, mf1, mf2, qbits; };
 // table-free: the six scales of a position class are 5-bit fields of one constant (scale / 16 <= 29), so a
 // macroblock's parameters cost a handful of scalar ALU operations instead of dependent constant-memory loads
-__device__ __forceinline__ int dq_scale(int cls, int rem)
-{   // core/set.c:27-35: {10,11,13,14,16,18}, {13,14,16,18,20,23}, {16,18,20,23,25,29}
+// (core/set.c:27-35: {10,11,13,14,16,18}, {13,14,16,18,20,23}, {16,18,20,23,25,29}; dq_s: without the factor 16 the reference folds in)
+__device__ __forceinline__ uint32_t dq_s(int cls, int rem)
+{
     const uint32_t k = cls == 0 ? (10u | 11u << 5 | 13u << 10 | 14u << 15 | 16u << 20 | 18u << 25)
                      : cls == 1 ? (13u | 14u << 5 | 16u << 10 | 18u << 15 | 20u << 20 | 23u << 25)
                                 : (16u | 18u << 5 | 20u << 10 | 23u << 15 | 25u << 20 | 29u << 25);
-    return (int)((k >> (5 * rem)) & 31u) * 16;
+    return (k >> (5 * rem)) & 31u;
 }
-__device__ __forceinline__ DqParams dq_params(int qp)
-{
-    const int per = (qp * 43) >> 8, rem = qp - per * 6;          // qp / 6 and qp % 6 for 0 <= qp < 64
-    DqParams d = { dq_scale(0, rem), dq_scale(1, rem), dq_scale(2, rem), per - 4 };
-    return d;
-}
+__device__ __forceinline__ int dq_scale(int cls, int rem) { return (int)dq_s(cls, rem) * 16; }
 // chroma QP of a luma QP index 0..51 (core/macroblock.h:210-218 = H.264 table 8-15): identity below 30, then
 // qp minus a 4-bit correction
 __device__ __forceinline__ int chroma_qp(int qi)
@@ -163,16 +165,6 @@ __device__ __forceinline__ int chroma_qp(int qi)
     const int corr = k < 16 ? (int)((0x7765544332221111ull >> (4 * k)) & 15) : (int)((0xCBA998u >> (4 * (k - 16))) & 15);
     return qi - corr;
 }
-__device__ __forceinline__ int dequant_coef(int c, int pos, const DqParams &d)
-{   // core/quant.c:66-99; position class (pos&1) + ((pos>>2)&1); int16 store wrap = A-Q8
-    int cls = (pos & 1) + ((pos >> 2) & 1);
-    const int m1 = -(int)(cls == 1), m2 = -(int)(cls == 2);            // lane-varying class: masks, not branches
-    int mf = (d.mf0 & ~(m1 | m2)) | (d.mf1 & m1) | (d.mf2 & m2);
-    int v = c * mf;
-    v = d.qbits >= 0 ? (int)((unsigned)v << d.qbits) : (v + (1 << (-d.qbits - 1))) >> (-d.qbits);
-    return (int)(int16_t)v;
-}
-
 // luma 4x4 block index (decode order, core/macroblock.h:194-201) <-> position
 __device__ __forceinline__ int blk_x(int i) { return (i & 1) | ((i >> 1) & 2); }
 __device__ __forceinline__ int blk_y(int i) { return ((i >> 1) & 1) | ((i >> 2) & 2); }
@@ -184,17 +176,6 @@ __device__ __forceinline__ uint32_t coef_slot(uint32_t mask, int blk)
     return ((mask >> 24) & 1) + ((mask >> 25) & 1) + __popc(mask & ((1u << blk) - 1u) & 0xffffffu);
 }
 
-// ---- dequantisation, one coefficient (core/quant.c:66-99; int16 store wrap = A-Q8) -------
-__device__ __forceinline__ int dequant_coef(int c, int pos, int qp)
-{
-    const int per = (qp * 43) >> 8, rem = qp - per * 6;
-    int mf = dq_scale((pos & 1) + ((pos >> 2) & 1), rem);
-    int qbits = per - 4;
-    int v = c * mf;
-    v = qbits >= 0 ? (int)((unsigned)v << qbits) : (v + (1 << (-qbits - 1))) >> (-qbits);
-    return (int)(int16_t)v;
-}
-
 // a + b or a - b, with the pair picked by lane-varying flags (all-ones masks), branch-free
 __device__ __forceinline__ int pick_addsub(int a0, int a1, int b0, int b1, bool second, bool minus)
 {
@@ -202,34 +183,3 @@ __device__ __forceinline__ int pick_addsub(int a0, int a1, int b0, int b1, bool 
     const int a = (a1 & ms) | (a0 & ~ms), b = (b1 & ms) | (b0 & ~ms);
     return a + ((b ^ neg) - neg);
 }
-
-// Output k (0..3) of the transform's butterfly {s02+s13, d02+d13, d02-d13, s02-s13} with k varying per lane, without
-// branches: nested ?: on a lane-varying index compiles to nested exec-mask regions (~16 scalar instructions per use).
-__device__ __forceinline__ int butterfly_pick(int s02, int d02, int s13, int d13, int k)
-{
-    const int outer = -(int)(k == 0 || k == 3), neg = -(int)(k >= 2);     // all-ones masks
-    const int a = (s02 & outer) | (d02 & ~outer), b = (s13 & outer) | (d13 & ~outer);
-    return a + ((b ^ neg) - neg);
-}
-
-// The 4x4 inverse transform (core/dct.c:205-247), shared between the four lanes that own the four rows of a block: lane y
-// runs the horizontal pass on ROW y only and puts it back in place (int16, as the reference stores its tmp), then - after
-// a fence - every lane reads the 16 intermediate values and evaluates the vertical pass for its own output row.  (Each
-// lane doing the whole horizontal pass for itself cost 4x the work of that pass.)
-__device__ __forceinline__ void idct4x4_rowpass(int16_t *c, int y)
-{
-    uint2 *r = (uint2 *)(c + y * 4);
-    const uint2 v = *r;
-    const int c0 = (int)(int16_t)(v.x & 0xffff), c1 = (int)v.x >> 16, c2 = (int)(int16_t)(v.y & 0xffff), c3 = (int)v.y >> 16;
-    const int s02 = c0 + c2, d02 = c0 - c2, s13 = c1 + (c3 >> 1), d13 = (c1 >> 1) - c3;
-    const uint32_t t0 = (uint32_t)(s02 + s13) & 0xffffu, t1 = (uint32_t)(d02 + d13) << 16;
-    const uint32_t t2 = (uint32_t)(d02 - d13) & 0xffffu, t3 = (uint32_t)(s02 - s13) << 16;
-    *r = make_uint2(t0 | t1, t2 | t3);
-}
-// one output sample (x,y) of the vertical pass over the intermediate left by idct4x4_rowpass
-__device__ __forceinline__ int idct4x4_col_sample(const int16_t *t, int x, int y)
-{
-    const int t0 = t[x], t1 = t[4 + x], t2 = t[8 + x], t3 = t[12 + x];
-    return (int)(int16_t)((butterfly_pick(t0 + t2, t0 - t2, t1 + (t3 >> 1), (t1 >> 1) - t3, y) + 32) >> 6);
-}
-

@@ -260,9 +260,8 @@ void k_deblock_bs(const PicDev *__restrict__ pics, Geom g, EdgeInfo *__restrict_
     }
     const int mbi = blockIdx.x * 256 + threadIdx.x;
     if (mbi >= g.n_mb) return;
-    int mby = (int)__umulhi((unsigned)mbi, inv_mbw);
-    if (mbi - mby * g.mb_w >= g.mb_w) mby++;
-    const int mbx = mbi - mby * g.mb_w;
+    int mbx, mby;
+    split_mb(mbi, g, inv_mbw, mbx, mby);
     const uint4 rec = gload4(ubase(pd->mb, (uint32_t)mbi * 16u));
     const int *mvs = pd->mv;
     const uint4 m0 = gload4(ubase(mvs, (uint32_t)mbi * 64u)), m1 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 16u)), m2 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 32u)), m3 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 48u));

@@ -19,7 +19,7 @@
 // Grid: (tiles of a picture / 4, pictures); a wavefront never mixes pictures.
 #pragma once
 #include "device_common.h"
-#include "kernel_mc.h"
+#include "lane_ops.h"
 
 #define EXPORT_THREADS 256
 #define EXPORT_GROUPS  4            // 8-row groups of a tile
@@ -61,7 +61,7 @@ template <int NW> __device__ __forceinline__ void put_piece(uint8_t *p, const ui
 }
 
 // sixteen pixels of a luma strip row with the chroma row under them -> R, G, B, four pixels per dword.  The clip of (sum >> 13) to
-// a byte is kernel_mc.h's round_pack4 (v_ashr_pk_u8_i32, two values per instruction, only its defined low half used): written as
+// a byte is lane_ops.h's round_pack4 (v_ashr_pk_u8_i32, two values per instruction, only its defined low half used): written as
 // clip255(v >> 13) << 8k the compiler picks that instruction itself and ORs the other bytes onto its undefined upper half.
 __device__ __forceinline__ void rgb_row(const uint4 yv, const uint4 cv, const ExportParams &e, uint32_t (&R)[4], uint32_t (&G)[4], uint32_t (&B)[4])
 {

@@ -24,6 +24,8 @@
 #pragma once
 #include <stddef.h>
 #include "device_common.h"
+#include "lane_ops.h"
+#include "residual4x4.h"
 #include "wavefront_sync.h"
 #include "kernel_deblock.h"             // (edge_info_of: the edge-info role of k_intra_sparse)
 #include "kernel_t8x8.h"                // (c_scan8x8, t8_scale, t8_idct1d: the residual of Intra 8x8 macroblocks)
@@ -94,12 +96,7 @@ __device__ __forceinline__ int byte_sum(uint32_t v) { return (int)__builtin_amdg
 __device__ __forceinline__ void idct_res(const uint32_t (&col)[4][2], uint32_t (&r)[4][2])
 {
     s16x2 T[4][2];
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const s16x2 c0 = as_s16x2(col[0][j]), c1 = as_s16x2(col[1][j]), c2 = as_s16x2(col[2][j]), c3 = as_s16x2(col[3][j]);
-        const s16x2 s02 = c0 + c2, d02 = c0 - c2, s13 = c1 + (c3 >> 1), d13 = (c1 >> 1) - c3;
-        T[0][j] = s02 + s13; T[1][j] = d02 + d13; T[2][j] = d02 - d13; T[3][j] = s02 - s13;
-    }
+    idct_rows(col, T);
     int res[4][4];
 #pragma unroll
     for (int x = 0; x < 4; x++) {
@@ -523,7 +520,7 @@ __device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, I
     else if (r == 2) tile[3] = (uint8_t)vT;
     wave_lds_fence();
 
-    // ---- residuals of the eight blocks (same arithmetic as kernel_mc.h) ----
+    // ---- residuals of the eight blocks (residual4x4.h) ----
     if (__ballot(has_chroma)) {
         if (l < 8) {
             const int qpc = chroma_qp(clip3i(qp + pd->chroma_qp_offset, 0, 51));
@@ -531,7 +528,8 @@ __device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, I
             uint32_t col[4][2], rr[4][2];
             unscan_cols<true>(lv, col);
             dequant_cols(col, qpc);
-            // DC of block j: idct2x2dc (core/dct.c:55-68, int16 stores), then p264_mb_dequant_2x2_dc (core/quant.c:138-159)
+            // DC of block j: residual4x4.h's chroma_dc_level, written out (called from here, one add of the transform swaps its operands
+            // in all four k_intra* kernels, whatever the form of its parameters)
             const int j = l & 3;
             const int d0 = (int)(int16_t)(dcl.x & 0xffff), d1 = (int)dcl.x >> 16, d2 = (int)(int16_t)(dcl.y & 0xffff), d3 = (int)dcl.y >> 16;
             const int t0 = d0 + d1, t1 = d0 - d1, t2 = d2 + d3, t3 = d2 - d3;
@@ -708,9 +706,8 @@ __device__ __forceinline__ void intra_picture(IntraShared &sh, uint32_t *lut8, c
                     const int kn = k + n_waves * 4;
                     const int mbi_n = kn + grp < n ? (int)free_list[t][kn + grp] : 0;
                     const uint4 rec_n = gload4(pd->mb + mbi_n);
-                    int mby = (int)__umulhi((unsigned)mbi, inv_mbw);
-                    if (mbi - mby * g.mb_w >= g.mb_w) mby++;
-                    const int mbx = mbi - mby * g.mb_w;
+                    int mbx, mby;
+                    split_mb(mbi, g, inv_mbw, mbx, mby);
                     if (active) {
                         if (chroma_role) intra_chroma4(pd, g, L, mbx, mby, rec, l);
                         else             intra_luma4<I8>(pd, g, L, lut, lut8, mbx, mby, rec, l);
@@ -955,9 +952,8 @@ void k_intra_sparse(const PicDev *__restrict__ pics, Geom g, int *status, const 
             // into a 64-bit induction variable per lane - this build has 64 registers)
             int mbi = mbi_it;
             asm volatile("" : "+v"(mbi));
-            int mby = (int)__umulhi((unsigned)mbi, inv_mbw);
-            if (mbi - mby * g.mb_w >= g.mb_w) mby++;
-            const int mbx = mbi - mby * g.mb_w;
+            int mbx, mby;
+            split_mb(mbi, g, inv_mbw, mbx, mby);
             const uint4 rec = gload4(ubase(pd->mb, (uint32_t)mbi * 16u));
             const int *mvs = pd->mv;
             const uint4 m0 = gload4(ubase(mvs, (uint32_t)mbi * 64u)), m1 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 16u)), m2 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 32u)), m3 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 48u));

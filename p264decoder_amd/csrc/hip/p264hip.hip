@@ -16,6 +16,7 @@
 #include "device_common.h"
 #define P264HIP_K_DEBLOCK_DECL_ONLY          // k_deblock lives in k_deblock.hip (its own compiler options: kernel_deblock.h)
 #include "kernel_deblock.h"
+#include "kernel_mc_sort.h"                 // (McLayout, mc_layout, MC_SORT_THREADS, MCE_W_SHIFT, MCE_MAX_MB_W, the k_mc_sort* kernels)
 #include "kernel_mc.h"
 #include "kernel_intra.h"
 #include "kernel_t8x8.h"
@@ -157,7 +158,7 @@ static uint8_t *frame_ptr(p264hip_ctx *c, int stream, int slot)
 
 extern "C" int p264hip_create(p264hip_ctx **out, int device, int mb_w, int mb_h, int n_streams, int slots, int max_pictures)
 {
-    if (!out || mb_w < 1 || mb_w > 2047 || mb_h < 1 || mb_h > MAX_MB_ROWS ||    /* (11 bits of macroblock column in a work-list entry) */
+    if (!out || mb_w < 1 || mb_w > MCE_MAX_MB_W || mb_h < 1 || mb_h > MAX_MB_ROWS ||    /* (the column and row fields of a work-list entry, kernel_mc_sort.h) */
         n_streams < 1 || slots < 1 || slots > P264HIP_MAX_REFS + 1 || max_pictures < 1)
         return fail(P264HIP_EINVAL, "p264hip_create: bad argument (mb %dx%d, streams %d, slots %d, pictures %d)", mb_w, mb_h, n_streams, slots, max_pictures);
     int ndev = 0;
@@ -932,7 +933,7 @@ static void launch_inter(p264hip_ctx *c, const PicDev *batch, int n, const Batch
     ScopedStamp t(c, 0);
     const Geom g = c->g;
     const McLayout ml = c->ml;
-    // (explicit weighted prediction in the batch: the instances that route such pictures to the weighted class, kernel_mc.h)
+    // (explicit weighted prediction in the batch: the instances that route such pictures to the weighted class, kernel_mc_sort.h)
     if (k.b) hipLaunchKernelGGL(k.wp ? k_mc_sort_b_wp : k_mc_sort_b, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, batch, c->d_mc, g, ml, inv_mb_w(c), c->d_is_intra);
     else hipLaunchKernelGGL(k.wp ? k_mc_sort_wp : k_mc_sort, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, batch, c->d_mc, g, ml, inv_mb_w(c), c->d_is_intra);
     // one launch for luma / chroma, macroblock / quadrant items (k_mc)

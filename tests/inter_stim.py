@@ -2,7 +2,7 @@
 cell of what tests/inter_checker.py's census and this module's residual survey record, instead of hoping that random vectors
 land one sample from a border.  Everything is generated from seeds; nothing is data.
 
-* `window_set()`: k_mc decides "window inside the picture / clamped" per work item with a window test (kernel_mc.h, mc_classify;
+* `window_set()`: k_mc decides "window inside the picture / clamped" per work item with a window test (kernel_mc_sort.h, mc_classify;
   windows in tests/inter_checker.py).  On pictures of 4 x 3 macroblocks, for each of the seven phase classes and each item kind -
   whole macroblock, quadrant, and the per-block fetch of quadrants whose vectors differ (the eighth class) - one item each with its
   luma window flush with each border, one sample past each border, in all four corners (flush and past), wholly outside on each

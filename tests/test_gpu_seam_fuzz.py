@@ -44,7 +44,7 @@ def test_seam_fuzz(lib, oracle, name, mb_w, mb_h, n_pics, kw):
                 seen["weighted"].add(int(pic.desc.weighted_bipred))
                 r0, r1 = pic.ref_idx.reshape(n, 4)[inter], pic.ref_idx_l1.reshape(n, 4)[inter]
                 seen["dirs"] |= set(((r0 >= 0).astype(int) + 2 * (r1 >= 0).astype(int)).reshape(-1).tolist())
-                # which road through the motion-compensation stage (kernel_mc.h, mc_classify): one list -> the P road; both lists
+                # which road through the motion-compensation stage (kernel_mc_sort.h, mc_classify): one list -> the P road; both lists
                 # with one vector per quadrant and list -> two passes (whole-macroblock items, quadrant items, quadrants that the
                 # second pass only carries through); vectors differing inside a quadrant -> the generic two-list class
                 mv1 = pic.mv_l1.reshape(n, 4, 4, 2)
