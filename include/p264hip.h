@@ -80,7 +80,7 @@ enum {
  * The range rule (coef_index + popcount(mask) <= n_coef_blocks), the compact format's int8 / int16 choice per entry and the loop
  * filter's "the block that holds the sample has coefficients" (8.7.2.1: the 8x8 block, for such a macroblock) read the mask as
  * they read any other.  Chroma (bits 16-25, its entries behind the luma ones) is as on every record; the levels are scaled with
- * flat scaling lists.  The loop filter leaves the macroblock's inner luma edges 1 and 3 alone (8.7: no transform edges).  Every
+ * list 7 of a picture with scaling_lists, else with flat lists.  The loop filter leaves the macroblock's inner luma edges 1 and 3 alone (8.7: no transform edges).  Every
  * road into an input slot (the list at P264_IPCM_COEF_MASK) rejects a flagged record that is not inter, one whose luma nibbles are
  * neither 0x0 nor 0xF, and one in a picture whose descriptor says 0. */
 #define P264_MB_T8X8 0x04
@@ -191,7 +191,21 @@ typedef struct p264hip_picture {
      * other bit: inter records of the picture may carry P264_MB_T8X8, and a batch that holds the picture launches the kernel that
      * adds their luma residual (k_t8x8, between motion compensation and intra prediction).  0 and 1 mean what they always meant. */
     int32_t             transform_8x8;
+    /* ---- scaling matrices (High profile, H.264 7.3.2.1.1.1, 8.5.9: LevelScale = weightScale * normAdjust).  scaling_lists != 0: the
+     * levels of the picture are scaled with the eight lists below instead of Flat_4x4_16 / Flat_8x8_16 - 4x4: 0 Intra Y, 1 Intra Cb,
+     * 2 Intra Cr, 3 Inter Y, 4 Inter Cb, 5 Inter Cr; 8x8: 0 Intra Y (list 6, records with P264_MB_I8X8), 1 Inter Y (list 7, records
+     * with P264_MB_T8X8) - RESOLVED (defaults and fall-backs applied) and in SCAN order: weight [k] belongs to scan position k, the
+     * order the levels of an entry are in (an AC-only entry holds scan positions 1 .. 15 at [0 .. 14]: its level [k] pairs with weight
+     * [k + 1]).  Intra or inter is the macroblock's, not the picture's.  Any byte is legal (0 zeroes the coefficient), no road checks
+     * or refuses anything here.  Such a picture carries the 224 bytes in its input slot (off_scaling below): p264hip_upload copies the
+     * descriptor's, the packed and compact roads carry the block's.  A batch that holds such a picture launches instances of the sort
+     * and intra kernels that know the table and a kernel that adds the residual of its inter macroblocks (k_scaled_inter);
+     * 0 = flat: what every zeroed descriptor says. */
+    int32_t             scaling_lists;
+    uint8_t             scaling4x4[6][16];
+    uint8_t             scaling8x8[2][64];
 } p264hip_picture_t;
+#define P264HIP_SCALING_BYTES 224                    /* scaling4x4 and scaling8x8 back to back: the table as it lies in a slot and in a compact block */
 
 typedef struct p264hip_ctx p264hip_ctx;
 
@@ -237,7 +251,8 @@ typedef struct p264hip_input_layout {
     size_t off_mb, off_mv, off_ref, off_i4, off_coef;      /* p264hip_mb_t[n], int16[n][16][2], int8[n][4], uint8[n][16], int16[n_coef_blocks][16] */
     size_t off_mv_l1, off_ref_l1, off_weights;             /* B pictures only (0 otherwise): list-1 vectors, indices, bipred_weight[] */
     size_t bytes;                                          /* of the whole block */
-    size_t off_wp;                                         /* explicit_wp pictures only (0 otherwise): wp[][][][], behind everything else */
+    size_t off_wp;                                         /* explicit_wp pictures only (0 otherwise): wp[][][][], behind everything above */
+    size_t off_scaling;                                    /* scaling_lists pictures only (0 otherwise): scaling4x4, scaling8x8 (P264HIP_SCALING_BYTES), behind everything else */
 } p264hip_input_layout_t;
 int  p264hip_input_layout(const p264hip_picture_t *desc, p264hip_input_layout_t *out);
 /* 0, or P264HIP_EINVAL where an explicit_wp picture's denominators, weights or offsets are out of range (every upload path checks it) */
@@ -289,7 +304,8 @@ typedef struct p264hip_compact_hdr {                /* 128 bytes; sections follo
     uint32_t n_i4, level_bytes;                     /* macroblocks with an Intra4x4 mode entry, bytes of levels */
     struct { uint32_t off_ref, off_shape, off_vec, n_vec; } list[2];               /* n_vec: vectors (dwords) in the list's vec section */
     uint32_t off_wp;                                /* explicit_wp pictures: wp[][][][] (384 bytes), 0 otherwise */
-    uint32_t reserved[10];
+    uint32_t off_scaling;                           /* scaling_lists pictures: the table (P264HIP_SCALING_BYTES), 0 otherwise */
+    uint32_t reserved[9];
 } p264hip_compact_hdr_t;
 /* bytes a compact block of this picture needs at most */
 size_t  p264hip_compact_bound(const p264hip_picture_t *pic);
@@ -404,8 +420,11 @@ typedef struct p264hip_launch_info {
     int32_t edge_info_fused;       /* edge-info workgroups per picture inside the k_intra_sparse launch (0: own launch k_deblock_bs) */
     int32_t deblock_pics_per_wg, deblock_rb_log2, deblock_waves, deblock_wgs;
     int32_t deblock_odd_single;    /* 1: odd pictures per workgroup - pairs in bands of 4 rows, the last picture alone in bands of 8 */
-    int32_t t8x8_wgs;              /* k_t8x8: workgroups of the launch (0: no picture of the batch has transform_8x8, no launch) */
-    int32_t reserved[4];
+    int32_t t8x8_wgs;              /* k_t8x8: workgroups of the launch (0: no picture of the batch has transform_8x8, no launch - or a picture of the
+                                      batch has scaling_lists: k_scaled_inter then adds the 8x8 blocks of every picture of the batch) */
+    int32_t scaled_pictures;       /* pictures of the batch with scaling_lists.  Not 0: the batch ran the instances that know the table (k_mc_sort_scaled / k_mc_sort_scaled_p,
+                                      k_scaled_inter behind the inter launches, k_intra_scaled / k_intra_sparse_scaled) */
+    int32_t reserved[3];
     int32_t intra_i8;              /* 1: the intra launch ran the Intra 8x8 instances (a picture of the batch has P264_T8X8_INTRA) */
 } p264hip_launch_info_t;
 int  p264hip_last_launch(p264hip_ctx *ctx, p264hip_launch_info_t *out);

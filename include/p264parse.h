@@ -28,6 +28,11 @@ enum {
                                    P264_MB_I8X8, in pictures whose descriptor carries P264_T8X8_INTRA (include/p264hip.h).  Off by default:
                                    only the owner of the backend that takes the pictures can say whether it knows the record; without
                                    the option such a macroblock ends the slice with "Intra 8x8 prediction unsupported" */
+    P264PARSE_OPT_SCALING = 8,  /* read the scaling matrices of High-profile parameter sets (seq_ / pic_scaling_matrix_present_flag) and hand
+                                   out every picture's eight resolved lists in its descriptor (scaling_lists, scaling4x4, scaling8x8:
+                                   include/p264hip.h; lists that are 16 everywhere give scaling_lists = 0).  Off by default, for the reason
+                                   P264PARSE_OPT_INTRA8X8 is: only the owner of the backend knows whether it reads the table; without the
+                                   option such a parameter set is refused ("flat scaling lists only") as it always was */
     P264PARSE_OPT_STRICT = 2    /* H.264-conformant QP accumulation also for Baseline CAVLC streams, where the default is the
                                    reference's rule (decoder/macroblock.c:568, core/macroblock.c:1247-1252; SURVEY A-Q2).
                                    CABAC, B slices and every profile but Baseline - none of which the reference decodes -

@@ -21,6 +21,7 @@ COEF_CHROMA_DC = 1 << 25
 AVAIL_LEFT, AVAIL_TOP, AVAIL_TOPRIGHT, AVAIL_TOPLEFT = 1, 2, 4, 8
 EDGE_LEFT, EDGE_TOP, EDGE_INNER = 1, 2, 4
 MB_I8X8 = 0x08          # bit of MbInfo.intra_modes: an I4x4 record predicted as Intra 8x8 (luma coded as 8x8 blocks)
+SCALING_BYTES = 224     # Picture.scaling4x4 + Picture.scaling8x8: the table as it lies in an input slot and in a compact block
 T8X8_INTRA = 2          # bit of Picture.transform_8x8: Intra4x4 records may carry MB_I8X8
 MB_T8X8 = 0x04          # bit of MbInfo.intra_modes: the inter macroblock's luma residual is coded as 8x8 blocks
 
@@ -48,6 +49,8 @@ class Picture(C.Structure):
         ("ref_slot_l1", C.c_int32 * MAX_REFS), ("bipred_weight", C.c_int16 * (MAX_REFS * MAX_REFS)),
         ("explicit_wp", C.c_int32), ("wp_log2_denom", C.c_int32 * 2), ("wp", C.c_int16 * (2 * MAX_REFS * 3 * 2)),   # wp: [list][ref_idx][Y, Cb, Cr][weight, offset], flat
         ("transform_8x8", C.c_int32),
+        # scaling matrices: the eight resolved lists in scan order (4x4: Intra Y, Cb, Cr, Inter Y, Cb, Cr; 8x8: Intra Y, Inter Y), flat
+        ("scaling_lists", C.c_int32), ("scaling4x4", C.c_uint8 * (6 * 16)), ("scaling8x8", C.c_uint8 * (2 * 64)),
     ]
 
 
@@ -57,7 +60,7 @@ assert C.sizeof(MbInfo) == 16
 class LaunchInfo(C.Structure):
     """p264hip_launch_info_t"""
     _fields_ = [(n, C.c_int32) for n in ("pictures", "compute_units", "mc_wgs_per_picture", "intra_waves", "edge_info_fused",
-                                         "deblock_pics_per_wg", "deblock_rb_log2", "deblock_waves", "deblock_wgs", "deblock_odd_single", "t8x8_wgs")] + [("reserved", C.c_int32 * 4), ("intra_i8", C.c_int32)]
+                                         "deblock_pics_per_wg", "deblock_rb_log2", "deblock_waves", "deblock_wgs", "deblock_odd_single", "t8x8_wgs", "scaled_pictures")] + [("reserved", C.c_int32 * 3), ("intra_i8", C.c_int32)]
 
 
 BUILD_TIMING = 1
@@ -65,18 +68,24 @@ BUILD_TIMING = 1
 
 class InputLayout(C.Structure):
     """p264hip_input_layout_t"""
-    _fields_ = [(n, C.c_size_t) for n in ("off_mb", "off_mv", "off_ref", "off_i4", "off_coef", "off_mv_l1", "off_ref_l1", "off_weights", "bytes", "off_wp")]
+    _fields_ = [(n, C.c_size_t) for n in ("off_mb", "off_mv", "off_ref", "off_i4", "off_coef", "off_mv_l1", "off_ref_l1", "off_weights", "bytes", "off_wp", "off_scaling")]
 
 
 class CompactList(C.Structure):
     _fields_ = [("off_ref", C.c_uint32), ("off_shape", C.c_uint32), ("off_vec", C.c_uint32), ("n_vec", C.c_uint32)]
 
 
+class _CompactTail(C.Union):
+    """the last ten words of p264hip_compact_hdr_t: off_scaling is the first of what used to be reserved[10] (0 for flat pictures)"""
+    _fields_ = [("reserved", C.c_uint32 * 10), ("off_scaling", C.c_uint32)]
+
+
 class CompactHdr(C.Structure):
     """p264hip_compact_hdr_t (128 bytes)"""
+    _anonymous_ = ("tail",)
     _fields_ = [("magic", C.c_uint32), ("n_mb", C.c_uint32), ("n_coef_blocks", C.c_uint32), ("bytes", C.c_uint32), ("n_lists", C.c_uint32),
                 ("off_rec", C.c_uint32), ("off_i4flag", C.c_uint32), ("off_i4", C.c_uint32), ("off_lvflag", C.c_uint32), ("off_levels", C.c_uint32),
-                ("off_weights", C.c_uint32), ("n_i4", C.c_uint32), ("level_bytes", C.c_uint32), ("list", CompactList * 2), ("off_wp", C.c_uint32), ("reserved", C.c_uint32 * 10)]
+                ("off_weights", C.c_uint32), ("n_i4", C.c_uint32), ("level_bytes", C.c_uint32), ("list", CompactList * 2), ("off_wp", C.c_uint32), ("tail", _CompactTail)]
 
 
 class PipeStats(C.Structure):

@@ -14,7 +14,7 @@
 #pragma once
 #include "device_common.h"
 
-struct ExpandJob { const uint8_t *src; uint8_t *dst; uint32_t off_mv, off_ref, off_i4, off_coef, off_mv_l1, off_ref_l1, off_weights, off_wp; };   // off_wp: explicit_wp pictures only (0 otherwise)
+struct ExpandJob { const uint8_t *src; uint8_t *dst; uint32_t off_mv, off_ref, off_i4, off_coef, off_mv_l1, off_ref_l1, off_weights, off_wp, off_scaling; };   // off_wp / off_scaling: explicit_wp / scaling_lists pictures only (0 otherwise)
 #define EXPAND_THREADS 1024
 
 // exclusive prefix sum of one value per thread over the workgroup (v in, the sum of the threads before this one out)
@@ -100,6 +100,8 @@ void k_expand_compact(const ExpandJob *__restrict__ jobs)
     if (h.n_lists > 1 && tid < 32) gstore4(job.dst + job.off_weights + (size_t)tid * 16, gload4(src + h.off_weights + (size_t)tid * 16));   // bipred_weight[]: 512 bytes
     // explicit weight table: 384 bytes (the header check: off_wp is set exactly for explicit_wp pictures, inside the block; the slot has the section then)
     if (h.off_wp && job.off_wp && tid < 24) gstore4(job.dst + job.off_wp + (size_t)tid * 16, gload4(src + h.off_wp + (size_t)tid * 16));
+    // scaling lists: 224 bytes (the header check: off_scaling is set exactly for scaling_lists pictures, inside the block; the slot has the section then)
+    if (h.off_scaling && job.off_scaling && tid < P264HIP_SCALING_BYTES / 16) gstore4(job.dst + job.off_scaling + (size_t)tid * 16, gload4(src + h.off_scaling + (size_t)tid * 16));
     // ---- coded levels: thread t owns blocks [t * B, t * B + B); a block is sixteen int8 (flag bit set) or sixteen int16 ----
     const int nb = (int)h.n_coef_blocks, B = (nb + EXPAND_THREADS - 1) / EXPAND_THREADS, b0 = min(tid * B, nb), b1 = min(b0 + B, nb);
     const uint8_t *flag = src + h.off_lvflag, *lv = src + h.off_levels;

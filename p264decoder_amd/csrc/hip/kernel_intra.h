@@ -29,6 +29,7 @@
 #include "wavefront_sync.h"
 #include "kernel_deblock.h"             // (edge_info_of: the edge-info role of k_intra_sparse)
 #include "kernel_t8x8.h"                // (c_scan8x8, t8_scale, t8_idct1d: the residual of Intra 8x8 macroblocks)
+#include "kernel_scaling.h"             // (ScaleDev, scaling_to_lds, scale_cols_w, chroma_dc_level_w, t8_scale_w: the SC instances)
 
 #define IT_STRIDE 24               // luma tile: row -1..15, byte 3 = left column, 4..19 = MB, 20..23 = top-right
 #define CT_STRIDE 12               // chroma tile (one per plane): byte 3 = left column, 4..11 = MB
@@ -171,8 +172,13 @@ __device__ __forceinline__ uint32_t lut8_entry(int mode, int x, int y)
 //   samples   lane l = row l >> 1, samples 4 (l & 1) .. + 3: three table places each, DC apart; residual added, one dword into the
 //             tile, from where the next block takes its neighbours.
 // With I8 = false none of this exists: the instances k_intra / k_intra_sparse are the code they were.
-template <bool I8>
-__device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, IntraGrp &L, const uint32_t *lut, const uint32_t *lut8, int mbx, int mby, const uint4 rec, int l)
+//
+// SC (k_intra_scaled / k_intra_sparse_scaled, the instances a batch takes when one of its pictures has scaling_lists; built with I8):
+// the levels are scaled with the picture's intra lists - 0 (luma 4x4 blocks and the Intra16x16 DC), 6 (Intra 8x8 blocks); 1 and 2 in
+// intra_chroma4 - read from sw, the workgroup's table in raster order (kernel_scaling.h), in 32 bits.  A flat picture of such a
+// batch has an all-16 table there.  With SC = false sw is not looked at.
+template <bool I8, bool SC>
+__device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, IntraGrp &L, const uint32_t *lut, const uint32_t *lut8, const uint8_t *sw, int mbx, int mby, const uint4 rec, int l)
 {
     // Everything below that depends on the lane number alone (roles, tile offsets, edge slots) would otherwise be hoisted
     // out of the caller's loops and kept - or spilled - across them: recomputing it per macroblock is a few dozen
@@ -257,7 +263,8 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
                 }
                 const int s01 = tcol[0] + tcol[1], d01 = tcol[0] - tcol[1], s23 = tcol[2] + tcol[3], d23 = tcol[2] - tcol[3];
                 v = (int)(int16_t)pick_addsub(s01, d01, s23, d23, j >= 2, j == 1 || j == 2);
-                const int per = (qp * 43) >> 8, rem = qp - per * 6, qbits = per - 6, mf = dq_scale(0, rem);
+                const int qps = SC ? (qp & 63) : qp;                              // (8.5.10 with LevelScale(qP % 6, 0, 0) of list 0)
+                const int per = (qps * 43) >> 8, rem = qps - per * 6, qbits = per - 6, mf = SC ? (int)sw[0] * (int)dq_s(0, rem) : dq_scale(0, rem);
                 v = qbits >= 0 ? v * (int)((unsigned)mf << qbits) : (v * mf + (1 << (-qbits - 1))) >> (-qbits);
                 v = (int)(int16_t)v;
             }
@@ -279,7 +286,8 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
 #pragma unroll
             for (int x = 0; x < 4; x++) { col[x][0] = is16 ? c16[x][0] : c4[x][0]; col[x][1] = is16 ? c16[x][1] : c4[x][1]; }
         }
-        dequant_cols(col, qp);
+        if (SC) scale_cols_w(col, qp, *(const uint4 *)sw);
+        else dequant_cols(col, qp);
         if (is16) col[0][0] = (col[0][0] & 0xffff0000u) | ((uint32_t)dcv & 0xffffu);
         idct_res(col, r);
         const bool mine = coded || dcflag;
@@ -307,7 +315,7 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
                     for (int i = 0; i < 8; i++) {
                         const int c = (i & 1) ? (int)lw[i >> 1] >> 16 : (int)(int16_t)(lw[i >> 1] & 0xffffu);
                         const int p = (int)(((i < 4 ? sc.x : sc.y) >> (8 * (i & 3))) & 63u);
-                        t8[p] = t8_scale(c, p, vrow, per);
+                        t8[p] = SC ? t8_scale_w(c, p, vrow, per, (int)sw[SCL_8X8_AT + p]) : t8_scale(c, p, vrow, per);
                     }
                 }
                 wave_lds_fence();
@@ -483,7 +491,8 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
 // chroma of one intra macroblock per group of sixteen lanes: lane l = row r = l & 7 of plane p = l >> 3
 // (core/predict.c:199-361, decoder/macroblock.c:721-753,851-890)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, IntraGrp &L, int mbx, int mby, const uint4 rec, int l)
+template <bool SC>
+__device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, IntraGrp &L, const uint8_t *sw, int mbx, int mby, const uint4 rec, int l)
 {
     asm volatile("" : "+v"(l));                            // (as in intra_luma4)
     const int X0 = mbx * 8, Y0 = mby * 8;
@@ -527,7 +536,9 @@ __device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, I
             const uint32_t lv[8] = { la.x, la.y, la.z, la.w, lb.x, lb.y, lb.z, lb.w };
             uint32_t col[4][2], rr[4][2];
             unscan_cols<true>(lv, col);
-            dequant_cols(col, qpc);
+            const uint4 wr = SC ? *(const uint4 *)(sw + 16 + (l & 4) * 4) : make_uint4(0, 0, 0, 0);      // (lists 1, 2: the plane's own)
+            if (SC) scale_cols_w(col, qpc, wr);
+            else dequant_cols(col, qpc);
             // DC of block j: residual4x4.h's chroma_dc_level, written out (called from here, one add of the transform swaps its operands
             // in all four k_intra* kernels, whatever the form of its parameters)
             const int j = l & 3;
@@ -536,7 +547,8 @@ __device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, I
             int f = pick_addsub(t0, t1, t2, t3, j & 1, j & 2);                    // {t0+t2, t1+t3, t0-t2, t1-t3}[j]
             f = (int)(int16_t)f;
             const int per = (qpc * 43) >> 8, rem = qpc - per * 6;
-            const int dc = (f * (int)(dq_s(0, rem) << per)) >> 1;
+            // (SC: 8.5.11 with the list's weight at position 0, chroma_dc_level_w's last line)
+            const int dc = SC ? (int)((unsigned)(f * ((int)(wr.x & 255u) * (int)dq_s(0, rem))) << per) >> 5 : (f * (int)(dq_s(0, rem) << per)) >> 1;
             col[0][0] = (col[0][0] & 0xffff0000u) | ((uint32_t)dc & 0xffffu);
             idct_res(col, rr);
             uint4 *out = (uint4 *)(L.res + l * 16);
@@ -606,9 +618,9 @@ struct IntraShared {
     unsigned long long m_intra[INTRA_MASKS], m_walk[INTRA_MASKS];   // per row window: intra macroblocks / those left to the band walk
     int free_n[2];
 };
-template <bool I8>
+template <bool I8, bool SC = false>
 __device__ __forceinline__ void intra_picture(IntraShared &sh, uint32_t *lut8, const PicDev *__restrict__ pics, const Geom &g, int *status, const uint8_t *__restrict__ is_intra_all,
-                                              const int pic_index, const bool chroma_role)
+                                              const int pic_index, const bool chroma_role, uint8_t *sw = nullptr, const ScaleDev *__restrict__ scale = nullptr)
 {
     IntraSync &sync = sh.sync;
     uint32_t *lut = sh.lut;
@@ -626,6 +638,7 @@ __device__ __forceinline__ void intra_picture(IntraShared &sh, uint32_t *lut8, c
     const int n_bands = (g.mb_h + INTRA_BAND - 1) / INTRA_BAND;
     for (int i = threadIdx.x; i < INTRA_LUT_ENTRIES; i += blockDim.x) lut[i] = lut_entry(i >> 4, i & 3, (i >> 2) & 3);
     if (I8) for (int i = threadIdx.x; i < INTRA_LUT8_ENTRIES; i += blockDim.x) lut8[i] = lut8_entry(i >> 6, i & 7, (i >> 3) & 7);
+    if (SC) scaling_to_lds(sw, scale[pic_index].lists);     // (the picture's table, or the all-16 one of a flat picture)
     for (int i = threadIdx.x; i <= n_bands; i += blockDim.x) sync.progress[i] = 0;
     const int wins = (g.mb_w + 63) / 64, n_win = g.mb_h * wins;
     const bool use_free = pd->slice_type != P264_SLICE_I && n_win <= INTRA_MASKS && g.n_mb < 65536;     // (scalar)
@@ -709,8 +722,8 @@ __device__ __forceinline__ void intra_picture(IntraShared &sh, uint32_t *lut8, c
                     int mbx, mby;
                     split_mb(mbi, g, inv_mbw, mbx, mby);
                     if (active) {
-                        if (chroma_role) intra_chroma4(pd, g, L, mbx, mby, rec, l);
-                        else             intra_luma4<I8>(pd, g, L, lut, lut8, mbx, mby, rec, l);
+                        if (chroma_role) intra_chroma4<SC>(pd, g, L, sw, mbx, mby, rec, l);
+                        else             intra_luma4<I8, SC>(pd, g, L, lut, lut8, sw, mbx, mby, rec, l);
                     }
                     k = kn; mbi = mbi_n; rec = rec_n;
                 }
@@ -838,8 +851,8 @@ __device__ __forceinline__ void intra_picture(IntraShared &sh, uint32_t *lut8, c
             const uint4 rec = make_uint4(pick(srec[0].x, srec[1].x, srec[2].x, srec[3].x), pick(srec[0].y, srec[1].y, srec[2].y, srec[3].y),
                                          pick(srec[0].z, srec[1].z, srec[2].z, srec[3].z), pick(srec[0].w, srec[1].w, srec[2].w, srec[3].w));
             if (active) {
-                if (chroma_role) intra_chroma4(pd, g, L, mbx, R0 + grp, rec, l);
-                else             intra_luma4<I8>(pd, g, L, lut, lut8, mbx, R0 + grp, rec, l);
+                if (chroma_role) intra_chroma4<SC>(pd, g, L, sw, mbx, R0 + grp, rec, l);
+                else             intra_luma4<I8, SC>(pd, g, L, lut, lut8, sw, mbx, R0 + grp, rec, l);
             }
 #pragma unroll
             for (int r = 0; r < INTRA_BAND; r++) if (go[r]) todo[r] &= todo[r] - 1;
@@ -873,6 +886,26 @@ void k_intra_sparse_i8(const PicDev *__restrict__ pics, Geom g, int *status, con
     __shared__ uint32_t lut8[INTRA_LUT8_ENTRIES];
     const int pic = rfl((int)(blockIdx.x >> 1));
     intra_picture<true>(sh, lut8, pics, g, status, is_intra, pic, (blockIdx.x & 1) != 0);
+}
+// The scaled instances (intra_luma4<true, true>, intra_chroma4<true>): what a batch launches in place of the four kernels around here
+// when one of its pictures has scaling_lists.  Built with Intra 8x8 compiled in, bounded like the _i8 instances (128 registers); the
+// table of the workgroup's picture in LDS.  Like them the sparse one carries no edge-info role: such batches take k_deblock_bs.
+__global__ __launch_bounds__(INTRA_ROW_WAVES * 64, INTRA_I8_WAVES_PER_EU)
+void k_intra_scaled(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra, const ScaleDev *__restrict__ scale)
+{
+    __shared__ IntraShared sh;
+    __shared__ uint32_t lut8[INTRA_LUT8_ENTRIES];
+    __shared__ __attribute__((aligned(16))) uint8_t sw[P264HIP_SCALING_BYTES];
+    intra_picture<true, true>(sh, lut8, pics, g, status, is_intra, (int)blockIdx.x, blockIdx.y != 0, sw, scale);
+}
+__global__ __launch_bounds__(INTRA_ROW_WAVES * 64, INTRA_I8_WAVES_PER_EU)
+void k_intra_sparse_scaled(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra, const ScaleDev *__restrict__ scale)
+{
+    __shared__ IntraShared sh;
+    __shared__ uint32_t lut8[INTRA_LUT8_ENTRIES];
+    __shared__ __attribute__((aligned(16))) uint8_t sw[P264HIP_SCALING_BYTES];
+    const int pic = rfl((int)(blockIdx.x >> 1));            // (two workgroups per picture, as k_intra_sparse_i8)
+    intra_picture<true, true>(sh, lut8, pics, g, status, is_intra, pic, (blockIdx.x & 1) != 0, sw, scale);
 }
 #define INTRA_SPARSE_WAVES_PER_EU 8
 // The sparse build also carries the loop filter's EDGE INFO pass (kernel_deblock.h, K4a) as a third role: that pass is bound

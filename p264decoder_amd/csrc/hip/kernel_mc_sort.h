@@ -3,6 +3,7 @@
 #pragma once
 #include "device_common.h"
 #include "wavefront_sync.h"          // (MAX_MB_ROWS: the row field of a list entry)
+#include "kernel_scaling.h"          // (ScaleDev: which pictures of the batch k_mc_sort_scaled files without residuals)
 
 // ------------------------------------------------------------------------------------------
 // work lists
@@ -153,8 +154,10 @@ __device__ __forceinline__ McIn mc_load(const PicDev *pd, int mbi)
     }
     return in;
 }
+// scaled (k_mc_sort_scaled only): the picture has scaling_lists - luma and chroma of its macroblocks are filed as "no residual", the
+// motion-compensation kernels leave the clipped prediction and k_scaled_inter adds the residual behind them (kernel_scaling.h)
 template <bool BPIC, bool WP>
-__device__ __forceinline__ McMb mc_classify(const PicDev *pd, const Geom &g, const McIn &in, int mbi, uint32_t inv_mbw, int band_log2, int pass)
+__device__ __forceinline__ McMb mc_classify(const PicDev *pd, const Geom &g, const McIn &in, int mbi, uint32_t inv_mbw, int band_log2, int pass, const bool scaled = false)
 {
     McMb k;
     const uint4 rec = in.rec;
@@ -166,9 +169,9 @@ __device__ __forceinline__ McMb mc_classify(const PicDev *pd, const Geom &g, con
     int mbx, mby;
     split_mb(mbi, g, inv_mbw, mbx, mby);
     const int band = mby >> band_log2;
-    const unsigned cc = rec.y & (0x00ff0000u | P264_COEF_CHROMA_DC);   // any chroma level present
+    const unsigned cc = scaled ? 0u : rec.y & (0x00ff0000u | P264_COEF_CHROMA_DC);   // any chroma level present
     // (a macroblock with P264_MB_T8X8: its luma items are filed as "no residual" - k_t8x8 adds it behind this stage, kernel_t8x8.h)
-    const unsigned mask = ((rec.x >> 24) & P264_MB_T8X8) ? (rec.y & ~0xffffu) : rec.y;
+    const unsigned mask = scaled ? 0u : ((rec.x >> 24) & P264_MB_T8X8) ? (rec.y & ~0xffffu) : rec.y;
     if (WP && pd->explicit_wp) {
         // explicit weighted prediction (wave-uniform: a picture per workgroup; compiled into the k_mc_sort*_wp instances only): every inter macroblock goes to the generic two-list
         // class, all four quadrants, first pass - its lanes look up their lists, indices and weights themselves (mc_luma_body /
@@ -303,7 +306,7 @@ __device__ __forceinline__ void scatter_split_mb(int mbi, const Geom &g, uint32_
     if (mbi - mby * g.mb_w >= g.mb_w) mby++;
     mbx = mbi - mby * g.mb_w;
 }
-__device__ __forceinline__ void mc_scatter(const McSortCtx &c, const McMb &k, int mbi, const Geom &g, uint32_t inv_mbw)
+__device__ __forceinline__ void mc_scatter(const McSortCtx &c, const McMb &k, int mbi, const Geom &g, uint32_t inv_mbw, const bool scaled = false)
 {
     if (!(k.info & MCMB_INTER)) return;
     int mbx, mby;
@@ -328,7 +331,7 @@ __device__ __forceinline__ void mc_scatter(const McSortCtx &c, const McMb &k, in
     // second pass: the record's residual fields and the weight of the pair of references (the table the parser derived,
     // core/macroblock.c:525-583; 32 = plain average) ride in the entry
     const uint4 rec = gload4(c.pd->mb + mbi);              // (second look at the record: out of the cache)
-    const uint32_t ez = mce2_z(rec.y, (rec.x >> 8) & 63u);
+    const uint32_t ez = mce2_z(scaled ? 0u : rec.y, (rec.x >> 8) & 63u);      // (a scaled picture: no residual field anywhere, as in the first pass's keys)
     // (luma entries of a P264_MB_T8X8 macroblock: no coded block; the chroma entries keep the bits - they count them to find their levels)
     const uint32_t ezy = ((rec.x >> 24) & P264_MB_T8X8) ? (ez & ~0xffffu) : ez;
     uint32_t ew[4];
@@ -363,7 +366,7 @@ __device__ __forceinline__ void mc_scatter(const McSortCtx &c, const McMb &k, in
 // twice - keeping two classifications of eight macroblocks does not fit the register file).
 template <bool BPIC, bool WP>
 __device__ __forceinline__ void mc_sort_picture(const PicDev *__restrict__ pics, uint32_t *__restrict__ mc_all, const Geom &g, const McLayout &ml, uint32_t inv_mbw,
-                                                uint32_t *cnt, uint32_t *pos, uint8_t *__restrict__ is_intra_all)
+                                                uint32_t *cnt, uint32_t *pos, uint8_t *__restrict__ is_intra_all, const bool scaled = false)
 {
     // by-product for the intra stage (k_intra's collect pass): one byte per macroblock, 1 = intra
     AS1 uint8_t *is_intra = glob(is_intra_all + (size_t)blockIdx.x * g.n_mb);
@@ -391,7 +394,7 @@ __device__ __forceinline__ void mc_sort_picture(const PicDev *__restrict__ pics,
             const int mbi = tid + j * MC_SORT_THREADS;
             kept[j].info = 0;
             if (mbi < g.n_mb) {
-                kept[j] = mc_classify<BPIC, WP>(pd, g, mc_load<BPIC>(pd, mbi), mbi, inv_mbw, (int)ml.band_log2, 0); mc_count(ctx[0], kept[j]);
+                kept[j] = mc_classify<BPIC, WP>(pd, g, mc_load<BPIC>(pd, mbi), mbi, inv_mbw, (int)ml.band_log2, 0, scaled); mc_count(ctx[0], kept[j]);
                 is_intra[mbi] = (uint8_t)!(kept[j].info & MCMB_INTER);
             }
         }
@@ -400,7 +403,7 @@ __device__ __forceinline__ void mc_sort_picture(const PicDev *__restrict__ pics,
             const McIn in = mc_load<BPIC>(pd, mbi);
             is_intra[mbi] = (uint8_t)(P264_MB_IS_INTRA(in.rec.x & 255) != 0);
 #pragma unroll
-            for (int ps = 0; ps < NP; ps++) if (ps < n_pass) mc_count(ctx[ps], mc_classify<BPIC, WP>(pd, g, in, mbi, inv_mbw, (int)ml.band_log2, ps));
+            for (int ps = 0; ps < NP; ps++) if (ps < n_pass) mc_count(ctx[ps], mc_classify<BPIC, WP>(pd, g, in, mbi, inv_mbw, (int)ml.band_log2, ps, scaled));
         }
     }
     __syncthreads();
@@ -430,12 +433,12 @@ __device__ __forceinline__ void mc_sort_picture(const PicDev *__restrict__ pics,
     __syncthreads();
     if (keep) {
 #pragma unroll
-        for (int j = 0; j < (BPIC ? 1 : MC_SORT_KEEP); j++) mc_scatter(ctx[0], kept[j], tid + j * MC_SORT_THREADS, g, inv_mbw);
+        for (int j = 0; j < (BPIC ? 1 : MC_SORT_KEEP); j++) mc_scatter(ctx[0], kept[j], tid + j * MC_SORT_THREADS, g, inv_mbw, scaled);
     } else {
         for (int mbi = tid; mbi < g.n_mb; mbi += MC_SORT_THREADS) {
             const McIn in = mc_load<BPIC>(pd, mbi);
 #pragma unroll
-            for (int ps = 0; ps < NP; ps++) if (ps < n_pass) mc_scatter(ctx[ps], mc_classify<BPIC, WP>(pd, g, in, mbi, inv_mbw, (int)ml.band_log2, ps), mbi, g, inv_mbw);
+            for (int ps = 0; ps < NP; ps++) if (ps < n_pass) mc_scatter(ctx[ps], mc_classify<BPIC, WP>(pd, g, in, mbi, inv_mbw, (int)ml.band_log2, ps, scaled), mbi, g, inv_mbw, scaled);
         }
     }
     __syncthreads();
@@ -487,4 +490,21 @@ void k_mc_sort_b_wp(const PicDev *__restrict__ pics, uint32_t *__restrict__ mc_a
 {
     __shared__ uint32_t cnt[2 * MC_KEY_SLOTS], pos[2 * MC_KEY_SLOTS];
     mc_sort_picture<true, true>(pics, mc_all, g, ml, inv_mbw, cnt, pos, is_intra);
+}
+// batches with a picture that has scaling_lists: the residuals of such a picture's inter macroblocks are left to k_scaled_inter.
+// scale[picture].scaled is per workgroup.  Two instances: batches of unweighted P (and I) pictures - k_mc_sort's shape, the
+// classification kept in registers -, and every other batch - the two-list, weighted instance.
+__global__ __launch_bounds__(MC_SORT_THREADS)
+void k_mc_sort_scaled_p(const PicDev *__restrict__ pics, uint32_t *__restrict__ mc_all, Geom g, McLayout ml, uint32_t inv_mbw, uint8_t *__restrict__ is_intra,
+                        const ScaleDev *__restrict__ scale)
+{
+    __shared__ uint32_t cnt[MC_KEY_SLOTS], pos[MC_KEY_SLOTS];
+    mc_sort_picture<false, false>(pics, mc_all, g, ml, inv_mbw, cnt, pos, is_intra, scale[blockIdx.x].scaled != 0);
+}
+__global__ __launch_bounds__(MC_SORT_THREADS, MC_SORT_B_WAVES_PER_EU)
+void k_mc_sort_scaled(const PicDev *__restrict__ pics, uint32_t *__restrict__ mc_all, Geom g, McLayout ml, uint32_t inv_mbw, uint8_t *__restrict__ is_intra,
+                      const ScaleDev *__restrict__ scale)
+{
+    __shared__ uint32_t cnt[2 * MC_KEY_SLOTS], pos[2 * MC_KEY_SLOTS];
+    mc_sort_picture<true, true>(pics, mc_all, g, ml, inv_mbw, cnt, pos, is_intra, scale[blockIdx.x].scaled != 0);
 }

@@ -20,6 +20,7 @@
 #include "kernel_mc.h"
 #include "kernel_intra.h"
 #include "kernel_t8x8.h"
+#include "kernel_scaling.h"
 #include "kernel_expand.h"
 #include "kernel_export.h"
 
@@ -114,6 +115,10 @@ struct p264hip_ctx {
     size_t frame_bytes = 0;
     std::vector<PicSlot> pics;
     PicDev *h_batch[BATCH_RING] = {}, *d_batch[BATCH_RING] = {};
+    // pictures with scaling_lists: one ScaleDev per picture of the batch beside its PicDev (copied only for batches that hold such a
+    // picture), and the all-16 table the batch's flat pictures point to
+    ScaleDev *h_scale[BATCH_RING] = {}, *d_scale[BATCH_RING] = {};
+    uint8_t *d_flat16 = nullptr;
     hipEvent_t batch_free[BATCH_RING] = {};
     int batch_cap = 0, ring = 0;
     int *d_status = nullptr;
@@ -201,6 +206,8 @@ extern "C" int p264hip_create(p264hip_ctx **out, int device, int mb_w, int mb_h,
     if (e == hipSuccess) e = hipMemsetAsync(c->d_status, 0, sizeof(int), c->stream);
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_slot_bad, sizeof(int) * (size_t)max_pictures);
     if (e == hipSuccess) e = hipMemsetAsync(c->d_slot_bad, 0, sizeof(int) * (size_t)max_pictures, c->stream);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_flat16, 256);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_flat16, 16, 256, c->stream);                 // (Flat_4x4_16 / Flat_8x8_16: every weight 16)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         int rc = fail(e == hipErrorOutOfMemory ? P264HIP_ENOMEM : P264HIP_EHIP, "p264hip_create: %s", hipGetErrorString(e));
@@ -226,6 +233,8 @@ extern "C" void p264hip_destroy(p264hip_ctx *c)
     for (int i = 0; i < BATCH_RING; i++) {
         if (c->h_batch[i]) (void)hipHostFree(c->h_batch[i]);
         if (c->d_batch[i]) (void)hipFree(c->d_batch[i]);
+        if (c->h_scale[i]) (void)hipHostFree(c->h_scale[i]);
+        if (c->d_scale[i]) (void)hipFree(c->d_scale[i]);
         if (c->batch_free[i]) (void)hipEventDestroy(c->batch_free[i]);
     }
     for (int i = 0; i < BATCH_RING; i++) {
@@ -244,6 +253,7 @@ extern "C" void p264hip_destroy(p264hip_ctx *c)
     for (auto &m : c->markers) if (m) (void)hipEventDestroy(m);
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->d_slot_bad) (void)hipFree(c->d_slot_bad);
+    if (c->d_flat16) (void)hipFree(c->d_flat16);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -363,7 +373,7 @@ static int expand_launch(p264hip_ctx *c)
     for (int i = 0; i < n; i++) {
         PicSlot &s = c->pics[(size_t)c->pending[(size_t)i]];
         c->h_jobs[i] = ExpandJob{ s.stage, s.dev, (uint32_t)s.L.off_mv, (uint32_t)s.L.off_ref, (uint32_t)s.L.off_i4, (uint32_t)s.L.off_coef,
-                                  (uint32_t)s.L.off_mv_l1, (uint32_t)s.L.off_ref_l1, (uint32_t)s.L.off_weights, (uint32_t)s.L.off_wp };
+                                  (uint32_t)s.L.off_mv_l1, (uint32_t)s.L.off_ref_l1, (uint32_t)s.L.off_weights, (uint32_t)s.L.off_wp, (uint32_t)s.L.off_scaling };
         stamp(c, s);
     }
     for (int i = 0; i < COPY_STREAMS; i++) {                 // the blocks' copies (side streams) in front of the kernel that reads them
@@ -420,7 +430,10 @@ extern "C" int p264hip_upload_async(p264hip_ctx *c, int id, const p264hip_pictur
             HIPCHK(hipMemcpyAsync(s.dev + L.off_coef, p->coefs, (size_t)p->n_coef_blocks * 32, hipMemcpyHostToDevice, c->stream));
     }
     if (p->explicit_wp) HIPCHK(hipMemcpyAsync(s.dev + L.off_wp, p->wp, sizeof p->wp, hipMemcpyHostToDevice, c->stream));
-    c->upload_copies += (as_slot ? 1 : 5) + (p->explicit_wp ? 1 : 0);
+    // (scaling4x4 and scaling8x8 lie back to back in the descriptor, as they do in the slot)
+    static_assert(offsetof(p264hip_picture_t, scaling8x8) == offsetof(p264hip_picture_t, scaling4x4) + sizeof p->scaling4x4 && sizeof p->scaling4x4 + sizeof p->scaling8x8 == P264HIP_SCALING_BYTES, "the scaling table");
+    if (p->scaling_lists) HIPCHK(hipMemcpyAsync(s.dev + L.off_scaling, p->scaling4x4, P264HIP_SCALING_BYTES, hipMemcpyHostToDevice, c->stream));
+    c->upload_copies += (as_slot ? 1 : 5) + (p->explicit_wp ? 1 : 0) + (p->scaling_lists ? 1 : 0);
     slot_exit(c, id, *p, READY);
     return P264HIP_OK;
 }
@@ -745,7 +758,9 @@ static int batch_reserve(p264hip_ctx *c, int n)
     c->batch_cap = 0;
     for (int i = 0; i < BATCH_RING; i++) {
         int rc = grow(c, (void **)&c->h_batch[i], nullptr, (size_t)n * sizeof(PicDev), 0, true, WAIT_NONE, "the batch");
-        if (rc || (rc = grow(c, (void **)&c->d_batch[i], nullptr, (size_t)n * sizeof(PicDev), 0, false, WAIT_NONE, "the batch"))) return rc;
+        if (rc || (rc = grow(c, (void **)&c->d_batch[i], nullptr, (size_t)n * sizeof(PicDev), 0, false, WAIT_NONE, "the batch")) ||
+            (rc = grow(c, (void **)&c->h_scale[i], nullptr, (size_t)n * sizeof(ScaleDev), 0, true, WAIT_NONE, "the batch")) ||
+            (rc = grow(c, (void **)&c->d_scale[i], nullptr, (size_t)n * sizeof(ScaleDev), 0, false, WAIT_NONE, "the batch"))) return rc;
         if (!c->batch_free[i]) HIPCHK(hipEventCreateWithFlags(&c->batch_free[i], hipEventDisableTiming));
         HIPCHK(hipEventRecord(c->batch_free[i], c->stream));
     }
@@ -818,11 +833,12 @@ static PicDev picdev_of(p264hip_ctx *c, const PicSlot &s, int st)
 
 // What the batch holds - the kernel instances and launch shapes follow from it: any picture with inter macroblocks / any B picture /
 // any I picture / any explicit weights / any unweighted P picture whose list 0 holds one frame at several indices / any picture
-// whose inter macroblocks may use the 8x8 transform / any picture whose Intra4x4 records may carry P264_MB_I8X8
-struct BatchKinds { bool p = false, b = false, i = false, wp = false, dup = false, t8 = false, i8 = false; };
+// whose inter macroblocks may use the 8x8 transform / any picture whose Intra4x4 records may carry P264_MB_I8X8; sc: how many
+// pictures have scaling_lists
+struct BatchKinds { bool p = false, b = false, i = false, wp = false, dup = false, t8 = false, i8 = false; int sc = 0; };
 
 // the batch's streams and slots checked (nothing is queued yet), one PicDev per picture in hb
-static int batch_fill(p264hip_ctx *c, const int *pic_ids, const int *streams, int n, PicDev *hb, BatchKinds *kinds)
+static int batch_fill(p264hip_ctx *c, const int *pic_ids, const int *streams, int n, PicDev *hb, ScaleDev *hs, BatchKinds *kinds)
 {
     for (int i = 0; i < n; i++) {                          // two pictures of one call must not share a stream: they would race on its frames
         const int st = streams[i];
@@ -844,6 +860,9 @@ static int batch_fill(p264hip_ctx *c, const int *pic_ids, const int *streams, in
         k.dup |= hb[i].dup_refs != 0;
         k.t8 |= (s.meta.transform_8x8 & ~P264_T8X8_INTRA) != 0 && s.meta.slice_type != P264_SLICE_I;
         k.i8 |= (s.meta.transform_8x8 & P264_T8X8_INTRA) != 0;
+        // the picture's table in its slot; a flat picture: the all-16 table (what a batch with a scaled picture runs it through)
+        hs[i] = ScaleDev{ s.meta.scaling_lists ? s.dev + s.L.off_scaling : c->d_flat16, s.meta.scaling_lists ? 1 : 0, 0 };
+        k.sc += s.meta.scaling_lists != 0;
     }
     *kinds = k;
     return 0;
@@ -881,7 +900,7 @@ static int intra_waves(const p264hip_ctx *c, int n)
 // (k_deblock_bs)
 static int edge_info_fused(const p264hip_ctx *c, const BatchKinds &k)
 {
-    if (k.i || k.b || k.wp || k.dup || k.t8 || k.i8 || c->tune_bs_fused == 0) return 0;
+    if (k.i || k.b || k.wp || k.dup || k.t8 || k.i8 || k.sc || c->tune_bs_fused == 0) return 0;
     return c->tune_bs_fused > 0 ? c->tune_bs_fused : INTRA_BS_WGS;
 }
 
@@ -928,11 +947,14 @@ static uint32_t inv_mb_w(const p264hip_ctx *c) { return (uint32_t)(((1ull << 32)
 
 // motion compensation + residual of all inter macroblocks: device-side counting sort of the work items by what the
 // interpolation has to do, then the luma and chroma kernels over the sorted lists (kernel_mc.h), side by side
-static void launch_inter(p264hip_ctx *c, const PicDev *batch, int n, const BatchKinds &k)
+static void launch_inter(p264hip_ctx *c, const PicDev *batch, const ScaleDev *scale, int n, const BatchKinds &k)
 {
     ScopedStamp t(c, 0);
     const Geom g = c->g;
     const McLayout ml = c->ml;
+    // (a picture with scaling_lists in the batch: the instance that files such a picture's residuals as absent - k_scaled_inter adds them)
+    if (k.sc) hipLaunchKernelGGL((k.b || k.wp) ? k_mc_sort_scaled : k_mc_sort_scaled_p, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, batch, c->d_mc, g, ml, inv_mb_w(c), c->d_is_intra, scale);
+    else
     // (explicit weighted prediction in the batch: the instances that route such pictures to the weighted class, kernel_mc_sort.h)
     if (k.b) hipLaunchKernelGGL(k.wp ? k_mc_sort_b_wp : k_mc_sort_b, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, batch, c->d_mc, g, ml, inv_mb_w(c), c->d_is_intra);
     else hipLaunchKernelGGL(k.wp ? k_mc_sort_wp : k_mc_sort, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, batch, c->d_mc, g, ml, inv_mb_w(c), c->d_is_intra);
@@ -958,10 +980,28 @@ static void launch_t8x8(p264hip_ctx *c, const PicDev *batch, int n)
     hipLaunchKernelGGL(k_t8x8, dim3((unsigned)per_pic, (unsigned)n), dim3(T8_THREADS), 0, c->stream, batch, c->g);
 }
 
-static void launch_intra(p264hip_ctx *c, const PicDev *batch, int n, const BatchKinds &k)
+// the residual of the inter macroblocks of the batch's scaled pictures, and the 8x8 blocks of every picture of the batch
+// (kernel_scaling.h), where launch_t8x8 runs in other batches.  Counts as inter time.
+static void launch_scaled_inter(p264hip_ctx *c, const PicDev *batch, const ScaleDev *scale, int n)
+{
+    ScopedStamp t(c, 0);
+    const int per_pic = (c->g.n_mb + SCL_MBS_PER_WG - 1) / SCL_MBS_PER_WG;
+    hipLaunchKernelGGL(k_scaled_inter, dim3((unsigned)per_pic, (unsigned)n), dim3(SCL_THREADS), 0, c->stream, batch, scale, c->g);
+}
+
+static void launch_intra(p264hip_ctx *c, const PicDev *batch, const ScaleDev *scale, int n, const BatchKinds &k)
 {
     ScopedStamp t(c, 1);
     const int waves = c->last.intra_waves = intra_waves(c, n);
+    // (a picture of the batch has scaling_lists: the instances that scale with the table - kernel_intra.h; they know Intra 8x8, and
+    // the edge info has its own launch)
+    if (k.sc) {
+        c->last.intra_i8 = k.i8 ? 1 : 0;
+        if (k.i) hipLaunchKernelGGL(k_intra_scaled, dim3(n, 2), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status, (const uint8_t *)c->d_is_intra, scale);
+        else hipLaunchKernelGGL(k_intra_sparse_scaled, dim3((unsigned)n * 2), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status,
+                                (const uint8_t *)c->d_is_intra, scale);
+        return;
+    }
     // (a picture of the batch may hold Intra 8x8 macroblocks: the instances that know them - kernel_intra.h; the edge info then has
     // its own launch, edge_info_fused)
     if (k.i8) {
@@ -1006,7 +1046,7 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     const int r = c->ring; c->ring = (c->ring + 1) % BATCH_RING;
     HIPCHK(hipEventSynchronize(c->batch_free[r]));            // the copy that last used this staging buffer is done
     BatchKinds k;
-    if ((rc = batch_fill(c, pic_ids, streams, n, c->h_batch[r], &k))) return rc;
+    if ((rc = batch_fill(c, pic_ids, streams, n, c->h_batch[r], c->h_scale[r], &k))) return rc;
     // from here on work that reads the batch's input slots is (about to be) queued: the slots carry the new epoch BEFORE the first
     // launch, so that whichever way this function returns - a launch error half-way included - a later p264hip_input_reserve
     // of one of them waits for the stream instead of letting a peer overwrite a block under running kernels
@@ -1014,12 +1054,14 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     for (int i = 0; i < n; i++) stamp(c, c->pics[(size_t)pic_ids[i]]);
     ScopedStamp whole(c, 3);
     HIPCHK(hipMemcpyAsync(c->d_batch[r], c->h_batch[r], (size_t)n * sizeof(PicDev), hipMemcpyHostToDevice, c->stream));
+    if (k.sc) HIPCHK(hipMemcpyAsync(c->d_scale[r], c->h_scale[r], (size_t)n * sizeof(ScaleDev), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->batch_free[r], c->stream));
     memset(&c->last, 0, sizeof c->last);
-    c->last.pictures = n; c->last.compute_units = c->n_cu;
-    if (k.p) launch_inter(c, c->d_batch[r], n, k);
-    if (k.t8) launch_t8x8(c, c->d_batch[r], n);
-    launch_intra(c, c->d_batch[r], n, k);
+    c->last.pictures = n; c->last.compute_units = c->n_cu; c->last.scaled_pictures = k.sc;
+    if (k.p) launch_inter(c, c->d_batch[r], c->d_scale[r], n, k);
+    if (k.sc) { if (k.p) launch_scaled_inter(c, c->d_batch[r], c->d_scale[r], n); }     // (it owns the batch's 8x8 blocks too: no k_t8x8 beside it)
+    else if (k.t8) launch_t8x8(c, c->d_batch[r], n);
+    launch_intra(c, c->d_batch[r], c->d_scale[r], n, k);
     launch_deblock(c, c->d_batch[r], n, k);
     HIPCHK(hipGetLastError());
     return P264HIP_OK;

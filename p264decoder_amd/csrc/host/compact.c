@@ -14,7 +14,7 @@ size_t p264hip_compact_bound(const p264hip_picture_t *p)
     if (!p || p->mb_w < 1 || p->mb_h < 1) return 0;
     const size_t n = (size_t)p->mb_w * (size_t)p->mb_h, lists = p->slice_type == P264_SLICE_B ? 2 : 1;
     return sizeof(p264hip_compact_hdr_t) + n * 16 + 16 + lists * (n * 4 + 16 + n / 4 + 32 + n * 64 + 16) + n / 8 + 32 + n * 16 + 16
-           + (size_t)p->n_coef_blocks / 8 + 32 + (size_t)p->n_coef_blocks * 32 + 64 + 512 + 64 + (p->explicit_wp ? sizeof p->wp + 16 : 0);
+           + (size_t)p->n_coef_blocks / 8 + 32 + (size_t)p->n_coef_blocks * 32 + 64 + 512 + 64 + (p->explicit_wp ? sizeof p->wp + 16 : 0) + (p->scaling_lists ? P264HIP_SCALING_BYTES + 16 : 0);
 }
 
 /* 0 sixteen zero vectors, 1 one vector, 2 one per 8x8 quadrant, 3 sixteen */
@@ -107,6 +107,12 @@ int64_t p264hip_pack_compact(const p264hip_picture_t *p, void *dst_, size_t cap)
     at = up16(at + used) + 32;
     if (isB) { h.off_weights = at; memcpy(dst + at, p->bipred_weight, 512); at += 512; }
     if (p->explicit_wp) { h.off_wp = at; memcpy(dst + at, p->wp, sizeof p->wp); at += (uint32_t)sizeof p->wp; }     /* (384: stays 16-byte aligned) */
+    if (p->scaling_lists) {                                   /* (224 bytes: stays 16-byte aligned) */
+        h.off_scaling = at;
+        memcpy(dst + at, p->scaling4x4, sizeof p->scaling4x4);
+        memcpy(dst + at + sizeof p->scaling4x4, p->scaling8x8, sizeof p->scaling8x8);
+        at += P264HIP_SCALING_BYTES;
+    }
     h.bytes = at;
     memcpy(dst, &h, sizeof h);
     return (int64_t)h.bytes;
@@ -147,11 +153,13 @@ int p264hip_compact_header_ok(const p264hip_picture_t *d, const void *compact, s
     at = (uint64_t)h.off_lvflag + (h.n_coef_blocks + 7) / 8;
     if (h.off_levels < at) return 0;
     at = (uint64_t)h.off_levels + h.level_bytes + 32;
-    if ((h.off_i4flag | h.off_i4 | h.off_lvflag | h.off_levels | h.off_weights | h.off_wp) & 15u) return 0;
+    if ((h.off_i4flag | h.off_i4 | h.off_lvflag | h.off_levels | h.off_weights | h.off_wp | h.off_scaling) & 15u) return 0;
     if (h.n_lists == 2) { if (h.off_weights < at) return 0; at = (uint64_t)h.off_weights + 512; }
     else if (h.off_weights) return 0;
     if (d->explicit_wp) { if (h.off_wp < at) return 0; at = (uint64_t)h.off_wp + sizeof d->wp; }
     else if (h.off_wp) return 0;
+    if (d->scaling_lists) { if (h.off_scaling < at) return 0; at = (uint64_t)h.off_scaling + P264HIP_SCALING_BYTES; }
+    else if (h.off_scaling) return 0;
     return at <= h.bytes;
 }
 
@@ -226,5 +234,6 @@ int p264hip_expand_compact(const p264hip_picture_t *d, const void *compact, size
     }
     if (h.n_lists == 2) memcpy(out + L.off_weights, b + h.off_weights, 512);
     if (h.off_wp) memcpy(out + L.off_wp, b + h.off_wp, sizeof d->wp);
+    if (h.off_scaling) memcpy(out + L.off_scaling, b + h.off_scaling, P264HIP_SCALING_BYTES);
     return P264HIP_OK;
 }

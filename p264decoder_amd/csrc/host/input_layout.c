@@ -28,6 +28,10 @@ int p264hip_input_layout(const p264hip_picture_t *d, p264hip_input_layout_t *o)
         o->off_wp = end;
         end += up256(sizeof d->wp);
     }
+    if (d->scaling_lists) {                                                     /* (flat pictures: the layout of before, byte for byte) */
+        o->off_scaling = end;
+        end += up256(P264HIP_SCALING_BYTES);
+    }
     o->bytes = end;
     return P264HIP_OK;
 }
@@ -57,6 +61,10 @@ int64_t p264hip_pack_input(const p264hip_picture_t *p, void *dst_, size_t cap)
     if (p->explicit_wp) {
         if (p264hip_wp_check(p)) return P264HIP_EINVAL;
         memcpy(dst + L.off_wp, p->wp, sizeof p->wp);
+    }
+    if (p->scaling_lists) {                                                     /* scaling4x4 then scaling8x8: contiguous in the descriptor too */
+        memcpy(dst + L.off_scaling, p->scaling4x4, sizeof p->scaling4x4);
+        memcpy(dst + L.off_scaling + sizeof p->scaling4x4, p->scaling8x8, sizeof p->scaling8x8);
     }
     return (int64_t)L.bytes;
 }
@@ -130,5 +138,9 @@ int p264hip_unpack_input(const p264hip_picture_t *desc, const void *packed, size
         pic->ref_idx_l1 = (const int8_t *)(b + L.off_ref_l1);
     }
     if (desc->explicit_wp) memcpy(pic->wp, b + L.off_wp, sizeof pic->wp);     /* the table the block carries (what the kernels read) */
+    if (desc->scaling_lists) {                                                /* and the block's scaling lists */
+        memcpy(pic->scaling4x4, b + L.off_scaling, sizeof pic->scaling4x4);
+        memcpy(pic->scaling8x8, b + L.off_scaling + sizeof pic->scaling4x4, sizeof pic->scaling8x8);
+    }
     return P264HIP_OK;
 }

@@ -31,6 +31,12 @@
 #define NAL_SPS       7
 #define NAL_PPS       8
 
+/* scaling matrices (7.3.2.1.1.1, 7.4.2.1.1; P264PARSE_OPT_SCALING).  One scaling_list( ) as coded: present, with
+ * useDefaultScalingMatrixFlag, or its values in scan order; a parameter set's matrix: the lists it codes (SPS: 8; PPS: 6, and 2
+ * more with transform_8x8_mode_flag).  What a list that is absent or says "default" stands for is table 7-2's (cqm_resolve). */
+typedef struct { uint8_t present, use_default, v[64]; } cqm_list_t;
+typedef struct { uint8_t l4[6][16], l8[2][64]; } cqm_t;      /* eight resolved lists, scan order: the table of p264hip_picture_t */
+
 typedef struct {
     int valid, profile_idc, level_idc;
     int log2_max_frame_num, poc_type, log2_max_poc_lsb;
@@ -38,6 +44,7 @@ typedef struct {
     int num_ref_frames, gaps_allowed, mb_w, mb_h, frame_mbs_only, direct_8x8_inference;
     int crop[4];
     int high;                                        /* one of the profiles whose SPS and PPS carry the High extensions (sps_is_high) */
+    int cqm; cqm_t lists;                            /* seq_scaling_matrix_present_flag, and its lists resolved with fall-back rule A */
 } sps_t;
 
 typedef struct {
@@ -46,6 +53,9 @@ typedef struct {
     int pic_init_qp, chroma_qp_offset, deblock_ctrl, constrained_intra, redundant_pic_cnt;
     /* what follows while more_rbsp_data( ) (7.3.2.2), as read; honoured only by slices whose SPS is a High one (open_slice) */
     int ext, t8x8_mode, scaling_matrix, second_chroma_qp_offset;
+    /* P264PARSE_OPT_SCALING: the PPS's lists as coded - which rule resolves them depends on the SPS, known at activation - and
+     * whether the extension ended inside them (a complaint that waits for the activation by a slice of a High-profile SPS too) */
+    cqm_list_t cqm[8]; int cqm_read, ext_short;
 } pps_t;
 
 typedef struct {
@@ -95,6 +105,7 @@ typedef struct {
     int16_t bipred_weight[P264HIP_MAX_REFS * P264HIP_MAX_REFS];   /* implicit weights (8.4.2.3.1) */
     int t8x8;                                 /* a slice of the picture had transform_8x8_mode_flag: its inter records may carry P264_MB_T8X8 */
     int i8x8;                                 /* the picture holds at least one Intra 8x8 record (P264_MB_I8X8) */
+    int cqm; cqm_t lists;                     /* the picture's resolved scaling lists (its first slice's; cqm 0: every weight is 16) */
 } curpic_t;
 
 struct p264parse {
@@ -166,6 +177,53 @@ static int sps_is_high(int profile)
     return profile == 100 || profile == 110 || profile == 122 || profile == 244 || profile == 44 || profile == 83 || profile == 86 ||
            profile == 118 || profile == 128;
 }
+/* tables 7-3 and 7-4, scan order */
+static const uint8_t cqm_default4[2][16] = {
+    { 6, 13, 13, 20, 20, 20, 28, 28, 28, 28, 32, 32, 32, 37, 37, 42 }, { 10, 14, 14, 20, 20, 20, 24, 24, 24, 24, 27, 27, 27, 30, 30, 34 } };
+static const uint8_t cqm_default8[2][64] = {
+    { 6, 10, 10, 13, 11, 13, 16, 16, 16, 16, 18, 18, 18, 18, 18, 23, 23, 23, 23, 23, 23, 25, 25, 25, 25, 25, 25, 25, 27, 27, 27, 27, 27, 27, 27, 27,
+      29, 29, 29, 29, 29, 29, 29, 31, 31, 31, 31, 31, 31, 33, 33, 33, 33, 33, 36, 36, 36, 36, 38, 38, 38, 40, 40, 42 },
+    { 9, 13, 13, 15, 13, 15, 17, 17, 17, 17, 19, 19, 19, 19, 19, 21, 21, 21, 21, 21, 21, 22, 22, 22, 22, 22, 22, 22, 24, 24, 24, 24, 24, 24, 24, 24,
+      25, 25, 25, 25, 25, 25, 25, 27, 27, 27, 27, 27, 27, 28, 28, 28, 28, 28, 30, 30, 30, 30, 32, 32, 32, 33, 33, 35 } };
+/* scaling_list( ) (7.3.2.1.1.1) behind its present flag: nextScale = (lastScale + delta_scale + 256) % 256; a first nextScale of 0
+ * is useDefaultScalingMatrixFlag, a later one ends the list - the remaining positions repeat lastScale */
+static void cqm_read_list(bitrd_t *b, int size, cqm_list_t *o)
+{
+    memset(o, 0, sizeof *o);
+    o->present = (uint8_t)br_u1(b);
+    if (!o->present) return;
+    int last = 8, next = 8;
+    for (int j = 0; j < size; j++) {
+        if (next != 0) {
+            next = (int)((unsigned)(last + br_se(b)) & 255u);
+            if (j == 0 && next == 0) o->use_default = 1;
+        }
+        o->v[j] = (uint8_t)(next == 0 ? last : next);
+        last = o->v[j];
+    }
+}
+/* table 7-2: the eight lists of a set that codes the first `coded` of them.  fb = NULL: fall-back rule A (an absent list 0 / 3 / 6 / 7
+ * takes its default); fb = the SPS's resolved lists: rule B (... takes the SPS's list of that number).  Either way an absent list
+ * 1, 2, 4, 5 takes the list before it, and useDefaultScalingMatrixFlag the default. */
+static void cqm_resolve(const cqm_list_t *l, int coded, const cqm_t *fb, cqm_t *o)
+{
+    for (int n = 0; n < 6; n++) {
+        if (n < coded && l[n].present) memcpy(o->l4[n], l[n].use_default ? cqm_default4[n / 3] : l[n].v, 16);
+        else if (n % 3) memcpy(o->l4[n], o->l4[n - 1], 16);
+        else memcpy(o->l4[n], fb ? fb->l4[n] : cqm_default4[n / 3], 16);
+    }
+    for (int n = 0; n < 2; n++) {
+        if (6 + n < coded && l[6 + n].present) memcpy(o->l8[n], l[6 + n].use_default ? cqm_default8[n] : l[6 + n].v, 64);
+        else memcpy(o->l8[n], fb ? fb->l8[n] : cqm_default8[n], 64);
+    }
+}
+static int cqm_is_flat(const cqm_t *c)
+{
+    const uint8_t *v = &c->l4[0][0];
+    for (size_t i = 0; i < sizeof *c; i++) if (v[i] != 16) return 0;
+    return 1;
+}
+
 /* decoder/set.c:37-167 */
 static int parse_sps(p264parse *p, bitrd_t *b)
 {
@@ -180,16 +238,24 @@ static int parse_sps(p264parse *p, bitrd_t *b)
     s->profile_idc = profile; s->level_idc = level;
     s->high = sps_is_high(profile);
     if (s->high) {
-        /* what the kernels decode of the High tools: 4:2:0, 8 bits, no transform bypass, flat scaling lists */
+        /* what the kernels decode of the High tools: 4:2:0, 8 bits, no transform bypass; scaling lists where the backend is said to
+         * read the picture's table (P264PARSE_OPT_SCALING), else flat ones only */
         const unsigned cf = br_ue(b);
         const int separate = cf == 3 ? (int)br_u1(b) : 0;
         const unsigned bd_y = br_ue(b), bd_c = br_ue(b);
         const int bypass = (int)br_u1(b), matrices = (int)br_u1(b);
-        if (br_eof(b) || cf != 1 || separate || bd_y || bd_c || bypass || matrices) {
+        if (br_eof(b) || cf != 1 || separate || bd_y || bd_c || bypass || (matrices && !(p->opts & P264PARSE_OPT_SCALING))) {
             ERR(p, "SPS %u (profile %d): chroma_format_idc %u, bit depths %u / %u, transform bypass %d, scaling matrices %d unsupported (4:2:0, 8 bits, flat lists)",
                 id, profile, cf, bd_y + 8, bd_c + 8, bypass, matrices);
             *s = old;                                   /* keep the set we had */
             return -1;
+        }
+        if (matrices) {                                 /* eight lists for 4:2:0, resolved with rule A */
+            cqm_list_t l[8];
+            for (int n = 0; n < 8; n++) cqm_read_list(b, n < 6 ? 16 : 64, &l[n]);
+            if (br_eof(b)) { ERR(p, "SPS %u: incomplete scaling matrix", id); *s = old; return -1; }
+            s->cqm = 1;
+            cqm_resolve(l, 8, NULL, &s->lists);
         }
     }
     s->log2_max_frame_num = (int)br_ue(b) + 4;
@@ -258,8 +324,18 @@ static int parse_pps(p264parse *p, bitrd_t *b)
     if ((long)br_consumed(b) < rbsp_stop_bit(b->buf, (int)b->size)) {
         q->t8x8_mode = (int)br_u1(b);
         q->scaling_matrix = (int)br_u1(b);
+        if (q->scaling_matrix && (p->opts & P264PARSE_OPT_SCALING)) {
+            /* the lists as coded, then the real second offset.  Nothing here fails: a short extension is remembered */
+            const int coded = 6 + 2 * q->t8x8_mode;
+            for (int n = 0; n < coded; n++) cqm_read_list(b, n < 6 ? 16 : 64, &q->cqm[n]);
+            q->cqm_read = 1;
+            q->second_chroma_qp_offset = br_se(b);
+            q->ext_short = br_eof(b);
+            q->ext = 1;
+        } else {
         q->second_chroma_qp_offset = q->scaling_matrix ? q->chroma_qp_offset : br_se(b);      /* (behind matrices nothing can be read without parsing them) */
         q->ext = !br_eof(b);
+        }
     }
     q->valid = 1;
     INFO(p, "p264amd: pps:%u sps:%d %s ref0:%d QP:%d QC=%d DFC:%d CIP:%d\n", id, q->sps_id,
@@ -1499,6 +1575,10 @@ static void publish_picture(p264parse *p)
         memcpy(d->bipred_weight, c->bipred_weight, sizeof d->bipred_weight);
     }
     d->transform_8x8 = c->t8x8 | (c->i8x8 ? P264_T8X8_INTRA : 0);
+    if (c->cqm) {
+        d->scaling_lists = 1;
+        memcpy(d->scaling4x4, c->lists.l4, sizeof d->scaling4x4); memcpy(d->scaling8x8, c->lists.l8, sizeof d->scaling8x8);
+    }
     if (c->wp_set && c->wp) {
         d->explicit_wp = 1;
         d->wp_log2_denom[0] = c->wp_denom[0]; d->wp_log2_denom[1] = c->wp_denom[1];
@@ -1570,13 +1650,29 @@ static int open_slice(p264parse *p, const slice_t *sh)
     /* the PPS extension counts under a High SPS (decided here, where the pair is known, not where the PPS was parsed) */
     p->t8x8_mode = 0;
     if (p->sps[pps->sps_id].high && pps->ext) {
-        if (pps->scaling_matrix) { ERR(p, "pic_scaling_matrix_present_flag unsupported (flat scaling lists only)"); return REFUSE_SLICE; }
+        if (pps->scaling_matrix && !pps->cqm_read) { ERR(p, "pic_scaling_matrix_present_flag unsupported (flat scaling lists only)"); return REFUSE_SLICE; }
+        if (pps->ext_short) { ERR(p, "PPS %d: its extension ends inside the scaling matrix", sh->pps_id); return REFUSE_SLICE; }
         if (pps->second_chroma_qp_offset != pps->chroma_qp_offset) {
             ERR(p, "second_chroma_qp_index_offset %d differs from chroma_qp_index_offset %d: unsupported", pps->second_chroma_qp_offset, pps->chroma_qp_offset);
             return REFUSE_SLICE;
         }
         p->t8x8_mode = pps->t8x8_mode;
         c->t8x8 |= pps->t8x8_mode;
+    }
+    {
+        /* the picture's scaling lists (table 7-2): the PPS's - resolved against the SPS's where it has a matrix (rule B), against the
+         * defaults where not (rule A) -, else the SPS's, else flat.  One table per picture on the device, like the weights: the first
+         * slice's, every other one must resolve to the same.  (Lists that spell out weight 16 everywhere: a flat picture.) */
+        const sps_t *sps = &p->sps[pps->sps_id];
+        cqm_t now;
+        int cqm = 0;
+        if (sps->high && pps->ext && pps->scaling_matrix) { cqm_resolve(pps->cqm, 6 + 2 * pps->t8x8_mode, sps->cqm ? &sps->lists : NULL, &now); cqm = 1; }
+        else if (sps->high && sps->cqm) { now = sps->lists; cqm = 1; }
+        if (cqm && cqm_is_flat(&now)) cqm = 0;
+        if (c->slice_no == 0) { c->cqm = cqm; if (cqm) c->lists = now; }
+        else if (cqm != c->cqm || (cqm && memcmp(&now, &c->lists, sizeof now))) {
+            ERR(p, "slices of one picture with different scaling lists unsupported"); return REFUSE_SLICE;
+        }
     }
     p->slice_flags = sh->disable_deblock == 1 ? 0 : (uint16_t)(((sh->alpha_off - c->alpha) & 255) | ((sh->beta_off - c->beta) & 255) << 8);
     p->sh = *sh;

@@ -70,11 +70,13 @@ class ParsedPicture:
 class Parser:
     """p264parse_* : NAL units in, complete parsed pictures out (CPU, serial by nature)."""
 
-    def __init__(self, quiet=True, strict=False, lib=None, intra8x8=False):
+    def __init__(self, quiet=True, strict=False, lib=None, intra8x8=False, scaling=False):
         """intra8x8: hand out Intra 8x8 macroblocks as I4x4 records with MB_I8X8 (P264PARSE_OPT_INTRA8X8) - for pictures that go to
-        a backend that knows the record, as HipReconstructor does; off, such a macroblock ends its slice with an error"""
+        a backend that knows the record, as HipReconstructor does; off, such a macroblock ends its slice with an error.
+        scaling: read the scaling matrices of High-profile parameter sets and hand out each picture's eight lists in its descriptor
+        (P264PARSE_OPT_SCALING) - for a backend that reads the table, as HipReconstructor does; off, such a set is refused"""
         self.lib = lib or N.load()
-        self.h = self.lib.p264parse_open((1 if quiet else 0) | (2 if strict else 0) | (4 if intra8x8 else 0))
+        self.h = self.lib.p264parse_open((1 if quiet else 0) | (2 if strict else 0) | (4 if intra8x8 else 0) | (8 if scaling else 0))
         if not self.h:
             raise P264Error("p264parse_open failed")
 
@@ -297,10 +299,10 @@ class HipReconstructor:
 
     def last_launch(self):
         """The launch shapes of the last reconstruct call (p264hip_launch_info_t as a dict; what depends on the batch's CONTENT
-        rather than its size has its own accessor: last_t8x8_wgs, last_intra_i8)."""
+        rather than its size has its own accessor: last_t8x8_wgs, last_intra_i8, last_scaled_pictures)."""
         li = N.LaunchInfo()
         self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
-        return {n: int(getattr(li, n)) for n, _ in N.LaunchInfo._fields_ if n not in ("reserved", "t8x8_wgs", "intra_i8")}
+        return {n: int(getattr(li, n)) for n, _ in N.LaunchInfo._fields_ if n not in ("reserved", "t8x8_wgs", "intra_i8", "scaled_pictures")}
 
     def last_t8x8_wgs(self):
         """Workgroups of k_t8x8 in the last reconstruct call: 0 unless a picture of the batch had transform_8x8."""
@@ -314,6 +316,13 @@ class HipReconstructor:
         li = N.LaunchInfo()
         self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
         return int(li.intra_i8)
+
+    def last_scaled_pictures(self):
+        """Pictures with scaling_lists in the last reconstruct call; not 0: the batch ran the instances that read the scaling
+        table (k_mc_sort_scaled / k_mc_sort_scaled_p, k_scaled_inter, k_intra_scaled / k_intra_sparse_scaled), 0: what a flat batch always ran."""
+        li = N.LaunchInfo()
+        self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
+        return int(li.scaled_pictures)
 
 
 def device_count(lib=None):

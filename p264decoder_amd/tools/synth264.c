@@ -83,6 +83,13 @@
  *                            8x8 blocks in both coders (they appear in --dump-t8x8 like flagged inter macroblocks); [--dump-i8x8 f]
  *                            per picture uint32 macroblocks, then per macroblock the flag and the four modes.  --t8x8-intra has
  *                            no effect beside it.  Without --i8x8 the streams are what they were, byte for byte.
+ *            [--cqm jvt|rand:SEED]  (needs --t8x8) scaling matrices in the parameter sets: jvt signals the default lists of tables 7-3 /
+ *                            7-4 without spelling them (absent lists, useDefaultScalingMatrixFlag on 4x4 and 8x8 lists), rand writes
+ *                            explicit lists with weights 4 .. 64, two of them ending early on a repeated last value;
+ *                            [--cqm-where sps|pps|both] which set carries them (both: one set in the SPS, lists 1, 4 and 7 overridden in
+ *                            the PPS, so that both kinds of fall-back of rule B occur); [--dump-cqm f] per picture the 224 resolved
+ *                            weights the writer intends (4x4 lists 0 .. 5, 8x8 lists 6, 7, scan order).  The writer draws levels and does
+ *                            not quantise: nothing else changes, and without --cqm the streams are what they were, byte for byte.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -155,6 +162,14 @@ static int cur;                             /* current MB index */
 
 static int opt_pps_alt = 0, cur_pps = 0;
 static int opt_i8x8 = -1;                     /* --i8x8 PCT (-1: not given): see put_intra */
+/* --cqm jvt | rand:SEED (needs --t8x8): scaling matrices in the parameter sets (7.3.2.1.1.1); --cqm-where sps | pps | both; the
+ * writer draws levels and does not quantise, so nothing else of the stream changes.  See cqm_plan. */
+static int opt_cqm = 0, opt_cqm_where = 0;          /* 0 none, 1 jvt, 2 rand; 0 sps, 1 pps, 2 both */
+static unsigned long long cqm_seed = 1;
+static FILE *dump_cqm;                              /* --dump-cqm: per picture the 224 resolved weights the writer intends (4x4 lists 0 .. 5, 8x8 lists 6, 7; scan order) */
+typedef struct { int present, use_default; uint8_t v[64]; } cqm_wl_t;
+static cqm_wl_t cqm_sps[8], cqm_pps[8];
+static uint8_t cqm_final[224];
 static int opt_t8x8 = -1, opt_t8x8_intra = 0;   /* --t8x8 PCT (-1: not given), --t8x8-intra PCT: see put_inter_tail */
 static int opt_wp = 0, opt_wp_bi = 0, opt_wp_dup = 0, opt_wp_identity = 0, opt_wp_differ = 0, opt_wp_bad_sum = 0;
 static FILE *dump_wp = NULL;
@@ -1071,8 +1086,69 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
     }
 }
 
+/* ---- --cqm: scaling matrices ---- */
+static const uint8_t cqm_def4[2][16] = {            /* tables 7-3, 7-4: Default_4x4_Intra / _Inter, Default_8x8_Intra / _Inter, scan order */
+    { 6, 13, 13, 20, 20, 20, 28, 28, 28, 28, 32, 32, 32, 37, 37, 42 }, { 10, 14, 14, 20, 20, 20, 24, 24, 24, 24, 27, 27, 27, 30, 30, 34 } };
+static const uint8_t cqm_def8[2][64] = {
+    { 6, 10, 10, 13, 11, 13, 16, 16, 16, 16, 18, 18, 18, 18, 18, 23, 23, 23, 23, 23, 23, 25, 25, 25, 25, 25, 25, 25, 27, 27, 27, 27, 27, 27, 27, 27,
+      29, 29, 29, 29, 29, 29, 29, 31, 31, 31, 31, 31, 31, 33, 33, 33, 33, 33, 36, 36, 36, 36, 38, 38, 38, 40, 40, 42 },
+    { 9, 13, 13, 15, 13, 15, 17, 17, 17, 17, 19, 19, 19, 19, 19, 21, 21, 21, 21, 21, 21, 22, 22, 22, 22, 22, 22, 22, 24, 24, 24, 24, 24, 24, 24, 24,
+      25, 25, 25, 25, 25, 25, 25, 27, 27, 27, 27, 27, 27, 28, 28, 28, 28, 28, 30, 30, 30, 30, 32, 32, 32, 33, 33, 35 } };
+/* scaling_list_present_flag and scaling_list( ): useDefaultScalingMatrixFlag is a first nextScale of 0 (delta -8); a tail that repeats
+ * its last value is cut short by the delta that makes nextScale 0 */
+static void put_cqm_list(bw_t *b, int size, const cqm_wl_t *l)
+{
+    bw_put(b, 1, (uint32_t)l->present);
+    if (!l->present) return;
+    if (l->use_default) { bw_se(b, -8); return; }
+    int end = size, last = 8;
+    while (end > 1 && l->v[end - 1] == l->v[end - 2]) end--;
+    for (int j = 0; j < end; j++) { bw_se(b, ((l->v[j] - last + 128) & 255) - 128); last = l->v[j]; }
+    if (end < size) bw_se(b, ((0 - last + 128) & 255) - 128);
+}
+/* table 7-2 on what a set codes; fb: the SPS's resolved lists (fall-back rule B) or NULL (rule A).  o: 224 bytes */
+static void cqm_resolve_w(const cqm_wl_t *l, const uint8_t *fb, uint8_t *o)
+{
+    for (int n = 0; n < 8; n++) {
+        const int size = n < 6 ? 16 : 64;
+        uint8_t *d = n < 6 ? o + 16 * n : o + 96 + 64 * (n - 6);
+        const uint8_t *def = n < 6 ? cqm_def4[n / 3] : cqm_def8[n - 6];
+        if (l[n].present) memcpy(d, l[n].use_default ? def : l[n].v, (size_t)size);
+        else if (n < 6 && n % 3) memcpy(d, d - 16, 16);
+        else memcpy(d, fb ? fb + (d - o) : def, (size_t)size);
+    }
+}
+/* What the parameter sets will code, and cqm_final, the picture's lists that follows from it.
+ *   jvt: the defaults without spelling them - list 0, 2, 4, 5, 6 absent, lists 1, 3, 7 present with useDefaultScalingMatrixFlag
+ *   rand: every list spelled out, weights 4 .. 64; the tails of lists 2 and 6 repeat their last value (coded short)
+ *   both: that set in the SPS; the PPS codes lists 1, 4 and 7 only (jvt: as defaults, rand: other lists) - 0, 3, 6 fall back to the
+ *   SPS's (rule B), 2 and 5 to the list in front of them */
+static void cqm_plan(void)
+{
+    unsigned long long r = cqm_seed * 0x9e3779b97f4a7c15ull + 7;
+    cqm_wl_t full[8], over[8];
+    memset(full, 0, sizeof full); memset(over, 0, sizeof over);
+    for (int n = 0; n < 8; n++) {
+        const int size = n < 6 ? 16 : 64;
+        for (int pass = 0; pass < 2; pass++) {
+            cqm_wl_t *l = pass ? &over[n] : &full[n];
+            if (opt_cqm == 1) { l->present = l->use_default = pass ? 1 : (n == 1 || n == 3 || n == 7); continue; }
+            l->present = 1;
+            for (int j = 0; j < size; j++) { r = r * 6364136223846793005ull + 1442695040888963407ull; l->v[j] = (uint8_t)(4 + (r >> 33) % 61); }
+            if (n == 2 || n == 6) for (int j = size - size / 3; j < size; j++) l->v[j] = l->v[size - size / 3 - 1];
+        }
+        if (n != 1 && n != 4 && n != 7) memset(&over[n], 0, sizeof over[n]);
+    }
+    uint8_t seq[224];
+    cqm_resolve_w(full, NULL, seq);
+    if (opt_cqm_where == 0) { memcpy(cqm_sps, full, sizeof full); memcpy(cqm_final, seq, 224); }
+    else if (opt_cqm_where == 1) { memcpy(cqm_pps, full, sizeof full); memcpy(cqm_final, seq, 224); }
+    else { memcpy(cqm_sps, full, sizeof full); memcpy(cqm_pps, over, sizeof over); cqm_resolve_w(over, seq, cqm_final); }
+}
+
 int main(int argc, char **argv)
 {
+    const char *cqm_arg = NULL, *cqm_where_arg = NULL;
     if (argc < 2) { fprintf(stderr, "usage: synth264 out.264 [--mbw N --mbh N --frames N --gop N --seed N --intra-only ...]\n"); return 2; }
     int frames = 30, gop = 30, intra_only = 0, crop_bottom = 0, crop[4] = { 0, 0, 0, 0 }, have_crop = 0;
     uint64_t seed = 1;
@@ -1135,10 +1211,22 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--i8x8")) { opt_i8x8 = v < 0 ? 0 : v > 100 ? 100 : v; i++; }
         else if (!strcmp(a, "--dump-i8x8")) { dump_i8 = fopen(argv[i + 1], "wb"); i++; }
         else if (!strcmp(a, "--dump-t8x8")) { dump_t8 = fopen(argv[i + 1], "wb"); i++; }
+        else if (!strcmp(a, "--cqm")) { cqm_arg = i + 1 < argc ? argv[i + 1] : ""; i++; }
+        else if (!strcmp(a, "--cqm-where")) { cqm_where_arg = i + 1 < argc ? argv[i + 1] : ""; i++; }
+        else if (!strcmp(a, "--dump-cqm")) { dump_cqm = fopen(argv[i + 1], "wb"); i++; }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
     if (W < 1 || H < 1 || W > 512 || H > 512 || frames < 1 || opt_qp < 0 || opt_qp > 51 || opt_refs < 1 || opt_refs > ((opt_mmco || opt_bframes) ? 4 : 2) || (opt_bframes && (opt_refs < 2 || opt_bframes > 4)) || opt_alpha < -6 || opt_alpha > 6 || opt_beta < -6 || opt_beta > 6) { fprintf(stderr, "bad geometry\n"); return 2; }
     if (opt_slice_lists && (opt_mmco || opt_refs < 2 || opt_reorder || opt_wp_dup)) { fprintf(stderr, "--slice-lists needs --refs >= 2 and excludes --mmco, --reorder, --wp-dup\n"); return 2; }
+    if (cqm_arg) {
+        if (!strcmp(cqm_arg, "jvt")) opt_cqm = 1;
+        else if (!strncmp(cqm_arg, "rand:", 5)) { opt_cqm = 2; cqm_seed = strtoull(cqm_arg + 5, NULL, 10); }
+        else { fprintf(stderr, "--cqm jvt | rand:SEED\n"); return 2; }
+        const char *w = cqm_where_arg ? cqm_where_arg : "sps";
+        opt_cqm_where = !strcmp(w, "sps") ? 0 : !strcmp(w, "pps") ? 1 : !strcmp(w, "both") ? 2 : -1;
+        if (opt_cqm_where < 0 || opt_t8x8 < 0) { fprintf(stderr, "--cqm needs --t8x8 (High profile); --cqm-where sps | pps | both\n"); return 2; }
+        cqm_plan();
+    } else if (cqm_where_arg || dump_cqm) { fprintf(stderr, "--cqm-where and --dump-cqm need --cqm\n"); return 2; }
     NMB = W * H;
     if (opt_slice_lists || dump_slices) { w_slice = calloc((size_t)NMB, 4); w_qpic[0] = malloc((size_t)NMB * 32); w_qpic[1] = malloc((size_t)NMB * 32); }
     g_rng = seed * 0x9e3779b97f4a7c15ull + 264;
@@ -1156,7 +1244,11 @@ int main(int argc, char **argv)
         else { bw_put(&b, 8, 66); bw_put(&b, 8, 0xc0); bw_put(&b, 8, 40); }
         bw_ue(&b, 0);
         /* High: chroma_format_idc 1, both bit depths 8, no transform bypass, no scaling matrices */
-        if (opt_t8x8 >= 0) { bw_ue(&b, 1); bw_ue(&b, 0); bw_ue(&b, 0); bw_put(&b, 1, 0); bw_put(&b, 1, 0); }
+        if (opt_t8x8 >= 0) {
+            const int m = opt_cqm && opt_cqm_where != 1;                /* seq_scaling_matrix_present_flag: eight lists for 4:2:0 */
+            bw_ue(&b, 1); bw_ue(&b, 0); bw_ue(&b, 0); bw_put(&b, 1, 0); bw_put(&b, 1, (uint32_t)m);
+            if (m) for (int n = 0; n < 8; n++) put_cqm_list(&b, n < 6 ? 16 : 64, &cqm_sps[n]);
+        }
         bw_ue(&b, log2_fn - 4);
         if (opt_bframes) { bw_ue(&b, 0); bw_ue(&b, 8 - 4); }   /* pic_order_cnt_type 0, log2_max_pic_order_cnt_lsb 8 */
         else bw_ue(&b, 2);
@@ -1176,7 +1268,12 @@ int main(int argc, char **argv)
         bw_ue(&b, 0); bw_ue(&b, 0); bw_put(&b, 1, (uint32_t)opt_wp); bw_put(&b, 2, (uint32_t)(opt_wp_bi ? 1 : opt_implicit ? 2 : 0));   /* weighted_pred, weighted_bipred_idc */
         bw_se(&b, opt_qp - 26); bw_se(&b, 0); bw_se(&b, opt_cqo);
         bw_put(&b, 1, 1); bw_put(&b, 1, (uint32_t)opt_cintra); bw_put(&b, 1, 0);   /* deblocking_filter_control_present, constrained_intra_pred, redundant_pic_cnt_present */
-        if (opt_t8x8 >= 0) { bw_put(&b, 1, 1); bw_put(&b, 1, 0); bw_se(&b, opt_cqo); }   /* transform_8x8_mode_flag, pic_scaling_matrix_present_flag, second_chroma_qp_index_offset */
+        if (opt_t8x8 >= 0) {   /* transform_8x8_mode_flag, pic_scaling_matrix_present_flag (6 + 2 lists), second_chroma_qp_index_offset */
+            const int m = opt_cqm && opt_cqm_where != 0;
+            bw_put(&b, 1, 1); bw_put(&b, 1, (uint32_t)m);
+            if (m) for (int n = 0; n < 8; n++) put_cqm_list(&b, n < 6 ? 16 : 64, &cqm_pps[n]);
+            bw_se(&b, opt_cqo);
+        }
         bw_trailing(&b);
         write_nal(f, 3, 8, &b); free(b.buf);
     }
@@ -1192,6 +1289,7 @@ int main(int argc, char **argv)
             cur_poc = 2 * (is_b ? (group - 1) * (opt_bframes + 1) + pos : group * (opt_bframes + 1));
             cur_entry = -1;
             put_slice(f, idr, !idr && !is_b, is_b, frame_num, idr_id, log2_fn, since_idr, n);
+            if (dump_cqm) fwrite(cqm_final, 1, sizeof cqm_final, dump_cqm);
             if (!is_b && (idr || pos == 0)) frame_num = (frame_num + 1) & ((1 << log2_fn) - 1);
         }
         fclose(f);
@@ -1202,6 +1300,7 @@ int main(int argc, char **argv)
         if (dump_slices) fclose(dump_slices);
         if (dump_t8) fclose(dump_t8);
         if (dump_i8) fclose(dump_i8);
+        if (dump_cqm) fclose(dump_cqm);
         return 0;
     }
     for (int n = 0; n < frames; n++) {
@@ -1210,6 +1309,7 @@ int main(int argc, char **argv)
         cur_pps = opt_pps_alt ? (n & 1) : 0;
         had_mmco5 = 0;
         put_slice(f, idr, !idr, 0, frame_num, idr_id, log2_fn, since_idr, n);   /* since_idr = reference pictures available (sliding window) */
+        if (dump_cqm) fwrite(cqm_final, 1, sizeof cqm_final, dump_cqm);
         since_idr++;
         if (idr) idr_id = (idr_id + 1) & 0xffff;
         frame_num = had_mmco5 ? 1 : (frame_num + 1) & ((1 << log2_fn) - 1);
@@ -1222,5 +1322,6 @@ int main(int argc, char **argv)
     if (dump_slices) fclose(dump_slices);
     if (dump_t8) fclose(dump_t8);
     if (dump_i8) fclose(dump_i8);
+    if (dump_cqm) fclose(dump_cqm);
     return 0;
 }
