@@ -27,6 +27,27 @@ def test_pipeline_mixed_streams(lib, f26, f26_hashes):
     pipe.close()
 
 
+def test_pipeline_high_profile_streams(lib):
+    """The pipeline's parsers hand out Intra 8x8 records and scaling lists: a CABAC stream with B pictures and scaling matrices, one
+    with matrices and explicit weights, a flat High stream (8x8 transform, Intra 8x8) and a Main stream, twice each and interleaved
+    - every round is a batch that mixes scaled and flat pictures.  The last picture of every stream is the standard's (committed
+    SHA-256 of tests/scaling_checker.py's picture, tests/golden/high_pool.json)."""
+    from tests import distinct_pool
+    names = list(distinct_pool.PIPELINE_HIGH)
+    order = [0, 2, 1, 3, 2, 0, 3, 1]
+    specs = [distinct_pool.PIPELINE_HIGH[names[k]] for k in order]
+    streams, hashes = zip(*[distinct_pool.stream_of(s) for s in specs])
+    assert all(len(h) == 7 for h in hashes)
+    pipe = Pipeline(list(streams), threads=4, device=0, lib=lib)
+    try:
+        st = pipe.run()
+        assert st["pictures"] == 8 * 7 and st["rounds"] == 7, st
+        for i, k in enumerate(order):
+            assert frame_sha256(*pipe.read_frame(i)) == hashes[i][-1], "stream %d (%s)" % (i, names[k])
+    finally:
+        pipe.close()
+
+
 def test_pipeline_picture_limit(lib, f26, f26_hashes):
     pipe = Pipeline([f26] * 5, threads=2, device=0, lib=lib)
     st = pipe.run(max_pictures=9)

@@ -3,9 +3,11 @@ Checks the thread pool, the per-stream picture counts (streams of different leng
 single-threaded parser, and the allocator hook of p264parse."""
 import ctypes as C
 
+import numpy as np
 import pytest
 
 from p264decoder_amd import Parser, Pipeline, _native as N
+from p264decoder_amd.recon import P264Error
 from tests import synth_cases
 
 
@@ -25,6 +27,45 @@ def test_parse_only_pipeline_limit(lib, f26):
     st = pipe.run(max_pictures=7)
     assert st["pictures"] == 28 and st["threads"] == 4 and st["rounds"] == 7
     pipe.close()
+
+
+def test_parse_only_pipeline_takes_high_profile_streams(lib):
+    """the CPU twin of tests/test_gpu_pipeline.py: test_pipeline_high_profile_streams.  The pipeline's parsers hand out Intra 8x8
+    records and scaling lists (P264PARSE_OPT_INTRA8X8 | P264PARSE_OPT_SCALING), with and without a device: streams with scaling
+    matrices, with explicit weights beside them, flat High and Main streams side by side, every picture counted"""
+    from tests import distinct_pool
+    names = list(distinct_pool.PIPELINE_HIGH)
+    order = [0, 2, 1, 3, 2, 0, 3, 1]
+    data = {n: distinct_pool.read_stream(distinct_pool.PIPELINE_HIGH[n]) for n in names}
+    # what the four are: by a parser with the same options
+    about = {}
+    for n in names:
+        parser = Parser(quiet=True, lib=lib, intra8x8=True, scaling=True)
+        try:
+            pics = parser.parse_stream(data[n])
+        finally:
+            parser.close()
+        flags = np.concatenate([p.mb_records()["intra_modes"] for p in pics])
+        about[n] = (len(pics), all(int(p.desc.scaling_lists) for p in pics), any(p.desc.explicit_wp for p in pics),
+                    any(p.desc.slice_type == N.SLICE_B for p in pics), bool((flags & N.MB_T8X8).any()), bool((flags & N.MB_I8X8).any()))
+    assert about == {"scaled cabac b": (7, True, False, True, True, True), "scaled weighted": (7, True, True, True, True, True),
+                     "flat high": (7, False, False, True, True, True), "main": (7, False, False, True, False, False)}, about
+    assert "--cabac" in distinct_pool.PIPELINE_HIGH["scaled cabac b"]
+    plain = Parser(quiet=True, lib=lib)                                  # (a parser without the options refuses the matrices)
+    try:
+        with pytest.raises(P264Error):
+            plain.parse_stream(data["scaled cabac b"])
+    finally:
+        plain.close()
+    streams = [data[names[k]] for k in order]
+    pipe = Pipeline(streams, threads=4, device=-1, lib=lib)
+    try:
+        st = pipe.run()
+        assert st["pictures"] == 8 * 7 and st["rounds"] == 7 and st["streams"] == 8 and st["threads"] == 4
+        assert [pipe.pictures(i) for i in range(8)] == [7] * 8
+        assert st["bytes"] == sum(len(s) for s in streams)
+    finally:
+        pipe.close()
 
 
 def test_gpu_pipeline_needs_a_device(lib):
