@@ -88,11 +88,12 @@ def allowed_flags(pic, m):
     return (N.AVAIL_LEFT if x > 0 else 0) | (N.AVAIL_TOP if y > 0 else 0) | (N.AVAIL_TOPRIGHT if y > 0 and x + 1 < w else 0) | (N.AVAIL_TOPLEFT if x > 0 and y > 0 else 0)
 
 
-def convert(pic, rng, chosen, plan, coded=0.6):
-    """the I4x4 macroblocks `chosen` become Intra 8x8 records.  Returns (macroblocks with levels, of them redrawn)."""
+def convert(pic, rng, chosen, plan, coded=0.6, first=0):
+    """the I4x4 macroblocks `chosen` become Intra 8x8 records.  Returns (macroblocks with levels, of them redrawn).  first: where the
+    cycle of seven starts - 1: the first converted macroblock has all four blocks coded (a picture of one macroblock)."""
     rec = pic.mb_records()
     old = np.asarray(pic.coefs).reshape(-1, 16)
-    out, drawn, redrawn, nth = [], 0, 0, 0
+    out, drawn, redrawn, nth = [], 0, 0, first
     for m in range(pic.n_mb):
         r = rec[m]
         mask, at = int(r["coef_mask"]), int(r["coef_index"])
@@ -134,8 +135,8 @@ def convert(pic, rng, chosen, plan, coded=0.6):
     return drawn, redrawn
 
 
-def dense_picture(rng, plan, name="dense I 9x9", deblock=True):
-    w, h = DENSE_W, DENSE_H
+def dense_picture(rng, plan, name="dense I 9x9", deblock=True, mb_w=DENSE_W, mb_h=DENSE_H):
+    w, h = mb_w, mb_h
     n = w * h
     plain = [m for m in range(n) if ((m % w) + 3 * (m // w)) % 4 == 0]        # the macroblocks that stay what they are
     kinds = {m: ("i4", "i16", "ipcm")[i % 3] for i, m in enumerate(plain)}
@@ -160,8 +161,8 @@ CLUSTER = (7, 8, 9, 13, 14, 15, 20)
 SPARSE = (7, 10, 16, 21, 27)
 
 
-def inter_picture(rng, plan, name, flagged, t8_share, **kw):
-    st = TS.drawn_picture(rng, name, MB_W, MB_H, share=t8_share, intra_share=0.1, force={m: "i4" for m in flagged}, **kw)
+def inter_picture(rng, plan, name, flagged, t8_share, mb_w=MB_W, mb_h=MB_H, **kw):
+    st = TS.drawn_picture(rng, name, mb_w, mb_h, share=t8_share, intra_share=0.1, force={m: "i4" for m in flagged}, **kw)
     pic = st.pic
     if not (pic.mb_records()["intra_modes"] & N.MB_T8X8).any():
         pic.desc.transform_8x8 = 0                         # (no inter record carries the flag: Intra 8x8 alone)

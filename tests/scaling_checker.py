@@ -152,12 +152,25 @@ def norm8(m, i, j):
 
 class Census:
     """what the scaled blocks exercised: lists[n] - non-zero levels of list n met at a position whose weight is not 16; branches -
-    (rule, "shift" / "round", qP) of blocks with a non-zero level; chroma_dc - (plane, "intra" / "inter") with a non-zero level"""
+    (rule, "shift" / "round", qP) of blocks with a non-zero level; chroma_dc - (plane, "intra" / "inter") with a non-zero level;
+    classes[(n, class)] - non-zero levels of list n met at a weight of that class (weight_class: 0, 1 .. 3, 4 .. 64, 65 .. 255), the DC
+    blocks among them also in dc_classes[("luma", class)] (Intra16x16) and dc_classes[((plane, "intra" / "inter"), class)] (chroma)"""
 
     def __init__(self):
         self.lists = collections.Counter()
         self.branches = collections.Counter()
         self.chroma_dc = collections.Counter()
+        self.classes = collections.Counter()
+        self.dc_classes = collections.Counter()
+
+
+WEIGHT_CLASSES = ("0", "1..3", "4..64", "65..255")
+
+
+def weight_class(w):
+    """a byte of a list -> one of WEIGHT_CLASSES (4 .. 64 is what every list before tests/scaling_stim.py: extreme_set held)"""
+    assert 0 <= w <= 255
+    return WEIGHT_CLASSES[0 if w == 0 else 1 if w <= 3 else 2 if w <= 64 else 3]
 
 
 # ---- the formulas --------------------------------------------------------------------------------------------------------------
@@ -177,6 +190,7 @@ def scale4x4(c, qp, w, rng, dc=None, census=None, n=None):
                 d[i][j] = (c[i][j] * ls + (1 << (3 - s))) >> (4 - s)
             if census is not None and c[i][j]:
                 census.branches[("4x4", "shift" if qp >= 24 else "round", qp)] += 1
+                census.classes[(n, weight_class(w[i][j]))] += 1
                 if w[i][j] != 16:
                     census.lists[n] += 1
     rng.see("d", [x for r in d for x in r])
@@ -193,6 +207,8 @@ def luma_dc(c, qp, w, rng, census=None):
         dc = [[(x * ls + (1 << (5 - qp // 6))) >> (6 - qp // 6) for x in r] for r in f]
     if census is not None and any(x for r in f for x in r):
         census.branches[("luma dc", "shift" if qp >= 36 else "round", qp)] += 1
+        census.classes[(INTRA_Y, weight_class(w[0][0]))] += 1
+        census.dc_classes[("luma", weight_class(w[0][0]))] += 1
         if w[0][0] != 16:
             census.lists[INTRA_Y] += 1
     rng.see("dcY", [x for r in dc for x in r])
@@ -208,7 +224,10 @@ def chroma_dc(c4, qpc, w, rng, census=None, n=None):
     ls = w[0][0] * norm4(qpc % 6, 0, 0)
     dc = [((x * ls) << (qpc // 6)) >> 5 for r in f for x in r]
     if census is not None and any(x for r in f for x in r):
-        census.chroma_dc[(1 if n in (INTRA_CB, INTER_CB) else 2, "intra" if n < 3 else "inter")] += 1
+        which = (1 if n in (INTRA_CB, INTER_CB) else 2, "intra" if n < 3 else "inter")
+        census.chroma_dc[which] += 1
+        census.classes[(n, weight_class(w[0][0]))] += 1
+        census.dc_classes[(which, weight_class(w[0][0]))] += 1
         if w[0][0] != 16:
             census.lists[n] += 1
     rng.see("dcC", dc)
@@ -227,6 +246,7 @@ def scale8x8(c, qp, w, rng, census=None, n=None):
             for j in range(8):
                 if c[i][j]:
                     census.branches[("8x8", "shift" if qp >= 36 else "round", qp)] += 1
+                    census.classes[(n, weight_class(w[i][j]))] += 1
                     if w[i][j] != 16:
                         census.lists[n] += 1
     rng.see("d", [x for r in d for x in r])

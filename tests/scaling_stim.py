@@ -10,6 +10,9 @@ The lists: JVT (the defaults of tables 7-3 / 7-4), random lists with weights 4 .
 a list set with a different weight at every scan position (a wrong scan -> raster mapping shows at once) - and the all-16 set, with
 scaling_lists = 1: the flat decode through the scaled kernels.
 
+`extreme_set()`: the rest of the byte - include/p264hip.h: "Any byte is legal (0 zeroes the coefficient)" - weights 1 .. 3, where the
+rounding term of the right-shift branch dominates, 65 .. 255, where the 32-bit product is up to sixteen times a flat one, and 0.
+
 `directed_set()`: the QPs on both sides of every branch (23 / 24, 35 / 36) for 4x4 blocks, the luma DC and 8x8 blocks, chroma DC of
 both planes in intra and in inter macroblocks.  `random_set()`: drawn pictures over all QPs.  `assert_covered` says what the sets
 must reach."""
@@ -54,6 +57,12 @@ def marked_lists(seed):
 def ramp_lists():
     """a different weight at every scan position of every list"""
     return [[8 + 3 * n + k if size == 16 else 6 + n + (k * 37) % 61 for k in range(size)] for n, size in enumerate(SC.SIZES)]
+
+
+def chosen_lists(seed, weights):
+    """every position of every list drawn from `weights`"""
+    rng = np.random.default_rng(seed)
+    return [[int(v) for v in rng.choice(weights, size=n)] for n in SC.SIZES]
 
 
 def flat_lists():
@@ -128,6 +137,32 @@ def random_set(seed=8591):
     return out
 
 
+LOW_QPS = (0, 5, 10, 14, 18, 22)
+SMALL_WEIGHTS, LARGE_WEIGHTS, MIXED_WEIGHTS, ZERO_WEIGHTS = (1, 2, 3), (65, 96, 128, 160, 200, 254, 255), (1, 2, 3, 16, 65, 128, 255), (0, 16, 40)
+
+
+def extreme_sources(seed):
+    """six fresh pictures (`scaled` changes the one it is given): P residual sweeps with Intra16x16 / Intra4x4 / inter macroblocks, T8X8
+    inter records, Intra 8x8 among inter macroblocks in a P and a B picture, an I picture"""
+    res, i8 = S.residual_set(), IS.inter_set()
+    return [res[0], res[12], TS.directed_set()[0], i8[0], i8[4], i_picture(np.random.default_rng(seed), "I picture")]
+
+
+def extreme_set(seed=8597):
+    """weights 1 .. 3 at the pictures' own QPs and at the threshold QPs; 65 .. 255, the whole byte mixed, and 0 beside 16 and 40 at QPs
+    below 24.  (Large weights at high QPs are left out: 8.5.13's range leaves too few non-zero levels there - of the 968 level blocks of
+    the six pictures make_conformant shrinks 382 at QPs (23, 24, 35, 36, 51, 30), 119 at LOW_QPS.)  Weight 0 is legal at the seam only:
+    a stream's list cannot carry it."""
+    out = []
+    for k, (what, weights, qps) in enumerate((("weights 1..3", SMALL_WEIGHTS, None), ("weights 1..3 at the thresholds", SMALL_WEIGHTS, THRESHOLD_QPS),
+                                              ("weights 65..255", LARGE_WEIGHTS, LOW_QPS), ("weights 1..255", MIXED_WEIGHTS, LOW_QPS),
+                                              ("weights 0, 16, 40", ZERO_WEIGHTS, LOW_QPS))):
+        for i, st in enumerate(extreme_sources(seed + k)):
+            rot = None if qps is None else qps[i % len(qps):] + qps[:i % len(qps)]
+            out.append(scaled(st, chosen_lists(seed + 10 * k + i, weights), "%s %s" % (what, st.name), rot))
+    return out
+
+
 def flat_twins(n=6):
     """pairs (picture with scaling_lists = 1 and all-16 lists, the same picture flat) of conformant pictures: P, B, explicit weights,
     T8X8, Intra 8x8, I"""
@@ -141,7 +176,7 @@ def flat_twins(n=6):
     return out
 
 
-SETS = ("directed_set", "random_set")
+SETS = ("directed_set", "random_set", "extreme_set")
 
 
 def survey(stims):
@@ -173,6 +208,18 @@ def assert_covered(which, stims):
         if int(d.slice_type) != N.SLICE_I and intra.any() and not intra.all():
             kinds.add("mixed")
     assert kinds >= {(N.SLICE_P, False, False), (N.SLICE_B, False, False), (N.SLICE_I, False, False), "t8", "i8", "mixed"}, kinds
+    if which == "extreme_set":
+        small, large, zero = SC.WEIGHT_CLASSES[1], SC.WEIGHT_CLASSES[3], SC.WEIGHT_CLASSES[0]
+        for n in range(8):
+            for cls in (small, large):
+                assert c.classes[(n, cls)] > 0, "list %d never met a non-zero level at a weight of %s: %s" % (n, cls, sorted(c.classes.items()))
+        assert any(c.classes[(n, zero)] for n in range(6)) and any(c.classes[(n, zero)] for n in (6, 7)), sorted(c.classes.items())
+        for plane in (1, 2):
+            for kind in ("intra", "inter"):
+                assert c.dc_classes[((plane, kind), large)] > 0, "chroma DC of plane %d in %s macroblocks at a weight >= 65" % (plane, kind)
+        assert c.dc_classes[("luma", large)] > 0 and c.dc_classes[("luma", small)] > 0, sorted(c.dc_classes.items())
+        tables = [bytes(st.pic.desc.scaling4x4) + bytes(st.pic.desc.scaling8x8) for st in stims]
+        assert {b for t in tables for b in t} >= {0, 1, 2, 3, 254, 255}
     if which != "directed_set":
         return
     assert kinds >= {(N.SLICE_B, False, True), (N.SLICE_P, True, False), (N.SLICE_B, True, False), "no t8", "no i8"}, kinds

@@ -138,6 +138,16 @@ def test_the_kernels_are_in_the_code_object_without_spills_or_scratch(lib):
         assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0 and r["group_segment_fixed_size"] == 0, (k, r)
 
 
+def test_the_wide_windows_reach_every_tile_column():
+    """the windows of tests/test_gpu_export_wide.py: three luma tile columns, two I420 chroma tile columns, the odd last strip pair,
+    a window whose first strip is no multiple of the tile - restated from the windows and held against the table that file keeps"""
+    from tests import test_gpu_export_wide as W
+    W.assert_reach()
+    assert len(W.WINDOWS) == 6 and {r[2] for r in W.WINDOWS.values()} == {2, 3} and {r[5] for r in W.WINDOWS.values()} == {1, 2}
+    assert any(r[0] % 8 for r in W.WINDOWS.values()) and any(c[0] % 16 for c in W.WINDOWS)
+    assert {fmt for fmt, _, _ in W.KINDS} == set(X.FORMATS) and len(W.KINDS) == 10
+
+
 def test_abi_mirror(lib):
     import os
     import subprocess

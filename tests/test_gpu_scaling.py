@@ -1,4 +1,5 @@
-"""Scaling matrices on the MI355X: the pictures of tests/scaling_stim.py through p264hip_submit, in batches of three through the
+"""Scaling matrices on the MI355X: the pictures of tests/scaling_stim.py (weights over the whole byte: 0, 1 .. 3, 4 .. 64 and
+65 .. 255 - extreme_set) through p264hip_submit, in batches of three through the
 upload, compact and commit roads, and in one batch that mixes scaled and flat pictures of every kind, all three planes byte for byte
 against tests/scaling_checker.py (H.264 8.5.9 - 8.5.13 with the picture's lists: the reference forces flat lists and is no oracle
 here); what the launch reports; all-16 lists against the flat decode of the same pictures; two whole streams whose parameter sets
@@ -41,13 +42,15 @@ def test_submit_equals_the_standard(lib, expected, which):
 @pytest.mark.parametrize("road", ["upload", "compact", "commit"])
 def test_batches_of_three_equal_the_standard(lib, expected, road):
     sent_all = []
-    for size, cases in H.by_size(expected["directed_set"] + expected["random_set"]).items():
+    for size, cases in H.by_size(expected["directed_set"] + expected["random_set"] + expected["extreme_set"]).items():
         bad, sent, counts = H.run_batches(lib, cases, road=road, slots=SLOTS, probe=scaled_in)
         assert not bad, "%s: %d of %d pictures differ: %s" % (size, len(bad), len(sent), bad[:3])
         assert all(got == want == 3 for got, want in counts)
         sent_all += sent
     directed = {id(st.pic) for st, _ in expected["directed_set"]}
     SS.assert_covered("directed_set", [st for st in {id(st.pic): st for st in sent_all}.values() if id(st.pic) in directed])
+    extreme = {id(st.pic) for st, _ in expected["extreme_set"]}
+    SS.assert_covered("extreme_set", [st for st in {id(st.pic): st for st in sent_all}.values() if id(st.pic) in extreme])
 
 
 def flat_cases():

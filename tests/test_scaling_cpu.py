@@ -62,6 +62,50 @@ def test_a_weight_scales_its_own_position():
         assert SC.scale8x8(T8.unscan8(lv), 40, SC.weight8(other), RC.Range()) == f
 
 
+def test_the_ends_of_the_byte():
+    """weight 0 zeroes its coefficient whatever the level; 255 scales a level to 255 / 16 of its flat value where nothing rounds (qP 28,
+    40), and below qP 24 / 36 a weight of 1 leaves the rounding term alone: (c * v + 2^(3 - s)) >> (4 - s); the census files each"""
+    assert [SC.weight_class(w) for w in (0, 1, 3, 4, 16, 64, 65, 255)] == ["0", "1..3", "1..3", "4..64", "4..64", "4..64", "65..255", "65..255"]
+    for k in range(16):
+        lv = [0] * 16
+        lv[k] = -7
+        for w, mul in ((0, 0), (255, 255)):
+            lst = [16] * 16
+            lst[k] = w
+            seen = SC.Census()
+            d = SC.scale4x4(RC.unscan(lv), 28, SC.weight4(lst), RC.Range(), census=seen, n=3)
+            f = RC.scale4x4(RC.unscan(lv), 28, RC.Range())
+            assert [[16 * x for x in r] for r in d] == [[mul * x for x in r] for r in f]
+            assert seen.classes == {(3, SC.weight_class(w)): 1}
+    i, j = RC.ZIGZAG[5]
+    lst = [16] * 16
+    lst[5] = 1
+    for qp in range(24):
+        lv = [0] * 16
+        lv[5] = 3
+        d = SC.scale4x4(RC.unscan(lv), qp, SC.weight4(lst), RC.Range())
+        assert d[i][j] == (3 * SC.norm4(qp % 6, i, j) + (1 << (3 - qp // 6))) >> (4 - qp // 6) and sum(bool(x) for r in d for x in r) <= 1
+    lv = [0] * 64
+    lv[9] = 4
+    for w in (0, 255):
+        lst = [16] * 64
+        lst[9] = w
+        f = T8.scale8x8(T8.unscan8(lv), 40, RC.Range())
+        assert [[16 * x for x in r] for r in SC.scale8x8(T8.unscan8(lv), 40, SC.weight8(lst), RC.Range())] == [[w * x for x in r] for r in f]
+    # chroma DC and the Intra16x16 DC line take position 0 of their list
+    c4 = [5, -3, 2, 1]
+    for w in (0, 1, 255):
+        lst = [w] + [16] * 15
+        seen = SC.Census()
+        got = SC.chroma_dc(c4, 20, SC.weight4(lst), RC.Range(), seen, SC.INTER_CR)
+        f = [5 - 3 + 2 + 1, 5 + 3 + 2 - 1, 5 - 3 - 2 - 1, 5 + 3 - 2 + 1]
+        assert got == [((x * w * SC.norm4(20 % 6, 0, 0)) << 3) >> 5 for x in f]
+        assert seen.dc_classes == {((2, "inter"), SC.weight_class(w)): 1}
+        seen = SC.Census()
+        dc = SC.luma_dc([[2, 0, 0, 0]] + [[0] * 4] * 3, 30, SC.weight4(lst), RC.Range(), seen)
+        assert dc == [[(2 * w * SC.norm4(0, 0, 0) + 1) >> 1] * 4] * 4 and seen.dc_classes == {("luma", SC.weight_class(w)): 1}
+
+
 def test_flat_pictures_equal_the_checkers_they_extend():
     """scaling_lists = 0, and scaling_lists = 1 with all-16 lists: every macroblock's residual is residual_checker's (4x4, chroma) and
     t8x8_checker's / i8x8_checker's (8x8 blocks)"""
