@@ -23,6 +23,7 @@
 // 16-bit arithmetic without branches, and a wavefront walks eight macroblock rows as a diagonal.
 #pragma once
 #include "device_common.h"
+#include "launch_shared.h"              // (DB_LAG, MAX_PICS_PER_WG, ROW_WAVES)
 #include "wavefront_sync.h"
 #define DEBLOCK_WAIT_SLEEP 16
 #define DY_DW 5                    // luma tile row: 5 dwords = cols -4..15
@@ -453,7 +454,7 @@ template <int K> __device__ __forceinline__ pk16 pair_byte(uint32_t a, uint32_t 
 // work on macroblock x - 1 of its row in the SAME iteration: a lag of one column per row, not two (rounds 1 - 5 ran with two:
 // 2 x 67 + 120 = 254 dependent iterations down a 1080p picture instead of 67 + 120 = 187 - what a picture costs where it has a
 // CU to itself: 0.98 -> 0.7x ms at 256 pictures per launch and for the single picture of the drop-in API).
-#define DB_LAG 1
+// (DB_LAG = 1: launch_shared.h - the launch plan costs the band shapes with it)
 #define RING_SLOTS   4
 #define RING_DW      24            // per slot: 4 luma rows x 4 dwords, then 2 planes x 2 rows x 2 dwords
 #define TILE_DW      100           // 16 luma rows x 4 dwords, 2 planes x 8 rows x 2 dwords, +4 so that octets land on different banks
@@ -462,7 +463,7 @@ struct OctLds {                    // per octet: 252 dwords (= 28 modulo 32: the
     uint32_t ring[RING_SLOTS][RING_DW];
     uint32_t edge[EDGE_DW];
 };
-#define MAX_PICS_PER_WG 16             // pictures one workgroup serves (in groups of as many as a wavefront holds)
+// (MAX_PICS_PER_WG, pictures one workgroup serves: launch_shared.h)
 #define MAX_BANDS (MAX_MB_ROWS / 2)
 
 // The kernel is DEFINED in a translation unit of its own (k_deblock.hip, round 6) and only declared where it is launched

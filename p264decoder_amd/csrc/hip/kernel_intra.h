@@ -24,6 +24,7 @@
 #pragma once
 #include <stddef.h>
 #include "device_common.h"
+#include "launch_shared.h"              // (INTRA_ROW_WAVES, INTRA_BS_WGS)
 #include "lane_ops.h"
 #include "residual4x4.h"
 #include "wavefront_sync.h"
@@ -597,7 +598,7 @@ __device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, I
     gstore2(F + mb_chroma_off(g, mbx, mby) + r * 16 + p * 8, make_uint2(pa, pb));
 }
 
-#define INTRA_ROW_WAVES 16          // most wavefronts per picture workgroup
+// (INTRA_ROW_WAVES, most wavefronts per picture workgroup: launch_shared.h)
 #define INTRA_WAVES_PER_EU 8        // (64 registers.  Round 3's kernel spilled at that and was built for 5 wavefronts per SIMD - 96 registers; since
                                     //  the band walk's state is scalar it needs 75 and fits 64 without scratch: config 2 at 5 / 6 / 7 / 8 wavefronts
                                     //  per SIMD 235 / 234 / 242 / 254 k frames/s, scratch/r4_intraocc.sh)
@@ -916,8 +917,7 @@ void k_intra_sparse_scaled(const PicDev *__restrict__ pics, Geom g, int *status,
 // workgroups are neighbours in the dispatch order, so the roles are in flight together all through the launch.
 // Measured at 2048 pictures per launch (scratch/r4_bsfused2.sh, three runs each): own launch 0.59 + (0.37 + 4.78) ms for
 // k_intra_sparse + (k_deblock_bs + k_deblock), fused 0.87 + 4.72 ms - 186.1 k -> 189.1 k frames/s; 2 / 4 / 8 edge-info
-// workgroups per picture: 5.76 / 5.57 / 5.56 ms for the pair against 5.46 with one.
-#define INTRA_BS_WGS 1
+// workgroups per picture: 5.76 / 5.57 / 5.56 ms for the pair against 5.46 with one (INTRA_BS_WGS = 1, launch_shared.h).
 __global__ __launch_bounds__(INTRA_ROW_WAVES * 64, INTRA_SPARSE_WAVES_PER_EU)
 void k_intra_sparse(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra, EdgeInfo *__restrict__ info, uint32_t inv_mbw, int bs_wgs)
 {

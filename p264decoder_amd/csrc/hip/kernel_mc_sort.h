@@ -2,6 +2,7 @@
 // classification of a macroblock, and k_mc_sort*, the counting sort that writes the lists (one workgroup per picture).
 #pragma once
 #include "device_common.h"
+#include "launch_shared.h"           // (the lists' layout and the sort's workgroup size)
 #include "wavefront_sync.h"          // (MAX_MB_ROWS: the row field of a list entry)
 #include "kernel_scaling.h"          // (ScaleDev: which pictures of the batch k_mc_sort_scaled files without residuals)
 
@@ -15,42 +16,11 @@ enum { PC_COPY = 0, PC_H = 1, PC_V = 2, PC_DIAG = 3, PC_C = 4, PC_CH = 5, PC_CV 
 // (p264_mb_mc_1xywh / _01xywh, core/macroblock.c:525-583).
 #define MCY_CLAMP   8               // luma key bits: phase class | window not inside the picture | item has coded luma blocks
 #define MCY_RESID   16
-#define MCY_KEYS    32
 #define MCC_CLAMP   1               // chroma key bits: window not inside the picture (quadrant items: or vectors differing inside) | residual
 #define MCC_RESID   2
 #define MCC_BI      4               // | macroblock of a B picture that predicts from list 1 somewhere (quadrant items only)
-#define MCC_KEYS    8
-enum { ML_YM = 0, ML_YQ = 1, ML_CM = 2, ML_CQ = 3, ML_LISTS = 4 };      // luma macroblocks, luma quadrants, chroma macroblocks, chroma quadrants
-#define MC_MAX_BANDS 32
-#define MC_SORT_THREADS 1024
-__host__ __device__ static inline int mc_chunk_items(int l) { return l == ML_YM ? 4 : l == ML_YQ ? 16 : l == ML_CM ? 8 : 32; }   // items per wavefront
-__host__ __device__ static inline int mc_list_keys(int l) { return l < ML_CM ? MCY_KEYS : MCC_KEYS; }
-
-// Per-picture scratch written by k_mc_sort (32-bit words): [l] chunks in use of list l, then per list one class byte
-// per chunk, then the lists (their entries: "list entries" below).  Same layout for every picture of a batch.
-__host__ __device__ static inline uint32_t mc_entry_words(int pass) { return pass ? 4u : 2u; }
-struct McLayout {
-    uint32_t band_log2, n_bands;
-    uint32_t max_chunks[2 * ML_LISTS], off_cls[2 * ML_LISTS], off_list[2 * ML_LISTS], words;     // [pass * ML_LISTS + list]
-};
-static inline McLayout mc_layout(int mb_w, int mb_h, int band_log2)
-{
-    McLayout L;
-    L.band_log2 = (uint32_t)band_log2;
-    L.n_bands = (uint32_t)((mb_h + (1 << band_log2) - 1) >> band_log2);
-    const uint32_t n_mb = (uint32_t)(mb_w * mb_h);
-    uint32_t at = 16;
-    for (int l = 0; l < 2 * ML_LISTS; l++) {
-        const int t = l % ML_LISTS;
-        const uint32_t items = (t == ML_YM || t == ML_CM) ? n_mb : n_mb * 4u, per = (uint32_t)mc_chunk_items(t);
-        L.max_chunks[l] = (items + L.n_bands * (uint32_t)mc_list_keys(t) * (per - 1)) / per + 1;
-        L.off_cls[l] = at; at += (L.max_chunks[l] + 3) / 4;
-    }
-    at = (at + 15) & ~15u;
-    for (int l = 0; l < 2 * ML_LISTS; l++) { L.off_list[l] = at; at += L.max_chunks[l] * (uint32_t)mc_chunk_items(l % ML_LISTS) * mc_entry_words(l / ML_LISTS); }
-    L.words = (at + 63) & ~63u;
-    return L;
-}
+// (keys per band MCY_KEYS / MCC_KEYS, the lists ML_*, MC_MAX_BANDS, MC_SORT_THREADS, mc_chunk_items, mc_list_keys, mc_entry_words,
+// McLayout and mc_layout - the per-picture scratch this sort writes: launch_shared.h, which the launch plan reads too)
 
 // the list entry a reference index names: negative (list unused) or at / past the list's length = entry 0, on every road
 // (prediction, implicit and explicit weights; the loop filter's pic_of_init reads the same, include/p264hip.h: ref_idx)

@@ -97,9 +97,7 @@ __device__ __forceinline__ int t8_scale_w(int c, int p, uint64_t vrow, int per, 
 // the chroma blocks (plane, block), then all 32 the four 8x8 blocks.  Bound by memory: it re-reads and re-writes the samples of every
 // block that has a residual.
 // ------------------------------------------------------------------------------------------
-#define SCL_THREADS    256
-#define SCL_MBS_PER_WG (SCL_THREADS / 32)
-
+// (SCL_THREADS, SCL_MBS_PER_WG: launch_shared.h, through kernel_t8x8.h)
 // grid: (macroblocks of a picture / SCL_MBS_PER_WG, pictures of the batch)
 __global__ __launch_bounds__(SCL_THREADS)
 void k_scaled_inter(const PicDev *__restrict__ pics, const ScaleDev *__restrict__ scale, Geom g)
@@ -175,13 +173,7 @@ void k_scaled_inter(const PicDev *__restrict__ pics, const ScaleDev *__restrict_
     }
     wave_lds_fence();
     int d[8];
-    if (coded8) {                                          // rows first
-        const int4 lo = *(const int4 *)(tile + r * 8), hi = *(const int4 *)(tile + r * 8 + 4);
-        d[0] = lo.x; d[1] = lo.y; d[2] = lo.z; d[3] = lo.w; d[4] = hi.x; d[5] = hi.y; d[6] = hi.z; d[7] = hi.w;
-        t8_idct1d(d);
-        *(int4 *)(tile + r * 8) = make_int4(d[0], d[1], d[2], d[3]);
-        *(int4 *)(tile + r * 8 + 4) = make_int4(d[4], d[5], d[6], d[7]);
-    }
+    if (coded8) t8_row_pass(tile, r, d);                   // rows first
     wave_lds_fence();
     if (coded8) {                                          // column r, rounded
 #pragma unroll

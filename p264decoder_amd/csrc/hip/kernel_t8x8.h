@@ -12,9 +12,8 @@
 // 32-bit: a conforming stream keeps every value inside 16 bits, anything else still gives a defined result here.
 #pragma once
 #include "device_common.h"
+#include "launch_shared.h"           // (T8_THREADS, T8_MBS_PER_WG)
 
-#define T8_THREADS    256
-#define T8_MBS_PER_WG (T8_THREADS / 32)
 #define T8_BLK_STRIDE 72             // dwords between the 8x8 tiles of a wavefront in LDS: 64 + 8, so that the eight blocks' column reads meet no bank twice
 
 // 8x8 zig-zag frame scan (H.264 8.5.6): scan index -> x + 8 * y
@@ -47,6 +46,17 @@ __device__ __forceinline__ void t8_idct1d(int (&d)[8])
     const int b1 = a1 + (a7 >> 2), b3 = a3 + (a5 >> 2), b5 = (a3 >> 2) - a5, b7 = a7 - (a1 >> 2);
     d[0] = b0 + b7; d[1] = b2 + b5; d[2] = b4 + b3; d[3] = b6 + b1;
     d[4] = b6 - b1; d[5] = b4 - b3; d[6] = b2 - b5; d[7] = b0 - b7;
+}
+
+// The horizontal pass of a block's walk (k_t8x8, k_scaled_inter): rows first (the >> 1 and >> 2 of the stage make the order
+// observable) - row r of the tile, back in place.  d: the lane's eight values, the column pass goes on in them.
+__device__ __forceinline__ void t8_row_pass(int *tile, int r, int (&d)[8])
+{
+    const int4 lo = *(const int4 *)(tile + r * 8), hi = *(const int4 *)(tile + r * 8 + 4);
+    d[0] = lo.x; d[1] = lo.y; d[2] = lo.z; d[3] = lo.w; d[4] = hi.x; d[5] = hi.y; d[6] = hi.z; d[7] = hi.w;
+    t8_idct1d(d);
+    *(int4 *)(tile + r * 8) = make_int4(d[0], d[1], d[2], d[3]);
+    *(int4 *)(tile + r * 8 + 4) = make_int4(d[4], d[5], d[6], d[7]);
 }
 
 // grid: (macroblocks of a picture / T8_MBS_PER_WG, pictures of the batch)
@@ -82,14 +92,7 @@ void k_t8x8(const PicDev *__restrict__ pics, Geom g)
     }
     wave_lds_fence();
     int d[8];
-    // ---- rows first (the >> 1 and >> 2 of the stage make the order observable): row r, back in place
-    if (coded) {
-        const int4 lo = *(const int4 *)(tile + r * 8), hi = *(const int4 *)(tile + r * 8 + 4);
-        d[0] = lo.x; d[1] = lo.y; d[2] = lo.z; d[3] = lo.w; d[4] = hi.x; d[5] = hi.y; d[6] = hi.z; d[7] = hi.w;
-        t8_idct1d(d);
-        *(int4 *)(tile + r * 8) = make_int4(d[0], d[1], d[2], d[3]);
-        *(int4 *)(tile + r * 8 + 4) = make_int4(d[4], d[5], d[6], d[7]);
-    }
+    if (coded) t8_row_pass(tile, r, d);
     wave_lds_fence();
     // ---- column r, rounded, back in place (a lane reads and writes its own column only)
     if (coded) {

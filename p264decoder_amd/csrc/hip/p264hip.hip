@@ -14,9 +14,10 @@
 #include <unordered_map>
 #include "p264hip.h"
 #include "device_common.h"
+#include "launch_plan.h"                    // (BatchKinds, LaunchKnobs, LaunchDevice with its McLayout, plan_launches: what a batch launches)
 #define P264HIP_K_DEBLOCK_DECL_ONLY          // k_deblock lives in k_deblock.hip (its own compiler options: kernel_deblock.h)
 #include "kernel_deblock.h"
-#include "kernel_mc_sort.h"                 // (McLayout, mc_layout, MC_SORT_THREADS, MCE_W_SHIFT, MCE_MAX_MB_W, the k_mc_sort* kernels)
+#include "kernel_mc_sort.h"                 // (MCE_W_SHIFT, MCE_MAX_MB_W, the k_mc_sort* kernels)
 #include "kernel_mc.h"
 #include "kernel_intra.h"
 #include "kernel_t8x8.h"
@@ -107,7 +108,7 @@ __global__ void k_check_records(const p264hip_mb_t *mb, int n_mb, uint32_t n_coe
 }
 
 struct p264hip_ctx {
-    int device = 0, n_cu = 256;
+    int device = 0;
     hipStream_t stream = nullptr;
     Geom g;
     int n_streams = 0, slots = 0, max_pictures = 0;
@@ -135,16 +136,17 @@ struct p264hip_ctx {
     uint64_t upload_copies = 0;            // host -> HBM copies queued by p264hip_upload / _upload_async (one per picture whose arrays lie like a slot)
     uint64_t epoch = 0, done_epoch = 0;    // work queued on the stream / known to have completed (a slot is free for a new producer once its last_use is done)
     EdgeInfo *d_edge = nullptr;            // [batch_cap][n_mb], scratch between k_deblock_bs and k_deblock
-    uint32_t *d_mc = nullptr;              // [batch_cap][ml.words], motion-compensation work lists (k_mc_sort -> k_mc, k_mc_second)
+    uint32_t *d_mc = nullptr;              // [batch_cap][dev.ml.words], motion-compensation work lists (k_mc_sort -> k_mc, k_mc_second)
     uint8_t *d_is_intra = nullptr;         // [batch_cap][n_mb], 1 = intra macroblock (k_mc_sort -> k_intra's collect pass; P / B pictures)
-    McLayout ml;
+    // what the launch plan is a function of, beside the batch (launch_plan.h): the P264AMD_* tuning knobs, read from the environment
+    // ONCE (p264hip_create), and geometry, compute units and work-list layout
+    LaunchKnobs knobs;
+    LaunchDevice dev;
     std::vector<int> stream_seen;          // p264hip_reconstruct: batch index + 1 that last named a stream in the current call
     uint8_t *d_planar = nullptr;           // planar staging for p264hip_read_frame / p264hip_write_frame
     std::vector<uint8_t *> planar_pool;    // p264hip_frame_planar_device: planar I420 frames that stay on the device
     // p264hip_export_frames: the frame index (stream * slots + slot) of every picture of a call, a ring like the batch's
     uint32_t *h_exp[BATCH_RING] = {}, *d_exp[BATCH_RING] = {}; hipEvent_t exp_free[BATCH_RING] = {}; int exp_cap = 0, exp_ring = 0;
-    // tuning knobs, read from the environment ONCE (p264hip_create); 0 = built-in choice
-    int tune_mc_wgs = 0, tune_intra_waves = 0, tune_rb_log2 = 0, tune_pics_per_wg = 0, tune_db_waves = 0, tune_bs_fused = -1, tune_odd_single = -1;
     p264hip_launch_info_t last = {};       // what the last p264hip_reconstruct launched
     hipEvent_t markers[P264HIP_MARKERS] = {};
     int next_marker = 0;
@@ -182,24 +184,14 @@ extern "C" int p264hip_create(p264hip_ctx **out, int device, int mb_w, int mb_h,
     // (one stream's store is addressed by 32-bit offsets through one buffer descriptor, and the kernels use MC_OOB as "an offset
     // beyond any store" for loads that must return zeros - kernel_mc.h: the store has to end at or below it)
     if (c->frame_bytes * (size_t)slots > (size_t)MC_OOB) { delete c; return fail(P264HIP_EINVAL, "frame store of one stream exceeds %u bytes (%d slots of %zu bytes)", MC_OOB, slots, c->frame_bytes); }
-    {   // locality band of the motion-compensation lists: 16 macroblock rows unless that makes more than MC_MAX_BANDS bands
-        int band_log2 = 4;
-        if (const char *e = getenv("P264AMD_MC_BAND_LOG2")) { int v = atoi(e); if (v >= 0 && v <= 9) band_log2 = v; }
-        while (((mb_h + (1 << band_log2) - 1) >> band_log2) > MC_MAX_BANDS) band_log2++;
-        c->ml = mc_layout(mb_w, mb_h, band_log2);
-    }
     c->stream_seen.assign((size_t)n_streams, 0);
     c->pics.resize((size_t)max_pictures);
-    { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0) c->n_cu = v; }
-    c->last.compute_units = c->n_cu;                        // (p264hip_last_launch before the first batch: the device's size)
+    int n_cu = 256;
+    { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0) n_cu = v; }
+    c->knobs = launch_knobs_read(getenv);
+    c->dev = launch_device(mb_w, mb_h, n_cu, c->knobs);
+    c->last.compute_units = n_cu;                           // (p264hip_last_launch before the first batch: the device's size)
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (const char *env = getenv("P264AMD_MC_WGS_PER_PIC")) c->tune_mc_wgs = atoi(env);
-    if (const char *env = getenv("P264AMD_INTRA_WAVES")) c->tune_intra_waves = atoi(env);
-    if (const char *env = getenv("P264AMD_DEBLOCK_RB_LOG2")) c->tune_rb_log2 = atoi(env);
-    if (const char *env = getenv("P264AMD_DEBLOCK_ODD_SINGLE")) c->tune_odd_single = atoi(env) != 0;   /* 0: never, 1: whenever the shape allows it */
-    if (const char *env = getenv("P264AMD_DEBLOCK_PICS_PER_WG")) c->tune_pics_per_wg = atoi(env);
-    if (const char *env = getenv("P264AMD_DEBLOCK_WAVES")) c->tune_db_waves = atoi(env);
-    if (const char *env = getenv("P264AMD_BS_FUSED")) { c->tune_bs_fused = atoi(env); if (c->tune_bs_fused > 16) c->tune_bs_fused = 16; }   // 0: own launch; n: n edge-info workgroups per picture in the k_intra_sparse launch
     if (e == hipSuccess) e = hipMalloc((void **)&c->frames, c->frame_bytes * (size_t)n_streams * slots);
     if (e == hipSuccess) e = hipMemsetAsync(c->frames, 0, c->frame_bytes * (size_t)n_streams * slots, c->stream);
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_status, sizeof(int));
@@ -766,7 +758,7 @@ static int batch_reserve(p264hip_ctx *c, int n)
     }
     int rc = grow(c, (void **)&c->d_is_intra, nullptr, (size_t)n * c->g.n_mb, 0, false, WAIT_NONE, "the batch");
     if (rc || (rc = grow(c, (void **)&c->d_edge, nullptr, (size_t)n * c->g.n_mb * sizeof(EdgeInfo), 0, false, WAIT_NONE, "the batch")) ||
-        (rc = grow(c, (void **)&c->d_mc, nullptr, (size_t)n * c->ml.words * sizeof(uint32_t), 0, false, WAIT_NONE, "the batch"))) return rc;
+        (rc = grow(c, (void **)&c->d_mc, nullptr, (size_t)n * c->dev.ml.words * sizeof(uint32_t), 0, false, WAIT_NONE, "the batch"))) return rc;
     c->batch_cap = n;
     return 0;
 }
@@ -831,13 +823,7 @@ static PicDev picdev_of(p264hip_ctx *c, const PicSlot &s, int st)
     return d;
 }
 
-// What the batch holds - the kernel instances and launch shapes follow from it: any picture with inter macroblocks / any B picture /
-// any I picture / any explicit weights / any unweighted P picture whose list 0 holds one frame at several indices / any picture
-// whose inter macroblocks may use the 8x8 transform / any picture whose Intra4x4 records may carry P264_MB_I8X8; sc: how many
-// pictures have scaling_lists
-struct BatchKinds { bool p = false, b = false, i = false, wp = false, dup = false, t8 = false, i8 = false; int sc = 0; };
-
-// the batch's streams and slots checked (nothing is queued yet), one PicDev per picture in hb
+// the batch's streams and slots checked (nothing is queued yet), one PicDev per picture in hb; kinds: what the batch holds (launch_plan.h)
 static int batch_fill(p264hip_ctx *c, const int *pic_ids, const int *streams, int n, PicDev *hb, ScaleDev *hs, BatchKinds *kinds)
 {
     for (int i = 0; i < n; i++) {                          // two pictures of one call must not share a stream: they would race on its frames
@@ -868,173 +854,90 @@ static int batch_fill(p264hip_ctx *c, const int *pic_ids, const int *streams, in
     return 0;
 }
 
-// The launch shapes: functions of the geometry, the compute units, the batch size, the batch's kinds and the tune_* knobs - no
-// HIP call in them.  Each fills its part of p264hip_launch_info_t.
-// k_mc: every picture gets the same number of workgroups, which split into the four roles on the device.  Enough workgroups per
-// picture to fill the chip a few times over, no more than there can be chunks (four wavefronts per workgroup, one chunk per
-// wavefront pass).
-static int mc_wgs_per_picture(const p264hip_ctx *c, int n)
-{
-    int wgs = (c->n_cu * 48 + n - 1) / n;   // (a dozen rounds of workgroups on small batches.  Round 5, 256 pictures per launch: 48 / 64 / 96 / 128 / 192 / 256
-                                       //  per picture -> 0.685 / 0.687 / 0.691 / 0.704 / 0.724 / 0.751 ms for the stage - a wavefront's first chunk has no prefetch)
-    if (wgs < 48) wgs = 48;            // (2048 pictures: 24 / 32 / 48 / 64 / 96 per picture -> 5.34 / 5.31 / 5.24 / 5.31 / 5.34 ms; with 24 the stage's reads grew by half:
-                                       //  a picture's roles drift apart and stop sharing reference lines in L2)
-    int max_wgs = 0;
-    for (int l = 0; l < ML_LISTS; l++) max_wgs += (int)(c->ml.max_chunks[l] + 3) / 4;
-    if (wgs > max_wgs) wgs = max_wgs;
-    if (c->tune_mc_wgs >= 4 && c->tune_mc_wgs <= max_wgs) wgs = c->tune_mc_wgs;
-    return wgs < 4 ? 4 : wgs;
-}
-
-// k_intra / k_intra_sparse, one workgroup per picture and role: 16 wavefronts while every picture can have a CU to itself, else 8 or
-// 4 so that two or four pictures share a CU (measured +19 % at 512 and +9 % at 1024 pictures; 2048: 2 / 4 / 8 / 16 -> 1.02 / 0.87 /
-// 0.90 / 1.10 ms)
-static int intra_waves(const p264hip_ctx *c, int n)
-{
-    if (c->tune_intra_waves >= 1 && c->tune_intra_waves <= INTRA_ROW_WAVES) return c->tune_intra_waves;
-    return n > 2 * c->n_cu ? INTRA_ROW_WAVES / 4 : n > c->n_cu ? INTRA_ROW_WAVES / 2 : INTRA_ROW_WAVES;
-}
-
-// edge-info workgroups per picture inside the k_intra_sparse launch (P pictures only, by index: no B picture, no explicit weights,
-// no frame twice in a list, no 8x8 transform - the fused role is compiled without its edge mask), 0: the pass takes its own launch
-// (k_deblock_bs)
-static int edge_info_fused(const p264hip_ctx *c, const BatchKinds &k)
-{
-    if (k.i || k.b || k.wp || k.dup || k.t8 || k.i8 || k.sc || c->tune_bs_fused == 0) return 0;
-    return c->tune_bs_fused > 0 ? c->tune_bs_fused : INTRA_BS_WGS;
-}
-
-static void deblock_shape(const p264hip_ctx *c, int n, p264hip_launch_info_t *li)
-{
-    const Geom &g = c->g;
-    // pictures per workgroup = as many as it takes to cover the batch with one workgroup per CU (a second, half-empty round
-    // of workgroups costs more than sharing a workgroup: 1280 pictures as 320 workgroups of 4 took 5.35 ms, as 256 of 5 ...)
-    int per_wg = (n + c->n_cu - 1) / c->n_cu;
-    if (per_wg < 1) per_wg = 1;
-    if (per_wg > MAX_PICS_PER_WG) per_wg = MAX_PICS_PER_WG;
-    // bands of 8 rows of one picture per wavefront while every picture has a CU to itself, else 4 rows of two pictures; a
-    // workgroup with more pictures than a wavefront holds (8 >> rb_log2) works on them in groups (units = band x group).
-    // (Round 4: 2 rows x 4 pictures ran as fast, 2.70 ms, but every second row's bottom lines cross a band - 0.4 GB more
-    // through memory per launch.)
-    // Which shape: the stage's time follows the wavefront-iterations it issues (round 5: 1.07 ms per 16 units of 127 iterations at
-    // 2 ... 15 pictures per workgroup, half-empty units included - it is bound by vector-instruction issue).  Bands of 4 rows hold
-    // two pictures per wavefront: an odd picture count leaves one unit in every band half empty; bands of 8 rows hold one picture,
-    // but run 8 iterations longer and the last band of a 68-row picture is half empty.  Take the cheaper one.
-    auto units_cost = [&](int lg) {
-        const int rows = 1 << lg, pw = 8 >> lg;
-        const long bands = (g.mb_h + rows - 1) / rows, groups = (per_wg + pw - 1) / pw;
-        return bands * groups * (long)(g.mb_w + 1 + DB_LAG * (rows - 1));
-    };
-    int rb_log2 = units_cost(3) < units_cost(2) ? 3 : 2;
-    // an odd number (>= 3) of pictures: the pairs in bands of 4 rows, the last picture alone in bands of 8 (k_deblock, odd_single)
-    const long cost_mixed = (per_wg >= 3 && (per_wg & 1)) ? ((g.mb_h + 3) / 4) * (long)(per_wg / 2) * (g.mb_w + 1 + 3 * DB_LAG) + ((g.mb_h + 7) / 8) * (long)(g.mb_w + 1 + 7 * DB_LAG) : -1;
-    int odd_single = cost_mixed >= 0 && cost_mixed < units_cost(rb_log2);
-    if (odd_single) rb_log2 = 2;
-    if (c->tune_rb_log2 >= 1 && c->tune_rb_log2 <= 3) { rb_log2 = c->tune_rb_log2; odd_single = 0; }
-    if (c->tune_pics_per_wg >= 1 && c->tune_pics_per_wg <= MAX_PICS_PER_WG) { per_wg = c->tune_pics_per_wg; odd_single = 0; }
-    if (c->tune_odd_single >= 0) odd_single = c->tune_odd_single && rb_log2 == 2 && per_wg >= 3 && (per_wg & 1);
-    const int n_bands = (g.mb_h + (1 << rb_log2) - 1) >> rb_log2;
-    const int n_units = !odd_single ? n_bands * ((per_wg + (8 >> rb_log2) - 1) / (8 >> rb_log2)) : n_bands * (per_wg / 2) + (g.mb_h + 7) / 8;
-    int waves = n_units < ROW_WAVES ? n_units : ROW_WAVES;
-    if (c->tune_db_waves >= 1 && c->tune_db_waves < waves) waves = c->tune_db_waves;
-    li->deblock_pics_per_wg = per_wg; li->deblock_rb_log2 = rb_log2; li->deblock_waves = waves; li->deblock_wgs = (n + per_wg - 1) / per_wg;
-    li->deblock_odd_single = odd_single;
-}
-
-// The launches, in stream order.  batch: the n PicDevs on the device; a failed launch is reported by p264hip_reconstruct's
-// hipGetLastError behind the last of them.
+// The launches, in stream order: each issues its stage of the batch's plan (launch_plan.h: which instance, which shape and why) and
+// decides nothing.  batch: the n PicDevs on the device, scale: their ScaleDevs (copied for scaled batches only); a failed launch is
+// reported by p264hip_reconstruct's hipGetLastError behind the last of them.
 static uint32_t inv_mb_w(const p264hip_ctx *c) { return (uint32_t)(((1ull << 32) - 1) / (unsigned)c->g.mb_w); }
+static dim3 grid_of(const LaunchShape &s) { return dim3(s.grid_x, s.grid_y); }
 
 // motion compensation + residual of all inter macroblocks: device-side counting sort of the work items by what the
 // interpolation has to do, then the luma and chroma kernels over the sorted lists (kernel_mc.h), side by side
-static void launch_inter(p264hip_ctx *c, const PicDev *batch, const ScaleDev *scale, int n, const BatchKinds &k)
+static void launch_inter(p264hip_ctx *c, const PicDev *batch, const ScaleDev *scale, const LaunchPlan &pl)
 {
+    if (pl.sort == SortKernel::none) return;
     ScopedStamp t(c, 0);
     const Geom g = c->g;
-    const McLayout ml = c->ml;
-    // (a picture with scaling_lists in the batch: the instance that files such a picture's residuals as absent - k_scaled_inter adds them)
-    if (k.sc) hipLaunchKernelGGL((k.b || k.wp) ? k_mc_sort_scaled : k_mc_sort_scaled_p, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, batch, c->d_mc, g, ml, inv_mb_w(c), c->d_is_intra, scale);
-    else
-    // (explicit weighted prediction in the batch: the instances that route such pictures to the weighted class, kernel_mc_sort.h)
-    if (k.b) hipLaunchKernelGGL(k.wp ? k_mc_sort_b_wp : k_mc_sort_b, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, batch, c->d_mc, g, ml, inv_mb_w(c), c->d_is_intra);
-    else hipLaunchKernelGGL(k.wp ? k_mc_sort_wp : k_mc_sort, dim3(n), dim3(MC_SORT_THREADS), 0, c->stream, batch, c->d_mc, g, ml, inv_mb_w(c), c->d_is_intra);
-    // one launch for luma / chroma, macroblock / quadrant items (k_mc)
-    const int wgs = c->last.mc_wgs_per_picture = mc_wgs_per_picture(c, n);
-    // (a batch with explicit weighted prediction somewhere: the instance with the weighted generic class, kernel_mc.h: k_mc_wp)
-    hipLaunchKernelGGL(k.wp ? k_mc_wp : k_mc, dim3(((size_t)wgs * n + 7) / 8 * 8), dim3(256), 0, c->stream, batch, (const uint32_t *)c->d_mc, g, ml,
-                       wgs, wgs * n, (uint32_t)(((1ull << 32) - 1) / (unsigned)wgs));
-    // B pictures: the blocks that predict from both lists get their second prediction (and their residual) in a second pass
-    if (k.b)
-        hipLaunchKernelGGL(k_mc_second, dim3(((size_t)wgs * n + 7) / 8 * 8), dim3(256), 0, c->stream, batch, (const uint32_t *)c->d_mc, g, ml,
-                           wgs, wgs * n, (uint32_t)(((1ull << 32) - 1) / (unsigned)wgs));
+    const McLayout ml = c->dev.ml;
+#define SORT(kernel, ...) hipLaunchKernelGGL(kernel, grid_of(pl.sort_shape), dim3(pl.sort_shape.threads), 0, c->stream, batch, c->d_mc, g, ml, inv_mb_w(c), c->d_is_intra, ##__VA_ARGS__)
+    switch (pl.sort) {
+    case SortKernel::none:     break;
+    case SortKernel::plain:    SORT(k_mc_sort); break;
+    case SortKernel::wp:       SORT(k_mc_sort_wp); break;
+    case SortKernel::b:        SORT(k_mc_sort_b); break;
+    case SortKernel::b_wp:     SORT(k_mc_sort_b_wp); break;
+    case SortKernel::scaled:   SORT(k_mc_sort_scaled, scale); break;
+    case SortKernel::scaled_p: SORT(k_mc_sort_scaled_p, scale); break;
+    }
+#undef SORT
+    // one launch for luma / chroma, macroblock / quadrant items; B pictures: a second pass over the second list set
+#define MC(kernel) hipLaunchKernelGGL(kernel, grid_of(pl.mc_shape), dim3(pl.mc_shape.threads), 0, c->stream, batch, (const uint32_t *)c->d_mc, g, ml, \
+                                      pl.info.mc_wgs_per_picture, pl.mc_wgs_total, pl.mc_inv_wgs)
+    switch (pl.mc) {
+    case McKernel::none:  break;
+    case McKernel::plain: MC(k_mc); break;
+    case McKernel::wp:    MC(k_mc_wp); break;
+    }
+    if (pl.mc_second) MC(k_mc_second);
+#undef MC
 }
 
-// luma residual of the macroblocks with P264_MB_T8X8 (kernel_t8x8.h), on top of the prediction the inter launches left in the
-// frame store; in front of the intra launch, whose macroblocks predict from their inter neighbours' finished samples.  Counts
-// as inter time (timing index 0).
-static void launch_t8x8(p264hip_ctx *c, const PicDev *batch, int n)
+// the residuals the inter launches left out, added in place on top of the prediction in the frame store: the luma of the macroblocks
+// with P264_MB_T8X8 (kernel_t8x8.h), or - scaled batches - everything of the scaled pictures' inter macroblocks and the 8x8 blocks of
+// every picture (kernel_scaling.h).  Counts as inter time (timing index 0).
+static void launch_residual(p264hip_ctx *c, const PicDev *batch, const ScaleDev *scale, const LaunchPlan &pl)
 {
+    if (pl.residual == ResidualKernel::none) return;
     ScopedStamp t(c, 0);
-    const int per_pic = (c->g.n_mb + T8_MBS_PER_WG - 1) / T8_MBS_PER_WG;
-    c->last.t8x8_wgs = per_pic * n;
-    hipLaunchKernelGGL(k_t8x8, dim3((unsigned)per_pic, (unsigned)n), dim3(T8_THREADS), 0, c->stream, batch, c->g);
+    const dim3 grid = grid_of(pl.residual_shape), block(pl.residual_shape.threads);
+    switch (pl.residual) {
+    case ResidualKernel::none:         break;
+    case ResidualKernel::t8x8:         hipLaunchKernelGGL(k_t8x8, grid, block, 0, c->stream, batch, c->g); break;
+    case ResidualKernel::scaled_inter: hipLaunchKernelGGL(k_scaled_inter, grid, block, 0, c->stream, batch, scale, c->g); break;
+    }
 }
 
-// the residual of the inter macroblocks of the batch's scaled pictures, and the 8x8 blocks of every picture of the batch
-// (kernel_scaling.h), where launch_t8x8 runs in other batches.  Counts as inter time.
-static void launch_scaled_inter(p264hip_ctx *c, const PicDev *batch, const ScaleDev *scale, int n)
-{
-    ScopedStamp t(c, 0);
-    const int per_pic = (c->g.n_mb + SCL_MBS_PER_WG - 1) / SCL_MBS_PER_WG;
-    hipLaunchKernelGGL(k_scaled_inter, dim3((unsigned)per_pic, (unsigned)n), dim3(SCL_THREADS), 0, c->stream, batch, scale, c->g);
-}
-
-static void launch_intra(p264hip_ctx *c, const PicDev *batch, const ScaleDev *scale, int n, const BatchKinds &k)
+static void launch_intra(p264hip_ctx *c, const PicDev *batch, const ScaleDev *scale, const LaunchPlan &pl)
 {
     ScopedStamp t(c, 1);
-    const int waves = c->last.intra_waves = intra_waves(c, n);
-    // (a picture of the batch has scaling_lists: the instances that scale with the table - kernel_intra.h; they know Intra 8x8, and
-    // the edge info has its own launch)
-    if (k.sc) {
-        c->last.intra_i8 = k.i8 ? 1 : 0;
-        if (k.i) hipLaunchKernelGGL(k_intra_scaled, dim3(n, 2), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status, (const uint8_t *)c->d_is_intra, scale);
-        else hipLaunchKernelGGL(k_intra_sparse_scaled, dim3((unsigned)n * 2), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status,
-                                (const uint8_t *)c->d_is_intra, scale);
-        return;
+    const uint8_t *is_intra = c->d_is_intra;
+#define INTRA(kernel, ...) hipLaunchKernelGGL(kernel, grid_of(pl.intra_shape), dim3(pl.intra_shape.threads), (size_t)pl.info.intra_waves * sizeof(IntraLds), c->stream, \
+                                              batch, c->g, c->d_status, is_intra, ##__VA_ARGS__)
+    switch (pl.intra) {
+    case IntraKernel::dense:         INTRA(k_intra); break;
+    case IntraKernel::sparse:        INTRA(k_intra_sparse, c->d_edge, inv_mb_w(c), pl.info.edge_info_fused); break;      // (with the edge-info workgroups, if any)
+    case IntraKernel::dense_i8:      INTRA(k_intra_i8); break;
+    case IntraKernel::sparse_i8:     INTRA(k_intra_sparse_i8, c->d_edge, inv_mb_w(c), 0); break;
+    case IntraKernel::dense_scaled:  INTRA(k_intra_scaled, scale); break;
+    case IntraKernel::sparse_scaled: INTRA(k_intra_sparse_scaled, scale); break;
     }
-    // (a picture of the batch may hold Intra 8x8 macroblocks: the instances that know them - kernel_intra.h; the edge info then has
-    // its own launch, edge_info_fused)
-    if (k.i8) {
-        c->last.intra_i8 = 1;
-        if (k.i) hipLaunchKernelGGL(k_intra_i8, dim3(n, 2), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status, (const uint8_t *)c->d_is_intra);
-        else hipLaunchKernelGGL(k_intra_sparse_i8, dim3((unsigned)n * 2), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status,
-                                (const uint8_t *)c->d_is_intra, c->d_edge, inv_mb_w(c), 0);
-        return;
-    }
-    // luma and chroma of a picture are independent chains: as two workgroups they run side by side
-    if (k.i) hipLaunchKernelGGL(k_intra, dim3(n, 2), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status, (const uint8_t *)c->d_is_intra);
-    else {
-        // (P / B pictures only.  Batches without B pictures: the loop filter's edge info is computed by extra workgroups of this
-        // launch, kernel_intra.h)
-        const int bs_wgs = c->last.edge_info_fused = edge_info_fused(c, k);
-        hipLaunchKernelGGL(k_intra_sparse, dim3((unsigned)n * (2 + bs_wgs)), dim3(waves * 64), (size_t)waves * sizeof(IntraLds), c->stream, batch, c->g, c->d_status,
-                           (const uint8_t *)c->d_is_intra, c->d_edge, inv_mb_w(c), bs_wgs);
-    }
+#undef INTRA
 }
 
-static void launch_deblock(p264hip_ctx *c, const PicDev *batch, int n, const BatchKinds &k)
+// edge info (boundary strengths, averaged QPs per edge class: everything about an edge that does not depend on samples) where the
+// intra launch did not carry it, then the loop filter
+static void launch_deblock(p264hip_ctx *c, const PicDev *batch, const LaunchPlan &pl)
 {
     ScopedStamp t(c, 2);
     const Geom g = c->g;
-    // edge info (boundary strengths, averaged QPs per edge class): everything about an edge that does not depend on samples
-    // (explicit weighted prediction, a P list with one frame twice: the two-list instance, which compares reference pictures rather
-    // than indices - kernel_deblock.h)
-    if (k.b || k.wp || k.dup) hipLaunchKernelGGL(k_deblock_bs<true>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, batch, g, c->d_edge, inv_mb_w(c));
-    else if (!c->last.edge_info_fused) hipLaunchKernelGGL(k_deblock_bs<false>, dim3((g.n_mb + 255) / 256, n), dim3(256), 0, c->stream, batch, g, c->d_edge, inv_mb_w(c));
-    p264hip_launch_info_t &li = c->last;
-    deblock_shape(c, n, &li);
-    hipLaunchKernelGGL(k_deblock, dim3(li.deblock_wgs), dim3(li.deblock_waves * 64), 0, c->stream, batch, g,
-                       (const EdgeInfo *)c->d_edge, c->d_status, n, li.deblock_rb_log2, li.deblock_pics_per_wg, li.deblock_odd_single);
+    const dim3 grid = grid_of(pl.edge_shape), block(pl.edge_shape.threads);
+    switch (pl.edge) {
+    case EdgeInfoRoad::fused:         break;
+    case EdgeInfoRoad::bs_by_picture: hipLaunchKernelGGL(k_deblock_bs<true>, grid, block, 0, c->stream, batch, g, c->d_edge, inv_mb_w(c)); break;
+    case EdgeInfoRoad::bs_by_index:   hipLaunchKernelGGL(k_deblock_bs<false>, grid, block, 0, c->stream, batch, g, c->d_edge, inv_mb_w(c)); break;
+    }
+    const p264hip_launch_info_t &li = pl.info;
+    hipLaunchKernelGGL(k_deblock, grid_of(pl.deblock_shape), dim3(pl.deblock_shape.threads), 0, c->stream, batch, g,
+                       (const EdgeInfo *)c->d_edge, c->d_status, li.pictures, li.deblock_rb_log2, li.deblock_pics_per_wg, li.deblock_odd_single);
 }
 
 extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int *streams, int n)
@@ -1047,6 +950,8 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     HIPCHK(hipEventSynchronize(c->batch_free[r]));            // the copy that last used this staging buffer is done
     BatchKinds k;
     if ((rc = batch_fill(c, pic_ids, streams, n, c->h_batch[r], c->h_scale[r], &k))) return rc;
+    const LaunchPlan plan = plan_launches(c->dev, c->knobs, k, n);
+    c->last = plan.info;
     // from here on work that reads the batch's input slots is (about to be) queued: the slots carry the new epoch BEFORE the first
     // launch, so that whichever way this function returns - a launch error half-way included - a later p264hip_input_reserve
     // of one of them waits for the stream instead of letting a peer overwrite a block under running kernels
@@ -1054,15 +959,12 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     for (int i = 0; i < n; i++) stamp(c, c->pics[(size_t)pic_ids[i]]);
     ScopedStamp whole(c, 3);
     HIPCHK(hipMemcpyAsync(c->d_batch[r], c->h_batch[r], (size_t)n * sizeof(PicDev), hipMemcpyHostToDevice, c->stream));
-    if (k.sc) HIPCHK(hipMemcpyAsync(c->d_scale[r], c->h_scale[r], (size_t)n * sizeof(ScaleDev), hipMemcpyHostToDevice, c->stream));
+    if (plan.copy_scale_table) HIPCHK(hipMemcpyAsync(c->d_scale[r], c->h_scale[r], (size_t)n * sizeof(ScaleDev), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->batch_free[r], c->stream));
-    memset(&c->last, 0, sizeof c->last);
-    c->last.pictures = n; c->last.compute_units = c->n_cu; c->last.scaled_pictures = k.sc;
-    if (k.p) launch_inter(c, c->d_batch[r], c->d_scale[r], n, k);
-    if (k.sc) { if (k.p) launch_scaled_inter(c, c->d_batch[r], c->d_scale[r], n); }     // (it owns the batch's 8x8 blocks too: no k_t8x8 beside it)
-    else if (k.t8) launch_t8x8(c, c->d_batch[r], n);
-    launch_intra(c, c->d_batch[r], c->d_scale[r], n, k);
-    launch_deblock(c, c->d_batch[r], n, k);
+    launch_inter(c, c->d_batch[r], c->d_scale[r], plan);
+    launch_residual(c, c->d_batch[r], c->d_scale[r], plan);
+    launch_intra(c, c->d_batch[r], c->d_scale[r], plan);
+    launch_deblock(c, c->d_batch[r], plan);
     HIPCHK(hipGetLastError());
     return P264HIP_OK;
 }

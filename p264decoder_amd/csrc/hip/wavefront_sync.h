@@ -10,8 +10,8 @@
 // dependence on dispatch order or XCD placement.  Every spin is bounded.
 #pragma once
 #include "device_common.h"
+#include "launch_shared.h"           // (ROW_WAVES: wavefronts per picture workgroup, 1024 threads)
 
-#define ROW_WAVES      16            // wavefronts per picture workgroup (1024 threads)
 #define MAX_MB_ROWS    512
 #define SPIN_LIMIT     (1 << 22)
 #define WAIT_SLEEP     32            // x64 cycles between polls: a polling wave must not eat the CU's scalar issue slots

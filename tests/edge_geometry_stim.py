@@ -119,7 +119,7 @@ def is_scaled(st):
 
 
 def runs_k_t8x8(st):
-    """the picture alone makes a flat batch launch k_t8x8 (p264hip.hip: BatchKinds.t8)"""
+    """the picture alone makes a flat batch launch k_t8x8 (batch_fill in p264hip.hip fills BatchKinds.t8, launch_plan.h turns it into the launch)"""
     return bool(int(st.pic.desc.transform_8x8) & ~N.T8X8_INTRA) and int(st.pic.desc.slice_type) != N.SLICE_I
 
 
