@@ -29,8 +29,8 @@
 #include "residual4x4.h"
 #include "wavefront_sync.h"
 #include "kernel_deblock.h"             // (edge_info_of: the edge-info role of k_intra_sparse)
-#include "kernel_t8x8.h"                // (c_scan8x8, t8_scale, t8_idct1d: the residual of Intra 8x8 macroblocks)
-#include "kernel_scaling.h"             // (ScaleDev, scaling_to_lds, scale_cols_w, chroma_dc_level_w, t8_scale_w: the SC instances)
+#include "kernel_t8x8.h"                // (t8_scatter with T8Flat, t8_idct1d: the residual of Intra 8x8 macroblocks)
+#include "kernel_scaling.h"             // (ScaleDev, scaling_to_lds, scale_cols_w, scaling_list8: the SC instances)
 
 #define IT_STRIDE 24               // luma tile: row -1..15, byte 3 = left column, 4..19 = MB, 20..23 = top-right
 #define CT_STRIDE 12               // chroma tile (one per plane): byte 3 = left column, 4..11 = MB
@@ -164,7 +164,7 @@ __device__ __forceinline__ uint32_t lut8_entry(int mode, int x, int y)
 // whose record carries P264_MB_I8X8 takes the Intra 8x8 road, told apart per group as I_PCM and Intra16x16 are.  Its lane plan:
 //   levels    lane l = row octet l & 7 (scan positions 8r .. 8r+7) of 8x8 blocks (l >> 3) and 2 + (l >> 3): two loads at the top;
 //   residual  two passes of eight lanes per block pair (blocks 0, 1 then 2, 3), lane = row, then column, of its block exactly as in
-//             k_t8x8 (scan, t8_scale, t8_idct1d on rows, then on columns, (v + 32) >> 6, all 32-bit); the 2 x 64 ints of a pass live
+//             k_t8x8 (t8_scatter, t8_idct1d on rows, then on columns, (v + 32) >> 6, all 32-bit); the 2 x 64 ints of a pass live
 //             in the group's res[] area, the results wait in registers and are parked there as int16 (saturated: the sum with a
 //             sample is clipped to 0 .. 255 anyway) once both passes are through - block k at res[64 k], raster;
 //   edge      per block the 25 reference samples straight out of the tile (128 where the neighbour is missing, the row above's
@@ -176,8 +176,9 @@ __device__ __forceinline__ uint32_t lut8_entry(int mode, int x, int y)
 //
 // SC (k_intra_scaled / k_intra_sparse_scaled, the instances a batch takes when one of its pictures has scaling_lists; built with I8):
 // the levels are scaled with the picture's intra lists - 0 (luma 4x4 blocks and the Intra16x16 DC), 6 (Intra 8x8 blocks); 1 and 2 in
-// intra_chroma4 - read from sw, the workgroup's table in raster order (kernel_scaling.h), in 32 bits.  A flat picture of such a
-// batch has an all-16 table there.  With SC = false sw is not looked at.
+// intra_chroma4 - read from sw, the workgroup's table in raster order (kernel_scaling.h), in 32 bits; t8_scatter takes list 6 as its
+// source of weights where the other instances hand it T8Flat.  A flat picture of such a batch has an all-16 table there.  With
+// SC = false sw is not looked at.
 template <bool I8, bool SC>
 __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, IntraGrp &L, const uint32_t *lut, const uint32_t *lut8, const uint8_t *sw, int mbx, int mby, const uint4 rec, int l)
 {
@@ -310,14 +311,8 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
                 const bool c8 = res8 && (ps ? c8b : c8a);
                 int d[8];
                 if (c8) {
-                    const uint2 sc = *(const uint2 *)(c_scan8x8 + r * 8);
-                    const uint32_t lw[4] = { ps ? lb.x : la.x, ps ? lb.y : la.y, ps ? lb.z : la.z, ps ? lb.w : la.w };
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        const int c = (i & 1) ? (int)lw[i >> 1] >> 16 : (int)(int16_t)(lw[i >> 1] & 0xffffu);
-                        const int p = (int)(((i < 4 ? sc.x : sc.y) >> (8 * (i & 3))) & 63u);
-                        t8[p] = SC ? t8_scale_w(c, p, vrow, per, (int)sw[SCL_8X8_AT + p]) : t8_scale(c, p, vrow, per);
-                    }
+                    if constexpr (SC) t8_scatter(ps ? lb : la, r, vrow, per, t8, scaling_list8(sw, 6));
+                    else t8_scatter(ps ? lb : la, r, vrow, per, t8, T8Flat());
                 }
                 wave_lds_fence();
                 if (c8) {                                   // rows first
@@ -612,19 +607,27 @@ __device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, I
 #define INTRA_FREE_CAP   256        // entries per list (uint16 macroblock index); macroblocks beyond it stay in the band walk
 #define INTRA_MASKS      160        // pictures of up to this many row windows (rows x windows of 64 macroblocks): 1080p has 136
 struct IntraSync { int progress[MAX_MB_ROWS / INTRA_BAND + 1]; };            // per band: columns of its last row that are final
+// What a workgroup of an instance keeps in static LDS.  The two tables of the High-profile instances are members of no size where
+// the instance has no use for them: k_intra / k_intra_sparse hold what they always held.
+template <bool I8, bool SC>
 struct IntraShared {
     IntraSync sync;
     uint32_t lut[INTRA_LUT_ENTRIES];
     uint16_t free_list[2][INTRA_FREE_CAP];
     unsigned long long m_intra[INTRA_MASKS], m_walk[INTRA_MASKS];   // per row window: intra macroblocks / those left to the band walk
     int free_n[2];
+    // (both read in 16-byte words: a lane's four places of a row of lut8, a 4x4 list of sw)
+    alignas(I8 ? 16 : 4) uint32_t lut8[I8 ? INTRA_LUT8_ENTRIES : 0];    // lut8_entry: the places of Intra 8x8 prediction
+    alignas(SC ? 16 : 1) uint8_t sw[SC ? P264HIP_SCALING_BYTES : 0];    // the picture's scaling table in raster order (kernel_scaling.h)
 };
-template <bool I8, bool SC = false>
-__device__ __forceinline__ void intra_picture(IntraShared &sh, uint32_t *lut8, const PicDev *__restrict__ pics, const Geom &g, int *status, const uint8_t *__restrict__ is_intra_all,
-                                              const int pic_index, const bool chroma_role, uint8_t *sw = nullptr, const ScaleDev *__restrict__ scale = nullptr)
+// scale: the batch's ScaleDev array (the SC instances; the others pass nullptr, nothing reads it)
+template <bool I8, bool SC>
+__device__ __forceinline__ void intra_picture(IntraShared<I8, SC> &sh, const PicDev *__restrict__ pics, const Geom &g, int *status, const uint8_t *__restrict__ is_intra_all,
+                                              const int pic_index, const bool chroma_role, const ScaleDev *__restrict__ scale)
 {
     IntraSync &sync = sh.sync;
-    uint32_t *lut = sh.lut;
+    uint32_t *lut = sh.lut, *lut8 = sh.lut8;
+    uint8_t *sw = sh.sw;
     uint16_t (*free_list)[INTRA_FREE_CAP] = sh.free_list;
     unsigned long long *m_intra = sh.m_intra, *m_walk = sh.m_walk;
     int *free_n = sh.free_n;
@@ -865,28 +868,25 @@ __device__ __forceinline__ void intra_picture(IntraShared &sh, uint32_t *lut8, c
 __global__ __launch_bounds__(INTRA_ROW_WAVES * 64, INTRA_WAVES_PER_EU)
 void k_intra(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra)
 {
-    __shared__ IntraShared sh;
-    intra_picture<false>(sh, nullptr, pics, g, status, is_intra, (int)blockIdx.x, blockIdx.y != 0);
+    __shared__ IntraShared<false, false> sh;
+    intra_picture(sh, pics, g, status, is_intra, (int)blockIdx.x, blockIdx.y != 0, nullptr);
 }
 // The Intra 8x8 instances (intra_luma4<true>): what a batch launches in place of the two kernels around here when one of its pictures
 // carries P264_T8X8_INTRA.  128 registers (the sixteen wavefronts of a workgroup are four per SIMD whatever the bound says) and a
-// second table in LDS; k_intra_sparse_i8 has no edge-info role (such batches take k_deblock_bs, which knows the flag).
+// second table in LDS; k_intra_sparse_i8 has no edge-info role (such batches take k_deblock_bs, which knows the flag), so no
+// argument for one: two workgroups per picture.
 #define INTRA_I8_WAVES_PER_EU 4
 __global__ __launch_bounds__(INTRA_ROW_WAVES * 64, INTRA_I8_WAVES_PER_EU)
 void k_intra_i8(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra)
 {
-    __shared__ IntraShared sh;
-    __shared__ uint32_t lut8[INTRA_LUT8_ENTRIES];
-    intra_picture<true>(sh, lut8, pics, g, status, is_intra, (int)blockIdx.x, blockIdx.y != 0);
+    __shared__ IntraShared<true, false> sh;
+    intra_picture(sh, pics, g, status, is_intra, (int)blockIdx.x, blockIdx.y != 0, nullptr);
 }
 __global__ __launch_bounds__(INTRA_ROW_WAVES * 64, INTRA_I8_WAVES_PER_EU)
-void k_intra_sparse_i8(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra, EdgeInfo *__restrict__ info, uint32_t inv_mbw, int bs_wgs)
+void k_intra_sparse_i8(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra)
 {
-    (void)info; (void)inv_mbw; (void)bs_wgs;               // (the signature of k_intra_sparse; two workgroups per picture)
-    __shared__ IntraShared sh;
-    __shared__ uint32_t lut8[INTRA_LUT8_ENTRIES];
-    const int pic = rfl((int)(blockIdx.x >> 1));
-    intra_picture<true>(sh, lut8, pics, g, status, is_intra, pic, (blockIdx.x & 1) != 0);
+    __shared__ IntraShared<true, false> sh;
+    intra_picture(sh, pics, g, status, is_intra, rfl((int)(blockIdx.x >> 1)), (blockIdx.x & 1) != 0, nullptr);     // (two workgroups per picture)
 }
 // The scaled instances (intra_luma4<true, true>, intra_chroma4<true>): what a batch launches in place of the four kernels around here
 // when one of its pictures has scaling_lists.  Built with Intra 8x8 compiled in, bounded like the _i8 instances (128 registers); the
@@ -894,19 +894,14 @@ void k_intra_sparse_i8(const PicDev *__restrict__ pics, Geom g, int *status, con
 __global__ __launch_bounds__(INTRA_ROW_WAVES * 64, INTRA_I8_WAVES_PER_EU)
 void k_intra_scaled(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra, const ScaleDev *__restrict__ scale)
 {
-    __shared__ IntraShared sh;
-    __shared__ uint32_t lut8[INTRA_LUT8_ENTRIES];
-    __shared__ __attribute__((aligned(16))) uint8_t sw[P264HIP_SCALING_BYTES];
-    intra_picture<true, true>(sh, lut8, pics, g, status, is_intra, (int)blockIdx.x, blockIdx.y != 0, sw, scale);
+    __shared__ IntraShared<true, true> sh;
+    intra_picture(sh, pics, g, status, is_intra, (int)blockIdx.x, blockIdx.y != 0, scale);
 }
 __global__ __launch_bounds__(INTRA_ROW_WAVES * 64, INTRA_I8_WAVES_PER_EU)
 void k_intra_sparse_scaled(const PicDev *__restrict__ pics, Geom g, int *status, const uint8_t *__restrict__ is_intra, const ScaleDev *__restrict__ scale)
 {
-    __shared__ IntraShared sh;
-    __shared__ uint32_t lut8[INTRA_LUT8_ENTRIES];
-    __shared__ __attribute__((aligned(16))) uint8_t sw[P264HIP_SCALING_BYTES];
-    const int pic = rfl((int)(blockIdx.x >> 1));            // (two workgroups per picture, as k_intra_sparse_i8)
-    intra_picture<true, true>(sh, lut8, pics, g, status, is_intra, pic, (blockIdx.x & 1) != 0, sw, scale);
+    __shared__ IntraShared<true, true> sh;
+    intra_picture(sh, pics, g, status, is_intra, rfl((int)(blockIdx.x >> 1)), (blockIdx.x & 1) != 0, scale);        // (two workgroups per picture)
 }
 #define INTRA_SPARSE_WAVES_PER_EU 8
 // The sparse build also carries the loop filter's EDGE INFO pass (kernel_deblock.h, K4a) as a third role: that pass is bound
@@ -996,6 +991,6 @@ void k_intra_sparse(const PicDev *__restrict__ pics, Geom g, int *status, const 
         }
         return;
     }
-    __shared__ IntraShared sh;
-    intra_picture<false>(sh, nullptr, pics, g, status, is_intra, pic, role != 0);
+    __shared__ IntraShared<false, false> sh;
+    intra_picture(sh, pics, g, status, is_intra, pic, role != 0, nullptr);
 }

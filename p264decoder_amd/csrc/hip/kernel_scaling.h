@@ -2,7 +2,8 @@
 // k_scaled_inter, which adds the residual of the inter macroblocks of pictures with scaling_lists (include/p264hip.h).
 //
 // No counterpart in the reference, whose decoder forces flat lists (decoder/set.c:261-263).  LevelScale = weightScale * normAdjust
-// (8.5.9); with weight 16 everywhere the functions below give what dequant_cols, chroma_dc_level and t8_scale give.  All scaling is
+// (8.5.9); with weight 16 everywhere the functions below give what dequant_cols and chroma_dc_level give.  The levels of 8x8 blocks have
+// no function of their own here: t8_scale / t8_scatter of kernel_t8x8.h take the weight from a T8List of this table.  All scaling is
 // 32-bit: the packed 16-bit multiply of dequant_cols is exact only because flat products are multiples of 16.  A conforming stream
 // keeps every value inside 16 bits; anything else still gives a defined result here (shifts on unsigned values, QP taken modulo 64).
 //
@@ -74,13 +75,8 @@ __device__ __forceinline__ int chroma_dc_level_w(uint2 dcl, bool right, bool low
     const int per = (qpc * 43) >> 8, rem = qpc - per * 6;
     return (int)((unsigned)(f * (w00 * (int)dq_s(0, rem))) << per) >> 5;
 }
-// 8.5.13: one level at raster position p of an 8x8 block; t8_scale of kernel_t8x8.h with the list's weight w in place of 16
-__device__ __forceinline__ int t8_scale_w(int c, int p, uint64_t vrow, int per, int w)
-{
-    const int cls = (int)((T8_CLASSES >> (4 * (((p >> 3) & 3) * 4 + (p & 3)))) & 15u);
-    const int t = c * (w * (int)((vrow >> (8 * cls)) & 255u));
-    return per >= 6 ? (int)((unsigned)t << (per - 6)) : (t + (1 << (5 - per))) >> (6 - per);
-}
+// 8.5.13, the levels of an 8x8 block: t8_scatter of kernel_t8x8.h with a T8List of the table's list 6 (intra) or 7 (inter)
+__device__ __forceinline__ T8List scaling_list8(const uint8_t *sw, int n) { return T8List{ sw + SCL_8X8_AT + 64 * (n - 6) }; }
 
 // ------------------------------------------------------------------------------------------
 // k_scaled_inter: the residual of the inter macroblocks of scaled pictures, added in place.  The batch's sort files luma and
@@ -89,7 +85,8 @@ __device__ __forceinline__ int t8_scale_w(int c, int p, uint64_t vrow, int per, 
 // stage - where k_t8x8 runs in other batches - adds
 //   the coded 4x4 luma blocks (list 3), chroma DC and AC of both planes (lists 4, 5): lane = block, everything in its registers
 //   (unscan_cols, scale_cols_w, idct_add on the block's four rows of samples);
-//   the coded 8x8 blocks of P264_MB_T8X8 records (list 7): k_t8x8's walk, eight lanes per block, with t8_scale_w.
+//   the coded 8x8 blocks of P264_MB_T8X8 records (list 7): k_t8x8's lane plan, scatter and walk (kernel_t8x8.h: t8_lane, t8_scatter,
+//   t8_walk), eight lanes per block, the weights from the table.
 // It owns the 8x8 blocks of the batch's FLAT pictures too (k_t8x8 is not launched beside it): they take the all-16 table, and
 // nothing else of a flat picture is touched - its 4x4 and chroma residuals went through k_mc as ever.
 //
@@ -97,12 +94,11 @@ __device__ __forceinline__ int t8_scale_w(int c, int p, uint64_t vrow, int per, 
 // the chroma blocks (plane, block), then all 32 the four 8x8 blocks.  Bound by memory: it re-reads and re-writes the samples of every
 // block that has a residual.
 // ------------------------------------------------------------------------------------------
-// (SCL_THREADS, SCL_MBS_PER_WG: launch_shared.h, through kernel_t8x8.h)
-// grid: (macroblocks of a picture / SCL_MBS_PER_WG, pictures of the batch)
-__global__ __launch_bounds__(SCL_THREADS)
+// grid: (macroblocks of a picture / T8_MBS_PER_WG, pictures of the batch)
+__global__ __launch_bounds__(T8_THREADS)
 void k_scaled_inter(const PicDev *__restrict__ pics, const ScaleDev *__restrict__ scale, Geom g)
 {
-    __shared__ int tiles[(SCL_THREADS / 64) * 8 * T8_BLK_STRIDE];
+    __shared__ int tiles[(T8_THREADS / 64) * 8 * T8_BLK_STRIDE];
     __shared__ __attribute__((aligned(16))) uint8_t sw[P264HIP_SCALING_BYTES];
     const PicDev *pd = pics + blockIdx.y;
     if (pd->slice_type == P264_SLICE_I) return;            // (no inter record)
@@ -110,16 +106,13 @@ void k_scaled_inter(const PicDev *__restrict__ pics, const ScaleDev *__restrict_
     const bool scaled = sd->scaled != 0;                   // (per workgroup)
     scaling_to_lds(sw, sd->lists);
     __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane & 31;
-    const int mbi = ((int)blockIdx.x * (SCL_THREADS / 64) + wave) * 2 + (lane >> 5);
-    uint4 rec = make_uint4(0, 0, 0, 0);
-    if (mbi < g.n_mb) rec = gload4(pd->mb + mbi);
-    const bool inter = mbi < g.n_mb && !P264_MB_IS_INTRA(rec.x & 255u);
+    const T8Lane t = t8_lane(pd, g, tiles);
+    const int h = threadIdx.x & 31, mbx = t.mbx(g), mby = t.mby(g);
+    const uint4 rec = t.rec;
+    const bool inter = t.mbi < g.n_mb && !P264_MB_IS_INTRA(rec.x & 255u);
     const unsigned mask = inter ? rec.y : 0u;
     const bool t8 = ((rec.x >> 24) & P264_MB_T8X8) != 0;
     const int qp = (int)((rec.x >> 8) & 63u);
-    int mby = mbi / g.mb_w;
-    const int mbx = mbi - mby * g.mb_w;
     const int16_t *cf = pd->coefs + (size_t)rec.z * 16;
     // ---- 4x4 blocks: lane h < 16 the luma block h (decoding order), 16 .. 23 chroma block (h - 16) & 3 of plane (h - 16) >> 2 ----
     {
@@ -153,47 +146,11 @@ void k_scaled_inter(const PicDev *__restrict__ pics, const ScaleDev *__restrict_
         }
     }
     // ---- 8x8 blocks of P264_MB_T8X8 records (kernel_t8x8.h's walk): 8 lanes per block, lane r = its row, then its column ----
-    const int k = (lane >> 3) & 3, r = lane & 7;
-    const bool coded8 = inter && t8 && ((mask >> (4 * k)) & 1u);
+    const bool coded8 = inter && t8 && ((mask >> (4 * t.k)) & 1u);
     if (!__ballot(coded8)) return;
-    int *tile = tiles + (wave * 8 + (lane >> 3)) * T8_BLK_STRIDE;
-    const uint8_t *w8 = sw + SCL_8X8_AT + 64;              // list 7
     if (coded8) {
         const int per = (qp * 43) >> 8;
-        const uint64_t vrow = c_t8_v[qp - per * 6];
-        const uint4 l = gload4(cf + coef_slot(mask, 4 * k) * 16 + r * 8);
-        const uint2 sc = *(const uint2 *)(c_scan8x8 + r * 8);
-        const uint32_t lw[4] = { l.x, l.y, l.z, l.w };
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int c = (i & 1) ? (int)lw[i >> 1] >> 16 : (int)(int16_t)(lw[i >> 1] & 0xffffu);
-            const int p = (int)(((i < 4 ? sc.x : sc.y) >> (8 * (i & 3))) & 63u);
-            tile[p] = t8_scale_w(c, p, vrow, per, (int)w8[p]);
-        }
+        t8_scatter(gload4(cf + coef_slot(mask, 4 * t.k) * 16 + t.r * 8), t.r, c_t8_v[qp - per * 6], per, t.tile, scaling_list8(sw, 7));
     }
-    wave_lds_fence();
-    int d[8];
-    if (coded8) t8_row_pass(tile, r, d);                   // rows first
-    wave_lds_fence();
-    if (coded8) {                                          // column r, rounded
-#pragma unroll
-        for (int y = 0; y < 8; y++) d[y] = tile[y * 8 + r];
-        t8_idct1d(d);
-#pragma unroll
-        for (int y = 0; y < 8; y++) tile[y * 8 + r] = (d[y] + 32) >> 6;
-    }
-    wave_lds_fence();
-    if (coded8) {                                          // row r of the block: prediction + residual, clipped
-        uint8_t *px = pd->dst + mb_luma_off(g, mbx, mby) + (uint32_t)(((k >> 1) * 8 + r) * 16 + (k & 1) * 8);
-        const uint2 s = gload2(px);
-        const int4 lo = *(const int4 *)(tile + r * 8), hi = *(const int4 *)(tile + r * 8 + 4);
-        const int res[8] = { lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w };
-        uint32_t o[2] = { 0, 0 };
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int v = clip255((int)(((i < 4 ? s.x : s.y) >> (8 * (i & 3))) & 255u) + res[i]);
-            o[i >> 2] |= (uint32_t)v << (8 * (i & 3));
-        }
-        gstore2(px, make_uint2(o[0], o[1]));
-    }
+    t8_walk(pd, g, t, coded8);
 }

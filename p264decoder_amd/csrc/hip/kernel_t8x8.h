@@ -10,6 +10,11 @@
 // order, then row r of the horizontal pass, column r of the vertical pass, row r of the samples).  The three changes of
 // ownership go through LDS; nothing leaves the wavefront, so fences do (device_common.h: wave_lds_fence).  All arithmetic is
 // 32-bit: a conforming stream keeps every value inside 16 bits, anything else still gives a defined result here.
+//
+// The 8x8 residual of every kernel is written here, once: t8_scale and t8_scatter (the weights from a T8Flat, or from a T8List
+// where the picture has scaling lists), t8_idct1d, t8_row_pass; and what k_t8x8 and k_scaled_inter (kernel_scaling.h) have in
+// common - T8Lane / t8_lane, a lane's macroblock, block and tile, and t8_walk, everything behind the scatter.  intra_luma4
+// (kernel_intra.h) takes the scatter and the one-dimensional stage; its passes are its own, its lanes own other things.
 #pragma once
 #include "device_common.h"
 #include "launch_shared.h"           // (T8_THREADS, T8_MBS_PER_WG)
@@ -28,12 +33,34 @@ __device__ __constant__ const uint64_t c_t8_v[6] = {
 // position class by (y & 3) * 4 + (x & 3): 0 3 4 3 / 3 1 5 1 / 4 5 2 5 / 3 1 5 1, one nibble each
 #define T8_CLASSES 0x1513525415133430ull
 
-// one level at raster position p of the block, scaled (flat scaling lists: weight 16)
-__device__ __forceinline__ int t8_scale(int c, int p, uint64_t vrow, int per)
+// one level at raster position p of the block, scaled: LevelScale = w * normAdjust8x8, w the scaling list's weight at p (flat lists: 16)
+__device__ __forceinline__ int t8_scale(int c, int p, uint64_t vrow, int per, int w)
 {
     const int cls = (int)((T8_CLASSES >> (4 * (((p >> 3) & 3) * 4 + (p & 3)))) & 15u);
-    const int t = c * 16 * (int)((vrow >> (8 * cls)) & 255u);
+    const int t = c * (w * (int)((vrow >> (8 * cls)) & 255u));
     return per >= 6 ? (int)((unsigned)t << (per - 6)) : (t + (1 << (5 - per))) >> (6 - per);
+}
+// Where t8_scatter takes the weight at raster position p from.  A type, so that the flat instances hold the constant and no table:
+// nothing at run time tells flat from scaled.
+struct T8Flat { __device__ __forceinline__ int operator()(int) const { return 16; } };
+struct T8List {                      // an 8x8 list of the workgroup's raster table in LDS (kernel_scaling.h: scaling_to_lds)
+    const uint8_t *w;
+    __device__ __forceinline__ int operator()(int p) const { return (int)w[p]; }
+};
+
+// Levels 8r .. 8r+7 of a block's scan (l: eight int16, as loaded), scaled, to their raster places in the block's tile of 64 ints.
+// vrow, per: c_t8_v[qP % 6], qP / 6.  Every 8x8 residual starts here: k_t8x8, k_scaled_inter, intra_luma4 (kernel_intra.h).
+template <class Weight>
+__device__ __forceinline__ void t8_scatter(const uint4 l, int r, uint64_t vrow, int per, int *tile, const Weight weight)
+{
+    const uint2 sc = *(const uint2 *)(c_scan8x8 + r * 8);
+    const uint32_t lw[4] = { l.x, l.y, l.z, l.w };
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int c = (i & 1) ? (int)lw[i >> 1] >> 16 : (int)(int16_t)(lw[i >> 1] & 0xffffu);
+        const int p = (int)(((i < 4 ? sc.x : sc.y) >> (8 * (i & 3))) & 63u);
+        tile[p] = t8_scale(c, p, vrow, per, weight(p));
+    }
 }
 
 // the one-dimensional stage of 8.5.13, in place
@@ -48,8 +75,8 @@ __device__ __forceinline__ void t8_idct1d(int (&d)[8])
     d[4] = b6 - b1; d[5] = b4 - b3; d[6] = b2 - b5; d[7] = b0 - b7;
 }
 
-// The horizontal pass of a block's walk (k_t8x8, k_scaled_inter): rows first (the >> 1 and >> 2 of the stage make the order
-// observable) - row r of the tile, back in place.  d: the lane's eight values, the column pass goes on in them.
+// The horizontal pass of a block's walk: rows first (the >> 1 and >> 2 of the stage make the order observable) - row r of the tile,
+// back in place.  d: the lane's eight values, the column pass goes on in them.
 __device__ __forceinline__ void t8_row_pass(int *tile, int r, int (&d)[8])
 {
     const int4 lo = *(const int4 *)(tile + r * 8), hi = *(const int4 *)(tile + r * 8 + 4);
@@ -59,37 +86,35 @@ __device__ __forceinline__ void t8_row_pass(int *tile, int r, int (&d)[8])
     *(int4 *)(tile + r * 8 + 4) = make_int4(d[4], d[5], d[6], d[7]);
 }
 
-// grid: (macroblocks of a picture / T8_MBS_PER_WG, pictures of the batch)
-__global__ __launch_bounds__(T8_THREADS)
-void k_t8x8(const PicDev *__restrict__ pics, Geom g)
+// A lane's place in the two inter kernels (the shape above), from its number alone.  tiles: the workgroup's
+// (T8_THREADS / 64) * 8 * T8_BLK_STRIDE ints.
+struct T8Lane {
+    int mbi;                         // the macroblock of the wavefront's pair; behind the picture's last one rec is all zero
+    int k, r;                        // 8x8 block of the macroblock (quadrants in raster order), row / column of the block
+    uint4 rec;                       // the macroblock's record
+    int *tile;                       // the block's tile
+    __device__ __forceinline__ int mby(const Geom &g) const { return mbi / g.mb_w; }
+    __device__ __forceinline__ int mbx(const Geom &g) const { return mbi - mby(g) * g.mb_w; }
+    // row r of the block in the frame store
+    __device__ __forceinline__ uint8_t *px(const PicDev *pd, const Geom &g) const { return pd->dst + mb_luma_off(g, mbx(g), mby(g)) + (uint32_t)(((k >> 1) * 8 + r) * 16 + (k & 1) * 8); }
+};
+__device__ __forceinline__ T8Lane t8_lane(const PicDev *pd, const Geom &g, int *tiles)
 {
-    __shared__ int tiles[(T8_THREADS / 64) * 8 * T8_BLK_STRIDE];
-    const PicDev *pd = pics + blockIdx.y;
-    if (pd->slice_type == P264_SLICE_I) return;            // (no inter record, and only those may carry the flag)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int mbi = ((int)blockIdx.x * (T8_THREADS / 64) + wave) * 2 + (lane >> 5);
-    const int k = (lane >> 3) & 3, r = lane & 7;           // 8x8 block of the macroblock (quadrants in raster order), row / column of the block
-    uint4 rec = make_uint4(0, 0, 0, 0);
-    if (mbi < g.n_mb) rec = gload4(pd->mb + mbi);
-    const unsigned mask = rec.y;
-    const bool coded = ((rec.x >> 24) & P264_MB_T8X8) && !P264_MB_IS_INTRA(rec.x & 255u) && ((mask >> (4 * k)) & 1u);
-    if (!__ballot(coded)) return;                          // unflagged macroblocks leave at once
-    int *tile = tiles + (wave * 8 + (lane >> 3)) * T8_BLK_STRIDE;
-    // ---- levels 8r .. 8r+7 of the block's scan, scaled, to their places in the tile
-    if (coded) {
-        const int qp = (int)((rec.x >> 8) & 63u), per = (qp * 43) >> 8;
-        const uint64_t vrow = c_t8_v[qp - per * 6];
-        const int16_t *lv = pd->coefs + ((size_t)rec.z + coef_slot(mask, 4 * k)) * 16 + r * 8;     // four entries per coded block: 64 levels
-        const uint4 l = gload4(lv);
-        const uint2 sc = *(const uint2 *)(c_scan8x8 + r * 8);
-        const uint32_t lw[4] = { l.x, l.y, l.z, l.w };
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int c = (i & 1) ? (int)lw[i >> 1] >> 16 : (int)(int16_t)(lw[i >> 1] & 0xffffu);
-            const int p = (int)(((i < 4 ? sc.x : sc.y) >> (8 * (i & 3))) & 63u);
-            tile[p] = t8_scale(c, p, vrow, per);
-        }
-    }
+    T8Lane t;
+    t.mbi = ((int)blockIdx.x * (T8_THREADS / 64) + wave) * 2 + (lane >> 5);
+    t.k = (lane >> 3) & 3; t.r = lane & 7;
+    t.rec = make_uint4(0, 0, 0, 0);
+    if (t.mbi < g.n_mb) t.rec = gload4(pd->mb + t.mbi);
+    t.tile = tiles + (wave * 8 + (lane >> 3)) * T8_BLK_STRIDE;
+    return t;
+}
+
+// The walk of the inter kernels behind t8_scatter, every lane of the wavefront in it (coded: the lane's block has levels in its tile)
+__device__ __forceinline__ void t8_walk(const PicDev *pd, const Geom &g, const T8Lane &t, bool coded)
+{
+    int *tile = t.tile;
+    const int r = t.r;
     wave_lds_fence();
     int d[8];
     if (coded) t8_row_pass(tile, r, d);
@@ -105,9 +130,7 @@ void k_t8x8(const PicDev *__restrict__ pics, Geom g)
     wave_lds_fence();
     // ---- row r of the block: 8 samples of the prediction the inter launches left, plus the residual, clipped
     if (coded) {
-        int mby = mbi / g.mb_w;
-        const int mbx = mbi - mby * g.mb_w;
-        uint8_t *px = pd->dst + mb_luma_off(g, mbx, mby) + (uint32_t)(((k >> 1) * 8 + r) * 16 + (k & 1) * 8);
+        uint8_t *px = t.px(pd, g);
         const uint2 s = gload2(px);
         const int4 lo = *(const int4 *)(tile + r * 8), hi = *(const int4 *)(tile + r * 8 + 4);
         const int res[8] = { lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w };
@@ -119,4 +142,22 @@ void k_t8x8(const PicDev *__restrict__ pics, Geom g)
         }
         gstore2(px, make_uint2(o[0], o[1]));
     }
+}
+
+// grid: (macroblocks of a picture / T8_MBS_PER_WG, pictures of the batch)
+__global__ __launch_bounds__(T8_THREADS)
+void k_t8x8(const PicDev *__restrict__ pics, Geom g)
+{
+    __shared__ int tiles[(T8_THREADS / 64) * 8 * T8_BLK_STRIDE];
+    const PicDev *pd = pics + blockIdx.y;
+    if (pd->slice_type == P264_SLICE_I) return;            // (no inter record, and only those may carry the flag)
+    const T8Lane t = t8_lane(pd, g, tiles);
+    const bool coded = ((t.rec.x >> 24) & P264_MB_T8X8) && !P264_MB_IS_INTRA(t.rec.x & 255u) && ((t.rec.y >> (4 * t.k)) & 1u);
+    if (!__ballot(coded)) return;                          // unflagged macroblocks leave at once
+    if (coded) {
+        const int qp = (int)((t.rec.x >> 8) & 63u), per = (qp * 43) >> 8;
+        const int16_t *lv = pd->coefs + ((size_t)t.rec.z + coef_slot(t.rec.y, 4 * t.k)) * 16 + t.r * 8;     // four entries per coded block: 64 levels
+        t8_scatter(gload4(lv), t.r, c_t8_v[qp - per * 6], per, t.tile, T8Flat());
+    }
+    t8_walk(pd, g, t, coded);
 }

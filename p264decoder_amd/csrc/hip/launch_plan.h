@@ -170,7 +170,7 @@ static inline LaunchPlan plan_launches(const LaunchDevice &dev, const LaunchKnob
         // inter neighbours' finished samples): a scaled batch's k_scaled_inter owns the 8x8 blocks of all its pictures - no k_t8x8 beside it
         if (scaled) {
             pl.residual = ResidualKernel::scaled_inter;
-            pl.residual_shape = LaunchShape{ (unsigned)((n_mb + SCL_MBS_PER_WG - 1) / SCL_MBS_PER_WG), (unsigned)n, SCL_THREADS };
+            pl.residual_shape = LaunchShape{ (unsigned)((n_mb + T8_MBS_PER_WG - 1) / T8_MBS_PER_WG), (unsigned)n, T8_THREADS };
         } else if (k.t8) {
             pl.residual = ResidualKernel::t8x8;
             pl.residual_shape = LaunchShape{ (unsigned)((n_mb + T8_MBS_PER_WG - 1) / T8_MBS_PER_WG), (unsigned)n, T8_THREADS };

@@ -15,10 +15,8 @@
 #define INTRA_BS_WGS    1            // edge-info workgroups per picture inside the k_intra_sparse launch (kernel_intra.h, with the measurements)
 #define DB_LAG          1            // columns a row of a k_deblock band lags behind the row above it (kernel_deblock.h)
 #define MAX_PICS_PER_WG 16           // pictures one k_deblock workgroup serves (in groups of as many as a wavefront holds)
-#define T8_THREADS      256          // k_t8x8 (kernel_t8x8.h): one wavefront per two macroblocks
+#define T8_THREADS      256          // k_t8x8 (kernel_t8x8.h) and k_scaled_inter (kernel_scaling.h): one wavefront per two macroblocks
 #define T8_MBS_PER_WG   (T8_THREADS / 32)
-#define SCL_THREADS     256          // k_scaled_inter (kernel_scaling.h): as k_t8x8
-#define SCL_MBS_PER_WG  (SCL_THREADS / 32)
 #define MC_SORT_THREADS 1024         // k_mc_sort* (kernel_mc_sort.h): one workgroup per picture
 
 // ---- the work lists of the motion-compensation stage (kernel_mc_sort.h writes them, kernel_mc.h reads them) ----

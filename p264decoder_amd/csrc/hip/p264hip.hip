@@ -916,7 +916,7 @@ static void launch_intra(p264hip_ctx *c, const PicDev *batch, const ScaleDev *sc
     case IntraKernel::dense:         INTRA(k_intra); break;
     case IntraKernel::sparse:        INTRA(k_intra_sparse, c->d_edge, inv_mb_w(c), pl.info.edge_info_fused); break;      // (with the edge-info workgroups, if any)
     case IntraKernel::dense_i8:      INTRA(k_intra_i8); break;
-    case IntraKernel::sparse_i8:     INTRA(k_intra_sparse_i8, c->d_edge, inv_mb_w(c), 0); break;
+    case IntraKernel::sparse_i8:     INTRA(k_intra_sparse_i8); break;
     case IntraKernel::dense_scaled:  INTRA(k_intra_scaled, scale); break;
     case IntraKernel::sparse_scaled: INTRA(k_intra_sparse_scaled, scale); break;
     }

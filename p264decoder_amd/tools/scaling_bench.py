@@ -5,9 +5,10 @@ default lists of tables 7-3 / 7-4 in the SPS: every picture has scaling_lists, t
 k_intra_sparse_scaled), at 256 and at 2048 pictures per launch in one context, inputs resident, --runs runs each.  Only the P
 launches are timed; the stage times are the context's HIP events (inter = sort + motion compensation + k_scaled_inter).  This is NOT
 bench.py's metric and has no pass mark: it is the pair DESIGN.md quotes for the extra pass.  Nothing checks the pictures here (the
-tests do).
+tests do).  --t8x8 PCT gives that share of the inter macroblocks the 8x8 transform: the flat batch then launches k_t8x8, and
+k_scaled_inter walks 8x8 blocks too; the default 0 is the stream of the committed figures.
 
-  python -m p264decoder_amd.tools.scaling_bench [--streams 256 2048] [--pictures 5] [--runs 3] [--out profiles/scaling_bench.json]
+  python -m p264decoder_amd.tools.scaling_bench [--streams 256 2048] [--pictures 5] [--runs 3] [--t8x8 0] [--out profiles/scaling_bench.json]
 """
 import argparse
 import json
@@ -23,7 +24,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 MB_W, MB_H = 120, 68
-OPTIONS = "--mbw %d --mbh %d --gop 0 --seed 33 --coded 12 --maxlevel 12 --crop-bottom 4 --t8x8 0" % (MB_W, MB_H)
+OPTIONS = "--mbw %d --mbh %d --gop 0 --seed 33 --coded 12 --maxlevel 12 --crop-bottom 4 --t8x8 %%d" % (MB_W, MB_H)     # (--t8x8 PCT: main)
 CASES = (("flat", ""), ("cqm_jvt", "--cqm jvt --cqm-where sps"))
 
 
@@ -47,6 +48,7 @@ def main():
     ap.add_argument("--streams", type=int, nargs="+", default=[256, 2048], help="pictures of a batch = streams of the context")
     ap.add_argument("--pictures", type=int, default=5, help="pictures per stream: one IDR picture and the P launches of a run")
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--t8x8", type=int, default=0, metavar="PCT", help="per cent of the inter macroblocks coded with the 8x8 transform")
     ap.add_argument("--out", default=None, help="also write the result there")
     args = ap.parse_args()
     from p264decoder_amd import HipReconstructor, Parser
@@ -55,13 +57,14 @@ def main():
     if not os.path.exists(tool):
         _build.build_tools()
     T = args.pictures
+    options = OPTIONS % args.t8x8
     res = {"metric": "reconstruction of 1080p P pictures (bench.py's all-P stream as High profile), inputs resident, P launches only", "unit": "frames/s",
-           "pictures_per_stream": T, "runs": args.runs, "stream_options": OPTIONS, "batches": {}}
+           "pictures_per_stream": T, "runs": args.runs, "stream_options": options, "batches": {}}
     with tempfile.TemporaryDirectory() as td:
         parsed = {}
         for name, extra in CASES:
             path = os.path.join(td, name + ".264")
-            subprocess.run([tool, path] + OPTIONS.split() + ["--frames", str(T)] + extra.split(), check=True)
+            subprocess.run([tool, path] + options.split() + ["--frames", str(T)] + extra.split(), check=True)
             parsed[name] = Parser(quiet=True, intra8x8=True, scaling=True).parse_stream(open(path, "rb").read())
             assert len(parsed[name]) == T and all(bool(p.desc.scaling_lists) == bool(extra) for p in parsed[name])
         for S in args.streams:
