@@ -126,6 +126,9 @@ def _quad_blocks(q):
     return (b0, b0 + 1, b0 + 4, b0 + 5)
 
 
+quad_blocks = _quad_blocks             # (public names: tests/worklist_model.py and tests/worklist_stim.py build on them)
+
+
 def classify(pic, m):
     """The work items inter macroblock m becomes: {(list, block): (kind, blocks of the item, (mvx, mvy) of the item or None)} for
     every (list, 4x4 block in raster order) that is predicted - kind 'mb' / 'quad' / 'lane' as in the module's text - and the
@@ -192,6 +195,9 @@ def _side(lo, n, size):
     return a, b
 
 
+side = _side
+
+
 DECODE_INDEX = {bb: i for i, bb in enumerate([0, 1, 4, 5, 2, 3, 6, 7, 8, 9, 12, 13, 10, 11, 14, 15])}     # raster 4x4 block -> coef_mask bit
 LUMA_WINDOW = {"mb": (21, 16), "quad": (13, 8), "lane": (9, 4)}       # kind -> (window, item) size in samples
 CHROMA_WINDOW = {"mb": (9, 8), "quad": (5, 4), "lane": (3, 2)}
@@ -223,6 +229,9 @@ class Census:
 
 def _inside(sides):
     return all(s in ("in", "flush") for s in sides)
+
+
+inside = _inside
 
 
 def survey(pic, census):

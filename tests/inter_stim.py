@@ -95,11 +95,17 @@ def _stim(name, pic, frames):
     return Stim(name, pic, frames, kept)
 
 
+stim = _stim                           # (public names: tests/worklist_stim.py draws its macroblocks with them)
+
+
 def _some_levels(rng, n=16, count=3, top=9):
     lv = np.zeros(16, np.int64)
     pos = rng.choice(n, size=count, replace=False)
     lv[pos] = rng.integers(1, top + 1, size=count) * rng.choice([-1, 1], size=count)
     return lv
+
+
+some_levels = _some_levels
 
 
 def _code_item(rng, b, m, raster_blocks):
@@ -144,6 +150,9 @@ def _vector(wx, wy, x0, y0, frac, chroma, rng):
     if not chroma:
         return (wx + 2 - x0) * 4 + frac[0], (wy + 2 - y0) * 4 + frac[1]
     return (wx - x0 // 2) * 8 + frac[0] + 4 * int(rng.integers(0, 2)), (wy - y0 // 2) * 8 + frac[1] + 4 * int(rng.integers(0, 2))
+
+
+vector_onto = _vector
 
 
 def window_set(seed=8422):

@@ -6,7 +6,8 @@ the invariants that tie the stages together; knob values out of range are ignore
 
 The program reads one case per line, `mb_w mb_h n compute_units  i p b wp dup t8 i8 sc  [P264AMD_NAME=value ...]`, feeds the
 knobs through launch_knobs_read by a getenv of its own and prints `key=value ...`: the plan's enums, copy_scale_table, the
-band of the work lists and every field of the plan's p264hip_launch_info_t."""
+band of the work lists, every field of the plan's p264hip_launch_info_t, and the work lists' layout (max_chunks per pass and list, the
+chunk sizes and key counts of launch_shared.h: tests/test_worklist_cpu.py reads them through this program too)."""
 import itertools
 import json
 import os
@@ -46,10 +47,15 @@ int main(void) {
         const p264hip_launch_info_t &li = pl.info;
         printf("sort=%s mc=%s second=%d residual=%s intra=%s edge=%s copy_scale_table=%d band_log2=%u n_bands=%u "
                "pictures=%d compute_units=%d mc_wgs_per_picture=%d intra_waves=%d edge_info_fused=%d deblock_pics_per_wg=%d deblock_rb_log2=%d "
-               "deblock_waves=%d deblock_wgs=%d deblock_odd_single=%d t8x8_wgs=%d scaled_pictures=%d intra_i8=%d\n",
+               "deblock_waves=%d deblock_wgs=%d deblock_odd_single=%d t8x8_wgs=%d scaled_pictures=%d intra_i8=%d",
                sort[(int)pl.sort], mc[(int)pl.mc], (int)pl.mc_second, residual[(int)pl.residual], intra[(int)pl.intra], edge[(int)pl.edge], (int)pl.copy_scale_table,
                dev.ml.band_log2, dev.ml.n_bands, li.pictures, li.compute_units, li.mc_wgs_per_picture, li.intra_waves, li.edge_info_fused, li.deblock_pics_per_wg,
                li.deblock_rb_log2, li.deblock_waves, li.deblock_wgs, li.deblock_odd_single, li.t8x8_wgs, li.scaled_pictures, li.intra_i8);
+        // the work lists' layout and the constants tests/worklist_model.py types in: [pass * ML_LISTS + list]
+        for (int l = 0; l < 2 * ML_LISTS; l++) printf(" max_chunks%d=%u", l, dev.ml.max_chunks[l]);
+        for (int l = 0; l < ML_LISTS; l++) printf(" chunk_items%d=%d list_keys%d=%d", l, mc_chunk_items(l), l, mc_list_keys(l));
+        printf(" MCY_KEYS=%d MCC_KEYS=%d MC_MAX_BANDS=%d ML_LISTS=%d ML_YM=%d ML_YQ=%d ML_CM=%d ML_CQ=%d\n", MCY_KEYS, MCC_KEYS, MC_MAX_BANDS, ML_LISTS,
+               (int)ML_YM, (int)ML_YQ, (int)ML_CM, (int)ML_CQ);
     }
     return 0;
 }
@@ -193,5 +199,8 @@ def test_knob_values_out_of_range_are_ignored(plan):
     zero = one("wide_70", 2, {"MC_BAND_LOG2": "0"})
     assert (zero["band_log2"], zero["n_bands"]) == (0, 3)
     assert one("wide_70", 2, {"MC_BAND_LOG2": "-1"}) == unset and one("wide_70", 2, {"MC_BAND_LOG2": "10"}) == unset
+    # ... and the band doubles until the picture has at most MC_MAX_BANDS (32) of them: 32 rows are 32 bands of one, 33 rows 17 bands of two
+    deep = plan([(8, 32, 2, CU, P, {K + "MC_BAND_LOG2": "0"}), (8, 33, 2, CU, P, {K + "MC_BAND_LOG2": "0"}), (8, 512, 2, CU, P, {})])
+    assert [(d["band_log2"], d["n_bands"]) for d in deep] == [(0, 32), (1, 17), (4, 32)]
     # DEBLOCK_ODD_SINGLE is a switch: any value but 0 is "on"
     assert one("qpdelta", 769, {"DEBLOCK_ODD_SINGLE": "5"}) == one("qpdelta", 769, {"DEBLOCK_ODD_SINGLE": "1"})
