@@ -204,6 +204,16 @@ typedef struct p264hip_picture {
     int32_t             scaling_lists;
     uint8_t             scaling4x4[6][16];
     uint8_t             scaling8x8[2][64];
+    /* ---- Cr's own QP offset (High profile, H.264 7.3.2.2: second_chroma_qp_index_offset), as a DELTA on chroma_qp_offset:
+     * second_chroma_qp_index_offset - chroma_qp_index_offset.  Cb's qPI is Clip3(0, 51, QPY + chroma_qp_offset) as ever, Cr's is
+     * Clip3(0, 51, QPY + chroma_qp_offset + cr_qp_offset_delta): in the chroma residual (8.5.8, 8.5.11) of inter and intra
+     * macroblocks and in the loop filter's indexA / indexB / tc0 of Cr's edges (8.7.2.2), those of I_PCM macroblocks included (QPY 0
+     * with the plane's offset).  Any int gives a defined result, no road checks or refuses anything here; a stream's offsets are
+     * -12 .. 12 each, its delta -24 .. 24.  A descriptor scalar: it travels beside the packed and compact blocks, whose layouts do
+     * not know it.  A batch that holds a picture with a non-zero delta runs that picture through the instances that read the
+     * scaling table (with the all-16 table where it has no lists: scaling_lists above) and launches the Cr instances of the loop
+     * filter's two kernels (k_deblock_bs_cr, k_deblock_cr); 0 = Cr uses chroma_qp_offset: what every zeroed descriptor says. */
+    int32_t             cr_qp_offset_delta;
 } p264hip_picture_t;
 #define P264HIP_SCALING_BYTES 224                    /* scaling4x4 and scaling8x8 back to back: the table as it lies in a slot and in a compact block */
 
@@ -422,9 +432,11 @@ typedef struct p264hip_launch_info {
     int32_t deblock_odd_single;    /* 1: odd pictures per workgroup - pairs in bands of 4 rows, the last picture alone in bands of 8 */
     int32_t t8x8_wgs;              /* k_t8x8: workgroups of the launch (0: no picture of the batch has transform_8x8, no launch - or a picture of the
                                       batch has scaling_lists: k_scaled_inter then adds the 8x8 blocks of every picture of the batch) */
-    int32_t scaled_pictures;       /* pictures of the batch with scaling_lists.  Not 0: the batch ran the instances that know the table (k_mc_sort_scaled / k_mc_sort_scaled_p,
+    int32_t scaled_pictures;       /* pictures of the batch that take the scaled road: those with scaling_lists and those with a non-zero cr_qp_offset_delta
+                                      (a picture with both counts once).  Not 0: the batch ran the instances that know the table (k_mc_sort_scaled / k_mc_sort_scaled_p,
                                       k_scaled_inter behind the inter launches, k_intra_scaled / k_intra_sparse_scaled) */
-    int32_t reserved[3];
+    int32_t cr_pictures;           /* pictures of the batch with a non-zero cr_qp_offset_delta.  Not 0: the loop filter ran its Cr instances (k_deblock_bs_cr, k_deblock_cr) */
+    int32_t reserved[2];
     int32_t intra_i8;              /* 1: the intra launch ran the Intra 8x8 instances (a picture of the batch has P264_T8X8_INTRA) */
 } p264hip_launch_info_t;
 int  p264hip_last_launch(p264hip_ctx *ctx, p264hip_launch_info_t *out);

@@ -33,6 +33,11 @@ enum {
                                    include/p264hip.h; lists that are 16 everywhere give scaling_lists = 0).  Off by default, for the reason
                                    P264PARSE_OPT_INTRA8X8 is: only the owner of the backend knows whether it reads the table; without the
                                    option such a parameter set is refused ("flat scaling lists only") as it always was */
+    P264PARSE_OPT_CR_OFFSET = 16, /* accept a High-profile PPS whose second_chroma_qp_index_offset differs from chroma_qp_index_offset and
+                                   hand out the difference as the descriptor's cr_qp_offset_delta (include/p264hip.h), taken from the
+                                   PPS that gives chroma_qp_offset.  Off by default, for the same reason: only the owner of the backend
+                                   knows whether it reads the delta; without the option the slices of such a PPS are refused
+                                   ("second_chroma_qp_index_offset ... unsupported") as they always were */
     P264PARSE_OPT_STRICT = 2    /* H.264-conformant QP accumulation also for Baseline CAVLC streams, where the default is the
                                    reference's rule (decoder/macroblock.c:568, core/macroblock.c:1247-1252; SURVEY A-Q2).
                                    CABAC, B slices and every profile but Baseline - none of which the reference decodes -

@@ -51,6 +51,8 @@ class Picture(C.Structure):
         ("transform_8x8", C.c_int32),
         # scaling matrices: the eight resolved lists in scan order (4x4: Intra Y, Cb, Cr, Inter Y, Cb, Cr; 8x8: Intra Y, Inter Y), flat
         ("scaling_lists", C.c_int32), ("scaling4x4", C.c_uint8 * (6 * 16)), ("scaling8x8", C.c_uint8 * (2 * 64)),
+        # second_chroma_qp_index_offset - chroma_qp_index_offset: Cr's qPI is Clip3(0, 51, QPY + chroma_qp_offset + cr_qp_offset_delta)
+        ("cr_qp_offset_delta", C.c_int32),
     ]
 
 
@@ -60,7 +62,7 @@ assert C.sizeof(MbInfo) == 16
 class LaunchInfo(C.Structure):
     """p264hip_launch_info_t"""
     _fields_ = [(n, C.c_int32) for n in ("pictures", "compute_units", "mc_wgs_per_picture", "intra_waves", "edge_info_fused",
-                                         "deblock_pics_per_wg", "deblock_rb_log2", "deblock_waves", "deblock_wgs", "deblock_odd_single", "t8x8_wgs", "scaled_pictures")] + [("reserved", C.c_int32 * 3), ("intra_i8", C.c_int32)]
+                                         "deblock_pics_per_wg", "deblock_rb_log2", "deblock_waves", "deblock_wgs", "deblock_odd_single", "t8x8_wgs", "scaled_pictures", "cr_pictures")] + [("reserved", C.c_int32 * 2), ("intra_i8", C.c_int32)]
 
 
 BUILD_TIMING = 1

@@ -165,6 +165,13 @@ __device__ __forceinline__ int chroma_qp(int qi)
     const int corr = k < 16 ? (int)((0x7765544332221111ull >> (4 * k)) & 15) : (int)((0xCBA998u >> (4 * (k - 16))) & 15);
     return qi - corr;
 }
+// Cr's QP offset, chroma_qp_offset + cr_qp_offset_delta (include/p264hip.h), for any two ints: the sum in 64 bits, brought to
+// -512 .. 512 - with a QP of 0 .. 255 on top, Clip3(0, 51, .) of it is what the unbounded sum gives
+__device__ __forceinline__ int cr_offset_of(int offset, int delta)
+{
+    const long long o = (long long)offset + (long long)delta;
+    return (int)(o < -512 ? -512 : o > 512 ? 512 : o);
+}
 // luma 4x4 block index (decode order, core/macroblock.h:194-201) <-> position
 __device__ __forceinline__ int blk_x(int i) { return (i & 1) | ((i >> 1) & 2); }
 __device__ __forceinline__ int blk_y(int i) { return ((i >> 1) & 1) | ((i >> 2) & 2); }

@@ -270,6 +270,50 @@ void k_deblock_bs(const PicDev *__restrict__ pics, Geom g, EdgeInfo *__restrict_
     gstore4((uint8_t *)(info + (size_t)blockIdx.y * g.n_mb) + (uint32_t)mbi * 16u, edge_info_of<TWO_LISTS>(pd, g, mbi, mbx, mby, rec, m0, m1, m2, m3, refs, &pic_tab));
 }
 
+// ---- K4c: Cr with a QP offset of its own (p264hip_picture_t::cr_qp_offset_delta; no counterpart in the reference) ----
+// H.264 8.7.2.2 takes indexA / indexB / tc0 of a chroma edge from the QPc of the plane that is filtered.  EdgeInfo has room for one
+// chroma plane (avg: 2 bits free, qp: 8), so Cr's three averaged QPs travel in ONE MORE dword per macroblock, in a side array of the
+// scratch that exists from the first batch that needs it: left (bits 0-5), top (6-11), own / inner (12-17), from
+// chroma_qp(Clip3(0, 51, QP + chroma_qp_offset + delta)) of the macroblock and its neighbours - an I_PCM record's QP is 0, which makes
+// its edges "the QPc of QPy 0 with the plane's offset".  A batch that holds such a picture takes k_deblock_bs_cr and k_deblock_cr for
+// all its pictures (delta 0: Cb's QPs again, the same samples as k_deblock writes); EdgeInfo and the flat instances do not change.
+struct ScaleDev;                                                                // (kernel_scaling.h: the batch's side array carries the delta)
+__device__ __forceinline__ int cr_delta_of(const ScaleDev *scale, int pic);     // (defined there)
+__device__ __forceinline__ uint32_t edge_cr_word(const PicDev *pd, const Geom &g, int mbi, int mbx, uint32_t rec_x, int cr_delta)
+{
+    // neighbours as edge_info_of picks them (self where there is none: the class is unused)
+    const int above = mbi - g.mb_w;
+    const int li = mbx > 0 ? mbi - 1 : mbi, ti = above >= 0 ? above : mbi;
+    const int cqo = cr_offset_of(pd->chroma_qp_offset, cr_delta);
+    const int qp = (int)((rec_x >> 8) & 255u);
+    const int qpL = (int)((gload1(ubase(pd->mb, (uint32_t)li * 16u)) >> 8) & 255u), qpT = (int)((gload1(ubase(pd->mb, (uint32_t)ti * 16u)) >> 8) & 255u);
+    const int own = chroma_qp(clip3i(qp + cqo, 0, 51));
+    return (uint32_t)((own + chroma_qp(clip3i(qpL + cqo, 0, 51)) + 1) >> 1) | (uint32_t)((own + chroma_qp(clip3i(qpT + cqo, 0, 51)) + 1) >> 1) << 6 | (uint32_t)own << 12;
+}
+// k_deblock_bs and the side word.  scale: the batch's ScaleDev array; cr_info: [picture][macroblock]
+template <bool TWO_LISTS>
+__global__ __launch_bounds__(256)
+void k_deblock_bs_cr(const PicDev *__restrict__ pics, Geom g, EdgeInfo *__restrict__ info, uint32_t inv_mbw, const ScaleDev *__restrict__ scale, uint32_t *__restrict__ cr_info)
+{
+    const PicDev *pd = pics + blockIdx.y;
+    if (!pd->deblock) return;
+    __shared__ PicOf pic_tab;
+    if (TWO_LISTS) {
+        if (pd->slice_type == P264_SLICE_B || pd->explicit_wp || pd->dup_refs) pic_of_init(pic_tab, pd);
+        __syncthreads();
+    }
+    const int mbi = blockIdx.x * 256 + threadIdx.x;
+    if (mbi >= g.n_mb) return;
+    int mbx, mby;
+    split_mb(mbi, g, inv_mbw, mbx, mby);
+    const uint4 rec = gload4(ubase(pd->mb, (uint32_t)mbi * 16u));
+    const int *mvs = pd->mv;
+    const uint4 m0 = gload4(ubase(mvs, (uint32_t)mbi * 64u)), m1 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 16u)), m2 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 32u)), m3 = gload4(ubase(mvs, (uint32_t)mbi * 64u + 48u));
+    const uint32_t refs = gload1(ubase(pd->ref_idx, (uint32_t)mbi * 4u));
+    gstore4((uint8_t *)(info + (size_t)blockIdx.y * g.n_mb) + (uint32_t)mbi * 16u, edge_info_of<TWO_LISTS>(pd, g, mbi, mbx, mby, rec, m0, m1, m2, m3, refs, &pic_tab));
+    gstore1((uint8_t *)(cr_info + (size_t)blockIdx.y * g.n_mb) + (uint32_t)mbi * 4u, edge_cr_word(pd, g, mbi, mbx, rec.x, cr_delta_of(scale, (int)blockIdx.y)));
+}
+
 // alpha | tc0 of strengths 1..3 (one dword per index A) and beta (per index B): core/frame.c:262-291
 struct EdgeTables { uint32_t alpha_tc[52]; uint8_t beta[52]; };
 __device__ __forceinline__ void edge_tables_init(EdgeTables &T)
@@ -296,6 +340,23 @@ __device__ __forceinline__ EdgeClass edge_expand(const EdgeTables &T, uint32_t q
     const uint32_t a2 = (v & 0xffu) * 0x00010001u, b2 = be * 0x00010001u;
     EdgeClass c;
     c.ab = make_uint4(a2, b2, 0u - a2 + ((a2 & 0xffffu) ? 0x00010000u : 0u), 0u - b2 + ((b2 & 0xffffu) ? 0x00010000u : 0u));   // (per-half negation: the low half's borrow given back)
+    c.tc = v & 0xffffff00u;
+    return c;
+}
+
+// The Cr instance's nine classes: k = 0 .. 5 as edge_expand, 6 .. 8 Cr's left, top and inner class from the side word (edge_cr_word) -
+// the chroma classes 3 .. 5 with Cr's averaged QP.  k varies per lane here too, so one pass gives a lane any of the nine.
+__device__ __forceinline__ EdgeClass edge_expand_cr(const EdgeTables &T, uint32_t qp, uint32_t avg, uint32_t crw, int k, int alpha_off, int beta_off)
+{
+    const int sh = k < 2 ? 6 * k : 6 * (k - 1);
+    const int q = k >= 6 ? (int)((crw >> (6 * (k - 6))) & 63u) : k == 2 ? (int)(qp & 63u) : (int)((avg >> sh) & 63u);
+    const uint32_t at = T.alpha_tc[clip3i(q + alpha_off + (int)(int8_t)(qp >> 16), 0, 51)];
+    const uint32_t be = T.beta[clip3i(q + beta_off + ((int)qp >> 24), 0, 51)];
+    uint32_t v = at + (k >= 3 ? 0x01010100u : 0u);
+    if (k != 2 && k != 5 && k != 8) v &= 0x00ffffffu;
+    const uint32_t a2 = (v & 0xffu) * 0x00010001u, b2 = be * 0x00010001u;
+    EdgeClass c;
+    c.ab = make_uint4(a2, b2, 0u - a2 + ((a2 & 0xffffu) ? 0x00010000u : 0u), 0u - b2 + ((b2 & 0xffffu) ? 0x00010000u : 0u));
     c.tc = v & 0xffffff00u;
     return c;
 }
@@ -458,10 +519,12 @@ template <int K> __device__ __forceinline__ pk16 pair_byte(uint32_t a, uint32_t 
 #define RING_SLOTS   4
 #define RING_DW      24            // per slot: 4 luma rows x 4 dwords, then 2 planes x 2 rows x 2 dwords
 #define TILE_DW      100           // 16 luma rows x 4 dwords, 2 planes x 8 rows x 2 dwords, +4 so that octets land on different banks
-struct OctLds {                    // per octet: 252 dwords (= 28 modulo 32: the eight octets of a wavefront start on eight different banks)
-    uint32_t tile[TILE_DW];
+#define EDGE_DW_CR   80            // the Cr instance: nine classes (4 + 9 x 8 = 76) and four words so that its octets start on different banks too
+template <int EDGE>
+struct OctLdsT {                   // per octet: 252 dwords (= 28 modulo 32, 60 modulo 64: the eight octets of a wavefront start on eight different banks);
+    uint32_t tile[TILE_DW];        // the Cr instance 276 (= 20 modulo 32 and modulo 64: starts 0, 20, 40, 60, 16, 36, 56, 12 - eight banks again)
     uint32_t ring[RING_SLOTS][RING_DW];
-    uint32_t edge[EDGE_DW];
+    uint32_t edge[EDGE];
 };
 // (MAX_PICS_PER_WG, pictures one workgroup serves: launch_shared.h)
 #define MAX_BANDS (MAX_MB_ROWS / 2)
@@ -473,317 +536,18 @@ struct OctLds {                    // per octet: 252 dwords (= 28 modulo 32: the
 // 0.79 -> 0.91 ms; k_mc is unchanged).  The option is per compilation, there is no per-function form a HIP source can spell.
 #ifdef P264HIP_K_DEBLOCK_DECL_ONLY
 __global__ void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restrict__ info, int *status, int n_pics, int rb_log2_, int pics_per_wg, int odd_single);
+__global__ void k_deblock_cr(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restrict__ info, int *status, int n_pics, int rb_log2_, int pics_per_wg, int odd_single,
+                             const uint32_t *__restrict__ cr_info);
 #else
-__global__ __launch_bounds__(ROW_WAVES * 64)
-void k_deblock(const PicDev *__restrict__ pics, Geom g_, const EdgeInfo *__restrict__ info, int *status, int n_pics, int rb_log2_, int pics_per_wg, int odd_single)
-{
-    __shared__ int progress[MAX_PICS_PER_WG][MAX_BANDS];     // fully stored macroblocks of a band's last row
-    __shared__ OctLds lds[ROW_WAVES][8];
-    __shared__ EdgeTables tables;
-    edge_tables_init(tables);
-    const Geom g = g_;
-    // (the wavefront number is a scalar: without readfirstlane the compiler takes the unit loop for divergent and keeps all of its
-    // book-keeping - unit, band, picture pointers - in vector registers)
-    const int wave = rfl((int)(threadIdx.x >> 6)), n_waves = blockDim.x >> 6, lane = threadIdx.x & 63;
-    // A work unit = (band, group of pictures): `1 << rb_log2` rows of `8 >> rb_log2` pictures.  odd_single (with bands of 4 rows and
-    // an odd number of pictures, round 5): the pictures go in pairs and the LAST one on its own in bands of 8 rows - a pair's
-    // group with one picture missing would issue every instruction of its 17 units for half the lanes.
-    const int n_bands_all = (g.mb_h + (1 << rb_log2_) - 1) >> rb_log2_;
-    const int n_groups_all = (pics_per_wg + (8 >> rb_log2_) - 1) / (8 >> rb_log2_);
-    const int n_pairs = pics_per_wg >> 1, n_bands8 = (g.mb_h + 7) >> 3, per_step = 2 * n_pairs + 1;     // odd_single: units per two pair bands + one single band
-    const int n_units = !odd_single ? n_bands_all * n_groups_all : (n_bands8 - 1) * per_step + (n_bands_all - 2 * (n_bands8 - 1)) * n_pairs + 1;
-    for (int k = threadIdx.x; k < MAX_PICS_PER_WG * MAX_BANDS; k += blockDim.x) (&progress[0][0])[k] = 0;
-    __syncthreads();
-    bool ok = true;
-
-    // units in band-major order: a wavefront takes unit u only after u - n_waves, and band b of a group only waits for band
-    // b - 1 of the same group, which is an earlier unit - nobody waits for a unit that has not been started
-    for (int unit = wave; unit < n_units; unit += n_waves) {
-        // the unit's shape, band and first picture (scalars).  odd_single: steps of {band 2s of every pair, band s of the single
-        // picture, band 2s + 1 of every pair} - a band still only waits for the band above it of the same pictures, an earlier unit
-        int rb_log2 = rb_log2_, band, pic0;
-        if (!odd_single) { band = unit / n_groups_all; pic0 = (unit - band * n_groups_all) * (8 >> rb_log2_); }
-        else {
-            const int st = unit / per_step, r = unit - st * per_step;
-            if (r < n_pairs) { band = 2 * st; pic0 = 2 * r; }
-            else if (r == n_pairs) { rb_log2 = 3; band = st; pic0 = pics_per_wg - 1; }
-            else { band = 2 * st + 1; pic0 = 2 * (r - n_pairs - 1); }
-        }
-        const int RB = 1 << rb_log2, PW = 8 >> rb_log2;         // rows of the band, pictures of the wavefront
-        // Everything that follows from the lane number is derived again per unit (a few dozen instructions against ~100 000 of the
-        // unit): hoisted out of this loop, the lane constants that only the unit's set-up needs (64-bit offsets of the lane's rows,
-        // products with the strip sizes) stayed alive through the iteration loop - the kernel has no register to spare for them
-        // and spilled 17.
-        int lane_u = lane;
-        asm volatile("" : "+v"(lane_u));
-        const int o = lane_u >> 3, j = lane_u & 7;
-        const int gr = o & (RB - 1), pi = o >> rb_log2;           // row inside the band, picture inside the wavefront
-        OctLds &L = lds[wave][o];
-        const int seg2 = (j >> 1) * 2, cseg2 = (j & 3) * 2;       // 2 x the bS segment of this lane's luma / chroma lines
-        const int cp = j >> 2, cr = (j & 3) * 2;                  // chroma plane, first chroma line of this lane
-        uint8_t *tile8 = (uint8_t *)L.tile;
-        const int piw = pic0 + pi;                                // picture inside the workgroup
-        const int pic = blockIdx.x * pics_per_wg + piw;
-        const PicDev *pd = pics + min(pic, n_pics - 1);
-        const bool pic_ok = pi < PW && piw < pics_per_wg && pic < n_pics && pd->deblock;
-        uint8_t *F = pd->dst;                                     // strip frame layout (device_common.h)
-        const EdgeInfo *pinfo = info + (size_t)min(pic, n_pics - 1) * g.n_mb;
-        const int alpha_off = pd->alpha_off, beta_off = pd->beta_off;
-        uint32_t last_qp = 0xffffffffu, last_avg = 0xffffffffu;   // QPs the octet's class parameters in LDS were expanded for
-        const int R0 = band << rb_log2;
-        const int nrows = min(RB, g.mb_h - R0), last = nrows - 1;
-        const int row = R0 + gr;
-        const bool have_row = pic_ok && gr < nrows;
-        const bool below_in_band = gr < last;                  // the row below belongs to the next octet
-        const bool top_exists = row > 0;
-        const bool from_above = have_row && gr == 0 && band > 0;   // the rows above come from the band above, through memory
-        const int rowc = min(row, g.mb_h - 1);
-        // Strip layout: macroblock x of this row owns the 256 luma bytes at x*ystrip + row*256 and the 128 chroma bytes at
-        // coff + x*cstrip + row*128 (rows of 8 bytes U, 8 bytes V).  This lane's two luma rows are the 32 bytes at +32j, its
-        // two chroma rows 8 bytes each: an octet reads and writes whole cache lines.
-        const uint32_t sY = g.ystrip, sC = g.cstrip;
-        uint8_t *ownY = F + (size_t)rowc * MB_LUMA_BYTES + j * 32, *ownC = F + g.coff + (size_t)rowc * MB_CHROMA_BYTES + cr * 16 + cp * 8;
-        // the rows above (valid if top_exists): lanes 0..3 luma rows 12..15 of the macroblock above, lanes 4..7 its chroma
-        // rows 6,7 of plane (j>>1)&1
-        const uint32_t sT = j < 4 ? sY : sC;
-        uint8_t *topP = j < 4 ? F + (ptrdiff_t)(rowc - 1) * MB_LUMA_BYTES + 192 + j * 16
-                              : F + g.coff + (ptrdiff_t)(rowc - 1) * MB_CHROMA_BYTES + (6 + (j & 1)) * 16 + ((j >> 1) & 1) * 8;
-        // Addresses inside the iteration loop: macroblock x = t - 2 gr of the row.  The lane-constant part (- 2 gr strips) is folded
-        // into the bases here, in 64-bit arithmetic, so that the loop adds only t x strip - a scalar - to one pointer per array
-        // (as (uint32) x * strip the compiler cannot fold it and keeps one 64-bit constant per array alive: registers it does not have).
-        const ptrdiff_t lag = -(ptrdiff_t)(DB_LAG * gr);
-        uint8_t *ownY0 = ownY + lag * (ptrdiff_t)sY, *ownC0 = ownC + lag * (ptrdiff_t)sC, *topP0 = topP + lag * (ptrdiff_t)sT;
-        const EdgeInfo *pinfo0 = pinfo + (ptrdiff_t)row * g.mb_w + lag;
-        int *my_progress = &progress[piw & (MAX_PICS_PER_WG - 1)][band];
-        const bool publisher = have_row && gr == last && j == 0;
-        OctLds &Lnext = lds[wave][min(o + 1, 7)];
-
-        uint32_t ya0 = 0, yb0 = 0, ca0 = 0, cb0 = 0;                  // columns -4..-1: the previous macroblock's last four
-        uint4 fYa = make_uint4(0, 0, 0, 0), fYb = fYa, fC = fYa, fT = fYa, fE = fYa;   // in flight for the next iteration
-        const int n_iter = g.mb_w + 1 + DB_LAG * last;
-        const int *wait_on = from_above ? my_progress - 1 : my_progress;
-        // tile addresses of this lane's rows
-        uint32_t *tYa = L.tile + (2 * j) * 4, *tYb = tYa + 4, *tCa = L.tile + 64 + cp * 16 + cr * 2, *tCb = tCa + 2;
-
-        // loads for iteration t
-        auto prefetch = [&](int t) {
-            const int x = t - DB_LAG * gr;
-            const bool actn = have_row && x >= 0 && x < g.mb_w;
-            if (ok) {
-                // macroblock x needs the band above to have stored x completely
-                const bool need = from_above && actn;
-                const int want = x + 1;
-                int spins = 0;
-                while (__ballot(need && __hip_atomic_load(wait_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < want)) {
-                    __builtin_amdgcn_s_sleep(DEBLOCK_WAIT_SLEEP);
-                    if (++spins > SPIN_LIMIT) { if (lane_u == 0) atomicOr(status, 1); ok = false; break; }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            }
-            if (actn) {
-                if (j == 0) fE = gload4(pinfo0 + t);
-                const uint8_t *tp = topP0 + (ptrdiff_t)t * (ptrdiff_t)sT;
-                if (from_above) {
-                    if (j < 4) fT = gload4(tp);
-                    else { uint2 v2 = gload2(tp); fT.x = v2.x; fT.y = v2.y; }
-                }
-                const uint8_t *yp = ownY0 + (ptrdiff_t)t * (ptrdiff_t)sY, *cp2 = ownC0 + (ptrdiff_t)t * (ptrdiff_t)sC;
-                fYa = gload4(yp); fYb = gload4(yp + 16);
-                const uint2 ca2 = gload2(cp2), cb2 = gload2(cp2 + 16);
-                fC = make_uint4(ca2.x, ca2.y, cb2.x, cb2.y);
-            }
-        };
-
-        prefetch(0);
-        for (int t = 0; t < n_iter; t++) {
-            const int x = t - DB_LAG * gr;
-            const bool act = have_row && x >= 0 && x < g.mb_w;         // filter macroblock x
-            const bool flush = have_row && x >= 1 && x <= g.mb_w;       // store macroblock x-1
-            uint32_t *ring = L.ring[x & 3];
-            // ---- land what was prefetched for this iteration: pixels stay in registers for the vertical pass ----
-            uint32_t ya[5] = { ya0, fYa.x, fYa.y, fYa.z, fYa.w }, yb[5] = { yb0, fYb.x, fYb.y, fYb.z, fYb.w };
-            uint32_t ca[3] = { ca0, fC.x, fC.y }, cb[3] = { cb0, fC.z, fC.w };
-            if (act) {
-                if (from_above) {
-                    if (j < 4) *(uint4 *)(ring + j * 4) = fT;
-                    else *(uint2 *)(ring + 16 + (j - 4) * 2) = make_uint2(fT.x, fT.y);
-                }
-                if (j == 0) *(uint4 *)L.edge = fE;
-            }
-            // Everything this wave has issued is complete here (the prefetch was issued before the previous
-            // iteration's horizontal pass, its stores before that): macroblocks 0 .. x-2 of this row are in memory.
-            // Publish with RELEASE semantics at workgroup scope: the band below reads these macroblocks' pixels through global
-            // memory on the same CU.  (The explicit wait drains the WHOLE wave's stores - the publisher lane speaks for all
-            // eight octets of its wave, and a release fence only orders the publishing lane's own view.)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (publisher) __hip_atomic_store(my_progress, min(max(x - 1, 0), g.mb_w), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            wave_lds_fence();
-            // the rows above macroblock x-1 were finished by its horizontal pass in the previous iteration
-            if (flush && top_exists) {
-                const uint32_t *pr = L.ring[(x - 1) & 3];
-                uint8_t *tp = topP0 + (ptrdiff_t)(t - 1) * (ptrdiff_t)sT;
-                if (j < 4) gstore4(tp, *(const uint4 *)(pr + j * 4));
-                else gstore2(tp, *(const uint2 *)(pr + 16 + (j - 4) * 2));
-            }
-            EdgeRegs E;
-            {
-                const uint4 v = act ? *(const uint4 *)L.edge : make_uint4(0, 0, 0, 0);
-                E.e[0] = v.x; E.e[1] = v.y; E.lds = L.edge;
-                // the class parameters of the octet's LDS copy follow the macroblock's QPs and offset deltas (v.z holds both): expanded
-                // again only when those change
-                const bool changed = act && (v.z != last_qp || v.w != last_avg);
-                if (__ballot(changed)) {
-                    if (act) {
-                        if (j < 6) { const EdgeClass ec = edge_expand(tables, v.z, v.w, j, alpha_off, beta_off); *(uint4 *)(L.edge + 4 + 8 * j) = ec.ab; L.edge[8 + 8 * j] = ec.tc; }
-                        last_qp = v.z; last_avg = v.w;
-                    }
-                    wave_lds_fence();
-                }
-            }
-            const bool any_edges = __ballot((E.e[0] | E.e[1]) != 0) != 0;
-
-            if (any_edges) {
-                // ---------- vertical edges, in registers ----------
-#pragma unroll
-                for (int ed = 0; ed < 4; ed++) {
-                    const int b = E.code(0, ed, seg2), k = edge_class(0, ed);
-                    if (__ballot(b != 0) == 0) continue;
-                    pk16 p2 = pair_byte<1>(ya[ed], yb[ed]), p1 = pair_byte<2>(ya[ed], yb[ed]), p0 = pair_byte<3>(ya[ed], yb[ed]);
-                    pk16 q0 = pair_byte<0>(ya[ed+1], yb[ed+1]), q1 = pair_byte<1>(ya[ed+1], yb[ed+1]), q2 = pair_byte<2>(ya[ed+1], yb[ed+1]);
-                    const EdgeParams ep(E, k);
-                    const pk16 A = as_pk(ep.alpha2()), B = as_pk(ep.beta2()), nA = as_pk(ep.nalpha2()), nB = as_pk(ep.nbeta2());
-                    pk16 e;
-                    const pk16 f = pk_edge_flag(p1, p0, q0, q1, A, nA, B, nB, e);
-                    const pk16 ap = pk_sign(pk_within(p2 - p0, B, nB)), aq = pk_sign(pk_within(q2 - q0, B, nB));
-                    const pk16 en = as_pk(mask_bs123(b, ed));
-                    const pk16 op2 = p2, op1 = p1, op0 = p0, oq0 = q0, oq1 = q1, oq2 = q2;
-                    pk_luma_normal(p2, p1, p0, q0, q1, q2, e, f & en, ap, aq, as_pk(ep.tc2(b)));
-                    // bS 4 exists on macroblock edges only (k_deblock_bs), and the strong filter changes nothing where the
-                    // sample flag is off
-                    if (ed == 0 && __ballot((as_u(f) & mask_bs4(b)) != 0)) {
-                        const pk16 str = as_pk(mask_bs4(b));
-                        pk16 sp2 = op2, sp1 = op1, sp0 = op0, sq0 = oq0, sq1 = oq1, sq2 = oq2;
-                        pk_luma_strong(pair_byte<0>(ya[ed], yb[ed]), sp2, sp1, sp0, sq0, sq1, sq2, pair_byte<3>(ya[ed+1], yb[ed+1]), f & str, ap, aq, A);
-                        p1 = pk_sel(str, sp1, p1); p0 = pk_sel(str, sp0, p0); q0 = pk_sel(str, sq0, q0); q1 = pk_sel(str, sq1, q1);
-                        ya[ed] = perm(as_u(sp2), ya[ed], 0x03020400u);   yb[ed] = perm(as_u(sp2), yb[ed], 0x03020600u);
-                        ya[ed+1] = perm(as_u(sq2), ya[ed+1], 0x03040100u); yb[ed+1] = perm(as_u(sq2), yb[ed+1], 0x03060100u);
-                    }
-                    // p0 / q0 clipped into byte pairs (row 2j in byte 0, row 2j+1 in byte 1), merged with p1 / q1: bytes {p1 a, p0 a, p1 b, p0 b}
-                    const uint32_t tp = perm(pk_clip_bytes(p0), as_u(p1), 0x05020400u), tq = perm(as_u(q1), pk_clip_bytes(q0), 0x06010400u);
-                    ya[ed] = perm(tp, ya[ed], 0x05040100u);     yb[ed] = perm(tp, yb[ed], 0x07060100u);
-                    ya[ed+1] = perm(tq, ya[ed+1], 0x03020504u); yb[ed+1] = perm(tq, yb[ed+1], 0x03020706u);
-                }
-#pragma unroll
-                for (int ed = 0; ed < 4; ed += 2) {
-                    const int b = E.code(0, ed, cseg2), k = edge_class(0, ed) + 3, c = ed >> 1;
-                    if (__ballot(b != 0) == 0) continue;
-                    pk16 p1 = pair_byte<2>(ca[c], cb[c]), p0 = pair_byte<3>(ca[c], cb[c]);
-                    pk16 q0 = pair_byte<0>(ca[c+1], cb[c+1]), q1 = pair_byte<1>(ca[c+1], cb[c+1]);
-                    const EdgeParams ep(E, k);
-                    const pk16 A = as_pk(ep.alpha2()), B = as_pk(ep.beta2());
-                    pk16 e;
-                    const pk16 f = pk_edge_flag(p1, p0, q0, q1, A, as_pk(ep.nalpha2()), B, as_pk(ep.nbeta2()), e);
-                    pk_chroma(p1, p0, q0, q1, e, f, as_pk(mask_bs123(b, ed)), as_pk(ed == 0 ? mask_bs4(b) : 0u), ed == 0 && __ballot(b == 3) != 0, as_pk(ep.tc2(b)));
-                    const uint32_t P0 = pk_clip_bytes(p0), Q0 = pk_clip_bytes(q0);      // (row a in byte 0, row b in byte 1)
-                    ca[c] = perm(P0, ca[c], 0x04020100u);     cb[c] = perm(P0, cb[c], 0x05020100u);
-                    ca[c+1] = perm(Q0, ca[c+1], 0x03020104u); cb[c+1] = perm(Q0, cb[c+1], 0x03020105u);
-                }
-            }
-            // ---- macroblock x-1 is final now: columns 0..11 still sit in the tile, its last four columns are ya[0]/yb[0].
-            // Store it as whole rows; rows 12..15 go to the octet below instead, which stores them as its "rows above".
-            if (flush) {
-                uint4 sa = *(const uint4 *)tYa, sb = *(const uint4 *)tYb;
-                uint2 ta = *(const uint2 *)tCa, tb = *(const uint2 *)tCb;
-                sa.w = ya[0]; sb.w = yb[0]; ta.y = ca[0]; tb.y = cb[0];
-                uint32_t *nr = Lnext.ring[(x - 1) & 3];
-                uint8_t *yp = ownY0 + (ptrdiff_t)(t - 1) * (ptrdiff_t)sY, *cp2 = ownC0 + (ptrdiff_t)(t - 1) * (ptrdiff_t)sC;
-                if (below_in_band && j >= 6) { *(uint4 *)(nr + (2 * j - 12) * 4) = sa; *(uint4 *)(nr + (2 * j - 11) * 4) = sb; }
-                else { gstore4(yp, sa); gstore4(yp + 16, sb); }
-                if (below_in_band && (j & 3) == 3) { *(uint2 *)(nr + 16 + cp * 4) = ta; *(uint2 *)(nr + 16 + cp * 4 + 2) = tb; }
-                else { gstore2(cp2, ta); gstore2(cp2 + 16, tb); }
-            }
-            wave_lds_fence();
-            // ---------- rows of macroblock x -> tile ----------
-            if (act) {
-                *(uint4 *)tYa = make_uint4(ya[1], ya[2], ya[3], ya[4]); *(uint4 *)tYb = make_uint4(yb[1], yb[2], yb[3], yb[4]);
-                *(uint2 *)tCa = make_uint2(ca[1], ca[2]);               *(uint2 *)tCb = make_uint2(cb[1], cb[2]);
-            }
-            wave_lds_fence();
-            if (t + 1 < n_iter) prefetch(t + 1);                      // the next iteration's loads travel during the horizontal pass
-            // ---------- horizontal edges: column pairs out of the tile, filtered, back into the tile ----------
-            const bool h_edges = __ballot(E.e[1] != 0) != 0;
-            if (h_edges) {
-                if (act) {
-                    // luma: columns 2j, 2j+1
-                    const uint8_t *top = (const uint8_t *)ring + 2 * j, *col = tile8 + 2 * j;
-                    pk16 c[20];
-#pragma unroll
-                    for (int r = 0; r < 4; r++) { uint32_t v = *(const uint16_t *)(top + r * 16); c[r] = as_pk(perm(v, v, 0x0c010c00u)); }
-#pragma unroll
-                    for (int r = 0; r < 16; r++) { uint32_t v = *(const uint16_t *)(col + r * 16); c[4 + r] = as_pk(perm(v, v, 0x0c010c00u)); }
-#pragma unroll
-                    for (int ed = 0; ed < 4; ed++) {
-                        const int b = E.code(1, ed, seg2), k = edge_class(1, ed);
-                        if (__ballot(b != 0) == 0) continue;
-                        pk16 &p3 = c[4*ed], &p2 = c[4*ed+1], &p1 = c[4*ed+2], &p0 = c[4*ed+3], &q0 = c[4*ed+4], &q1 = c[4*ed+5], &q2 = c[4*ed+6], &q3 = c[4*ed+7];
-                        const EdgeParams ep(E, k);
-                        const pk16 A = as_pk(ep.alpha2()), B = as_pk(ep.beta2()), nA = as_pk(ep.nalpha2()), nB = as_pk(ep.nbeta2());
-                        pk16 e;
-                        const pk16 f = pk_edge_flag(p1, p0, q0, q1, A, nA, B, nB, e);
-                        const pk16 ap = pk_sign(pk_within(p2 - p0, B, nB)), aq = pk_sign(pk_within(q2 - q0, B, nB));
-                        const pk16 en = as_pk(mask_bs123(b, ed));
-                        pk16 sp2 = p2, sp1 = p1, sp0 = p0, sq0 = q0, sq1 = q1, sq2 = q2;
-                        pk_luma_normal(p2, p1, p0, q0, q1, q2, e, f & en, ap, aq, as_pk(ep.tc2(b)));
-                        if (ed == 0 && __ballot((as_u(f) & mask_bs4(b)) != 0)) {
-                            const pk16 str = as_pk(mask_bs4(b));
-                            pk_luma_strong(p3, sp2, sp1, sp0, sq0, sq1, sq2, q3, f & str, ap, aq, A);
-                            p2 = pk_sel(str, sp2, p2); p1 = pk_sel(str, sp1, p1); p0 = pk_sel(str, sp0, p0);
-                            q0 = pk_sel(str, sq0, q0); q1 = pk_sel(str, sq1, q1); q2 = pk_sel(str, sq2, q2);
-                        }
-                    }
-                    // rows -3 .. 14 back (row -4 cannot change).  The rows either side of an edge (p0 / q0: -1 | 0, 3 | 4, 7 | 8, 11 | 12) may
-                    // hold p0 + delta / q0 - delta not yet clipped: clipped into a byte pair here, one 16-bit store
-                    {
-                        uint8_t *topw = (uint8_t *)ring + 2 * j, *colw = tile8 + 2 * j;
-                        lds_put_pair<1 * 16>(topw, c[1]); lds_put_pair<2 * 16>(topw, c[2]); lds_put_clipped<3 * 16>(topw, c[3]);
-                        lds_put_clipped<0 * 16>(colw, c[4]);  lds_put_pair<1 * 16>(colw, c[5]);   lds_put_pair<2 * 16>(colw, c[6]);   lds_put_clipped<3 * 16>(colw, c[7]);
-                        lds_put_clipped<4 * 16>(colw, c[8]);  lds_put_pair<5 * 16>(colw, c[9]);   lds_put_pair<6 * 16>(colw, c[10]);  lds_put_clipped<7 * 16>(colw, c[11]);
-                        lds_put_clipped<8 * 16>(colw, c[12]); lds_put_pair<9 * 16>(colw, c[13]);  lds_put_pair<10 * 16>(colw, c[14]); lds_put_clipped<11 * 16>(colw, c[15]);
-                        lds_put_clipped<12 * 16>(colw, c[16]); lds_put_pair<13 * 16>(colw, c[17]); lds_put_pair<14 * 16>(colw, c[18]);
-                    }
-                    // chroma: columns cr, cr+1 of plane cp; only rows -1, 0, 3, 4 can change
-                    const uint8_t *ctop = (const uint8_t *)ring + 64 + cp * 16 + cr;
-                    uint8_t *ccol = tile8 + 256 + cp * 64 + cr;
-                    pk16 d[10];
-#pragma unroll
-                    for (int r = 0; r < 2; r++) { uint32_t v = *(const uint16_t *)(ctop + r * 8); d[r] = as_pk(perm(v, v, 0x0c010c00u)); }
-#pragma unroll
-                    for (int r = 0; r < 8; r++) { uint32_t v = *(const uint16_t *)(ccol + r * 8); d[2 + r] = as_pk(perm(v, v, 0x0c010c00u)); }
-#pragma unroll
-                    for (int ed = 0; ed < 4; ed += 2) {
-                        const int b = E.code(1, ed, cseg2), k = edge_class(1, ed) + 3;
-                        if (__ballot(b != 0) == 0) continue;
-                        const EdgeParams ep(E, k);
-                        const pk16 A = as_pk(ep.alpha2()), B = as_pk(ep.beta2());
-                        pk16 e;
-                        const pk16 f = pk_edge_flag(d[2*ed], d[2*ed+1], d[2*ed+2], d[2*ed+3], A, as_pk(ep.nalpha2()), B, as_pk(ep.nbeta2()), e);
-                        pk_chroma(d[2*ed], d[2*ed+1], d[2*ed+2], d[2*ed+3], e, f, as_pk(mask_bs123(b, ed)), as_pk(ed == 0 ? mask_bs4(b) : 0u), ed == 0 && __ballot(b == 3) != 0, as_pk(ep.tc2(b)));
-                    }
-                    // (all four are p0 / q0 rows: clipped here)
-                    lds_put_clipped<8>((uint8_t *)ring + 64 + cp * 16 + cr, d[1]);
-                    lds_put_clipped<0>(ccol, d[2]);
-                    lds_put_clipped<3 * 8>(ccol, d[5]);
-                    lds_put_clipped<4 * 8>(ccol, d[6]);
-                }
-                wave_lds_fence();
-            }
-            // the last four columns of this macroblock are the next one's columns -4..-1
-            if (act) { ya0 = tYa[3]; yb0 = tYb[3]; ca0 = tCa[1]; cb0 = tCb[1]; }
-            wave_lds_fence();
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (publisher) __hip_atomic_store(my_progress, g.mb_w, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        wave_lds_fence();
-    }
-}
+// The two kernels are ONE text, kernel_deblock_body.h, included once each: k_deblock (DEBLOCK_CR 0) and k_deblock_cr (DEBLOCK_CR 1, K4c:
+// batches that hold a picture whose Cr has a QP offset of its own - the lanes of chroma plane 1 read three classes of their own, Cr
+// left / top / inner, expanded from the side word of edge_cr_word, where the other kernel's read Cb's; luma and Cb are instruction for
+// instruction what k_deblock does; +24 dwords of LDS per octet).  (As two instances of a template behind __global__ wrappers the
+// flat kernel came out one register and 24 bytes larger than the kernel written out: included text leaves it what it was.)
+#define DEBLOCK_CR 0
+#include "kernel_deblock_body.h"
+#undef DEBLOCK_CR
+#define DEBLOCK_CR 1
+#include "kernel_deblock_body.h"
+#undef DEBLOCK_CR
 #endif   // P264HIP_K_DEBLOCK_DECL_ONLY

@@ -488,7 +488,7 @@ __device__ __forceinline__ void intra_luma4(const PicDev *pd, const Geom &g, Int
 // (core/predict.c:199-361, decoder/macroblock.c:721-753,851-890)
 // ------------------------------------------------------------------------------------------
 template <bool SC>
-__device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, IntraGrp &L, const uint8_t *sw, int mbx, int mby, const uint4 rec, int l)
+__device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, IntraGrp &L, const uint8_t *sw, int mbx, int mby, const uint4 rec, int l, const int cr_delta)
 {
     asm volatile("" : "+v"(l));                            // (as in intra_luma4)
     const int X0 = mbx * 8, Y0 = mby * 8;
@@ -528,7 +528,8 @@ __device__ __forceinline__ void intra_chroma4(const PicDev *pd, const Geom &g, I
     // ---- residuals of the eight blocks (residual4x4.h) ----
     if (__ballot(has_chroma)) {
         if (l < 8) {
-            const int qpc = chroma_qp(clip3i(qp + pd->chroma_qp_offset, 0, 51));
+            // (SC: Cr's lanes, l >> 2 = 1, with the picture's cr_qp_offset_delta on top - kernel_scaling.h: plane_qpc)
+            const int qpc = SC ? plane_qpc(qp, pd->chroma_qp_offset, cr_delta, (l & 4) != 0) : chroma_qp(clip3i(qp + pd->chroma_qp_offset, 0, 51));
             const uint32_t lv[8] = { la.x, la.y, la.z, la.w, lb.x, lb.y, lb.z, lb.w };
             uint32_t col[4][2], rr[4][2];
             unscan_cols<true>(lv, col);
@@ -643,6 +644,7 @@ __device__ __forceinline__ void intra_picture(IntraShared<I8, SC> &sh, const Pic
     for (int i = threadIdx.x; i < INTRA_LUT_ENTRIES; i += blockDim.x) lut[i] = lut_entry(i >> 4, i & 3, (i >> 2) & 3);
     if (I8) for (int i = threadIdx.x; i < INTRA_LUT8_ENTRIES; i += blockDim.x) lut8[i] = lut8_entry(i >> 6, i & 7, (i >> 3) & 7);
     if (SC) scaling_to_lds(sw, scale[pic_index].lists);     // (the picture's table, or the all-16 one of a flat picture)
+    const int cr_delta = SC ? scale[pic_index].cr_delta : 0;    // (scalar: what Cr's qPI adds to Cb's, kernel_scaling.h)
     for (int i = threadIdx.x; i <= n_bands; i += blockDim.x) sync.progress[i] = 0;
     const int wins = (g.mb_w + 63) / 64, n_win = g.mb_h * wins;
     const bool use_free = pd->slice_type != P264_SLICE_I && n_win <= INTRA_MASKS && g.n_mb < 65536;     // (scalar)
@@ -726,7 +728,7 @@ __device__ __forceinline__ void intra_picture(IntraShared<I8, SC> &sh, const Pic
                     int mbx, mby;
                     split_mb(mbi, g, inv_mbw, mbx, mby);
                     if (active) {
-                        if (chroma_role) intra_chroma4<SC>(pd, g, L, sw, mbx, mby, rec, l);
+                        if (chroma_role) intra_chroma4<SC>(pd, g, L, sw, mbx, mby, rec, l, cr_delta);
                         else             intra_luma4<I8, SC>(pd, g, L, lut, lut8, sw, mbx, mby, rec, l);
                     }
                     k = kn; mbi = mbi_n; rec = rec_n;
@@ -855,7 +857,7 @@ __device__ __forceinline__ void intra_picture(IntraShared<I8, SC> &sh, const Pic
             const uint4 rec = make_uint4(pick(srec[0].x, srec[1].x, srec[2].x, srec[3].x), pick(srec[0].y, srec[1].y, srec[2].y, srec[3].y),
                                          pick(srec[0].z, srec[1].z, srec[2].z, srec[3].z), pick(srec[0].w, srec[1].w, srec[2].w, srec[3].w));
             if (active) {
-                if (chroma_role) intra_chroma4<SC>(pd, g, L, sw, mbx, R0 + grp, rec, l);
+                if (chroma_role) intra_chroma4<SC>(pd, g, L, sw, mbx, R0 + grp, rec, l, cr_delta);
                 else             intra_luma4<I8, SC>(pd, g, L, lut, lut8, sw, mbx, R0 + grp, rec, l);
             }
 #pragma unroll

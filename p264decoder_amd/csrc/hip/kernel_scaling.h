@@ -16,6 +16,10 @@
 // such a picture takes (k_mc_sort_scaled / k_mc_sort_scaled_p, k_scaled_inter, k_intra_scaled / k_intra_sparse_scaled); PicDev and
 // the kernels of flat batches are what they were.  The batch's flat pictures get an all-16 table from the host: nothing in here
 // branches on "flat".
+//
+// A picture whose Cr has a QP offset of its own (cr_qp_offset_delta != 0) takes the same road, with the all-16 table where it has no
+// lists: the delta sits beside the table in its ScaleDev, and the lanes of plane 1 add it to the offset (plane_qpc below).  The same
+// rule: PicDev and the kernels of flat batches do not know it.
 #pragma once
 #include "device_common.h"
 #include "residual4x4.h"
@@ -23,7 +27,8 @@
 
 struct ScaleDev {
     const uint8_t *lists;          // P264HIP_SCALING_BYTES: the picture's table in its input slot, or the context's all-16 table
-    int32_t scaled, pad;           // the picture has scaling_lists: the sort files its residuals as absent, k_scaled_inter adds them
+    int32_t scaled, cr_delta;      // scaled: the picture has scaling_lists or a Cr offset of its own: the sort files its residuals as absent,
+                                   // k_scaled_inter adds them.  cr_delta: cr_qp_offset_delta (include/p264hip.h), what Cr's qPI adds to Cb's
 };
 static_assert(sizeof(ScaleDev) == 16, "ScaleDev: one per picture, indexed by every kernel that takes the array");
 
@@ -75,6 +80,10 @@ __device__ __forceinline__ int chroma_dc_level_w(uint2 dcl, bool right, bool low
     const int per = (qpc * 43) >> 8, rem = qpc - per * 6;
     return (int)((unsigned)(f * (w00 * (int)dq_s(0, rem))) << per) >> 5;
 }
+// QPc of a lane's chroma plane (8.5.8 with the plane's own offset): Cb's qPI is Clip3(0, 51, QPY + offset), Cr's
+// Clip3(0, 51, QPY + offset + cr_delta) - cr_offset_of (device_common.h) keeps the sum of any two ints defined
+__device__ __forceinline__ int plane_qpc(int qp, int offset, int cr_delta, bool cr) { return chroma_qp(clip3i(qp + (cr ? cr_offset_of(offset, cr_delta) : offset), 0, 51)); }
+__device__ __forceinline__ int cr_delta_of(const ScaleDev *scale, int pic) { return scale[pic].cr_delta; }     // (declared in kernel_deblock.h, which does not know the struct)
 // 8.5.13, the levels of an 8x8 block: t8_scatter of kernel_t8x8.h with a T8List of the table's list 6 (intra) or 7 (inter)
 __device__ __forceinline__ T8List scaling_list8(const uint8_t *sw, int n) { return T8List{ sw + SCL_8X8_AT + 64 * (n - 6) }; }
 
@@ -132,7 +141,7 @@ void k_scaled_inter(const PicDev *__restrict__ pics, const ScaleDev *__restrict_
             const uint32_t lv[8] = { la.x, la.y, la.z, la.w, lb.x, lb.y, lb.z, lb.w };
             uint32_t col[4][2];
             if (chroma) {
-                const int qpc = chroma_qp(clip3i(qp + pd->chroma_qp_offset, 0, 51));
+                const int qpc = plane_qpc(qp, pd->chroma_qp_offset, sd->cr_delta, p != 0);
                 unscan_cols<true>(lv, col);
                 scale_cols_w(col, qpc, wr);
                 const int dc = chroma_dc_level_w(dcl, j & 1, j & 2, qpc, (int)(wr.x & 255u));

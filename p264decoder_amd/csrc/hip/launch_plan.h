@@ -10,8 +10,9 @@
 // What the batch holds - the kernel instances and launch shapes follow from it: any picture with inter macroblocks / any B picture /
 // any I picture / any explicit weights / any unweighted P picture whose list 0 holds one frame at several indices / any picture
 // whose inter macroblocks may use the 8x8 transform / any picture whose Intra4x4 records may carry P264_MB_I8X8; sc: how many
-// pictures have scaling_lists.  (As batch_fill fills it, wp, dup and t8 come with p: only pictures with inter macroblocks set them.)
-struct BatchKinds { bool p = false, b = false, i = false, wp = false, dup = false, t8 = false, i8 = false; int sc = 0; };
+// pictures take the scaled road (scaling_lists, or a Cr QP offset of its own); cr: any picture with a non-zero cr_qp_offset_delta (sc
+// counts it) and n_cr: how many.  (As batch_fill fills it, wp, dup and t8 come with p: only pictures with inter macroblocks set them.)
+struct BatchKinds { bool p = false, b = false, i = false, wp = false, dup = false, t8 = false, i8 = false; int sc = 0; bool cr = false; int n_cr = 0; };
 
 // tuning knobs, read from the environment ONCE per context (p264hip_create); 0 (bs_fused, odd_single, mc_band_log2: -1) = built-in
 // choice.  The values are kept as read; the shapes ignore what is out of their range.
@@ -67,6 +68,7 @@ struct LaunchPlan {
     LaunchShape deblock_shape;
     bool copy_scale_table = false;                  // the batch's ScaleDev array travels to the device
     p264hip_launch_info_t info = {};                // what p264hip_last_launch reports of the batch
+    bool deblock_cr = false;                        // the Cr instances of the loop filter's two launches (k_deblock_bs_cr, k_deblock_cr: kernel_deblock.h, K4c)
 };
 
 // k_mc: every picture gets the same number of workgroups, which split into the four roles on the device.  Enough workgroups per
@@ -195,5 +197,9 @@ static inline LaunchPlan plan_launches(const LaunchDevice &dev, const LaunchKnob
 
     deblock_shape(dev, knobs, n, &li);
     pl.deblock_shape = LaunchShape{ (unsigned)li.deblock_wgs, 1, (unsigned)li.deblock_waves * 64 };
+    // a picture whose Cr has a QP offset of its own: the instances that carry Cr's averaged QPs beside the EdgeInfo, same roads and
+    // shapes (never fused: such a batch is a scaled one, edge_info_fused)
+    pl.deblock_cr = k.cr;
+    li.cr_pictures = k.n_cr;
     return pl;
 }

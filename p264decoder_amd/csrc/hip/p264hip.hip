@@ -116,7 +116,7 @@ struct p264hip_ctx {
     size_t frame_bytes = 0;
     std::vector<PicSlot> pics;
     PicDev *h_batch[BATCH_RING] = {}, *d_batch[BATCH_RING] = {};
-    // pictures with scaling_lists: one ScaleDev per picture of the batch beside its PicDev (copied only for batches that hold such a
+    // pictures with scaling_lists or a cr_qp_offset_delta: one ScaleDev per picture of the batch beside its PicDev (copied only for batches that hold such a
     // picture), and the all-16 table the batch's flat pictures point to
     ScaleDev *h_scale[BATCH_RING] = {}, *d_scale[BATCH_RING] = {};
     uint8_t *d_flat16 = nullptr;
@@ -136,6 +136,7 @@ struct p264hip_ctx {
     uint64_t upload_copies = 0;            // host -> HBM copies queued by p264hip_upload / _upload_async (one per picture whose arrays lie like a slot)
     uint64_t epoch = 0, done_epoch = 0;    // work queued on the stream / known to have completed (a slot is free for a new producer once its last_use is done)
     EdgeInfo *d_edge = nullptr;            // [batch_cap][n_mb], scratch between k_deblock_bs and k_deblock
+    uint32_t *d_edge_cr = nullptr;         // [batch_cap][n_mb], Cr's averaged QPs beside it (k_deblock_bs_cr -> k_deblock_cr); from the first batch with a cr_qp_offset_delta
     uint32_t *d_mc = nullptr;              // [batch_cap][dev.ml.words], motion-compensation work lists (k_mc_sort -> k_mc, k_mc_second)
     uint8_t *d_is_intra = nullptr;         // [batch_cap][n_mb], 1 = intra macroblock (k_mc_sort -> k_intra's collect pass; P / B pictures)
     // what the launch plan is a function of, beside the batch (launch_plan.h): the P264AMD_* tuning knobs, read from the environment
@@ -238,6 +239,7 @@ extern "C" void p264hip_destroy(p264hip_ctx *c)
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     if (c->frames) (void)hipFree(c->frames);
     if (c->d_edge) (void)hipFree(c->d_edge);
+    if (c->d_edge_cr) (void)hipFree(c->d_edge_cr);
     if (c->d_mc) (void)hipFree(c->d_mc);
     if (c->d_is_intra) (void)hipFree(c->d_is_intra);
     if (c->d_planar) (void)hipFree(c->d_planar);
@@ -759,8 +761,16 @@ static int batch_reserve(p264hip_ctx *c, int n)
     int rc = grow(c, (void **)&c->d_is_intra, nullptr, (size_t)n * c->g.n_mb, 0, false, WAIT_NONE, "the batch");
     if (rc || (rc = grow(c, (void **)&c->d_edge, nullptr, (size_t)n * c->g.n_mb * sizeof(EdgeInfo), 0, false, WAIT_NONE, "the batch")) ||
         (rc = grow(c, (void **)&c->d_mc, nullptr, (size_t)n * c->dev.ml.words * sizeof(uint32_t), 0, false, WAIT_NONE, "the batch"))) return rc;
+    // (the Cr side array, if the context has one, grows with the others; the stream has been waited for above)
+    if (c->d_edge_cr && (rc = grow(c, (void **)&c->d_edge_cr, nullptr, (size_t)n * c->g.n_mb * sizeof(uint32_t), 0, false, WAIT_NONE, "the batch"))) return rc;
     c->batch_cap = n;
     return 0;
+}
+// the first batch that holds a picture with a cr_qp_offset_delta: one dword per macroblock for every picture a batch can hold
+static int edge_cr_reserve(p264hip_ctx *c)
+{
+    if (c->d_edge_cr) return 0;
+    return grow(c, (void **)&c->d_edge_cr, nullptr, (size_t)c->batch_cap * c->g.n_mb * sizeof(uint32_t), 0, false, WAIT_NONE, "the batch");
 }
 
 // pictures that came through p264hip_input_commit: the verdicts of their record checks, one wait for the whole batch
@@ -846,9 +856,14 @@ static int batch_fill(p264hip_ctx *c, const int *pic_ids, const int *streams, in
         k.dup |= hb[i].dup_refs != 0;
         k.t8 |= (s.meta.transform_8x8 & ~P264_T8X8_INTRA) != 0 && s.meta.slice_type != P264_SLICE_I;
         k.i8 |= (s.meta.transform_8x8 & P264_T8X8_INTRA) != 0;
-        // the picture's table in its slot; a flat picture: the all-16 table (what a batch with a scaled picture runs it through)
-        hs[i] = ScaleDev{ s.meta.scaling_lists ? s.dev + s.L.off_scaling : c->d_flat16, s.meta.scaling_lists ? 1 : 0, 0 };
-        k.sc += s.meta.scaling_lists != 0;
+        // the picture's table in its slot; a flat picture: the all-16 table (what a batch with a scaled picture runs it through).  A
+        // picture whose Cr has a QP offset of its own takes the scaled road too, with the all-16 table where it has no lists
+        const int cr_delta = s.meta.cr_qp_offset_delta;
+        const bool scaled = s.meta.scaling_lists != 0 || cr_delta != 0;
+        hs[i] = ScaleDev{ s.meta.scaling_lists ? s.dev + s.L.off_scaling : c->d_flat16, scaled ? 1 : 0, cr_delta };
+        k.sc += scaled;
+        k.cr |= cr_delta != 0;
+        k.n_cr += cr_delta != 0;
     }
     *kinds = k;
     return 0;
@@ -925,17 +940,27 @@ static void launch_intra(p264hip_ctx *c, const PicDev *batch, const ScaleDev *sc
 
 // edge info (boundary strengths, averaged QPs per edge class: everything about an edge that does not depend on samples) where the
 // intra launch did not carry it, then the loop filter
-static void launch_deblock(p264hip_ctx *c, const PicDev *batch, const LaunchPlan &pl)
+static void launch_deblock(p264hip_ctx *c, const PicDev *batch, const ScaleDev *scale, const LaunchPlan &pl)
 {
     ScopedStamp t(c, 2);
     const Geom g = c->g;
     const dim3 grid = grid_of(pl.edge_shape), block(pl.edge_shape.threads);
+    const p264hip_launch_info_t &li = pl.info;
+    if (pl.deblock_cr) {                                     // (K4c: Cr's averaged QPs in the side array; such a batch is never fused)
+        switch (pl.edge) {
+        case EdgeInfoRoad::fused:         break;
+        case EdgeInfoRoad::bs_by_picture: hipLaunchKernelGGL(k_deblock_bs_cr<true>, grid, block, 0, c->stream, batch, g, c->d_edge, inv_mb_w(c), scale, c->d_edge_cr); break;
+        case EdgeInfoRoad::bs_by_index:   hipLaunchKernelGGL(k_deblock_bs_cr<false>, grid, block, 0, c->stream, batch, g, c->d_edge, inv_mb_w(c), scale, c->d_edge_cr); break;
+        }
+        hipLaunchKernelGGL(k_deblock_cr, grid_of(pl.deblock_shape), dim3(pl.deblock_shape.threads), 0, c->stream, batch, g,
+                           (const EdgeInfo *)c->d_edge, c->d_status, li.pictures, li.deblock_rb_log2, li.deblock_pics_per_wg, li.deblock_odd_single, (const uint32_t *)c->d_edge_cr);
+        return;
+    }
     switch (pl.edge) {
     case EdgeInfoRoad::fused:         break;
     case EdgeInfoRoad::bs_by_picture: hipLaunchKernelGGL(k_deblock_bs<true>, grid, block, 0, c->stream, batch, g, c->d_edge, inv_mb_w(c)); break;
     case EdgeInfoRoad::bs_by_index:   hipLaunchKernelGGL(k_deblock_bs<false>, grid, block, 0, c->stream, batch, g, c->d_edge, inv_mb_w(c)); break;
     }
-    const p264hip_launch_info_t &li = pl.info;
     hipLaunchKernelGGL(k_deblock, grid_of(pl.deblock_shape), dim3(pl.deblock_shape.threads), 0, c->stream, batch, g,
                        (const EdgeInfo *)c->d_edge, c->d_status, li.pictures, li.deblock_rb_log2, li.deblock_pics_per_wg, li.deblock_odd_single);
 }
@@ -951,6 +976,7 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     BatchKinds k;
     if ((rc = batch_fill(c, pic_ids, streams, n, c->h_batch[r], c->h_scale[r], &k))) return rc;
     const LaunchPlan plan = plan_launches(c->dev, c->knobs, k, n);
+    if (plan.deblock_cr && (rc = edge_cr_reserve(c))) return rc;
     c->last = plan.info;
     // from here on work that reads the batch's input slots is (about to be) queued: the slots carry the new epoch BEFORE the first
     // launch, so that whichever way this function returns - a launch error half-way included - a later p264hip_input_reserve
@@ -964,7 +990,7 @@ extern "C" int p264hip_reconstruct(p264hip_ctx *c, const int *pic_ids, const int
     launch_inter(c, c->d_batch[r], c->d_scale[r], plan);
     launch_residual(c, c->d_batch[r], c->d_scale[r], plan);
     launch_intra(c, c->d_batch[r], c->d_scale[r], plan);
-    launch_deblock(c, c->d_batch[r], plan);
+    launch_deblock(c, c->d_batch[r], c->d_scale[r], plan);
     HIPCHK(hipGetLastError());
     return P264HIP_OK;
 }

@@ -171,7 +171,7 @@ p264_t *p264_decoder_open(p264_param_t *param)
     h->device = d ? atoi(d) : 0;
     /* analyse.intra & 0x0002: the reference's own I8x8 bit (P264_ANALYSE_I8x8; p264_param_default sets it) - the caller takes Intra 8x8
      * macroblocks, which this decoder's own HIP layer reconstructs */
-    h->parser = p264parse_open(P264PARSE_OPT_SCALING | ((q && atoi(q)) ? P264PARSE_OPT_QUIET : 0) | ((param && (param->analyse.intra & 0x0002u)) ? P264PARSE_OPT_INTRA8X8 : 0));
+    h->parser = p264parse_open(P264PARSE_OPT_SCALING | P264PARSE_OPT_CR_OFFSET | ((q && atoi(q)) ? P264PARSE_OPT_QUIET : 0) | ((param && (param->analyse.intra & 0x0002u)) ? P264PARSE_OPT_INTRA8X8 : 0));
     if (!h->parser) { free(h); return NULL; }
     { const char *pp = getenv("P264AMD_PINNED_PARSE"); if (!pp || atoi(pp)) p264parse_set_allocator(h->parser, p264hip_host_alloc, p264hip_host_free); }      /* picture arrays in pinned memory */
     return h;

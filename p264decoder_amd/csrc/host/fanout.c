@@ -637,7 +637,7 @@ static int root_job_init(root_job_t *J, p264fan *f, int n_streams, const uint8_t
     for (int s = 0; s < n_streams && !rc; s++) {
         /* (Intra 8x8 macroblocks only for the library's own backend on every rank - a plug-in backend's owner has not said that it
          * knows the record, include/p264parse.h) */
-        P->st[s].parser = p264parse_open(P264PARSE_OPT_QUIET | (f->own_bk ? P264PARSE_OPT_INTRA8X8 | P264PARSE_OPT_SCALING : 0));
+        P->st[s].parser = p264parse_open(P264PARSE_OPT_QUIET | (f->own_bk ? P264PARSE_OPT_INTRA8X8 | P264PARSE_OPT_SCALING | P264PARSE_OPT_CR_OFFSET : 0));
         annexb_reader_set_input(&P->st[s], annexb[s], sizes[s]);
         if (!P->st[s].parser) rc = fail("p264parse_open failed");
     }

@@ -1559,6 +1559,8 @@ static void publish_picture(p264parse *p)
     d->mb_w = p->mb_w; d->mb_h = p->mb_h;
     d->slice_type = c->type;
     d->chroma_qp_offset = pps->chroma_qp_offset;
+    /* Cr's own offset as a delta on it, from the same PPS; the extension counts under a High SPS only (open_slice) */
+    if ((p->opts & P264PARSE_OPT_CR_OFFSET) && p->sps[pps->sps_id].high && pps->ext) d->cr_qp_offset_delta = pps->second_chroma_qp_offset - pps->chroma_qp_offset;
     d->deblock = (!pps->deblock_ctrl || c->deblock) ? 1 : 0;         /* per-macroblock `edges` gate the slices that switch it off */
     d->alpha_c0_offset = c->alpha; d->beta_offset = c->beta;
     d->dst_slot = p->cur_slot;
@@ -1652,9 +1654,12 @@ static int open_slice(p264parse *p, const slice_t *sh)
     if (p->sps[pps->sps_id].high && pps->ext) {
         if (pps->scaling_matrix && !pps->cqm_read) { ERR(p, "pic_scaling_matrix_present_flag unsupported (flat scaling lists only)"); return REFUSE_SLICE; }
         if (pps->ext_short) { ERR(p, "PPS %d: its extension ends inside the scaling matrix", sh->pps_id); return REFUSE_SLICE; }
-        if (pps->second_chroma_qp_offset != pps->chroma_qp_offset) {
+        if (pps->second_chroma_qp_offset != pps->chroma_qp_offset && !(p->opts & P264PARSE_OPT_CR_OFFSET)) {      /* (with the option: publish_picture hands the difference out) */
             ERR(p, "second_chroma_qp_index_offset %d differs from chroma_qp_index_offset %d: unsupported", pps->second_chroma_qp_offset, pps->chroma_qp_offset);
             return REFUSE_SLICE;
+        }
+        if (pps->second_chroma_qp_offset != pps->chroma_qp_offset && (pps->second_chroma_qp_offset < -12 || pps->second_chroma_qp_offset > 12)) {   /* (7.4.2.2) */
+            ERR(p, "second_chroma_qp_index_offset %d out of range (-12 .. 12)", pps->second_chroma_qp_offset); return REFUSE_SLICE;
         }
         p->t8x8_mode = pps->t8x8_mode;
         c->t8x8 |= pps->t8x8_mode;

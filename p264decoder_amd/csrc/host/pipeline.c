@@ -168,9 +168,9 @@ p264pipe *p264pipe_open(int device, int n_streams, int n_threads)
     const char *pin = getenv("P264AMD_PIPE_PINNED");
     const int pinned = pin ? atoi(pin) != 0 : device >= 0;
     for (int i = 0; i < n_streams; i++) {
-        /* (the pictures go to this library's HIP layer, which knows Intra 8x8 records and reads the scaling lists; device -1 runs
+        /* (the pictures go to this library's HIP layer, which knows Intra 8x8 records and reads the scaling lists and Cr's offset delta; device -1 runs
          * the same parsers, so that what it accepts, counts and times is what the device pipeline would be fed) */
-        p->st[i].rd.parser = p264parse_open(P264PARSE_OPT_QUIET | P264PARSE_OPT_INTRA8X8 | P264PARSE_OPT_SCALING);
+        p->st[i].rd.parser = p264parse_open(P264PARSE_OPT_QUIET | P264PARSE_OPT_INTRA8X8 | P264PARSE_OPT_SCALING | P264PARSE_OPT_CR_OFFSET);
         if (!p->st[i].rd.parser) { p264pipe_close(p); return NULL; }
         if (pinned) p264parse_set_allocator(p->st[i].rd.parser, p264hip_host_alloc, p264hip_host_free);
         p->st[i].last_slot = -1;

@@ -70,13 +70,16 @@ class ParsedPicture:
 class Parser:
     """p264parse_* : NAL units in, complete parsed pictures out (CPU, serial by nature)."""
 
-    def __init__(self, quiet=True, strict=False, lib=None, intra8x8=False, scaling=False):
+    def __init__(self, quiet=True, strict=False, lib=None, intra8x8=False, scaling=False, cr_offset=False):
         """intra8x8: hand out Intra 8x8 macroblocks as I4x4 records with MB_I8X8 (P264PARSE_OPT_INTRA8X8) - for pictures that go to
         a backend that knows the record, as HipReconstructor does; off, such a macroblock ends its slice with an error.
         scaling: read the scaling matrices of High-profile parameter sets and hand out each picture's eight lists in its descriptor
-        (P264PARSE_OPT_SCALING) - for a backend that reads the table, as HipReconstructor does; off, such a set is refused"""
+        (P264PARSE_OPT_SCALING) - for a backend that reads the table, as HipReconstructor does; off, such a set is refused.
+        cr_offset: accept a High-profile PPS whose second_chroma_qp_index_offset differs from chroma_qp_index_offset and hand out the
+        difference as the descriptor's cr_qp_offset_delta (P264PARSE_OPT_CR_OFFSET) - for a backend that reads the delta, as
+        HipReconstructor does; off, the slices of such a PPS are refused"""
         self.lib = lib or N.load()
-        self.h = self.lib.p264parse_open((1 if quiet else 0) | (2 if strict else 0) | (4 if intra8x8 else 0) | (8 if scaling else 0))
+        self.h = self.lib.p264parse_open((1 if quiet else 0) | (2 if strict else 0) | (4 if intra8x8 else 0) | (8 if scaling else 0) | (16 if cr_offset else 0))
         if not self.h:
             raise P264Error("p264parse_open failed")
 
@@ -299,10 +302,10 @@ class HipReconstructor:
 
     def last_launch(self):
         """The launch shapes of the last reconstruct call (p264hip_launch_info_t as a dict; what depends on the batch's CONTENT
-        rather than its size has its own accessor: last_t8x8_wgs, last_intra_i8, last_scaled_pictures)."""
+        rather than its size has its own accessor: last_t8x8_wgs, last_intra_i8, last_scaled_pictures, last_cr_pictures)."""
         li = N.LaunchInfo()
         self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
-        return {n: int(getattr(li, n)) for n, _ in N.LaunchInfo._fields_ if n not in ("reserved", "t8x8_wgs", "intra_i8", "scaled_pictures")}
+        return {n: int(getattr(li, n)) for n, _ in N.LaunchInfo._fields_ if n not in ("reserved", "t8x8_wgs", "intra_i8", "scaled_pictures", "cr_pictures")}
 
     def last_t8x8_wgs(self):
         """Workgroups of k_t8x8 in the last reconstruct call: 0 unless a picture of the batch had transform_8x8."""
@@ -318,11 +321,18 @@ class HipReconstructor:
         return int(li.intra_i8)
 
     def last_scaled_pictures(self):
-        """Pictures with scaling_lists in the last reconstruct call; not 0: the batch ran the instances that read the scaling
+        """Pictures with scaling_lists or a non-zero cr_qp_offset_delta in the last reconstruct call; not 0: the batch ran the instances that read the scaling
         table (k_mc_sort_scaled / k_mc_sort_scaled_p, k_scaled_inter, k_intra_scaled / k_intra_sparse_scaled), 0: what a flat batch always ran."""
         li = N.LaunchInfo()
         self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
         return int(li.scaled_pictures)
+
+    def last_cr_pictures(self):
+        """Pictures with a non-zero cr_qp_offset_delta in the last reconstruct call; not 0: the loop filter ran its Cr instances
+        (k_deblock_bs_cr, k_deblock_cr), 0: what such a batch always ran."""
+        li = N.LaunchInfo()
+        self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
+        return int(li.cr_pictures)
 
 
 def device_count(lib=None):

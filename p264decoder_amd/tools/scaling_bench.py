@@ -6,7 +6,9 @@ k_intra_sparse_scaled), at 256 and at 2048 pictures per launch in one context, i
 launches are timed; the stage times are the context's HIP events (inter = sort + motion compensation + k_scaled_inter).  This is NOT
 bench.py's metric and has no pass mark: it is the pair DESIGN.md quotes for the extra pass.  Nothing checks the pictures here (the
 tests do).  --t8x8 PCT gives that share of the inter macroblocks the 8x8 transform: the flat batch then launches k_t8x8, and
-k_scaled_inter walks 8x8 blocks too; the default 0 is the stream of the committed figures.
+k_scaled_inter walks 8x8 blocks too; the default 0 is the stream of the committed figures.  A third variant, cr_offset: the flat stream
+with --cqo2 different from --cqo (every picture has a cr_qp_offset_delta: the scaled road with the all-16 table, and the Cr instances
+of the loop filter, k_deblock_bs_cr and k_deblock_cr) - what such a picture costs, against the flat and the scaled variant of the same run.
 
   python -m p264decoder_amd.tools.scaling_bench [--streams 256 2048] [--pictures 5] [--runs 3] [--t8x8 0] [--out profiles/scaling_bench.json]
 """
@@ -25,7 +27,7 @@ if ROOT not in sys.path:
 
 MB_W, MB_H = 120, 68
 OPTIONS = "--mbw %d --mbh %d --gop 0 --seed 33 --coded 12 --maxlevel 12 --crop-bottom 4 --t8x8 %%d" % (MB_W, MB_H)     # (--t8x8 PCT: main)
-CASES = (("flat", ""), ("cqm_jvt", "--cqm jvt --cqm-where sps"))
+CASES = (("flat", ""), ("cqm_jvt", "--cqm jvt --cqm-where sps"), ("cr_offset", "--cqo 2 --cqo2 -3"))
 
 
 def one_run(hip, S, T):
@@ -65,8 +67,9 @@ def main():
         for name, extra in CASES:
             path = os.path.join(td, name + ".264")
             subprocess.run([tool, path] + options.split() + ["--frames", str(T)] + extra.split(), check=True)
-            parsed[name] = Parser(quiet=True, intra8x8=True, scaling=True).parse_stream(open(path, "rb").read())
-            assert len(parsed[name]) == T and all(bool(p.desc.scaling_lists) == bool(extra) for p in parsed[name])
+            parsed[name] = Parser(quiet=True, intra8x8=True, scaling=True, cr_offset=True).parse_stream(open(path, "rb").read())
+            assert len(parsed[name]) == T and all(bool(p.desc.scaling_lists) == ("--cqm" in extra) for p in parsed[name])
+            assert all(bool(p.desc.cr_qp_offset_delta) == ("--cqo2" in extra) for p in parsed[name])
         for S in args.streams:
             out = res["batches"][str(S)] = {}
             for name, _ in CASES:
@@ -83,9 +86,11 @@ def main():
                 fps = [r[0] for r in runs]
                 out[name] = {"frames_per_s": [round(f, 1) for f in fps], "median": round(statistics.median(fps), 1),
                              "stage_ms_per_launch": runs[[round(f, 1) for f in fps].index(round(statistics.median(fps), 1))][1],
-                             "scaled_pictures_per_launch": hip.last_scaled_pictures(), "coded_blocks_per_picture": int(pics[-1].desc.n_coef_blocks)}
+                             "scaled_pictures_per_launch": hip.last_scaled_pictures(), "cr_pictures_per_launch": hip.last_cr_pictures(), "coded_blocks_per_picture": int(pics[-1].desc.n_coef_blocks)}
                 hip.close()
             out["cqm_relative_to_flat"] = round(out["cqm_jvt"]["median"] / out["flat"]["median"], 3)
+            out["cr_offset_relative_to_flat"] = round(out["cr_offset"]["median"] / out["flat"]["median"], 3)
+            out["cr_offset_relative_to_cqm"] = round(out["cr_offset"]["median"] / out["cqm_jvt"]["median"], 3)
     line = json.dumps(res)
     if args.out:
         with open(args.out, "w") as f:

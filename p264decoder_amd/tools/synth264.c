@@ -13,6 +13,8 @@
  *
  *   synth264 out.264 --mbw 120 --mbh 68 --frames 60 --gop 30 --seed 3 [--intra-only]
  *            [--qp 26] [--coded 12] [--maxlevel 32] [--mvmax 64] [--cqo 0] [--nodeblock]
+ *            [--cqo2 N]      second_chroma_qp_index_offset (Cr's own offset) in the PPS extension; default: --cqo's value.  Only with
+ *                            --t8x8 (>= 0), which is what makes the writer emit the extension (High profile)
  *            [--refs 2]      two reference frames, reference index per partition (outside the reference's safe subset, A-Q5)
  *            [--slices N]    N slices per picture (equal runs of macroblocks; the reference handles one, decoder/decoder.c:516-523)
  *            [--dump-mv f]   per picture: the intended vectors int16[mb][16][2] and reference indices int8[mb][16]
@@ -151,6 +153,7 @@ static void write_nal(FILE *f, int ref_idc, int type, const bw_t *b)
 enum { T_I4 = 0, T_I16 = 1, T_PCM = 2, T_P = 3, T_P8 = 4, T_SKIP = 5 };
 static int W, H, NMB;                       /* in macroblocks */
 static int opt_qp = 26, opt_coded = 12, opt_maxlevel = 32, opt_mvmax = 64, opt_cqo = 0, opt_deblock = 1, opt_refs = 1;
+static int opt_cqo2 = 0, have_cqo2 = 0;          /* --cqo2 N: second_chroma_qp_index_offset where the PPS has its extension (--t8x8); default: opt_cqo */
 static int n_active = 1;                    /* num_ref_idx_l0_active of the current slice */
 static int8_t *refs;                        /* [mb][16] reference index per 4x4 block (-1 intra) */
 static FILE *dump_mv;                       /* --dump-mv: intended vectors and reference indices, for checking a parser */
@@ -1166,6 +1169,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--maxlevel")) { opt_maxlevel = v; i++; }
         else if (!strcmp(a, "--mvmax")) { opt_mvmax = v; i++; }
         else if (!strcmp(a, "--cqo")) { opt_cqo = v; i++; }
+        else if (!strcmp(a, "--cqo2")) { opt_cqo2 = v; have_cqo2 = 1; i++; }
         else if (!strcmp(a, "--crop-bottom")) { crop_bottom = v; i++; }
         else if (!strcmp(a, "--crop")) {                /* left right top bottom, in cropping units (two luma samples) */
             for (int k = 0; k < 4; k++) crop[k] = i + 1 + k < argc ? atoi(argv[i + 1 + k]) : 0;
@@ -1272,7 +1276,7 @@ int main(int argc, char **argv)
             const int m = opt_cqm && opt_cqm_where != 0;
             bw_put(&b, 1, 1); bw_put(&b, 1, (uint32_t)m);
             if (m) for (int n = 0; n < 8; n++) put_cqm_list(&b, n < 6 ? 16 : 64, &cqm_pps[n]);
-            bw_se(&b, opt_cqo);
+            bw_se(&b, have_cqo2 ? opt_cqo2 : opt_cqo);
         }
         bw_trailing(&b);
         write_nal(f, 3, 8, &b); free(b.buf);
