@@ -387,6 +387,61 @@ int     p264hip_export_check(const p264hip_export_t *e, int mb_w, int mb_h);
 int     p264hip_export_frames(p264hip_ctx *ctx, const int *streams, const int *slots, int n,
                               const p264hip_export_t *e, void *dst_dev, size_t dst_bytes);
 
+/* ---- the same road with a RESIZE on it: a source window of each picture resized to width x height, written in one of the four
+ * layouts above as uint8, or - the two RGB formats - as float16 / float32 after a per-channel scale and bias.  "The existing export
+ * of a virtual width x height picture": with width x height equal to the window it writes the bytes p264hip_export_frames writes.
+ *
+ * Taps.  Each plane is resized on its own: luma from the window's cw x ch samples to W x H, U and V from cw/2 x ch/2 to W/2 x H/2.
+ * Sample centres sit at half positions (the geometry of align_corners = False), positions are in 1/256 of a sample.  For the
+ * destination index d of an axis with S source and D destination samples
+ *   pos(d) = clamp( floor(((2d+1)*S*256 + D) / (2D)) - 128,  0,  (S-1)*256 )
+ *   i0 = pos >> 8,  f = pos & 255,  i1 = min(i0+1, S-1)
+ * with indices relative to the window: taps clamp at the WINDOW's edges, a sample outside it is never read (p264hip_resize_taps
+ * gives pos[]).  With a, b the samples (i0, i1) of source row j0 and c, d those of row j1, fx and fy the two fractions:
+ *   v = (a*(256-fx)*(256-fy) + b*fx*(256-fy) + c*(256-fx)*fy + d*fx*fy + 32768) >> 16
+ * Every sum stays below 2^24.  D == S returns the source, D == S/2 is exactly (a+b+c+d+2) >> 2, and the result is within 1 of
+ * floor(real bilinear + 1/2) (each axis' position is off by at most 1/512: at most 255/512 per axis, and two roundings of 1/2).
+ * The filter is bilinear ONLY: there is no antialiasing prefilter, a large reduction aliases exactly as
+ * torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=False) does.  `filter` is there so that a box or
+ * antialiased filter can be added without another struct.
+ *
+ * Layouts.  The resized planes are treated as p264hip_export_t treats a frame: I420 / NV12 store them; RGB24 / RGBP take the chroma
+ * sample (x >> 1, y >> 1) of the RESIZED chroma planes and the formula, coefficients and clip above.  The layout table above holds
+ * with W x H the output size and every byte count times the element size (1, 2 or 4): tight P = W*elem (RGB24: 3*W*elem).
+ *
+ * Float elements (RGB24 and RGBP only).  For channel k in the order R, G, B and the 8-bit value c
+ *   e = fl32( fl32((float)c * scale[k]) + bias[k] )
+ * two separately rounded IEEE single operations, never contracted into one; float16 is e converted round-to-nearest-even with
+ * subnormals kept (numpy's astype(float16)).  tests/resize_checker.py is all of this in numpy. */
+enum { P264HIP_DTYPE_U8 = 0, P264HIP_DTYPE_F16 = 1, P264HIP_DTYPE_F32 = 2 };
+enum { P264HIP_FILTER_BILINEAR = 0 };
+typedef struct p264hip_resize {
+    int32_t format, matrix, full_range;                     /* as in p264hip_export_t */
+    int32_t crop_left, crop_top, crop_width, crop_height;   /* source window, luma samples, all even, inside the frame */
+    int32_t width, height;                                  /* output, both even, 2 .. 16384 */
+    int32_t dtype, filter;
+    int32_t pitch;                                          /* bytes per row of plane 0; 0 = tight = W*elem (RGB24: 3*W*elem) */
+    int64_t frame_stride;                                   /* bytes; 0 = tight */
+    float   scale[3], bias[3];                              /* R, G, B; float dtypes only, all 0 otherwise */
+} p264hip_resize_t;
+/* bytes of one picture (host only, no device); < 0 = P264HIP_EINVAL for what p264hip_export_frame_bytes refuses in the fields the two
+ * share, an output size that is odd, below 2 or above 16384, an unknown dtype or filter, a float dtype on a YUV format, a scale or
+ * bias that is not finite - or not 0 where the dtype is U8 -, a pitch below the tight one or no multiple of the element size (I420: of
+ * twice the element size, as its chroma pitch is pitch/2) */
+int64_t p264hip_resize_frame_bytes(const p264hip_resize_t *r);
+/* 0, or P264HIP_EINVAL for the above, a window that leaves the frame of mb_w x mb_h macroblocks and a frame_stride (other than 0)
+ * below the picture's bytes or no multiple of the element size (host only) */
+int     p264hip_resize_check(const p264hip_resize_t *r, int mb_w, int mb_h);
+/* pos[d] above for d = 0 .. dst_n - 1 (host only); P264HIP_EINVAL for a null pos or a count outside 1 .. 2^20 */
+int     p264hip_resize_taps(int src_n, int dst_n, int32_t *pos);
+/* the contract of p264hip_export_frames: picture i = frame slots[i] of stream streams[i], resized, at dst_dev + i*frame_stride;
+ * asynchronous on the context's stream behind every reconstruct queued before it, complete after p264hip_sync or a marker; entries
+ * may repeat; more than 65535 pictures go out as several launches.  P264HIP_EINVAL, before anything is queued, for a null argument,
+ * n < 1, a stream or slot out of range, whatever p264hip_resize_check refuses, a dst_dev that is no multiple of the element size and
+ * dst_bytes < (n-1)*frame_stride + the picture's bytes.  The kernel writes the bytes of the layout and no others. */
+int     p264hip_export_resized(p264hip_ctx *ctx, const int *streams, const int *slots, int n,
+                               const p264hip_resize_t *r, void *dst_dev, size_t dst_bytes);
+
 /* plain synchronous copies between host and device memory (the fan-out's TCP transport uses them where it stands in for a
  * device-to-device transport in tests) */
 int  p264hip_copy_to_device(void *dev, const void *host, size_t bytes);

@@ -64,6 +64,11 @@ int  p264pipe_export_last(p264pipe *p, const p264hip_export_t *e, void *dst_dev,
  * The description and the pointers are copied; the buffers are borrowed until the sink is replaced or the pipeline closed. */
 typedef void (*p264pipe_sink_fn)(void *user, int round, int n, const int *streams, void *dev);
 int  p264pipe_set_sink(p264pipe *p, const p264hip_export_t *e, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user);
+/* The same two exits with a resize on them (p264hip_resize_t, include/p264hip.h: a window of each picture resized, as bytes or -
+ * RGB formats - normalised floats; p264hip_export_resized).  A pipeline has ONE sink: setting either kind replaces the other, and
+ * fn = NULL to either call takes it away.  p264pipe_export_last and p264pipe_set_sink behave as before. */
+int  p264pipe_export_last_resized(p264pipe *p, const p264hip_resize_t *r, void *dst_dev, size_t bytes);
+int  p264pipe_set_sink_resized(p264pipe *p, const p264hip_resize_t *r, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user);
 void p264pipe_close(p264pipe *p);
 
 #ifdef __cplusplus

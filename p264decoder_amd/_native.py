@@ -123,6 +123,42 @@ def export_desc(fmt="i420", crop=None, frame=None, matrix="bt601", full_range=Fa
     return e
 
 
+class Resize(C.Structure):
+    """p264hip_resize_t"""
+    _fields_ = [("format", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32),
+                ("crop_left", C.c_int32), ("crop_top", C.c_int32), ("crop_width", C.c_int32), ("crop_height", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("dtype", C.c_int32), ("filter", C.c_int32),
+                ("pitch", C.c_int32), ("frame_stride", C.c_int64), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+DTYPE_U8, DTYPE_F16, DTYPE_F32 = range(3)
+FILTER_BILINEAR = 0
+DTYPES = {"u8": DTYPE_U8, "f16": DTYPE_F16, "f32": DTYPE_F32}
+ELEM_BYTES = {DTYPE_U8: 1, DTYPE_F16: 2, DTYPE_F32: 4}
+
+
+def resize_desc(fmt="rgbp", size=None, crop=None, frame=None, dtype="u8", scale=None, bias=None, matrix="bt601", full_range=False, pitch=0,
+                frame_stride=0, filter=FILTER_BILINEAR):
+    """A p264hip_resize_t: fmt / dtype / matrix by name (or number), size = (width, height) of the output (None: the window's), crop =
+    (left, top, width, height) of the source window or None for the whole `frame` = (width, height), scale / bias = one number for
+    all channels or three (R, G, B; None: 0).  Names that do not exist raise; everything else is the library's to check."""
+    r = Resize()
+    r.format = FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+    r.matrix = MATRICES[matrix] if isinstance(matrix, str) else int(matrix)
+    r.full_range = int(full_range)
+    r.crop_left, r.crop_top, r.crop_width, r.crop_height = crop if crop is not None else (0, 0, frame[0], frame[1])
+    r.width, r.height = size if size is not None else (r.crop_width, r.crop_height)
+    r.dtype = DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+    r.filter = int(filter)
+    r.pitch, r.frame_stride = int(pitch), int(frame_stride)
+    for name, v in (("scale", scale), ("bias", bias)):
+        v = (0.0, 0.0, 0.0) if v is None else tuple(v) if hasattr(v, "__len__") else (v, v, v)
+        if len(v) != 3:
+            raise ValueError("%s: one number or three" % name)
+        setattr(r, name, (C.c_float * 3)(*v))
+    return r
+
+
 def import_torch():
     """torch, for the calls that hand frames to it (HipReconstructor.export_frames, Pipeline.export_last / set_sink).  A process must
     hold ONE HIP runtime: a torch wheel brings its own libamdhip64.so, which libp264amd.so shares when torch was imported before
@@ -242,6 +278,15 @@ def load(path=None):
         lib.p264hip_export_check.argtypes = [C.POINTER(Export), C.c_int, C.c_int]
         lib.p264hip_export_frames.restype = C.c_int
         lib.p264hip_export_frames.argtypes = [C.c_void_p, ip, ip, C.c_int, C.POINTER(Export), C.c_void_p, C.c_size_t]
+    if hasattr(lib, "p264hip_export_resized"):
+        lib.p264hip_resize_frame_bytes.restype = C.c_int64
+        lib.p264hip_resize_frame_bytes.argtypes = [C.POINTER(Resize)]
+        lib.p264hip_resize_check.restype = C.c_int
+        lib.p264hip_resize_check.argtypes = [C.POINTER(Resize), C.c_int, C.c_int]
+        lib.p264hip_resize_taps.restype = C.c_int
+        lib.p264hip_resize_taps.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        lib.p264hip_export_resized.restype = C.c_int
+        lib.p264hip_export_resized.argtypes = [C.c_void_p, ip, ip, C.c_int, C.POINTER(Resize), C.c_void_p, C.c_size_t]
     # ---- p264pipe.h
     if hasattr(lib, "p264pipe_open"):
         lib.p264pipe_open.restype = C.c_void_p
@@ -264,6 +309,11 @@ def load(path=None):
         lib.p264pipe_export_last.argtypes = [C.c_void_p, C.POINTER(Export), C.c_void_p, C.c_size_t]
         lib.p264pipe_set_sink.restype = C.c_int
         lib.p264pipe_set_sink.argtypes = [C.c_void_p, C.POINTER(Export), C.POINTER(C.c_void_p), C.c_int, C.c_size_t, SINK_FN, C.c_void_p]
+    if hasattr(lib, "p264pipe_set_sink_resized"):
+        lib.p264pipe_export_last_resized.restype = C.c_int
+        lib.p264pipe_export_last_resized.argtypes = [C.c_void_p, C.POINTER(Resize), C.c_void_p, C.c_size_t]
+        lib.p264pipe_set_sink_resized.restype = C.c_int
+        lib.p264pipe_set_sink_resized.argtypes = [C.c_void_p, C.POINTER(Resize), C.POINTER(C.c_void_p), C.c_int, C.c_size_t, SINK_FN, C.c_void_p]
     if path is None:
         _lib = lib
     return lib

@@ -24,6 +24,7 @@
 #include "kernel_scaling.h"
 #include "kernel_expand.h"
 #include "kernel_export.h"
+#include "kernel_resize.h"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -549,7 +550,7 @@ extern "C" int p264hip_frame_planar_device(p264hip_ctx *c, int stream, int slot,
 // ---- frames handed on on the device (include/p264hip.h: p264hip_export_t; kernel_export.h) ----
 extern "C" const char *p264hip_export_why_(const p264hip_export_t *e, int mb_w, int mb_h);     // csrc/host/export_layout.c
 
-// room for the table of a call with n pictures in every buffer of the ring
+// room for the table of a call with n pictures (a resized export: n words, its tap tables among them) in every buffer of the ring
 static int export_reserve(p264hip_ctx *c, int n)
 {
     if (n <= c->exp_cap) return 0;
@@ -617,6 +618,87 @@ extern "C" int p264hip_export_frames(p264hip_ctx *c, const int *streams, const i
         case P264HIP_FMT_NV12:  hipLaunchKernelGGL(k_export_nv12, grid, dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p); break;
         case P264HIP_FMT_RGB24: hipLaunchKernelGGL(k_export_rgb24, grid, dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p); break;
         default:                hipLaunchKernelGGL(k_export_rgbp, grid, dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p); break;
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return P264HIP_OK;
+}
+
+// ---- the same with a resize (include/p264hip.h: p264hip_resize_t; kernel_resize.h) ----
+extern "C" const char *p264hip_resize_why_(const p264hip_resize_t *r, int mb_w, int mb_h);     // csrc/host/resize_layout.c
+
+// one tap table (kernel_resize.h): fraction | (i1 - i0) << 8 | i0 << 16 per destination index, i0 a coordinate of the frame; the
+// entries behind dst_n up to the next multiple of 4 repeat the last one.  The positions are computed into the table itself and turned
+// into its words in place.  (The counts have passed p264hip_resize_check: 1 .. 16384 destination samples of 1 .. 65535 source samples,
+// which p264hip_resize_taps cannot refuse.)
+static void resize_table(uint32_t *t, int first, int src_n, int dst_n)
+{
+    (void)p264hip_resize_taps(src_n, dst_n, (int32_t *)t);
+    const int padded = (dst_n + 3) & ~3;
+    const uint32_t last = t[dst_n - 1];
+    for (int d = 0; d < padded; d++) {
+        const uint32_t p = d < dst_n ? t[d] : last, i0 = p >> 8;
+        t[d] = (p & 255u) | ((int)i0 < src_n - 1 ? 1u << 8 : 0u) | ((uint32_t)first + i0) << 16;
+    }
+}
+
+#define RESIZE_LAUNCH(name) hipLaunchKernelGGL(name, grid, dim3(RESIZE_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p)
+
+extern "C" int p264hip_export_resized(p264hip_ctx *c, const int *streams, const int *slots, int n, const p264hip_resize_t *e, void *dst, size_t dst_bytes)
+{
+    if (!c || !streams || !slots || !e || !dst || n < 1) return fail(P264HIP_EINVAL, "p264hip_export_resized: bad argument (n %d)", n);
+    if (const char *why = p264hip_resize_why_(e, c->g.mb_w, c->g.mb_h))
+        return fail(P264HIP_EINVAL, "p264hip_export_resized: %s (format %d dtype %d filter %d matrix %d full_range %d, window %d,%d %dx%d in a %dx%d frame to %dx%d, pitch %d, frame_stride %lld)", why,
+                    e->format, e->dtype, e->filter, e->matrix, e->full_range, e->crop_left, e->crop_top, e->crop_width, e->crop_height, c->g.w, c->g.h, e->width, e->height, e->pitch, (long long)e->frame_stride);
+    if (c->g.w > 65535 || c->g.h > 65535) return fail(P264HIP_EINVAL, "p264hip_export_resized: a frame of %dx%d samples (a tap holds a coordinate in 16 bits)", c->g.w, c->g.h);
+    for (int i = 0; i < n; i++)
+        if (streams[i] < 0 || streams[i] >= c->n_streams || slots[i] < 0 || slots[i] >= c->slots)
+            return fail(P264HIP_EINVAL, "p264hip_export_resized: picture %d names stream %d slot %d (have %d x %d)", i, streams[i], slots[i], c->n_streams, c->slots);
+    const int elem = e->dtype == P264HIP_DTYPE_U8 ? 1 : e->dtype == P264HIP_DTYPE_F16 ? 2 : 4;
+    if ((uintptr_t)dst % (uintptr_t)elem) return fail(P264HIP_EINVAL, "p264hip_export_resized: dst is no multiple of the element size %d", elem);
+    const int64_t bytes = p264hip_resize_frame_bytes(e), stride = e->frame_stride ? e->frame_stride : bytes;
+    const int64_t pitch = e->pitch ? e->pitch : (e->format == P264HIP_FMT_RGB24 ? 3 * (int64_t)e->width : (int64_t)e->width) * elem;
+    if (n > 1 && stride > (INT64_MAX - bytes) / (n - 1)) return fail(P264HIP_EINVAL, "p264hip_export_resized: %d pictures %lld bytes apart", n, (long long)stride);
+    const uint64_t need = (uint64_t)(n - 1) * (uint64_t)stride + (uint64_t)bytes;
+    if ((uint64_t)dst_bytes < need) return fail(P264HIP_EINVAL, "p264hip_export_resized: %d pictures need %llu bytes, dst has %zu", n, (unsigned long long)need, dst_bytes);
+    HIPCHK(hipSetDevice(c->device));
+    // the call's table: the frame indices, then the four tap tables, each from a multiple of 4 words
+    const bool rgb = e->format == P264HIP_FMT_RGB24 || e->format == P264HIP_FMT_RGBP;
+    const int W = e->width, H = e->height, cw = W / 2, ch = H / 2;
+    ResizeParams p = {};
+    p.w = W; p.h = H;
+    p.t_xl = (n + 3) & ~3; p.t_yl = p.t_xl + ((W + 3) & ~3); p.t_xc = p.t_yl + ((H + 3) & ~3); p.t_yc = p.t_xc + ((cw + 3) & ~3);
+    const int words = p.t_yc + ((ch + 3) & ~3);
+    int rc = export_reserve(c, words);
+    if (rc) return rc;
+    const int r = c->exp_ring; c->exp_ring = (c->exp_ring + 1) % BATCH_RING;
+    HIPCHK(hipEventSynchronize(c->exp_free[r]));              // the copy that last used this staging buffer is done
+    uint32_t *t = c->h_exp[r];
+    for (int i = 0; i < n; i++) t[i] = (uint32_t)(streams[i] * c->slots + slots[i]);
+    for (int i = n; i < p.t_xl; i++) t[i] = 0;
+    resize_table(t + p.t_xl, e->crop_left, e->crop_width, W); resize_table(t + p.t_yl, e->crop_top, e->crop_height, H);
+    resize_table(t + p.t_xc, e->crop_left / 2, e->crop_width / 2, cw); resize_table(t + p.t_yc, e->crop_top / 2, e->crop_height / 2, ch);
+    HIPCHK(hipMemcpyAsync(c->d_exp[r], t, (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->exp_free[r], c->stream));
+    p.ltx = (W + RESIZE_TILE_W - 1) / RESIZE_TILE_W; p.n_ltiles = p.ltx * (H / 2);
+    p.ctx = (cw + RESIZE_TILE_W - 1) / RESIZE_TILE_W; p.n_tiles = p.n_ltiles + (rgb ? 0 : p.ctx * ch);
+    p.inv_ltx = 0xffffffffu / (uint32_t)p.ltx; p.inv_ctx = 0xffffffffu / (uint32_t)p.ctx;
+    p.pitch = pitch; p.frame_stride = stride;
+    const int32_t *k = export_coefs[e->matrix][e->full_range];
+    p.cy = k[0]; p.yo = e->full_range ? 0 : 16; p.r_cv = k[1]; p.g_cu = k[2]; p.g_cv = k[3]; p.b_cu = k[4];
+    for (int i = 0; i < 3; i++) { p.scale[i] = e->scale[i]; p.bias[i] = e->bias[i]; }
+    const unsigned gx = (unsigned)((p.n_tiles + RESIZE_THREADS / WAVE - 1) / (RESIZE_THREADS / WAVE));
+    for (int base = 0; base < n; base += 65535) {            // (a grid's second dimension ends at 65535)
+        const dim3 grid(gx, (unsigned)(n - base < 65535 ? n - base : 65535));
+        switch (e->format * 3 + e->dtype) {
+        case P264HIP_FMT_I420 * 3:                       RESIZE_LAUNCH(k_resize_i420); break;
+        case P264HIP_FMT_NV12 * 3:                       RESIZE_LAUNCH(k_resize_nv12); break;
+        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_U8:   RESIZE_LAUNCH(k_resize_rgb24_u8); break;
+        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F16:  RESIZE_LAUNCH(k_resize_rgb24_f16); break;
+        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F32:  RESIZE_LAUNCH(k_resize_rgb24_f32); break;
+        case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_U8:    RESIZE_LAUNCH(k_resize_rgbp_u8); break;
+        case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_F16:   RESIZE_LAUNCH(k_resize_rgbp_f16); break;
+        default:                                         RESIZE_LAUNCH(k_resize_rgbp_f32); break;
         }
     }
     HIPCHK(hipGetLastError());

@@ -22,6 +22,7 @@
 #include "p264_dropin.h"
 #include "host_cpu.h"
 #include "annexb_reader.h"
+#include "pipeline_sink.h"
 
 typedef struct {
     annexb_reader_t rd;
@@ -48,8 +49,9 @@ struct p264pipe {
     int failed_in_round[2];              /* a task of the round failed (under mu) */
     const p264hip_picture_t **round_pic[2];  /* [round parity][stream]: the picture a round's task produced, or NULL */
     double parse_seconds;
-    /* the sink (p264pipe_set_sink): every round's pictures exported into the caller's device buffers */
-    p264hip_export_t sink_e; void **sink_bufs; int sink_n_bufs; size_t sink_bytes; p264pipe_sink_fn sink_fn; void *sink_user;
+    /* the sink (p264pipe_set_sink; pipeline_sink.h): every round's pictures exported into the caller's device buffers by sink_export
+     * with the description sink_desc (a copy) */
+    p264pipe_export_fn sink_export; void *sink_desc; void **sink_bufs; int sink_n_bufs; size_t sink_bytes; p264pipe_sink_fn sink_fn; void *sink_user;
 };
 
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
@@ -223,7 +225,7 @@ static int submit_round(p264pipe *p, int r, int n, p264pipe_stats_t *S)
     }
     if (!rc && p264hip_reconstruct(p->ctx, p->ids, p->sts, n)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
     void *sink = p->sink_fn ? p->sink_bufs[r % p->sink_n_bufs] : NULL;       /* the round's pictures, behind its kernels */
-    if (!rc && sink && p264hip_export_frames(p->ctx, p->sts, p->dsts, n, &p->sink_e, sink, p->sink_bytes)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
+    if (!rc && sink && p->sink_export(p->ctx, p->sts, p->dsts, n, p->sink_desc, sink, p->sink_bytes)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
     int marker = -1;
     if (!rc) { marker = p264hip_marker(p->ctx); if (marker < 0) rc = -1; }
     S->submit_seconds += now_s() - s0;
@@ -283,9 +285,20 @@ int p264pipe_crop(p264pipe *p, int *left, int *top, int *width, int *height)
     return p ? p264parse_crop(p->st[0].rd.parser, left, top, width, height) : -1;
 }
 
-int p264pipe_export_last(p264pipe *p, const p264hip_export_t *e, void *dst_dev, size_t bytes)
+/* the export kind of this file: p264hip_export_t through p264hip_export_frames */
+static int export_plain(p264hip_ctx *ctx, const int *streams, const int *slots, int n, const void *desc, void *dst_dev, size_t bytes)
 {
-    if (!p || !p->ctx || !e || !dst_dev) return -1;
+    return p264hip_export_frames(ctx, streams, slots, n, (const p264hip_export_t *)desc, dst_dev, bytes);
+}
+
+void p264pipe_geometry_(const p264pipe *p, int *device, int *mb_w, int *mb_h)
+{
+    *device = p->device; *mb_w = p->mb_w; *mb_h = p->mb_h;
+}
+
+int p264pipe_export_last_with_(p264pipe *p, const char *who, p264pipe_export_fn ex, const void *desc, void *dst_dev, size_t bytes)
+{
+    if (!p || !p->ctx || !desc || !dst_dev) return -1;
     int *sts = (int *)malloc(sizeof(int) * 2 * (size_t)p->n_streams);
     if (!sts) return -1;
     int rc = 0;
@@ -293,34 +306,55 @@ int p264pipe_export_last(p264pipe *p, const p264hip_export_t *e, void *dst_dev, 
         if (p->st[i].last_slot < 0) rc = -1;
         sts[i] = i; sts[p->n_streams + i] = p->st[i].last_slot;
     }
-    if (!rc && (p264hip_export_frames(p->ctx, sts, sts + p->n_streams, p->n_streams, e, dst_dev, bytes) || p264hip_sync(p->ctx))) {
-        fprintf(stderr, "p264pipe_export_last: %s\n", p264hip_last_error()); rc = -1;
+    if (!rc && (ex(p->ctx, sts, sts + p->n_streams, p->n_streams, desc, dst_dev, bytes) || p264hip_sync(p->ctx))) {
+        fprintf(stderr, "%s: %s\n", who, p264hip_last_error()); rc = -1;
     }
     free(sts);
     return rc;
 }
 
+int p264pipe_export_last(p264pipe *p, const p264hip_export_t *e, void *dst_dev, size_t bytes)
+{
+    return p264pipe_export_last_with_(p, "p264pipe_export_last", export_plain, e, dst_dev, bytes);
+}
+
+void p264pipe_sink_remove_(p264pipe *p)
+{
+    free(p->sink_bufs); free(p->sink_desc);
+    p->sink_bufs = NULL; p->sink_desc = NULL; p->sink_fn = NULL; p->sink_export = NULL; p->sink_n_bufs = 0;
+}
+
+int p264pipe_sink_install_(p264pipe *p, const char *who, p264pipe_export_fn ex, const void *desc, size_t desc_bytes, int64_t bytes, int64_t frame_stride,
+                           void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user)
+{
+    if (!p || !ex || !desc || !fn || !bufs || n_bufs < 1 || bytes < 1) return -1;
+    for (int i = 0; i < n_bufs; i++) if (!bufs[i]) return -1;
+    /* every round may bring a picture of every stream */
+    const int64_t stride = frame_stride ? frame_stride : bytes;
+    if (stride > (INT64_MAX - bytes) / p->n_streams || (uint64_t)buf_bytes < (uint64_t)(p->n_streams - 1) * (uint64_t)stride + (uint64_t)bytes) {
+        fprintf(stderr, "%s: %d pictures %lld bytes apart do not fit %zu bytes\n", who, p->n_streams, (long long)stride, buf_bytes); return -1;
+    }
+    void **copy = (void **)malloc(sizeof(void *) * (size_t)n_bufs);
+    void *d = malloc(desc_bytes);
+    if (!copy || !d) { free(copy); free(d); return -1; }
+    memcpy(copy, bufs, sizeof(void *) * (size_t)n_bufs);
+    memcpy(d, desc, desc_bytes);
+    p264pipe_sink_remove_(p);
+    p->sink_export = ex; p->sink_desc = d; p->sink_bufs = copy; p->sink_n_bufs = n_bufs; p->sink_bytes = buf_bytes; p->sink_fn = fn; p->sink_user = user;
+    return 0;
+}
+
 int p264pipe_set_sink(p264pipe *p, const p264hip_export_t *e, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user)
 {
     if (!p) return -1;
-    if (!fn) { free(p->sink_bufs); p->sink_bufs = NULL; p->sink_fn = NULL; p->sink_n_bufs = 0; return 0; }
+    if (!fn) { p264pipe_sink_remove_(p); return 0; }
     if (p->device < 0 || !e || !bufs || n_bufs < 1) return -1;
-    for (int i = 0; i < n_bufs; i++) if (!bufs[i]) return -1;
-    /* every round may bring a picture of every stream (the frame itself is known at the first round: p264hip_export_frames checks the window) */
+    /* (the frame itself is known at the first round: p264hip_export_frames checks the window) */
     const int64_t bytes = p264hip_export_frame_bytes(e);
     if (bytes < 0 || (p->mb_w && p264hip_export_check(e, p->mb_w, p->mb_h)) || e->frame_stride < 0 || (e->frame_stride && e->frame_stride < bytes)) {
         fprintf(stderr, "p264pipe_set_sink: bad export description\n"); return -1;
     }
-    const int64_t stride = e->frame_stride ? e->frame_stride : bytes;
-    if (stride > (INT64_MAX - bytes) / p->n_streams || (uint64_t)buf_bytes < (uint64_t)(p->n_streams - 1) * (uint64_t)stride + (uint64_t)bytes) {
-        fprintf(stderr, "p264pipe_set_sink: %d pictures %lld bytes apart do not fit %zu bytes\n", p->n_streams, (long long)stride, buf_bytes); return -1;
-    }
-    void **copy = (void **)malloc(sizeof(void *) * (size_t)n_bufs);
-    if (!copy) return -1;
-    memcpy(copy, bufs, sizeof(void *) * (size_t)n_bufs);
-    free(p->sink_bufs);
-    p->sink_e = *e; p->sink_bufs = copy; p->sink_n_bufs = n_bufs; p->sink_bytes = buf_bytes; p->sink_fn = fn; p->sink_user = user;
-    return 0;
+    return p264pipe_sink_install_(p, "p264pipe_set_sink", export_plain, e, sizeof *e, bytes, e->frame_stride, bufs, n_bufs, buf_bytes, fn, user);
 }
 
 int64_t p264pipe_stream_pictures(p264pipe *p, int stream)
@@ -338,6 +372,6 @@ void p264pipe_close(p264pipe *p)
     if (p->ctx) p264hip_destroy(p->ctx);
     pthread_mutex_destroy(&p->mu); pthread_cond_destroy(&p->go); pthread_cond_destroy(&p->idle); pthread_cond_destroy(&p->turn);
     free(p->parsed); free((void *)p->round_pic[0]); free((void *)p->round_pic[1]);
-    free(p->sink_bufs); free(p->ids); free(p->sts); free(p->dsts); free((void *)p->pics);
+    free(p->sink_bufs); free(p->sink_desc); free(p->ids); free(p->sts); free(p->dsts); free((void *)p->pics);
     free(p->st); free(p->threads); free(p);
 }

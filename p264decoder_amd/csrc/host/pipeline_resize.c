@@ -1,0 +1,32 @@
+/* pipeline_resize.c - the pipeline's two exits in device memory with a resize on them (include/p264pipe.h:
+ * p264pipe_export_last_resized, p264pipe_set_sink_resized): the export kind p264hip_resize_t / p264hip_export_resized, installed
+ * through pipeline_sink.h.  pipeline.c runs the sink and knows nothing of the description. */
+#include <stdio.h>
+#include "pipeline_sink.h"
+
+static int export_resized(p264hip_ctx *ctx, const int *streams, const int *slots, int n, const void *desc, void *dst_dev, size_t bytes)
+{
+    return p264hip_export_resized(ctx, streams, slots, n, (const p264hip_resize_t *)desc, dst_dev, bytes);
+}
+
+int p264pipe_export_last_resized(p264pipe *p, const p264hip_resize_t *r, void *dst_dev, size_t bytes)
+{
+    return p264pipe_export_last_with_(p, "p264pipe_export_last_resized", export_resized, r, dst_dev, bytes);
+}
+
+int p264pipe_set_sink_resized(p264pipe *p, const p264hip_resize_t *r, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user)
+{
+    if (!p) return -1;
+    if (!fn) { p264pipe_sink_remove_(p); return 0; }
+    int device, mb_w, mb_h;
+    p264pipe_geometry_(p, &device, &mb_w, &mb_h);
+    if (device < 0 || !r || !bufs || n_bufs < 1) return -1;
+    /* (before the first round the frame is not known: the description is checked against the smallest frame that holds its window,
+     * and p264hip_export_resized checks the window against the streams' frame in the first round) */
+    const int64_t bytes = p264hip_resize_frame_bytes(r);
+    const int64_t fw = bytes < 0 ? 0 : ((int64_t)r->crop_left + r->crop_width + 15) / 16, fh = bytes < 0 ? 0 : ((int64_t)r->crop_top + r->crop_height + 15) / 16;
+    if (bytes < 0 || fw > 65536 || fh > 65536 || p264hip_resize_check(r, mb_w ? mb_w : (int)fw, mb_w ? mb_h : (int)fh)) {
+        fprintf(stderr, "p264pipe_set_sink_resized: bad resize description\n"); return -1;
+    }
+    return p264pipe_sink_install_(p, "p264pipe_set_sink_resized", export_resized, r, sizeof *r, bytes, r->frame_stride, bufs, n_bufs, buf_bytes, fn, user);
+}

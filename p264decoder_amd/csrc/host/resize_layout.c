@@ -1,0 +1,75 @@
+/* resize_layout.c - the layout of a resized exported picture (include/p264hip.h: p264hip_resize_t), the checks every resized
+ * export runs before anything is queued, and the tap positions of the bilinear filter.  Pure host code, no device involved; the
+ * kernel is csrc/hip/kernel_resize.h. */
+#include <math.h>
+#include "p264hip.h"
+
+static int is_rgb(int format) { return format == P264HIP_FMT_RGB24 || format == P264HIP_FMT_RGBP; }
+
+/* why the description is refused on its own (NULL: it is not); *pitch, *bytes: the pitch in bytes and one picture's bytes */
+static const char *describe(const p264hip_resize_t *r, int64_t *pitch, int64_t *bytes, int *elem)
+{
+    if (!r) return "null description";
+    if (r->format < P264HIP_FMT_I420 || r->format > P264HIP_FMT_RGBP) return "unknown format";
+    if (r->matrix != P264HIP_MATRIX_BT601 && r->matrix != P264HIP_MATRIX_BT709) return "unknown matrix";
+    if (r->full_range != 0 && r->full_range != 1) return "full_range is neither 0 nor 1";
+    if (!is_rgb(r->format) && (r->matrix || r->full_range)) return "matrix / full_range set on a YUV format";
+    if (r->crop_left < 0 || r->crop_top < 0 || r->crop_width < 1 || r->crop_height < 1) return "window with a negative offset or without samples";
+    if ((r->crop_left | r->crop_top | r->crop_width | r->crop_height) & 1) return "window with an odd member";
+    if (r->width < 2 || r->height < 2 || r->width > 16384 || r->height > 16384) return "output size outside 2 .. 16384";
+    if ((r->width | r->height) & 1) return "odd output size";
+    if (r->dtype != P264HIP_DTYPE_U8 && r->dtype != P264HIP_DTYPE_F16 && r->dtype != P264HIP_DTYPE_F32) return "unknown dtype";
+    if (r->filter != P264HIP_FILTER_BILINEAR) return "unknown filter";
+    if (r->dtype != P264HIP_DTYPE_U8 && !is_rgb(r->format)) return "float dtype on a YUV format";
+    for (int k = 0; k < 3; k++) {
+        if (!isfinite(r->scale[k]) || !isfinite(r->bias[k])) return "scale / bias not finite";
+        if (r->dtype == P264HIP_DTYPE_U8 && (r->scale[k] != 0.0f || r->bias[k] != 0.0f)) return "scale / bias set on the dtype U8";
+    }
+    const int64_t e = r->dtype == P264HIP_DTYPE_U8 ? 1 : r->dtype == P264HIP_DTYPE_F16 ? 2 : 4;
+    const int64_t tight = (r->format == P264HIP_FMT_RGB24 ? 3 * (int64_t)r->width : (int64_t)r->width) * e;
+    const int64_t p = r->pitch ? (int64_t)r->pitch : tight;
+    if (p < tight) return "pitch below the tight pitch";
+    if (p % e) return "pitch no multiple of the element size";
+    if (r->format == P264HIP_FMT_I420 && (p & 1)) return "odd pitch for I420";
+    const int64_t h = r->height;
+    *pitch = p; *elem = (int)e;
+    *bytes = r->format == P264HIP_FMT_RGB24 ? p * h : r->format == P264HIP_FMT_RGBP ? 3 * p * h : p * h + p * (h / 2);
+    return 0;
+}
+
+/* the same with the frame and the stride (what p264hip_export_resized reports through p264hip_last_error) */
+const char *p264hip_resize_why_(const p264hip_resize_t *r, int mb_w, int mb_h)
+{
+    int64_t pitch, bytes;
+    int elem;
+    const char *why = describe(r, &pitch, &bytes, &elem);
+    if (why) return why;
+    if (mb_w < 1 || mb_h < 1) return "no frame";
+    if ((int64_t)r->crop_left + r->crop_width > (int64_t)mb_w * 16 || (int64_t)r->crop_top + r->crop_height > (int64_t)mb_h * 16) return "window leaves the frame";
+    if (r->frame_stride < 0 || (r->frame_stride && r->frame_stride < bytes)) return "frame_stride below the picture's bytes";
+    if (r->frame_stride % elem) return "frame_stride no multiple of the element size";
+    return 0;
+}
+
+int64_t p264hip_resize_frame_bytes(const p264hip_resize_t *r)
+{
+    int64_t pitch, bytes;
+    int elem;
+    return describe(r, &pitch, &bytes, &elem) ? P264HIP_EINVAL : bytes;
+}
+
+int p264hip_resize_check(const p264hip_resize_t *r, int mb_w, int mb_h)
+{
+    return p264hip_resize_why_(r, mb_w, mb_h) ? P264HIP_EINVAL : P264HIP_OK;
+}
+
+int p264hip_resize_taps(int src_n, int dst_n, int32_t *pos)
+{
+    if (!pos || src_n < 1 || dst_n < 1 || src_n > (1 << 20) || dst_n > (1 << 20)) return P264HIP_EINVAL;
+    const int64_t S = src_n, D = dst_n, last = (S - 1) * 256;
+    for (int64_t d = 0; d < D; d++) {
+        int64_t p = ((2 * d + 1) * S * 256 + D) / (2 * D) - 128;           /* (the dividend is positive: / is floor) */
+        pos[d] = (int32_t)(p < 0 ? 0 : p > last ? last : p);
+    }
+    return P264HIP_OK;
+}

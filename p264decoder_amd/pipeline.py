@@ -114,6 +114,55 @@ class Pipeline:
         self._sink = (fn, keep, ptrs, callback)
         return per
 
+    def export_last_resized(self, size, fmt="rgbp", dtype="u8", crop=None, scale=None, bias=None, matrix="bt601", full_range=False, pitch=0, out=None):
+        """The last picture of every stream in device memory, the window `crop` (None: the display window) resized to size = (width,
+        height) (p264pipe_export_last_resized); the arguments, `out` and the result as HipReconstructor.export_resized has them."""
+        n = len(self._bufs)
+        r = N.resize_desc(fmt, size, self._window(crop), None, dtype, scale, bias, matrix, full_range, pitch)
+        per = self.lib.p264hip_resize_frame_bytes(C.byref(r))
+        if per < 0:
+            raise RuntimeError("export_last_resized: p264hip_resize_frame_bytes refuses the description")
+        if out is None:
+            torch = N.import_torch()
+            W, H = r.width, r.height
+            shape = (n, H * 3 // 2, W) if r.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if r.format == N.FMT_RGB24 else (n, 3, H, W)
+            want = {N.DTYPE_F16: torch.float16, N.DTYPE_F32: torch.float32}.get(r.dtype, torch.uint8)
+            out = torch.empty(shape, dtype=want, device="cuda") if not pitch else torch.empty((n, per), dtype=torch.uint8, device="cuda")
+        ptr, cap = out if isinstance(out, tuple) else (out.data_ptr(), out.numel() * out.element_size())
+        if self.lib.p264pipe_export_last_resized(self.h, C.byref(r), ptr, cap):
+            raise RuntimeError("p264pipe_export_last_resized failed: %s" % self.lib.p264hip_last_error().decode())
+        return out
+
+    def set_sink_resized(self, size, callback, fmt="rgbp", dtype="u8", depth=2, crop=None, scale=None, bias=None, matrix="bt601", full_range=False,
+                         pitch=0, buffers=None):
+        """set_sink with a resize on it (p264pipe_set_sink_resized): callback(round, streams, dev, bytes) for every round of run(),
+        picture k of the round at dev + k * bytes, the window `crop` (None: the display window of stream 0) resized to size = (width,
+        height), as `fmt` / `dtype` with scale and bias as HipReconstructor.export_resized has them.  It replaces a sink set before."""
+        n = len(self._bufs)
+        r = N.resize_desc(fmt, size, self._window(crop), None, dtype, scale, bias, matrix, full_range, pitch)
+        per = self.lib.p264hip_resize_frame_bytes(C.byref(r))
+        if per < 0:
+            raise RuntimeError("set_sink_resized: p264hip_resize_frame_bytes refuses the description")
+        keep = None
+        if buffers is None:
+            torch = N.import_torch()
+            keep = [torch.empty(n * per, dtype=torch.uint8, device="cuda") for _ in range(depth)]
+            buffers = [(t.data_ptr(), t.numel()) for t in keep]
+        ptrs = (C.c_void_p * len(buffers))(*[b[0] for b in buffers])
+        cap = min(b[1] for b in buffers)
+
+        def trampoline(user, rnd, k, streams, dev):
+            try:                                          # (an exception cannot cross the C frames: run() raises it)
+                if self._sink_error is None:
+                    callback(rnd, [streams[i] for i in range(k)], dev, per)
+            except BaseException as exc:
+                self._sink_error = exc
+        fn = N.SINK_FN(trampoline)
+        if self.lib.p264pipe_set_sink_resized(self.h, C.byref(r), ptrs, len(buffers), cap, fn, None):
+            raise RuntimeError("p264pipe_set_sink_resized refused (a buffer too small for %d pictures of %d bytes?)" % (n, per))
+        self._sink = (fn, keep, ptrs, callback)
+        return per
+
     def close(self):
         if self.h:
             self.lib.p264pipe_close(self.h)

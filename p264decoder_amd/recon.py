@@ -257,6 +257,46 @@ class HipReconstructor:
             self.sync()
         return out
 
+    def export_resized(self, streams, slots, size, fmt="rgbp", dtype="u8", crop=None, scale=None, bias=None, matrix="bt601", full_range=False,
+                       pitch=0, frame_stride=0, out=None, sync=True):
+        """Frames slots[i] of streams[i] into device memory with the window crop = (left, top, width, height) (None: the whole frame)
+        resized to size = (width, height) by the bilinear filter of include/p264hip.h, as "i420" / "nv12" / "rgb24" / "rgbp"; dtype
+        "u8", or - "rgb24" / "rgbp" - "f16" / "f32": channel * scale + bias, scale and bias one number or three (R, G, B)
+        (p264hip_export_resized: one launch, queued behind every reconstruct before it).
+        out: a torch tensor of that dtype (or uint8) on the device (filled in place, from its first element), a (device pointer, bytes) pair, or
+        None - a new torch tensor (n, H*3//2, W) for I420 / NV12, (n, H, W, 3) for RGB24, (n, 3, H, W) for RGBP at the tight layout,
+        (n, bytes) uint8 otherwise.  Returns the tensor (the pair as given).  sync=False leaves the wait to sync() or a marker."""
+        n = len(streams)
+        r = N.resize_desc(fmt, size, crop, (self.mb_w * 16, self.mb_h * 16), dtype, scale, bias, matrix, full_range, pitch, frame_stride)
+        if len(slots) != n:
+            raise P264Error("export_resized: %d streams, %d slots" % (n, len(slots)))
+        if out is None or not isinstance(out, tuple):
+            torch = N.import_torch()                      # only here: the module imports without torch or a GPU
+            want = {N.DTYPE_U8: torch.uint8, N.DTYPE_F16: torch.float16, N.DTYPE_F32: torch.float32}.get(r.dtype, torch.uint8)
+        if out is None:
+            per = self.lib.p264hip_resize_frame_bytes(C.byref(r))
+            if per < 0:
+                raise P264Error("export_resized: p264hip_resize_frame_bytes refuses the description")
+            W, H = r.width, r.height
+            shape = (n, H * 3 // 2, W) if r.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if r.format == N.FMT_RGB24 else (n, 3, H, W)
+            if not pitch and not frame_stride:
+                out = torch.empty(shape, dtype=want, device="cuda")
+            else:
+                out = torch.empty((n, r.frame_stride or per), dtype=torch.uint8, device="cuda")
+        if isinstance(out, tuple):
+            ptr, cap = out
+        else:
+            if not (out.is_cuda and out.is_contiguous() and out.dtype in (want, torch.uint8)):
+                raise P264Error("export_resized: out must be a contiguous %s (or uint8) tensor on the device" % want)
+            torch.cuda.current_stream(out.device).synchronize()     # (whatever torch still has queued on the tensor: the context has its own stream)
+            ptr, cap = out.data_ptr(), out.numel() * out.element_size()
+        a = (C.c_int * max(n, 1))(*streams)
+        b = (C.c_int * max(n, 1))(*slots)
+        self._chk(self.lib.p264hip_export_resized(self.h, a, b, n, C.byref(r), ptr, cap), "p264hip_export_resized")
+        if sync:
+            self.sync()
+        return out
+
     def clone_picture(self, dst, src):
         self._chk(self.lib.p264hip_clone_picture(self.h, dst, src), "p264hip_clone_picture")
 
