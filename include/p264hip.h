@@ -401,9 +401,31 @@ int     p264hip_export_frames(p264hip_ctx *ctx, const int *streams, const int *s
  *   v = (a*(256-fx)*(256-fy) + b*fx*(256-fy) + c*(256-fx)*fy + d*fx*fy + 32768) >> 16
  * Every sum stays below 2^24.  D == S returns the source, D == S/2 is exactly (a+b+c+d+2) >> 2, and the result is within 1 of
  * floor(real bilinear + 1/2) (each axis' position is off by at most 1/512: at most 255/512 per axis, and two roundings of 1/2).
- * The filter is bilinear ONLY: there is no antialiasing prefilter, a large reduction aliases exactly as
- * torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=False) does.  `filter` is there so that a box or
- * antialiased filter can be added without another struct.
+ * This filter (P264HIP_FILTER_BILINEAR, 0) has no antialiasing prefilter: a large reduction aliases exactly as
+ * torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=False) does.  For a reduction set `filter` to
+ * P264HIP_FILTER_BILINEAR_AA (2), below.  Value 1 is not assigned and is refused.
+ *
+ * The antialiased filter (P264HIP_FILTER_BILINEAR_AA).  The triangle filter whose half-width grows with the reduction - what PIL's
+ * BILINEAR and torch's interpolate(mode="bilinear", align_corners=False, antialias=True) compute -, separable and in integers only.
+ * For an axis with S source samples (the window's), D destination samples and the destination index d
+ *   U    = 2 * max(S, D)
+ *   r(j) = U - | (2j+1)*D - (2d+1)*S |        for the source index j = 0 .. S-1, relative to the window
+ *   taps = the j with r(j) > 0                (a contiguous run first .. first+n-1, never empty)
+ *   R    = the sum of r(j) over the taps
+ *   w(j) = floor( r(j) * 32768 / R )          (64-bit integers)
+ *   w(k) += 32768 - sum of w(j)               k = the tap with the largest r, the lowest index among equals
+ * The weights are Q15, not negative, and their sum is exactly 32768.  A source sample outside the WINDOW is no tap: it is dropped
+ * and the others renormalised (not clamped), and it is never read.  With D >= S this is bilinear at exact rational positions (two
+ * taps, D == S: one of 32768); with D == S/2 the inner weights are 1, 3, 3, 1 over 8.  Planes are resized one by one as above,
+ * vertically FIRST and then horizontally, with one rounding each:
+ *   t(y, c) = ( sum_k wy[y][k] * src[firsty[y]+k][c]  + 256  ) >> 9       0 .. 16320, the sample times 64; sums below 2^23
+ *   v(y, x) = ( sum_k wx[x][k] * t(y, firstx[x]+k)    + 2^20 ) >> 21      0 .. 255; sums below 2^30, no clip
+ * The order is part of the contract (the two roundings do not commute); vertical first because rows of a strip of the frame
+ * store are 16 contiguous bytes one after the other.  Against the real-valued filter |v - real| <= 1/2 + 1/128 + 255*(nx+ny-2)/32768
+ * with nx, ny the largest tap counts of the two axes: below 1 for 1080p to 224 x 224, below 2.5 at the limit.  The limit: a
+ * description with crop_width > 32 * width or crop_height > 32 * height is refused with this filter, so that an output sample has at
+ * most P264HIP_AA_MAX_TAPS taps per axis.  Layouts, RGB and the float step below are the same for both filters;
+ * tests/resize_aa_checker.py is this filter in numpy.
  *
  * Layouts.  The resized planes are treated as p264hip_export_t treats a frame: I420 / NV12 store them; RGB24 / RGBP take the chroma
  * sample (x >> 1, y >> 1) of the RESIZED chroma planes and the formula, coefficients and clip above.  The layout table above holds
@@ -414,7 +436,8 @@ int     p264hip_export_frames(p264hip_ctx *ctx, const int *streams, const int *s
  * two separately rounded IEEE single operations, never contracted into one; float16 is e converted round-to-nearest-even with
  * subnormals kept (numpy's astype(float16)).  tests/resize_checker.py is all of this in numpy. */
 enum { P264HIP_DTYPE_U8 = 0, P264HIP_DTYPE_F16 = 1, P264HIP_DTYPE_F32 = 2 };
-enum { P264HIP_FILTER_BILINEAR = 0 };
+enum { P264HIP_FILTER_BILINEAR = 0, P264HIP_FILTER_BILINEAR_AA = 2 };
+#define P264HIP_AA_MAX_TAPS 64
 typedef struct p264hip_resize {
     int32_t format, matrix, full_range;                     /* as in p264hip_export_t */
     int32_t crop_left, crop_top, crop_width, crop_height;   /* source window, luma samples, all even, inside the frame */
@@ -427,13 +450,18 @@ typedef struct p264hip_resize {
 /* bytes of one picture (host only, no device); < 0 = P264HIP_EINVAL for what p264hip_export_frame_bytes refuses in the fields the two
  * share, an output size that is odd, below 2 or above 16384, an unknown dtype or filter, a float dtype on a YUV format, a scale or
  * bias that is not finite - or not 0 where the dtype is U8 -, a pitch below the tight one or no multiple of the element size (I420: of
- * twice the element size, as its chroma pitch is pitch/2) */
+ * twice the element size, as its chroma pitch is pitch/2), and with P264HIP_FILTER_BILINEAR_AA a window more than 32 times the output
+ * in width or in height */
 int64_t p264hip_resize_frame_bytes(const p264hip_resize_t *r);
 /* 0, or P264HIP_EINVAL for the above, a window that leaves the frame of mb_w x mb_h macroblocks and a frame_stride (other than 0)
  * below the picture's bytes or no multiple of the element size (host only) */
 int     p264hip_resize_check(const p264hip_resize_t *r, int mb_w, int mb_h);
 /* pos[d] above for d = 0 .. dst_n - 1 (host only); P264HIP_EINVAL for a null pos or a count outside 1 .. 2^20 */
 int     p264hip_resize_taps(int src_n, int dst_n, int32_t *pos);
+/* the taps of P264HIP_FILTER_BILINEAR_AA (host only): first[d], count[d] and the Q15 weights of destination index d in
+ * weights[d * P264HIP_AA_MAX_TAPS ..], the entries behind count[d] 0; indices relative to the window.  P264HIP_EINVAL for a null
+ * pointer, a count outside 1 .. 2^20 or src_n > 32 * dst_n */
+int     p264hip_resize_aa_taps(int src_n, int dst_n, int32_t *first, int32_t *count, uint16_t *weights);
 /* the contract of p264hip_export_frames: picture i = frame slots[i] of stream streams[i], resized, at dst_dev + i*frame_stride;
  * asynchronous on the context's stream behind every reconstruct queued before it, complete after p264hip_sync or a marker; entries
  * may repeat; more than 65535 pictures go out as several launches.  P264HIP_EINVAL, before anything is queued, for a null argument,

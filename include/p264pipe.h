@@ -65,7 +65,9 @@ int  p264pipe_export_last(p264pipe *p, const p264hip_export_t *e, void *dst_dev,
 typedef void (*p264pipe_sink_fn)(void *user, int round, int n, const int *streams, void *dev);
 int  p264pipe_set_sink(p264pipe *p, const p264hip_export_t *e, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user);
 /* The same two exits with a resize on them (p264hip_resize_t, include/p264hip.h: a window of each picture resized, as bytes or -
- * RGB formats - normalised floats; p264hip_export_resized).  A pipeline has ONE sink: setting either kind replaces the other, and
+ * RGB formats - normalised floats; p264hip_export_resized).  The description's `filter` goes through unchanged: with
+ * P264HIP_FILTER_BILINEAR_AA every round's pictures, and the last ones, are resized by the antialiased filter (at most 32:1; a
+ * description above that is refused here as p264hip_resize_check refuses it).  A pipeline has ONE sink: setting either kind replaces the other, and
  * fn = NULL to either call takes it away.  p264pipe_export_last and p264pipe_set_sink behave as before. */
 int  p264pipe_export_last_resized(p264pipe *p, const p264hip_resize_t *r, void *dst_dev, size_t bytes);
 int  p264pipe_set_sink_resized(p264pipe *p, const p264hip_resize_t *r, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user);

@@ -132,14 +132,16 @@ class Resize(C.Structure):
 
 
 DTYPE_U8, DTYPE_F16, DTYPE_F32 = range(3)
-FILTER_BILINEAR = 0
+FILTER_BILINEAR, FILTER_BILINEAR_AA = 0, 2
+FILTERS = {"bilinear": FILTER_BILINEAR, "bilinear_aa": FILTER_BILINEAR_AA}
+AA_MAX_TAPS = 64
 DTYPES = {"u8": DTYPE_U8, "f16": DTYPE_F16, "f32": DTYPE_F32}
 ELEM_BYTES = {DTYPE_U8: 1, DTYPE_F16: 2, DTYPE_F32: 4}
 
 
 def resize_desc(fmt="rgbp", size=None, crop=None, frame=None, dtype="u8", scale=None, bias=None, matrix="bt601", full_range=False, pitch=0,
                 frame_stride=0, filter=FILTER_BILINEAR):
-    """A p264hip_resize_t: fmt / dtype / matrix by name (or number), size = (width, height) of the output (None: the window's), crop =
+    """A p264hip_resize_t: fmt / dtype / matrix / filter ("bilinear", "bilinear_aa") by name (or number), size = (width, height) of the output (None: the window's), crop =
     (left, top, width, height) of the source window or None for the whole `frame` = (width, height), scale / bias = one number for
     all channels or three (R, G, B; None: 0).  Names that do not exist raise; everything else is the library's to check."""
     r = Resize()
@@ -149,7 +151,7 @@ def resize_desc(fmt="rgbp", size=None, crop=None, frame=None, dtype="u8", scale=
     r.crop_left, r.crop_top, r.crop_width, r.crop_height = crop if crop is not None else (0, 0, frame[0], frame[1])
     r.width, r.height = size if size is not None else (r.crop_width, r.crop_height)
     r.dtype = DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
-    r.filter = int(filter)
+    r.filter = FILTERS[filter] if isinstance(filter, str) else int(filter)
     r.pitch, r.frame_stride = int(pitch), int(frame_stride)
     for name, v in (("scale", scale), ("bias", bias)):
         v = (0.0, 0.0, 0.0) if v is None else tuple(v) if hasattr(v, "__len__") else (v, v, v)
@@ -285,6 +287,9 @@ def load(path=None):
         lib.p264hip_resize_check.argtypes = [C.POINTER(Resize), C.c_int, C.c_int]
         lib.p264hip_resize_taps.restype = C.c_int
         lib.p264hip_resize_taps.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        if hasattr(lib, "p264hip_resize_aa_taps"):
+            lib.p264hip_resize_aa_taps.restype = C.c_int
+            lib.p264hip_resize_aa_taps.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint16)]
         lib.p264hip_export_resized.restype = C.c_int
         lib.p264hip_export_resized.argtypes = [C.c_void_p, ip, ip, C.c_int, C.POINTER(Resize), C.c_void_p, C.c_size_t]
     # ---- p264pipe.h

@@ -144,11 +144,59 @@ template <int DT> __device__ __forceinline__ void put_rgb24(uint8_t *p, uint32_t
     }
 }
 
+// four luma samples v of an output row (`row`: its first byte in plane 0) from column x on, n of them inside the row, with the two
+// chroma pairs under them (cb, cr: less 128; RGB formats only) -> the elements of the format.  Shared with kernel_resize_aa.h.
+template <int FMT, int DT>
+__device__ __forceinline__ void put_luma4(uint8_t *row, int x, const int (&v)[4], const int (&cb)[2], const int (&cr)[2], int n, const ResizeParams &e)
+{
+    constexpr bool RGB = FMT == P264HIP_FMT_RGB24 || FMT == P264HIP_FMT_RGBP;
+    constexpr int ELEM = DT == P264HIP_DTYPE_U8 ? 1 : DT == P264HIP_DTYPE_F16 ? 2 : 4;
+    if (!RGB) {
+        const uint32_t w[1] = { pack4(v[0], v[1], v[2], v[3]) };
+        put_elems<1, 4, 1>(row + x, w, n);
+    } else {
+        int tr[4], tg[4], tb[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {       // (kernel_export.h's rgb_row: every sum of the pixel stays below 2^23)
+            const int yy = __mul24(e.cy, v[j] - e.yo) + 4096;
+            tr[j] = yy + __mul24(e.r_cv, cr[j >> 1]);
+            tg[j] = yy + __mul24(e.g_cu, cb[j >> 1]) + __mul24(e.g_cv, cr[j >> 1]);
+            tb[j] = yy + __mul24(e.b_cu, cb[j >> 1]);
+        }
+        const uint32_t R = round_pack4<13>(tr), G = round_pack4<13>(tg), B = round_pack4<13>(tb);
+        if (FMT == P264HIP_FMT_RGBP) {
+            const int64_t plane = e.pitch * e.h;
+            put_channel4<DT>(row + x * ELEM, R, n, e.scale[0], e.bias[0]);
+            put_channel4<DT>(row + plane + x * ELEM, G, n, e.scale[1], e.bias[1]);
+            put_channel4<DT>(row + 2 * plane + x * ELEM, B, n, e.scale[2], e.bias[2]);
+        } else {
+            put_rgb24<DT>(row + 3 * x * ELEM, R, G, B, n, e);
+        }
+    }
+}
+
+// four chroma samples u, v of chroma row y from chroma column x on, n of them inside the row, behind the luma plane of picture `out`
+// (I420 / NV12).  Shared with kernel_resize_aa.h.
+template <int FMT>
+__device__ __forceinline__ void put_chroma4(uint8_t *out, int y, int x, const int (&u)[4], const int (&v)[4], int n, const ResizeParams &e)
+{
+    uint8_t *planes = out + e.pitch * e.h;
+    if (FMT == P264HIP_FMT_NV12) {
+        const uint32_t w[2] = { pack4(u[0], v[0], u[1], v[1]), pack4(u[2], v[2], u[3], v[3]) };
+        put_elems<2, 8, 1>(planes + (int64_t)y * e.pitch + 2 * x, w, 2 * n);
+    } else {
+        const int64_t cp = e.pitch >> 1;
+        const uint32_t uw[1] = { pack4(u[0], u[1], u[2], u[3]) }, vw[1] = { pack4(v[0], v[1], v[2], v[3]) };
+        uint8_t *row = planes + (int64_t)y * cp + x;
+        put_elems<1, 4, 1>(row, uw, n);
+        put_elems<1, 4, 1>(row + cp * (e.h >> 1), vw, n);
+    }
+}
+
 template <int FMT, int DT>
 __device__ __forceinline__ void resize_body(const uint8_t *frames, size_t frame_bytes, const Geom &g, const uint32_t *table, int pic_base, uint8_t *dst, const ResizeParams &e)
 {
     constexpr bool RGB = FMT == P264HIP_FMT_RGB24 || FMT == P264HIP_FMT_RGBP;
-    constexpr int ELEM = DT == P264HIP_DTYPE_U8 ? 1 : DT == P264HIP_DTYPE_F16 ? 2 : 4;
     const int lane = threadIdx.x & 63;
     const int wt = rfl((int)(blockIdx.x * (RESIZE_THREADS / WAVE) + (threadIdx.x >> 6)));
     if (wt >= e.n_tiles) return;
@@ -201,34 +249,12 @@ __device__ __forceinline__ void resize_body(const uint8_t *frames, size_t frame_
             int v[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) v[j] = bilinear(s[r][j], fx[j], fy[r]);
-            uint8_t *row = out + (int64_t)(y + r) * e.pitch;
-            if (!RGB) {
-                const uint32_t w[1] = { pack4(v[0], v[1], v[2], v[3]) };
-                put_elems<1, 4, 1>(row + x, w, n);
-            } else {
-                int tr[4], tg[4], tb[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) {       // (kernel_export.h's rgb_row: every sum of the pixel stays below 2^23)
-                    const int yy = __mul24(e.cy, v[j] - e.yo) + 4096;
-                    tr[j] = yy + __mul24(e.r_cv, cr[j >> 1]);
-                    tg[j] = yy + __mul24(e.g_cu, cb[j >> 1]) + __mul24(e.g_cv, cr[j >> 1]);
-                    tb[j] = yy + __mul24(e.b_cu, cb[j >> 1]);
-                }
-                const uint32_t R = round_pack4<13>(tr), G = round_pack4<13>(tg), B = round_pack4<13>(tb);
-                if (FMT == P264HIP_FMT_RGBP) {
-                    const int64_t plane = e.pitch * e.h;
-                    put_channel4<DT>(row + x * ELEM, R, n, e.scale[0], e.bias[0]);
-                    put_channel4<DT>(row + plane + x * ELEM, G, n, e.scale[1], e.bias[1]);
-                    put_channel4<DT>(row + 2 * plane + x * ELEM, B, n, e.scale[2], e.bias[2]);
-                } else {
-                    put_rgb24<DT>(row + 3 * x * ELEM, R, G, B, n, e);
-                }
-            }
+            put_luma4<FMT, DT>(out + (int64_t)(y + r) * e.pitch, x, v, cb, cr, n, e);
         }
     } else if (!RGB) {
         int y, tx;
         split_tile(wt - e.n_ltiles, e.ctx, e.inv_ctx, y, tx);
-        const int x = (tx * WAVE + lane) * RESIZE_PX, cw = e.w >> 1, ch = e.h >> 1;
+        const int x = (tx * WAVE + lane) * RESIZE_PX, cw = e.w >> 1;
         if (x >= cw) return;
         const uint4 xq = gload4(table + e.t_xc + x);
         const uint32_t xt[4] = { xq.x, xq.y, xq.z, xq.w };
@@ -248,17 +274,7 @@ __device__ __forceinline__ void resize_body(const uint8_t *frames, size_t frame_
 #pragma unroll
         for (int j = 0; j < 4; j++) { u[j] = bilinear(s[0][j], fx[j], fy); v[j] = bilinear(s[1][j], fx[j], fy); }
         const int n = min(cw - x, RESIZE_PX);
-        uint8_t *planes = out + e.pitch * e.h;
-        if (FMT == P264HIP_FMT_NV12) {
-            const uint32_t w[2] = { pack4(u[0], v[0], u[1], v[1]), pack4(u[2], v[2], u[3], v[3]) };
-            put_elems<2, 8, 1>(planes + (int64_t)y * e.pitch + 2 * x, w, 2 * n);
-        } else {
-            const int64_t cp = e.pitch >> 1;
-            const uint32_t uw[1] = { pack4(u[0], u[1], u[2], u[3]) }, vw[1] = { pack4(v[0], v[1], v[2], v[3]) };
-            uint8_t *row = planes + (int64_t)y * cp + x;
-            put_elems<1, 4, 1>(row, uw, n);
-            put_elems<1, 4, 1>(row + cp * ch, vw, n);
-        }
+        put_chroma4<FMT>(out, y, x, u, v, n, e);
     }
 }
 

@@ -25,6 +25,7 @@
 #include "kernel_expand.h"
 #include "kernel_export.h"
 #include "kernel_resize.h"
+#include "kernel_resize_aa.h"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -642,6 +643,103 @@ static void resize_table(uint32_t *t, int first, int src_n, int dst_n)
     }
 }
 
+// ---- the antialiased filter (kernel_resize_aa.h) ----
+// the taps of one axis as p264hip_resize_aa_taps gives them (the counts have passed p264hip_resize_check, which it cannot refuse)
+struct AaTaps {
+    std::vector<int32_t> first, count;
+    std::vector<uint16_t> w;
+    int n, off, stride;             // destination samples; the window's offset in the frame; the largest count, rounded up to even
+    void build(int offset, int src_n, int dst_n)
+    {
+        n = dst_n; off = offset;
+        first.resize((size_t)n); count.resize((size_t)n); w.resize((size_t)n * P264HIP_AA_MAX_TAPS);
+        (void)p264hip_resize_aa_taps(src_n, dst_n, first.data(), count.data(), w.data());
+        int top = 1;
+        for (int d = 0; d < n; d++) top = count[(size_t)d] > top ? count[(size_t)d] : top;
+        stride = (top + 1) & ~1;
+    }
+    int pos_words() const { return (n + 3) & ~3; }
+    int weight_words() const { return (n * (stride / 2) + 3) & ~3; }
+    // strips (of 1 << sh samples) of the widest source span among the tiles of tw destination samples
+    int span(int tw, int sh) const
+    {
+        int top = 1;
+        for (int x0 = 0; x0 < n; x0 += tw) {
+            const int x1 = (x0 + tw < n ? x0 + tw : n) - 1;
+            const int s = ((off + first[(size_t)x1] + count[(size_t)x1] - 1) >> sh) - ((off + first[(size_t)x0]) >> sh) + 1;
+            top = s > top ? s : top;
+        }
+        return top;
+    }
+    // the axis into the call's table from word `at` on; returns the word behind it
+    int put(uint32_t *t, int at, AaAxis &ax) const
+    {
+        ax.pos = at; ax.wts = at + pos_words(); ax.stride = stride;
+        for (int d = 0; d < pos_words(); d++) { const size_t k = (size_t)(d < n ? d : n - 1); t[at + d] = (uint32_t)(off + first[k]) | (uint32_t)count[k] << 16; }
+        uint16_t *wt = (uint16_t *)(t + ax.wts);
+        for (int d = 0; d < n; d++)
+            for (int k = 0; k < stride; k++) wt[(size_t)d * stride + k] = w[(size_t)d * P264HIP_AA_MAX_TAPS + k];
+        for (size_t k = (size_t)n * stride; k < (size_t)weight_words() * 2; k++) wt[k] = 0;
+        return ax.wts + weight_words();
+    }
+};
+
+#define RESIZE_AA_LAUNCH(name) hipLaunchKernelGGL(name, grid, dim3(AA_THREADS), lds, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p)
+
+// p264hip_export_resized with P264HIP_FILTER_BILINEAR_AA: everything has been checked
+static int export_resized_aa(p264hip_ctx *c, const int *streams, const int *slots, int n, const p264hip_resize_t *e, void *dst, int64_t pitch, int64_t stride)
+{
+    const int W = e->width, H = e->height;
+    AaTaps xl, yl, xc, yc;
+    xl.build(e->crop_left, e->crop_width, W); yl.build(e->crop_top, e->crop_height, H);
+    xc.build(e->crop_left / 2, e->crop_width / 2, W / 2); yc.build(e->crop_top / 2, e->crop_height / 2, H / 2);
+    AaParams p = {};
+    // the widest tile whose source columns fit the LDS, luma and chroma
+    int tw = AA_TW;
+    for (;; tw >>= 1) {
+        p.ns_l = xl.span(tw, 4); p.ns_c = xc.span(tw / 2, 3);
+        if (p.ns_l * 16 * AA_TH <= AA_T_CAP && p.ns_c * 16 * (AA_TH / 2) <= AA_T_CAP) break;
+        if (tw == 8) return fail(P264HIP_EINVAL, "p264hip_export_resized: a tile of 8 samples spans %d luma and %d chroma strips", p.ns_l, p.ns_c);
+    }
+    for (p.tw_shift = 0; (4 << p.tw_shift) < tw; p.tw_shift++) ;
+    p.inv_ns_l = 0xffffffffu / (uint32_t)p.ns_l; p.inv_ns_c = 0xffffffffu / (uint32_t)p.ns_c;
+    p.ntx = (W + tw - 1) / tw; p.inv_ntx = 0xffffffffu / (uint32_t)p.ntx;
+    const int first_word = (n + 3) & ~3;
+    const int words = first_word + xl.pos_words() + xl.weight_words() + yl.pos_words() + yl.weight_words() + xc.pos_words() + xc.weight_words() + yc.pos_words() + yc.weight_words();
+    int rc = export_reserve(c, words);
+    if (rc) return rc;
+    const int r = c->exp_ring; c->exp_ring = (c->exp_ring + 1) % BATCH_RING;
+    HIPCHK(hipEventSynchronize(c->exp_free[r]));              // the copy that last used this staging buffer is done
+    uint32_t *t = c->h_exp[r];
+    for (int i = 0; i < n; i++) t[i] = (uint32_t)(streams[i] * c->slots + slots[i]);
+    for (int i = n; i < first_word; i++) t[i] = 0;
+    int at = xl.put(t, first_word, p.xl);
+    at = yl.put(t, at, p.yl); at = xc.put(t, at, p.xc); at = yc.put(t, at, p.yc);
+    HIPCHK(hipMemcpyAsync(c->d_exp[r], t, (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->exp_free[r], c->stream));
+    p.r.w = W; p.r.h = H; p.r.pitch = pitch; p.r.frame_stride = stride;
+    const int32_t *k = export_coefs[e->matrix][e->full_range];
+    p.r.cy = k[0]; p.r.yo = e->full_range ? 0 : 16; p.r.r_cv = k[1]; p.r.g_cu = k[2]; p.r.g_cv = k[3]; p.r.b_cu = k[4];
+    for (int i = 0; i < 3; i++) { p.r.scale[i] = e->scale[i]; p.r.bias[i] = e->bias[i]; }
+    const unsigned gx = (unsigned)(p.ntx * ((H + AA_TH - 1) / AA_TH));
+    const size_t lds = sizeof(uint16_t) * 16 * (size_t)(p.ns_l * AA_TH > p.ns_c * (AA_TH / 2) ? p.ns_l * AA_TH : p.ns_c * (AA_TH / 2));
+    for (int base = 0; base < n; base += 65535) {            // (a grid's second dimension ends at 65535)
+        const dim3 grid(gx, (unsigned)(n - base < 65535 ? n - base : 65535));
+        switch (e->format * 3 + e->dtype) {
+        case P264HIP_FMT_I420 * 3:                       RESIZE_AA_LAUNCH(k_resize_aa_i420); break;
+        case P264HIP_FMT_NV12 * 3:                       RESIZE_AA_LAUNCH(k_resize_aa_nv12); break;
+        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_U8:   RESIZE_AA_LAUNCH(k_resize_aa_rgb24_u8); break;
+        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F16:  RESIZE_AA_LAUNCH(k_resize_aa_rgb24_f16); break;
+        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F32:  RESIZE_AA_LAUNCH(k_resize_aa_rgb24_f32); break;
+        case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_U8:    RESIZE_AA_LAUNCH(k_resize_aa_rgbp_u8); break;
+        case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_F16:   RESIZE_AA_LAUNCH(k_resize_aa_rgbp_f16); break;
+        default:                                         RESIZE_AA_LAUNCH(k_resize_aa_rgbp_f32); break;
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return P264HIP_OK;
+}
+
 #define RESIZE_LAUNCH(name) hipLaunchKernelGGL(name, grid, dim3(RESIZE_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p)
 
 extern "C" int p264hip_export_resized(p264hip_ctx *c, const int *streams, const int *slots, int n, const p264hip_resize_t *e, void *dst, size_t dst_bytes)
@@ -662,6 +760,7 @@ extern "C" int p264hip_export_resized(p264hip_ctx *c, const int *streams, const 
     const uint64_t need = (uint64_t)(n - 1) * (uint64_t)stride + (uint64_t)bytes;
     if ((uint64_t)dst_bytes < need) return fail(P264HIP_EINVAL, "p264hip_export_resized: %d pictures need %llu bytes, dst has %zu", n, (unsigned long long)need, dst_bytes);
     HIPCHK(hipSetDevice(c->device));
+    if (e->filter == P264HIP_FILTER_BILINEAR_AA) return export_resized_aa(c, streams, slots, n, e, dst, pitch, stride);
     // the call's table: the frame indices, then the four tap tables, each from a multiple of 4 words
     const bool rgb = e->format == P264HIP_FMT_RGB24 || e->format == P264HIP_FMT_RGBP;
     const int W = e->width, H = e->height, cw = W / 2, ch = H / 2;

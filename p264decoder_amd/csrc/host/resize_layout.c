@@ -1,6 +1,6 @@
 /* resize_layout.c - the layout of a resized exported picture (include/p264hip.h: p264hip_resize_t), the checks every resized
- * export runs before anything is queued, and the tap positions of the bilinear filter.  Pure host code, no device involved; the
- * kernel is csrc/hip/kernel_resize.h. */
+ * export runs before anything is queued, and the taps of the two filters.  Pure host code, no device involved; the kernels are
+ * csrc/hip/kernel_resize.h and kernel_resize_aa.h. */
 #include <math.h>
 #include "p264hip.h"
 
@@ -19,7 +19,7 @@ static const char *describe(const p264hip_resize_t *r, int64_t *pitch, int64_t *
     if (r->width < 2 || r->height < 2 || r->width > 16384 || r->height > 16384) return "output size outside 2 .. 16384";
     if ((r->width | r->height) & 1) return "odd output size";
     if (r->dtype != P264HIP_DTYPE_U8 && r->dtype != P264HIP_DTYPE_F16 && r->dtype != P264HIP_DTYPE_F32) return "unknown dtype";
-    if (r->filter != P264HIP_FILTER_BILINEAR) return "unknown filter";
+    if (r->filter != P264HIP_FILTER_BILINEAR && r->filter != P264HIP_FILTER_BILINEAR_AA) return "unknown filter";
     if (r->dtype != P264HIP_DTYPE_U8 && !is_rgb(r->format)) return "float dtype on a YUV format";
     for (int k = 0; k < 3; k++) {
         if (!isfinite(r->scale[k]) || !isfinite(r->bias[k])) return "scale / bias not finite";
@@ -31,6 +31,8 @@ static const char *describe(const p264hip_resize_t *r, int64_t *pitch, int64_t *
     if (p < tight) return "pitch below the tight pitch";
     if (p % e) return "pitch no multiple of the element size";
     if (r->format == P264HIP_FMT_I420 && (p & 1)) return "odd pitch for I420";
+    if (r->filter == P264HIP_FILTER_BILINEAR_AA && (r->crop_width > 32 * (int64_t)r->width || r->crop_height > 32 * (int64_t)r->height))
+        return "reduction above 32:1 with the antialiased filter";
     const int64_t h = r->height;
     *pitch = p; *elem = (int)e;
     *bytes = r->format == P264HIP_FMT_RGB24 ? p * h : r->format == P264HIP_FMT_RGBP ? 3 * p * h : p * h + p * (h / 2);
@@ -70,6 +72,38 @@ int p264hip_resize_taps(int src_n, int dst_n, int32_t *pos)
     for (int64_t d = 0; d < D; d++) {
         int64_t p = ((2 * d + 1) * S * 256 + D) / (2 * D) - 128;           /* (the dividend is positive: / is floor) */
         pos[d] = (int32_t)(p < 0 ? 0 : p > last ? last : p);
+    }
+    return P264HIP_OK;
+}
+
+static int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }        /* b > 0 */
+
+int p264hip_resize_aa_taps(int src_n, int dst_n, int32_t *first, int32_t *count, uint16_t *weights)
+{
+    if (!first || !count || !weights || src_n < 1 || dst_n < 1 || src_n > (1 << 20) || dst_n > (1 << 20) || (int64_t)src_n > 32 * (int64_t)dst_n) return P264HIP_EINVAL;
+    const int64_t S = src_n, D = dst_n, U = 2 * (S > D ? S : D);
+    for (int64_t d = 0; d < D; d++) {
+        const int64_t c = (2 * d + 1) * S;
+        /* r(j) > 0: c - U < (2j+1)*D < c + U */
+        int64_t lo = floor_div(c - U - D, 2 * D) + 1, hi = -floor_div(-(c + U - D), 2 * D) - 1;
+        if (lo < 0) lo = 0;
+        if (hi > S - 1) hi = S - 1;
+        uint16_t *w = weights + d * P264HIP_AA_MAX_TAPS;
+        int64_t R = 0, best = -1, sum = 0;
+        int n = 0, at = 0;
+        for (int64_t j = lo; j <= hi && n < P264HIP_AA_MAX_TAPS; j++, n++) {
+            int64_t a = (2 * j + 1) * D - c;
+            R += U - (a < 0 ? -a : a);
+        }
+        for (int k = 0; k < n; k++) {
+            int64_t a = (2 * (lo + k) + 1) * D - c;
+            const int64_t r = U - (a < 0 ? -a : a), q = r * 32768 / R;
+            if (r > best) { best = r; at = k; }
+            w[k] = (uint16_t)q; sum += q;
+        }
+        w[at] = (uint16_t)(w[at] + (32768 - sum));
+        for (int k = n; k < P264HIP_AA_MAX_TAPS; k++) w[k] = 0;
+        first[d] = (int32_t)lo; count[d] = n;
     }
     return P264HIP_OK;
 }

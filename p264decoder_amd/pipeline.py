@@ -114,11 +114,12 @@ class Pipeline:
         self._sink = (fn, keep, ptrs, callback)
         return per
 
-    def export_last_resized(self, size, fmt="rgbp", dtype="u8", crop=None, scale=None, bias=None, matrix="bt601", full_range=False, pitch=0, out=None):
+    def export_last_resized(self, size, fmt="rgbp", dtype="u8", crop=None, scale=None, bias=None, matrix="bt601", full_range=False, pitch=0, out=None, *,
+                            filter="bilinear"):
         """The last picture of every stream in device memory, the window `crop` (None: the display window) resized to size = (width,
-        height) (p264pipe_export_last_resized); the arguments, `out` and the result as HipReconstructor.export_resized has them."""
+        height) (p264pipe_export_last_resized); the arguments, `filter` among them, `out` and the result as HipReconstructor.export_resized has them."""
         n = len(self._bufs)
-        r = N.resize_desc(fmt, size, self._window(crop), None, dtype, scale, bias, matrix, full_range, pitch)
+        r = N.resize_desc(fmt, size, self._window(crop), None, dtype, scale, bias, matrix, full_range, pitch, filter=filter)
         per = self.lib.p264hip_resize_frame_bytes(C.byref(r))
         if per < 0:
             raise RuntimeError("export_last_resized: p264hip_resize_frame_bytes refuses the description")
@@ -134,12 +135,12 @@ class Pipeline:
         return out
 
     def set_sink_resized(self, size, callback, fmt="rgbp", dtype="u8", depth=2, crop=None, scale=None, bias=None, matrix="bt601", full_range=False,
-                         pitch=0, buffers=None):
+                         pitch=0, buffers=None, *, filter="bilinear"):
         """set_sink with a resize on it (p264pipe_set_sink_resized): callback(round, streams, dev, bytes) for every round of run(),
         picture k of the round at dev + k * bytes, the window `crop` (None: the display window of stream 0) resized to size = (width,
-        height), as `fmt` / `dtype` with scale and bias as HipReconstructor.export_resized has them.  It replaces a sink set before."""
+        height), as `fmt` / `dtype` with scale, bias and `filter` as HipReconstructor.export_resized has them.  It replaces a sink set before."""
         n = len(self._bufs)
-        r = N.resize_desc(fmt, size, self._window(crop), None, dtype, scale, bias, matrix, full_range, pitch)
+        r = N.resize_desc(fmt, size, self._window(crop), None, dtype, scale, bias, matrix, full_range, pitch, filter=filter)
         per = self.lib.p264hip_resize_frame_bytes(C.byref(r))
         if per < 0:
             raise RuntimeError("set_sink_resized: p264hip_resize_frame_bytes refuses the description")

@@ -258,16 +258,17 @@ class HipReconstructor:
         return out
 
     def export_resized(self, streams, slots, size, fmt="rgbp", dtype="u8", crop=None, scale=None, bias=None, matrix="bt601", full_range=False,
-                       pitch=0, frame_stride=0, out=None, sync=True):
+                       pitch=0, frame_stride=0, out=None, sync=True, *, filter="bilinear"):
         """Frames slots[i] of streams[i] into device memory with the window crop = (left, top, width, height) (None: the whole frame)
-        resized to size = (width, height) by the bilinear filter of include/p264hip.h, as "i420" / "nv12" / "rgb24" / "rgbp"; dtype
+        resized to size = (width, height) by the bilinear filter of include/p264hip.h (filter="bilinear_aa": its antialiased filter,
+        the one for a reduction; at most 32:1), as "i420" / "nv12" / "rgb24" / "rgbp"; dtype
         "u8", or - "rgb24" / "rgbp" - "f16" / "f32": channel * scale + bias, scale and bias one number or three (R, G, B)
         (p264hip_export_resized: one launch, queued behind every reconstruct before it).
         out: a torch tensor of that dtype (or uint8) on the device (filled in place, from its first element), a (device pointer, bytes) pair, or
         None - a new torch tensor (n, H*3//2, W) for I420 / NV12, (n, H, W, 3) for RGB24, (n, 3, H, W) for RGBP at the tight layout,
         (n, bytes) uint8 otherwise.  Returns the tensor (the pair as given).  sync=False leaves the wait to sync() or a marker."""
         n = len(streams)
-        r = N.resize_desc(fmt, size, crop, (self.mb_w * 16, self.mb_h * 16), dtype, scale, bias, matrix, full_range, pitch, frame_stride)
+        r = N.resize_desc(fmt, size, crop, (self.mb_w * 16, self.mb_h * 16), dtype, scale, bias, matrix, full_range, pitch, frame_stride, filter)
         if len(slots) != n:
             raise P264Error("export_resized: %d streams, %d slots" % (n, len(slots)))
         if out is None or not isinstance(out, tuple):
