@@ -60,7 +60,7 @@ int p264parse_nal(p264parse *p, int nal_type, int nal_ref_idc,
 /* geometry / frame-store size of the active SPS (0 before the first slice) */
 int p264parse_mb_width(const p264parse *p);
 int p264parse_mb_height(const p264parse *p);
-int p264parse_slots(const p264parse *p);          /* num_ref_frames + 1 */
+int p264parse_slots(const p264parse *p);          /* num_ref_frames + 1; with output order on: D + 1 (below) */
 /* The display window of the active SPS in luma samples: its frame cropping offsets times 2 in both directions (4:2:0, frame
  * macroblocks only); without cropping the MB-aligned frame.  The parser itself never crops: its pictures, and every frame store
  * behind them, stay MB-aligned - the window is what a caller puts into a p264hip_export_t.  -1 before the first slice, or where
@@ -68,6 +68,52 @@ int p264parse_slots(const p264parse *p);          /* num_ref_frames + 1 */
 int p264parse_crop(const p264parse *p, int *left, int *top, int *width, int *height);
 /* bumped every time a new SPS/PPS pair is activated (context re-init, decoder.c:304-343) */
 int p264parse_generation(const p264parse *p);
+
+/* ---- pictures in output (display) order: the output process of H.264 C.4, "bumping" (C.4.5.3).  Off by default ----
+ * The parser's pictures come in decode order, and without this option a slot of the frame store is reused as soon as it holds no
+ * reference.  With it, a completed picture joins the set W of pictures that wait for their output and keeps its slot until it is
+ * due: no later picture's dst_slot names a slot that holds a reference or a member of W.
+ *
+ * Per active SPS: D, the frames the decoded picture buffer holds - max_dec_frame_buffering where the SPS carries a VUI with
+ * bitstream_restriction_flag, else MaxDpbFrames = min(MaxDpbMbs(level_idc) / (mb_w * mb_h), 16) of table A-1 (16 for an unknown
+ * level_idc), in both cases at least num_ref_frames (and 1) and at most 16; R, the reorder depth - num_reorder_frames of that
+ * restriction, else 0 under pic_order_cnt_type 2 (output order is decode order, 8.2.1.3), else D.  A VUI that overruns its NAL
+ * unit or holds num_reorder_frames > max_dec_frame_buffering or either above 16 counts as absent; it never refuses the SPS.
+ *
+ * The rule, applied when picture P is complete:
+ *   1. if P is an IDR picture or carried memory_management_control_operation 5, every member of W is due, ascending by order count
+ *      (no_output_of_prior_pics_flag is read and ignored: pictures are never discarded);
+ *   2. P joins W, with the order count the frame store records for it (0 after operation 5);
+ *   3. while |W| > R the member with the smallest order count is due (of equal counts - a broken stream - the one decoded first);
+ *   4. while no slot is free of both a reference and a member of W, and W is not empty, the member with the smallest order count
+ *      is due; only with W empty the oldest short-term reference is dropped, as without the option;
+ *   5. the next picture's slot is chosen among the free ones.
+ * A conforming stream's pictures come out with strictly ascending order counts between two flushes (step 1, p264parse_flush).  A
+ * stream that is not, or a depth below the stream's real one, gets every picture all the same, exactly once, in the order the
+ * rule gives: no error, no drop.
+ *
+ * A picture due with P may be P itself, and a slot named in P's output list may be the destination of the very next picture.
+ * The caller's contract makes that safe: export P's outputs behind P's reconstruct and before the next one, on the same HIP stream.
+ *
+ * A change of picture size or of the frame-store size (p264parse_generation moves) starts a new frame store: what still waited in
+ * the old one is not handed out. */
+enum { P264PARSE_OUT_IDR = 1, P264PARSE_OUT_MMCO5 = 2 };     /* p264parse_output_t.flags */
+#define P264PARSE_MAX_OUTPUTS (P264HIP_MAX_REFS + 1)        /* the most pictures one call hands out */
+typedef struct {
+    int slot;            /* of the stream's frame store: where the picture lies */
+    int poc;             /* its picture order count, as the frame store records it */
+    int decode_index;    /* which of the parser's completed pictures it is, from 0 */
+    int flags;           /* P264PARSE_OUT_* */
+} p264parse_output_t;
+/* on != 0 switches the output process on.  reorder_depth < 0 takes R from the stream; 0 .. 16 overrides it (the caller's low-delay
+ * switch: 0 hands every picture out with itself, in decode order).  Only before the first slice NAL, like
+ * p264parse_set_allocator; -1 (and nothing changed) later, or for a depth above 16. */
+int p264parse_set_output_order(p264parse *p, int on, int reorder_depth);
+/* The pictures that became due with the picture just completed, in output order, into out[0 .. max): returns how many there are
+ * (at most P264PARSE_MAX_OUTPUTS; 0 with the option off).  The list is valid until the next call that completes a picture. */
+int p264parse_outputs(const p264parse *p, p264parse_output_t *out, int max);
+/* All of W, ascending by order count, the same way; W is empty afterwards.  For the end of a stream. */
+int p264parse_flush(p264parse *p, p264parse_output_t *out, int max);
 
 /* Annex-B helper: find the next NAL unit in buf[*pos..size).  On success returns 1 and sets
  * *nal_off / *nal_len (start code and its leading zeros excluded, like p264decoder.c:259-325);
@@ -102,6 +148,12 @@ int p264parse_kat_bipred(int n0, const int *poc0, int n1, const int *poc1, int c
 int p264parse_kat_direct(int spatial, const int8_t *nb_ref, const int16_t *nb_mv, int col_intra, const int8_t *col_ref, const int16_t *col_mv,
                          int n0, const int *poc0, int poc1_0, int cur_poc, int n_col_list, const int *col_list_poc,
                          int8_t *out_ref, int16_t *out_mv);
+/* p264parse_kat_output_order: steps 1 - 3 of the output process above (the parser's own static functions; slots without bound, so
+ * step 4 never fires) on a hand-made sequence of n pictures in decode order with reorder depth `depth`: poc[i] the order count,
+ * flags[i] P264PARSE_OUT_IDR / P264PARSE_OUT_MMCO5 (such a picture counts with order count 0).  order[k] receives the decode index
+ * of the k-th picture handed out, due_after[k] the decode index of the picture it became due with, n for those of the final
+ * flush; n entries each.  0, or -1 on a bad argument. */
+int p264parse_kat_output_order(int depth, int n, const int *poc, const int *flags, int *order, int *due_after);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@
  * the threads already parse round r+1 - they do not stop at the end of a round: a stream's next picture may be parsed as
  * soon as its previous one is and the device has finished with the round before that (whose buffers the parser reuses).  Output pictures stay in HBM (the frame stores of p264hip); p264pipe_read_frame fetches the last one of a
  * stream to the host, p264pipe_export_last hands the last one of every stream on in device memory, and a sink
- * (p264pipe_set_sink) receives every round's pictures there while the run goes on.  There is no counterpart in the reference (its decoder is single-stream, single-threaded,
+ * (p264pipe_set_sink) receives every round's pictures there while the run goes on - in decode order, or in display order (p264pipe_set_output_order).  There is no counterpart in the reference (its decoder is single-stream, single-threaded,
  * p264decoder.c:164-381); the per-stream behaviour is that of p264_decoder_decode.
  *
  * device < 0 runs the parsers only (no GPU is touched): the host-side ceiling of the pipeline.
@@ -58,8 +58,8 @@ int  p264pipe_export_last(p264pipe *p, const p264hip_export_t *e, void *dst_dev,
  * round at k * frame_stride; fn is called on the thread that runs p264pipe_run, after the wait for the round's marker - the
  * buffer is complete - with the round's number, its n pictures' streams (ascending; a stream that has ended is absent) and the
  * buffer.  The buffer is written again n_bufs rounds later: whatever still reads it then (work the callback queued on another
- * stream) is the caller's to wait for.  Pictures arrive in DECODE order; display-order output (reordering B pictures by their
- * picture order counts) is not part of this.  A buf_bytes too small for n_streams pictures is refused here, a window that does
+ * stream) is the caller's to wait for.  Pictures arrive in DECODE order unless p264pipe_set_output_order says
+ * otherwise (below).  A buf_bytes too small for n_streams pictures is refused here, a window that does
  * not fit the streams' frame at the first round (p264pipe_run fails): never by writing short.  fn = NULL takes the sink away.
  * The description and the pointers are copied; the buffers are borrowed until the sink is replaced or the pipeline closed. */
 typedef void (*p264pipe_sink_fn)(void *user, int round, int n, const int *streams, void *dev);
@@ -71,6 +71,38 @@ int  p264pipe_set_sink(p264pipe *p, const p264hip_export_t *e, void *const *bufs
  * fn = NULL to either call takes it away.  p264pipe_export_last and p264pipe_set_sink behave as before. */
 int  p264pipe_export_last_resized(p264pipe *p, const p264hip_resize_t *r, void *dst_dev, size_t bytes);
 int  p264pipe_set_sink_resized(p264pipe *p, const p264hip_resize_t *r, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user);
+
+/* ---- pictures in OUTPUT (display) order ----
+ * on != 0: every stream's parser runs the output process of H.264 C.4 (p264parse_set_output_order, include/p264parse.h: the rule,
+ * D and R; reorder_depth < 0 takes each stream's own depth, 0 .. 16 overrides it for all of them - 0 is decode order, one picture
+ * per picture).  Pictures that are decoded but not yet due stay in their frame-store slots; the context gets the largest frame
+ * store any stream asks for (at most 17 slots).  Only before the first p264pipe_run; -1 afterwards.
+ *
+ * The sink - either kind, one sink as before - then receives DELIVERIES instead of rounds.  Behind round r's reconstruct the
+ * pictures that became due in round r go out in one export into bufs[d % n_bufs], d counting the deliveries of the run from 0:
+ * ordered by stream ascending and in output order within a stream, picture k at k * frame_stride.  fn(user, d, n, streams, dev) is
+ * called after the wait for the marker behind the export; `streams` may name a stream several times.  A round in which nothing
+ * became due makes no call.  A round with more due pictures than a buffer holds (the pictures that fit buf_bytes at frame_stride;
+ * setting the sink still asks for n_streams at least) goes out as several deliveries.  A buffer is never written again before
+ * its own callback has returned.  After the last round - the end of the streams, or max_pictures - every stream is flushed and what
+ * still waited is delivered the same way, ascending by order count within a stream.
+ *
+ * p264pipe_delivery, inside the callback: what the delivery's n pictures are (NULL and 0 outside).
+ *
+ * With device < 0 and output order on, p264pipe_set_sink is accepted (after p264pipe_set_output_order; bufs may be NULL, buf_bytes
+ * and the description still give the capacity) and fn is called with dev = NULL: nothing is exported, the order and the grouping are
+ * what the device pipeline would deliver.  With output order off the sink stays refused there, as before.
+ *
+ * p264pipe_export_last and p264pipe_read_frame keep meaning the last DECODED picture of a stream: its slot is intact after the
+ * final flush, since nothing is decoded behind it. */
+typedef struct {
+    int stream;          /* which input */
+    int poc;             /* picture order count, as the stream's frame store records it */
+    int decode_index;    /* which of the stream's decoded pictures, from 0 */
+    int flags;           /* P264PARSE_OUT_* of include/p264parse.h (bit 0: an IDR picture) */
+} p264pipe_output_t;
+int  p264pipe_set_output_order(p264pipe *p, int on, int reorder_depth);
+const p264pipe_output_t *p264pipe_delivery(p264pipe *p, int *n);
 void p264pipe_close(p264pipe *p);
 
 #ifdef __cplusplus

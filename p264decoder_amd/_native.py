@@ -96,6 +96,20 @@ class PipeStats(C.Structure):
                 ("submit_seconds", C.c_double), ("rounds", C.c_int), ("streams", C.c_int), ("threads", C.c_int), ("reserved", C.c_int),
                 ("bytes_uploaded", C.c_int64), ("wait_parse_seconds", C.c_double), ("wait_device_seconds", C.c_double)]
 
+class ParseOutput(C.Structure):
+    """p264parse_output_t"""
+    _fields_ = [("slot", C.c_int), ("poc", C.c_int), ("decode_index", C.c_int), ("flags", C.c_int)]
+
+
+class PipeOutput(C.Structure):
+    """p264pipe_output_t"""
+    _fields_ = [("stream", C.c_int), ("poc", C.c_int), ("decode_index", C.c_int), ("flags", C.c_int)]
+
+
+OUT_IDR, OUT_MMCO5 = 1, 2
+MAX_OUTPUTS = MAX_REFS + 1
+
+
 class Export(C.Structure):
     """p264hip_export_t"""
     _fields_ = [("format", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32),
@@ -203,6 +217,14 @@ def load(path=None):
     if hasattr(lib, "p264parse_crop"):
         lib.p264parse_crop.restype = C.c_int
         lib.p264parse_crop.argtypes = [C.c_void_p, ip, ip, ip, ip]
+    if hasattr(lib, "p264parse_set_output_order"):
+        lib.p264parse_set_output_order.restype = C.c_int
+        lib.p264parse_set_output_order.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        for f in ("p264parse_outputs", "p264parse_flush"):
+            getattr(lib, f).restype = C.c_int
+            getattr(lib, f).argtypes = [C.c_void_p, C.POINTER(ParseOutput), C.c_int]
+        lib.p264parse_kat_output_order.restype = C.c_int
+        lib.p264parse_kat_output_order.argtypes = [C.c_int, C.c_int, ip, ip, ip, ip]
     lib.p264_annexb_next.restype = C.c_int
     lib.p264_annexb_next.argtypes = [C.c_void_p, C.c_int64, i64p, i64p, i64p]
     # ---- p264hip.h
@@ -319,6 +341,11 @@ def load(path=None):
         lib.p264pipe_export_last_resized.argtypes = [C.c_void_p, C.POINTER(Resize), C.c_void_p, C.c_size_t]
         lib.p264pipe_set_sink_resized.restype = C.c_int
         lib.p264pipe_set_sink_resized.argtypes = [C.c_void_p, C.POINTER(Resize), C.POINTER(C.c_void_p), C.c_int, C.c_size_t, SINK_FN, C.c_void_p]
+    if hasattr(lib, "p264pipe_set_output_order"):
+        lib.p264pipe_set_output_order.restype = C.c_int
+        lib.p264pipe_set_output_order.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        lib.p264pipe_delivery.restype = C.POINTER(PipeOutput)
+        lib.p264pipe_delivery.argtypes = [C.c_void_p, ip]
     if path is None:
         _lib = lib
     return lib

@@ -45,6 +45,9 @@ typedef struct {
     int crop[4];
     int high;                                        /* one of the profiles whose SPS and PPS carry the High extensions (sps_is_high) */
     int cqm; cqm_t lists;                            /* seq_scaling_matrix_present_flag, and its lists resolved with fall-back rule A */
+    /* bitstream_restriction_flag of the VUI and the two of its fields that bound the output process (parse_vui); a VUI that is
+     * damaged counts as absent */
+    int restriction, num_reorder_frames, max_dec_frame_buffering;
 } sps_t;
 
 typedef struct {
@@ -108,6 +111,10 @@ typedef struct {
     int cqm; cqm_t lists;                     /* the picture's resolved scaling lists (its first slice's; cqm 0: every weight is 16) */
 } curpic_t;
 
+/* output order (H.264 C.4; p264parse_set_output_order): per frame-store slot, whether the picture in it waits for its output,
+ * with what the output entry will say of it */
+typedef struct { int waiting, poc, index, flags; } wait_t;
+
 struct p264parse {
     int opts;
     sps_t sps[32];
@@ -142,6 +149,12 @@ struct p264parse {
 
     dpb_frame_t dpb[P264HIP_MAX_REFS + 1];
     int cur_slot;
+    /* output order: off unless asked for.  out_depth: the caller's reorder depth (< 0: the stream's); reorder: the depth in
+     * force (R); wait: the set W; outs: the pictures that became due with the last completed picture, or the last flush */
+    int out_on, out_depth, reorder;
+    wait_t wait[P264HIP_MAX_REFS + 1];
+    p264parse_output_t outs[P264PARSE_MAX_OUTPUTS]; int n_outs;
+    int decode_index;                         /* completed pictures so far */
     int last_qp;                              /* never reset, like h->mb.i_last_qp (core/macroblock.c:1248-1252) */
     int qp_pred;                              /* conformant chain only (strict_qp) */
     int strict_qp;                            /* this slice: QP_Y = (QP_Y,PRED + mb_qp_delta + 52) % 52 (H.264 7.4.5) */
@@ -224,6 +237,67 @@ static int cqm_is_flat(const cqm_t *c)
     return 1;
 }
 
+/* hrd_parameters( ) (E.1.2), skipped; 0 where cpb_cnt_minus1 is out of range */
+static int skip_hrd(bitrd_t *b)
+{
+    const unsigned cpb_cnt = br_ue(b);
+    if (cpb_cnt > 31) return 0;
+    br_skip(b, 8);                                  /* bit_rate_scale, cpb_size_scale */
+    for (unsigned i = 0; i <= cpb_cnt; i++) { br_ue(b); br_ue(b); br_u1(b); }
+    br_skip(b, 20);                                 /* four lengths of five bits */
+    return 1;
+}
+/* vui_parameters( ) (E.1.1), read for one thing: num_reorder_frames and max_dec_frame_buffering of the bitstream restriction,
+ * which bound the output process (p264parse_set_output_order).  Everything in front of them is skipped.  Nothing here refuses a
+ * parameter set: a VUI that runs past the rbsp_stop_one_bit or holds a value out of range leaves the SPS as it is without one. */
+static void parse_vui(bitrd_t *b, sps_t *s)
+{
+    if (br_u1(b) && br_u(b, 8) == 255) br_skip(b, 32);          /* aspect ratio; Extended_SAR: sar_width, sar_height */
+    if (br_u1(b)) br_u1(b);                                     /* overscan */
+    if (br_u1(b)) { br_skip(b, 4); if (br_u1(b)) br_skip(b, 24); }   /* video signal type; colour description */
+    if (br_u1(b)) { br_ue(b); br_ue(b); }                       /* chroma sample location */
+    if (br_u1(b)) { br_skip(b, 32); br_skip(b, 32); br_u1(b); } /* timing: num_units_in_tick, time_scale, fixed_frame_rate_flag */
+    const int nal_hrd = (int)br_u1(b);
+    if (nal_hrd && !skip_hrd(b)) return;
+    const int vcl_hrd = (int)br_u1(b);
+    if (vcl_hrd && !skip_hrd(b)) return;
+    if (nal_hrd || vcl_hrd) br_u1(b);                           /* low_delay_hrd_flag */
+    br_u1(b);                                                   /* pic_struct_present_flag */
+    if (!br_u1(b)) return;                                      /* bitstream_restriction_flag */
+    br_u1(b);                                                   /* motion_vectors_over_pic_boundaries_flag */
+    for (int i = 0; i < 4; i++) br_ue(b);                       /* max_bytes_per_pic_denom, max_bits_per_mb_denom, log2_max_mv_length_horizontal / _vertical */
+    const unsigned reorder = br_ue(b), buffering = br_ue(b);
+    if ((long)br_consumed(b) > rbsp_stop_bit(b->buf, (int)b->size) || buffering > 16 || reorder > buffering) return;
+    s->restriction = 1; s->num_reorder_frames = (int)reorder; s->max_dec_frame_buffering = (int)buffering;
+}
+
+/* The frames the decoded picture buffer holds (D) and the reorder depth (R) of an SPS, for the output process: the bitstream
+ * restriction's where there is one; else MaxDpbFrames of the level (A.3.1 h, table A-1) and - nothing bounds the reordering - the
+ * same again, except under pic_order_cnt_type 2, whose output order is decode order (8.2.1.3). */
+static int sps_dpb_frames(const sps_t *s)
+{
+    static const struct { int level, mbs; } max_dpb_mbs[] = {
+        { 9, 396 }, { 10, 396 }, { 11, 900 }, { 12, 2376 }, { 13, 2376 }, { 20, 2376 }, { 21, 4752 }, { 22, 8100 }, { 30, 8100 }, { 31, 18000 },
+        { 32, 20480 }, { 40, 32768 }, { 41, 32768 }, { 42, 34816 }, { 50, 110400 }, { 51, 184320 }, { 52, 184320 } };
+    int d = 16;
+    if (s->restriction) d = s->max_dec_frame_buffering;
+    else for (size_t i = 0; i < sizeof max_dpb_mbs / sizeof max_dpb_mbs[0]; i++)
+        if (max_dpb_mbs[i].level == s->level_idc) { d = max_dpb_mbs[i].mbs / (s->mb_w * s->mb_h); break; }
+    if (d < s->num_ref_frames) d = s->num_ref_frames;
+    return d < 1 ? 1 : d > 16 ? 16 : d;                         /* (one frame at least: the frame store has two slots at least) */
+}
+static int sps_reorder_depth(const sps_t *s)
+{
+    return s->restriction ? s->num_reorder_frames : s->poc_type == 2 ? 0 : sps_dpb_frames(s);
+}
+/* slots of the frame store under an SPS: one per reference frame and the picture being decoded; with output order on, one per frame
+ * of the decoded picture buffer and that one */
+static int sps_slots(const p264parse *p, const sps_t *s)
+{
+    const int slots = (p->out_on ? sps_dpb_frames(s) : s->num_ref_frames) + 1;
+    return slots < 2 ? 2 : slots;
+}
+
 /* decoder/set.c:37-167 */
 static int parse_sps(p264parse *p, bitrd_t *b)
 {
@@ -276,8 +350,9 @@ static int parse_sps(p264parse *p, bitrd_t *b)
     if (!s->frame_mbs_only) br_u1(b);
     s->direct_8x8_inference = (int)br_u1(b);
     if (br_u1(b)) for (int i = 0; i < 4; i++) s->crop[i] = (int)br_ue(b);   /* left, right, top, bottom: never applied to what the parser delivers (A-Q1), reported by p264parse_crop */
-    br_u1(b);                                       /* vui_parameters_present: not parsed, like set.c:136-144 */
+    const int vui = (int)br_u1(b);                  /* vui_parameters_present (not parsed by set.c:136-144) */
     if (br_eof(b)) { ERR(p, "incomplete SPS"); return -1; }
+    if (vui) parse_vui(b, s);                       /* (behind the check: whatever the VUI holds, the set is accepted as it was without it) */
     /* untrusted input: H.264 7.4.2.1 ranges (the slice header reads fields of these widths; sizes drive every allocation) */
     if (s->log2_max_frame_num < 4 || s->log2_max_frame_num > 16 || (s->poc_type == 0 && (s->log2_max_poc_lsb < 4 || s->log2_max_poc_lsb > 16)) ||
         s->mb_w < 1 || s->mb_w > 1024 || s->mb_h < 1 || s->mb_h > 512 || s->num_ref_frames < 0 || s->num_ref_frames > 16) {
@@ -287,7 +362,7 @@ static int parse_sps(p264parse *p, bitrd_t *b)
         return -1;
     }
     s->valid = 1;
-    if ((int)id == p->active_sps && (old.mb_w != s->mb_w || old.mb_h != s->mb_h || old.num_ref_frames != s->num_ref_frames))
+    if ((int)id == p->active_sps && (old.mb_w != s->mb_w || old.mb_h != s->mb_h || old.num_ref_frames != s->num_ref_frames || (p->out_on && sps_slots(p, &old) != sps_slots(p, s))))
         p->active_sps = -1;                         /* same id, new geometry: force a context re-init */
     INFO(p, "p264amd: sps:%u profile:%d/%d poc:%d ref:%d %dx%d crop:%d-%d-%d-%d\n", id, profile, level,
          s->poc_type, s->num_ref_frames, s->mb_w, s->mb_h, s->crop[0], s->crop[1], s->crop[2], s->crop[3]);
@@ -373,8 +448,7 @@ static int init_context(p264parse *p, int sps_id, int pps_id)
     const sps_t *s = &p->sps[sps_id];
     free_context(p, 0);
     p->mb_w = s->mb_w; p->mb_h = s->mb_h; p->n_mb = s->mb_w * s->mb_h;
-    p->slots = s->num_ref_frames + 1;
-    if (p->slots < 2) p->slots = 2;
+    p->slots = sps_slots(p, s);
     size_t n = (size_t)p->n_mb;
     for (int i = 0; i < 2; i++) {
         picbuf_t *q = &p->buf[i];
@@ -413,6 +487,7 @@ static int init_context(p264parse *p, int sps_id, int pps_id)
     p->slice_of = (uint16_t *)malloc(n * sizeof(uint16_t));
     if (!p->nnz || !p->slice_of) return -1;
     memset(p->dpb, 0, sizeof p->dpb);
+    memset(p->wait, 0, sizeof p->wait);             /* (a new frame store: what waited in the old one is gone with it, include/p264parse.h) */
     p->cur_slot = 0;
     p->active_sps = sps_id; p->active_pps = pps_id;
     p->generation++;
@@ -686,6 +761,46 @@ static void implicit_weights(p264parse *p)
         }
 }
 
+/* ---- the output process (H.264 C.4.5.3; include/p264parse.h has the rule) ----
+ * the member of W that is due first: the smallest order count, of equal ones (a broken stream) the one decoded first; -1: W is empty */
+static int wait_first(const wait_t *w, int n)
+{
+    int at = -1;
+    for (int i = 0; i < n; i++)
+        if (w[i].waiting && (at < 0 || w[i].poc < w[at].poc || (w[i].poc == w[at].poc && w[i].index < w[at].index))) at = i;
+    return at;
+}
+static void wait_emit(wait_t *w, int slot, p264parse_output_t *out, int *n_out)
+{
+    p264parse_output_t *o = &out[(*n_out)++];
+    o->slot = slot; o->poc = w[slot].poc; o->decode_index = w[slot].index; o->flags = w[slot].flags;
+    w[slot].waiting = 0;
+}
+/* steps 1 - 3 for the picture completed in `slot` (n slots; *n_wait = |W|): everything is due in front of an IDR picture or one with
+ * operation 5, the picture joins W, and W shrinks to `depth` */
+static void output_steps(wait_t *w, int n, int *n_wait, int slot, int poc, int index, int flags, int depth, p264parse_output_t *out, int *n_out)
+{
+    if (flags & (P264PARSE_OUT_IDR | P264PARSE_OUT_MMCO5)) for (int i; (i = wait_first(w, n)) >= 0; (*n_wait)--) wait_emit(w, i, out, n_out);
+    w[slot].waiting = 1; w[slot].poc = poc; w[slot].index = index; w[slot].flags = flags;
+    for (++*n_wait; *n_wait > depth; (*n_wait)--) wait_emit(w, wait_first(w, n), out, n_out);
+}
+/* the picture in cur_slot is complete and marked: p->outs becomes what is due with it (steps 1 - 4), and the return the slot of
+ * the next picture (step 5), -1 where every slot holds a reference */
+static int output_process(p264parse *p, int had_mmco5)
+{
+    int n_wait = 0;
+    for (int i = 0; i < p->slots; i++) n_wait += p->wait[i].waiting;
+    p->n_outs = 0;
+    output_steps(p->wait, p->slots, &n_wait, p->cur_slot, p->dpb[p->cur_slot].poc, p->decode_index,
+                 (p->pic.is_idr ? P264PARSE_OUT_IDR : 0) | (had_mmco5 ? P264PARSE_OUT_MMCO5 : 0), p->reorder, p->outs, &p->n_outs);
+    for (;;) {
+        for (int i = 0; i < p->slots; i++) if (!p->dpb[i].used && !p->wait[i].waiting) return i;
+        const int first = wait_first(p->wait, p->slots);        /* C.4.5.3 "bumping": no empty frame buffer */
+        if (first < 0) return -1;
+        wait_emit(p->wait, first, p->outs, &p->n_outs);
+    }
+}
+
 /* Reference picture marking (H.264 8.2.5; the reference implements the sliding window only, decoder/lists.c:152-228) and
  * the choice of the next slot. */
 static void finish_picture_marking(p264parse *p)
@@ -750,9 +865,11 @@ static void finish_picture_marking(p264parse *p)
         p->prev_poc_lsb = had_mmco5 ? 0 : first->poc_lsb;
     }
     if (sps->poc_type == 2) { p->frame_num_offset = had_mmco5 ? 0 : frame_num_offset_of(p, sps, first, p->pic.is_idr); p->prev_frame_num = had_mmco5 ? 0 : first->frame_num; }
-    /* next picture goes into a slot that holds no reference */
+    /* next picture goes into a slot that holds no reference - nor, with output order on, a picture that waits */
     int next = -1;
-    for (int i = 0; i < p->slots; i++) if (!p->dpb[i].used) { next = i; break; }
+    if (p->out_on) next = output_process(p, had_mmco5);
+    else for (int i = 0; i < p->slots; i++) if (!p->dpb[i].used) { next = i; break; }
+    p->decode_index++;
     if (next < 0) {                               /* a stream that keeps more pictures than num_ref_frames: drop the oldest short-term one */
         int oldest = -1, oldest_num = 0;
         for (int i = 0; i < p->slots; i++) {
@@ -1603,11 +1720,11 @@ static int slice_header_and_context(p264parse *p, bitrd_t *b, int nal_type, int 
     if (rc > 0) return rc;
     const pps_t *pps = &p->pps[sh->pps_id];
     const sps_t *sps = &p->sps[pps->sps_id];
-    int slots = sps->num_ref_frames + 1;
-    if (slots < 2) slots = 2;
+    const int slots = sps_slots(p, sps);
     if (p->active_sps < 0 || !p->buf[0].mb || sps->mb_w != p->mb_w || sps->mb_h != p->mb_h || slots != p->slots) {
         if (init_context(p, pps->sps_id, sh->pps_id) < 0) { ERR(p, "out of memory"); return REFUSE_SLICE; }
     } else { p->active_sps = pps->sps_id; p->active_pps = sh->pps_id; }
+    if (p->out_on) p->reorder = p->out_depth >= 0 ? p->out_depth : sps_reorder_depth(sps);
     return 0;
 }
 
@@ -1625,7 +1742,7 @@ static int open_picture(p264parse *p, const slice_t *sh, int nal_type, int nal_r
     c->is_idr = nal_type == NAL_SLICE_IDR; c->ref_idc = nal_ref_idc;
     if (c->is_idr) {                              /* p264_slice_idr, decoder/decoder.c:43-64 */
         for (int i = 0; i < p->slots; i++) p->dpb[i].used = 0;
-        p->cur_slot = 0;
+        if (!p->out_on) p->cur_slot = 0;          /* (output order: pictures from before may still wait, slot 0 among them - cur_slot is free) */
     }
     c->first = *sh;
     c->type = sh->type;
@@ -1819,6 +1936,28 @@ void p264parse_set_allocator(p264parse *p, void *(*alloc)(size_t bytes), void (*
     p->alloc = alloc; p->release = release;
 }
 
+int p264parse_set_output_order(p264parse *p, int on, int reorder_depth)
+{
+    if (!p || p->n_mb || reorder_depth > P264HIP_MAX_REFS) return -1;      /* only before the first context is built */
+    p->out_on = on != 0; p->out_depth = reorder_depth < 0 ? -1 : reorder_depth;
+    return 0;
+}
+
+int p264parse_outputs(const p264parse *p, p264parse_output_t *out, int max)
+{
+    if (!p || !p->out_on || (max > 0 && !out)) return 0;
+    for (int i = 0; i < p->n_outs && i < max; i++) out[i] = p->outs[i];
+    return p->n_outs;
+}
+
+int p264parse_flush(p264parse *p, p264parse_output_t *out, int max)
+{
+    if (!p || !p->out_on || (max > 0 && !out)) return 0;
+    p->n_outs = 0;
+    for (int i; (i = wait_first(p->wait, p->slots)) >= 0; ) wait_emit(p->wait, i, p->outs, &p->n_outs);
+    return p264parse_outputs(p, out, max);
+}
+
 void p264parse_close(p264parse *p)
 {
     if (!p) return;
@@ -1988,4 +2127,21 @@ int p264parse_kat_direct(int spatial, const int8_t *nb_ref, const int16_t *nb_mv
     memcpy(out_ref, d.ref, sizeof d.ref); memcpy(out_mv, d.mv, sizeof d.mv);
     kat_free(p);
     return 0;
+}
+
+int p264parse_kat_output_order(int depth, int n, const int *poc, const int *flags, int *order, int *due_after)
+{
+    if (depth < 0 || n < 0 || (n && (!poc || !flags || !order || !due_after))) return -1;
+    wait_t *w = (wait_t *)calloc((size_t)n + 1, sizeof *w);
+    p264parse_output_t *out = (p264parse_output_t *)malloc(((size_t)n + 1) * sizeof *out);
+    if (!w || !out) { free(w); free(out); return -1; }
+    int n_wait = 0, done = 0;
+    for (int i = 0; i <= n; i++) {                              /* picture i in a slot of its own; i = n: the flush */
+        int n_out = 0;
+        if (i < n) output_steps(w, n, &n_wait, i, (flags[i] & P264PARSE_OUT_MMCO5) ? 0 : poc[i], i, flags[i], depth, out, &n_out);
+        else for (int k; (k = wait_first(w, n)) >= 0; ) wait_emit(w, k, out, &n_out);
+        for (int k = 0; k < n_out; k++, done++) { order[done] = out[k].decode_index; due_after[done] = i; }
+    }
+    free(w); free(out);
+    return done == n ? 0 : -1;
 }

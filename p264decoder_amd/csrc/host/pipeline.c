@@ -8,6 +8,10 @@
  * The main thread waits for the last task of round r, hands the pictures to the GPU - asynchronous uploads out of the parsers'
  * pinned double buffers, one batched reconstruct - and waits for the marker behind them: by then the threads are well into
  * round r + 1, and that wait is what lets them into round r + 2.
+ *
+ * Output order (p264pipe_set_output_order): the parsers keep pictures that are not yet due in their slots, the task that completes
+ * a picture copies the list of those that became due with it (the parser's own list does not survive its next picture, and the
+ * parsers run ahead of the device), and the sink receives deliveries of due pictures instead of rounds (deliver).
  */
 #define _GNU_SOURCE
 #include <pthread.h>
@@ -39,6 +43,7 @@ struct p264pipe {
     pthread_mutex_t mu; pthread_cond_t go, idle, turn;
     int turn_waiters;                    /* (under mu) threads blocked on `turn`: a stream's previous picture is still being parsed */
     int generation, busy, quit, max_pictures;
+    int started_run;                     /* p264pipe_run has been called: the parsers' options are settled */
     /* one run: tasks t = round * n_streams + stream, taken in order */
     long long next_task;                 /* (atomic) */
     int done_rounds;                     /* rounds the device has finished with (under mu; waited for through `go`) */
@@ -52,6 +57,13 @@ struct p264pipe {
     /* the sink (p264pipe_set_sink; pipeline_sink.h): every round's pictures exported into the caller's device buffers by sink_export
      * with the description sink_desc (a copy) */
     p264pipe_export_fn sink_export; void *sink_desc; void **sink_bufs; int sink_n_bufs; size_t sink_bytes; p264pipe_sink_fn sink_fn; void *sink_user;
+    int sink_capacity;                   /* pictures a sink buffer holds at its frame stride */
+    /* output order: on / the reorder depth for every parser (< 0: the stream's); what became due with the picture a round's task
+     * produced; the delivery being handed to the sink (p264pipe_delivery) and how many there were */
+    int out_on, out_depth;
+    p264parse_output_t *round_out[2]; int *round_n_out[2];   /* [round parity][stream][P264PARSE_MAX_OUTPUTS], [round parity][stream] */
+    int *due_sts, *due_slots; p264pipe_output_t *due;        /* [n_streams * P264PARSE_MAX_OUTPUTS] the pictures due in a round, or at the flush */
+    const p264pipe_output_t *delivery; int delivery_n, deliveries;
 };
 
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
@@ -92,6 +104,7 @@ static void *worker(void *arg)
             p->st[s].pic = annexb_reader_next(&p->st[s].rd, p->max_pictures);
             spent += now_s() - t0;
             p->round_pic[R & 1][s] = p->st[s].pic;
+            if (p->out_on) p->round_n_out[R & 1][s] = p->st[s].pic ? p264parse_outputs(p->st[s].rd.parser, p->round_out[R & 1] + (size_t)s * P264PARSE_MAX_OUTPUTS, P264PARSE_MAX_OUTPUTS) : 0;
             __atomic_store_n(&p->parsed[s], R + 1, __ATOMIC_RELEASE);
             const int failed = annexb_reader_failed(&p->st[s].rd);
             pthread_mutex_lock(&p->mu);
@@ -164,8 +177,12 @@ p264pipe *p264pipe_open(int device, int n_streams, int n_threads)
     p->ids = (int *)malloc(sizeof(int) * (size_t)n_streams); p->sts = (int *)malloc(sizeof(int) * (size_t)n_streams);
     p->dsts = (int *)malloc(sizeof(int) * (size_t)n_streams);
     p->pics = (const p264hip_picture_t **)malloc(sizeof(void *) * (size_t)n_streams);
+    const size_t due = (size_t)n_streams * P264PARSE_MAX_OUTPUTS;
+    for (int i = 0; i < 2; i++) { p->round_out[i] = (p264parse_output_t *)calloc(due, sizeof(p264parse_output_t)); p->round_n_out[i] = (int *)calloc((size_t)n_streams, sizeof(int)); }
+    p->due_sts = (int *)malloc(sizeof(int) * due); p->due_slots = (int *)malloc(sizeof(int) * due); p->due = (p264pipe_output_t *)malloc(sizeof(p264pipe_output_t) * due);
     pthread_mutex_init(&p->mu, NULL); pthread_cond_init(&p->go, NULL); pthread_cond_init(&p->idle, NULL); pthread_cond_init(&p->turn, NULL);
-    if (!p->st || !p->threads || !p->parsed || !p->round_pic[0] || !p->round_pic[1] || !p->ids || !p->sts || !p->dsts || !p->pics) { p264pipe_close(p); return NULL; }
+    if (!p->st || !p->threads || !p->parsed || !p->round_pic[0] || !p->round_pic[1] || !p->ids || !p->sts || !p->dsts || !p->pics ||
+        !p->round_out[0] || !p->round_out[1] || !p->round_n_out[0] || !p->round_n_out[1] || !p->due_sts || !p->due_slots || !p->due) { p264pipe_close(p); return NULL; }
     /* picture buffers in pinned host memory when they are uploaded (P264AMD_PIPE_PINNED=0 / 1 forces either kind: experiments) */
     const char *pin = getenv("P264AMD_PIPE_PINNED");
     const int pinned = pin ? atoi(pin) != 0 : device >= 0;
@@ -202,18 +219,74 @@ static int collect_round(p264pipe *p, int r)
     }
     return n;
 }
-/* the device context, once: geometry is known after the first picture */
-static int ensure_context(p264pipe *p)
+/* the device context, once: geometry is known after the first picture (n: pictures of the round) */
+static int ensure_context(p264pipe *p, int n)
 {
     if (p->device < 0 || p->ctx) return 0;
     p->mb_w = p->pics[0]->mb_w; p->mb_h = p->pics[0]->mb_h; p->slots = p264parse_slots(p->st[p->sts[0]].rd.parser);
+    /* with output order on a stream's frame store follows its own buffering (VUI, level): the context gets the largest */
+    for (int k = 1; p->out_on && k < n; k++) { const int s = p264parse_slots(p->st[p->sts[k]].rd.parser); if (s > p->slots) p->slots = s; }
     if (p264hip_create(&p->ctx, p->device, p->mb_w, p->mb_h, p->n_streams, p->slots, p->n_streams * 2)) {
         fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); return -1;
     }
     return 0;
 }
+/* ---- output order ----
+ * one stream's due pictures appended to the list of due pictures */
+static int add_due(p264pipe *p, int n, int stream, const p264parse_output_t *out, int n_out)
+{
+    for (int k = 0; k < n_out; k++, n++) {
+        p->due_sts[n] = stream; p->due_slots[n] = out[k].slot;
+        p->due[n].stream = stream; p->due[n].poc = out[k].poc; p->due[n].decode_index = out[k].decode_index; p->due[n].flags = out[k].flags;
+    }
+    return n;
+}
+/* the pictures that became due in round r, by stream and in output order within a stream; returns how many */
+static int collect_due(p264pipe *p, int r)
+{
+    int n = 0;
+    for (int i = 0; i < p->n_streams; i++)
+        if (p->round_pic[r & 1][i]) n = add_due(p, n, i, p->round_out[r & 1] + (size_t)i * P264PARSE_MAX_OUTPUTS, p->round_n_out[r & 1][i]);
+    return n;
+}
+/* ... and what every stream's parser still holds, at the end of a run (the threads have left their task loop) */
+static int collect_flush(p264pipe *p)
+{
+    int n = 0;
+    p264parse_output_t out[P264PARSE_MAX_OUTPUTS];
+    for (int i = 0; i < p->n_streams; i++) n = add_due(p, n, i, out, p264parse_flush(p->st[i].rd.parser, out, P264PARSE_MAX_OUTPUTS));
+    return n;
+}
+/* The n due pictures to the sink, as many deliveries as the buffers' capacity makes of them: delivery d is exported into
+ * bufs[d % n_bufs] behind everything queued so far (the round's reconstruct), and fn is called after the wait for the marker
+ * behind the export - before the next delivery is exported, so no buffer is written before its callback has returned.  Without a
+ * device nothing is exported and fn gets dev = NULL. */
+static int deliver(p264pipe *p, int n, p264pipe_stats_t *S)
+{
+    for (int at = 0; at < n; ) {
+        const int k = n - at < p->sink_capacity ? n - at : p->sink_capacity;
+        void *buf = p->ctx ? p->sink_bufs[p->deliveries % p->sink_n_bufs] : NULL;
+        if (p->ctx) {
+            const double s0 = now_s();
+            int rc = p->sink_export(p->ctx, p->due_sts + at, p->due_slots + at, k, p->sink_desc, buf, p->sink_bytes);
+            const int marker = rc ? -1 : p264hip_marker(p->ctx);
+            S->submit_seconds += now_s() - s0;
+            if (rc || marker < 0) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); return -1; }
+            const double w0 = now_s();
+            if (p264hip_marker_wait(p->ctx, marker)) return -1;
+            S->wait_device_seconds += now_s() - w0;
+        }
+        p->delivery = p->due + at; p->delivery_n = k;
+        p->sink_fn(p->sink_user, p->deliveries++, k, p->due_sts + at, buf);
+        p->delivery = NULL; p->delivery_n = 0;
+        at += k;
+    }
+    return 0;
+}
+
 /* round r's n pictures to the device: uploads, one batched reconstruct, the sink's export behind the round's kernels, and the
- * wait for the marker behind all of it */
+ * wait for the marker behind all of it.  With output order on the sink gets the round's due pictures instead (deliver), behind
+ * that wait. */
 static int submit_round(p264pipe *p, int r, int n, p264pipe_stats_t *S)
 {
     const double s0 = now_s();
@@ -224,7 +297,7 @@ static int submit_round(p264pipe *p, int r, int n, p264pipe_stats_t *S)
         else S->bytes_uploaded += (int64_t)p->mb_w * p->mb_h * (16 + 64 + 4 + 16) + (int64_t)p->pics[k]->n_coef_blocks * 32;
     }
     if (!rc && p264hip_reconstruct(p->ctx, p->ids, p->sts, n)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
-    void *sink = p->sink_fn ? p->sink_bufs[r % p->sink_n_bufs] : NULL;       /* the round's pictures, behind its kernels */
+    void *sink = p->sink_fn && !p->out_on ? p->sink_bufs[r % p->sink_n_bufs] : NULL;       /* the round's pictures, behind its kernels */
     if (!rc && sink && p->sink_export(p->ctx, p->sts, p->dsts, n, p->sink_desc, sink, p->sink_bytes)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
     int marker = -1;
     if (!rc) { marker = p264hip_marker(p->ctx); if (marker < 0) rc = -1; }
@@ -242,7 +315,9 @@ int p264pipe_run(p264pipe *p, int max_pictures, p264pipe_stats_t *stats)
 {
     if (!p) return -1;
     for (int i = 0; i < p->n_streams; i++) if (!p->st[i].rd.in) { fprintf(stderr, "p264pipe_run: stream %d has no input\n", i); return -1; }
-    p->max_pictures = max_pictures; p->parse_seconds = 0;
+    p->max_pictures = max_pictures; p->parse_seconds = 0; p->deliveries = 0;
+    if (!p->started_run) for (int i = 0; i < p->n_streams; i++) (void)p264parse_set_output_order(p->st[i].rd.parser, p->out_on, p->out_depth);
+    p->started_run = 1;
     p264pipe_stats_t S; memset(&S, 0, sizeof S);                /* (the main thread's waits: P264AMD_PIPE_DEBUG=1 prints them) */
     int rc = 0;
     const double t0 = now_s();
@@ -252,10 +327,13 @@ int p264pipe_run(p264pipe *p, int max_pictures, p264pipe_stats_t *stats)
         const int n = collect_round(p, r);
         if (n == 0 || rc) break;
         S.rounds++; S.pictures += n;
-        if ((rc = ensure_context(p)) || (p->ctx && (rc = submit_round(p, r, n, &S)))) break;
+        if ((rc = ensure_context(p, n)) || (p->ctx && (rc = submit_round(p, r, n, &S)))) break;
+        if (p->out_on && p->sink_fn && (rc = deliver(p, collect_due(p, r), &S))) break;
         rounds_done(p, r);
     }
     end_run(p);
+    /* the end of the streams (or max_pictures): what still waits is due now */
+    if (p->out_on && !rc) { const int n = collect_flush(p); if (p->sink_fn) rc = deliver(p, n, &S); }
     if (p->ctx && p264hip_sync(p->ctx)) { fprintf(stderr, "p264pipe_run: %s\n", p264hip_last_error()); rc = -1; }
     S.seconds = now_s() - t0; S.parse_seconds = p->parse_seconds; S.streams = p->n_streams; S.threads = p->n_threads;
     if (getenv("P264AMD_PIPE_DEBUG"))
@@ -327,19 +405,24 @@ void p264pipe_sink_remove_(p264pipe *p)
 int p264pipe_sink_install_(p264pipe *p, const char *who, p264pipe_export_fn ex, const void *desc, size_t desc_bytes, int64_t bytes, int64_t frame_stride,
                            void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user)
 {
-    if (!p || !ex || !desc || !fn || !bufs || n_bufs < 1 || bytes < 1) return -1;
+    /* (parsers only: nothing is exported, so there need be no buffers - buf_bytes still says how many pictures a delivery holds) */
+    const int no_bufs = p && p->device < 0 && !bufs;
+    if (no_bufs) n_bufs = 0;
+    if (!p || !ex || !desc || !fn || (!no_bufs && (!bufs || n_bufs < 1)) || bytes < 1) return -1;
     for (int i = 0; i < n_bufs; i++) if (!bufs[i]) return -1;
     /* every round may bring a picture of every stream */
     const int64_t stride = frame_stride ? frame_stride : bytes;
     if (stride > (INT64_MAX - bytes) / p->n_streams || (uint64_t)buf_bytes < (uint64_t)(p->n_streams - 1) * (uint64_t)stride + (uint64_t)bytes) {
         fprintf(stderr, "%s: %d pictures %lld bytes apart do not fit %zu bytes\n", who, p->n_streams, (long long)stride, buf_bytes); return -1;
     }
-    void **copy = (void **)malloc(sizeof(void *) * (size_t)n_bufs);
+    void **copy = (void **)malloc(sizeof(void *) * (size_t)(n_bufs ? n_bufs : 1));
     void *d = malloc(desc_bytes);
     if (!copy || !d) { free(copy); free(d); return -1; }
     memcpy(copy, bufs, sizeof(void *) * (size_t)n_bufs);
     memcpy(d, desc, desc_bytes);
     p264pipe_sink_remove_(p);
+    const uint64_t more = ((uint64_t)buf_bytes - (uint64_t)bytes) / (uint64_t)stride;      /* pictures behind the first */
+    p->sink_capacity = more < (uint64_t)INT32_MAX ? (int)more + 1 : INT32_MAX;
     p->sink_export = ex; p->sink_desc = d; p->sink_bufs = copy; p->sink_n_bufs = n_bufs; p->sink_bytes = buf_bytes; p->sink_fn = fn; p->sink_user = user;
     return 0;
 }
@@ -348,13 +431,26 @@ int p264pipe_set_sink(p264pipe *p, const p264hip_export_t *e, void *const *bufs,
 {
     if (!p) return -1;
     if (!fn) { p264pipe_sink_remove_(p); return 0; }
-    if (p->device < 0 || !e || !bufs || n_bufs < 1) return -1;
+    if ((p->device < 0 && !p->out_on) || !e || (p->device >= 0 && (!bufs || n_bufs < 1))) return -1;
     /* (the frame itself is known at the first round: p264hip_export_frames checks the window) */
     const int64_t bytes = p264hip_export_frame_bytes(e);
     if (bytes < 0 || (p->mb_w && p264hip_export_check(e, p->mb_w, p->mb_h)) || e->frame_stride < 0 || (e->frame_stride && e->frame_stride < bytes)) {
         fprintf(stderr, "p264pipe_set_sink: bad export description\n"); return -1;
     }
     return p264pipe_sink_install_(p, "p264pipe_set_sink", export_plain, e, sizeof *e, bytes, e->frame_stride, bufs, n_bufs, buf_bytes, fn, user);
+}
+
+int p264pipe_set_output_order(p264pipe *p, int on, int reorder_depth)
+{
+    if (!p || p->started_run || reorder_depth > P264HIP_MAX_REFS) return -1;
+    p->out_on = on != 0; p->out_depth = reorder_depth < 0 ? -1 : reorder_depth;
+    return 0;
+}
+
+const p264pipe_output_t *p264pipe_delivery(p264pipe *p, int *n)
+{
+    if (n) *n = p ? p->delivery_n : 0;
+    return p ? p->delivery : NULL;
 }
 
 int64_t p264pipe_stream_pictures(p264pipe *p, int stream)
@@ -372,6 +468,8 @@ void p264pipe_close(p264pipe *p)
     if (p->ctx) p264hip_destroy(p->ctx);
     pthread_mutex_destroy(&p->mu); pthread_cond_destroy(&p->go); pthread_cond_destroy(&p->idle); pthread_cond_destroy(&p->turn);
     free(p->parsed); free((void *)p->round_pic[0]); free((void *)p->round_pic[1]);
+    for (int i = 0; i < 2; i++) { free(p->round_out[i]); free(p->round_n_out[i]); }
+    free(p->due_sts); free(p->due_slots); free(p->due);
     free(p->sink_bufs); free(p->sink_desc); free(p->ids); free(p->sts); free(p->dsts); free((void *)p->pics);
     free(p->st); free(p->threads); free(p);
 }

@@ -13,8 +13,9 @@ typedef int (*p264pipe_export_fn)(p264hip_ctx *ctx, const int *streams, const in
 /* device (-1: parsers only) and, once the first round has run, the frame in macroblocks (0 x 0 before) */
 void p264pipe_geometry_(const p264pipe *p, int *device, int *mb_w, int *mb_h);
 /* the pipeline's ONE sink becomes this one: pictures of `bytes` bytes, frame_stride (0: bytes) apart, exported by ex with a copy of
- * desc into bufs[round % n_bufs].  -1 (and the sink as it was) if a buffer is null or too small for a picture of every stream.
- * The caller has checked the description. */
+ * desc into bufs[round % n_bufs] - with output order on, a delivery's pictures into bufs[delivery % n_bufs], as many as fit buf_bytes.
+ * -1 (and the sink as it was) if a buffer is null or too small for a picture of every stream.  On a pipeline without a device bufs
+ * may be NULL: nothing is exported there.  The caller has checked the description. */
 int p264pipe_sink_install_(p264pipe *p, const char *who, p264pipe_export_fn ex, const void *desc, size_t desc_bytes, int64_t bytes, int64_t frame_stride,
                            void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user);
 /* no sink */

@@ -16,6 +16,7 @@ class Pipeline:
         if not self.h:
             raise RuntimeError("p264pipe_open failed (no HIP device? the reconstruction has no CPU fallback; device=-1 parses only)")
         self._sink, self._sink_error = None, None
+        self.device = device
         for i, b in enumerate(self._bufs):
             if self.lib.p264pipe_set_input(self.h, i, b, len(b)):
                 raise RuntimeError("p264pipe_set_input(%d) failed" % i)
@@ -29,6 +30,19 @@ class Pipeline:
         if rc:
             raise RuntimeError("p264pipe_run failed")
         return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def set_output_order(self, depth=None):
+        """Deliver pictures in display order (p264pipe_set_output_order; before the first run()): the sink's callback then gets
+        deliveries of the pictures that became due instead of rounds, and delivery() says which they are.  depth None: every
+        stream's own reorder depth; 0 .. 16 overrides it (0: decode order, one picture per picture)."""
+        if self.lib.p264pipe_set_output_order(self.h, 1, -1 if depth is None else int(depth)):
+            raise RuntimeError("p264pipe_set_output_order refused (after run(), or a depth above 16)")
+
+    def delivery(self):
+        """Inside a sink's callback with output order on: [(stream, poc, decode_index, idr)] of the delivery's pictures."""
+        n = C.c_int()
+        d = self.lib.p264pipe_delivery(self.h, C.byref(n))
+        return [(d[i].stream, d[i].poc, d[i].decode_index, bool(d[i].flags & N.OUT_IDR)) for i in range(n.value)]
 
     def pictures(self, stream):
         return self.lib.p264pipe_stream_pictures(self.h, stream)
@@ -87,20 +101,28 @@ class Pipeline:
     def set_sink(self, fmt, callback, depth=2, crop=None, matrix="bt601", full_range=False, pitch=0, buffers=None):
         """callback(round, streams, dev, bytes) for every round of run(): `streams` lists the round's streams, picture k of the round
         lies at dev + k * bytes in device memory, in format `fmt`, cropped to `crop` (None: the display window of stream 0).  `depth`
-        buffers take turns: one is written again `depth` rounds later.  Pictures arrive in decode order.  buffers: (pointer, bytes)
-        pairs of the caller's device memory; None allocates torch tensors.  The wrapper keeps callback and buffers alive."""
+        buffers take turns: one is written again `depth` rounds later.  Pictures arrive in decode order - after set_output_order() in
+        display order: callback(delivery, streams, dev, bytes) for every delivery, `streams` may then name a stream several times and
+        delivery() tells the pictures.  buffers: (pointer, bytes)
+        pairs of the caller's device memory; None allocates torch tensors.  The wrapper keeps callback and buffers alive.
+        On a pipeline without a device (device=-1) a sink is taken only after set_output_order(): nothing is exported, dev is None,
+        and of `buffers` only the bytes count (how many pictures a delivery holds; None: one per stream)."""
         n = len(self._bufs)
         e = N.export_desc(fmt, self._window(crop), None, matrix, full_range, pitch)
         per = self.lib.p264hip_export_frame_bytes(C.byref(e))
         if per < 0:
             raise RuntimeError("set_sink: p264hip_export_frame_bytes refuses the description")
         keep = None
-        if buffers is None:
+        if self.device < 0:                               # parsers only: no memory, the bytes alone say what a delivery holds
+            cap = min(b[1] for b in buffers) if buffers else n * per
+            buffers, ptrs = [], None
+        elif buffers is None:
             torch = N.import_torch()
             keep = [torch.empty(n * per, dtype=torch.uint8, device="cuda") for _ in range(depth)]
             buffers = [(t.data_ptr(), t.numel()) for t in keep]
-        ptrs = (C.c_void_p * len(buffers))(*[b[0] for b in buffers])
-        cap = min(b[1] for b in buffers)
+        if self.device >= 0:
+            ptrs = (C.c_void_p * len(buffers))(*[b[0] for b in buffers])
+            cap = min(b[1] for b in buffers)
 
         def trampoline(user, rnd, k, streams, dev):
             try:                                          # (an exception cannot cross the C frames: run() raises it)
@@ -138,7 +160,8 @@ class Pipeline:
                          pitch=0, buffers=None, *, filter="bilinear"):
         """set_sink with a resize on it (p264pipe_set_sink_resized): callback(round, streams, dev, bytes) for every round of run(),
         picture k of the round at dev + k * bytes, the window `crop` (None: the display window of stream 0) resized to size = (width,
-        height), as `fmt` / `dtype` with scale, bias and `filter` as HipReconstructor.export_resized has them.  It replaces a sink set before."""
+        height), as `fmt` / `dtype` with scale, bias and `filter` as HipReconstructor.export_resized has them.  It replaces a sink set before.
+        After set_output_order() the callback gets deliveries in display order, as set_sink's does."""
         n = len(self._bufs)
         r = N.resize_desc(fmt, size, self._window(crop), None, dtype, scale, bias, matrix, full_range, pitch, filter=filter)
         per = self.lib.p264hip_resize_frame_bytes(C.byref(r))

@@ -107,6 +107,25 @@ class Parser:
     def slots(self):
         return self.lib.p264parse_slots(self.h)
 
+    def set_output_order(self, depth=None):
+        """Switch the output process on (p264parse_set_output_order; before the first slice): pictures keep their slots until they
+        are due for display, slots becomes D + 1.  depth None: the stream's reorder depth; 0 .. 16 overrides it (0: decode order)."""
+        if self.lib.p264parse_set_output_order(self.h, 1, -1 if depth is None else int(depth)):
+            raise P264Error("p264parse_set_output_order refused (after the first slice, or a depth above 16)")
+
+    def _outputs(self, call):
+        out = (N.ParseOutput * N.MAX_OUTPUTS)()
+        n = call(self.h, out, N.MAX_OUTPUTS)
+        return [(o.slot, o.poc, o.decode_index, bool(o.flags & N.OUT_IDR)) for o in out[:n]]
+
+    def outputs(self):
+        """[(slot, poc, decode_index, idr)]: the pictures that became due with the picture feed() just returned, in output order"""
+        return self._outputs(self.lib.p264parse_outputs)
+
+    def flush(self):
+        """[(slot, poc, decode_index, idr)]: every picture that still waits, ascending by order count (the end of a stream)"""
+        return self._outputs(self.lib.p264parse_flush)
+
     @property
     def crop(self):
         """(left, top, width, height) of the active SPS's display window in luma samples (p264parse_crop); None before the first slice."""

@@ -92,6 +92,13 @@
  *                            the PPS, so that both kinds of fall-back of rule B occur); [--dump-cqm f] per picture the 224 resolved
  *                            weights the writer intends (4x4 lists 0 .. 5, 8x8 lists 6, 7, scan order).  The writer draws levels and does
  *                            not quantise: nothing else changes, and without --cqm the streams are what they were, byte for byte.
+ *            [--vui-reorder N[:full]]  the SPS carries a VUI (vui_parameters_present_flag 1) with bitstream_restriction_flag 1,
+ *                            num_reorder_frames N and max_dec_frame_buffering max(N, --refs); with :full every optional group in front
+ *                            of the restriction too - the extended sample aspect ratio, overscan, video signal type with colour
+ *                            description, chroma sample location, timing, NAL and VCL HRD parameters with cpb_cnt_minus1 1, and
+ *                            pic_struct_present_flag - for a parser's skipping code.  A tight N for --bframes streams is 1 (only the P
+ *                            picture precedes its B pictures in decoding and follows them in output).  Nothing else changes, and
+ *                            without the option the streams are what they were, byte for byte.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -1149,6 +1156,32 @@ static void cqm_plan(void)
     else { memcpy(cqm_sps, full, sizeof full); memcpy(cqm_pps, over, sizeof over); cqm_resolve_w(over, seq, cqm_final); }
 }
 
+/* --vui-reorder N[:full]: vui_parameters( ) (E.1.1) with the bitstream restriction; with :full every optional group in front of it
+ * (no field holds two zero bytes in a row: the stream needs no emulation prevention inside them) */
+static int opt_vui_reorder = -1, opt_vui_full = 0;
+static void put_hrd(bw_t *b)
+{
+    bw_ue(b, 1); bw_put(b, 4, 3); bw_put(b, 4, 5);              /* cpb_cnt_minus1 = 1, bit_rate_scale, cpb_size_scale */
+    for (int i = 0; i < 2; i++) { bw_ue(b, (uint32_t)(700 + i)); bw_ue(b, (uint32_t)(900 + i)); bw_put(b, 1, (uint32_t)i); }
+    bw_put(b, 5, 23); bw_put(b, 5, 23); bw_put(b, 5, 23); bw_put(b, 5, 24);
+}
+static void put_vui(bw_t *b)
+{
+    const int full = opt_vui_full;
+    bw_put(b, 1, (uint32_t)full); if (full) { bw_put(b, 8, 255); bw_put(b, 16, 0x0203); bw_put(b, 16, 0x0101); }   /* Extended_SAR */
+    bw_put(b, 1, (uint32_t)full); if (full) bw_put(b, 1, 1);                                                       /* overscan */
+    bw_put(b, 1, (uint32_t)full); if (full) { bw_put(b, 3, 5); bw_put(b, 1, 0); bw_put(b, 1, 1); bw_put(b, 8, 1); bw_put(b, 8, 1); bw_put(b, 8, 1); }   /* video signal type, colour description */
+    bw_put(b, 1, (uint32_t)full); if (full) { bw_ue(b, 2); bw_ue(b, 3); }                                          /* chroma sample location */
+    bw_put(b, 1, (uint32_t)full); if (full) { bw_put(b, 32, 0x010203e9u); bw_put(b, 32, 0x0101ea60u); bw_put(b, 1, 1); }   /* timing */
+    bw_put(b, 1, (uint32_t)full); if (full) put_hrd(b);                                                            /* NAL HRD */
+    bw_put(b, 1, (uint32_t)full); if (full) put_hrd(b);                                                            /* VCL HRD */
+    if (full) bw_put(b, 1, 0);                                                                                     /* low_delay_hrd_flag */
+    bw_put(b, 1, (uint32_t)full);                                                                                  /* pic_struct_present_flag */
+    bw_put(b, 1, 1);                                                                                               /* bitstream_restriction_flag */
+    bw_put(b, 1, 1); bw_ue(b, 2); bw_ue(b, 1); bw_ue(b, 16); bw_ue(b, 16);
+    bw_ue(b, (uint32_t)opt_vui_reorder); bw_ue(b, (uint32_t)(opt_vui_reorder > opt_refs ? opt_vui_reorder : opt_refs));   /* num_reorder_frames, max_dec_frame_buffering */
+}
+
 int main(int argc, char **argv)
 {
     const char *cqm_arg = NULL, *cqm_where_arg = NULL;
@@ -1218,6 +1251,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--cqm")) { cqm_arg = i + 1 < argc ? argv[i + 1] : ""; i++; }
         else if (!strcmp(a, "--cqm-where")) { cqm_where_arg = i + 1 < argc ? argv[i + 1] : ""; i++; }
         else if (!strcmp(a, "--dump-cqm")) { dump_cqm = fopen(argv[i + 1], "wb"); i++; }
+        else if (!strcmp(a, "--vui-reorder")) { opt_vui_reorder = v < 0 ? 0 : v > 16 ? 16 : v; opt_vui_full = i + 1 < argc && strstr(argv[i + 1], ":full") != NULL; i++; }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
     if (W < 1 || H < 1 || W > 512 || H > 512 || frames < 1 || opt_qp < 0 || opt_qp > 51 || opt_refs < 1 || opt_refs > ((opt_mmco || opt_bframes) ? 4 : 2) || (opt_bframes && (opt_refs < 2 || opt_bframes > 4)) || opt_alpha < -6 || opt_alpha > 6 || opt_beta < -6 || opt_beta > 6) { fprintf(stderr, "bad geometry\n"); return 2; }
@@ -1262,7 +1296,8 @@ int main(int argc, char **argv)
         if (have_crop) { bw_put(&b, 1, 1); for (int k = 0; k < 4; k++) bw_ue(&b, (uint32_t)crop[k]); }
         else if (crop_bottom) { bw_put(&b, 1, 1); bw_ue(&b, 0); bw_ue(&b, 0); bw_ue(&b, 0); bw_ue(&b, (uint32_t)crop_bottom); }
         else bw_put(&b, 1, 0);
-        bw_put(&b, 1, 0);
+        bw_put(&b, 1, (uint32_t)(opt_vui_reorder >= 0));   /* vui_parameters_present_flag */
+        if (opt_vui_reorder >= 0) put_vui(&b);
         bw_trailing(&b);
         write_nal(f, 3, 7, &b); free(b.buf);
     }
