@@ -4,7 +4,8 @@ without a GPU.  Three things are asserted: the 47 cases an MI355X recorded (test
 test_gpu_launch_shapes) come out as recorded; every combination of kinds gets the kernel instances the rules below name, with
 the invariants that tie the stages together; knob values out of range are ignored.
 
-The program reads one case per line, `mb_w mb_h n compute_units  i p b wp dup t8 i8 sc  [P264AMD_NAME=value ...]`, feeds the
+The program reads one case per line, `mb_w mb_h n compute_units  i p b wp dup t8 i8 sc cr  [P264AMD_NAME=value ...]` (sc, cr: how many
+pictures take the scaled road / have a Cr QP offset of their own), feeds the
 knobs through launch_knobs_read by a getenv of its own and prints `key=value ...`: the plan's enums, copy_scale_table, the
 band of the work lists, every field of the plan's p264hip_launch_info_t, and the work lists' layout (max_chunks per pass and list, the
 chunk sizes and key counts of launch_shared.h: tests/test_worklist_cpu.py reads them through this program too)."""
@@ -16,6 +17,7 @@ import tempfile
 
 import pytest
 
+from tests.batch_kinds import plan_rules
 from tests.test_gpu_launch_shapes import CASES, COMPOSITION, GEOMETRY, GOLDEN, K, case_id
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,11 +36,11 @@ int main(void) {
     std::string line;
     while (std::getline(std::cin, line)) {
         std::istringstream in(line);
-        int mb_w, mb_h, n, cu, f[7];
+        int mb_w, mb_h, n, cu, f[7], cr;
         BatchKinds k;
-        in >> mb_w >> mb_h >> n >> cu >> f[0] >> f[1] >> f[2] >> f[3] >> f[4] >> f[5] >> f[6] >> k.sc;
+        in >> mb_w >> mb_h >> n >> cu >> f[0] >> f[1] >> f[2] >> f[3] >> f[4] >> f[5] >> f[6] >> k.sc >> cr;
         if (!in) { fprintf(stderr, "bad case: %s\n", line.c_str()); return 2; }
-        k.i = f[0]; k.p = f[1]; k.b = f[2]; k.wp = f[3]; k.dup = f[4]; k.t8 = f[5]; k.i8 = f[6];
+        k.i = f[0]; k.p = f[1]; k.b = f[2]; k.wp = f[3]; k.dup = f[4]; k.t8 = f[5]; k.i8 = f[6]; k.cr = cr != 0; k.n_cr = cr;
         std::map<std::string, std::string> env;
         for (std::string kv; in >> kv; ) env[kv.substr(0, kv.find('='))] = kv.substr(kv.find('=') + 1);
         const LaunchKnobs knobs = launch_knobs_read([&](const char *name) { auto it = env.find(name); return it == env.end() ? (const char *)nullptr : it->second.c_str(); });
@@ -47,10 +49,10 @@ int main(void) {
         const p264hip_launch_info_t &li = pl.info;
         printf("sort=%s mc=%s second=%d residual=%s intra=%s edge=%s copy_scale_table=%d band_log2=%u n_bands=%u "
                "pictures=%d compute_units=%d mc_wgs_per_picture=%d intra_waves=%d edge_info_fused=%d deblock_pics_per_wg=%d deblock_rb_log2=%d "
-               "deblock_waves=%d deblock_wgs=%d deblock_odd_single=%d t8x8_wgs=%d scaled_pictures=%d intra_i8=%d",
+               "deblock_waves=%d deblock_wgs=%d deblock_odd_single=%d t8x8_wgs=%d scaled_pictures=%d intra_i8=%d deblock_cr=%d cr_pictures=%d",
                sort[(int)pl.sort], mc[(int)pl.mc], (int)pl.mc_second, residual[(int)pl.residual], intra[(int)pl.intra], edge[(int)pl.edge], (int)pl.copy_scale_table,
                dev.ml.band_log2, dev.ml.n_bands, li.pictures, li.compute_units, li.mc_wgs_per_picture, li.intra_waves, li.edge_info_fused, li.deblock_pics_per_wg,
-               li.deblock_rb_log2, li.deblock_waves, li.deblock_wgs, li.deblock_odd_single, li.t8x8_wgs, li.scaled_pictures, li.intra_i8);
+               li.deblock_rb_log2, li.deblock_waves, li.deblock_wgs, li.deblock_odd_single, li.t8x8_wgs, li.scaled_pictures, li.intra_i8, (int)pl.deblock_cr, li.cr_pictures);
         // the work lists' layout and the constants tests/worklist_model.py types in: [pass * ML_LISTS + list]
         for (int l = 0; l < 2 * ML_LISTS; l++) printf(" max_chunks%d=%u", l, dev.ml.max_chunks[l]);
         for (int l = 0; l < ML_LISTS; l++) printf(" chunk_items%d=%d list_keys%d=%d", l, mc_chunk_items(l), l, mc_list_keys(l));
@@ -61,7 +63,7 @@ int main(void) {
 }
 '''
 
-KINDS = ("i", "p", "b", "wp", "dup", "t8", "i8", "sc")
+KINDS = ("i", "p", "b", "wp", "dup", "t8", "i8", "sc", "cr")
 MB = {"tiny_1x1": (1, 1), "col_Nx1": (1, 7), "wide_70": (70, 3), "qpdelta": (11, 9)}     # macroblocks: GEOMETRY's --mbw / --mbh
 CU = 256                                                                                 # what the golden table was recorded on
 
@@ -112,42 +114,11 @@ def test_the_recorded_launch_shapes(plan):
 
 # ---- the instance of every stage by the batch's kinds, restated from the rules (not from the header's code) ----
 N_MB = 11 * 9
-T8_MBS_PER_WG = 8            # k_t8x8: 256 threads, one wavefront per two macroblocks
 
 
 def expected(k, n, bs_knob):
-    """The plan's enums and the info fields that follow from the kinds alone.  Without p there is no inter stage at all: no sort, no
-    motion compensation, no in-place residual (batch_fill sets wp, dup and t8 only for pictures that also set p)."""
-    i, p, b, wp, dup, t8, i8, sc = (k[x] for x in KINDS)
-    e = {"sort": "none", "mc": "none", "second": 0, "residual": "none"}
-    if p:
-        if sc:
-            e["sort"] = "scaled" if b or wp else "scaled_p"
-        elif b:
-            e["sort"] = "b_wp" if wp else "b"
-        else:
-            e["sort"] = "wp" if wp else "plain"
-        e["mc"] = "wp" if wp else "plain"
-        e["second"] = int(b)
-        e["residual"] = "scaled_inter" if sc else "t8x8" if t8 else "none"
-    e["t8x8_wgs"] = (N_MB + T8_MBS_PER_WG - 1) // T8_MBS_PER_WG * n if e["residual"] == "t8x8" else 0
-    if sc:
-        e["intra"] = "dense_scaled" if i else "sparse_scaled"
-    elif i8:
-        e["intra"] = "dense_i8" if i else "sparse_i8"
-    else:
-        e["intra"] = "dense" if i else "sparse"
-    e["intra_i8"] = int(i8)
-    if i or b or wp or dup or t8 or i8 or sc or bs_knob == 0:
-        bs_wgs = 0
-    else:
-        bs_wgs = bs_knob if bs_knob is not None and bs_knob > 0 else 1          # INTRA_BS_WGS = 1
-    e["edge_info_fused"] = bs_wgs
-    e["edge"] = "bs_true" if b or wp or dup else "fused" if bs_wgs > 0 else "bs_false"
-    e["copy_scale_table"] = int(bool(sc))
-    e["scaled_pictures"] = sc
-    e["pictures"] = n
-    return e
+    """tests/batch_kinds.py: plan_rules, which the batches of tests/test_gpu_batch_kinds.py are planned with too"""
+    return plan_rules(k, n, bs_knob, N_MB)
 
 
 def test_every_combination_of_kinds(plan):
@@ -155,13 +126,15 @@ def test_every_combination_of_kinds(plan):
     for n in (1, 2, 257):
         for flags in itertools.product((False, True), repeat=7):
             for sc in sorted({0, 1, n}):
-                k = dict(zip(KINDS, flags + (sc,)))
-                if not (k["i"] or k["p"]) or (k["b"] and not k["p"]):
-                    continue
-                for bs_knob in (None, 0, 3):
-                    cases.append((11, 9, n, CU, k, {} if bs_knob is None else {K + "BS_FUSED": str(bs_knob)}))
-                    meta.append((k, n, bs_knob))
-    assert len(cases) == (64 + 16) * (2 + 3 + 3) * 3        # (with p: six free kinds; without: i, and no b) x sc values per n x knob
+                for cr in sorted({0, 1, sc} if sc else {0}):             # (batch_fill counts a picture with a Cr delta as a scaled one: cr <= sc)
+                    k = dict(zip(KINDS, flags + (sc, cr)))
+                    if not (k["i"] or k["p"]) or (k["b"] and not k["p"]):
+                        continue
+                    for bs_knob in (None, 0, 3):
+                        cases.append((11, 9, n, CU, k, {} if bs_knob is None else {K + "BS_FUSED": str(bs_knob)}))
+                        meta.append((k, n, bs_knob))
+    # (with p: six free kinds; without: i, and no b) x (sc, cr) values per n (sc 0: cr 0; sc 1: cr 0, 1; sc n > 1: cr 0, 1, n) x knob
+    assert len(cases) == (64 + 16) * (3 + 6 + 6) * 3
     for (k, n, bs_knob), got in zip(meta, plan(cases)):
         what = "%s n=%d BS_FUSED=%s: %s" % (k, n, bs_knob, got)
         want = expected(k, n, bs_knob)
@@ -175,6 +148,9 @@ def test_every_combination_of_kinds(plan):
         if not k["p"]:
             assert (got["sort"], got["mc"], got["second"], got["residual"]) == ("none", "none", 0, "none"), what
         assert got["copy_scale_table"] == int(bool(k["sc"])), what
+        # the Cr instances of the loop filter: with any Cr delta, and then never behind the fused edge info (such a batch is a scaled one)
+        assert got["deblock_cr"] == int(bool(k["cr"])) and got["cr_pictures"] == k["cr"], what
+        assert not (got["deblock_cr"] and got["edge"] == "fused"), what
 
 
 def test_knob_values_out_of_range_are_ignored(plan):
