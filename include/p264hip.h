@@ -470,6 +470,59 @@ int     p264hip_resize_aa_taps(int src_n, int dst_n, int32_t *first, int32_t *co
 int     p264hip_export_resized(p264hip_ctx *ctx, const int *streams, const int *slots, int n,
                                const p264hip_resize_t *r, void *dst_dev, size_t dst_bytes);
 
+/* ---- the same road with a window PER PICTURE, each resized into a rectangle of the output (a letterbox), in one call: crops of
+ * different places in different pictures (a detector's boxes for a second model), or a 1920 x 1080 picture into the 640 x 360
+ * middle of a 640 x 640 input with a constant round it.
+ *
+ * r gives the output as it does for p264hip_export_resized: format, matrix, full_range, width x height (W x H), dtype, pitch,
+ * frame_stride, scale, bias, with the same meanings and refusals.  Its crop_* fields are NOT READ: the windows are the ROIs'.
+ * Its filter must be P264HIP_FILTER_BILINEAR; the antialiased filter is refused (its tile width and LDS size are chosen per call
+ * from one window - per-ROI taps with weights are not built).  fill is Y | Cb << 8 | Cr << 16, bits 24 - 31 must be 0.
+ *
+ * Output picture i, at dst_dev + i*frame_stride, is the existing export of a VIRTUAL W x H 4:2:0 picture V:
+ *   luma    V.Y[y][x] = fill.Y outside the rectangle (dst_left, dst_top, dst_width, dst_height); inside, sample (x - dst_left,
+ *           y - dst_top) of the ROI's luma window resized to dst_width x dst_height by exactly the filter-0 arithmetic above - pos(d),
+ *           i0, i1, f and the >> 16 sum, S the window's size and D the rectangle's.  Taps clamp at the window's edges; nothing outside
+ *           the window is read
+ *   chroma  the same with every number halved: fill.Cb / fill.Cr outside, the window's width/2 x height/2 samples to
+ *           dst_width/2 x dst_height/2 at (dst_left/2, dst_top/2)
+ * and then the layout step of p264hip_resize_t unchanged: I420 / NV12 store the planes of V; RGB24 / RGBP take chroma sample
+ * (x >> 1, y >> 1) of V, the fixed-point formula and the clip; the float step is scale / bias as two separately rounded operations.
+ * The fill goes through the same RGB and float steps as any sample.  So: with every rectangle the whole output and every ROI naming
+ * one window the call writes what p264hip_export_resized writes for that window; a rectangle of the window's own size pastes the
+ * window unchanged; the bytes outside the rectangle are those of the export of a constant picture.  tests/roi_checker.py is this
+ * in numpy.
+ *
+ * The taps are made on the device (k_roi_taps) into a scratch area of the context of at most P264HIP_ROI_SCRATCH_BYTES; a call
+ * whose ROIs need more goes out as several pairs of launches on the one stream.  Per call the host sends the n descriptors and
+ * nothing per destination index.
+ *
+ * Not built: the antialiased filter for ROIs; ROI lists that live in device memory (the host must know n to size dst anyway;
+ * k_roi_taps is what such a variant would keep); a pipeline sink that takes ROIs; deliveries in output order as ROI sources. */
+typedef struct p264hip_roi {            /* 40 bytes */
+    int32_t stream, slot;               /* the picture */
+    int32_t left, top, width, height;   /* source window, luma samples: all even, width, height > 0, inside the frame */
+    int32_t dst_left, dst_top, dst_width, dst_height;   /* where in the W x H output the resized window lands: all even, inside the
+                                           output, dst_width, dst_height >= 2; all four 0 = the whole output */
+} p264hip_roi_t;
+#define P264HIP_ROI_SCRATCH_BYTES (16 << 20)     /* the tap scratch of one pair of launches: 4096 ROIs to 224 x 224 take 11 MB */
+/* what p264hip_resize_frame_bytes gives for the same description with a valid window (host only); P264HIP_EINVAL also for a filter
+ * other than P264HIP_FILTER_BILINEAR */
+int64_t p264hip_rois_frame_bytes(const p264hip_resize_t *r);
+/* 0, or P264HIP_EINVAL (host only) for what p264hip_rois_frame_bytes refuses, a frame_stride p264hip_resize_check refuses, a null
+ * list, n < 1, a fill with bits above 23, and for any ROI: a stream or slot outside n_streams x slots, a window with an odd or
+ * non-positive member or leaving the frame of mb_w x mb_h macroblocks, a rectangle - unless all four members are 0 - with an odd
+ * member, below 2 x 2 or leaving the output */
+int     p264hip_rois_check(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill,
+                           int mb_w, int mb_h, int n_streams, int slots);
+/* asynchronous on the context's stream behind every reconstruct queued before it, complete after p264hip_sync or a marker; rois[] is
+ * consumed before the call returns; entries may repeat; n >= 1, bounded only by dst_bytes.  P264HIP_EINVAL, before anything is
+ * queued, for whatever p264hip_rois_check refuses against the context's geometry (the message names the first bad ROI's index), a
+ * dst_dev that is no multiple of the element size, dst_bytes < (n-1)*frame_stride + the picture's bytes, and a frame above 65535
+ * samples a side (a tap holds a coordinate in 16 bits).  The kernel writes the bytes of the layout and no others. */
+int     p264hip_export_rois(p264hip_ctx *ctx, const p264hip_roi_t *rois, int n, const p264hip_resize_t *r,
+                            uint32_t fill, void *dst_dev, size_t dst_bytes);
+
 /* plain synchronous copies between host and device memory (the fan-out's TCP transport uses them where it stands in for a
  * device-to-device transport in tests) */
 int  p264hip_copy_to_device(void *dev, const void *host, size_t bytes);

@@ -71,6 +71,19 @@ int  p264pipe_set_sink(p264pipe *p, const p264hip_export_t *e, void *const *bufs
  * fn = NULL to either call takes it away.  p264pipe_export_last and p264pipe_set_sink behave as before. */
 int  p264pipe_export_last_resized(p264pipe *p, const p264hip_resize_t *r, void *dst_dev, size_t bytes);
 int  p264pipe_set_sink_resized(p264pipe *p, const p264hip_resize_t *r, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user);
+/* Windows of the streams' last decoded pictures, each resized into a rectangle of the output (p264hip_roi_t / p264hip_export_rois,
+ * include/p264hip.h), ROI i at dst_dev + i * frame_stride, in one call; complete when the call returns.  rois[i].slot must be -1:
+ * it stands for the last DECODED picture of rois[i].stream, what p264pipe_read_frame and p264pipe_export_last mean by "last".  A
+ * stream may be named any number of times, or not at all.  -1 where a named stream has no picture yet, a slot is not -1, or
+ * p264hip_export_rois refuses.
+ * It may be called between runs AND FROM INSIDE A SINK CALLBACK.  The callback runs on the thread that runs p264pipe_run, after the
+ * round's marker and before the next round's reconstruct is queued: with a decode-order sink the pictures the callback has just
+ * received are exactly the "last decoded" ones of their streams.  That is the detect-then-crop cascade: the sink hands round r's
+ * pictures to a detector, and the callback asks for round r's boxes at the second model's input size before round r + 1 overwrites
+ * anything.  With output order on (below) "last decoded" is NOT what a delivery carries - a delivery's pictures were decoded rounds
+ * ago -, so this call is of no use to a delivery's callback; deliveries in output order as ROI sources, and a sink that takes ROIs,
+ * are not built. */
+int  p264pipe_export_last_rois(p264pipe *p, const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, void *dst_dev, size_t bytes);
 
 /* ---- pictures in OUTPUT (display) order ----
  * on != 0: every stream's parser runs the output process of H.264 C.4 (p264parse_set_output_order, include/p264parse.h: the rule,

@@ -15,7 +15,8 @@ from . import _native
 from .recon import HipReconstructor, ParsedPicture, Parser, P264Error, device_count
 from .decoder import Decoder, param_default
 from .pipeline import Pipeline
+from ._native import letterbox
 from .fanout import FanOut
 
 __all__ = ["Decoder", "param_default", "Pipeline", "FanOut", "Parser", "ParsedPicture", "HipReconstructor", "P264Error",
-           "device_count", "_native"]
+           "device_count", "letterbox", "_native"]

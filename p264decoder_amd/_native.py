@@ -175,6 +175,63 @@ def resize_desc(fmt="rgbp", size=None, crop=None, frame=None, dtype="u8", scale=
     return r
 
 
+class Roi(C.Structure):
+    """p264hip_roi_t"""
+    _fields_ = [("stream", C.c_int32), ("slot", C.c_int32),
+                ("left", C.c_int32), ("top", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("dst_left", C.c_int32), ("dst_top", C.c_int32), ("dst_width", C.c_int32), ("dst_height", C.c_int32)]
+
+
+ROI_SCRATCH_BYTES = 16 << 20          # P264HIP_ROI_SCRATCH_BYTES
+
+
+def roi_array(rois, head=2):
+    """A (p264hip_roi_t array, n) from a sequence of rows or an (n, k) integer array.  A row is `head` leading members (stream, slot -
+    or stream alone: head=1, the slot becomes -1), the window (left, top, width, height) and, optionally, the rectangle (dst_left,
+    dst_top, dst_width, dst_height); without the rectangle the window fills the whole output.  A row of another length raises."""
+    import numpy as np
+    a = rois if isinstance(rois, np.ndarray) else None
+    if a is None:
+        rows = [tuple(row) for row in rois]
+        for i, row in enumerate(rows):
+            if len(row) not in (head + 4, head + 8):
+                raise ValueError("ROI %d has %d members: %d or %d" % (i, len(row), head + 4, head + 8))
+        a = np.array([row + (0, 0, 0, 0) if len(row) == head + 4 else row for row in rows], dtype=np.int64).reshape(len(rows), head + 8)
+    if a.ndim != 2 or a.shape[1] not in (head + 4, head + 8) or a.dtype.kind not in "iu":
+        raise ValueError("ROIs: an (n, %d) or (n, %d) integer array" % (head + 4, head + 8))
+    full = np.zeros((max(len(a), 1), 10), np.int32)
+    if head == 1:
+        full[:len(a), 0] = a[:, 0]
+        full[:len(a), 1] = -1
+        full[:len(a), 2:1 + a.shape[1]] = a[:, 1:]
+    else:
+        full[:len(a), :a.shape[1]] = a
+    arr = (Roi * len(full)).from_buffer_copy(full.tobytes())
+    return arr, len(a)
+
+
+def fill_word(fill):
+    """fill = (Y, Cb, Cr) as p264hip_export_rois takes it: Y | Cb << 8 | Cr << 16"""
+    y, cb, cr = (int(v) for v in fill)
+    if not all(0 <= v <= 255 for v in (y, cb, cr)):
+        raise ValueError("fill: three values 0 .. 255")
+    return y | cb << 8 | cr << 16
+
+
+def letterbox(w, h, W, H):
+    """(dst_left, dst_top, dst_width, dst_height): the centred even rectangle of a W x H output that a w x h window fills at its own
+    aspect ratio - one side the output's, the other the nearest even number to the exact ratio, at least 2.  Integers only.
+    1920 x 1080 into 640 x 640 gives (0, 140, 640, 360)."""
+    w, h, W, H = int(w), int(h), int(W), int(H)
+    if min(w, h) < 1 or min(W, H) < 2:
+        raise ValueError("letterbox: a window of %d x %d into %d x %d" % (w, h, W, H))
+    if w * H >= h * W:
+        dw, dh = W, min(max(2 * ((h * W + w) // (2 * w)), 2), H)
+    else:
+        dw, dh = min(max(2 * ((w * H + h) // (2 * h)), 2), W), H
+    return 2 * ((W - dw) // 4), 2 * ((H - dh) // 4), dw, dh
+
+
 def import_torch():
     """torch, for the calls that hand frames to it (HipReconstructor.export_frames, Pipeline.export_last / set_sink).  A process must
     hold ONE HIP runtime: a torch wheel brings its own libamdhip64.so, which libp264amd.so shares when torch was imported before
@@ -336,6 +393,16 @@ def load(path=None):
         lib.p264pipe_export_last.argtypes = [C.c_void_p, C.POINTER(Export), C.c_void_p, C.c_size_t]
         lib.p264pipe_set_sink.restype = C.c_int
         lib.p264pipe_set_sink.argtypes = [C.c_void_p, C.POINTER(Export), C.POINTER(C.c_void_p), C.c_int, C.c_size_t, SINK_FN, C.c_void_p]
+    if hasattr(lib, "p264hip_export_rois"):
+        lib.p264hip_rois_frame_bytes.restype = C.c_int64
+        lib.p264hip_rois_frame_bytes.argtypes = [C.POINTER(Resize)]
+        lib.p264hip_rois_check.restype = C.c_int
+        lib.p264hip_rois_check.argtypes = [C.POINTER(Roi), C.c_int, C.POINTER(Resize), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.p264hip_export_rois.restype = C.c_int
+        lib.p264hip_export_rois.argtypes = [C.c_void_p, C.POINTER(Roi), C.c_int, C.POINTER(Resize), C.c_uint32, C.c_void_p, C.c_size_t]
+    if hasattr(lib, "p264pipe_export_last_rois"):
+        lib.p264pipe_export_last_rois.restype = C.c_int
+        lib.p264pipe_export_last_rois.argtypes = [C.c_void_p, C.POINTER(Roi), C.c_int, C.POINTER(Resize), C.c_uint32, C.c_void_p, C.c_size_t]
     if hasattr(lib, "p264pipe_set_sink_resized"):
         lib.p264pipe_export_last_resized.restype = C.c_int
         lib.p264pipe_export_last_resized.argtypes = [C.c_void_p, C.POINTER(Resize), C.c_void_p, C.c_size_t]

@@ -26,6 +26,7 @@
 #include "kernel_export.h"
 #include "kernel_resize.h"
 #include "kernel_resize_aa.h"
+#include "kernel_roi.h"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -150,6 +151,7 @@ struct p264hip_ctx {
     std::vector<uint8_t *> planar_pool;    // p264hip_frame_planar_device: planar I420 frames that stay on the device
     // p264hip_export_frames: the frame index (stream * slots + slot) of every picture of a call, a ring like the batch's
     uint32_t *h_exp[BATCH_RING] = {}, *d_exp[BATCH_RING] = {}; hipEvent_t exp_free[BATCH_RING] = {}; int exp_cap = 0, exp_ring = 0;
+    uint32_t *d_roi = nullptr; size_t roi_cap = 0;          // the tap scratch of p264hip_export_rois (kernel_roi.h), bytes
     p264hip_launch_info_t last = {};       // what the last p264hip_reconstruct launched
     hipEvent_t markers[P264HIP_MARKERS] = {};
     int next_marker = 0;
@@ -237,6 +239,7 @@ extern "C" void p264hip_destroy(p264hip_ctx *c)
         if (c->d_exp[i]) (void)hipFree(c->d_exp[i]);
         if (c->exp_free[i]) (void)hipEventDestroy(c->exp_free[i]);
     }
+    if (c->d_roi) (void)hipFree(c->d_roi);
     for (auto &s : c->stamps) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     if (c->frames) (void)hipFree(c->frames);
@@ -798,6 +801,97 @@ extern "C" int p264hip_export_resized(p264hip_ctx *c, const int *streams, const 
         case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_U8:    RESIZE_LAUNCH(k_resize_rgbp_u8); break;
         case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_F16:   RESIZE_LAUNCH(k_resize_rgbp_f16); break;
         default:                                         RESIZE_LAUNCH(k_resize_rgbp_f32); break;
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return P264HIP_OK;
+}
+
+// ---- a window per picture into a rectangle of the output (include/p264hip.h: p264hip_roi_t; kernel_roi.h) ----
+extern "C" const char *p264hip_rois_why_(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int *bad);     // csrc/host/resize_layout.c
+
+#define ROI_LAUNCH(name) hipLaunchKernelGGL(name, grid, dim3(RESIZE_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const RoiDev *)c->d_exp[r], (const uint32_t *)c->d_roi, base, (uint8_t *)dst, p, fill)
+
+extern "C" int p264hip_export_rois(p264hip_ctx *c, const p264hip_roi_t *rois, int n, const p264hip_resize_t *e, uint32_t fill, void *dst, size_t dst_bytes)
+{
+    if (!c || !dst) return fail(P264HIP_EINVAL, "p264hip_export_rois: bad argument (n %d)", n);
+    int bad;
+    if (const char *why = p264hip_rois_why_(rois, n, e, fill, c->g.mb_w, c->g.mb_h, c->n_streams, c->slots, &bad)) {
+        if (bad < 0) return fail(P264HIP_EINVAL, "p264hip_export_rois: %s (n %d, fill 0x%x)", why, n, fill);
+        const p264hip_roi_t &o = rois[bad];
+        return fail(P264HIP_EINVAL, "p264hip_export_rois: ROI %d: %s (stream %d slot %d of %d x %d, window %d,%d %dx%d in a %dx%d frame, rectangle %d,%d %dx%d in %dx%d)", bad, why,
+                    o.stream, o.slot, c->n_streams, c->slots, o.left, o.top, o.width, o.height, c->g.w, c->g.h, o.dst_left, o.dst_top, o.dst_width, o.dst_height, e->width, e->height);
+    }
+    if (c->g.w > 65535 || c->g.h > 65535) return fail(P264HIP_EINVAL, "p264hip_export_rois: a frame of %dx%d samples (a tap holds a coordinate in 16 bits)", c->g.w, c->g.h);
+    const int elem = e->dtype == P264HIP_DTYPE_U8 ? 1 : e->dtype == P264HIP_DTYPE_F16 ? 2 : 4;
+    if ((uintptr_t)dst % (uintptr_t)elem) return fail(P264HIP_EINVAL, "p264hip_export_rois: dst is no multiple of the element size %d", elem);
+    const int64_t bytes = p264hip_rois_frame_bytes(e), stride = e->frame_stride ? e->frame_stride : bytes;
+    const int64_t pitch = e->pitch ? e->pitch : (e->format == P264HIP_FMT_RGB24 ? 3 * (int64_t)e->width : (int64_t)e->width) * elem;
+    if (n > 1 && stride > (INT64_MAX - bytes) / (n - 1)) return fail(P264HIP_EINVAL, "p264hip_export_rois: %d pictures %lld bytes apart", n, (long long)stride);
+    const uint64_t need = (uint64_t)(n - 1) * (uint64_t)stride + (uint64_t)bytes;
+    if ((uint64_t)dst_bytes < need) return fail(P264HIP_EINVAL, "p264hip_export_rois: %d pictures need %llu bytes, dst has %zu", n, (unsigned long long)need, dst_bytes);
+    constexpr int desc_words = (int)(sizeof(RoiDev) / sizeof(uint32_t));
+    if (n > INT32_MAX / desc_words - 16) return fail(P264HIP_ENOMEM, "p264hip_export_rois: %d descriptors", n);
+    HIPCHK(hipSetDevice(c->device));
+    int rc = export_reserve(c, n * desc_words);
+    if (rc) return rc;
+    const int r = c->exp_ring; c->exp_ring = (c->exp_ring + 1) % BATCH_RING;
+    HIPCHK(hipEventSynchronize(c->exp_free[r]));              // the copy that last used this staging buffer is done
+    // the descriptors, and the launch pairs: ROIs first .. first + count - 1 of a pair share the scratch, a segment each from word 0 on
+    // (one segment is at most 49152 words, so every pair holds at least one ROI)
+    constexpr size_t scratch_words = P264HIP_ROI_SCRATCH_BYTES / sizeof(uint32_t);
+    struct Pair { int first, count, widest; };
+    std::vector<Pair> pairs;
+    RoiDev *t = (RoiDev *)c->h_exp[r];
+    const int W = e->width, H = e->height;
+    size_t used = 0, most = 0;
+    for (int i = 0; i < n; i++) {
+        const p264hip_roi_t &o = rois[i];
+        const bool whole = !(o.dst_left | o.dst_top | o.dst_width | o.dst_height);
+        const int dl = whole ? 0 : o.dst_left, dt = whole ? 0 : o.dst_top, dw = whole ? W : o.dst_width, dh = whole ? H : o.dst_height;
+        const int words = roi_seg_words(dw, dh);
+        if (pairs.empty() || used + (size_t)words > scratch_words) { pairs.push_back({ i, 0, 0 }); used = 0; }
+        Pair &pr = pairs.back();
+        t[i] = RoiDev{ (uint32_t)(o.stream * c->slots + o.slot), (uint32_t)used, (uint32_t)dl | (uint32_t)dw << 16, (uint32_t)dt | (uint32_t)dh << 16,
+                       (uint32_t)o.left | (uint32_t)o.width << 16, (uint32_t)o.top | (uint32_t)o.height << 16, { 0, 0 } };
+        used += (size_t)words; pr.count++;
+        pr.widest = words > pr.widest ? words : pr.widest;
+        most = used > most ? used : most;
+    }
+    if ((rc = grow(c, (void **)&c->d_roi, &c->roi_cap, most * sizeof(uint32_t), 0, false, WAIT_STREAM, "the ROI taps"))) return rc;
+    HIPCHK(hipMemcpyAsync(c->d_exp[r], t, (size_t)n * sizeof(RoiDev), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->exp_free[r], c->stream));
+    const bool rgb = e->format == P264HIP_FMT_RGB24 || e->format == P264HIP_FMT_RGBP;
+    const int cw = W / 2, ch = H / 2;
+    ResizeParams p = {};                                    // (t_xl .. t_yc stay 0: the tables are the segments')
+    p.w = W; p.h = H;
+    p.ltx = (W + RESIZE_TILE_W - 1) / RESIZE_TILE_W; p.n_ltiles = p.ltx * (H / 2);
+    p.ctx = (cw + RESIZE_TILE_W - 1) / RESIZE_TILE_W; p.n_tiles = p.n_ltiles + (rgb ? 0 : p.ctx * ch);
+    p.inv_ltx = 0xffffffffu / (uint32_t)p.ltx; p.inv_ctx = 0xffffffffu / (uint32_t)p.ctx;
+    p.pitch = pitch; p.frame_stride = stride;
+    const int32_t *k = export_coefs[e->matrix][e->full_range];
+    p.cy = k[0]; p.yo = e->full_range ? 0 : 16; p.r_cv = k[1]; p.g_cu = k[2]; p.g_cv = k[3]; p.b_cu = k[4];
+    for (int i = 0; i < 3; i++) { p.scale[i] = e->scale[i]; p.bias[i] = e->bias[i]; }
+    const unsigned gx = (unsigned)((p.n_tiles + RESIZE_THREADS / WAVE - 1) / (RESIZE_THREADS / WAVE));
+    for (const Pair &pr : pairs) {                          // (one stream: a pair's taps are read before the next pair's are written)
+        const unsigned tx = (unsigned)((pr.widest + ROI_TAPS_THREADS - 1) / ROI_TAPS_THREADS);
+        for (int base = pr.first; base < pr.first + pr.count; base += 65535) {            // (a grid's second dimension ends at 65535)
+            const int left = pr.first + pr.count - base;
+            hipLaunchKernelGGL(k_roi_taps, dim3(tx, (unsigned)(left < 65535 ? left : 65535)), dim3(ROI_TAPS_THREADS), 0, c->stream, (const RoiDev *)c->d_exp[r], base, c->d_roi);
+        }
+        for (int base = pr.first; base < pr.first + pr.count; base += 65535) {
+            const int left = pr.first + pr.count - base;
+            const dim3 grid(gx, (unsigned)(left < 65535 ? left : 65535));
+            switch (e->format * 3 + e->dtype) {
+            case P264HIP_FMT_I420 * 3:                       ROI_LAUNCH(k_roi_i420); break;
+            case P264HIP_FMT_NV12 * 3:                       ROI_LAUNCH(k_roi_nv12); break;
+            case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_U8:   ROI_LAUNCH(k_roi_rgb24_u8); break;
+            case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F16:  ROI_LAUNCH(k_roi_rgb24_f16); break;
+            case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F32:  ROI_LAUNCH(k_roi_rgb24_f32); break;
+            case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_U8:    ROI_LAUNCH(k_roi_rgbp_u8); break;
+            case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_F16:   ROI_LAUNCH(k_roi_rgbp_f16); break;
+            default:                                         ROI_LAUNCH(k_roi_rgbp_f32); break;
+            }
         }
     }
     HIPCHK(hipGetLastError());

@@ -374,6 +374,12 @@ void p264pipe_geometry_(const p264pipe *p, int *device, int *mb_w, int *mb_h)
     *device = p->device; *mb_w = p->mb_w; *mb_h = p->mb_h;
 }
 
+p264hip_ctx *p264pipe_last_slot_(const p264pipe *p, int stream, int *slot)
+{
+    *slot = p->ctx && stream >= 0 && stream < p->n_streams ? p->st[stream].last_slot : -1;
+    return p->ctx;
+}
+
 int p264pipe_export_last_with_(p264pipe *p, const char *who, p264pipe_export_fn ex, const void *desc, void *dst_dev, size_t bytes)
 {
     if (!p || !p->ctx || !desc || !dst_dev) return -1;

@@ -2,6 +2,7 @@
  * p264pipe_export_last_resized, p264pipe_set_sink_resized): the export kind p264hip_resize_t / p264hip_export_resized, installed
  * through pipeline_sink.h.  pipeline.c runs the sink and knows nothing of the description. */
 #include <stdio.h>
+#include <stdlib.h>
 #include "pipeline_sink.h"
 
 static int export_resized(p264hip_ctx *ctx, const int *streams, const int *slots, int n, const void *desc, void *dst_dev, size_t bytes)
@@ -12,6 +13,30 @@ static int export_resized(p264hip_ctx *ctx, const int *streams, const int *slots
 int p264pipe_export_last_resized(p264pipe *p, const p264hip_resize_t *r, void *dst_dev, size_t bytes)
 {
     return p264pipe_export_last_with_(p, "p264pipe_export_last_resized", export_resized, r, dst_dev, bytes);
+}
+
+/* per-picture windows of the streams' last decoded pictures (p264hip_roi_t / p264hip_export_rois): slot -1 becomes the stream's slot */
+int p264pipe_export_last_rois(p264pipe *p, const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, void *dst_dev, size_t bytes)
+{
+    if (!p || !rois || n < 1 || !r || !dst_dev) return -1;
+    p264hip_roi_t *mine = (p264hip_roi_t *)malloc(sizeof *mine * (size_t)n);
+    if (!mine) return -1;
+    p264hip_ctx *ctx = NULL;
+    int rc = 0;
+    for (int i = 0; i < n && !rc; i++) {
+        int slot;
+        ctx = p264pipe_last_slot_(p, rois[i].stream, &slot);
+        if (!ctx || rois[i].slot != -1 || slot < 0) {
+            fprintf(stderr, "p264pipe_export_last_rois: ROI %d: stream %d slot %d (the slot must be -1, the stream one with a decoded picture)\n", i, rois[i].stream, rois[i].slot);
+            rc = -1;
+        }
+        mine[i] = rois[i]; mine[i].slot = slot;
+    }
+    if (!rc && (p264hip_export_rois(ctx, mine, n, r, fill, dst_dev, bytes) || p264hip_sync(ctx))) {
+        fprintf(stderr, "p264pipe_export_last_rois: %s\n", p264hip_last_error()); rc = -1;
+    }
+    free(mine);
+    return rc;
 }
 
 int p264pipe_set_sink_resized(p264pipe *p, const p264hip_resize_t *r, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user)

@@ -1,8 +1,9 @@
 /* resize_layout.c - the layout of a resized exported picture (include/p264hip.h: p264hip_resize_t), the checks every resized
- * export runs before anything is queued, and the taps of the two filters.  Pure host code, no device involved; the kernels are
- * csrc/hip/kernel_resize.h and kernel_resize_aa.h. */
+ * export runs before anything is queued - the list of per-picture windows of p264hip_export_rois among them -, and the taps of the
+ * two filters.  Pure host code, no device involved; the kernels are csrc/hip/kernel_resize.h, kernel_resize_aa.h and kernel_roi.h. */
 #include <math.h>
 #include "p264hip.h"
+#include "p264hip_pos.h"
 
 static int is_rgb(int format) { return format == P264HIP_FMT_RGB24 || format == P264HIP_FMT_RGBP; }
 
@@ -68,12 +69,60 @@ int p264hip_resize_check(const p264hip_resize_t *r, int mb_w, int mb_h)
 int p264hip_resize_taps(int src_n, int dst_n, int32_t *pos)
 {
     if (!pos || src_n < 1 || dst_n < 1 || src_n > (1 << 20) || dst_n > (1 << 20)) return P264HIP_EINVAL;
-    const int64_t S = src_n, D = dst_n, last = (S - 1) * 256;
-    for (int64_t d = 0; d < D; d++) {
-        int64_t p = ((2 * d + 1) * S * 256 + D) / (2 * D) - 128;           /* (the dividend is positive: / is floor) */
-        pos[d] = (int32_t)(p < 0 ? 0 : p > last ? last : p);
-    }
+    for (int d = 0; d < dst_n; d++) pos[d] = p264hip_resize_pos(src_n, dst_n, d);      /* (p264hip_pos.h: the device runs the same text) */
     return P264HIP_OK;
+}
+
+/* ---- per-picture windows into rectangles of the output (include/p264hip.h: p264hip_roi_t; csrc/hip/kernel_roi.h) ---- */
+/* the description with a window every frame holds: crop_* are not read on this road */
+static p264hip_resize_t without_window(const p264hip_resize_t *r)
+{
+    p264hip_resize_t q = *r;
+    q.crop_left = q.crop_top = 0; q.crop_width = q.crop_height = 2;
+    return q;
+}
+
+/* why the call is refused (NULL: it is not); *bad: the index of the first bad ROI, -1 where the call is refused on its own */
+const char *p264hip_rois_why_(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int *bad)
+{
+    *bad = -1;
+    if (!r) return "null description";
+    if (r->filter == P264HIP_FILTER_BILINEAR_AA) return "the antialiased filter has no per-picture windows (filter must be P264HIP_FILTER_BILINEAR)";
+    const p264hip_resize_t q = without_window(r);
+    const char *why = p264hip_resize_why_(&q, mb_w, mb_h);
+    if (why) return why;
+    if (!rois) return "null ROI list";
+    if (n < 1) return "no ROI";
+    if (n_streams < 1 || slots < 1) return "no frame store";
+    if (fill >> 24) return "fill with a bit above 23 set";
+    const int64_t fw = (int64_t)mb_w * 16, fh = (int64_t)mb_h * 16;
+    for (int i = 0; i < n; i++) {
+        const p264hip_roi_t *o = rois + i;
+        *bad = i;
+        if (o->stream < 0 || o->stream >= n_streams || o->slot < 0 || o->slot >= slots) return "stream or slot out of range";
+        if (o->left < 0 || o->top < 0 || o->width < 1 || o->height < 1) return "window with a negative offset or without samples";
+        if ((o->left | o->top | o->width | o->height) & 1) return "window with an odd member";
+        if ((int64_t)o->left + o->width > fw || (int64_t)o->top + o->height > fh) return "window leaves the frame";
+        if (!(o->dst_left | o->dst_top | o->dst_width | o->dst_height)) continue;          /* the whole output */
+        if (o->dst_left < 0 || o->dst_top < 0 || o->dst_width < 2 || o->dst_height < 2) return "rectangle with a negative offset or below 2 x 2";
+        if ((o->dst_left | o->dst_top | o->dst_width | o->dst_height) & 1) return "rectangle with an odd member";
+        if ((int64_t)o->dst_left + o->dst_width > r->width || (int64_t)o->dst_top + o->dst_height > r->height) return "rectangle leaves the output";
+    }
+    *bad = -1;
+    return 0;
+}
+
+int64_t p264hip_rois_frame_bytes(const p264hip_resize_t *r)
+{
+    if (!r || r->filter != P264HIP_FILTER_BILINEAR) return P264HIP_EINVAL;
+    const p264hip_resize_t q = without_window(r);
+    return p264hip_resize_frame_bytes(&q);
+}
+
+int p264hip_rois_check(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots)
+{
+    int bad;
+    return p264hip_rois_why_(rois, n, r, fill, mb_w, mb_h, n_streams, slots, &bad) ? P264HIP_EINVAL : P264HIP_OK;
 }
 
 static int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }        /* b > 0 */

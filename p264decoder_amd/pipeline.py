@@ -156,6 +156,30 @@ class Pipeline:
             raise RuntimeError("p264pipe_export_last_resized failed: %s" % self.lib.p264hip_last_error().decode())
         return out
 
+    def export_last_rois(self, rois, size, fmt="rgbp", dtype="u8", fill=(16, 128, 128), scale=None, bias=None, matrix="bt601", full_range=False,
+                         pitch=0, frame_stride=0, out=None):
+        """Windows of the streams' last DECODED pictures, each resized into a rectangle of the size = (width, height) output with the
+        constant `fill` round it (p264pipe_export_last_rois); complete on return.  rois: rows (stream, left, top, width, height) or
+        the same with the rectangle (dst_left, dst_top, dst_width, dst_height) behind it, or an (n, 5 | 9) integer array; the other
+        arguments, `out` and the result as HipReconstructor.export_rois has them.  It may be called from inside a sink's callback:
+        with a decode-order sink the round's pictures are the last decoded ones - detect on the sink's buffer, crop here."""
+        arr, n = N.roi_array(rois, head=1)
+        r = N.resize_desc(fmt, size, (0, 0, 2, 2), None, dtype, scale, bias, matrix, full_range, pitch, frame_stride)
+        per = self.lib.p264hip_rois_frame_bytes(C.byref(r))
+        if per < 0:
+            raise RuntimeError("export_last_rois: p264hip_rois_frame_bytes refuses the description")
+        if out is None:
+            torch = N.import_torch()
+            W, H = r.width, r.height
+            shape = (n, H * 3 // 2, W) if r.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if r.format == N.FMT_RGB24 else (n, 3, H, W)
+            want = {N.DTYPE_F16: torch.float16, N.DTYPE_F32: torch.float32}.get(r.dtype, torch.uint8)
+            plain = not pitch and not frame_stride
+            out = torch.empty(shape, dtype=want, device="cuda") if plain else torch.empty((n, r.frame_stride or per), dtype=torch.uint8, device="cuda")
+        ptr, cap = out if isinstance(out, tuple) else (out.data_ptr(), out.numel() * out.element_size())
+        if self.lib.p264pipe_export_last_rois(self.h, arr, n, C.byref(r), N.fill_word(fill), ptr, cap):
+            raise RuntimeError("p264pipe_export_last_rois failed: %s" % self.lib.p264hip_last_error().decode())
+        return out
+
     def set_sink_resized(self, size, callback, fmt="rgbp", dtype="u8", depth=2, crop=None, scale=None, bias=None, matrix="bt601", full_range=False,
                          pitch=0, buffers=None, *, filter="bilinear"):
         """set_sink with a resize on it (p264pipe_set_sink_resized): callback(round, streams, dev, bytes) for every round of run(),

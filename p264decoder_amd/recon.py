@@ -317,6 +317,41 @@ class HipReconstructor:
             self.sync()
         return out
 
+    def export_rois(self, rois, size, fmt="rgbp", dtype="u8", fill=(16, 128, 128), scale=None, bias=None, matrix="bt601", full_range=False,
+                    pitch=0, frame_stride=0, out=None, sync=True):
+        """A window PER PICTURE, each resized by the bilinear filter into a rectangle of the size = (width, height) output and the
+        constant fill = (Y, Cb, Cr) round it, in one call (p264hip_export_rois; include/p264hip.h has the contract).  rois: a sequence
+        of rows, or an (n, 6 | 10) integer array: (stream, slot, left, top, width, height) - the window fills the whole output - or
+        the same with the rectangle (dst_left, dst_top, dst_width, dst_height) behind it (_native.letterbox gives one that keeps the
+        window's aspect ratio).  The other arguments, `out` and the result are those of export_resized, picture i being ROI i."""
+        arr, n = N.roi_array(rois)
+        r = N.resize_desc(fmt, size, (0, 0, 2, 2), None, dtype, scale, bias, matrix, full_range, pitch, frame_stride)
+        word = N.fill_word(fill)
+        if out is None or not isinstance(out, tuple):
+            torch = N.import_torch()                      # only here: the module imports without torch or a GPU
+            want = {N.DTYPE_U8: torch.uint8, N.DTYPE_F16: torch.float16, N.DTYPE_F32: torch.float32}.get(r.dtype, torch.uint8)
+        if out is None:
+            per = self.lib.p264hip_rois_frame_bytes(C.byref(r))
+            if per < 0:
+                raise P264Error("export_rois: p264hip_rois_frame_bytes refuses the description")
+            W, H = r.width, r.height
+            shape = (n, H * 3 // 2, W) if r.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if r.format == N.FMT_RGB24 else (n, 3, H, W)
+            if not pitch and not frame_stride:
+                out = torch.empty(shape, dtype=want, device="cuda")
+            else:
+                out = torch.empty((n, r.frame_stride or per), dtype=torch.uint8, device="cuda")
+        if isinstance(out, tuple):
+            ptr, cap = out
+        else:
+            if not (out.is_cuda and out.is_contiguous() and out.dtype in (want, torch.uint8)):
+                raise P264Error("export_rois: out must be a contiguous %s (or uint8) tensor on the device" % want)
+            torch.cuda.current_stream(out.device).synchronize()     # (whatever torch still has queued on the tensor: the context has its own stream)
+            ptr, cap = out.data_ptr(), out.numel() * out.element_size()
+        self._chk(self.lib.p264hip_export_rois(self.h, arr, n, C.byref(r), word, ptr, cap), "p264hip_export_rois")
+        if sync:
+            self.sync()
+        return out
+
     def clone_picture(self, dst, src):
         self._chk(self.lib.p264hip_clone_picture(self.h, dst, src), "p264hip_clone_picture")
 

@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""Rate of the export of per-picture windows (p264hip_export_rois) out of a store of 1080p frames, beside the roads that existed before
+it.  The roads of a case alternate repetition by repetition in one run; every repetition is closed by a sync; the median of --reps is
+reported with min and max.  Bytes are counted from the shapes.  This is NOT bench.py's metric (the reconstruction); it is the figure
+DESIGN.md quotes for K6b.
+
+  a  the same work as the existing road: one ROI per frame, the whole 1920 x 1080 window to 224 x 224 planar RGB float32 normalised,
+     beside p264hip_export_resized of the same description.  What the device-made taps, the per-picture segment and the per-sample
+     select cost: the ROI road is required to reach 0.9 of export_resized's rate in the same run.
+  b  what the feature is for: 4096 drawn windows (seeded, 64 .. 512 samples a side, two per frame) to 224 x 224 planar RGB float32 in
+     ONE export_rois call, beside one export_resized call per window, measured on the first 256 of them.
+  c  letterbox: every frame into 640 x 640 planar RGB float16 through letterbox(), beside export_resized to 640 x 360 followed by
+     torch.nn.functional.pad on the device.
+
+  python -m p264decoder_amd.tools.roi_bench [--frames 2048] [--reps 20] [--warmup 3] [--out profiles/roi_bench.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from p264decoder_amd.tools.resize_bench import H, MB_H, MB_W, MEAN, STD, W, alternating, entry      # noqa: E402
+
+PER_CALL = 256              # windows of case b the one-call-per-window road is measured on
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=2048, help="frames of the store = streams of the context (2 slots each)")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None, help="also write the result there")
+    ap.add_argument("--only", default="abc", help="the cases to run")
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    import torch.nn.functional as F
+    if not torch.cuda.is_available():
+        raise SystemExit("roi_bench: no GPU - there is nothing to measure without one")
+    from p264decoder_amd import HipReconstructor, letterbox
+    n = args.frames
+    hip = HipReconstructor(MB_W, MB_H, n_streams=n, slots=2, max_pictures=1)
+    streams, slots = list(range(n)), [i & 1 for i in range(n)]
+    scale, bias = [1 / (255 * s) for s in STD], [-m / s for m, s in zip(MEAN, STD)]
+    src = W * H * 3 // 2                       # bytes of a whole picture in the frame store
+    res = {"metric": "export of per-picture windows out of %d 1080p frames" % n, "unit": "pictures/s", "frames": n, "reps": args.reps, "warmup": args.warmup, "cases": {}}
+
+    def mem(t):
+        return (t.data_ptr(), t.numel() * t.element_size())
+
+    if "a" in args.only:
+        out = torch.empty((n, 3, 224, 224), dtype=torch.float32, device="cuda")
+        rois = np.array([(s, k, 0, 0, W, H) for s, k in zip(streams, slots)], np.int32)
+        t = alternating({"rois": lambda: hip.export_rois(rois, (224, 224), "rgbp", "f32", scale=scale, bias=bias, out=mem(out)),
+                         "resized": lambda: hip.export_resized(streams, slots, (224, 224), "rgbp", "f32", (0, 0, W, H), scale, bias, out=mem(out))}, args.warmup, args.reps)
+        moved = n * (src + 3 * 224 * 224 * 4)
+        ratio = round(t["resized"][0] / t["rois"][0], 3)
+        res["cases"]["a_whole_frames_rgbp_f32_224x224_normalised"] = {
+            "p264hip_export_rois": entry(n, t["rois"], moved), "p264hip_export_resized": entry(n, t["resized"], moved),
+            "rate_over_export_resized": ratio, "required": 0.9, "met": ratio >= 0.9}
+        res["value"] = res["cases"]["a_whole_frames_rgbp_f32_224x224_normalised"]["p264hip_export_rois"]["frames_per_s"]
+        del out
+    if "b" in args.only:
+        g = np.random.default_rng(2663)
+        m = 2 * n
+        ww, wh = 2 * g.integers(32, 257, m), 2 * g.integers(32, 257, m)
+        left, top = 2 * (g.integers(0, 1 << 30, m) % ((W - ww) // 2 + 1)), 2 * (g.integers(0, 1 << 30, m) % ((H - wh) // 2 + 1))
+        rois = np.stack([np.arange(m) // 2, np.arange(m) & 1, left, top, ww, wh], axis=1).astype(np.int32)
+        assert rois[:, 4].min() >= 64 and rois[:, 4].max() <= 512 and np.all(rois[:, 2] + rois[:, 4] <= W) and np.all(rois[:, 3] + rois[:, 5] <= H)
+        out = torch.empty((m, 3, 224, 224), dtype=torch.float32, device="cuda")
+        per = 3 * 224 * 224 * 4
+        first = [tuple(int(v) for v in r) for r in rois[:PER_CALL]]
+
+        def one_by_one():
+            for i, r in enumerate(first):
+                hip.export_resized([r[0]], [r[1]], (224, 224), "rgbp", "f32", r[2:], scale, bias, out=(out.data_ptr() + i * per, per), sync=False)
+            hip.sync()
+        t = alternating({"rois": lambda: hip.export_rois(rois, (224, 224), "rgbp", "f32", scale=scale, bias=bias, out=mem(out)), "one_by_one": one_by_one}, args.warmup, args.reps)
+        read = int((rois[:, 4].astype(np.int64) * rois[:, 5] * 3 // 2).sum())
+        read_first = int((rois[:PER_CALL, 4].astype(np.int64) * rois[:PER_CALL, 5] * 3 // 2).sum())
+        a, b = entry(m, t["rois"], read + m * per), entry(PER_CALL, t["one_by_one"], read_first + PER_CALL * per)
+        res["cases"]["b_drawn_windows_rgbp_f32_224x224_normalised"] = {
+            "windows": m, "window_side": "64 .. 512, even, seeded", "p264hip_export_rois_one_call": a,
+            "p264hip_export_resized_one_call_per_window": dict(b, windows_measured=PER_CALL),
+            "rate_over_one_call_per_window": round(a["frames_per_s"] / b["frames_per_s"], 2)}
+        del out
+    if "c" in args.only:
+        rect = letterbox(W, H, 640, 640)
+        assert rect == (0, 140, 640, 360)
+        boxed = torch.empty((n, 3, 640, 640), dtype=torch.float16, device="cuda")
+        strip = torch.empty((n, 3, 360, 640), dtype=torch.float16, device="cuda")
+        rois = np.array([(s, k, 0, 0, W, H) + rect for s, k in zip(streams, slots)], np.int32)
+        keep = []
+
+        def pad_road():
+            hip.export_resized(streams, slots, (640, 360), "rgbp", "f16", (0, 0, W, H), 1 / 255, 0.0, out=mem(strip))
+            keep[:] = [F.pad(strip, (0, 0, rect[1], 640 - rect[1] - rect[3]), value=0.0)]       # (fill (16, 128, 128) is RGB 0, 0, 0)
+            torch.cuda.synchronize()
+        t = alternating({"rois": lambda: hip.export_rois(rois, (640, 640), "rgbp", "f16", (16, 128, 128), 1 / 255, 0.0, out=mem(boxed)), "pad": pad_road}, args.warmup, args.reps)
+        same = bool(torch.equal(keep[0], boxed))
+        res["cases"]["c_letterbox_rgbp_f16_640x640"] = {
+            "rectangle": list(rect), "p264hip_export_rois": entry(n, t["rois"], n * (src + 3 * 640 * 640 * 2)),
+            "export_resized_640x360_then_torch_pad": entry(n, t["pad"], n * (src + 2 * 3 * 360 * 640 * 2 + 3 * 640 * 640 * 2)),
+            "rate_over_resized_then_pad": round(t["pad"][0] / t["rois"][0], 2), "the_two_roads_agree": same}
+    hip.close()
+    line = json.dumps(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
