@@ -476,8 +476,9 @@ int     p264hip_export_resized(p264hip_ctx *ctx, const int *streams, const int *
  *
  * r gives the output as it does for p264hip_export_resized: format, matrix, full_range, width x height (W x H), dtype, pitch,
  * frame_stride, scale, bias, with the same meanings and refusals.  Its crop_* fields are NOT READ: the windows are the ROIs'.
- * Its filter must be P264HIP_FILTER_BILINEAR; the antialiased filter is refused (its tile width and LDS size are chosen per call
- * from one window - per-ROI taps with weights are not built).  fill is Y | Cb << 8 | Cr << 16, bits 24 - 31 must be 0.
+ * Its filter must be P264HIP_FILTER_BILINEAR; the antialiased filter is refused here because it has entry points of its own,
+ * p264hip_export_rois_aa and its two siblings below (their limit is per ROI, their taps carry weights and their tile width is chosen
+ * per ROI).  fill is Y | Cb << 8 | Cr << 16, bits 24 - 31 must be 0.
  *
  * Output picture i, at dst_dev + i*frame_stride, is the existing export of a VIRTUAL W x H 4:2:0 picture V:
  *   luma    V.Y[y][x] = fill.Y outside the rectangle (dst_left, dst_top, dst_width, dst_height); inside, sample (x - dst_left,
@@ -497,8 +498,8 @@ int     p264hip_export_resized(p264hip_ctx *ctx, const int *streams, const int *
  * whose ROIs need more goes out as several pairs of launches on the one stream.  Per call the host sends the n descriptors and
  * nothing per destination index.
  *
- * Not built: the antialiased filter for ROIs; ROI lists that live in device memory (the host must know n to size dst anyway;
- * k_roi_taps is what such a variant would keep); a pipeline sink that takes ROIs; deliveries in output order as ROI sources. */
+ * Not built: ROI lists that live in device memory (the host must know n to size dst anyway; k_roi_taps / k_roi_aa_taps are what
+ * such a variant would keep); a pipeline sink that takes ROIs; deliveries in output order as ROI sources. */
 typedef struct p264hip_roi {            /* 40 bytes */
     int32_t stream, slot;               /* the picture */
     int32_t left, top, width, height;   /* source window, luma samples: all even, width, height > 0, inside the frame */
@@ -522,6 +523,42 @@ int     p264hip_rois_check(const p264hip_roi_t *rois, int n, const p264hip_resiz
  * samples a side (a tap holds a coordinate in 16 bits).  The kernel writes the bytes of the layout and no others. */
 int     p264hip_export_rois(p264hip_ctx *ctx, const p264hip_roi_t *rois, int n, const p264hip_resize_t *r,
                             uint32_t fill, void *dst_dev, size_t dst_bytes);
+
+/* ---- the same three with the ANTIALIASED filter (P264HIP_FILTER_BILINEAR_AA): the letterbox of a 1920 x 1080 picture and a
+ * detector's boxes at 224 x 224 are reductions, on which filter 0 aliases.  Everything said of p264hip_export_rois holds, but:
+ *   - r->filter must be P264HIP_FILTER_BILINEAR_AA; every other value is refused;
+ *   - the 32:1 limit is PER ROI: an ROI with width > 32 * dst_width or height > 32 * dst_height - the rectangle being the whole
+ *     W x H output where all four dst_* are 0 - is refused, and the message names its index;
+ *   - inside the rectangle each plane of the window is resized to the rectangle's size by exactly the filter-2 arithmetic above:
+ *     r(j), the Q15 weights with the residue to the largest tap, the vertical pass first, one rounding per pass, S the window's size
+ *     and D the rectangle's (chroma: every number halved).  Samples outside the WINDOW are dropped and the rest renormalised: they
+ *     are never read.
+ * Outside the rectangle V holds the fill; the layout, RGB and float steps are unchanged and the fill goes through them like any
+ * sample.  So: with every rectangle the whole output and every ROI naming one window the bytes are those of p264hip_export_resized
+ * with filter 2 for that window; a rectangle of the window's own size pastes the window unchanged (D == S: one tap of 32768, and
+ * (64 s * 32768 + 2^20) >> 21 is s); the bytes outside the rectangle are those of p264hip_export_rois.  tests/roi_aa_checker.py is
+ * this in numpy.
+ *
+ * The taps are made on the device (k_roi_aa_taps) into the same scratch with the same cap.  The SEGMENT of an ROI there: four axes
+ * in the order x luma, y luma, x chroma, y chroma, each D words first | count << 16 (first a coordinate of the frame) padded to a
+ * multiple of 4 with the last one, then D rows of 16-bit Q15 weights with the row stride 2 for S <= D and min(64, ceil(2 S / D))
+ * rounded up to even otherwise, padded with 0 to a multiple of 4 words (include/p264hip_aa.h has the text host and device compile).
+ * A workgroup of k_roi_aa_* holds 16 rows of a tile's source columns as 16-bit values in LDS, P264HIP_ROI_AA_TILE_VALUES at most;
+ * the tile is 64, 32, 16 or 8 output samples wide, chosen per ROI. */
+#define P264HIP_ROI_AA_TILE_VALUES 20480
+int64_t p264hip_rois_aa_frame_bytes(const p264hip_resize_t *r);
+int     p264hip_rois_aa_check(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill,
+                              int mb_w, int mb_h, int n_streams, int slots);
+int     p264hip_export_rois_aa(p264hip_ctx *ctx, const p264hip_roi_t *rois, int n, const p264hip_resize_t *r,
+                               uint32_t fill, void *dst_dev, size_t dst_bytes);
+/* host only, no device: the words of the segment of one ROI in the output r describes, and the segment itself as k_roi_aa_taps
+ * writes it (the same text).  They read the ROI's window and rectangle and r's width and height, nothing else; P264HIP_EINVAL for a
+ * null pointer, an odd or non-positive size, a rectangle above 16384 or a window more than 32 times the rectangle */
+int     p264hip_roi_aa_segment_words(const p264hip_roi_t *roi, const p264hip_resize_t *r);
+int     p264hip_roi_aa_segment(const p264hip_roi_t *roi, const p264hip_resize_t *r, uint32_t *words);
+/* host only: the tile width k_roi_aa_* use for this ROI (64, 32, 16 or 8) and the strips of 16 luma / 8 chroma samples of a tile
+ * row in LDS (either pointer may be null); P264HIP_EINVAL as above */
+int     p264hip_roi_aa_tile_width(const p264hip_roi_t *roi, const p264hip_resize_t *r, int *luma_strips, int *chroma_strips);
 
 /* plain synchronous copies between host and device memory (the fan-out's TCP transport uses them where it stands in for a
  * device-to-device transport in tests) */

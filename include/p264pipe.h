@@ -75,7 +75,8 @@ int  p264pipe_set_sink_resized(p264pipe *p, const p264hip_resize_t *r, void *con
  * include/p264hip.h), ROI i at dst_dev + i * frame_stride, in one call; complete when the call returns.  rois[i].slot must be -1:
  * it stands for the last DECODED picture of rois[i].stream, what p264pipe_read_frame and p264pipe_export_last mean by "last".  A
  * stream may be named any number of times, or not at all.  -1 where a named stream has no picture yet, a slot is not -1, or
- * p264hip_export_rois refuses.
+ * p264hip_export_rois refuses.  With r->filter P264HIP_FILTER_BILINEAR_AA the call goes to p264hip_export_rois_aa, the antialiased
+ * filter with its limit of 32:1 per ROI, and fails where that one refuses.
  * It may be called between runs AND FROM INSIDE A SINK CALLBACK.  The callback runs on the thread that runs p264pipe_run, after the
  * round's marker and before the next round's reconstruct is queued: with a decode-order sink the pictures the callback has just
  * received are exactly the "last decoded" ones of their streams.  That is the detect-then-crop cascade: the sink hands round r's

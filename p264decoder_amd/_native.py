@@ -400,6 +400,19 @@ def load(path=None):
         lib.p264hip_rois_check.argtypes = [C.POINTER(Roi), C.c_int, C.POINTER(Resize), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int]
         lib.p264hip_export_rois.restype = C.c_int
         lib.p264hip_export_rois.argtypes = [C.c_void_p, C.POINTER(Roi), C.c_int, C.POINTER(Resize), C.c_uint32, C.c_void_p, C.c_size_t]
+    if hasattr(lib, "p264hip_export_rois_aa"):
+        lib.p264hip_rois_aa_frame_bytes.restype = C.c_int64
+        lib.p264hip_rois_aa_frame_bytes.argtypes = lib.p264hip_rois_frame_bytes.argtypes
+        lib.p264hip_rois_aa_check.restype = C.c_int
+        lib.p264hip_rois_aa_check.argtypes = lib.p264hip_rois_check.argtypes
+        lib.p264hip_export_rois_aa.restype = C.c_int
+        lib.p264hip_export_rois_aa.argtypes = lib.p264hip_export_rois.argtypes
+        lib.p264hip_roi_aa_segment_words.restype = C.c_int
+        lib.p264hip_roi_aa_segment_words.argtypes = [C.POINTER(Roi), C.POINTER(Resize)]
+        lib.p264hip_roi_aa_segment.restype = C.c_int
+        lib.p264hip_roi_aa_segment.argtypes = [C.POINTER(Roi), C.POINTER(Resize), C.POINTER(C.c_uint32)]
+        lib.p264hip_roi_aa_tile_width.restype = C.c_int
+        lib.p264hip_roi_aa_tile_width.argtypes = [C.POINTER(Roi), C.POINTER(Resize), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if hasattr(lib, "p264pipe_export_last_rois"):
         lib.p264pipe_export_last_rois.restype = C.c_int
         lib.p264pipe_export_last_rois.argtypes = [C.c_void_p, C.POINTER(Roi), C.c_int, C.POINTER(Resize), C.c_uint32, C.c_void_p, C.c_size_t]

@@ -82,6 +82,38 @@ __device__ __forceinline__ void aa_span(const uint32_t *table, const AaAxis &ax,
     ns = min((((int)(b & 0xffffu) + (int)(b >> 16) - 1) >> sh) - strip0 + 1, ns_max);
 }
 
+// pass 2, one sample: the column weights of destination index xx of the axis over a row of t whose first strip is strip0
+__device__ __forceinline__ int aa_col_luma(const uint32_t *table, const AaAxis &ax, int xx, int strip0, const uint16_t *trow)
+{
+    const uint32_t pw = gload1(table + ax.pos + xx);
+    const int first = (int)(pw & 0xffffu) - strip0 * 16, count = (int)(pw >> 16);
+    const uint16_t *w = (const uint16_t *)(table + ax.wts) + xx * ax.stride;
+    uint32_t sum = 1u << 20;
+    for (int k = 0; k < count; k++) sum += __umul24(gu16(w + k), (uint32_t)trow[first + k]);
+    return (int)(sum >> 21);
+}
+// the same for a chroma sample, U and V: a strip row of t is 8 of U, then 8 of V
+__device__ __forceinline__ void aa_col_chroma(const uint32_t *table, const AaAxis &ax, int xx, int strip0, const uint16_t *trow, int &u, int &v)
+{
+    const uint32_t pw = gload1(table + ax.pos + xx);
+    const int first = (int)(pw & 0xffffu) - strip0 * 8, count = (int)(pw >> 16);
+    const uint16_t *w = (const uint16_t *)(table + ax.wts) + xx * ax.stride;
+    uint32_t su = 1u << 20, sv = 1u << 20;
+    for (int k = 0; k < count; k++) {
+        const int c = first + k, at = ((c >> 3) << 4) + (c & 7);
+        const uint32_t wk = gu16(w + k);
+        su += __umul24(wk, (uint32_t)trow[at]); sv += __umul24(wk, (uint32_t)trow[at + 8]);
+    }
+    u = (int)(su >> 21); v = (int)(sv >> 21);
+}
+// the chroma of a luma lane's two pairs out of the tile's resized chroma (RGB formats): lane q of luma row `row`
+__device__ __forceinline__ void aa_lane_chroma(const uint32_t (&cs)[2][AA_TH / 2][AA_TW / 8], int row, int q, int (&cb)[2], int (&cr)[2])
+{
+    const uint32_t uw = cs[0][row >> 1][q >> 1] >> (16 * (q & 1)), vw = cs[1][row >> 1][q >> 1] >> (16 * (q & 1));
+    cb[0] = (int)(uw & 255u) - 128; cb[1] = (int)((uw >> 8) & 255u) - 128;
+    cr[0] = (int)(vw & 255u) - 128; cr[1] = (int)((vw >> 8) & 255u) - 128;
+}
+
 template <int FMT, int DT>
 __device__ __forceinline__ void resize_aa_body(const uint8_t *frames, size_t frame_bytes, const Geom &g, const uint32_t *table, int pic_base, uint8_t *dst, const AaParams &e)
 {
@@ -108,19 +140,7 @@ __device__ __forceinline__ void resize_aa_body(const uint8_t *frames, size_t fra
             const uint16_t *trow = t + row * (e.ns_c * 16);
             int u[4], v[4];
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int xx = min(x + j, cw - 1);
-                const uint32_t pw = gload1(table + e.xc.pos + xx);
-                const int first = (int)(pw & 0xffffu) - strip0 * 8, count = (int)(pw >> 16);
-                const uint16_t *w = (const uint16_t *)(table + e.xc.wts) + xx * e.xc.stride;
-                uint32_t su = 1u << 20, sv = 1u << 20;
-                for (int k = 0; k < count; k++) {
-                    const int c = first + k, at = ((c >> 3) << 4) + (c & 7);
-                    const uint32_t wk = gu16(w + k);
-                    su += __umul24(wk, (uint32_t)trow[at]); sv += __umul24(wk, (uint32_t)trow[at + 8]);
-                }
-                u[j] = (int)(su >> 21); v[j] = (int)(sv >> 21);
-            }
+            for (int j = 0; j < 4; j++) aa_col_chroma(table, e.xc, min(x + j, cw - 1), strip0, trow, u[j], v[j]);
             if (RGB) { cs[0][row][q] = pack4(u[0], u[1], u[2], u[3]); cs[1][row][q] = pack4(v[0], v[1], v[2], v[3]); }
             else put_chroma4<FMT>(out, cy0 + row, x, u, v, min(cw - x, RESIZE_PX), e.r);
         }
@@ -137,20 +157,8 @@ __device__ __forceinline__ void resize_aa_body(const uint8_t *frames, size_t fra
             const uint16_t *trow = t + row * (e.ns_l * 16);
             int v[4], cb[2] = { 0, 0 }, cr[2] = { 0, 0 };
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int xx = min(x + j, W - 1);
-                const uint32_t pw = gload1(table + e.xl.pos + xx);
-                const int first = (int)(pw & 0xffffu) - strip0 * 16, count = (int)(pw >> 16);
-                const uint16_t *w = (const uint16_t *)(table + e.xl.wts) + xx * e.xl.stride;
-                uint32_t sum = 1u << 20;
-                for (int k = 0; k < count; k++) sum += __umul24(gu16(w + k), (uint32_t)trow[first + k]);
-                v[j] = (int)(sum >> 21);
-            }
-            if (RGB) {
-                const uint32_t uw = cs[0][row >> 1][q >> 1] >> (16 * (q & 1)), vw = cs[1][row >> 1][q >> 1] >> (16 * (q & 1));
-                cb[0] = (int)(uw & 255u) - 128; cb[1] = (int)((uw >> 8) & 255u) - 128;
-                cr[0] = (int)(vw & 255u) - 128; cr[1] = (int)((vw >> 8) & 255u) - 128;
-            }
+            for (int j = 0; j < 4; j++) v[j] = aa_col_luma(table, e.xl, min(x + j, W - 1), strip0, trow);
+            if (RGB) aa_lane_chroma(cs, row, q, cb, cr);
             put_luma4<FMT, DT>(out + (int64_t)(y0 + row) * e.r.pitch, x, v, cb, cr, min(W - x, RESIZE_PX), e.r);
         }
     }

@@ -27,6 +27,7 @@
 #include "kernel_resize.h"
 #include "kernel_resize_aa.h"
 #include "kernel_roi.h"
+#include "kernel_roi_aa.h"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -808,39 +809,43 @@ extern "C" int p264hip_export_resized(p264hip_ctx *c, const int *streams, const 
 }
 
 // ---- a window per picture into a rectangle of the output (include/p264hip.h: p264hip_roi_t; kernel_roi.h) ----
+extern "C" const char *p264hip_rois_aa_why_(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int *bad);
 extern "C" const char *p264hip_rois_why_(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int *bad);     // csrc/host/resize_layout.c
 
+#define ROI_AA_LAUNCH(name) hipLaunchKernelGGL(name, grid, dim3(AA_THREADS), lds, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const RoiDev *)c->d_exp[r], (const uint32_t *)c->d_roi, base, (uint8_t *)dst, pa, fill)
 #define ROI_LAUNCH(name) hipLaunchKernelGGL(name, grid, dim3(RESIZE_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const RoiDev *)c->d_exp[r], (const uint32_t *)c->d_roi, base, (uint8_t *)dst, p, fill)
 
-extern "C" int p264hip_export_rois(p264hip_ctx *c, const p264hip_roi_t *rois, int n, const p264hip_resize_t *e, uint32_t fill, void *dst, size_t dst_bytes)
+// p264hip_export_rois (aa false) and p264hip_export_rois_aa: the checks, the descriptors and the launch pairs are one text
+static int export_rois(p264hip_ctx *c, const p264hip_roi_t *rois, int n, const p264hip_resize_t *e, uint32_t fill, void *dst, size_t dst_bytes, bool aa)
 {
-    if (!c || !dst) return fail(P264HIP_EINVAL, "p264hip_export_rois: bad argument (n %d)", n);
+    const char *fn = aa ? "p264hip_export_rois_aa" : "p264hip_export_rois";
+    if (!c || !dst) return fail(P264HIP_EINVAL, "%s: bad argument (n %d)", fn, n);
     int bad;
-    if (const char *why = p264hip_rois_why_(rois, n, e, fill, c->g.mb_w, c->g.mb_h, c->n_streams, c->slots, &bad)) {
-        if (bad < 0) return fail(P264HIP_EINVAL, "p264hip_export_rois: %s (n %d, fill 0x%x)", why, n, fill);
+    if (const char *why = (aa ? p264hip_rois_aa_why_ : p264hip_rois_why_)(rois, n, e, fill, c->g.mb_w, c->g.mb_h, c->n_streams, c->slots, &bad)) {
+        if (bad < 0) return fail(P264HIP_EINVAL, "%s: %s (n %d, fill 0x%x)", fn, why, n, fill);
         const p264hip_roi_t &o = rois[bad];
-        return fail(P264HIP_EINVAL, "p264hip_export_rois: ROI %d: %s (stream %d slot %d of %d x %d, window %d,%d %dx%d in a %dx%d frame, rectangle %d,%d %dx%d in %dx%d)", bad, why,
+        return fail(P264HIP_EINVAL, "%s: ROI %d: %s (stream %d slot %d of %d x %d, window %d,%d %dx%d in a %dx%d frame, rectangle %d,%d %dx%d in %dx%d)", fn, bad, why,
                     o.stream, o.slot, c->n_streams, c->slots, o.left, o.top, o.width, o.height, c->g.w, c->g.h, o.dst_left, o.dst_top, o.dst_width, o.dst_height, e->width, e->height);
     }
-    if (c->g.w > 65535 || c->g.h > 65535) return fail(P264HIP_EINVAL, "p264hip_export_rois: a frame of %dx%d samples (a tap holds a coordinate in 16 bits)", c->g.w, c->g.h);
+    if (c->g.w > 65535 || c->g.h > 65535) return fail(P264HIP_EINVAL, "%s: a frame of %dx%d samples (a tap holds a coordinate in 16 bits)", fn, c->g.w, c->g.h);
     const int elem = e->dtype == P264HIP_DTYPE_U8 ? 1 : e->dtype == P264HIP_DTYPE_F16 ? 2 : 4;
-    if ((uintptr_t)dst % (uintptr_t)elem) return fail(P264HIP_EINVAL, "p264hip_export_rois: dst is no multiple of the element size %d", elem);
-    const int64_t bytes = p264hip_rois_frame_bytes(e), stride = e->frame_stride ? e->frame_stride : bytes;
+    if ((uintptr_t)dst % (uintptr_t)elem) return fail(P264HIP_EINVAL, "%s: dst is no multiple of the element size %d", fn, elem);
+    const int64_t bytes = aa ? p264hip_rois_aa_frame_bytes(e) : p264hip_rois_frame_bytes(e), stride = e->frame_stride ? e->frame_stride : bytes;
     const int64_t pitch = e->pitch ? e->pitch : (e->format == P264HIP_FMT_RGB24 ? 3 * (int64_t)e->width : (int64_t)e->width) * elem;
-    if (n > 1 && stride > (INT64_MAX - bytes) / (n - 1)) return fail(P264HIP_EINVAL, "p264hip_export_rois: %d pictures %lld bytes apart", n, (long long)stride);
+    if (n > 1 && stride > (INT64_MAX - bytes) / (n - 1)) return fail(P264HIP_EINVAL, "%s: %d pictures %lld bytes apart", fn, n, (long long)stride);
     const uint64_t need = (uint64_t)(n - 1) * (uint64_t)stride + (uint64_t)bytes;
-    if ((uint64_t)dst_bytes < need) return fail(P264HIP_EINVAL, "p264hip_export_rois: %d pictures need %llu bytes, dst has %zu", n, (unsigned long long)need, dst_bytes);
+    if ((uint64_t)dst_bytes < need) return fail(P264HIP_EINVAL, "%s: %d pictures need %llu bytes, dst has %zu", fn, n, (unsigned long long)need, dst_bytes);
     constexpr int desc_words = (int)(sizeof(RoiDev) / sizeof(uint32_t));
-    if (n > INT32_MAX / desc_words - 16) return fail(P264HIP_ENOMEM, "p264hip_export_rois: %d descriptors", n);
+    if (n > INT32_MAX / desc_words - 16) return fail(P264HIP_ENOMEM, "%s: %d descriptors", fn, n);
     HIPCHK(hipSetDevice(c->device));
     int rc = export_reserve(c, n * desc_words);
     if (rc) return rc;
     const int r = c->exp_ring; c->exp_ring = (c->exp_ring + 1) % BATCH_RING;
     HIPCHK(hipEventSynchronize(c->exp_free[r]));              // the copy that last used this staging buffer is done
     // the descriptors, and the launch pairs: ROIs first .. first + count - 1 of a pair share the scratch, a segment each from word 0 on
-    // (one segment is at most 49152 words, so every pair holds at least one ROI)
+    // (one segment is at most 49152 words - 300 000 with weights -, so every pair holds at least one ROI)
     constexpr size_t scratch_words = P264HIP_ROI_SCRATCH_BYTES / sizeof(uint32_t);
-    struct Pair { int first, count, widest; };
+    struct Pair { int first, count, widest, tiles, lds; };   // (tiles, lds: the grid and the dynamic LDS of the pair's k_roi_aa_* launches)
     std::vector<Pair> pairs;
     RoiDev *t = (RoiDev *)c->h_exp[r];
     const int W = e->width, H = e->height;
@@ -849,13 +854,24 @@ extern "C" int p264hip_export_rois(p264hip_ctx *c, const p264hip_roi_t *rois, in
         const p264hip_roi_t &o = rois[i];
         const bool whole = !(o.dst_left | o.dst_top | o.dst_width | o.dst_height);
         const int dl = whole ? 0 : o.dst_left, dt = whole ? 0 : o.dst_top, dw = whole ? W : o.dst_width, dh = whole ? H : o.dst_height;
-        const int words = roi_seg_words(dw, dh);
-        if (pairs.empty() || used + (size_t)words > scratch_words) { pairs.push_back({ i, 0, 0 }); used = 0; }
+        const int words = aa ? p264hip_roi_aa_words(o.width, o.height, dw, dh) : roi_seg_words(dw, dh);
+        if (pairs.empty() || used + (size_t)words > scratch_words) { pairs.push_back({ i, 0, 0, 0, 0 }); used = 0; }
         Pair &pr = pairs.back();
         t[i] = RoiDev{ (uint32_t)(o.stream * c->slots + o.slot), (uint32_t)used, (uint32_t)dl | (uint32_t)dw << 16, (uint32_t)dt | (uint32_t)dh << 16,
                        (uint32_t)o.left | (uint32_t)o.width << 16, (uint32_t)o.top | (uint32_t)o.height << 16, { 0, 0 } };
+        const int entries = roi_seg_words(dw, dh);          // (filter 0: a word each; the antialiased filter: an entry of p264hip_aa.h each)
+        if (aa) {
+            // the ROI's tile width and LDS rows, and its four weight strides (kernel_roi_aa.h)
+            int ns_l, ns_c;
+            const int tw_shift = p264hip_roi_aa_tile(o.width, dw, AA_T_CAP, &ns_l, &ns_c), tw = 4 << tw_shift;
+            t[i].pad[0] = (uint32_t)tw_shift | (uint32_t)ns_l << 8 | (uint32_t)ns_c << 16;
+            t[i].pad[1] = (uint32_t)p264hip_aa_stride(o.width, dw) | (uint32_t)p264hip_aa_stride(o.height, dh) << 8
+                        | (uint32_t)p264hip_aa_stride(o.width >> 1, dw >> 1) << 16 | (uint32_t)p264hip_aa_stride(o.height >> 1, dh >> 1) << 24;
+            const int tiles = ((W + tw - 1) / tw) * ((H + AA_TH - 1) / AA_TH), lds = 32 * (ns_l * AA_TH > ns_c * (AA_TH / 2) ? ns_l * AA_TH : ns_c * (AA_TH / 2));
+            pr.tiles = tiles > pr.tiles ? tiles : pr.tiles; pr.lds = lds > pr.lds ? lds : pr.lds;
+        }
         used += (size_t)words; pr.count++;
-        pr.widest = words > pr.widest ? words : pr.widest;
+        pr.widest = entries > pr.widest ? entries : pr.widest;
         most = used > most ? used : most;
     }
     if ((rc = grow(c, (void **)&c->d_roi, &c->roi_cap, most * sizeof(uint32_t), 0, false, WAIT_STREAM, "the ROI taps"))) return rc;
@@ -873,6 +889,36 @@ extern "C" int p264hip_export_rois(p264hip_ctx *c, const p264hip_roi_t *rois, in
     p.cy = k[0]; p.yo = e->full_range ? 0 : 16; p.r_cv = k[1]; p.g_cu = k[2]; p.g_cv = k[3]; p.b_cu = k[4];
     for (int i = 0; i < 3; i++) { p.scale[i] = e->scale[i]; p.bias[i] = e->bias[i]; }
     const unsigned gx = (unsigned)((p.n_tiles + RESIZE_THREADS / WAVE - 1) / (RESIZE_THREADS / WAVE));
+    if (aa) {
+        RoiAaParams pa = {};
+        pa.r = p;
+        pa.tile_rows = (H + AA_TH - 1) / AA_TH;
+        for (int s = 1; s <= 4; s++) pa.inv_ntx[s - 1] = 0xffffffffu / (uint32_t)((W + (4 << s) - 1) / (4 << s));
+        for (const Pair &pr : pairs) {                      // (one stream: a pair's taps are read before the next pair's are written)
+            const unsigned tx = (unsigned)((pr.widest + ROI_TAPS_THREADS - 1) / ROI_TAPS_THREADS);
+            for (int base = pr.first; base < pr.first + pr.count; base += 65535) {        // (a grid's second dimension ends at 65535)
+                const int left = pr.first + pr.count - base;
+                hipLaunchKernelGGL(k_roi_aa_taps, dim3(tx, (unsigned)(left < 65535 ? left : 65535)), dim3(ROI_TAPS_THREADS), 0, c->stream, (const RoiDev *)c->d_exp[r], base, c->d_roi);
+            }
+            for (int base = pr.first; base < pr.first + pr.count; base += 65535) {
+                const int left = pr.first + pr.count - base;
+                const dim3 grid((unsigned)pr.tiles, (unsigned)(left < 65535 ? left : 65535));
+                const size_t lds = (size_t)pr.lds;
+                switch (e->format * 3 + e->dtype) {
+                case P264HIP_FMT_I420 * 3:                       ROI_AA_LAUNCH(k_roi_aa_i420); break;
+                case P264HIP_FMT_NV12 * 3:                       ROI_AA_LAUNCH(k_roi_aa_nv12); break;
+                case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_U8:   ROI_AA_LAUNCH(k_roi_aa_rgb24_u8); break;
+                case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F16:  ROI_AA_LAUNCH(k_roi_aa_rgb24_f16); break;
+                case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F32:  ROI_AA_LAUNCH(k_roi_aa_rgb24_f32); break;
+                case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_U8:    ROI_AA_LAUNCH(k_roi_aa_rgbp_u8); break;
+                case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_F16:   ROI_AA_LAUNCH(k_roi_aa_rgbp_f16); break;
+                default:                                         ROI_AA_LAUNCH(k_roi_aa_rgbp_f32); break;
+                }
+            }
+        }
+        HIPCHK(hipGetLastError());
+        return P264HIP_OK;
+    }
     for (const Pair &pr : pairs) {                          // (one stream: a pair's taps are read before the next pair's are written)
         const unsigned tx = (unsigned)((pr.widest + ROI_TAPS_THREADS - 1) / ROI_TAPS_THREADS);
         for (int base = pr.first; base < pr.first + pr.count; base += 65535) {            // (a grid's second dimension ends at 65535)
@@ -896,6 +942,15 @@ extern "C" int p264hip_export_rois(p264hip_ctx *c, const p264hip_roi_t *rois, in
     }
     HIPCHK(hipGetLastError());
     return P264HIP_OK;
+}
+
+extern "C" int p264hip_export_rois(p264hip_ctx *c, const p264hip_roi_t *rois, int n, const p264hip_resize_t *e, uint32_t fill, void *dst, size_t dst_bytes)
+{
+    return export_rois(c, rois, n, e, fill, dst, dst_bytes, false);
+}
+extern "C" int p264hip_export_rois_aa(p264hip_ctx *c, const p264hip_roi_t *rois, int n, const p264hip_resize_t *e, uint32_t fill, void *dst, size_t dst_bytes)
+{
+    return export_rois(c, rois, n, e, fill, dst, dst_bytes, true);
 }
 
 extern "C" int p264hip_copy_to_device(void *dev, const void *host, size_t bytes)

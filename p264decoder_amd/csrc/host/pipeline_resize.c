@@ -15,7 +15,7 @@ int p264pipe_export_last_resized(p264pipe *p, const p264hip_resize_t *r, void *d
     return p264pipe_export_last_with_(p, "p264pipe_export_last_resized", export_resized, r, dst_dev, bytes);
 }
 
-/* per-picture windows of the streams' last decoded pictures (p264hip_roi_t / p264hip_export_rois): slot -1 becomes the stream's slot */
+/* per-picture windows of the streams' last decoded pictures (p264hip_roi_t / p264hip_export_rois, p264hip_export_rois_aa by r->filter): slot -1 becomes the stream's slot */
 int p264pipe_export_last_rois(p264pipe *p, const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, void *dst_dev, size_t bytes)
 {
     if (!p || !rois || n < 1 || !r || !dst_dev) return -1;
@@ -32,7 +32,8 @@ int p264pipe_export_last_rois(p264pipe *p, const p264hip_roi_t *rois, int n, con
         }
         mine[i] = rois[i]; mine[i].slot = slot;
     }
-    if (!rc && (p264hip_export_rois(ctx, mine, n, r, fill, dst_dev, bytes) || p264hip_sync(ctx))) {
+    /* (the antialiased filter has entry points of its own; any other value is p264hip_export_rois' to accept or refuse) */
+    if (!rc && ((r->filter == P264HIP_FILTER_BILINEAR_AA ? p264hip_export_rois_aa : p264hip_export_rois)(ctx, mine, n, r, fill, dst_dev, bytes) || p264hip_sync(ctx))) {
         fprintf(stderr, "p264pipe_export_last_rois: %s\n", p264hip_last_error()); rc = -1;
     }
     free(mine);

@@ -1,9 +1,11 @@
 /* resize_layout.c - the layout of a resized exported picture (include/p264hip.h: p264hip_resize_t), the checks every resized
- * export runs before anything is queued - the list of per-picture windows of p264hip_export_rois among them -, and the taps of the
- * two filters.  Pure host code, no device involved; the kernels are csrc/hip/kernel_resize.h, kernel_resize_aa.h and kernel_roi.h. */
+ * export runs before anything is queued - the lists of per-picture windows of p264hip_export_rois and p264hip_export_rois_aa among
+ * them -, the taps of the two filters and the tap segment of an ROI.  Pure host code, no device involved; the kernels are
+ * csrc/hip/kernel_resize.h, kernel_resize_aa.h, kernel_roi.h and kernel_roi_aa.h. */
 #include <math.h>
 #include "p264hip.h"
 #include "p264hip_pos.h"
+#include "p264hip_aa.h"
 
 static int is_rgb(int format) { return format == P264HIP_FMT_RGB24 || format == P264HIP_FMT_RGBP; }
 
@@ -83,11 +85,13 @@ static p264hip_resize_t without_window(const p264hip_resize_t *r)
 }
 
 /* why the call is refused (NULL: it is not); *bad: the index of the first bad ROI, -1 where the call is refused on its own */
-const char *p264hip_rois_why_(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int *bad)
+/* aa: the call is p264hip_export_rois_aa's, whose filter is the antialiased one, limited to 32:1 per ROI */
+static const char *rois_why(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int *bad, int aa)
 {
     *bad = -1;
     if (!r) return "null description";
-    if (r->filter == P264HIP_FILTER_BILINEAR_AA) return "the antialiased filter has no per-picture windows (filter must be P264HIP_FILTER_BILINEAR)";
+    if (!aa && r->filter == P264HIP_FILTER_BILINEAR_AA) return "the antialiased filter is p264hip_export_rois_aa's (filter must be P264HIP_FILTER_BILINEAR)";
+    if (aa && r->filter != P264HIP_FILTER_BILINEAR_AA) return "filter must be P264HIP_FILTER_BILINEAR_AA (p264hip_export_rois has the plain bilinear filter)";
     const p264hip_resize_t q = without_window(r);
     const char *why = p264hip_resize_why_(&q, mb_w, mb_h);
     if (why) return why;
@@ -103,13 +107,22 @@ const char *p264hip_rois_why_(const p264hip_roi_t *rois, int n, const p264hip_re
         if (o->left < 0 || o->top < 0 || o->width < 1 || o->height < 1) return "window with a negative offset or without samples";
         if ((o->left | o->top | o->width | o->height) & 1) return "window with an odd member";
         if ((int64_t)o->left + o->width > fw || (int64_t)o->top + o->height > fh) return "window leaves the frame";
-        if (!(o->dst_left | o->dst_top | o->dst_width | o->dst_height)) continue;          /* the whole output */
-        if (o->dst_left < 0 || o->dst_top < 0 || o->dst_width < 2 || o->dst_height < 2) return "rectangle with a negative offset or below 2 x 2";
-        if ((o->dst_left | o->dst_top | o->dst_width | o->dst_height) & 1) return "rectangle with an odd member";
-        if ((int64_t)o->dst_left + o->dst_width > r->width || (int64_t)o->dst_top + o->dst_height > r->height) return "rectangle leaves the output";
+        const int whole = !(o->dst_left | o->dst_top | o->dst_width | o->dst_height);
+        if (!whole) {
+            if (o->dst_left < 0 || o->dst_top < 0 || o->dst_width < 2 || o->dst_height < 2) return "rectangle with a negative offset or below 2 x 2";
+            if ((o->dst_left | o->dst_top | o->dst_width | o->dst_height) & 1) return "rectangle with an odd member";
+            if ((int64_t)o->dst_left + o->dst_width > r->width || (int64_t)o->dst_top + o->dst_height > r->height) return "rectangle leaves the output";
+        }
+        if (aa && (o->width > 32 * (int64_t)(whole ? r->width : o->dst_width) || o->height > 32 * (int64_t)(whole ? r->height : o->dst_height)))
+            return "reduction above 32:1 with the antialiased filter";
     }
     *bad = -1;
     return 0;
+}
+
+const char *p264hip_rois_why_(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int *bad)
+{
+    return rois_why(rois, n, r, fill, mb_w, mb_h, n_streams, slots, bad, 0);
 }
 
 int64_t p264hip_rois_frame_bytes(const p264hip_resize_t *r)
@@ -125,34 +138,69 @@ int p264hip_rois_check(const p264hip_roi_t *rois, int n, const p264hip_resize_t 
     return p264hip_rois_why_(rois, n, r, fill, mb_w, mb_h, n_streams, slots, &bad) ? P264HIP_EINVAL : P264HIP_OK;
 }
 
-static int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }        /* b > 0 */
-
 int p264hip_resize_aa_taps(int src_n, int dst_n, int32_t *first, int32_t *count, uint16_t *weights)
 {
     if (!first || !count || !weights || src_n < 1 || dst_n < 1 || src_n > (1 << 20) || dst_n > (1 << 20) || (int64_t)src_n > 32 * (int64_t)dst_n) return P264HIP_EINVAL;
-    const int64_t S = src_n, D = dst_n, U = 2 * (S > D ? S : D);
-    for (int64_t d = 0; d < D; d++) {
-        const int64_t c = (2 * d + 1) * S;
-        /* r(j) > 0: c - U < (2j+1)*D < c + U */
-        int64_t lo = floor_div(c - U - D, 2 * D) + 1, hi = -floor_div(-(c + U - D), 2 * D) - 1;
-        if (lo < 0) lo = 0;
-        if (hi > S - 1) hi = S - 1;
-        uint16_t *w = weights + d * P264HIP_AA_MAX_TAPS;
-        int64_t R = 0, best = -1, sum = 0;
-        int n = 0, at = 0;
-        for (int64_t j = lo; j <= hi && n < P264HIP_AA_MAX_TAPS; j++, n++) {
-            int64_t a = (2 * j + 1) * D - c;
-            R += U - (a < 0 ? -a : a);
-        }
-        for (int k = 0; k < n; k++) {
-            int64_t a = (2 * (lo + k) + 1) * D - c;
-            const int64_t r = U - (a < 0 ? -a : a), q = r * 32768 / R;
-            if (r > best) { best = r; at = k; }
-            w[k] = (uint16_t)q; sum += q;
-        }
-        w[at] = (uint16_t)(w[at] + (32768 - sum));
-        for (int k = n; k < P264HIP_AA_MAX_TAPS; k++) w[k] = 0;
-        first[d] = (int32_t)lo; count[d] = n;
+    for (int d = 0; d < dst_n; d++) {
+        uint16_t *w = weights + (size_t)d * P264HIP_AA_MAX_TAPS;
+        count[d] = p264hip_aa_tap(src_n, dst_n, d, P264HIP_AA_MAX_TAPS, first + d, w);         /* (p264hip_aa.h: the device runs the same text) */
+        for (int k = count[d]; k < P264HIP_AA_MAX_TAPS; k++) w[k] = 0;
     }
     return P264HIP_OK;
+}
+
+/* ---- per-picture windows with the antialiased filter (include/p264hip.h: p264hip_export_rois_aa; csrc/hip/kernel_roi_aa.h) ---- */
+const char *p264hip_rois_aa_why_(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int *bad)
+{
+    return rois_why(rois, n, r, fill, mb_w, mb_h, n_streams, slots, bad, 1);
+}
+
+int64_t p264hip_rois_aa_frame_bytes(const p264hip_resize_t *r)
+{
+    if (!r || r->filter != P264HIP_FILTER_BILINEAR_AA) return P264HIP_EINVAL;
+    const p264hip_resize_t q = without_window(r);
+    return p264hip_resize_frame_bytes(&q);
+}
+
+int p264hip_rois_aa_check(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots)
+{
+    int bad;
+    return p264hip_rois_aa_why_(rois, n, r, fill, mb_w, mb_h, n_streams, slots, &bad) ? P264HIP_EINVAL : P264HIP_OK;
+}
+
+/* the rectangle of an ROI in a W x H output; 0 where the segment helpers cannot take the pair (they check sizes, not the frame) */
+static int segment_rect(const p264hip_roi_t *o, const p264hip_resize_t *r, int *dw, int *dh)
+{
+    if (!o || !r) return 0;
+    const int whole = !(o->dst_left | o->dst_top | o->dst_width | o->dst_height);
+    *dw = whole ? r->width : o->dst_width; *dh = whole ? r->height : o->dst_height;
+    if (*dw < 2 || *dh < 2 || *dw > 16384 || *dh > 16384 || ((*dw | *dh) & 1)) return 0;
+    if (o->left < 0 || o->top < 0 || o->width < 2 || o->height < 2 || ((o->left | o->top | o->width | o->height) & 1)) return 0;
+    if ((int64_t)o->left + o->width > 65536 || (int64_t)o->top + o->height > 65536) return 0;
+    return o->width <= 32 * (int64_t)*dw && o->height <= 32 * (int64_t)*dh;
+}
+
+int p264hip_roi_aa_segment_words(const p264hip_roi_t *roi, const p264hip_resize_t *r)
+{
+    int dw, dh;
+    return segment_rect(roi, r, &dw, &dh) ? p264hip_roi_aa_words(roi->width, roi->height, dw, dh) : P264HIP_EINVAL;
+}
+
+int p264hip_roi_aa_segment(const p264hip_roi_t *roi, const p264hip_resize_t *r, uint32_t *words)
+{
+    int dw, dh;
+    if (!words || !segment_rect(roi, r, &dw, &dh)) return P264HIP_EINVAL;
+    const int n = p264hip_roi_aa_entries(dw, dh);
+    for (int t = 0; t < n; t++) (void)p264hip_roi_aa_entry(words, roi->left, roi->top, roi->width, roi->height, dw, dh, t);   /* (k_roi_aa_taps: a thread each) */
+    return P264HIP_OK;
+}
+
+int p264hip_roi_aa_tile_width(const p264hip_roi_t *roi, const p264hip_resize_t *r, int *luma_strips, int *chroma_strips)
+{
+    int dw, dh, ns_l, ns_c;
+    if (!segment_rect(roi, r, &dw, &dh)) return P264HIP_EINVAL;
+    const int shift = p264hip_roi_aa_tile(roi->width, dw, P264HIP_ROI_AA_TILE_VALUES, &ns_l, &ns_c);
+    if (luma_strips) *luma_strips = ns_l;
+    if (chroma_strips) *chroma_strips = ns_c;
+    return 4 << shift;
 }

@@ -157,17 +157,19 @@ class Pipeline:
         return out
 
     def export_last_rois(self, rois, size, fmt="rgbp", dtype="u8", fill=(16, 128, 128), scale=None, bias=None, matrix="bt601", full_range=False,
-                         pitch=0, frame_stride=0, out=None):
+                         pitch=0, frame_stride=0, out=None, *, filter="bilinear"):
         """Windows of the streams' last DECODED pictures, each resized into a rectangle of the size = (width, height) output with the
         constant `fill` round it (p264pipe_export_last_rois); complete on return.  rois: rows (stream, left, top, width, height) or
         the same with the rectangle (dst_left, dst_top, dst_width, dst_height) behind it, or an (n, 5 | 9) integer array; the other
-        arguments, `out` and the result as HipReconstructor.export_rois has them.  It may be called from inside a sink's callback:
+        arguments, `out` and the result as HipReconstructor.export_rois has them; filter="bilinear_aa" is the antialiased filter
+        (HipReconstructor.export_rois_aa: at most 32:1 per ROI).  It may be called from inside a sink's callback:
         with a decode-order sink the round's pictures are the last decoded ones - detect on the sink's buffer, crop here."""
         arr, n = N.roi_array(rois, head=1)
-        r = N.resize_desc(fmt, size, (0, 0, 2, 2), None, dtype, scale, bias, matrix, full_range, pitch, frame_stride)
-        per = self.lib.p264hip_rois_frame_bytes(C.byref(r))
+        r = N.resize_desc(fmt, size, (0, 0, 2, 2), None, dtype, scale, bias, matrix, full_range, pitch, frame_stride, filter)
+        aa = r.filter == N.FILTER_BILINEAR_AA
+        per = (self.lib.p264hip_rois_aa_frame_bytes if aa else self.lib.p264hip_rois_frame_bytes)(C.byref(r))
         if per < 0:
-            raise RuntimeError("export_last_rois: p264hip_rois_frame_bytes refuses the description")
+            raise RuntimeError("export_last_rois: %s refuses the description" % ("p264hip_rois_aa_frame_bytes" if aa else "p264hip_rois_frame_bytes"))
         if out is None:
             torch = N.import_torch()
             W, H = r.width, r.height

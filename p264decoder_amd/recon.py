@@ -324,16 +324,27 @@ class HipReconstructor:
         of rows, or an (n, 6 | 10) integer array: (stream, slot, left, top, width, height) - the window fills the whole output - or
         the same with the rectangle (dst_left, dst_top, dst_width, dst_height) behind it (_native.letterbox gives one that keeps the
         window's aspect ratio).  The other arguments, `out` and the result are those of export_resized, picture i being ROI i."""
+        return self._export_rois(rois, size, fmt, dtype, fill, scale, bias, matrix, full_range, pitch, frame_stride, out, sync, "bilinear")
+
+    def export_rois_aa(self, rois, size, fmt="rgbp", dtype="u8", fill=(16, 128, 128), scale=None, bias=None, matrix="bt601", full_range=False,
+                       pitch=0, frame_stride=0, out=None, sync=True):
+        """export_rois with the ANTIALIASED filter, the one for reductions - a 1920 x 1080 picture letterboxed into 640 x 640, a
+        detector's boxes at 224 x 224 - (p264hip_export_rois_aa): every argument and the result as export_rois has them.  A window may
+        be at most 32 times its rectangle in width and in height."""
+        return self._export_rois(rois, size, fmt, dtype, fill, scale, bias, matrix, full_range, pitch, frame_stride, out, sync, "bilinear_aa")
+
+    def _export_rois(self, rois, size, fmt, dtype, fill, scale, bias, matrix, full_range, pitch, frame_stride, out, sync, filter):
         arr, n = N.roi_array(rois)
-        r = N.resize_desc(fmt, size, (0, 0, 2, 2), None, dtype, scale, bias, matrix, full_range, pitch, frame_stride)
+        r = N.resize_desc(fmt, size, (0, 0, 2, 2), None, dtype, scale, bias, matrix, full_range, pitch, frame_stride, filter)
         word = N.fill_word(fill)
+        aa = r.filter == N.FILTER_BILINEAR_AA                # (its own entry points; any other value is p264hip_export_rois' to refuse)
         if out is None or not isinstance(out, tuple):
             torch = N.import_torch()                      # only here: the module imports without torch or a GPU
             want = {N.DTYPE_U8: torch.uint8, N.DTYPE_F16: torch.float16, N.DTYPE_F32: torch.float32}.get(r.dtype, torch.uint8)
         if out is None:
-            per = self.lib.p264hip_rois_frame_bytes(C.byref(r))
+            per = (self.lib.p264hip_rois_aa_frame_bytes if aa else self.lib.p264hip_rois_frame_bytes)(C.byref(r))
             if per < 0:
-                raise P264Error("export_rois: p264hip_rois_frame_bytes refuses the description")
+                raise P264Error("export_rois: %s refuses the description" % ("p264hip_rois_aa_frame_bytes" if aa else "p264hip_rois_frame_bytes"))
             W, H = r.width, r.height
             shape = (n, H * 3 // 2, W) if r.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if r.format == N.FMT_RGB24 else (n, 3, H, W)
             if not pitch and not frame_stride:
@@ -347,7 +358,10 @@ class HipReconstructor:
                 raise P264Error("export_rois: out must be a contiguous %s (or uint8) tensor on the device" % want)
             torch.cuda.current_stream(out.device).synchronize()     # (whatever torch still has queued on the tensor: the context has its own stream)
             ptr, cap = out.data_ptr(), out.numel() * out.element_size()
-        self._chk(self.lib.p264hip_export_rois(self.h, arr, n, C.byref(r), word, ptr, cap), "p264hip_export_rois")
+        if aa:
+            self._chk(self.lib.p264hip_export_rois_aa(self.h, arr, n, C.byref(r), word, ptr, cap), "p264hip_export_rois_aa")
+        else:
+            self._chk(self.lib.p264hip_export_rois(self.h, arr, n, C.byref(r), word, ptr, cap), "p264hip_export_rois")
         if sync:
             self.sync()
         return out

@@ -12,7 +12,13 @@ DESIGN.md quotes for K6b.
   c  letterbox: every frame into 640 x 640 planar RGB float16 through letterbox(), beside export_resized to 640 x 360 followed by
      torch.nn.functional.pad on the device.
 
+--aa-out measures the ANTIALIASED filter (p264hip_export_rois_aa, kernel_roi_aa.h) as well: the same three shapes, each beside the same
+call with filter 0 from this build (what the antialiasing costs) and, for the whole frames of case a, beside
+export_resized(filter="bilinear_aa") at the same shape - the kernel the ROI kernels share their passes with, so the ratio is what the
+per-ROI tables, the clipping and the device-made taps cost.  No figure is required of these; DESIGN.md K6c quotes them.
+
   python -m p264decoder_amd.tools.roi_bench [--frames 2048] [--reps 20] [--warmup 3] [--out profiles/roi_bench.json]
+                                            [--aa-out profiles/roi_aa_bench.json [--only-aa]]
 """
 import argparse
 import json
@@ -28,6 +34,103 @@ from p264decoder_amd.tools.resize_bench import H, MB_H, MB_W, MEAN, STD, W, alte
 PER_CALL = 256              # windows of case b the one-call-per-window road is measured on
 
 
+def launch_pairs(lib, rois, size):
+    """how many pairs of launches p264hip_export_rois_aa makes for these ROIs (p264hip.hip: a pair ends where the next segment would
+    cross P264HIP_ROI_SCRATCH_BYTES), and the words of all segments"""
+    import ctypes as C
+    from p264decoder_amd import _native as N
+    r = N.resize_desc("rgbp", size, (0, 0, 2, 2), None, filter="bilinear_aa")
+    arr, n = N.roi_array(rois)
+    pairs, used, total = 1, 0, 0
+    for i in range(n):
+        words = lib.p264hip_roi_aa_segment_words(C.byref(arr[i]), C.byref(r))
+        assert words > 0
+        if used + words > N.ROI_SCRATCH_BYTES // 4:
+            pairs, used = pairs + 1, 0
+        used += words
+        total += words
+    return pairs, total
+
+
+def tile_widths(lib, rois, size):
+    """{tile width: ROIs} as k_roi_aa_* run them"""
+    import ctypes as C
+    from p264decoder_amd import _native as N
+    r = N.resize_desc("rgbp", size, (0, 0, 2, 2), None, filter="bilinear_aa")
+    arr, n = N.roi_array(rois)
+    hist = {}
+    for i in range(n):
+        tw = lib.p264hip_roi_aa_tile_width(C.byref(arr[i]), C.byref(r), None, None)
+        hist[tw] = hist.get(tw, 0) + 1
+    return {str(k): hist[k] for k in sorted(hist)}
+
+
+def aa_cases(args, hip, streams, slots, scale, bias):
+    """the three shapes with filter 2, each beside filter 0 and - whole frames - beside export_resized with filter 2"""
+    import numpy as np
+    import torch
+    from p264decoder_amd import letterbox
+    n = args.frames
+    src = W * H * 3 // 2
+    res = {"metric": "antialiased export of per-picture windows out of %d 1080p frames" % n, "unit": "pictures/s", "frames": n, "reps": args.reps, "warmup": args.warmup, "cases": {}}
+
+    def mem(t):
+        return (t.data_ptr(), t.numel() * t.element_size())
+
+    def table(rois, size, dtype, fill, sb, out, extra=None):
+        roads = {"aa": lambda: hip.export_rois_aa(rois, size, "rgbp", dtype, fill, sb[0], sb[1], out=mem(out)),
+                 "bilinear": lambda: hip.export_rois(rois, size, "rgbp", dtype, fill, sb[0], sb[1], out=mem(out))}
+        roads.update(extra or {})
+        return alternating(roads, args.warmup, args.reps)
+
+    if "a" in args.only:
+        out = torch.empty((n, 3, 224, 224), dtype=torch.float32, device="cuda")
+        rois = np.array([(s, k, 0, 0, W, H) for s, k in zip(streams, slots)], np.int32)
+        t = table(rois, (224, 224), "f32", (16, 128, 128), (scale, bias), out,
+                  {"resized_aa": lambda: hip.export_resized(streams, slots, (224, 224), "rgbp", "f32", (0, 0, W, H), scale, bias, out=mem(out), filter="bilinear_aa")})
+        moved = n * (src + 3 * 224 * 224 * 4)
+        pairs, words = launch_pairs(hip.lib, rois, (224, 224))
+        res["cases"]["a_whole_frames_rgbp_f32_224x224_normalised"] = {
+            "p264hip_export_rois_aa": entry(n, t["aa"], moved), "p264hip_export_rois_filter_0": entry(n, t["bilinear"]),
+            "p264hip_export_resized_filter_2": entry(n, t["resized_aa"], moved),
+            "cost_over_filter_0": round(t["aa"][0] / t["bilinear"][0], 2), "time_over_export_resized_filter_2": round(t["aa"][0] / t["resized_aa"][0], 3),
+            "launch_pairs": pairs, "segment_words": words, "tile_widths": tile_widths(hip.lib, rois[:1], (224, 224))}
+        res["value"] = res["cases"]["a_whole_frames_rgbp_f32_224x224_normalised"]["p264hip_export_rois_aa"]["frames_per_s"]
+        del out
+    if "b" in args.only:
+        g = np.random.default_rng(2663)                     # (the windows of case b above)
+        m = 2 * n
+        ww, wh = 2 * g.integers(32, 257, m), 2 * g.integers(32, 257, m)
+        left, top = 2 * (g.integers(0, 1 << 30, m) % ((W - ww) // 2 + 1)), 2 * (g.integers(0, 1 << 30, m) % ((H - wh) // 2 + 1))
+        rois = np.stack([np.arange(m) // 2, np.arange(m) & 1, left, top, ww, wh], axis=1).astype(np.int32)
+        out = torch.empty((m, 3, 224, 224), dtype=torch.float32, device="cuda")
+        t = table(rois, (224, 224), "f32", (16, 128, 128), (scale, bias), out)
+        read = int((rois[:, 4].astype(np.int64) * rois[:, 5] * 3 // 2).sum())
+        pairs, words = launch_pairs(hip.lib, rois, (224, 224))
+        res["cases"]["b_drawn_windows_rgbp_f32_224x224_normalised"] = {
+            "windows": m, "window_side": "64 .. 512, even, seeded", "p264hip_export_rois_aa_one_call": entry(m, t["aa"], read + m * 3 * 224 * 224 * 4),
+            "p264hip_export_rois_filter_0_one_call": entry(m, t["bilinear"]), "cost_over_filter_0": round(t["aa"][0] / t["bilinear"][0], 2),
+            "launch_pairs": pairs, "segment_words": words, "tile_widths": tile_widths(hip.lib, rois, (224, 224))}
+        del out
+    if "c" in args.only:
+        rect = letterbox(W, H, 640, 640)
+        boxed = torch.empty((n, 3, 640, 640), dtype=torch.float16, device="cuda")
+        rois = np.array([(s, k, 0, 0, W, H) + rect for s, k in zip(streams, slots)], np.int32)
+        strip = torch.empty((n, 3, 360, 640), dtype=torch.float16, device="cuda")
+        t = table(rois, (640, 640), "f16", (16, 128, 128), (1 / 255, 0.0), boxed,
+                  {"resized_aa": lambda: hip.export_resized(streams, slots, (640, 360), "rgbp", "f16", (0, 0, W, H), 1 / 255, 0.0, out=mem(strip), filter="bilinear_aa")})
+        hip.export_rois_aa(rois, (640, 640), "rgbp", "f16", (16, 128, 128), 1 / 255, 0.0, out=mem(boxed))         # (the last road into `boxed` was filter 0)
+        same = bool(torch.equal(boxed[:, :, rect[1]:rect[1] + rect[3], :], strip))
+        pairs, words = launch_pairs(hip.lib, rois, (640, 640))
+        res["cases"]["c_letterbox_rgbp_f16_640x640"] = {
+            "rectangle": list(rect), "p264hip_export_rois_aa": entry(n, t["aa"], n * (src + 3 * 640 * 640 * 2)),
+            "p264hip_export_rois_filter_0": entry(n, t["bilinear"]), "cost_over_filter_0": round(t["aa"][0] / t["bilinear"][0], 2),
+            "p264hip_export_resized_filter_2_to_640x360_without_the_bars": entry(n, t["resized_aa"]),
+            "time_over_export_resized_filter_2_without_the_bars": round(t["aa"][0] / t["resized_aa"][0], 3), "the_rectangle_is_export_resized_filter_2": same,
+            "launch_pairs": pairs, "segment_words": words, "tile_widths": tile_widths(hip.lib, rois[:1], (640, 640))}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=2048, help="frames of the store = streams of the context (2 slots each)")
@@ -35,6 +138,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the result there")
     ap.add_argument("--only", default="abc", help="the cases to run")
+    ap.add_argument("--aa-out", default=None, help="measure the antialiased filter too and write its table there")
+    ap.add_argument("--only-aa", action="store_true", help="with --aa-out: skip the filter-0 cases against the roads that existed before")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -52,6 +157,14 @@ def main():
     def mem(t):
         return (t.data_ptr(), t.numel() * t.element_size())
 
+    if args.aa_out:
+        aa = aa_cases(args, hip, streams, slots, scale, bias)
+        with open(args.aa_out, "w") as f:
+            f.write(json.dumps(aa) + "\n")
+        if args.only_aa:
+            hip.close()
+            print(json.dumps(aa))
+            return
     if "a" in args.only:
         out = torch.empty((n, 3, 224, 224), dtype=torch.float32, device="cuda")
         rois = np.array([(s, k, 0, 0, W, H) for s, k in zip(streams, slots)], np.int32)
