@@ -218,6 +218,33 @@ def fill_word(fill):
     return y | cb << 8 | cr << 16
 
 
+def export_out(n, desc, per, pitch, frame_stride, out, check=None):
+    """(out, pointer, bytes): where an export call writes its n pictures of the description `desc` (p264hip_export_t /
+    p264hip_resize_t), `per` bytes each.  out: a (device pointer, bytes) pair, handed through; a torch tensor on the device; or None -
+    a new tensor (n, H*3//2, W) for I420 / NV12, (n, H, W, 3) for RGB24, (n, 3, H, W) for RGBP of the description's dtype at the tight
+    layout, (n, bytes) uint8 where a pitch or a frame_stride is given.  check = (exception type, method name): refuse a tensor that
+    is not contiguous, on the device and of the dtype (or uint8), and wait for what torch's current stream still has queued on it -
+    the context has its own stream.  torch is imported only where a tensor is involved."""
+    if isinstance(out, tuple):
+        return out, out[0], out[1]
+    torch = import_torch()
+    dtype = getattr(desc, "dtype", None)                 # (None: a p264hip_export_t, bytes)
+    want = {DTYPE_F16: torch.float16, DTYPE_F32: torch.float32}.get(dtype, torch.uint8)
+    if out is None:
+        W, H = desc.width, desc.height
+        shape = (n, H * 3 // 2, W) if desc.format in (FMT_I420, FMT_NV12) else (n, H, W, 3) if desc.format == FMT_RGB24 else (n, 3, H, W)
+        if not pitch and not frame_stride:
+            out = torch.empty(shape, dtype=want, device="cuda")
+        else:
+            out = torch.empty((n, desc.frame_stride or per), dtype=torch.uint8, device="cuda")
+    if check is not None:
+        error, name = check
+        if not (out.is_cuda and out.is_contiguous() and (out.element_size() == 1 if dtype is None else out.dtype in (want, torch.uint8))):
+            raise error("%s: out must be a contiguous %s tensor on the device" % (name, "uint8" if dtype is None else "%s (or uint8)" % want))
+        torch.cuda.current_stream(out.device).synchronize()
+    return out, out.data_ptr(), out.numel() * out.element_size()
+
+
 def letterbox(w, h, W, H):
     """(dst_left, dst_top, dst_width, dst_height): the centred even rectangle of a W x H output that a w x h window fills at its own
     aspect ratio - one side the output's, the other the nearest even number to the exact ratio, at least 2.  Integers only.

@@ -278,15 +278,21 @@ __device__ __forceinline__ void resize_body(const uint8_t *frames, size_t frame_
     }
 }
 
-// (one named kernel per instance: tools/kernel_resources.py and the tests find them by name)
-#define RESIZE_KERNEL(name, fmt, dt) \
-    __global__ __launch_bounds__(RESIZE_THREADS) void name(const uint8_t *frames, size_t frame_bytes, Geom g, const uint32_t *table, int pic_base, uint8_t *dst, ResizeParams e) \
+// The instances of a resizing export: X(family, suffix, format, dtype) for each (format, dtype) the description may name.  The four
+// families - k_resize_*, k_resize_aa_*, k_roi_*, k_roi_aa_* - define their kernels from this list, one named kernel per instance
+// (tools/kernel_resources.py and the tests find them by name: family ## suffix), and the host (p264hip.hip) builds its tables of
+// kernel pointers and the index into them from it.
+#define EXPORT_INSTANCES(X, family) \
+    X(family, i420, P264HIP_FMT_I420, P264HIP_DTYPE_U8) \
+    X(family, nv12, P264HIP_FMT_NV12, P264HIP_DTYPE_U8) \
+    X(family, rgb24_u8, P264HIP_FMT_RGB24, P264HIP_DTYPE_U8) \
+    X(family, rgb24_f16, P264HIP_FMT_RGB24, P264HIP_DTYPE_F16) \
+    X(family, rgb24_f32, P264HIP_FMT_RGB24, P264HIP_DTYPE_F32) \
+    X(family, rgbp_u8, P264HIP_FMT_RGBP, P264HIP_DTYPE_U8) \
+    X(family, rgbp_f16, P264HIP_FMT_RGBP, P264HIP_DTYPE_F16) \
+    X(family, rgbp_f32, P264HIP_FMT_RGBP, P264HIP_DTYPE_F32)
+
+#define RESIZE_KERNEL(family, sfx, fmt, dt) \
+    __global__ __launch_bounds__(RESIZE_THREADS) void family##sfx(const uint8_t *frames, size_t frame_bytes, Geom g, const uint32_t *table, int pic_base, uint8_t *dst, ResizeParams e) \
     { resize_body<fmt, dt>(frames, frame_bytes, g, table, pic_base, dst, e); }
-RESIZE_KERNEL(k_resize_i420, P264HIP_FMT_I420, P264HIP_DTYPE_U8)
-RESIZE_KERNEL(k_resize_nv12, P264HIP_FMT_NV12, P264HIP_DTYPE_U8)
-RESIZE_KERNEL(k_resize_rgb24_u8, P264HIP_FMT_RGB24, P264HIP_DTYPE_U8)
-RESIZE_KERNEL(k_resize_rgb24_f16, P264HIP_FMT_RGB24, P264HIP_DTYPE_F16)
-RESIZE_KERNEL(k_resize_rgb24_f32, P264HIP_FMT_RGB24, P264HIP_DTYPE_F32)
-RESIZE_KERNEL(k_resize_rgbp_u8, P264HIP_FMT_RGBP, P264HIP_DTYPE_U8)
-RESIZE_KERNEL(k_resize_rgbp_f16, P264HIP_FMT_RGBP, P264HIP_DTYPE_F16)
-RESIZE_KERNEL(k_resize_rgbp_f32, P264HIP_FMT_RGBP, P264HIP_DTYPE_F32)
+EXPORT_INSTANCES(RESIZE_KERNEL, k_resize_)

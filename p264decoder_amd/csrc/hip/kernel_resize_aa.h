@@ -164,15 +164,8 @@ __device__ __forceinline__ void resize_aa_body(const uint8_t *frames, size_t fra
     }
 }
 
-// (one named kernel per instance, as kernel_resize.h's)
-#define RESIZE_AA_KERNEL(name, fmt, dt) \
-    __global__ __launch_bounds__(AA_THREADS) void name(const uint8_t *frames, size_t frame_bytes, Geom g, const uint32_t *table, int pic_base, uint8_t *dst, AaParams e) \
+// (a named kernel per instance of kernel_resize.h's EXPORT_INSTANCES)
+#define RESIZE_AA_KERNEL(family, sfx, fmt, dt) \
+    __global__ __launch_bounds__(AA_THREADS) void family##sfx(const uint8_t *frames, size_t frame_bytes, Geom g, const uint32_t *table, int pic_base, uint8_t *dst, AaParams e) \
     { resize_aa_body<fmt, dt>(frames, frame_bytes, g, table, pic_base, dst, e); }
-RESIZE_AA_KERNEL(k_resize_aa_i420, P264HIP_FMT_I420, P264HIP_DTYPE_U8)
-RESIZE_AA_KERNEL(k_resize_aa_nv12, P264HIP_FMT_NV12, P264HIP_DTYPE_U8)
-RESIZE_AA_KERNEL(k_resize_aa_rgb24_u8, P264HIP_FMT_RGB24, P264HIP_DTYPE_U8)
-RESIZE_AA_KERNEL(k_resize_aa_rgb24_f16, P264HIP_FMT_RGB24, P264HIP_DTYPE_F16)
-RESIZE_AA_KERNEL(k_resize_aa_rgb24_f32, P264HIP_FMT_RGB24, P264HIP_DTYPE_F32)
-RESIZE_AA_KERNEL(k_resize_aa_rgbp_u8, P264HIP_FMT_RGBP, P264HIP_DTYPE_U8)
-RESIZE_AA_KERNEL(k_resize_aa_rgbp_f16, P264HIP_FMT_RGBP, P264HIP_DTYPE_F16)
-RESIZE_AA_KERNEL(k_resize_aa_rgbp_f32, P264HIP_FMT_RGBP, P264HIP_DTYPE_F32)
+EXPORT_INSTANCES(RESIZE_AA_KERNEL, k_resize_aa_)

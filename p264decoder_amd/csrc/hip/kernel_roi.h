@@ -161,15 +161,8 @@ __device__ __forceinline__ void roi_body(const uint8_t *frames, size_t frame_byt
     }
 }
 
-// (one named kernel per instance: tools/kernel_resources.py and the tests find them by name)
-#define ROI_KERNEL(name, fmt, dt) \
-    __global__ __launch_bounds__(RESIZE_THREADS) void name(const uint8_t *frames, size_t frame_bytes, Geom g, const RoiDev *rois, const uint32_t *scratch, int pic_base, uint8_t *dst, ResizeParams e, uint32_t fill) \
+// (a named kernel per instance of kernel_resize.h's EXPORT_INSTANCES)
+#define ROI_KERNEL(family, sfx, fmt, dt) \
+    __global__ __launch_bounds__(RESIZE_THREADS) void family##sfx(const uint8_t *frames, size_t frame_bytes, Geom g, const RoiDev *rois, const uint32_t *scratch, int pic_base, uint8_t *dst, ResizeParams e, uint32_t fill) \
     { roi_body<fmt, dt>(frames, frame_bytes, g, rois, scratch, pic_base, dst, e, fill); }
-ROI_KERNEL(k_roi_i420, P264HIP_FMT_I420, P264HIP_DTYPE_U8)
-ROI_KERNEL(k_roi_nv12, P264HIP_FMT_NV12, P264HIP_DTYPE_U8)
-ROI_KERNEL(k_roi_rgb24_u8, P264HIP_FMT_RGB24, P264HIP_DTYPE_U8)
-ROI_KERNEL(k_roi_rgb24_f16, P264HIP_FMT_RGB24, P264HIP_DTYPE_F16)
-ROI_KERNEL(k_roi_rgb24_f32, P264HIP_FMT_RGB24, P264HIP_DTYPE_F32)
-ROI_KERNEL(k_roi_rgbp_u8, P264HIP_FMT_RGBP, P264HIP_DTYPE_U8)
-ROI_KERNEL(k_roi_rgbp_f16, P264HIP_FMT_RGBP, P264HIP_DTYPE_F16)
-ROI_KERNEL(k_roi_rgbp_f32, P264HIP_FMT_RGBP, P264HIP_DTYPE_F32)
+EXPORT_INSTANCES(ROI_KERNEL, k_roi_)

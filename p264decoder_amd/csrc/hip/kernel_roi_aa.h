@@ -133,15 +133,8 @@ __device__ __forceinline__ void roi_aa_body(const uint8_t *frames, size_t frame_
     }
 }
 
-// (one named kernel per instance, as kernel_roi.h's)
-#define ROI_AA_KERNEL(name, fmt, dt) \
-    __global__ __launch_bounds__(AA_THREADS) void name(const uint8_t *frames, size_t frame_bytes, Geom g, const RoiDev *rois, const uint32_t *scratch, int pic_base, uint8_t *dst, RoiAaParams e, uint32_t fill) \
+// (a named kernel per instance of kernel_resize.h's EXPORT_INSTANCES)
+#define ROI_AA_KERNEL(family, sfx, fmt, dt) \
+    __global__ __launch_bounds__(AA_THREADS) void family##sfx(const uint8_t *frames, size_t frame_bytes, Geom g, const RoiDev *rois, const uint32_t *scratch, int pic_base, uint8_t *dst, RoiAaParams e, uint32_t fill) \
     { roi_aa_body<fmt, dt>(frames, frame_bytes, g, rois, scratch, pic_base, dst, e, fill); }
-ROI_AA_KERNEL(k_roi_aa_i420, P264HIP_FMT_I420, P264HIP_DTYPE_U8)
-ROI_AA_KERNEL(k_roi_aa_nv12, P264HIP_FMT_NV12, P264HIP_DTYPE_U8)
-ROI_AA_KERNEL(k_roi_aa_rgb24_u8, P264HIP_FMT_RGB24, P264HIP_DTYPE_U8)
-ROI_AA_KERNEL(k_roi_aa_rgb24_f16, P264HIP_FMT_RGB24, P264HIP_DTYPE_F16)
-ROI_AA_KERNEL(k_roi_aa_rgb24_f32, P264HIP_FMT_RGB24, P264HIP_DTYPE_F32)
-ROI_AA_KERNEL(k_roi_aa_rgbp_u8, P264HIP_FMT_RGBP, P264HIP_DTYPE_U8)
-ROI_AA_KERNEL(k_roi_aa_rgbp_f16, P264HIP_FMT_RGBP, P264HIP_DTYPE_F16)
-ROI_AA_KERNEL(k_roi_aa_rgbp_f32, P264HIP_FMT_RGBP, P264HIP_DTYPE_F32)
+EXPORT_INSTANCES(ROI_AA_KERNEL, k_roi_aa_)

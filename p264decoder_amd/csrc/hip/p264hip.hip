@@ -572,6 +572,76 @@ static int export_reserve(p264hip_ctx *c, int n)
     return 0;
 }
 
+// ---- the steps the export roads share ----
+// every picture of the call is a frame of the store
+static int export_pictures_check(const char *fn, const p264hip_ctx *c, const int *streams, const int *slots, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (streams[i] < 0 || streams[i] >= c->n_streams || slots[i] < 0 || slots[i] >= c->slots)
+            return fail(P264HIP_EINVAL, "%s: picture %d names stream %d slot %d (have %d x %d)", fn, i, streams[i], slots[i], c->n_streams, c->slots);
+    return 0;
+}
+
+// where n pictures of `bytes` bytes, elements of `elem` bytes, lie in dst: the description's pitch and frame_stride, 0 being the
+// tight ones, in bytes - or why dst cannot hold them
+static int export_dst(const char *fn, int n, int64_t bytes, int elem, int pitch, int64_t frame_stride, int format, int width, const void *dst, size_t dst_bytes,
+                      int64_t *pitch_bytes, int64_t *stride_bytes)
+{
+    if ((uintptr_t)dst % (uintptr_t)elem) return fail(P264HIP_EINVAL, "%s: dst is no multiple of the element size %d", fn, elem);
+    const int64_t stride = frame_stride ? frame_stride : bytes;
+    if (n > 1 && stride > (INT64_MAX - bytes) / (n - 1)) return fail(P264HIP_EINVAL, "%s: %d pictures %lld bytes apart", fn, n, (long long)stride);
+    const uint64_t need = (uint64_t)(n - 1) * (uint64_t)stride + (uint64_t)bytes;
+    if ((uint64_t)dst_bytes < need) return fail(P264HIP_EINVAL, "%s: %d pictures need %llu bytes, dst has %zu", fn, n, (unsigned long long)need, dst_bytes);
+    *pitch_bytes = pitch ? pitch : (format == P264HIP_FMT_RGB24 ? 3 * (int64_t)width : (int64_t)width) * elem;
+    *stride_bytes = stride;
+    return 0;
+}
+static int elem_bytes(int dtype) { return dtype == P264HIP_DTYPE_U8 ? 1 : dtype == P264HIP_DTYPE_F16 ? 2 : 4; }
+
+// The staging ring: a call's table is written into a pinned buffer and copied to its device twin on the context's stream; the event
+// says when that copy is done and the pinned buffer may be written again.  export_stage: the ring's next buffer with room for
+// `words` words, its last copy done (the ring advances once per call, also one that fails later); export_send: its first bytes out
+struct ExportTable { uint32_t *host; const uint32_t *dev; hipEvent_t free; };
+static int export_stage(p264hip_ctx *c, int words, ExportTable *t)
+{
+    const int rc = export_reserve(c, words);
+    if (rc) return rc;
+    const int r = c->exp_ring; c->exp_ring = (c->exp_ring + 1) % BATCH_RING;
+    *t = ExportTable{ c->h_exp[r], c->d_exp[r], c->exp_free[r] };
+    HIPCHK(hipEventSynchronize(t->free));
+    return 0;
+}
+static int export_send(p264hip_ctx *c, const ExportTable &t, size_t bytes)
+{
+    HIPCHK(hipMemcpyAsync((void *)t.dev, t.host, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(t.free, c->stream));
+    return 0;
+}
+// the frame index of every picture, then zeros up to the next multiple of 4 words, where a call's tap tables begin: returns it
+static int export_indices(const p264hip_ctx *c, uint32_t *t, const int *streams, const int *slots, int n)
+{
+    const int first_word = (n + 3) & ~3;
+    for (int i = 0; i < n; i++) t[i] = (uint32_t)(streams[i] * c->slots + slots[i]);
+    for (int i = n; i < first_word; i++) t[i] = 0;
+    return first_word;
+}
+
+// the colour conversion of the RGB formats (ExportParams and ResizeParams name the six fields alike)
+template <typename P> static void export_colour(P &p, int matrix, int full_range)
+{
+    const int32_t *k = export_coefs[matrix][full_range];
+    p.cy = k[0]; p.yo = full_range ? 0 : 16; p.r_cv = k[1]; p.g_cu = k[2]; p.g_cv = k[3]; p.b_cu = k[4];
+}
+
+// [first, first + count) in the slices one launch takes - a grid's second dimension ends at 65535: launch(base, rows) for each
+template <typename F> static void for_grid_rows(int first, int count, F launch)
+{
+    for (int base = first; base < first + count; base += 65535) {
+        const int left = first + count - base;
+        launch(base, (unsigned)(left < 65535 ? left : 65535));
+    }
+}
+
 // the tiles of a picture (kernel_export.h); the description has passed p264hip_export_check
 static ExportParams export_params(const p264hip_export_t &e, int64_t pitch, int64_t stride)
 {
@@ -587,8 +657,7 @@ static ExportParams export_params(const p264hip_export_t &e, int64_t pitch, int6
     p.ctx = p.n_ccols ? (p.n_ccols + 7) / 8 : 1;
     p.n_tiles = p.n_ltiles + (p.n_ccols ? p.ctx * ((p.n_cgroups + EXPORT_GROUPS - 1) / EXPORT_GROUPS) : 0);
     p.pitch = pitch; p.frame_stride = stride;
-    const int32_t *k = export_coefs[e.matrix][e.full_range];
-    p.cy = k[0]; p.yo = e.full_range ? 0 : 16; p.r_cv = k[1]; p.g_cu = k[2]; p.g_cv = k[3]; p.b_cu = k[4];
+    export_colour(p, e.matrix, e.full_range);
     return p;
 }
 
@@ -598,33 +667,20 @@ extern "C" int p264hip_export_frames(p264hip_ctx *c, const int *streams, const i
     if (const char *why = p264hip_export_why_(e, c->g.mb_w, c->g.mb_h))
         return fail(P264HIP_EINVAL, "p264hip_export_frames: %s (format %d matrix %d full_range %d, window %d,%d %dx%d in a %dx%d frame, pitch %d, frame_stride %lld)", why,
                     e->format, e->matrix, e->full_range, e->crop_left, e->crop_top, e->width, e->height, c->g.w, c->g.h, e->pitch, (long long)e->frame_stride);
-    for (int i = 0; i < n; i++)
-        if (streams[i] < 0 || streams[i] >= c->n_streams || slots[i] < 0 || slots[i] >= c->slots)
-            return fail(P264HIP_EINVAL, "p264hip_export_frames: picture %d names stream %d slot %d (have %d x %d)", i, streams[i], slots[i], c->n_streams, c->slots);
-    const int64_t bytes = p264hip_export_frame_bytes(e), stride = e->frame_stride ? e->frame_stride : bytes;
-    const int64_t pitch = e->pitch ? e->pitch : (e->format == P264HIP_FMT_RGB24 ? 3 * (int64_t)e->width : (int64_t)e->width);
-    if (n > 1 && stride > (INT64_MAX - bytes) / (n - 1)) return fail(P264HIP_EINVAL, "p264hip_export_frames: %d pictures %lld bytes apart", n, (long long)stride);
-    const uint64_t need = (uint64_t)(n - 1) * (uint64_t)stride + (uint64_t)bytes;
-    if ((uint64_t)dst_bytes < need) return fail(P264HIP_EINVAL, "p264hip_export_frames: %d pictures need %llu bytes, dst has %zu", n, (unsigned long long)need, dst_bytes);
-    HIPCHK(hipSetDevice(c->device));
-    int rc = export_reserve(c, n);
+    int rc = export_pictures_check("p264hip_export_frames", c, streams, slots, n);
     if (rc) return rc;
-    const int r = c->exp_ring; c->exp_ring = (c->exp_ring + 1) % BATCH_RING;
-    HIPCHK(hipEventSynchronize(c->exp_free[r]));              // the copy that last used this staging buffer is done
-    for (int i = 0; i < n; i++) c->h_exp[r][i] = (uint32_t)(streams[i] * c->slots + slots[i]);
-    HIPCHK(hipMemcpyAsync(c->d_exp[r], c->h_exp[r], (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->exp_free[r], c->stream));
+    int64_t pitch, stride;              // (bytes only: an element size of 1)
+    if ((rc = export_dst("p264hip_export_frames", n, p264hip_export_frame_bytes(e), 1, e->pitch, e->frame_stride, e->format, e->width, dst, dst_bytes, &pitch, &stride))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    ExportTable t;                      // the call's table: the frame indices
+    if ((rc = export_stage(c, n, &t))) return rc;
+    for (int i = 0; i < n; i++) t.host[i] = (uint32_t)(streams[i] * c->slots + slots[i]);
+    if ((rc = export_send(c, t, (size_t)n * sizeof(uint32_t)))) return rc;
     const ExportParams p = export_params(*e, pitch, stride);
     const unsigned gx = (unsigned)((p.n_tiles + EXPORT_THREADS / WAVE - 1) / (EXPORT_THREADS / WAVE));
-    for (int base = 0; base < n; base += 65535) {            // (a grid's second dimension ends at 65535)
-        const dim3 grid(gx, (unsigned)(n - base < 65535 ? n - base : 65535));
-        switch (e->format) {
-        case P264HIP_FMT_I420:  hipLaunchKernelGGL(k_export_i420, grid, dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p); break;
-        case P264HIP_FMT_NV12:  hipLaunchKernelGGL(k_export_nv12, grid, dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p); break;
-        case P264HIP_FMT_RGB24: hipLaunchKernelGGL(k_export_rgb24, grid, dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p); break;
-        default:                hipLaunchKernelGGL(k_export_rgbp, grid, dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p); break;
-        }
-    }
+    static decltype(&k_export_i420) const kernels[] = { k_export_i420, k_export_nv12, k_export_rgb24, k_export_rgbp };     // by P264HIP_FMT_*
+    static_assert(P264HIP_FMT_I420 == 0 && P264HIP_FMT_NV12 == 1 && P264HIP_FMT_RGB24 == 2 && P264HIP_FMT_RGBP == 3, "kernels[] is indexed by the format");
+    for_grid_rows(0, n, [&](int base, unsigned rows) { hipLaunchKernelGGL(kernels[e->format], dim3(gx, rows), dim3(EXPORT_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, t.dev, base, (uint8_t *)dst, p); });
     HIPCHK(hipGetLastError());
     return P264HIP_OK;
 }
@@ -688,7 +744,42 @@ struct AaTaps {
     }
 };
 
-#define RESIZE_AA_LAUNCH(name) hipLaunchKernelGGL(name, grid, dim3(AA_THREADS), lds, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p)
+// ---- what the resizing roads share: the kernels of an instance, and ResizeParams ----
+// the four families' kernel pointers in the order of kernel_resize.h's EXPORT_INSTANCES, and the place of (format, dtype) in it
+// (the description has passed p264hip_resize_check: a format and a dtype of the list)
+#define INSTANCE_NAME(family, sfx, fmt, dt) family##sfx,
+#define INSTANCE_CASE(family, sfx, fmt, dt) case fmt * 3 + dt: return family##sfx;
+static decltype(&k_resize_i420) const resize_kernels[] = { EXPORT_INSTANCES(INSTANCE_NAME, k_resize_) };
+static decltype(&k_resize_aa_i420) const resize_aa_kernels[] = { EXPORT_INSTANCES(INSTANCE_NAME, k_resize_aa_) };
+static decltype(&k_roi_i420) const roi_kernels[] = { EXPORT_INSTANCES(INSTANCE_NAME, k_roi_) };
+static decltype(&k_roi_aa_i420) const roi_aa_kernels[] = { EXPORT_INSTANCES(INSTANCE_NAME, k_roi_aa_) };
+enum { EXPORT_INSTANCES(INSTANCE_NAME, instance_) n_instances };
+static int instance_of(int format, int dtype)
+{
+    switch (format * 3 + dtype) { EXPORT_INSTANCES(INSTANCE_CASE, instance_) }
+    return n_instances - 1;
+}
+
+// what every resizing kernel reads of ResizeParams: the output, where its pictures lie, colour conversion, scale and bias
+static ResizeParams resize_params(const p264hip_resize_t &e, int64_t pitch, int64_t stride)
+{
+    ResizeParams p = {};
+    p.w = e.width; p.h = e.height;
+    p.pitch = pitch; p.frame_stride = stride;
+    export_colour(p, e.matrix, e.full_range);
+    for (int i = 0; i < 3; i++) { p.scale[i] = e.scale[i]; p.bias[i] = e.bias[i]; }
+    return p;
+}
+// the tiles of resize_body / roi_body (a wavefront each), which split a tile index; returns the first dimension of their grid
+static unsigned resize_tiles(ResizeParams &p, int format)
+{
+    const bool rgb = format == P264HIP_FMT_RGB24 || format == P264HIP_FMT_RGBP;
+    const int cw = p.w / 2, ch = p.h / 2;
+    p.ltx = (p.w + RESIZE_TILE_W - 1) / RESIZE_TILE_W; p.n_ltiles = p.ltx * (p.h / 2);
+    p.ctx = (cw + RESIZE_TILE_W - 1) / RESIZE_TILE_W; p.n_tiles = p.n_ltiles + (rgb ? 0 : p.ctx * ch);
+    p.inv_ltx = 0xffffffffu / (uint32_t)p.ltx; p.inv_ctx = 0xffffffffu / (uint32_t)p.ctx;
+    return (unsigned)((p.n_tiles + RESIZE_THREADS / WAVE - 1) / (RESIZE_THREADS / WAVE));
+}
 
 // p264hip_export_resized with P264HIP_FILTER_BILINEAR_AA: everything has been checked
 static int export_resized_aa(p264hip_ctx *c, const int *streams, const int *slots, int n, const p264hip_resize_t *e, void *dst, int64_t pitch, int64_t stride)
@@ -710,41 +801,20 @@ static int export_resized_aa(p264hip_ctx *c, const int *streams, const int *slot
     p.ntx = (W + tw - 1) / tw; p.inv_ntx = 0xffffffffu / (uint32_t)p.ntx;
     const int first_word = (n + 3) & ~3;
     const int words = first_word + xl.pos_words() + xl.weight_words() + yl.pos_words() + yl.weight_words() + xc.pos_words() + xc.weight_words() + yc.pos_words() + yc.weight_words();
-    int rc = export_reserve(c, words);
+    ExportTable t;                      // the call's table: the frame indices, then the four axes' positions and weights
+    int rc = export_stage(c, words, &t);
     if (rc) return rc;
-    const int r = c->exp_ring; c->exp_ring = (c->exp_ring + 1) % BATCH_RING;
-    HIPCHK(hipEventSynchronize(c->exp_free[r]));              // the copy that last used this staging buffer is done
-    uint32_t *t = c->h_exp[r];
-    for (int i = 0; i < n; i++) t[i] = (uint32_t)(streams[i] * c->slots + slots[i]);
-    for (int i = n; i < first_word; i++) t[i] = 0;
-    int at = xl.put(t, first_word, p.xl);
-    at = yl.put(t, at, p.yl); at = xc.put(t, at, p.xc); at = yc.put(t, at, p.yc);
-    HIPCHK(hipMemcpyAsync(c->d_exp[r], t, (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->exp_free[r], c->stream));
-    p.r.w = W; p.r.h = H; p.r.pitch = pitch; p.r.frame_stride = stride;
-    const int32_t *k = export_coefs[e->matrix][e->full_range];
-    p.r.cy = k[0]; p.r.yo = e->full_range ? 0 : 16; p.r.r_cv = k[1]; p.r.g_cu = k[2]; p.r.g_cv = k[3]; p.r.b_cu = k[4];
-    for (int i = 0; i < 3; i++) { p.r.scale[i] = e->scale[i]; p.r.bias[i] = e->bias[i]; }
+    int at = xl.put(t.host, export_indices(c, t.host, streams, slots, n), p.xl);
+    at = yl.put(t.host, at, p.yl); at = xc.put(t.host, at, p.xc); at = yc.put(t.host, at, p.yc);
+    if ((rc = export_send(c, t, (size_t)words * sizeof(uint32_t)))) return rc;
+    p.r = resize_params(*e, pitch, stride);                 // (the tile fields stay 0: AaParams has this filter's tiles)
     const unsigned gx = (unsigned)(p.ntx * ((H + AA_TH - 1) / AA_TH));
     const size_t lds = sizeof(uint16_t) * 16 * (size_t)(p.ns_l * AA_TH > p.ns_c * (AA_TH / 2) ? p.ns_l * AA_TH : p.ns_c * (AA_TH / 2));
-    for (int base = 0; base < n; base += 65535) {            // (a grid's second dimension ends at 65535)
-        const dim3 grid(gx, (unsigned)(n - base < 65535 ? n - base : 65535));
-        switch (e->format * 3 + e->dtype) {
-        case P264HIP_FMT_I420 * 3:                       RESIZE_AA_LAUNCH(k_resize_aa_i420); break;
-        case P264HIP_FMT_NV12 * 3:                       RESIZE_AA_LAUNCH(k_resize_aa_nv12); break;
-        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_U8:   RESIZE_AA_LAUNCH(k_resize_aa_rgb24_u8); break;
-        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F16:  RESIZE_AA_LAUNCH(k_resize_aa_rgb24_f16); break;
-        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F32:  RESIZE_AA_LAUNCH(k_resize_aa_rgb24_f32); break;
-        case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_U8:    RESIZE_AA_LAUNCH(k_resize_aa_rgbp_u8); break;
-        case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_F16:   RESIZE_AA_LAUNCH(k_resize_aa_rgbp_f16); break;
-        default:                                         RESIZE_AA_LAUNCH(k_resize_aa_rgbp_f32); break;
-        }
-    }
+    const auto kernel = resize_aa_kernels[instance_of(e->format, e->dtype)];
+    for_grid_rows(0, n, [&](int base, unsigned rows) { hipLaunchKernelGGL(kernel, dim3(gx, rows), dim3(AA_THREADS), lds, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, t.dev, base, (uint8_t *)dst, p); });
     HIPCHK(hipGetLastError());
     return P264HIP_OK;
 }
-
-#define RESIZE_LAUNCH(name) hipLaunchKernelGGL(name, grid, dim3(RESIZE_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const uint32_t *)c->d_exp[r], base, (uint8_t *)dst, p)
 
 extern "C" int p264hip_export_resized(p264hip_ctx *c, const int *streams, const int *slots, int n, const p264hip_resize_t *e, void *dst, size_t dst_bytes)
 {
@@ -753,57 +823,26 @@ extern "C" int p264hip_export_resized(p264hip_ctx *c, const int *streams, const 
         return fail(P264HIP_EINVAL, "p264hip_export_resized: %s (format %d dtype %d filter %d matrix %d full_range %d, window %d,%d %dx%d in a %dx%d frame to %dx%d, pitch %d, frame_stride %lld)", why,
                     e->format, e->dtype, e->filter, e->matrix, e->full_range, e->crop_left, e->crop_top, e->crop_width, e->crop_height, c->g.w, c->g.h, e->width, e->height, e->pitch, (long long)e->frame_stride);
     if (c->g.w > 65535 || c->g.h > 65535) return fail(P264HIP_EINVAL, "p264hip_export_resized: a frame of %dx%d samples (a tap holds a coordinate in 16 bits)", c->g.w, c->g.h);
-    for (int i = 0; i < n; i++)
-        if (streams[i] < 0 || streams[i] >= c->n_streams || slots[i] < 0 || slots[i] >= c->slots)
-            return fail(P264HIP_EINVAL, "p264hip_export_resized: picture %d names stream %d slot %d (have %d x %d)", i, streams[i], slots[i], c->n_streams, c->slots);
-    const int elem = e->dtype == P264HIP_DTYPE_U8 ? 1 : e->dtype == P264HIP_DTYPE_F16 ? 2 : 4;
-    if ((uintptr_t)dst % (uintptr_t)elem) return fail(P264HIP_EINVAL, "p264hip_export_resized: dst is no multiple of the element size %d", elem);
-    const int64_t bytes = p264hip_resize_frame_bytes(e), stride = e->frame_stride ? e->frame_stride : bytes;
-    const int64_t pitch = e->pitch ? e->pitch : (e->format == P264HIP_FMT_RGB24 ? 3 * (int64_t)e->width : (int64_t)e->width) * elem;
-    if (n > 1 && stride > (INT64_MAX - bytes) / (n - 1)) return fail(P264HIP_EINVAL, "p264hip_export_resized: %d pictures %lld bytes apart", n, (long long)stride);
-    const uint64_t need = (uint64_t)(n - 1) * (uint64_t)stride + (uint64_t)bytes;
-    if ((uint64_t)dst_bytes < need) return fail(P264HIP_EINVAL, "p264hip_export_resized: %d pictures need %llu bytes, dst has %zu", n, (unsigned long long)need, dst_bytes);
+    int rc = export_pictures_check("p264hip_export_resized", c, streams, slots, n);
+    if (rc) return rc;
+    int64_t pitch, stride;
+    if ((rc = export_dst("p264hip_export_resized", n, p264hip_resize_frame_bytes(e), elem_bytes(e->dtype), e->pitch, e->frame_stride, e->format, e->width, dst, dst_bytes, &pitch, &stride))) return rc;
     HIPCHK(hipSetDevice(c->device));
     if (e->filter == P264HIP_FILTER_BILINEAR_AA) return export_resized_aa(c, streams, slots, n, e, dst, pitch, stride);
     // the call's table: the frame indices, then the four tap tables, each from a multiple of 4 words
-    const bool rgb = e->format == P264HIP_FMT_RGB24 || e->format == P264HIP_FMT_RGBP;
     const int W = e->width, H = e->height, cw = W / 2, ch = H / 2;
-    ResizeParams p = {};
-    p.w = W; p.h = H;
+    ResizeParams p = resize_params(*e, pitch, stride);
     p.t_xl = (n + 3) & ~3; p.t_yl = p.t_xl + ((W + 3) & ~3); p.t_xc = p.t_yl + ((H + 3) & ~3); p.t_yc = p.t_xc + ((cw + 3) & ~3);
     const int words = p.t_yc + ((ch + 3) & ~3);
-    int rc = export_reserve(c, words);
-    if (rc) return rc;
-    const int r = c->exp_ring; c->exp_ring = (c->exp_ring + 1) % BATCH_RING;
-    HIPCHK(hipEventSynchronize(c->exp_free[r]));              // the copy that last used this staging buffer is done
-    uint32_t *t = c->h_exp[r];
-    for (int i = 0; i < n; i++) t[i] = (uint32_t)(streams[i] * c->slots + slots[i]);
-    for (int i = n; i < p.t_xl; i++) t[i] = 0;
-    resize_table(t + p.t_xl, e->crop_left, e->crop_width, W); resize_table(t + p.t_yl, e->crop_top, e->crop_height, H);
-    resize_table(t + p.t_xc, e->crop_left / 2, e->crop_width / 2, cw); resize_table(t + p.t_yc, e->crop_top / 2, e->crop_height / 2, ch);
-    HIPCHK(hipMemcpyAsync(c->d_exp[r], t, (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->exp_free[r], c->stream));
-    p.ltx = (W + RESIZE_TILE_W - 1) / RESIZE_TILE_W; p.n_ltiles = p.ltx * (H / 2);
-    p.ctx = (cw + RESIZE_TILE_W - 1) / RESIZE_TILE_W; p.n_tiles = p.n_ltiles + (rgb ? 0 : p.ctx * ch);
-    p.inv_ltx = 0xffffffffu / (uint32_t)p.ltx; p.inv_ctx = 0xffffffffu / (uint32_t)p.ctx;
-    p.pitch = pitch; p.frame_stride = stride;
-    const int32_t *k = export_coefs[e->matrix][e->full_range];
-    p.cy = k[0]; p.yo = e->full_range ? 0 : 16; p.r_cv = k[1]; p.g_cu = k[2]; p.g_cv = k[3]; p.b_cu = k[4];
-    for (int i = 0; i < 3; i++) { p.scale[i] = e->scale[i]; p.bias[i] = e->bias[i]; }
-    const unsigned gx = (unsigned)((p.n_tiles + RESIZE_THREADS / WAVE - 1) / (RESIZE_THREADS / WAVE));
-    for (int base = 0; base < n; base += 65535) {            // (a grid's second dimension ends at 65535)
-        const dim3 grid(gx, (unsigned)(n - base < 65535 ? n - base : 65535));
-        switch (e->format * 3 + e->dtype) {
-        case P264HIP_FMT_I420 * 3:                       RESIZE_LAUNCH(k_resize_i420); break;
-        case P264HIP_FMT_NV12 * 3:                       RESIZE_LAUNCH(k_resize_nv12); break;
-        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_U8:   RESIZE_LAUNCH(k_resize_rgb24_u8); break;
-        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F16:  RESIZE_LAUNCH(k_resize_rgb24_f16); break;
-        case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F32:  RESIZE_LAUNCH(k_resize_rgb24_f32); break;
-        case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_U8:    RESIZE_LAUNCH(k_resize_rgbp_u8); break;
-        case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_F16:   RESIZE_LAUNCH(k_resize_rgbp_f16); break;
-        default:                                         RESIZE_LAUNCH(k_resize_rgbp_f32); break;
-        }
-    }
+    ExportTable t;
+    if ((rc = export_stage(c, words, &t))) return rc;
+    export_indices(c, t.host, streams, slots, n);
+    resize_table(t.host + p.t_xl, e->crop_left, e->crop_width, W); resize_table(t.host + p.t_yl, e->crop_top, e->crop_height, H);
+    resize_table(t.host + p.t_xc, e->crop_left / 2, e->crop_width / 2, cw); resize_table(t.host + p.t_yc, e->crop_top / 2, e->crop_height / 2, ch);
+    if ((rc = export_send(c, t, (size_t)words * sizeof(uint32_t)))) return rc;
+    const unsigned gx = resize_tiles(p, e->format);
+    const auto kernel = resize_kernels[instance_of(e->format, e->dtype)];
+    for_grid_rows(0, n, [&](int base, unsigned rows) { hipLaunchKernelGGL(kernel, dim3(gx, rows), dim3(RESIZE_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, t.dev, base, (uint8_t *)dst, p); });
     HIPCHK(hipGetLastError());
     return P264HIP_OK;
 }
@@ -811,9 +850,6 @@ extern "C" int p264hip_export_resized(p264hip_ctx *c, const int *streams, const 
 // ---- a window per picture into a rectangle of the output (include/p264hip.h: p264hip_roi_t; kernel_roi.h) ----
 extern "C" const char *p264hip_rois_aa_why_(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int *bad);
 extern "C" const char *p264hip_rois_why_(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int *bad);     // csrc/host/resize_layout.c
-
-#define ROI_AA_LAUNCH(name) hipLaunchKernelGGL(name, grid, dim3(AA_THREADS), lds, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const RoiDev *)c->d_exp[r], (const uint32_t *)c->d_roi, base, (uint8_t *)dst, pa, fill)
-#define ROI_LAUNCH(name) hipLaunchKernelGGL(name, grid, dim3(RESIZE_THREADS), 0, c->stream, (const uint8_t *)c->frames, c->frame_bytes, c->g, (const RoiDev *)c->d_exp[r], (const uint32_t *)c->d_roi, base, (uint8_t *)dst, p, fill)
 
 // p264hip_export_rois (aa false) and p264hip_export_rois_aa: the checks, the descriptors and the launch pairs are one text
 static int export_rois(p264hip_ctx *c, const p264hip_roi_t *rois, int n, const p264hip_resize_t *e, uint32_t fill, void *dst, size_t dst_bytes, bool aa)
@@ -828,26 +864,20 @@ static int export_rois(p264hip_ctx *c, const p264hip_roi_t *rois, int n, const p
                     o.stream, o.slot, c->n_streams, c->slots, o.left, o.top, o.width, o.height, c->g.w, c->g.h, o.dst_left, o.dst_top, o.dst_width, o.dst_height, e->width, e->height);
     }
     if (c->g.w > 65535 || c->g.h > 65535) return fail(P264HIP_EINVAL, "%s: a frame of %dx%d samples (a tap holds a coordinate in 16 bits)", fn, c->g.w, c->g.h);
-    const int elem = e->dtype == P264HIP_DTYPE_U8 ? 1 : e->dtype == P264HIP_DTYPE_F16 ? 2 : 4;
-    if ((uintptr_t)dst % (uintptr_t)elem) return fail(P264HIP_EINVAL, "%s: dst is no multiple of the element size %d", fn, elem);
-    const int64_t bytes = aa ? p264hip_rois_aa_frame_bytes(e) : p264hip_rois_frame_bytes(e), stride = e->frame_stride ? e->frame_stride : bytes;
-    const int64_t pitch = e->pitch ? e->pitch : (e->format == P264HIP_FMT_RGB24 ? 3 * (int64_t)e->width : (int64_t)e->width) * elem;
-    if (n > 1 && stride > (INT64_MAX - bytes) / (n - 1)) return fail(P264HIP_EINVAL, "%s: %d pictures %lld bytes apart", fn, n, (long long)stride);
-    const uint64_t need = (uint64_t)(n - 1) * (uint64_t)stride + (uint64_t)bytes;
-    if ((uint64_t)dst_bytes < need) return fail(P264HIP_EINVAL, "%s: %d pictures need %llu bytes, dst has %zu", fn, n, (unsigned long long)need, dst_bytes);
+    int64_t pitch, stride;
+    int rc = export_dst(fn, n, aa ? p264hip_rois_aa_frame_bytes(e) : p264hip_rois_frame_bytes(e), elem_bytes(e->dtype), e->pitch, e->frame_stride, e->format, e->width, dst, dst_bytes, &pitch, &stride);
+    if (rc) return rc;
     constexpr int desc_words = (int)(sizeof(RoiDev) / sizeof(uint32_t));
     if (n > INT32_MAX / desc_words - 16) return fail(P264HIP_ENOMEM, "%s: %d descriptors", fn, n);
     HIPCHK(hipSetDevice(c->device));
-    int rc = export_reserve(c, n * desc_words);
-    if (rc) return rc;
-    const int r = c->exp_ring; c->exp_ring = (c->exp_ring + 1) % BATCH_RING;
-    HIPCHK(hipEventSynchronize(c->exp_free[r]));              // the copy that last used this staging buffer is done
+    ExportTable table;                  // the call's table: a descriptor per ROI
+    if ((rc = export_stage(c, n * desc_words, &table))) return rc;
     // the descriptors, and the launch pairs: ROIs first .. first + count - 1 of a pair share the scratch, a segment each from word 0 on
     // (one segment is at most 49152 words - 300 000 with weights -, so every pair holds at least one ROI)
     constexpr size_t scratch_words = P264HIP_ROI_SCRATCH_BYTES / sizeof(uint32_t);
     struct Pair { int first, count, widest, tiles, lds; };   // (tiles, lds: the grid and the dynamic LDS of the pair's k_roi_aa_* launches)
     std::vector<Pair> pairs;
-    RoiDev *t = (RoiDev *)c->h_exp[r];
+    RoiDev *t = (RoiDev *)table.host;
     const int W = e->width, H = e->height;
     size_t used = 0, most = 0;
     for (int i = 0; i < n; i++) {
@@ -875,70 +905,26 @@ static int export_rois(p264hip_ctx *c, const p264hip_roi_t *rois, int n, const p
         most = used > most ? used : most;
     }
     if ((rc = grow(c, (void **)&c->d_roi, &c->roi_cap, most * sizeof(uint32_t), 0, false, WAIT_STREAM, "the ROI taps"))) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_exp[r], t, (size_t)n * sizeof(RoiDev), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->exp_free[r], c->stream));
-    const bool rgb = e->format == P264HIP_FMT_RGB24 || e->format == P264HIP_FMT_RGBP;
-    const int cw = W / 2, ch = H / 2;
-    ResizeParams p = {};                                    // (t_xl .. t_yc stay 0: the tables are the segments')
-    p.w = W; p.h = H;
-    p.ltx = (W + RESIZE_TILE_W - 1) / RESIZE_TILE_W; p.n_ltiles = p.ltx * (H / 2);
-    p.ctx = (cw + RESIZE_TILE_W - 1) / RESIZE_TILE_W; p.n_tiles = p.n_ltiles + (rgb ? 0 : p.ctx * ch);
-    p.inv_ltx = 0xffffffffu / (uint32_t)p.ltx; p.inv_ctx = 0xffffffffu / (uint32_t)p.ctx;
-    p.pitch = pitch; p.frame_stride = stride;
-    const int32_t *k = export_coefs[e->matrix][e->full_range];
-    p.cy = k[0]; p.yo = e->full_range ? 0 : 16; p.r_cv = k[1]; p.g_cu = k[2]; p.g_cv = k[3]; p.b_cu = k[4];
-    for (int i = 0; i < 3; i++) { p.scale[i] = e->scale[i]; p.bias[i] = e->bias[i]; }
-    const unsigned gx = (unsigned)((p.n_tiles + RESIZE_THREADS / WAVE - 1) / (RESIZE_THREADS / WAVE));
-    if (aa) {
-        RoiAaParams pa = {};
-        pa.r = p;
-        pa.tile_rows = (H + AA_TH - 1) / AA_TH;
-        for (int s = 1; s <= 4; s++) pa.inv_ntx[s - 1] = 0xffffffffu / (uint32_t)((W + (4 << s) - 1) / (4 << s));
-        for (const Pair &pr : pairs) {                      // (one stream: a pair's taps are read before the next pair's are written)
-            const unsigned tx = (unsigned)((pr.widest + ROI_TAPS_THREADS - 1) / ROI_TAPS_THREADS);
-            for (int base = pr.first; base < pr.first + pr.count; base += 65535) {        // (a grid's second dimension ends at 65535)
-                const int left = pr.first + pr.count - base;
-                hipLaunchKernelGGL(k_roi_aa_taps, dim3(tx, (unsigned)(left < 65535 ? left : 65535)), dim3(ROI_TAPS_THREADS), 0, c->stream, (const RoiDev *)c->d_exp[r], base, c->d_roi);
-            }
-            for (int base = pr.first; base < pr.first + pr.count; base += 65535) {
-                const int left = pr.first + pr.count - base;
-                const dim3 grid((unsigned)pr.tiles, (unsigned)(left < 65535 ? left : 65535));
-                const size_t lds = (size_t)pr.lds;
-                switch (e->format * 3 + e->dtype) {
-                case P264HIP_FMT_I420 * 3:                       ROI_AA_LAUNCH(k_roi_aa_i420); break;
-                case P264HIP_FMT_NV12 * 3:                       ROI_AA_LAUNCH(k_roi_aa_nv12); break;
-                case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_U8:   ROI_AA_LAUNCH(k_roi_aa_rgb24_u8); break;
-                case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F16:  ROI_AA_LAUNCH(k_roi_aa_rgb24_f16); break;
-                case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F32:  ROI_AA_LAUNCH(k_roi_aa_rgb24_f32); break;
-                case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_U8:    ROI_AA_LAUNCH(k_roi_aa_rgbp_u8); break;
-                case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_F16:   ROI_AA_LAUNCH(k_roi_aa_rgbp_f16); break;
-                default:                                         ROI_AA_LAUNCH(k_roi_aa_rgbp_f32); break;
-                }
-            }
-        }
-        HIPCHK(hipGetLastError());
-        return P264HIP_OK;
-    }
+    if ((rc = export_send(c, table, (size_t)n * sizeof(RoiDev)))) return rc;
+    ResizeParams p = resize_params(*e, pitch, stride);      // (t_xl .. t_yc stay 0: the tables are the segments')
+    const unsigned gx = resize_tiles(p, e->format);
+    RoiAaParams pa = {};
+    pa.r = p;
+    pa.tile_rows = (H + AA_TH - 1) / AA_TH;
+    for (int s = 1; s <= 4; s++) pa.inv_ntx[s - 1] = 0xffffffffu / (uint32_t)((W + (4 << s) - 1) / (4 << s));
+    // what the filter chooses of a pair's two launches: the kernels, the body's block and its parameters (its ninth argument)
+    const int instance = instance_of(e->format, e->dtype);
+    const auto taps = aa ? k_roi_aa_taps : k_roi_taps;
+    const void *body = aa ? (const void *)roi_aa_kernels[instance] : (const void *)roi_kernels[instance];
+    const unsigned block = aa ? AA_THREADS : RESIZE_THREADS;
+    const uint8_t *frames = c->frames; const RoiDev *d_rois = (const RoiDev *)table.dev; const uint32_t *scratch = c->d_roi; uint8_t *out = (uint8_t *)dst;
     for (const Pair &pr : pairs) {                          // (one stream: a pair's taps are read before the next pair's are written)
         const unsigned tx = (unsigned)((pr.widest + ROI_TAPS_THREADS - 1) / ROI_TAPS_THREADS);
-        for (int base = pr.first; base < pr.first + pr.count; base += 65535) {            // (a grid's second dimension ends at 65535)
-            const int left = pr.first + pr.count - base;
-            hipLaunchKernelGGL(k_roi_taps, dim3(tx, (unsigned)(left < 65535 ? left : 65535)), dim3(ROI_TAPS_THREADS), 0, c->stream, (const RoiDev *)c->d_exp[r], base, c->d_roi);
-        }
-        for (int base = pr.first; base < pr.first + pr.count; base += 65535) {
-            const int left = pr.first + pr.count - base;
-            const dim3 grid(gx, (unsigned)(left < 65535 ? left : 65535));
-            switch (e->format * 3 + e->dtype) {
-            case P264HIP_FMT_I420 * 3:                       ROI_LAUNCH(k_roi_i420); break;
-            case P264HIP_FMT_NV12 * 3:                       ROI_LAUNCH(k_roi_nv12); break;
-            case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_U8:   ROI_LAUNCH(k_roi_rgb24_u8); break;
-            case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F16:  ROI_LAUNCH(k_roi_rgb24_f16); break;
-            case P264HIP_FMT_RGB24 * 3 + P264HIP_DTYPE_F32:  ROI_LAUNCH(k_roi_rgb24_f32); break;
-            case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_U8:    ROI_LAUNCH(k_roi_rgbp_u8); break;
-            case P264HIP_FMT_RGBP * 3 + P264HIP_DTYPE_F16:   ROI_LAUNCH(k_roi_rgbp_f16); break;
-            default:                                         ROI_LAUNCH(k_roi_rgbp_f32); break;
-            }
-        }
+        for_grid_rows(pr.first, pr.count, [&](int base, unsigned rows) { hipLaunchKernelGGL(taps, dim3(tx, rows), dim3(ROI_TAPS_THREADS), 0, c->stream, d_rois, base, c->d_roi); });
+        for_grid_rows(pr.first, pr.count, [&](int base, unsigned rows) {
+            void *args[] = { &frames, &c->frame_bytes, &c->g, &d_rois, &scratch, &base, &out, aa ? (void *)&pa : (void *)&p, &fill };
+            (void)hipLaunchKernel(body, dim3(aa ? (unsigned)pr.tiles : gx, rows), dim3(block), args, (size_t)pr.lds, c->stream);
+        });
     }
     HIPCHK(hipGetLastError());
     return P264HIP_OK;

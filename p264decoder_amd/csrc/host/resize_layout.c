@@ -120,22 +120,30 @@ static const char *rois_why(const p264hip_roi_t *rois, int n, const p264hip_resi
     return 0;
 }
 
+/* bytes of one picture of a call whose filter is `filter` */
+static int64_t rois_frame_bytes(const p264hip_resize_t *r, int filter)
+{
+    if (!r || r->filter != filter) return P264HIP_EINVAL;
+    const p264hip_resize_t q = without_window(r);
+    return p264hip_resize_frame_bytes(&q);
+}
+
+static int rois_check(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int aa)
+{
+    int bad;
+    return rois_why(rois, n, r, fill, mb_w, mb_h, n_streams, slots, &bad, aa) ? P264HIP_EINVAL : P264HIP_OK;
+}
+
 const char *p264hip_rois_why_(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots, int *bad)
 {
     return rois_why(rois, n, r, fill, mb_w, mb_h, n_streams, slots, bad, 0);
 }
 
-int64_t p264hip_rois_frame_bytes(const p264hip_resize_t *r)
-{
-    if (!r || r->filter != P264HIP_FILTER_BILINEAR) return P264HIP_EINVAL;
-    const p264hip_resize_t q = without_window(r);
-    return p264hip_resize_frame_bytes(&q);
-}
+int64_t p264hip_rois_frame_bytes(const p264hip_resize_t *r) { return rois_frame_bytes(r, P264HIP_FILTER_BILINEAR); }
 
 int p264hip_rois_check(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots)
 {
-    int bad;
-    return p264hip_rois_why_(rois, n, r, fill, mb_w, mb_h, n_streams, slots, &bad) ? P264HIP_EINVAL : P264HIP_OK;
+    return rois_check(rois, n, r, fill, mb_w, mb_h, n_streams, slots, 0);
 }
 
 int p264hip_resize_aa_taps(int src_n, int dst_n, int32_t *first, int32_t *count, uint16_t *weights)
@@ -155,17 +163,11 @@ const char *p264hip_rois_aa_why_(const p264hip_roi_t *rois, int n, const p264hip
     return rois_why(rois, n, r, fill, mb_w, mb_h, n_streams, slots, bad, 1);
 }
 
-int64_t p264hip_rois_aa_frame_bytes(const p264hip_resize_t *r)
-{
-    if (!r || r->filter != P264HIP_FILTER_BILINEAR_AA) return P264HIP_EINVAL;
-    const p264hip_resize_t q = without_window(r);
-    return p264hip_resize_frame_bytes(&q);
-}
+int64_t p264hip_rois_aa_frame_bytes(const p264hip_resize_t *r) { return rois_frame_bytes(r, P264HIP_FILTER_BILINEAR_AA); }
 
 int p264hip_rois_aa_check(const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots)
 {
-    int bad;
-    return p264hip_rois_aa_why_(rois, n, r, fill, mb_w, mb_h, n_streams, slots, &bad) ? P264HIP_EINVAL : P264HIP_OK;
+    return rois_check(rois, n, r, fill, mb_w, mb_h, n_streams, slots, 1);
 }
 
 /* the rectangle of an ROI in a W x H output; 0 where the segment helpers cannot take the pair (they check sizes, not the frame) */

@@ -79,6 +79,16 @@ class Pipeline:
             raise RuntimeError("stream 0 has no picture: no display window")
         return crop
 
+    def _sink_fn(self, callback, per):
+        """the C callback of a sink: callback(round, streams, dev, per), whose exception run() raises"""
+        def trampoline(user, rnd, k, streams, dev):
+            try:                                          # (an exception cannot cross the C frames: run() raises it)
+                if self._sink_error is None:
+                    callback(rnd, [streams[i] for i in range(k)], dev, per)
+            except BaseException as exc:
+                self._sink_error = exc
+        return N.SINK_FN(trampoline)
+
     def export_last(self, fmt="i420", crop=None, matrix="bt601", full_range=False, pitch=0, out=None):
         """The last picture of every stream in device memory, stream i first to last (p264pipe_export_last); `out` and the result as
         HipReconstructor.export_frames has them."""
@@ -88,12 +98,7 @@ class Pipeline:
         per = self.lib.p264hip_export_frame_bytes(C.byref(e))
         if per < 0:
             raise RuntimeError("export_last: p264hip_export_frame_bytes refuses the description")
-        if out is None:
-            torch = N.import_torch()
-            W, H = e.width, e.height
-            shape = (n, H * 3 // 2, W) if e.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if e.format == N.FMT_RGB24 else (n, 3, H, W)
-            out = torch.empty(shape if not pitch else (n, per), dtype=torch.uint8, device="cuda")
-        ptr, cap = out if isinstance(out, tuple) else (out.data_ptr(), out.numel())
+        out, ptr, cap = N.export_out(n, e, per, pitch, 0, out)
         if self.lib.p264pipe_export_last(self.h, C.byref(e), ptr, cap):
             raise RuntimeError("p264pipe_export_last failed: %s" % self.lib.p264hip_last_error().decode())
         return out
@@ -123,14 +128,7 @@ class Pipeline:
         if self.device >= 0:
             ptrs = (C.c_void_p * len(buffers))(*[b[0] for b in buffers])
             cap = min(b[1] for b in buffers)
-
-        def trampoline(user, rnd, k, streams, dev):
-            try:                                          # (an exception cannot cross the C frames: run() raises it)
-                if self._sink_error is None:
-                    callback(rnd, [streams[i] for i in range(k)], dev, per)
-            except BaseException as exc:
-                self._sink_error = exc
-        fn = N.SINK_FN(trampoline)
+        fn = self._sink_fn(callback, per)
         if self.lib.p264pipe_set_sink(self.h, C.byref(e), ptrs, len(buffers), cap, fn, None):
             raise RuntimeError("p264pipe_set_sink refused (a buffer too small for %d pictures of %d bytes?)" % (n, per))
         self._sink = (fn, keep, ptrs, callback)
@@ -145,13 +143,7 @@ class Pipeline:
         per = self.lib.p264hip_resize_frame_bytes(C.byref(r))
         if per < 0:
             raise RuntimeError("export_last_resized: p264hip_resize_frame_bytes refuses the description")
-        if out is None:
-            torch = N.import_torch()
-            W, H = r.width, r.height
-            shape = (n, H * 3 // 2, W) if r.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if r.format == N.FMT_RGB24 else (n, 3, H, W)
-            want = {N.DTYPE_F16: torch.float16, N.DTYPE_F32: torch.float32}.get(r.dtype, torch.uint8)
-            out = torch.empty(shape, dtype=want, device="cuda") if not pitch else torch.empty((n, per), dtype=torch.uint8, device="cuda")
-        ptr, cap = out if isinstance(out, tuple) else (out.data_ptr(), out.numel() * out.element_size())
+        out, ptr, cap = N.export_out(n, r, per, pitch, 0, out)
         if self.lib.p264pipe_export_last_resized(self.h, C.byref(r), ptr, cap):
             raise RuntimeError("p264pipe_export_last_resized failed: %s" % self.lib.p264hip_last_error().decode())
         return out
@@ -170,14 +162,7 @@ class Pipeline:
         per = (self.lib.p264hip_rois_aa_frame_bytes if aa else self.lib.p264hip_rois_frame_bytes)(C.byref(r))
         if per < 0:
             raise RuntimeError("export_last_rois: %s refuses the description" % ("p264hip_rois_aa_frame_bytes" if aa else "p264hip_rois_frame_bytes"))
-        if out is None:
-            torch = N.import_torch()
-            W, H = r.width, r.height
-            shape = (n, H * 3 // 2, W) if r.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if r.format == N.FMT_RGB24 else (n, 3, H, W)
-            want = {N.DTYPE_F16: torch.float16, N.DTYPE_F32: torch.float32}.get(r.dtype, torch.uint8)
-            plain = not pitch and not frame_stride
-            out = torch.empty(shape, dtype=want, device="cuda") if plain else torch.empty((n, r.frame_stride or per), dtype=torch.uint8, device="cuda")
-        ptr, cap = out if isinstance(out, tuple) else (out.data_ptr(), out.numel() * out.element_size())
+        out, ptr, cap = N.export_out(n, r, per, pitch, frame_stride, out)
         if self.lib.p264pipe_export_last_rois(self.h, arr, n, C.byref(r), N.fill_word(fill), ptr, cap):
             raise RuntimeError("p264pipe_export_last_rois failed: %s" % self.lib.p264hip_last_error().decode())
         return out
@@ -200,14 +185,7 @@ class Pipeline:
             buffers = [(t.data_ptr(), t.numel()) for t in keep]
         ptrs = (C.c_void_p * len(buffers))(*[b[0] for b in buffers])
         cap = min(b[1] for b in buffers)
-
-        def trampoline(user, rnd, k, streams, dev):
-            try:                                          # (an exception cannot cross the C frames: run() raises it)
-                if self._sink_error is None:
-                    callback(rnd, [streams[i] for i in range(k)], dev, per)
-            except BaseException as exc:
-                self._sink_error = exc
-        fn = N.SINK_FN(trampoline)
+        fn = self._sink_fn(callback, per)
         if self.lib.p264pipe_set_sink_resized(self.h, C.byref(r), ptrs, len(buffers), cap, fn, None):
             raise RuntimeError("p264pipe_set_sink_resized refused (a buffer too small for %d pictures of %d bytes?)" % (n, per))
         self._sink = (fn, keep, ptrs, callback)

@@ -253,22 +253,10 @@ class HipReconstructor:
         e = N.export_desc(fmt, crop, (self.mb_w * 16, self.mb_h * 16), matrix, full_range, pitch, frame_stride)
         if len(slots) != n:
             raise P264Error("export_frames: %d streams, %d slots" % (n, len(slots)))
-        if out is None:
-            torch = N.import_torch()                      # only here: the module imports without torch or a GPU
-            per = self.lib.p264hip_export_frame_bytes(C.byref(e))
-            if per < 0:
-                raise P264Error("export_frames: p264hip_export_frame_bytes refuses the description")
-            W, H = e.width, e.height
-            shape = (n, H * 3 // 2, W) if e.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if e.format == N.FMT_RGB24 else (n, 3, H, W)
-            out = torch.empty(shape if not pitch and not frame_stride else (n, e.frame_stride or per), dtype=torch.uint8, device="cuda")
-        if isinstance(out, tuple):
-            ptr, cap = out
-        else:
-            if not (out.is_cuda and out.is_contiguous() and out.element_size() == 1):
-                raise P264Error("export_frames: out must be a contiguous uint8 tensor on the device")
-            torch = N.import_torch()
-            torch.cuda.current_stream(out.device).synchronize()     # (whatever torch still has queued on the tensor: the context has its own stream)
-            ptr, cap = out.data_ptr(), out.numel()
+        per = self.lib.p264hip_export_frame_bytes(C.byref(e)) if out is None else 0      # (a given `out`: the call refuses what it cannot take)
+        if per < 0:
+            raise P264Error("export_frames: p264hip_export_frame_bytes refuses the description")
+        out, ptr, cap = N.export_out(n, e, per, pitch, frame_stride, out, (P264Error, "export_frames"))
         a = (C.c_int * max(n, 1))(*streams)
         b = (C.c_int * max(n, 1))(*slots)
         self._chk(self.lib.p264hip_export_frames(self.h, a, b, n, C.byref(e), ptr, cap), "p264hip_export_frames")
@@ -290,26 +278,10 @@ class HipReconstructor:
         r = N.resize_desc(fmt, size, crop, (self.mb_w * 16, self.mb_h * 16), dtype, scale, bias, matrix, full_range, pitch, frame_stride, filter)
         if len(slots) != n:
             raise P264Error("export_resized: %d streams, %d slots" % (n, len(slots)))
-        if out is None or not isinstance(out, tuple):
-            torch = N.import_torch()                      # only here: the module imports without torch or a GPU
-            want = {N.DTYPE_U8: torch.uint8, N.DTYPE_F16: torch.float16, N.DTYPE_F32: torch.float32}.get(r.dtype, torch.uint8)
-        if out is None:
-            per = self.lib.p264hip_resize_frame_bytes(C.byref(r))
-            if per < 0:
-                raise P264Error("export_resized: p264hip_resize_frame_bytes refuses the description")
-            W, H = r.width, r.height
-            shape = (n, H * 3 // 2, W) if r.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if r.format == N.FMT_RGB24 else (n, 3, H, W)
-            if not pitch and not frame_stride:
-                out = torch.empty(shape, dtype=want, device="cuda")
-            else:
-                out = torch.empty((n, r.frame_stride or per), dtype=torch.uint8, device="cuda")
-        if isinstance(out, tuple):
-            ptr, cap = out
-        else:
-            if not (out.is_cuda and out.is_contiguous() and out.dtype in (want, torch.uint8)):
-                raise P264Error("export_resized: out must be a contiguous %s (or uint8) tensor on the device" % want)
-            torch.cuda.current_stream(out.device).synchronize()     # (whatever torch still has queued on the tensor: the context has its own stream)
-            ptr, cap = out.data_ptr(), out.numel() * out.element_size()
+        per = self.lib.p264hip_resize_frame_bytes(C.byref(r)) if out is None else 0
+        if per < 0:
+            raise P264Error("export_resized: p264hip_resize_frame_bytes refuses the description")
+        out, ptr, cap = N.export_out(n, r, per, pitch, frame_stride, out, (P264Error, "export_resized"))
         a = (C.c_int * max(n, 1))(*streams)
         b = (C.c_int * max(n, 1))(*slots)
         self._chk(self.lib.p264hip_export_resized(self.h, a, b, n, C.byref(r), ptr, cap), "p264hip_export_resized")
@@ -338,26 +310,10 @@ class HipReconstructor:
         r = N.resize_desc(fmt, size, (0, 0, 2, 2), None, dtype, scale, bias, matrix, full_range, pitch, frame_stride, filter)
         word = N.fill_word(fill)
         aa = r.filter == N.FILTER_BILINEAR_AA                # (its own entry points; any other value is p264hip_export_rois' to refuse)
-        if out is None or not isinstance(out, tuple):
-            torch = N.import_torch()                      # only here: the module imports without torch or a GPU
-            want = {N.DTYPE_U8: torch.uint8, N.DTYPE_F16: torch.float16, N.DTYPE_F32: torch.float32}.get(r.dtype, torch.uint8)
-        if out is None:
-            per = (self.lib.p264hip_rois_aa_frame_bytes if aa else self.lib.p264hip_rois_frame_bytes)(C.byref(r))
-            if per < 0:
-                raise P264Error("export_rois: %s refuses the description" % ("p264hip_rois_aa_frame_bytes" if aa else "p264hip_rois_frame_bytes"))
-            W, H = r.width, r.height
-            shape = (n, H * 3 // 2, W) if r.format in (N.FMT_I420, N.FMT_NV12) else (n, H, W, 3) if r.format == N.FMT_RGB24 else (n, 3, H, W)
-            if not pitch and not frame_stride:
-                out = torch.empty(shape, dtype=want, device="cuda")
-            else:
-                out = torch.empty((n, r.frame_stride or per), dtype=torch.uint8, device="cuda")
-        if isinstance(out, tuple):
-            ptr, cap = out
-        else:
-            if not (out.is_cuda and out.is_contiguous() and out.dtype in (want, torch.uint8)):
-                raise P264Error("export_rois: out must be a contiguous %s (or uint8) tensor on the device" % want)
-            torch.cuda.current_stream(out.device).synchronize()     # (whatever torch still has queued on the tensor: the context has its own stream)
-            ptr, cap = out.data_ptr(), out.numel() * out.element_size()
+        per = (self.lib.p264hip_rois_aa_frame_bytes if aa else self.lib.p264hip_rois_frame_bytes)(C.byref(r)) if out is None else 0
+        if per < 0:
+            raise P264Error("export_rois: %s refuses the description" % ("p264hip_rois_aa_frame_bytes" if aa else "p264hip_rois_frame_bytes"))
+        out, ptr, cap = N.export_out(n, r, per, pitch, frame_stride, out, (P264Error, "export_rois"))
         if aa:
             self._chk(self.lib.p264hip_export_rois_aa(self.h, arr, n, C.byref(r), word, ptr, cap), "p264hip_export_rois_aa")
         else:
