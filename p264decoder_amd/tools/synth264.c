@@ -15,7 +15,10 @@
  *            [--qp 26] [--coded 12] [--maxlevel 32] [--mvmax 64] [--cqo 0] [--nodeblock]
  *            [--cqo2 N]      second_chroma_qp_index_offset (Cr's own offset) in the PPS extension; default: --cqo's value.  Only with
  *                            --t8x8 (>= 0), which is what makes the writer emit the extension (High profile)
- *            [--refs 2]      two reference frames, reference index per partition (outside the reference's safe subset, A-Q5)
+ *            [--refs N]      N = 2 .. 16 reference frames, reference index per partition (outside the reference's safe subset, A-Q5),
+ *                            with the sliding window alone, with --mmco and with --bframes.  Every frame of the window is an
+ *                            active entry of list 0 - but for --refs 3 and 4 without --mmco, which keep the two active entries
+ *                            the streams written so far have
  *            [--slices N]    N slices per picture (equal runs of macroblocks; the reference handles one, decoder/decoder.c:516-523)
  *            [--dump-mv f]   per picture: the intended vectors int16[mb][16][2] and reference indices int8[mb][16]
  *            [--qp-delta N]  random mb_qp_delta in [-N, N] on every macroblock that carries one (the reference adds it to the
@@ -26,7 +29,7 @@
  *            [--reorder]     with --refs 2: some P slices swap the two entries of list 0 (ref_pic_list_reordering; ignored by
  *                            the reference, decoder/lists.c:146-149)
  *            [--dump-mv f]   additionally records, per picture, one byte: 1 when list 0 was reordered
- *            [--mmco]        with --refs 2..4: adaptive reference picture marking (memory_management_control_operation 1, 2, 3, 6:
+ *            [--mmco]        with --refs 2..16: adaptive reference picture marking (memory_management_control_operation 1, 2, 3, 6:
  *                            short-term pictures dropped early, turned into long-term ones, long-term ones dropped, the current
  *                            picture stored as long-term) and long-term IDR pictures; --dump-mv then also records list 0 of every
  *                            picture as the writer means it: one byte n, then n 16-bit picture numbers (decode order)
@@ -235,16 +238,17 @@ static void wp_put(bw_t *b, int is_b, int n0, int n1, int differ)
 }
 static int opt_mmco = 0, opt_mmco5 = 0, had_mmco5 = 0;   /* --mmco5: also memory_management_control_operation 5; had_mmco5: the picture just written carried one */
 /* the writer's own model of the decoded picture buffer (H.264 8.2.4, 8.2.5) */
+#define NDPB 17                              /* frames the model holds: 16 references and the picture being written */
 typedef struct { int used, pic, frame_num, is_long, long_idx;
                  int poc; int16_t *cmv; int8_t *cref; int *cpic; } wdpb_t;   /* --bframes: picture order count; the picture's motion for direct prediction:
                                                                               * per 4x4 block its vector, reference index and the picture that index named (-1 intra) */
-static wdpb_t wdpb[8];
-static int wlist[8], wlist_n;                /* list 0 of the current picture: picture numbers in decode order */
+static wdpb_t wdpb[NDPB];
+static int wlist[NDPB], wlist_n;                /* list 0 of the current picture: picture numbers in decode order */
 static int opt_qpdelta = 0, opt_alpha = 0, opt_beta = 0, opt_sub8x8 = 0, opt_reorder = 0, slice_reordered;
 static int opt_idc = 0;                     /* --deblock-idc 2: no filtering across slice boundaries */
 /* --bframes N: N non-reference B pictures between consecutive reference pictures (Main profile, picture order count type 0) */
 static int opt_bframes = 0, opt_temporal = 0, opt_implicit = 0, opt_d8inf = 0;
-static int cur_poc, n_active1 = 1, blist[2][8], blist_n[2], cur_entry = -1;      /* B picture: its order count and its two lists as indices into wdpb */
+static int cur_poc, n_active1 = 1, blist[2][NDPB], blist_n[2], cur_entry = -1;      /* B picture: its order count and its two lists as indices into wdpb */
 static int opt_slice_deblock = 0, opt_slice_lists = 0, opt_slice_lists_many = 0;
 static FILE *dump_slices;
 static int8_t *w_slice;                     /* [mb][4]: slice, idc, alpha, beta */
@@ -749,8 +753,8 @@ static int try_skip(int mbx, int mby)
 static int model_list0(int frame_num, int max_fn, int *list)
 {
     int n = 0, n_short;
-    int key[8];
-    for (int i = 0; i < 8; i++) {                       /* short-term, PicNum descending */
+    int key[NDPB];
+    for (int i = 0; i < NDPB; i++) {                       /* short-term, PicNum descending */
         if (!wdpb[i].used || wdpb[i].is_long) continue;
         const int k = wdpb[i].frame_num > frame_num ? wdpb[i].frame_num - max_fn : wdpb[i].frame_num;
         int j = n++;
@@ -758,7 +762,7 @@ static int model_list0(int frame_num, int max_fn, int *list)
         key[j] = k; list[j] = wdpb[i].pic;
     }
     n_short = n;
-    for (int i = 0; i < 8; i++) {                       /* long-term, index ascending */
+    for (int i = 0; i < NDPB; i++) {                       /* long-term, index ascending */
         if (!wdpb[i].used || !wdpb[i].is_long) continue;
         int j = n++;
         while (j > n_short && key[j-1] > wdpb[i].long_idx) { key[j] = key[j-1]; list[j] = list[j-1]; j--; }
@@ -800,24 +804,24 @@ static void reordered_list(const int *init, int n_init, int len, const int *pick
 static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int idr_id, int log2_fn, int refs_available, int pic_no)
 {
     const int max_fn = 1 << log2_fn;
-    int full[8], n_full = 0;
+    int full[NDPB], n_full = 0;
     if (opt_mmco || opt_bframes) { n_full = is_p ? model_list0(frame_num, max_fn, full) : 0; refs_available = n_full; }
     n_active = is_p && opt_refs > 1 && refs_available > 1 ? (refs_available < opt_refs ? refs_available : opt_refs) : 1;
-    if (!opt_mmco && n_active > 2) n_active = 2;
+    if (!opt_mmco && opt_refs <= 4 && n_active > 2) n_active = 2;    /* (--refs 3 and 4 without --mmco keep the two active entries they always had; from 5 every frame of the window is active) */
     slice_reordered = opt_reorder && n_active > 1 && pct(50);
     wlist_n = 0;
     if ((opt_mmco || opt_bframes) && is_p) { wlist_n = n_active; for (int i = 0; i < n_active; i++) wlist[i] = full[i < n_full ? i : n_full - 1]; }
-    if (is_b) {                                     /* the two lists of a B picture, all of them active (at most four entries each) */
+    if (is_b) {                                     /* the two lists of a B picture, all of them active (at most sixteen entries each) */
         b_build_lists();
-        n_active = blist_n[0] > 4 ? 4 : blist_n[0]; n_active1 = blist_n[1] > 4 ? 4 : blist_n[1];
+        n_active = blist_n[0] > 16 ? 16 : blist_n[0]; n_active1 = blist_n[1] > 16 ? 16 : blist_n[1];
     }
     /* --slice-lists / --dump-slices: the lists before any reordering, as entries 0 .. n - 1 with their picture, frame_num (P) or
      * frame-store entry (B); taken here, before this picture's marking changes the model */
-    int init_pic[8] = { 0 }, init_fn[8] = { 0 }, n_init = 0, binit[2][8], binit_n[2] = { 0, 0 }, sl_prev[3] = { 0, 0, 0 };
+    int init_pic[NDPB] = { 0 }, init_fn[NDPB] = { 0 }, n_init = 0, binit[2][NDPB], binit_n[2] = { 0, 0 }, sl_prev[3] = { 0, 0, 0 };
     if (is_p && (opt_slice_lists || dump_slices)) {
         if (opt_mmco || opt_bframes) {
             n_init = n_full;
-            for (int i = 0; i < n_full; i++) { init_pic[i] = full[i]; for (int e = 0; e < 8; e++) if (wdpb[e].used && wdpb[e].pic == full[i]) init_fn[i] = wdpb[e].frame_num; }
+            for (int i = 0; i < n_full; i++) { init_pic[i] = full[i]; for (int e = 0; e < NDPB; e++) if (wdpb[e].used && wdpb[e].pic == full[i]) init_fn[i] = wdpb[e].frame_num; }
         } else {
             n_init = refs_available < opt_refs ? refs_available : opt_refs;
             for (int i = 0; i < n_init; i++) { init_pic[i] = pic_no - 1 - i; init_fn[i] = (frame_num - 1 - i) & (max_fn - 1); }
@@ -833,21 +837,21 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
     /* ---- reference picture marking of this picture (decided once, written into every slice header) ---- */
     int n_cmd = 0, cmd[8][3], idr_long = 0, cur_long = 0, cur_long_idx = 0;
     if (opt_mmco) {
-        if (idr) { idr_long = pct(30); for (int i = 0; i < 8; i++) wdpb[i].used = 0; cur_long = idr_long; cur_long_idx = 0; }
+        if (idr) { idr_long = pct(30); for (int i = 0; i < NDPB; i++) wdpb[i].used = 0; cur_long = idr_long; cur_long_idx = 0; }
         else {
             int n_short = 0, n_long = 0, cnt = 0;
-            for (int i = 0; i < 8; i++) if (wdpb[i].used) { cnt++; if (wdpb[i].is_long) n_long++; else n_short++; }
+            for (int i = 0; i < NDPB; i++) if (wdpb[i].used) { cnt++; if (wdpb[i].is_long) n_long++; else n_short++; }
             const int want = pct(60) ? 1 + rnd(opt_mmco5 ? 5 : 4) : 0;   /* 1: drop a short-term, 2: short -> long, 3: drop a long-term, 4: current -> long, 5: drop everything */
             int pick = -1;
-            if (want == 1 || want == 2) { int k = n_short ? rnd(n_short) : -1; for (int i = 0; i < 8 && k >= 0; i++) if (wdpb[i].used && !wdpb[i].is_long && k-- == 0) pick = i; }
-            if (want == 3) { int k = n_long ? rnd(n_long) : -1; for (int i = 0; i < 8 && k >= 0; i++) if (wdpb[i].used && wdpb[i].is_long && k-- == 0) pick = i; }
+            if (want == 1 || want == 2) { int k = n_short ? rnd(n_short) : -1; for (int i = 0; i < NDPB && k >= 0; i++) if (wdpb[i].used && !wdpb[i].is_long && k-- == 0) pick = i; }
+            if (want == 3) { int k = n_long ? rnd(n_long) : -1; for (int i = 0; i < NDPB && k >= 0; i++) if (wdpb[i].used && wdpb[i].is_long && k-- == 0) pick = i; }
             if (want == 1 && pick >= 0 && cnt > 1) {
                 const int num = wdpb[pick].frame_num > frame_num ? wdpb[pick].frame_num - max_fn : wdpb[pick].frame_num;
                 cmd[n_cmd][0] = 1; cmd[n_cmd][1] = frame_num - num - 1; n_cmd++; wdpb[pick].used = 0;
             } else if (want == 2 && pick >= 0) {
                 const int num = wdpb[pick].frame_num > frame_num ? wdpb[pick].frame_num - max_fn : wdpb[pick].frame_num, li = rnd(2);
                 cmd[n_cmd][0] = 3; cmd[n_cmd][1] = frame_num - num - 1; cmd[n_cmd][2] = li; n_cmd++;
-                for (int i = 0; i < 8; i++) if (i != pick && wdpb[i].used && wdpb[i].is_long && wdpb[i].long_idx == li) wdpb[i].used = 0;
+                for (int i = 0; i < NDPB; i++) if (i != pick && wdpb[i].used && wdpb[i].is_long && wdpb[i].long_idx == li) wdpb[i].used = 0;
                 wdpb[pick].is_long = 1; wdpb[pick].long_idx = li;
             } else if (want == 3 && pick >= 0 && cnt > 1) {
                 cmd[n_cmd][0] = 2; cmd[n_cmd][1] = wdpb[pick].long_idx; n_cmd++; wdpb[pick].used = 0;
@@ -855,36 +859,36 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
                 /* operation 5: every other reference goes, and the picture counts as frame_num 0 from here on (7.4.3, 8.2.1):
                  * the next picture is written with frame_num 1 (main loop) */
                 cmd[n_cmd][0] = 5; n_cmd++;
-                for (int i = 0; i < 8; i++) wdpb[i].used = 0;
+                for (int i = 0; i < NDPB; i++) wdpb[i].used = 0;
                 had_mmco5 = 1;
             } else if (want == 4) {
                 const int li = rnd(2);
                 cmd[n_cmd][0] = 6; cmd[n_cmd][2] = li; n_cmd++;
-                for (int i = 0; i < 8; i++) if (wdpb[i].used && wdpb[i].is_long && wdpb[i].long_idx == li) wdpb[i].used = 0;
+                for (int i = 0; i < NDPB; i++) if (wdpb[i].used && wdpb[i].is_long && wdpb[i].long_idx == li) wdpb[i].used = 0;
                 cur_long = 1; cur_long_idx = li;
             }
             /* no sliding window under adaptive marking: make room for this picture ourselves */
-            cnt = 0; for (int i = 0; i < 8; i++) cnt += wdpb[i].used;
+            cnt = 0; for (int i = 0; i < NDPB; i++) cnt += wdpb[i].used;
             if (n_cmd && cnt >= opt_refs) {
                 int old = -1, old_num = 0;
-                for (int i = 0; i < 8; i++) if (wdpb[i].used && !wdpb[i].is_long) { const int num = wdpb[i].frame_num > frame_num ? wdpb[i].frame_num - max_fn : wdpb[i].frame_num; if (old < 0 || num < old_num) { old = i; old_num = num; } }
+                for (int i = 0; i < NDPB; i++) if (wdpb[i].used && !wdpb[i].is_long) { const int num = wdpb[i].frame_num > frame_num ? wdpb[i].frame_num - max_fn : wdpb[i].frame_num; if (old < 0 || num < old_num) { old = i; old_num = num; } }
                 if (old >= 0) { cmd[n_cmd][0] = 1; cmd[n_cmd][1] = frame_num - old_num - 1; n_cmd++; wdpb[old].used = 0; }
-                else { for (int i = 0; i < 8; i++) if (wdpb[i].used) { cmd[n_cmd][0] = 2; cmd[n_cmd][1] = wdpb[i].long_idx; n_cmd++; wdpb[i].used = 0; break; } }
+                else { for (int i = 0; i < NDPB; i++) if (wdpb[i].used) { cmd[n_cmd][0] = 2; cmd[n_cmd][1] = wdpb[i].long_idx; n_cmd++; wdpb[i].used = 0; break; } }
             }
             if (!n_cmd) {                                       /* sliding window (8.2.5.3) */
                 int old = -1, old_num = 0;
-                for (int i = 0; i < 8; i++) if (wdpb[i].used && !wdpb[i].is_long) { const int num = wdpb[i].frame_num > frame_num ? wdpb[i].frame_num - max_fn : wdpb[i].frame_num; if (old < 0 || num < old_num) { old = i; old_num = num; } }
+                for (int i = 0; i < NDPB; i++) if (wdpb[i].used && !wdpb[i].is_long) { const int num = wdpb[i].frame_num > frame_num ? wdpb[i].frame_num - max_fn : wdpb[i].frame_num; if (old < 0 || num < old_num) { old = i; old_num = num; } }
                 if (cnt >= opt_refs && old >= 0) wdpb[old].used = 0;
             }
         }
-        for (int i = 0; i < 8; i++) if (!wdpb[i].used) { wdpb[i].used = 1; wdpb[i].pic = pic_no; wdpb[i].frame_num = had_mmco5 ? 0 : frame_num; wdpb[i].is_long = cur_long; wdpb[i].long_idx = cur_long_idx; break; }
+        for (int i = 0; i < NDPB; i++) if (!wdpb[i].used) { wdpb[i].used = 1; wdpb[i].pic = pic_no; wdpb[i].frame_num = had_mmco5 ? 0 : frame_num; wdpb[i].is_long = cur_long; wdpb[i].long_idx = cur_long_idx; break; }
     }
     if (opt_bframes && !opt_mmco && !is_b) {        /* reference picture under the sliding window; its motion is saved when it is finished */
-        if (idr) for (int i = 0; i < 8; i++) wdpb[i].used = 0;
+        if (idr) for (int i = 0; i < NDPB; i++) wdpb[i].used = 0;
         int cnt = 0, old = -1, old_num = 0;
-        for (int i = 0; i < 8; i++) if (wdpb[i].used) { cnt++; const int num = wdpb[i].frame_num > frame_num ? wdpb[i].frame_num - max_fn : wdpb[i].frame_num; if (old < 0 || num < old_num) { old = i; old_num = num; } }
+        for (int i = 0; i < NDPB; i++) if (wdpb[i].used) { cnt++; const int num = wdpb[i].frame_num > frame_num ? wdpb[i].frame_num - max_fn : wdpb[i].frame_num; if (old < 0 || num < old_num) { old = i; old_num = num; } }
         if (cnt >= opt_refs && old >= 0) wdpb[old].used = 0;
-        for (int i = 0; i < 8; i++) if (!wdpb[i].used) { wdpb[i].used = 1; wdpb[i].pic = pic_no; wdpb[i].frame_num = frame_num; wdpb[i].is_long = 0; wdpb[i].poc = cur_poc; cur_entry = i; break; }
+        for (int i = 0; i < NDPB; i++) if (!wdpb[i].used) { wdpb[i].used = 1; wdpb[i].pic = pic_no; wdpb[i].frame_num = frame_num; wdpb[i].is_long = 0; wdpb[i].poc = cur_poc; cur_entry = i; break; }
     }
     for (int sl = 0; sl < opt_slices; sl++) {
         const int first = (int)((long)NMB * sl / opt_slices), end = (int)((long)NMB * (sl + 1) / opt_slices);
@@ -904,8 +908,8 @@ static void put_slice(FILE *f, int idr, int is_p, int is_b, int frame_num, int i
         if (opt_slice_lists && (is_p || is_b)) {
             for (int X = 0; X < (is_b ? 2 : 1); X++) {
                 const int ni = is_b ? binit_n[X] : n_init;
-                int len = X ? pic_n_active1 : pic_n_active, idx[16], init_idx[8], list[16], k = 0;
-                for (int i = 0; i < 8; i++) init_idx[i] = i;
+                int len = X ? pic_n_active1 : pic_n_active, idx[16], init_idx[NDPB], list[16], k = 0;
+                for (int i = 0; i < NDPB; i++) init_idx[i] = i;
                 if (many) {                                   /* the four frames twice, rotated by the slice's number: all eight entries named */
                     k = 8;
                     for (int i = 0; i < 8; i++) idx[i] = (i + sl) & 3;
@@ -1254,7 +1258,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--vui-reorder")) { opt_vui_reorder = v < 0 ? 0 : v > 16 ? 16 : v; opt_vui_full = i + 1 < argc && strstr(argv[i + 1], ":full") != NULL; i++; }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
-    if (W < 1 || H < 1 || W > 512 || H > 512 || frames < 1 || opt_qp < 0 || opt_qp > 51 || opt_refs < 1 || opt_refs > ((opt_mmco || opt_bframes) ? 4 : 2) || (opt_bframes && (opt_refs < 2 || opt_bframes > 4)) || opt_alpha < -6 || opt_alpha > 6 || opt_beta < -6 || opt_beta > 6) { fprintf(stderr, "bad geometry\n"); return 2; }
+    if (W < 1 || H < 1 || W > 512 || H > 512 || frames < 1 || opt_qp < 0 || opt_qp > 51 || opt_refs < 1 || opt_refs > 16 || (opt_bframes && (opt_refs < 2 || opt_bframes > 4)) || opt_alpha < -6 || opt_alpha > 6 || opt_beta < -6 || opt_beta > 6) { fprintf(stderr, "bad geometry\n"); return 2; }
     if (opt_slice_lists && (opt_mmco || opt_refs < 2 || opt_reorder || opt_wp_dup)) { fprintf(stderr, "--slice-lists needs --refs >= 2 and excludes --mmco, --reorder, --wp-dup\n"); return 2; }
     if (cqm_arg) {
         if (!strcmp(cqm_arg, "jvt")) opt_cqm = 1;

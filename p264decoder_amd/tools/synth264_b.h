@@ -18,7 +18,7 @@ static void b_build_lists(void)
             const int want_before = (l == 0) == (side == 0);
             for (;;) {
                 int best = -1;
-                for (int i = 0; i < 8; i++) {
+                for (int i = 0; i < NDPB; i++) {
                     if (!wdpb[i].used || wdpb[i].is_long) continue;
                     if ((wdpb[i].poc < cur_poc) != want_before) continue;
                     int taken = 0;

@@ -217,7 +217,9 @@ class Census:
     predicted 4x4 block, list and plane kind - coded: the plane's residual of the block's ITEM is present (the RESID bit of the
     item's key: any luma block of the item / any chroma level of the macroblock); items: Counter of (kind, phase class, luma window
     inside, chroma window inside, luma coded, chroma coded) per luma item; roads: Counter of classify's roads - (road, weighted_bipred) for the macroblocks of B pictures without explicit weights; weights: the set of
-    (weighted_bipred, w0) of the bi-predicted blocks; stats: j / j_outside."""
+    (weighted_bipred, w0) of the bi-predicted blocks; stats: j / j_outside; entries: Counter of (list, entry, item kind, 'p' / 'b'
+    by the picture's slice type, road) per predicted 4x4 block and list; pairs: Counter of (entry 0, entry 1, item kind of the
+    list-0 fetch, road) per bi-predicted 4x4 block."""
 
     def __init__(self):
         self.cells = collections.Counter()
@@ -225,6 +227,8 @@ class Census:
         self.roads = collections.Counter()
         self.weights = set()
         self.stats = collections.Counter()
+        self.entries = collections.Counter()
+        self.pairs = collections.Counter()
 
 
 def _inside(sides):
@@ -261,6 +265,9 @@ def survey(pic, census):
                 acc += _side(x, n, W >> chroma) + _side(y, n, H >> chroma)
             census.cells[("y", v[0] & 3, v[1] & 3, kind, tuple(sy), lists, coded_y)] += 1
             census.cells[("c", v[0] & 7, v[1] & 7, kind, tuple(sc), lists, coded_c)] += 1
+            census.entries[(l, (e0, e1)[l], kind, "b" if d.slice_type == N.SLICE_B else "p", road)] += 1
+            if lists == "bi" and l == 0:
+                census.pairs[(e0, e1, kind, road)] += 1
             if (l, blocks) not in seen:
                 seen.add((l, blocks))
                 census.items[(kind, phase_class(v[0] & 3, v[1] & 3), _inside(sy), _inside(sc), coded_y, coded_c)] += 1

@@ -30,6 +30,7 @@ def arguments():
     out += [("b:%d" % i, v) for i, v in enumerate(A.B_STREAMS)]
     for tag, group in (("mmco", A.MMCO), ("sliced", A.SLICED), ("sub8x8", A.SUB8X8), ("reorder", [A.REORDER])):
         out += [("multiref:%s:%d" % (tag, i), v) for i, v in enumerate(group)]
+    out += [("long_lists:" + k, v) for k, v in A.LONG_LISTS.items()]       # (behind everything recorded before them: the damage drawn for those stays)
     return out
 
 

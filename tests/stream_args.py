@@ -74,6 +74,17 @@ MMCO = ["--mbw 8 --mbh 6 --frames 40 --gop 14 --seed 71 --refs 3 --mmco --coded 
         # operation 5 too: everything but the current picture goes, which then counts as frame_num 0 (7.4.3, 8.2.1) - the
         # pictures behind it (at least num_ref_frames P pictures before the next one) build their lists against that
         "--mbw 7 --mbh 5 --frames 60 --gop 0 --seed 73 --refs 3 --mmco5 --coded 8 --maxlevel 6"]
+# reference lists that grow to 16 entries in a store of 17 slots (tests/test_long_lists_streams_cpu.py): 7 x 5 macroblocks, more
+# pictures than the window holds - a P stream more than 17 pictures, a B stream more than 17 reference pictures
+LONG_LISTS_COMMON = "--mbw 7 --mbh 5 --coded 8 --maxlevel 6"
+LONG_LISTS = {
+    "p_cavlc": LONG_LISTS_COMMON + " --frames 24 --gop 0 --seed 161 --refs 16 --sub8x8",
+    "p_cavlc_mmco": LONG_LISTS_COMMON + " --frames 44 --gop 0 --seed 162 --refs 16 --sub8x8 --mmco",
+    "p_cabac_9": LONG_LISTS_COMMON + " --frames 16 --gop 0 --seed 163 --refs 9 --cabac",
+    "b_cabac_temporal": LONG_LISTS_COMMON + " --frames 58 --seed 164 --refs 16 --bframes 2 --implicit --temporal --cabac",
+    "b_cavlc_wp_8": LONG_LISTS_COMMON + " --frames 37 --seed 165 --refs 8 --bframes 2 --wp --wp-bi",
+    "p_slice_lists_6": LONG_LISTS_COMMON + " --frames 12 --gop 0 --seed 166 --refs 6 --slices 3 --slice-lists",
+}
 B_CIF = "--mbw 22 --mbh 18 --frames 7 --seed 5 --refs 2 --bframes 2 --implicit --d8inf --coded 8 --maxlevel 8"      # I P B B P B B
 
 LAUNCH_SHAPES = [  # (P264AMD_DEBLOCK_RB_LOG2, P264AMD_DEBLOCK_PICS_PER_WG, P264AMD_INTRA_WAVES)

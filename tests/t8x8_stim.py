@@ -239,7 +239,9 @@ def drawn_picture(rng, name, mb_w, mb_h, share=0.6, unflagged=(), **kw):
     """a seam_fuzz picture; `share` of its inter macroblocks (none of `unflagged`) lose their 4x4 luma blocks and get 8x8 ones"""
     kw.setdefault("n_ref", 2)
     kw.setdefault("n_ref_l1", 2)
-    pic = seam_fuzz.make_picture(rng, mb_w, mb_h, slots=3, dst_slot=0, level_style="small", qp_mode="random", mv_range=40, **kw)
+    kw.setdefault("slots", 3)
+    kw.setdefault("dst_slot", 0)
+    pic = seam_fuzz.make_picture(rng, mb_w, mb_h, level_style="small", qp_mode="random", mv_range=40, **kw)
     rec = pic.rec
     chosen = [m for m in range(pic.n_mb) if rec["mb_type"][m] > N.MB_IPCM and m not in unflagged and rng.random() < share]
     # take the chosen macroblocks' 4x4 luma entries out of the stream
