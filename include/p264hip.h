@@ -498,8 +498,8 @@ int     p264hip_export_resized(p264hip_ctx *ctx, const int *streams, const int *
  * whose ROIs need more goes out as several pairs of launches on the one stream.  Per call the host sends the n descriptors and
  * nothing per destination index.
  *
- * Not built: ROI lists that live in device memory (the host must know n to size dst anyway; k_roi_taps / k_roi_aa_taps are what
- * such a variant would keep); a pipeline sink that takes ROIs; deliveries in output order as ROI sources. */
+ * ROI lists that live in device memory - a detector's boxes - have an entry of their own, p264hip_export_rois_device below.
+ * Not built: a pipeline sink that takes ROIs; deliveries in output order as ROI sources. */
 typedef struct p264hip_roi {            /* 40 bytes */
     int32_t stream, slot;               /* the picture */
     int32_t left, top, width, height;   /* source window, luma samples: all even, width, height > 0, inside the frame */
@@ -559,6 +559,66 @@ int     p264hip_roi_aa_segment(const p264hip_roi_t *roi, const p264hip_resize_t 
 /* host only: the tile width k_roi_aa_* use for this ROI (64, 32, 16 or 8) and the strips of 16 luma / 8 chroma samples of a tile
  * row in LDS (either pointer may be null); P264HIP_EINVAL as above */
 int     p264hip_roi_aa_tile_width(const p264hip_roi_t *roi, const p264hip_resize_t *r, int *luma_strips, int *chroma_strips);
+
+/* ---- the same exports from an ROI LIST IN DEVICE MEMORY: a detector's boxes go to a second model without the host seeing them.
+ * One entry for both filters (r->filter is 0 or 2).  The host knows the capacity n of the list and the output, nothing of an ROI;
+ * what it decided per ROI above - the check, the descriptor, the segment's place, the tile - the kernel k_roi_plan decides on the
+ * device (csrc/hip/kernel_roi_dev.h), by the text of include/p264hip_roi_rule.h, which the host compiles as p264hip_roi_status.
+ *
+ * An ROI has a STATUS: 0, or the first rule it breaks in the order of the refusals of p264hip_rois_check / p264hip_rois_aa_check.
+ * Picture i with status 0 gets exactly the bytes p264hip_export_rois / p264hip_export_rois_aa writes for that ROI at index i; for a
+ * picture with any other status NO byte at dst_dev + i*frame_stride is written.  An invalid ROI refuses nothing: the call cannot
+ * know of it.  status_dev, where given, receives the n status words. */
+enum { P264HIP_ROI_OK = 0,              /* the ROI is valid */
+       P264HIP_ROI_UNUSED = 1,          /* index at or beyond the device count */
+       P264HIP_ROI_BAD_PICTURE = 2,     /* stream or slot out of range */
+       P264HIP_ROI_NO_PICTURE = 3,      /* slot -1 and the slot table has no picture for the stream */
+       P264HIP_ROI_WINDOW_EMPTY = 4,    /* negative offset or no samples */
+       P264HIP_ROI_WINDOW_ODD = 5,      /* window with an odd member */
+       P264HIP_ROI_WINDOW_OUTSIDE = 6,  /* window leaves the frame */
+       P264HIP_ROI_RECT_SMALL = 7,      /* rectangle with a negative offset or below 2 x 2 */
+       P264HIP_ROI_RECT_ODD = 8,        /* rectangle with an odd member */
+       P264HIP_ROI_RECT_OUTSIDE = 9,    /* rectangle leaves the output */
+       P264HIP_ROI_REDUCTION = 10 };    /* filter 2 only: width > m*dst_width or height > m*dst_height, m = max_reduction; 0 means 32 */
+/* host only, no device: the status of one ROI (one of 0, 2, 4 .. 10: the slot is taken as it stands) in the output r describes
+ * (width, height and filter are read), a frame of mb_w x mb_h macroblocks and a store of n_streams x slots.  0 exactly where
+ * p264hip_rois_check / p264hip_rois_aa_check - with max_reduction 0 - accepts the ROI in an acceptable description */
+int     p264hip_roi_status(const p264hip_roi_t *roi, const p264hip_resize_t *r, int mb_w, int mb_h, int n_streams, int slots, int max_reduction);
+/* The plan of a call.  The host cannot add up segments it has not seen, so EVERY ROI of a device-list call gets a segment of
+ * seg_words words - with filter 2 the largest segment of any ROI that passes the rule at max_reduction - and a pair of launches
+ * takes rois_per_pair = P264HIP_ROI_SCRATCH_BYTES / 4 / seg_words ROIs (at least 1); the antialiased bodies launch with aa_tiles
+ * workgroups per ROI and aa_lds_bytes of dynamic LDS, the most any passing ROI needs (both 0 with filter 0).  max_reduction is what
+ * keeps a caller whose boxes reduce by 3:1 from paying for 32:1.  Host only; P264HIP_EINVAL for a description
+ * p264hip_rois_frame_bytes / _aa_frame_bytes refuses and a max_reduction other than 0 with filter 0, outside 0 .. 32 with filter 2 */
+typedef struct p264hip_rois_plan { int32_t seg_words, rois_per_pair, aa_tiles, aa_lds_bytes; } p264hip_rois_plan_t;
+int     p264hip_rois_device_plan(const p264hip_resize_t *r, int max_reduction, p264hip_rois_plan_t *out);
+enum { P264HIP_ROIS_AFTER = 1, P264HIP_ROIS_BEFORE = 2 };
+typedef struct p264hip_rois_dev {
+    const p264hip_roi_t *rois_dev;      /* device memory, n entries, address a multiple of 8 */
+    const int32_t *count_dev;           /* device, one value, clamped into 0 .. n: the ROIs from it on are P264HIP_ROI_UNUSED; NULL: all n */
+    int32_t       *status_dev;          /* device, n entries; NULL: not written */
+    const int32_t *slot_of_stream;      /* HOST, n_streams entries (a slot, or -1: no picture), consumed before the call returns: what
+                                           slot -1 of an ROI stands for; NULL: slot -1 is invalid */
+    void          *after_stream, *before_stream;    /* hipStream_t; read with the flags below, NULL: the legacy default stream */
+    int32_t n, max_reduction, flags;    /* P264HIP_ROIS_AFTER: the context's stream waits for what after_stream has queued before it
+                                           reads the list; P264HIP_ROIS_BEFORE: before_stream waits for the call's last launch */
+} p264hip_rois_dev_t;
+/* 0, or P264HIP_EINVAL (host only) for what can be known without the list: whatever p264hip_rois_frame_bytes / _aa_frame_bytes
+ * refuses in the description, a frame_stride p264hip_resize_check refuses, a null or misaligned rois_dev, n < 1, a fill with a bit
+ * above 23 set, a frame above 65535 samples a side, a max_reduction p264hip_rois_device_plan refuses, unknown flag bits and a
+ * slot-table entry outside -1 .. slots - 1 */
+int     p264hip_rois_device_check(const p264hip_rois_dev_t *l, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots);
+/* Asynchronous on the context's stream behind every reconstruct queued before it: one k_roi_plan launch, then a pair of launches
+ * (taps, body) per rois_per_pair ROIs.  P264HIP_EINVAL, before anything is queued, for what p264hip_rois_device_check refuses
+ * against the context's geometry, a null dst_dev or one that is no multiple of the element size, and dst_bytes <
+ * (n-1)*frame_stride + the picture's bytes.  Per call the host stages the parameters and, where given, the n_streams integers of
+ * the slot table: nothing per ROI, and it reads nothing back.  The descriptors and the taps lie in buffers of the context that
+ * grow with n and the plan; growing one waits for the context's stream.  A call that finds them large enough does not synchronise
+ * the host with the device (it may wait for the copy of the slot table of three calls before, long done in any steady state).
+ * Without P264HIP_ROIS_BEFORE the call is complete after p264hip_sync or a marker; rois_dev, count_dev and status_dev belong to
+ * the call until then (with the flag: until before_stream has passed the wait).  The kernels write the bytes of the layout of the
+ * pictures with status 0, the status words, and no others. */
+int     p264hip_export_rois_device(p264hip_ctx *ctx, const p264hip_rois_dev_t *l, const p264hip_resize_t *r, uint32_t fill, void *dst_dev, size_t dst_bytes);
 
 /* plain synchronous copies between host and device memory (the fan-out's TCP transport uses them where it stands in for a
  * device-to-device transport in tests) */

@@ -85,6 +85,14 @@ int  p264pipe_set_sink_resized(p264pipe *p, const p264hip_resize_t *r, void *con
  * ago -, so this call is of no use to a delivery's callback; deliveries in output order as ROI sources, and a sink that takes ROIs,
  * are not built. */
 int  p264pipe_export_last_rois(p264pipe *p, const p264hip_roi_t *rois, int n, const p264hip_resize_t *r, uint32_t fill, void *dst_dev, size_t bytes);
+/* The same from an ROI LIST IN DEVICE MEMORY (p264hip_export_rois_device, include/p264hip.h: one entry for both filters).  The
+ * ROIs carry slot -1; the pipeline fills the slot table from every stream's last decoded picture, so l->slot_of_stream must be NULL.
+ * A stream without a picture yet refuses nothing: its ROIs get the status P264HIP_ROI_NO_PICTURE and their pictures are not
+ * written, as any invalid ROI's.  -1 before the first round (there is no device context), for a slot table, and for what
+ * p264hip_export_rois_device refuses.  The rest of l passes through.  Callable between runs and from inside a decode-order sink's
+ * callback, as its sibling.  Without P264HIP_ROIS_BEFORE it is complete on return; with it the call is queued only, before_stream
+ * waits for it, and the next round's reconstruct is on the context's stream behind it. */
+int  p264pipe_export_last_rois_device(p264pipe *p, const p264hip_rois_dev_t *l, const p264hip_resize_t *r, uint32_t fill, void *dst_dev, size_t bytes);
 
 /* ---- pictures in OUTPUT (display) order ----
  * on != 0: every stream's parser runs the output process of H.264 C.4 (p264parse_set_output_order, include/p264parse.h: the rule,

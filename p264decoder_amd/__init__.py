@@ -16,7 +16,8 @@ from .recon import HipReconstructor, ParsedPicture, Parser, P264Error, device_co
 from .decoder import Decoder, param_default
 from .pipeline import Pipeline
 from ._native import letterbox
+from .rois import rois_from_boxes
 from .fanout import FanOut
 
 __all__ = ["Decoder", "param_default", "Pipeline", "FanOut", "Parser", "ParsedPicture", "HipReconstructor", "P264Error",
-           "device_count", "letterbox", "_native"]
+           "device_count", "letterbox", "rois_from_boxes", "_native"]

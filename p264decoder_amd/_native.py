@@ -183,6 +183,30 @@ class Roi(C.Structure):
 
 
 ROI_SCRATCH_BYTES = 16 << 20          # P264HIP_ROI_SCRATCH_BYTES
+# P264HIP_ROI_*: the status of an ROI of a list in device memory (p264hip_export_rois_device)
+(ROI_OK, ROI_UNUSED, ROI_BAD_PICTURE, ROI_NO_PICTURE, ROI_WINDOW_EMPTY, ROI_WINDOW_ODD, ROI_WINDOW_OUTSIDE, ROI_RECT_SMALL, ROI_RECT_ODD,
+ ROI_RECT_OUTSIDE, ROI_REDUCTION) = range(11)
+ROIS_AFTER, ROIS_BEFORE = 1, 2        # P264HIP_ROIS_*
+
+
+class RoisPlan(C.Structure):
+    """p264hip_rois_plan_t"""
+    _fields_ = [("seg_words", C.c_int32), ("rois_per_pair", C.c_int32), ("aa_tiles", C.c_int32), ("aa_lds_bytes", C.c_int32)]
+
+
+class RoisDev(C.Structure):
+    """p264hip_rois_dev_t"""
+    _fields_ = [("rois_dev", C.c_void_p), ("count_dev", C.c_void_p), ("status_dev", C.c_void_p), ("slot_of_stream", C.POINTER(C.c_int32)),
+                ("after_stream", C.c_void_p), ("before_stream", C.c_void_p), ("n", C.c_int32), ("max_reduction", C.c_int32), ("flags", C.c_int32)]
+
+
+def rois_device_plan(desc, max_reduction=0, lib=None):
+    """p264hip_rois_device_plan as a dict (seg_words, rois_per_pair, aa_tiles, aa_lds_bytes): what a call with an ROI list in device
+    memory reserves per ROI for the output `desc` (a p264hip_resize_t) describes.  Raises where the library refuses."""
+    plan = RoisPlan()
+    if (lib or load()).p264hip_rois_device_plan(C.byref(desc), int(max_reduction), C.byref(plan)) != 0:
+        raise ValueError("p264hip_rois_device_plan refuses the description (filter %d, max_reduction %d)" % (desc.filter, max_reduction))
+    return {n: int(getattr(plan, n)) for n, _ in RoisPlan._fields_}
 
 
 def roi_array(rois, head=2):
@@ -218,13 +242,14 @@ def fill_word(fill):
     return y | cb << 8 | cr << 16
 
 
-def export_out(n, desc, per, pitch, frame_stride, out, check=None):
+def export_out(n, desc, per, pitch, frame_stride, out, check=None, wait=True):
     """(out, pointer, bytes): where an export call writes its n pictures of the description `desc` (p264hip_export_t /
     p264hip_resize_t), `per` bytes each.  out: a (device pointer, bytes) pair, handed through; a torch tensor on the device; or None -
     a new tensor (n, H*3//2, W) for I420 / NV12, (n, H, W, 3) for RGB24, (n, 3, H, W) for RGBP of the description's dtype at the tight
     layout, (n, bytes) uint8 where a pitch or a frame_stride is given.  check = (exception type, method name): refuse a tensor that
     is not contiguous, on the device and of the dtype (or uint8), and wait for what torch's current stream still has queued on it -
-    the context has its own stream.  torch is imported only where a tensor is involved."""
+    the context has its own stream; wait=False leaves that wait out, for a call that orders the streams itself.  torch is imported
+    only where a tensor is involved."""
     if isinstance(out, tuple):
         return out, out[0], out[1]
     torch = import_torch()
@@ -241,7 +266,8 @@ def export_out(n, desc, per, pitch, frame_stride, out, check=None):
         error, name = check
         if not (out.is_cuda and out.is_contiguous() and (out.element_size() == 1 if dtype is None else out.dtype in (want, torch.uint8))):
             raise error("%s: out must be a contiguous %s tensor on the device" % (name, "uint8" if dtype is None else "%s (or uint8)" % want))
-        torch.cuda.current_stream(out.device).synchronize()
+        if wait:
+            torch.cuda.current_stream(out.device).synchronize()
     return out, out.data_ptr(), out.numel() * out.element_size()
 
 
@@ -440,6 +466,18 @@ def load(path=None):
         lib.p264hip_roi_aa_segment.argtypes = [C.POINTER(Roi), C.POINTER(Resize), C.POINTER(C.c_uint32)]
         lib.p264hip_roi_aa_tile_width.restype = C.c_int
         lib.p264hip_roi_aa_tile_width.argtypes = [C.POINTER(Roi), C.POINTER(Resize), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(lib, "p264hip_export_rois_device"):
+        lib.p264hip_roi_status.restype = C.c_int
+        lib.p264hip_roi_status.argtypes = [C.POINTER(Roi), C.POINTER(Resize), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.p264hip_rois_device_plan.restype = C.c_int
+        lib.p264hip_rois_device_plan.argtypes = [C.POINTER(Resize), C.c_int, C.POINTER(RoisPlan)]
+        lib.p264hip_rois_device_check.restype = C.c_int
+        lib.p264hip_rois_device_check.argtypes = [C.POINTER(RoisDev), C.POINTER(Resize), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.p264hip_export_rois_device.restype = C.c_int
+        lib.p264hip_export_rois_device.argtypes = [C.c_void_p, C.POINTER(RoisDev), C.POINTER(Resize), C.c_uint32, C.c_void_p, C.c_size_t]
+    if hasattr(lib, "p264pipe_export_last_rois_device"):
+        lib.p264pipe_export_last_rois_device.restype = C.c_int
+        lib.p264pipe_export_last_rois_device.argtypes = [C.c_void_p, C.POINTER(RoisDev), C.POINTER(Resize), C.c_uint32, C.c_void_p, C.c_size_t]
     if hasattr(lib, "p264pipe_export_last_rois"):
         lib.p264pipe_export_last_rois.restype = C.c_int
         lib.p264pipe_export_last_rois.argtypes = [C.c_void_p, C.POINTER(Roi), C.c_int, C.POINTER(Resize), C.c_uint32, C.c_void_p, C.c_size_t]

@@ -28,6 +28,9 @@ struct RoiDev {                     // one ROI as the kernels read it: 32 bytes
     uint32_t sx, sy;                // the window: left | width << 16, top | height << 16
     uint32_t pad[2];
 };
+// frame == ROI_SKIP: an ROI of a device list that k_roi_plan (kernel_roi_dev.h) found invalid - every kernel returns for it behind
+// its first load of the record.  A host list never holds it: its frame indices are below n_streams * slots
+#define ROI_SKIP 0xffffffffu
 
 __host__ __device__ __forceinline__ int roi_pad4(int n) { return (n + 3) & ~3; }
 // words of the segment of a dw x dh rectangle
@@ -37,6 +40,7 @@ __global__ __launch_bounds__(ROI_TAPS_THREADS) void k_roi_taps(const RoiDev *roi
 {
     const RoiDev *o = rois + roi_base + (int)blockIdx.y;
     const uint4 q = gload4(o);
+    if (q.x == ROI_SKIP) return;
     const uint2 s = gload2(&o->sx);
     const int dw = (int)(q.z >> 16), dh = (int)(q.w >> 16);
     const int t = (int)(blockIdx.x * ROI_TAPS_THREADS + threadIdx.x);
@@ -66,6 +70,7 @@ __device__ __forceinline__ void roi_body(const uint8_t *frames, size_t frame_byt
     if (wt >= e.n_tiles) return;
     const int pic = pic_base + (int)blockIdx.y;
     const uint4 q = gload4(rois + pic);
+    if (q.x == ROI_SKIP) return;                            // (a device list's invalid ROI: its picture is not written)
     const uint8_t *src = frames + (size_t)q.x * frame_bytes;
     const uint32_t *seg = scratch + q.y;
     uint8_t *out = dst + (int64_t)pic * e.frame_stride;

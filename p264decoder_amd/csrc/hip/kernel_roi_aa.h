@@ -38,6 +38,7 @@ __global__ __launch_bounds__(ROI_TAPS_THREADS) void k_roi_aa_taps(const RoiDev *
 {
     const RoiDev *o = rois + roi_base + (int)blockIdx.y;
     const uint4 q = gload4(o);
+    if (q.x == ROI_SKIP) return;
     const uint2 s = gload2(&o->sx);
     (void)p264hip_roi_aa_entry(scratch + q.y, (int)(s.x & 0xffffu), (int)(s.y & 0xffffu), (int)(s.x >> 16), (int)(s.y >> 16), (int)(q.z >> 16), (int)(q.w >> 16),
                          (int)(blockIdx.x * ROI_TAPS_THREADS + threadIdx.x));
@@ -61,6 +62,7 @@ __device__ __forceinline__ void roi_aa_body(const uint8_t *frames, size_t frame_
     const int pic = pic_base + (int)blockIdx.y;
     const RoiDev *o = rois + pic;
     const uint4 q = gload4(o);
+    if (q.x == ROI_SKIP) return;                            // (workgroup-uniform, before the first barrier: a device list's invalid ROI)
     const uint2 cfg = gload2(&o->pad[0]);
     const int tw_shift = rfl((int)(cfg.x & 255u)), ns_l = rfl((int)((cfg.x >> 8) & 255u)), ns_c = rfl((int)((cfg.x >> 16) & 255u));
     const int W = e.r.w, H = e.r.h, cw = W >> 1;

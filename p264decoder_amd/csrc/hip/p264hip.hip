@@ -28,6 +28,7 @@
 #include "kernel_resize_aa.h"
 #include "kernel_roi.h"
 #include "kernel_roi_aa.h"
+#include "kernel_roi_dev.h"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -153,6 +154,8 @@ struct p264hip_ctx {
     // p264hip_export_frames: the frame index (stream * slots + slot) of every picture of a call, a ring like the batch's
     uint32_t *h_exp[BATCH_RING] = {}, *d_exp[BATCH_RING] = {}; hipEvent_t exp_free[BATCH_RING] = {}; int exp_cap = 0, exp_ring = 0;
     uint32_t *d_roi = nullptr; size_t roi_cap = 0;          // the tap scratch of p264hip_export_rois (kernel_roi.h), bytes
+    // p264hip_export_rois_device: the descriptors k_roi_plan writes (kernel_roi_dev.h), bytes, and the events of its two stream orders
+    RoiDev *d_roi_tab = nullptr; size_t roi_tab_cap = 0; hipEvent_t roi_after = nullptr, roi_before = nullptr;
     p264hip_launch_info_t last = {};       // what the last p264hip_reconstruct launched
     hipEvent_t markers[P264HIP_MARKERS] = {};
     int next_marker = 0;
@@ -241,6 +244,9 @@ extern "C" void p264hip_destroy(p264hip_ctx *c)
         if (c->exp_free[i]) (void)hipEventDestroy(c->exp_free[i]);
     }
     if (c->d_roi) (void)hipFree(c->d_roi);
+    if (c->d_roi_tab) (void)hipFree(c->d_roi_tab);
+    if (c->roi_after) (void)hipEventDestroy(c->roi_after);
+    if (c->roi_before) (void)hipEventDestroy(c->roi_before);
     for (auto &s : c->stamps) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     if (c->frames) (void)hipFree(c->frames);
@@ -937,6 +943,74 @@ extern "C" int p264hip_export_rois(p264hip_ctx *c, const p264hip_roi_t *rois, in
 extern "C" int p264hip_export_rois_aa(p264hip_ctx *c, const p264hip_roi_t *rois, int n, const p264hip_resize_t *e, uint32_t fill, void *dst, size_t dst_bytes)
 {
     return export_rois(c, rois, n, e, fill, dst, dst_bytes, true);
+}
+
+// ---- the same from an ROI list in device memory (include/p264hip.h: p264hip_rois_dev_t; kernel_roi_dev.h) ----
+extern "C" const char *p264hip_rois_device_why_(const p264hip_rois_dev_t *l, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots);     // csrc/host/resize_layout.c
+
+extern "C" int p264hip_export_rois_device(p264hip_ctx *c, const p264hip_rois_dev_t *l, const p264hip_resize_t *e, uint32_t fill, void *dst, size_t dst_bytes)
+{
+    const char *fn = "p264hip_export_rois_device";
+    if (!c || !dst) return fail(P264HIP_EINVAL, "%s: bad argument", fn);
+    if (const char *why = p264hip_rois_device_why_(l, e, fill, c->g.mb_w, c->g.mb_h, c->n_streams, c->slots))
+        return fail(P264HIP_EINVAL, "%s: %s (n %d, max_reduction %d, flags 0x%x, fill 0x%x, a %dx%d frame)", fn, why, l ? l->n : 0, l ? l->max_reduction : 0, l ? l->flags : 0, fill, c->g.w, c->g.h);
+    const bool aa = e->filter == P264HIP_FILTER_BILINEAR_AA;
+    const int n = l->n;
+    int64_t pitch, stride;
+    int rc = export_dst(fn, n, aa ? p264hip_rois_aa_frame_bytes(e) : p264hip_rois_frame_bytes(e), elem_bytes(e->dtype), e->pitch, e->frame_stride, e->format, e->width, dst, dst_bytes, &pitch, &stride);
+    if (rc) return rc;
+    p264hip_rois_plan_t plan;
+    if (p264hip_rois_device_plan(e, l->max_reduction, &plan)) return fail(P264HIP_EINVAL, "%s: no plan for this output", fn);
+    if ((size_t)n > SIZE_MAX / sizeof(RoiDev) / 2) return fail(P264HIP_ENOMEM, "%s: %d descriptors", fn, n);
+    HIPCHK(hipSetDevice(c->device));
+    // the context's buffers: a descriptor per ROI, and the segments of one pair (every ROI has one of plan.seg_words)
+    const int per_pair = plan.rois_per_pair < n ? plan.rois_per_pair : n;
+    if ((rc = grow(c, (void **)&c->d_roi_tab, &c->roi_tab_cap, (size_t)n * sizeof(RoiDev), (size_t)n / 2 * sizeof(RoiDev), false, WAIT_STREAM, "the ROI descriptors"))) return rc;
+    if ((rc = grow(c, (void **)&c->d_roi, &c->roi_cap, (size_t)per_pair * (size_t)plan.seg_words * sizeof(uint32_t), 0, false, WAIT_STREAM, "the ROI taps"))) return rc;
+    if (l->flags & P264HIP_ROIS_AFTER) {                    // the list is what after_stream has queued so far
+        if (!c->roi_after) HIPCHK(hipEventCreateWithFlags(&c->roi_after, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->roi_after, (hipStream_t)l->after_stream));
+        HIPCHK(hipStreamWaitEvent(c->stream, c->roi_after, 0));
+    }
+    const int32_t *d_slots = nullptr;
+    if (l->slot_of_stream) {                                // the one table the call stages: n_streams integers
+        ExportTable t;
+        if ((rc = export_stage(c, c->n_streams, &t))) return rc;
+        memcpy(t.host, l->slot_of_stream, (size_t)c->n_streams * sizeof(int32_t));
+        if ((rc = export_send(c, t, (size_t)c->n_streams * sizeof(int32_t)))) return rc;
+        d_slots = (const int32_t *)t.dev;
+    }
+    const RoiPlanParams pp = { n, e->width, e->height, e->filter, c->g.w, c->g.h, c->n_streams, c->slots, l->max_reduction, plan.seg_words, plan.rois_per_pair, AA_T_CAP };
+    hipLaunchKernelGGL(k_roi_plan, dim3((unsigned)((n + ROI_PLAN_THREADS - 1) / ROI_PLAN_THREADS)), dim3(ROI_PLAN_THREADS), 0, c->stream, l->rois_dev, l->count_dev, d_slots, pp, c->d_roi_tab, l->status_dev);
+    const int W = e->width, H = e->height;
+    ResizeParams p = resize_params(*e, pitch, stride);      // (t_xl .. t_yc stay 0: the tables are the segments')
+    const unsigned gx = resize_tiles(p, e->format);
+    RoiAaParams pa = {};
+    pa.r = p;
+    pa.tile_rows = (H + AA_TH - 1) / AA_TH;
+    for (int s = 1; s <= 4; s++) pa.inv_ntx[s - 1] = 0xffffffffu / (uint32_t)((W + (4 << s) - 1) / (4 << s));
+    const int instance = instance_of(e->format, e->dtype);
+    const auto taps = aa ? k_roi_aa_taps : k_roi_taps;
+    const void *body = aa ? (const void *)roi_aa_kernels[instance] : (const void *)roi_kernels[instance];
+    const unsigned block = aa ? AA_THREADS : RESIZE_THREADS;
+    const uint8_t *frames = c->frames; const RoiDev *d_rois = c->d_roi_tab; const uint32_t *scratch = c->d_roi; uint8_t *out = (uint8_t *)dst;
+    // every rectangle is inside the output: no segment has more entries than the whole output's
+    const unsigned tx = (unsigned)((roi_seg_words(W, H) + ROI_TAPS_THREADS - 1) / ROI_TAPS_THREADS);
+    for (int first = 0; first < n; first += plan.rois_per_pair) {        // (one stream: a pair's taps are read before the next pair's are written)
+        const int count = n - first < plan.rois_per_pair ? n - first : plan.rois_per_pair;
+        for_grid_rows(first, count, [&](int base, unsigned rows) { hipLaunchKernelGGL(taps, dim3(tx, rows), dim3(ROI_TAPS_THREADS), 0, c->stream, d_rois, base, c->d_roi); });
+        for_grid_rows(first, count, [&](int base, unsigned rows) {
+            void *args[] = { &frames, &c->frame_bytes, &c->g, &d_rois, &scratch, &base, &out, aa ? (void *)&pa : (void *)&p, &fill };
+            (void)hipLaunchKernel(body, dim3(aa ? (unsigned)plan.aa_tiles : gx, rows), dim3(block), args, (size_t)plan.aa_lds_bytes, c->stream);
+        });
+    }
+    HIPCHK(hipGetLastError());
+    if (l->flags & P264HIP_ROIS_BEFORE) {
+        if (!c->roi_before) HIPCHK(hipEventCreateWithFlags(&c->roi_before, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->roi_before, c->stream));
+        HIPCHK(hipStreamWaitEvent((hipStream_t)l->before_stream, c->roi_before, 0));
+    }
+    return P264HIP_OK;
 }
 
 extern "C" int p264hip_copy_to_device(void *dev, const void *host, size_t bytes)

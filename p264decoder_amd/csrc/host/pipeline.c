@@ -380,6 +380,8 @@ p264hip_ctx *p264pipe_last_slot_(const p264pipe *p, int stream, int *slot)
     return p->ctx;
 }
 
+int p264pipe_streams_(const p264pipe *p) { return p->n_streams; }
+
 int p264pipe_export_last_with_(p264pipe *p, const char *who, p264pipe_export_fn ex, const void *desc, void *dst_dev, size_t bytes)
 {
     if (!p || !p->ctx || !desc || !dst_dev) return -1;

@@ -40,6 +40,31 @@ int p264pipe_export_last_rois(p264pipe *p, const p264hip_roi_t *rois, int n, con
     return rc;
 }
 
+/* the same from an ROI list in device memory (p264hip_export_rois_device): the slot table is every stream's last decoded picture */
+int p264pipe_export_last_rois_device(p264pipe *p, const p264hip_rois_dev_t *l, const p264hip_resize_t *r, uint32_t fill, void *dst_dev, size_t bytes)
+{
+    int slot;
+    if (!p || !l || !r || !dst_dev) return -1;
+    p264hip_ctx *ctx = p264pipe_last_slot_(p, 0, &slot);
+    if (!ctx || l->slot_of_stream) {
+        fprintf(stderr, "p264pipe_export_last_rois_device: %s\n", ctx ? "slot_of_stream must be NULL (the pipeline fills it)" : "no stream has a decoded picture yet");
+        return -1;
+    }
+    const int n_streams = p264pipe_streams_(p);
+    int32_t *table = (int32_t *)malloc(sizeof *table * (size_t)n_streams);
+    if (!table) return -1;
+    for (int i = 0; i < n_streams; i++) { (void)p264pipe_last_slot_(p, i, &slot); table[i] = slot < 0 ? -1 : slot; }
+    p264hip_rois_dev_t mine = *l;
+    mine.slot_of_stream = table;
+    int rc = 0;
+    /* (with P264HIP_ROIS_BEFORE the call is queued only: the next round's reconstruct is on the same stream behind it) */
+    if (p264hip_export_rois_device(ctx, &mine, r, fill, dst_dev, bytes) || (!(l->flags & P264HIP_ROIS_BEFORE) && p264hip_sync(ctx))) {
+        fprintf(stderr, "p264pipe_export_last_rois_device: %s\n", p264hip_last_error()); rc = -1;
+    }
+    free(table);
+    return rc;
+}
+
 int p264pipe_set_sink_resized(p264pipe *p, const p264hip_resize_t *r, void *const *bufs, int n_bufs, size_t buf_bytes, p264pipe_sink_fn fn, void *user)
 {
     if (!p) return -1;

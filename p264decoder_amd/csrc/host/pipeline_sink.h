@@ -15,6 +15,8 @@ void p264pipe_geometry_(const p264pipe *p, int *device, int *mb_w, int *mb_h);
 /* the device context (NULL before the first round) and the frame-store slot of the stream's last decoded picture (-1: none yet, or no
  * such stream) */
 p264hip_ctx *p264pipe_last_slot_(const p264pipe *p, int stream, int *slot);
+/* the streams of the pipeline: the n_streams of its device context */
+int p264pipe_streams_(const p264pipe *p);
 /* the pipeline's ONE sink becomes this one: pictures of `bytes` bytes, frame_stride (0: bytes) apart, exported by ex with a copy of
  * desc into bufs[round % n_bufs] - with output order on, a delivery's pictures into bufs[delivery % n_bufs], as many as fit buf_bytes.
  * -1 (and the sink as it was) if a buffer is null or too small for a picture of every stream.  On a pipeline without a device bufs

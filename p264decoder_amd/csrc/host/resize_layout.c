@@ -6,6 +6,7 @@
 #include "p264hip.h"
 #include "p264hip_pos.h"
 #include "p264hip_aa.h"
+#include "p264hip_roi_rule.h"
 
 static int is_rgb(int format) { return format == P264HIP_FMT_RGB24 || format == P264HIP_FMT_RGBP; }
 
@@ -205,4 +206,60 @@ int p264hip_roi_aa_tile_width(const p264hip_roi_t *roi, const p264hip_resize_t *
     if (luma_strips) *luma_strips = ns_l;
     if (chroma_strips) *chroma_strips = ns_c;
     return 4 << shift;
+}
+
+/* ---- ROI lists that live in device memory (include/p264hip.h: p264hip_export_rois_device; csrc/hip/kernel_roi_dev.h) ---- */
+int p264hip_roi_status(const p264hip_roi_t *roi, const p264hip_resize_t *r, int mb_w, int mb_h, int n_streams, int slots, int max_reduction)
+{
+    if (!roi || !r) return P264HIP_EINVAL;
+    return p264hip_roi_rule(&roi->stream, r->width, r->height, r->filter, (int64_t)mb_w * 16, (int64_t)mb_h * 16, n_streams, slots, max_reduction);     /* (p264hip_roi_rule.h: the device runs the same text) */
+}
+
+/* why a description and a reduction give no plan (NULL: they do) */
+static const char *plan_why(const p264hip_resize_t *r, int max_reduction)
+{
+    if (!r) return "null description";
+    if (r->filter != P264HIP_FILTER_BILINEAR && r->filter != P264HIP_FILTER_BILINEAR_AA) return "unknown filter";
+    if (rois_frame_bytes(r, r->filter) < 0) return "p264hip_rois_frame_bytes / p264hip_rois_aa_frame_bytes refuses the description";
+    if (r->filter == P264HIP_FILTER_BILINEAR ? max_reduction != 0 : (max_reduction < 0 || max_reduction > 32)) return "max_reduction must be 0 with the bilinear filter and 0 .. 32 with the antialiased one";
+    return 0;
+}
+
+int p264hip_rois_device_plan(const p264hip_resize_t *r, int max_reduction, p264hip_rois_plan_t *out)
+{
+    if (!out || plan_why(r, max_reduction)) return P264HIP_EINVAL;
+    const int m = max_reduction ? max_reduction : 32;
+    out->aa_tiles = out->aa_lds_bytes = 0;
+    if (r->filter == P264HIP_FILTER_BILINEAR) out->seg_words = p264hip_roi_aa_entries(r->width, r->height);      /* (a word per entry: kernel_roi.h) */
+    else {
+        out->seg_words = p264hip_roi_rule_axis_bound(r->width, m) + p264hip_roi_rule_axis_bound(r->height, m);
+        out->aa_tiles = p264hip_roi_rule_tiles(r->width, r->height, m, P264HIP_ROI_AA_TILE_VALUES, &out->aa_lds_bytes);
+    }
+    out->rois_per_pair = (int32_t)(P264HIP_ROI_SCRATCH_BYTES / 4 / out->seg_words);
+    return out->rois_per_pair >= 1 ? P264HIP_OK : P264HIP_EINVAL;
+}
+
+const char *p264hip_rois_device_why_(const p264hip_rois_dev_t *l, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots)
+{
+    if (!l) return "null list";
+    const char *why = plan_why(r, l->max_reduction);
+    if (why) return why;
+    const p264hip_resize_t q = without_window(r);
+    if ((why = p264hip_resize_why_(&q, mb_w, mb_h))) return why;
+    if (!l->rois_dev) return "null ROI list";
+    if ((uintptr_t)l->rois_dev & 7) return "ROI list at an address that is no multiple of 8";
+    if (l->n < 1) return "no ROI";
+    if (n_streams < 1 || slots < 1) return "no frame store";
+    if (fill >> 24) return "fill with a bit above 23 set";
+    if ((int64_t)mb_w * 16 > 65535 || (int64_t)mb_h * 16 > 65535) return "a frame above 65535 samples a side (a tap holds a coordinate in 16 bits)";
+    if (l->flags & ~(P264HIP_ROIS_AFTER | P264HIP_ROIS_BEFORE)) return "unknown flag bits";
+    if (l->slot_of_stream)
+        for (int i = 0; i < n_streams; i++)
+            if (l->slot_of_stream[i] < -1 || l->slot_of_stream[i] >= slots) return "slot table with an entry outside -1 .. slots - 1";
+    return 0;
+}
+
+int p264hip_rois_device_check(const p264hip_rois_dev_t *l, const p264hip_resize_t *r, uint32_t fill, int mb_w, int mb_h, int n_streams, int slots)
+{
+    return p264hip_rois_device_why_(l, r, fill, mb_w, mb_h, n_streams, slots) ? P264HIP_EINVAL : P264HIP_OK;
 }

@@ -167,6 +167,21 @@ class Pipeline:
             raise RuntimeError("p264pipe_export_last_rois failed: %s" % self.lib.p264hip_last_error().decode())
         return out
 
+    def export_last_rois_device(self, rois, size, fmt="rgbp", dtype="u8", fill=(16, 128, 128), scale=None, bias=None, matrix="bt601", full_range=False,
+                                pitch=0, frame_stride=0, out=None, *, count=None, status=False, filter="bilinear", max_reduction=0, stream="current"):
+        """export_last_rois from an ROI list IN DEVICE MEMORY (p264pipe_export_last_rois_device): HipReconstructor.export_rois_device
+        with (n, 9) rows (stream, left, top, width, height, dst_left, dst_top, dst_width, dst_height), the picture being the
+        stream's last decoded one; a (pointer, n) pair names full p264hip_roi_t rows whose slot is -1.  A stream without a picture
+        yet gives the status ROI_NO_PICTURE.  With an ordering stream the call is queued only (the tensors stay referenced until
+        close() or the next call without one); without, it is complete on return.  Callable from inside a sink's callback."""
+        from .recon import rois_device_call
+        l, r, word, out, ptr, cap, keep, status = rois_device_call(self.lib, RuntimeError, rois, size, fmt, dtype, fill, scale, bias, matrix, full_range, pitch,
+                                                                   frame_stride, out, count, status, filter, max_reduction, stream, head=1)
+        self._rois_in_flight = (getattr(self, "_rois_in_flight", []) if l.flags else []) + [keep]
+        if self.lib.p264pipe_export_last_rois_device(self.h, C.byref(l), C.byref(r), word, ptr, cap):
+            raise RuntimeError("p264pipe_export_last_rois_device failed: %s" % self.lib.p264hip_last_error().decode())
+        return out if status is None else (out, status)
+
     def set_sink_resized(self, size, callback, fmt="rgbp", dtype="u8", depth=2, crop=None, scale=None, bias=None, matrix="bt601", full_range=False,
                          pitch=0, buffers=None, *, filter="bilinear"):
         """set_sink with a resize on it (p264pipe_set_sink_resized): callback(round, streams, dev, bytes) for every round of run(),

@@ -322,6 +322,28 @@ class HipReconstructor:
             self.sync()
         return out
 
+    def export_rois_device(self, rois, size, fmt="rgbp", dtype="u8", fill=(16, 128, 128), scale=None, bias=None, matrix="bt601", full_range=False,
+                           pitch=0, frame_stride=0, out=None, *, count=None, status=False, filter="bilinear", max_reduction=0, stream="current",
+                           sync=None):
+        """export_rois / export_rois_aa (filter="bilinear_aa") from an ROI list IN DEVICE MEMORY - a detector's boxes, see
+        rois.rois_from_boxes - (p264hip_export_rois_device; include/p264hip.h has the contract): the host sees no ROI, an invalid one
+        refuses nothing and its picture is NOT WRITTEN.  rois: an (n, 10) contiguous int32 tensor on the device (the rows of
+        p264hip_roi_t), or a (device pointer, n) pair.  count: None (all n), a one-element int32 device tensor or a pointer: the
+        ROIs from it on are unused.  status: True allocates an (n,) int32 tensor and returns (out, status); a tensor or pointer
+        is written and returned as given; False: no status.  max_reduction (antialiased filter): the largest reduction an ROI
+        may have, 0 meaning 32 - the scratch a call reserves per ROI grows with it (_native.rois_device_plan).
+        stream: "current" - the default where a tensor is involved - orders the call behind what torch's current stream has queued
+        and torch's current stream behind the call: it behaves like a torch operation and never synchronises the host; None: no
+        ordering; an integer: a raw stream handle to order with.  sync=None waits (sync()) only where there is no ordering.  The
+        tensors stay referenced until the next sync().  The other arguments and `out` as export_rois has them."""
+        l, r, word, out, ptr, cap, keep, status = rois_device_call(self.lib, P264Error, rois, size, fmt, dtype, fill, scale, bias, matrix, full_range, pitch,
+                                                                   frame_stride, out, count, status, filter, max_reduction, stream)
+        self._in_flight.append(keep)
+        self._chk(self.lib.p264hip_export_rois_device(self.h, C.byref(l), C.byref(r), word, ptr, cap), "p264hip_export_rois_device")
+        if sync if sync is not None else not l.flags:
+            self.sync()
+        return out if status is None else (out, status)
+
     def clone_picture(self, dst, src):
         self._chk(self.lib.p264hip_clone_picture(self.h, dst, src), "p264hip_clone_picture")
 
@@ -398,6 +420,55 @@ class HipReconstructor:
         li = N.LaunchInfo()
         self._chk(self.lib.p264hip_last_launch(self.h, C.byref(li)), "p264hip_last_launch")
         return int(li.cr_pictures)
+
+
+def rois_device_call(lib, error, rois, size, fmt, dtype, fill, scale, bias, matrix, full_range, pitch, frame_stride, out, count, status, filter,
+                     max_reduction, stream, head=2):
+    """What HipReconstructor.export_rois_device and Pipeline.export_last_rois_device share: the arguments as (p264hip_rois_dev_t,
+    p264hip_resize_t, fill word, out, its pointer, its bytes, the tensors to keep alive, the status tensor / pointer or None).
+    head: the leading members of a row (2: stream, slot; 1: stream alone).  torch is imported only where a tensor is involved."""
+    r = N.resize_desc(fmt, size, (0, 0, 2, 2), None, dtype, scale, bias, matrix, full_range, pitch, frame_stride, filter)
+    keep = []
+
+    def pointer(v, what, numel=None):
+        if v is None or isinstance(v, int):
+            return v
+        torch = N.import_torch()
+        if not (v.is_cuda and v.is_contiguous() and v.dtype == torch.int32 and (numel is None or v.numel() == numel)):
+            raise error("export_rois_device: %s must be a contiguous int32 tensor on the device%s" % (what, "" if numel is None else " of %d elements" % numel))
+        keep.append(v)
+        return v.data_ptr()
+    if isinstance(rois, tuple):
+        rois_ptr, n = int(rois[0]), int(rois[1])
+    else:
+        if rois.dim() != 2 or rois.shape[1] != head + 8:
+            raise error("export_rois_device: rois must be an (n, %d) tensor or a (pointer, n) pair" % (head + 8))
+        if head == 1:                                        # (stream, window, rectangle) -> the rows of p264hip_roi_t with slot -1
+            torch = N.import_torch()
+            rois = torch.cat([rois[:, :1], torch.full_like(rois[:, :1], -1), rois[:, 1:]], dim=1).contiguous()
+        n = int(rois.shape[0])
+        rois_ptr = pointer(rois, "rois")
+    count_ptr = pointer(count, "count", 1)
+    if status is True:
+        torch = N.import_torch()
+        status = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+    elif status is False:
+        status = None
+    status_ptr = pointer(status, "status", None if isinstance(status, int) else n)
+    if stream == "current":                                  # (the default where a tensor is involved; pointers alone: no ordering)
+        stream = N.import_torch().cuda.current_stream().cuda_stream if keep or not isinstance(out, tuple) else None
+    aa = r.filter == N.FILTER_BILINEAR_AA
+    per = (lib.p264hip_rois_aa_frame_bytes if aa else lib.p264hip_rois_frame_bytes)(C.byref(r)) if out is None else 0
+    if per < 0:
+        raise error("export_rois_device: %s refuses the description" % ("p264hip_rois_aa_frame_bytes" if aa else "p264hip_rois_frame_bytes"))
+    out, ptr, cap = N.export_out(max(n, 1), r, per, pitch, frame_stride, out, (error, "export_rois_device"), wait=stream is None)
+    if not isinstance(out, tuple):
+        keep.append(out)
+    l = N.RoisDev(rois_ptr, count_ptr, status_ptr, None, None, None, n, int(max_reduction), 0)
+    if stream is not None:
+        l.after_stream = l.before_stream = int(stream) or None
+        l.flags = N.ROIS_AFTER | N.ROIS_BEFORE
+    return l, r, N.fill_word(fill), out, ptr, cap, keep, status
 
 
 def device_count(lib=None):

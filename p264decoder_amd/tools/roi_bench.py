@@ -17,8 +17,14 @@ call with filter 0 from this build (what the antialiasing costs) and, for the wh
 export_resized(filter="bilinear_aa") at the same shape - the kernel the ROI kernels share their passes with, so the ratio is what the
 per-ROI tables, the clipping and the device-made taps cost.  No figure is required of these; DESIGN.md K6c quotes them.
 
+--device-out measures the ROI LIST IN DEVICE MEMORY (p264hip_export_rois_device, kernel_roi_dev.h) on case b's 4096 windows: filter 0
+host list against device list, filter 2 host list against device list with max_reduction 0 and 3 (the windows reduce by 2.3:1 at
+most), and - what a caller whose boxes are a device tensor had to do before - .cpu(), a Python loop over the rows and the host-list
+call.  Per road: the rate with a sync behind every call, the launch pairs, the scratch bytes of a pair, and the wall time until the
+call RETURNS with nothing waited for (the host cost).  No figure is required of these; DESIGN.md K6d quotes them.
+
   python -m p264decoder_amd.tools.roi_bench [--frames 2048] [--reps 20] [--warmup 3] [--out profiles/roi_bench.json]
-                                            [--aa-out profiles/roi_aa_bench.json [--only-aa]]
+                                            [--aa-out profiles/roi_aa_bench.json [--only-aa]] [--device-out profiles/roi_device_bench.json [--only-device]]
 """
 import argparse
 import json
@@ -131,6 +137,80 @@ def aa_cases(args, hip, streams, slots, scale, bias):
     return res
 
 
+def device_cases(args, hip, scale, bias):
+    """case b's windows from a list in device memory, beside the host list and beside tensor -> host -> host list"""
+    import time
+    import statistics
+    import numpy as np
+    import torch
+    from p264decoder_amd import _native as N
+    n = args.frames
+    g = np.random.default_rng(2663)                         # (the windows of case b)
+    m = 2 * n
+    ww, wh = 2 * g.integers(32, 257, m), 2 * g.integers(32, 257, m)
+    left, top = 2 * (g.integers(0, 1 << 30, m) % ((W - ww) // 2 + 1)), 2 * (g.integers(0, 1 << 30, m) % ((H - wh) // 2 + 1))
+    rois = np.stack([np.arange(m) // 2, np.arange(m) & 1, left, top, ww, wh] + [np.zeros(m, np.int64)] * 4, axis=1).astype(np.int32)
+    dev = torch.tensor(rois, dtype=torch.int32, device="cuda")
+    status = torch.empty(m, dtype=torch.int32, device="cuda")
+    out = torch.empty((m, 3, 224, 224), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    mem = (out.data_ptr(), out.numel() * out.element_size())
+    lst = (dev.data_ptr(), m)
+    size = (224, 224)
+
+    def host(call, sync=True):
+        return lambda: call(rois, size, "rgbp", "f32", (16, 128, 128), scale, bias, out=mem, sync=sync)
+
+    def device(filter, reduction, sync=True):
+        return lambda: hip.export_rois_device(lst, size, "rgbp", "f32", (16, 128, 128), scale, bias, out=mem, status=status.data_ptr(), filter=filter, max_reduction=reduction,
+                                              stream=None, sync=sync)
+
+    def from_tensor(call):
+        def road():
+            rows = dev.cpu().tolist()
+            call([tuple(r) for r in rows], size, "rgbp", "f32", (16, 128, 128), scale, bias, out=mem)
+        return road
+    roads = {"filter_0_host_list": (host(hip.export_rois), host(hip.export_rois, False), 0, None),
+             "filter_0_device_list": (device("bilinear", 0), device("bilinear", 0, False), 0, 0),
+             "filter_0_tensor_to_host_then_host_list": (from_tensor(hip.export_rois), None, 0, None),
+             "filter_2_host_list": (host(hip.export_rois_aa), host(hip.export_rois_aa, False), 2, None),
+             "filter_2_device_list_max_reduction_0": (device("bilinear_aa", 0), device("bilinear_aa", 0, False), 2, 0),
+             "filter_2_device_list_max_reduction_3": (device("bilinear_aa", 3), device("bilinear_aa", 3, False), 2, 3),
+             "filter_2_tensor_to_host_then_host_list": (from_tensor(hip.export_rois_aa), None, 2, None)}
+    t = alternating({k: v[0] for k, v in roads.items()}, args.warmup, args.reps)
+    assert status.cpu().eq(0).all()
+    # the wall time until the call returns, nothing waited for (a sync, not timed, behind each)
+    back = {k: [] for k, v in roads.items() if v[1]}
+    for _ in range(args.reps):
+        for k in back:
+            t0 = time.perf_counter()
+            roads[k][1]()
+            back[k].append((time.perf_counter() - t0) * 1e3)
+            hip.sync()
+    read = int((rois[:, 4].astype(np.int64) * rois[:, 5] * 3 // 2).sum())
+    res = {"metric": "export of %d drawn windows (64 .. 512 a side) of %d 1080p frames to 224 x 224 planar RGB float32, the ROI list in device memory" % (m, n), "unit": "pictures/s",
+           "frames": n, "windows": m, "reps": args.reps, "warmup": args.warmup, "roads": {}}
+    for k, (_, _, filter, reduction) in roads.items():
+        e = entry(m, t[k], read + m * 3 * 224 * 224 * 4)
+        if k in back:
+            e["ms_until_the_call_returns"] = {"median": round(statistics.median(back[k]), 3), "min": round(min(back[k]), 3), "max": round(max(back[k]), 3)}
+        if reduction is not None:
+            plan = N.rois_device_plan(N.resize_desc("rgbp", size, (0, 0, 2, 2), None, filter=filter), reduction, hip.lib)
+            e.update(launch_pairs=-(-m // plan["rois_per_pair"]), scratch_bytes_of_a_pair=4 * plan["seg_words"] * min(m, plan["rois_per_pair"]), plan=plan)
+        elif filter == 2:
+            pairs, words = launch_pairs(hip.lib, rois[:, :6], size)
+            e.update(launch_pairs=pairs, scratch_bytes_of_all_segments=4 * words)
+        else:
+            e.update(launch_pairs=1, scratch_bytes_of_all_segments=4 * 672 * m)
+        res["roads"][k] = e
+    r = res["roads"]
+    res["device_over_host_list_rate"] = {"filter_0": round(r["filter_0_device_list"]["frames_per_s"] / r["filter_0_host_list"]["frames_per_s"], 3),
+                                         "filter_2_max_reduction_0": round(r["filter_2_device_list_max_reduction_0"]["frames_per_s"] / r["filter_2_host_list"]["frames_per_s"], 3),
+                                         "filter_2_max_reduction_3": round(r["filter_2_device_list_max_reduction_3"]["frames_per_s"] / r["filter_2_host_list"]["frames_per_s"], 3)}
+    res["value"] = r["filter_2_device_list_max_reduction_3"]["frames_per_s"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=2048, help="frames of the store = streams of the context (2 slots each)")
@@ -140,6 +220,8 @@ def main():
     ap.add_argument("--only", default="abc", help="the cases to run")
     ap.add_argument("--aa-out", default=None, help="measure the antialiased filter too and write its table there")
     ap.add_argument("--only-aa", action="store_true", help="with --aa-out: skip the filter-0 cases against the roads that existed before")
+    ap.add_argument("--device-out", default=None, help="measure the ROI list in device memory too and write its table there")
+    ap.add_argument("--only-device", action="store_true", help="with --device-out: skip every other case")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -157,6 +239,14 @@ def main():
     def mem(t):
         return (t.data_ptr(), t.numel() * t.element_size())
 
+    if args.device_out:
+        dv = device_cases(args, hip, scale, bias)
+        with open(args.device_out, "w") as f:
+            f.write(json.dumps(dv) + "\n")
+        if args.only_device:
+            hip.close()
+            print(json.dumps(dv))
+            return
     if args.aa_out:
         aa = aa_cases(args, hip, streams, slots, scale, bias)
         with open(args.aa_out, "w") as f:
